@@ -21,6 +21,10 @@ Rank 0 prints ONE JSON line.  Besides the driver's fields it carries
                   cores on a bounded sample of the same workload (2 warm-ups, median of 3; host_cores / threads / cpu_model stated)
   cpu_baseline_c1 -- BASELINE config 1 in full on the host: RangeDM, 10-step DDIM, batch 1 (the GPU leg is in other_configs)
   fell_back    -- whether any persistent launch failed its self-check during the run (plans rebuilt as one launch per layer)
+
+`--dump-outputs DIR` writes what the last timed step handed its caller -- the finished range images, all ranks gathered -- as
+DIR/images.npy (float32, rank 0).  Inputs and weights are functions of --seed alone, so two builds run with the same arguments
+can be compared output for output.  Above DUMP_LIMIT_BYTES a fixed, seeded sample of whole images is written instead.
 """
 import argparse
 import ctypes as C
@@ -38,6 +42,20 @@ import torch  # noqa: E402
 
 PEAK_BF16_TFLOPS = 2500.0      # dense MFMA bf16, MI355X_MICROARCH.md (measured 2495)
 PEAK_HBM_GBS = 8000.0
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(outdir, arrays, seed=0):
+    """--dump-outputs: each of `arrays` (name -> tensor) as <outdir>/<name>.npy in float32.  An array larger than its share of
+    DUMP_LIMIT_BYTES is cut to a sample of whole rows along dim 0 (images), drawn by a fixed seed: the same rows every run."""
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share:
+            rows = np.random.default_rng(seed).choice(a.shape[0], share // (a.nbytes // a.shape[0]), replace=False)
+            a = a[np.sort(rows)]
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def build_models(preset, seed):
@@ -451,7 +469,13 @@ def main():
     ap.add_argument("--train", action="store_true",
                     help="BASELINE config 5 instead of the headline: the data-parallel training step (tools/bench_train.py, same "
                          "--gpus / --steps / --warmup contract, metric training samples/sec)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's images (all ranks gathered) to DIR/images.npy, float32, at most 64 MB")
     args, rest = ap.parse_known_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.train and args.dump_outputs:
+        ap.error("--dump-outputs covers the sampling path, not --train")
     if args.train:
         sys.argv = [os.path.join(ROOT, "tools", "bench_train.py"), "--gpus", str(args.gpus), "--steps", str(args.steps),
                     "--warmup", str(args.warmup)] + rest
@@ -545,8 +569,8 @@ def main():
     dt = D.max_over_ranks(dt, dev)
     pipe._fused.status_all()                             # raises if any call of the loop tripped the persistent launches' self-check
     assert torch.isfinite(out).all()
-    if rank == 0 and os.environ.get("RLDM_BENCH_DUMP"):  # (tests: the gathered images of the last step, for the N-rank == 1-rank check)
-        torch.save(out.detach().cpu(), os.environ["RLDM_BENCH_DUMP"])
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"images": out})
     # the exchange step on its own (it is inside the timed region too): one all-gather of a finished batch, HIP events on the
     # stream it is issued on; and the proof that `world` ranks met -- every rank's id through the same collective path
     comm = D.comm_info(dev)

@@ -1,5 +1,5 @@
 import os, sys, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from rangeldm_amd import train_ops as T
 for shape in [(8, 256, 16, 128), (8, 256, 16, 256), (8, 128, 8, 256)]:
     x = torch.randn(*shape, device="cuda"); dy = torch.randn(*shape, device="cuda")

@@ -1,6 +1,7 @@
 import os, sys, torch
-sys.path.insert(0, '/root/repo')
-os.chdir('/root/repo')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+os.chdir(ROOT)
 from rangeldm_amd import training as TR, distributed as D, train_ops as T
 from rangeldm_amd.config import UNetConfig
 from rangeldm_amd.params import unet_param_shapes
