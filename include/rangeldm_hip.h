@@ -340,7 +340,9 @@ int rldm_train_flush_reduce(void);
  * calls that the all-taps kernel covers are QUEUED (their dy / x / statistics operands must stay alive and unmodified), and
  * rldm_train_wgrad_group_flush -- or group(0), or a queued call on another stream -- runs the queue as a handful of launches that each
  * compute up to 22 layers (block id -> layer, tile, K slice; the K slices of a tile are summed in slice order by the tile's last
- * arriver: no reduction launches, bit-reproducible gradients).  dw / rows / total are final only after the flush.  One caller thread. */
+ * arriver: no reduction launches, bit-reproducible gradients).  A dw may be queued again: the call flushes the queue first, so its
+ * gradients add in call order.  dw / rows / total are final only after the flush, which empties the queue even when it fails.  One
+ * caller thread. */
 int rldm_train_wgrad_group(int on);
 int rldm_train_wgrad_group_flush(void);
 int rldm_train_wgrad_group_pending(void);   /* queued layers (tests) */

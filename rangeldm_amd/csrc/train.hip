@@ -14,8 +14,8 @@
 //                         workgroups and waves, fp32 atomics into the zeroed gradient.
 //   tr_colsum_kernel      bias / time-embedding-row gradients: per-image column sums of dy.
 //   tr_gn_*               GroupNorm(32) statistics, forward (+ SiLU), backward (reduce + apply, d gamma / d beta).
-//   tr_attn_*             head_dim 8 softmax attention, forward (+ log-sum-exp) and backward (dq ; dk, dv): one thread per
-//                         query / key against the head's K, V (or Q, dO) staged in LDS; no atomics, deterministic.
+//   attention             head_dim 8 softmax attention, forward (+ log-sum-exp) and backward: the matrix-core kernels of
+//                         train_attn.hip behind this file's C entry points.
 //   elementwise           add, channel copy (concat / split), 2x2 sum (nearest-x2 backward), SiLU, sinusoidal timestep
 //                         embedding, input packing, MSE loss + gradient, sum of squares, AdamW (+ clip scale + EMA),
 //                         weight repacking.
@@ -38,17 +38,6 @@ int tr_attention_backward_mfma(const float* q, const float* k, const float* v, i
 }  // namespace rldm
 
 namespace {
-
-inline bool gn_vec_reduce_env() {
-    static const bool v = getenv("RLDM_TR_GN_VEC_REDUCE") != nullptr;
-    return v;
-}
-
-// RLDM_TR_ATTN=scalar: the fp32 one-thread-per-query kernels of this file (A/B runs)
-inline bool attention_scalar() {
-    static const bool v = getenv("RLDM_TR_ATTN") && std::string(getenv("RLDM_TR_ATTN")) == "scalar";
-    return v;
-}
 
 // dw[n][c][t] += sum over slices of part[t][slice][n][c], four channels per thread (Cin % 4 == 0), `nb` workgroups of `nt` threads
 // striding over the (tap, channel quad) items: the body of tr_wgrad_reduce_vec_kernel, also run as a rider of the next conv launch.
@@ -128,17 +117,7 @@ struct TrFuse {
 };
 
 // (v_exp_f32 + v_rcp_f32: the IEEE division of 1.f / x costs ten more instructions per element of every staged tile)
-#ifndef RLDM_TR_LAST_ACQUIRE
-#define RLDM_TR_LAST_ACQUIRE 1  /* the last arriver of a fused split-K tile acquires (agent scope) before it re-reads the tile */
-#endif
-#ifndef RLDM_TR_ABL
-#define RLDM_TR_ABL 0          /* timing experiments (wrong results): 1 no statistics atomics, 2 no sigmoid in the staging transforms, 4 no split-K output atomics, 8 plain stores instead of them; weight gradient: 16 no LDS stash, 32 no MFMA loop, 64 no global fetch of the next chunk */
-#endif
-#if RLDM_TR_ABL & 2
-__device__ inline float tr_sigmoid(float z) { return z; }
-#else
 __device__ inline float tr_sigmoid(float z) { return __builtin_amdgcn_rcpf(1.f + __expf(-z)); }
-#endif
 
 // y = x * a + b = GroupNorm(x) for the channels [c_lo, c_hi) of image `img` of a (possibly two-source) tensor with npix pixels per
 // image: sc[c] = (a, b).  Every thread sums its own channel's group from global memory (<= 24 pairs, L2 hits): no barrier inside, the
@@ -183,17 +162,18 @@ __device__ inline void tr_gn_coeffs_tile(float4* ce, int BN, int n0, const float
     }
 }
 
-// Epilogue of a fused conv over the finished fp32 tile in LDS (tile[pl * (BN + 1) + cl], PT pixels of ONE image x BN channels):
+// Epilogue of a fused conv over the finished fp32 tile in LDS (tile[pl * (BN + 1) + cl], 64 pixels of ONE image x BN channels), run by
+// the workgroup's 256 threads:
 // thread (channel cl = tid % BN, pixel group tid / BN) walks its pixels: + bias / row / residual (add_terms), the GroupNorm-backward
 // transform where asked, the store (coalesced along the channels), and the per-channel sums, which reach cs_out / gs_out as one atomic
 // per (workgroup, channel, component).  colacc: [2 * BN] floats of LDS.
-template <int BN, int PT, int NT>
+template <int BN>
 __device__ inline void tr_tile_epilogue(const float* tile, float* colacc, const float4* ce, const TrConv& p, const TrFuse& f, int px0,
                                         int n0, int img, bool add_terms, bool store_y) {
     // thread (channel quad cq = tid % (BN / 4), pixel group tid / (BN / 4)): 16-byte global accesses, all of a thread's loads in flight
     // at once (the 4-byte form of this pass -- a channel per thread, 32 pixels in two batches -- was ~5 us of every fused launch)
-    constexpr int NQ = BN / 4, NPG = NT / NQ, IT = PT / NPG;        // BN = 128, 256 threads: 32 quads x 8 groups, 8 pixels per thread
-    static_assert(PT % NPG == 0 && IT <= 16, "tile epilogue shape");
+    constexpr int PT = 64, NT = 256;
+    constexpr int NQ = BN / 4, NPG = NT / NQ, IT = PT / NPG;        // BN = 128: 32 quads x 8 groups, 8 pixels per thread
     const int tid = threadIdx.x, cq = tid % NQ, pg = tid / NQ, cl = 4 * cq, ch = n0 + cl, N = p.N;
     for (int e = tid; e < 2 * BN; e += NT) colacc[e] = 0.f;
     __syncthreads();
@@ -258,9 +238,7 @@ __device__ inline void tr_tile_epilogue(const float* tile, float* colacc, const 
     float* out = f.gs_out ? f.gs_out : f.cs_out;
     for (int e = tid; e < 2 * BN; e += NT) {
         const int c2 = n0 + (e >> 1);
-#if !(RLDM_TR_ABL & 1)
         if (c2 < N) unsafeAtomicAdd(out + ((size_t)img * N + c2) * 2 + (e & 1), colacc[e]);
-#endif
     }
 }
 
@@ -535,13 +513,7 @@ __global__ __launch_bounds__(256) void tr_conv_lds_kernel(const TrConv p, const 
                 if (p.rowadd) u += p.rowadd[(size_t)(gp / HW) * p.rowadd_ld + ch];
                 if (p.res) u += p.res[(size_t)gp * p.N + ch];
             }
-#if RLDM_TR_ABL & 4
-            if (u == 12345.678f) p.y[(size_t)gp * p.N + ch] = u;      // (timing experiment: no split-K atomics)
-#elif RLDM_TR_ABL & 8
-            p.y[(size_t)gp * p.N + ch] = u;                          // (timing experiment: plain stores instead of atomics)
-#else
             unsafeAtomicAdd(p.y + (size_t)gp * p.N + ch, u);
-#endif
         }
         if constexpr (FU) {
             if (f.cs_out || f.gs_out) {
@@ -561,12 +533,10 @@ __global__ __launch_bounds__(256) void tr_conv_lds_kernel(const TrConv p, const 
                 }
                 __syncthreads();
                 if (!sLast) return;
-#if RLDM_TR_LAST_ACQUIRE
                 // (round 6) the argument above rests on what an atomic does to a line of the issuing XCD's L2, which nothing documents:
                 // the ONE workgroup per tile that re-reads the sums pairs the release on the ticket with an agent-scope acquire (an
-                // invalidate of what its caches may hold of the tile) before it does.  -DRLDM_TR_LAST_ACQUIRE=0: the round-5 form.
+                // invalidate of what its caches may hold of the tile) before it does.
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
                 if (f.gs_out) tr_gn_coeffs_tile(sCe, BN, n0, f.gcs0, f.gcs1, f.G0, N, img, f.ggroups, f.geps, Wout * Hout, f.ggamma, f.gbeta);
                 if ((N & 3) == 0) {
                     for (int e = tid; e < 64 * (BN / 4); e += 256) {
@@ -584,7 +554,7 @@ __global__ __launch_bounds__(256) void tr_conv_lds_kernel(const TrConv p, const 
                     }
                 }
                 __syncthreads();
-                tr_tile_epilogue<BN, 64, 256>(tile, sCol, sCe, p, f, px0, n0, img, false, false);
+                tr_tile_epilogue<BN>(tile, sCol, sCe, p, f, px0, n0, img, false, false);
             }
         }
         return;
@@ -599,7 +569,7 @@ __global__ __launch_bounds__(256) void tr_conv_lds_kernel(const TrConv p, const 
 #pragma unroll
                 for (int r = 0; r < 16; ++r) trow[32 * h + 8 * (r >> 2) + 4 * kg + (r & 3)] = h ? acc1[r] : acc0[r];
             __syncthreads();
-            tr_tile_epilogue<BN, 64, 256>(tile, sCol, sCe, p, f, px0, n0, img, true, true);
+            tr_tile_epilogue<BN>(tile, sCol, sCe, p, f, px0, n0, img, true, true);
             return;
         }
     }
@@ -645,16 +615,16 @@ __global__ __launch_bounds__(256) void tr_conv_lds_kernel(const TrConv p, const 
 // (64 / H + 2) azimuth columns x (H + 2) beams, circular in azimuth, zero rows above and below -- and the nine taps read
 // their B fragments from it at a uniform row offset dw * (H + 2) + dh; only the weight tile is staged per tap.  x traffic
 // and fp32->bf16 conversions drop 5x.  Stage order: chunk-major, tap fastest.
-template <int BN, int PT, bool FU = false>
-__global__ __launch_bounds__(PT * 4) void tr_conv_halo_kernel(const TrConv p, const TrFuse f) {
+template <int BN, bool FU = false>
+__global__ __launch_bounds__(256) void tr_conv_halo_kernel(const TrConv p, const TrFuse f) {
     static_assert(BN == 64 || BN == 128, "channel tile");
     constexpr int CK = 64;
-    static_assert(PT == 64 || PT == 128, "pixel tile");
-    constexpr int NT = PT * 4;                      // threads: PT / 32 pixel groups x 2 channel halves of waves
+    constexpr int PT = 64;                          // pixel tile
+    constexpr int NT = 256;                         // threads: PT / 32 pixel groups x 2 channel halves of waves
     constexpr int TPR = NT / BN, NR = BN / 64;
     constexpr int PITCH = CK + 8;
     constexpr int WV = CK / (8 * TPR);
-    constexpr int MAXHP = PT == 64 ? 136 : 264;     // (PT / H + 2) * (H + 2) for H = 2 .. 32
+    constexpr int MAXHP = 136;                      // (PT / H + 2) * (H + 2) for H = 2 .. 32
     // (FU: one buffer, the fp32 output tile [PT][BN + 1] of the fused epilogue afterwards)
     constexpr int STAGE_BYTES = (MAXHP + BN) * PITCH * 2, TILE_BYTES = FU ? PT * (BN + 1) * 4 : 0;
     __shared__ __attribute__((aligned(16))) unsigned char hraw[STAGE_BYTES > TILE_BYTES ? STAGE_BYTES : TILE_BYTES];
@@ -826,7 +796,7 @@ __global__ __launch_bounds__(PT * 4) void tr_conv_halo_kernel(const TrConv p, co
 #pragma unroll
                 for (int r = 0; r < 16; ++r) trow[32 * h + 8 * (r >> 2) + 4 * kg + (r & 3)] = h ? acc1[r] : acc0[r];
             __syncthreads();
-            tr_tile_epilogue<BN, PT, NT>(tile, sCol, sCe, p, f, px0, n0, b, true, true);
+            tr_tile_epilogue<BN>(tile, sCol, sCe, p, f, px0, n0, b, true, true);
             return;
         }
     }
@@ -1124,11 +1094,9 @@ __device__ __forceinline__ void tr_wgrad2_body(const TrWgrad2& p, const TrFuse& 
     for (int chunk = z * p.cpw; chunk < chunk_end; ++chunk) {
         const int b = chunk / nwc, w0 = (chunk - b * nwc) << p.lwc;
         __syncthreads();                                             // the previous chunk's fragments have been read
-#if !(RLDM_TR_ABL & 16)
 #pragma unroll
         for (int it = 0; it < 4; ++it)
             if (2 * (ppl + 16 * it) < KP) stash(ppl + 16 * it, R[it], b);
-#endif
         __syncthreads();
         if (do_sums) {                                               // thread (row n = tid >> 2, quarter of the chunk's pixels)
             const bf16_t* r = sA + (tid >> 2) * pitchA + (tid & 3) * (KP >> 2);
@@ -1147,17 +1115,12 @@ __device__ __forceinline__ void tr_wgrad2_body(const TrWgrad2& p, const TrFuse& 
             sum_img += sacc;
             sum_all += sacc;
         }
-#if !(RLDM_TR_ABL & 64)
         if (chunk + 1 < chunk_end) {                                 // the next chunk's loads fly during this chunk's MFMAs
             const int nb_ = (chunk + 1) / nwc, nw0 = ((chunk + 1) - nb_ * nwc) << p.lwc;
 #pragma unroll
             for (int it = 0; it < 4; ++it)
                 if (2 * (ppl + 16 * it) < KP) fetch(ppl + 16 * it, nb_, nw0, R[it]);
         }
-#endif
-#if RLDM_TR_ABL & 32
-        if (chunk >= 0) continue;
-#endif
         const bf16_t* fa = sA + (32 * wi + l31) * pitchA + 8 * kg;
         const bf16_t* fb = sB + (32 * wj + l31) * pitchB + 8 * kg;
         // fragments of k-step k + 1 are requested before the MFMAs of k-step k (one wave per SIMD: nothing else hides the LDS latency)
@@ -1559,29 +1522,6 @@ __global__ __launch_bounds__(256) void tr_gn_stats_kernel(const float* __restric
     }
 }
 
-// 4 channels per thread for 4 | channels-per-group <= 16: thread (pixel lane t / Q, channel quad t % Q), Q = cpg / 4
-__global__ __launch_bounds__(256) void tr_gn_stats_vec_kernel(const float* __restrict__ x, int npix, int C, int groups, float eps,
-                                                              float2* __restrict__ stats) {
-    __shared__ double sh[4];
-    const int g = blockIdx.x, b = blockIdx.y, cpg = C / groups, Q = cpg >> 2;
-    const int q = threadIdx.x % Q, pl = threadIdx.x / Q, step = 256 / Q;
-    const float* base = x + (size_t)b * npix * C + g * cpg + 4 * q;
-    double s = 0.0, ss = 0.0;
-    for (int p = pl; p < npix; p += step) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(base + (size_t)p * C);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { s += v[e]; ss += (double)v[e] * v[e]; }
-    }
-    s = block_sum_d(s, sh);
-    ss = block_sum_d(ss, sh);
-    if (threadIdx.x == 0) {
-        const double n = (double)npix * cpg, mean = s / n;
-        double var = ss / n - mean * mean;
-        var = var < 0.0 ? 0.0 : var;
-        stats[b * groups + g] = make_float2((float)mean, (float)(1.0 / sqrt(var + (double)eps)));
-    }
-}
-
 __device__ inline float sigmoid_f(float z) { return 1.f / (1.f + __expf(-z)); }
 
 // Statistics AND apply in one launch for the small tensors (levels 1-3): the block of (image, group) re-reads its own slab
@@ -1770,52 +1710,6 @@ __global__ __launch_bounds__(256) void tr_gn_bwd_reduce_kernel(const float* __re
     if (threadIdx.x < cpg) {
         float tg = 0.f, tb = 0.f;
         for (int t = threadIdx.x; t < TT; t += cpg) { tg += shg[t]; tb += shb[t]; }
-        unsafeAtomicAdd(dgamma + g * cpg + threadIdx.x, tg);
-        unsafeAtomicAdd(dbeta + g * cpg + threadIdx.x, tb);
-    }
-    if (threadIdx.x == 0) sums[b * groups + g] = make_float2((float)s1, (float)s2);
-}
-
-__global__ __launch_bounds__(256) void tr_gn_bwd_reduce_vec_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                                   const float2* __restrict__ stats, const float* __restrict__ gamma,
-                                                                   const float* __restrict__ beta, int npix, int C, int groups, int silu,
-                                                                   float2* __restrict__ sums, float* __restrict__ dgamma,
-                                                                   float* __restrict__ dbeta) {
-    __shared__ double sh[4];
-    __shared__ float shg[4][256], shb[4][256];
-    const int g = blockIdx.x, b = blockIdx.y, cpg = C / groups, Q = cpg >> 2;
-    const int q = threadIdx.x % Q, pl = threadIdx.x / Q, step = 256 / Q;
-    const float2 st = stats[b * groups + g];
-    const size_t base = (size_t)b * npix * C + g * cpg + 4 * q;
-    const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + g * cpg + 4 * q), be = *reinterpret_cast<const f32x4*>(beta + g * cpg + 4 * q);
-    double s1 = 0.0, s2 = 0.0;
-    float dg[4] = {0.f, 0.f, 0.f, 0.f}, db[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int p = pl; p < npix; p += step) {
-        const f32x4 xv = *reinterpret_cast<const f32x4*>(x + base + (size_t)p * C);
-        const f32x4 dv = *reinterpret_cast<const f32x4*>(dy + base + (size_t)p * C);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float xh = (xv[e] - st.x) * st.y;
-            float dz = dv[e];
-            if (silu) {
-                const float z = xh * ga[e] + be[e], sg = sigmoid_f(z);
-                dz *= sg * (1.f + z * (1.f - sg));
-            }
-            s1 += (double)(dz * ga[e]);
-            s2 += (double)(dz * ga[e] * xh);
-            dg[e] += dz * xh;
-            db[e] += dz;
-        }
-    }
-    s1 = block_sum_d(s1, sh);
-    s2 = block_sum_d(s2, sh);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { shg[e][threadIdx.x] = dg[e]; shb[e][threadIdx.x] = db[e]; }
-    __syncthreads();
-    if (threadIdx.x < cpg) {                                          // channel ci = 4 q' + e: threads t = q' (mod Q)
-        const int qq = threadIdx.x >> 2, e = threadIdx.x & 3;
-        float tg = 0.f, tb = 0.f;
-        for (int t = qq; t < 256; t += Q) { tg += shg[e][t]; tb += shb[e][t]; }
         unsafeAtomicAdd(dgamma + g * cpg + threadIdx.x, tg);
         unsafeAtomicAdd(dbeta + g * cpg + threadIdx.x, tb);
     }
@@ -2013,167 +1907,6 @@ __global__ __launch_bounds__(256) void tr_gn_bwd_apply2_kernel(const TrGnApply a
         float* dst = (first ? a.dx0 : a.dx1) + off;
         if (first ? a.acc0 : a.acc1) out += *reinterpret_cast<const f32x4*>(dst);
         *reinterpret_cast<f32x4*>(dst) = out;
-    }
-}
-
-// ---- attention, head_dim 8 -----------------------------------------------------------------------------------------------
-// q, k, v, o: [B][L][C] fp32, head h = channels 8h .. 8h + 8.  grid (ceil(L / 128), heads, B), 128 threads = 128 queries.
-// The other side (keys / values, or queries / dO) passes through LDS in tiles of ATT_TK rows (16-18 KB: ten workgroups per
-// CU instead of two with the whole head resident), every thread reads the same row at a time (LDS broadcast).
-constexpr int ATT_TK = 256;
-
-__global__ __launch_bounds__(128) void tr_attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
-                                                          const float* __restrict__ v, int L, int C, float scale,
-                                                          float* __restrict__ o, float* __restrict__ lse) {
-    __shared__ __attribute__((aligned(16))) float sK[ATT_TK * 8];
-    __shared__ __attribute__((aligned(16))) float sV[ATT_TK * 8];
-    const int h = blockIdx.y, b = blockIdx.z, heads = gridDim.y;
-    const size_t base = (size_t)b * L * C + h * 8;
-    const int i = blockIdx.x * 128 + threadIdx.x;
-    const bool live = i < L;
-    float qi[8], acc[8];
-#pragma unroll
-    for (int d = 0; d < 8; ++d) { qi[d] = live ? q[base + (size_t)i * C + d] * scale : 0.f; acc[d] = 0.f; }
-    float m = -INFINITY, l = 0.f;
-    for (int j0 = 0; j0 < L; j0 += ATT_TK) {
-        const int nt = min(ATT_TK, L - j0);
-        __syncthreads();
-        for (int e = threadIdx.x; e < nt * 8; e += 128) {
-            sK[e] = k[base + (size_t)(j0 + (e >> 3)) * C + (e & 7)];
-            sV[e] = v[base + (size_t)(j0 + (e >> 3)) * C + (e & 7)];
-        }
-        __syncthreads();
-        // groups of 8 keys: one running-maximum update (one rescale of the accumulator) per group
-        for (int jj = 0; jj < nt; jj += 8) {
-            float sc[8];
-            float gm = m;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                float t = -INFINITY;
-                if (jj + u < nt) {
-                    t = 0.f;
-#pragma unroll
-                    for (int d = 0; d < 8; ++d) t += qi[d] * sK[(jj + u) * 8 + d];
-                }
-                sc[u] = t;
-                gm = fmaxf(gm, t);
-            }
-            const float corr = __expf(m - gm);
-            l *= corr;
-#pragma unroll
-            for (int d = 0; d < 8; ++d) acc[d] *= corr;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                if (jj + u < nt) {
-                    const float pj = __expf(sc[u] - gm);
-                    l += pj;
-#pragma unroll
-                    for (int d = 0; d < 8; ++d) acc[d] += pj * sV[(jj + u) * 8 + d];
-                }
-            }
-            m = gm;
-        }
-    }
-    if (!live) return;
-    const float inv = 1.f / l;
-#pragma unroll
-    for (int d = 0; d < 8; ++d) o[base + (size_t)i * C + d] = acc[d] * inv;
-    lse[((size_t)b * heads + h) * L + i] = m + __logf(l);
-}
-
-// dq and delta_i = dO_i . O_i ; one thread per query
-__global__ __launch_bounds__(128) void tr_attn_bwd_dq_kernel(const float* __restrict__ q, const float* __restrict__ k,
-                                                             const float* __restrict__ v, const float* __restrict__ o,
-                                                             const float* __restrict__ dO, const float* __restrict__ lse, int L, int C,
-                                                             float scale, float* __restrict__ dq, float* __restrict__ delta) {
-    __shared__ __attribute__((aligned(16))) float sK[ATT_TK * 8];
-    __shared__ __attribute__((aligned(16))) float sV[ATT_TK * 8];
-    const int h = blockIdx.y, b = blockIdx.z, heads = gridDim.y;
-    const size_t base = (size_t)b * L * C + h * 8;
-    const int i = blockIdx.x * 128 + threadIdx.x;
-    const bool live = i < L;
-    float qi[8], doi[8], acc[8];
-    float D = 0.f;
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-        qi[d] = live ? q[base + (size_t)i * C + d] * scale : 0.f;
-        doi[d] = live ? dO[base + (size_t)i * C + d] : 0.f;
-        D += live ? doi[d] * o[base + (size_t)i * C + d] : 0.f;
-        acc[d] = 0.f;
-    }
-    const float li = live ? lse[((size_t)b * heads + h) * L + i] : 0.f;
-    for (int j0 = 0; j0 < L; j0 += ATT_TK) {
-        const int nt = min(ATT_TK, L - j0);
-        __syncthreads();
-        for (int e = threadIdx.x; e < nt * 8; e += 128) {
-            sK[e] = k[base + (size_t)(j0 + (e >> 3)) * C + (e & 7)];
-            sV[e] = v[base + (size_t)(j0 + (e >> 3)) * C + (e & 7)];
-        }
-        __syncthreads();
-        for (int j = 0; j < nt; ++j) {
-            float s = 0.f, dp = 0.f;
-#pragma unroll
-            for (int d = 0; d < 8; ++d) { s += qi[d] * sK[j * 8 + d]; dp += doi[d] * sV[j * 8 + d]; }
-            const float ds = __expf(s - li) * (dp - D);
-#pragma unroll
-            for (int d = 0; d < 8; ++d) acc[d] += ds * sK[j * 8 + d];
-        }
-    }
-    if (!live) return;
-#pragma unroll
-    for (int d = 0; d < 8; ++d) dq[base + (size_t)i * C + d] = acc[d] * scale;
-    delta[((size_t)b * heads + h) * L + i] = D;
-}
-
-// dk, dv: one thread per key against all queries (Q * scale, dO, lse, delta pass through LDS in tiles)
-__global__ __launch_bounds__(128) void tr_attn_bwd_dkv_kernel(const float* __restrict__ q, const float* __restrict__ k,
-                                                              const float* __restrict__ v, const float* __restrict__ dO,
-                                                              const float* __restrict__ lse, const float* __restrict__ delta, int L,
-                                                              int C, float scale, float* __restrict__ dk, float* __restrict__ dv) {
-    __shared__ __attribute__((aligned(16))) float sQ[ATT_TK * 8];
-    __shared__ __attribute__((aligned(16))) float sDO[ATT_TK * 8];
-    __shared__ float sL[ATT_TK];
-    __shared__ float sD[ATT_TK];
-    const int h = blockIdx.y, b = blockIdx.z, heads = gridDim.y;
-    const size_t base = (size_t)b * L * C + h * 8;
-    const size_t rbase = ((size_t)b * heads + h) * L;
-    const int j = blockIdx.x * 128 + threadIdx.x;
-    const bool live = j < L;
-    float kj[8], vj[8], ak[8], av[8];
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-        kj[d] = live ? k[base + (size_t)j * C + d] : 0.f;
-        vj[d] = live ? v[base + (size_t)j * C + d] : 0.f;
-        ak[d] = 0.f;
-        av[d] = 0.f;
-    }
-    for (int i0 = 0; i0 < L; i0 += ATT_TK) {
-        const int nt = min(ATT_TK, L - i0);
-        __syncthreads();
-        for (int e = threadIdx.x; e < nt * 8; e += 128) {
-            sQ[e] = q[base + (size_t)(i0 + (e >> 3)) * C + (e & 7)] * scale;
-            sDO[e] = dO[base + (size_t)(i0 + (e >> 3)) * C + (e & 7)];
-        }
-        for (int e = threadIdx.x; e < nt; e += 128) {
-            sL[e] = lse[rbase + i0 + e];
-            sD[e] = delta[rbase + i0 + e];
-        }
-        __syncthreads();
-        for (int i = 0; i < nt; ++i) {
-            float s = 0.f, dp = 0.f;
-#pragma unroll
-            for (int d = 0; d < 8; ++d) { s += sQ[i * 8 + d] * kj[d]; dp += sDO[i * 8 + d] * vj[d]; }
-            const float pij = __expf(s - sL[i]);
-            const float ds = pij * (dp - sD[i]);
-#pragma unroll
-            for (int d = 0; d < 8; ++d) { av[d] += pij * sDO[i * 8 + d]; ak[d] += ds * sQ[i * 8 + d]; }
-        }
-    }
-    if (!live) return;
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-        dk[base + (size_t)j * C + d] = ak[d];          // sQ already carries the scale
-        dv[base + (size_t)j * C + d] = av[d];
     }
 }
 
@@ -2589,17 +2322,14 @@ static void conv_lds_plan(int P, int N, int Cin, int taps, bool* narrow_out, int
     // 128-channel tiles stage the pixel operand half as often; 64-channel tiles double the workgroups in flight, which
     // is what hides a stage's load latency when the launch has fewer than ~2 workgroups per CU (3x3 levels 1-3: 10-20 %
     // faster; the 512-workgroup level 0 and the two-stage 1x1 convs are faster with the wide tile)
-    static const int bn_env = getenv("RLDM_TR_BN") ? atoi(getenv("RLDM_TR_BN")) : 0;
-    const bool narrow = bn_env ? bn_env == 64 : (taps == 9 && gx * gy < 512);   // (measured per level)
+    const bool narrow = taps == 9 && gx * gy < 512;   // (measured per level)
     if (narrow) gy = (N + 63) / 64;
-    // split K when the launch cannot fill the chip (see the kernel): aim at >= 512 workgroups, >= 3 stages each
-    static const int ks_env = getenv("RLDM_TR_KSPLIT") ? atoi(getenv("RLDM_TR_KSPLIT")) : -1;
+    // split K when the launch cannot fill the chip (see the kernel): aim at >= kTarget workgroups, >= kMinStages stages each (the
+    // split width is on a plateau from 128 to 512 target workgroups; more splits lose 1 - 8 %)
+    constexpr int kTarget = 512, kMinStages = 3;
     const int niter = taps * (Cin / (Cin % 64 == 0 ? 64 : 32));
     const long long wgs = gx * gy;
-    static const int tgt_env = getenv("RLDM_TR_KSPLIT_TARGET") ? atoi(getenv("RLDM_TR_KSPLIT_TARGET")) : 512;
-    static const int minst_env = getenv("RLDM_TR_KSPLIT_MINSTAGES") ? atoi(getenv("RLDM_TR_KSPLIT_MINSTAGES")) : 3;
-    int ksplit = wgs > 192 ? 1 : (int)std::min<long long>((tgt_env + wgs - 1) / wgs, niter / minst_env);
-    if (ks_env >= 0) ksplit = ks_env;
+    const int ksplit = wgs > 192 ? 1 : (int)std::min<long long>((kTarget + wgs - 1) / wgs, niter / kMinStages);
     *narrow_out = narrow;
     *ksplit_out = std::max(1, std::min(ksplit, niter));
 }
@@ -2615,36 +2345,38 @@ int rldm_train_conv_splits(const rldm_train_conv_desc* d, int rowadd_ld) {
     return ksplit;
 }
 
-// The scratch buffers of this file (arrival tickets, partial tiles, fp64 accumulators) are process-wide and live on the device that was
-// current when the first of them was allocated: ONE training device per process (one process per GPU is how this library scales).
-// A call on another device is refused instead of handing it a pointer into the first device's memory.
-static int tr_scratch_device_ok() {
+// The scratch buffers of this file, one per slot, all owned by tr_scratch.  They are process-wide and live on the device that was current
+// when the first of them was allocated: ONE training device per process (one process per GPU is how this library scales); a call on
+// another device is refused instead of handing it a pointer into the first device's memory.  One caller thread; launches are stream
+// ordered, so consecutive launches may share a buffer.  A buffer grows outside stream captures only (the first, eager, step of a shape
+// sizes it), and the block it outgrew is kept, never freed: a step graph captured at an earlier, smaller shape still holds its address.
+enum TrScratchSlot { kFuseTickets, kGnAccumulators, kWgradPartials, kGroupPartials, kGroupTickets, kScratchSlots };
+
+// -> *out: at least `bytes` of the slot's buffer; `zeroed`: a new block is zeroed once (tickets / accumulators, which every user leaves
+// zeroed).  Growth rounds up to `min_bytes`.
+static int tr_scratch(TrScratchSlot slot, size_t bytes, size_t min_bytes, bool zeroed, hipStream_t st, void** out) {
     static int dev0 = -1;
+    static void* buf[kScratchSlots] = {};
+    static size_t cap[kScratchSlots] = {};
     int dev = -1;
     RLDM_HIP_CHECK(hipGetDevice(&dev));
     if (dev0 < 0) dev0 = dev;
     RLDM_REQUIRE(dev == dev0, "the training scratch buffers of this process live on device " + std::to_string(dev0) +
                                   ": one training device per process (current device " + std::to_string(dev) + ")");
-    return 0;
-}
-
-// arrival counters of the fused split-K launches: zeroed once, every launch leaves them zeroed (one caller thread, stream ordered;
-// never reallocated during a stream capture: the first, eager, step of a shape sizes it)
-static int fuse_tickets(size_t count, hipStream_t st, unsigned** out) {
-    static unsigned* buf = nullptr;
-    static size_t cap = 0;
-    if (tr_scratch_device_ok()) return 1;
-    if (count > cap) {
+    if (bytes > cap[slot]) {
+        hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+        RLDM_HIP_CHECK(hipStreamIsCapturing(st, &capture));
+        RLDM_REQUIRE(capture == hipStreamCaptureStatusNone,
+                     "a training scratch buffer would grow during a stream capture: run one eager step at this shape first");
         RLDM_HIP_CHECK(hipStreamSynchronize(st));
-        if (buf) RLDM_HIP_CHECK(hipFree(buf));
-        buf = nullptr;
-        cap = 0;
-        const size_t want = std::max<size_t>(count, 16384);
-        RLDM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&buf), want * sizeof(unsigned)));
-        RLDM_HIP_CHECK(hipMemset(buf, 0, want * sizeof(unsigned)));
-        cap = want;
+        const size_t want = std::max(bytes, min_bytes);
+        void* p = nullptr;
+        RLDM_HIP_CHECK(hipMalloc(&p, want));
+        if (zeroed) RLDM_HIP_CHECK(hipMemset(p, 0, want));
+        buf[slot] = p;                              // (the outgrown block stays allocated: see above)
+        cap[slot] = want;
     }
-    *out = buf;
+    *out = buf[slot];
     return 0;
 }
 
@@ -2757,7 +2489,11 @@ static int train_conv_impl(const rldm_train_conv_desc* d, const rldm_train_fuse*
         if (ksplit > 1) {
             if (!accumulate) tr_zero_kernel<<<nblk((size_t)P * p.N / 4 + 1), 256, 0, st>>>(y, (size_t)P * p.N);   // (a kernel, not a memset node: see tr_zero_kernel)
             grid.z = ksplit;
-            if (fu && (f.cs_out || f.gs_out) && fuse_tickets((size_t)grid.x * grid.y, st, &f.tickets)) return 1;
+            // (arrival counters of the fused split-K launches: every launch leaves them zeroed)
+            if (fu && (f.cs_out || f.gs_out) &&
+                tr_scratch(kFuseTickets, (size_t)grid.x * grid.y * sizeof(unsigned), 16384 * sizeof(unsigned), true, st,
+                           reinterpret_cast<void**>(&f.tickets)))
+                return 1;
         } else if (fu && (f.cs_out || f.gs_out)) {
             RLDM_REQUIRE(!accumulate, "rldm_train_conv_fused: the fused epilogue writes y (no accumulation)");
             p.accumulate = 0;
@@ -2767,16 +2503,13 @@ static int train_conv_impl(const rldm_train_conv_desc* d, const rldm_train_fuse*
             if (planes < 0) return 1;
             grid.z += planes;
         }
-        static const bool nohalo_env = getenv("RLDM_TR_NO_HALO") != nullptr;           // A/B: the per-tap staging kernel
         const int H = p.Hout;
-        const bool halo = !nohalo_env && ksplit == 1 && p.taps == 9 && p.stride == 1 && p.mode == 0 && p.Cin % 64 == 0 && p.N % 4 == 0 &&
+        const bool halo = ksplit == 1 && p.taps == 9 && p.stride == 1 && p.mode == 0 && p.Cin % 64 == 0 && p.N % 4 == 0 &&
                           H >= 2 && H <= 32 && (H & (H - 1)) == 0 && (p.Wout * H) % 64 == 0 && p.Wout % (64 / H) == 0 && p.Wout >= 64 / H + 2;
-        static const int pt_env = getenv("RLDM_TR_PT") ? atoi(getenv("RLDM_TR_PT")) : 0;
-        const bool wide_px = pt_env == 128 && !f.rblocks && halo && !narrow && (p.Wout * H) % 128 == 0 && p.Wout % (128 / H) == 0 && p.Wout >= 128 / H + 2;
         if (fu) {                                   // the fused instances (conv_fuse_ok held)
             if (halo) {
-                if (narrow) tr_conv_halo_kernel<64, 64, true><<<grid, 256, 0, st>>>(p, f);
-                else tr_conv_halo_kernel<128, 64, true><<<grid, 256, 0, st>>>(p, f);
+                if (narrow) tr_conv_halo_kernel<64, true><<<grid, 256, 0, st>>>(p, f);
+                else tr_conv_halo_kernel<128, true><<<grid, 256, 0, st>>>(p, f);
             } else if (p.Cin % 64 == 0) {
                 if (narrow) tr_conv_lds_kernel<64, 64, true><<<grid, 256, 0, st>>>(p, f);
                 else tr_conv_lds_kernel<64, 128, true><<<grid, 256, 0, st>>>(p, f);
@@ -2784,12 +2517,9 @@ static int train_conv_impl(const rldm_train_conv_desc* d, const rldm_train_fuse*
                 if (narrow) tr_conv_lds_kernel<32, 64, true><<<grid, 256, 0, st>>>(p, f);
                 else tr_conv_lds_kernel<32, 128, true><<<grid, 256, 0, st>>>(p, f);
             }
-        } else if (halo && wide_px) {
-            grid.x = P / 128;
-            tr_conv_halo_kernel<128, 128><<<grid, 512, 0, st>>>(p, f);
         } else if (halo) {
-            if (narrow) tr_conv_halo_kernel<64, 64><<<grid, 256, 0, st>>>(p, f);
-            else tr_conv_halo_kernel<128, 64><<<grid, 256, 0, st>>>(p, f);
+            if (narrow) tr_conv_halo_kernel<64><<<grid, 256, 0, st>>>(p, f);
+            else tr_conv_halo_kernel<128><<<grid, 256, 0, st>>>(p, f);
         } else if (p.Cin % 64 == 0) {
             if (narrow) tr_conv_lds_kernel<64, 64><<<grid, 256, 0, st>>>(p, f);
             else tr_conv_lds_kernel<64, 128><<<grid, 256, 0, st>>>(p, f);
@@ -2821,7 +2551,7 @@ static bool wgrad_v2_shape(const rldm_train_conv_desc* d) {
 }
 
 int rldm_train_wgrad_fused_ok(const rldm_train_conv_desc* d, const rldm_train_fuse* fu) {
-    if (!d || !fu || getenv("RLDM_TR_WG_V1")) return 0;
+    if (!d || !fu) return 0;
     if (!wgrad_v2_shape(d) || d->mode != 0 || d->B > 16) return 0;
     if (fu->x1 && (fu->C0 <= 0 || fu->C0 >= d->Cin || fu->C0 % 64 != 0)) return 0;
     if (fu->cs0 && (fu->groups < 1 || d->Cin % fu->groups != 0 || !fu->gamma || !fu->beta || (fu->x1 && !fu->cs1))) return 0;
@@ -2831,62 +2561,38 @@ int rldm_train_wgrad_fused_ok(const rldm_train_conv_desc* d, const rldm_train_fu
 // ---- (round 6) grouped weight gradients: the queue ------------------------------------------------------------------------------------
 // rldm_train_wgrad_group(1): all-taps weight gradients are queued instead of launched; rldm_train_wgrad_group_flush (or group(0)) runs
 // the queue as a few launches of tr_wgrad2_group_kernel.  One caller thread, one stream per queue (a call on another stream flushes
-// first); the caller keeps every queued operand alive and unmodified until the flush (rangeldm_amd/training.py does).
+// first, and so does queueing a dw that is already queued: two items of one launch must not add into the same dw); the caller keeps every
+// queued operand alive and unmodified until the flush (rangeldm_amd/training.py does).  A flush empties the queue, failed or not.
 struct WgQueued { WgItem it; int taps; bool fu, v3; int tiles; size_t part_floats; size_t smem; double unit; };
 static std::vector<WgQueued> g_wgq;
 static hipStream_t g_wgq_stream = nullptr;
 static int g_wg_group = 0;
 
-static int wg_group_flush() {
-    if (g_wgq.empty()) return 0;
-    if (tr_scratch_device_ok()) return 1;
+static int wg_group_launch() {
     hipStream_t st = g_wgq_stream;
     // K slices.  With every layer of a class in one launch the chip is full whatever a single layer brings, so the slices per tile --
     // partial tiles to write and re-read, a last arriver to sum them -- shrink from the launch-per-layer form's 64 to <= 16: a workgroup
     // takes `budget` units of work (a unit = a chunk of 128 pixels x 9 taps; a 1x1 tap set costs about a third).  Measured per class at
     // the RangeLDM size, batch 8 (profiles/round6_wgrad_group_budget.txt): 3x3 launches are fastest at 32 units (712 / 276 us; 16: 769 /
     // 307, 8: 996 / 434, 4: 1543 / 514 -- the last arriver's serial sum over the slices is the tail), the 1x1 launches at 8 - 16.
-    static const int budget_env = getenv("RLDM_TR_WG_GROUP_CPW") ? atoi(getenv("RLDM_TR_WG_GROUP_CPW")) : 0;
-    for (int cls = 0; cls < 8; ++cls) {
-        const int taps = (cls & 1) ? 1 : 9;
-        const bool fu = (cls & 2) != 0, v3 = (cls & 4) != 0;
-        const double budget = budget_env ? (double)budget_env : (taps == 9 ? 32.0 : 12.0);
-        for (auto& q : g_wgq) {
-            if (q.taps != taps || q.fu != fu || q.v3 != v3) continue;
-            WgItem& it = q.it;
-            int cpw = std::max(1, (int)(budget / q.unit + 0.5));
-            cpw = std::min(cpw, it.nchunks);
-            int Z = (it.nchunks + cpw - 1) / cpw;
-            cpw = (it.nchunks + Z - 1) / Z;
-            Z = (it.nchunks + cpw - 1) / cpw;
-            it.cpw = cpw; it.Z = Z;
-            q.part_floats = Z > 1 ? (size_t)q.taps * Z * it.N * it.Cin : 0;
-        }
+    for (auto& q : g_wgq) {
+        const double budget = q.taps == 9 ? 32.0 : 12.0;
+        WgItem& it = q.it;
+        int cpw = std::max(1, (int)(budget / q.unit + 0.5));
+        cpw = std::min(cpw, it.nchunks);
+        int Z = (it.nchunks + cpw - 1) / cpw;
+        cpw = (it.nchunks + Z - 1) / Z;
+        Z = (it.nchunks + cpw - 1) / cpw;
+        it.cpw = cpw; it.Z = Z;
+        q.part_floats = Z > 1 ? (size_t)q.taps * Z * it.N * it.Cin : 0;
     }
-    // scratch of the partial tiles (layers with more than one K slice) and the arrival tickets: grown outside captures only (the first,
-    // eager, step of a shape sizes them -- as every scratch buffer of this file)
+    // scratch of the partial tiles (layers with more than one K slice) and the arrival tickets (every launch leaves them zeroed)
     size_t need = 0, ntick = 0;
     for (auto& q : g_wgq) { need += q.part_floats; ntick += (size_t)q.tiles; }
-    static float* scratch = nullptr;
-    static size_t scratch_cap = 0;
-    static unsigned* tickets = nullptr;
-    static size_t tick_cap = 0;
-    if (need > scratch_cap) {
-        RLDM_HIP_CHECK(hipStreamSynchronize(st));
-        if (scratch) RLDM_HIP_CHECK(hipFree(scratch));
-        scratch = nullptr; scratch_cap = 0;
-        RLDM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&scratch), need * sizeof(float)));
-        scratch_cap = need;
-    }
-    if (ntick > tick_cap) {
-        RLDM_HIP_CHECK(hipStreamSynchronize(st));
-        if (tickets) RLDM_HIP_CHECK(hipFree(tickets));
-        tickets = nullptr; tick_cap = 0;
-        const size_t want = std::max<size_t>(ntick, 4096);
-        RLDM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&tickets), want * sizeof(unsigned)));
-        RLDM_HIP_CHECK(hipMemset(tickets, 0, want * sizeof(unsigned)));        // zeroed once; every launch leaves them zeroed
-        tick_cap = want;
-    }
+    float* scratch = nullptr;
+    unsigned* tickets = nullptr;
+    if (tr_scratch(kGroupPartials, need * sizeof(float), 0, false, st, reinterpret_cast<void**>(&scratch))) return 1;
+    if (tr_scratch(kGroupTickets, ntick * sizeof(unsigned), 4096 * sizeof(unsigned), true, st, reinterpret_cast<void**>(&tickets))) return 1;
     typedef void (*GroupKernel)(const WgGroup);
     static const GroupKernel kernels[8] = {tr_wgrad2_group_kernel<9, false, false>, tr_wgrad2_group_kernel<1, false, false>,
                                            tr_wgrad2_group_kernel<9, true, false>,  tr_wgrad2_group_kernel<1, true, false>,
@@ -2930,8 +2636,14 @@ static int wg_group_flush() {
             TR_LAUNCH_CHECK();
         }
     }
-    g_wgq.clear();
     return 0;
+}
+
+static int wg_group_flush() {
+    if (g_wgq.empty()) return 0;
+    const int rc = wg_group_launch();
+    g_wgq.clear();
+    return rc;
 }
 
 int rldm_train_wgrad_group(int on) {
@@ -2970,15 +2682,14 @@ static int train_wgrad_impl(const rldm_train_conv_desc* d, const rldm_train_fuse
     const int P = p.B * p.Wout * p.Hout;
     const int tiles = ((p.N + 63) / 64) * ((p.Cin + 63) / 64) * p.taps;
     // a wave contracts `chunk` pixels into its own partial tile; ~1024 pixels per wave, fewer only to fill the chip
-    int chunk = getenv("RLDM_TR_WG_CHUNK") ? atoi(getenv("RLDM_TR_WG_CHUNK")) : 1024;
+    int chunk = 1024;
     while (chunk > 128 && (long long)tiles * ((P + 4 * chunk - 1) / (4 * chunk)) < 256) chunk >>= 1;
     int splits = (P + 4 * chunk - 1) / (4 * chunk);
     p.chunk = chunk;
     size_t need = (size_t)p.taps * splits * 4 * p.N * p.Cin * sizeof(float);
     // all-taps kernel (see tr_wgrad2_kernel): stride 1, 64-multiples of channels, H a power of two <= 16, chunk of WC columns
-    static const bool v1_env = getenv("RLDM_TR_WG_V1") != nullptr;                // A/B: the one-tap-per-workgroup kernel
     TrWgrad2 w2{};
-    bool v2 = !v1_env && d->stride == 1 && d->mode <= 1 && p.N % 64 == 0 && p.Cin % 64 == 0 && p.Hout >= 2 && p.Hout <= 16 &&
+    bool v2 = d->stride == 1 && d->mode <= 1 && p.N % 64 == 0 && p.Cin % 64 == 0 && p.Hout >= 2 && p.Hout <= 16 &&
               (p.Hout & (p.Hout - 1)) == 0;
     if (v2) {
         const int H = p.Hout, W = p.Wout;
@@ -2991,11 +2702,10 @@ static int train_wgrad_impl(const rldm_train_conv_desc* d, const rldm_train_fuse
             const int WC = 1 << lwc;
             w2.nchunks = p.B * (W / WC);
             const int tiles2 = (p.N / 64) * (p.Cin / 64);
-            static const int wg_env = getenv("RLDM_TR_WG_BLOCKS") ? atoi(getenv("RLDM_TR_WG_BLOCKS")) : 256;
+            constexpr int kBlocks = 256;                // workgroups to aim at
             // (few chunks -- the 32 x 2 level -- : two per workgroup halve the partial tiles for the same kernel time)
-            static const int cpw_env = getenv("RLDM_TR_WG_CPW") ? atoi(getenv("RLDM_TR_WG_CPW")) : 0;
-            const int cpw_min = cpw_env ? cpw_env : (w2.nchunks <= 16 ? 2 : 1);
-            int Z = std::max(1, std::min(std::max(1, w2.nchunks / cpw_min), (wg_env + tiles2 - 1) / tiles2));
+            const int cpw_min = w2.nchunks <= 16 ? 2 : 1;
+            int Z = std::max(1, std::min(std::max(1, w2.nchunks / cpw_min), (kBlocks + tiles2 - 1) / tiles2));
             w2.cpw = (w2.nchunks + Z - 1) / Z;
             Z = (w2.nchunks + w2.cpw - 1) / w2.cpw;
             w2.pitchA = WC * H + 8;
@@ -3006,8 +2716,9 @@ static int train_wgrad_impl(const rldm_train_conv_desc* d, const rldm_train_fuse
     }
     hipStream_t st = (hipStream_t)stream;
     if (v2 && g_wg_group) {
-        // queued for a grouped launch (tr_wgrad2_group_kernel; K slices: wg_group_flush)
-        if (!g_wgq.empty() && g_wgq_stream != st && wg_group_flush()) return 1;
+        // queued for a grouped launch (tr_wgrad2_group_kernel; K slices: wg_group_launch)
+        const bool dw_queued = std::any_of(g_wgq.begin(), g_wgq.end(), [dw](const WgQueued& q) { return q.it.dw == dw; });
+        if ((dw_queued || (!g_wgq.empty() && g_wgq_stream != st)) && wg_group_flush()) return 1;
         g_wgq_stream = st;
         const int KP = w2.H << w2.lwc;
         WgQueued q{};
@@ -3020,8 +2731,7 @@ static int train_wgrad_impl(const rldm_train_conv_desc* d, const rldm_train_fuse
         it.x1 = f.x1; it.C0 = f.C0; it.cs0 = f.cs0; it.cs1 = f.cs1; it.gamma = f.gamma; it.beta = f.beta; it.silu = f.silu;
         it.groups = f.groups; it.eps = f.eps;
         q.taps = p.taps; q.fu = fu != nullptr;
-        static const bool v3_off = getenv("RLDM_TR_WG_V3") && atoi(getenv("RLDM_TR_WG_V3")) == 0;       // (A/B: the round-5 staging)
-        q.v3 = !v3_off && w2.H >= 8 && w2.mode == 0;
+        q.v3 = w2.H >= 8 && w2.mode == 0;
         q.tiles = (p.N / 64) * (p.Cin / 64);
         q.part_floats = 0;
         const int pitchB = q.v3 ? ((1 << w2.lwc) + (p.taps == 9 ? 2 : 0)) * w2.H + 8 : w2.pitchB;
@@ -3033,22 +2743,12 @@ static int train_wgrad_impl(const rldm_train_conv_desc* d, const rldm_train_fuse
         g_wgq.push_back(q);
         return 0;
     }
-    static float* scratch = nullptr;                   // (one caller thread; launches are stream ordered)
-    static size_t scratch_cap = 0;
-    if (tr_scratch_device_ok()) return 1;
-    if (need > scratch_cap) {
-        RLDM_HIP_CHECK(hipStreamSynchronize(st));
-        if (scratch) RLDM_HIP_CHECK(hipFree(scratch));
-        scratch = nullptr;
-        scratch_cap = 0;
-        RLDM_HIP_CHECK(hipMalloc(&scratch, need));
-        scratch_cap = need;
-    }
+    float* scratch = nullptr;
+    if (tr_scratch(kWgradPartials, need, 0, false, st, reinterpret_cast<void**>(&scratch))) return 1;
     p.dw = scratch;
     if (v2) {
-        static const bool part_env = getenv("RLDM_TR_WG_PARTIALS") != nullptr;      // A/B: partial tiles + reduction launch
         w2.dy = dy; w2.x = x; w2.part = scratch;
-        w2.dw = (part_env || p.taps == 9) ? nullptr : dw;      // (measured: 3x3 tiles are 9x larger, their 38 MB of atomics lose to the
+        w2.dw = p.taps == 9 ? nullptr : dw;                     // (measured: 3x3 tiles are 9x larger, their 38 MB of atomics lose to the
                                                                 //  partial tiles + reduction launch by 10-30 %; 1x1 wins 25-35 %)
         w2.rows = rows; w2.rows_ld = rows_ld; w2.total = total;
         if (rows && !rows_accumulate) tr_zero2d_kernel<<<nblk((size_t)p.B * p.N), 256, 0, st>>>(rows, rows_ld, p.N, p.B);
@@ -3122,25 +2822,9 @@ int rldm_train_colsum(const float* dy, int B, int npix, int N, float* rows, int 
     return 0;
 }
 
-// fp64 accumulators of the slab GroupNorm kernels: one growing device buffer (one caller thread; launches are stream
-// ordered, so consecutive launches may share it).  Never reallocated while a stream capture is running: the first
-// (eager) step of a shape sizes it.
+// fp64 accumulators of the slab GroupNorm kernels: zeroed once, every user leaves them zeroed (finish kernels)
 static int gn_accumulators(size_t count, hipStream_t st, double** out) {
-    static double* buf = nullptr;
-    static size_t cap = 0;
-    if (tr_scratch_device_ok()) return 1;
-    if (count > cap) {
-        RLDM_HIP_CHECK(hipStreamSynchronize(st));
-        if (buf) RLDM_HIP_CHECK(hipFree(buf));
-        buf = nullptr;
-        cap = 0;
-        const size_t want = std::max<size_t>(count, 4096);
-        RLDM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&buf), want * sizeof(double)));
-        RLDM_HIP_CHECK(hipMemset(buf, 0, want * sizeof(double)));        // zero once; every user leaves it zeroed (finish kernels)
-        cap = want;
-    }
-    *out = buf;
-    return 0;
+    return tr_scratch(kGnAccumulators, count * sizeof(double), 4096 * sizeof(double), true, st, reinterpret_cast<void**>(out));
 }
 
 int rldm_train_gn_forward(const float* x, int B, int npix, int C, int groups, float eps, const float* gamma, const float* beta,
@@ -3156,14 +2840,10 @@ int rldm_train_gn_forward(const float* x, int B, int npix, int C, int groups, fl
         tr_gn_stats_finish_kernel<<<nblk((size_t)B * groups), 256, 0, st>>>(acc, B * groups, (double)npix * (C / groups), eps,
                                                                            reinterpret_cast<float2*>(stats));
     } else if ((C / groups) % 4 == 0 && C / groups <= 16 && (C / groups & (C / groups - 1)) == 0) {
-        static const bool nofuse = getenv("RLDM_TR_GN_NOFUSE") != nullptr;
-        if (!nofuse) {
-            tr_gn_fwd_fused_vec_kernel<<<dim3(groups, B), 256, 0, st>>>(x, npix, C, groups, eps, gamma, beta, silu,
-                                                                        reinterpret_cast<float2*>(stats), y);
-            TR_LAUNCH_CHECK();
-            return 0;
-        }
-        tr_gn_stats_vec_kernel<<<dim3(groups, B), 256, 0, st>>>(x, npix, C, groups, eps, reinterpret_cast<float2*>(stats));
+        tr_gn_fwd_fused_vec_kernel<<<dim3(groups, B), 256, 0, st>>>(x, npix, C, groups, eps, gamma, beta, silu,
+                                                                    reinterpret_cast<float2*>(stats), y);
+        TR_LAUNCH_CHECK();
+        return 0;
     } else
         tr_gn_stats_kernel<<<dim3(groups, B), 256, 0, st>>>(x, npix, C, groups, eps, reinterpret_cast<float2*>(stats));
     const size_t total = (size_t)B * npix * C;
@@ -3187,16 +2867,13 @@ int rldm_train_gn_backward(const float* x, const float* dy, const float* stats, 
     if (slab) {
         double* acc = nullptr;
         if (gn_accumulators((size_t)B * groups * 2, st, &acc)) return 1;
-        static const int slab_env = getenv("RLDM_TR_GN_SLAB") ? atoi(getenv("RLDM_TR_GN_SLAB")) : 64;
-        tr_gn_bwd_reduce_slab_kernel<<<dim3((npix + slab_env - 1) / slab_env, B), 256, 0, st>>>(x, dy, reinterpret_cast<const float2*>(stats), gamma,
+        constexpr int kSlab = 64;                   // pixels per block
+        tr_gn_bwd_reduce_slab_kernel<<<dim3((npix + kSlab - 1) / kSlab, B), 256, 0, st>>>(x, dy, reinterpret_cast<const float2*>(stats), gamma,
                                                                                beta, npix, C, groups, silu, acc, dgamma, dbeta);
         tr_gn_sums_finish_kernel<<<nblk((size_t)B * groups), 256, 0, st>>>(acc, B * groups, reinterpret_cast<float2*>(scratch));
-    } else if (gn_vec_reduce_env() && (C / groups) % 4 == 0 && C / groups <= 16 && (C / groups & (C / groups - 1)) == 0)
-        // (A/B only: measured 14.0 us against 10.1 us for the channel-pinned kernel below -- four sigmoids per iteration and the
-        //  wider LDS epilogue cost more than the 16-byte loads save; fusing the apply pass into it was no faster either)
-        tr_gn_bwd_reduce_vec_kernel<<<dim3(groups, B), 256, 0, st>>>(x, dy, reinterpret_cast<const float2*>(stats), gamma, beta, npix, C,
-                                                                 groups, silu, reinterpret_cast<float2*>(scratch), dgamma, dbeta);
-    else
+    } else
+        // (a four-channels-per-thread form measured 14.0 us against this kernel's 10.1: four sigmoids per iteration and the wider
+        //  LDS epilogue cost more than the 16-byte loads save)
         tr_gn_bwd_reduce_kernel<<<dim3(groups, B), 256, 0, st>>>(x, dy, reinterpret_cast<const float2*>(stats), gamma, beta, npix, C,
                                                                  groups, silu, reinterpret_cast<float2*>(scratch), dgamma, dbeta);
     const size_t total = (size_t)B * npix * C;
@@ -3246,10 +2923,7 @@ int rldm_train_attention_forward(const float* q, const float* k, const float* v,
                                  void* stream) {
     RLDM_REQUIRE(q && k && v && o && lse, "null argument");
     RLDM_REQUIRE(C % 8 == 0, "head_dim is 8");
-    if (!attention_scalar()) return rldm::tr_attention_forward_mfma(q, k, v, C, B, L, C, o, lse, (hipStream_t)stream);
-    tr_attn_fwd_kernel<<<dim3((L + 127) / 128, C / 8, B), 128, 0, (hipStream_t)stream>>>(q, k, v, L, C, 0.35355339059327373f, o, lse);
-    TR_LAUNCH_CHECK();
-    return 0;
+    return rldm::tr_attention_forward_mfma(q, k, v, C, B, L, C, o, lse, (hipStream_t)stream);
 }
 
 int rldm_train_attention_qkv_forward(const float* qkv, int B, int L, int C, float* o, float* lse, void* stream) {
@@ -3270,14 +2944,7 @@ int rldm_train_attention_backward(const float* q, const float* k, const float* v
                                   int B, int L, int C, float* delta, float* dq, float* dk, float* dv, void* stream) {
     RLDM_REQUIRE(q && k && v && o && dO && lse && delta && dq && dk && dv, "null argument");
     RLDM_REQUIRE(C % 8 == 0, "head_dim is 8");
-    hipStream_t st = (hipStream_t)stream;
-    if (!attention_scalar()) return rldm::tr_attention_backward_mfma(q, k, v, C, o, dO, lse, B, L, C, delta, dq, dk, dv, st);
-    const float scale = 0.35355339059327373f;
-    const dim3 grid((L + 127) / 128, C / 8, B);
-    tr_attn_bwd_dq_kernel<<<grid, 128, 0, st>>>(q, k, v, o, dO, lse, L, C, scale, dq, delta);
-    tr_attn_bwd_dkv_kernel<<<grid, 128, 0, st>>>(q, k, v, dO, lse, delta, L, C, scale, dk, dv);
-    TR_LAUNCH_CHECK();
-    return 0;
+    return rldm::tr_attention_backward_mfma(q, k, v, C, o, dO, lse, B, L, C, delta, dq, dk, dv, (hipStream_t)stream);
 }
 
 int rldm_train_add(const float* a, const float* b, float* y, int64_t n, void* stream) {

@@ -196,16 +196,15 @@ class UNetTrainer:
         self._step_dev = torch.zeros((), dtype=torch.int64, device=self.device)
         self._step_dev_mirror = 0
         self._dyn = torch.zeros(4, dtype=torch.float32, device=self.device)
-        # fused tape (round 5): GroupNorm folded into its producers / consumers, concatenations read in place
-        # (RLDM_TRAIN_FUSED=0: the op-per-layer tape, kept as the cross-check)
-        self.fused_tape = os.environ.get("RLDM_TRAIN_FUSED", "1") != "0"
-        self.fused_min_pixels = int(os.environ.get("RLDM_TRAIN_FUSED_MINPX", "1024"))
-        # the reduction of a weight gradient's partial tiles rides on the layer's data-gradient launch (RLDM_TR_DEFER_REDUCE=0: own launch)
-        self.defer_reduce = os.environ.get("RLDM_TR_DEFER_REDUCE", "1") != "0"
+        # fused tape (round 5): GroupNorm folded into its producers / consumers, concatenations read in place, on the levels of at least
+        # `fused_min_pixels` pixels per image (fused_tape = False: the op-per-layer tape, kept as the cross-check)
+        self.fused_tape = True
+        self.fused_min_pixels = 1024
         # (round 6) the weight gradients of the step are queued and run as a few grouped launches (rldm_train_wgrad_group: nothing in
-        # backward waits for a weight gradient, and ~85 launches of them each sat at its launch floor); RLDM_TR_WGRAD_GROUP=0: launched
-        # where the tape reaches them.  _wg_keep: the queued launches' operands (dy, inputs, statistics), alive until the flush
-        self.wgrad_group = os.environ.get("RLDM_TR_WGRAD_GROUP", "1") != "0"
+        # backward waits for a weight gradient, and ~85 launches of them each sat at its launch floor); wgrad_group = False: launched
+        # where the tape reaches them, the cross-check.  _wg_keep: the queued launches' operands (dy, inputs, statistics), alive until
+        # the flush
+        self.wgrad_group = True
         self._wg_on, self._wg_keep = False, []
         self._cs = {}
 
@@ -537,11 +536,22 @@ class UNetTrainer:
         def __init__(self, a, b):
             self.a, self.b = a, b
 
+    def _end_queues(self, report=True):
+        """Run the queued weight gradients and the deferred reduction, and switch both queues off: every gradient is final from here
+        on.  The switches are reset whatever fails; report=False drops the flush's own error."""
+        try:
+            try:
+                T.wgrad_group(False)                    # (runs what is still queued)
+            finally:
+                self._wg_on = False
+                self._wg_keep.clear()
+                T.defer_reduce(False)                   # (flushes)
+        except Exception:
+            if report:
+                raise
+
     def fused_shape_ok(self, B, W, H):
-        """Do the fused kernels cover every layer of this network at this input size?  (RLDM_TR_WG_V1, the A/B switch that makes the
-        library refuse the all-taps weight-gradient kernel, also switches the fused blocks off: they have no other weight gradient)"""
-        if os.environ.get("RLDM_TR_WG_V1"):
-            return False
+        """Do the fused kernels cover every layer of this network at this input size?"""
         return self.fused_tape and fused_tape_supported(self.cfg, self.fused, B, W, H)
 
     def _srcs(self, x):
@@ -763,17 +773,17 @@ class UNetTrainer:
             avg = torch.distributed.get_backend() == "nccl" or D.cabi_communicator() is not None
             self._reduce_op = torch.distributed.ReduceOp.AVG if avg else torch.distributed.ReduceOp.SUM
         self._acc(self._out, dpred, False)
-        T.defer_reduce(self.defer_reduce)
+        # the reduction of a weight gradient's partial tiles rides on the layer's data-gradient launch
+        T.defer_reduce(True)
         self._wg_on = bool(self.wgrad_group)
-        T.wgrad_group(self._wg_on)
         try:
+            T.wgrad_group(self._wg_on)
             for fn in reversed(self._tape):
                 fn()
-        finally:
-            T.wgrad_group(False)                        # (runs what is still queued)
-            self._wg_on = False
-            self._wg_keep.clear()
-            T.defer_reduce(False)                       # (flushes: every gradient is final from here on)
+        except BaseException:
+            self._end_queues(report=False)              # (the tape's error is the one to report)
+            raise
+        self._end_queues()
         self._tape, self._grad, self._cs = [], {}, {}
         T.set_zero_arena(None)
         if launch_collectives:

@@ -422,6 +422,16 @@ def test_graphed_steps_equal_eager_steps():
     b.train_step_graphed(x, t, target, w, pos_encoding=True)
     assert int(b._step_dev) == b.global_step == 8
     _adam_close(a.state_dict(), b.state_dict(), lr, "parameters after mixed steps")
+    # a larger batch grows the library's scratch buffers (sizing step, capture, replay); the batch-2 graph captured before the growth
+    # still holds the outgrown blocks' addresses, and replaying it afterwards must find them allocated
+    for B in (32, 32, 32, 2):
+        x, target = torch.randn(B, 4, 32, 8, generator=g).cuda(), torch.randn(B, 4, 32, 8, generator=g).cuda()
+        t, w = torch.randint(0, 1000, (B,), generator=g).cuda(), torch.rand(B, generator=g).cuda()
+        a.train_step(x, t, target, w, pos_encoding=True)
+        b.train_step_graphed(x, t, target, w, pos_encoding=True)
+    assert len(b._graphs) == 2 and int(b._step_dev) == b.global_step == 12
+    _adam_close(a.state_dict(), b.state_dict(), lr, "parameters after a larger batch")
+    _adam_close(a.state_dict(ema=True), b.state_dict(ema=True), lr, "ema after a larger batch")
 
 
 @pytest.mark.gpu
@@ -543,7 +553,7 @@ def test_training_step_loop_body_unconditional_and_conditional():
 @pytest.mark.gpu
 def test_fused_tape_equals_layer_tape_full_config():
     """BASELINE config-5 shapes, batch 2: the fused tape (3 launches per resnet forward; GroupNorm only inside conv kernels) against
-    the op-per-layer tape (RLDM_TRAIN_FUSED=0's path) on the same weights: same prediction and same gradients up to the bf16
+    the op-per-layer tape (fused_tape = False) on the same weights: same prediction and same gradients up to the bf16
     rounding of operands (z = x a + b against ((x - mean) rstd) gamma + beta: last-bit differences in fp32 flip bf16 roundings, which
     a 60-conv network amplifies to 4e-3 on the prediction) and the order of the fp32 atomics."""
     from rangeldm_amd import train_ops as T

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Training attention kernels at the UNet's shapes (batch 8): forward / backward time by HIP events.
-RLDM_TR_ATTN=scalar selects the fp32 one-thread-per-query kernels for A/B runs."""
+(The matrix-core kernels of train_attn.hip behind rldm_train_attention_forward / _backward.)"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
