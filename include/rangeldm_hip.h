@@ -335,6 +335,7 @@ int rldm_train_wgrad_fused(const rldm_train_conv_desc* d, const rldm_train_fuse*
  * call, rldm_train_flush_reduce, rldm_train_defer_reduce(0).  Call rldm_train_flush_reduce before anything else reads dw. */
 int rldm_train_defer_reduce(int on);
 int rldm_train_flush_reduce(void);
+int rldm_train_reduce_pending(void);   /* 1 while a deferred reduction waits for a launch to ride on (tests) */
 /* (round 6) Grouped weight gradients.  The weight gradients of a step (`loss.backward()`, ldm/train_unconditional.py:545) depend on
  * nothing behind them in the backward pass and nothing in it depends on them.  With grouping on, rldm_train_wgrad_bias / _wgrad_fused
  * calls that the all-taps kernel covers are QUEUED (their dy / x / statistics operands must stay alive and unmodified), and

@@ -2416,6 +2416,8 @@ int rldm_train_defer_reduce(int on) {
 
 int rldm_train_flush_reduce(void) { return flush_reduce(); }
 
+int rldm_train_reduce_pending(void) { return g_red.part ? 1 : 0; }
+
 static TrFuse to_device_fuse(const rldm_train_fuse* fu, int Cin, int N) {
     TrFuse f{};
     if (!fu) { f.C0 = Cin; return f; }

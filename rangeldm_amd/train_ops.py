@@ -439,6 +439,11 @@ def flush_reduce():
     _chk(_lib.lib().rldm_train_flush_reduce(), "rldm_train_flush_reduce")
 
 
+def reduce_pending():
+    """True while a deferred weight-gradient reduction waits for a conv launch to ride on (tests)."""
+    return bool(_lib.lib().rldm_train_reduce_pending())
+
+
 def wgrad_group(on):
     """Queue the all-taps weight gradients instead of launching them (rldm_train_wgrad_group); off: flush."""
     _chk(_lib.lib().rldm_train_wgrad_group(1 if on else 0), "rldm_train_wgrad_group")

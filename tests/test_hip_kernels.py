@@ -9,7 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import ops
-from tests.hip_util import bf16r, rel_l2, hip_conv, hip_attention, hip_attention_qkv, hip_conv_stats
+from tests.hip_util import bf16r, rel_l2, hip_conv, hip_attention, hip_attention_qkv, hip_conv_stats, assert_banded_rel_l2
 
 pytestmark = pytest.mark.gpu
 TOL_Q, TOL_F = 4e-3, 2e-2
@@ -165,6 +165,8 @@ def test_conv_gn_silu_concat_temb_residual(C0, C1, Cout, W, H, conv_flags):
 
     assert rel_l2(y, ref(bf16r)) < TOL_Q
     assert rel_l2(y, ref(lambda t: t)) < TOL_F
+    # band by band: one image's GroupNorm statistics, the wrap seam, the zero-padded beams, the last image
+    assert_banded_rel_l2(y, ref(bf16r), TOL_Q, groups=32, what=f"{(C0, C1, Cout, W, H)} flags {conv_flags}")
 
 
 @pytest.fixture(params=[0, 1 << 25, 1 << 24], ids=["default", "runs-of-8-workgroups", "per-tile-kernel"])
@@ -196,6 +198,7 @@ def test_conv_c64_register_weights(B, W, H, gn, res, regw_flags):
 
     assert rel_l2(y, ref(bf16r)) < TOL_Q
     assert rel_l2(y, ref(lambda t: t)) < TOL_F
+    assert_banded_rel_l2(y, ref(bf16r), TOL_Q, groups=32, what=f"c64 {(B, W, H, gn, res)} flags {regw_flags}")
     # per image and channel: a wrong tile of a run, a stale halo buffer or a lost residual is a local error the L2 norm forgives
     d = (y - ref(bf16r)).abs().amax(dim=(2, 3))
     assert float(d.max()) < 0.05
@@ -252,6 +255,7 @@ def test_conv_out_fp32_nchw(B, W, H, N, flags):
     assert rel_l2(y, ref(bf16r)) < 2e-3
     assert rel_l2(y, ref(lambda t: t)) < TOL_F
     assert float((y - ref(bf16r)).abs().max()) < 0.02
+    assert_banded_rel_l2(y, ref(bf16r), 2e-3, what=f"conv_out {(B, W, H, N)} flags {flags}")
 
 
 @pytest.mark.parametrize("B,W,H,N", [(16, 256, 16, 4), (3, 256, 16, 2), (2, 1024, 8, 4), (1, 1024, 64, 2)])
@@ -279,6 +283,7 @@ def test_unet_output_layer_fp32_nchw(B, W, H, N, route):
     assert rel_l2(y, ref(bf16r)) < 2e-3
     assert rel_l2(y, ref(lambda t: t)) < TOL_F
     assert float((y - ref(bf16r)).abs().max()) < 0.02
+    assert_banded_rel_l2(y, ref(bf16r), 2e-3, what=f"UNet conv_out {(B, W, H, N)} {route}")
 
 
 @pytest.mark.parametrize("B,W,H", [(4, 512, 64), (2, 128, 16), (3, 64, 32)])
@@ -337,6 +342,7 @@ def test_conv_pointwise_small_route(B, C, N, W, H, gn, res):
 
     assert rel_l2(y, ref(bf16r)) < TOL_Q
     assert rel_l2(y, ref(lambda t: t)) < TOL_F
+    assert_banded_rel_l2(y, ref(bf16r), TOL_Q, groups=32, what=f"pointwise {(B, C, N, W, H, gn, res)}")
 
 
 def test_conv_gn_no_silu_1x1():

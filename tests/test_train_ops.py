@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import ops as o_ops
+from tests.hip_util import assert_banded_rel_l2
 
 pytestmark = pytest.mark.gpu
 TOL_MM = 6e-3
@@ -302,6 +303,11 @@ def test_fused_norm_conv_forward_backward(B, C0, C1, N, W, H, taps, silu):
     assert rel(nchw(dsts[0]), want[:, :C0]) < TOL_MM
     if C1:
         assert rel(nchw(dsts[1]), want[:, C0:] + 0.5) < TOL_MM
+    # band by band (the fused data gradient + gn_backward_apply): per image and GroupNorm group, wrap seam, boundary beams, last image
+    case = (B, C0, C1, N, W, H, taps, silu)
+    assert_banded_rel_l2(nchw(dsts[0]), want[:, :C0], TOL_MM, groups=C0 // (Cin // 32), what=f"gn_backward_apply x0 {case}")
+    if C1:
+        assert_banded_rel_l2(nchw(dsts[1]), want[:, C0:] + 0.5, TOL_MM, groups=C1 // (Cin // 32), what=f"gn_backward_apply x1 {case}")
     assert rel(dg.cpu(), g.grad) < TOL_MM and rel(db.cpu(), b.grad) < TOL_MM
     # weight gradient with the operand rebuilt from the raw sources
     if T.wgrad_fused_ok(srcs, N, taps, gn=gn):
