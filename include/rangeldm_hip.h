@@ -126,6 +126,20 @@ int rldm_sched_ddpm_step(const float coef[5], const float* eps, const float* x, 
 #define RLDM_PRED_SAMPLE 2
 int rldm_sched_step(int sampler_mode, int prediction_type, const float coef[5], const float* model_output, const float* x,
                     const float* noise, float* x_prev, int64_t n, void* stream);
+/* replaces DPMSolverMultistepScheduler.step (diffusers; algorithm_type "dpmsolver++", solver_type "midpoint", order 1 or 2,
+ * final_sigmas_type "zero"): deterministic DPM-Solver++(2M).  Step i of N, sigma_i = sqrt((1-alpha_prod_t)/alpha_prod_t),
+ * alpha_i = 1/sqrt(sigma_i^2+1), s_i = sigma_i*alpha_i, lambda_i = log alpha_i - log s_i (sigma_N = 0, lambda_N = +inf):
+ *   x0 = the RLDM_PRED_* conversion above with sqrt_alpha_t = alpha_i, sqrt_beta_t = s_i
+ *   prev = coef[2]*x0 + coef[3]*x + coef[4]*x0_prev
+ * coef = {alpha_i, s_i, c_x0, c_xt, c_x0prev}; with h = lambda_{i+1} - lambda_i, phi = exp(-h) - 1 (-1 at the last step):
+ *   first order (i == 0, solver_order 1, the last step):  c_x0 = -alpha_{i+1}*phi, c_xt = s_{i+1}/s_i, c_x0prev = 0
+ *   second order, r = (lambda_i - lambda_{i-1})/h:        c_x0 = -alpha_{i+1}*phi*(1 + 1/(2r)), c_xt = s_{i+1}/s_i,
+ *                                                         c_x0prev = alpha_{i+1}*phi/(2r)
+ *   the last row is {alpha, s, 1, 0, 0}: the step returns x0.
+ * x0_history: device fp32 [n], read only when coef[4] != 0 (it holds the previous step's x0), then overwritten with this
+ * step's x0; it must not alias the other tensors.  The same rows are rldm_sampler_config::coef for RLDM_SAMPLER_DPMSOLVER. */
+int rldm_sched_dpmsolver_step(int prediction_type, const float coef[5], const float* model_output, const float* x,
+                              float* x0_history, float* x_prev, int64_t n, void* stream);
 /* replaces DDPMScheduler.add_noise (ldm/train_unconditional.py:498): out = sa[b]*x0 + sb[b]*noise (sa, sb HOST [B]).
  * DDPMScheduler.get_velocity (ldm/train_unconditional.py:508) is the same map: v = sa[b]*noise - sb[b]*x0, i.e. this entry point
  * with (x0, noise) swapped and sb negated (rangeldm_amd/schedulers.py get_velocity). */
@@ -135,6 +149,8 @@ int rldm_sched_add_noise(const float* x0, const float* noise, const float* sqrt_
 /* ---- whole sampling loop (HIP-graph captured) --------------------------------------------------------------- */
 #define RLDM_SAMPLER_DDIM 0   /* eta = 0 DDIM  (DDIMPipelineRange, ldm/pipelines.py:144-258; BASELINE metric) */
 #define RLDM_SAMPLER_DDPM 1   /* strided ancestral DDPM (LDMPipelineRange as shipped, ldm/pipelines.py:282-383) */
+#define RLDM_SAMPLER_DPMSOLVER 2   /* DPM-Solver++(2M), rows of rldm_sched_dpmsolver_step; each lane keeps its x0 history on the
+                                    * device, so rldm_sample takes no step_noise (NULL) and no state carries between calls */
 
 typedef struct rldm_sampler_config {
     int32_t batch;            /* per-GPU batch                                                                */
@@ -142,7 +158,7 @@ typedef struct rldm_sampler_config {
     int32_t mode;             /* RLDM_SAMPLER_*                                                               */
     int32_t pos_encoding;     /* extra constant channel: 1 at azimuth 0 (ldm/pipelines.py:229-232,346-349)     */
     int32_t cond_channels;    /* channels of the per-step concatenated condition (ldm/pipelines.py:498), or 0  */
-    /* per-step scheduler coefficients, HOST, [num_steps][5] in the layout of rldm_sched_{ddim,ddpm}_step      */
+    /* per-step scheduler coefficients, HOST, [num_steps][5] in the layout of rldm_sched_{ddim,ddpm,dpmsolver}_step */
     const float* coef;
     /* timesteps, HOST int64 [num_steps] (scheduler.timesteps)                                                 */
     const int64_t* timesteps;
@@ -157,7 +173,7 @@ typedef struct rldm_sampler_config {
 int rldm_sampler_create(rldm_unet* unet, rldm_vae* vae, const rldm_sampler_config* cfg, rldm_sampler** out);
 void rldm_sampler_destroy(rldm_sampler* s);
 /* replaces the loop + decode of ldm/pipelines.py:353-367 (:496-507 with cond, :234-246 without VAE).
- * x_T: device fp32 [B, out_ch, W, H]; step_noise: device fp32 [num_steps, B, out_ch, W, H] or NULL (DDIM);
+ * x_T: device fp32 [B, out_ch, W, H]; step_noise: device fp32 [num_steps, B, out_ch, W, H] (DDPM) or NULL (DDIM, DPMSOLVER);
  * cond: device fp32 [B, cond_channels, W, H] or NULL; images: device fp32 [B, 2, 4W, 4H] (or the final x_0 when
  * the sampler has no VAE); latents_out: optional device fp32 [B, out_ch, W, H] receiving the final latent. */
 int rldm_sample(rldm_sampler* s, const float* x_T, const float* step_noise, const float* cond, float* images,

@@ -7,6 +7,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # RLDM_LIB selects another build of the same library (tools/: the -DRLDM_ABLATE timeline build); never a fallback
 LIB_PATH = os.environ.get("RLDM_LIB") or os.path.join(_HERE, "librangeldm_hip.so")
 RLDM_MAX_LEVELS = 8
+# rldm_sampler_config::mode (RLDM_SAMPLER_*)
+RLDM_SAMPLER_DDIM, RLDM_SAMPLER_DDPM, RLDM_SAMPLER_DPMSOLVER = 0, 1, 2
 
 
 class UNetConfigC(C.Structure):
@@ -92,6 +94,7 @@ PROTOTYPES = {
     "rldm_sched_ddim_step": (C.c_int, [C.POINTER(C.c_float), _P, _P, _P, _P, C.c_int64, _P]),
     "rldm_sched_ddpm_step": (C.c_int, [C.POINTER(C.c_float), _P, _P, _P, _P, C.c_int64, _P]),
     "rldm_sched_step": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_float), _P, _P, _P, _P, C.c_int64, _P]),
+    "rldm_sched_dpmsolver_step": (C.c_int, [C.c_int, C.POINTER(C.c_float), _P, _P, _P, _P, C.c_int64, _P]),
     "rldm_sched_add_noise": (C.c_int, [_P, _P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int64, _P, _P]),
     "rldm_sampler_create": (C.c_int, [_P, _P, C.POINTER(SamplerConfigC), C.POINTER(_P)]),
     "rldm_sampler_destroy": (None, [_P]),

@@ -679,11 +679,13 @@ __global__ void __launch_bounds__(64 * NW, 1) conv_igemm_kernel(const ConvParams
         const bool sched = p.sch.coef_table != nullptr;
         float c0 = 1.f, c1 = 0.f, c2 = 0.f, c3 = 0.f, c4 = 0.f;
         const float* nz = nullptr;
+        float* hist = nullptr;
         if (sched) {
             const int step = *p.sch.step_ptr;
             const float* c = p.sch.coef_table + 5 * step;
             c0 = c[0]; c1 = c[1]; c2 = c[2]; c3 = c[3]; c4 = c[4];
             if (p.sch.noise && c4 != 0.f) nz = p.sch.noise + (size_t)step * p.sch.noise_step_stride;
+            hist = sched_history(p.sch.mode, p.sch.noise);
         }
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
@@ -702,8 +704,10 @@ __global__ void __launch_bounds__(64 * NW, 1) conv_igemm_kernel(const ConvParams
                         p.y_nchw[i] = e;
                         if (sched) {
                             const float x = p.sch.x[i];
-                            float prev = sched_prev(p.sch.mode, c0, c1, c2, c3, x, e);
+                            float x0;
+                            float prev = sched_prev(p.sch.mode, c0, c1, c2, c3, x, e, x0);
                             if (nz) prev += c4 * nz[i];
+                            if (hist) hist[i] = x0;
                             p.sch.x_prev[i] = prev;
                             if (p.sch.pack) p.sch.pack[(((size_t)b * p.Wout + ow) * p.Hout + oh) * p.sch.pack_ld + ch] = f32_to_bf16(prev);
                         }

@@ -153,7 +153,7 @@ int launch_temb(const TembParams& p, hipStream_t stream) {
     return 0;
 }
 
-// ---- scheduler steps (diffusers DDIMScheduler.step / DDPMScheduler.step [3P]) ------------------
+// ---- scheduler steps (diffusers DDIMScheduler.step / DDPMScheduler.step [3P]; DPMSolverMultistepScheduler.step)
 __global__ void __launch_bounds__(256) sched_step_kernel(const SchedParams p) {
     float c0, c1, c2, c3, c4;
     const float* nz = p.noise;
@@ -166,10 +166,13 @@ __global__ void __launch_bounds__(256) sched_step_kernel(const SchedParams p) {
         c0 = p.coef[0]; c1 = p.coef[1]; c2 = p.coef[2]; c3 = p.coef[3]; c4 = p.coef[4];
     }
     const bool use_noise = nz != nullptr && c4 != 0.f;
+    float* const hist = sched_history(p.mode, p.noise);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < p.n; i += (long long)gridDim.x * 256) {
         const float x = p.x[i], e = p.eps[i];
-        float prev = sched_prev(p.mode, c0, c1, c2, c3, x, e);
+        float x0;
+        float prev = sched_prev(p.mode, c0, c1, c2, c3, x, e, x0);
         if (use_noise) prev += c4 * nz[i];
+        if (hist) hist[i] = x0;
         p.x_prev[i] = prev;
     }
 }

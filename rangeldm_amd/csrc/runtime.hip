@@ -3011,6 +3011,7 @@ struct SamplerLane {
     std::unique_ptr<Plan> uplan;                    // private UNet plan (graph-baked pointers)
     std::unique_ptr<Plan> dplan;                    // private VAE decode plan
     DevBuf x, eps, cond, step, image;
+    DevBuf hist;                                    // RLDM_SAMPLER_DPMSOLVER: the previous step's x0 (sized like x)
     hipStream_t stream = nullptr;
     hipEvent_t ev_out = nullptr;
     hipGraphExec_t step_graph = nullptr, decode_graph = nullptr;
@@ -3085,6 +3086,12 @@ static Plan* g_trace_plan = nullptr;
 
 // (rldm_debug_set_flags(1 << 23) at sampler creation keeps the scheduler step and the step counter as launches of their own)
 
+// SchedParams / SchedFuse::mode of a sampler's scheduler step (sched_prev)
+static int sampler_sched_mode(const rldm_sampler* s) {
+    const int m = s->cfg.mode;
+    return (m == RLDM_SAMPLER_DDIM ? 0 : 1) | (s->cfg.prediction_type << 1) | (m == RLDM_SAMPLER_DPMSOLVER ? kSchedMultistep : 0);
+}
+
 // x_T (just copied into the lane's x) as conv_in's input: once per call when the steps' pack_input launch is fused into conv_out
 static int sampler_pack_x(rldm_sampler* s, SamplerLane* ln, hipStream_t st) {
     const PlanIO& io = ln->uplan->io;
@@ -3102,7 +3109,9 @@ static int sampler_pack_x(rldm_sampler* s, SamplerLane* ln, hipStream_t st) {
 
 static int sampler_enqueue_step(rldm_sampler* s, SamplerLane* ln, const float* noise, hipStream_t st) {
     const bool fused = ln->fused_tail;
-    if (fused) ln->uplan->io.sch.noise = noise;        // (the rest of io.sch / io.step_inc: sampler_build_plans)
+    const bool multistep = s->cfg.mode == RLDM_SAMPLER_DPMSOLVER;
+    // (the rest of io.sch / io.step_inc: sampler_build_plans; a multistep sampler's x0 history is fixed there)
+    if (fused && !multistep) ln->uplan->io.sch.noise = noise;
     if ((g_dbg_flags | s->plan_flags) & 8192) {
         if (!g_trace.p) {
             if (g_trace.alloc(4096 * 8)) return 1;
@@ -3114,13 +3123,18 @@ static int sampler_enqueue_step(rldm_sampler* s, SamplerLane* ln, const float* n
     if (fused) return 0;
     SchedParams sp;
     memset(&sp, 0, sizeof(sp));
-    sp.mode = (s->cfg.mode == RLDM_SAMPLER_DDIM ? 0 : 1) | (s->cfg.prediction_type << 1);
+    sp.mode = sampler_sched_mode(s);
     sp.coef_table = s->coef.as<float>();
     sp.step_ptr = ln->step.as<int>();
     sp.eps = ln->eps.as<float>();
     sp.x = ln->x.as<float>();
-    sp.noise = noise;                               // already offset to this lane's first sample
-    sp.noise_step_stride = s->n_latent;             // the caller's tensor is [steps][whole batch][...]
+    if (multistep) {
+        sp.noise = ln->hist.as<float>();            // the lane's x0 history: the same elements every step
+        sp.noise_step_stride = 0;
+    } else {
+        sp.noise = noise;                           // already offset to this lane's first sample
+        sp.noise_step_stride = s->n_latent;         // the caller's tensor is [steps][whole batch][...]
+    }
     sp.x_prev = ln->x.as<float>();
     sp.n = ln->n_latent;
     if (launch_sched_step(sp, st)) return 1;
@@ -3174,10 +3188,15 @@ static int sampler_build_plans(rldm_sampler* s) {
             f.coef_table = s->coef.as<float>();
             f.step_ptr = ln->step.as<int>();
             f.x = ln->x.as<float>();
-            f.noise = nullptr;                          // per call: sampler_enqueue_step
-            f.noise_step_stride = s->n_latent;
             f.x_prev = ln->x.as<float>();
-            f.mode = (s->cfg.mode == RLDM_SAMPLER_DDIM ? 0 : 1) | (s->cfg.prediction_type << 1);
+            f.mode = sampler_sched_mode(s);
+            if (s->cfg.mode == RLDM_SAMPLER_DPMSOLVER) {
+                f.noise = ln->hist.as<float>();         // the lane's x0 history, the same elements every step (no per-call tensor)
+                f.noise_step_stride = 0;
+            } else {
+                f.noise = nullptr;                      // per call: sampler_enqueue_step
+                f.noise_step_stride = s->n_latent;
+            }
             io.step_inc = ln->step.as<int>();
             // ... and the next step's conv_in input: no pack_input launch inside the steps (rldm_debug_set_flags(64) keeps it)
             if (!((g_dbg_flags | s->plan_flags) & 64) && io.xin && io.sample_scale == 1.f) {
@@ -3475,6 +3494,14 @@ int rldm_sched_ddpm_step(const float coef[5], const float* eps, const float* x, 
                          int64_t n, void* stream) {
     return sched_step(1, coef, eps, x, noise, x_prev, n, stream);
 }
+int rldm_sched_dpmsolver_step(int prediction_type, const float coef[5], const float* model_output, const float* x,
+                              float* x0_history, float* x_prev, int64_t n, void* stream) {
+    RLDM_REQUIRE(prediction_type >= RLDM_PRED_EPSILON && prediction_type <= RLDM_PRED_SAMPLE, "unknown prediction type");
+    RLDM_REQUIRE(x0_history != nullptr, "null argument");
+    RLDM_REQUIRE(x0_history != x_prev && x0_history != x && x0_history != model_output, "x0_history must not alias another tensor");
+    // (coef[4] == 0: the history is not read, only overwritten -- sched_step's noise check passes with the pointer set)
+    return sched_step(1 | (prediction_type << 1) | kSchedMultistep, coef, model_output, x, x0_history, x_prev, n, stream);
+}
 int rldm_sched_step(int sampler_mode, int prediction_type, const float coef[5], const float* model_output, const float* x,
                     const float* noise, float* x_prev, int64_t n, void* stream) {
     RLDM_REQUIRE(sampler_mode == RLDM_SAMPLER_DDIM || sampler_mode == RLDM_SAMPLER_DDPM, "unknown sampler mode");
@@ -3513,6 +3540,8 @@ int rldm_sampler_create(rldm_unet* unet, rldm_vae* vae, const rldm_sampler_confi
     RLDM_REQUIRE(!vae || vae->params.finalized, "vae not finalized");
     RLDM_REQUIRE(cfg->batch >= 1 && cfg->num_steps >= 1 && cfg->coef && cfg->timesteps, "bad sampler config");
     RLDM_REQUIRE(cfg->prediction_type >= RLDM_PRED_EPSILON && cfg->prediction_type <= RLDM_PRED_SAMPLE, "bad sampler config: prediction_type");
+    RLDM_REQUIRE(cfg->mode == RLDM_SAMPLER_DDIM || cfg->mode == RLDM_SAMPLER_DDPM || cfg->mode == RLDM_SAMPLER_DPMSOLVER,
+                 "bad sampler config: mode");
     const auto& uc = unet->cfg;
     RLDM_REQUIRE(uc.out_channels + (cfg->pos_encoding ? 1 : 0) + cfg->cond_channels == uc.in_channels,
                  "unet.in_channels != out_channels + pos_encoding + cond_channels (ldm/pipelines.py:351,480)");
@@ -3551,6 +3580,7 @@ int rldm_sampler_create(rldm_unet* unet, rldm_vae* vae, const rldm_sampler_confi
         RLDM_HIP_CHECK(hipStreamCreateWithFlags(&ln->stream, hipStreamNonBlocking));
         RLDM_HIP_CHECK(hipEventCreateWithFlags(&ln->ev_out, hipEventDisableTiming));
         if (ln->x.alloc(ln->n_latent * 4) || ln->eps.alloc(ln->n_latent * 4) || ln->step.alloc(64)) return 1;
+        if (cfg->mode == RLDM_SAMPLER_DPMSOLVER && ln->hist.alloc(ln->n_latent * 4)) return 1;
         if (cfg->cond_channels && ln->cond.alloc((size_t)ln->n_cond * 4)) return 1;
         if (vae && ln->image.alloc(ln->n_image * 4)) return 1;
         s->lanes.push_back(std::move(ln));
@@ -3605,7 +3635,7 @@ int rldm_sample(rldm_sampler* s, const float* x_T, const float* step_noise, cons
     RLDM_REQUIRE(s && x_T, "null argument");
     RLDM_REQUIRE(images || latents_out, "no output requested");
     RLDM_REQUIRE((s->cfg.cond_channels == 0) == (cond == nullptr), "cond tensor does not match sampler.cond_channels");
-    RLDM_REQUIRE(s->cfg.mode == RLDM_SAMPLER_DDIM || step_noise != nullptr, "DDPM sampling needs step_noise");
+    RLDM_REQUIRE(s->cfg.mode != RLDM_SAMPLER_DDPM || step_noise != nullptr, "DDPM sampling needs step_noise");
     hipStream_t caller = reinterpret_cast<hipStream_t>(stream);
     if (s->unet_gen != s->unet->generation || (s->vae && s->vae_gen != s->vae->generation) || !s->unet->params.finalized ||
         (s->vae && !s->vae->params.finalized)) {

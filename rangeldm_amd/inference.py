@@ -13,7 +13,8 @@ none is given, the deterministic synthetic state dict (no checkpoints exist offl
 ldm/inference.py:171-183 writes it: `<idx>.bin` (float32 [N, 4] x, y, z, remission of the returns closer than 90 m),
 `<idx>.png` (8-bit BEV density) and `<idx>_range.png` (8-bit range channel) -- the point cloud, the BEV volume, the depth
 filter and the 8-bit rendering all run on the GPU (rangeldm_amd.range_image); only finished bytes cross PCIe.
-`--save-npy` adds `<idx>.npy`, the raw (2, W, H) fp32 range image.
+`--save-npy` adds `<idx>.npy`, the raw (2, W, H) fp32 range image.  `--scheduler {ddpm,ddim,dpmsolver++}` and `--steps N`
+override the sampler and step count the config runs (e.g. `--scheduler dpmsolver++ --steps 20`).
 """
 import argparse
 import os
@@ -84,6 +85,22 @@ def vae_config_for(y, unet, base_dir):
     return VAEConfig(sample_size=(unet.sample_size[0] * f_, unet.sample_size[1] * f_))
 
 
+SCHEDULER_CHOICES = ("ddpm", "ddim", "dpmsolver++")
+
+
+def make_scheduler(name, sched_cfg):
+    """--scheduler NAME: the scheduler class of that name on the run's scheduler config (None: the defaults)."""
+    from .schedulers import DDIMSchedulerHIP, DDPMSchedulerHIP, DPMSolverMultistepSchedulerHIP
+    cls = {"ddpm": DDPMSchedulerHIP, "ddim": DDIMSchedulerHIP, "dpmsolver++": DPMSolverMultistepSchedulerHIP}[name]
+    return cls(sched_cfg)
+
+
+def add_sampling_args(ap):
+    ap.add_argument("--scheduler", choices=SCHEDULER_CHOICES, default=None,
+                    help="sampler (default: what the config runs; dpmsolver++ = DPM-Solver++(2M), for 20-25 steps)")
+    ap.add_argument("--steps", type=int, default=None, help="num_inference_steps (default: the config's)")
+
+
 def device_step_noise(seed, global_indices, steps, lat_shape, device):
     """[steps][B, C, W, H] ancestral noise, drawn ON THE DEVICE from one generator per GLOBAL sample index (seed and index
     only: independent of rank, world size and batch composition).  The reference draws it from the unseeded global device RNG
@@ -150,6 +167,7 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=20240310)
     ap.add_argument("--ema", action="store_true", help="read <weights>/unet_ema instead of <weights>/unet")
     ap.add_argument("--save-npy", action="store_true", help="also write the raw (2, W, H) fp32 range image")
+    add_sampling_args(ap)
     a = ap.parse_args(argv)
 
     from .params import unet_param_shapes, vae_param_shapes
@@ -161,7 +179,7 @@ def main(argv=None):
 
     cfg = load_config(a.cfg)
     B = a.batch_size or cfg.get("batch", 16)
-    steps = cfg.get("steps", 50)
+    steps = a.steps or cfg.get("steps", 50)
     rank, world, local = D.init_from_env()
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
@@ -186,9 +204,12 @@ def main(argv=None):
         vae = AutoencoderKLHIP(cfg["vae"])
         vae.load_state_dict(vsd)
         # ldm/inference.py:131-136: the LDM branch keeps the DDPM scheduler (strided ancestral sampling)
-        pipe = LDMPipelineRange(vae=vae, unet=unet, scheduler=DDPMSchedulerHIP(sched_cfg),
+        pipe = LDMPipelineRange(vae=vae, unet=unet, scheduler=make_scheduler(a.scheduler or "ddpm", sched_cfg),
                                 pos_encoding=cfg["pos_encoding"])
-    elif cfg.get("ddim", True):
+    elif a.scheduler == "dpmsolver++":
+        # (DDIMPipelineRange forces DDIM, ldm/pipelines.py:135-139: pixel-space DPM-Solver++ runs in DDPMPipelineRange)
+        pipe = DDPMPipelineRange(unet=unet, scheduler=make_scheduler(a.scheduler, sched_cfg))
+    elif a.scheduler == "ddim" or (a.scheduler is None and cfg.get("ddim", True)):
         pipe = DDIMPipelineRange(unet=unet, scheduler=DDIMSchedulerHIP(sched_cfg), pos_encoding=cfg["pos_encoding"])
     else:
         # ldm/inference.py:141-145: ddim False -> DDPMPipelineRange (ancestral sampling in pixel space; it takes no

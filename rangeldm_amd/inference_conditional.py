@@ -25,7 +25,7 @@ import torch
 from . import distributed as D
 from .conditional import downsample_range_image, inpainting_inputs, sparse_input_image
 from .config import PRESETS, UNetConfig, VAEConfig
-from .inference import postprocess, save_png, sensor_for, vae_config_for
+from .inference import add_sampling_args, make_scheduler, postprocess, save_png, sensor_for, vae_config_for
 
 
 def load_conditional_config(cfg):
@@ -95,19 +95,19 @@ def main(argv=None):
     ap.add_argument("--weights", default=None, help="reference-style output_dir with unet/ and vae/ safetensors")
     ap.add_argument("--seed", type=int, default=20240310)
     ap.add_argument("--ema", action="store_true")
+    add_sampling_args(ap)
     a = ap.parse_args(argv)
 
     from .encoders import SparseRangeImageEncoder2
     from .params import unet_param_shapes, vae_param_shapes
     from .pipelines import LDMUpscalePipelineRange
-    from .schedulers import DDPMSchedulerHIP
     from .synth import synth_state_dict
     from .unet import UNet2DModelHIP
     from .vae import AutoencoderKLHIP
 
     cfg = load_conditional_config(a.cfg)
     B = a.batch_size or cfg["batch"]
-    steps = cfg["steps"]
+    steps = a.steps or cfg["steps"]
     rank, world, local = D.init_from_env()
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
@@ -131,7 +131,7 @@ def main(argv=None):
     vae = AutoencoderKLHIP(cfg["vae"])
     vae.load_state_dict(vsd)
     # ldm/inference_conditional.py:121-134: DDPM scheduler (strided ancestral sampling), SparseRangeImageEncoder2 for up-sampling
-    pipe = LDMUpscalePipelineRange(unet=unet, scheduler=DDPMSchedulerHIP(sched_cfg), vae=vae)
+    pipe = LDMUpscalePipelineRange(unet=unet, scheduler=make_scheduler(a.scheduler or "ddpm", sched_cfg), vae=vae)
     condition_encoder = SparseRangeImageEncoder2() if cfg["task"] == "upsample" else None
 
     f = cfg["vae"].downscale

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .schedulers import DDIMSchedulerHIP, DDPMSchedulerHIP, randn_tensor
+from .schedulers import DDIMSchedulerHIP, DDPMSchedulerHIP, DPMSolverMultistepSchedulerHIP, randn_tensor
 
 
 class ImagePipelineOutput:
@@ -22,8 +22,17 @@ class ImagePipelineOutput:
         self.images = images
 
 
+def _sampler_mode(scheduler):
+    """rldm_sampler_config::mode of a scheduler: DDIM, DPM-Solver++, else the (strided ancestral) DDPM step."""
+    if isinstance(scheduler, DDIMSchedulerHIP):
+        return _lib.RLDM_SAMPLER_DDIM
+    if isinstance(scheduler, DPMSolverMultistepSchedulerHIP):
+        return _lib.RLDM_SAMPLER_DPMSOLVER
+    return _lib.RLDM_SAMPLER_DDPM
+
+
 class _FusedSampler:
-    """Owns one rldm_sampler per (batch, steps, mode, pos_encoding, cond_channels, eta)."""
+    """Owns one rldm_sampler per (batch, steps, mode, pos_encoding, cond_channels, eta, schedule)."""
 
     def __init__(self):
         self._cache = {}
@@ -32,19 +41,17 @@ class _FusedSampler:
         # keyed by the model objects themselves (kept alive by the cache entry, so an id is never reused for another
         # model); weights reloaded through load_state_dict are picked up by the library: rldm_sample re-plans and
         # re-captures when the model's generation counter moved (include/rangeldm_hip.h, rldm_unet_finalize)
+        # ... and by the schedule itself (timesteps and coefficient rows): two schedulers of one kind and step count can differ
+        # in their spacing or solver order
         pred = int(getattr(scheduler, "prediction_code", 0))
-        key = (id(unet), id(vae), batch, steps, mode, bool(pos_encoding), cond_channels, float(eta), pred)
+        scheduler.set_timesteps(steps)
+        ts = np.ascontiguousarray(scheduler.timesteps.numpy().astype(np.int64))
+        coef = scheduler.sampler_table(eta if mode == _lib.RLDM_SAMPLER_DDIM else 0.0)
+        key = (id(unet), id(vae), batch, steps, mode, bool(pos_encoding), cond_channels, float(eta), pred, ts.tobytes(),
+               coef.tobytes())
         ent = self._cache.get(key)
         if ent is not None:
             return ent[0]
-        scheduler.set_timesteps(steps)
-        ts = scheduler.timesteps.numpy().astype(np.int64)
-        if mode == 0:
-            coef = np.asarray([scheduler.coefficients(int(t), eta) for t in ts], dtype=np.float32)
-        else:
-            coef = np.asarray([scheduler.coefficients(int(t)) for t in ts], dtype=np.float32)
-        coef = np.ascontiguousarray(coef)
-        ts = np.ascontiguousarray(ts)
         cfg = _lib.SamplerConfigC()
         cfg.batch, cfg.num_steps, cfg.mode = batch, steps, mode
         cfg.pos_encoding = 1 if pos_encoding else 0
@@ -117,8 +124,9 @@ class _PipelineBase:
             vae.save_pretrained(os.path.join(output_dir, "vae"))
         self.scheduler.save_pretrained(os.path.join(output_dir, "scheduler"))
         import json
+        sched = "DPMSolverMultistepScheduler" if isinstance(self.scheduler, DPMSolverMultistepSchedulerHIP) else "DDPMScheduler"
         index = {"_class_name": type(self).__name__, "_diffusers_version": "0.21.0",
-                 "unet": ["diffusers", "UNet2DModel"], "scheduler": ["diffusers", "DDPMScheduler"]}
+                 "unet": ["diffusers", "UNet2DModel"], "scheduler": ["diffusers", sched]}
         if vae is not None:
             index["vae"] = ["diffusers", "AutoencoderKL"]
         with open(os.path.join(output_dir, "model_index.json"), "w") as f:
@@ -176,18 +184,22 @@ class DDPMPipelineRange(_PipelineBase):
         else:
             image = randn_tensor(shape, generator=generator, device=self.device, dtype=torch.float32)
         self.scheduler.set_timesteps(num_inference_steps)
-        if fused and isinstance(self.scheduler, DDPMSchedulerHIP):
-            zs = step_noise if step_noise is not None else self._draw_step_noise(
-                num_inference_steps, self.scheduler.timesteps, shape, generator, self.device)
-            zs = zs.to(self.device, torch.float32).contiguous()
-            h = self._fused.get(self.unet, None, self.scheduler, batch_size, num_inference_steps, 1, False, 0)
+        is_dpm = isinstance(self.scheduler, DPMSolverMultistepSchedulerHIP)
+        if fused and (isinstance(self.scheduler, DDPMSchedulerHIP) or is_dpm):
+            zs = None
+            if not is_dpm:
+                zs = step_noise if step_noise is not None else self._draw_step_noise(
+                    num_inference_steps, self.scheduler.timesteps, shape, generator, self.device)
+                zs = zs.to(self.device, torch.float32).contiguous()
+            h = self._fused.get(self.unet, None, self.scheduler, batch_size, num_inference_steps, _sampler_mode(self.scheduler),
+                                False, 0)
             out = torch.empty_like(image)
             self._fused.run(h, image.contiguous(), zs, None, out, check=kwargs.get("check", True))
             image = out
         else:
             for i, t in enumerate(self.progress_bar(self.scheduler.timesteps)):
                 model_output = self.unet(image, t).sample
-                kw = {"noise": step_noise[i]} if step_noise is not None else {"generator": generator}
+                kw = {"noise": step_noise[i]} if step_noise is not None and not is_dpm else {"generator": generator}
                 image = self.scheduler.step(model_output, t, image, **kw).prev_sample
         return self._finish(image, output_type, return_dict)
 
@@ -242,7 +254,8 @@ class DDIMPipelineRange(_PipelineBase):
 
 class LDMPipelineRange(_PipelineBase):
     """ldm/pipelines.py:261-383 (latent sampling + VAE decode).  With a DDPM scheduler this is the strided ancestral
-    sampler the reference actually runs; pass a DDIMSchedulerHIP for the BASELINE's DDIM eta=0."""
+    sampler the reference actually runs; pass a DDIMSchedulerHIP for the BASELINE's DDIM eta=0, or a
+    DPMSolverMultistepSchedulerHIP for DPM-Solver++(2M) in 20-25 steps."""
 
     def __init__(self, vae, unet, scheduler, pos_encoding=False):
         super().__init__()
@@ -261,10 +274,11 @@ class LDMPipelineRange(_PipelineBase):
         self.scheduler.set_timesteps(num_inference_steps)
         accepts_eta = "eta" in set(inspect.signature(self.scheduler.step).parameters.keys())
         is_ddim = isinstance(self.scheduler, DDIMSchedulerHIP)
+        is_ddpm = isinstance(self.scheduler, DDPMSchedulerHIP)
         if fused and final_only and (not is_ddim or eta == 0.0):
-            mode = 0 if is_ddim else 1
+            mode = _sampler_mode(self.scheduler)
             zs = None
-            if mode == 1:
+            if mode == _lib.RLDM_SAMPLER_DDPM:
                 zs = step_noise if step_noise is not None else self._draw_step_noise(
                     num_inference_steps, self.scheduler.timesteps, shape, generator, self.device)
                 zs = zs.to(self.device, torch.float32).contiguous()
@@ -290,7 +304,7 @@ class LDMPipelineRange(_PipelineBase):
                 latent_model_input = torch.cat([latent_model_input, pos_encoding], dim=1)
             noise_prediction = self.unet(latent_model_input, t).sample
             kw = dict(extra_kwargs)
-            if step_noise is not None and not is_ddim:
+            if step_noise is not None and is_ddpm:
                 kw["noise"] = step_noise[i]
             latents = self.scheduler.step(noise_prediction, t, latents, **kw).prev_sample
         latents = latents / self.vae.config.scaling_factor
@@ -344,10 +358,11 @@ class LDMUpscalePipelineRange(_PipelineBase):
         self.scheduler.set_timesteps(num_inference_steps)
         accepts_eta = "eta" in set(inspect.signature(self.scheduler.step).parameters.keys())
         is_ddim = isinstance(self.scheduler, DDIMSchedulerHIP)
+        is_ddpm = isinstance(self.scheduler, DDPMSchedulerHIP)
         if fused and (not is_ddim or eta == 0.0):
-            mode = 0 if is_ddim else 1
+            mode = _sampler_mode(self.scheduler)
             zs = None
-            if mode == 1:
+            if mode == _lib.RLDM_SAMPLER_DDPM:
                 zs = step_noise if step_noise is not None else self._draw_step_noise(
                     num_inference_steps, self.scheduler.timesteps, shape, generator, self.device)
                 zs = zs.to(self.device, torch.float32).contiguous()
@@ -364,7 +379,7 @@ class LDMUpscalePipelineRange(_PipelineBase):
             latent_model_input = torch.cat([latent_model_input, image], dim=1)
             noise_prediction = self.unet(latent_model_input, t).sample
             kw = dict(extra_kwargs)
-            if step_noise is not None and not is_ddim:
+            if step_noise is not None and is_ddpm:
                 kw["noise"] = step_noise[i]
             latents = self.scheduler.step(noise_prediction, t, latents, **kw).prev_sample
         latents = latents / self.vae.config.scaling_factor

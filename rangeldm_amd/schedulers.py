@@ -1,8 +1,12 @@
 """DDPMSchedulerHIP / DDIMSchedulerHIP -- mirror of the diffusers scheduler surface the reference touches
 (SURVEY.md 8b, Appendix B): set_timesteps, timesteps, step(...).prev_sample, scale_model_input, init_noise_sigma,
 add_noise, alphas_cumprod, config.  Coefficients are computed on the host in fp32 exactly as diffusers does
-(torch.linspace / cumprod in float32); the elementwise update runs in librangeldm_hip."""
+(torch.linspace / cumprod in float32); the elementwise update runs in librangeldm_hip.
+
+DPMSolverMultistepSchedulerHIP -- the few-step ODE solver a diffusers user swaps in with
+`DPMSolverMultistepScheduler.from_config(pipe.scheduler.config)`: deterministic DPM-Solver++(2M)."""
 import ctypes as C
+import math
 from types import SimpleNamespace
 
 import numpy as np
@@ -41,6 +45,7 @@ PREDICTION_TYPES = {"epsilon": 0, "v_prediction": 1, "sample": 2}
 class _SchedulerBase:
     init_noise_sigma = 1.0
     order = 1
+    _SPACINGS = ("leading",)
 
     def __init__(self, config=None, **kwargs):
         if config is None:
@@ -51,7 +56,7 @@ class _SchedulerBase:
             config = SchedulerConfig(**{k: getattr(config, k) for k in SchedulerConfig.__dataclass_fields__
                                         if hasattr(config, k)})
         c = self._cfg = config
-        if c.beta_schedule != "linear" or c.timestep_spacing != "leading":
+        if c.beta_schedule != "linear" or c.timestep_spacing not in self._SPACINGS:
             raise NotImplementedError("only the reference's scheduler config is supported (linear betas, leading spacing)")
         if c.prediction_type not in PREDICTION_TYPES:
             # (the message of diffusers' schedulers; ldm/train_unconditional.py:505-510 accepts epsilon and v_prediction)
@@ -67,6 +72,7 @@ class _SchedulerBase:
         self.final_alpha_cumprod = torch.tensor(1.0) if c.set_alpha_to_one else self.alphas_cumprod[0]
         self.num_inference_steps = None
         self.timesteps = torch.arange(c.num_train_timesteps - 1, -1, -1, dtype=torch.int64)
+        self._table_key = self._table = None
 
     @classmethod
     def from_config(cls, config, **kw):
@@ -109,6 +115,15 @@ class _SchedulerBase:
 
     def scale_model_input(self, sample, timestep=None):
         return sample
+
+    def sampler_table(self, eta=0.0):
+        """[steps][5] fp32 coefficient rows of the current timesteps (rldm_sampler_config::coef), memoised per schedule."""
+        key = (self.timesteps.numpy().tobytes(), float(eta))
+        if self._table_key != key:
+            rows = [self._sampler_row(int(t), eta) for t in self.timesteps]
+            self._table = np.ascontiguousarray(np.asarray(rows, dtype=np.float32).reshape(-1, 5))
+            self._table_key = key
+        return self._table
 
     def _prev_t(self, t):
         n = self.num_inference_steps or self._cfg.num_train_timesteps
@@ -181,6 +196,9 @@ class DDPMSchedulerHIP(_SchedulerBase):
         return [float(a_t ** 0.5), float(b_t ** 0.5), float((a_prev ** 0.5 * cur_b) / b_t),
                 float(cur_a ** 0.5 * b_prev / b_t), float(sigma)]
 
+    def _sampler_row(self, t, eta):
+        return self.coefficients(t)
+
     def step(self, model_output, timestep, sample, generator=None, return_dict=True, noise=None):
         coef = self.coefficients(timestep)
         if coef[4] != 0.0 and noise is None:
@@ -203,6 +221,9 @@ class DDIMSchedulerHIP(_SchedulerBase):
         return [float(a_t ** 0.5), float(b_t ** 0.5), float(a_prev ** 0.5), float((1 - a_prev - std ** 2) ** 0.5),
                 float(std)]
 
+    def _sampler_row(self, t, eta):
+        return self.coefficients(t, eta)
+
     def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None,
              variance_noise=None, return_dict=True):
         coef = self.coefficients(timestep, eta)
@@ -212,3 +233,183 @@ class DDIMSchedulerHIP(_SchedulerBase):
                                  dtype=torch.float32)
         prev = self._launch(0, coef, model_output, sample, noise if coef[4] != 0.0 else None)
         return SchedulerOutput(prev) if return_dict else (prev,)
+
+
+# DPMSolverMultistepScheduler settings: the supported value of each (diffusers' names); any other value raises
+_DPM_FIXED = {"algorithm_type": "dpmsolver++", "solver_type": "midpoint", "lower_order_final": True, "euler_at_final": False,
+              "final_sigmas_type": "zero", "use_karras_sigmas": False, "thresholding": False}
+_DPM_KEYS = tuple(_DPM_FIXED) + ("solver_order", "lambda_min_clipped")
+
+
+def _config_items(config):
+    if config is None:
+        return {}
+    if isinstance(config, dict):
+        return dict(config)
+    if isinstance(config, SchedulerConfig):
+        return config.to_dict()
+    return dict(vars(config))                          # a SimpleNamespace: another scheduler's .config
+
+
+class DPMSolverMultistepSchedulerHIP(_SchedulerBase):
+    """diffusers DPMSolverMultistepScheduler with algorithm_type="dpmsolver++", solver_type="midpoint", solver_order 1 or 2,
+    lower_order_final=True, euler_at_final=False, final_sigmas_type="zero", no Karras sigmas, no thresholding,
+    lambda_min_clipped=-inf: deterministic DPM-Solver++(2M), for the three prediction types.
+
+    Every step is prev = c_x0 * x0 + c_xt * x + c_x0prev * x0_prev, one row [alpha_i, s_i, c_x0, c_xt, c_x0prev] per step
+    (include/rangeldm_hip.h, rldm_sched_dpmsolver_step), computed on the host in float64 from the fp32 alphas_cumprod and stored
+    as fp32.  `step` keeps the step index and the previous x0 (a device tensor); set_timesteps resets both.  The captured
+    sampler (RLDM_SAMPLER_DPMSOLVER) runs the same rows with the history on the device."""
+
+    _SPACINGS = ("leading", "linspace", "trailing")
+
+    def __init__(self, config=None, **kwargs):
+        d = _config_items(config)
+        d.update(kwargs)
+        solver = {"solver_order": 2, "lambda_min_clipped": -math.inf, **_DPM_FIXED}
+        solver.update({k: d[k] for k in _DPM_KEYS if k in d})
+        for k, want in _DPM_FIXED.items():
+            if solver[k] != want:
+                raise NotImplementedError(f"DPMSolverMultistepScheduler {k}={solver[k]!r}: only {want!r} is implemented")
+        if solver["solver_order"] not in (1, 2):
+            raise NotImplementedError(f"DPMSolverMultistepScheduler solver_order={solver['solver_order']!r}: only 1 and 2 are implemented")
+        if solver["lambda_min_clipped"] != -math.inf:
+            raise NotImplementedError(f"DPMSolverMultistepScheduler lambda_min_clipped={solver['lambda_min_clipped']!r}: only -inf is implemented")
+        spacing = d.get("timestep_spacing", "leading")
+        if spacing not in self._SPACINGS:
+            raise NotImplementedError(f"DPMSolverMultistepScheduler timestep_spacing={spacing!r}: only {self._SPACINGS} are implemented")
+        # clip_sample / variance_type / set_alpha_to_one of a DDPM / DDIM config mean nothing to this solver (diffusers ignores them)
+        base = {k: d[k] for k in ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "prediction_type",
+                                  "timestep_spacing", "steps_offset") if k in d}
+        if base.get("beta_schedule", "linear") != "linear":
+            raise NotImplementedError(f"DPMSolverMultistepScheduler beta_schedule={base['beta_schedule']!r}: only 'linear' is implemented")
+        super().__init__(SchedulerConfig(**base))
+        self.solver_order = int(solver["solver_order"])
+        self._solver = solver
+        self.config = SimpleNamespace(**{k: v for k, v in self._cfg.to_dict().items()
+                                         if k not in ("clip_sample", "variance_type", "set_alpha_to_one")}, **solver)
+        self.sigmas = None
+        self._schedules = {}
+        self._reset()
+
+    def _reset(self):
+        self._step_index = None
+        self._hist = None
+        self._have_x0 = False
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    @classmethod
+    def load_config(cls, path, subfolder=None):
+        import json
+        import os
+        from .checkpoint import SCHEDULER_CONFIG_NAME
+        if subfolder:
+            path = os.path.join(path, subfolder)
+        if os.path.isdir(path):
+            path = os.path.join(path, SCHEDULER_CONFIG_NAME)
+        with open(path) as f:
+            d = json.load(f)
+        return {k: v for k, v in d.items() if not k.startswith("_")}
+
+    def save_pretrained(self, path):
+        import json
+        import os
+        from .checkpoint import SCHEDULER_CONFIG_NAME
+        os.makedirs(path, exist_ok=True)
+        d = {"_class_name": "DPMSolverMultistepScheduler", "_diffusers_version": "0.21.0"}
+        d.update(vars(self.config))
+        with open(os.path.join(path, SCHEDULER_CONFIG_NAME), "w") as f:
+            json.dump(d, f, indent=2, sort_keys=True)          # (lambda_min_clipped: -Infinity, as diffusers writes it)
+
+    def _timesteps(self, n):
+        c = self._cfg
+        T = c.num_train_timesteps
+        if c.timestep_spacing == "leading":
+            r = T // (n + 1)
+            ts = (np.arange(0, n + 1) * r).round()[::-1][:-1].copy().astype(np.int64) + c.steps_offset
+        elif c.timestep_spacing == "linspace":
+            ts = np.linspace(0, T - 1, n + 1).round()[::-1][:-1].copy().astype(np.int64)
+        else:
+            ts = np.arange(T, 0, -T / n).round().copy().astype(np.int64) - 1
+        if len(ts) != n or ts.min() < 0 or ts.max() >= T or (n > 1 and np.any(np.diff(ts) >= 0)):
+            raise ValueError(f"{n} inference steps with timestep_spacing={c.timestep_spacing!r} do not give {n} distinct timesteps "
+                             f"in [0, {T})")
+        return ts
+
+    def _rows(self, ts, order):
+        """[N][5] float64 rows [alpha_i, s_i, c_x0, c_xt, c_x0prev] (the class docstring)."""
+        ac = self.alphas_cumprod.numpy().astype(np.float64)[ts]
+        n = len(ts)
+        sigma = np.sqrt((1.0 - ac) / ac)
+        alpha = 1.0 / np.sqrt(sigma ** 2 + 1.0)
+        s = sigma * alpha
+        lam = np.log(alpha) - np.log(s)
+        rows = np.zeros((n, 5), dtype=np.float64)
+        rows[:, 0], rows[:, 1] = alpha, s
+        for i in range(n):
+            if i == n - 1:                                  # sigma_N = 0: first order, phi = -1, the step returns x0
+                rows[i, 2:] = (1.0, 0.0, 0.0)
+                continue
+            h = lam[i + 1] - lam[i]
+            phi = math.exp(-h) - 1.0
+            rows[i, 3] = s[i + 1] / s[i]
+            if i == 0 or order == 1:
+                rows[i, 2] = -alpha[i + 1] * phi
+            else:
+                r = (lam[i] - lam[i - 1]) / h
+                rows[i, 2] = -alpha[i + 1] * phi * (1.0 + 1.0 / (2.0 * r))
+                rows[i, 4] = alpha[i + 1] * phi / (2.0 * r)
+        return rows
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        if num_inference_steps < 1 or num_inference_steps > self._cfg.num_train_timesteps:
+            raise ValueError("num_inference_steps must be in [1, num_train_timesteps]")
+        if num_inference_steps not in self._schedules:      # (the pipelines set the timesteps on every call: computed once)
+            ts = self._timesteps(num_inference_steps)
+            ac = self.alphas_cumprod.numpy().astype(np.float64)[ts]
+            sigmas = torch.from_numpy(np.concatenate([np.sqrt((1.0 - ac) / ac), [0.0]]).astype(np.float32))
+            self._schedules[num_inference_steps] = (ts, sigmas, np.ascontiguousarray(self._rows(ts, self.solver_order).astype(np.float32)),
+                                                    np.ascontiguousarray(self._rows(ts, 1).astype(np.float32)))
+        ts, self.sigmas, self._table, self._table_first = self._schedules[num_inference_steps]
+        self.num_inference_steps = num_inference_steps
+        self.timesteps = torch.from_numpy(ts.copy())
+        self._reset()
+
+    def coefficients(self):
+        """The [num_inference_steps][5] fp32 rows of the current timesteps (rldm_sampler_config::coef, RLDM_SAMPLER_DPMSOLVER)."""
+        if self.num_inference_steps is None:
+            raise ValueError("call set_timesteps first")
+        return self._table
+
+    def sampler_table(self, eta=0.0):
+        return self.coefficients()
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True):
+        if self.num_inference_steps is None:
+            raise ValueError("call set_timesteps first")
+        if self._step_index is None:
+            hit = (self.timesteps == int(timestep)).nonzero()
+            if len(hit) == 0:
+                raise ValueError(f"timestep {int(timestep)} is not in scheduler.timesteps")
+            self._step_index = int(hit[0, 0])
+        i = self._step_index
+        if i >= self.num_inference_steps:
+            raise ValueError("step called more often than num_inference_steps after set_timesteps")
+        e = model_output.to(dtype=torch.float32).contiguous()
+        x = sample.to(device=e.device, dtype=torch.float32).contiguous()
+        if self._hist is None or self._hist.shape != x.shape or self._hist.device != x.device:
+            self._hist = torch.empty_like(x)
+            self._have_x0 = False
+        # without a previous x0 (the first step taken since set_timesteps) the step is first order, as diffusers' lower_order_nums
+        row = self._table[i] if self._have_x0 else self._table_first[i]
+        out = torch.empty_like(x)
+        cf = (C.c_float * 5)(*[float(v) for v in row])
+        _lib.check(_lib.lib().rldm_sched_dpmsolver_step(self.prediction_code, cf, C.c_void_p(e.data_ptr()), C.c_void_p(x.data_ptr()),
+                                                        C.c_void_p(self._hist.data_ptr()), C.c_void_p(out.data_ptr()), x.numel(),
+                                                        _lib.stream_ptr(e.device)), "DPM-Solver++ step")
+        self._have_x0 = True
+        self._step_index = i + 1
+        return SchedulerOutput(out) if return_dict else (out,)
