@@ -520,6 +520,18 @@ int rldm_test_attention(const float* qkv, int B, int L, int C, float* out, void*
  * -> out device fp32 [B][L][C], heads concatenated. */
 int rldm_test_attention_qkv(const float* x, int B, int L, int C, int groups, float eps, const float* gamma, const float* beta,
                             const float* wqkv, const float* bqkv, float* out, void* stream);
+/* (tests) what that launch runs for (B, L, C): route[0] = 2 (attention_qkv2_d8_kernel) or 1 (the first generation,
+ * attention_qkv_d8_kernel), [1] PAIR (two query tiles per wave), [2] HG (heads per workgroup), [3] waves per workgroup,
+ * [4] 1 if the output projection can ride on the launch for the shape alone, [5] ... and on this device's CU count (the seam). */
+int rldm_test_attention_route(int B, int L, int C, int* route);
+/* (tests) the whole block: that launch, then y = x + to_out(o) with to_out_w host [C][C], to_out_b host [C]; mode 0: the output
+ * projection as a launch of its own, 1: behind the seam inside the launch (fails if the device cannot hold every workgroup at
+ * once, or if the seam reports an error), 2: the regular 1x1 conv of the unfused plan.  Needs a shape whose launch can carry the
+ * projection (route[4]).  y device fp32 [B][L][C] (the bf16 output); stats device fp32 [B][L/64][C][2] = the (sum, sum of squares)
+ * partials of y per 64-token block (mode 2: the per-image totals of the conv's partials in block 0, the other blocks zero). */
+int rldm_test_attention_block(const float* x, int B, int L, int C, int groups, float eps, const float* gamma, const float* beta,
+                              const float* wqkv, const float* bqkv, const float* to_out_w, const float* to_out_b, int mode, float* y,
+                              float* stats, void* stream);
 /* HIP-event time of that launch alone on synthetic data (tools/bench_attn.py) */
 int rldm_bench_attention_qkv(int B, int L, int C, int warmup, int iters, float* avg_us, void* stream);
 

@@ -350,6 +350,18 @@ int launch_attention_qkv(const AttnQkvParams& p, hipStream_t stream) {
     return 0;
 }
 
+void attention_qkv_route(int B, int L, int C, int cus, int* route) {
+    const int ntiles = (L + 31) / 32;
+    int HG = 0, waves = 0;
+    const bool gen2 = !g_attn_old && attention_qkv2_geometry(B, L, C, &HG, &waves) == 0;
+    route[0] = gen2 ? 2 : 1;
+    route[1] = gen2 && ntiles >= 32 ? 1 : 0;
+    route[2] = gen2 ? HG : 1;
+    route[3] = gen2 ? waves : (ntiles <= 4 ? 4 : (ntiles <= 8 ? ntiles : 16));
+    route[4] = attention_proj_fusable(B, L, C, -1) ? 1 : 0;
+    route[5] = attention_proj_fusable(B, L, C, cus) ? 1 : 0;
+}
+
 int launch_attention(const AttnParams& p, hipStream_t stream) {
     RLDM_REQUIRE(p.L >= 1 && p.L <= 4096, "attention: token count must be in [1, 4096] (K/V of one head are LDS-resident)");
     RLDM_REQUIRE(p.C % 8 == 0, "attention: channels must be a multiple of head_dim 8");

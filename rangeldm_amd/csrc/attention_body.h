@@ -652,7 +652,7 @@ __device__ __forceinline__ void attention_qkv2_body(const AttnQkvParams& p, cons
     const float dA = __shfl(oA[4], l31);
     const float dB = PAIR ? __shfl(oB[4], l31) : 1.f;
     // a denominator that is not a finite number below 2^120: some score beat the first tile's maximum by ~100 log2 units ->
-    // this wave redoes its tiles with the running-maximum loop (rare; exercised by tests/test_hip_kernels.py)
+    // this wave redoes its tiles with the running-maximum loop (rare; the R3 cases of tests/test_attention_exact.py need it)
     const bool bad = !(dA < 1.3e36f) || (haveB && !(dB < 1.3e36f));
     if (__builtin_amdgcn_ballot_w64(bad) != 0ull) {
 #pragma unroll

@@ -343,6 +343,9 @@ int attention_qkv2_geometry(int B, int L, int C, int* HG, int* waves);
 // ... and whether that launch can carry the output projection (workgroups of an image = 64-pixel blocks, all co-resident)
 bool attention_proj_fusable(int B, int L, int C, int cus);
 int launch_attention_proj(const AttnQkvParams& p, hipStream_t stream);    // the same tail as a launch of its own (proj_counter unused)
+// what launch_attention_qkv runs for (B, L, C) (tests): route[0] = 2 (attention_qkv2_d8_kernel) or 1 (attention_qkv_d8_kernel), [1] PAIR,
+// [2] HG, [3] waves per workgroup, [4] attention_proj_fusable for the shape alone, [5] the same on `cus` compute units
+void attention_qkv_route(int B, int L, int C, int cus, int* route);
 // weight fragments per wave a phase of the persistent launch requests for the NEXT phase (trunk_seam.h; the plan builder's TW_G)
 #ifndef RLDM_TRUNK_PREFETCH
 #define RLDM_TRUNK_PREFETCH 18     /* (round 3: 12 -> 18 = the whole ring of a 3x3 / 256-channel phase: +0.5 %, trunk<0> 201 -> 225 VGPRs) */

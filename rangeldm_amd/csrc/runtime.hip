@@ -4191,6 +4191,96 @@ int rldm_test_attention_qkv(const float* x, int B, int L, int C, int groups, flo
     return 0;
 }
 
+int rldm_test_attention_route(int B, int L, int C, int* route) {
+    RLDM_REQUIRE(route && B >= 1 && L >= 1 && C >= 8, "bad argument");
+    attention_qkv_route(B, L, C, Builder::device_cus(), route);
+    return 0;
+}
+
+// The attention block as the plan runs it: the fused launch, then the output projection y = x + to_out(o) with y's statistics
+// partials, in one of three forms: 0 = launch_attention_proj behind the launch, 1 = the tail behind the seam inside the launch,
+// 2 = the regular 1x1 conv (the unfused plan; stats: per-image totals in partial row 0, the other rows zero).
+int rldm_test_attention_block(const float* x, int B, int L, int C, int groups, float eps, const float* gamma, const float* beta,
+                              const float* wqkv, const float* bqkv, const float* wout, const float* bout, int mode, float* y,
+                              float* stats, void* stream) {
+    RLDM_REQUIRE(x && gamma && beta && wqkv && bqkv && wout && bout && y && stats, "null argument");
+    RLDM_REQUIRE(mode >= 0 && mode <= 2 && C % 16 == 0 && C % groups == 0 && L % 64 == 0, "attention_block: bad argument");
+    RLDM_REQUIRE(attention_proj_fusable(B, L, C, -1), "attention_block: the output projection cannot ride on this shape");
+    RLDM_REQUIRE(mode != 1 || attention_proj_fusable(B, L, C, Builder::device_cus()),
+                 "attention_block: not every workgroup of the launch is resident on this device (no seam)");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const size_t n = (size_t)B * L * C;
+    const int parts = L / 64;
+    std::vector<float> hx(n);
+    RLDM_HIP_CHECK(hipMemcpy(hx.data(), x, n * 4, hipMemcpyDeviceToHost));
+    std::vector<bf16_t> hb(n);
+    for (size_t i = 0; i < n; ++i) hb[i] = f32_to_bf16(hx[i]);
+    AttnCase ac;
+    if (make_attn_case(ac, hb, B, L, C, groups, eps, gamma, beta, wqkv, bqkv)) return 1;
+    std::vector<bf16_t> hy(n);
+    std::vector<float> hs((size_t)B * parts * C * 2, 0.f);
+    if (mode < 2) {
+        // to_out in the tail's A-fragment order (get_fragpacked, one k-group, no residual steps): [C/32][C/16][64 lanes][8]
+        const int nks = C / 16;
+        std::vector<bf16_t> img((size_t)(C / 32) * nks * 512 + 512, 0);
+        for (int o = 0; o < C; ++o)
+            for (int c = 0; c < C; ++c)
+                img[(((size_t)(o / 32) * nks + c / 16) * 64 + ((c % 16) / 8) * 32 + o % 32) * 8 + c % 8] = f32_to_bf16(wout[(size_t)o * C + c]);
+        DevBuf dw, db, dy, dstats, dctr, derr;
+        if (upload(dw, img.data(), img.size() * 2) || upload(db, bout, (size_t)C * 4) || dy.alloc(n * 2) ||
+            dstats.alloc(hs.size() * 4) || dctr.alloc((size_t)B * 32 * 4) || derr.alloc(64))
+            return 1;
+        RLDM_HIP_CHECK(hipMemset(dctr.p, 0, dctr.bytes));
+        RLDM_HIP_CHECK(hipMemset(derr.p, 0, derr.bytes));
+        AttnQkvParams& ap = ac.ap;
+        ap.proj_w = dw.as<bf16_t>(); ap.proj_bias = db.as<float>(); ap.proj_res = ac.dx.as<bf16_t>();
+        ap.proj_y = dy.as<bf16_t>(); ap.proj_stats = dstats.as<float2>();
+        if (mode == 1) {
+            ap.proj_counter = dctr.as<unsigned>();
+            ap.proj_error = derr.as<int>();
+            if (launch_attention_qkv(ap, st)) return 1;
+        } else {
+            AttnQkvParams plain = ap;
+            plain.proj_w = nullptr;
+            if (launch_attention_qkv(plain, st) || launch_attention_proj(ap, st)) return 1;
+        }
+        RLDM_HIP_CHECK(hipStreamSynchronize(st));
+        int err = 0;
+        RLDM_HIP_CHECK(hipMemcpy(&err, derr.p, 4, hipMemcpyDeviceToHost));
+        RLDM_REQUIRE(err == 0, "attention_block: the seam reported error " + std::to_string(err) +
+                                   " (1: a wait gave up, 2: an image's workgroups on several XCDs)");
+        RLDM_HIP_CHECK(hipMemcpy(hy.data(), dy.p, n * 2, hipMemcpyDeviceToHost));
+        RLDM_HIP_CHECK(hipMemcpy(hs.data(), dstats.p, hs.size() * 4, hipMemcpyDeviceToHost));
+    } else {
+        if (launch_attention_qkv(ac.ap, st)) return 1;
+        rldm_conv_desc d;
+        memset(&d, 0, sizeof(d));
+        d.B = B; d.Cin0 = C; d.Win = L / 8; d.Hin = 8; d.Cout = C; d.ksize = 1; d.stride = 1; d.eps = eps;
+        ConvCase cc;
+        if (make_conv_case(cc, &d, wout, bout, nullptr, nullptr, C, false)) return 1;
+        char* base = cc.plan.arena.as<char>();
+        RLDM_HIP_CHECK(hipMemcpyAsync(base + cc.t0.off, ac.dout.p, n * 2, hipMemcpyDeviceToDevice, st));
+        RLDM_HIP_CHECK(hipMemcpyAsync(base + cc.tr.off, ac.dx.p, n * 2, hipMemcpyDeviceToDevice, st));
+        if (cc.plan.run(st)) return 1;
+        RLDM_HIP_CHECK(hipStreamSynchronize(st));
+        RLDM_REQUIRE(cc.out.P > 0, "internal: conv output carries no statistics");
+        RLDM_HIP_CHECK(hipMemcpy(hy.data(), base + cc.out.off, n * 2, hipMemcpyDeviceToHost));
+        std::vector<float2> part((size_t)B * cc.out.P * C);
+        RLDM_HIP_CHECK(hipMemcpy(part.data(), base + cc.out.st_off, part.size() * sizeof(float2), hipMemcpyDeviceToHost));
+        for (int b = 0; b < B; ++b)
+            for (int q = 0; q < cc.out.P; ++q)
+                for (int c = 0; c < C; ++c) {
+                    const float2 v = part[((size_t)b * cc.out.P + q) * C + c];
+                    hs[((size_t)b * parts * C + c) * 2] += v.x;
+                    hs[((size_t)b * parts * C + c) * 2 + 1] += v.y;
+                }
+    }
+    for (size_t i = 0; i < n; ++i) hx[i] = bf16_to_f32(hy[i]);
+    RLDM_HIP_CHECK(hipMemcpy(y, hx.data(), n * 4, hipMemcpyHostToDevice));
+    RLDM_HIP_CHECK(hipMemcpy(stats, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+
 // times the fused attention launch alone (HIP events on `stream`) on synthetic data of the given geometry
 int rldm_bench_attention_qkv(int B, int L, int C, int warmup, int iters, float* avg_us, void* stream) {
     RLDM_REQUIRE(avg_us && iters >= 1 && C % 32 == 0, "bad argument");

@@ -226,3 +226,220 @@ def silu_targets(values):
         assert abs(s - h) <= 0.05 * ulp, f"silu^-1({h}) not resolvable in fp32"
         out.append(b32)
     return torch.tensor(out, dtype=torch.float32)
+
+
+# ---- selective-softmax operands (attention) -----------------------------------------------------------------------------------------
+# Softmax is exact on operands built for it: if every query i gives one set S(i) of 2^j keys equal scores and every other key a
+# score >= `gap` log2 units lower, the output is the mean of those keys' V rows (exact in bf16 for small integer V) on every route,
+# in any tile order and whichever maximum stabilises the exponent.  Scores are in the kernels' log2 units: qh = bf16(q * log2(e) /
+# sqrt(8)) against k.  Per head, dims 0..n-1 carry codes (query: alpha * the target's code, key: its own code, both +-1 and signed /
+# permuted differently per (image, head)), dim 6 a tier (qh = 8) that lifts or sinks whole key tiles, dim 7 a fine tier (qh = 1/4).
+# Every value is a bit pattern of per-token +-1 "bits" through one linear map, so the same q / k / v can also come out of
+# GroupNorm -> to_q / to_k / to_v: x carries each bit and its negation in adjacent channels (every group: mean 0, variance 1).
+QS_INFER = float(np.float32(1.4426950408889634) / np.sqrt(np.float32(8.0)))          # attention.hip / runtime.hip (host, fp32)
+QS_TRAIN = float(np.float32(0.35355339059327373) * np.float32(1.4426950408889634))   # train_attn.hip kScale * kLog2e (fp32)
+R2_MARGINS, R3_MARGINS = (32, 48, 64, 88), (144, 160, 200)
+
+
+def _prescaled(val, qs):
+    """fp32 w with bf16(fp32(w * qs)) == val (what the kernels see after their own scaling and rounding)."""
+    w = np.float32(val / qs)
+    for _ in range(8):
+        got = float(torch.tensor(float(np.float32(w) * np.float32(qs)), dtype=torch.float32).to(torch.bfloat16))
+        if got == val:
+            return float(w)
+        w = np.nextafter(w, np.float32(np.inf) if got < val else np.float32(-np.inf), dtype=np.float32)
+    raise AssertionError(f"no fp32 operand lands on {val} after * {qs} and bf16 rounding")
+
+
+def _int_bits(v, nb):
+    """integer values -> (nb, ...) +-1 bits and the affine map back: v = base + sum_b 2^(b-1) bit_b."""
+    lo = int(v.min())
+    u = (v - lo).long()
+    assert int(u.max()) < 2 ** nb
+    bits = torch.stack([((u >> b) & 1).float() * 2 - 1 for b in range(nb)])
+    w = [2.0 ** (b - 1) for b in range(nb)]
+    return bits, w, lo + sum(w)
+
+
+def selective_operands(B, L, C, regime="R1", seed=0, alpha=16.0, gap=32, margin=None, fused=False):
+    """q, k, v (B, L, C) fp32 with head h = channels 8h .. 8h+7, and qh = bf16(q * log2(e)/sqrt(8)) exactly as given.
+    regime: R1 (every S(i) inside the first key tile), R2 / R3 (S(i) outside it, `margin` log2 units above its maximum: 30..90 = the
+    fast path with P >> 1, >= 140 = the overflow fallback), stair (the maxima of the last <= 12 decoy tiles lie 7.75 and 8.25 log2 units
+    above the running maximum in turn, just under and just over its threshold 8; S(i) in the last, ragged tile).  fused: C/2 bits per token (x has C
+    channels), and the returned dict carries x, gamma, beta, wqkv, bqkv of a GroupNorm -> to_q / to_k / to_v that produces them."""
+    g = torch.Generator().manual_seed(seed)
+    H = C // 8
+    F = C // 2 if fused else 32
+    T = (L + 31) // 32
+    if regime == "stair" and T < 2:
+        regime = "R1"
+    if regime in ("R2", "R3"):
+        assert L > 32, "R2 / R3 need keys outside the first tile"
+        if margin is None:
+            margin = (R2_MARGINS if regime == "R2" else R3_MARGINS)[seed % (4 if regime == "R2" else 3)]
+        assert margin % 8 == 0 and margin >= gap
+    tier_bits = 8 if regime == "stair" else 1
+    cap = {"R1": min(32, L), "R2": L - 32, "R3": L - 32, "stair": L - 32 * (T - 1)}[regime]
+    e = cap.bit_length() - 1
+    n = min(5, (F - tier_bits - 1) // 2, max(0, e - 1))       # j >= 1 where there is room: one selected key has dS = 0
+    j = min(3, e - n)
+    if regime in ("R2", "R3", "stair"):
+        assert 2 ** n <= 32
+    assert n >= 0 and j >= 0 and 2 * n + tier_bits <= F, (L, C, regime)
+    Nc = 2 ** (n + j)
+    # every tier sits below 0 so that the selected score is -8: a key past L read as zeros (score 0) would then win unless masked
+    assert (n * alpha) % 8 == 0
+    off = -int(n * alpha) // 8 - 1
+    # ---- token roles and bits, per image ----
+    bits = torch.randint(0, 2, (B, L, F), generator=g).float() * 2 - 1
+    k6 = torch.zeros(B, L)
+    k7 = torch.zeros(B, L)
+    tb, kb = list(range(n)), list(range(n, 2 * n))
+    tier0 = 2 * n
+    for b in range(B):
+        if regime == "R1":
+            pos = torch.randperm(min(32, L), generator=g)[:Nc]
+        elif regime == "stair":
+            pos = 32 * (T - 1) + torch.randperm(cap, generator=g)[:Nc]
+        else:
+            pos = 32 + torch.randperm(L - 32, generator=g)[:Nc]
+        coded = torch.zeros(L, dtype=torch.bool)
+        coded[pos] = True
+        codes = torch.arange(Nc) % (2 ** n)                     # 2^j keys per code
+        for i, p in enumerate(pos.tolist()):
+            for t in range(n):
+                bits[b, p, kb[t]] = float(((int(codes[i]) >> t) & 1) * 2 - 1)
+        if regime in ("R2", "R3", "stair"):                     # decoy tiles hold every code: their maximum is the tier's, for every query
+            for t0 in range(0, 32 * (T - 1) if regime == "stair" else 32, 32):
+                cov = torch.randperm(32, generator=g) % (2 ** n)
+                for i in range(32):
+                    for t in range(n):
+                        bits[b, t0 + i, kb[t]] = float(((int(cov[i]) >> t) & 1) * 2 - 1)
+        if regime == "stair":
+            u = (torch.arange(T - 1) - max(0, T - 1 - 12)).clamp(min=0)
+            umax = int(u.max())
+            base = -(gap // 8) - (umax + 1) // 2 - 1
+            lvl6 = base + u // 2 + u % 2
+            lvl7 = u // 2 - u % 2
+            k6[b, :32 * (T - 1)] = off + lvl6.repeat_interleave(32).float()
+            k7[b, :32 * (T - 1)] = lvl7.repeat_interleave(32).float()
+            k6[b, 32 * (T - 1):] = off + base                    # fillers of the last tile: the lowest tier
+            k6[b, coded] = off
+        else:
+            drop = (margin if regime in ("R2", "R3") else gap) / 8
+            k6[b] = torch.where(coded, float(off), off - drop)
+    # tier bits (k6 and k7 as affine maps of bits)
+    tier_map = []
+    if regime == "stair":
+        b6, w6, c6 = _int_bits(k6, 5)
+        b7, w7, c7 = _int_bits(k7, 3)
+        for t in range(5):
+            bits[:, :, tier0 + t] = b6[t]
+        for t in range(3):
+            bits[:, :, tier0 + 5 + t] = b7[t]
+        tier_map = [(6, [(tier0 + t, w6[t]) for t in range(5)], c6), (7, [(tier0 + 5 + t, w7[t]) for t in range(3)], c7)]
+    else:
+        lo = float(k6.min())
+        bits[:, :, tier0] = torch.where(k6 == off, 1.0, -1.0)
+        tier_map = [(6, [(tier0, (off - lo) / 2)], (off + lo) / 2), (7, [], 0.0)]
+    pool = tb + list(range(tier0 + tier_bits, F))
+    if len(pool) < 2:
+        pool = list(range(F))
+    # ---- per-head linear maps: rows of q (in qh units), k, v over the bits ----
+    Wq, Wk, Wv = torch.zeros(3, C, F, dtype=torch.float64)
+    bq, bk, bv = torch.zeros(3, C, dtype=torch.float64)
+    for h in range(H):
+        pq = torch.randperm(n, generator=g).tolist()
+        pk = torch.randperm(n, generator=g).tolist()
+        sq = (torch.randint(0, 2, (n,), generator=g) * 2 - 1).tolist()
+        sk = (torch.randint(0, 2, (n,), generator=g) * 2 - 1).tolist()
+        for d in range(n):
+            Wq[8 * h + d, tb[pq[d]]] = alpha * sq[d]
+            Wk[8 * h + d, kb[pk[d]]] = sk[d]
+        for d in range(n, 6):                                   # dims no query reads: keys of one set differ there (dq != 0)
+            Wk[8 * h + d, pool[int(torch.randint(0, len(pool), (1,), generator=g))]] = 1.0
+        bq[8 * h + 6], bq[8 * h + 7] = 8.0, 0.25
+        for d, terms, c0 in tier_map:
+            for bit, w in terms:
+                Wk[8 * h + d, bit] = w
+            bk[8 * h + d] = c0
+        for d in range(8):
+            a, c = torch.randperm(len(pool), generator=g)[:2].tolist()
+            s = float(torch.randint(0, 2, (1,), generator=g) * 2 - 1)
+            Wv[8 * h + d, pool[a]], Wv[8 * h + d, pool[c]], bv[8 * h + d] = s, 2 * s, 4 * s
+    bd = bits.double()
+    qh, k, v = (bd @ W.T + bb for W, bb in ((Wq, bq), (Wk, bk), (Wv, bv)))
+    out = dict(qh=qh.float(), k=k.float(), v=v.float(), n=n, j=j, regime=regime, margin=margin, gap=gap)
+    for t in (out["qh"], out["k"], out["v"]):
+        assert_on_grid(t, 0.25)
+    out["q_infer"] = _from_qh(out["qh"], QS_INFER)
+    out["q_train"] = _from_qh(out["qh"], QS_TRAIN)
+    if fused:
+        x = torch.zeros(B, L, C)
+        x[..., 0::2], x[..., 1::2] = bits, -bits
+        w = torch.zeros(3 * C, C)
+        lut = {}
+        for r in range(C):
+            for m in range(F):
+                if Wq[r, m] != 0:
+                    val = float(Wq[r, m])
+                    w[r, 2 * m] = lut.setdefault(val, _prescaled(val, QS_INFER))
+        w[C:2 * C, 0::2], w[2 * C:, 0::2] = Wk.float(), Wv.float()
+        bias = torch.cat([torch.tensor([_prescaled(float(t), QS_INFER) if t else 0.0 for t in bq]), bk.float(), bv.float()])
+        eps = 1e-5
+        out.update(x=x, wqkv=w, bqkv=bias.float(), eps=eps, groups=32 if C % 64 == 0 else C // 2,   # (an even count per group)
+                   gamma=torch.full((C,), float(np.float32(np.sqrt(1 + eps)))), beta=torch.zeros(C))
+    return out
+
+
+def _from_qh(qh, qs):
+    lut = {v: _prescaled(v, qs) for v in qh.unique().tolist()}
+    return qh.clone().apply_(lambda t: lut[t])
+
+
+def selective_reference(qh, k, v, j=None):
+    """fp64 / exact analysis of selective operands (B, L, C): -> dict(out = mean of V over S(i) (B, L, C), count |S(i)|,
+    smax = the selected score, gap = smax - best other key, margin = smax - maximum of the first key tile (B, H, L)).
+    Scores are exact in fp32 (grid 1/16, < 2^24 units), so they are computed there, a few images at a time."""
+    B, L, C = qh.shape
+    H = C // 8
+    chunk = max(1, 2 ** 24 // (H * L * L))
+    res = {n: [] for n in ("out", "count", "smax", "gap", "margin")}
+    for b0 in range(0, B, chunk):
+        q4 = qh[b0:b0 + chunk].view(-1, L, H, 8).transpose(1, 2)
+        k4 = k[b0:b0 + chunk].view(-1, L, H, 8).transpose(1, 2)
+        v4 = v[b0:b0 + chunk].view(-1, L, H, 8).transpose(1, 2).double()
+        s = q4 @ k4.transpose(-1, -2)
+        smax = s.amax(-1, keepdim=True)
+        sel = s == smax
+        cnt = sel.sum(-1)
+        other = torch.where(sel, torch.tensor(float("-inf")), s).amax(-1)
+        res["out"].append(((sel.double() @ v4) / cnt[..., None].double()).transpose(1, 2).reshape(-1, L, C))
+        res["count"].append(cnt)
+        res["smax"].append(smax[..., 0].double())
+        res["gap"].append((smax[..., 0] - other).double())
+        res["margin"].append((smax[..., 0] - s[..., :min(32, L)].amax(-1)).double())
+    r = {n: torch.cat(t) for n, t in res.items()}
+    if j is not None:
+        assert bool((r["count"] == 2 ** j).all()), "every S(i) must hold 2^j keys"
+    return r
+
+
+def bands_tokens(L):
+    """token bands of a (B, L, C) attention output where a local error hides: first / last query tile, rows past the last full tile."""
+    bands = [("first query tile", slice(0, min(32, L))), ("last query tile", slice(32 * ((L - 1) // 32), L))]
+    if L % 32:
+        bands.append(("rows past the last full tile", slice(L - L % 32, L)))
+    return bands
+
+
+def assert_banded_rel_l2_tokens(y, ref, tol, what=""):
+    """rel-L2 <= tol on the whole (B, L, C) token-major tensor AND on each (image, head), the first / last query tile and the
+    rows past the last full tile."""
+    y, ref = y.detach().double().cpu(), ref.detach().double().cpu()
+    B, L, Cc = y.shape
+    bands = [("whole", (slice(None),))] + [(name, (slice(None), sl)) for name, sl in bands_tokens(L)]
+    bands += [(f"image {b} head {h}", (b, slice(None), slice(8 * h, 8 * h + 8))) for b in range(B) for h in range(Cc // 8)]
+    worst = [f"{name}: {e:.3g}" for name, sl in bands for e in [rel_l2(y[sl], ref[sl])] if not e <= tol]
+    assert not worst, f"{what}: rel-L2 above {tol} on " + ", ".join(worst[:8]) + (f" (+{len(worst) - 8} more)" if len(worst) > 8 else "")

@@ -9,7 +9,8 @@ import torch
 import torch.nn.functional as F
 
 from oracle import ops
-from tests.hip_util import bf16r, rel_l2, hip_conv, hip_attention, hip_attention_qkv, hip_conv_stats, assert_banded_rel_l2
+from tests.hip_util import (bf16r, rel_l2, hip_conv, hip_attention, hip_attention_qkv, hip_conv_stats, assert_banded_rel_l2,
+                            assert_banded_rel_l2_tokens)
 
 pytestmark = pytest.mark.gpu
 TOL_Q, TOL_F = 4e-3, 2e-2
@@ -367,6 +368,7 @@ def test_attention_d8(B, L, C):
     qh, kh, vh = (t.view(B, L, nh, 8).transpose(1, 2) for t in (q, k, v))
     ref = F.scaled_dot_product_attention(qh, kh, vh).transpose(1, 2).reshape(B, L, C)
     assert rel_l2(out, ref) < 1e-2
+    assert_banded_rel_l2_tokens(out, ref, 2e-2, what=f"attention_d8 B{B} L{L} C{C}")
 
 
 def test_attention_large_logits():
@@ -414,6 +416,8 @@ def test_attention_qkv_fused_kernel(B, L, C):
     ref = _attn_qkv_ref(x, gamma, beta, wqkv, bqkv, groups=groups)
     for h in range(C // 8):
         assert rel_l2(out[..., 8 * h:8 * h + 8], ref[..., 8 * h:8 * h + 8]) < 2e-2, h
+    # ... and per image and head, first / last query tile, rows past the last full tile
+    assert_banded_rel_l2_tokens(out, ref, 2e-2, what=f"attention_qkv B{B} L{L} C{C}")
 
 
 def test_attention_qkv_dominant_key():

@@ -13,7 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import ops as o_ops
-from tests.hip_util import assert_banded_rel_l2
+from tests.hip_util import assert_banded_rel_l2, assert_banded_rel_l2_tokens
 
 pytestmark = pytest.mark.gpu
 TOL_MM = 6e-3
@@ -163,6 +163,10 @@ def test_attention_forward_backward(B, L, C):
         assert float((lse.cpu() - lse_ref).abs().max()) < 8e-2
         gt = max(tol, 8e-3)
         assert rel(dq, gq) < gt and rel(dk, gk) < gt and rel(dv, gv) < gt, (gt, rel(dq, gq), rel(dk, gk), rel(dv, gv))
+        # per image and head, first / last query tile and rows past the last full tile (lse: per row above), at twice the gate:
+        # a band of a few rows scatters more than the whole tensor (as the per-head gate of test_attention_qkv_fused_kernel)
+        for name, y, r, t in (("o", o, ref, tol), ("dq", dq, gq, gt), ("dk", dk, gk, gt), ("dv", dv, gv, gt)):
+            assert_banded_rel_l2_tokens(y, r, 2 * t, what=f"{name} B{B} L{L} C{C} tol {tol}")
 
 
 @pytest.mark.parametrize("B,K,N", [(8, 512, 4352), (2, 128, 96), (16, 4352, 512), (3, 40, 24)])
