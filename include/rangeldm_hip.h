@@ -269,6 +269,32 @@ int rldm_hist_spectral_sq(const uint32_t* hx, int nx, const uint32_t* hy, int ny
  * out4 HOST doubles = {s1, s2, cross, s1 + s2 - 2 cross} (the call synchronises the stream). */
 int rldm_hist_mmd(const uint32_t* hx, int nx, const uint32_t* hy, int ny, int bins, float sigma, double* out4, void* stream);
 
+/* ---- reconstruction metrics (rangeldm_amd/csrc/chamfer.hip) ------------------------------------------------------ */
+/* pytorch3d.loss.chamfer_distance (ldm/convert_vae.py:262-271), first half: for a ragged batch of cloud PAIRS
+ * (pair p = x[x_offsets[p] .. x_offsets[p+1]) against y[y_offsets[p] .. y_offsets[p+1]); device fp32 [n][stride >= 3], only
+ * xyz read; device int32 offsets [num_pairs + 1], starting at 0) the squared distance of every point to its nearest
+ * neighbour in the other cloud: x_nn_d2 device fp32 [x_offsets[num_pairs]], y_nn_d2 likewise.  d^2 = ((dx*dx + dy*dy) +
+ * dz*dz) in fp32 without contraction: each minimum is bit-equal to that expression evaluated on the CPU.  Every cloud must
+ * be non-empty; non-finite coordinates give unspecified results.  The call synchronises the stream. */
+int rldm_chamfer_nn(const float* x, const int32_t* x_offsets, int x_stride, const float* y, const int32_t* y_offsets,
+                    int y_stride, int num_pairs, float* x_nn_d2, float* y_nn_d2, void* stream);
+/* second half (point_reduction="mean"): per pair the fp64 mean of each direction, x_mean / y_mean device fp64 [num_pairs];
+ * a fixed-order reduction (bit-identical run to run).  CD of pair p = x_mean[p] + y_mean[p]. */
+int rldm_chamfer_mean(const float* x_nn_d2, const int32_t* x_offsets, const float* y_nn_d2, const int32_t* y_offsets,
+                      int num_pairs, double* x_mean, double* y_mean, void* stream);
+/* Range-image errors (ldm/convert_vae.py:236-247 MAE / PSNR; metrics/metrics/mae.py:45-117 range MAE): a, b device fp32
+ * (B, C, W, H), C <= 8.  Per image, over the channels of channel_mask and the azimuth columns (w0 + k) mod W,
+ * k in [0, w1 - w0) (0 <= w0 < W, w0 < w1 <= w0 + W: the window may wrap past the seam), with v -> v * scale[c] + shift[c]
+ * (scale / shift HOST fp32 [C]) applied to both images in fp64: abs_sum / sq_sum device fp64 [B] = sum |a' - b'| and
+ * sum (a' - b')^2, fixed-order reductions.  The caller divides by the pixel count. */
+int rldm_range_errors(const float* a, const float* b, int B, int C, int W, int H, int channel_mask, const float* scale,
+                      const float* shift, int w0, int w1, double* abs_sum, double* sq_sum, void* stream);
+#define RLDM_UPSAMPLE_NEAREST 0   /* cv2 INTER_NEAREST: source row floor(r / rate) */
+#define RLDM_UPSAMPLE_BICUBIC 1   /* cv2 INTER_CUBIC restated: src = (r + 0.5) / rate - 0.5, Keys A = -0.75, rows clamped */
+/* The beam-upsampling baselines of metrics/metrics/mae.py:61-81 (cv2.resize(target[::rate], fx=1, fy=rate)): src device
+ * fp32 (B, C, W, Hs) -> dst device fp32 (B, C, W, Hs * rate) along the beam (last) axis. */
+int rldm_beam_upsample(const float* src, int B, int C, int W, int Hs, int rate, int mode, float* dst, void* stream);
+
 /* ---- UNet training step (rangeldm_amd/csrc/train.hip; ldm/train_unconditional.py:466-558) ----
  * Op-level entry points driven by rangeldm_amd/training.py (the autograd tape is host-side).  Every tensor is device
  * fp32, activations / gradients channels-last [B][W][H][C] (W wraps, H zero-pads); GEMM operands are rounded to bf16 into

@@ -120,6 +120,14 @@ PROTOTYPES = {
     "rldm_hist_jsd": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_double), _P]),
     "rldm_hist_spectral_sq": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rldm_hist_mmd": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_double), _P]),
+    # pytorch3d.loss.chamfer_distance as ldm/convert_vae.py:262-271 calls it (nearest squared distances, then per-pair means)
+    "rldm_chamfer_nn": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "rldm_chamfer_mean": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P]),
+    # MAE / PSNR of ldm/convert_vae.py:236-247 and the range MAE of metrics/metrics/mae.py:45-117
+    "rldm_range_errors": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
+                                    C.POINTER(C.c_float), C.c_int, C.c_int, _P, _P, _P]),
+    # cv2.resize(target[::rate], fx=1, fy=rate, INTER_NEAREST / INTER_CUBIC) baselines, metrics/metrics/mae.py:61-81
+    "rldm_beam_upsample": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rldm_train_conv": (C.c_int, [C.POINTER(TrainConvDescC), _P, _P, _P, _P, C.c_int, _P, _P, C.c_int, _P]),
     "rldm_train_conv_splits": (C.c_int, [C.POINTER(TrainConvDescC), C.c_int]),
     "rldm_train_wgrad": (C.c_int, [C.POINTER(TrainConvDescC), _P, _P, _P, _P]),

@@ -1,0 +1,330 @@
+"""Reconstruction evaluation on the MI355X: score what the VAE and the conditional sampler reconstruct.
+
+    python -m rangeldm_amd.evaluate vae --weights outputs/RangeLDM --samples 1000 --batch-size 4 [--input DIR]
+    python -m rangeldm_amd.evaluate densification --exp outputs/upsample/generated [--cfg upsample]
+    python -m rangeldm_amd.evaluate inpainting --exp outputs/inpainting/generated [--cfg inpainting]
+    python -m rangeldm_amd.evaluate chamfer A_DIR B_DIR
+
+Every command prints one JSON object on stdout (`--json PATH` also writes it).  Under `torch.distributed.run` the work is
+sharded over the ranks and rank 0 reduces and prints.  The arithmetic runs in librangeldm_hip (rangeldm_amd/csrc/chamfer.hip
+and lidar.hip); Chamfer distance (CD) is pytorch3d.loss.chamfer_distance's default: per pair
+mean_x min_y |x - y|^2 + mean_y min_x |x - y|^2 over xyz.
+
+  vae            ldm/convert_vae.py:221-271: the round trip `vae(batch).sample` over the test range images (`--input DIR` of
+                 (2, W, H) .npy files, else the synthetic batch of inference_conditional.load_batch); MAE and PSNR per image
+                 on channel 0 mapped to (x * std + mean) / range_fill_value[0] and channel 1 as is, averaged over images;
+                 CD between filter_points(to_pc_torch(.), 70) of input and reconstruction.
+  densification  metrics/metrics/mae.py:45-89 (`metric.py --mae`) on the layout inference_conditional writes: result
+                 `<j>_seed_<s>.bin` against target `<j>_seed_0.bin`, both re-projected with the KITTI sensor's project();
+                 range MAE in metres over all W x H pixels and CD, for ours and the nearest / bicubic beam-upsampling
+                 baselines built from every `rate`-th beam of the target.
+  inpainting     mae.py:91-117 (`metric.py --inpainting_mae`): range MAE in metres over the config's masked azimuth span,
+                 with the reference's denominator (files x W x H, mae.py:111) and per masked pixel; and CD.
+  chamfer        mean CD over the .bin files of two folders, paired by name.
+
+Only the linear range normalisation (x * std + mean, every shipped config) is supported: `log` / `inverse` sensors raise
+NotImplementedError.  nuScenes `.bin` files carry no ring column, so they cannot be re-projected: nuScenes raises too.
+"""
+import argparse
+import glob
+import json
+import math
+import os
+import re
+
+import numpy as np
+import torch
+
+from . import distributed as D
+
+_RESULT_RE = re.compile(r"^(\d+)_seed_(\d+)\.bin$")
+
+
+# ---- host-side helpers (no GPU) ---------------------------------------------------------------------------------------
+def build_parser():
+    ap = argparse.ArgumentParser(prog="python -m rangeldm_amd.evaluate",
+                                 description="reconstruction metrics (MAE, PSNR, Chamfer distance) on MI355X")
+    sub = ap.add_subparsers(dest="cmd", required=True)
+
+    v = sub.add_parser("vae", help="VAE round trip: MAE, PSNR, CD (ldm/convert_vae.py:193-271)")
+    v.add_argument("--weights", default=None, help="diffusers VAE directory, or a training output_dir holding vae/")
+    v.add_argument("--sgm-ckpt", default=None, help="sgm AutoencodingEngine .ckpt (ldm/convert_vae.py:149-189)")
+    v.add_argument("--sgm-yaml", default=None, help="the yaml the sgm checkpoint was trained with")
+    v.add_argument("--input", default=None, help="directory of (2, W, H) .npy range images (default: synthetic batch)")
+    v.add_argument("--samples", type=int, default=1000)
+    v.add_argument("--batch-size", type=int, default=4)
+    v.add_argument("--seed", type=int, default=20240310)
+
+    for task in ("densification", "inpainting"):
+        t = sub.add_parser(task, help=f"{task} results of inference_conditional against their targets")
+        t.add_argument("--exp", required=True, help=f"directory holding {task}_result/ and {task}_target/")
+        t.add_argument("--cfg", default="upsample" if task == "densification" else "inpainting",
+                       help="preset name or reference yaml (rate / masked fraction, sensor)")
+
+    c = sub.add_parser("chamfer", help="mean CD over .bin files of two folders, paired by name")
+    c.add_argument("a_dir")
+    c.add_argument("b_dir")
+    c.add_argument("--columns", type=int, default=4, help="float32 columns per point in the .bin files")
+
+    for p in (v, *[sub.choices[k] for k in ("densification", "inpainting")], c):
+        p.add_argument("--json", default=None, help="also write the result object to this file")
+    return ap
+
+
+def pair_result_files(result_dir, target_dir):
+    """[(result_path, target_path)] sorted by (j, seed): every `<j>_seed_<s>.bin` of result_dir with `<j>_seed_0.bin` of
+    target_dir (inference_conditional writes the target once, for seed 0).  A result without its target is an error."""
+    found = []
+    for path in glob.glob(os.path.join(result_dir, "*.bin")):
+        m = _RESULT_RE.match(os.path.basename(path))
+        if m:
+            found.append((int(m.group(1)), int(m.group(2)), path))
+    pairs = []
+    for j, s, path in sorted(found):
+        target = os.path.join(target_dir, f"{j}_seed_0.bin")
+        if not os.path.isfile(target):
+            raise FileNotFoundError(f"{path}: no target {target}")
+        pairs.append((path, target))
+    if not pairs:
+        raise FileNotFoundError(f"no <j>_seed_<s>.bin results in {result_dir}")
+    return pairs
+
+
+def pair_by_name(a_dir, b_dir):
+    """[(a_path, b_path)] for the .bin names present in both folders, sorted by name."""
+    a = {os.path.basename(p) for p in glob.glob(os.path.join(a_dir, "*.bin"))}
+    b = {os.path.basename(p) for p in glob.glob(os.path.join(b_dir, "*.bin"))}
+    common = sorted(a & b)
+    if not common:
+        raise FileNotFoundError(f"no .bin file name common to {a_dir} and {b_dir}")
+    return [(os.path.join(a_dir, n), os.path.join(b_dir, n)) for n in common]
+
+
+def range_affine(sensor):
+    """(std, mean) of the sensor's range normalisation: metres = x * std + mean.  Only the linear map is supported."""
+    if getattr(sensor, "log", False) or getattr(sensor, "inverse", False):
+        raise NotImplementedError("range MAE in metres is implemented for the linear normalisation only "
+                                  "(log / inverse sensors are not)")
+    return float(sensor.std), float(sensor.mean)
+
+
+def require_reprojectable(sensor):
+    """The .bin protocol re-projects returns with the sensor's project(): KITTI-360 finds the beam from the inclination;
+    nuScenes needs the ring column, which the written (x, y, z, remission) files do not carry."""
+    from .range_image import point_cloud_to_range_image_nuScenes
+    if isinstance(sensor, point_cloud_to_range_image_nuScenes):
+        raise NotImplementedError("nuScenes .bin files carry no ring column: they cannot be re-projected")
+    return sensor
+
+
+def task_sensor(cfg_arg):
+    """The sensor a conditional config's images come from, with the yaml's `log` / `inverse` switches."""
+    from .inference import sensor_for
+    from .inference_conditional import load_conditional_config
+    cfg = load_conditional_config(cfg_arg)
+    kw = {}
+    if cfg_arg not in ("upsample", "inpainting"):
+        import yaml
+        with open(cfg_arg) as f:
+            y = yaml.safe_load(f)
+        kw = {k: bool(y[k]) for k in ("log", "inverse") if k in y}
+    beams = cfg["unet"].sample_size[1] * cfg["vae"].downscale
+    return cfg, require_reprojectable(sensor_for(beams, **kw))
+
+
+def masked_window(fraction, W, start=0.0):
+    """[w0, w1) azimuth columns of the in-painting mask (ldm/dataset.py:348-362; w1 > W wraps past the seam)."""
+    w0, end = int(start * W), start + fraction
+    return (w0, int(end * W)) if end < 1.0 else (w0, W + int((end - 1.0) * W))
+
+
+def _emit(result, json_path):
+    text = json.dumps(result, sort_keys=True)
+    print(text)
+    if json_path:
+        with open(json_path, "w") as f:
+            f.write(text + "\n")
+
+
+def _sum_over_ranks(values, device):
+    """Element-wise fp64 sum of a list of floats over the ranks (identity on one process)."""
+    t = torch.tensor(values, dtype=torch.float64, device=device)
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t.cpu().tolist()
+
+
+def _load_bin(path, columns, device):
+    return torch.from_numpy(np.fromfile(path, dtype=np.float32).reshape(-1, columns)).to(device)
+
+
+def _chunks(seq, n):
+    for i in range(0, len(seq), n):
+        yield seq[i:i + n]
+
+
+# ---- commands ---------------------------------------------------------------------------------------------------------
+def _load_vae(a):
+    from .vae import AutoencoderKLHIP
+    if a.sgm_ckpt:
+        return AutoencoderKLHIP.from_sgm_checkpoint(a.sgm_ckpt, a.sgm_yaml), "sgm:" + os.path.basename(a.sgm_ckpt)
+    if a.weights:
+        sub = "vae" if os.path.isdir(os.path.join(a.weights, "vae")) else None
+        return AutoencoderKLHIP.from_pretrained(a.weights, subfolder=sub), "diffusers:" + os.path.basename(a.weights)
+    from .config import VAEConfig
+    from .params import vae_param_shapes
+    from .synth import synth_state_dict
+    cfg = VAEConfig()
+    vae = AutoencoderKLHIP(cfg)
+    vae.load_state_dict(synth_state_dict(vae_param_shapes(cfg), seed=a.seed, prefix="vae."))
+    return vae, "synthetic"
+
+
+def cmd_vae(a, rank, world, dev):
+    from .inference import sensor_for
+    from .inference_conditional import load_batch
+    from .metrics import chamfer_pairs, range_errors
+    vae, origin = _load_vae(a)
+    shape = (vae._cfg.in_channels, *vae._cfg.sample_size)
+    files = sorted(glob.glob(os.path.join(a.input, "*.npy")))[:a.samples] if a.input else None
+    total = len(files) if files is not None else a.samples
+    if total == 0:
+        raise ValueError(f"{a.input}: no .npy range images")
+    to_range = sensor_for(shape[2])
+    std, mean = range_affine(to_range)
+    fill = float(to_range.range_fill_value[0])
+    sums = [0.0, 0.0, 0.0, 0.0]                          # MAE, PSNR, CD, images
+    n_batches = (total + a.batch_size - 1) // a.batch_size
+    for b in range(rank, n_batches, world):              # batch b holds global samples [b * bs, (b + 1) * bs)
+        lo, hi = b * a.batch_size, min(total, (b + 1) * a.batch_size)
+        if files is not None:
+            x = torch.from_numpy(np.stack([np.load(f).astype(np.float32) for f in files[lo:hi]]))
+            if tuple(x.shape[1:]) != shape:
+                raise ValueError(f"range images of shape {tuple(x.shape[1:])}, the VAE expects {shape}")
+        else:
+            x = load_batch(None, hi - lo, shape, a.seed + b)
+        x = x.to(dev)
+        rec = vae(x).sample                              # ldm/convert_vae.py:228
+        # :236-247: channel 0 -> (x * std + mean) / range_fill_value[0], channel 1 as is; per-image mean over C x W x H
+        sa, ss, count = range_errors(x, rec, scale=[std / fill, 1.0], shift=[mean / fill, 0.0])
+        mse = (ss / count).cpu().tolist()
+        sums[0] += float((sa / count).sum())
+        sums[1] += sum(10.0 * math.log10(1.0 / m) if m > 0 else math.inf for m in mse)
+        # :249-271: xyz of the returns closer than 70 m, input against reconstruction
+        pin, cin = to_range.filter_points(to_range.to_pc_torch(x), 70.0)
+        pout, cout = to_range.filter_points(to_range.to_pc_torch(rec), 70.0)
+        cin, cout = cin.cpu().tolist(), cout.cpu().tolist()
+        xm, ym = chamfer_pairs([pin[j, :cin[j], :3] for j in range(len(cin))],
+                               [pout[j, :cout[j], :3] for j in range(len(cout))])
+        sums[2] += float((xm + ym).sum())
+        sums[3] += hi - lo
+    mae, psnr, cd, n = _sum_over_ranks(sums, dev)
+    return {"task": "vae", "weights": origin, "samples": int(n), "mae": mae / n, "psnr": psnr / n, "cd": cd / n}
+
+
+def _conditional_pairs(a, task):
+    stem = "densification" if task == "upsample" else "inpainting"
+    return pair_result_files(os.path.join(a.exp, f"{stem}_result"), os.path.join(a.exp, f"{stem}_target"))
+
+
+def cmd_densification(a, rank, world, dev):
+    from .metrics import beam_upsample, chamfer_pairs, range_errors
+    cfg, sensor = task_sensor(a.cfg)
+    if cfg["task"] != "upsample":
+        raise ValueError(f"{a.cfg} is not an up-sampling config")
+    std, mean = range_affine(sensor)
+    rate, lim = cfg["rate"], cfg["range_limit"]
+    pairs = _conditional_pairs(a, "upsample")
+    methods = ("ours", "nearest", "bicubic")
+    abs_sum = {m: 0.0 for m in methods}
+    cd_sum = {m: 0.0 for m in methods}
+    W, H = sensor.width, sensor.H
+    for chunk in _chunks(pairs[rank::world], 32):
+        clouds = {m: [] for m in methods}
+        targets = []
+        for rpath, tpath in chunk:
+            res, tgt = _load_bin(rpath, 4, dev), _load_bin(tpath, 4, dev)
+            img_r, img_t = sensor.project(res)["jpg"][None], sensor.project(tgt)["jpg"][None]
+            # baselines from every rate-th beam of the target starting at beam 0 (`target[::4]`, mae.py:61-81).  The
+            # model's own condition takes beams rate//2, rate//2 + rate, ... (ldm/dataset.py:340-346): a quirk of the
+            # reference, reproduced as it is
+            low = img_t[..., ::rate].contiguous()
+            imgs = {"ours": img_r, "nearest": beam_upsample(low, rate, "nearest"), "bicubic": beam_upsample(low, rate, "bicubic")}
+            for m in methods:
+                sa, _, _ = range_errors(imgs[m], img_t, scale=[std, 1.0], shift=[mean, 0.0], channels=[0])
+                abs_sum[m] += float(sa.sum())
+            targets.append(tgt[:, :3])
+            clouds["ours"].append(res[:, :3])
+            for m in ("nearest", "bicubic"):
+                pts, cnt = sensor.filter_points(sensor.to_pc_torch(imgs[m]), lim)
+                clouds[m].append(pts[0, :int(cnt[0]), :3])
+        for m in methods:
+            xm, ym = chamfer_pairs(clouds[m], targets)
+            cd_sum[m] += float((xm + ym).sum())
+    tot = _sum_over_ranks([abs_sum[m] for m in methods] + [cd_sum[m] for m in methods], dev)
+    n = len(pairs)
+    return {"task": "densification", "pairs": n, "rate": rate,
+            "mae_m": {m: tot[i] / (n * W * H) for i, m in enumerate(methods)},
+            "cd": {m: tot[3 + i] / n for i, m in enumerate(methods)}}
+
+
+def cmd_inpainting(a, rank, world, dev):
+    from .metrics import chamfer_pairs, range_errors
+    cfg, sensor = task_sensor(a.cfg)
+    if cfg["task"] != "inpainting":
+        raise ValueError(f"{a.cfg} is not an in-painting config")
+    std, mean = range_affine(sensor)
+    W, H = sensor.width, sensor.H
+    w0, w1 = masked_window(cfg["fraction"], W)
+    pairs = _conditional_pairs(a, "inpainting")
+    abs_sum = cd_sum = 0.0
+    for chunk in _chunks(pairs[rank::world], 32):
+        res_c, tgt_c = [], []
+        for rpath, tpath in chunk:
+            res, tgt = _load_bin(rpath, 4, dev), _load_bin(tpath, 4, dev)
+            sa, _, _ = range_errors(sensor.project(res)["jpg"][None], sensor.project(tgt)["jpg"][None], scale=[std, 1.0],
+                                    shift=[mean, 0.0], channels=[0], window=(w0, w1))
+            abs_sum += float(sa.sum())
+            res_c.append(res[:, :3])
+            tgt_c.append(tgt[:, :3])
+        xm, ym = chamfer_pairs(res_c, tgt_c)
+        cd_sum += float((xm + ym).sum())
+    abs_sum, cd_sum = _sum_over_ranks([abs_sum, cd_sum], dev)
+    n = len(pairs)
+    return {"task": "inpainting", "pairs": n, "window": [w0, w1],
+            "mae_m": {"reference": abs_sum / (n * W * H),            # mae.py:111: divided by files x W x H (a quirk)
+                      "per_masked_pixel": abs_sum / (n * (w1 - w0) * H)},
+            "cd": cd_sum / n}
+
+
+def cmd_chamfer(a, rank, world, dev):
+    from .metrics import chamfer_pairs
+    pairs = pair_by_name(a.a_dir, a.b_dir)
+    cd = 0.0
+    for chunk in _chunks(pairs[rank::world], 32):
+        xs = [_load_bin(p, a.columns, dev)[:, :3] for p, _ in chunk]
+        ys = [_load_bin(q, a.columns, dev)[:, :3] for _, q in chunk]
+        xm, ym = chamfer_pairs(xs, ys)
+        cd += float((xm + ym).sum())
+    (cd,) = _sum_over_ranks([cd], dev)
+    return {"task": "chamfer", "pairs": len(pairs), "cd": cd / len(pairs)}
+
+
+COMMANDS = {"vae": cmd_vae, "densification": cmd_densification, "inpainting": cmd_inpainting, "chamfer": cmd_chamfer}
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    rank, world, local = D.init_from_env()
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    result = COMMANDS[a.cmd](a, rank, world, dev)
+    if rank == 0:
+        _emit(result, a.json)
+    D.barrier()
+    return result
+
+
+if __name__ == "__main__":
+    main()

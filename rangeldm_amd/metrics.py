@@ -5,6 +5,9 @@ device tensors in, librangeldm_hip.so (rangeldm_amd/csrc/metrics.hip) underneath
     hists = point_cloud_to_histogram(160, 100, clouds)            # list of (n_i, >= 3) device tensors -> (S, 100, 100)
     jsd   = jsd_2d(model_hists, data_hists)
     mmd   = compute_mmd(data_hists, model_hists)                  # gaussian kernel, sigma = 0.5, is_hist=True
+
+Reconstruction metrics (rangeldm_amd/csrc/chamfer.hip): chamfer_distance (pytorch3d call shape), nearest_sq_dists,
+range_errors (MAE / PSNR / range MAE sums) and beam_upsample (the nearest / bicubic baselines).
 """
 import ctypes as C
 
@@ -97,3 +100,152 @@ def evaluate_folders(sample_folder, data_files, nuscenes=False, limit=None):
     model = point_cloud_to_histogram(160, 100, [load_bin(f, 4) for f in samples], lo, hi)
     data = point_cloud_to_histogram(160, 100, [load_bin(f, 5 if nuscenes else 4) for f in data_files[:len(samples)]], lo, hi)
     return {"jsd": jsd_2d(data, model), "mmd": compute_mmd(data, model)}
+
+
+# ---- reconstruction metrics (rangeldm_amd/csrc/chamfer.hip) ---------------------------------------------------------
+def _clouds(x, lengths, name):
+    """Padded (N, P, >= 3) tensor (+ optional lengths) or a list of (n_i, >= 3) tensors -> list of (n_i, k) tensors.
+    Shapes and emptiness are checked before anything touches the device."""
+    if torch.is_tensor(x):
+        if x.dim() != 3 or x.shape[2] < 3:
+            raise ValueError(f"{name} must be (N, P, >= 3), got {tuple(x.shape)}")
+        if lengths is None:
+            clouds = list(x.unbind(0))
+        else:
+            ls = [int(v) for v in torch.as_tensor(lengths).tolist()]
+            if len(ls) != x.shape[0] or any(v > x.shape[1] for v in ls):
+                raise ValueError(f"{name}_lengths do not match {name}")
+            clouds = [x[i, :n] for i, n in enumerate(ls)]
+    else:
+        if lengths is not None:
+            raise ValueError(f"{name}_lengths is only meaningful for a padded tensor")
+        clouds = list(x)
+    if not clouds:
+        raise ValueError(f"{name}: no point clouds")
+    for c in clouds:
+        if c.dim() != 2 or c.shape[1] < 3:
+            raise ValueError(f"every cloud of {name} must be (n, >= 3)")
+        if c.shape[0] == 0:
+            raise ValueError(f"{name} holds an empty point cloud (the Chamfer distance is undefined)")
+    return clouds
+
+
+def _pack(clouds):
+    """list of (n_i, k) device tensors -> (packed (sum n_i, k) fp32, offsets int32 [S + 1] on the device, k)."""
+    for c in clouds:
+        if not c.is_cuda:
+            raise RuntimeError("point clouds must live on the GPU (rangeldm_amd has no CPU path)")
+    k = min(c.shape[1] for c in clouds)
+    pts = torch.cat([c.detach()[:, :k].float() for c in clouds], 0).contiguous()
+    counts = torch.tensor([0] + [c.shape[0] for c in clouds], dtype=torch.int64).cumsum(0)
+    if int(counts[-1]) >= 2 ** 31:
+        raise ValueError("more than 2^31 - 1 points")
+    return pts, counts.to(torch.int32).to(pts.device), k
+
+
+def _nn(x, y, x_lengths, y_lengths):
+    xs, ys = _clouds(x, x_lengths, "x"), _clouds(y, y_lengths, "y")
+    if len(xs) != len(ys):
+        raise ValueError(f"{len(xs)} x clouds against {len(ys)} y clouds")
+    _lib.require_gpu()
+    xp, xo, xk = _pack(xs)
+    yp, yo, yk = _pack(ys)
+    xd = torch.empty(xp.shape[0], dtype=torch.float32, device=xp.device)
+    yd = torch.empty(yp.shape[0], dtype=torch.float32, device=xp.device)
+    _lib.check(_lib.lib().rldm_chamfer_nn(xp.data_ptr(), xo.data_ptr(), xk, yp.data_ptr(), yo.data_ptr(), yk, len(xs),
+                                          xd.data_ptr(), yd.data_ptr(), _lib.stream_ptr(xp.device)), "rldm_chamfer_nn")
+    return xd, xo, yd, yo, len(xs)
+
+
+def nearest_sq_dists(x, y, x_lengths=None, y_lengths=None):
+    """Per point of every cloud, the SQUARED distance to its nearest neighbour in the paired cloud of the other side (xyz
+    only).  Returns (x_nn, y_nn): lists of 1-D fp32 device tensors, one per pair.  Each value is bit-equal to the fp32
+    expression ((dx*dx + dy*dy) + dz*dz), dx = x_q - x_t, minimised over the other cloud."""
+    xd, xo, yd, yo, _ = _nn(x, y, x_lengths, y_lengths)
+    xs, ys = xo.cpu().tolist(), yo.cpu().tolist()
+    return ([xd[a:b] for a, b in zip(xs[:-1], xs[1:])], [yd[a:b] for a, b in zip(ys[:-1], ys[1:])])
+
+
+def chamfer_pairs(x, y, x_lengths=None, y_lengths=None):
+    """(x_mean, y_mean): fp64 device tensors [N] -- per pair the mean over x of min_y d^2 and the mean over y of min_x d^2
+    (fixed-order reductions: bit-identical run to run).  The Chamfer distance of pair p is x_mean[p] + y_mean[p]."""
+    xd, xo, yd, yo, n = _nn(x, y, x_lengths, y_lengths)
+    xm = torch.empty(n, dtype=torch.float64, device=xd.device)
+    ym = torch.empty(n, dtype=torch.float64, device=xd.device)
+    _lib.check(_lib.lib().rldm_chamfer_mean(xd.data_ptr(), xo.data_ptr(), yd.data_ptr(), yo.data_ptr(), n, xm.data_ptr(),
+                                            ym.data_ptr(), _lib.stream_ptr(xd.device)), "rldm_chamfer_mean")
+    return xm, ym
+
+
+def chamfer_distance(x, y, x_lengths=None, y_lengths=None, point_reduction="mean", batch_reduction="mean", norm=2):
+    """pytorch3d.loss.chamfer_distance with its defaults (ldm/convert_vae.py:262-271): padded (N, P, >= 3) tensors with
+    optional lengths, or lists of (n_i, >= 3) device tensors; only xyz is used.  Returns (dist, None) like pytorch3d (no
+    normals).  dist is an fp64 device scalar: batch_reduction "mean" averages the per-pair sums
+    mean_x min_y d^2 + mean_y min_x d^2, "sum" adds them, None returns the (N,) vector."""
+    if point_reduction != "mean" or norm != 2:
+        raise NotImplementedError("only point_reduction='mean', norm=2 (pytorch3d's defaults, the call the reference makes)")
+    if batch_reduction not in ("mean", "sum", None):
+        raise ValueError(f"batch_reduction must be 'mean', 'sum' or None, got {batch_reduction!r}")
+    xm, ym = chamfer_pairs(x, y, x_lengths, y_lengths)
+    per_pair = xm + ym
+    if batch_reduction is None:
+        return per_pair, None
+    return (per_pair.sum() if batch_reduction == "sum" else per_pair.mean()), None
+
+
+def range_errors(a, b, scale, shift=None, channels=None, window=None):
+    """Per image fp64 (sum |a' - b'|, sum (a' - b')^2, pixel count) with v' = v * scale[c] + shift[c] (computed in fp64)
+    over `channels` (default: all) and the azimuth columns [w0, w1) of `window` (default: all W; w1 may exceed W, the window
+    then wraps past the seam).  a, b: (B, C, W, H) device fp32.  Returns (abs_sum (B,) fp64, sq_sum (B,) fp64, count)."""
+    if a.shape != b.shape or a.dim() != 4:
+        raise ValueError(f"a and b must be the same (B, C, W, H) shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    B, Cc, W, H = a.shape
+    channels = list(range(Cc)) if channels is None else sorted(set(int(c) for c in channels))
+    w0, w1 = (0, W) if window is None else (int(window[0]), int(window[1]))
+    sc = (C.c_float * Cc)(*[float(v) for v in (scale if hasattr(scale, "__len__") else [scale] * Cc)])
+    sh = (C.c_float * Cc)(*[float(v) for v in (shift if shift is not None else [0.0] * Cc)])
+    if not a.is_cuda or not b.is_cuda:
+        raise RuntimeError("range images must live on the GPU (rangeldm_amd has no CPU path)")
+    a = a.detach().float().contiguous()
+    b = b.detach().float().contiguous()
+    mask = sum(1 << c for c in channels)
+    sa = torch.empty(B, dtype=torch.float64, device=a.device)
+    ss = torch.empty(B, dtype=torch.float64, device=a.device)
+    _lib.check(_lib.lib().rldm_range_errors(a.data_ptr(), b.data_ptr(), B, Cc, W, H, mask, sc, sh, w0, w1, sa.data_ptr(),
+                                            ss.data_ptr(), _lib.stream_ptr(a.device)), "rldm_range_errors")
+    return sa, ss, len(channels) * (w1 - w0) * H
+
+
+def cubic_weights(frac):
+    """The four fp32 weights of OpenCV's `interpolateCubic` (Keys, A = -0.75) at fraction(s) `frac`, numpy, in its
+    operation order -- the host statement of what beam_upsample(mode="bicubic") computes per output row."""
+    import numpy as np
+    x = np.asarray(frac, dtype=np.float32)
+    A, one = np.float32(-0.75), np.float32(1.0)
+    c0 = ((A * (x + one) - np.float32(5.0) * A) * (x + one) + np.float32(8.0) * A) * (x + one) - np.float32(4.0) * A
+    c1 = ((A + np.float32(2.0)) * x - (A + np.float32(3.0))) * x * x + one
+    c2 = ((A + np.float32(2.0)) * (one - x) - (A + np.float32(3.0))) * (one - x) * (one - x) + one
+    c3 = one - c0 - c1 - c2
+    return np.stack([c0, c1, c2, c3], -1).astype(np.float32)
+
+
+def beam_upsample(images, rate, mode="nearest"):
+    """(B, C, W, Hs) device fp32 -> (B, C, W, Hs * rate) along the beam axis: the baselines of metrics/metrics/mae.py:61-81
+    (`cv2.resize(target[::rate], (0, 0), fx=1.0, fy=rate, interpolation=...)`).
+      nearest: cv2 INTER_NEAREST, source row floor(r / rate).
+      bicubic: cv2 INTER_CUBIC as restated here -- src = (r + 0.5) / rate - 0.5 (in double, then fp32), Keys weights with
+               A = -0.75 in fp32 as OpenCV's interpolateCubic computes them (cubic_weights), source rows clamped to
+               [0, Hs - 1], sum ((w0 s0 + w1 s1) + w2 s2) + w3 s3.  OpenCV is not available to pin this against: it is a
+               restatement of its documented algorithm, not a bit-for-bit reproduction of cv2's output."""
+    if mode not in ("nearest", "bicubic"):
+        raise ValueError(f"mode must be 'nearest' or 'bicubic', got {mode!r}")
+    if images.dim() != 4:
+        raise ValueError(f"images must be (B, C, W, Hs), got {tuple(images.shape)}")
+    if not images.is_cuda:
+        raise RuntimeError("images must live on the GPU (rangeldm_amd has no CPU path)")
+    x = images.detach().float().contiguous()
+    B, Cc, W, Hs = x.shape
+    out = torch.empty((B, Cc, W, Hs * int(rate)), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().rldm_beam_upsample(x.data_ptr(), B, Cc, W, Hs, int(rate), 0 if mode == "nearest" else 1,
+                                             out.data_ptr(), _lib.stream_ptr(x.device)), "rldm_beam_upsample")
+    return out

@@ -1,5 +1,5 @@
 """AutoencoderKLHIP -- mirror of the diffusers `AutoencoderKL` surface the reference touches:
-`vae.decode(z).sample`, `vae.encode(x).latent_dist.sample()`, `vae.config.scaling_factor`.
+`vae.decode(z).sample`, `vae.encode(x).latent_dist.sample()`, `vae.config.scaling_factor`, `vae(x).sample`.
 Accepts diffusers-layout keys (ldm/inference.py:97) or sgm `AutoencodingEngine` keys (mapped as ldm/convert_vae.py does)."""
 import ctypes as C
 from types import SimpleNamespace
@@ -172,6 +172,13 @@ class AutoencoderKLHIP:
         _lib.check(_lib.lib().rldm_vae_encode(self._h, C.c_void_p(x.data_ptr()), B, w, h, C.c_void_p(mom.data_ptr()),
                                               _lib.stream_ptr(self.device)), "rldm_vae_encode")
         return EncoderOutput(DiagonalGaussianDistributionHIP(mom))
+
+    def __call__(self, sample, sample_posterior=False, return_dict=True, generator=None):
+        """diffusers `AutoencoderKL.forward` (the round trip of ldm/convert_vae.py:228, `vae(batch).sample`): encode, take
+        the posterior's mode (or a sample drawn with `generator`), decode."""
+        posterior = self.encode(sample).latent_dist
+        z = posterior.sample(generator=generator) if sample_posterior else posterior.mode()
+        return self.decode(z, return_dict=return_dict)
 
     def decode_flops(self, batch, latent_w, latent_h):
         return float(_lib.lib().rldm_vae_decode_flops(self._h, batch, latent_w, latent_h))
