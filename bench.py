@@ -13,7 +13,10 @@ batch of 16 (whole samples are sharded; no collective on the data path except th
 (4 images per GPU at N = 8), same all-gather; `value` is then global-batch images / time.  Weights are synthetic
 (rangeldm_amd.synth), the architecture and sizes are the reference's.
 
-Rank 0 prints ONE JSON line.  Besides the driver's fields it carries
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes
+--dump-outputs if asked and prints the driver's fields (metric, value, unit, ms_per_step, ..., the `comm` proof that the ranks met).
+`--full` adds the rest, all measured after the timed region (--no-cpu-baseline, --no-pipelined and --no-other-configs each
+drop one part of it):
   roofline     -- dominant kernel: algorithmic FLOPs of its launches / HIP-event time of those launches, measured in this
                   process right after the timed region by an instrumented eager pass on the sampler's stream
   roofline_worst -- the kernel maximising (share of kernel time) x (1 - fraction of its roofline), with its counter traffic ratio
@@ -21,6 +24,7 @@ Rank 0 prints ONE JSON line.  Besides the driver's fields it carries
                   cores on a bounded sample of the same workload (2 warm-ups, median of 3; host_cores / threads / cpu_model stated)
   cpu_baseline_c1 -- BASELINE config 1 in full on the host: RangeDM, 10-step DDIM, batch 1 (the GPU leg is in other_configs)
   fell_back    -- whether any persistent launch failed its self-check during the run (plans rebuilt as one launch per layer)
+  calibration, pipelined, other_configs, roofline.in_graph, comm.allgather_ms -- see main()
 
 `--dump-outputs DIR` writes what the last timed step handed its caller -- the finished range images, all ranks gathered -- as
 DIR/images.npy (float32, rank 0).  Inputs and weights are functions of --seed alone, so two builds run with the same arguments
@@ -462,10 +466,15 @@ def main():
     ap.add_argument("--sampler", choices=["ddim", "ddpm"], default="ddim")
     ap.add_argument("--preset", default="RangeLDM")
     ap.add_argument("--seed", type=int, default=20240310)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pipelined", action="store_true", help="skip the secondary three-requests-in-flight measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else the line can carry: roofline and per-kernel figures, "
+                         "calibration, CPU baselines, the pipelined figure, the other BASELINE configs (off: the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-pipelined", action="store_true",
+                    help="with --full: skip the secondary three-requests-in-flight measurement")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the `other_configs` block (BASELINE configs 1, 3, 4, 5 as short legs after the headline measurement)")
+                    help="with --full: skip the `other_configs` block (BASELINE configs 1, 3, 4, 5 as short legs after the headline "
+                         "measurement)")
     ap.add_argument("--train", action="store_true",
                     help="BASELINE config 5 instead of the headline: the data-parallel training step (tools/bench_train.py, same "
                          "--gpus / --steps / --warmup contract, metric training samples/sec)")
@@ -571,11 +580,11 @@ def main():
     assert torch.isfinite(out).all()
     if rank == 0 and args.dump_outputs:
         dump_outputs(args.dump_outputs, {"images": out})
-    # the exchange step on its own (it is inside the timed region too): one all-gather of a finished batch, HIP events on the
-    # stream it is issued on; and the proof that `world` ranks met -- every rank's id through the same collective path
+    # the proof that `world` ranks met -- every rank's id through the same collective path; and (--full) the exchange step on its
+    # own (it is inside the timed region too): one all-gather of a finished batch, HIP events on the stream it is issued on
     comm = D.comm_info(dev)
     gather_ms = 0.0
-    if world > 1:
+    if world > 1 and args.full:
         img_l = out[rank * B:(rank + 1) * B].contiguous()
         D.all_gather_images(img_l)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -604,9 +613,10 @@ def main():
                        "global_batch": B * world, "batch_per_gpu": B, "inference_steps": S, "sampler": args.sampler,
                        "parallelism": f"sample-sharded x{world}, RCCL all-gather of finished images"},
             # N ranks really met: world / ranks_seen from a collective over the images' own path, the RCCL communicator's view
-            "comm": dict(comm, allgather_ms=round(gather_ms, 4), allgather_bytes_per_rank=int(B * out[0].numel() * 4)),
+            "comm": dict(comm, **({"allgather_ms": round(gather_ms, 4)} if args.full else {}),
+                         allgather_bytes_per_rank=int(B * out[0].numel() * 4)),
         }
-        if True:                                        # (per-GPU figures, measured on rank 0's GPU for every N)
+        if args.full:                                   # (per-GPU figures, measured on rank 0's GPU for every N)
             h = pipe._fused.get(unet, vae, sched, B, S, 0 if args.sampler == "ddim" else 1, p["pos_encoding"], p["cond_channels"])
             rl, kernels, rl_worst = roofline(pipe, h, xs[0], S)
             gflop_per_image = (S * unet.flops(B) + (vae.decode_flops(B, *lat_shape[1:]) if vae else 0.0)) / B / 1e9

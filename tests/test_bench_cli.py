@@ -22,12 +22,13 @@ def _free_port():
     return p
 
 
-def _run_bench(nproc, extra, timeout=900, steps=2, dump=None):
+def _run_bench(nproc, extra, timeout=900, steps=2, dump=None, full=False):
     env = dict(os.environ, RLDM_DIST_BACKEND="gloo", RLDM_DBG_FLAGS=str(1 << 24), HSA_ENABLE_IPC_MODE_LEGACY="0")
     launcher = ([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1",
                  "--master-port", str(_free_port())] if nproc > 1 else [sys.executable])
     cmd = launcher + [os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", str(steps), "--warmup", "1",
-                      "--no-cpu-baseline", "--no-pipelined", "--no-other-configs"] + extra + (["--dump-outputs", dump] if dump else [])
+                      "--no-cpu-baseline", "--no-pipelined", "--no-other-configs"] + (["--full"] if full else []) + extra + \
+        (["--dump-outputs", dump] if dump else [])
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -36,8 +37,9 @@ def _run_bench(nproc, extra, timeout=900, steps=2, dump=None):
 
 
 def test_bench_two_ranks_weak_scaling_line():
-    """`bench.py --gpus 2` as the driver launches it: every rank samples its own batch of 16"""
-    res = _run_bench(2, [])
+    """`bench.py --gpus 2` as the driver launches it: every rank samples its own batch of 16 (with `--full`: the roofline
+    figures are checked too)"""
+    res = _run_bench(2, [], full=True)
     assert res["n_gpus"] == 2 and res["scaling"] == "weak" and res["steps"] == 2 and res["warmup"] == 1
     assert res["comm"]["world"] == 2 and res["comm"]["ranks_seen"] == [0, 1]
     assert res["config"]["global_batch"] == 32 and res["config"]["batch_per_gpu"] == 16
@@ -47,6 +49,18 @@ def test_bench_two_ranks_weak_scaling_line():
     assert res["roofline"]["bound"] == "mfma" and 0 < res["roofline"]["frac"] < 1
     assert res["roofline_worst"]["kernel"] and res["fell_back"] is False
     assert "cpu_baseline" not in res                               # rank 0 at N = 1 only
+
+
+def test_bench_plain_run_prints_the_headline_alone():
+    """`bench.py --gpus 1 --steps K --warmup W` without `--full`: the driver's fields, and none of what only `--full` measures"""
+    res = _run_bench(1, [])
+    assert res["n_gpus"] == 1 and res["steps"] == 2 and res["warmup"] == 1 and res["dtype"] == "bf16"
+    assert res["metric"].startswith("range-images/sec") and res["unit"] == "range-images/sec" and res["higher_is_better"] is True
+    assert abs(res["value"] - 16 * res["steps"] / (res["ms_per_step"] * 1e-3 * res["steps"])) < 1e-6 * res["value"]
+    assert res["comm"]["world"] == 1 and res["comm"]["ranks_seen"] == [0] and "allgather_ms" not in res["comm"]
+    for k in ("roofline", "roofline_worst", "kernels", "fell_back", "calibration", "cpu_baseline", "cpu_baseline_c1", "pipelined",
+              "other_configs"):
+        assert k not in res, k
 
 
 def test_bench_two_ranks_strong_scaling_config3_line():

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kernel table of one bench.py line (stdin): share, launches per batch, average us, TFLOP/s, algorithmic GB/s."""
+"""Per-kernel table of one `bench.py --full` line (stdin): share, launches per batch, average us, TFLOP/s, algorithmic GB/s."""
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(f"{d['value']:.2f} {d['unit']}  ({d['ms_per_step']:.3f} ms per batch)")
