@@ -162,8 +162,8 @@ typedef struct rldm_sampler_config {
     const float* coef;
     /* timesteps, HOST int64 [num_steps] (scheduler.timesteps)                                                 */
     const int64_t* timesteps;
-    /* routing options of THIS sampler's plans: the bits of rldm_debug_set_flags, scoped to the sampler (0: defaults).
-     * 1 << 24 = every layer a launch of its own -- what a host sets for a sampler it knows will share the GPU.         */
+    /* routing options of THIS sampler's plans: RLDM_FLAG_* bits (enum rldm_flag), scoped to the sampler (0: defaults).
+     * RLDM_FLAG_NO_PERSISTENT = every layer a launch of its own -- what a host sets for a sampler it knows will share the GPU. */
     int32_t plan_flags;
     /* RLDM_PRED_*: what the UNet's output means to the scheduler step (scheduler.config.prediction_type)               */
     int32_t prediction_type;
@@ -512,28 +512,42 @@ int rldm_unet_set_plan_flags(rldm_unet* m, int flags);
 int rldm_debug_inject_trunk_error(rldm_sampler* s, int code);
 int rldm_debug_timestamps(unsigned long long* host_out);   /* NULL: enable; else read back [4][64] s_memtime stamps */
 int rldm_debug_block_times(unsigned long long* host_out, int nblocks);   /* ABLATE builds: [start, end] (100 MHz) of every workgroup of the last conv_stream launch */
-/* routing / ablation switches, PROCESS-WIDE, read when a plan is built (RLDM_DBG_FLAGS seeds them): for tuning runs and tests.  A host
- * that wants one sampler / model routed differently uses rldm_sampler_config::plan_flags / rldm_unet_set_plan_flags (same bits, scoped),
- * and the library's own fall-backs are scoped the same way.  The ones a maintainer may need
- * (INTEGRATION.md section 5): 1 << 24 every layer a launch of its own with the persistent launches' tiles (identical results),
- * 1 << 25 ... with the default tiles, 1 << 26 no multi-tile clusters (the 64x4 / 256x16 levels as launches: required when the GPU
- * is shared with other streams), 512 / 1 << 28 only the conv_small / conv_stream clusters off, 1 << 27 gn_apply stays a launch,
- * 1 << 30 the 128x8 conv pairs as 2-phase launches, 64 keeps the sampler's pack_input launch, 1 << 23 keeps the scheduler step
- * a launch, 1 << 20 every GroupNorm on the consumer side.  0 restores the defaults. */
+/* Routing switches, PROCESS-WIDE, read when a plan is built (RLDM_DBG_FLAGS seeds the first word): for tests and tuning runs.  A host
+ * that wants one sampler / model routed differently uses rldm_sampler_config::plan_flags / rldm_unet_set_plan_flags (the same
+ * RLDM_FLAG_* bits, scoped), and the library's own fall-backs are scoped the same way.  0 restores the defaults.  The switches
+ * choose the launches of a plan; they do not reach the kernels (only the -DRLDM_ABLATE timeline build hands the word on). */
+enum rldm_flag {
+    RLDM_FLAG_ATTN_PROJ_LAUNCH = 1 << 7,    /* the attention output projection as a launch of its own                              */
+    RLDM_FLAG_NO_CONV_SMALL    = 1 << 8,    /* no conv_small route                                                                  */
+    RLDM_FLAG_SMALL_128PX      = 1 << 10,   /* the 128x8 level on conv_small's 128-pixel tiles                                      */
+    RLDM_FLAG_NO_STREAM_REGW   = 1 << 11,   /* no conv_stream / conv_c16 / conv_o4 / conv_ds2 / conv_regw route (with
+                                             * RLDM_FLAG_NO_CONV_SMALL: every conv on the generic kernel)                           */
+    RLDM_FLAG_STREAM_ANY_GRID  = 1 << 12,   /* conv_stream wherever it fits, whatever its grid size                                 */
+    RLDM_FLAG_GRAPH_TRACE      = 1 << 13,   /* stamps between the launches of a sampler's step graph (rldm_debug_graph_trace)       */
+    RLDM_FLAG_SMALL_64PX_32X2  = 1 << 19,   /* 32x2 images as one 64-pixel conv_small tile (default: two 32-pixel tiles)            */
+    RLDM_FLAG_CONSUMER_GN      = 1 << 20,   /* every GroupNorm applied by its consumer (no producer-side normalised copies)         */
+    RLDM_FLAG_NO_WIDE_SPLIT    = 1 << 21,   /* concatenations over 512 channels on the generic kernel, not run half by half         */
+    RLDM_FLAG_OWN_IMAGE_COPIES = 1 << 22,   /* every conv that can own its image does, and writes two normalised copies (tests)     */
+    RLDM_FLAG_SCHED_LAUNCH     = 1 << 23,   /* the sampler's scheduler step as launches of their own                                */
+    RLDM_FLAG_NO_PERSISTENT    = 1 << 24,   /* no persistent launches: every layer a launch of its own, same tiles, same results    */
+    RLDM_FLAG_NO_CLUSTERS      = 1 << 26    /* no multi-tile clusters (the 64x4 / 256x16 levels as launches: for a shared GPU)      */
+};
 int rldm_debug_set_flags(int flags);
-/* second word of the same kind (RLDM_DBG_FLAGS2 seeds it), round 4: 1 / 2 / 4 keep the 8-wave conv_stream workgroups at the
- * full-resolution levels / the 128x8 level / the VAE's 64-channel level (default: 4-wave workgroups, two resident per CU), 8 keeps the
- * 4-wave full-resolution convs launches of their own, 16 / 128 keep the round-3 tiles of the 128x8 level / the generic kernel for the first
- * down-sampler, 32 / 64 route to the specialised-wave experiment / the 64-pixel tile wherever it fits (tests); 1 << 24 keeps the VAE
- * decoder's 64 -> 64 convs and conv_out on the per-tile kernels (default: conv_regw.hip -- weights resident in registers, a run of tiles per
- * workgroup), 1 << 25 caps that kernel's grid at 8 runs (tests: runs of several tiles on small images), 1 << 26 makes a test / bench conv of
- * <= 4 output channels an fp32-NCHW output layer like the decoder's conv_out (rldm_test_conv, rldm_bench_conv); 1 << 27 keeps nearest x2 +
- * 3x3 convs as a 3x3 over the up-sampled halo (default: the sub-pixel form -- four 2x2 convs over the input with summed weights), 1 << 28
- * keeps the 256x16 level's sub-pixel up-sampler a launch of its own (default: a phase of that level's persistent launch), 1 << 29 keeps the
- * 16 x 8 tiles with a staged halo ring at the 16- / 8-beam levels (default: tiles as tall as the image). */
+/* second word of the same kind (no environment seed) */
+enum rldm_flag2 {
+    RLDM_FLAG2_STREAM_8WAVE_FULL = 1,       /* full-resolution conv_stream launches keep the 8-wave 256-pixel workgroups            */
+    RLDM_FLAG2_STREAM_8WAVE_128X8 = 2,      /* the 128x8 level keeps the 8-wave 128 x 64 x 4-k-group workgroups                     */
+    RLDM_FLAG2_STREAM_8WAVE_C64 = 4,        /* the VAE's 64-channel level keeps the 8-wave 256 x 64 workgroups                      */
+    RLDM_FLAG2_STREAM_SPEC_WAVES = 32,      /* the 256 x 128 conv_stream tile with specialised matrix / staging waves              */
+    RLDM_FLAG2_STREAM_64PX = 64,            /* the 8 x 8 x 128-channel x 2-k-group conv_stream tile wherever it fits                */
+    RLDM_FLAG2_NO_REGW = 1 << 24,           /* the VAE decoder's 64 -> 64 convs and conv_out on the per-tile kernels, not conv_regw  */
+    RLDM_FLAG2_REGW_CAP8 = 1 << 25,         /* conv_regw's grid capped at 8 runs (runs of several tiles on small test images)      */
+    RLDM_FLAG2_FP32_OUT = 1 << 26,          /* a test / bench conv of <= 4 output channels is an fp32-NCHW output layer            */
+    RLDM_FLAG2_HALO_RING = 1 << 29          /* 16 x 8 conv_stream tiles with a staged halo ring at the 16- / 8-beam levels          */
+};
 int rldm_debug_set_flags2(int flags);
-/* in-graph timeline of the UNet ops of the sampler's step graph (debug flag 8192 set before rldm_sampler_create) */
-int rldm_debug_graph_trace(unsigned long long* stamps, int cap, char* names, size_t names_cap);   /* kernel ablation switches, see ConvParams::dbg */
+/* in-graph timeline of the UNet ops of the sampler's step graph (RLDM_FLAG_GRAPH_TRACE set before rldm_sampler_create) */
+int rldm_debug_graph_trace(unsigned long long* stamps, int cap, char* names, size_t names_cap);
 /* statistics side-output of the conv epilogue (feeds the next GroupNorm): stats device fp32 [B][Cout][2] = per-image
  * (sum, sum of squares) of the bf16 outputs of conv(x0); plain single-input conv only. */
 int rldm_test_conv_stats(const rldm_conv_desc* d, const float* x0, const float* weight, const float* bias, float* stats,

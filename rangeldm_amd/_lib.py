@@ -1,6 +1,7 @@
 """ctypes binding of librangeldm_hip.so (include/rangeldm_hip.h).  The product path has NO fallback: if the HIP
 library is missing or a call fails, a RuntimeError carrying rldm_last_error() is raised."""
 import ctypes as C
+import enum
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -9,6 +10,36 @@ LIB_PATH = os.environ.get("RLDM_LIB") or os.path.join(_HERE, "librangeldm_hip.so
 RLDM_MAX_LEVELS = 8
 # rldm_sampler_config::mode (RLDM_SAMPLER_*)
 RLDM_SAMPLER_DDIM, RLDM_SAMPLER_DDPM, RLDM_SAMPLER_DPMSOLVER = 0, 1, 2
+
+
+class Flag(enum.IntFlag):
+    """Routing switches of rldm_debug_set_flags / plan_flags (enum rldm_flag: Flag.X is RLDM_FLAG_X)."""
+    ATTN_PROJ_LAUNCH = 1 << 7
+    NO_CONV_SMALL = 1 << 8
+    SMALL_128PX = 1 << 10
+    NO_STREAM_REGW = 1 << 11
+    STREAM_ANY_GRID = 1 << 12
+    GRAPH_TRACE = 1 << 13
+    SMALL_64PX_32X2 = 1 << 19
+    CONSUMER_GN = 1 << 20
+    NO_WIDE_SPLIT = 1 << 21
+    OWN_IMAGE_COPIES = 1 << 22
+    SCHED_LAUNCH = 1 << 23
+    NO_PERSISTENT = 1 << 24
+    NO_CLUSTERS = 1 << 26
+
+
+class Flag2(enum.IntFlag):
+    """Routing switches of rldm_debug_set_flags2 (enum rldm_flag2: Flag2.X is RLDM_FLAG2_X)."""
+    STREAM_8WAVE_FULL = 1
+    STREAM_8WAVE_128X8 = 2
+    STREAM_8WAVE_C64 = 4
+    STREAM_SPEC_WAVES = 32
+    STREAM_64PX = 64
+    NO_REGW = 1 << 24
+    REGW_CAP8 = 1 << 25
+    FP32_OUT = 1 << 26
+    HALO_RING = 1 << 29
 
 
 class UNetConfigC(C.Structure):

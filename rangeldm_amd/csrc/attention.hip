@@ -262,9 +262,6 @@ __global__ void __launch_bounds__(1024) attention_qkv2_d8_kernel(const AttnQkvPa
     attention_qkv2_body<PAIR, false>(p, waves, Lp, HG, bid / hgroups, bid % hgroups, none);
 }
 
-static int g_attn_old = getenv("RLDM_ATTN_OLD") ? atoi(getenv("RLDM_ATTN_OLD")) : 0;
-static int g_attn_hg = getenv("RLDM_ATTN_HG") ? atoi(getenv("RLDM_ATTN_HG")) : 0;      // force heads per workgroup (A/B runs)
-
 int attention_qkv2_geometry(int B, int L, int C, int* HG_out, int* waves_out) {
     const int Lp = (L + 31) / 32 * 32;
     const int ntiles = Lp / 32;
@@ -275,7 +272,6 @@ int attention_qkv2_geometry(int B, int L, int C, int* HG_out, int* waves_out) {
     const int wph = pair ? (ntiles + 1) / 2 : ntiles;     // waves per head
     int HG = 1;
     while (HG * 2 * wph <= 16 && heads % (HG * 2) == 0 && (long long)B * (heads / (HG * 2)) >= 256) HG *= 2;
-    if (g_attn_hg > 0 && g_attn_hg * wph <= 16 && heads % g_attn_hg == 0) HG = g_attn_hg;
     const int waves = HG * wph;
     if (waves > 16 || L > 1024 || C % 64 != 0) return -1;          // (caller falls back to the first-generation kernel; C % 64: the
                                                                     //  projection stages x in groups of 64 channels)
@@ -291,7 +287,7 @@ int attention_qkv2_geometry(int B, int L, int C, int* HG_out, int* waves_out) {
 // workgroup is resident at once (1024 threads, > 80 KB of LDS: one per CU).
 bool attention_proj_fusable(int B, int L, int C, int cus) {     // (cus < 0: the shape only -- the tail as a launch of its own)
     int HG = 0, waves = 0;
-    if (g_attn_old || attention_qkv2_geometry(B, L, C, &HG, &waves)) return false;
+    if (attention_qkv2_geometry(B, L, C, &HG, &waves)) return false;
     const int R = (C / 8) / HG, grid = B * R;
     if (cus < 0) cus = grid;
     const int ng = waves * 128 / C;                       // pixel groups of the tail's statistics pass (threads / channel pairs)
@@ -333,10 +329,8 @@ int launch_attention_qkv2(const AttnQkvParams& p, hipStream_t stream) {
 int launch_attention_qkv(const AttnQkvParams& p, hipStream_t stream) {
     RLDM_REQUIRE(p.L >= 1 && p.L <= 1024, "attention_qkv: token count must be in [1, 1024]");
     RLDM_REQUIRE(p.C % 16 == 0 && p.C <= 512 && p.C % p.groups == 0, "attention_qkv: channels must be a multiple of 16, <= 512");
-    if (!g_attn_old) {
-        const int rc = launch_attention_qkv2(p, stream);
-        if (rc >= 0) return rc;
-    }
+    const int rc = launch_attention_qkv2(p, stream);       // (< 0: no second-generation geometry for the shape)
+    if (rc >= 0) return rc;
     RLDM_REQUIRE(p.proj_w == nullptr, "attention_qkv: the fused output projection needs the second-generation launch");
     const int Lp = (p.L + 31) / 32 * 32;
     const int ntiles = Lp / 32;
@@ -353,7 +347,7 @@ int launch_attention_qkv(const AttnQkvParams& p, hipStream_t stream) {
 void attention_qkv_route(int B, int L, int C, int cus, int* route) {
     const int ntiles = (L + 31) / 32;
     int HG = 0, waves = 0;
-    const bool gen2 = !g_attn_old && attention_qkv2_geometry(B, L, C, &HG, &waves) == 0;
+    const bool gen2 = attention_qkv2_geometry(B, L, C, &HG, &waves) == 0;
     route[0] = gen2 ? 2 : 1;
     route[1] = gen2 && ntiles >= 32 ? 1 : 0;
     route[2] = gen2 ? HG : 1;

@@ -57,7 +57,7 @@ __global__ void __launch_bounds__(kRwTeam * TEAMS, TEAMS == 1 ? 2 : 1) conv_regw
     const int b = blockIdx.x / wg_per_image, part = blockIdx.x - b * wg_per_image;
     const int t_first = (part * TEAMS + team) * tiles_per_team;
     const unsigned long long ts_core0 = __builtin_amdgcn_s_memtime(), ts_real0 = __builtin_amdgcn_s_memrealtime();   // (tuning: the launch's clock)
-    const int abl = p.exp >> 16;                        // (tuning: RLDM_RW_ABL -- 1 no K loop, 2 no staging arithmetic, 4 no output stores, 8 no halo loads, 16 start offset)
+    const int abl = p.exp >> 16;                        // (ablation bits, 0 from the host: 1 no K loop, 2 no staging arithmetic, 4 no output stores, 8 no halo loads, 16 start offset)
 
     unsigned char* const sA = smem + team * kRwTeamBytes;               // this team's halo (normalised), then its waves' landing zones
     unsigned char* const sRaw = sA + kRwABytes + tw4 * kRwRawWave;      // this wave's

@@ -621,31 +621,52 @@ struct ViewPlan {
     }
 };
 
-// routing / ablation switches (rldm_debug_set_flags); RLDM_DBG_FLAGS seeds them for A/B runs of unmodified drivers
+// routing switches (rldm_debug_set_flags, enum rldm_flag); RLDM_DBG_FLAGS seeds them for runs of unmodified drivers
 static int g_dbg_flags = getenv("RLDM_DBG_FLAGS") ? atoi(getenv("RLDM_DBG_FLAGS")) : 0;
 // ... and the options of the plan being built (Plan::flags: rldm_sampler_config::plan_flags, rldm_unet_set_plan_flags, the fall-back
 // of a sampler whose persistent launches failed their self-check) -- scoped to that plan, unlike the process-wide word above
 static thread_local int t_plan_flags = 0;
 static inline int dbg() { return g_dbg_flags | t_plan_flags; }
-// second word of process-wide tuning switches (rldm_debug_set_flags2 / RLDM_DBG_FLAGS2), round 4:
-//   1 full-resolution conv_stream launches keep the 8-wave 256-pixel workgroups (default: 4-wave 128 x 128 workgroups, two per CU)
-//   2 the 128x8 level keeps the 8-wave 128 x 64 x 4-k-group workgroups (default: 4-wave 128 x 64 x 2 k-groups, two per CU)
-//   4 the VAE's 64-channel level keeps the 8-wave 256 x 64 instance
-// 128 stride-2 convs stay on the generic kernel (default: the 64-pixel conv_stream tile where its grid fits)
-//  16 the 128x8 level keeps the 128 x 64 x 4-k-group tiles (default: 64 pixels x 128 channels x 2 k-groups)
-//   8 the 4-wave full-resolution convs stay launches of their own (default: phases of trunk variant 4, two workgroups per CU)
-//   bits 8..15: conv_stream experiment switches (ConvParams::exp); bits 16..23: (n + 1) = trunk variant 4's start offset n
-static int g_dbg_flags2 = getenv("RLDM_DBG_FLAGS2") ? atoi(getenv("RLDM_DBG_FLAGS2")) : 0;
+// second word of process-wide routing switches (rldm_debug_set_flags2, enum rldm_flag2)
+static int g_dbg_flags2 = 0;
 static inline int dbg2() { return g_dbg_flags2; }
-static const int kInst4MinBlocks = getenv("RLDM_INST4_MIN") ? atoi(getenv("RLDM_INST4_MIN")) : 96;    // (tuning; 192 -> 96: nuScenes at 4 images 87.4 -> 89.4,
-                                                                                           //  KITTI at 8 images 134.4 -> 137.5 img/s)
-static constexpr int kTrunkSkewDefault = 0;     // (trunk variant 4: start offset of the second image group, x 1024 cycles; measured 0 / 4 / 8 / 16 /
-                                                //  24 -> 230.6 / 230.1 / 230.8 / 228.7 / 223.7 img/s; RLDM_DBG_FLAGS2 = (n + 1) << 16: n)
+// ConvParams::dbg: the kernels' ablation bits.  The routing word reaches them only in RLDM_ABLATE builds (the timeline tools).
+static inline int kernel_dbg() {
+#ifdef RLDM_ABLATE
+    return dbg();
+#else
+    return 0;
+#endif
+}
 static unsigned long long* g_ts_buf = nullptr;   // rldm_debug_timestamps: device [4][64] s_memtime stamps
-static int g_force_bm = 0, g_force_bn = 0, g_force_ks = 0;
-static int g_split_auto = 0;     // automatic split-K is off: the in-launch combine costs more than the idle CUs     // rldm_debug_force_tile: tuning override (0: automatic)
+// in-kernel stamps (rldm_debug_timestamps, RLDM_ABLATE builds) of the launches the timeline tools pick, read once: RLDM_TS_TRUNK = n
+// the persistent launch of n phases (RLDM_TS_TRUNK_FIRST: only the first one built), RLDM_TS_ORD = n conv n of a network,
+// RLDM_TS_ATTN_L = L the attention launch of L tokens (AttnQkvParams::ts_L); none set: every conv and attention launch
+struct StampEnv {
+    const char *trunk, *trunk_first, *attn_l, *ord;
+};
+static const StampEnv& stamp_env() {
+    static const StampEnv e = {getenv("RLDM_TS_TRUNK"), getenv("RLDM_TS_TRUNK_FIRST"), getenv("RLDM_TS_ATTN_L"), getenv("RLDM_TS_ORD")};
+    return e;
+}
+enum class StampSite { Conv, Attn, TestAttn, Trunk };
+// where a launch writes its stamps (g_ts_buf or nowhere); n: the conv's ordinal (Conv), the launch's phase count (Trunk)
+static unsigned long long* stamp_buf(StampSite site, int n = 0) {
+    const StampEnv& e = stamp_env();
+    switch (site) {
+        case StampSite::Conv:     return e.ord ? (atoi(e.ord) == n ? g_ts_buf : nullptr) : (e.attn_l || e.trunk) ? nullptr : g_ts_buf;
+        case StampSite::Attn:     return (e.trunk || e.ord) ? nullptr : g_ts_buf;
+        case StampSite::TestAttn: return e.trunk ? nullptr : g_ts_buf;
+        case StampSite::Trunk:    return (e.trunk && atoi(e.trunk) == n) ? g_ts_buf : nullptr;
+    }
+    return nullptr;
+}
+static constexpr int kInst4MinBlocks = 96;      // (192 -> 96: nuScenes at 4 images 87.4 -> 89.4, KITTI at 8 images 134.4 -> 137.5 img/s)
+static constexpr int kTrunkSkew = 0;            // (trunk variant 4: start offset of the second image group, x 1024 cycles; measured 0 / 4 / 8 / 16 /
+                                                //  24 -> 230.6 / 230.1 / 230.8 / 228.7 / 223.7 img/s)
+static int g_force_bm = 0, g_force_bn = 0, g_force_ks = 0;     // rldm_debug_force_tile: tuning override (0: automatic)
+static constexpr int kGraphSteps = 10;          // sampler steps per captured graph (at most; a divisor of the step count)
 
-static constexpr bool kStreamPairs64Default = false;
 static thread_local int g_concurrent_plans = 1;   // plans being built will share the device with this many of their kind (sampler chains)
 
 struct TileChoice {
@@ -740,16 +761,11 @@ static TileChoice choose_tile(long long B, int Wout, int Hout, int stride, int N
         c.tile.BM = 64; c.tile.BN = 64; c.tile.CK = 16; c.tile.taps = taps;
         return c;                    // caller reports "no kernel instance" if this one does not exist either
     }
-    // split-K over channel chunks when the tile grid leaves most CUs idle (fp32 NCHW outputs skip it: tiny N anyway)
+    // split-K over channel chunks only on request (rldm_debug_force_tile): the in-launch combine costs more than the idle CUs
+    // (DESIGN.md); fp32 NCHW outputs never split
     c.ksplit = 1;
     const int ncc = Cin_pad / c.tile.CK;
-    if (!nchw) {
-        int ks = 1;
-        if (g_split_auto)
-            while (best_blocks * ks * 2 <= 320 && ks * 2 <= ncc && ncc % (ks * 2) == 0) ks *= 2;
-        c.ksplit = ks;
-        if (g_force_ks > 0 && g_force_ks <= std::max(1, ncc)) c.ksplit = g_force_ks;
-    }
+    if (!nchw && g_force_ks > 0 && g_force_ks <= std::max(1, ncc)) c.ksplit = g_force_ks;
     return c;
 }
 
@@ -838,10 +854,8 @@ struct Builder {
     bool trunk_open = false;
     std::map<int, int> trunk_seen;  // persistent launches built so far, by phase count (RLDM_TS_TRUNK_FIRST)
     std::vector<Tensor> deferred;  // releases held back while a segment is open (clusters of different images drift apart)
-    // rldm_debug_set_flags: 1 << 24 keeps every phase a launch of its own with the tiles unchanged (tests: identical results);
-    // 1 << 25 also gives the convs back their default tiles (A/B runs of the whole feature)
-    static bool trunk_enabled() { return !(dbg() & ((1 << 24) | (1 << 25))); }
-    static bool trunk_tiles() { return !(dbg() & (1 << 25)); }
+    // RLDM_FLAG_NO_PERSISTENT keeps every phase a launch of its own with the tiles unchanged (tests: identical results)
+    static bool trunk_enabled() { return !(dbg() & RLDM_FLAG_NO_PERSISTENT); }
     void note_launch() {           // every launch that is not a trunk phase closes the open segment
         flush_trunk();
         ++launches;
@@ -853,7 +867,7 @@ struct Builder {
         // the runtime's own answer to "are all these workgroups resident at once?" (variant 4: two per CU) -- asked here, at plan build,
         // not left to the launch's bounded-wait self-check.  A query that FAILS (< 0) changes nothing; a clear "no" keeps the layers launches.
         const int need_per_cu = pend.variant == 4 ? 2 : 1;
-        const int resident = (!dry && pend.phases.size() > 1 && !(dbg() & (1 << 29))) ? trunk_max_resident(pend.variant, pend.lds) : need_per_cu;
+        const int resident = (!dry && pend.phases.size() > 1) ? trunk_max_resident(pend.variant, pend.lds) : need_per_cu;
         const bool not_resident = resident >= 0 && resident < need_per_cu && pend.standalone.size() == pend.phases.size();
         if (not_resident) {
             static bool said = false;
@@ -862,7 +876,7 @@ struct Builder {
             said = true;
             launches += (int)pend.standalone.size() - 1;
             for (auto& op : pend.standalone) plan->ops.push_back(op);
-        } else if (!dry && pend.phases.size() == 1 && pend.standalone.size() == 1 && !(dbg() & (1 << 29))) {
+        } else if (!dry && pend.phases.size() == 1 && pend.standalone.size() == 1) {
             plan->ops.push_back(pend.standalone[0]);
         } else if (!dry && !pend.phases.empty()) {
             auto recs = std::make_unique<DevBuf>();
@@ -883,8 +897,7 @@ struct Builder {
             tp.ntile_n = pend.nwn == 1 ? pend.ranks : pend.ntile_n;
             tp.nwn = pend.nwn;
             tp.variant = pend.variant;
-            // (variant 4's start offset between the two image groups, x 1024 cycles; RLDM_DBG_FLAGS2 bits 16..23 override the default)
-            tp.skew = pend.variant == 4 ? (((dbg2() >> 16) & 255) ? ((dbg2() >> 16) & 255) - 1 : kTrunkSkewDefault) : 0;
+            tp.skew = pend.variant == 4 ? kTrunkSkew : 0;
             tp.counters = ctrs->as<unsigned>();
             tp.error = plan->trunk_error.as<int>();
             tp.temb_ld = temb_ld;
@@ -892,13 +905,13 @@ struct Builder {
             plan->trunk_bufs.push_back(std::move(ctrs));
             Plan* pl = plan;
             const size_t lds = pend.lds;
-            const bool ts_ok = !getenv("RLDM_TS_TRUNK_FIRST") || ++trunk_seen[(int)pend.phases.size()] == 1;   // (timeline of the FIRST such launch)
+            const bool ts_ok = !stamp_env().trunk_first || ++trunk_seen[(int)pend.phases.size()] == 1;   // (timeline of the FIRST such launch)
             plan->ops.push_back({[tp, lds, pl, ts_ok](hipStream_t st) mutable {
                 tp.temb = pl->io.temb;
                 tp.step_ptr = pl->io.step_ptr;
                 tp.temb_rows_per_step = pl->io.temb_rows_per_step;
                 tp.temb_per_sample = pl->io.temb_per_sample;
-                tp.ts = (ts_ok && getenv("RLDM_TS_TRUNK") && tp.nphases == atoi(getenv("RLDM_TS_TRUNK"))) ? g_ts_buf : nullptr;
+                tp.ts = ts_ok ? stamp_buf(StampSite::Trunk, tp.nphases) : nullptr;
                 return launch_trunk(tp, lds, st);
             }, std::string("trunk_kernel<") + (pend.variant == 0 ? "conv_small image tiles" : pend.variant == 1 ? "conv_small 64x64 clusters" :
                                                pend.variant == 2 ? "conv_stream 256x128" : pend.variant == 3 ? "conv_stream 128x64" : pend.variant == 5 ? "conv_stream 64x128" : "conv_stream 128x128 x2/CU") +
@@ -927,7 +940,7 @@ struct Builder {
     // ... of a multi-tile cluster: raw x + statistics (the fold runs inside the phase), two query tiles per wave; 0: not eligible
     int cluster_attention_ranks(const Tensor& x, bool pre) const {
         const int L = x.W * x.H, ranks = cluster_ranks(x.B, x.C, L);
-        if (!cluster_enabled() || (dbg() & 512) || pre || ranks == 0 || x.P <= 0 || (x.C / 8) % ranks != 0 || L % 32 != 0) return 0;
+        if (!cluster_enabled() || pre || ranks == 0 || x.P <= 0 || (x.C / 8) % ranks != 0 || L % 32 != 0) return 0;
         const int HG = (x.C / 8) / ranks, wph = L / 32;
         if (HG * wph != 16 || x.C > 512) return 0;                // 8 waves x two query tiles
         return trunk_attention_lds(L, x.C, HG) <= 160 * 1024 ? ranks : 0;
@@ -941,11 +954,10 @@ struct Builder {
     // for the rest) and the device's real CU count (partitions / smaller parts)
     // (per_cu = 2: the 4-wave conv_stream variant, whose workgroups are built for two per CU)
     // (round 5) channels per image-owning tile: 16 for the 64-pixel images of the KITTI network's 32x2 level (256 output channels -> 16
-    // workgroups per image), when that grid is resident at once; 32 otherwise.  RLDM_OWN16=0 keeps 32 everywhere (A/B runs).
-    static bool own16_enabled() { static const bool on = !(getenv("RLDM_OWN16") && atoi(getenv("RLDM_OWN16")) == 0); return on; }
+    // workgroups per image), when that grid is resident at once; 32 otherwise.  (Also without persistent launches: the per-layer
+    // fall-back keeps their tiles, so its results stay identical.)
     static int own_tile_channels(int B, int npix, int N) {
-        return (own16_enabled() && trunk_tiles() && npix == 64 && N == 256 && trunk_grid_fits(16, B)) ? 16 : 32;    // (trunk_tiles(), not trunk_enabled():
-        // the per-layer fall-back -- 1 << 24 -- keeps the persistent launches' tiles, so its results stay identical)
+        return (npix == 64 && N == 256 && trunk_grid_fits(16, B)) ? 16 : 32;
     }
     static bool trunk_grid_fits(int ranks, int B, int per_cu = 1) {
         return 8 * ranks * ((B + 7) / 8) * std::max(1, g_concurrent_plans) <= device_cus() * per_cu;
@@ -967,10 +979,10 @@ struct Builder {
     }
     // multi-tile clusters (trunk.hip, kinds 8..13): an image = (N / 64) channel tiles x (pixels / 64) pixel tiles of conv_small's
     // 64 x 64 instance, all of them resident at once and on one XCD (8 * ranks * ceil(B / 8) workgroups <= the chip's CUs).
-    // rldm_debug_set_flags(1 << 26) keeps these levels as separate launches (A/B runs)
+    // RLDM_FLAG_NO_CLUSTERS keeps these levels as separate launches
     // (and only for plans that run ALONE on the device: a 256-workgroup launch of one sampler chain and one of another could each
     //  hold part of the chip and wait for the rest -- sampler_build_plans sets g_concurrent_plans to its number of chains)
-    static bool cluster_enabled() { return trunk_enabled() && !(dbg() & (1 << 26)) && g_concurrent_plans <= 1; }
+    static bool cluster_enabled() { return trunk_enabled() && !(dbg() & RLDM_FLAG_NO_CLUSTERS) && g_concurrent_plans <= 1; }
     static int cluster_ranks(int B, int C, int npix) {
         if (C % 64 != 0 || npix % 64 != 0) return 0;
         const int r = (C / 64) * (npix / 64);
@@ -1033,20 +1045,21 @@ struct Builder {
     }
     // geometry + channel counts of the route; `epi_res`: the identity residual is added in the epilogue instead of the K loop
     static bool small_params(const ConvArgs& a, int Cin_t, int R_t, int taps, int Wout, int Hout, ConvParams* q, bool* epi_res) {
-        if (dbg() & 256) return false;
+        if (dbg() & RLDM_FLAG_NO_CONV_SMALL) return false;
         if ((taps != 9 && taps != 1) || a.stride != 1 || (a.up != 1 && !(a.up == 2 && taps == 9 && !a.gn && R_t == 0)) || a.out_f32_nchw)
             return false;
         // (128-pixel tiles for the 128x8 level are built and tested but lose to the generic kernel there: the separate
-        //  GroupNorm pass over a 12 MB tensor costs more than the faster K loop wins; rldm_debug_set_flags(1024) routes them)
+        //  GroupNorm pass over a 12 MB tensor costs more than the faster K loop wins; RLDM_FLAG_SMALL_128PX routes them)
         // small images (C2: the 64x4 / 32x2 levels at batch 16), or few pixels in the whole batch (C1 / C3: 128x8 at batch 1,
         // 128x4 at batch 4): the same 64-pixel tiles, more of them per image
-        const bool few_px = (long long)a.x0.B * Wout * Hout <= 4096 && !(dbg() & 65536);
-        if (taps == 9 && (a.pad_mode != 0 || (Wout * Hout > ((dbg() & 1024) ? 1024 : 256) && !few_px))) return false;
+        const bool few_px = (long long)a.x0.B * Wout * Hout <= 4096;
+        if (taps == 9 && (a.pad_mode != 0 || (Wout * Hout > ((dbg() & RLDM_FLAG_SMALL_128PX) ? 1024 : 256) && !few_px))) return false;
         // pixel tile: 64; 128 for the 3x3 convs of the 128x8 level (each weight fragment then feeds 4 MFMAs)
         // (32 for 32x1 images: the lowest nuScenes level, which otherwise runs as 8 workgroups of the generic kernel; and for
         //  32x2 images, as two tiles each: twice the workgroups, half the staging / epilogue per workgroup -- level-3 convs
-        //  13.4-14.2 -> 13.0 us, +0.5-1 % end to end; rldm_debug_set_flags(524288) keeps the 64-pixel tile: A/B runs, tests)
-        int bm = (taps == 9 && Wout * Hout > 256 && !few_px) ? 128 : ((Wout * Hout == 32 || (Wout * Hout == 64 && Hout == 2 && !(dbg() & 524288))) && a.up == 1 ? 32 : 64);
+        //  13.4-14.2 -> 13.0 us, +0.5-1 % end to end; RLDM_FLAG_SMALL_64PX_32X2 keeps the 64-pixel tile: tests)
+        int bm = (taps == 9 && Wout * Hout > 256 && !few_px) ? 128 :
+                 ((Wout * Hout == 32 || (Wout * Hout == 64 && Hout == 2 && !(dbg() & RLDM_FLAG_SMALL_64PX_32X2))) && a.up == 1 ? 32 : 64);
         if (a.own_image) {                      // one tile per image (<= 64 pixels), or not this route
             if (Wout * Hout > 64 || a.up != 1) return false;
             bm = Wout * Hout;
@@ -1110,16 +1123,14 @@ struct Builder {
         return 0;
     }
     // GroupNorm (+ SiLU) folded into the conv's staging: every 1x1, and the 3x3 convs over ONE input tensor (a concatenated
-    // input keeps the separate gn_apply launch; rldm_debug_set_flags(131072) keeps it for every 3x3: A/B runs)
+    // input on an image-owning tile keeps the separate gn_apply launch / phase)
     // (round 4) ... and a concatenated 3x3 input on tiles that do not own their image (the 64x4 level's cluster phases, the stand-alone
     // launches of the small-batch configurations): the gn_apply phase / launch it replaces costs 12-23 k cycles, the four-fold repeated
-    // arithmetic in the staging ~4.7 k; RLDM_SMALL_CONCAT_GN=0 keeps gn_apply (A/B runs)
-    static bool small_concat_gn() { static const bool on = !(getenv("RLDM_SMALL_CONCAT_GN") && atoi(getenv("RLDM_SMALL_CONCAT_GN")) == 0); return on; }
+    // arithmetic in the staging ~4.7 k
     static bool small_gn_fused(const ConvArgs& a, int taps) {
         if (a.gn == nullptr) return false;
         if (taps == 1) return true;
-        if (dbg() & 131072) return false;
-        return !a.x1.valid() || (small_concat_gn() && !a.own_image && a.x0.C % 8 == 0 && a.x1.C % 8 == 0);
+        return !a.x1.valid() || (!a.own_image && a.x0.C % 8 == 0 && a.x1.C % 8 == 0);
     }
     bool small_route(const ConvArgs& a, int Cin_t, int R_t, int taps, int Wout, int Hout) const {
         ConvParams q;
@@ -1143,9 +1154,8 @@ struct Builder {
         ConvParams p;
         bool epi_res = false;
         RLDM_REQUIRE(small_params(a, Cin_t, R_t, taps, Wout, Hout, &p, &epi_res), "conv " + L->name + ": conv_small route lost");
-        p.dbg = dbg();
-        p.ts = (getenv("RLDM_TS_ATTN_L") || getenv("RLDM_TS_TRUNK")) ? nullptr : g_ts_buf;      // (the attention timeline owns the buffer then)
-        if (getenv("RLDM_TS_ORD")) p.ts = atoi(getenv("RLDM_TS_ORD")) == conv_ord - 1 ? g_ts_buf : nullptr;
+        p.dbg = kernel_dbg();
+        p.ts = stamp_buf(StampSite::Conv, conv_ord - 1);
         int BN = small_bn(p, taps, gn_fused, a.own_image);
         RLDM_REQUIRE(BN != 0, "conv " + L->name + ": conv_small route lost its instance");
         // (round 5) image-owning tiles of the 32x2 level: 16 channels per workgroup -- the level's persistent launch then runs on 16
@@ -1180,23 +1190,23 @@ struct Builder {
                         2 * p.TH * (Cin_t / 8) <= 512 && vts.size() <= 2;
         // (a concatenated input is normalised by a gn_apply phase in front of the conv's -- or the conv stays a launch of its own)
         const bool gn_phase_t = in_trunk && preact && Cin_t <= 512 && (Wout * Hout) % ranks_t == 0 && a.x0.C % 8 == 0 &&
-                                (!a.x1.valid() || a.x1.C % 8 == 0) && !(dbg() & (1 << 27));
+                                (!a.x1.valid() || a.x1.C % 8 == 0);
         in_trunk = in_trunk && (!preact || gn_phase_t);
         // ... or a phase of a MULTI-TILE cluster (the 64x4 level at batch <= 16): conv_small's default 64-pixel x 64-channel tiles, the
         // consumer-side GroupNorm fold stays inside the phase
         // (3x3 over 128 channels -- the all-taps-ring instance, 211 registers on its own -- does not fit beside the phase loop's state)
-        const int kind_c = (taps == 9 && Cin_t == 128 && !getenv("RLDM_NO_CL128")) ? TK_CL_3x3_128 : (taps == 9 && Cin_t == 256) ? TK_CL_3x3_256 :
+        const int kind_c = (taps == 9 && Cin_t == 128) ? TK_CL_3x3_128 : (taps == 9 && Cin_t == 256) ? TK_CL_3x3_256 :
                            (taps == 9 && Cin_t == 384) ? TK_CL_3x3_384 : (taps == 9 && Cin_t == 512) ? TK_CL_3x3_512 :
                            (taps == 1 && Cin_t == 256) ? TK_CL_1x1_256 : -1;
         const int ranks_c = cluster_ranks(x0.B, N, Wout * Hout);
-        const bool in_cluster = !in_trunk && cluster_enabled() && !(dbg() & 512) && !a.own_image && kind_c >= 0 && BN == 64 && px_t == 64 &&
+        const bool in_cluster = !in_trunk && cluster_enabled() && !a.own_image && kind_c >= 0 && BN == 64 && px_t == 64 &&
                                 (p.up == 1 || p.up == 2) && vts.empty() && ranks_c == (N / 64) * p.tiles_img &&
                                 p.Win * p.up == Wout && p.Hin * p.up == Hout;
         // GroupNorm + SiLU once, ahead of the conv: every channel tile of the conv would otherwise redo it (4-8x at these levels) --
         // as a launch (norm.hip) or, in front of a multi-tile cluster phase, as a phase of the same persistent launch
         if (preact) {
             const bool gn_phase = gn_phase_t || (in_cluster && Cin_t <= 512 && (Wout * Hout) % ranks_c == 0 && a.x0.C % 8 == 0 &&
-                                                 (!a.x1.valid() || a.x1.C % 8 == 0) && !(dbg() & (1 << 27)));
+                                                 (!a.x1.valid() || a.x1.C % 8 == 0));
             if (gn_phase_t) trunk_begin(x0.B, ranks_t);
             else if (gn_phase) trunk_begin(x0.B, ranks_c, N / 64, 2);
             else note_launch();
@@ -1355,10 +1365,10 @@ struct Builder {
 
     // conv_stream.hip route: 3x3 / stride 1 convs whose output has at least 128 tiles of 32 x 8 pixels x 128 channels, or
     // (the 128x8 level) of 16 x 8 pixels x 64 channels
-    static inline const int kSubMinBlocks = getenv("RLDM_SUB_MIN") ? atoi(getenv("RLDM_SUB_MIN")) : 96;     // (env: tuning runs)
+    static constexpr int kSubMinBlocks = 96;
     static bool stream_params_tw(const ConvArgs& a, int Cin_t, int R_t, int taps, int Wout, int Hout, int TW, long long min_blocks,
                                  long long max_blocks, ConvParams* q, int TH = 8, int inst = 0) {
-        if (dbg() & 2048) return false;
+        if (dbg() & RLDM_FLAG_NO_STREAM_REGW) return false;
         if (taps != 9 || (a.stride != 1 && !(a.stride == 2 && inst == 5)) || a.pad_mode != 0 || a.out_f32_nchw || g_force_bm) return false;
         // (inst 6, round 4: nearest x2 + 3x3 in its sub-pixel form -- the tiles are INPUT tiles, four parity workgroups each)
         const bool sub = inst == 6;
@@ -1396,7 +1406,7 @@ struct Builder {
         q->ksplit = 1;
         if (a.gn) q->st0 = reinterpret_cast<const float2*>(q);      // (only its presence matters to the shape check)
         const long long blocks = (long long)q->B * q->tiles_img * (q->N / conv_stream_bn(*q)) * (sub ? 4 : 1);
-        const bool ok = conv_stream_supported(*q, 9) && ((dbg() & 4096) || (blocks >= min_blocks && blocks <= max_blocks));
+        const bool ok = conv_stream_supported(*q, 9) && ((dbg() & RLDM_FLAG_STREAM_ANY_GRID) || (blocks >= min_blocks && blocks <= max_blocks));
         q->st0 = nullptr;
         return ok;
     }
@@ -1408,45 +1418,46 @@ struct Builder {
         // level and the VAE's 64-channel level
         const int N_ = a.layer->Cout;
         // (round 4) stride 2 (Downsample2D, pad 1) on the 64-pixel x 128-channel tile with a 17 x 17 halo: the 256x16 -> 128x8 down-sampler ran on
-        // the generic kernel's half-empty 256-pixel tile; rldm_debug_set_flags2(128) keeps it there
+        // the generic kernel's half-empty 256-pixel tile
         if (a.stride == 2) {
-            if ((dbg2() & 128) || N_ % 128 != 0 || R_t != 0 || a.up != 1) return false;
+            if (N_ % 128 != 0 || R_t != 0 || a.up != 1) return false;
             if (stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 8, kInst4MinBlocks, 512, q, 8, 5)) return true;
             // outputs of 4 beams (the 128x8 -> 64x4 down-sampler): 16 x 4 tiles, from 48 workgroups on
-            return Hout == 4 && !getenv("RLDM_NO_S2_H4") && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 16, 48, 512, q, 4, 5);
+            return Hout == 4 && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 16, 48, 512, q, 4, 5);
         }
-        // (experiment, rldm_debug_set_flags2(32)) the 256 x 128 tile with specialised waves wherever the 8-wave 256 x 128 instance would run
-        if ((dbg2() & 32) && N_ % 128 == 0 && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 32, 200, 1ll << 40, q, 8, 3)) return true;
-        // (tests, rldm_debug_set_flags2(64)) the 64-pixel x 128-channel tile first, at any level it fits
-        if ((dbg2() & 64) && N_ % 128 == 0 && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 8, 192, 512, q, 8, 4)) return true;
+        const int f2 = dbg2();
+        // (experiment, RLDM_FLAG2_STREAM_SPEC_WAVES) the 256 x 128 tile with specialised waves wherever the 8-wave 256 x 128 instance would run
+        if ((f2 & RLDM_FLAG2_STREAM_SPEC_WAVES) && N_ % 128 == 0 && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 32, 200, 1ll << 40, q, 8, 3))
+            return true;
+        // (tests, RLDM_FLAG2_STREAM_64PX) the 64-pixel x 128-channel tile first, at any level it fits
+        if ((f2 & RLDM_FLAG2_STREAM_64PX) && N_ % 128 == 0 && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 8, 192, 512, q, 8, 4)) return true;
         // (round 4) nearest x2 + 3x3 as four 2x2 convs over the input (sub-pixel form: 4 taps instead of 9 per output pixel) on the 4-wave
-        // 128 x 128 tile; rldm_debug_set_flags2(1 << 27) keeps the 3x3 over the up-sampled halo
-        if (!(dbg2() & (1 << 27)) && !(dbg2() & 1) && a.up == 2 && N_ % 128 == 0 &&
+        // 128 x 128 tile
+        if (!(f2 & RLDM_FLAG2_STREAM_8WAVE_FULL) && a.up == 2 && N_ % 128 == 0 &&
             (stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 16, kSubMinBlocks, 1ll << 40, q, 8, 6) ||
              (a.x0.H % 8 != 0 && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 32, kSubMinBlocks, 1ll << 40, q, 4, 6)))) return true;   // (inputs of 4 beams: 32 x 4 tiles)
-        // (round 4) images of 16 beams: 8 x 16 tiles as tall as the image -- five staged pieces per thread instead of six; rldm_debug_set_flags2(1 << 29):
-        // the 16 x 8 tiles
-        if (!(dbg2() & 1) && !(dbg2() & (1 << 29)) && N_ % 128 == 0 && (Hout == 16 || Hout == 8) && a.up == 1 &&
+        // (round 4) images of 16 beams: 8 x 16 tiles as tall as the image -- five staged pieces per thread instead of six;
+        // RLDM_FLAG2_HALO_RING: the 16 x 8 tiles
+        if (!(f2 & (RLDM_FLAG2_STREAM_8WAVE_FULL | RLDM_FLAG2_HALO_RING)) && N_ % 128 == 0 && (Hout == 16 || Hout == 8) && a.up == 1 &&
             stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, Hout == 16 ? 8 : 16, 384, 1ll << 40, q, Hout, 7)) return true;       // (8 beams: 16 x 8)
-        if (!(dbg2() & 1) && N_ % 128 == 0 && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 16, 384, 1ll << 40, q, 8, 1)) return true;
-        if (!(dbg2() & 4) && N_ % 128 != 0 && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 16, 384, 1ll << 40, q, 8, 2)) return true;
+        if (!(f2 & RLDM_FLAG2_STREAM_8WAVE_FULL) && N_ % 128 == 0 && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 16, 384, 1ll << 40, q, 8, 1))
+            return true;
+        if (!(f2 & RLDM_FLAG2_STREAM_8WAVE_C64) && N_ % 128 != 0 && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 16, 384, 1ll << 40, q, 8, 2))
+            return true;
         if (stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 32, 200, 1ll << 40, q)) return true;
         // (round 4) the 128x8 level: 64-pixel x 128-channel x 2-k-group tiles (8 x 8: a smaller halo, normalised once for all 128 channels,
-        // half the partial sums to exchange); rldm_debug_set_flags2(16) keeps the 128 x 64 x 4-k-group tiles
-        if (!(dbg2() & 16) && !(dbg() & 16384) && N_ % 128 == 0 && Hout == 8 &&       // (at the 256x16 level of small batches it breaks the clusters: -4 %; RangeDM at batch 1: +1 %, not worth a rule)
+        // half the partial sums to exchange)
+        if (N_ % 128 == 0 && Hout == 8 &&       // (at the 256x16 level of small batches it breaks the clusters: -4 %; RangeDM at batch 1: +1 %, not worth a rule)
             stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 8, kInst4MinBlocks, 320, q, 8, 4)) return true;      // (one round of 8-wave workgroups: at 512
         // blocks -- the 256-channel up-sampler conv of the level -- two co-resident 4-wave workgroups per CU win, 23.6 against 27.1 us)
-        if (!(dbg2() & 2) && !(dbg() & 16384) && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 16, 257, 512, q, 8, 2)) return true;
-        if (!(dbg() & 16384) && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 16, 128, 512, q)) return true;
+        if (!(f2 & RLDM_FLAG2_STREAM_8WAVE_128X8) && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 16, 257, 512, q, 8, 2)) return true;
+        if (stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 16, 128, 512, q)) return true;
         // images of 4 beams (nuScenes' 128 x 4 level at batch 32): the same 128-pixel instance on 32 x 4 tiles (round 3; it ran on the
         // generic kernel at 27.8 us / 257 TFLOP/s per conv: 16 % of that configuration's step)
-        if (Hout % 8 != 0 && !(dbg() & 16384) && !(dbg() & 16) && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 32, 128, 512, q, 4)) return true;
+        if (Hout % 8 != 0 && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 32, 128, 512, q, 4)) return true;
         return stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 32, 128, 1ll << 40, q);
     }
 
-    // (round 5) the conv pairs of the 128x8 level -- 64-pixel x 128-channel tiles, 16 workgroups per image -- as 2-phase persistent launches
-    // (trunk variant 5); RLDM_STREAM_PAIRS64=0 / 1 overrides the default
-    static bool stream_pairs64() { static const bool on = getenv("RLDM_STREAM_PAIRS64") ? atoi(getenv("RLDM_STREAM_PAIRS64")) != 0 : kStreamPairs64Default; return on; }
     int conv_stream(const ConvArgs& a, int Cin_t, int R_t, int Wout, int Hout, Tensor* out) {
         ConvLayer* L = a.layer;
         const int N = L->Cout;
@@ -1457,20 +1468,10 @@ struct Builder {
             RLDM_REQUIRE(a.gn->C == Cin_t && Cin_t % a.groups == 0, "conv " + L->name + ": GroupNorm channel mismatch");
             RLDM_REQUIRE(x0.P > 0 && (!a.x1.valid() || a.x1.P > 0), "conv " + L->name + ": GroupNorm input without statistics");
         }
-        p.dbg = dbg();
-        p.ts = (getenv("RLDM_TS_ATTN_L") || getenv("RLDM_TS_TRUNK")) ? nullptr : g_ts_buf;      // (the attention timeline owns the buffer then)
-        if (getenv("RLDM_TS_ORD")) p.ts = atoi(getenv("RLDM_TS_ORD")) == conv_ord - 1 ? g_ts_buf : nullptr;   // ONE conv of a network
+        p.dbg = kernel_dbg();
+        p.ts = stamp_buf(StampSite::Conv, conv_ord - 1);
         const bool sub = p.st_inst == 6;
         p.ntile_n = N / conv_stream_bn(p) * (sub ? 4 : 1);      // (grid x: channel tiles x parities)
-        p.exp = (dbg2() >> 8) & 255;            // (bits 8..15 only: 16..23 are trunk variant 4's start offset)
-        if (p.exp & 2) {
-            static int* locks = nullptr;            // (experiment: never freed)
-            if (!locks) {
-                RLDM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&locks), 4096 * sizeof(int)));
-                RLDM_HIP_CHECK(hipMemset(locks, 0, 4096 * sizeof(int)));
-            }
-            p.cu_lock = locks;
-        }
         Tensor y = make(x0.B, Wout, Hout, N);
         if (a.want_stats) add_stats(y, p.tiles_img * (sub ? 4 : 1));
         const double fl_ref = 2.0 * (double)x0.B * Wout * Hout * N * ((double)L->Cin * 9 + (L->sc_identity ? 0.0 : (double)L->R));
@@ -1479,19 +1480,18 @@ struct Builder {
         const double fl = sub ? fl_ref * 4.0 / 9.0 : fl_ref;
         // a phase of the persistent launch (trunk.hip, variants 2 / 3): the image's tiles_img x ntile_n workgroups (16 at both
         // full-resolution levels) form a cluster on one XCD; consecutive convs of a level hand over through its L2 -- no end-of-kernel
-        // write-back of the 16.8 MB outputs, no argument fetch / cold start per layer.  rldm_debug_set_flags(1 << 28): separate launches
+        // write-back of the 16.8 MB outputs, no argument fetch / cold start per layer
         const int ranks_s = p.tiles_img * p.ntile_n;            // (sub-pixel form: input tiles x parities, one 128-channel tile)
-        // (round 4) the 4-wave 128 x 128 instance: 32 workgroups per image, two per CU -- trunk variant 4; rldm_debug_set_flags2(8): launches
+        // (round 4) the 4-wave 128 x 128 instance: 32 workgroups per image, two per CU -- trunk variant 4
         const bool inst1 = p.st_inst == 1 || p.st_inst == 7;      // (the 4-wave 128 x 128 tile: 16 x 8, or 8 x 16 as tall as the image)
         const int per_cu = inst1 || sub ? 2 : 1;
-        const bool in_stream_cluster = cluster_enabled() && !(dbg() & (1 << 28)) && ranks_s >= 2 && ranks_s <= 16 * per_cu &&
+        // (the 128x8 level's conv pairs measured slower as 2-phase launches than as two launches, 216.9 against 220.0 img/s: they
+        //  stay launches)
+        const bool in_stream_cluster = cluster_enabled() && ranks_s >= 2 && ranks_s <= 16 * per_cu &&
                                        trunk_grid_fits(ranks_s, x0.B, per_cu) && y.P <= kFoldAboveP && N % 128 == 0 &&
-                                       ((p.st_inst == 4 && stream_pairs64()) ||       // (round 5: the 128x8 level's 64-pixel x 128-channel tile as phases)
-                                        (p.st_inst == 0 && (p.TW * p.TH == 256 || (dbg() & (1 << 30)))) ||     // (the 128x8 level's conv
-                                        // PAIRS measured slower as 2-phase launches than as two launches, 216.9 against 220.0 img/s: off unless 1 << 30)
-                                        ((inst1 || (sub && N == 128 && p.TH == 8 && !(dbg2() & (1 << 28)))) && !(dbg2() & 8) && conv_stream_lds_bytes(p) <= 80 * 1024));
-        if (in_stream_cluster) trunk_begin(x0.B, ranks_s, sub ? 1 : p.ntile_n, inst1 || sub || p.TW * p.TH == 256 || p.st_inst == 4 ? 4 : 2,
-                                           inst1 || sub ? 4 : (p.st_inst == 4 ? 5 : (p.TW * p.TH == 256 ? 2 : 3)));
+                                       ((p.st_inst == 0 && p.TW * p.TH == 256) ||
+                                        ((inst1 || (sub && N == 128 && p.TH == 8)) && conv_stream_lds_bytes(p) <= 80 * 1024));
+        if (in_stream_cluster) trunk_begin(x0.B, ranks_s, sub ? 1 : p.ntile_n, 4, inst1 || sub ? 4 : 2);
         else note_launch();
         if (!dry) {
             ConvLayer::Packed* pk = nullptr;
@@ -1560,10 +1560,9 @@ struct Builder {
     }
 
     // conv_regw.hip, conv_c16_kernel (round 4): the network's input layer (16 padded input channels, 128 | N, no norm / residual / time
-    // embedding): every weight in one wave's registers; RLDM_NO_C16=1 keeps the generic kernel
+    // embedding): every weight in one wave's registers
     static bool c16_params(const ConvArgs& a, int Cin_t, int R_t, int taps, int Wout, int Hout, ConvParams* q) {
-        static const bool off = getenv("RLDM_NO_C16") != nullptr;
-        if (off || (dbg() & 2048) || g_force_bm || taps != 9 || a.stride != 1 || a.pad_mode != 0 || a.up != 1 || a.out_f32_nchw) return false;
+        if ((dbg() & RLDM_FLAG_NO_STREAM_REGW) || g_force_bm || taps != 9 || a.stride != 1 || a.pad_mode != 0 || a.up != 1 || a.out_f32_nchw) return false;
         if (a.x1.valid() || a.gn || a.temb_off >= 0 || R_t != 0 || Cin_t != 16 || a.layer->Cout % 128 != 0 || Wout % 16 != 0 || Hout % 8 != 0) return false;
         memset(q, 0, sizeof(*q));
         q->C0 = 16;
@@ -1611,10 +1610,9 @@ struct Builder {
     }
 
     // conv_regw.hip, conv_o4_kernel (round 4): the UNet's output layer (GroupNorm + SiLU -> 3x3 over 128 channels -> <= 4 channels, fp32 NCHW + the
-    // scheduler step); RLDM_NO_O4=1 keeps the generic kernel
+    // scheduler step)
     static bool o4_params(const ConvArgs& a, int Cin_t, int R_t, int taps, int Wout, int Hout, ConvParams* q) {
-        static const bool off = getenv("RLDM_NO_O4") != nullptr;
-        if (off || (dbg() & 2048) || g_force_bm || taps != 9 || a.stride != 1 || a.pad_mode != 0 || a.up != 1 || !a.out_f32_nchw) return false;
+        if ((dbg() & RLDM_FLAG_NO_STREAM_REGW) || g_force_bm || taps != 9 || a.stride != 1 || a.pad_mode != 0 || a.up != 1 || !a.out_f32_nchw) return false;
         if (a.x1.valid() || a.temb_off >= 0 || R_t != 0 || Cin_t != 128 || a.layer->Cin != 128 || a.layer->Cout > 4 || Wout % 16 != 0 || Hout % 8 != 0) return false;
         memset(q, 0, sizeof(*q));
         q->C0 = 128;
@@ -1676,11 +1674,9 @@ struct Builder {
         return 0;
     }
 
-    // conv_regw.hip, conv_ds2_kernel (round 4): stride-2 convs of 256 raw channels onto few pixels (the 64x4 -> 32x2 down-sampler); RLDM_NO_DS2=1 keeps
-    // the generic kernel
+    // conv_regw.hip, conv_ds2_kernel (round 4): stride-2 convs of 256 raw channels onto few pixels (the 64x4 -> 32x2 down-sampler)
     static bool ds2_params(const ConvArgs& a, int Cin_t, int R_t, int taps, int Wout, int Hout, ConvParams* q) {
-        static const bool off = getenv("RLDM_NO_DS2") != nullptr;
-        if (off || (dbg() & 2048) || g_force_bm || taps != 9 || a.stride != 2 || a.pad_mode != 0 || a.up != 1 || a.out_f32_nchw) return false;
+        if ((dbg() & RLDM_FLAG_NO_STREAM_REGW) || g_force_bm || taps != 9 || a.stride != 2 || a.pad_mode != 0 || a.up != 1 || a.out_f32_nchw) return false;
         if (a.x1.valid() || a.gn || a.temb_off >= 0 || R_t != 0 || Cin_t != 256 || a.layer->Cin != 256 || a.layer->Cout % 32 != 0 || Wout % 32 != 0) return false;
         memset(q, 0, sizeof(*q));
         q->C0 = 256;
@@ -1724,12 +1720,12 @@ struct Builder {
     }
 
     // conv_regw.hip route (round 4): 64 -> 64 channel 3x3 convs over many 16 x 8 tiles (the VAE decoder's full-resolution level) -- the weights stay
-    // in registers, a workgroup walks a run of tiles; rldm_debug_set_flags2(1 << 24) keeps them on conv_stream's per-tile instance
+    // in registers, a workgroup walks a run of tiles; RLDM_FLAG2_NO_REGW keeps them on conv_stream's per-tile instance
     static bool regw_params(const ConvArgs& a, int Cin_t, int R_t, int taps, int Wout, int Hout, ConvParams* q) {
         const int N_ = a.layer->Cout;
-        if ((dbg2() & (1 << 24)) || (dbg() & 2048) || g_force_bm || taps != 9 || a.stride != 1 || a.pad_mode != 0 || a.up != 1) return false;
+        if ((dbg2() & RLDM_FLAG2_NO_REGW) || (dbg() & RLDM_FLAG_NO_STREAM_REGW) || g_force_bm || taps != 9 || a.stride != 1 || a.pad_mode != 0 || a.up != 1) return false;
         if (a.x1.valid() || a.temb_off >= 0 || Cin_t != 64 || a.layer->Cin != 64 || a.first_of_step) return false;
-        if (a.out_f32_nchw ? (N_ > 4 || R_t != 0 || getenv("RLDM_NO_RW_OUT") != nullptr) : N_ != 64) return false;
+        if (a.out_f32_nchw ? (N_ > 4 || R_t != 0) : N_ != 64) return false;
         if (R_t != 0 && !(a.layer->sc_identity && R_t == 64 && a.r0.valid() && a.r0.C == 64)) return false;
         if (Wout % 16 != 0 || Hout % 8 != 0) return false;
         memset(q, 0, sizeof(*q));
@@ -1752,7 +1748,7 @@ struct Builder {
         q->gn_eps = a.eps;
         q->gn_groups = a.groups;
         q->ksplit = 1;
-        q->exp = ((dbg2() & (1 << 25)) ? 8 : 0) | (getenv("RLDM_RW_ABL") ? atoi(getenv("RLDM_RW_ABL")) << 16 : 0);   // (tests: at most 8 team runs, so that small images give runs of several tiles; tuning)
+        q->exp = (dbg2() & RLDM_FLAG2_REGW_CAP8) ? 8 : 0;      // (tests: at most 8 team runs, so that small images give runs of several tiles)
         if (a.gn) q->st0 = reinterpret_cast<const float2*>(q);      // (only their presence matters to the shape check)
         if (a.out_f32_nchw) q->y_nchw = reinterpret_cast<float*>(q);
         const bool ok = conv_regw_supported(*q);
@@ -1770,7 +1766,7 @@ struct Builder {
             RLDM_REQUIRE(a.gn->C == Cin_t && Cin_t % a.groups == 0, "conv " + L->name + ": GroupNorm channel mismatch");
             RLDM_REQUIRE(x0.P > 0, "conv " + L->name + ": GroupNorm input without statistics");
         }
-        p.dbg = dbg();
+        p.dbg = kernel_dbg();
         p.ts = g_ts_buf;
         p.ntile_n = 1;
         Tensor y;
@@ -1816,10 +1812,10 @@ struct Builder {
     }
 
     // Statistics of a tensor with many pixel tiles per image are folded once, by one small launch, instead of by every
-    // workgroup of every consumer (gn_fold_kernel); RLDM_DBG_FLAGS=262144 keeps the raw partials for A/B runs.
-    static inline const int kFoldAboveP = getenv("RLDM_FOLD_ABOVE") ? atoi(getenv("RLDM_FOLD_ABOVE")) : 32;   // (env: tuning runs)
+    // workgroup of every consumer (gn_fold_kernel).
+    static constexpr int kFoldAboveP = 32;
     int fold_stats(Tensor& y) {
-        if (!y.valid() || y.P <= kFoldAboveP || (dbg() & 262144)) return 0;
+        if (!y.valid() || y.P <= kFoldAboveP) return 0;
         const size_t raw_off = y.st_off, raw_bytes = y.st_bytes();
         const int rawP = y.P;
         add_stats(y, 2);
@@ -1857,7 +1853,7 @@ struct Builder {
             if ((int)vp->can_emit.size() <= ord) vp->can_emit.resize(ord + 1, 0);
             if ((int)vp->out_c.size() <= ord) vp->out_c.resize(ord + 1, 0);
             vp->out_c[ord] = L->Cout;
-            vp->can_emit[ord] = !(dbg() & 1048576) && !a.out_f32_nchw && small_route(o, Cin_t, R_t, taps, Wout, Hout) &&
+            vp->can_emit[ord] = !(dbg() & RLDM_FLAG_CONSUMER_GN) && !a.out_f32_nchw && small_route(o, Cin_t, R_t, taps, Wout, Hout) &&
                                 (!a.gn || small_route(oc, Cin_t, R_t, taps, Wout, Hout));
         } else if (vp) {
             if (take_view(a.gn, &view)) {
@@ -1867,7 +1863,7 @@ struct Builder {
             cur_emit = (it != vp->emit.end() && !it->second.empty()) ? &it->second : nullptr;
             // one tile per image: to normalise for the consumers, and (input ready, nothing to fold) to be a trunk phase
             a.own_image = cur_emit != nullptr ||
-                          (trunk_tiles() && !a.gn && ord < (int)vp->can_emit.size() && vp->can_emit[ord] && !a.x1.valid());
+                          (!a.gn && ord < (int)vp->can_emit.size() && vp->can_emit[ord] && !a.x1.valid());
         }
         const size_t ops_before = plan->ops.size(), ph_before = pend.standalone.size();
         if (conv_route(a, out)) return 1;
@@ -1942,9 +1938,8 @@ struct Builder {
         p.N = N;
         p.silu = a.silu;
         p.gn_eps = a.eps;
-        p.dbg = dbg();
-        p.ts = (getenv("RLDM_TS_ATTN_L") || getenv("RLDM_TS_TRUNK")) ? nullptr : g_ts_buf;      // (the attention timeline owns the buffer then)
-        if (getenv("RLDM_TS_ORD")) p.ts = atoi(getenv("RLDM_TS_ORD")) == conv_ord - 1 ? g_ts_buf : nullptr;
+        p.dbg = kernel_dbg();
+        p.ts = stamp_buf(StampSite::Conv, conv_ord - 1);
         p.gn_groups = a.groups;
         p.ksplit = tc.ksplit;
         const int tiles_img = (Wout / p.TW) * (Hout / p.TH);
@@ -2048,16 +2043,14 @@ static int build_plan(Plan* plan, int temb_ld, const std::function<int(Builder&)
         rec.temb_ld = temb_ld;
         if (walk(rec)) return 1;
         vplan.decide();
-        // tuning aid (tools/bench_conv.py on a single conv): RLDM_FAKE_VIEWS=n makes every conv that could normalise for a
-        // consumer write n copies nobody reads (identity affine, SiLU on), so the epilogue's cost can be stamped alone
-        const char* fv = getenv("RLDM_FAKE_VIEWS");
-        if (!fv && (dbg() & (1 << 22))) fv = "2";     // (tests: the own-image tile + epilogue on single-conv plans)
-        if (fv) {
+        // tests (RLDM_FLAG_OWN_IMAGE_COPIES): every conv that could normalise for a consumer writes two copies nobody reads (identity
+        // affine, SiLU on) -- the own-image tile + epilogue on single-conv plans
+        if (dbg() & RLDM_FLAG_OWN_IMAGE_COPIES) {
             static std::map<int, std::unique_ptr<NormParams>> dummies;
             for (int ord = 0; ord < (int)vplan.can_emit.size(); ++ord) {
                 if (!vplan.can_emit[ord] || vplan.emit.count(ord) || vplan.out_c[ord] % 32 != 0) continue;
                 const int C = vplan.out_c[ord];
-                for (int i = 0; i < std::min(3, atoi(fv)); ++i) {
+                for (int i = 0; i < 2; ++i) {
                     auto& d = dummies[C * 4 + i];
                     if (!d) {
                         d = std::make_unique<NormParams>();
@@ -2124,9 +2117,9 @@ struct NetCommon {
     //     y  = shortcut[:, x.C:](skip) + u              a 1x1 conv with u as its identity residual
     // -- four launches of the fast kernel for two of the slow one; t and u are rounded to bf16 on the way (one more rounding of a
     // partial sum: inside the network tolerance, tests/test_hip_models.py::test_other_presets_full_size_match_reference).
-    // rldm_debug_set_flags(1 << 21) keeps the two generic launches (A/B runs).
+    // RLDM_FLAG_NO_WIDE_SPLIT keeps the two generic launches.
     bool wide_concat(const Builder& b, const Tensor& x, const Tensor& skip) const {
-        if (dbg() & (1 << 21)) return false;
+        if (dbg() & RLDM_FLAG_NO_WIDE_SPLIT) return false;
         if (!skip.valid() || x.C + skip.C <= 512 || x.C > 512 || skip.C > 512 || x.C % 64 != 0 || skip.C % 64 != 0) return false;
         const long long px = (long long)x.W * x.H;
         (void)b;
@@ -2330,7 +2323,7 @@ struct NetCommon {
 
     int attention(Builder& b, const std::string& p, Tensor x, Tensor* out) {
         const int Lt = x.W * x.H;
-        if (!(dbg() & 32768) && x.C % 16 == 0 && x.C <= 512 && Lt <= 1024 && x.P > 0 && x.C % groups == 0) {
+        if (x.C % 16 == 0 && x.C <= 512 && Lt <= 1024 && x.P > 0 && x.C % groups == 0) {
             // GroupNorm + q/k/v projection inside the attention launch: no [B][L][3C] tensor, one launch less
             NormParams* gnp = layers.get_norm(p + ".group_norm");
             b.record_consumer(gnp, x, Tensor(), 0, true, groups, eps);
@@ -2347,10 +2340,10 @@ struct NetCommon {
             in_trunk = in_trunk || cl_ranks != 0;
             // the stand-alone launch also carries the block's output projection (+ x, + statistics) when an image's workgroups are
             // 64-pixel blocks of it on one XCD, all resident: the 128x8 level at batch 8 / 16 (attention_body.h, attention_proj_tail);
-            // rldm_debug_set_flags(128) keeps the projection a launch of its own
-            // (without clusters -- a sampler's per-layer fall-back, several chains, the A/B switches -- the SAME tail runs as a launch of
+            // RLDM_FLAG_ATTN_PROJ_LAUNCH keeps the projection a launch of its own
+            // (without clusters -- a sampler's per-layer fall-back, several chains, the routing switches -- the SAME tail runs as a launch of
             //  its own behind the attention launch: identical results)
-            const bool proj_tail = !in_trunk && !(dbg() & 128) && attention_proj_fusable(x.B, Lt, x.C, -1);
+            const bool proj_tail = !in_trunk && !(dbg() & RLDM_FLAG_ATTN_PROJ_LAUNCH) && attention_proj_fusable(x.B, Lt, x.C, -1);
             const bool proj_seam = proj_tail && Builder::cluster_enabled() &&
                                    attention_proj_fusable(x.B, Lt, x.C, Builder::device_cus() / std::max(1, g_concurrent_plans));
             const bool fuse_proj = proj_tail;
@@ -2378,8 +2371,8 @@ struct NetCommon {
                 ap.bias = f->bias.as<float>();
                 ap.out = b.tptr(o);
                 ap.B = x.B; ap.L = Lt; ap.C = x.C;
-                ap.ts = (getenv("RLDM_TS_TRUNK") || getenv("RLDM_TS_ORD")) ? nullptr : g_ts_buf;
-                ap.ts_L = getenv("RLDM_TS_ATTN_L") ? atoi(getenv("RLDM_TS_ATTN_L")) : 0;
+                ap.ts = stamp_buf(StampSite::Attn);
+                ap.ts_L = stamp_env().attn_l ? atoi(stamp_env().attn_l) : 0;
                 double by = (double)x.B * Lt * x.C * 2.0 * 2.0 + 3.0 * x.C * x.C * 2.0;
                 double flp = fl;
                 if (fuse_proj) {
@@ -3084,7 +3077,7 @@ rldm_sampler::~rldm_sampler() {
 static DevBuf g_trace;                 // rldm_debug_graph_trace: 4096 timestamps
 static Plan* g_trace_plan = nullptr;
 
-// (rldm_debug_set_flags(1 << 23) at sampler creation keeps the scheduler step and the step counter as launches of their own)
+// (RLDM_FLAG_SCHED_LAUNCH at sampler creation keeps the scheduler step and the step counter as launches of their own)
 
 // SchedParams / SchedFuse::mode of a sampler's scheduler step (sched_prev)
 static int sampler_sched_mode(const rldm_sampler* s) {
@@ -3112,7 +3105,7 @@ static int sampler_enqueue_step(rldm_sampler* s, SamplerLane* ln, const float* n
     const bool multistep = s->cfg.mode == RLDM_SAMPLER_DPMSOLVER;
     // (the rest of io.sch / io.step_inc: sampler_build_plans; a multistep sampler's x0 history is fixed there)
     if (fused && !multistep) ln->uplan->io.sch.noise = noise;
-    if ((g_dbg_flags | s->plan_flags) & 8192) {
+    if ((g_dbg_flags | s->plan_flags) & RLDM_FLAG_GRAPH_TRACE) {
         if (!g_trace.p) {
             if (g_trace.alloc(4096 * 8)) return 1;
             RLDM_HIP_CHECK(hipMemset(g_trace.p, 0, 4096 * 8));
@@ -3181,7 +3174,7 @@ static int sampler_build_plans(rldm_sampler* s) {
         io.step_ptr = ln->step.as<int>();
         io.temb_rows_per_step = 1;
         io.temb_per_sample = 0;
-        ln->fused_tail = !((g_dbg_flags | s->plan_flags) & (1 << 23));
+        ln->fused_tail = !((g_dbg_flags | s->plan_flags) & RLDM_FLAG_SCHED_LAUNCH);
         if (ln->fused_tail) {
             // the scheduler step rides in conv_out's epilogue, the step index is advanced by pack_input: 2 launches per step fewer
             SchedFuse& f = io.sch;
@@ -3198,8 +3191,8 @@ static int sampler_build_plans(rldm_sampler* s) {
                 f.noise_step_stride = s->n_latent;
             }
             io.step_inc = ln->step.as<int>();
-            // ... and the next step's conv_in input: no pack_input launch inside the steps (rldm_debug_set_flags(64) keeps it)
-            if (!((g_dbg_flags | s->plan_flags) & 64) && io.xin && io.sample_scale == 1.f) {
+            // ... and the next step's conv_in input: no pack_input launch inside the steps
+            if (io.xin && io.sample_scale == 1.f) {
                 io.pack_fused = true;
                 f.pack = io.xin;
                 f.pack_ld = io.xin_ld;
@@ -3346,10 +3339,10 @@ int rldm_unet_forward(rldm_unet* m, const float* sample, const int64_t* timestep
         int terr = 0;
         RLDM_HIP_CHECK(hipMemcpy(&terr, plan->trunk_error.p, 4, hipMemcpyDeviceToHost));
         if (terr != 0) {
-            RLDM_REQUIRE(!((g_dbg_flags | m->plan_flags) & (1 << 24)), "internal: self-check word set without persistent launches");
+            RLDM_REQUIRE(!((g_dbg_flags | m->plan_flags) & RLDM_FLAG_NO_PERSISTENT), "internal: self-check word set without persistent launches");
             fprintf(stderr, "librangeldm_hip: persistent launches of rldm_unet_forward failed their self-check (code %d); this model runs "
                             "one launch per layer from here on\n", terr);
-            m->plan_flags |= (1 << 24);
+            m->plan_flags |= RLDM_FLAG_NO_PERSISTENT;
             m->plans.clear();
             return rldm_unet_forward(m, sample, timesteps, nt, B, out, stream);
         }
@@ -3595,10 +3588,10 @@ int rldm_sampler_create(rldm_unet* unet, rldm_vae* vae, const rldm_sampler_confi
 }
 void rldm_sampler_destroy(rldm_sampler* s) { delete s; }
 
-// this sampler's plans again, every layer a launch of its own (same kernels, same tiles: rldm_debug_set_flags(1 << 24), scoped to it)
+// this sampler's plans again, every layer a launch of its own (same kernels, same tiles: RLDM_FLAG_NO_PERSISTENT, scoped to it)
 static int sampler_drop_persistent(rldm_sampler* s, const char* why, int code) {
     fprintf(stderr, "librangeldm_hip: %s (code %d); this sampler runs one launch per layer from here on\n", why, code);
-    s->plan_flags |= (1 << 24);
+    s->plan_flags |= RLDM_FLAG_NO_PERSISTENT;
     return sampler_build_plans(s);
 }
 
@@ -3672,7 +3665,7 @@ int rldm_sample(rldm_sampler* s, const float* x_T, const float* step_noise, cons
     if (s->latched_error) {                         // found while the plans were rebuilt (sampler_build_plans): the previous call failed
         const int code = s->latched_error;
         s->latched_error = 0;
-        if (!(s->plan_flags & (1 << 24)) && sampler_drop_persistent(s, "a persistent launch of the PREVIOUS rldm_sample call failed its self-check", code)) return 1;
+        if (!(s->plan_flags & RLDM_FLAG_NO_PERSISTENT) && sampler_drop_persistent(s, "a persistent launch of the PREVIOUS rldm_sample call failed its self-check", code)) return 1;
         RLDM_REQUIRE(false, "a persistent launch of the PREVIOUS rldm_sample call failed its self-check (code " + std::to_string(code) +
                                 "): its outputs were invalid (NaN-marked); the sampler now runs one launch per layer: call again");
     }
@@ -3698,7 +3691,7 @@ int rldm_sample(rldm_sampler* s, const float* x_T, const float* step_noise, cons
             if (ln->uplan->trunk_error.p) {         // the persistent trunk's self-check (a wait that gave up / a cluster off its XCD)
                 int terr = 0;
                 RLDM_HIP_CHECK(hipMemcpy(&terr, ln->uplan->trunk_error.p, 4, hipMemcpyDeviceToHost));
-                const bool off = ((g_dbg_flags | s->plan_flags) & (1 << 24)) != 0;
+                const bool off = ((g_dbg_flags | s->plan_flags) & RLDM_FLAG_NO_PERSISTENT) != 0;
                 if (getenv("RLDM_TEST_TRUNK_FAIL") && !off) terr = 2;      // (tests: the fall-back path below)
                 if (terr != 0 && !off) {
                     // the clusters' only assumption (an image's workgroups share an XCD; all of them resident) does not hold on this
@@ -3714,8 +3707,7 @@ int rldm_sample(rldm_sampler* s, const float* x_T, const float* step_noise, cons
             if (launch_step_counter(ln->step.as<int>(), ln->fused_tail ? -1 : 0, 0, st)) return 1;
             // the graph holds `gs` consecutive steps (the step index lives on the device, so the steps are identical launches):
             // fewer, longer graphs keep the queue fed across step boundaries
-            int gs = getenv("RLDM_GRAPH_STEPS") ? atoi(getenv("RLDM_GRAPH_STEPS")) : 10;
-            gs = std::max(1, std::min(gs, s->cfg.num_steps));
+            int gs = std::max(1, std::min(kGraphSteps, s->cfg.num_steps));
             while (s->cfg.num_steps % gs != 0) --gs;
             ln->graph_steps = gs;
             if (capture(st, [&]() {
@@ -3880,9 +3872,9 @@ int make_conv_case(ConvCase& cc, const rldm_conv_desc* d, const float* weight, c
         a.temb_off = with_temb ? 0 : -1;
         a.r0 = cc.tr;
         a.want_stats = true;
-        // rldm_debug_set_flags2(1 << 26): a conv of <= 4 output channels is a network OUTPUT layer -- fp32 NCHW into plan.io.out (the VAE
+        // RLDM_FLAG2_FP32_OUT: a conv of <= 4 output channels is a network OUTPUT layer -- fp32 NCHW into plan.io.out (the VAE
         // decoder's conv_out), no bf16 tensor, no statistics
-        if ((dbg2() & (1 << 26)) && d->Cout <= 4 && !with_res && !with_temb) {
+        if ((dbg2() & RLDM_FLAG2_FP32_OUT) && d->Cout <= 4 && !with_res && !with_temb) {
             a.out_f32_nchw = true;
             a.want_stats = false;
         }
@@ -4059,29 +4051,6 @@ int rldm_bench_conv(const rldm_conv_desc* d, int with_res, int with_temb, int wa
     hipEvent_t e0, e1;
     RLDM_HIP_CHECK(hipEventCreate(&e0));
     RLDM_HIP_CHECK(hipEventCreate(&e1));
-    // RLDM_BENCH_THRASH_MB=n: a sweep over n MB in front of every timed launch (not timed itself): the conv then finds its weights
-    // and input out of the L2s (n ~ 96: Infinity-Cache warm; n >= 512: HBM cold) -- the states a layer meets inside a sampler step
-    const size_t thrash = getenv("RLDM_BENCH_THRASH_MB") ? (size_t)atoi(getenv("RLDM_BENCH_THRASH_MB")) << 20 : 0;
-    if (thrash) {
-        DevBuf tb, sink;
-        if (tb.alloc(thrash) || sink.alloc(64)) return 1;
-        RLDM_HIP_CHECK(hipMemsetAsync(tb.p, 0, thrash, st));
-        double tot = 0.0;
-        for (int i = 0; i < iters; ++i) {
-            if (launch_thrash(tb.p, thrash, sink.as<float>(), st)) return 1;
-            RLDM_HIP_CHECK(hipEventRecord(e0, st));
-            if (run_unit()) return 1;
-            RLDM_HIP_CHECK(hipEventRecord(e1, st));
-            RLDM_HIP_CHECK(hipStreamSynchronize(st));
-            float ms = 0.f;
-            RLDM_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-            tot += ms;
-        }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        *avg_us = (float)(tot * 1000.0 / iters);
-        return 0;
-    }
     RLDM_HIP_CHECK(hipEventRecord(e0, st));
     for (int i = 0; i < iters; ++i)
         if (run_unit()) return 1;
@@ -4164,7 +4133,7 @@ int make_attn_case(AttnCase& ac, const std::vector<bf16_t>& hb, int B, int L, in
     ap.magic_cpg = ((1 << 20) + cpg - 1) / cpg;
     ap.wfrag = ac.dw.as<bf16_t>(); ap.bias = ac.dbias.as<float>(); ap.out = ac.dout.as<bf16_t>();
     ap.B = B; ap.L = L; ap.C = C;
-    ap.ts = getenv("RLDM_TS_TRUNK") ? nullptr : g_ts_buf;                                  // ABLATE builds: phase stamps (rldm_debug_timestamps)
+    ap.ts = stamp_buf(StampSite::TestAttn);                                                 // ABLATE builds: phase stamps (rldm_debug_timestamps)
     ap.ts_L = L;
     return 0;
 }

@@ -17,6 +17,26 @@ def _header_symbols():
     return sorted(set(re.findall(r"\b(rldm_[a-z0-9_]+)\s*\(", src)))
 
 
+def _header_enum(name):
+    src = open(os.path.join(ROOT, "include", "rangeldm_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    body = re.search(r"enum\s+" + name + r"\s*\{(.*?)\}", src, flags=re.S).group(1)
+    out = {}
+    for item in body.split(","):
+        key, val = (t.strip() for t in item.split("="))
+        m = re.fullmatch(r"1\s*<<\s*(\d+)", val)
+        out[key] = 1 << int(m.group(1)) if m else int(val)
+    return out
+
+
+def test_flag_enums_mirror_header():
+    from rangeldm_amd import _lib
+    for enum_name, prefix, py in (("rldm_flag", "RLDM_FLAG_", _lib.Flag), ("rldm_flag2", "RLDM_FLAG2_", _lib.Flag2)):
+        header = _header_enum(enum_name)
+        assert header and all(k.startswith(prefix) for k in header)
+        assert {k[len(prefix):]: v for k, v in header.items()} == {m.name: int(m.value) for m in py}
+
+
 def test_library_exports_every_declared_symbol():
     from rangeldm_amd import _lib
     if not os.path.exists(_lib.LIB_PATH):

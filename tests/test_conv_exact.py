@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from oracle import ops
+from rangeldm_amd._lib import Flag, Flag2
 from tests.hip_util import (RefCache, amax, assert_bitexact, assert_exact_bound, bf16_rne, hip_conv, int_grid, silu_targets)
 from tests.test_hip_kernels import CONV_CASES, GN_CASES, conv_flags, regw_flags  # noqa: F401  (fixtures)
 
@@ -172,7 +173,8 @@ def test_conv_pointwise_gn_gamma0_exact(B, C, N, W, H, res):
 
 
 @pytest.mark.parametrize("B,W,H,N", [(4, 512, 64, 2), (2, 128, 16, 1), (3, 64, 32, 4)])
-@pytest.mark.parametrize("flags", [1 << 26, (1 << 26) | (1 << 25), (1 << 26) | (1 << 24)], ids=["default", "runs-of-8-workgroups", "generic-kernel"])
+@pytest.mark.parametrize("flags", [Flag2.FP32_OUT, Flag2.FP32_OUT | Flag2.REGW_CAP8, Flag2.FP32_OUT | Flag2.NO_REGW],
+                         ids=["default", "runs-of-8-workgroups", "generic-kernel"])
 def test_conv_out_fp32_nchw_gamma0_exact(B, W, H, N, flags):
     """the VAE decoder's output layer (fp32 NCHW, no output rounding): equal to the fp64 reference."""
     from rangeldm_amd import _lib
@@ -195,9 +197,9 @@ def test_unet_output_layer_gamma0_exact(B, W, H, N, route):
     x, w, b = _x((B, 128, W, H), 181), _w((N, 128, 3, 3), 182), _b((N,), 183)
     beta, h = _gn_beta(128, 184, True)
     assert_exact_bound(HU * U, (1152, 2 * amax(w)), (1, amax(b)))
-    _lib.lib().rldm_debug_set_flags2(1 << 26)
+    _lib.lib().rldm_debug_set_flags2(Flag2.FP32_OUT)
     if route == "generic":
-        _lib.lib().rldm_debug_set_flags(256 + 2048)
+        _lib.lib().rldm_debug_set_flags(Flag.NO_CONV_SMALL | Flag.NO_STREAM_REGW)
     try:
         y = hip_conv(x, w, b, gamma=torch.zeros(128), beta=beta, silu=True, eps=1e-5)
     finally:
@@ -212,7 +214,7 @@ def test_conv_out_fp32_nchw_exact(B, W, H, N):
     from rangeldm_amd import _lib
     x, w, b = _x((B, 64, W, H), 191), _w((N, 64, 3, 3), 192), _b((N,), 193)
     assert_exact_bound(U, (576, amax(x) * amax(w)), (1, amax(b)))
-    _lib.lib().rldm_debug_set_flags2(1 << 26)
+    _lib.lib().rldm_debug_set_flags2(Flag2.FP32_OUT)
     try:
         y = hip_conv(x, w, b)
     finally:

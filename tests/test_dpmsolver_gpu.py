@@ -175,14 +175,14 @@ def test_captured_upscale_and_pixel_samplers_match_eager_loop(golden):
 
 
 def test_separate_launch_tail_and_lanes_match_fused_tail(monkeypatch):
-    """rldm_debug_set_flags(1 << 23) at sampler creation: the scheduler step as sched_step_kernel launches of their own, against
+    """rldm_debug_set_flags(Flag.SCHED_LAUNCH) at sampler creation: the scheduler step as sched_step_kernel launches of their own, against
     the step in conv_out's epilogue; and a sampler split into two lanes (each with its own x0 history)."""
     from rangeldm_amd.pipelines import LDMPipelineRange
     cfg = small_cfg(5, 4)
     vae, _ = hip_vae()
     x_T = T(normal(86, "dpm/xT4", (4, 4, 32, 8)))
     outs = {}
-    for key, flags in (("fused", 0), ("separate", 1 << 23)):
+    for key, flags in (("fused", 0), ("separate", _lib.Flag.SCHED_LAUNCH)):
         _lib.lib().rldm_debug_set_flags(flags)
         try:
             unet, _ = hip_unet(cfg, "dpm/small.")
@@ -226,11 +226,11 @@ def test_sampler_keeps_no_state_between_calls():
 # ---- full width ------------------------------------------------------------------------------------------------------------
 def test_batch16_sampler_clusters_match_launch_per_layer():
     """BASELINE config 2 at its real batch, 20 DPM++ steps through the captured sampler: the persistent clusters against
-    rldm_debug_set_flags(1 << 26) (one launch per layer).  Same kernels on the same operands: identical images."""
+    rldm_debug_set_flags(Flag.NO_CLUSTERS) (one launch per layer).  Same kernels on the same operands: identical images."""
     from rangeldm_amd.pipelines import LDMPipelineRange
     x_T = T(normal(88, "dpm/b16/xT", (16, 4, 256, 16)))
     outs = []
-    for flags in (0, 1 << 26):
+    for flags in (0, _lib.Flag.NO_CLUSTERS):
         _lib.lib().rldm_debug_set_flags(flags)
         try:
             unet, _ = hip_unet(UNetConfig(), "")

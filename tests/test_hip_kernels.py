@@ -8,6 +8,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from rangeldm_amd._lib import Flag, Flag2
 from oracle import ops
 from tests.hip_util import (bf16r, rel_l2, hip_conv, hip_attention, hip_attention_qkv, hip_conv_stats, assert_banded_rel_l2,
                             assert_banded_rel_l2_tokens)
@@ -125,22 +126,27 @@ GN_CASES = [(256, 256, 256, 32, 1), (128, 128, 128, 32, 16), (256, 128, 256, 16,
             (256, 256, 192, 32, 8), (256, 256, 128, 64, 8)]  # (4-wave conv_stream instances, 512 input channels: two channels per thread in the GroupNorm fold)   # (conv_stream.hip <2, 2>: 64 output channels, identity residual of 64)
 
 
-@pytest.fixture(params=[0, 1024, 4096, (4096, 7), (4096, 7 + 32), (4096, 64), 256 + 2048, 524288, 1 << 22],
+_8WAVES = Flag2.STREAM_8WAVE_FULL | Flag2.STREAM_8WAVE_128X8 | Flag2.STREAM_8WAVE_C64
+
+
+@pytest.fixture(params=[0, Flag.SMALL_128PX, Flag.STREAM_ANY_GRID, (Flag.STREAM_ANY_GRID, _8WAVES),
+                        (Flag.STREAM_ANY_GRID, _8WAVES | Flag2.STREAM_SPEC_WAVES), (Flag.STREAM_ANY_GRID, Flag2.STREAM_64PX),
+                        Flag.NO_CONV_SMALL | Flag.NO_STREAM_REGW, Flag.SMALL_64PX_32X2, Flag.OWN_IMAGE_COPIES],
                 ids=["default", "small-128px-tiles", "stream-any-grid", "stream-any-grid-8-waves", "stream-any-grid-specialised-waves",
                      "stream-any-grid-64px-tiles", "generic-only", "level3-64px-tiles", "own-image-tiles"])
 def conv_flags(request):
-    """Routing of the conv launches: 0 default; 1024 also sends the 128x8 level to conv_small.hip (128-pixel tiles);
-    4096 sends every eligible 3x3 to conv_stream.hip regardless of the grid size (by default it needs >= 128 workgroups);
-    256 + 2048 keeps everything on the generic implicit-GEMM kernel; 524288 keeps 32x2 images on one 64-pixel conv_small tile
-    (by default they run as two 32-pixel tiles); 1 << 22 makes every conv that can own a whole image (<= 64 pixels, conv_small.hip)
-    do so and write two normalised copies of its output (producer-side GroupNorm epilogue; the copies are checked at network level:
+    """Routing of the conv launches: 0 default; SMALL_128PX also sends the 128x8 level to conv_small.hip (128-pixel tiles);
+    STREAM_ANY_GRID sends every eligible 3x3 to conv_stream.hip regardless of the grid size (by default it needs >= 128 workgroups);
+    NO_CONV_SMALL | NO_STREAM_REGW keeps everything on the generic implicit-GEMM kernel; SMALL_64PX_32X2 keeps 32x2 images on one
+    64-pixel conv_small tile (by default they run as two 32-pixel tiles); OWN_IMAGE_COPIES makes every conv that can own a whole
+    image (<= 64 pixels, conv_small.hip) do so and write two normalised copies of its output (producer-side GroupNorm epilogue; the copies are checked at network level:
     test_producer_side_groupnorm_matches_consumer_side)."""
     from rangeldm_amd import _lib
     f1, f2 = request.param if isinstance(request.param, tuple) else (request.param, 0)
     _lib.lib().rldm_debug_set_flags(f1)
-    _lib.lib().rldm_debug_set_flags2(f2)      # (7: round 4's 4-wave conv_stream workgroups off -> the 8-wave instances keep their coverage;
-                                              #  32: the 256 x 128 tile runs with specialised matrix / staging waves;
-                                              #  64: 8 x 8 tiles x 128 channels x 2 k-groups wherever 128 | N -- the 128x8 level's default)
+    _lib.lib().rldm_debug_set_flags2(f2)      # (_8WAVES: round 4's 4-wave conv_stream workgroups off -> the 8-wave instances keep their coverage;
+                                              #  STREAM_SPEC_WAVES: the 256 x 128 tile runs with specialised matrix / staging waves;
+                                              #  STREAM_64PX: 8 x 8 tiles x 128 channels x 2 k-groups wherever 128 | N -- the 128x8 level's default)
     yield f1
     _lib.lib().rldm_debug_set_flags(0)
     _lib.lib().rldm_debug_set_flags2(0)
@@ -170,10 +176,10 @@ def test_conv_gn_silu_concat_temb_residual(C0, C1, Cout, W, H, conv_flags):
     assert_banded_rel_l2(y, ref(bf16r), TOL_Q, groups=32, what=f"{(C0, C1, Cout, W, H)} flags {conv_flags}")
 
 
-@pytest.fixture(params=[0, 1 << 25, 1 << 24], ids=["default", "runs-of-8-workgroups", "per-tile-kernel"])
+@pytest.fixture(params=[0, Flag2.REGW_CAP8, Flag2.NO_REGW], ids=["default", "runs-of-8-workgroups", "per-tile-kernel"])
 def regw_flags(request):
     """conv_regw.hip (64 -> 64 channels, weights in registers, a run of 16 x 8 tiles per workgroup): by default where an image batch has at
-    least 2048 tiles; 1 << 25 caps the grid at 8 workgroups so that small images are walked in runs too; 1 << 24 keeps conv_stream's
+    least 2048 tiles; REGW_CAP8 caps the grid at 8 workgroups so that small images are walked in runs too; NO_REGW keeps conv_stream's
     per-tile instance (the comparison)."""
     from rangeldm_amd import _lib
     _lib.lib().rldm_debug_set_flags2(request.param)
@@ -234,10 +240,11 @@ def test_conv_c64_register_weights_ping_pong_variant():
 
 
 @pytest.mark.parametrize("B,W,H,N", [(4, 512, 64, 2), (2, 128, 16, 2), (3, 64, 32, 4), (2, 1024, 64, 2), (2, 128, 16, 1)])
-@pytest.mark.parametrize("flags", [1 << 26, (1 << 26) | (1 << 25), (1 << 26) | (1 << 24)], ids=["default", "runs-of-8-workgroups", "generic-kernel"])
+@pytest.mark.parametrize("flags", [Flag2.FP32_OUT, Flag2.FP32_OUT | Flag2.REGW_CAP8, Flag2.FP32_OUT | Flag2.NO_REGW],
+                         ids=["default", "runs-of-8-workgroups", "generic-kernel"])
 def test_conv_out_fp32_nchw(B, W, H, N, flags):
     """The VAE decoder's output layer: GroupNorm(32) + SiLU -> conv3x3 (64 -> 2) written as fp32 NCHW by the kernel itself
-    (rldm_debug_set_flags2(1 << 26) makes the test conv such an output layer): conv_regw.hip's one-tile variant, or the generic kernel."""
+    (rldm_debug_set_flags2(Flag2.FP32_OUT) makes the test conv such an output layer): conv_regw.hip's one-tile variant, or the generic kernel."""
     from rangeldm_amd import _lib
     x = _rand(B, 64, W, H, seed=70) * 1.3 + 0.2
     w = _rand(N, 64, 3, 3, seed=71, scale=(64 * 9) ** -0.5)
@@ -263,15 +270,15 @@ def test_conv_out_fp32_nchw(B, W, H, N, flags):
 @pytest.mark.parametrize("route", ["conv_o4", "generic"])
 def test_unet_output_layer_fp32_nchw(B, W, H, N, route):
     """The UNet's conv_out: GroupNorm(32) + SiLU over 128 channels -> conv3x3 -> N <= 4 channels as fp32 NCHW (conv_regw.hip's conv_o4_kernel:
-    a wave per 32 input channels; RLDM_NO_O4 is read once per process, so the generic kernel is reached through its force-tile switch)."""
+    a wave per 32 input channels; the generic kernel is reached through Flag.NO_CONV_SMALL | Flag.NO_STREAM_REGW)."""
     from rangeldm_amd import _lib
     x = _rand(B, 128, W, H, seed=80) * 1.2 - 0.1
     w = _rand(N, 128, 3, 3, seed=81, scale=(128 * 9) ** -0.5)
     b = _rand(N, seed=82, scale=0.1)
     gamma, beta = 1 + 0.2 * _rand(128, seed=83), 0.2 * _rand(128, seed=84)
-    _lib.lib().rldm_debug_set_flags2(1 << 26)
+    _lib.lib().rldm_debug_set_flags2(Flag2.FP32_OUT)
     if route == "generic":
-        _lib.lib().rldm_debug_set_flags(256 + 2048)
+        _lib.lib().rldm_debug_set_flags(Flag.NO_CONV_SMALL | Flag.NO_STREAM_REGW)
     try:
         y = hip_conv(x, w, b, gamma=gamma, beta=beta, silu=True, eps=1e-5)
     finally:

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from rangeldm_amd.config import UNetConfig, VAEConfig
+from rangeldm_amd._lib import Flag, Flag2
 from rangeldm_amd.params import unet_param_shapes, vae_param_shapes
 from rangeldm_amd.synth import synth_state_dict, normal
 from oracle import unet as o_unet, vae as o_vae, schedulers as o_sched, pipelines as o_pipe
@@ -80,13 +81,13 @@ def test_wide_concatenation_runs_half_by_half(size, B):
     tile takes: the resnet runs as gn_apply (two outputs) + conv1 in two halves + conv2 (+ the shortcut as one or two pointwise convs),
     NetCommon::resnet_wide.  A two-level 512-channel UNet exercises both forms -- (64, 8): the 64-pixel tiles of the 512-pixel level, where
     the 3x3 tile and the shortcut's tile do not fit the LDS together -- against the oracle, and against the same network on the generic
-    kernel (rldm_debug_set_flags(1 << 21))."""
+    kernel (rldm_debug_set_flags(Flag.NO_WIDE_SPLIT))."""
     from rangeldm_amd import _lib
     cfg = UNetConfig(sample_size=size, block_out_channels=(512, 512), down_block_types=("DownBlock2D", "AttnDownBlock2D"),
                      up_block_types=("AttnUpBlock2D", "UpBlock2D"))
     x = T(normal(17, "x", (B, cfg.in_channels, *cfg.sample_size)))
     outs, launches = [], []
-    for flags in (0, 1 << 21):
+    for flags in (0, Flag.NO_WIDE_SPLIT):
         _lib.lib().rldm_debug_set_flags(flags)
         try:
             m, sd = hip_unet(cfg, "wide.")
@@ -104,13 +105,13 @@ def test_wide_concatenation_runs_half_by_half(size, B):
 @pytest.mark.parametrize("B", [8, 16])
 def test_fused_attention_projection_matches_separate_launch(B):
     """The 1024-token attention launch carries the block's output projection (+ x, + GroupNorm statistics) behind a cluster seam
-    (attention_proj_tail); rldm_debug_set_flags(128) keeps the projection a conv_small launch, 1 << 24 runs the SAME tail as a launch of
-    its own (identical bits).  All three against the oracle."""
+    (attention_proj_tail); rldm_debug_set_flags(Flag.ATTN_PROJ_LAUNCH) keeps the projection a conv_small launch, NO_PERSISTENT runs
+    the SAME tail as a launch of its own (identical bits).  All three against the oracle."""
     from rangeldm_amd import _lib
     cfg = UNetConfig()
     x = T(normal(19, "x", (B, cfg.in_channels, *cfg.sample_size)))
     outs, launches = {}, {}
-    for flags in (0, 128, 1 << 24):
+    for flags in (0, Flag.ATTN_PROJ_LAUNCH, Flag.NO_PERSISTENT):
         _lib.lib().rldm_debug_set_flags(flags)
         try:
             m, sd = hip_unet(cfg, "fp.")
@@ -120,10 +121,10 @@ def test_fused_attention_projection_matches_separate_launch(B):
         finally:
             _lib.lib().rldm_debug_set_flags(0)
     ref = o_unet.OracleUNet(cfg, sd)(x[:2], 450).sample
-    assert launches[0] == launches[128] - 5                    # five attention blocks at 1024 tokens
-    assert torch.equal(outs[0], outs[1 << 24])
-    assert rel_l2(outs[0][:2], ref) < TOL_FWD and rel_l2(outs[128][:2], ref) < TOL_FWD
-    assert rel_l2(outs[0], outs[128]) < TOL_FWD / 2
+    assert launches[0] == launches[Flag.ATTN_PROJ_LAUNCH] - 5          # five attention blocks at 1024 tokens
+    assert torch.equal(outs[0], outs[Flag.NO_PERSISTENT])
+    assert rel_l2(outs[0][:2], ref) < TOL_FWD and rel_l2(outs[Flag.ATTN_PROJ_LAUNCH][:2], ref) < TOL_FWD
+    assert rel_l2(outs[0], outs[Flag.ATTN_PROJ_LAUNCH]) < TOL_FWD / 2
 
 
 def test_unet_forward_nuscenes_config():
@@ -152,13 +153,13 @@ def test_unet_forward_full_config_golden(golden):
 def test_producer_side_groupnorm_matches_consumer_side(size):
     """Producer-side GroupNorm (conv_small.hip epilogue: a conv whose tile owns a whole <= 64-pixel image writes the normalised +
     activated copies its consumers read) against the same network with every GroupNorm applied by the consumer
-    (rldm_debug_set_flags(1048576)): the arithmetic is the same, only the summation split of the statistics (one 64-pixel tile
+    (rldm_debug_set_flags(Flag.CONSUMER_GN)): the arithmetic is the same, only the summation split of the statistics (one 64-pixel tile
     against two 32-pixel tiles) differs, and a last-bit change of a scale flips bf16 roundings downstream -- so the two forwards differ by about what either differs from the oracle."""
     from rangeldm_amd import _lib
     cfg = UNetConfig(sample_size=size)
     x = T(normal(11, "x", (2, cfg.in_channels, *cfg.sample_size))).cuda()
     outs = []
-    for flags in (0, 1048576):
+    for flags in (0, Flag.CONSUMER_GN):
         _lib.lib().rldm_debug_set_flags(flags)
         try:
             m, _ = hip_unet(cfg, "ps.")
@@ -179,13 +180,13 @@ def test_persistent_trunk_matches_separate_launches(B, size):
     """The persistent trunk launch (trunk.hip: the convs of the 32x2 level and the mid block as phases of one launch, the channel
     tiles of an image handing over through their XCD's L2; from 13 images on also the 64x4 level as multi-tile clusters -- 4 pixel
     tiles x 4 channel tiles per image, GroupNorm folds and gn_apply as phases) against the same plan as separate launches
-    (rldm_debug_set_flags(1 << 24)): the SAME kernels' code on the SAME operands in the same order, so the outputs are identical,
+    (rldm_debug_set_flags(Flag.NO_PERSISTENT)): the SAME kernels' code on the SAME operands in the same order, so the outputs are identical,
     and repeated forwards (the cluster counters re-arm themselves) stay identical."""
     from rangeldm_amd import _lib
     cfg = UNetConfig(sample_size=size)              # (256, 8): the nuScenes network, whose lowest level has 32 x 1 images
     x = T(normal(13, "x", (B, cfg.in_channels, *cfg.sample_size))).cuda()
     outs, launches = [], []
-    for flags in (0, 1 << 24):
+    for flags in (0, Flag.NO_PERSISTENT):
         _lib.lib().rldm_debug_set_flags(flags)
         try:
             m, _ = hip_unet(cfg, "tk.")
@@ -205,15 +206,15 @@ def test_persistent_trunk_matches_separate_launches(B, size):
 @pytest.mark.parametrize("B,size", [(16, (256, 16)), (24, (256, 8))])      # (24 x 16 tiles = 384 workgroups: where the 8-beam level takes the 4-wave instance)
 def test_full_height_tiles_in_and_out_of_the_persistent_launch(B, size):
     """conv_stream's tiles as tall as the image (8 x 16 on 16-beam levels, 16 x 8 on 8-beam ones: the halo rows above / below are never
-    staged) against the 16 x 8 tiles with a staged halo ring (rldm_debug_set_flags2(1 << 29)), each as phases of the persistent launch and as
-    launches of their own (rldm_debug_set_flags(1 << 24)).  The kernel picks its instance from the phase record, not from the tile's shape:
-    a 16 x 8 tile on an 8-beam level is BOTH shapes."""
+    staged) against the 16 x 8 tiles with a staged halo ring (rldm_debug_set_flags2(Flag2.HALO_RING)), each as phases of the persistent launch
+    and as launches of their own (rldm_debug_set_flags(Flag.NO_PERSISTENT)).  The kernel picks its instance from the phase record, not
+    from the tile's shape: a 16 x 8 tile on an 8-beam level is BOTH shapes."""
     from rangeldm_amd import _lib
     cfg = UNetConfig(sample_size=size)
     x = T(normal(17, "x", (B, cfg.in_channels, *cfg.sample_size))).cuda()
     outs = {}
-    for f2 in (0, 1 << 29):
-        for f1 in (0, 1 << 24):
+    for f2 in (0, Flag2.HALO_RING):
+        for f1 in (0, Flag.NO_PERSISTENT):
             _lib.lib().rldm_debug_set_flags(f1)
             _lib.lib().rldm_debug_set_flags2(f2)
             try:
@@ -225,11 +226,11 @@ def test_full_height_tiles_in_and_out_of_the_persistent_launch(B, size):
             finally:
                 _lib.lib().rldm_debug_set_flags(0)
                 _lib.lib().rldm_debug_set_flags2(0)
-    for f2 in (0, 1 << 29):
-        assert torch.equal(outs[(f2, 0)], outs[(f2, 1 << 24)])
+    for f2 in (0, Flag2.HALO_RING):
+        assert torch.equal(outs[(f2, 0)], outs[(f2, Flag.NO_PERSISTENT)])
     # two tilings of the same sums: the statistics partials are grouped differently, nothing else (bf16 roundings flip and travel through
     # the network: measured 2.6e-3; the same bound as the other plan variants)
-    assert rel_l2(outs[(0, 0)], outs[(1 << 29, 0)]) < TOL_FWD / 2
+    assert rel_l2(outs[(0, 0)], outs[(Flag2.HALO_RING, 0)]) < TOL_FWD / 2
 
 
 def test_unet_errors():
@@ -481,7 +482,7 @@ def test_full_config_sampler_properties():
 def test_batch16_sampler_clusters_match_launch_per_layer(sched_name):
     """BASELINE config 2 at its real batch (16 images: every level of the UNet runs as clusters of 16 workgroups per image inside
     persistent launches, trunk.hip) through the CAPTURED sampler -- step graphs, fused scheduler tail, VAE decode -- against the same
-    sampler with the clusters off (rldm_debug_set_flags(1 << 26): one launch per layer above the 32x2 level).  Same kernels' code on
+    sampler with the clusters off (rldm_debug_set_flags(Flag.NO_CLUSTERS): one launch per layer above the 32x2 level).  Same kernels' code on
     the same operands: identical images; the launch count drops."""
     from rangeldm_amd import _lib
     from rangeldm_amd.pipelines import LDMPipelineRange
@@ -490,7 +491,7 @@ def test_batch16_sampler_clusters_match_launch_per_layer(sched_name):
     x_T = T(normal(21, "xT", (16, 4, 256, 16)))
     zs = T(normal(22, "zs", (3, 16, 4, 256, 16)))
     outs, launches = [], []
-    for flags in (0, 1 << 26):
+    for flags in (0, Flag.NO_CLUSTERS):
         _lib.lib().rldm_debug_set_flags(flags)
         try:
             unet, _ = hip_unet(cfg, "")
@@ -532,7 +533,7 @@ def test_sampler_falls_back_when_the_cluster_self_check_fails(monkeypatch):
             assert torch.isfinite(outs[-1]).all()
     finally:
         monkeypatch.delenv("RLDM_TEST_TRUNK_FAIL", raising=False)
-        _lib.lib().rldm_debug_set_flags(0)              # (the fall-back sets 1 << 24 for the process)
+        _lib.lib().rldm_debug_set_flags(0)              # (the fall-back sets Flag.NO_PERSISTENT for the process)
     assert torch.equal(outs[0], outs[1])
 
 

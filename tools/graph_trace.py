@@ -2,7 +2,7 @@
 """Timeline of the UNet launches as they run back to back inside the sampler's captured step graph.
 
 A host-side profiler (rocprofv3 --kernel-trace) spaces the kernels out; here a one-thread kernel writes the 100 MHz
-real-time counter between consecutive launches of the graph itself (rldm_debug_set_flags(8192) before the sampler is
+real-time counter between consecutive launches of the graph itself (rldm_debug_set_flags(Flag.GRAPH_TRACE) before the sampler is
 built), so the deltas are the durations the launches have in the production regime (+ the constant cost of the stamp
 launch, printed as the median gap of the cheapest op).
 
@@ -31,7 +31,7 @@ def main():
     ap.add_argument("--preset", default="RangeLDM", help="RangeLDM | nuscenes | RangeDM (config.PRESETS)")
     a = ap.parse_args()
     _lib.require_gpu()
-    _lib.lib().rldm_debug_set_flags(8192 | a.flags)
+    _lib.lib().rldm_debug_set_flags(_lib.Flag.GRAPH_TRACE | a.flags)
     from rangeldm_amd.pipelines import LDMPipelineRange, DDIMPipelineRange
     from rangeldm_amd.schedulers import DDIMSchedulerHIP
     from rangeldm_amd.synth import latent_noise
