@@ -8,10 +8,6 @@
 
 #include <type_traits>
 
-#ifndef RLDM_ATTN_WEAVE
-#define RLDM_ATTN_WEAVE 1           /* 0: the round-2 block form of the two-chain key loop (A/B builds) */
-#endif
-
 namespace rldm {
 
 // One 32-query tile against all Lp keys staged in LDS (sK rows, sVt = V^T in consumption order + ones + zero rows).
@@ -306,7 +302,7 @@ __device__ __forceinline__ void attention_qkv2_body(const AttnQkvParams& p, cons
         for (int j = 0; j < KB; ++j)
             if ((j & ~3) < nks) {
                 const int row = min((T0 + ti * wph) * 32 + (j & 3) * 8 + xr8, L - 1);
-                xpre[ti][j] = ld_act_frag<TRUNK>(xt + (size_t)row * C + (j >> 2) * 64);
+                xpre[ti][j] = ld_act_frag(xt + (size_t)row * C + (j >> 2) * 64);
             }
     }
 
@@ -337,19 +333,19 @@ __device__ __forceinline__ void attention_qkv2_body(const AttnQkvParams& p, cons
             for (; q + 8 <= p.P; q += 8) {
                 float2 v[8];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = ld_act8<TRUNK>(src + (size_t)(q + j) * C);
+                for (int j = 0; j < 8; ++j) v[j] = ld_act8(src + (size_t)(q + j) * C);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) { S += (double)v[j].x; SS += (double)v[j].y; }
             }
             for (; q + 4 <= p.P; q += 4) {                // (P = 4 at the 64x4 level: one round trip, not four dependent ones)
                 float2 v[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = ld_act8<TRUNK>(src + (size_t)(q + j) * C);
+                for (int j = 0; j < 4; ++j) v[j] = ld_act8(src + (size_t)(q + j) * C);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { S += (double)v[j].x; SS += (double)v[j].y; }
             }
             for (; q < p.P; ++q) {
-                const float2 v = ld_act8<TRUNK>(src + (size_t)q * C);
+                const float2 v = ld_act8(src + (size_t)q * C);
                 S += (double)v.x;
                 SS += (double)v.y;
             }
@@ -431,7 +427,7 @@ __device__ __forceinline__ void attention_qkv2_body(const AttnQkvParams& p, cons
             for (int j = 0; j < KB; ++j) {
                 if (k0 == 0) xv[j] = xpre[ti][j];
                 else if (k0 + (j & ~3) < nks)
-                    xv[j] = ld_act_frag<TRUNK>(xt + (size_t)min(T * 32 + (j & 3) * 8 + xr8, L - 1) * C + ((k0 + j) >> 2) * 64);
+                    xv[j] = ld_act_frag(xt + (size_t)min(T * 32 + (j & 3) * 8 + xr8, L - 1) * C + ((k0 + j) >> 2) * 64);
             }
 #pragma unroll
             for (int g = 0; g < KB / 4; ++g) {
@@ -516,7 +512,6 @@ __device__ __forceinline__ void attention_qkv2_body(const AttnQkvParams& p, cons
 #pragma unroll
     for (int r = 0; r < 16; ++r) { oA[r] = 0.f; oB[r] = 0.f; }
     uint4 v0, v1;
-#if RLDM_ATTN_WEAVE
     if constexpr (PAIR) {
         // (round 5) the two chains WOVEN at instruction granularity instead of block by block: in the block form a wave issued
         // [24 VALU][PV][PV][S] per chain and stalled twice per chain at the matrix pipe (PV2 behind PV1 on the same accumulator, S behind
@@ -592,11 +587,9 @@ __device__ __forceinline__ void attention_qkv2_body(const AttnQkvParams& p, cons
         };
         if (ragged) key_loop(std::true_type{});
         else key_loop(std::false_type{});
-    } else
-#endif
-    {
+    } else {
+    // one chain (PAIR == false): the block form
     sA = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf), __builtin_bit_cast(bf16x8, qB[0]), zero, 0, 0, 0);
-    if (PAIR) sB = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf), __builtin_bit_cast(bf16x8, qB[TPW - 1]), zero, 0, 0, 0);
     kf = *reinterpret_cast<const uint4*>(kptr);
     kptr += kstep;
     v0 = *reinterpret_cast<const uint4*>(vptr);
@@ -605,7 +598,7 @@ __device__ __forceinline__ void attention_qkv2_body(const AttnQkvParams& p, cons
         if (ragged && k0 + 32 > L) {                      // last tile: keys >= L get -inf scores
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                if (k0 + (r & 3) + 8 * (r >> 2) + 4 * hh >= L) { sA[r] = -1e30f; if (PAIR) sB[r] = -1e30f; }
+                if (k0 + (r & 3) + 8 * (r >> 2) + 4 * hh >= L) sA[r] = -1e30f;
         }
         uint32_t pk[8];
 #pragma unroll
@@ -617,17 +610,6 @@ __device__ __forceinline__ void attention_qkv2_body(const AttnQkvParams& p, cons
                                                      __builtin_bit_cast(bf16x8, make_uint4(pk[4], pk[5], pk[6], pk[7])), oA, 0, 0, 0);
         sA = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf), __builtin_bit_cast(bf16x8, qB[0]), zero, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
-        if (PAIR) {
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) pk[r >> 1] = pack_bf16x2(__builtin_amdgcn_exp2f(sB[r]), __builtin_amdgcn_exp2f(sB[r + 1]));
-            __builtin_amdgcn_sched_barrier(0);
-            oB = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, v0),
-                                                         __builtin_bit_cast(bf16x8, make_uint4(pk[0], pk[1], pk[2], pk[3])), oB, 0, 0, 0);
-            oB = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, v1),
-                                                         __builtin_bit_cast(bf16x8, make_uint4(pk[4], pk[5], pk[6], pk[7])), oB, 0, 0, 0);
-            sB = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf), __builtin_bit_cast(bf16x8, qB[TPW - 1]), zero, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
         // next iteration's fragments (consumed a whole chain of exponentials from now)
         kf = *reinterpret_cast<const uint4*>(kptr);
         kptr += kstep;

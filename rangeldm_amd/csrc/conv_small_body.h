@@ -1,15 +1,11 @@
 // Body of conv_small_kernel (conv_small.hip) as a device function, shared with the persistent trunk kernel (trunk.hip).
 // TRUNK = false: one launch = one conv (arguments from the kernel-argument segment).
 // TRUNK = true : one PHASE of a persistent launch: the arguments live in device memory, the weight ring arrives prefetched, the
-//                activations another workgroup of the image's cluster published are read past the L1 (nontemporal loads), and the
+//                activations another workgroup of the image's cluster published are read behind one L1 invalidate (trunk_seam.h), and the
 //                phase ends by publishing (arrive on the cluster's counter) instead of by a kernel boundary.
 #pragma once
 #include "kernels.h"
 #include "trunk_seam.h"
-
-#ifndef RLDM_H16_NB
-#define RLDM_H16_NB 3               /* k-steps of pixel fragments per LDS block of the 16-channel K loop (x 4 fragments each) */
-#endif
 
 namespace rldm {
 
@@ -141,19 +137,19 @@ __device__ __forceinline__ void conv_small_body(const ConvParams& p, const int n
         for (; q + 8 <= P; q += 8) {            // (8 pixel tiles per image -- 128x4 / 128x8 inputs: one round trip instead of two)
             float2 u[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) u[j] = ld_act8<TRUNK>(src + (size_t)(q + j) * Ct);
+            for (int j = 0; j < 8; ++j) u[j] = ld_act8(src + (size_t)(q + j) * Ct);
 #pragma unroll
             for (int j = 0; j < 8; ++j) { gS += (double)u[j].x; gSS += (double)u[j].y; }
         }
         for (; q + 4 <= P; q += 4) {
             float2 u[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) u[j] = ld_act8<TRUNK>(src + (size_t)(q + j) * Ct);
+            for (int j = 0; j < 4; ++j) u[j] = ld_act8(src + (size_t)(q + j) * Ct);
 #pragma unroll
             for (int j = 0; j < 4; ++j) { gS += (double)u[j].x; gSS += (double)u[j].y; }
         }
         for (; q < P; ++q) {
-            const float2 u = ld_act8<TRUNK>(src + (size_t)q * Ct);
+            const float2 u = ld_act8(src + (size_t)q * Ct);
             gS += (double)u.x;
             gSS += (double)u.y;
         }
@@ -210,13 +206,13 @@ __device__ __forceinline__ void conv_small_body(const ConvParams& p, const int n
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const int q = tid + i * NT;
-            if (NPIECE % NT == 0 || q < NPIECE) v[i] = ld_act16<TRUNK>(img + (size_t)q * 16);
+            if (NPIECE % NT == 0 || q < NPIECE) v[i] = ld_act16(img + (size_t)q * 16);
         }
         // halo columns (3x3): piece hq = (side, row, c8); side 0 -> LDS column 0 <- image column W - 1, side 1 -> column TW + 1 <- 0
         const int nhalo = HALO ? 2 * p.TH * C8 : 0;
         const int hside = tid / (p.TH * C8), hrem = tid - hside * (p.TH * C8);
         if (HALO && tid < nhalo)
-            hv[0] = ld_act16<TRUNK>(img + ((size_t)(hside ? 0 : (p.TW - 1) * p.TH) * C8 + hrem) * 16);
+            hv[0] = ld_act16(img + ((size_t)(hside ? 0 : (p.TW - 1) * p.TH) * C8 + hrem) * 16);
         RLDM_STAMP();                           // tile loads issued
         if (HALO) {                             // zero rows 0 and TH + 1 of every halo column
             const uint4 z = make_uint4(0u, 0u, 0u, 0u);
@@ -284,7 +280,7 @@ __device__ __forceinline__ void conv_small_body(const ConvParams& p, const int n
                     // 32-bit byte offset of the column (uniform; the tensors on this route are far below 4 GiB): scalar base +
                     // one VGPR offset per load instead of a 64-bit pointer per column
                     const unsigned coff = (unsigned)((b * p.Win + (vw >> ups)) * p.Hin) * pitch_l;
-                    if (inimg[kb]) v[kb][j] = ld_act16<TRUNK>(xg + (coff + goff));
+                    if (inimg[kb]) v[kb][j] = ld_act16(xg + (coff + goff));
                 }
             }
             if (k0 == 0) { RLDM_STAMP(); }      // tile loads issued
@@ -369,7 +365,7 @@ __device__ __forceinline__ void conv_small_body(const ConvParams& p, const int n
                     const int pw = pidx >> p.th_shift, ph = pidx - (pw << p.th_shift);
                     rv[u] = make_uint4(0u, 0u, 0u, 0u);
                     if (pl < HB && rc8 < R8)
-                        rv[u] = ld_act16<TRUNK>(lbase + (size_t)(unsigned)(pix0 + pw * p.Hin + ph) * ld2);
+                        rv[u] = ld_act16(lbase + (size_t)(unsigned)(pix0 + pw * p.Hin + ph) * ld2);
                 }
 #pragma unroll
                 for (int u = 0; u < NBR; ++u) {
@@ -422,7 +418,7 @@ __device__ __forceinline__ void conv_small_body(const ConvParams& p, const int n
             const int pw = pidx >> p.th_shift, ph = pidx - (pw << p.th_shift);
             resv[hp][q] = make_uint4(0u, 0u, 0u, 0u);
             if (p.res && pl < HB)
-                resv[hp][q] = ld_act16<TRUNK>(
+                resv[hp][q] = ld_act16(
                     p.res + (((size_t)b * p.Wout + (w0 + pw)) * p.Hout + (h0 + ph)) * p.N + nt * BN + (tid % NC8) * 8);
         }
 
@@ -444,7 +440,7 @@ __device__ __forceinline__ void conv_small_body(const ConvParams& p, const int n
         // pixel fragments in blocks of NB k-steps, double-buffered: 16 ds_read_b128 per wave in flight while the previous block's 16 MFMAs
         // run (the loop is LDS-bound -- 64 pixels x K x 2 B = 295 KB per workgroup and phase -- and the LDS only reaches its rate with
         // >= 16 reads per wait, MI355X_MICROARCH.md; with 2-3 reads ahead the K loop + barrier took 2.9 k cycles whatever the MFMA count)
-        constexpr int NB = RLDM_H16_NB, NBLK = (G + NB - 1) / NB;
+        constexpr int NB = kH16Block, NBLK = (G + NB - 1) / NB;
         bf16x8 xb[2][NB * PT];
         auto issue = [&](const int blk) __attribute__((always_inline)) {
 #pragma unroll
@@ -577,7 +573,7 @@ __device__ __forceinline__ void conv_small_body(const ConvParams& p, const int n
     RLDM_STAMP();
     // (multi-tile clusters: the next phase's weights are touched into the XCD's L2 now -- trunk_seam.h)
     TrunkWarm warm;
-    if constexpr (TRUNK && (NWN > 1 || RLDM_TRUNK_WARM0)) trunk_warm_next(seam, tid, NT, warm);
+    if constexpr (TRUNK && NWN > 1) trunk_warm_next(seam, tid, NT, warm);
     lds_barrier_s();                            // everyone is done with the input images: LDS is reused below
     RLDM_STAMP();
 
@@ -724,7 +720,7 @@ __device__ __forceinline__ void conv_small_body(const ConvParams& p, const int n
         }
     }
     RLDM_STAMP();
-    if constexpr (TRUNK && (NWN > 1 || RLDM_TRUNK_WARM0)) trunk_warm_done(warm);
+    if constexpr (TRUNK && NWN > 1) trunk_warm_done(warm);
     if constexpr (TRUNK) trunk_arrive(seam, tid);
     if constexpr (TRUNK && PF > 0) {            // the next phase's first fragments: requested behind the arrive (its vmcnt(0) must not
                                                 // wait for them), in flight during the seam and the next gather

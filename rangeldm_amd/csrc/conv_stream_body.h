@@ -97,8 +97,7 @@ __device__ __forceinline__ void conv_stream_body(const ConvParams& p, const int 
 
     const int Cin = p.C0 + p.C1;
     const int NCC = Cin / CK;                  // main-phase chunks: 9 taps x 4 k-steps
-    const int NCBw = (p.R0 + p.R1) / CK;       // residual-phase chunks: centre tap, 4 k-steps, raw input
-    const int NCB = RLDM_EXP_NORES ? 0 : NCBw;
+    const int NCB = (p.R0 + p.R1) / CK;        // residual-phase chunks: centre tap, 4 k-steps, raw input
     const int NCT = NCC + NCB;
     const int THv = (p.TH - 1) * STR + 3, TWv = (p.TW - 1) * STR + 3;
     static_assert(STR == 1 || (STR == 2 && MI == 2), "stride 2: the 64-pixel instance only");
@@ -113,7 +112,7 @@ __device__ __forceinline__ void conv_stream_body(const ConvParams& p, const int 
     float* sBias = sGs + Cin;                                  // BN
 
     // ---- this wave's weight stream (channel tile WN*nt + wn, k-group kg): [NCC][9 taps][SPT k-steps] then [NCB][SPT], 1 KiB each
-    const int nsteps = NCC * CST + NCBw * SPT;
+    const int nsteps = NCC * CST + NCB * SPT;
     const unsigned char* wptr = reinterpret_cast<const unsigned char*>(p.wpk) +
                                 (size_t)(SUB ? (nt * WN + wn) * 4 + (par_w * 2 + par_h) : (nt * WN + wn) * KG + kg) * nsteps * 1024;
     const unsigned woff = lane * 16 + 4096;     // lane offset: immediates of +-4 KiB around it reach 8 fragments
@@ -126,11 +125,10 @@ __device__ __forceinline__ void conv_stream_body(const ConvParams& p, const int 
     const int atotal = TWv * THs * C8;
     int apix[ACH];
     const int my_c8 = (tid % C8) * 8;
-    // halo pieces of a chunk in registers between its request and its store: one set, or two for the short-chunk instance (KG == 4: a
-    // chunk is 9 k-steps per wave, ~2.5 k cycles -- less than the pieces' round trip, so chunk cs + 2 is requested during chunk cs and
-    // stored during chunk cs + 1; round 4: the 128x8 convs' K loops ran 5.5 k cycles per chunk for 2.3 k of matrix-pipe time, most of the
-    // rest was store_next waiting for loads issued ~400 cycles earlier)
-    constexpr bool PF2 = (KG == 4 && RLDM_STREAM_PF2) || (MI == 2 && RLDM_STREAM_PF2_MI2);     // (MI == 2: two pieces per thread, 8 registers)
+    // halo pieces of a chunk in registers between its request and its store: one set, or two for the 64-pixel instance (MI == 2: a chunk
+    // is 18 k-steps of 64 cycles -- less than the pieces' round trip, so chunk cs + 2 is requested during chunk cs and stored during
+    // chunk cs + 1; two pieces per thread, the second set costs 8 registers)
+    constexpr bool PF2 = MI == 2;
     uint4 areg[ACH];
     uint4 areg2[ACH];                          // (second set: PF2 only -- never touched otherwise)
     // (the sets are selected by a compile-time tag inside the lambdas: passing an array of uint4 by reference sends it to scratch)
@@ -154,13 +152,13 @@ __device__ __forceinline__ void conv_stream_body(const ConvParams& p, const int 
 #pragma unroll
         for (int i = 0; i < ACH; ++i) {
             const int pix = apix[i] < 0 ? 0 : apix[i];
-            const uint4 v = ld_act16<TRUNK>(base + (size_t)pix * ld);
+            const uint4 v = ld_act16(base + (size_t)pix * ld);
             if constexpr (decltype(W)::value == 0) areg[i] = v; else areg2[i] = v;
         }
     };
     auto store_a = [&](int cs, auto W) __attribute__((always_inline)) {           // GroupNorm + SiLU (main phase) -> LDS
         unsigned char* dstbuf = sA + (cs & 1) * abytes;
-        const bool anorm = gn && cs < NCC && !RLDM_EXP_NONORM;
+        const bool anorm = gn && cs < NCC;
         float4 ga0, ga1, gs0, gs1;
         if (anorm) {
             const int c = cs * CK + my_c8;
@@ -209,7 +207,7 @@ __device__ __forceinline__ void conv_stream_body(const ConvParams& p, const int 
         const bf16_t* src = base + (size_t)((b * p.Wout + w0 + pw) * p.Hout + h0 + ph) * ld;
         const size_t step = (size_t)((RSTEP >> p.th_shift) * p.Hout) * ld;
 #pragma unroll
-        for (int i = 0; i < RCH; ++i) rr[i] = ld_act16<TRUNK>(src + i * step);
+        for (int i = 0; i < RCH; ++i) rr[i] = ld_act16(src + i * step);
     };
     auto store_r = [&](int cs, const uint4* rr) __attribute__((always_inline)) {
         const int pidx = tid / C8, pw = pidx >> p.th_shift, ph = pidx - (pw << p.th_shift);
@@ -245,8 +243,7 @@ __device__ __forceinline__ void conv_stream_body(const ConvParams& p, const int 
         const bool first = ch < nC0;
         const int c = first ? ch : ch - nC0;
         const int C = first ? nC0 : nC1;
-        const int P = RLDM_EXP_NOSTATS ? 0 : (first ? nP0 : nP1);
-        if (RLDM_EXP_NOSTATS) gSS[sl] = (double)(1.0f / p.gn_inv_n) / (Cin / p.gn_groups);   // (mean 0, variance 1: finite garbage)
+        const int P = first ? nP0 : nP1;
         const float2* src = (first ? gs0p : gs1p) + (size_t)b * P * C + c;
         g_gamma[sl] = p.gn_gamma[ch];
         g_beta[sl] = p.gn_beta[ch];
@@ -255,7 +252,7 @@ __device__ __forceinline__ void conv_stream_body(const ConvParams& p, const int 
             for (; q + 32 <= P; q += 32) {
                 float2 v[32];
 #pragma unroll
-                for (int j = 0; j < 32; ++j) v[j] = ld_act8<TRUNK>(src + (size_t)(q + j) * C);
+                for (int j = 0; j < 32; ++j) v[j] = ld_act8(src + (size_t)(q + j) * C);
 #pragma unroll
                 for (int j = 0; j < 32; ++j) { gS[sl] += (double)v[j].x; gSS[sl] += (double)v[j].y; }
             }
@@ -263,19 +260,19 @@ __device__ __forceinline__ void conv_stream_body(const ConvParams& p, const int 
         for (; q + 16 <= P; q += 16) {          // 16 partials per round trip (P = pixel tiles per image of the producer)
             float2 v[16];
 #pragma unroll
-            for (int j = 0; j < 16; ++j) v[j] = ld_act8<TRUNK>(src + (size_t)(q + j) * C);
+            for (int j = 0; j < 16; ++j) v[j] = ld_act8(src + (size_t)(q + j) * C);
 #pragma unroll
             for (int j = 0; j < 16; ++j) { gS[sl] += (double)v[j].x; gSS[sl] += (double)v[j].y; }
         }
         for (; q + 4 <= P; q += 4) {
             float2 v[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = ld_act8<TRUNK>(src + (size_t)(q + j) * C);
+            for (int j = 0; j < 4; ++j) v[j] = ld_act8(src + (size_t)(q + j) * C);
 #pragma unroll
             for (int j = 0; j < 4; ++j) { gS[sl] += (double)v[j].x; gSS[sl] += (double)v[j].y; }
         }
         for (; q < P; ++q) {
-            const float2 v = ld_act8<TRUNK>(src + (size_t)q * C);
+            const float2 v = ld_act8(src + (size_t)q * C);
             gS[sl] += (double)v.x;
             gSS[sl] += (double)v.y;
         }
@@ -402,7 +399,6 @@ __device__ __forceinline__ void conv_stream_body(const ConvParams& p, const int 
 #pragma unroll
         for (int j = 0; j < ROW; ++j) {
             const int c = ti * ROW + j, slot = c % G;
-#if RLDM_STREAM_ILV
             // (round 4) each pixel fragment of step c + PFX is requested right behind the MFMA that consumed its register, not behind
             // the step's last MFMA: ~100 cycles more lead per read.  A wave ALONE on its SIMD (the 4-wave instances while the other
             // workgroup of the CU is outside its K loop) ran 236 cycles per k-step against 128 of matrix-pipe time -- waiting on LDS.
@@ -421,13 +417,6 @@ __device__ __forceinline__ void conv_stream_body(const ConvParams& p, const int 
                 if (c + PFX < CST) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
             }
             __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-#else
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-                acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wr[slot], xr[c % PFX][mi], acc[mi], 0, 0, 0);
-            wr[slot] = w_load(wptr, slot);
-            if (c + PFX < CST) x_read(cur, nxt, j + PFX, xr[c % PFX]);   // (no read-ahead across the chunk's barrier)
-#endif
             __builtin_amdgcn_sched_barrier(0);  // steps stay in program order: every wait then leaves G - 1 loads in flight
         }
         if ((ti * ROW + ROW) % G == 0) wptr += G * 1024;
@@ -504,21 +493,17 @@ __device__ __forceinline__ void conv_stream_body(const ConvParams& p, const int 
         for (int cs = 0; cs < NCC; ++cs) main_chunk(cs, Set0(), Set1());
     }
     // residual phase: centre tap of the raw block input, SPT k-steps per chunk; ring slots continue (CST % G == 0).  A chunk is 16
-    // MFMAs per wave -- far less than a round trip to the L2 -- so RD chunks are kept in flight in registers (the main loop's
-    // read-ahead registers are dead here): chunk k lands in set k % RD, requested RD iterations before it is written to LDS.
+    // MFMAs per wave -- far less than a round trip to the L2 -- so the next chunk is kept in flight in registers (the main loop's
+    // read-ahead registers are dead here), requested one iteration before it is written to LDS (deeper: measured the same).
     constexpr int RCR = G / SPT;                // residual chunks per ring revolution
-    constexpr int RD = RLDM_RES_DEPTH, RUN = RCR * RD;
-    uint4 rreg[RD][RCH];
+    uint4 rreg[RCH];                            // (chunk 0 came through the halo registers during the last main chunk)
+    for (int rc0 = 0; rc0 < NCB; rc0 += RCR) {
 #pragma unroll
-    for (int k = 1; k < RD; ++k)
-        if (k < NCB) load_r(NCC + k, rreg[k % RD]);             // (chunk 0 came through the halo registers during the last main chunk)
-    for (int rc0 = 0; rc0 < NCB; rc0 += RUN) {
-#pragma unroll
-        for (int r = 0; r < RUN; ++r) {
+        for (int r = 0; r < RCR; ++r) {
             const int rc = rc0 + r;
             if (rc < NCB) {
                 const int cs = NCC + rc;
-                if (rc + RD < NCB) load_r(cs + RD, rreg[r % RD]);
+                if (rc + 1 < NCB) load_r(cs + 1, rreg);
                 int xc[MI];
 #pragma unroll
                 for (int mi = 0; mi < MI; ++mi) xc[mi] = xoff[mi] + (cs & 1) * abytes + colb + RS;
@@ -529,13 +514,13 @@ __device__ __forceinline__ void conv_stream_body(const ConvParams& p, const int 
                     for (int mi = 0; mi < MI; ++mi) xf[mi] = *reinterpret_cast<const bf16x8*>(smem + xc[mi] + ks * 32);
 #pragma unroll
                     for (int mi = 0; mi < MI; ++mi)
-                        acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wr[(r % RCR) * SPT + ks], xf[mi], acc[mi], 0, 0, 0);
-                    wr[(r % RCR) * SPT + ks] = w_load(wptr, (r % RCR) * SPT + ks);
+                        acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wr[r * SPT + ks], xf[mi], acc[mi], 0, 0, 0);
+                    wr[r * SPT + ks] = w_load(wptr, r * SPT + ks);
                 }
-                if (rc + 1 < NCB) store_r(cs + 1, rreg[(r + 1) % RD]);
+                if (rc + 1 < NCB) store_r(cs + 1, rreg);
                 lds_barrier_b();
             }
-            if (r % RCR == RCR - 1) wptr += G * 1024;
+            if (r == RCR - 1) wptr += G * 1024;
         }
     }
     RLDM_STAMP();

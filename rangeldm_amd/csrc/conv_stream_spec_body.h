@@ -99,19 +99,19 @@ __device__ __forceinline__ void conv_stream_spec_body(const ConvParams& p, const
         for (; q + 16 <= P; q += 16) {
             float2 v[16];
 #pragma unroll
-            for (int j = 0; j < 16; ++j) v[j] = ld_act8<TRUNK>(src + (size_t)(q + j) * C);
+            for (int j = 0; j < 16; ++j) v[j] = ld_act8(src + (size_t)(q + j) * C);
 #pragma unroll
             for (int j = 0; j < 16; ++j) { gS += (double)v[j].x; gSS += (double)v[j].y; }
         }
         for (; q + 4 <= P; q += 4) {
             float2 v[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = ld_act8<TRUNK>(src + (size_t)(q + j) * C);
+            for (int j = 0; j < 4; ++j) v[j] = ld_act8(src + (size_t)(q + j) * C);
 #pragma unroll
             for (int j = 0; j < 4; ++j) { gS += (double)v[j].x; gSS += (double)v[j].y; }
         }
         for (; q < P; ++q) {
-            const float2 v = ld_act8<TRUNK>(src + (size_t)q * C);
+            const float2 v = ld_act8(src + (size_t)q * C);
             gS += (double)v.x;
             gSS += (double)v.y;
         }
@@ -132,7 +132,7 @@ __device__ __forceinline__ void conv_stream_spec_body(const ConvParams& p, const
 #pragma unroll
         for (int i = 0; i < ACH; ++i) {
             const int pix = apix[i] < 0 ? 0 : apix[i];
-            areg[i] = ld_act16<TRUNK>(base + (size_t)pix * ld);
+            areg[i] = ld_act16(base + (size_t)pix * ld);
         }
     };
     auto store_a = [&](int cs) __attribute__((always_inline)) {                 // GroupNorm + SiLU -> LDS
@@ -179,7 +179,7 @@ __device__ __forceinline__ void conv_stream_spec_body(const ConvParams& p, const
         const bf16_t* src = base + (size_t)((b * p.Wout + w0 + pw) * p.Hout + h0 + ph) * ld;
         const size_t step = (size_t)((RSTEP >> p.th_shift) * p.Hout) * ld;
 #pragma unroll
-        for (int i = 0; i < RCH; ++i) rr[i] = ld_act16<TRUNK>(src + i * step);
+        for (int i = 0; i < RCH; ++i) rr[i] = ld_act16(src + i * step);
     };
     auto store_r = [&](int cs, const uint4* rr) __attribute__((always_inline)) {
         const int pidx = stid / C8, pw = pidx >> p.th_shift, ph = pidx - (pw << p.th_shift);

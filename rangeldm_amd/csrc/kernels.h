@@ -201,45 +201,16 @@ int launch_conv_ds2(const ConvParams& p, hipStream_t stream);
 // tiles) as the phases of ONE launch; the N / 32 workgroups of an image hand their outputs to each other through the L2 of the
 // XCD they share.  `kind`: 0 = 3x3 over 256 channels, 1 = 3x3 over 512, 2 = 1x1 over 256 (conv_small instances <1,2,9,2>,
 // <1,4,9,2>, <1,2,1,2>).
-// A phase record is 64 dwords: ONE vector load per wave (lane l holds word l), requested a phase ahead, and v_readlane puts the
-// fields into SGPRs -- the place the kernel-argument copy of a stand-alone launch lives in.
-enum TrunkWord {
-    TW_X0 = 0, TW_R0 = 2, TW_R1 = 4, TW_WPK = 6, TW_BIAS = 8, TW_Y = 10, TW_YSTATS = 12, TW_RES = 14,    // 64-bit pointers
-    TW_R0C = 16, TW_R1C, TW_WIN, TW_HIN, TW_WOUT, TW_HOUT, TW_TW, TW_TH, TW_COLB, TW_THSHIFT, TW_N, TW_YLD, TW_NVIEWS,
-    TW_KIND, TW_G, TW_NMINE, TW_TEMBOFF,
-    TW_NV0 = 34,            // 2 views x 11 words: y (2), gamma (2), beta (2), ld, cpg_shift, inv_n, eps, silu
-    TW_NVSTRIDE = 11,
-    // phases of a MULTI-TILE cluster (kind >= 8: an image is several 64-pixel tiles x 64-channel tiles; no views) keep the
-    // consumer-side GroupNorm of their input in the words the views would occupy
-    TW_ST0 = 34, TW_GAMMA = 36, TW_BETA = 38,                   // 64-bit pointers
-    TW_P0 = 40, TW_GROUPS, TW_MAGIC_CPG, TW_INVN, TW_EPS, TW_SILU, TW_TILES_H, TW_TILES_IMG,
-    // conv_stream phases (kind 15: the full-resolution levels as clusters of 16 pixel tiles / 8 pixel tiles x 2 channel tiles)
-    TW_X1 = 48, TW_ST1 = 50,                                    // 64-bit pointers
-    TW_C0 = 52, TW_C1, TW_P1, TW_MAGIC_THV, TW_UP,
-    TW_SUB,                 // conv_stream phases of variant 4: 1 = the sub-pixel form of nearest x2 + 3x3 (rank = input tile * 4 + parity, 128 output channels),
-                            // 2 = tiles as tall as the image (st_inst 7)
-    TW_WBYTES = 58,         // bytes of the phase's packed weights (TW_WPK ...): what the PREVIOUS phase touches, one dword per 128-byte line,
-                            // so that they wait in the XCD's L2 (round 5: trunk_warm_next; 0: nothing to warm)
-    TW_WORDS = 64
-};
-// phase kinds: 0..2 / 4..6 image-owning conv_small tiles (64 / 32 pixels), 3 attention over a pre-normalised x,
-// 9..11 3x3 conv over 256 / 384 / 512 channels on 64-pixel x 64-channel tiles of a multi-tile image (8: 128 channels, not instantiated), 12 its 1x1 over 256,
-// 13 attention with the GroupNorm fold inside (two query tiles per wave)
-// 14 GroupNorm (+ SiLU) of a concatenated input as a phase of its own (norm.hip's gn_apply_kernel; record: x0 / x1 in TW_X0 / TW_R0,
-// their channels in TW_R0C / TW_R1C, statistics in TW_ST0 / TW_RES with TW_P0 / TW_TILES_H partials, pixels per image in TW_WIN)
-// (round 5) 16..18: the image-owning 64-pixel kinds 0..2 on 16-channel tiles (conv_small_body's H16 instances)
-enum TrunkKind { TK_H16 = 16, TK_ATTN = 3, TK_CL_3x3_128 = 8, TK_CL_3x3_256, TK_CL_3x3_384, TK_CL_3x3_512, TK_CL_1x1_256, TK_ATTN_FOLD, TK_GN_APPLY, TK_STREAM };
-struct TrunkPhase {
-    unsigned w[TW_WORDS];
-};
+// The phase record (TrunkPhase: 64 dwords), its host-side encoders and the kernel's decoders: trunk_record.h.
+struct TrunkPhase;
 struct TrunkParams {
     const TrunkPhase* phases;   // device
     int nphases;
     int B, ranks;               // images; workgroups per image (its cluster): channel tiles x pixel tiles
     int ntile_n, nwn;           // channel tiles per image and 32-channel tiles per workgroup (N / 32 and 1 for image-owning tiles)
     int variant;                // kernel: 0 image-owning conv_small tiles, 1 multi-tile conv_small clusters, 2 conv_stream<256 px, 128 ch>,
-                                // 3 conv_stream<128 px, 64 ch> (each set of instances has its own register allocation),
                                 // 4 conv_stream<128 px, 128 ch> on 4 waves: 32 workgroups per image, two per CU (round 4)
+                                // (each set of instances has its own register allocation; 3 and 5 were 128x8-level variants, removed)
     int skew;                   // variant 4: start delay of the second image group, x 1024 cycles
     unsigned* counters;         // device [B][32] zero-initialised: [0] arrivals (monotonic), [1] rank 0's XCC id + 1, [3] launches so far
     int* error;                 // device flag: 1 a bounded wait gave up, 2 a cluster is spread over several XCDs
@@ -346,39 +317,6 @@ int launch_attention_proj(const AttnQkvParams& p, hipStream_t stream);    // the
 // what launch_attention_qkv runs for (B, L, C) (tests): route[0] = 2 (attention_qkv2_d8_kernel) or 1 (attention_qkv_d8_kernel), [1] PAIR,
 // [2] HG, [3] waves per workgroup, [4] attention_proj_fusable for the shape alone, [5] the same on `cus` compute units
 void attention_qkv_route(int B, int L, int C, int cus, int* route);
-// weight fragments per wave a phase of the persistent launch requests for the NEXT phase (trunk_seam.h; the plan builder's TW_G)
-#ifndef RLDM_TRUNK_PREFETCH
-#define RLDM_TRUNK_PREFETCH 18     /* (round 3: 12 -> 18 = the whole ring of a 3x3 / 256-channel phase: +0.5 %, trunk<0> 201 -> 225 VGPRs) */
-#endif
-// Timing-only ablations of the round-3 headroom study: `make TAG=x EXTRA=-DRLDM_EXP_NORES=1` etc. build a library
-// whose RESULTS ARE WRONG and whose speed bounds what the removed piece can be worth (tools/ab_libs.sh, tools/fwd_time.py).  All 0 in
-// every shipped build.  NORES: conv_stream skips its residual phase; NONORM: ... the GroupNorm + SiLU arithmetic of its staging (raw
-// copy); NOSTATS: ... the statistics partial loads in front of its fold (mean 0 / variance 1 instead); NOWAIT: the persistent launches' cluster waits do not poll.
-#ifndef RLDM_EXP_NORES
-#define RLDM_EXP_NORES 0
-#endif
-#ifndef RLDM_EXP_NONORM
-#define RLDM_EXP_NONORM 0
-#endif
-#ifndef RLDM_EXP_NOSTATS
-#define RLDM_EXP_NOSTATS 0
-#endif
-#ifndef RLDM_EXP_NOWAIT
-#define RLDM_EXP_NOWAIT 0
-#endif
-#ifndef RLDM_STREAM_PF2
-#define RLDM_STREAM_PF2 0          /* conv_stream's 4-k-group instance: halo chunks requested two chunks ahead (round 4 experiment; measured
-                                      SLOWER, 128x8 convs 13.4 -> 15.1 us: +16 VGPRs = 15 spills; the waits were not the loads') */
-#endif
-#ifndef RLDM_STREAM_PF2_MI2
-#define RLDM_STREAM_PF2_MI2 1      /* ... the same for the 64-pixel instance (a chunk is 18 k-steps of 64 cycles; the second set costs 8 registers) */
-#endif
-#ifndef RLDM_STREAM_ILV
-#define RLDM_STREAM_ILV 1          /* conv_stream K loop: pixel-fragment reads interleaved with the step's MFMAs (round 4; 0 = behind them) */
-#endif
-#ifndef RLDM_RES_DEPTH
-#define RLDM_RES_DEPTH 1           /* residual chunks of a conv_stream tile in flight in registers (conv_stream_body.h); 2 and 3 measured the same */
-#endif
 // LDS of the second-generation fused attention body (attention_body.h) for HG heads per workgroup on `waves` waves: K rows, V^T,
 // the GroupNorm affine + scratch, the heads' W' fragments and biases, and one 32-row x 144-byte x staging tile per wave
 constexpr int kAttnXRowBytes = 128 + 16, kAttnXStageBytes = 32 * kAttnXRowBytes;

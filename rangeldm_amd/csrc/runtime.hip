@@ -6,6 +6,7 @@
 // (vae/sgm/modules/diffusionmodules/model.py:852-896,1024-1057); the loop follows ldm/pipelines.py:353-367.
 #include "../../include/rangeldm_hip.h"
 #include "kernels.h"
+#include "trunk_seam.h"
 
 #include <algorithm>
 #include <atomic>
@@ -662,8 +663,6 @@ static unsigned long long* stamp_buf(StampSite site, int n = 0) {
     return nullptr;
 }
 static constexpr int kInst4MinBlocks = 96;      // (192 -> 96: nuScenes at 4 images 87.4 -> 89.4, KITTI at 8 images 134.4 -> 137.5 img/s)
-static constexpr int kTrunkSkew = 0;            // (trunk variant 4: start offset of the second image group, x 1024 cycles; measured 0 / 4 / 8 / 16 /
-                                                //  24 -> 230.6 / 230.1 / 230.8 / 228.7 / 223.7 img/s)
 static int g_force_bm = 0, g_force_bn = 0, g_force_ks = 0;     // rldm_debug_force_tile: tuning override (0: automatic)
 static constexpr int kGraphSteps = 10;          // sampler steps per captured graph (at most; a divisor of the step count)
 
@@ -675,12 +674,11 @@ struct TileChoice {
 };
 
 // output-pixel tile of a block: as tall as the image allows (<= 16 beams), then as wide as BM allows
-static void pixel_tile(int BM, int Wout, int Hout, int stride, int* TW, int* TH) {
+static void pixel_tile(int BM, int Wout, int Hout, int* TW, int* TH) {
     int th = 1;
     while (th * 2 <= Hout && th * 2 <= 16 && Hout % (th * 2) == 0) th *= 2;
     int tw = 1;
     while (tw * 2 * th <= BM && Wout % (tw * 2) == 0) tw *= 2;
-    (void)stride;
     *TW = tw;
     *TH = th;
 }
@@ -699,7 +697,7 @@ static TileChoice choose_tile(long long B, int Wout, int Hout, int stride, int N
             ConvTile v;
             v.BM = BM; v.BN = BN; v.CK = ck; v.taps = taps;
             if (!conv_tile_supported(v)) continue;
-            pixel_tile(BM, Wout, Hout, stride, tw, th);
+            pixel_tile(BM, Wout, Hout, tw, th);
             // shrink the tile until the halo fits the instance's register staging capacity
             bool ok = true;
             while (((*tw - 1) * stride + KW) * ((*th - 1) * stride + KW) > conv_max_halo_slots(v)) {
@@ -897,7 +895,7 @@ struct Builder {
             tp.ntile_n = pend.nwn == 1 ? pend.ranks : pend.ntile_n;
             tp.nwn = pend.nwn;
             tp.variant = pend.variant;
-            tp.skew = pend.variant == 4 ? kTrunkSkew : 0;
+            tp.skew = 0;                    // (variant 4 can start its second image group late: no offset measured faster, docs/history/rounds1-4.md)
             tp.counters = ctrs->as<unsigned>();
             tp.error = plan->trunk_error.as<int>();
             tp.temb_ld = temb_ld;
@@ -914,7 +912,7 @@ struct Builder {
                 tp.ts = ts_ok ? stamp_buf(StampSite::Trunk, tp.nphases) : nullptr;
                 return launch_trunk(tp, lds, st);
             }, std::string("trunk_kernel<") + (pend.variant == 0 ? "conv_small image tiles" : pend.variant == 1 ? "conv_small 64x64 clusters" :
-                                               pend.variant == 2 ? "conv_stream 256x128" : pend.variant == 3 ? "conv_stream 128x64" : pend.variant == 5 ? "conv_stream 64x128" : "conv_stream 128x128 x2/CU") +
+                                               pend.variant == 2 ? "conv_stream 256x128" : "conv_stream 128x128 x2/CU") +
                    ", " + std::to_string(pend.phases.size()) + " phases>", pend.flops, pend.bytes});
         }
         pend = PendingTrunk();
@@ -989,22 +987,8 @@ struct Builder {
         return (r >= 2 && r <= 16 && npix > 64 && trunk_grid_fits(r, B)) ? r : 0;
     }
     void trunk_push_attention(const AttnQkvParams& ap, double fl, double by) {
-        TrunkPhase ph;
-        memset(&ph, 0, sizeof(ph));
-        auto put64 = [&](int at, const void* ptr) {
-            const unsigned long long u = (unsigned long long)(uintptr_t)ptr;
-            ph.w[at] = (unsigned)u;
-            ph.w[at + 1] = (unsigned)(u >> 32);
-        };
-        put64(TW_X0, ap.x); put64(TW_WPK, ap.wfrag); put64(TW_BIAS, ap.bias); put64(TW_Y, ap.out);
-        ph.w[TW_WIN] = ap.L; ph.w[TW_N] = ap.C;
-        ph.w[TW_KIND] = ap.st ? TK_ATTN_FOLD : TK_ATTN; ph.w[TW_G] = 0; ph.w[TW_NMINE] = 0; ph.w[TW_TEMBOFF] = (unsigned)-1;
+        TrunkPhase ph = trunk_attention_phase(ap);
         ph.w[TW_WBYTES] = (unsigned)(3 * ap.C * ap.C * 2);          // q / k / v projection fragments (attention_body.h)
-        if (ap.st) {                    // the consumer-side GroupNorm of x (multi-tile clusters)
-            put64(TW_ST0, ap.st); put64(TW_GAMMA, ap.gamma); put64(TW_BETA, ap.beta);
-            ph.w[TW_P0] = ap.P; ph.w[TW_GROUPS] = ap.groups; ph.w[TW_MAGIC_CPG] = ap.magic_cpg;
-            memcpy(&ph.w[TW_INVN], &ap.inv_n, 4); memcpy(&ph.w[TW_EPS], &ap.eps, 4);
-        }
         pend.phases.push_back(ph);
         pend.lds = std::max(pend.lds, trunk_attention_lds(ap.L, ap.C, (ap.C / 8) / pend.ranks));
         pend.flops += fl;
@@ -1180,7 +1164,6 @@ struct Builder {
         plan->flops += fl;
         // a phase of the persistent trunk launch (trunk.hip) instead of a launch of its own: the tile owns the image, the input
         // arrives pre-activated (or needs no norm), one of the three instances the trunk kernel carries
-        const int cpt_t = Cin_t / 128;
         const int px_t = p.TW * p.TH;
         const int kind_l = (taps == 9 && Cin_t == 256) ? 0 : ((taps == 9 && Cin_t == 512) ? 1 : ((taps == 1 && Cin_t == 256) ? 2 : -1));
         const int trunk_kind = kind_l < 0 ? -1 : kind_l + (BN == 16 ? TK_H16 : (px_t == 32 ? 4 : 0));      // (+4: the 32-pixel instances; +16: 16-channel tiles)
@@ -1224,21 +1207,8 @@ struct Builder {
                 g.y = tptr(act);
                 const double by = (double)g.B * g.npix * Cin_t * 4.0;
                 if (gn_phase) {
-                    TrunkPhase ph;
-                    memset(&ph, 0, sizeof(ph));
-                    auto put64 = [&](int at, const void* ptr) {
-                        const unsigned long long u = (unsigned long long)(uintptr_t)ptr;
-                        ph.w[at] = (unsigned)u;
-                        ph.w[at + 1] = (unsigned)(u >> 32);
-                    };
-                    put64(TW_X0, g.x0); put64(TW_R0, g.x1); put64(TW_ST0, g.st0); put64(TW_RES, g.st1);
-                    put64(TW_GAMMA, g.gamma); put64(TW_BETA, g.beta); put64(TW_Y, g.y);
-                    ph.w[TW_R0C] = g.C0; ph.w[TW_R1C] = g.C1; ph.w[TW_P0] = g.P0; ph.w[TW_TILES_H] = g.P1; ph.w[TW_WIN] = g.npix;
-                    ph.w[TW_GROUPS] = g.groups; ph.w[TW_SILU] = g.silu;
-                    const float inv_n = (float)(1.0 / ((double)g.npix * (Cin_t / g.groups)));
-                    memcpy(&ph.w[TW_INVN], &inv_n, 4); memcpy(&ph.w[TW_EPS], &g.eps, 4);
-                    ph.w[TW_KIND] = TK_GN_APPLY; ph.w[TW_TEMBOFF] = (unsigned)-1;
-                    pend.phases.push_back(ph);
+                    g.inv_n = (float)(1.0 / ((double)g.npix * (Cin_t / g.groups)));      // (what launch_gn_apply sets for the launch)
+                    pend.phases.push_back(trunk_gn_apply_phase(g));
                     pend.lds = std::max(pend.lds, (size_t)(2 * 512 * 8 + 2 * 512 * 4));
                     pend.bytes += by;
                     pend.standalone.push_back({[g](hipStream_t s) { return launch_gn_apply(g, s); }, "gn_apply_kernel", 0.0, by});
@@ -1251,7 +1221,6 @@ struct Builder {
         else if (in_cluster) trunk_begin(x0.B, ranks_c, N / 64, 2);
         else note_launch();
         in_trunk = in_trunk || in_cluster;
-        (void)cpt_t;
         if (!dry) {
             ConvLayer::Packed* pk = nullptr;
             if (BN == 16 ? L->get_fragpacked16(Cin_t, epi_res, &pk) : L->get_fragpacked(Cin_t, conv_small_kgroups(BN), epi_res, &pk)) return 1;
@@ -1297,50 +1266,16 @@ struct Builder {
                               (double)x0.B * Wout * Hout * N * 2.0 * (1.0 + (double)vts.size()) + (double)x0.B * Wout * Hout * R_t * 2.0;
             const std::string kname = "conv_small_kernel<" + std::to_string(p.TW * p.TH) + "," + std::to_string(BN) + ",taps" + std::to_string(taps) + ">";
             if (in_trunk) {
-                TrunkPhase ph;
-                memset(&ph, 0, sizeof(ph));
-                auto put64 = [&](int at, const void* ptr) {
-                    const unsigned long long u = (unsigned long long)(uintptr_t)ptr;
-                    ph.w[at] = (unsigned)u;
-                    ph.w[at + 1] = (unsigned)(u >> 32);
-                };
-                auto putf = [&](int at, float f) { memcpy(&ph.w[at], &f, 4); };
-                put64(TW_X0, p.x0); put64(TW_R0, p.r0); put64(TW_R1, p.r1); put64(TW_WPK, p.wpk); put64(TW_BIAS, p.bias);
-                put64(TW_Y, p.y); put64(TW_YSTATS, p.y_stats); put64(TW_RES, p.res);
-                ph.w[TW_R0C] = p.R0; ph.w[TW_R1C] = p.R1; ph.w[TW_WIN] = p.Win; ph.w[TW_HIN] = p.Hin; ph.w[TW_WOUT] = p.Wout;
-                ph.w[TW_HOUT] = p.Hout; ph.w[TW_TW] = p.TW; ph.w[TW_TH] = p.TH; ph.w[TW_COLB] = p.colb; ph.w[TW_THSHIFT] = p.th_shift;
-                ph.w[TW_N] = p.N; ph.w[TW_YLD] = p.y_ld; ph.w[TW_NVIEWS] = p.nviews;
-                if (in_cluster) {
-                    const int KG = 4, cpt = Cin_t / (16 * KG);
-                    const int TPG = taps == 1 ? 1 : (cpt <= 2 ? 9 : (cpt <= 4 ? 3 : 1));      // conv_small_body.h, MI == 2
-                    ph.w[TW_KIND] = kind_c;
-                    ph.w[TW_G] = std::min(TPG * cpt, RLDM_TRUNK_PREFETCH);
-                    ph.w[TW_NMINE] = taps * cpt + ((p.R0 + p.R1) / 16) / KG;
-                    ph.w[TW_WBYTES] = (unsigned)((N / 32) * KG * ph.w[TW_NMINE]) * 1024u;
-                    RLDM_REQUIRE(p.nviews == 0, "conv " + L->name + ": a multi-tile cluster phase writes no views");
-                    put64(TW_ST0, p.st0); put64(TW_GAMMA, p.gn_gamma); put64(TW_BETA, p.gn_beta);
-                    ph.w[TW_P0] = p.P0; ph.w[TW_GROUPS] = p.gn_groups; ph.w[TW_MAGIC_CPG] = p.magic_cpg;
-                    putf(TW_INVN, p.gn_inv_n); putf(TW_EPS, p.gn_eps);
-                    ph.w[TW_SILU] = p.silu; ph.w[TW_TILES_H] = p.tiles_h; ph.w[TW_TILES_IMG] = p.tiles_img;
-                    ph.w[TW_UP] = p.up;
-                    put64(TW_X1, p.x1); put64(TW_ST1, p.st1);
-                    ph.w[TW_C0] = p.C0; ph.w[TW_C1] = p.C1; ph.w[TW_P1] = p.P1;
-                } else {
-                const int KG = 8, ksc = BN == 16 ? 32 : 16, cpt = Cin_t / (ksc * KG);
-                const int G = BN == 16 ? (taps == 9 ? 9 : 1) * cpt : ((trunk_kind & 3) == 0 ? 18 : ((trunk_kind & 3) == 1 ? 12 : cpt));
-                ph.w[TW_KIND] = trunk_kind;
-                ph.w[TW_G] = std::min(G, RLDM_TRUNK_PREFETCH);       // == kTrunkPrefetch (conv_small_body.h)
+                RLDM_REQUIRE(!in_cluster || p.nviews == 0, "conv " + L->name + ": a multi-tile cluster phase writes no views");
+                TrunkPhase ph = trunk_conv_phase(p, in_cluster ? kind_c : trunk_kind, in_cluster, temb_off);
+                // the wave's weight stream: k-groups, channels per k-step, k-steps per tap and k-group; fragments in its ring (conv_small_body.h)
+                const int KG = in_cluster ? 4 : 8, ksc = BN == 16 ? 32 : 16, cpt = Cin_t / (ksc * KG);
+                int G;
+                if (in_cluster) G = (taps == 1 ? 1 : (cpt <= 2 ? 9 : (cpt <= 4 ? 3 : 1))) * cpt;      // (MI == 2)
+                else G = BN == 16 ? (taps == 9 ? 9 : 1) * cpt : ((trunk_kind & 3) == 0 ? 18 : ((trunk_kind & 3) == 1 ? 12 : cpt));
+                ph.w[TW_G] = std::min(G, kTrunkPrefetch);
                 ph.w[TW_NMINE] = taps * cpt + ((p.R0 + p.R1) / ksc) / KG;
-                ph.w[TW_WBYTES] = (unsigned)((N / BN) * KG * ph.w[TW_NMINE]) * 1024u;
-                }
-                ph.w[TW_TEMBOFF] = (unsigned)temb_off;
-                for (int v = 0; v < p.nviews; ++v) {
-                    const int at = TW_NV0 + v * TW_NVSTRIDE;
-                    put64(at, p.nv[v].y); put64(at + 2, p.nv[v].gamma); put64(at + 4, p.nv[v].beta);
-                    ph.w[at + 6] = p.nv[v].ld; ph.w[at + 7] = p.nv[v].cpg_shift;
-                    putf(at + 8, p.nv[v].inv_n); putf(at + 9, p.nv[v].eps);
-                    ph.w[at + 10] = p.nv[v].silu;
-                }
+                ph.w[TW_WBYTES] = (unsigned)((N / (in_cluster ? 32 : BN)) * KG * ph.w[TW_NMINE]) * 1024u;
                 pend.phases.push_back(ph);
                 pend.lds = std::max(pend.lds, conv_small_lds_bytes(p, taps, BN));
                 pend.flops += fl;
@@ -1478,7 +1413,7 @@ struct Builder {
         plan->flops += fl_ref;                  // (the network's nominal count: 9 taps)
         // what THIS launch / phase executes (the bench line's roofline is priced with it): the sub-pixel form multiplies 4 taps per output pixel
         const double fl = sub ? fl_ref * 4.0 / 9.0 : fl_ref;
-        // a phase of the persistent launch (trunk.hip, variants 2 / 3): the image's tiles_img x ntile_n workgroups (16 at both
+        // a phase of the persistent launch (trunk.hip, variants 2 / 4): the image's tiles_img x ntile_n workgroups (16 at both
         // full-resolution levels) form a cluster on one XCD; consecutive convs of a level hand over through its L2 -- no end-of-kernel
         // write-back of the 16.8 MB outputs, no argument fetch / cold start per layer
         const int ranks_s = p.tiles_img * p.ntile_n;            // (sub-pixel form: input tiles x parities, one 128-channel tile)
@@ -1519,26 +1454,7 @@ struct Builder {
             const double by = (double)x0.B * x0.W * x0.H * Cin_t * 2.0 + (double)N * (L->Cin * 9 + L->R) * 2.0 +
                               (double)x0.B * Wout * Hout * N * 2.0 + (double)x0.B * Wout * Hout * R_t * 2.0;
             if (in_stream_cluster) {
-                TrunkPhase ph;
-                memset(&ph, 0, sizeof(ph));
-                auto put64 = [&](int at, const void* ptr) {
-                    const unsigned long long u = (unsigned long long)(uintptr_t)ptr;
-                    ph.w[at] = (unsigned)u;
-                    ph.w[at + 1] = (unsigned)(u >> 32);
-                };
-                auto putf = [&](int at, float f) { memcpy(&ph.w[at], &f, 4); };
-                put64(TW_X0, p.x0); put64(TW_X1, p.x1); put64(TW_R0, p.r0); put64(TW_R1, p.r1); put64(TW_WPK, p.wpk); put64(TW_BIAS, p.bias);
-                put64(TW_Y, p.y); put64(TW_YSTATS, p.y_stats); put64(TW_ST0, p.st0); put64(TW_ST1, p.st1);
-                put64(TW_GAMMA, p.gn_gamma); put64(TW_BETA, p.gn_beta);
-                ph.w[TW_C0] = p.C0; ph.w[TW_C1] = p.C1; ph.w[TW_R0C] = p.R0; ph.w[TW_R1C] = p.R1; ph.w[TW_P0] = p.P0; ph.w[TW_P1] = p.P1;
-                ph.w[TW_WIN] = p.Win; ph.w[TW_HIN] = p.Hin; ph.w[TW_WOUT] = p.Wout; ph.w[TW_HOUT] = p.Hout; ph.w[TW_UP] = p.up;
-                ph.w[TW_TW] = p.TW; ph.w[TW_TH] = p.TH; ph.w[TW_COLB] = p.colb; ph.w[TW_THSHIFT] = p.th_shift;
-                ph.w[TW_TILES_H] = p.tiles_h; ph.w[TW_TILES_IMG] = p.tiles_img; ph.w[TW_MAGIC_THV] = p.magic_thv;
-                ph.w[TW_MAGIC_CPG] = p.magic_cpg; ph.w[TW_GROUPS] = p.gn_groups; ph.w[TW_SILU] = p.silu;
-                putf(TW_INVN, p.gn_inv_n); putf(TW_EPS, p.gn_eps);
-                ph.w[TW_N] = p.N; ph.w[TW_YLD] = p.y_ld;
-                ph.w[TW_KIND] = TK_STREAM; ph.w[TW_TEMBOFF] = (unsigned)temb_off; ph.w[TW_SUB] = sub ? 1 : (p.st_inst == 7 ? 2 : 0);
-                pend.phases.push_back(ph);
+                pend.phases.push_back(trunk_conv_phase(p, TK_STREAM, true, temb_off));      // (no TW_G / TW_WBYTES: variants 2 and 4 neither prefetch nor warm)
                 pend.lds = std::max(pend.lds, conv_stream_lds_bytes(p));
                 pend.flops += fl;
                 pend.bytes += by;

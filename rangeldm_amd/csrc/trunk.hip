@@ -18,7 +18,7 @@
 // Second generation: the same seam for images of SEVERAL tiles.  At 13..16 images an image is 16 workgroups at every level --
 // 16 pixel tiles of conv_stream's 256 x 128 instance at 256x16, 4 x 4 tiles of conv_small's 64 x 64 instance at 64x4 -- so
 // 16 images x 16 = 256 workgroups fill the chip once, two images per XCD, and halos, channel slices and GroupNorm statistics
-// partials (folded by the CONSUMER phase, as in the stand-alone kernels) still never leave the image.  Four kernels (template V),
+// partials (folded by the CONSUMER phase, as in the stand-alone kernels) still never leave the image.  Four kernels (template V = 0, 1, 2, 4),
 // one per set of phase bodies, so that each set has its own register allocation; the bodies are the stand-alone kernels' code
 // (conv_small_body.h / conv_stream_body.h / attention_body.h, TRUNK = true) plus gn_apply_phase below.  DESIGN.md section 3.7.
 #include "conv_small_body.h"
@@ -27,84 +27,7 @@
 
 namespace rldm {
 
-// A phase record is 64 dwords (kernels.h, TrunkWord): every wave loads it with ONE instruction (lane l = word l) a phase ahead,
-// and v_readlane moves the fields into SGPRs -- where the kernel-argument copy of a stand-alone launch lives.  (Reading the record
-// field by field would be ~60 dependent VECTOR loads per phase: the launch also writes device memory, so the compiler may not use
-// scalar loads for it.)
-__device__ __forceinline__ unsigned rl(unsigned rec, int word) { return (unsigned)__builtin_amdgcn_readlane((int)rec, word); }
-// The pointer is built as a GLOBAL-address-space pointer and only then converted to the generic type the bodies take: the compiler
-// then proves every access through it global and emits global_load / global_store.  Built from an integer alone it is a FLAT pointer:
-// every load and store of every phase became a flat_* instruction, which counts on lgkmcnt as well as vmcnt -- each LDS wait of a K
-// loop then also waited for the whole weight ring in flight, i.e. the ring was no ring (round 3: the "open question" of DESIGN.md 3.7,
-// a 128x8 phase's K loop 16.3 k cycles against 12.8 k in the stand-alone launch; tools/l1_probe.sh).
-template <class T> __device__ __forceinline__ T* rl_ptr(unsigned rec, int word) {
-#ifdef RLDM_TRUNK_FLAT          // (A/B builds: the round-2 behaviour)
-    return reinterpret_cast<T*>(((unsigned long long)rl(rec, word + 1) << 32) | rl(rec, word));
-#else
-    typedef __attribute__((address_space(1))) T* global_ptr_t;
-    return (T*)(global_ptr_t)(((unsigned long long)rl(rec, word + 1) << 32) | rl(rec, word));
-#endif
-}
-__device__ __forceinline__ void unpack_phase(ConvParams& q, unsigned rec) {
-    q.x0 = rl_ptr<const bf16_t>(rec, TW_X0);
-    q.r0 = rl_ptr<const bf16_t>(rec, TW_R0);
-    q.r1 = rl_ptr<const bf16_t>(rec, TW_R1);
-    q.wpk = rl_ptr<const bf16_t>(rec, TW_WPK);
-    q.bias = rl_ptr<const float>(rec, TW_BIAS);
-    q.y = rl_ptr<bf16_t>(rec, TW_Y);
-    q.y_stats = rl_ptr<float2>(rec, TW_YSTATS);
-    q.res = rl_ptr<const bf16_t>(rec, TW_RES);
-    q.R0 = (int)rl(rec, TW_R0C); q.R1 = (int)rl(rec, TW_R1C);
-    q.Win = (int)rl(rec, TW_WIN); q.Hin = (int)rl(rec, TW_HIN); q.Wout = (int)rl(rec, TW_WOUT); q.Hout = (int)rl(rec, TW_HOUT);
-    q.TW = (int)rl(rec, TW_TW); q.TH = (int)rl(rec, TW_TH); q.colb = (int)rl(rec, TW_COLB); q.th_shift = (int)rl(rec, TW_THSHIFT);
-    q.N = (int)rl(rec, TW_N); q.y_ld = (int)rl(rec, TW_YLD); q.nviews = (int)rl(rec, TW_NVIEWS);
-#pragma unroll
-    for (int v = 0; v < 2; ++v) {
-        const int at = TW_NV0 + v * TW_NVSTRIDE;
-        q.nv[v].y = rl_ptr<bf16_t>(rec, at);
-        q.nv[v].gamma = rl_ptr<const float>(rec, at + 2);
-        q.nv[v].beta = rl_ptr<const float>(rec, at + 4);
-        q.nv[v].ld = (int)rl(rec, at + 6);
-        q.nv[v].cpg_shift = (int)rl(rec, at + 7);
-        q.nv[v].inv_n = __uint_as_float(rl(rec, at + 8));
-        q.nv[v].eps = __uint_as_float(rl(rec, at + 9));
-        q.nv[v].silu = (int)rl(rec, at + 10);
-    }
-    q.nv[2] = q.nv[1];                          // (trunk phases write at most two copies)
-    // what a trunk phase never has / what its tile implies
-    q.x1 = nullptr; q.C0 = 0; q.C1 = 0; q.st0 = nullptr; q.st1 = nullptr; q.P0 = 0; q.P1 = 0; q.temb = nullptr; q.step_ptr = nullptr;
-    q.ts = nullptr; q.up = 1; q.stride = 1; q.tiles_h = 1; q.tiles_img = 1; q.dbg = 0; q.silu = 0; q.B = 0;
-}
-// a phase of a multi-tile cluster (kind >= 8): no views; the words they would occupy carry the consumer-side GroupNorm of the input
-__device__ __forceinline__ void unpack_cluster_phase(ConvParams& q, unsigned rec) {
-    unpack_phase(q, rec);
-    q.nviews = 0;
-    q.st0 = rl_ptr<const float2>(rec, TW_ST0);
-    q.gn_gamma = rl_ptr<const float>(rec, TW_GAMMA);
-    q.gn_beta = rl_ptr<const float>(rec, TW_BETA);
-    q.P0 = (int)rl(rec, TW_P0);
-    q.gn_groups = (int)rl(rec, TW_GROUPS);
-    q.magic_cpg = (int)rl(rec, TW_MAGIC_CPG);
-    q.gn_inv_n = __uint_as_float(rl(rec, TW_INVN));
-    q.gn_eps = __uint_as_float(rl(rec, TW_EPS));
-    q.silu = (int)rl(rec, TW_SILU);
-    q.tiles_h = (int)rl(rec, TW_TILES_H);
-    q.tiles_img = (int)rl(rec, TW_TILES_IMG);
-    q.up = max((int)rl(rec, TW_UP), 1);         // (nearest x2 folded into the staging of an up-sampler's conv)
-    // (round 4) a concatenated input normalised by the phase itself: second tensor, its statistics, the split (C1 == 0: one tensor)
-    q.x1 = rl_ptr<const bf16_t>(rec, TW_X1);
-    q.st1 = rl_ptr<const float2>(rec, TW_ST1);
-    q.C0 = (int)rl(rec, TW_C0); q.C1 = (int)rl(rec, TW_C1); q.P1 = (int)rl(rec, TW_P1);
-}
-
-// a conv_stream phase (kind TK_STREAM): the cluster words + the second input tensor of a concatenation, nearest-x2, halo divisor
-__device__ __forceinline__ void unpack_stream_phase(ConvParams& q, unsigned rec) {
-    unpack_cluster_phase(q, rec);
-    q.x1 = rl_ptr<const bf16_t>(rec, TW_X1);
-    q.st1 = rl_ptr<const float2>(rec, TW_ST1);
-    q.C0 = (int)rl(rec, TW_C0); q.C1 = (int)rl(rec, TW_C1); q.P1 = (int)rl(rec, TW_P1);
-    q.magic_thv = (int)rl(rec, TW_MAGIC_THV);
-}
+// (the phase record, its encoders and the unpack_* decoders used below: trunk_record.h)
 
 // GroupNorm (+ SiLU) of cat[x0, x1] as a phase (a concatenated conv input is normalised once, not by every channel tile of the conv:
 // norm.hip's gn_apply_kernel, same arithmetic per element): rank r of the image's cluster takes pixels [r, r + 1) * npix / ranks, all
@@ -138,12 +61,12 @@ __device__ __forceinline__ void gn_apply_phase(const ConvParams& cp, const int r
         for (; q + 4 <= P; q += 4) {
             float2 u[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) u[j] = ld_act8<true>(src + (size_t)(q + j) * C);
+            for (int j = 0; j < 4; ++j) u[j] = ld_act8(src + (size_t)(q + j) * C);
 #pragma unroll
             for (int j = 0; j < 4; ++j) { S += (double)u[j].x; SS += (double)u[j].y; }
         }
         for (; q < P; ++q) {
-            const float2 u = ld_act8<true>(src + (size_t)q * C);
+            const float2 u = ld_act8(src + (size_t)q * C);
             S += (double)u.x;
             SS += (double)u.y;
         }
@@ -164,7 +87,7 @@ __device__ __forceinline__ void gn_apply_phase(const ConvParams& cp, const int r
             v[j] = make_uint4(0u, 0u, 0u, 0u);
             if (q < total) {
                 const bool first = cl[j] < C0;
-                v[j] = ld_act16<true>(first ? gx0 + pix * C0 + cl[j] : gx1 + pix * C1 + (cl[j] - C0));
+                v[j] = ld_act16(first ? gx0 + pix * C0 + cl[j] : gx1 + pix * C1 + (cl[j] - C0));
             }
         }
     };
@@ -214,14 +137,16 @@ __device__ __forceinline__ void gn_apply_phase(const ConvParams& cp, const int r
     trunk_arrive(seam, tid);
 }
 
-// CL = false: image-owning tiles (kinds 0..6 + attention over a pre-normalised x); CL = true: multi-tile clusters (kinds 8..13).
-// Two kernels, so that each set of instances gets its own register allocation.
+// V == 0: image-owning tiles (kinds 0..6, 16..18 + attention over a pre-normalised x); V == 1 (CL): multi-tile clusters (kinds 8..13);
+// V == 2: the full-resolution level on conv_stream's 8-wave 256 x 128 instance.  One kernel each, so that each set of instances gets its
+// own register allocation.
 // V == 4 (round 4): the full-resolution level on conv_stream's 4-wave 128 x 128 instance -- 32 workgroups of 256 threads per image,
 // TWO workgroups per CU (512 in all at 16 images: __launch_bounds__' second argument is waves per SIMD).  The two workgroups of a
 // CU belong to different images (block ids below 256 are images 0..7, the rest images 8..15), i.e. to clusters that are never
 // ordered against each other: one's statistics round trip / fold / first halo chunk / epilogue runs under the other's K loop.
 template <int V>
 __global__ void __launch_bounds__(V == 4 ? 256 : 512, V == 4 ? 2 : 1) trunk_kernel(const TrunkParams tp) {
+    static_assert(V == 0 || V == 1 || V == 2 || V == 4, "trunk_kernel: the variants that are launched");
     constexpr bool CL = V == 1, ST = V >= 2;
     // block id -> (image, channel tile): ids with the same (id % 8) share an XCD; an image's `ranks` tiles are 8 apart
     const int wg = blockIdx.x;
@@ -259,9 +184,8 @@ __global__ void __launch_bounds__(V == 4 ? 256 : 512, V == 4 ? 2 : 1) trunk_kern
     auto wave_stream = [&](unsigned r) __attribute__((always_inline)) {
         return reinterpret_cast<const unsigned char*>(rl_ptr<const bf16_t>(r, TW_WPK)) + ((size_t)stream_id * rl(r, TW_NMINE)) * 1024;
     };
-    // (round 4: the multi-tile clusters of variant 1 carry kClusterPrefetch fragments across phases too -- the kernel sits at 196 VGPRs since
-    //  round 2's hoisting fix, and its K loops start on weights that every XCD pulls from the Infinity Cache: 8.7 k cycles against 3 k stand-alone)
-    constexpr bool PFV = V == 0 || (V == 1 && kClusterPrefetch > 0);
+    // (only variant 0 carries weight fragments across phases: the multi-tile clusters of variant 1 warm the L2 instead, trunk_seam.h)
+    constexpr bool PFV = V == 0;
     if constexpr (PFV) {
         const unsigned char* w0 = wave_stream(rec);
         const int g0 = (int)rl(rec, TW_G);
@@ -300,11 +224,6 @@ __global__ void __launch_bounds__(V == 4 ? 256 : 512, V == 4 ? 2 : 1) trunk_kern
         bool conv_done = true;
         if constexpr (V == 2) {
             conv_stream_body<2, 4, true>(cp, nt, mt, b, seam);      // full-resolution level: 16 tiles of 256 pixels x 128 channels per image
-        } else if constexpr (V == 3) {
-            conv_stream_body<1, 2, true>(cp, nt, mt, b, seam);      // 128x8 level: 8 tiles of 128 pixels x 2 channel tiles of 64
-        } else if constexpr (V == 5) {
-            // (round 5) 128x8 level on round 4's tile: 16 tiles of 64 pixels (8 x 8) x 128 channels x 2 k-groups per image
-            conv_stream_body<1, 4, true, 8, 2>(cp, nt, mt, b, seam);
         } else if constexpr (V == 4) {
             // full-resolution level: 32 tiles of 128 pixels x 128 channels per image, 4 waves; the level's up-sampler conv in its sub-pixel
             // form: 8 INPUT tiles x 4 parities
@@ -343,23 +262,12 @@ __global__ void __launch_bounds__(V == 4 ? 256 : 512, V == 4 ? 2 : 1) trunk_kern
             switch (kind) {
                 // (round 4: 128 input channels -- the first conv of the level, behind the stride-2 down-sampler; the kernel has had the registers
                 //  for its 18-fragment ring since round 2's hoisting fix)
-                case TK_CL_3x3_128: conv_small_body<2, 2, 9, 2, true, kClusterPrefetch>(cp, nt, mt, b, wpf, seam); break;
-                case TK_CL_3x3_256: conv_small_body<2, 4, 9, 2, true, kClusterPrefetch>(cp, nt, mt, b, wpf, seam); break;
-                case TK_CL_3x3_384: conv_small_body<2, 6, 9, 2, true, kClusterPrefetch>(cp, nt, mt, b, wpf, seam); break;
-                case TK_CL_3x3_512: conv_small_body<2, 8, 9, 2, true, kClusterPrefetch>(cp, nt, mt, b, wpf, seam); break;
-                case TK_CL_1x1_256: conv_small_body<2, 4, 1, 2, true, kClusterPrefetch>(cp, nt, mt, b, wpf, seam); break;
-                case TK_GN_APPLY: {
-                    gn_apply_phase(cp, rank, ranks, b, seam);
-                    if constexpr (kClusterPrefetch > 0) {       // (a phase without weights: the next conv's first fragments are requested here)
-                        const int next_g = (int)rl(nrec, TW_G);
-                        if (next_g > 0) {
-                            const unsigned char* nw = wave_stream(nrec);
-#pragma unroll
-                            for (int j = 0; j < kClusterPrefetch; ++j)
-                                if (j < next_g) wpf[j] = *reinterpret_cast<const bf16x8*>(nw + (unsigned)(j * 1024 + lane * 16));
-                        }
-                    }
-                } break;
+                case TK_CL_3x3_128: conv_small_body<2, 2, 9, 2, true, 0>(cp, nt, mt, b, wpf, seam); break;
+                case TK_CL_3x3_256: conv_small_body<2, 4, 9, 2, true, 0>(cp, nt, mt, b, wpf, seam); break;
+                case TK_CL_3x3_384: conv_small_body<2, 6, 9, 2, true, 0>(cp, nt, mt, b, wpf, seam); break;
+                case TK_CL_3x3_512: conv_small_body<2, 8, 9, 2, true, 0>(cp, nt, mt, b, wpf, seam); break;
+                case TK_CL_1x1_256: conv_small_body<2, 4, 1, 2, true, 0>(cp, nt, mt, b, wpf, seam); break;
+                case TK_GN_APPLY: gn_apply_phase(cp, rank, ranks, b, seam); break;
                 default: conv_done = false; break;
             }
         }
@@ -397,18 +305,32 @@ __global__ void __launch_bounds__(V == 4 ? 256 : 512, V == 4 ? 2 : 1) trunk_kern
     if (rank == 0 && tid == 0) counter[3] = epoch + 1u;
 }
 
+// a variant's kernel and its workgroup size (null: no such variant)
+struct TrunkKernel {
+    void (*kern)(const TrunkParams);
+    int threads;
+};
+static TrunkKernel trunk_kernel_of(int variant) {
+    switch (variant) {
+        case 0: return {trunk_kernel<0>, 512};
+        case 1: return {trunk_kernel<1>, 512};
+        case 2: return {trunk_kernel<2>, 512};
+        case 4: return {trunk_kernel<4>, 256};
+        default: return {nullptr, 0};
+    }
+}
+static DynLdsLimit g_trunk_lds_limit[5];        // per variant and device, thread safe
+
 // workgroups of trunk_kernel<variant> the runtime will keep resident on ONE CU with `lds` bytes of dynamic LDS each (< 0: the query
 // failed).  The plan builder asks before it commits a segment to a persistent launch: a spin-waiting grid that is not co-resident
 // only fails through the bounded-wait self-check, which is a slow way to find out (variant 4 needs TWO per CU: 2 x 80 KiB is the
 // whole LDS, so any static LDS, scratch or a partitioned CU would halve it).
 int trunk_max_resident(int variant, size_t lds) {
-    if (variant < 0 || variant > 5) return -1;
-    static DynLdsLimit lds_limit[6];
-    const int cl = variant;
-    auto kern = cl == 0 ? trunk_kernel<0> : (cl == 1 ? trunk_kernel<1> : (cl == 2 ? trunk_kernel<2> : (cl == 3 ? trunk_kernel<3> : (cl == 4 ? trunk_kernel<4> : trunk_kernel<5>))));
-    if (lds_limit[cl].ensure(reinterpret_cast<const void*>(kern), lds) != hipSuccess) return -1;
+    const TrunkKernel k = trunk_kernel_of(variant);
+    if (!k.kern) return -1;
+    if (g_trunk_lds_limit[variant].ensure(reinterpret_cast<const void*>(k.kern), lds) != hipSuccess) return -1;
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(kern), cl == 4 ? 256 : 512, lds) != hipSuccess) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(k.kern), k.threads, lds) != hipSuccess) {
         (void)hipGetLastError();
         return -1;
     }
@@ -416,7 +338,8 @@ int trunk_max_resident(int variant, size_t lds) {
 }
 
 int launch_trunk(const TrunkParams& tp, size_t lds, hipStream_t stream) {
-    RLDM_REQUIRE(tp.variant >= 0 && tp.variant <= 5, "trunk: bad kernel variant");
+    const TrunkKernel k = trunk_kernel_of(tp.variant);
+    RLDM_REQUIRE(k.kern != nullptr, "trunk: bad kernel variant");
     const int per_cu = tp.variant == 4 ? 2 : 1;  // (variant 4: 256-thread workgroups, two per CU)
     RLDM_REQUIRE(tp.nphases >= 1 && tp.ranks >= 1 && tp.ranks <= 16 * per_cu && tp.B >= 1 && (tp.nwn == 1 || tp.nwn == 2 || tp.nwn == 4) &&
                      tp.ntile_n >= 1 && tp.ranks % tp.ntile_n == 0, "trunk: bad parameters");
@@ -424,11 +347,8 @@ int launch_trunk(const TrunkParams& tp, size_t lds, hipStream_t stream) {
     const int groups = (tp.B + 7) / 8;
     const int grid = 8 * tp.ranks * groups;
     RLDM_REQUIRE(grid <= 256 * per_cu, "trunk: the grid must be co-resident (one workgroup per CU; two of the 4-wave variant)");
-    static DynLdsLimit lds_limit[6];             // per instantiation and device, thread safe
-    const int cl = tp.variant;
-    auto kern = cl == 0 ? trunk_kernel<0> : (cl == 1 ? trunk_kernel<1> : (cl == 2 ? trunk_kernel<2> : (cl == 3 ? trunk_kernel<3> : (cl == 4 ? trunk_kernel<4> : trunk_kernel<5>))));
-    RLDM_HIP_CHECK(lds_limit[cl].ensure(reinterpret_cast<const void*>(kern), lds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(cl == 4 ? 256 : 512), lds, stream, tp);
+    RLDM_HIP_CHECK(g_trunk_lds_limit[tp.variant].ensure(reinterpret_cast<const void*>(k.kern), lds));
+    hipLaunchKernelGGL(k.kern, dim3(grid), dim3(k.threads), lds, stream, tp);
     RLDM_HIP_CHECK(hipGetLastError());
     return 0;
 }

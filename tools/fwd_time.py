@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Time of one UNet forward at batch B (HIP events over N replays of the eager plan), values ignored: for ablation builds whose
-results are garbage (RLDM_LIB=... python tools/fwd_time.py [--B 16] [--n 50])."""
+"""Time of one UNet forward at batch B (HIP events over N replays of the eager plan; the values are not checked) with whichever build of
+the library RLDM_LIB names, the in-tree one by default ([RLDM_LIB=...] python tools/fwd_time.py [--B 16] [--n 50])."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -36,8 +36,8 @@ def op_name(k):
         return f"conv_regw_kernel<128,{32 * int(m.group(2))},taps9>"
     m = re.match(r"trunk_kernel<(\d+)>", k)
     if m:       # persistent launches: one entry per kernel variant (bench.py scales it by a launch's share of the variant's phases)
-        return "trunk_kernel<" + ("conv_small image tiles", "conv_small 64x64 clusters", "conv_stream 256x128", "conv_stream 128x64",
-                                 "conv_stream 128x128 x2/CU", "conv_stream 64x128")[int(m.group(1))] + ">"
+        return "trunk_kernel<" + {0: "conv_small image tiles", 1: "conv_small 64x64 clusters", 2: "conv_stream 256x128",
+                                  4: "conv_stream 128x128 x2/CU"}[int(m.group(1))] + ">"
     if re.match(r"attention_qkv2_d8_kernel<1>", k):      # bench.py's name of the 1024-token launch with its fused output projection
         return "attention_qkv_d8_kernel + to_out"
     if re.match(r"attention_qkv2_d8_kernel<0>", k):
