@@ -282,6 +282,26 @@ int rldm_chamfer_nn(const float* x, const int32_t* x_offsets, int x_stride, cons
  * a fixed-order reduction (bit-identical run to run).  CD of pair p = x_mean[p] + y_mean[p]. */
 int rldm_chamfer_mean(const float* x_nn_d2, const int32_t* x_offsets, const float* y_nn_d2, const int32_t* y_offsets,
                       int num_pairs, double* x_mean, double* y_mean, void* stream);
+/* All-pairs Chamfer matrix between two ragged SETS of clouds, X (nx clouds) and Y (ny clouds), packed as rldm_chamfer_nn
+ * takes them (device fp32 [n][stride >= 3], only xyz read; device int32 offsets [nx + 1] / [ny + 1], starting at 0):
+ *   xy[i][j] = mean over points q of X_i of min over points t of Y_j of d2(q, t)
+ *   yx[i][j] = mean over points t of Y_j of min over points q of X_i of d2(q, t)          CD[i][j] = xy[i][j] + yx[i][j]
+ * xy / yx device fp64 [nx][ny].  d2 and every minimum as in rldm_chamfer_nn (bit-equal to the fp32 expression on the CPU);
+ * each mean is an fp64 sum of the minima in a fixed order that depends on the two clouds alone (per 2048-point block of
+ * the averaged cloud, then the blocks in order), divided once: bit-identical run to run, and identical whether a row is
+ * computed in this call or in a call that holds only a block of the rows.  No floating-point atomics.
+ * symmetric != 0: Y is X -- the caller passes the SAME buffers, offsets, stride and count; only j > i is computed, the
+ * diagonal is 0 and xy[j][i] = yx[i][j], yx[j][i] = xy[i][j] (bit-equal to the rectangular call on (X, X) off the diagonal).
+ * Every cloud must be non-empty; non-finite coordinates give unspecified results.  nx * ny < 2^31, and the scratch
+ * (2048-point blocks of one set x clouds of the other, fp64) at most 2^28 entries: else an error (rldm_last_error).
+ * The call synchronises the stream. */
+int rldm_chamfer_matrix(const float* x, const int32_t* x_offsets, int x_stride, int nx, const float* y,
+                        const int32_t* y_offsets, int y_stride, int ny, int symmetric, double* xy, double* yx, void* stream);
+/* Per row of a device fp64 matrix m [rows][cols] its minimum (min_out device fp64 [rows]) and the LOWEST column index
+ * attaining it (arg_out device int32 [rows]): the tie rule the set metrics (COV, 1-NNA) count with.  exclude_diag != 0
+ * skips column r of row r; a row left without a column gives +inf / -1.  NaN entries give unspecified results. */
+int rldm_matrix_row_argmin(const double* m, int rows, int cols, int exclude_diag, double* min_out, int32_t* arg_out,
+                           void* stream);
 /* Range-image errors (ldm/convert_vae.py:236-247 MAE / PSNR; metrics/metrics/mae.py:45-117 range MAE): a, b device fp32
  * (B, C, W, H), C <= 8.  Per image, over the channels of channel_mask and the azimuth columns (w0 + k) mod W,
  * k in [0, w1 - w0) (0 <= w0 < W, w0 < w1 <= w0 + W: the window may wrap past the seam), with v -> v * scale[c] + shift[c]

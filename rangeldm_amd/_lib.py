@@ -154,6 +154,9 @@ PROTOTYPES = {
     # pytorch3d.loss.chamfer_distance as ldm/convert_vae.py:262-271 calls it (nearest squared distances, then per-pair means)
     "rldm_chamfer_nn": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "rldm_chamfer_mean": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P]),
+    # all-pairs Chamfer matrix of two sets of clouds, and the lowest-index row argmin the set metrics count with
+    "rldm_chamfer_matrix": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "rldm_matrix_row_argmin": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     # MAE / PSNR of ldm/convert_vae.py:236-247 and the range MAE of metrics/metrics/mae.py:45-117
     "rldm_range_errors": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
                                     C.POINTER(C.c_float), C.c_int, C.c_int, _P, _P, _P]),

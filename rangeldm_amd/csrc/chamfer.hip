@@ -4,6 +4,10 @@
 //
 //   chamfer_nn_kernel      for every query point the SQUARED distance to its nearest neighbour in the other cloud of its pair
 //   chamfer_mean_kernel    per pair and direction the mean of those minima, fp64, fixed order
+//   chamfer_matrix_kernel  one direction of the ALL-PAIRS matrix between two sets of clouds: a workgroup keeps one query block
+//                          in registers and streams a run of target clouds past it, one fp64 block sum per (i, j, block)
+//   matrix_finish_kernel   those block sums added in block order and divided once -> xy / yx
+//   row_argmin_kernel      per row of an fp64 matrix the minimum and the LOWEST column attaining it
 //   range_errors_kernel    per image fp64 sum |a - b| and sum (a - b)^2 after a per-channel affine map, over a channel set and
 //                          an azimuth window that may wrap past the seam
 //   beam_upsample_kernel   (B, C, W, Hs) -> (B, C, W, Hs * rate) along the beam axis: cv2 INTER_NEAREST / INTER_CUBIC
@@ -153,6 +157,144 @@ __global__ __launch_bounds__(256) void chamfer_mean_kernel(const float* __restri
     if (threadIdx.x == 0) (blockIdx.y ? ymean : xmean)[p] = acc / (double)(e - b);
 }
 
+// ---- all-pairs matrix -----------------------------------------------------------------------------------------------
+// One direction: query set Q (nq clouds), target set T (nt clouds).  Workgroup = (query block g, run r): the block's NN_QB
+// points stay in registers while the target clouds [r * run, (r + 1) * run) -- in the symmetric case only those above
+// (tri > 0) or below (tri < 0) the query cloud -- stream through the LDS tile with chamfer_nn_kernel's inner loop.  A target
+// cloud is never split, so each minimum is final when its cloud ends: the block then adds its minima in fp64 (per thread in
+// slot order, block_sum across threads) into part[qb_start[c] * nt + j * nqb(c) + qb].  That sum depends on (c, qb, j)
+// alone -- not on `run`, the grid, or which other clouds the call holds.
+__global__ __launch_bounds__(NN_THREADS) void chamfer_matrix_kernel(const float* __restrict__ q, const int* __restrict__ qoff,
+                                                                    int qstride, int nq, const float* __restrict__ t,
+                                                                    const int* __restrict__ toff, int tstride, int nt,
+                                                                    const int* __restrict__ qb_start, int run, int runs,
+                                                                    int tri, double* __restrict__ part) {
+    __shared__ float4 tile[NN_TILE];
+    __shared__ double sh[NN_THREADS / 64];
+    const int tid = threadIdx.x;
+    const int g = blockIdx.x / runs, r = blockIdx.x - g * runs;
+    int lo = 0, hi = nq;                                 // qb_start[lo] <= g < qb_start[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (qb_start[mid] <= g) lo = mid; else hi = mid;
+    }
+    const int c = lo, qb = g - qb_start[c], nqb = qb_start[c + 1] - qb_start[c];
+    int j0 = r * run, j1 = min(nt, j0 + run);
+    if (tri > 0) j0 = max(j0, c + 1);
+    if (tri < 0) j1 = min(j1, c);
+    if (j0 >= j1) return;                                // (uniform over the workgroup)
+    const int q0 = qoff[c], nqp = qoff[c + 1] - q0;
+
+    f2 qx[NN_R / 2], qy[NN_R / 2], qz[NN_R / 2];
+#pragma unroll
+    for (int k = 0; k < NN_R / 2; ++k) {
+        float v[2][3];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int i = min(qb * NN_QB + (2 * k + h) * NN_THREADS + tid, nqp - 1);    // past the end: a valid duplicate
+            const float* pt = q + (size_t)(q0 + i) * qstride;
+            v[h][0] = pt[0]; v[h][1] = pt[1]; v[h][2] = pt[2];
+        }
+        qx[k] = f2{v[0][0], v[1][0]};
+        qy[k] = f2{v[0][1], v[1][1]};
+        qz[k] = f2{v[0][2], v[1][2]};
+    }
+
+    for (int j = j0; j < j1; ++j) {
+        const int t0 = toff[j], ntp = toff[j + 1] - t0;
+        f2 best[NN_R / 2];
+#pragma unroll
+        for (int k = 0; k < NN_R / 2; ++k) best[k] = f2{INFINITY, INFINITY};
+        for (int base = 0; base < ntp; base += NN_TILE) {
+            const int n = min(NN_TILE, ntp - base);
+            __syncthreads();                             // the previous tile has been read
+            for (int i = tid; i < NN_TILE; i += NN_THREADS) {
+                float4 v = make_float4(INFINITY, INFINITY, INFINITY, 0.f);
+                if (i < n) {
+                    const float* pt = t + (size_t)(t0 + base + i) * tstride;
+                    v = make_float4(pt[0], pt[1], pt[2], 0.f);
+                }
+                tile[i] = v;
+            }
+            __syncthreads();
+            const int n4 = (n + 3) & ~3;                 // entries [n, n4) are the +inf padding
+            for (int e = 0; e < n4; e += 4) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const float4 tp = tile[e + u];
+                    const f2 tx = f2{tp.x, tp.x}, ty = f2{tp.y, tp.y}, tz = f2{tp.z, tp.z};
+#pragma unroll
+                    for (int k = 0; k < NN_R / 2; ++k) {
+                        const f2 dx = qx[k] - tx, dy = qy[k] - ty, dz = qz[k] - tz;
+                        const f2 d2 = (dx * dx + dy * dy) + dz * dz;
+                        best[k] = min2(best[k], d2);
+                    }
+                }
+            }
+        }
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < NN_R / 2; ++k) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                if (qb * NN_QB + (2 * k + h) * NN_THREADS + tid < nqp) acc += (double)(h ? best[k].y : best[k].x);
+        }
+        acc = block_sum(acc, sh);
+        if (tid == 0) part[(size_t)qb_start[c] * nt + (size_t)j * nqb + qb] = acc;
+    }
+}
+
+// one thread per (query cloud c, target cloud j): the block sums in block order, divided once.  main[c * mc + j * mj] gets the
+// mean; in the symmetric case the other matrix's mirrored entry (mirror[c * mj + j * mc]) gets it too.
+__global__ __launch_bounds__(256) void matrix_finish_kernel(const double* __restrict__ part, const int* __restrict__ qoff,
+                                                            const int* __restrict__ qb_start, int nq, int nt, int tri,
+                                                            double* __restrict__ main_out, long long mc, long long mj,
+                                                            double* __restrict__ mirror) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long long)nq * nt) return;
+    const int c = (int)(e / nt), j = (int)(e - (long long)c * nt);
+    if ((tri > 0 && j <= c) || (tri < 0 && j >= c)) return;
+    const int nqb = qb_start[c + 1] - qb_start[c];
+    const double* p = part + (size_t)qb_start[c] * nt + (size_t)j * nqb;
+    double s = 0.0;
+    for (int b = 0; b < nqb; ++b) s += p[b];
+    s /= (double)(qoff[c + 1] - qoff[c]);
+    main_out[c * mc + j * mj] = s;
+    if (mirror) mirror[c * mj + j * mc] = s;
+}
+
+// one workgroup per row: every thread scans its columns upwards (a strict < keeps the first), then the 256 candidates are
+// merged pairwise with "smaller value, else smaller column" -- the lowest column attaining the row minimum, in any order
+__global__ __launch_bounds__(256) void row_argmin_kernel(const double* __restrict__ m, int cols, int exclude_diag,
+                                                         double* __restrict__ min_out, int* __restrict__ arg_out) {
+    __shared__ double sv[256];
+    __shared__ int si[256];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const double* p = m + (size_t)row * cols;
+    double bv = INFINITY;
+    int bi = 0x7fffffff;
+    for (int j = tid; j < cols; j += 256) {
+        if (exclude_diag && j == row) continue;
+        const double v = p[j];
+        if (v < bv || bi == 0x7fffffff) { bv = v; bi = j; }
+    }
+    sv[tid] = bv;
+    si[tid] = bi;
+    __syncthreads();
+    for (int o = 128; o; o >>= 1) {
+        if (tid < o) {
+            const double v = sv[tid + o];
+            const int i = si[tid + o];
+            if (v < sv[tid] || (v == sv[tid] && i < si[tid])) { sv[tid] = v; si[tid] = i; }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        min_out[row] = sv[0];
+        arg_out[row] = si[0] == 0x7fffffff ? -1 : si[0];
+    }
+}
+
 // ---- range-image errors -------------------------------------------------------------------------------------------
 constexpr int RE_MAXC = 8;
 struct RangeErrArgs {                                    // kernel-argument block (not part of the C ABI)
@@ -290,6 +432,95 @@ int rldm_chamfer_mean(const float* x_nn_d2, const int32_t* x_offsets, const floa
     RLDM_REQUIRE(num_pairs > 0, "bad shape");
     hipStream_t st = (hipStream_t)stream;
     chamfer_mean_kernel<<<dim3(num_pairs, 2), 256, 0, st>>>(x_nn_d2, x_offsets, y_nn_d2, y_offsets, x_mean, y_mean);
+    RLDM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int rldm_chamfer_matrix(const float* x, const int32_t* x_offsets, int x_stride, int nx, const float* y,
+                        const int32_t* y_offsets, int y_stride, int ny, int symmetric, double* xy, double* yx, void* stream) {
+    RLDM_REQUIRE(x && x_offsets && y && y_offsets && xy && yx, "null argument");
+    RLDM_REQUIRE(nx > 0 && ny > 0 && x_stride >= 3 && y_stride >= 3, "bad shape");
+    RLDM_REQUIRE(!symmetric || (x == y && x_offsets == y_offsets && x_stride == y_stride && nx == ny),
+                 "symmetric: y must be x (the same buffers)");
+    RLDM_REQUIRE((long long)nx * ny < (1LL << 31), "matrix too large (nx * ny must stay below 2^31)");
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int32_t> off[2] = {std::vector<int32_t>(nx + 1), std::vector<int32_t>(ny + 1)};
+    RLDM_HIP_CHECK(hipMemcpyAsync(off[0].data(), x_offsets, off[0].size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    RLDM_HIP_CHECK(hipMemcpyAsync(off[1].data(), y_offsets, off[1].size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    RLDM_HIP_CHECK(hipStreamSynchronize(st));
+    RLDM_REQUIRE(off[0][0] == 0 && off[1][0] == 0, "offsets must start at 0");
+    const int n[2] = {nx, ny};
+    // query-block tables of both sets in one allocation: [x: nx + 1][y: ny + 1]
+    std::vector<int32_t> qbs(nx + ny + 2);
+    int32_t* qb[2] = {qbs.data(), qbs.data() + nx + 1};
+    for (int s = 0; s < 2; ++s) {
+        long long acc = 0;
+        for (int c = 0; c < n[s]; ++c) {
+            RLDM_REQUIRE(off[s][c + 1] > off[s][c], "every cloud must be non-empty");
+            qb[s][c] = (int32_t)acc;
+            acc += (off[s][c + 1] - off[s][c] + NN_QB - 1) / NN_QB;
+        }
+        qb[s][n[s]] = (int32_t)acc;
+    }
+    // direction 0: X queries, Y targets; direction 1: Y queries, X targets.  A run is a whole number of target clouds: long
+    // enough to amortise the query load (>= MX_RUN_POINTS targets on average), short enough that the grid has many more
+    // workgroups than the chip has slots (the tail of an uneven last wave of workgroups stays small)
+    constexpr long long MX_RUN_POINTS = 16384, MX_MAX_WGS = (1LL << 31) / NN_THREADS, MX_MAX_PART = 1LL << 28;
+    int run[2], runs[2];
+    long long part_len = 0;
+    for (int d = 0; d < 2; ++d) {
+        const int s = d, t = 1 - d;
+        const long long blocks = qb[s][n[s]], tpoints = off[t][n[t]];
+        RLDM_REQUIRE(blocks * n[t] <= MX_MAX_PART, "scratch too large (query blocks x target clouds above 2^28)");
+        part_len = std::max(part_len, blocks * n[t]);
+        const long long want = (16LL * NN_FILL_WGS + blocks - 1) / blocks;
+        long long len = std::max<long long>((n[t] + want - 1) / want, (MX_RUN_POINTS * n[t] + tpoints - 1) / tpoints);
+        len = std::min<long long>(std::max<long long>(len, 1), n[t]);
+        while (len < n[t] && blocks * ((n[t] + len - 1) / len) >= MX_MAX_WGS) len *= 2;
+        len = std::min<long long>(len, n[t]);
+        run[d] = (int)len;
+        runs[d] = (int)((n[t] + len - 1) / len);
+        RLDM_REQUIRE(blocks * runs[d] < MX_MAX_WGS, "too many workgroups");
+    }
+    int32_t* dqb = nullptr;
+    double* part = nullptr;
+    RLDM_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&dqb), qbs.size() * sizeof(int32_t), st));
+    RLDM_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&part), (size_t)part_len * sizeof(double), st));
+    RLDM_HIP_CHECK(hipMemcpyAsync(dqb, qbs.data(), qbs.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (symmetric) {                                     // the diagonal; every other entry is written below
+        RLDM_HIP_CHECK(hipMemsetAsync(xy, 0, (size_t)nx * ny * sizeof(double), st));
+        RLDM_HIP_CHECK(hipMemsetAsync(yx, 0, (size_t)nx * ny * sizeof(double), st));
+    }
+    const int fin_grid = (int)(((long long)nx * ny + 255) / 256);
+    for (int d = 0; d < 2; ++d) {                        // one after the other on the stream: they share `part`
+        const int tri = symmetric ? (d ? -1 : 1) : 0;
+        const int grid = qb[d][n[d]] * runs[d];
+        if (d == 0) {
+            chamfer_matrix_kernel<<<grid, NN_THREADS, 0, st>>>(x, x_offsets, x_stride, nx, y, y_offsets, y_stride, ny, dqb,
+                                                               run[0], runs[0], tri, part);
+            RLDM_HIP_CHECK(hipGetLastError());
+            matrix_finish_kernel<<<fin_grid, 256, 0, st>>>(part, x_offsets, dqb, nx, ny, tri, xy, ny, 1,
+                                                           symmetric ? yx : nullptr);
+        } else {
+            chamfer_matrix_kernel<<<grid, NN_THREADS, 0, st>>>(y, y_offsets, y_stride, ny, x, x_offsets, x_stride, nx,
+                                                               dqb + nx + 1, run[1], runs[1], tri, part);
+            RLDM_HIP_CHECK(hipGetLastError());
+            matrix_finish_kernel<<<fin_grid, 256, 0, st>>>(part, y_offsets, dqb + nx + 1, ny, nx, tri, yx, 1, ny,
+                                                           symmetric ? xy : nullptr);
+        }
+        RLDM_HIP_CHECK(hipGetLastError());
+    }
+    RLDM_HIP_CHECK(hipFreeAsync(part, st));
+    RLDM_HIP_CHECK(hipFreeAsync(dqb, st));
+    RLDM_HIP_CHECK(hipStreamSynchronize(st));          // `qbs` (pageable host memory) must outlive its upload
+    return 0;
+}
+
+int rldm_matrix_row_argmin(const double* m, int rows, int cols, int exclude_diag, double* min_out, int32_t* arg_out,
+                           void* stream) {
+    RLDM_REQUIRE(m && min_out && arg_out, "null argument");
+    RLDM_REQUIRE(rows > 0 && cols > 0, "bad shape");
+    row_argmin_kernel<<<rows, 256, 0, (hipStream_t)stream>>>(m, cols, exclude_diag != 0, min_out, arg_out);
     RLDM_HIP_CHECK(hipGetLastError());
     return 0;
 }

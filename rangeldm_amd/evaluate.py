@@ -1,9 +1,10 @@
-"""Reconstruction evaluation on the MI355X: score what the VAE and the conditional sampler reconstruct.
+"""Evaluation on the MI355X: score what the VAE and the conditional sampler reconstruct, and what the sampler generates.
 
     python -m rangeldm_amd.evaluate vae --weights outputs/RangeLDM --samples 1000 --batch-size 4 [--input DIR]
     python -m rangeldm_amd.evaluate densification --exp outputs/upsample/generated [--cfg upsample]
     python -m rangeldm_amd.evaluate inpainting --exp outputs/inpainting/generated [--cfg inpainting]
     python -m rangeldm_amd.evaluate chamfer A_DIR B_DIR
+    python -m rangeldm_amd.evaluate generation GEN_DIR REF_DIR [--points 2048] [--limit N] [--seed 0] [--max-depth M]
 
 Every command prints one JSON object on stdout (`--json PATH` also writes it).  Under `torch.distributed.run` the work is
 sharded over the ranks and rank 0 reduces and prints.  The arithmetic runs in librangeldm_hip (rangeldm_amd/csrc/chamfer.hip
@@ -21,6 +22,12 @@ mean_x min_y |x - y|^2 + mean_y min_x |x - y|^2 over xyz.
   inpainting     mae.py:91-117 (`metric.py --inpainting_mae`): range MAE in metres over the config's masked azimuth span,
                  with the reference's denominator (files x W x H, mae.py:111) and per masked pixel; and CD.
   chamfer        mean CD over the .bin files of two folders, paired by name.
+  generation     set-level metrics of a folder of generated .bin clouds against a folder of reference sweeps (Achlioptas et
+                 al. 2018; Yang et al. 2019): MMD-CD, COV-CD and 1-NNA-CD (metrics.set_metrics) from the all-pairs Chamfer
+                 matrices, every cloud cut to the points closer than --max-depth and sub-sampled to --points
+                 (metrics.subsample with seed + file index); the BEV-histogram jsd / mmd of metrics.evaluate_folders on the
+                 full clouds beside them.  Each rank computes a block of rows of each matrix; an entry does not depend on the
+                 block it was computed in, so the result is the same for any number of ranks.
 
 Only the linear range normalisation (x * std + mean, every shipped config) is supported: `log` / `inverse` sensors raise
 NotImplementedError.  nuScenes `.bin` files carry no ring column, so they cannot be re-projected: nuScenes raises too.
@@ -43,7 +50,8 @@ _RESULT_RE = re.compile(r"^(\d+)_seed_(\d+)\.bin$")
 # ---- host-side helpers (no GPU) ---------------------------------------------------------------------------------------
 def build_parser():
     ap = argparse.ArgumentParser(prog="python -m rangeldm_amd.evaluate",
-                                 description="reconstruction metrics (MAE, PSNR, Chamfer distance) on MI355X")
+                                 description="reconstruction metrics (MAE, PSNR, Chamfer distance) and set-level generation "
+                                             "metrics (MMD-CD, COV-CD, 1-NNA-CD) on MI355X")
     sub = ap.add_subparsers(dest="cmd", required=True)
 
     v = sub.add_parser("vae", help="VAE round trip: MAE, PSNR, CD (ldm/convert_vae.py:193-271)")
@@ -66,7 +74,17 @@ def build_parser():
     c.add_argument("b_dir")
     c.add_argument("--columns", type=int, default=4, help="float32 columns per point in the .bin files")
 
-    for p in (v, *[sub.choices[k] for k in ("densification", "inpainting")], c):
+    g = sub.add_parser("generation", help="MMD-CD / COV-CD / 1-NNA-CD (+ BEV jsd / mmd) of generated against reference clouds")
+    g.add_argument("gen_dir")
+    g.add_argument("ref_dir")
+    g.add_argument("--points", type=int, default=2048, help="points kept per cloud (deterministic sub-sample)")
+    g.add_argument("--limit", type=int, default=None, help="use the first N files (sorted by name) of each folder")
+    g.add_argument("--seed", type=int, default=0, help="sub-sampling seed (file i uses seed + i)")
+    g.add_argument("--max-depth", type=float, default=None, help="drop points at this distance from the sensor or farther")
+    g.add_argument("--columns", type=int, default=4, choices=(4, 5),
+                   help="float32 columns per point of the REFERENCE files (5: nuScenes sweeps); generated files have 4")
+
+    for p in (v, *[sub.choices[k] for k in ("densification", "inpainting")], c, g):
         p.add_argument("--json", default=None, help="also write the result object to this file")
     return ap
 
@@ -311,7 +329,64 @@ def cmd_chamfer(a, rank, world, dev):
     return {"task": "chamfer", "pairs": len(pairs), "cd": cd / len(pairs)}
 
 
-COMMANDS = {"vae": cmd_vae, "densification": cmd_densification, "inpainting": cmd_inpainting, "chamfer": cmd_chamfer}
+def _sum_matrix_over_ranks(m):
+    """Element-wise sum of a device fp64 matrix over the ranks (identity on one process; gloo reduces host tensors)."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        return m
+    if dist.get_backend() == "gloo":
+        host = m.cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.SUM)
+        return host.to(m.device)
+    dist.all_reduce(m, op=dist.ReduceOp.SUM)
+    return m
+
+
+def _matrix_over_ranks(xs, ys, rank, world):
+    """chamfer_matrix(xs, ys) (ys None: xs against itself) with the rows shared out over the ranks: every rank writes its
+    block of rows into a zero matrix and the sum over the ranks (adding zeros is exact) is the whole."""
+    from .metrics import chamfer_matrix
+    if world == 1:
+        return chamfer_matrix(xs, ys)
+    cols = xs if ys is None else ys
+    full = torch.zeros((len(xs), len(cols)), dtype=torch.float64, device=xs[0].device)
+    lo, hi = D.shard_range(len(xs), rank, world)
+    if hi > lo:
+        full[lo:hi] = chamfer_matrix(xs[lo:hi], cols)    # (a cloud against itself: every d^2 minimum is exactly 0)
+    return _sum_matrix_over_ranks(full)
+
+
+def load_generation_clouds(files, columns, points, seed, max_depth, device):
+    """xyz of every file: the points closer than max_depth (None: all), then subsample(.., points, seed + file index)."""
+    from .metrics import subsample
+    clouds = []
+    for i, path in enumerate(files):
+        xyz = _load_bin(path, columns, device)[:, :3]
+        if max_depth is not None:
+            xyz = xyz[xyz.norm(dim=1) < max_depth]
+        if xyz.shape[0] == 0:
+            raise ValueError(f"{path}: no point left (max_depth={max_depth})")
+        clouds.append(subsample(xyz, points, seed + i))
+    return clouds
+
+
+def cmd_generation(a, rank, world, dev):
+    from .metrics import evaluate_folders, set_metrics
+    gen_files = sorted(glob.glob(os.path.join(a.gen_dir, "*.bin")))[:a.limit]
+    ref_files = sorted(glob.glob(os.path.join(a.ref_dir, "*.bin")))[:a.limit]
+    if not gen_files or not ref_files:
+        raise FileNotFoundError(f"no .bin files in {a.gen_dir if not gen_files else a.ref_dir}")
+    gen = load_generation_clouds(gen_files, 4, a.points, a.seed, a.max_depth, dev)
+    ref = load_generation_clouds(ref_files, a.columns, a.points, a.seed, a.max_depth, dev)
+    result = {"task": "generation", "points": a.points}
+    result.update(set_metrics(_matrix_over_ranks(gen, None, rank, world), _matrix_over_ranks(gen, ref, rank, world),
+                              _matrix_over_ranks(ref, None, rank, world)))
+    if rank == 0:                                        # the BEV histograms of the full clouds: cheap, one rank
+        result.update(evaluate_folders(a.gen_dir, ref_files, nuscenes=a.columns == 5, limit=a.limit))
+    return result
+
+
+COMMANDS = {"generation": cmd_generation, "vae": cmd_vae, "densification": cmd_densification, "inpainting": cmd_inpainting, "chamfer": cmd_chamfer}
 
 
 def main(argv=None):

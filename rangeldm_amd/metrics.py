@@ -8,6 +8,10 @@ device tensors in, librangeldm_hip.so (rangeldm_amd/csrc/metrics.hip) underneath
 
 Reconstruction metrics (rangeldm_amd/csrc/chamfer.hip): chamfer_distance (pytorch3d call shape), nearest_sq_dists,
 range_errors (MAE / PSNR / range MAE sums) and beam_upsample (the nearest / bicubic baselines).
+
+Set-level generation metrics (same file): chamfer_matrix (every cloud of one set against every cloud of another),
+row_argmin (lowest index wins a tie) and generation_metrics (MMD-CD, COV-CD, 1-NNA-CD of Achlioptas et al. 2018 /
+Yang et al. 2019); set_metrics_host is the numpy statement of the three reductions.
 """
 import ctypes as C
 
@@ -191,6 +195,111 @@ def chamfer_distance(x, y, x_lengths=None, y_lengths=None, point_reduction="mean
     if batch_reduction is None:
         return per_pair, None
     return (per_pair.sum() if batch_reduction == "sum" else per_pair.mean()), None
+
+
+# ---- set-level generation metrics: all-pairs Chamfer matrix, MMD-CD / COV-CD / 1-NNA-CD -------------------------------
+def chamfer_matrix(x, y=None, x_lengths=None, y_lengths=None, return_directions=False):
+    """CD[i][j] = mean_{q in x_i} min_{t in y_j} d^2 + mean_{t in y_j} min_{q in x_i} d^2 for EVERY cloud of x against every
+    cloud of y: an fp64 device (nx, ny) tensor.  y=None is the symmetric case (x against itself: zero diagonal, CD equal to
+    its transpose bit for bit).  Inputs as chamfer_distance takes them.  return_directions=True returns (xy, yx), the two
+    terms.  Every entry is a fixed-order fp64 mean of fp32 minima that are bit-equal to the CPU expression, and depends on its
+    two clouds alone: a block of rows computed on its own (x[a:b] against y) equals those rows of the whole matrix."""
+    xs = _clouds(x, x_lengths, "x")
+    ys = None if y is None else _clouds(y, y_lengths, "y")
+    if y is None and y_lengths is not None:
+        raise ValueError("y_lengths without y")
+    _lib.require_gpu()
+    xp, xo, xk = _pack(xs)
+    yp, yo, yk = (xp, xo, xk) if ys is None else _pack(ys)
+    nx, ny = len(xs), len(xs if ys is None else ys)
+    xy = torch.empty((nx, ny), dtype=torch.float64, device=xp.device)
+    yx = torch.empty_like(xy)
+    _lib.check(_lib.lib().rldm_chamfer_matrix(xp.data_ptr(), xo.data_ptr(), xk, nx, yp.data_ptr(), yo.data_ptr(), yk, ny,
+                                              1 if ys is None else 0, xy.data_ptr(), yx.data_ptr(), _lib.stream_ptr(xp.device)),
+               "rldm_chamfer_matrix")
+    return (xy, yx) if return_directions else xy + yx
+
+
+def row_argmin(m, exclude_diag=False):
+    """Per row of a device fp64 (n, m) matrix: (minimum, LOWEST column index attaining it) as fp64 / int32 device tensors.
+    exclude_diag skips column r of row r (a cloud is not its own neighbour).  torch.argmin does not promise which index wins
+    a tie; the set metrics are counts of argmins, so the rule is stated and kept here."""
+    if m.dim() != 2 or m.shape[0] == 0 or m.shape[1] == 0:
+        raise ValueError(f"m must be a non-empty (n, m) matrix, got {tuple(m.shape)}")
+    if not m.is_cuda:
+        raise RuntimeError("the matrix must live on the GPU (rangeldm_amd has no CPU path)")
+    m = m.detach().to(torch.float64).contiguous()
+    mn = torch.empty(m.shape[0], dtype=torch.float64, device=m.device)
+    arg = torch.empty(m.shape[0], dtype=torch.int32, device=m.device)
+    _lib.check(_lib.lib().rldm_matrix_row_argmin(m.data_ptr(), m.shape[0], m.shape[1], 1 if exclude_diag else 0,
+                                                 mn.data_ptr(), arg.data_ptr(), _lib.stream_ptr(m.device)),
+               "rldm_matrix_row_argmin")
+    return mn, arg
+
+
+def _mean_exact(values):
+    """Correctly rounded mean of a 1-D device tensor (math.fsum on the host: no dependence on a reduction order)."""
+    import math
+    v = values.cpu().tolist()
+    return math.fsum(v) / len(v)
+
+
+def set_metrics(cd_gg, cd_gr, cd_rr):
+    """MMD-CD, COV-CD and 1-NNA-CD from the three device fp64 Chamfer matrices: generated x generated (ng, ng), generated x
+    reference (ng, nr), reference x reference (nr, nr).  Ties go to the lowest index (row_argmin).
+      mmd_cd   mean over reference clouds r of min_g CD[g][r]
+      cov_cd   distinct reference clouds that are argmin_r CD[g][r] for some generated g, over nr
+      nna_cd   leave-one-out 1-nearest-neighbour accuracy over the union ordered [G_0 .. G_{ng-1}, R_0 .. R_{nr-1}]: the
+               fraction of clouds whose nearest OTHER cloud carries their own label (0.5 is ideal; nna_cd_gen / nna_cd_ref: the
+               same over the generated / the reference clouds alone)."""
+    ng, nr = cd_gr.shape
+    if tuple(cd_gg.shape) != (ng, ng) or tuple(cd_rr.shape) != (nr, nr):
+        raise ValueError(f"matrices of shapes {tuple(cd_gg.shape)}, {tuple(cd_gr.shape)}, {tuple(cd_rr.shape)} do not fit")
+    mins, _ = row_argmin(cd_gr.t())
+    _, covered = row_argmin(cd_gr)
+    union = torch.cat([torch.cat([cd_gg, cd_gr], 1), torch.cat([cd_gr.t(), cd_rr], 1)], 0)
+    _, nn = row_argmin(union, exclude_diag=True)
+    same = (nn >= ng) == (torch.arange(ng + nr, device=nn.device) >= ng)
+    right_gen, right_ref = int(same[:ng].sum()), int(same[ng:].sum())
+    return {"mmd_cd": _mean_exact(mins), "cov_cd": int(torch.unique(covered).numel()) / nr,
+            "nna_cd": (right_gen + right_ref) / (ng + nr), "nna_cd_gen": right_gen / ng, "nna_cd_ref": right_ref / nr,
+            "n_gen": ng, "n_ref": nr}
+
+
+def set_metrics_host(cd_gg, cd_gr, cd_rr):
+    """The numpy statement of set_metrics (np.argmin returns the first minimum: the same lowest-index rule)."""
+    import math
+    import numpy as np
+    gg, gr, rr = (np.asarray(m, dtype=np.float64) for m in (cd_gg, cd_gr, cd_rr))
+    ng, nr = gr.shape
+    union = np.block([[gg, gr], [gr.T, rr]])
+    np.fill_diagonal(union, np.inf)
+    nn = union.argmin(1)
+    same = (nn >= ng) == (np.arange(ng + nr) >= ng)
+    return {"mmd_cd": math.fsum(gr.min(0).tolist()) / nr, "cov_cd": len(set(gr.argmin(1).tolist())) / nr,
+            "nna_cd": int(same.sum()) / (ng + nr), "nna_cd_gen": int(same[:ng].sum()) / ng,
+            "nna_cd_ref": int(same[ng:].sum()) / nr, "n_gen": ng, "n_ref": nr}
+
+
+def generation_metrics(gen, ref):
+    """MMD-CD / COV-CD / 1-NNA-CD (set_metrics) of a generated set against a reference set: lists of (n_i, >= 3) device
+    tensors or padded (N, P, >= 3) tensors.  Three Chamfer matrices: gen x gen and ref x ref (symmetric), gen x ref."""
+    gs, rs = _clouds(gen, None, "gen"), _clouds(ref, None, "ref")
+    return set_metrics(chamfer_matrix(gs), chamfer_matrix(gs, rs), chamfer_matrix(rs))
+
+
+def subsample(cloud, n, seed):
+    """`n` points of a (P, k) cloud chosen without replacement, in their original order; all of them if P <= n.  The choice
+    is a function of (P, n, seed) alone (numpy's PCG64 on the host), so two runs and two rank counts pick the same points."""
+    import numpy as np
+    P = int(cloud.shape[0])
+    n = int(n)
+    if n <= 0:
+        raise ValueError(f"n must be positive, got {n}")
+    if P <= n:
+        return cloud
+    idx = np.sort(np.random.Generator(np.random.PCG64(int(seed))).choice(P, size=n, replace=False))
+    return cloud[torch.from_numpy(idx).to(cloud.device)]
 
 
 def range_errors(a, b, scale, shift=None, channels=None, window=None):

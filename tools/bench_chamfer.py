@@ -3,7 +3,11 @@
 KITTI-360-size clouds, ldm/convert_vae.py:262-271) and one 65 536 x 65 536 pair, price it against the fp32 VALU issue
 rate, and time a same-process host baseline (scipy cKDTree, 16 workers).
 
-    python tools/bench_chamfer.py [--pairs 1000] [--points 60000] [--host-pairs 8]
+    python tools/bench_chamfer.py [--pairs 1000] [--points 60000] [--host-pairs 8] [--matrix NX NY POINTS]
+
+--matrix NX NY POINTS adds the all-pairs matrix (rldm_chamfer_matrix, both directions) between NX and NY clouds of POINTS
+points, and the same cloud size through the pair entry point on a --matrix-block x --matrix-block sub-block with every cloud
+replicated once per partner (what the matrix would cost without the kernel's reuse); five repetitions each, spread reported.
 
 Instruction count per evaluation, read from the ISA of chamfer_nn_kernel's inner loop (hipcc --save-temps, gfx950): one
 iteration handles 4 targets x 8 queries = 32 evaluations with 80 v_pk_add_f32 + 48 v_pk_mul_f32 + 16 v_min3_f32 +
@@ -61,6 +65,53 @@ def time_nn(xs, ys, reps):
     return float(np.median(ts)), float((xm + ym).mean())
 
 
+def time_matrix(xs, ys, reps):
+    """Seconds per call of rldm_chamfer_matrix on pre-packed sets (every one of `reps`, after one warm-up call)."""
+    from rangeldm_amd import _lib
+    from rangeldm_amd.metrics import _pack
+    xp, xo, xk = _pack(xs)
+    yp, yo, yk = _pack(ys)
+    xy = torch.empty((len(xs), len(ys)), dtype=torch.float64, device=xp.device)
+    yx = torch.empty_like(xy)
+    L, st = _lib.lib(), _lib.stream_ptr(xp.device)
+
+    def run():
+        _lib.check(L.rldm_chamfer_matrix(xp.data_ptr(), xo.data_ptr(), xk, len(xs), yp.data_ptr(), yo.data_ptr(), yk, len(ys), 0,
+                                         xy.data_ptr(), yx.data_ptr(), st), "rldm_chamfer_matrix")
+        torch.cuda.synchronize()
+    run()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        run()
+        ts.append(time.perf_counter() - t0)
+    return ts, xy + yx
+
+
+def spread(ts, evals):
+    med = float(np.median(ts))
+    return {"seconds": med, "seconds_min": min(ts), "seconds_max": max(ts), "reps": len(ts), "evals_per_s": evals / med,
+            "evals_per_s_spread": [evals / max(ts), evals / min(ts)],
+            "valu_issue_fraction": evals / med * VALU_PER_EVAL / LANE_ISSUE_PER_S}
+
+
+def matrix_report(g, nx, ny, points, block, dev):
+    xs = [kitti_like(g, points, dev) for _ in range(nx)]
+    ys = [kitti_like(g, points, dev) for _ in range(ny)]
+    ts, cd = time_matrix(xs, ys, 5)
+    out = {"matrix": {"case": f"{nx} x {ny} clouds of {points} pts, both directions", **spread(ts, 2.0 * nx * ny * points * points),
+                      "cd_mean": float(cd.mean())}}
+    # the same clouds through the pair entry point: a block x block corner of the matrix, every cloud once per partner
+    bx, by = min(block, nx), min(block, ny)
+    px = [xs[i] for i in range(bx) for _ in range(by)]
+    py = [ys[j] for _ in range(bx) for j in range(by)]
+    ts = [time_nn(px, py, 1)[0] for _ in range(5)]
+    out["pair_path_block"] = {"case": f"{bx} x {by} corner as {bx * by} pairs of {points} pts",
+                              **spread(ts, 2.0 * bx * by * points * points)}
+    out["pair_path_block"]["seconds_for_whole_matrix"] = out["pair_path_block"]["seconds"] * (nx * ny) / (bx * by)
+    return out
+
+
 def host_seconds_per_pair(xs, ys):
     from scipy.spatial import cKDTree
     t0 = time.perf_counter()
@@ -85,6 +136,9 @@ def main():
     ap.add_argument("--points", type=int, default=60000)
     ap.add_argument("--host-pairs", type=int, default=8, help="pairs the cKDTree baseline times (per-pair cost is reported)")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--matrix", type=int, nargs=3, metavar=("NX", "NY", "POINTS"), default=None,
+                    help="also time the all-pairs matrix between NX and NY clouds of POINTS points")
+    ap.add_argument("--matrix-block", type=int, default=64, help="side of the sub-block timed through the pair entry point")
     a = ap.parse_args()
     dev = torch.device("cuda")
     g = torch.Generator(device=dev).manual_seed(1)
@@ -99,6 +153,8 @@ def main():
     host = host_seconds_per_pair(xs[:a.host_pairs], ys[:a.host_pairs])
     out["host_ckdtree_16w_ms_per_pair"] = 1e3 * host
     out["speedup_vs_host"] = host / (out["runs"][0]["seconds"] / a.pairs)
+    if a.matrix:
+        out.update(matrix_report(g, *a.matrix, a.matrix_block, dev))
     print(json.dumps(out, indent=1))
 
 
