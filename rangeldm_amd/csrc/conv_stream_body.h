@@ -42,8 +42,9 @@ __device__ __forceinline__ void conv_stream_body(const ConvParams& p, const int 
     constexpr int TAPW = SUB ? 2 : 3;          // taps per row / rows of taps
     const int nt = SUB ? nt_ >> 2 : nt_;
     const int par_w = SUB ? (nt_ >> 1) & 1 : 0, par_h = SUB ? nt_ & 1 : 0;
-    constexpr int NT = 64 * NW, CK = 64, KG = NW / (WM * WN);
-    constexpr int BM = 32 * MI * WM, BN = 32 * WN;
+    constexpr StreamInstDesc D = {WM, WN, NW, MI};       // (the host reads the same figures from the same functions: kStreamInst)
+    constexpr int NT = D.threads(), CK = 64, KG = D.kgroups();
+    constexpr int BM = D.bm(), BN = D.bn();
     constexpr int RS = CK * 2 + 16;            // halo row stride (bytes): 9 16-byte slots
     constexpr int C8 = CK / 8;
     // 16-byte halo pieces per thread and chunk: 34 x 10 pixels (6); the 128-pixel instance 18 x 10 = 16 x 8 tiles, or 34 x 6 = 32 x 4

@@ -134,8 +134,7 @@ struct ConvParams {
     int* step_inc;          // conv_igemm.hip: the sampler's device step index, advanced by the step's FIRST launch (conv_in, which does not read it) or null
     int nviews;             // conv_small.hip, image-owning tiles: normalised copies of the output for up to 3 consumers
     NormView nv[3];
-    int st_inst;            // conv_stream.hip: 0 the 8-wave instance the tile implies; round 4's 4-wave workgroups on 16 x 8 tiles, two
-                            // resident per CU: 1 = 128 pixels x 128 channels, 2 = 128 pixels x 64 channels x 2 k-groups
+    int st_inst;            // conv_stream.hip: which kernel runs (StreamInst below; host side only, no kernel reads it)
     int exp;                // ... round-4 experiment switches (rldm_debug_set_flags2 >> 8; conv_stream_body.h)
     int* cu_lock;           // ... [4096] zero-initialised per-CU locks (exp & 2)
 };
@@ -163,18 +162,70 @@ size_t conv_small_lds_bytes(const ConvParams& p, int taps, int BN);
 bool conv_small_supported(const ConvParams& p, int taps, int BN);
 int launch_conv_small(const ConvParams& p, int taps, int BN, hipStream_t stream);
 
-// Weight-streaming 3x3 / stride 1 variant (conv_stream.hip): 256 pixels (32 x 8) x 128 channels per workgroup for the
-// full-resolution levels, 128 pixels (16 x 8) x 64 channels with 4 k-groups for the 128x8 level; 64-channel chunks.  Same
-// ConvParams (colb = conv_halo_col_bytes of a CK = 64 tile); wpk is the fragment-ordered image
-// [N/32][KG][(Cin/64 * 9 + R/64) * 4/KG k-steps][64 lanes][8 bf16] (ConvLayer::get_streampacked).
-int conv_stream_bn(const ConvParams& p);          // 128 (TW = 32) | 64 (TW = 16: the 4-k-group instance)
+// Weight-streaming 3x3 variant (conv_stream.hip), 64-channel chunks.  Same ConvParams (colb = conv_halo_col_bytes of a CK = 64 tile); wpk
+// is the fragment-ordered image [N/32][KG][(Cin/64 * 9 + R/64) * 4/KG k-steps][64 lanes][8 bf16] (ConvLayer::get_streampacked), or the
+// sub-pixel instances' summed taps (ConvLayer::get_subpixpacked).
+// One row of kStreamInst per compiled kernel, chosen by ConvParams::st_inst.  A row is the kernel's template arguments (conv_stream_body.h
+// explains them) plus the preconditions that are the instance's own: the pixel tiles it takes, "no nearest x2 folded into the staging",
+// "no residual phase".  Everything else -- threads, tile, k-groups, workgroups per CU, the LDS cap -- follows from the template arguments
+// through the functions of the row, which are the ones conv_stream_body computes its constants with.
+enum StreamInst : int {
+    SI_256x128,             // pixels x channels of a workgroup's tile.  8 waves, one workgroup per CU:
+    SI_256x64,              //   layers of 64 (192, ...) output channels: 2 k-groups (the VAE decoder's full-resolution level)
+    SI_128x64,              //   the 128x8 level, too few 256-pixel tiles to fill the chip: 4 k-groups; 32 x 4 tiles for images of 4 beams
+    SI_256x128_SPEC,        //   conv_stream_spec_kernel: 4 matrix waves + 4 staging waves (Flag2.STREAM_SPEC_WAVES)
+    SI_64x128,              //   the 128x8 level: 8 x 8 tiles, two 32-pixel fragments per wave, 2 k-groups
+    SI_64x128_S2,           //   ... at stride 2 (Downsample2D); 16 x 4 tiles for outputs of 4 beams
+    SI_128x128_W4,          // 4 waves, two workgroups per CU:
+    SI_128x64_W4,           //   2 k-groups
+    SI_SUB_W4,              //   nearest x2 + 3x3 in its sub-pixel form: the tiles are INPUT tiles, four parity workgroups each
+    SI_SUB_T4_W4,           //   ... on 32 x 4 tiles (inputs of 4 beams)
+    SI_FULLH_W4,            //   tiles as tall as the image (8 x 16 | 16 x 8): the halo rows above / below are never staged
+    SI_COUNT
+};
+// what a conv_stream phase of the persistent launch runs (trunk.hip, TW_SUB of its record); TSF_NONE: the instance is launched only
+enum TrunkStreamForm : int { TSF_NONE = -1, TSF_PLAIN = 0, TSF_SUB = 1, TSF_FULLH = 2 };
+struct StreamTile {
+    int TW, TH;
+};
+struct StreamInstDesc {
+    int WM, WN, NW = 8, MI = 4, STR = 1;
+    bool SUB = false, T4 = false, FH = false;
+    bool spec = false;                          // conv_stream_spec_kernel instead of conv_stream_kernel<...>
+    StreamTile tiles[2] = {};                   // pixel tiles (TW = 0: no second one)
+    bool up1 = false, no_res = false;           // ConvParams::up == 1 only / R0 + R1 == 0 only
+    int trunk = TSF_NONE;
+    constexpr int threads() const { return 64 * NW; }
+    constexpr int kgroups() const { return NW / (WM * WN); }
+    constexpr int bm() const { return 32 * MI * WM; }
+    constexpr int bn() const { return 32 * WN; }
+    constexpr int wg_per_cu() const { return NW == 4 ? 2 : 1; }
+    constexpr int lds_cap() const { return 160 * 1024 / wg_per_cu(); }      // (co-resident workgroups share the CU's LDS)
+    constexpr bool takes(int TW, int TH) const { return (tiles[0].TW == TW && tiles[0].TH == TH) || (tiles[1].TW == TW && tiles[1].TH == TH); }
+};
+constexpr StreamInstDesc kStreamInst[SI_COUNT] = {
+    //                     WM WN NW MI STR  SUB    T4     FH     spec    tiles               up1    no_res trunk
+    /* SI_256x128      */ {2, 4, 8, 4, 1, false, false, false, false, {{32, 8}},          false, false, TSF_PLAIN},
+    /* SI_256x64       */ {2, 2, 8, 4, 1, false, false, false, false, {{32, 8}}},
+    /* SI_128x64       */ {1, 2, 8, 4, 1, false, false, false, false, {{16, 8}, {32, 4}}},
+    /* SI_256x128_SPEC */ {2, 4, 8, 4, 1, false, false, false, true,  {{32, 8}}},
+    /* SI_64x128       */ {1, 4, 8, 2, 1, false, false, false, false, {{8, 8}}},
+    /* SI_64x128_S2    */ {1, 4, 8, 2, 2, false, false, false, false, {{8, 8}, {16, 4}},  true,  true},
+    /* SI_128x128_W4   */ {1, 4, 4, 4, 1, false, false, false, false, {{16, 8}},          false, false, TSF_PLAIN},
+    /* SI_128x64_W4    */ {1, 2, 4, 4, 1, false, false, false, false, {{16, 8}}},
+    /* SI_SUB_W4       */ {1, 4, 4, 4, 1, true,  false, false, false, {{16, 8}},          true,  true,  TSF_SUB},
+    /* SI_SUB_T4_W4    */ {1, 4, 4, 4, 1, true,  true,  false, false, {{32, 4}},          true,  true},
+    /* SI_FULLH_W4     */ {1, 4, 4, 4, 1, false, false, true,  false, {{8, 16}, {16, 8}}, true,  false, TSF_FULLH},
+};
+inline const StreamInstDesc& stream_inst(const ConvParams& p) { return kStreamInst[p.st_inst]; }     // (st_inst: a StreamInst)
+int conv_stream_bn(const ConvParams& p);
 int conv_stream_kgroups(const ConvParams& p);
 size_t conv_stream_lds_bytes(const ConvParams& p);
 bool conv_stream_supported(const ConvParams& p, int taps);
 int launch_conv_stream(const ConvParams& p, hipStream_t stream);
 
 // conv_regw.hip (round 4): 64 -> 64 channel 3x3 / stride 1 convs over 16 x 8 tiles with the weights resident in registers and a persistent
-// tile loop per workgroup (the VAE decoder's full-resolution level).  `p` as for conv_stream (st_inst 2's tile); the output statistics are
+// tile loop per workgroup (the VAE decoder's full-resolution level).  `p` as for conv_stream (16 x 8 tiles); the output statistics are
 // ONE partial per workgroup: y_stats is [B][conv_regw_wg_per_image(p)][N].
 size_t conv_regw_lds_bytes();
 int conv_regw_wg_per_image(const ConvParams& p);

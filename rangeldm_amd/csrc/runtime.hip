@@ -1301,12 +1301,17 @@ struct Builder {
     // conv_stream.hip route: 3x3 / stride 1 convs whose output has at least 128 tiles of 32 x 8 pixels x 128 channels, or
     // (the 128x8 level) of 16 x 8 pixels x 64 channels
     static constexpr int kSubMinBlocks = 96;
-    static bool stream_params_tw(const ConvArgs& a, int Cin_t, int R_t, int taps, int Wout, int Hout, int TW, long long min_blocks,
-                                 long long max_blocks, ConvParams* q, int TH = 8, int inst = 0) {
+    static constexpr long long kAnyGrid = 1ll << 40;
+    // instance `inst` (kernels.h: kStreamInst) on pixel tile `tile` (TW = 0: the instance's only one), for a grid of [min_blocks, max_blocks] workgroups
+    static bool stream_params_tw(const ConvArgs& a, int Cin_t, int R_t, int taps, int Wout, int Hout, StreamInst inst, long long min_blocks,
+                                 long long max_blocks, ConvParams* q, StreamTile tile = {}) {
+        const StreamInstDesc& d = kStreamInst[inst];
+        if (tile.TW == 0) tile = d.tiles[0];
+        const int TW = tile.TW, TH = tile.TH;
         if (dbg() & RLDM_FLAG_NO_STREAM_REGW) return false;
-        if (taps != 9 || (a.stride != 1 && !(a.stride == 2 && inst == 5)) || a.pad_mode != 0 || a.out_f32_nchw || g_force_bm) return false;
-        // (inst 6, round 4: nearest x2 + 3x3 in its sub-pixel form -- the tiles are INPUT tiles, four parity workgroups each)
-        const bool sub = inst == 6;
+        if (taps != 9 || a.stride != d.STR || a.pad_mode != 0 || a.out_f32_nchw || g_force_bm) return false;
+        // (round 4: nearest x2 + 3x3 in its sub-pixel form -- the tiles are INPUT tiles, four parity workgroups each)
+        const bool sub = d.SUB;
         if (sub) {
             if (a.up != 2 || R_t != 0 || Wout != 2 * a.x0.W || Hout != 2 * a.x0.H) return false;
             Wout = a.x0.W; Hout = a.x0.H;
@@ -1328,7 +1333,7 @@ struct Builder {
         q->tiles_h = Hout / TH;
         q->tiles_img = (Wout / TW) * q->tiles_h;
         {
-            const int thv = inst == 7 ? TH : (TH - 1) * a.stride + 3;       // (7: only the tile's own rows are staged)
+            const int thv = d.FH ? TH : (TH - 1) * a.stride + 3;        // (full-height tiles: only the tile's own rows are staged)
             q->magic_thv = ((1 << 20) + thv - 1) / thv;
         }
         const int cpg = std::max(1, Cin_t / a.groups);
@@ -1340,57 +1345,62 @@ struct Builder {
         q->gn_groups = a.groups;
         q->ksplit = 1;
         if (a.gn) q->st0 = reinterpret_cast<const float2*>(q);      // (only its presence matters to the shape check)
-        const long long blocks = (long long)q->B * q->tiles_img * (q->N / conv_stream_bn(*q)) * (sub ? 4 : 1);
+        const long long blocks = (long long)q->B * q->tiles_img * (q->N / d.bn()) * (sub ? 4 : 1);
         const bool ok = conv_stream_supported(*q, 9) && ((dbg() & RLDM_FLAG_STREAM_ANY_GRID) || (blocks >= min_blocks && blocks <= max_blocks));
         q->st0 = nullptr;
         return ok;
     }
     static bool stream_params(const ConvArgs& a, int Cin_t, int R_t, int taps, int Wout, int Hout, ConvParams* q) {
+        // the first rule that fits, in this order
+        const auto fits = [&](StreamInst inst, long long min_blocks, long long max_blocks, StreamTile tile = {}) {
+            return stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, inst, min_blocks, max_blocks, q, tile);
+        };
         // 256-pixel tiles when they fill the chip; else the 4-k-group instance (it re-streams the weights per 128 pixels:
         // only where its grid is about one or two rounds); else 256-pixel tiles on at least half the chip
         // (round 4) half-size workgroups, two per CU: 16 x 8 tiles x 128 channels on 4 waves where that grid is at least ~1.5 per CU
         // (UNet 256x16 level at batch >= 12, the VAE decoder's 128 / 256-channel levels), x 64 channels x 2 k-groups for the 128x8
         // level and the VAE's 64-channel level
         const int N_ = a.layer->Cout;
+        const bool n128 = N_ % 128 == 0;
         // (round 4) stride 2 (Downsample2D, pad 1) on the 64-pixel x 128-channel tile with a 17 x 17 halo: the 256x16 -> 128x8 down-sampler ran on
         // the generic kernel's half-empty 256-pixel tile
         if (a.stride == 2) {
-            if (N_ % 128 != 0 || R_t != 0 || a.up != 1) return false;
-            if (stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 8, kInst4MinBlocks, 512, q, 8, 5)) return true;
+            if (!n128 || R_t != 0 || a.up != 1) return false;
+            if (fits(SI_64x128_S2, kInst4MinBlocks, 512, {8, 8})) return true;
             // outputs of 4 beams (the 128x8 -> 64x4 down-sampler): 16 x 4 tiles, from 48 workgroups on
-            return Hout == 4 && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 16, 48, 512, q, 4, 5);
+            return Hout == 4 && fits(SI_64x128_S2, 48, 512, {16, 4});
         }
         const int f2 = dbg2();
+        // the 256-pixel tile's 8-wave instance: 128 channels, or 64 x 2 k-groups for layers of 64 (192, ...) output channels (round 3: the
+        // VAE decoder's full-resolution level, which ran on the generic kernel at 278 us per conv)
+        const StreamInst px256 = n128 ? SI_256x128 : SI_256x64;
         // (experiment, RLDM_FLAG2_STREAM_SPEC_WAVES) the 256 x 128 tile with specialised waves wherever the 8-wave 256 x 128 instance would run
-        if ((f2 & RLDM_FLAG2_STREAM_SPEC_WAVES) && N_ % 128 == 0 && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 32, 200, 1ll << 40, q, 8, 3))
-            return true;
+        if ((f2 & RLDM_FLAG2_STREAM_SPEC_WAVES) && n128 && fits(SI_256x128_SPEC, 200, kAnyGrid)) return true;
         // (tests, RLDM_FLAG2_STREAM_64PX) the 64-pixel x 128-channel tile first, at any level it fits
-        if ((f2 & RLDM_FLAG2_STREAM_64PX) && N_ % 128 == 0 && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 8, 192, 512, q, 8, 4)) return true;
+        if ((f2 & RLDM_FLAG2_STREAM_64PX) && n128 && fits(SI_64x128, 192, 512)) return true;
         // (round 4) nearest x2 + 3x3 as four 2x2 convs over the input (sub-pixel form: 4 taps instead of 9 per output pixel) on the 4-wave
-        // 128 x 128 tile
-        if (!(f2 & RLDM_FLAG2_STREAM_8WAVE_FULL) && a.up == 2 && N_ % 128 == 0 &&
-            (stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 16, kSubMinBlocks, 1ll << 40, q, 8, 6) ||
-             (a.x0.H % 8 != 0 && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 32, kSubMinBlocks, 1ll << 40, q, 4, 6)))) return true;   // (inputs of 4 beams: 32 x 4 tiles)
-        // (round 4) images of 16 beams: 8 x 16 tiles as tall as the image -- five staged pieces per thread instead of six;
+        // 128 x 128 tile; inputs of 4 beams: 32 x 4 tiles
+        if (!(f2 & RLDM_FLAG2_STREAM_8WAVE_FULL) && a.up == 2 && n128 &&
+            (fits(SI_SUB_W4, kSubMinBlocks, kAnyGrid) || (a.x0.H % 8 != 0 && fits(SI_SUB_T4_W4, kSubMinBlocks, kAnyGrid)))) return true;
+        // (round 4) images of 16 beams: 8 x 16 tiles as tall as the image -- five staged pieces per thread instead of six (8 beams: 16 x 8);
         // RLDM_FLAG2_HALO_RING: the 16 x 8 tiles
-        if (!(f2 & (RLDM_FLAG2_STREAM_8WAVE_FULL | RLDM_FLAG2_HALO_RING)) && N_ % 128 == 0 && (Hout == 16 || Hout == 8) && a.up == 1 &&
-            stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, Hout == 16 ? 8 : 16, 384, 1ll << 40, q, Hout, 7)) return true;       // (8 beams: 16 x 8)
-        if (!(f2 & RLDM_FLAG2_STREAM_8WAVE_FULL) && N_ % 128 == 0 && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 16, 384, 1ll << 40, q, 8, 1))
-            return true;
-        if (!(f2 & RLDM_FLAG2_STREAM_8WAVE_C64) && N_ % 128 != 0 && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 16, 384, 1ll << 40, q, 8, 2))
-            return true;
-        if (stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 32, 200, 1ll << 40, q)) return true;
+        if (!(f2 & (RLDM_FLAG2_STREAM_8WAVE_FULL | RLDM_FLAG2_HALO_RING)) && n128 && (Hout == 16 || Hout == 8) && a.up == 1 &&
+            fits(SI_FULLH_W4, 384, kAnyGrid, {Hout == 16 ? 8 : 16, Hout})) return true;
+        if (!(f2 & RLDM_FLAG2_STREAM_8WAVE_FULL) && n128 && fits(SI_128x128_W4, 384, kAnyGrid)) return true;
+        if (!(f2 & RLDM_FLAG2_STREAM_8WAVE_C64) && !n128 && fits(SI_128x64_W4, 384, kAnyGrid)) return true;
+        if (fits(px256, 200, kAnyGrid)) return true;
         // (round 4) the 128x8 level: 64-pixel x 128-channel x 2-k-group tiles (8 x 8: a smaller halo, normalised once for all 128 channels,
         // half the partial sums to exchange)
-        if (N_ % 128 == 0 && Hout == 8 &&       // (at the 256x16 level of small batches it breaks the clusters: -4 %; RangeDM at batch 1: +1 %, not worth a rule)
-            stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 8, kInst4MinBlocks, 320, q, 8, 4)) return true;      // (one round of 8-wave workgroups: at 512
-        // blocks -- the 256-channel up-sampler conv of the level -- two co-resident 4-wave workgroups per CU win, 23.6 against 27.1 us)
-        if (!(f2 & RLDM_FLAG2_STREAM_8WAVE_128X8) && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 16, 257, 512, q, 8, 2)) return true;
-        if (stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 16, 128, 512, q)) return true;
+        // (at the 256x16 level of small batches it breaks the clusters: -4 %; RangeDM at batch 1: +1 %, not worth a rule)
+        // (one round of 8-wave workgroups: at 512 blocks -- the 256-channel up-sampler conv of the level -- two co-resident 4-wave workgroups
+        // per CU win, 23.6 against 27.1 us)
+        if (n128 && Hout == 8 && fits(SI_64x128, kInst4MinBlocks, 320)) return true;
+        if (!(f2 & RLDM_FLAG2_STREAM_8WAVE_128X8) && fits(SI_128x64_W4, 257, 512)) return true;
+        if (fits(SI_128x64, 128, 512, {16, 8})) return true;
         // images of 4 beams (nuScenes' 128 x 4 level at batch 32): the same 128-pixel instance on 32 x 4 tiles (round 3; it ran on the
         // generic kernel at 27.8 us / 257 TFLOP/s per conv: 16 % of that configuration's step)
-        if (Hout % 8 != 0 && stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 32, 128, 512, q, 4)) return true;
-        return stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, 32, 128, 1ll << 40, q);
+        if (Hout % 8 != 0 && fits(SI_128x64, 128, 512, {32, 4})) return true;
+        return fits(px256, 128, kAnyGrid);
     }
 
     int conv_stream(const ConvArgs& a, int Cin_t, int R_t, int Wout, int Hout, Tensor* out) {
@@ -1405,8 +1415,9 @@ struct Builder {
         }
         p.dbg = kernel_dbg();
         p.ts = stamp_buf(StampSite::Conv, conv_ord - 1);
-        const bool sub = p.st_inst == 6;
-        p.ntile_n = N / conv_stream_bn(p) * (sub ? 4 : 1);      // (grid x: channel tiles x parities)
+        const StreamInstDesc& d = stream_inst(p);
+        const bool sub = d.SUB;
+        p.ntile_n = N / d.bn() * (sub ? 4 : 1);      // (grid x: channel tiles x parities)
         Tensor y = make(x0.B, Wout, Hout, N);
         if (a.want_stats) add_stats(y, p.tiles_img * (sub ? 4 : 1));
         const double fl_ref = 2.0 * (double)x0.B * Wout * Hout * N * ((double)L->Cin * 9 + (L->sc_identity ? 0.0 : (double)L->R));
@@ -1417,20 +1428,18 @@ struct Builder {
         // full-resolution levels) form a cluster on one XCD; consecutive convs of a level hand over through its L2 -- no end-of-kernel
         // write-back of the 16.8 MB outputs, no argument fetch / cold start per layer
         const int ranks_s = p.tiles_img * p.ntile_n;            // (sub-pixel form: input tiles x parities, one 128-channel tile)
-        // (round 4) the 4-wave 128 x 128 instance: 32 workgroups per image, two per CU -- trunk variant 4
-        const bool inst1 = p.st_inst == 1 || p.st_inst == 7;      // (the 4-wave 128 x 128 tile: 16 x 8, or 8 x 16 as tall as the image)
-        const int per_cu = inst1 || sub ? 2 : 1;
+        // (round 4) the 4-wave 128 x 128 instances: 32 workgroups per image, two per CU -- trunk variant 4; the 256 x 128 instance: variant 2
+        const int per_cu = d.wg_per_cu();
         // (the 128x8 level's conv pairs measured slower as 2-phase launches than as two launches, 216.9 against 220.0 img/s: they
         //  stay launches)
         const bool in_stream_cluster = cluster_enabled() && ranks_s >= 2 && ranks_s <= 16 * per_cu &&
                                        trunk_grid_fits(ranks_s, x0.B, per_cu) && y.P <= kFoldAboveP && N % 128 == 0 &&
-                                       ((p.st_inst == 0 && p.TW * p.TH == 256) ||
-                                        ((inst1 || (sub && N == 128 && p.TH == 8)) && conv_stream_lds_bytes(p) <= 80 * 1024));
-        if (in_stream_cluster) trunk_begin(x0.B, ranks_s, sub ? 1 : p.ntile_n, 4, inst1 || sub ? 4 : 2);
+                                       d.trunk != TSF_NONE && (!sub || N == 128) && conv_stream_lds_bytes(p) <= (size_t)d.lds_cap();
+        if (in_stream_cluster) trunk_begin(x0.B, ranks_s, sub ? 1 : p.ntile_n, 4, d.NW == 4 ? 4 : 2);
         else note_launch();
         if (!dry) {
             ConvLayer::Packed* pk = nullptr;
-            if (sub ? L->get_subpixpacked(Cin_t, &pk) : L->get_streampacked(Cin_t, conv_stream_kgroups(p), &pk)) return 1;
+            if (sub ? L->get_subpixpacked(Cin_t, &pk) : L->get_streampacked(Cin_t, d.kgroups(), &pk)) return 1;
             p.x0 = tptr(x0);
             p.x1 = tptr(a.x1);
             p.r0 = tptr(a.r0);
@@ -1467,7 +1476,7 @@ struct Builder {
                     p.temb_per_sample = pl->io.temb_per_sample;
                 }
                 return launch_conv_stream(p, s);
-            }, "conv_stream_kernel<" + std::to_string(p.TW * p.TH) + "," + std::to_string(conv_stream_bn(p)) + ",CK64,taps9" + (p.stride == 2 ? ",s2" : "") + (p.st_inst == 6 ? ",sub" : "") + ">", fl, by};
+            }, "conv_stream_kernel<" + std::to_string(p.TW * p.TH) + "," + std::to_string(d.bn()) + ",CK64,taps9" + (p.stride == 2 ? ",s2" : "") + (sub ? ",sub" : "") + ">", fl, by};
             if (in_stream_cluster) pend.standalone.push_back(standalone);
             else plan->ops.push_back(standalone);
         }

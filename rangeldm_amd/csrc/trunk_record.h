@@ -23,8 +23,8 @@ enum TrunkWord {
     // conv_stream phases (kind 15: the full-resolution levels as clusters of 16 or 32 pixel tiles)
     TW_X1 = 48, TW_ST1 = 50,                                    // 64-bit pointers
     TW_C0 = 52, TW_C1, TW_P1, TW_MAGIC_THV, TW_UP,
-    TW_SUB,                 // conv_stream phases of variant 4: 1 = the sub-pixel form of nearest x2 + 3x3 (rank = input tile * 4 + parity, 128 output channels),
-                            // 2 = tiles as tall as the image (st_inst 7)
+    TW_SUB,                 // conv_stream phases of variant 4, a TrunkStreamForm (kernels.h): TSF_SUB = the sub-pixel form of nearest x2 + 3x3 (rank =
+                            // input tile * 4 + parity, 128 output channels), TSF_FULLH = tiles as tall as the image
     TW_WBYTES = 58,         // bytes of the phase's packed weights (TW_WPK ...): what the PREVIOUS phase touches, one dword per 128-byte line,
                             // so that they wait in the XCD's L2 (round 5: trunk_warm_next; 0: nothing to warm)
     TW_WORDS = 64
@@ -73,7 +73,7 @@ inline TrunkPhase trunk_conv_phase(const ConvParams& p, int kind, bool consumer_
         put64(ph, TW_X1, p.x1); put64(ph, TW_ST1, p.st1);
         ph.w[TW_C0] = p.C0; ph.w[TW_C1] = p.C1; ph.w[TW_P1] = p.P1;
         ph.w[TW_MAGIC_THV] = p.magic_thv; ph.w[TW_UP] = p.up;
-        ph.w[TW_SUB] = p.st_inst == 6 ? 1 : (p.st_inst == 7 ? 2 : 0);       // (conv_stream's sub-pixel / full-height instances)
+        if (kind == TK_STREAM) ph.w[TW_SUB] = stream_inst(p).trunk;          // (conv_stream's sub-pixel / full-height instances)
     } else {
         for (int v = 0; v < 2 && v < p.nviews; ++v) {
             const int at = TW_NV0 + v * TW_NVSTRIDE;
