@@ -126,6 +126,22 @@ int rldm_sched_ddpm_step(const float coef[5], const float* eps, const float* x, 
 #define RLDM_PRED_SAMPLE 2
 int rldm_sched_step(int sampler_mode, int prediction_type, const float coef[5], const float* model_output, const float* x,
                     const float* noise, float* x_prev, int64_t n, void* stream);
+/* Guided (RePaint-style) step on an UNCONDITIONAL model: rldm_sched_step, then known-region replacement, then an optional
+ * re-noise, one launch, fp32:
+ *   u  = the step of rldm_sched_step(sampler_mode, prediction_type, coef[0..4], ...)      (the same expression, bit for bit)
+ *   g  = m * (ka * z0 + kb * nk) + (1 - m) * u        z0 = `known`, nk = `known_noise`, m = `mask` (1: known)
+ *   x' = ra * g + rb * nr                             nr = `renoise_noise`
+ * coef = {the 5 of rldm_sched_step, ka, kb, ra, rb}: (ka, kb) = (sqrt(alpha_prod_prev), sqrt(1 - alpha_prod_prev)) of the row (1, 0
+ * after the last timestep); (ra, rb) = (1, 0), or (sqrt(a_hi / a_lo), sqrt(1 - a_hi / a_lo)) on a row that jumps back up from
+ * alpha_prod a_lo to a_hi (the forward noising across the levels in closed form, one draw).
+ * model_output, x, noise, known, known_noise, renoise_noise, x_prev: device fp32 [B, C, spatial]; mask: device fp32 [B, 1, spatial],
+ * broadcast over C.  m == 1 / m == 0 select: a known pixel does not depend on u (nor on a non-finite model output), an unknown one not
+ * on z0.  ka * z0 + kb * nk is evaluated without contraction (bit-equal to the fp32 expression on a host).  known_noise is read only
+ * when kb != 0, renoise_noise only when (ra, rb) != (1, 0), noise only when coef[4] != 0: each may be NULL otherwise.  x_prev may
+ * alias x. */
+int rldm_sched_guided_step(int sampler_mode, int prediction_type, const float coef[9], const float* model_output, const float* x,
+                           const float* noise, const float* known, const float* mask, const float* known_noise,
+                           const float* renoise_noise, float* x_prev, int B, int C, int64_t spatial, void* stream);
 /* replaces DPMSolverMultistepScheduler.step (diffusers; algorithm_type "dpmsolver++", solver_type "midpoint", order 1 or 2,
  * final_sigmas_type "zero"): deterministic DPM-Solver++(2M).  Step i of N, sigma_i = sqrt((1-alpha_prod_t)/alpha_prod_t),
  * alpha_i = 1/sqrt(sigma_i^2+1), s_i = sigma_i*alpha_i, lambda_i = log alpha_i - log s_i (sigma_N = 0, lambda_N = +inf):
@@ -158,7 +174,13 @@ typedef struct rldm_sampler_config {
     int32_t mode;             /* RLDM_SAMPLER_*                                                               */
     int32_t pos_encoding;     /* extra constant channel: 1 at azimuth 0 (ldm/pipelines.py:229-232,346-349)     */
     int32_t cond_channels;    /* channels of the per-step concatenated condition (ldm/pipelines.py:498), or 0  */
-    /* per-step scheduler coefficients, HOST, [num_steps][5] in the layout of rldm_sched_{ddim,ddpm,dpmsolver}_step */
+    /* 1: a guided sampler (rldm_sample_guided).  num_steps = the ROWS of its program, timesteps[row] may repeat and go back up,
+     * coef = [rows][9] in the layout of rldm_sched_guided_step.  RLDM_SAMPLER_DDIM (eta = 0) or RLDM_SAMPLER_DDPM only.  The scheduler
+     * step of such a sampler is always a launch of its own (as with RLDM_FLAG_SCHED_LAUNCH): the blend comes after it, so conv_out's
+     * epilogue cannot pack the next step's input.  0 (what a zeroed struct says): everything else here, unchanged.  The field is the
+     * newest one; it sits in what was the alignment hole in front of `coef`, so no existing offset and not the struct's size moved. */
+    int32_t guided;
+    /* per-step scheduler coefficients, HOST, [num_steps][5] in the layout of rldm_sched_{ddim,ddpm,dpmsolver}_step ([9]: guided) */
     const float* coef;
     /* timesteps, HOST int64 [num_steps] (scheduler.timesteps)                                                 */
     const int64_t* timesteps;
@@ -178,6 +200,13 @@ void rldm_sampler_destroy(rldm_sampler* s);
  * the sampler has no VAE); latents_out: optional device fp32 [B, out_ch, W, H] receiving the final latent. */
 int rldm_sample(rldm_sampler* s, const float* x_T, const float* step_noise, const float* cond, float* images,
                 float* latents_out, void* stream);
+/* rldm_sample for a sampler created with guided = 1: every row runs the UNet, then rldm_sched_guided_step with the row's coefficients.
+ * known: device fp32 [B, out_ch, W, H] (the clean known sample z0, at the UNet's sample resolution); mask: device fp32 [B, 1, W, H];
+ * known_noise / renoise_noise: device fp32 [rows, B, out_ch, W, H], each NULL when every row's coefficient for it is zero (kb; rb).
+ * step_noise: [rows, B, out_ch, W, H] (DDPM) or NULL (DDIM).  No cond.  rldm_sample refuses a guided sampler and this call an
+ * unguided one; rldm_sampler_status covers both. */
+int rldm_sample_guided(rldm_sampler* s, const float* x_T, const float* step_noise, const float* known, const float* mask,
+                       const float* known_noise, const float* renoise_noise, float* images, float* latents_out, void* stream);
 /* The reference's contract is "a correct tensor or an exception" (ldm/pipelines.py:218-222,463-464).  rldm_sample is asynchronous,
  * so the exception half is this call: it waits for the last rldm_sample of `s` and returns 0 when its outputs are valid.  Non-zero
  * = the self-check of the call's persistent launches tripped (1: a wait inside a workgroup cluster gave up, i.e. the GPU was shared

@@ -183,6 +183,117 @@ int launch_sched_step(const SchedParams& p, hipStream_t stream) {
     return 0;
 }
 
+// ---- guided scheduler step (RePaint-style known-region replacement on an unconditional sampler) -------------------------------
+// Per element of the lane's sample, in fp32:  u = the scheduler step above (same expression, same row, same roundings);
+//   g = m * (ka * z0 + kb * nk) + (1 - m) * u      m = the one-channel mask at sample resolution, broadcast over channels (1: known)
+//   x' = ra * g + rb * nr                          (ra, rb) = (1, 0) on rows that do not jump back up
+// Row = {c0 .. c4, ka, kb, ra, rb}.  m == 1 and m == 0 are SELECTIONS: a known pixel does not depend on u (an inf there stays
+// there), an unknown one not on z0 / nk.  ka * z0 + kb * nk is two roundings of the products and one of the sum (no contraction),
+// so a host can restate it bit for bit; nk is read only when kb != 0, nr only when the row jumps.
+// u, rounding by rounding as sched_step_kernel evaluates sched_prev (+ its noise term): which products are fused into an fma and which
+// are rounded on their own is spelled out here, so this kernel cannot drift from that one with the shape of the code around it
+// (tests/test_guided_gpu.py holds the two bit-equal for every mode and prediction type).
+__device__ __forceinline__ float guided_sched_u(const int mode, const float c0, const float c1, const float c2, const float c3, const float c4,
+                                                const float x, const float e, const float nz, const bool use_noise) {
+#pragma clang fp contract(off)
+    const int pred = (mode >> 1) & 3;
+    float x0, pe;
+    if (pred == 0) {
+        x0 = __builtin_fmaf(-c1, e, x) / c0;
+        pe = e;
+    } else if (pred == 1) {
+        const float c1e = c1 * e, c0e = c0 * e;
+        x0 = __builtin_fmaf(c0, x, -c1e);
+        pe = __builtin_fmaf(c1, x, c0e);
+    } else {
+        x0 = e;
+        pe = __builtin_fmaf(-c0, e, x) / c1;
+    }
+    const float a = c2 * x0;
+    const float b = c3 * ((mode & 1) == 0 ? pe : x);
+    float u = a + b;
+    if (use_noise) u = __builtin_fmaf(c4, nz, u);
+    return u;
+}
+__device__ __forceinline__ float guided_known(const float ka, const float z0, const float kb, const float nk, const bool use_nk) {
+#pragma clang fp contract(off)
+    const float a = ka * z0;
+    if (!use_nk) return a;
+    const float b = kb * nk;
+    return a + b;
+}
+template <int V> struct GuidedVec { float v[V]; };
+template <int V> __device__ __forceinline__ GuidedVec<V> guided_load(const float* p) {
+    GuidedVec<V> r;
+    if constexpr (V == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(p);
+        r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
+    } else {
+        r.v[0] = *p;
+    }
+    return r;
+}
+template <int V> __device__ __forceinline__ void guided_store(float* p, const GuidedVec<V>& r) {
+    if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
+    else *p = r.v[0];
+}
+// V = 4: n, spatial and every pointer (step strides included) are multiples of 4 floats -- the four elements of a group share
+// their image and channel, so the mask is one float4 as well.  V = 1: any shape.
+template <int V> __global__ void __launch_bounds__(256) sched_guided_step_kernel(const GuidedSchedParams p) {
+    float c0, c1, c2, c3, c4, ka, kb, ra, rb;
+    const float* nz = p.s.noise;
+    const float* nk = p.known_noise;
+    const float* nr = p.renoise_noise;
+    if (p.s.coef_table) {
+        const int step = *p.s.step_ptr;
+        const float* c = p.s.coef_table + 9 * step;
+        c0 = c[0]; c1 = c[1]; c2 = c[2]; c3 = c[3]; c4 = c[4]; ka = c[5]; kb = c[6]; ra = c[7]; rb = c[8];
+        const size_t off = (size_t)step * p.s.noise_step_stride;
+        if (nz) nz += off;
+        if (nk) nk += off;
+        if (nr) nr += off;
+    } else {
+        c0 = p.s.coef[0]; c1 = p.s.coef[1]; c2 = p.s.coef[2]; c3 = p.s.coef[3]; c4 = p.s.coef[4];
+        ka = p.k[0]; kb = p.k[1]; ra = p.k[2]; rb = p.k[3];
+    }
+    const bool use_noise = nz != nullptr && c4 != 0.f;
+    const bool use_nk = nk != nullptr && kb != 0.f;
+    const bool jump = nr != nullptr && (ra != 1.f || rb != 0.f);
+    const long long groups = p.s.n / V;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < groups; q += (long long)gridDim.x * 256) {
+        const long long i = q * V;
+        const long long mi = (i / p.per_sample) * p.spatial + i % p.spatial;
+        const GuidedVec<V> x = guided_load<V>(p.s.x + i), e = guided_load<V>(p.s.eps + i);
+        const GuidedVec<V> z0 = guided_load<V>(p.known + i), m = guided_load<V>(p.mask + mi);
+        GuidedVec<V> zn, zk, zr, out;
+        if (use_noise) zn = guided_load<V>(nz + i);
+        if (use_nk) zk = guided_load<V>(nk + i);
+        if (jump) zr = guided_load<V>(nr + i);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float u = guided_sched_u(p.s.mode, c0, c1, c2, c3, c4, x.v[j], e.v[j], use_noise ? zn.v[j] : 0.f, use_noise);
+            const float kn = guided_known(ka, z0.v[j], kb, use_nk ? zk.v[j] : 0.f, use_nk);
+            const float mm = m.v[j];
+            float g = mm == 1.f ? kn : u;
+            if (mm != 1.f && mm != 0.f) g = mm * kn + (1.f - mm) * u;
+            if (jump) g = ra * g + rb * zr.v[j];
+            out.v[j] = g;
+        }
+        guided_store<V>(p.s.x_prev + i, out);
+    }
+}
+int launch_sched_guided_step(const GuidedSchedParams& p, hipStream_t stream) {
+    auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    const bool vec = p.s.n % 4 == 0 && p.spatial % 4 == 0 && p.s.noise_step_stride % 4 == 0 && al(p.s.x) && al(p.s.eps) &&
+                     al(p.s.x_prev) && al(p.s.noise) && al(p.known) && al(p.mask) && al(p.known_noise) && al(p.renoise_noise);
+    const long long groups = vec ? p.s.n / 4 : p.s.n;
+    const unsigned grid = (unsigned)((groups + 255) / 256 > 2048 ? 2048 : (groups + 255) / 256);
+    if (vec) hipLaunchKernelGGL(sched_guided_step_kernel<4>, dim3(grid), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(sched_guided_step_kernel<1>, dim3(grid), dim3(256), 0, stream, p);
+    RLDM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 struct AddNoiseCoef { float sa[64]; float sb[64]; };
 __global__ void __launch_bounds__(256) add_noise_kernel(const float* x0, const float* noise, AddNoiseCoef c, long long per,
                                                         long long n, float* out) {

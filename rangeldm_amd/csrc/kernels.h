@@ -420,6 +420,19 @@ struct SchedParams {
     long long n;
 };
 int launch_sched_step(const SchedParams& p, hipStream_t stream);
+// guided scheduler step: the step of `s`, then the known-region blend and the re-noise (elementwise.hip).  In table mode the rows
+// are 9 floats wide ({coef[5], ka, kb, ra, rb}) and the three noise tensors share s.noise_step_stride; s.n = B * per_sample.
+struct GuidedSchedParams {
+    SchedParams s;
+    float k[4];                       // ka, kb, ra, rb (baked mode)
+    const float* known;               // z0, laid out like x
+    const float* mask;                // [B][spatial], 1 = known
+    const float* known_noise;         // nk, like noise; may be null when kb == 0 on every row
+    const float* renoise_noise;       // nr, like noise; may be null when no row jumps
+    long long per_sample;             // channels * spatial
+    long long spatial;
+};
+int launch_sched_guided_step(const GuidedSchedParams& p, hipStream_t stream);
 int launch_add_noise(const float* x0, const float* noise, const float* sa, const float* sb, int B, long long per,
                      float* out, hipStream_t stream);
 int launch_diag_gaussian(const float* moments, const float* noise, float scale, int B, int z, int spatial, float* out,

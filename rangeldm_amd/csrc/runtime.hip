@@ -2924,6 +2924,16 @@ static int vae_get_plan(rldm_vae* m, int B, int w, int h, bool enc, Plan** out) 
 // One lane = an independent slice of the batch with its own plans, buffers, stream and captured graphs.  Whole samples
 // never interact, so the lanes' 50-step chains run concurrently on separate streams: the low-resolution UNet levels
 // launch far fewer workgroups than the chip has CUs, and a second (third, fourth) chain fills the idle ones.
+// the four extra tensors of rldm_sample_guided (null for an unguided sampler)
+struct GuidedIO {
+    const float* known = nullptr;
+    const float* mask = nullptr;
+    const float* known_noise = nullptr;
+    const float* renoise_noise = nullptr;
+    bool operator==(const GuidedIO& o) const {
+        return known == o.known && mask == o.mask && known_noise == o.known_noise && renoise_noise == o.renoise_noise;
+    }
+};
 struct SamplerLane {
     int b0 = 0, nb = 0;                             // samples [b0, b0 + nb) of the batch
     std::unique_ptr<Plan> uplan;                    // private UNet plan (graph-baked pointers)
@@ -2936,6 +2946,7 @@ struct SamplerLane {
     int graph_steps = 1;                            // sampler steps captured in step_graph
     bool fused_tail = true;                         // scheduler step in conv_out's epilogue, step index advanced by pack_input
     const float* captured_noise = nullptr;
+    GuidedIO guided, captured_guided;               // guided sampler: this call's tensors (offset to the lane) / those the graph holds
     long long n_latent = 0, n_image = 0, n_cond = 0;
     int* check_host = nullptr;                      // pinned: the persistent launches' self-check word of the last call (copied behind its
     bool check_pending = false;                     // last launch; read by rldm_sampler_status, the next call or the destructor)
@@ -2966,6 +2977,7 @@ struct rldm_sampler {
                                                     // launches at the next call instead of meeting that sampler's launches again
     int latched_error = 0;                          // self-check code of a call whose pending word was read while the plans were rebuilt
     int inject_error = 0;                           // tests: rldm_debug_inject_trunk_error (one shot)
+    bool needs_known_noise = false, needs_renoise_noise = false;   // guided: some row has kb != 0 / (ra, rb) != (1, 0)
     bool has_persistent() const {
         for (auto& ln : lanes)
             if (ln->uplan && ln->uplan->trunk_error.p) return true;
@@ -3055,7 +3067,20 @@ static int sampler_enqueue_step(rldm_sampler* s, SamplerLane* ln, const float* n
     }
     sp.x_prev = ln->x.as<float>();
     sp.n = ln->n_latent;
-    if (launch_sched_step(sp, st)) return 1;
+    if (s->cfg.guided) {
+        // the guided step stands where the scheduler step stands: same row index, rows of 9, two more per-row noise tensors
+        const auto& uc = s->unet->cfg;
+        GuidedSchedParams gp;
+        memset(&gp, 0, sizeof(gp));
+        gp.s = sp;
+        gp.known = ln->guided.known;
+        gp.mask = ln->guided.mask;
+        gp.known_noise = ln->guided.known_noise;
+        gp.renoise_noise = ln->guided.renoise_noise;
+        gp.spatial = (long long)uc.sample_w * uc.sample_h;
+        gp.per_sample = gp.spatial * uc.out_channels;
+        if (launch_sched_guided_step(gp, st)) return 1;
+    } else if (launch_sched_step(sp, st)) return 1;
     return launch_step_counter(ln->step.as<int>(), 0, 1, st);
 }
 
@@ -3079,6 +3104,7 @@ static int sampler_build_plans(rldm_sampler* s) {
         if (ln->step_graph) { (void)hipGraphExecDestroy(ln->step_graph); ln->step_graph = nullptr; }
         if (ln->decode_graph) { (void)hipGraphExecDestroy(ln->decode_graph); ln->decode_graph = nullptr; }
         ln->captured_noise = nullptr;
+        ln->captured_guided = GuidedIO();
         ln->uplan.reset();
         ln->dplan.reset();
         g_concurrent_plans = (int)s->lanes.size();
@@ -3099,7 +3125,8 @@ static int sampler_build_plans(rldm_sampler* s) {
         io.step_ptr = ln->step.as<int>();
         io.temb_rows_per_step = 1;
         io.temb_per_sample = 0;
-        ln->fused_tail = !((g_dbg_flags | s->plan_flags) & RLDM_FLAG_SCHED_LAUNCH);
+        // (a guided sampler blends AFTER the scheduler step: the input conv_out's epilogue would pack for the next step would be stale)
+        ln->fused_tail = !((g_dbg_flags | s->plan_flags) & RLDM_FLAG_SCHED_LAUNCH) && !s->cfg.guided;
         if (ln->fused_tail) {
             // the scheduler step rides in conv_out's epilogue, the step index is advanced by pack_input: 2 launches per step fewer
             SchedFuse& f = io.sch;
@@ -3426,6 +3453,28 @@ int rldm_sched_step(int sampler_mode, int prediction_type, const float coef[5], 
     RLDM_REQUIRE(prediction_type >= RLDM_PRED_EPSILON && prediction_type <= RLDM_PRED_SAMPLE, "unknown prediction type");
     return sched_step((sampler_mode == RLDM_SAMPLER_DDIM ? 0 : 1) | (prediction_type << 1), coef, model_output, x, noise, x_prev, n, stream);
 }
+int rldm_sched_guided_step(int sampler_mode, int prediction_type, const float coef[9], const float* model_output, const float* x,
+                           const float* noise, const float* known, const float* mask, const float* known_noise,
+                           const float* renoise_noise, float* x_prev, int B, int C, int64_t spatial, void* stream) {
+    RLDM_REQUIRE(sampler_mode == RLDM_SAMPLER_DDIM || sampler_mode == RLDM_SAMPLER_DDPM, "guided step: sampler mode must be DDIM or DDPM");
+    RLDM_REQUIRE(prediction_type >= RLDM_PRED_EPSILON && prediction_type <= RLDM_PRED_SAMPLE, "unknown prediction type");
+    RLDM_REQUIRE(coef && model_output && x && known && mask && x_prev, "null argument");
+    RLDM_REQUIRE(B >= 1 && C >= 1 && spatial >= 1, "guided step: empty shape");
+    RLDM_REQUIRE(coef[4] == 0.f || noise != nullptr, "sigma != 0 requires a noise tensor");
+    RLDM_REQUIRE(coef[6] == 0.f || known_noise != nullptr, "kb != 0 requires a known_noise tensor");
+    RLDM_REQUIRE((coef[7] == 1.f && coef[8] == 0.f) || renoise_noise != nullptr, "(ra, rb) != (1, 0) requires a renoise_noise tensor");
+    GuidedSchedParams gp;
+    memset(&gp, 0, sizeof(gp));
+    gp.s.mode = (sampler_mode == RLDM_SAMPLER_DDIM ? 0 : 1) | (prediction_type << 1);
+    for (int i = 0; i < 5; ++i) gp.s.coef[i] = coef[i];
+    for (int i = 0; i < 4; ++i) gp.k[i] = coef[5 + i];
+    gp.s.eps = model_output; gp.s.x = x; gp.s.noise = noise; gp.s.x_prev = x_prev;
+    gp.known = known; gp.mask = mask; gp.known_noise = known_noise; gp.renoise_noise = renoise_noise;
+    gp.spatial = spatial;
+    gp.per_sample = spatial * C;
+    gp.s.n = gp.per_sample * B;
+    return launch_sched_guided_step(gp, reinterpret_cast<hipStream_t>(stream));
+}
 int rldm_sched_add_noise(const float* x0, const float* noise, const float* sqrt_alpha, const float* sqrt_beta, int B,
                          int64_t per_sample, float* out, void* stream) {
     RLDM_REQUIRE(x0 && noise && sqrt_alpha && sqrt_beta && out, "null argument");
@@ -3460,6 +3509,14 @@ int rldm_sampler_create(rldm_unet* unet, rldm_vae* vae, const rldm_sampler_confi
     RLDM_REQUIRE(cfg->prediction_type >= RLDM_PRED_EPSILON && cfg->prediction_type <= RLDM_PRED_SAMPLE, "bad sampler config: prediction_type");
     RLDM_REQUIRE(cfg->mode == RLDM_SAMPLER_DDIM || cfg->mode == RLDM_SAMPLER_DDPM || cfg->mode == RLDM_SAMPLER_DPMSOLVER,
                  "bad sampler config: mode");
+    RLDM_REQUIRE(cfg->guided == 0 || cfg->guided == 1, "bad sampler config: guided");
+    RLDM_REQUIRE(!cfg->guided || cfg->mode != RLDM_SAMPLER_DPMSOLVER,
+                 "a guided sampler runs DDIM (eta = 0) or DDPM rows: DPM-Solver++'s x0 history means nothing across a jump back up");
+    RLDM_REQUIRE(!cfg->guided || cfg->cond_channels == 0, "a guided sampler is unconditional (cond_channels == 0)");
+    const int coef_w = cfg->guided ? 9 : 5;
+    if (cfg->guided)
+        for (int i = 0; i < cfg->num_steps; ++i)
+            RLDM_REQUIRE(cfg->mode != RLDM_SAMPLER_DDIM || cfg->coef[(size_t)i * 9 + 4] == 0.f, "a guided DDIM sampler needs eta = 0 rows");
     const auto& uc = unet->cfg;
     RLDM_REQUIRE(uc.out_channels + (cfg->pos_encoding ? 1 : 0) + cfg->cond_channels == uc.in_channels,
                  "unet.in_channels != out_channels + pos_encoding + cond_channels (ldm/pipelines.py:351,480)");
@@ -3483,7 +3540,13 @@ int rldm_sampler_create(rldm_unet* unet, rldm_vae* vae, const rldm_sampler_confi
     s->n_latent = B * per_latent;
     s->n_image = B * per_image;
     RLDM_HIP_CHECK(hipEventCreateWithFlags(&s->ev_in, hipEventDisableTiming));
-    if (upload(s->coef, cfg->coef, (size_t)cfg->num_steps * 5 * 4)) return 1;
+    if (upload(s->coef, cfg->coef, (size_t)cfg->num_steps * coef_w * 4)) return 1;
+    if (cfg->guided)
+        for (int i = 0; i < cfg->num_steps; ++i) {
+            const float* r = cfg->coef + (size_t)i * 9;
+            s->needs_known_noise |= r[6] != 0.f;
+            s->needs_renoise_noise |= r[7] != 1.f || r[8] != 0.f;
+        }
     std::vector<float> tf(cfg->num_steps);
     for (int i = 0; i < cfg->num_steps; ++i) tf[i] = (float)cfg->timesteps[i];
     if (upload(s->t_dev, tf.data(), tf.size() * 4)) return 1;
@@ -3548,8 +3611,8 @@ int rldm_debug_inject_trunk_error(rldm_sampler* s, int code) {
     return 0;
 }
 
-int rldm_sample(rldm_sampler* s, const float* x_T, const float* step_noise, const float* cond, float* images,
-                float* latents_out, void* stream) {
+static int sample_impl(rldm_sampler* s, const float* x_T, const float* step_noise, const float* cond, const GuidedIO& gio, float* images,
+                       float* latents_out, void* stream) {
     RLDM_REQUIRE(s && x_T, "null argument");
     RLDM_REQUIRE(images || latents_out, "no output requested");
     RLDM_REQUIRE((s->cfg.cond_channels == 0) == (cond == nullptr), "cond tensor does not match sampler.cond_channels");
@@ -3609,7 +3672,14 @@ int rldm_sample(rldm_sampler* s, const float* x_T, const float* step_noise, cons
         if (sampler_pack_x(s, ln, st)) return 1;
         if (launch_step_counter(ln->step.as<int>(), ln->fused_tail ? -1 : 0, 0, st)) return 1;
         const float* noise = s->cfg.mode == RLDM_SAMPLER_DDPM ? step_noise + lat_off : nullptr;
-        if (!ln->step_graph || ln->captured_noise != noise) {
+        ln->guided = GuidedIO();
+        if (s->cfg.guided) {                        // each offset to the lane's first sample, exactly as step_noise is
+            ln->guided.known = gio.known + lat_off;
+            ln->guided.mask = gio.mask + (size_t)ln->b0 * s->unet->cfg.sample_w * s->unet->cfg.sample_h;
+            ln->guided.known_noise = gio.known_noise ? gio.known_noise + lat_off : nullptr;
+            ln->guided.renoise_noise = gio.renoise_noise ? gio.renoise_noise + lat_off : nullptr;
+        }
+        if (!ln->step_graph || ln->captured_noise != noise || !(ln->captured_guided == ln->guided)) {
             // one eager step first (sets kernel attributes, packs weights), then rewind and capture
             if (sampler_enqueue_step(s, ln, noise, st)) return 1;
             RLDM_HIP_CHECK(hipStreamSynchronize(st));
@@ -3622,7 +3692,7 @@ int rldm_sample(rldm_sampler* s, const float* x_T, const float* step_noise, cons
                     // the clusters' only assumption (an image's workgroups share an XCD; all of them resident) does not hold on this
                     // device / driver / right now: THIS sampler runs every layer as a launch of its own from here on (same kernels, tiles)
                     if (sampler_drop_persistent(s, "persistent launches failed their self-check at the warm-up step", terr)) return 1;
-                    return rldm_sample(s, x_T, step_noise, cond, images, latents_out, stream);
+                    return sample_impl(s, x_T, step_noise, cond, gio, images, latents_out, stream);
                 }
                 RLDM_REQUIRE(terr == 0, "persistent trunk launch failed its self-check (code " + std::to_string(terr) +
                                             "): set RLDM_DBG_FLAGS=16777216 to run the levels as separate launches");
@@ -3641,6 +3711,7 @@ int rldm_sample(rldm_sampler* s, const float* x_T, const float* step_noise, cons
                     return 0;
                 }, &ln->step_graph)) return 1;
             ln->captured_noise = noise;
+            ln->captured_guided = ln->guided;
         }
         if (images && s->vae && !ln->decode_graph) {
             // (the decode runs on whatever x holds now: only its launch list is recorded)
@@ -3692,6 +3763,26 @@ int rldm_sample(rldm_sampler* s, const float* x_T, const float* step_noise, cons
         RLDM_HIP_CHECK(hipStreamWaitEvent(caller, ln->ev_out, 0));
     }
     return 0;
+}
+
+int rldm_sample(rldm_sampler* s, const float* x_T, const float* step_noise, const float* cond, float* images,
+                float* latents_out, void* stream) {
+    RLDM_REQUIRE(s, "null argument");
+    RLDM_REQUIRE(!s->cfg.guided, "this sampler was created with guided = 1: call rldm_sample_guided (known, mask and the two noise "
+                                 "tensors are part of every row)");
+    return sample_impl(s, x_T, step_noise, cond, GuidedIO(), images, latents_out, stream);
+}
+
+int rldm_sample_guided(rldm_sampler* s, const float* x_T, const float* step_noise, const float* known, const float* mask,
+                       const float* known_noise, const float* renoise_noise, float* images, float* latents_out, void* stream) {
+    RLDM_REQUIRE(s, "null argument");
+    RLDM_REQUIRE(s->cfg.guided, "rldm_sample_guided needs a sampler created with guided = 1");
+    RLDM_REQUIRE(known && mask, "null argument: known / mask");
+    RLDM_REQUIRE(known_noise || !s->needs_known_noise, "some row has kb != 0: known_noise must be given");
+    RLDM_REQUIRE(renoise_noise || !s->needs_renoise_noise, "some row jumps back up: renoise_noise must be given");
+    GuidedIO gio;
+    gio.known = known; gio.mask = mask; gio.known_noise = known_noise; gio.renoise_noise = renoise_noise;
+    return sample_impl(s, x_T, step_noise, nullptr, gio, images, latents_out, stream);
 }
 
 // one instrumented UNet step + scheduler step (+ VAE decode) of lane 0: per-kernel launch counts, HIP-event time,

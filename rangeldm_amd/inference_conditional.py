@@ -14,6 +14,15 @@ What is the reference's and what is not:
     (`point_cloud_to_range_image.normalize`); without it a deterministic synthetic batch stands in (no dataset is reachable
     offline).  `down` / `masked_image` / `inpainting_mask` are derived as `ldm/dataset.py:340-362` does (rangeldm_amd.conditional).
   * the networks: `--weights` = the training run's output_dir (`unet/ vae/ scheduler/`), else synthetic weights.
+
+`--guided` takes an UNCONDITIONAL config (`RangeLDM`, `RangeDM`, or their yaml) instead: the released checkpoints complete a scan by
+known-region replacement inside the captured loop (RePaint; rangeldm_amd.schedulers.repaint_program), no conditional UNet needed.
+
+    python -m rangeldm_amd.inference_conditional --guided --cfg RangeLDM --samples 32 --out outputs/guided/generated
+    python -m rangeldm_amd.inference_conditional --guided --task densification --cfg RangeDM --jump-length 10 --jump-n-sample 10
+
+The same folders are written (`inpainting_*` / `densification_*`), so `rangeldm_amd.evaluate inpainting | densification` scores them
+unchanged.  Densification (every 4th beam known) needs the pixel-space model: no latent pixel is fully known under that mask.
 """
 import argparse
 import glob
@@ -85,6 +94,95 @@ def load_batch(input_dir, B, shape, seed):
     return torch.cat([rng.expand(B, 1, W, H).clamp(-0.5, 2.0), rem], 1).contiguous()
 
 
+def guided_known_mask(jpg, task, fraction=0.0625, rate=4):
+    """(B, 1, W, H) bool, True = known, and the image shown as the input (-1 where unknown).  inpainting: the reference's mask has
+    +1 over the masked azimuth span (conditional.inpainting_inputs), so known = mask < 0; densification: the beams
+    downsample_range_image keeps."""
+    if task == "inpainting":
+        mask, masked = inpainting_inputs(jpg, fraction)
+        return mask < 0, masked
+    known = torch.zeros((jpg.shape[0], 1, *jpg.shape[2:]), dtype=torch.bool, device=jpg.device)
+    known[..., (rate // 2)::rate] = True
+    return known, sparse_input_image(jpg, downsample_range_image(jpg, rate), rate)
+
+
+def main_guided(a):
+    """--guided: LDMPipelineRange / DDIMPipelineRange with `known` / `known_mask` on an unconditional config."""
+    from .inference import load_config
+    from .params import unet_param_shapes, vae_param_shapes
+    from .pipelines import DDIMPipelineRange, LDMPipelineRange
+    from .schedulers import DDIMSchedulerHIP
+    from .synth import synth_state_dict
+    from .unet import UNet2DModelHIP
+    from .vae import AutoencoderKLHIP
+
+    cfg = load_config(a.cfg)
+    if cfg.get("cond_channels", 0):
+        raise ValueError(f"--guided takes an unconditional config (RangeLDM, RangeDM); {a.cfg} is conditional")
+    if (a.scheduler or "ddpm") == "dpmsolver++":
+        raise NotImplementedError("--guided runs DDPM or DDIM rows (DPM-Solver++ keeps an x0 history that a jump invalidates)")
+    B = a.batch_size or cfg.get("batch", 16)
+    steps = a.steps or cfg.get("steps", 50)
+    rank, world, local = D.init_from_env()
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    out = a.out or os.path.join("outputs", os.path.splitext(os.path.basename(a.cfg))[0], "guided")
+    stem = a.task
+    result_path, target_path, input_path = (os.path.join(out, f"{stem}_{k}") for k in ("result", "target", "input"))
+    for d in (result_path, target_path, input_path):
+        os.makedirs(d, exist_ok=True)
+    sched_cfg = None
+    latent = cfg["vae"] is not None
+    if a.weights:
+        from .checkpoint import load_output_dir
+        ck = load_output_dir(a.weights, with_vae=latent, ema=a.ema)
+        cfg["unet"], usd, sched_cfg = ck["unet_config"], ck["unet"], ck["scheduler_config"]
+        if latent:
+            cfg["vae"], vsd = ck["vae_config"], ck["vae"]
+    else:
+        usd = synth_state_dict(unet_param_shapes(cfg["unet"]), seed=a.seed, prefix="")
+        if latent:
+            vsd = synth_state_dict(vae_param_shapes(cfg["vae"]), seed=a.seed, prefix="vae.")
+    unet = UNet2DModelHIP(cfg["unet"])
+    unet.load_state_dict(usd)
+    if latent:
+        vae = AutoencoderKLHIP(cfg["vae"])
+        vae.load_state_dict(vsd)
+        pipe = LDMPipelineRange(vae=vae, unet=unet, scheduler=make_scheduler(a.scheduler or "ddpm", sched_cfg),
+                                pos_encoding=cfg["pos_encoding"])
+        f = cfg["vae"].downscale
+        img_shape = (cfg["vae"].in_channels, cfg["unet"].sample_size[0] * f, cfg["unet"].sample_size[1] * f)
+    else:
+        pipe = DDIMPipelineRange(unet=unet, scheduler=DDIMSchedulerHIP(sched_cfg), pos_encoding=cfg["pos_encoding"])
+        img_shape = (cfg["unet"].out_channels, *cfg["unet"].sample_size)
+    jpg = load_batch(a.input, B, img_shape, a.seed).to(dev)
+    known_mask, shown = guided_known_mask(jpg, a.task)
+    to_range = sensor_for(jpg.shape[3])
+    lim = 90.0 if jpg.shape[3] == 32 else 70.0
+
+    def write(dirname, image, seed):
+        points, counts, bev_u8, _ = postprocess(to_range, image, max_depth=lim)
+        for j in range(image.shape[0]):
+            points[j, :counts[j]].tofile(os.path.join(dirname, f"{j}_seed_{seed}.bin"))
+            save_png(bev_u8[j], os.path.join(dirname, f"{j}_seed_{seed}.png"))
+            if a.save_npy:
+                np.save(os.path.join(dirname, f"{j}_seed_{seed}.npy"), image[j].float().cpu().numpy())
+
+    n_iter = a.samples // B // world + 1
+    for i in range(n_iter):
+        seed = rank + world * i
+        generator = torch.Generator().manual_seed(seed)
+        images = pipe(batch_size=B, generator=generator, num_inference_steps=steps, output_type="torch", known=jpg,
+                      known_mask=known_mask, jump_length=a.jump_length, jump_n_sample=a.jump_n_sample)
+        write(result_path, images.contiguous(), seed)
+        if seed == 0:
+            write(target_path, jpg, seed)
+            write(input_path, shown.contiguous(), seed)
+    D.barrier()
+    if rank == 0:
+        print(f"wrote {n_iter * B} guided {stem} results to {result_path}")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="RangeLDM conditional sampler on MI355X (ldm/inference_conditional.py counterpart)")
     ap.add_argument("--cfg", required=True)
@@ -95,8 +193,16 @@ def main(argv=None):
     ap.add_argument("--weights", default=None, help="reference-style output_dir with unet/ and vae/ safetensors")
     ap.add_argument("--seed", type=int, default=20240310)
     ap.add_argument("--ema", action="store_true")
+    ap.add_argument("--guided", action="store_true",
+                    help="complete the scan with an UNCONDITIONAL config (RangeLDM, RangeDM) by known-region replacement")
+    ap.add_argument("--task", choices=("inpainting", "densification"), default="inpainting", help="--guided: which mask")
+    ap.add_argument("--jump-length", type=int, default=1, help="--guided: RePaint's jump length (rows re-noised per jump)")
+    ap.add_argument("--jump-n-sample", type=int, default=1, help="--guided: RePaint's resampling count (1: no jumps)")
+    ap.add_argument("--save-npy", action="store_true", help="--guided: also write the raw (2, W, H) fp32 range images")
     add_sampling_args(ap)
     a = ap.parse_args(argv)
+    if a.guided:
+        return main_guided(a)
 
     from .encoders import SparseRangeImageEncoder2
     from .params import unet_param_shapes, vae_param_shapes

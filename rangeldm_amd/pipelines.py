@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .schedulers import DDIMSchedulerHIP, DDPMSchedulerHIP, DPMSolverMultistepSchedulerHIP, randn_tensor
+from .schedulers import (DDIMSchedulerHIP, DDPMSchedulerHIP, DPMSolverMultistepSchedulerHIP, guided_step, randn_tensor,
+                         repaint_program)
 
 
 class ImagePipelineOutput:
@@ -31,24 +32,46 @@ def _sampler_mode(scheduler):
     return _lib.RLDM_SAMPLER_DDPM
 
 
+def latent_known_mask(known_mask, downscale):
+    """Pixel mask (B, 1, W, H), 1 / True = known -> latent mask (B, 1, W / f, H / f) fp32: a latent pixel is known only if its
+    whole f x f footprint is (a min-pool).  A mask that leaves some sample without one fully known latent pixel -- every 4th beam
+    does -- cannot guide a latent sampler: ValueError."""
+    m = (known_mask.to(torch.float32) > 0.5).to(torch.float32)
+    if m.dim() != 4 or m.shape[1] != 1 or m.shape[2] % downscale or m.shape[3] % downscale:
+        raise ValueError(f"known_mask must be (B, 1, W, H) with W, H multiples of {downscale}; got {tuple(m.shape)}")
+    lat = -torch.nn.functional.max_pool2d(-m, kernel_size=downscale)
+    if bool((lat.flatten(1).sum(1) == 0).any()):
+        raise ValueError(f"known_mask leaves no latent pixel whose whole {downscale} x {downscale} footprint is known (a beam-subsampling "
+                         "mask does that): guide the pixel-space pipeline (DDIMPipelineRange, RangeDM) instead")
+    return lat
+
+
 class _FusedSampler:
-    """Owns one rldm_sampler per (batch, steps, mode, pos_encoding, cond_channels, eta, schedule)."""
+    """Owns one rldm_sampler per (batch, steps, mode, pos_encoding, cond_channels, eta, schedule, guided, plan_flags)."""
 
     def __init__(self):
         self._cache = {}
 
-    def get(self, unet, vae, scheduler, batch, steps, mode, pos_encoding, cond_channels, eta=0.0):
+    def get(self, unet, vae, scheduler, batch, steps, mode, pos_encoding, cond_channels, eta=0.0, program=None, plan_flags=0):
         # keyed by the model objects themselves (kept alive by the cache entry, so an id is never reused for another
         # model); weights reloaded through load_state_dict are picked up by the library: rldm_sample re-plans and
         # re-captures when the model's generation counter moved (include/rangeldm_hip.h, rldm_unet_finalize)
         # ... and by the schedule itself (timesteps and coefficient rows): two schedulers of one kind and step count can differ
         # in their spacing or solver order
+        # `program` = (timesteps, [rows][9] table) of schedulers.repaint_program: a guided sampler, whose num_steps is its row count
+        # plan_flags: rldm_sampler_config::plan_flags (_lib.Flag bits scoped to this sampler)
         pred = int(getattr(scheduler, "prediction_code", 0))
-        scheduler.set_timesteps(steps)
-        ts = np.ascontiguousarray(scheduler.timesteps.numpy().astype(np.int64))
-        coef = scheduler.sampler_table(eta if mode == _lib.RLDM_SAMPLER_DDIM else 0.0)
+        guided = program is not None
+        if guided:
+            ts = np.ascontiguousarray(program[0].numpy().astype(np.int64))
+            coef = np.ascontiguousarray(program[1], dtype=np.float32)
+            steps = len(ts)
+        else:
+            scheduler.set_timesteps(steps)
+            ts = np.ascontiguousarray(scheduler.timesteps.numpy().astype(np.int64))
+            coef = scheduler.sampler_table(eta if mode == _lib.RLDM_SAMPLER_DDIM else 0.0)
         key = (id(unet), id(vae), batch, steps, mode, bool(pos_encoding), cond_channels, float(eta), pred, ts.tobytes(),
-               coef.tobytes())
+               coef.tobytes(), guided, int(plan_flags))
         ent = self._cache.get(key)
         if ent is not None:
             return ent[0]
@@ -57,6 +80,8 @@ class _FusedSampler:
         cfg.pos_encoding = 1 if pos_encoding else 0
         cfg.cond_channels = cond_channels
         cfg.prediction_type = pred
+        cfg.guided = 1 if guided else 0
+        cfg.plan_flags = int(plan_flags)
         cfg.coef = coef.ctypes.data_as(C.POINTER(C.c_float))
         cfg.timesteps = ts.ctypes.data_as(C.POINTER(C.c_int64))
         h = C.c_void_p()
@@ -75,6 +100,15 @@ class _FusedSampler:
             return C.c_void_p(t.data_ptr()) if t is not None else None
         _lib.check(_lib.lib().rldm_sample(h, p(x_T), p(step_noise), p(cond), p(out), p(latents_out),
                                           _lib.stream_ptr(x_T.device)), "rldm_sample")
+        if check:
+            self.status(h)
+
+    def run_guided(self, h, x_T, step_noise, known, mask, known_noise, renoise_noise, out, latents_out=None, check=True):
+        """One rldm_sample_guided call on a sampler made with `program`; `check` as in run."""
+        def p(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(_lib.lib().rldm_sample_guided(h, p(x_T), p(step_noise), p(known), p(mask), p(known_noise), p(renoise_noise), p(out),
+                                                 p(latents_out), _lib.stream_ptr(x_T.device)), "rldm_sample_guided")
         if check:
             self.status(h)
 
@@ -162,6 +196,56 @@ class _PipelineBase:
         return zs
 
 
+    def _guided_latents(self, vae, x_T, z0, mask, num_inference_steps, jump_length, jump_n_sample, generator, step_noise, known_noise,
+                        renoise_noise, fused, check, out=None):
+        """The guided loop (schedulers.repaint_program) on the unconditional UNet: x_T, z0 (B, C, W, H) and mask (B, 1, W, H) at the
+        UNet's sample resolution -> the final sample; with `out` (and a VAE, fused) the decoded images are written as well.
+        Noise not injected is drawn from `generator` in this order: the step noise (one draw per row with sigma != 0), the
+        known-region noise (rows with kb != 0), the re-noise (rows that jump)."""
+        dev = self.device
+        sch = self.scheduler
+        ts, table = repaint_program(sch, num_inference_steps, jump_length, jump_n_sample)
+        rows, shape = len(ts), tuple(x_T.shape)
+        mode = _sampler_mode(sch)
+
+        def per_row(given, col, name):
+            need = table[:, col] != 0.0 if col != 7 else (table[:, 7] != 1.0) | (table[:, 8] != 0.0)
+            if given is not None:
+                if tuple(given.shape) != (rows, *shape):
+                    raise ValueError(f"{name} shape {tuple(given.shape)} != {(rows, *shape)} (one slice per row of the program)")
+                return given.to(dev, torch.float32).contiguous()
+            if not need.any():
+                return None
+            zs = torch.zeros((rows, *shape), device=dev, dtype=torch.float32)
+            for i in np.nonzero(need)[0]:
+                zs[i] = randn_tensor(shape, generator=generator, device=dev, dtype=torch.float32)
+            return zs
+        zs = per_row(step_noise, 4, "step_noise")
+        nk = per_row(known_noise, 6, "known_noise")
+        nr = per_row(renoise_noise, 7, "renoise_noise")
+        x = x_T.to(dev, torch.float32).contiguous()
+        z0 = z0.to(dev, torch.float32).contiguous()
+        mask = mask.to(dev, torch.float32).expand(shape[0], 1, *shape[2:]).contiguous()
+        if z0.shape != x.shape:
+            raise ValueError(f"known sample {tuple(z0.shape)} != sample shape {shape}")
+        if fused:
+            if zs is None and mode == _lib.RLDM_SAMPLER_DDPM:      # (a one-row program: sigma == 0, the tensor is still asked for)
+                zs = torch.zeros((rows, *shape), device=dev, dtype=torch.float32)
+            h = self._fused.get(self.unet, vae, sch, shape[0], rows, mode, self.pos_encoding, 0, program=(ts, table))
+            lat = torch.empty_like(x)
+            self._fused.run_guided(h, x, zs, z0, mask, nk, nr, out if vae is not None else None, latents_out=lat, check=check)
+            return lat
+        if self.pos_encoding:
+            pos_encoding = torch.zeros([shape[0], 1, shape[2], shape[3]], device=dev)
+            pos_encoding[:, :, 0, :] = 1
+        for i, t in enumerate(self.progress_bar(ts)):
+            model_input = torch.cat([x, pos_encoding], dim=1) if self.pos_encoding else x
+            model_output = self.unet(model_input, t).sample
+            x = guided_step(sch, table[i], model_output, x, None if zs is None else zs[i], z0, mask, None if nk is None else nk[i],
+                            None if nr is None else nr[i])
+        return x
+
+
 class DDPMPipelineRange(_PipelineBase):
     """ldm/pipelines.py:13-117 (pixel-space ancestral sampling, no pos-encoding channel)."""
 
@@ -215,8 +299,12 @@ class DDIMPipelineRange(_PipelineBase):
 
     @torch.no_grad()
     def __call__(self, batch_size=1, generator=None, eta=0.0, num_inference_steps=50, use_clipped_model_output=None,
-                 output_type="torch", return_dict=True, fused=True, latents=None, **kwargs):
-        """`latents` (not in the reference signature): x_T already resident on the device, instead of drawing it."""
+                 output_type="torch", return_dict=True, fused=True, latents=None, known=None, known_mask=None, jump_length=1,
+                 jump_n_sample=1, known_noise=None, renoise_noise=None, **kwargs):
+        """`latents` (not in the reference signature): x_T already resident on the device, instead of drawing it.
+        `known` (B, C, W, H normalised range image) + `known_mask` (B, 1, W, H; 1 / True = known, any pattern -- every 4th beam
+        densifies): guided completion with these unconditional weights (schedulers.repaint_program; jump_length / jump_n_sample
+        are RePaint's; known_noise / renoise_noise [rows, B, C, W, H] inject the draws).  The known pixels come back unchanged."""
         cfg = self.unet.config
         ss = cfg.sample_size if not isinstance(cfg.sample_size, int) else (cfg.sample_size, cfg.sample_size)
         shape = (batch_size, cfg.out_channels, *ss)
@@ -231,6 +319,15 @@ class DDIMPipelineRange(_PipelineBase):
         else:
             image = randn_tensor(shape, generator=generator, device=self._execution_device, dtype=self.unet.dtype)
         self.scheduler.set_timesteps(num_inference_steps)
+        if known is not None:
+            if known_mask is None:
+                raise ValueError("`known` needs `known_mask`")
+            if eta != 0.0:
+                raise NotImplementedError("guided DDIM sampling is eta = 0")
+            m = (known_mask.to(torch.float32) > 0.5).to(torch.float32)
+            image = self._guided_latents(None, image, known, m, num_inference_steps, jump_length, jump_n_sample, generator, None,
+                                         known_noise, renoise_noise, fused, kwargs.get("check", True))
+            return self._finish(image, output_type, return_dict)
         if fused and eta == 0.0:
             h = self._fused.get(self.unet, None, self.scheduler, batch_size, num_inference_steps, 0,
                                 self.pos_encoding, 0, eta)
@@ -264,7 +361,13 @@ class LDMPipelineRange(_PipelineBase):
 
     @torch.no_grad()
     def __call__(self, batch_size=1, generator=None, eta=0.0, num_inference_steps=50, output_type="torch",
-                 return_dict=True, final_only=True, fused=True, latents=None, step_noise=None, **kwargs):
+                 return_dict=True, final_only=True, fused=True, latents=None, step_noise=None, known=None, known_mask=None,
+                 jump_length=1, jump_n_sample=1, known_noise=None, renoise_noise=None, **kwargs):
+        """`known` (B, 2, W, H normalised range image) + `known_mask` (B, 1, W, H pixel mask; 1 / True = known): guided completion
+        with these unconditional weights.  z0 = vae.encode(known).latent_dist.mode() * scaling_factor; a latent pixel counts as
+        known only if its whole footprint is (latent_known_mask), so an azimuth-span mask works and a beam-subsampling mask raises.
+        step_noise / known_noise / renoise_noise are then [rows, B, C, W / f, H / f] of schedulers.repaint_program's rows.
+        `return_latents=True` (guided only) returns (images, final latents, z0, latent mask)."""
         cfg = self.unet.config
         shape = (batch_size, cfg.out_channels, *cfg.sample_size)
         if latents is None:
@@ -275,6 +378,26 @@ class LDMPipelineRange(_PipelineBase):
         accepts_eta = "eta" in set(inspect.signature(self.scheduler.step).parameters.keys())
         is_ddim = isinstance(self.scheduler, DDIMSchedulerHIP)
         is_ddpm = isinstance(self.scheduler, DDPMSchedulerHIP)
+        if known is not None:
+            if known_mask is None:
+                raise ValueError("`known` needs `known_mask`")
+            if is_ddim and eta != 0.0:
+                raise NotImplementedError("guided DDIM sampling is eta = 0")
+            if not final_only:
+                raise NotImplementedError("guided sampling returns the final image only")
+            f = self.vae._cfg.downscale
+            lat_mask = latent_known_mask(known_mask, f)
+            sf = self.vae.config.scaling_factor
+            z0 = self.vae.encode(known.to(self.device, torch.float32)).latent_dist.mode() * sf
+            image = torch.empty((batch_size, self.vae._cfg.out_channels, shape[2] * f, shape[3] * f), device=self.device,
+                                dtype=torch.float32)
+            lat = self._guided_latents(self.vae, latents.float(), z0, lat_mask, num_inference_steps, jump_length, jump_n_sample,
+                                       generator, step_noise, known_noise, renoise_noise, fused, kwargs.get("check", True), out=image)
+            if not fused:
+                image = self.vae.decode(lat / sf).sample
+            if kwargs.get("return_latents", False):
+                return image, lat, z0, lat_mask.to(self.device)
+            return self._finish(image, output_type, return_dict)
         if fused and final_only and (not is_ddim or eta == 0.0):
             mode = _sampler_mode(self.scheduler)
             zs = None

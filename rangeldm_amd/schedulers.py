@@ -413,3 +413,75 @@ class DPMSolverMultistepSchedulerHIP(_SchedulerBase):
         self._have_x0 = True
         self._step_index = i + 1
         return SchedulerOutput(out) if return_dict else (out,)
+
+
+# ---- guided sampling on unconditional weights (RePaint-style known-region replacement) -----------------------------------
+def repaint_program(scheduler, num_inference_steps, jump_length=1, jump_n_sample=1):
+    """The row program of a guided sampler: (timesteps int64 [rows], table fp32 [rows][9]).
+
+    Let N = num_inference_steps and "remaining" the number of denoise steps still needed to reach the clean sample.  A row
+    denoises from remaining m + 1 to m with the scheduler's own step (columns 0-4: its `sampler_table` row of that timestep),
+    replaces the known region by the observation noised to the level the row ends at (columns 5-6: ka, kb = sqrt(a_prev),
+    sqrt(1 - a_prev), with the a_prev the scheduler itself uses -- 1 after the last timestep) and, when m - 1 is a non-negative
+    multiple of jump_length below N - jump_length that has been reached fewer than jump_n_sample times, re-noises up to remaining
+    m + jump_length (columns 7-8: ra, rb = sqrt(a_hi / a_lo), sqrt(1 - a_hi / a_lo); (1, 0) otherwise).  This is RePaint's
+    jump schedule (Lugmayr et al. 2022); with jump_n_sample = 1 the program is the scheduler's N timesteps.
+    rows = N + (jump_n_sample - 1) * jump_length * (number of jump points)."""
+    if isinstance(scheduler, DPMSolverMultistepSchedulerHIP):
+        raise NotImplementedError("guided sampling runs DDPM or DDIM (eta = 0) rows: DPM-Solver++ keeps an x0 history that means "
+                                  "nothing across a jump back up")
+    N, jl, jn = int(num_inference_steps), int(jump_length), int(jump_n_sample)
+    if N < 1 or jl < 1 or jn < 1:
+        raise ValueError("num_inference_steps, jump_length and jump_n_sample must be >= 1")
+    scheduler.set_timesteps(N)
+    ts = [int(t) for t in scheduler.timesteps]
+    ac = scheduler.alphas_cumprod.numpy().astype(np.float64)
+    visits = {}
+    out_t, rows = [], []
+    rem = N
+    while rem >= 1:
+        t = ts[N - rem]
+        m = rem - 1
+        row = [float(v) for v in np.asarray(scheduler._sampler_row(t, 0.0), dtype=np.float32)]
+        a_lo = float(scheduler._alphas(t)[1])               # the level this row ends at, before any re-noise
+        ra, rb = 1.0, 0.0
+        p = m - 1
+        if p >= 0 and p % jl == 0 and p < N - jl:
+            visits[p] = visits.get(p, 0) + 1
+            if visits[p] < jn:
+                a_hi = ac[ts[N - (m + jl)]]
+                ra, rb = math.sqrt(a_hi / a_lo), math.sqrt(1.0 - a_hi / a_lo)
+                m += jl
+        out_t.append(t)
+        rows.append(row + [math.sqrt(a_lo), math.sqrt(1.0 - a_lo), ra, rb])
+        rem = m
+    return (torch.tensor(out_t, dtype=torch.int64),
+            np.ascontiguousarray(np.asarray(rows, dtype=np.float64).astype(np.float32).reshape(-1, 9)))
+
+
+def guided_step(scheduler, row, model_output, sample, noise, known, mask, known_noise, renoise_noise):
+    """One row of a guided program outside the captured loop (rldm_sched_guided_step): the scheduler's step with row[0:5], the
+    known-region blend with row[5:7], the re-noise with row[7:9].  mask: [B, 1, W, H], 1 = known."""
+    if isinstance(scheduler, DPMSolverMultistepSchedulerHIP):
+        raise NotImplementedError("guided sampling runs DDPM or DDIM (eta = 0) rows")
+    mode = _lib.RLDM_SAMPLER_DDIM if isinstance(scheduler, DDIMSchedulerHIP) else _lib.RLDM_SAMPLER_DDPM
+    e = model_output.to(dtype=torch.float32).contiguous()
+
+    def dev(t):
+        return None if t is None else t.to(device=e.device, dtype=torch.float32).contiguous()
+
+    def ptr(t):
+        return C.c_void_p(t.data_ptr()) if t is not None else None
+    x, z0, m = dev(sample), dev(known), dev(mask)
+    nz = dev(noise) if row[4] != 0.0 else None
+    nk = dev(known_noise) if row[6] != 0.0 else None
+    nr = dev(renoise_noise) if (row[7] != 1.0 or row[8] != 0.0) else None
+    B, Cc = x.shape[0], x.shape[1]
+    spatial = x.numel() // (B * Cc)
+    if z0.shape != x.shape or m.numel() != B * spatial:
+        raise ValueError(f"known {tuple(z0.shape)} / mask {tuple(m.shape)} do not match the sample {tuple(x.shape)}")
+    out = torch.empty_like(x)
+    cf = (C.c_float * 9)(*[float(v) for v in row])
+    _lib.check(_lib.lib().rldm_sched_guided_step(mode, scheduler.prediction_code, cf, ptr(e), ptr(x), ptr(nz), ptr(z0), ptr(m), ptr(nk),
+                                                 ptr(nr), ptr(out), B, Cc, spatial, _lib.stream_ptr(e.device)), "guided scheduler step")
+    return out
