@@ -331,6 +331,32 @@ int rldm_chamfer_matrix(const float* x, const int32_t* x_offsets, int x_stride, 
  * skips column r of row r; a row left without a column gives +inf / -1.  NaN entries give unspecified results. */
 int rldm_matrix_row_argmin(const double* m, int rows, int cols, int exclude_diag, double* min_out, int32_t* arg_out,
                            void* stream);
+/* ---- Earth Mover's Distance (rangeldm_amd/csrc/emd.hip) ------------------------------------------------------------ */
+#define RLDM_EMD_RECT 0          /* every cloud of X against every cloud of Y */
+#define RLDM_EMD_SYMMETRIC 1     /* Y is X (the same buffers): j > i computed, mirrored, zero diagonal */
+#define RLDM_EMD_DIAGONAL 2      /* nx == ny: only the entries [i][i] (X_i against Y_i) are computed and written */
+#define RLDM_EMD_MAX_POINTS 2048
+#define RLDM_EMD_BID_CAP 2       /* return value: a pair reached the bid cap (rldm_last_error names it) */
+/* All-pairs EMD matrix between two sets of EQUAL-SIZE clouds (1 <= N <= 2048 points each), packed as rldm_chamfer_matrix
+ * takes them.  emd[i][j] = (1 / N) sum_i c[i][a(i)] for the assignment a found by an epsilon-scaling forward auction
+ * (Gauss-Seidel, one bid at a time, FIFO of unassigned bidders starting as 0 .. N-1, lowest object index on ties):
+ *   c[i][j] = sqrtf((dx*dx + dy*dy) + dz*dz) in fp32, no contraction, IEEE sqrt
+ *   bid of i:  w[j] = c[i][j] + p[j];  j1 = argmin (lowest j), w2 = min over j != j1 (w2 = w1 for N = 1);
+ *              p[j1] = (p[j1] + (w2 - w1)) + e;  i takes j1, j1's previous owner joins the FIFO tail
+ *   phases:    e_0 = 0.25f * (largest fp32 side of the joint bounding box of the two clouds), phase k bids with
+ *              max(e_k, eps), e_{k+1} = e_k * 0.25f, the phase with e_k <= eps is the last; prices kept, assignments reset
+ *   value:     fp64 sum of c[i][a(i)], i ascending, one add after the other, divided once by N
+ * so the value, the assignment (assign_out device int32 [nx][ny][N], a permutation), the prices (price_out device fp32
+ * [nx][ny][N]) and the number of bids (bids_out device int32 [nx][ny]) depend on the two clouds and eps alone and can be
+ * reproduced bit for bit on a CPU; the prices certify emd <= optimum + max_i slack_i (LP duality).  assign_out, price_out
+ * and bids_out may be NULL.  emd_out device fp64 [nx][ny].
+ * symmetric: RLDM_EMD_RECT, RLDM_EMD_SYMMETRIC (emd_out / bids_out mirrored with a zero diagonal; assign_out / price_out
+ * written for j > i only) or RLDM_EMD_DIAGONAL (entries off the diagonal are left untouched).
+ * A pair that has made 1024 * N bids with bidders still waiting stops: its value is NaN, the call returns
+ * RLDM_EMD_BID_CAP and rldm_last_error names the pair.  Other errors return 1.  The call synchronises the stream. */
+int rldm_emd_matrix(const float* x, const int32_t* x_offsets, int x_stride, int nx, const float* y, const int32_t* y_offsets,
+                    int y_stride, int ny, int symmetric, float eps, double* emd_out, int32_t* assign_out, float* price_out,
+                    int32_t* bids_out, void* stream);
 /* Range-image errors (ldm/convert_vae.py:236-247 MAE / PSNR; metrics/metrics/mae.py:45-117 range MAE): a, b device fp32
  * (B, C, W, H), C <= 8.  Per image, over the channels of channel_mask and the azimuth columns (w0 + k) mod W,
  * k in [0, w1 - w0) (0 <= w0 < W, w0 < w1 <= w0 + W: the window may wrap past the seam), with v -> v * scale[c] + shift[c]

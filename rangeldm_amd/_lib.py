@@ -10,6 +10,9 @@ LIB_PATH = os.environ.get("RLDM_LIB") or os.path.join(_HERE, "librangeldm_hip.so
 RLDM_MAX_LEVELS = 8
 # rldm_sampler_config::mode (RLDM_SAMPLER_*)
 RLDM_SAMPLER_DDIM, RLDM_SAMPLER_DDPM, RLDM_SAMPLER_DPMSOLVER = 0, 1, 2
+# rldm_emd_matrix: the `symmetric` argument, and the return value that reports a pair at the bid cap
+RLDM_EMD_RECT, RLDM_EMD_SYMMETRIC, RLDM_EMD_DIAGONAL = 0, 1, 2
+RLDM_EMD_BID_CAP = 2
 
 
 class Flag(enum.IntFlag):
@@ -162,6 +165,8 @@ PROTOTYPES = {
     # all-pairs Chamfer matrix of two sets of clouds, and the lowest-index row argmin the set metrics count with
     "rldm_chamfer_matrix": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "rldm_matrix_row_argmin": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    # all-pairs Earth Mover's Distance (epsilon-scaling auction) between equal-size clouds: emd, assignment, prices, bids
+    "rldm_emd_matrix": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, _P]),
     # MAE / PSNR of ldm/convert_vae.py:236-247 and the range MAE of metrics/metrics/mae.py:45-117
     "rldm_range_errors": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
                                     C.POINTER(C.c_float), C.c_int, C.c_int, _P, _P, _P]),

@@ -5,6 +5,7 @@
     python -m rangeldm_amd.evaluate inpainting --exp outputs/inpainting/generated [--cfg inpainting]
     python -m rangeldm_amd.evaluate chamfer A_DIR B_DIR
     python -m rangeldm_amd.evaluate generation GEN_DIR REF_DIR [--points 2048] [--limit N] [--seed 0] [--max-depth M]
+                                               [--emd [--emd-eps 0.0078125]]
 
 Every command prints one JSON object on stdout (`--json PATH` also writes it).  Under `torch.distributed.run` the work is
 sharded over the ranks and rank 0 reduces and prints.  The arithmetic runs in librangeldm_hip (rangeldm_amd/csrc/chamfer.hip
@@ -27,7 +28,10 @@ mean_x min_y |x - y|^2 + mean_y min_x |x - y|^2 over xyz.
                  matrices, every cloud cut to the points closer than --max-depth and sub-sampled to --points
                  (metrics.subsample with seed + file index); the BEV-histogram jsd / mmd of metrics.evaluate_folders on the
                  full clouds beside them.  Each rank computes a block of rows of each matrix; an entry does not depend on the
-                 block it was computed in, so the result is the same for any number of ranks.
+                 block it was computed in, so the result is the same for any number of ranks.  --emd adds MMD-EMD, COV-EMD
+                 and 1-NNA-EMD from the all-pairs Earth Mover's Distance matrices (metrics.emd_matrix: an auction that ends
+                 at --emd-eps metres); EMD is a one-to-one matching, so every cloud must then hold exactly --points points
+                 (at most 2 048) after the depth cut.
 
 Only the linear range normalisation (x * std + mean, every shipped config) is supported: `log` / `inverse` sensors raise
 NotImplementedError.  nuScenes `.bin` files carry no ring column, so they cannot be re-projected: nuScenes raises too.
@@ -83,6 +87,10 @@ def build_parser():
     g.add_argument("--max-depth", type=float, default=None, help="drop points at this distance from the sensor or farther")
     g.add_argument("--columns", type=int, default=4, choices=(4, 5),
                    help="float32 columns per point of the REFERENCE files (5: nuScenes sweeps); generated files have 4")
+    g.add_argument("--emd", action="store_true",
+                   help="also MMD-EMD / COV-EMD / 1-NNA-EMD (every cloud must hold --points points, at most 2048)")
+    g.add_argument("--emd-eps", type=float, default=2.0 ** -7,
+                   help="final epsilon of the EMD auction, metres: the matching cost is within about this of the optimum")
 
     for p in (v, *[sub.choices[k] for k in ("densification", "inpainting")], c, g):
         p.add_argument("--json", default=None, help="also write the result object to this file")
@@ -342,18 +350,29 @@ def _sum_matrix_over_ranks(m):
     return m
 
 
-def _matrix_over_ranks(xs, ys, rank, world):
-    """chamfer_matrix(xs, ys) (ys None: xs against itself) with the rows shared out over the ranks: every rank writes its
-    block of rows into a zero matrix and the sum over the ranks (adding zeros is exact) is the whole."""
+def _matrix_over_ranks(xs, ys, rank, world, matrix=None):
+    """matrix(xs, ys) (ys None: xs against itself; default metrics.chamfer_matrix) with the rows shared out over the ranks:
+    every rank writes its block of rows into a zero matrix and the sum over the ranks (adding zeros is exact) is the whole.
+    A `matrix` passed in need not be symmetric in its arguments (an auction's matching of (a, b) is not that of (b, a)
+    read backwards): its symmetric case takes entry [i][j], i < j, from (xs[i], xs[j]) as the one-process call does, and
+    mirrors it."""
     from .metrics import chamfer_matrix
+    mirror = matrix is not None and ys is None
+    matrix = matrix or chamfer_matrix
     if world == 1:
-        return chamfer_matrix(xs, ys)
+        return matrix(xs, ys)
     cols = xs if ys is None else ys
     full = torch.zeros((len(xs), len(cols)), dtype=torch.float64, device=xs[0].device)
     lo, hi = D.shard_range(len(xs), rank, world)
-    if hi > lo:
-        full[lo:hi] = chamfer_matrix(xs[lo:hi], cols)    # (a cloud against itself: every d^2 minimum is exactly 0)
-    return _sum_matrix_over_ranks(full)
+    if hi > lo and mirror:
+        full[lo:hi, lo:] = matrix(xs[lo:hi], xs[lo:])    # the columns left of the block lie below the diagonal
+    elif hi > lo:
+        full[lo:hi] = matrix(xs[lo:hi], cols)            # (a cloud against itself: every d^2 minimum is exactly 0)
+    full = _sum_matrix_over_ranks(full)
+    if mirror:
+        upper = torch.triu(full, 1)
+        full = upper + upper.t()
+    return full
 
 
 def load_generation_clouds(files, columns, points, seed, max_depth, device):
@@ -370,17 +389,45 @@ def load_generation_clouds(files, columns, points, seed, max_depth, device):
     return clouds
 
 
+def check_emd_args(a):
+    """`generation --emd`: what can be refused before a file is read."""
+    from .metrics import EMD_MAX_POINTS
+    if a.points > EMD_MAX_POINTS:
+        raise ValueError(f"--emd: --points {a.points} is above the {EMD_MAX_POINTS} points an EMD matching takes")
+    if not (a.emd_eps > 0.0 and math.isfinite(a.emd_eps)):
+        raise ValueError(f"--emd-eps must be positive and finite, got {a.emd_eps}")
+
+
+def require_emd_sizes(files, clouds, points):
+    """EMD is a one-to-one matching: every cloud must hold exactly `points` points; the first file that does not is named."""
+    for path, cloud in zip(files, clouds):
+        if int(cloud.shape[0]) != points:
+            raise ValueError(f"{path}: {int(cloud.shape[0])} points are left, --emd needs --points {points} in every cloud "
+                             f"(EMD is a one-to-one matching)")
+
+
 def cmd_generation(a, rank, world, dev):
     from .metrics import evaluate_folders, set_metrics
+    if a.emd:
+        check_emd_args(a)
     gen_files = sorted(glob.glob(os.path.join(a.gen_dir, "*.bin")))[:a.limit]
     ref_files = sorted(glob.glob(os.path.join(a.ref_dir, "*.bin")))[:a.limit]
     if not gen_files or not ref_files:
         raise FileNotFoundError(f"no .bin files in {a.gen_dir if not gen_files else a.ref_dir}")
     gen = load_generation_clouds(gen_files, 4, a.points, a.seed, a.max_depth, dev)
     ref = load_generation_clouds(ref_files, a.columns, a.points, a.seed, a.max_depth, dev)
+    if a.emd:
+        require_emd_sizes(gen_files, gen, a.points)
+        require_emd_sizes(ref_files, ref, a.points)
     result = {"task": "generation", "points": a.points}
     result.update(set_metrics(_matrix_over_ranks(gen, None, rank, world), _matrix_over_ranks(gen, ref, rank, world),
                               _matrix_over_ranks(ref, None, rank, world)))
+    if a.emd:
+        from .metrics import emd_matrix
+        emd = lambda xs, ys: emd_matrix(xs, ys, eps=a.emd_eps)
+        result.update(set_metrics(_matrix_over_ranks(gen, None, rank, world, emd), _matrix_over_ranks(gen, ref, rank, world, emd),
+                                  _matrix_over_ranks(ref, None, rank, world, emd), name="emd"))
+        result["emd_eps"] = a.emd_eps
     if rank == 0:                                        # the BEV histograms of the full clouds: cheap, one rank
         result.update(evaluate_folders(a.gen_dir, ref_files, nuscenes=a.columns == 5, limit=a.limit))
     return result

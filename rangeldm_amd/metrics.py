@@ -12,12 +12,19 @@ range_errors (MAE / PSNR / range MAE sums) and beam_upsample (the nearest / bicu
 Set-level generation metrics (same file): chamfer_matrix (every cloud of one set against every cloud of another),
 row_argmin (lowest index wins a tie) and generation_metrics (MMD-CD, COV-CD, 1-NNA-CD of Achlioptas et al. 2018 /
 Yang et al. 2019); set_metrics_host is the numpy statement of the three reductions.
+
+Earth Mover's Distance (rangeldm_amd/csrc/emd.hip): emd_matrix / emd_pairs, an epsilon-scaling auction between equal-size
+clouds that returns the assignment and the dual prices with the value; generation_metrics(emd=True) adds MMD-EMD / COV-EMD /
+1-NNA-EMD.
 """
 import ctypes as C
 
 import torch
 
 from . import _lib
+
+EMD_EPS = 2.0 ** -7         # metres: the auction's final epsilon (the value is within about this of the optimal matching)
+EMD_MAX_POINTS = 2048       # RLDM_EMD_MAX_POINTS
 
 
 def _dev_u32(h):
@@ -244,9 +251,10 @@ def _mean_exact(values):
     return math.fsum(v) / len(v)
 
 
-def set_metrics(cd_gg, cd_gr, cd_rr):
+def set_metrics(cd_gg, cd_gr, cd_rr, name="cd"):
     """MMD-CD, COV-CD and 1-NNA-CD from the three device fp64 Chamfer matrices: generated x generated (ng, ng), generated x
-    reference (ng, nr), reference x reference (nr, nr).  Ties go to the lowest index (row_argmin).
+    reference (ng, nr), reference x reference (nr, nr).  Ties go to the lowest index (row_argmin).  `name` names the
+    distance in the keys ("emd": mmd_emd, cov_emd, nna_emd, ...; the matrices are then emd_matrix's).
       mmd_cd   mean over reference clouds r of min_g CD[g][r]
       cov_cd   distinct reference clouds that are argmin_r CD[g][r] for some generated g, over nr
       nna_cd   leave-one-out 1-nearest-neighbour accuracy over the union ordered [G_0 .. G_{ng-1}, R_0 .. R_{nr-1}]: the
@@ -261,12 +269,12 @@ def set_metrics(cd_gg, cd_gr, cd_rr):
     _, nn = row_argmin(union, exclude_diag=True)
     same = (nn >= ng) == (torch.arange(ng + nr, device=nn.device) >= ng)
     right_gen, right_ref = int(same[:ng].sum()), int(same[ng:].sum())
-    return {"mmd_cd": _mean_exact(mins), "cov_cd": int(torch.unique(covered).numel()) / nr,
-            "nna_cd": (right_gen + right_ref) / (ng + nr), "nna_cd_gen": right_gen / ng, "nna_cd_ref": right_ref / nr,
-            "n_gen": ng, "n_ref": nr}
+    return {f"mmd_{name}": _mean_exact(mins), f"cov_{name}": int(torch.unique(covered).numel()) / nr,
+            f"nna_{name}": (right_gen + right_ref) / (ng + nr), f"nna_{name}_gen": right_gen / ng,
+            f"nna_{name}_ref": right_ref / nr, "n_gen": ng, "n_ref": nr}
 
 
-def set_metrics_host(cd_gg, cd_gr, cd_rr):
+def set_metrics_host(cd_gg, cd_gr, cd_rr, name="cd"):
     """The numpy statement of set_metrics (np.argmin returns the first minimum: the same lowest-index rule)."""
     import math
     import numpy as np
@@ -276,16 +284,121 @@ def set_metrics_host(cd_gg, cd_gr, cd_rr):
     np.fill_diagonal(union, np.inf)
     nn = union.argmin(1)
     same = (nn >= ng) == (np.arange(ng + nr) >= ng)
-    return {"mmd_cd": math.fsum(gr.min(0).tolist()) / nr, "cov_cd": len(set(gr.argmin(1).tolist())) / nr,
-            "nna_cd": int(same.sum()) / (ng + nr), "nna_cd_gen": int(same[:ng].sum()) / ng,
-            "nna_cd_ref": int(same[ng:].sum()) / nr, "n_gen": ng, "n_ref": nr}
+    return {f"mmd_{name}": math.fsum(gr.min(0).tolist()) / nr, f"cov_{name}": len(set(gr.argmin(1).tolist())) / nr,
+            f"nna_{name}": int(same.sum()) / (ng + nr), f"nna_{name}_gen": int(same[:ng].sum()) / ng,
+            f"nna_{name}_ref": int(same[ng:].sum()) / nr, "n_gen": ng, "n_ref": nr}
 
 
-def generation_metrics(gen, ref):
+def generation_metrics(gen, ref, emd=False, emd_eps=EMD_EPS):
     """MMD-CD / COV-CD / 1-NNA-CD (set_metrics) of a generated set against a reference set: lists of (n_i, >= 3) device
-    tensors or padded (N, P, >= 3) tensors.  Three Chamfer matrices: gen x gen and ref x ref (symmetric), gen x ref."""
+    tensors or padded (N, P, >= 3) tensors.  Three Chamfer matrices: gen x gen and ref x ref (symmetric), gen x ref.
+    emd=True adds the same three under the Earth Mover's Distance (mmd_emd, cov_emd, nna_emd, nna_emd_gen, nna_emd_ref)
+    from three emd_matrix calls; every cloud must then hold the same number of points, at most 2 048."""
     gs, rs = _clouds(gen, None, "gen"), _clouds(ref, None, "ref")
-    return set_metrics(chamfer_matrix(gs), chamfer_matrix(gs, rs), chamfer_matrix(rs))
+    if emd:
+        _emd_sizes(gs + rs)
+    out = set_metrics(chamfer_matrix(gs), chamfer_matrix(gs, rs), chamfer_matrix(rs))
+    if emd:
+        out.update(set_metrics(emd_matrix(gs, eps=emd_eps), emd_matrix(gs, rs, eps=emd_eps), emd_matrix(rs, eps=emd_eps),
+                               name="emd"))
+    return out
+
+
+# ---- Earth Mover's Distance: epsilon-scaling auction (rangeldm_amd/csrc/emd.hip) ----------------------------------------
+def _emd_sizes(clouds):
+    """The common point count of the clouds; ValueError (before the device) if they differ or exceed the kernel's size."""
+    sizes = sorted({int(c.shape[0]) for c in clouds})
+    if len(sizes) != 1:
+        raise ValueError(f"EMD is a one-to-one matching: every cloud must hold the same number of points, got clouds of "
+                         f"{sizes[0]} and of {sizes[-1]} points (sub-sample them to a common size first)")
+    if sizes[0] > EMD_MAX_POINTS:
+        raise ValueError(f"EMD is a one-to-one matching held in one wave's registers: at most {EMD_MAX_POINTS} points per "
+                         f"cloud, got {sizes[0]}")
+    return sizes[0]
+
+
+def _emd_eps(eps):
+    import math
+    eps = float(eps)
+    if not (eps > 0.0 and math.isfinite(eps)):
+        raise ValueError(f"eps must be positive and finite, got {eps}")
+    return eps
+
+
+def _emd_status(rc, message, what="rldm_emd_matrix"):
+    """Map rldm_emd_matrix's return value: 0 passes; RLDM_EMD_BID_CAP raises EmdBidCapError naming the pair; anything else is
+    the library's ordinary error."""
+    if rc == 0:
+        return
+    if rc == _lib.RLDM_EMD_BID_CAP:
+        raise EmdBidCapError(f"{what}: {message} (non-finite or pathological input? a larger eps needs fewer bids)")
+    raise RuntimeError(f"librangeldm_hip: {what} failed: {message}")
+
+
+class EmdBidCapError(RuntimeError):
+    """A pair of clouds reached the auction's bid cap (1024 bids per point); no partial value is returned."""
+
+
+def _emd_call(xp, xo, xk, nx, yp, yo, yk, ny, mode, eps, n, extras):
+    dev = xp.device
+    out = torch.zeros((nx, ny), dtype=torch.float64, device=dev)
+    asg = price = bids = None
+    if extras:
+        asg = torch.full((nx, ny, n), -1, dtype=torch.int32, device=dev)
+        price = torch.zeros((nx, ny, n), dtype=torch.float32, device=dev)
+        bids = torch.zeros((nx, ny), dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    rc = L.rldm_emd_matrix(xp.data_ptr(), xo.data_ptr(), xk, nx, yp.data_ptr(), yo.data_ptr(), yk, ny, mode, eps,
+                           out.data_ptr(), asg.data_ptr() if extras else None, price.data_ptr() if extras else None,
+                           bids.data_ptr() if extras else None, _lib.stream_ptr(dev))
+    if rc != 0:
+        msg = L.rldm_last_error()
+        _emd_status(rc, msg.decode() if msg else "unknown error")
+    return out, asg, price, bids
+
+
+def emd_matrix(x, y=None, eps=EMD_EPS, return_assignment=False, x_lengths=None, y_lengths=None):
+    """EMD[i][j] = (1 / N) min over one-to-one matchings a of sum_q |x_i[q] - y_j[a(q)]| (Euclidean, xyz only) for EVERY
+    cloud of x against every cloud of y, to within the auction's certificate: an fp64 device (nx, ny) tensor.  y=None is the
+    symmetric case (j > i computed and mirrored, zero diagonal).  Inputs as chamfer_matrix takes them, but EMD is a one-to-one
+    matching: every cloud must hold the same number of points N <= 2 048 (ValueError before the device otherwise).
+
+    The matching is found by an epsilon-scaling forward auction that ends at `eps` (metres): the value exceeds the optimum
+    by at most eps plus a few fp32 roundings, and the returned prices prove it.  Every step is a single
+    correctly rounded fp32 operation and the mean a fixed-order fp64 sum, so an entry depends on its two clouds and eps
+    alone: two calls, a block of rows, and the symmetric and rectangular calls agree bit for bit.
+
+    return_assignment=True returns (emd, assignment int32 (nx, ny, N), prices fp32 (nx, ny, N), bids int32 (nx, ny));
+    in the symmetric case the assignment and prices are filled for j > i only (-1 / 0 elsewhere).  A pair that reaches
+    1024 N bids raises EmdBidCapError naming it."""
+    xs = _clouds(x, x_lengths, "x")
+    ys = None if y is None else _clouds(y, y_lengths, "y")
+    if y is None and y_lengths is not None:
+        raise ValueError("y_lengths without y")
+    n = _emd_sizes(xs + (ys or []))
+    eps = _emd_eps(eps)
+    _lib.require_gpu()
+    xp, xo, xk = _pack(xs)
+    yp, yo, yk = (xp, xo, xk) if ys is None else _pack(ys)
+    nx, ny = len(xs), len(xs if ys is None else ys)
+    out, asg, price, bids = _emd_call(xp, xo, xk, nx, yp, yo, yk, ny, _lib.RLDM_EMD_SYMMETRIC if ys is None else
+                                      _lib.RLDM_EMD_RECT, eps, n, return_assignment)
+    return (out, asg, price, bids) if return_assignment else out
+
+
+def emd_pairs(x, y, eps=EMD_EPS, x_lengths=None, y_lengths=None):
+    """Per-pair EMD, x_i against y_i: an fp64 device tensor [n].  The same kernel as emd_matrix, run on the diagonal of the
+    matrix layout: entry i equals emd_matrix(x, y)[i][i] bit for bit."""
+    xs, ys = _clouds(x, x_lengths, "x"), _clouds(y, y_lengths, "y")
+    if len(xs) != len(ys):
+        raise ValueError(f"{len(xs)} x clouds against {len(ys)} y clouds")
+    n = _emd_sizes(xs + ys)
+    eps = _emd_eps(eps)
+    _lib.require_gpu()
+    xp, xo, xk = _pack(xs)
+    yp, yo, yk = _pack(ys)
+    out, _, _, _ = _emd_call(xp, xo, xk, len(xs), yp, yo, yk, len(ys), _lib.RLDM_EMD_DIAGONAL, eps, n, False)
+    return torch.diagonal(out).clone()
 
 
 def subsample(cloud, n, seed):
