@@ -443,3 +443,197 @@ def assert_banded_rel_l2_tokens(y, ref, tol, what=""):
     bands += [(f"image {b} head {h}", (b, slice(None), slice(8 * h, 8 * h + 8))) for b in range(B) for h in range(Cc // 8)]
     worst = [f"{name}: {e:.3g}" for name, sl in bands for e in [rel_l2(y[sl], ref[sl])] if not e <= tol]
     assert not worst, f"{what}: rel-L2 above {tol} on " + ", ".join(worst[:8]) + (f" (+{len(worst) - 8} more)" if len(worst) > 8 else "")
+
+
+# ---- GroupNorm operands whose statistics discriminate -------------------------------------------------------------------------------
+# GroupNorm is exact on operands built for it.  Every (image, group) of cat[x0, x1] has its own location m = j s (|j| <= 3) and scale s
+# (a power of two); every pixel of a channel takes one of two values, equally often, so the group mean and variance are known in closed
+# form and the normalised value z = (x - mean) / sd is one of {+-1/5, +-7/5} (even channel count per group: the 3-4-5 form) or +-1
+# (odd).  With gamma on a grid that carries the factor 5 and beta on the 1/4 grid, t = beta + gamma z is a 1/4-grid value per (channel,
+# pixel value), the same for every image -- normalisation undoes m and s -- and only channels whose act(t) keeps >= 0.1 bf16 ulp from a
+# rounding midpoint are kept.  A kernel's eps, rsqrt, fp32 variance and SiLU then cannot move bf16(act(t)): the map has one right answer.
+GN_SCALES = (1.0, 2.0, 4.0, 8.0)        # s[b, g]: spread over a factor of 8
+GN_TMAX = 4.0                           # |t| <= 4: every |act(t)| lies in [2^-4, 4] (silu(-4) = -0.0719, silu(-1.25) = -0.278, silu(-0.25) = -0.110)
+
+
+def bf16_ulp(v):
+    """bf16 unit in the last place at |v| (fp64 tensor, v != 0)."""
+    return torch.exp2(torch.floor(torch.log2(v.abs())) - 7)
+
+
+def bf16_midpoint_margin(v):
+    """distance of v (fp64, != 0) from the nearest bf16 rounding midpoint, in bf16 ulps at v (0.5: v is a bf16 value)."""
+    q = v.abs() / bf16_ulp(v)
+    return (q - torch.floor(q) - 0.5).abs()
+
+
+def _act64(t, silu):
+    return t * torch.sigmoid(t) if silu else t
+
+
+def gn_scales(B, groups, seed):
+    """-> (j, s) (B, groups) fp64: location m = j s and scale s of every (image, group).  s differs between neighbouring images
+    (b, (b + 1) % B) of a group and between neighbouring groups of an image, so (m, s) does."""
+    assert B == 1 or (B - 1) % len(GN_SCALES) != 0, "the last image would share its scales with the first"
+    g = torch.Generator().manual_seed(seed)
+    r = int(torch.randint(0, len(GN_SCALES), (1,), generator=g))
+    sidx = (torch.arange(B)[:, None] + torch.arange(groups)[None, :] + r) % len(GN_SCALES)
+    s = torch.tensor(GN_SCALES, dtype=torch.float64)[sidx]
+    j = torch.randint(-3, 4, (B, groups), generator=g).double()
+    if B > 1:
+        assert bool((s != s.roll(-1, 0)).all())
+    assert bool((s[:, 1:] != s[:, :-1]).all())
+    return j, s
+
+
+def gn_operands(B, C0, C1, W, H, groups=32, seed=0, silu=True):
+    """x0 (B, C0, W, H), x1 (B, C1, W, H) or None, gamma, beta (C0 + C1) fp32, and the exact GroupNorm(groups) (+ SiLU) map of cat[x0, x1].
+
+    Even channel count per group (cpg): with u = s / 4, the first cpg / 2 channels of a group sit at m + 3u and the rest at m - 3u (or the
+    other way round, seeded per (image, group)), each with spread +-4u: mean m, standard deviation exactly 5u, and the channels of one
+    group -- and the two halves of a group -- have different means, so statistics per channel, over half a group or over two groups land
+    elsewhere.  (First half / second half and not strictly alternating channels: alternating, half a group would have the group's own
+    statistics, and `cpg per source` of two equal sources is half a group.)  Odd cpg: the plain two-valued form m +- s is enough (mean m,
+    standard deviation s): no 3-4-5 split exists for an odd count, and a wrong image or a wrong group still changes s by a factor >= 2.
+    The two values occur W H / 2 times each per channel in a seeded, irregular pattern over (w, h).
+
+    -> dict(x0, x1, gamma, beta, expect = bf16(act(t)) as fp32, t (fp64, exact), mean, var (B, groups: closed forms), j, s, cpg,
+    unit = the bf16 ulp of the smallest |expect| (every expect value is a multiple of it), amax = max |expect|)."""
+    Cin, npx = C0 + C1, W * H
+    assert Cin % groups == 0 and npx % 2 == 0
+    cpg = Cin // groups
+    even = cpg % 2 == 0
+    g = torch.Generator().manual_seed(seed)
+    j, s = gn_scales(B, groups, seed + 1)
+    m = j * s
+    u = s / 4 if even else s
+    sd = 5 * u if even else u
+    grp = torch.arange(Cin) // cpg
+    if even:
+        flip = (torch.randint(0, 2, (B, groups), generator=g) * 2 - 1).double()
+        half = torch.where(torch.arange(Cin) % cpg < cpg // 2, 1.0, -1.0).double()
+        off = 3 * half[None, :] * flip[:, grp]                                  # (B, Cin): +-3
+    else:
+        off = torch.zeros(B, Cin, dtype=torch.float64)
+    r = torch.randint(0, 2, (B, Cin, npx // 2), generator=g, dtype=torch.int8)
+    pm = torch.cat([r, 1 - r], -1)[..., torch.randperm(npx, generator=g)].double() * 2 - 1       # +-1, balanced per channel
+    assert bool((pm.sum(-1) == 0).all())
+    dev = off[..., None] + (4 if even else 1) * pm                              # (x - m) / u
+    x = m[:, grp, None] + dev * u[:, grp, None]
+    assert torch.equal(x.float().to(torch.bfloat16).double(), x), "values not exact in bf16"
+    # ---- gamma, beta: per channel, redrawn until every value of t is safe ----
+    zs = torch.tensor([-1.4, -0.2, 0.2, 1.4] if even else [-1.0, 1.0], dtype=torch.float64)
+    gk = torch.tensor([-2.5, -1.25, 1.25, 2.5] if even else [-1.75, -1.25, -0.5, -0.25, 0.25, 0.5, 1.25, 1.75], dtype=torch.float64)
+    sd_min = float(sd.min())
+    shrink = sd_min / np.sqrt(sd_min * sd_min + 1e-5)                          # the largest effect of eps (<= 1e-5) on z
+    gamma = torch.zeros(Cin, dtype=torch.float64)
+    beta = torch.zeros(Cin, dtype=torch.float64)
+    todo = torch.ones(Cin, dtype=torch.bool)
+    for _ in range(200):
+        n = int(todo.sum())
+        if n == 0:
+            break
+        ga = gk[torch.randint(0, len(gk), (n,), generator=g)]
+        be = torch.randint(-8, 9, (n,), generator=g).double() / 4
+        t = be[:, None] + ga[:, None] * zs[None, :]
+        t1 = be[:, None] + ga[:, None] * zs[None, :] * shrink
+        ok = ((t != 0) & (t.abs() <= GN_TMAX)).all(-1)
+        tt = torch.where(t == 0, torch.ones_like(t), t)
+        a, a1 = _act64(tt, silu), _act64(torch.where(t == 0, tt, t1), silu)
+        ok &= (bf16_midpoint_margin(a) >= 0.1).all(-1) & (bf16_midpoint_margin(a1) >= 0.1).all(-1)
+        ok &= (a.float().to(torch.bfloat16) == a1.float().to(torch.bfloat16)).all(-1)
+        idx = todo.nonzero()[:, 0][ok]
+        gamma[idx], beta[idx] = ga[ok], be[ok]
+        todo[idx] = False
+    assert not bool(todo.any()), "no safe (gamma, beta) found for some channel"
+    z = dev / (5 if even else 1)
+    t = beta[None, :, None] + gamma[None, :, None] * z
+    assert torch.equal(t * 4, (t * 4).round()) and bool((t != 0).all()) and float(t.abs().max()) <= GN_TMAX
+    a = _act64(t, silu)
+    assert float(bf16_midpoint_margin(a).min()) >= 0.1
+    expect = a.float().to(torch.bfloat16).float()
+    lo = float(expect.abs().min())
+    assert lo >= 2.0 ** -4, "a value of the map below 2^-4: the exactness unit would shrink"
+    unit = 2.0 ** (np.floor(np.log2(lo)) - 7)
+    shape = (B, Cin, W, H)
+    x = x.float().view(shape)
+    return dict(x0=x[:, :C0].contiguous(), x1=x[:, C0:].contiguous() if C1 else None, gamma=gamma.float(), beta=beta.float(),
+                expect=expect.view(shape), t=t.view(shape), mean=m, var=sd * sd, j=j, s=s, cpg=cpg, groups=groups, silu=silu,
+                unit=unit, amax=float(expect.abs().max()))
+
+
+def gn_bands(Cout, groups):
+    """-> (nb, band of every output channel): nb = min(groups, Cout) bands of consecutive output channels."""
+    nb = min(groups, Cout)
+    return nb, torch.arange(Cout) * nb // Cout
+
+
+def gn_block_weights(Cout, Cin, k, groups, seed, density=1.0):
+    """weights (Cout, Cin, k, k) on the 2^-5 integer grid ({-4 .. 4} / 32), block-diagonal by group: the output channels form
+    min(groups, Cout) bands, and band j reads the input groups g with g % bands == j only (Cout >= groups: input group j itself).
+    A wrong output element then names its image and its input group(s)."""
+    nb, band = gn_bands(Cout, groups)
+    cpg = Cin // groups
+    w = int_grid((Cout, Cin, k, k), seed, -4, 4, exp=-5, density=density)
+    mask = (band[:, None] == (torch.arange(Cin) // cpg % nb)[None, :]).float()
+    return w * mask[:, :, None, None]
+
+
+def assert_bitexact_groups(y, expect, groups, what=""):
+    """assert_bitexact for a conv with gn_block_weights: a mismatch names the (image, input group) bands that differ."""
+    y, expect = y.detach().float().cpu(), expect.detach().float().cpu()
+    assert y.shape == expect.shape, f"{what}: shape {tuple(y.shape)} != {tuple(expect.shape)}"
+    bad = ~(y == expect)
+    if not bool(bad.any()):
+        return
+    nb, band = gn_bands(y.shape[1], groups)
+    per = torch.stack([bad[:, band == j].flatten(1).sum(1) for j in range(nb)], 1)          # (B, nb)
+    where = [f"image {b} input group {j}" + (f" (mod {nb})" if nb < groups else "") + f": {int(per[b, j])}" for b, j in per.nonzero().tolist()]
+    head = ", ".join(where[:8]) + (f" (+{len(where) - 8} more)" if len(where) > 8 else "")
+    try:
+        assert_bitexact(y, expect, what=what)
+    except AssertionError as e:
+        raise AssertionError(f"{e}; by (image, input group): {head}") from None
+
+
+def assert_banded_rel_l2_groups(y, ref, tol, groups, what=""):
+    """rel-L2 <= tol on every (image, GroupNorm group) block of a (B, C, W, H) tensor whose C channels form `groups` groups."""
+    y, ref = y.detach().double().cpu(), ref.detach().double().cpu()
+    B, Cc = y.shape[:2]
+    cg = Cc // groups
+    worst = [f"image {b} group {g}: {e:.3g}" for b in range(B) for g in range(groups)
+             for e in [rel_l2(y[b, g * cg:(g + 1) * cg], ref[b, g * cg:(g + 1) * cg])] if not e <= tol]
+    assert not worst, f"{what}: rel-L2 above {tol} on " + ", ".join(worst[:8]) + (f" (+{len(worst) - 8} more)" if len(worst) > 8 else "")
+
+
+def gn_shift_scale_tokens(o, seed):
+    """selective_operands(fused=True) has every GroupNorm group of x at mean 0, variance 1.  -> x' = x s[b, g] + j[b, g] s[b, g]
+    (gn_scales: powers of two, other (j, s) than the neighbouring image / group).  Normalisation undoes both, so q, k, v and the output
+    are those of x.  The guards, asserted here: x' is exact in bf16 with exact fp32 channel sums; the kernels' folded weights
+    W' = bf16(w32 a), a = gamma rsqrt(s^2 + eps) = (1 + d) / s with |d| <= eps / 2 + 8 fp32 ulps, stay on the bf16 values w32 / s; and the
+    folded bias b' = b - sum_c w32[r, c] j (1 + d) misses its exact value by less than 0.1 bf16 ulp of the smallest q / k / v value of
+    that row (rows that produce 0 have no weights)."""
+    x = o["x"]
+    B, L, C = x.shape
+    G = o["groups"]
+    cpg = C // G
+    j, s = gn_scales(B, G, seed)
+    grp = torch.arange(C) // cpg
+    xs = (x.double() * s[:, None, grp] + (j * s)[:, None, grp])
+    assert torch.equal(xs.float().to(torch.bfloat16).double(), xs) and float((xs * xs).sum(1).max()) < 2 ** 24
+    xg = xs.view(B, L, G, cpg)
+    assert torch.equal(xg.mean((1, 3)), j * s) and torch.equal((xg * xg).mean((1, 3)) - (j * s) ** 2, s * s)
+    scale = torch.tensor([QS_INFER] * C + [1.0] * 2 * C, dtype=torch.float32)
+    w32 = (o["wqkv"] * scale[:, None]).to(torch.bfloat16).float()
+    dmax = o["eps"] / 2 + 8 * 2.0 ** -24
+    for sv in GN_SCALES:
+        for d in (-dmax, dmax):
+            a = torch.tensor(float(np.float32((1 + d) / sv)))
+            assert torch.equal((w32 * a).to(torch.bfloat16).float(), w32 / sv)
+    err = 3 * w32.double().abs().sum(1) * (dmax + C * 2.0 ** -24)                      # (3C,)
+    vals = torch.cat([o["qh"], o["k"], o["v"]], -1).double().abs().flatten(0, 1)         # (B L, 3C)
+    lo = torch.where(vals == 0, torch.full_like(vals, float("inf")), vals).amin(0)
+    assert bool((w32[(vals == 0).any(0)] == 0).all()), "a row that produces 0 carries weights"
+    live = torch.isfinite(lo) & (err > 0)
+    assert bool((err[live] <= 0.1 * bf16_ulp(lo[live])).all()), "the folded bias could move a q / k / v value"
+    return xs.float()

@@ -331,3 +331,102 @@ def test_fused_norm_conv_forward_backward(B, C0, C1, N, W, H, taps, silu):
         assert rel(rows2.cpu(), dy.sum((2, 3))) < 3e-3 and rel(tot2.cpu(), dy.sum((0, 2, 3))) < 3e-3
     else:
         assert Cin % 64 != 0
+
+
+# ---- GroupNorm statistics that differ per image and per group ---------------------------------------------------------------------------
+# The tests above draw every image and channel from one distribution, so every (image, group) has the same mean and variance to within
+# sampling noise and a kernel that reads another image's or group's statistics stays inside the tolerance.  Here each (image, group)
+# has its own location and scale (hip_util.gn_scales: powers of two over a factor of 8, other values than both neighbours).
+def _spread(x, groups, seed):
+    from tests.hip_util import gn_scales
+    B, Cc = x.shape[:2]
+    j, s = gn_scales(B, groups, seed)
+    grp = torch.arange(Cc) // (Cc // groups)
+    return x * s[:, grp, None, None].float() + (j * s)[:, grp, None, None].float()
+
+
+def _gn_reference(x, g, b, eps, silu):
+    """-> (act(GN(x)), t = the affine output with its gradient retained, xhat): dgamma_c = sum dt xhat and dbeta_c = sum dt over (image, pixel)."""
+    xhat = F.group_norm(x, 32, None, None, eps)
+    t = xhat * g[None, :, None, None] + b[None, :, None, None]
+    t.retain_grad()
+    return (F.silu(t) if silu else t), t, xhat
+
+
+def _assert_per_channel(got, ref, addends, tol, what):
+    """fp32 sums over (image, pixel): every channel within tol of its own sum of absolute addends (not of the whole vector's norm)."""
+    bound = tol * addends.double().abs().sum((0, 2, 3))
+    err = (got.double().cpu() - ref.double()).abs()
+    bad = (err > bound).nonzero()[:, 0].tolist()
+    assert not bad, f"{what}: channels {bad[:8]} off by {[float(err[c]) for c in bad[:8]]} (bound {[float(bound[c]) for c in bad[:8]]})"
+
+
+@pytest.mark.parametrize("B,C,W,H,silu", [(3, 64, 16, 8, True), (3, 32, 8, 4, False), (2, 96, 8, 4, True), (3, 512, 4, 2, True),
+                                            (2, 128, 256, 16, True)])       # 2 / 1 / 3 / 16 channels per group; the slab kernels
+def test_group_norm_spread_statistics(B, C, W, H, silu):
+    from rangeldm_amd import train_ops as T
+    from tests.hip_util import assert_banded_rel_l2_groups
+    x = _spread(rnd(B, C, W, H, seed=1), 32, 21).requires_grad_()
+    g = (1 + 0.3 * rnd(C, seed=2)).requires_grad_()
+    b = (0.2 * rnd(C, seed=3)).requires_grad_()
+    ref, t, xhat = _gn_reference(x, g, b, 1e-5, silu)
+    assert torch.allclose(ref, o_ops.group_norm_silu(x, g, b, 32, 1e-5, silu), rtol=1e-6, atol=1e-6)
+    dy = rnd(B, C, W, H, seed=4)
+    ref.backward(dy)
+    xd = nhwc(x.detach())
+    y, stats = T.gn_forward(xd, g.detach().cuda(), b.detach().cuda(), 32, 1e-5, silu)
+    case = (B, C, W, H, silu)
+    assert rel(nchw(y), ref.detach()) < TOL_F32
+    assert_banded_rel_l2_groups(nchw(y), ref.detach(), TOL_F32, 32, what=f"gn_forward {case}")
+    dg, db = torch.zeros(C).cuda(), torch.zeros(C).cuda()
+    dx = T.gn_backward(xd, nhwc(dy), stats, g.detach().cuda(), b.detach().cuda(), 32, silu, dg, db)
+    assert rel(nchw(dx), x.grad) < 1e-4
+    assert_banded_rel_l2_groups(nchw(dx), x.grad, 1e-4, 32, what=f"gn_backward dx {case}")
+    _assert_per_channel(dg, g.grad, t.grad * xhat.detach(), 1e-4, f"gn_backward dgamma {case}")
+    _assert_per_channel(db, b.grad, t.grad, 1e-4, f"gn_backward dbeta {case}")
+    assert rel(dg.cpu(), g.grad) < 1e-4 and rel(db.cpu(), b.grad) < 1e-4
+
+
+@pytest.mark.parametrize("B,C0,C1,N,W,H,taps,silu", [
+    (8, 256, 0, 256, 32, 2, 9, True),        # split-K
+    (4, 128, 0, 128, 256, 16, 9, True),      # halo tile
+    (8, 256, 128, 256, 64, 4, 9, True),      # two sources, groups straddle the seam
+])
+def test_fused_norm_conv_spread_statistics(B, C0, C1, N, W, H, taps, silu):
+    """test_fused_norm_conv_forward_backward's forward and data gradient, one case per kernel family, with statistics that differ per
+    (image, group): the output and dx per band, dgamma / dbeta per channel."""
+    from rangeldm_amd import train_ops as T
+    from tests.hip_util import assert_banded_rel_l2_groups
+    k = 3 if taps == 9 else 1
+    Cin = C0 + C1
+    x = _spread(rnd(B, Cin, W, H, seed=1), 32, 22).requires_grad_()
+    g = (1 + 0.3 * rnd(Cin, seed=2)).requires_grad_()
+    b = (0.2 * rnd(Cin, seed=3)).requires_grad_()
+    w = (rnd(N, Cin, k, k, seed=4) / (Cin * taps) ** 0.5).requires_grad_()
+    bias, row, res = rnd(N, seed=5), rnd(B, N, seed=6), rnd(B, N, W, H, seed=7)
+    h, t, xhat = _gn_reference(x, g, b, 1e-5, silu)
+    ref = o_ops.circ_conv2d(h, w, bias, 1, 1 if taps == 9 else 0) + row[:, :, None, None] + res
+    dy = rnd(*ref.shape, seed=8)
+    ref.backward(dy)
+    xd = nhwc(x.detach())
+    srcs = [T.Src(xd[..., :C0].contiguous())] + ([T.Src(xd[..., C0:].contiguous())] if C1 else [])
+    for s in srcs:
+        s.cs = T.chan_stats(s.t)
+    gn = T.GN(g.detach().cuda(), b.detach().cuda(), silu, 32, 1e-5)
+    wf, wt = T.pack_weights(w.detach().cuda(), taps)
+    assert T.conv_fused_ok(srcs, N, taps, gn=gn, want_stats=True)
+    y, cs = T.conv_fused(srcs, wf, N, taps, gn=gn, bias=bias.cuda(), rowadd=row.cuda(), res=nhwc(res), want_stats=True)
+    case = (B, C0, C1, N, W, H, taps, silu)
+    assert rel(nchw(y), ref.detach()) < TOL_MM
+    assert_banded_rel_l2(nchw(y), ref.detach(), TOL_MM, what=f"conv_fused {case}")
+    dsrc = [T.Src(nhwc(dy))]
+    assert T.conv_fused_ok(dsrc, Cin, taps, gsrcs=srcs, ggn=gn)
+    dz, gs = T.conv_fused(dsrc, wt, Cin, taps, gsrcs=srcs, ggn=gn)
+    dg, db = torch.zeros(Cin).cuda(), torch.zeros(Cin).cuda()
+    dsts = T.gn_backward_apply(dz, srcs, gs, gn, dg, db)
+    dx = torch.cat([nchw(d) for d in dsts], 1)
+    assert rel(dx, x.grad) < TOL_MM
+    assert_banded_rel_l2_groups(dx, x.grad, TOL_MM, 32, what=f"gn_backward_apply dx {case}")
+    _assert_per_channel(dg, g.grad, t.grad * xhat.detach(), TOL_MM, f"dgamma {case}")
+    _assert_per_channel(db, b.grad, t.grad, TOL_MM, f"dbeta {case}")
+    assert rel(dg.cpu(), g.grad) < TOL_MM and rel(db.cpu(), b.grad) < TOL_MM
