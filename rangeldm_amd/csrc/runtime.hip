@@ -115,236 +115,154 @@ struct ConvLayer {
     std::vector<float> sc_w;
     struct Packed {
         DevBuf w, bias;
-        int ntile_n = 0, Cin_pad = 0;
+        int Cin_pad = 0;
     };
-    std::map<std::pair<int, int>, std::unique_ptr<Packed>> packed;   // (BN, CK) -> image
+    // the order a kernel family reads its weights in, and the integers that layout is parameterised by:
+    // Igemm (BN, CK), Stream (k-groups), Frag / FragNoRes (channels per tile, k-groups)
+    enum class WeightLayout { Igemm, Stream, C16, SubPixel, Frag, FragNoRes };
+    using WeightKey = std::tuple<WeightLayout, int, int>;
+    std::map<WeightKey, std::unique_ptr<Packed>> packed;
 
-    // [ntile_n][Cin_pad/CK * taps + R/CK][BN][CK + 8] bf16; channel rows >= Cout and channels >= Cin are zero
-    int get_packed(int BN, int CK, int Cin_pad, Packed** out) {
-        auto key = std::make_pair(BN, CK);
+    float weight(int n, int c, int tap) const { return w[((size_t)n * Cin + c) * (ksize * ksize) + tap]; }
+    // residual phase: row n of the 1x1 shortcut over the block input, or of the identity
+    float res_weight(int n, int c) const { return sc_identity ? (c == n ? 1.f : 0.f) : sc_w[(size_t)n * R + c]; }
+
+    // the image under `key`: built on first use by fill(img, bias) (bias arrives as the layer's own, unpadded), uploaded and kept
+    template <class Fill> int cached(const WeightKey& key, int Cin_pad, Packed** out, Fill&& fill) {
         auto it = packed.find(key);
         if (it != packed.end()) {
             RLDM_REQUIRE(it->second->Cin_pad == Cin_pad, "conv layer reused with a different channel padding");
             *out = it->second.get();
             return 0;
         }
-        RLDM_REQUIRE(R % CK == 0, "conv " + name + ": residual channels not a multiple of the channel chunk");
-        const int taps = ksize * ksize;
-        const int ntile = (Cout + BN - 1) / BN;
-        const int ncc = Cin_pad / CK, ncb = R / CK;
-        const int RSE = CK + 8;
-        const size_t stages = (size_t)ncc * taps + ncb;
-        std::vector<bf16_t> img((size_t)ntile * stages * BN * RSE, 0);
-        for (int n = 0; n < Cout; ++n) {
-            const int nt = n / BN, nr = n % BN;
-            for (int c = 0; c < Cin; ++c) {
-                const int cc = c / CK, ck = c % CK;
-                for (int tap = 0; tap < taps; ++tap) {
-                    const float v = w[((size_t)n * Cin + c) * taps + tap];
-                    img[(((size_t)nt * stages + (size_t)cc * taps + tap) * BN + nr) * RSE + ck] = f32_to_bf16(v);
-                }
-            }
-            for (int c = 0; c < R; ++c) {
-                const float v = sc_identity ? (c == n ? 1.f : 0.f) : sc_w[(size_t)n * R + c];
-                img[(((size_t)nt * stages + (size_t)ncc * taps + c / CK) * BN + nr) * RSE + c % CK] = f32_to_bf16(v);
-            }
-        }
-        std::vector<float> bias((size_t)ntile * BN, 0.f);
-        for (int n = 0; n < Cout; ++n) bias[n] = b[n];
+        std::vector<bf16_t> img;
+        std::vector<float> bias = b;
+        if (fill(img, bias)) return 1;
         auto pk = std::make_unique<Packed>();
         if (upload(pk->w, img.data(), img.size() * sizeof(bf16_t))) return 1;
         if (upload(pk->bias, bias.data(), bias.size() * sizeof(float))) return 1;
-        pk->ntile_n = ntile;
         pk->Cin_pad = Cin_pad;
         *out = pk.get();
         packed[key] = std::move(pk);
         return 0;
+    }
+
+    // conv_igemm.hip image: [ntile_n][Cin_pad/CK * taps + R/CK][BN][CK + 8] bf16; channel rows >= Cout and channels >= Cin are
+    // zero; bias padded to ntile_n * BN
+    int get_packed(int BN, int CK, int Cin_pad, Packed** out) {
+        return cached({WeightLayout::Igemm, BN, CK}, Cin_pad, out, [&](std::vector<bf16_t>& img, std::vector<float>& bias) {
+            RLDM_REQUIRE(R % CK == 0, "conv " + name + ": residual channels not a multiple of the channel chunk");
+            const int taps = ksize * ksize;
+            const int ntile = (Cout + BN - 1) / BN;
+            const int ncc = Cin_pad / CK, ncb = R / CK;
+            const int RSE = CK + 8;
+            const size_t stages = (size_t)ncc * taps + ncb;
+            img.assign((size_t)ntile * stages * BN * RSE, 0);
+            auto at = [&](int n, size_t stage, int ck) -> bf16_t& { return img[(((size_t)(n / BN) * stages + stage) * BN + n % BN) * RSE + ck]; };
+            for (int n = 0; n < Cout; ++n) {
+                for (int c = 0; c < Cin; ++c)
+                    for (int tap = 0; tap < taps; ++tap) at(n, (size_t)(c / CK) * taps + tap, c % CK) = f32_to_bf16(weight(n, c, tap));
+                for (int c = 0; c < R; ++c) at(n, (size_t)ncc * taps + c / CK, c % CK) = f32_to_bf16(res_weight(n, c));
+            }
+            bias.resize((size_t)ntile * BN, 0.f);
+            return 0;
+        });
     }
 
     // conv_stream.hip image: MFMA A-fragment order, one contiguous stream of 1 KiB k-steps per (32-channel tile, k-group):
     // [Cout/32][KG][Cin_pad/64 chunks x 9 taps x 4/KG k-steps, then R/64 chunks x 4/KG k-steps][64 lanes][8 bf16] + 32 KiB
     // of zeros (the ring's read-ahead past the last stream: up to 18 fragments of 1 KiB in the 64-pixel instance); k-group kg owns the k-steps [kg*4/KG, (kg+1)*4/KG) of every
-    // tap of a chunk; lane l holds channel 32*t + (l & 31), k = 8*(l >> 5) .. +8 of the step
+    // tap of a chunk; lane l holds channel 32*t + (l & 31), k = 8*(l >> 5) .. +8 of the step; bias padded to whole tiles
     int get_streampacked(int Cin_pad, int KG, Packed** out) {
-        auto key = std::make_pair(-2, KG);
-        auto it = packed.find(key);
-        if (it != packed.end()) {
-            RLDM_REQUIRE(it->second->Cin_pad == Cin_pad, "conv layer reused with a different channel padding");
-            *out = it->second.get();
-            return 0;
-        }
-        RLDM_REQUIRE(ksize == 3 && (Cout % 32 == 0 || Cout < 32) && Cin_pad % 64 == 0 && R % 64 == 0, "conv " + name + ": not stream-packable");
-        const int SPT = 4 / KG, NCC = Cin_pad / 64, NCB = R / 64, nsteps = (NCC * 9 + NCB) * SPT;
-        const int ntile32 = (Cout + 31) / 32;        // (fewer than 32 output channels -- conv_regw.hip's conv_out: one tile, zero rows and zero bias behind them)
-        std::vector<bf16_t> img((size_t)ntile32 * KG * nsteps * 512 + 16384, 0);
-        auto at = [&](int n, int ks, int step, int k) -> bf16_t& {      // ks: 16-channel group within the 64-channel chunk
-            const size_t stream = (size_t)(n / 32) * KG + ks / SPT;
-            return img[((stream * nsteps + step + ks % SPT) * 64 + (k / 8) * 32 + n % 32) * 8 + k % 8];
-        };
-        for (int n = 0; n < Cout; ++n) {
-            for (int c = 0; c < Cin; ++c)
-                for (int tap = 0; tap < 9; ++tap)
-                    at(n, (c % 64) / 16, ((c / 64) * 9 + tap) * SPT, c % 16) = f32_to_bf16(w[((size_t)n * Cin + c) * 9 + tap]);
-            for (int c = 0; c < R; ++c) {
-                const float v = sc_identity ? (c == n ? 1.f : 0.f) : sc_w[(size_t)n * R + c];
-                at(n, (c % 64) / 16, (NCC * 9 + c / 64) * SPT, c % 16) = f32_to_bf16(v);
+        return cached({WeightLayout::Stream, KG, 0}, Cin_pad, out, [&](std::vector<bf16_t>& img, std::vector<float>& bias) {
+            RLDM_REQUIRE(ksize == 3 && (Cout % 32 == 0 || Cout < 32) && Cin_pad % 64 == 0 && R % 64 == 0, "conv " + name + ": not stream-packable");
+            const int SPT = 4 / KG, NCC = Cin_pad / 64, NCB = R / 64, nsteps = (NCC * 9 + NCB) * SPT;
+            const int ntile32 = (Cout + 31) / 32;        // (fewer than 32 output channels -- conv_regw.hip's conv_out: one tile, zero rows and zero bias behind them)
+            img.assign((size_t)ntile32 * KG * nsteps * 512 + 16384, 0);
+            auto at = [&](int n, int ks, int step, int k) -> bf16_t& {      // ks: 16-channel group within the 64-channel chunk
+                const size_t stream = (size_t)(n / 32) * KG + ks / SPT;
+                return img[((stream * nsteps + step + ks % SPT) * 64 + (k / 8) * 32 + n % 32) * 8 + k % 8];
+            };
+            for (int n = 0; n < Cout; ++n) {
+                for (int c = 0; c < Cin; ++c)
+                    for (int tap = 0; tap < 9; ++tap) at(n, (c % 64) / 16, ((c / 64) * 9 + tap) * SPT, c % 16) = f32_to_bf16(weight(n, c, tap));
+                for (int c = 0; c < R; ++c) at(n, (c % 64) / 16, (NCC * 9 + c / 64) * SPT, c % 16) = f32_to_bf16(res_weight(n, c));
             }
-        }
-        auto pk = std::make_unique<Packed>();
-        if (upload(pk->w, img.data(), img.size() * sizeof(bf16_t))) return 1;
-        std::vector<float> bias((size_t)ntile32 * 32, 0.f);
-        for (int n = 0; n < Cout; ++n) bias[n] = b[n];
-        if (upload(pk->bias, bias.data(), bias.size() * sizeof(float))) return 1;
-        pk->ntile_n = 0;
-        pk->Cin_pad = Cin_pad;
-        *out = pk.get();
-        packed[key] = std::move(pk);
-        return 0;
+            bias.resize((size_t)ntile32 * 32, 0.f);
+            return 0;
+        });
     }
 
     // conv_regw.hip, conv_c16_kernel (the input layer: <= 16 input channels): [Cout / 32][9 taps][64 lanes][8 bf16] -- lane l of a fragment holds
     // channel 32 t + (l & 31), input channels 8 (l >> 5) .. + 8
     int get_c16packed(Packed** out) {
-        auto key = std::make_pair(-4, 1);
-        auto it = packed.find(key);
-        if (it != packed.end()) {
-            *out = it->second.get();
+        return cached({WeightLayout::C16, 0, 0}, 16, out, [&](std::vector<bf16_t>& img, std::vector<float>&) {
+            RLDM_REQUIRE(ksize == 3 && Cout % 32 == 0 && Cin <= 16 && R == 0, "conv " + name + ": not a 16-channel input layer");
+            img.assign((size_t)(Cout / 32) * 9 * 512, 0);
+            for (int n = 0; n < Cout; ++n)
+                for (int c = 0; c < Cin; ++c)
+                    for (int tap = 0; tap < 9; ++tap)
+                        img[(((size_t)(n / 32) * 9 + tap) * 64 + (c / 8) * 32 + n % 32) * 8 + c % 8] = f32_to_bf16(weight(n, c, tap));
             return 0;
-        }
-        RLDM_REQUIRE(ksize == 3 && Cout % 32 == 0 && Cin <= 16 && R == 0, "conv " + name + ": not a 16-channel input layer");
-        std::vector<bf16_t> img((size_t)(Cout / 32) * 9 * 512, 0);
-        for (int n = 0; n < Cout; ++n)
-            for (int c = 0; c < Cin; ++c)
-                for (int tap = 0; tap < 9; ++tap)
-                    img[(((size_t)(n / 32) * 9 + tap) * 64 + (c / 8) * 32 + n % 32) * 8 + c % 8] = f32_to_bf16(w[((size_t)n * Cin + c) * 9 + tap]);
-        auto pk = std::make_unique<Packed>();
-        if (upload(pk->w, img.data(), img.size() * sizeof(bf16_t))) return 1;
-        if (upload(pk->bias, b.data(), b.size() * sizeof(float))) return 1;
-        pk->ntile_n = 0;
-        pk->Cin_pad = 16;
-        *out = pk.get();
-        packed[key] = std::move(pk);
-        return 0;
+        });
     }
 
     // conv_stream.hip, sub-pixel form of nearest x2 + 3x3 (conv_stream_body.h, SUB): per (32-channel tile, parity pw * 2 + ph) one stream
     // [Cin_pad/64 chunks][2 x 2 taps (w-major)][4 k-steps][64 lanes][8 bf16] of SUMMED weights -- along each axis parity 0 reads inputs
     // (x - 1, x) through (k[0], k[1] + k[2]), parity 1 reads (x, x + 1) through (k[0] + k[1], k[2]); summed in fp32, rounded once
     int get_subpixpacked(int Cin_pad, Packed** out) {
-        auto key = std::make_pair(-3, 1);
-        auto it = packed.find(key);
-        if (it != packed.end()) {
-            RLDM_REQUIRE(it->second->Cin_pad == Cin_pad, "conv layer reused with a different channel padding");
-            *out = it->second.get();
+        return cached({WeightLayout::SubPixel, 0, 0}, Cin_pad, out, [&](std::vector<bf16_t>& img, std::vector<float>&) {
+            RLDM_REQUIRE(ksize == 3 && Cout % 32 == 0 && Cin_pad % 64 == 0 && R == 0, "conv " + name + ": not sub-pixel-packable");
+            const int NCC = Cin_pad / 64, nsteps = NCC * 16;
+            img.assign((size_t)(Cout / 32) * 4 * nsteps * 512 + 16384, 0);
+            static const int lo[2][2] = {{0, 1}, {0, 2}}, hi[2][2] = {{0, 2}, {1, 2}};    // [parity][tap]: original taps lo .. hi summed
+            for (int n = 0; n < Cout; ++n)
+                for (int c = 0; c < Cin; ++c)
+                    for (int pw = 0; pw < 2; ++pw)
+                        for (int ph = 0; ph < 2; ++ph)
+                            for (int i = 0; i < 2; ++i)
+                                for (int j = 0; j < 2; ++j) {
+                                    float v = 0.f;
+                                    for (int a = lo[pw][i]; a <= hi[pw][i]; ++a)
+                                        for (int bb = lo[ph][j]; bb <= hi[ph][j]; ++bb) v += weight(n, c, a * 3 + bb);
+                                    const size_t stream = (size_t)(n / 32) * 4 + pw * 2 + ph;
+                                    const int step = ((c / 64) * 4 + i * 2 + j) * 4 + (c % 64) / 16, k = c % 16;
+                                    img[((stream * nsteps + step) * 64 + (k / 8) * 32 + n % 32) * 8 + k % 8] = f32_to_bf16(v);
+                                }
             return 0;
-        }
-        RLDM_REQUIRE(ksize == 3 && Cout % 32 == 0 && Cin_pad % 64 == 0 && R == 0, "conv " + name + ": not sub-pixel-packable");
-        const int NCC = Cin_pad / 64, nsteps = NCC * 16;
-        std::vector<bf16_t> img((size_t)(Cout / 32) * 4 * nsteps * 512 + 16384, 0);
-        static const int lo[2][2] = {{0, 1}, {0, 2}}, hi[2][2] = {{0, 2}, {1, 2}};    // [parity][tap]: original taps lo .. hi summed
-        for (int n = 0; n < Cout; ++n)
-            for (int c = 0; c < Cin; ++c)
-                for (int pw = 0; pw < 2; ++pw)
-                    for (int ph = 0; ph < 2; ++ph)
-                        for (int i = 0; i < 2; ++i)
-                            for (int j = 0; j < 2; ++j) {
-                                float v = 0.f;
-                                for (int a = lo[pw][i]; a <= hi[pw][i]; ++a)
-                                    for (int bb = lo[ph][j]; bb <= hi[ph][j]; ++bb) v += w[((size_t)n * Cin + c) * 9 + a * 3 + bb];
-                                const size_t stream = (size_t)(n / 32) * 4 + pw * 2 + ph;
-                                const int step = ((c / 64) * 4 + i * 2 + j) * 4 + (c % 64) / 16, k = c % 16;
-                                img[((stream * nsteps + step) * 64 + (k / 8) * 32 + n % 32) * 8 + k % 8] = f32_to_bf16(v);
-                            }
-        auto pk = std::make_unique<Packed>();
-        if (upload(pk->w, img.data(), img.size() * sizeof(bf16_t))) return 1;
-        if (upload(pk->bias, b.data(), b.size() * sizeof(float))) return 1;
-        pk->ntile_n = 0;
-        pk->Cin_pad = Cin_pad;
-        *out = pk.get();
-        packed[key] = std::move(pk);
-        return 0;
+        });
     }
 
-    // conv_small.hip image: MFMA A-fragment order, one contiguous stream of 1 KiB k-steps per (32-channel tile, k-group):
-    // [Cout/32][KG][taps*CPT main steps (tap-major) + RPT residual steps][64 lanes][8 bf16] + one zero fragment; k-group kg
-    // owns the 16-channel groups kg, kg + KG, ... of every tap; lane l of a step holds channel 32*t + (l & 31),
-    // k = 8*(l >> 5) .. +8.  `no_res`: the (identity) residual is added by the kernel's epilogue, not multiplied here.
-    int get_fragpacked(int Cin_pad, int KG, bool no_res, Packed** out) {
-        auto key = std::make_pair(no_res ? -1 : 0, KG);
-        auto it = packed.find(key);
-        if (it != packed.end()) {
-            RLDM_REQUIRE(it->second->Cin_pad == Cin_pad, "conv layer reused with a different channel padding");
-            *out = it->second.get();
-            return 0;
-        }
-        const int taps = ksize * ksize, Rp = no_res ? 0 : R;
-        RLDM_REQUIRE(Cout % 32 == 0 && Cin_pad % (16 * KG) == 0 && Rp % (16 * KG) == 0, "conv " + name + ": not fragment-packable");
-        const int CPT = Cin_pad / 16 / KG, RPT = Rp / 16 / KG, nmine = taps * CPT + RPT;
-        std::vector<bf16_t> img((size_t)(Cout / 32) * KG * nmine * 512 + 512, 0);
-        auto at = [&](int n, int step, int c16, int k) -> bf16_t& {     // step within the stream of k-group c16 % KG
-            const size_t stream = (size_t)(n / 32) * KG + c16 % KG;
-            return img[((stream * nmine + step) * 64 + (k / 8) * 32 + n % 32) * 8 + k % 8];
-        };
-        for (int n = 0; n < Cout; ++n) {
-            for (int c = 0; c < Cin; ++c)
-                for (int tap = 0; tap < taps; ++tap)
-                    at(n, tap * CPT + (c / 16) / KG, c / 16, c % 16) = f32_to_bf16(w[((size_t)n * Cin + c) * taps + tap]);
-            for (int c = 0; c < Rp; ++c) {
-                const float v = sc_identity ? (c == n ? 1.f : 0.f) : sc_w[(size_t)n * R + c];
-                at(n, taps * CPT + (c / 16) / KG, c / 16, c % 16) = f32_to_bf16(v);
+    // conv_small.hip image: MFMA A-fragment order, one contiguous stream of 1 KiB k-steps per (TN-channel tile, k-group):
+    // [Cout/TN][KG][taps*CPT main steps (tap-major) + RPT residual steps][64 lanes][8 bf16] + one zero fragment.  A k-step is
+    // 512 / TN input channels of a tap; k-group kg owns the channel groups kg, kg + KG, ... of every tap.
+    // TN == 32: k-steps of 16 channels, lane l holds channel 32*t + (l & 31), k = 8*(l >> 5) .. +8;
+    // TN == 16 (the image-owning 16-channel tiles, KG == 8): k-steps of 32 channels (v_mfma_f32_16x16x32_bf16), lane l holds
+    // channel 16*t + (l & 15), k = 8*(l >> 4) .. +8.
+    // `no_res`: the (identity) residual is added by the kernel's epilogue, not multiplied here.
+    int get_fragpacked(int Cin_pad, int TN, int KG, bool no_res, Packed** out) {
+        const WeightLayout layout = no_res ? WeightLayout::FragNoRes : WeightLayout::Frag;
+        return cached({layout, TN, KG}, Cin_pad, out, [&](std::vector<bf16_t>& img, std::vector<float>&) {
+            const int taps = ksize * ksize, Rp = no_res ? 0 : R, KS = 512 / TN;
+            RLDM_REQUIRE((TN == 32 || TN == 16) && Cout % TN == 0 && Cin_pad % (KS * KG) == 0 && Rp % (KS * KG) == 0,
+                         "conv " + name + ": not fragment-packable");
+            const int CPT = Cin_pad / KS / KG, RPT = Rp / KS / KG, nmine = taps * CPT + RPT;
+            img.assign((size_t)(Cout / TN) * KG * nmine * 512 + 512, 0);
+            auto at = [&](int n, int step0, int c) -> bf16_t& {             // step0: first step of the tap / of the residual phase
+                const int cg = c / KS, k = c % KS;                          // channel group (k-group cg % KG, its step cg / KG), k within it
+                const size_t stream = (size_t)(n / TN) * KG + cg % KG;
+                return img[((stream * nmine + step0 + cg / KG) * 64 + (k / 8) * TN + n % TN) * 8 + k % 8];
+            };
+            for (int n = 0; n < Cout; ++n) {
+                for (int c = 0; c < Cin; ++c)
+                    for (int tap = 0; tap < taps; ++tap) at(n, tap * CPT, c) = f32_to_bf16(weight(n, c, tap));
+                for (int c = 0; c < Rp; ++c) at(n, taps * CPT, c) = f32_to_bf16(res_weight(n, c));
             }
-        }
-        auto pk = std::make_unique<Packed>();
-        if (upload(pk->w, img.data(), img.size() * sizeof(bf16_t))) return 1;
-        if (upload(pk->bias, b.data(), b.size() * sizeof(float))) return 1;
-        pk->ntile_n = 0;
-        pk->Cin_pad = Cin_pad;
-        *out = pk.get();
-        packed[key] = std::move(pk);
-        return 0;
-    }
-
-    // (round 5) conv_small.hip's 16-channel tiles: one stream of 1 KiB k-steps per (16-channel tile, k-group of 8):
-    // [Cout/16][8][taps*CPT main steps (tap-major) + RPT residual steps][64 lanes][8 bf16] + one zero fragment; a k-step is 32 input
-    // channels (v_mfma_f32_16x16x32_bf16: lane l holds channel 16*t + (l & 15), k = 8*(l >> 4) .. +8); k-group kg owns the 32-channel
-    // groups kg, kg + 8, ... of every tap.
-    int get_fragpacked16(int Cin_pad, bool no_res, Packed** out) {
-        auto key = std::make_pair(no_res ? -6 : -5, 16);
-        auto it = packed.find(key);
-        if (it != packed.end()) {
-            RLDM_REQUIRE(it->second->Cin_pad == Cin_pad, "conv layer reused with a different channel padding");
-            *out = it->second.get();
             return 0;
-        }
-        const int taps = ksize * ksize, Rp = no_res ? 0 : R, KG = 8;
-        RLDM_REQUIRE(Cout % 16 == 0 && Cin_pad % (32 * KG) == 0 && Rp % (32 * KG) == 0, "conv " + name + ": not 16-channel fragment-packable");
-        const int CPT = Cin_pad / 32 / KG, RPT = Rp / 32 / KG, nmine = taps * CPT + RPT;
-        std::vector<bf16_t> img((size_t)(Cout / 16) * KG * nmine * 512 + 512, 0);
-        auto at = [&](int n, int step, int c32, int k) -> bf16_t& {     // step within the stream of k-group c32 % KG
-            const size_t stream = (size_t)(n / 16) * KG + c32 % KG;
-            return img[((stream * nmine + step) * 64 + (k / 8) * 16 + n % 16) * 8 + k % 8];
-        };
-        for (int n = 0; n < Cout; ++n) {
-            for (int c = 0; c < Cin; ++c)
-                for (int tap = 0; tap < taps; ++tap)
-                    at(n, tap * CPT + (c / 32) / KG, c / 32, c % 32) = f32_to_bf16(w[((size_t)n * Cin + c) * taps + tap]);
-            for (int c = 0; c < Rp; ++c) {
-                const float v = sc_identity ? (c == n ? 1.f : 0.f) : sc_w[(size_t)n * R + c];
-                at(n, taps * CPT + (c / 32) / KG, c / 32, c % 32) = f32_to_bf16(v);
-            }
-        }
-        auto pk = std::make_unique<Packed>();
-        if (upload(pk->w, img.data(), img.size() * sizeof(bf16_t))) return 1;
-        if (upload(pk->bias, b.data(), b.size() * sizeof(float))) return 1;
-        pk->ntile_n = 0;
-        pk->Cin_pad = Cin_pad;
-        *out = pk.get();
-        packed[key] = std::move(pk);
-        return 0;
+        });
     }
 };
 
-// (ConvLayer::get_streampacked is defined with the struct above)
 struct ParamStore {
     std::map<std::string, std::vector<float>> host;
     std::map<std::string, int64_t> expected;    // name -> numel
@@ -583,6 +501,47 @@ struct ConvArgs {
     bool out_f32_nchw = false;     // conv_out: write plan->io.out
     bool own_image = false;        // conv_small route with ONE tile per image (the producer normalises for its consumers)
     bool first_of_step = false;    // conv_in: advances the sampler's step index when the plan's pack_input launch is fused away
+};
+
+// the sizes every routing question is asked about: tensor (padded) channels of cat[x0, x1] and of cat[r0, r1], taps, output size
+struct ConvShape {
+    int Cin_t, R_t, taps, Wout, Hout;
+};
+static ConvShape conv_shape(const ConvArgs& a) {
+    return {a.x0.C + (a.x1.valid() ? a.x1.C : 0), (a.r0.valid() ? a.r0.C : 0) + (a.r1.valid() ? a.r1.C : 0),
+            a.layer->ksize * a.layer->ksize, a.x0.W * a.up / a.stride, a.x0.H * a.up / a.stride};
+}
+// algorithmic FLOPs (2*MACs; an identity residual multiplies nothing) and HBM bytes (input, weights, `out_copies` outputs,
+// residual sources -- each touched once) of a conv.  `res_weights`: the kernel reads the residual phase's weights
+static double conv_flops(const ConvArgs& a, const ConvShape& s) {
+    const ConvLayer* L = a.layer;
+    return 2.0 * (double)a.x0.B * s.Wout * s.Hout * L->Cout * ((double)L->Cin * s.taps + (L->sc_identity ? 0.0 : (double)L->R));
+}
+static double conv_bytes(const ConvArgs& a, const ConvShape& s, size_t out_copies = 1, bool res_weights = true) {
+    const ConvLayer* L = a.layer;
+    const double out_px = (double)a.x0.B * s.Wout * s.Hout;
+    return (double)a.x0.B * a.x0.W * a.x0.H * s.Cin_t * 2.0 + (double)L->Cout * (L->Cin * s.taps + (res_weights ? L->R : 0)) * 2.0 +
+           out_px * L->Cout * (a.out_f32_nchw ? 4.0 : 2.0) * (double)out_copies + out_px * s.R_t * 2.0;
+}
+
+// what a conv launch takes from the plan's I/O block every time it runs (the block's owner may rebind it between runs); an
+// emitter names the members its kernel reads
+struct ConvLate {
+    int temb_off = -1;             // >= 0: the time-embedding table at this channel offset, and the step index that selects its row
+    bool first_of_step = false;    // advances the sampler's step index when the pack_input launch is fused away
+    bool f32_out = false;          // writes io.out
+    bool sch = false;              // ... through the scheduler step
+    void apply(ConvParams& p, const PlanIO& io) const {
+        if (first_of_step) p.step_inc = io.pack_fused ? io.step_inc : nullptr;
+        if (temb_off >= 0) {
+            p.temb = io.temb + temb_off;
+            p.step_ptr = io.step_ptr;
+            p.temb_rows_per_step = io.temb_rows_per_step;
+            p.temb_per_sample = io.temb_per_sample;
+        }
+        if (f32_out) p.y_nchw = io.out;
+        if (sch) p.sch = io.sch;
+    }
 };
 
 // Producer-side GroupNorm: which convs write a normalised (+ activated) copy of their output for which
@@ -1019,6 +978,74 @@ struct Builder {
         return 0;
     }
 
+    // ---- convs: conv_route asks each route's *_params in turn; the first that admits the conv has filled its ConvParams, and the
+    // route's emitter (conv_small, conv_stream, ...) takes them from there.  What every route does the same way is stated once here.
+
+    // the fields all routes fill alike: channels, sizes, the pixel tile (s.Wout x s.Hout cut into TW x TH) and the reciprocals
+    // the kernels divide with; thv: halo rows of a tile (0: the route's kernels do not divide by it)
+    static void conv_geometry(const ConvArgs& a, const ConvShape& s, int TW, int TH, int thv, ConvParams* q) {
+        memset(q, 0, sizeof(*q));
+        q->C0 = a.x0.C;
+        q->C1 = s.Cin_t - a.x0.C;
+        q->R0 = a.r0.valid() ? a.r0.C : 0;
+        q->R1 = s.R_t - q->R0;
+        q->B = a.x0.B; q->Win = a.x0.W; q->Hin = a.x0.H;
+        q->up = a.up; q->stride = a.stride;
+        q->pad_lo = (s.taps == 1) ? 0 : (a.pad_mode == 0 ? 1 : 0);
+        q->Wout = s.Wout; q->Hout = s.Hout;
+        q->TW = TW; q->TH = TH;
+        while ((1 << q->th_shift) < TH) ++q->th_shift;
+        q->tiles_h = s.Hout / TH;
+        q->tiles_img = (s.Wout / TW) * q->tiles_h;
+        if (thv) q->magic_thv = ((1 << 20) + thv - 1) / thv;
+        const int cpg = std::max(1, s.Cin_t / a.groups);
+        q->magic_cpg = ((1 << 20) + cpg - 1) / cpg;
+        q->gn_inv_n = (float)(1.0 / ((double)a.x0.W * a.x0.H * cpg));
+        q->N = a.layer->Cout;
+        q->silu = a.silu;
+        q->gn_eps = a.eps;
+        q->gn_groups = a.groups;
+        q->ksplit = 1;
+    }
+    // the kernels' *_supported shape checks look at WHICH pointers are set, not where they point: ask with stand-ins
+    template <class F> static bool supported_with(ConvParams q, bool gn, bool f32_out, F&& supported) {
+        if (gn) q.st0 = reinterpret_cast<const float2*>(&q);
+        if (f32_out) q.y_nchw = reinterpret_cast<float*>(&q);
+        return supported(q);
+    }
+    int require_gn_input(const ConvArgs& a, int Cin_t) const {
+        if (!a.gn) return 0;
+        RLDM_REQUIRE(a.gn->C == Cin_t && Cin_t % a.groups == 0, "conv " + a.layer->name + ": GroupNorm channel mismatch");
+        RLDM_REQUIRE(a.x0.P > 0 && (!a.x1.valid() || a.x1.P > 0), "conv " + a.layer->name + ": GroupNorm input without statistics");
+        return 0;
+    }
+    // real pass: the device pointers of a conv launch -- inputs, residual sources, weights, the GroupNorm prologue's statistics
+    // and affine, the bf16 output y (invalid: the layer writes plan->io.out, bound when the launch runs)
+    void bind_conv(ConvParams& p, const ConvArgs& a, const ConvLayer::Packed& pk, const Tensor& y) const {
+        p.x0 = tptr(a.x0);
+        p.x1 = tptr(a.x1);
+        p.r0 = tptr(a.r0);
+        p.r1 = tptr(a.r1);
+        p.wpk = pk.w.as<bf16_t>();
+        p.bias = pk.bias.as<float>();
+        if (a.gn) {
+            p.st0 = sptr(a.x0);
+            p.st1 = sptr(a.x1);
+            p.P0 = a.x0.P;
+            p.P1 = a.x1.valid() ? a.x1.P : 0;
+            p.gn_gamma = a.gn->gamma.as<float>();
+            p.gn_beta = a.gn->beta.as<float>();
+        }
+        if (y.valid()) {
+            p.y = tptr(y);
+            p.y_ld = y.C;
+            p.y_stats = y.P ? ptr<float2>(y.st_off) : nullptr;
+        }
+        p.temb_ld = temb_ld;
+    }
+    // a launch of the plan, or (in_phase) the stand-alone form of a phase of the open persistent segment
+    void emit(Op op, bool in_phase = false) { (in_phase ? pend.standalone : plan->ops).push_back(std::move(op)); }
+
     // conv_small.hip route: 3x3 / stride 1 convs over <= 256-pixel images (the 64x4 and 32x2 UNet levels) and every
     // pointwise conv with 128..512 input channels (attention q/k/v and output projections)
     static void small_tile(int bm, int Wout, int Hout, int* tw, int* th) {
@@ -1028,7 +1055,8 @@ struct Builder {
         *tw = bm / h;
     }
     // geometry + channel counts of the route; `epi_res`: the identity residual is added in the epilogue instead of the K loop
-    static bool small_params(const ConvArgs& a, int Cin_t, int R_t, int taps, int Wout, int Hout, ConvParams* q, bool* epi_res) {
+    static bool small_params(const ConvArgs& a, const ConvShape& s, ConvParams* q, bool* epi_res) {
+        const int Cin_t = s.Cin_t, R_t = s.R_t, taps = s.taps, Wout = s.Wout, Hout = s.Hout;
         if (dbg() & RLDM_FLAG_NO_CONV_SMALL) return false;
         if ((taps != 9 && taps != 1) || a.stride != 1 || (a.up != 1 && !(a.up == 2 && taps == 9 && !a.gn && R_t == 0)) || a.out_f32_nchw)
             return false;
@@ -1055,30 +1083,13 @@ struct Builder {
         small_tile(bm, Wout, Hout, &tw, &th);
         if (Wout % tw != 0 || Hout % th != 0 || Wout < 2) return false;
         *epi_res = a.layer->sc_identity && a.r0.valid() && !a.r1.valid() && a.r0.C == a.layer->Cout;
-        memset(q, 0, sizeof(*q));
-        {
-            const bool cat = taps == 9 && a.x1.valid() && small_gn_fused(a, taps);     // a concatenated input normalised by the conv's own staging
-            q->C0 = cat ? a.x0.C : Cin_t;       // (else one input tensor: single, or pre-activated by gn_apply)
-            q->C1 = cat ? Cin_t - a.x0.C : 0;
+        conv_geometry(a, s, tw, th, 0, q);
+        if (!(taps == 9 && a.x1.valid() && small_gn_fused(a, taps))) {     // (that: a concatenated input normalised by the conv's own staging)
+            q->C0 = Cin_t;                      // one input tensor: single, or pre-activated by gn_apply
+            q->C1 = 0;
         }
-        q->R0 = *epi_res ? 0 : (a.r0.valid() ? a.r0.C : 0);
-        q->R1 = *epi_res ? 0 : R_t - q->R0;
-        q->B = a.x0.B; q->Win = a.x0.W; q->Hin = a.x0.H;
-        q->up = a.up; q->stride = 1; q->pad_lo = taps == 9 ? 1 : 0;
-        q->Wout = Wout; q->Hout = Hout;
-        q->TW = tw; q->TH = th;
+        if (*epi_res) q->R0 = q->R1 = 0;
         q->colb = conv_small_col_bytes(Cin_t, th, taps);
-        q->tiles_h = Hout / th;
-        q->tiles_img = (Wout / tw) * q->tiles_h;
-        while ((1 << q->th_shift) < th) ++q->th_shift;
-        const int cpg = std::max(1, Cin_t / a.groups);
-        q->magic_cpg = ((1 << 20) + cpg - 1) / cpg;
-        q->gn_inv_n = (float)(1.0 / ((double)a.x0.W * a.x0.H * cpg));
-        q->N = a.layer->Cout;
-        q->silu = a.silu;
-        q->gn_eps = a.eps;
-        q->gn_groups = a.groups;
-        q->ksplit = 1;
         return true;
     }
     // channel tile; 0: no instance / not worth it.
@@ -1086,15 +1097,16 @@ struct Builder {
     // 1x1: the work per block is a few MFMAs and the launch is one latency chain per block, so the route is taken only if
     // the grid fits one round of 256 workgroups -- with the narrowest tile that does (most blocks); else the generic kernel.
     static int small_bn(const ConvParams& q, int taps, bool gn_fused, bool own = false) {
-        ConvParams t = q;
-        if (gn_fused) t.st0 = reinterpret_cast<const float2*>(&t);      // (only its presence matters to the shape check)
+        const auto supported = [&](int bn) {
+            return supported_with(q, gn_fused, false, [&](const ConvParams& t) { return conv_small_supported(t, taps, bn); });
+        };
         const long long tiles = (long long)q.B * q.tiles_img;
-        if (own) return (q.tiles_img == 1 && conv_small_supported(t, taps, 32)) ? 32 : 0;      // whole groups per 32-channel tile
-        if (g_force_bn && conv_small_supported(t, taps, g_force_bn)) return g_force_bn;
+        if (own) return (q.tiles_img == 1 && supported(32)) ? 32 : 0;      // whole groups per 32-channel tile
+        if (g_force_bn && supported(g_force_bn)) return g_force_bn;
         if (taps == 9 && q.TW * q.TH == 128)    // one round of workgroups, or the generic kernel
-            return (conv_small_supported(t, 9, 64) && tiles * (q.N / 64) <= 256) ? 64 : 0;
+            return (supported(64) && tiles * (q.N / 64) <= 256) ? 64 : 0;
         if (taps == 9) {
-            const bool ok64 = conv_small_supported(t, 9, 64), ok32 = conv_small_supported(t, 9, 32);
+            const bool ok64 = supported(64), ok32 = supported(32);
             if (ok64 && (tiles * (q.N / 64) >= 200 || !ok32)) return 64;
             // (measured, round 3: giving a level that COULD run as multi-tile clusters the cluster's 64 x 64 tile at small batches --
             //  nuScenes 64x2 at 4 images: 66 -> 42 launches per step -- is slower, 84.3 against 86.9 img/s, and neutral for the KITTI
@@ -1103,7 +1115,7 @@ struct Builder {
         }
         const int cand[3] = {32, 64, 128};
         for (int bn : cand)
-            if (conv_small_supported(t, taps, bn) && tiles * (q.N / bn) <= 256) return bn;
+            if (supported(bn) && tiles * (q.N / bn) <= 256) return bn;
         return 0;
     }
     // GroupNorm (+ SiLU) folded into the conv's staging: every 1x1, and the 3x3 convs over ONE input tensor (a concatenated
@@ -1116,32 +1128,32 @@ struct Builder {
         if (taps == 1) return true;
         return !a.x1.valid() || (!a.own_image && a.x0.C % 8 == 0 && a.x1.C % 8 == 0);
     }
-    bool small_route(const ConvArgs& a, int Cin_t, int R_t, int taps, int Wout, int Hout) const {
+    // does the route take this conv?  If so *q, *epi_res and *bn (the channel tile) are what conv_small runs it with
+    static bool small_route(const ConvArgs& a, const ConvShape& s, ConvParams* q, bool* epi_res, int* bn) {
+        if (!small_params(a, s, q, epi_res)) return false;
+        *bn = small_bn(*q, s.taps, small_gn_fused(a, s.taps), a.own_image);
+        return *bn != 0;
+    }
+    // ... asked about a conv that is not being built (the recording pass, the wide-concat resnet's choice of layers)
+    static bool small_route(const ConvArgs& a, const ConvShape& s) {
         ConvParams q;
         bool epi;
-        if (!small_params(a, Cin_t, R_t, taps, Wout, Hout, &q, &epi)) return false;
-        return small_bn(q, taps, small_gn_fused(a, taps), a.own_image) != 0;
+        int bn;
+        return small_route(a, s, &q, &epi, &bn);
     }
 
-    int conv_small(const ConvArgs& a, int Cin_t, int R_t, int taps, int Wout, int Hout, Tensor* out) {
+    // p, epi_res, BN: as small_route decided them
+    int conv_small(const ConvArgs& a, const ConvShape& s, ConvParams p, bool epi_res, int BN, Tensor* out) {
         ConvLayer* L = a.layer;
-        const int N = L->Cout;
+        const int N = L->Cout, Cin_t = s.Cin_t, taps = s.taps, Wout = s.Wout, Hout = s.Hout;
         const bool gn_fused = small_gn_fused(a, taps);         // folded into the conv's staging
         const bool preact = a.gn != nullptr && !gn_fused;      // concatenated 3x3 input: GroupNorm + SiLU in their own launch
-        if (a.gn) {
-            RLDM_REQUIRE(a.gn->C == Cin_t && Cin_t % a.groups == 0, "conv " + L->name + ": GroupNorm channel mismatch");
-            RLDM_REQUIRE(a.x0.P > 0 && (!a.x1.valid() || a.x1.P > 0), "conv " + L->name + ": GroupNorm input without statistics");
-        }
+        if (require_gn_input(a, Cin_t)) return 1;
         Tensor act;
         if (preact) act = make(a.x0.B, a.x0.W, a.x0.H, Cin_t);
         const Tensor& x0 = preact ? act : a.x0;
-        ConvParams p;
-        bool epi_res = false;
-        RLDM_REQUIRE(small_params(a, Cin_t, R_t, taps, Wout, Hout, &p, &epi_res), "conv " + L->name + ": conv_small route lost");
         p.dbg = kernel_dbg();
         p.ts = stamp_buf(StampSite::Conv, conv_ord - 1);
-        int BN = small_bn(p, taps, gn_fused, a.own_image);
-        RLDM_REQUIRE(BN != 0, "conv " + L->name + ": conv_small route lost its instance");
         // (round 5) image-owning tiles of the 32x2 level: 16 channels per workgroup -- the level's persistent launch then runs on 16
         // workgroups per image (all 256 CUs at batch 16) with half the K loop, weight stream and epilogue per workgroup
         if (BN == 32 && a.own_image && own_tile_channels(x0.B, p.TW * p.TH, N) == 16 && !gn_fused && conv_small_supported(p, taps, 16)) BN = 16;
@@ -1160,7 +1172,7 @@ struct Builder {
                 vts.push_back(it->second);
             }
         }
-        const double fl = 2.0 * (double)x0.B * Wout * Hout * N * ((double)L->Cin * taps + (L->sc_identity ? 0.0 : (double)L->R));
+        const double fl = conv_flops(a, s);
         plan->flops += fl;
         // a phase of the persistent trunk launch (trunk.hip) instead of a launch of its own: the tile owns the image, the input
         // arrives pre-activated (or needs no norm), one of the three instances the trunk kernel carries
@@ -1211,10 +1223,8 @@ struct Builder {
                     pend.phases.push_back(trunk_gn_apply_phase(g));
                     pend.lds = std::max(pend.lds, (size_t)(2 * 512 * 8 + 2 * 512 * 4));
                     pend.bytes += by;
-                    pend.standalone.push_back({[g](hipStream_t s) { return launch_gn_apply(g, s); }, "gn_apply_kernel", 0.0, by});
-                } else {
-                    plan->ops.push_back({[g](hipStream_t s) { return launch_gn_apply(g, s); }, "gn_apply_kernel", 0.0, by});
                 }
+                emit({[g](hipStream_t st) { return launch_gn_apply(g, st); }, "gn_apply_kernel", 0.0, by}, gn_phase);
             }
         }
         if (in_trunk) trunk_begin(x0.B, ranks_t);
@@ -1223,28 +1233,16 @@ struct Builder {
         in_trunk = in_trunk || in_cluster;
         if (!dry) {
             ConvLayer::Packed* pk = nullptr;
-            if (BN == 16 ? L->get_fragpacked16(Cin_t, epi_res, &pk) : L->get_fragpacked(Cin_t, conv_small_kgroups(BN), epi_res, &pk)) return 1;
-            p.x0 = tptr(x0);
-            p.r0 = epi_res ? nullptr : tptr(a.r0);
-            p.r1 = epi_res ? nullptr : tptr(a.r1);
-            p.res = epi_res ? tptr(a.r0) : nullptr;
-            p.wpk = pk->w.as<bf16_t>();
-            p.bias = pk->bias.as<float>();
-            if (gn_fused) {
-                p.st0 = sptr(a.x0);
-                p.P0 = a.x0.P;
-                p.gn_gamma = a.gn->gamma.as<float>();
-                p.gn_beta = a.gn->beta.as<float>();
-                if (p.C1 != 0) {                // concatenated input: the second tensor and its statistics
-                    p.x1 = tptr(a.x1);
-                    p.st1 = sptr(a.x1);
-                    p.P1 = a.x1.P;
-                }
+            if (L->get_fragpacked(Cin_t, BN == 16 ? 16 : 32, BN == 16 ? 8 : conv_small_kgroups(BN), epi_res, &pk)) return 1;
+            ConvArgs k = a;                     // what the kernel itself reads:
+            k.x0 = x0;                          // the pre-activated copy;
+            if (!gn_fused) k.gn = nullptr;      // a GroupNorm only when it is folded into the staging,
+            if (!gn_fused || p.C1 == 0) k.x1 = Tensor();                   // ... the second tensor of a concat only under it;
+            if (epi_res) {                      // the identity residual in the epilogue, not as a K phase
+                p.res = tptr(a.r0);
+                k.r0 = k.r1 = Tensor();
             }
-            p.y = tptr(y);
-            p.y_ld = N;
-            p.y_stats = y.P ? ptr<float2>(y.st_off) : nullptr;
-            p.temb_ld = temb_ld;
+            bind_conv(p, k, *pk, y);
             for (size_t v = 0; v < vts.size(); ++v) {
                 const auto& e = (*cur_emit)[v];
                 NormView& nv = p.nv[v];
@@ -1262,8 +1260,7 @@ struct Builder {
             p.nviews = (int)vts.size();
             Plan* pl = plan;
             const int temb_off = a.temb_off;
-            const double by = (double)x0.B * x0.W * x0.H * Cin_t * 2.0 + (double)N * (L->Cin * taps + L->R) * 2.0 +
-                              (double)x0.B * Wout * Hout * N * 2.0 * (1.0 + (double)vts.size()) + (double)x0.B * Wout * Hout * R_t * 2.0;
+            const double by = conv_bytes(a, s, 1 + vts.size());
             const std::string kname = "conv_small_kernel<" + std::to_string(p.TW * p.TH) + "," + std::to_string(BN) + ",taps" + std::to_string(taps) + ">";
             if (in_trunk) {
                 RLDM_REQUIRE(!in_cluster || p.nviews == 0, "conv " + L->name + ": a multi-tile cluster phase writes no views");
@@ -1281,17 +1278,11 @@ struct Builder {
                 pend.flops += fl;
                 pend.bytes += by;
             }
-            Op standalone{[p, BN, taps, pl, temb_off](hipStream_t s) mutable {
-                if (temb_off >= 0) {
-                    p.temb = pl->io.temb + temb_off;
-                    p.step_ptr = pl->io.step_ptr;
-                    p.temb_rows_per_step = pl->io.temb_rows_per_step;
-                    p.temb_per_sample = pl->io.temb_per_sample;
-                }
-                return launch_conv_small(p, taps, BN, s);
-            }, kname, fl, by};
-            if (in_trunk) pend.standalone.push_back(standalone);
-            else plan->ops.push_back(standalone);
+            const ConvLate late{temb_off};
+            emit({[p, BN, taps, pl, late](hipStream_t st) mutable {
+                late.apply(p, pl->io);
+                return launch_conv_small(p, taps, BN, st);
+            }, kname, fl, by}, in_trunk);
         }
         if (preact) release(act);
         *out = y;
@@ -1303,57 +1294,39 @@ struct Builder {
     static constexpr int kSubMinBlocks = 96;
     static constexpr long long kAnyGrid = 1ll << 40;
     // instance `inst` (kernels.h: kStreamInst) on pixel tile `tile` (TW = 0: the instance's only one), for a grid of [min_blocks, max_blocks] workgroups
-    static bool stream_params_tw(const ConvArgs& a, int Cin_t, int R_t, int taps, int Wout, int Hout, StreamInst inst, long long min_blocks,
-                                 long long max_blocks, ConvParams* q, StreamTile tile = {}) {
+    static bool stream_params_tw(const ConvArgs& a, const ConvShape& s, StreamInst inst, long long min_blocks, long long max_blocks,
+                                 ConvParams* q, StreamTile tile = {}) {
         const StreamInstDesc& d = kStreamInst[inst];
         if (tile.TW == 0) tile = d.tiles[0];
         const int TW = tile.TW, TH = tile.TH;
         if (dbg() & RLDM_FLAG_NO_STREAM_REGW) return false;
-        if (taps != 9 || a.stride != d.STR || a.pad_mode != 0 || a.out_f32_nchw || g_force_bm) return false;
+        if (s.taps != 9 || a.stride != d.STR || a.pad_mode != 0 || a.out_f32_nchw || g_force_bm) return false;
         // (round 4: nearest x2 + 3x3 in its sub-pixel form -- the tiles are INPUT tiles, four parity workgroups each)
         const bool sub = d.SUB;
+        ConvShape tiled = s;                    // what the tiles cut up
         if (sub) {
-            if (a.up != 2 || R_t != 0 || Wout != 2 * a.x0.W || Hout != 2 * a.x0.H) return false;
-            Wout = a.x0.W; Hout = a.x0.H;
+            if (a.up != 2 || s.R_t != 0 || s.Wout != 2 * a.x0.W || s.Hout != 2 * a.x0.H) return false;
+            tiled.Wout = a.x0.W; tiled.Hout = a.x0.H;
         }
-        if (Wout % TW != 0 || Hout % TH != 0) return false;
-        memset(q, 0, sizeof(*q));
-        q->C0 = a.x0.C;
-        q->C1 = Cin_t - a.x0.C;
-        q->R0 = a.r0.valid() ? a.r0.C : 0;
-        q->R1 = R_t - q->R0;
-        q->B = a.x0.B; q->Win = a.x0.W; q->Hin = a.x0.H;
-        q->up = sub ? 1 : a.up; q->stride = a.stride; q->pad_lo = 1;
-        q->Wout = sub ? 2 * Wout : Wout; q->Hout = sub ? 2 * Hout : Hout;
-        q->TW = TW; q->TH = TH; q->th_shift = TH == 16 ? 4 : (TH == 8 ? 3 : 2);
+        if (tiled.Wout % TW != 0 || tiled.Hout % TH != 0) return false;
+        conv_geometry(a, tiled, TW, TH, d.FH ? TH : (TH - 1) * a.stride + 3, q);      // (full-height tiles: only the tile's own rows are staged)
+        if (sub) {
+            q->up = 1;
+            q->Wout = s.Wout; q->Hout = s.Hout;
+        }
         q->st_inst = inst;
         ConvTile t;
         t.BM = 256; t.BN = 128; t.CK = 64; t.taps = 9;
         q->colb = conv_halo_col_bytes(t, TH, a.stride);
-        q->tiles_h = Hout / TH;
-        q->tiles_img = (Wout / TW) * q->tiles_h;
-        {
-            const int thv = d.FH ? TH : (TH - 1) * a.stride + 3;        // (full-height tiles: only the tile's own rows are staged)
-            q->magic_thv = ((1 << 20) + thv - 1) / thv;
-        }
-        const int cpg = std::max(1, Cin_t / a.groups);
-        q->magic_cpg = ((1 << 20) + cpg - 1) / cpg;
-        q->gn_inv_n = (float)(1.0 / ((double)a.x0.W * a.x0.H * cpg));
-        q->N = a.layer->Cout;
-        q->silu = a.silu;
-        q->gn_eps = a.eps;
-        q->gn_groups = a.groups;
-        q->ksplit = 1;
-        if (a.gn) q->st0 = reinterpret_cast<const float2*>(q);      // (only its presence matters to the shape check)
         const long long blocks = (long long)q->B * q->tiles_img * (q->N / d.bn()) * (sub ? 4 : 1);
-        const bool ok = conv_stream_supported(*q, 9) && ((dbg() & RLDM_FLAG_STREAM_ANY_GRID) || (blocks >= min_blocks && blocks <= max_blocks));
-        q->st0 = nullptr;
-        return ok;
+        return supported_with(*q, a.gn != nullptr, false, [](const ConvParams& c) { return conv_stream_supported(c, 9); }) &&
+               ((dbg() & RLDM_FLAG_STREAM_ANY_GRID) || (blocks >= min_blocks && blocks <= max_blocks));
     }
-    static bool stream_params(const ConvArgs& a, int Cin_t, int R_t, int taps, int Wout, int Hout, ConvParams* q) {
+    static bool stream_params(const ConvArgs& a, const ConvShape& s, ConvParams* q) {
+        const int R_t = s.R_t, Hout = s.Hout;
         // the first rule that fits, in this order
         const auto fits = [&](StreamInst inst, long long min_blocks, long long max_blocks, StreamTile tile = {}) {
-            return stream_params_tw(a, Cin_t, R_t, taps, Wout, Hout, inst, min_blocks, max_blocks, q, tile);
+            return stream_params_tw(a, s, inst, min_blocks, max_blocks, q, tile);
         };
         // 256-pixel tiles when they fill the chip; else the 4-k-group instance (it re-streams the weights per 128 pixels:
         // only where its grid is about one or two rounds); else 256-pixel tiles on at least half the chip
@@ -1403,24 +1376,19 @@ struct Builder {
         return fits(px256, 128, kAnyGrid);
     }
 
-    int conv_stream(const ConvArgs& a, int Cin_t, int R_t, int Wout, int Hout, Tensor* out) {
+    int conv_stream(const ConvArgs& a, const ConvShape& s, ConvParams p, Tensor* out) {
         ConvLayer* L = a.layer;
         const int N = L->Cout;
         const Tensor& x0 = a.x0;
-        ConvParams p;
-        RLDM_REQUIRE(stream_params(a, Cin_t, R_t, 9, Wout, Hout, &p), "conv " + L->name + ": conv_stream route lost");
-        if (a.gn) {
-            RLDM_REQUIRE(a.gn->C == Cin_t && Cin_t % a.groups == 0, "conv " + L->name + ": GroupNorm channel mismatch");
-            RLDM_REQUIRE(x0.P > 0 && (!a.x1.valid() || a.x1.P > 0), "conv " + L->name + ": GroupNorm input without statistics");
-        }
+        if (require_gn_input(a, s.Cin_t)) return 1;
         p.dbg = kernel_dbg();
         p.ts = stamp_buf(StampSite::Conv, conv_ord - 1);
         const StreamInstDesc& d = stream_inst(p);
         const bool sub = d.SUB;
         p.ntile_n = N / d.bn() * (sub ? 4 : 1);      // (grid x: channel tiles x parities)
-        Tensor y = make(x0.B, Wout, Hout, N);
+        Tensor y = make(x0.B, s.Wout, s.Hout, N);
         if (a.want_stats) add_stats(y, p.tiles_img * (sub ? 4 : 1));
-        const double fl_ref = 2.0 * (double)x0.B * Wout * Hout * N * ((double)L->Cin * 9 + (L->sc_identity ? 0.0 : (double)L->R));
+        const double fl_ref = conv_flops(a, s);
         plan->flops += fl_ref;                  // (the network's nominal count: 9 taps)
         // what THIS launch / phase executes (the bench line's roofline is priced with it): the sub-pixel form multiplies 4 taps per output pixel
         const double fl = sub ? fl_ref * 4.0 / 9.0 : fl_ref;
@@ -1439,46 +1407,22 @@ struct Builder {
         else note_launch();
         if (!dry) {
             ConvLayer::Packed* pk = nullptr;
-            if (sub ? L->get_subpixpacked(Cin_t, &pk) : L->get_streampacked(Cin_t, d.kgroups(), &pk)) return 1;
-            p.x0 = tptr(x0);
-            p.x1 = tptr(a.x1);
-            p.r0 = tptr(a.r0);
-            p.r1 = tptr(a.r1);
-            p.wpk = pk->w.as<bf16_t>();
-            p.bias = pk->bias.as<float>();
-            if (a.gn) {
-                p.st0 = sptr(x0);
-                p.st1 = sptr(a.x1);
-                p.P0 = x0.P;
-                p.P1 = a.x1.valid() ? a.x1.P : 0;
-                p.gn_gamma = a.gn->gamma.as<float>();
-                p.gn_beta = a.gn->beta.as<float>();
-            }
-            p.y = tptr(y);
-            p.y_ld = N;
-            p.y_stats = y.P ? ptr<float2>(y.st_off) : nullptr;
-            p.temb_ld = temb_ld;
+            if (sub ? L->get_subpixpacked(s.Cin_t, &pk) : L->get_streampacked(s.Cin_t, d.kgroups(), &pk)) return 1;
+            bind_conv(p, a, *pk, y);
             Plan* pl = plan;
             const int temb_off = a.temb_off;
-            const double by = (double)x0.B * x0.W * x0.H * Cin_t * 2.0 + (double)N * (L->Cin * 9 + L->R) * 2.0 +
-                              (double)x0.B * Wout * Hout * N * 2.0 + (double)x0.B * Wout * Hout * R_t * 2.0;
+            const double by = conv_bytes(a, s);
             if (in_stream_cluster) {
                 pend.phases.push_back(trunk_conv_phase(p, TK_STREAM, true, temb_off));      // (no TW_G / TW_WBYTES: variants 2 and 4 neither prefetch nor warm)
                 pend.lds = std::max(pend.lds, conv_stream_lds_bytes(p));
                 pend.flops += fl;
                 pend.bytes += by;
             }
-            Op standalone{[p, pl, temb_off](hipStream_t s) mutable {
-                if (temb_off >= 0) {
-                    p.temb = pl->io.temb + temb_off;
-                    p.step_ptr = pl->io.step_ptr;
-                    p.temb_rows_per_step = pl->io.temb_rows_per_step;
-                    p.temb_per_sample = pl->io.temb_per_sample;
-                }
-                return launch_conv_stream(p, s);
-            }, "conv_stream_kernel<" + std::to_string(p.TW * p.TH) + "," + std::to_string(d.bn()) + ",CK64,taps9" + (p.stride == 2 ? ",s2" : "") + (sub ? ",sub" : "") + ">", fl, by};
-            if (in_stream_cluster) pend.standalone.push_back(standalone);
-            else plan->ops.push_back(standalone);
+            const ConvLate late{temb_off};
+            emit({[p, pl, late](hipStream_t st) mutable {
+                late.apply(p, pl->io);
+                return launch_conv_stream(p, st);
+            }, "conv_stream_kernel<" + std::to_string(p.TW * p.TH) + "," + std::to_string(d.bn()) + ",CK64,taps9" + (p.stride == 2 ? ",s2" : "") + (sub ? ",sub" : "") + ">", fl, by}, in_stream_cluster);
         }
         *out = y;
         return 0;
@@ -1486,49 +1430,30 @@ struct Builder {
 
     // conv_regw.hip, conv_c16_kernel (round 4): the network's input layer (16 padded input channels, 128 | N, no norm / residual / time
     // embedding): every weight in one wave's registers
-    static bool c16_params(const ConvArgs& a, int Cin_t, int R_t, int taps, int Wout, int Hout, ConvParams* q) {
+    static bool c16_params(const ConvArgs& a, const ConvShape& s, ConvParams* q) {
+        const int Cin_t = s.Cin_t, R_t = s.R_t, taps = s.taps, Wout = s.Wout, Hout = s.Hout;
         if ((dbg() & RLDM_FLAG_NO_STREAM_REGW) || g_force_bm || taps != 9 || a.stride != 1 || a.pad_mode != 0 || a.up != 1 || a.out_f32_nchw) return false;
         if (a.x1.valid() || a.gn || a.temb_off >= 0 || R_t != 0 || Cin_t != 16 || a.layer->Cout % 128 != 0 || Wout % 16 != 0 || Hout % 8 != 0) return false;
-        memset(q, 0, sizeof(*q));
-        q->C0 = 16;
-        q->B = a.x0.B; q->Win = a.x0.W; q->Hin = a.x0.H;
-        q->up = 1; q->stride = 1; q->pad_lo = 1;
-        q->Wout = Wout; q->Hout = Hout;
-        q->TW = 16; q->TH = 8; q->th_shift = 3;
-        q->tiles_h = Hout / 8;
-        q->tiles_img = (Wout / 16) * q->tiles_h;
-        q->N = a.layer->Cout;
+        conv_geometry(a, s, 16, 8, 0, q);
         q->ntile_n = q->N / 128;
-        q->ksplit = 1;
         return conv_c16_supported(*q) && (long long)q->B * q->tiles_img * q->ntile_n >= 64;
     }
-    int conv_c16(const ConvArgs& a, int Wout, int Hout, Tensor* out) {
-        ConvLayer* L = a.layer;
-        const int N = L->Cout;
-        const Tensor& x0 = a.x0;
-        ConvParams p;
-        RLDM_REQUIRE(c16_params(a, x0.C, 0, 9, Wout, Hout, &p), "conv " + L->name + ": conv_c16 route lost");
-        Tensor y = make(x0.B, Wout, Hout, N);
+    int conv_c16(const ConvArgs& a, const ConvShape& s, ConvParams p, Tensor* out) {
+        Tensor y = make(a.x0.B, s.Wout, s.Hout, a.layer->Cout);
         if (a.want_stats) add_stats(y, p.tiles_img);
-        const double fl = 2.0 * (double)x0.B * Wout * Hout * N * (double)L->Cin * 9;
+        const double fl = conv_flops(a, s);
         plan->flops += fl;
         note_launch();
         if (!dry) {
             ConvLayer::Packed* pk = nullptr;
-            if (L->get_c16packed(&pk)) return 1;
-            p.x0 = tptr(x0);
-            p.wpk = pk->w.as<bf16_t>();
-            p.bias = pk->bias.as<float>();
-            p.y = tptr(y);
-            p.y_ld = N;
-            p.y_stats = y.P ? ptr<float2>(y.st_off) : nullptr;
-            const double by = (double)x0.B * x0.W * x0.H * 16 * 2.0 + (double)N * L->Cin * 9 * 2.0 + (double)x0.B * Wout * Hout * N * 2.0;
+            if (a.layer->get_c16packed(&pk)) return 1;
+            bind_conv(p, a, *pk, y);
             Plan* pl = plan;
-            const bool first_of_step = a.first_of_step;
-            plan->ops.push_back({[p, pl, first_of_step](hipStream_t s) mutable {
-                p.step_inc = (first_of_step && pl->io.pack_fused) ? pl->io.step_inc : nullptr;
-                return launch_conv_c16(p, s);
-            }, "conv_c16_kernel<128,128,taps9>", fl, by});
+            const ConvLate late{-1, a.first_of_step};
+            emit({[p, pl, late](hipStream_t st) mutable {
+                late.apply(p, pl->io);
+                return launch_conv_c16(p, st);
+            }, "conv_c16_kernel<128,128,taps9>", fl, conv_bytes(a, s)});
         }
         *out = y;
         return 0;
@@ -1536,109 +1461,55 @@ struct Builder {
 
     // conv_regw.hip, conv_o4_kernel (round 4): the UNet's output layer (GroupNorm + SiLU -> 3x3 over 128 channels -> <= 4 channels, fp32 NCHW + the
     // scheduler step)
-    static bool o4_params(const ConvArgs& a, int Cin_t, int R_t, int taps, int Wout, int Hout, ConvParams* q) {
+    static bool o4_params(const ConvArgs& a, const ConvShape& s, ConvParams* q) {
+        const int Cin_t = s.Cin_t, R_t = s.R_t, taps = s.taps, Wout = s.Wout, Hout = s.Hout;
         if ((dbg() & RLDM_FLAG_NO_STREAM_REGW) || g_force_bm || taps != 9 || a.stride != 1 || a.pad_mode != 0 || a.up != 1 || !a.out_f32_nchw) return false;
         if (a.x1.valid() || a.temb_off >= 0 || R_t != 0 || Cin_t != 128 || a.layer->Cin != 128 || a.layer->Cout > 4 || Wout % 16 != 0 || Hout % 8 != 0) return false;
-        memset(q, 0, sizeof(*q));
-        q->C0 = 128;
-        q->B = a.x0.B; q->Win = a.x0.W; q->Hin = a.x0.H;
-        q->up = 1; q->stride = 1; q->pad_lo = 1;
-        q->Wout = Wout; q->Hout = Hout;
-        q->TW = 16; q->TH = 8; q->th_shift = 3;
-        q->tiles_h = Hout / 8;
-        q->tiles_img = (Wout / 16) * q->tiles_h;
-        const int cpg = std::max(1, Cin_t / a.groups);
-        q->gn_inv_n = (float)(1.0 / ((double)a.x0.W * a.x0.H * cpg));
-        q->N = a.layer->Cout;
+        conv_geometry(a, s, 16, 8, 0, q);
         q->ntile_n = 1;
-        q->silu = a.silu;
-        q->gn_eps = a.eps;
-        q->gn_groups = a.groups;
-        q->ksplit = 1;
-        if (a.gn) q->st0 = reinterpret_cast<const float2*>(q);      // (only their presence matters to the shape check)
-        q->y_nchw = reinterpret_cast<float*>(q);
-        const bool ok = conv_o4_supported(*q) && (long long)q->B * q->tiles_img >= 64;
-        q->st0 = nullptr;
-        q->y_nchw = nullptr;
-        return ok;
+        return supported_with(*q, a.gn != nullptr, true, conv_o4_supported) && (long long)q->B * q->tiles_img >= 64;
     }
-    int conv_o4(const ConvArgs& a, int Wout, int Hout, Tensor* out) {
-        ConvLayer* L = a.layer;
-        const int N = L->Cout;
-        const Tensor& x0 = a.x0;
-        ConvParams p;
-        RLDM_REQUIRE(o4_params(a, x0.C, 0, 9, Wout, Hout, &p), "conv " + L->name + ": conv_o4 route lost");
-        if (a.gn) {
-            RLDM_REQUIRE(a.gn->C == 128 && 128 % a.groups == 0, "conv " + L->name + ": GroupNorm channel mismatch");
-            RLDM_REQUIRE(x0.P > 0, "conv " + L->name + ": GroupNorm input without statistics");
-        }
-        const double fl = 2.0 * (double)x0.B * Wout * Hout * N * (double)L->Cin * 9;
+    int conv_o4(const ConvArgs& a, const ConvShape& s, ConvParams p, Tensor* out) {
+        if (require_gn_input(a, s.Cin_t)) return 1;
+        const double fl = conv_flops(a, s);
         plan->flops += fl;
         note_launch();
         if (!dry) {
             ConvLayer::Packed* pk = nullptr;
-            if (L->get_streampacked(128, 2, &pk)) return 1;
-            p.x0 = tptr(x0);
-            p.wpk = pk->w.as<bf16_t>();
-            p.bias = pk->bias.as<float>();
-            if (a.gn) {
-                p.st0 = sptr(x0);
-                p.P0 = x0.P;
-                p.gn_gamma = a.gn->gamma.as<float>();
-                p.gn_beta = a.gn->beta.as<float>();
-            }
-            const double by = (double)x0.B * x0.W * x0.H * 128 * 2.0 + (double)N * L->Cin * 9 * 2.0 + (double)x0.B * Wout * Hout * N * 4.0;
+            if (a.layer->get_streampacked(128, 2, &pk)) return 1;
+            bind_conv(p, a, *pk, Tensor());         // (no bf16 output)
             Plan* pl = plan;
-            plan->ops.push_back({[p, pl](hipStream_t s) mutable {
-                p.y_nchw = pl->io.out;
-                p.sch = pl->io.sch;
-                return launch_conv_o4(p, s);
-            }, "conv_o4_kernel<128,32,taps9>", fl, by});
+            const ConvLate late{-1, false, true, true};
+            emit({[p, pl, late](hipStream_t st) mutable {
+                late.apply(p, pl->io);
+                return launch_conv_o4(p, st);
+            }, "conv_o4_kernel<128,32,taps9>", fl, conv_bytes(a, s)});
         }
         *out = Tensor();
         return 0;
     }
 
     // conv_regw.hip, conv_ds2_kernel (round 4): stride-2 convs of 256 raw channels onto few pixels (the 64x4 -> 32x2 down-sampler)
-    static bool ds2_params(const ConvArgs& a, int Cin_t, int R_t, int taps, int Wout, int Hout, ConvParams* q) {
+    static bool ds2_params(const ConvArgs& a, const ConvShape& s, ConvParams* q) {
+        const int Cin_t = s.Cin_t, R_t = s.R_t, taps = s.taps, Wout = s.Wout;
         if ((dbg() & RLDM_FLAG_NO_STREAM_REGW) || g_force_bm || taps != 9 || a.stride != 2 || a.pad_mode != 0 || a.up != 1 || a.out_f32_nchw) return false;
         if (a.x1.valid() || a.gn || a.temb_off >= 0 || R_t != 0 || Cin_t != 256 || a.layer->Cin != 256 || a.layer->Cout % 32 != 0 || Wout % 32 != 0) return false;
-        memset(q, 0, sizeof(*q));
-        q->C0 = 256;
-        q->B = a.x0.B; q->Win = a.x0.W; q->Hin = a.x0.H;
-        q->up = 1; q->stride = 2; q->pad_lo = 1;
-        q->Wout = Wout; q->Hout = Hout;
-        q->TW = 32; q->TH = 1;
-        q->tiles_h = Hout;
-        q->tiles_img = (Wout / 32) * Hout;
-        q->N = a.layer->Cout;
+        conv_geometry(a, s, 32, 1, 0, q);
         q->ntile_n = q->N / 32;
-        q->ksplit = 1;
         const long long blocks = (long long)q->B * q->tiles_img * q->ntile_n;
         return conv_ds2_supported(*q) && blocks >= 32 && blocks <= 512;      // (more: conv_stream's stride-2 instance or the generic kernel fill the chip)
     }
-    int conv_ds2(const ConvArgs& a, int Wout, int Hout, Tensor* out) {
-        ConvLayer* L = a.layer;
-        const int N = L->Cout;
-        const Tensor& x0 = a.x0;
-        ConvParams p;
-        RLDM_REQUIRE(ds2_params(a, x0.C, 0, 9, Wout, Hout, &p), "conv " + L->name + ": conv_ds2 route lost");
-        Tensor y = make(x0.B, Wout, Hout, N);
+    int conv_ds2(const ConvArgs& a, const ConvShape& s, ConvParams p, Tensor* out) {
+        Tensor y = make(a.x0.B, s.Wout, s.Hout, a.layer->Cout);
         if (a.want_stats) add_stats(y, p.tiles_img);
-        const double fl = 2.0 * (double)x0.B * Wout * Hout * N * (double)L->Cin * 9;
+        const double fl = conv_flops(a, s);
         plan->flops += fl;
         note_launch();
         if (!dry) {
             ConvLayer::Packed* pk = nullptr;
-            if (L->get_streampacked(256, 2, &pk)) return 1;
-            p.x0 = tptr(x0);
-            p.wpk = pk->w.as<bf16_t>();
-            p.bias = pk->bias.as<float>();
-            p.y = tptr(y);
-            p.y_ld = N;
-            p.y_stats = y.P ? ptr<float2>(y.st_off) : nullptr;
-            const double by = (double)x0.B * x0.W * x0.H * 256 * 2.0 + (double)N * L->Cin * 9 * 2.0 + (double)x0.B * Wout * Hout * N * 2.0;
-            plan->ops.push_back({[p](hipStream_t s) { return launch_conv_ds2(p, s); }, "conv_ds2_kernel<32,32,taps9,s2>", fl, by});
+            if (a.layer->get_streampacked(256, 2, &pk)) return 1;
+            bind_conv(p, a, *pk, y);
+            emit({[p](hipStream_t st) { return launch_conv_ds2(p, st); }, "conv_ds2_kernel<32,32,taps9,s2>", fl, conv_bytes(a, s)});
         }
         *out = y;
         return 0;
@@ -1646,91 +1517,44 @@ struct Builder {
 
     // conv_regw.hip route (round 4): 64 -> 64 channel 3x3 convs over many 16 x 8 tiles (the VAE decoder's full-resolution level) -- the weights stay
     // in registers, a workgroup walks a run of tiles; RLDM_FLAG2_NO_REGW keeps them on conv_stream's per-tile instance
-    static bool regw_params(const ConvArgs& a, int Cin_t, int R_t, int taps, int Wout, int Hout, ConvParams* q) {
-        const int N_ = a.layer->Cout;
+    static bool regw_params(const ConvArgs& a, const ConvShape& s, ConvParams* q) {
+        const int N_ = a.layer->Cout, Cin_t = s.Cin_t, R_t = s.R_t, taps = s.taps, Wout = s.Wout, Hout = s.Hout;
         if ((dbg2() & RLDM_FLAG2_NO_REGW) || (dbg() & RLDM_FLAG_NO_STREAM_REGW) || g_force_bm || taps != 9 || a.stride != 1 || a.pad_mode != 0 || a.up != 1) return false;
         if (a.x1.valid() || a.temb_off >= 0 || Cin_t != 64 || a.layer->Cin != 64 || a.first_of_step) return false;
         if (a.out_f32_nchw ? (N_ > 4 || R_t != 0) : N_ != 64) return false;
         if (R_t != 0 && !(a.layer->sc_identity && R_t == 64 && a.r0.valid() && a.r0.C == 64)) return false;
         if (Wout % 16 != 0 || Hout % 8 != 0) return false;
-        memset(q, 0, sizeof(*q));
-        q->C0 = 64; q->R0 = R_t;
-        q->B = a.x0.B; q->Win = a.x0.W; q->Hin = a.x0.H;
-        q->up = 1; q->stride = 1; q->pad_lo = 1;
-        q->Wout = Wout; q->Hout = Hout;
-        q->TW = 16; q->TH = 8; q->th_shift = 3;
+        conv_geometry(a, s, 16, 8, 10, q);
         ConvTile t;
         t.BM = 256; t.BN = 128; t.CK = 64; t.taps = 9;
         q->colb = conv_halo_col_bytes(t, 8, 1);
-        q->tiles_h = Hout / 8;
-        q->tiles_img = (Wout / 16) * q->tiles_h;
-        q->magic_thv = ((1 << 20) + 9) / 10;
-        const int cpg = std::max(1, Cin_t / a.groups);
-        q->magic_cpg = ((1 << 20) + cpg - 1) / cpg;
-        q->gn_inv_n = (float)(1.0 / ((double)a.x0.W * a.x0.H * cpg));
-        q->N = N_;
-        q->silu = a.silu;
-        q->gn_eps = a.eps;
-        q->gn_groups = a.groups;
-        q->ksplit = 1;
         q->exp = (dbg2() & RLDM_FLAG2_REGW_CAP8) ? 8 : 0;      // (tests: at most 8 team runs, so that small images give runs of several tiles)
-        if (a.gn) q->st0 = reinterpret_cast<const float2*>(q);      // (only their presence matters to the shape check)
-        if (a.out_f32_nchw) q->y_nchw = reinterpret_cast<float*>(q);
-        const bool ok = conv_regw_supported(*q);
-        q->st0 = nullptr;
-        q->y_nchw = nullptr;
-        return ok;
+        return supported_with(*q, a.gn != nullptr, a.out_f32_nchw, conv_regw_supported);
     }
-    int conv_regw(const ConvArgs& a, int Cin_t, int R_t, int Wout, int Hout, Tensor* out) {
-        ConvLayer* L = a.layer;
-        const int N = L->Cout;
-        const Tensor& x0 = a.x0;
-        ConvParams p;
-        RLDM_REQUIRE(regw_params(a, Cin_t, R_t, 9, Wout, Hout, &p), "conv " + L->name + ": conv_regw route lost");
-        if (a.gn) {
-            RLDM_REQUIRE(a.gn->C == Cin_t && Cin_t % a.groups == 0, "conv " + L->name + ": GroupNorm channel mismatch");
-            RLDM_REQUIRE(x0.P > 0, "conv " + L->name + ": GroupNorm input without statistics");
-        }
+    int conv_regw(const ConvArgs& a, const ConvShape& s, ConvParams p, Tensor* out) {
+        if (require_gn_input(a, s.Cin_t)) return 1;
         p.dbg = kernel_dbg();
         p.ts = g_ts_buf;
         p.ntile_n = 1;
         Tensor y;
         if (!a.out_f32_nchw) {
-            y = make(x0.B, Wout, Hout, N);
+            y = make(a.x0.B, s.Wout, s.Hout, a.layer->Cout);
             if (a.want_stats) add_stats(y, conv_regw_partials(p));
         }
-        const double fl = 2.0 * (double)x0.B * Wout * Hout * N * (double)L->Cin * 9;
+        const double fl = conv_flops(a, s);
         plan->flops += fl;
         note_launch();
         if (!dry) {
             ConvLayer::Packed* pk = nullptr;
-            if (L->get_streampacked(Cin_t, 1, &pk)) return 1;
-            p.x0 = tptr(x0);
-            p.r0 = tptr(a.r0);
-            p.wpk = pk->w.as<bf16_t>();
-            p.bias = pk->bias.as<float>();
-            if (a.gn) {
-                p.st0 = sptr(x0);
-                p.P0 = x0.P;
-                p.gn_gamma = a.gn->gamma.as<float>();
-                p.gn_beta = a.gn->beta.as<float>();
-            }
-            if (y.valid()) {
-                p.y = tptr(y);
-                p.y_ld = N;
-                p.y_stats = y.P ? ptr<float2>(y.st_off) : nullptr;
-            }
-            const double by = (double)x0.B * x0.W * x0.H * Cin_t * 2.0 + (double)N * L->Cin * 9 * 2.0 +
-                              (double)x0.B * Wout * Hout * N * (a.out_f32_nchw ? 4.0 : 2.0) + (double)x0.B * Wout * Hout * R_t * 2.0;
+            if (a.layer->get_streampacked(s.Cin_t, 1, &pk)) return 1;
+            bind_conv(p, a, *pk, y);
             Plan* pl = plan;
-            const bool f32out = a.out_f32_nchw;
-            plan->ops.push_back({[p, pl, f32out](hipStream_t s) mutable {
-                if (f32out) {
-                    RLDM_REQUIRE(pl->io.sch.coef_table == nullptr, "conv_regw: a scheduler step fused into this output layer");
-                    p.y_nchw = pl->io.out;
-                }
-                return launch_conv_regw(p, s);
-            }, std::string("conv_regw_kernel<128,") + (f32out ? "32" : "64") + ",taps9>", fl, by});
+            const ConvLate late{-1, false, a.out_f32_nchw};          // (io.out without the scheduler step: the kernel has none)
+            emit({[p, pl, late](hipStream_t st) mutable {
+                RLDM_REQUIRE(!late.f32_out || pl->io.sch.coef_table == nullptr, "conv_regw: a scheduler step fused into this output layer");
+                late.apply(p, pl->io);
+                return launch_conv_regw(p, st);
+            }, std::string("conv_regw_kernel<128,") + (late.f32_out ? "32" : "64") + ",taps9>", fl, conv_bytes(a, s, 1, false)});
         }
         *out = y;
         return 0;
@@ -1762,28 +1586,24 @@ struct Builder {
         const int ord = conv_ord++;
         ConvLayer* L = a.layer;
         RLDM_REQUIRE(L != nullptr, "internal: missing conv layer");
-        const int taps = L->ksize * L->ksize;
-        const int Cin_t = a.x0.C + (a.x1.valid() ? a.x1.C : 0);
-        const int R_t = (a.r0.valid() ? a.r0.C : 0) + (a.r1.valid() ? a.r1.C : 0);
-        const int Wout = a.x0.W * a.up / a.stride, Hout = a.x0.H * a.up / a.stride;
         Tensor view;
+        if (vp && !recording && take_view(a.gn, &view)) {
+            a.x0 = view; a.x1 = Tensor(); a.gn = nullptr; a.silu = 0;
+        }
+        const ConvShape s = conv_shape(a);
         if (recording && vp) {
             // as a consumer: could this conv read cat[x0, x1] already normalised + activated?  (3x3 on the conv_small route)
             ConvArgs c = a;
-            c.x0.C = Cin_t; c.x1 = Tensor(); c.gn = nullptr; c.silu = 0;
-            if (a.gn) record_consumer(a.gn, a.x0, a.x1, a.silu, taps == 9 && small_route(c, Cin_t, R_t, taps, Wout, Hout), a.groups, a.eps);
+            c.x0.C = s.Cin_t; c.x1 = Tensor(); c.gn = nullptr; c.silu = 0;
+            if (a.gn) record_consumer(a.gn, a.x0, a.x1, a.silu, s.taps == 9 && small_route(c, s), a.groups, a.eps);
             // as a producer: with one tile per image, whether its own input arrives raw (statistics) or pre-activated
             ConvArgs o = a, oc = c;
             o.own_image = oc.own_image = true;
             if ((int)vp->can_emit.size() <= ord) vp->can_emit.resize(ord + 1, 0);
             if ((int)vp->out_c.size() <= ord) vp->out_c.resize(ord + 1, 0);
             vp->out_c[ord] = L->Cout;
-            vp->can_emit[ord] = !(dbg() & RLDM_FLAG_CONSUMER_GN) && !a.out_f32_nchw && small_route(o, Cin_t, R_t, taps, Wout, Hout) &&
-                                (!a.gn || small_route(oc, Cin_t, R_t, taps, Wout, Hout));
+            vp->can_emit[ord] = !(dbg() & RLDM_FLAG_CONSUMER_GN) && !a.out_f32_nchw && small_route(o, s) && (!a.gn || small_route(oc, s));
         } else if (vp) {
-            if (take_view(a.gn, &view)) {
-                a.x0 = view; a.x1 = Tensor(); a.gn = nullptr; a.silu = 0;
-            }
             auto it = vp->emit.find(ord);
             cur_emit = (it != vp->emit.end() && !it->second.empty()) ? &it->second : nullptr;
             // one tile per image: to normalise for the consumers, and (input ready, nothing to fold) to be a trunk phase
@@ -1791,7 +1611,7 @@ struct Builder {
                           (!a.gn && ord < (int)vp->can_emit.size() && vp->can_emit[ord] && !a.x1.valid());
         }
         const size_t ops_before = plan->ops.size(), ph_before = pend.standalone.size();
-        if (conv_route(a, out)) return 1;
+        if (conv_route(a, s, out)) return 1;
         if (!dry) {
             for (size_t i = ops_before; i < plan->ops.size(); ++i) plan->ops[i].tag += L->name + " ";
             for (size_t i = ph_before; i < pend.standalone.size(); ++i) pend.standalone[i].tag += L->name + " ";
@@ -1802,84 +1622,55 @@ struct Builder {
         if (out->valid()) live[out->id] = *out;
         return fold_stats(*out);
     }
-    int conv_route(const ConvArgs& a, Tensor* out) {
+    // the first route that admits the conv, in this order; its *_params has filled the ConvParams the emitter goes on with
+    int conv_route(const ConvArgs& a, const ConvShape& s, Tensor* out) {
         ConvLayer* L = a.layer;
-        RLDM_REQUIRE(L != nullptr, "internal: missing conv layer");
+        RLDM_REQUIRE(s.Cin_t >= L->Cin, "conv " + L->name + ": input tensor has fewer channels than the weights");
+        RLDM_REQUIRE(s.Cin_t % 16 == 0, "conv " + L->name + ": input channels must be a multiple of 16");
+        RLDM_REQUIRE(s.R_t == L->R, "conv " + L->name + ": residual sources do not match the layer's residual phase");
+        RLDM_REQUIRE((a.x0.W * a.up) % a.stride == 0 && (a.x0.H * a.up) % a.stride == 0, "conv " + L->name + ": odd size under stride 2");
+        RLDM_REQUIRE(s.R_t == 0 || (a.r0.W == s.Wout && a.r0.H == s.Hout), "conv " + L->name + ": residual resolution mismatch");
+        // (conv_in stays off the routes that cannot advance the sampler's step index: it is the step's first launch)
+        const bool first = a.first_of_step;
+        ConvParams p;
+        bool epi_res = false;
+        int bn = 0;
+        if (!first && small_route(a, s, &p, &epi_res, &bn)) return conv_small(a, s, p, epi_res, bn, out);
+        if (c16_params(a, s, &p)) return conv_c16(a, s, p, out);
+        if (o4_params(a, s, &p)) return conv_o4(a, s, p, out);
+        if (!first && ds2_params(a, s, &p)) return conv_ds2(a, s, p, out);
+        if (regw_params(a, s, &p)) return conv_regw(a, s, p, out);
+        if (!first && stream_params(a, s, &p)) return conv_stream(a, s, p, out);
+        return conv_generic(a, s, out);
+    }
+
+    // conv_igemm.hip: the implicit-GEMM kernel every other conv runs on, on the tile choose_tile picks
+    int conv_generic(const ConvArgs& a, const ConvShape& s, Tensor* out) {
+        ConvLayer* L = a.layer;
         const Tensor& x0 = a.x0;
-        const int Cin_t = x0.C + (a.x1.valid() ? a.x1.C : 0);      // tensor (padded) channels
-        RLDM_REQUIRE(Cin_t >= L->Cin, "conv " + L->name + ": input tensor has fewer channels than the weights");
-        RLDM_REQUIRE(Cin_t % 16 == 0, "conv " + L->name + ": input channels must be a multiple of 16");
-        const int R_t = (a.r0.valid() ? a.r0.C : 0) + (a.r1.valid() ? a.r1.C : 0);
-        RLDM_REQUIRE(R_t == L->R, "conv " + L->name + ": residual sources do not match the layer's residual phase");
-        const int taps = L->ksize * L->ksize;
-        const int Wv = x0.W * a.up, Hv = x0.H * a.up;
-        const int Wout = Wv / a.stride, Hout = Hv / a.stride;
-        RLDM_REQUIRE(Wv % a.stride == 0 && Hv % a.stride == 0, "conv " + L->name + ": odd size under stride 2");
-        RLDM_REQUIRE(R_t == 0 || (a.r0.W == Wout && a.r0.H == Hout), "conv " + L->name + ": residual resolution mismatch");
-        const int N = L->Cout;
-        // (conv_in stays on the generic kernel: it is the launch that advances the sampler's step index)
-        if (!a.first_of_step && small_route(a, Cin_t, R_t, taps, Wout, Hout)) return conv_small(a, Cin_t, R_t, taps, Wout, Hout, out);
-        {
-            ConvParams q;
-            if (c16_params(a, Cin_t, R_t, taps, Wout, Hout, &q)) return conv_c16(a, Wout, Hout, out);
-            if (o4_params(a, Cin_t, R_t, taps, Wout, Hout, &q)) return conv_o4(a, Wout, Hout, out);
-            if (!a.first_of_step && ds2_params(a, Cin_t, R_t, taps, Wout, Hout, &q)) return conv_ds2(a, Wout, Hout, out);
-            if (regw_params(a, Cin_t, R_t, taps, Wout, Hout, &q)) return conv_regw(a, Cin_t, R_t, Wout, Hout, out);
-        }
-        if (!a.first_of_step) {
-            ConvParams q;
-            if (stream_params(a, Cin_t, R_t, taps, Wout, Hout, &q)) return conv_stream(a, Cin_t, R_t, Wout, Hout, out);
-        }
-        const TileChoice tc = choose_tile(x0.B, Wout, Hout, a.stride, N, Cin_t, x0.C, R_t, a.r0.valid() ? a.r0.C : 0, taps,
+        const int N = L->Cout, Wout = s.Wout, Hout = s.Hout;
+        const TileChoice tc = choose_tile(x0.B, Wout, Hout, a.stride, N, s.Cin_t, x0.C, s.R_t, a.r0.valid() ? a.r0.C : 0, s.taps,
                                           a.out_f32_nchw, a.gn != nullptr);
         const ConvTile tile = tc.tile;
         RLDM_REQUIRE(conv_tile_supported(tile), "conv " + L->name + ": no kernel instance");
+        RLDM_REQUIRE((tc.TH & (tc.TH - 1)) == 0, "conv " + L->name + ": pixel tile height must be a power of two");
+        RLDM_REQUIRE(Wout % tc.TW == 0 && Hout % tc.TH == 0, "conv " + L->name + ": size not tileable (powers of two expected)");
 
         ConvParams p;
-        memset(&p, 0, sizeof(p));
-        p.C0 = x0.C;
-        p.C1 = a.x1.valid() ? a.x1.C : 0;
-        p.R0 = a.r0.valid() ? a.r0.C : 0;
-        p.R1 = a.r1.valid() ? a.r1.C : 0;
-        p.B = x0.B; p.Win = x0.W; p.Hin = x0.H;
-        p.up = a.up; p.stride = a.stride;
-        p.pad_lo = (L->ksize == 1) ? 0 : (a.pad_mode == 0 ? 1 : 0);
-        p.Wout = Wout; p.Hout = Hout;
-        p.TW = tc.TW; p.TH = tc.TH;
+        conv_geometry(a, s, tc.TW, tc.TH, (tc.TH - 1) * a.stride + (L->ksize == 3 ? 3 : 1), &p);
         p.colb = conv_halo_col_bytes(tile, tc.TH, a.stride);
-        p.tiles_h = Hout / p.TH;
-        p.tiles_img = (Wout / p.TW) * p.tiles_h;
-        RLDM_REQUIRE((p.TH & (p.TH - 1)) == 0, "conv " + L->name + ": pixel tile height must be a power of two");
-        p.th_shift = 0;
-        while ((1 << p.th_shift) < p.TH) ++p.th_shift;
-        {
-            const int thv = (p.TH - 1) * a.stride + (L->ksize == 3 ? 3 : 1);
-            p.magic_thv = ((1 << 20) + thv - 1) / thv;
-            const int cpg = std::max(1, Cin_t / a.groups);
-            p.magic_cpg = ((1 << 20) + cpg - 1) / cpg;
-            p.gn_inv_n = (float)(1.0 / ((double)x0.W * x0.H * cpg));
-        }
-        RLDM_REQUIRE(Wout % p.TW == 0 && Hout % p.TH == 0, "conv " + L->name + ": size not tileable (powers of two expected)");
-        p.N = N;
-        p.silu = a.silu;
-        p.gn_eps = a.eps;
         p.dbg = kernel_dbg();
         p.ts = stamp_buf(StampSite::Conv, conv_ord - 1);
-        p.gn_groups = a.groups;
         p.ksplit = tc.ksplit;
-        const int tiles_img = (Wout / p.TW) * (Hout / p.TH);
-        const int ntile_n = (N + tile.BN - 1) / tile.BN;
-        const long long tiles = (long long)x0.B * tiles_img * ntile_n;
+        p.ntile_n = (N + tile.BN - 1) / tile.BN;
+        const long long tiles = (long long)x0.B * p.tiles_img * p.ntile_n;
 
         Tensor y;
         if (!a.out_f32_nchw) {
             y = make(x0.B, Wout, Hout, N);
-            if (a.want_stats) add_stats(y, tiles_img);
+            if (a.want_stats) add_stats(y, p.tiles_img);
         }
-        if (a.gn) {
-            RLDM_REQUIRE(a.gn->C == Cin_t && Cin_t % a.groups == 0, "conv " + L->name + ": GroupNorm channel mismatch");
-            RLDM_REQUIRE(x0.P > 0 && (!a.x1.valid() || a.x1.P > 0), "conv " + L->name + ": GroupNorm input without statistics");
-        }
+        if (require_gn_input(a, s.Cin_t)) return 1;
         size_t slab_off = 0, slab_bytes = 0;
         int ticket_base = 0;
         if (tc.ksplit > 1) {
@@ -1888,58 +1679,25 @@ struct Builder {
             ticket_base = tickets;
             tickets += (int)tiles;
         }
-        plan->flops += 2.0 * (double)x0.B * Wout * Hout * N * ((double)L->Cin * taps + (L->sc_identity ? 0.0 : (double)L->R));
+        const double fl = conv_flops(a, s);
+        plan->flops += fl;
         note_launch();
         if (!dry) {
             ConvLayer::Packed* pk = nullptr;
-            if (L->get_packed(tile.BN, tile.CK, Cin_t, &pk)) return 1;
-            p.x0 = tptr(x0);
-            p.x1 = tptr(a.x1);
-            p.r0 = tptr(a.r0);
-            p.r1 = tptr(a.r1);
-            p.wpk = pk->w.as<bf16_t>();
-            p.bias = pk->bias.as<float>();
-            p.ntile_n = pk->ntile_n;
-            if (a.gn) {
-                p.st0 = sptr(x0);
-                p.st1 = sptr(a.x1);
-                p.P0 = x0.P;
-                p.P1 = a.x1.valid() ? a.x1.P : 0;
-                p.gn_gamma = a.gn->gamma.as<float>();
-                p.gn_beta = a.gn->beta.as<float>();
-            }
-            p.y = tptr(y);
-            p.y_ld = N;
-            p.y_stats = (y.valid() && y.P) ? ptr<float2>(y.st_off) : nullptr;
+            if (L->get_packed(tile.BN, tile.CK, s.Cin_t, &pk)) return 1;
+            bind_conv(p, a, *pk, y);
             if (tc.ksplit > 1) {
                 p.slab = ptr<float>(slab_off);
                 p.ticket = ticket_ptr + ticket_base;
             }
             Plan* pl = plan;
-            p.temb_ld = temb_ld;
-            const int temb_off = a.temb_off;
-            const bool f32out = a.out_f32_nchw;
-            const bool first_of_step = a.first_of_step;
-            const double fl = 2.0 * (double)x0.B * Wout * Hout * N * ((double)L->Cin * taps + (L->sc_identity ? 0.0 : (double)L->R));
-            const double by = (double)x0.B * x0.W * x0.H * Cin_t * 2.0 + (double)N * (L->Cin * taps + L->R) * 2.0 +
-                              (double)x0.B * Wout * Hout * N * (a.out_f32_nchw ? 4.0 : 2.0) +
-                              (double)x0.B * Wout * Hout * R_t * 2.0;
+            const ConvLate late{a.temb_off, a.first_of_step, a.out_f32_nchw, a.out_f32_nchw};
             const std::string kname = "conv_igemm_kernel<" + std::to_string(tile.BM) + "," + std::to_string(tile.BN) +
                                       ",CK" + std::to_string(tile.CK) + ",taps" + std::to_string(tile.taps) + ">";
-            plan->ops.push_back({[p, tile, pl, temb_off, f32out, first_of_step](hipStream_t s) mutable {
-                p.step_inc = (first_of_step && pl->io.pack_fused) ? pl->io.step_inc : nullptr;
-                if (temb_off >= 0) {
-                    p.temb = pl->io.temb + temb_off;
-                    p.step_ptr = pl->io.step_ptr;
-                    p.temb_rows_per_step = pl->io.temb_rows_per_step;
-                    p.temb_per_sample = pl->io.temb_per_sample;
-                }
-                if (f32out) {
-                    p.y_nchw = pl->io.out;
-                    p.sch = pl->io.sch;
-                }
-                return launch_conv(tile, p, s);
-            }, kname, fl, by});
+            emit({[p, tile, pl, late](hipStream_t st) mutable {
+                late.apply(p, pl->io);
+                return launch_conv(tile, p, st);
+            }, kname, fl, conv_bytes(a, s)});
         }
         if (tc.ksplit > 1) arena.release(slab_off, slab_bytes);
         *out = y;
@@ -2145,7 +1903,7 @@ struct NetCommon {
         C2.eps = eps; C2.groups = groups; C2.silu = 1;
         C2.r0 = x;
         Tensor u;
-        if (!b.small_route(C2, h1.C, x.C, 9, h1.W, h1.H)) {
+        if (!Builder::small_route(C2, conv_shape(C2))) {
             // the 3x3 tile and the shortcut's input tile do not fit the LDS together (64x4 images: 112 + 67 KB): the shortcut over x
             // becomes a pointwise conv of its own as well --  u0 = conv2(..) + b;  u = shortcut[:, :x.C](x) + u0
             ConvLayer* c2m = layers.get_conv(p + ".conv2@main");
@@ -2304,7 +2062,7 @@ struct NetCommon {
                     ConvLayer* Lo = layers.get_conv(p + ".to_out.0");
                     ConvLayer::Packed* pk = nullptr;
                     RLDM_REQUIRE(Lo && Lo->Cin == x.C && Lo->Cout == x.C && Lo->sc_identity, "attention " + p + ": unexpected to_out");
-                    if (Lo->get_fragpacked(x.C, 1, true, &pk)) return 1;
+                    if (Lo->get_fragpacked(x.C, 32, 1, true, &pk)) return 1;
                     ap.proj_w = pk->w.as<bf16_t>();
                     ap.proj_bias = pk->bias.as<float>();
                     ap.proj_res = b.tptr(x);
