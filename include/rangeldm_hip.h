@@ -357,6 +357,34 @@ int rldm_matrix_row_argmin(const double* m, int rows, int cols, int exclude_diag
 int rldm_emd_matrix(const float* x, const int32_t* x_offsets, int x_stride, int nx, const float* y, const int32_t* y_offsets,
                     int y_stride, int ny, int symmetric, float eps, double* emd_out, int32_t* assign_out, float* price_out,
                     int32_t* bids_out, void* stream);
+/* ---- Frechet distance over dumped activations (rangeldm_amd/csrc/frechet.hip) --------------------------------------- */
+#define RLDM_FRECHET_SWEEP_CAP 2   /* return value: the Jacobi loop ran max_sweeps sweeps and the last still rotated */
+#define RLDM_FRECHET_NONFINITE 3   /* return value: an input holds NaN or inf (nothing was computed) */
+#define RLDM_FRECHET_MAX_SWEEPS 60 /* the host-side sweep cap rldm_frechet_distance runs with */
+/* out [n1][n2] = a . b^T for device fp64 a [n1][d], b [n2][d] on v_mfma_f64_16x16x4_f64; edge tiles are zero filled.
+ * K is walked in one ascending order by one workgroup per tile (no split-K, no atomics): an entry depends on its two rows
+ * and d alone, whatever tile or call it is computed in. */
+int rldm_gram_f64(const double* a, int n1, const double* b, int n2, int d, double* out, void* stream);
+/* Singular values of a device fp64 matrix m [rows][cols] by one-sided (Hestenes) Jacobi on the orientation with fewer
+ * columns: round-robin pair order (column count padded to even, count - 1 steps per sweep), ONE LAUNCH PER STEP with one
+ * workgroup per column pair, no workgroup ever waiting on another.  A pair with |a_p . a_q| <= tol |a_p| |a_q|, or with a
+ * zero column, or whose rotation rounds to the identity, is left alone and not counted; tol <= 0 selects
+ * sqrt(column length) * 2^-52.  The host reads the count of rotations once per sweep and stops after the first sweep that
+ * applied none; *sweeps_out (host, may be NULL) is the number of sweeps
+ * run.  After max_sweeps sweeps that all rotated the call returns RLDM_FRECHET_SWEEP_CAP; NaN / inf in m returns
+ * RLDM_FRECHET_NONFINITE before the loop.  sv_out device fp64 [min(rows, cols)]: the final column norms, sorted
+ * descending.  Every reduction runs in a fixed order: two calls agree bit for bit.  The call synchronises the stream. */
+int rldm_singular_values_f64(const double* m, int rows, int cols, double tol, int max_sweeps, double* sv_out,
+                             int* sweeps_out, void* stream);
+/* Frechet distance between the Gaussians fitted (np.mean, np.cov) to two sets of activations x [n1][d], y [n2][d] (device
+ * fp64, n1, n2 >= 2): metrics/metrics/fid/fid_score.py calculate_frechet_distance, without any d x d matrix.  With A, B
+ * the centred sets, Tr sqrtm(C1 C2) = |A B^T|_* / sqrt((n1 - 1)(n2 - 1)) (nuclear norm), Tr C1 = sum A^2 / (n1 - 1).
+ * out5 (HOST fp64 [5]) = {distance, |mu1 - mu2|^2, Tr C1, Tr C2, Tr sqrtm(C1 C2)}; distance = [1] + [2] + [3] - 2 [4],
+ * not clamped at 0.  Return values as rldm_singular_values_f64 (default tol, RLDM_FRECHET_MAX_SWEEPS); the inputs are
+ * checked for NaN / inf before anything else.  The call synchronises the stream. */
+int rldm_frechet_distance(const double* x, int n1, const double* y, int n2, int d, double* out5, void* stream);
+/* Sweeps the Jacobi loop of this thread's last rldm_frechet_distance call ran (0 before the first). */
+int rldm_frechet_last_sweeps(void);
 /* Range-image errors (ldm/convert_vae.py:236-247 MAE / PSNR; metrics/metrics/mae.py:45-117 range MAE): a, b device fp32
  * (B, C, W, H), C <= 8.  Per image, over the channels of channel_mask and the azimuth columns (w0 + k) mod W,
  * k in [0, w1 - w0) (0 <= w0 < W, w0 < w1 <= w0 + W: the window may wrap past the seam), with v -> v * scale[c] + shift[c]

@@ -13,6 +13,8 @@ RLDM_SAMPLER_DDIM, RLDM_SAMPLER_DDPM, RLDM_SAMPLER_DPMSOLVER = 0, 1, 2
 # rldm_emd_matrix: the `symmetric` argument, and the return value that reports a pair at the bid cap
 RLDM_EMD_RECT, RLDM_EMD_SYMMETRIC, RLDM_EMD_DIAGONAL = 0, 1, 2
 RLDM_EMD_BID_CAP = 2
+# rldm_singular_values_f64 / rldm_frechet_distance: the return values that are not the ordinary error
+RLDM_FRECHET_SWEEP_CAP, RLDM_FRECHET_NONFINITE, RLDM_FRECHET_MAX_SWEEPS = 2, 3, 60
 
 
 class Flag(enum.IntFlag):
@@ -167,6 +169,11 @@ PROTOTYPES = {
     "rldm_matrix_row_argmin": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     # all-pairs Earth Mover's Distance (epsilon-scaling auction) between equal-size clouds: emd, assignment, prices, bids
     "rldm_emd_matrix": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, _P]),
+    # Frechet distance over dumped activations: fp64 Gram product (MFMA), one-sided Jacobi singular values, the distance
+    "rldm_gram_f64": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
+    "rldm_singular_values_f64": (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_int, _P, C.POINTER(C.c_int), _P]),
+    "rldm_frechet_distance": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_double), _P]),
+    "rldm_frechet_last_sweeps": (C.c_int, []),
     # MAE / PSNR of ldm/convert_vae.py:236-247 and the range MAE of metrics/metrics/mae.py:45-117
     "rldm_range_errors": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
                                     C.POINTER(C.c_float), C.c_int, C.c_int, _P, _P, _P]),

@@ -6,6 +6,7 @@
     python -m rangeldm_amd.evaluate chamfer A_DIR B_DIR
     python -m rangeldm_amd.evaluate generation GEN_DIR REF_DIR [--points 2048] [--limit N] [--seed 0] [--max-depth M]
                                                [--emd [--emd-eps 0.0078125]]
+    python -m rangeldm_amd.evaluate frd FOLDER1 FOLDER2 [--limit 1100]
 
 Every command prints one JSON object on stdout (`--json PATH` also writes it).  Under `torch.distributed.run` the work is
 sharded over the ranks and rank 0 reduces and prints.  The arithmetic runs in librangeldm_hip (rangeldm_amd/csrc/chamfer.hip
@@ -32,6 +33,11 @@ mean_x min_y |x - y|^2 + mean_y min_x |x - y|^2 over xyz.
                  and 1-NNA-EMD from the all-pairs Earth Mover's Distance matrices (metrics.emd_matrix: an auction that ends
                  at --emd-eps metres); EMD is a one-to-one matching, so every cloud must then hold exactly --points points
                  (at most 2 048) after the depth cut.
+  frd            `metric.py --fid --fid_folder1 FOLDER1 --fid_folder2 FOLDER2` (metrics/metrics/fid/lidargen_fid.py get_fid): the
+                 Frechet distance between two folders of dumped RangeNet++ activations (`.npy`, 2 097 152 values each), on
+                 the reference's 4 096 randomly drawn values per file and at most --limit files per folder (sorted by name),
+                 by metrics.frechet_distance.  The work is one small matrix: rank 0 alone loads and computes, so the output
+                 is the same for any number of ranks.  (Producing the activations -- RangeNet++ inference -- is not here.)
 
 Only the linear range normalisation (x * std + mean, every shipped config) is supported: `log` / `inverse` sensors raise
 NotImplementedError.  nuScenes `.bin` files carry no ring column, so they cannot be re-projected: nuScenes raises too.
@@ -92,7 +98,14 @@ def build_parser():
     g.add_argument("--emd-eps", type=float, default=2.0 ** -7,
                    help="final epsilon of the EMD auction, metres: the matching cost is within about this of the optimum")
 
-    for p in (v, *[sub.choices[k] for k in ("densification", "inpainting")], c, g):
+    f = sub.add_parser("frd", help="Frechet distance between two folders of dumped activations (metric.py --fid)")
+    f.add_argument("folder1")
+    f.add_argument("folder2")
+    f.add_argument("--limit", type=int, default=1100, help="use the first N files (sorted by name) of each folder")
+    f.add_argument("--total", type=int, default=2097152, help="values per dumped file (other than the default: tests)")
+    f.add_argument("--count", type=int, default=4096, help="values drawn per file (other than the default: tests)")
+
+    for p in (v, *[sub.choices[k] for k in ("densification", "inpainting")], c, g, f):
         p.add_argument("--json", default=None, help="also write the result object to this file")
     return ap
 
@@ -433,7 +446,27 @@ def cmd_generation(a, rank, world, dev):
     return result
 
 
-COMMANDS = {"generation": cmd_generation, "vae": cmd_vae, "densification": cmd_densification, "inpainting": cmd_inpainting, "chamfer": cmd_chamfer}
+def check_frd_args(a):
+    """`frd`: what can be refused before a file is read."""
+    if a.limit < 2:
+        raise ValueError(f"--limit must be at least 2 (a covariance needs 2 samples), got {a.limit}")
+    if not 1 <= a.count <= a.total:
+        raise ValueError(f"--count {a.count} values cannot be drawn from --total {a.total}")
+
+
+def cmd_frd(a, rank, world, dev):
+    from .metrics import frd_indices, frechet_distance, load_activations
+    check_frd_args(a)
+    if rank != 0:                                        # one small matrix: nothing to shard
+        return None
+    idx = frd_indices(a.total, a.count)
+    x = load_activations(a.folder1, idx, a.limit, a.total, dev)
+    y = load_activations(a.folder2, idx, a.limit, a.total, dev)
+    terms = frechet_distance(x, y, return_terms=True)
+    return {"task": "frd", **terms, "n1": int(x.shape[0]), "n2": int(y.shape[0]), "dims": int(x.shape[1])}
+
+
+COMMANDS = {"frd": cmd_frd, "generation": cmd_generation, "vae": cmd_vae, "densification": cmd_densification, "inpainting": cmd_inpainting, "chamfer": cmd_chamfer}
 
 
 def main(argv=None):

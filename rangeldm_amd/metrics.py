@@ -16,6 +16,11 @@ Yang et al. 2019); set_metrics_host is the numpy statement of the three reductio
 Earth Mover's Distance (rangeldm_amd/csrc/emd.hip): emd_matrix / emd_pairs, an epsilon-scaling auction between equal-size
 clouds that returns the assignment and the dual prices with the value; generation_metrics(emd=True) adds MMD-EMD / COV-EMD /
 1-NNA-EMD.
+
+Frechet distance (rangeldm_amd/csrc/frechet.hip; metrics/metrics/fid/{lidargen_fid.py, fid_score.py}, the `--fid` command
+over two folders of dumped activations): frechet_distance from an fp64 Gram product (gram_f64, on the fp64 MFMA) and its
+singular values (singular_values, one-sided Jacobi); frechet_distance_host is the numpy statement, frd_indices and
+load_activations the reference's index draw and file reading.
 """
 import ctypes as C
 
@@ -399,6 +404,161 @@ def emd_pairs(x, y, eps=EMD_EPS, x_lengths=None, y_lengths=None):
     yp, yo, yk = _pack(ys)
     out, _, _, _ = _emd_call(xp, xo, xk, len(xs), yp, yo, yk, len(ys), _lib.RLDM_EMD_DIAGONAL, eps, n, False)
     return torch.diagonal(out).clone()
+
+
+# ---- Frechet distance over dumped activations (rangeldm_amd/csrc/frechet.hip) -------------------------------------------
+class FrechetConvergenceError(RuntimeError):
+    """The Jacobi loop reached its sweep cap (60 sweeps) with rotations still being applied; no value is returned."""
+
+
+def _frechet_status(rc, message, what):
+    """Map the return value of rldm_singular_values_f64 / rldm_frechet_distance: 0 passes; the sweep cap raises
+    FrechetConvergenceError, non-finite input ValueError; anything else is the library's ordinary error."""
+    if rc == 0:
+        return
+    if rc == _lib.RLDM_FRECHET_SWEEP_CAP:
+        raise FrechetConvergenceError(f"{what}: {message}")
+    if rc == _lib.RLDM_FRECHET_NONFINITE:
+        raise ValueError(f"{what}: {message}")
+    raise RuntimeError(f"librangeldm_hip: {what} failed: {message}")
+
+
+def _frechet_check(rc, what):
+    if rc != 0:
+        msg = _lib.lib().rldm_last_error()
+        _frechet_status(rc, msg.decode() if msg else "unknown error", what)
+
+
+def _require_matrix(m, name):
+    """ValueError unless m is a non-empty 2-D float tensor (checked before the device and the library are looked at)."""
+    if not torch.is_tensor(m) or m.dim() != 2 or m.shape[0] == 0 or m.shape[1] == 0:
+        raise ValueError(f"{name} must be a non-empty 2-D tensor, got {tuple(m.shape) if torch.is_tensor(m) else type(m)}")
+    if not m.is_floating_point():
+        raise ValueError(f"{name} must hold floating-point values, got {m.dtype}")
+    return m
+
+
+def _on_device(*tensors):
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError("activations and matrices must live on the GPU (rangeldm_amd has no CPU path)")
+    return [t.detach().to(torch.float64).contiguous() for t in tensors]
+
+
+def _activation_sets(x, y):
+    x, y = _require_matrix(x, "x"), _require_matrix(y, "y")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"x holds {x.shape[1]} values per sample, y {y.shape[1]}")
+    if x.shape[0] < 2 or y.shape[0] < 2:
+        raise ValueError(f"a covariance needs at least 2 samples per set, got {x.shape[0]} and {y.shape[0]}")
+    return x, y
+
+
+def gram_f64(a, b):
+    """a . b^T for (n1, d) and (n2, d) device tensors, in fp64 on the fp64 MFMA: an fp64 device (n1, n2) tensor.  K is walked
+    in one fixed order without split-K, so an entry depends on its two rows alone (a block of rows computed on its own equals
+    those rows of the whole product bit for bit); operands and sums that are exact in fp64 give the exact product."""
+    a, b = _require_matrix(a, "a"), _require_matrix(b, "b")
+    if a.shape[1] != b.shape[1]:
+        raise ValueError(f"a holds {a.shape[1]} values per row, b {b.shape[1]}")
+    a, b = _on_device(a, b)
+    _lib.require_gpu()
+    out = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float64, device=a.device)
+    _lib.check(_lib.lib().rldm_gram_f64(a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0], a.shape[1], out.data_ptr(),
+                                        _lib.stream_ptr(a.device)), "rldm_gram_f64")
+    return out
+
+
+def singular_values(m, tol=None, max_sweeps=60, return_sweeps=False):
+    """The singular values of a (rows, cols) device tensor, fp64, sorted descending: min(rows, cols) of them.  One-sided
+    (Hestenes) Jacobi on the orientation with fewer columns, round-robin pair order, one launch per step.  A
+    pair of columns is left alone once |a_p . a_q| <= tol |a_p| |a_q| (tol None: sqrt(column length) * 2^-52); the loop ends
+    with the first sweep that rotates nothing.  return_sweeps=True returns (values, sweeps run).  Raises ValueError for
+    NaN / inf entries and FrechetConvergenceError when max_sweeps sweeps all rotated."""
+    m = _require_matrix(m, "m")
+    if int(max_sweeps) < 1:
+        raise ValueError(f"max_sweeps must be at least 1, got {max_sweeps}")
+    (m,) = _on_device(m)
+    _lib.require_gpu()
+    sv = torch.empty(min(m.shape), dtype=torch.float64, device=m.device)
+    sweeps = C.c_int(0)
+    _frechet_check(_lib.lib().rldm_singular_values_f64(m.data_ptr(), m.shape[0], m.shape[1], 0.0 if tol is None else float(tol),
+                                                       int(max_sweeps), sv.data_ptr(), C.byref(sweeps),
+                                                       _lib.stream_ptr(m.device)), "rldm_singular_values_f64")
+    return (sv, sweeps.value) if return_sweeps else sv
+
+
+def frechet_distance(x, y, return_terms=False):
+    """metrics/metrics/fid/fid_score.py calculate_frechet_distance(np.mean(x, 0), np.cov(x, rowvar=False), ... of y): the
+    Frechet distance between the Gaussians fitted to two sets of activations, (n1, d) and (n2, d) device tensors of any float
+    dtype (converted to fp64), n1, n2 >= 2.  No d x d matrix is formed: with A, B the centred sets,
+
+        Tr sqrtm(C1 C2) = |A B^T|_* / sqrt((n1 - 1)(n2 - 1))         (nuclear norm: the sum of singular values)
+
+    so the work is two column means, two sums of squares, one (n1, n2) Gram product over d and the singular values of that
+    matrix.  Every reduction runs in a fixed order: two calls agree bit for bit.  The value is NOT clamped at 0 (the reference
+    does not clamp): identical sets give a rounding-sized number of either sign.
+
+    Returns the distance as a float; return_terms=True returns a dict: frd, mean_sq (|mu1 - mu2|^2), tr1, tr2 (Tr C1, Tr C2),
+    tr_sqrt (Tr sqrtm(C1 C2)) and sweeps (Jacobi sweeps run); frd = mean_sq + tr1 + tr2 - 2 tr_sqrt.
+    Raises ValueError for shapes that do not fit (before the device) and for NaN / inf activations, RuntimeError for host
+    tensors, FrechetConvergenceError if the Jacobi loop reaches its cap of 60 sweeps."""
+    x, y = _activation_sets(x, y)
+    x, y = _on_device(x, y)
+    _lib.require_gpu()
+    out = (C.c_double * 5)()
+    L = _lib.lib()
+    _frechet_check(L.rldm_frechet_distance(x.data_ptr(), x.shape[0], y.data_ptr(), y.shape[0], x.shape[1], out,
+                                           _lib.stream_ptr(x.device)), "rldm_frechet_distance")
+    if not return_terms:
+        return out[0]
+    return {"frd": out[0], "mean_sq": out[1], "tr1": out[2], "tr2": out[3], "tr_sqrt": out[4],
+            "sweeps": int(L.rldm_frechet_last_sweeps())}
+
+
+def frechet_distance_host(x, y):
+    """The numpy statement of frechet_distance, fp64: np.linalg.svd(A @ B.T, compute_uv=False).sum() for the trace term."""
+    import numpy as np
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    if x.ndim != 2 or y.ndim != 2 or x.shape[1] != y.shape[1] or x.shape[0] < 2 or y.shape[0] < 2:
+        raise ValueError(f"x and y must be (n >= 2, d) with the same d, got {x.shape} and {y.shape}")
+    mu1, mu2 = x.mean(0), y.mean(0)
+    a, b = x - mu1, y - mu2
+    n1, n2 = x.shape[0], y.shape[0]
+    diff = mu1 - mu2
+    tr_sqrt = np.linalg.svd(a @ b.T, compute_uv=False).sum() / np.sqrt((n1 - 1.0) * (n2 - 1.0))
+    return float(diff.dot(diff) + (a * a).sum() / (n1 - 1) + (b * b).sum() / (n2 - 1) - 2.0 * tr_sqrt)
+
+
+FRD_TOTAL, FRD_COUNT, FRD_LIMIT = 2097152, 4096, 1100     # values per dumped file, values kept, files used per folder
+
+
+def frd_indices(total=FRD_TOTAL, count=FRD_COUNT, seed=0):
+    """metrics/metrics/fid/lidargen_fid.py get_fid's draw: `random.seed(seed); random.sample(range(total), count)`."""
+    import random
+    return random.Random(seed).sample(range(total), count)
+
+
+def load_activations(folder, indices, limit=FRD_LIMIT, total=FRD_TOTAL, device="cuda"):
+    """lidargen_fid.py load_activations: `np.load(f).reshape(-1)[indices]` of the `.npy` files of `folder`, stacked into a
+    (files, len(indices)) tensor on `device` in the files' dtype.  At most `limit` files are used, taken in SORTED order: the
+    reference takes them in glob order and then `[0:1100]`, which is an arbitrary subset once a folder holds more than 1 100
+    files; sorted order makes the choice a function of the names.  A file whose flattened size is not `total` raises
+    ValueError naming it."""
+    import glob
+    import os
+    import numpy as np
+    files = sorted(glob.glob(os.path.join(folder, "*.npy")))[:limit]
+    if not files:
+        raise FileNotFoundError(f"no .npy files in {folder}")
+    idx = np.asarray(indices, dtype=np.int64)
+    rows = []
+    for path in files:
+        flat = np.load(path).reshape(-1)
+        if flat.shape[0] != total:
+            raise ValueError(f"{path}: {flat.shape[0]} values, expected {total}")
+        rows.append(flat[idx])
+    return torch.from_numpy(np.stack(rows, 0)).to(device)
 
 
 def subsample(cloud, n, seed):
