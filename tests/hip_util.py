@@ -16,6 +16,12 @@ def rel_l2(a, b):
     return float((a - b).norm() / (b.norm() + 1e-30))
 
 
+def _ulps(a, b):
+    a, b = a.double(), b.double()
+    ulp = torch.from_numpy(np.spacing(np.abs(b.numpy()).astype(np.float32)).astype(np.float64))
+    return float(((a - b).abs() / ulp).max())
+
+
 def hip_conv(x0, weight, bias, x1=None, stride=1, pad_mode=0, upsample=False, gamma=None, beta=None, silu=False,
              eps=1e-5, temb=None, res=None):
     """rldm_test_conv: fp32 NCHW tensors in/out, the kernel under test in the middle."""

@@ -14,7 +14,7 @@ import pytest
 import torch
 
 from rangeldm_amd import _lib
-from tests.hip_util import (RefCache, assert_bitexact, assert_exact_bound, bf16_rne, hip_attention, hip_attention_qkv,
+from tests.hip_util import (RefCache, _ulps, assert_bitexact, assert_exact_bound, bf16_rne, hip_attention, hip_attention_qkv,
                             selective_operands, selective_reference)
 
 pytestmark = pytest.mark.gpu
@@ -206,12 +206,6 @@ def _one_hot_dO(B, L, Cc, seed):
     idx = torch.randint(0, 8, (B, L, Cc // 8, 1), generator=g)
     val = (torch.randint(0, 2, idx.shape, generator=g) * 2 - 1).float() * 2.0 ** torch.randint(0, 2, idx.shape, generator=g).float()
     return dO.scatter_(-1, idx, val).view(B, L, Cc)
-
-
-def _ulps(a, b):
-    a, b = a.double(), b.double()
-    ulp = torch.from_numpy(np.spacing(np.abs(b.numpy()).astype(np.float32)).astype(np.float64))
-    return float(((a - b).abs() / ulp).max())
 
 
 @pytest.mark.parametrize("B,L,Cc", TRAIN)
