@@ -357,6 +357,28 @@ int rldm_matrix_row_argmin(const double* m, int rows, int cols, int exclude_diag
 int rldm_emd_matrix(const float* x, const int32_t* x_offsets, int x_stride, int nx, const float* y, const int32_t* y_offsets,
                     int y_stride, int ny, int symmetric, float eps, double* emd_out, int32_t* assign_out, float* price_out,
                     int32_t* bids_out, void* stream);
+/* ---- farthest point sampling (rangeldm_amd/csrc/fps.hip) ------------------------------------------------------------- */
+#define RLDM_FPS_BLOCK 1024              /* lanes of the one workgroup a cloud gets: point i belongs to lane i mod 1024 */
+#define RLDM_FPS_RESIDENT_POINTS 65536   /* a cloud's first 64 x 1024 points keep their min-distance in registers */
+#define RLDM_FPS_MAX_POINTS 1048576      /* the largest cloud accepted */
+/* Farthest point sampling of every cloud of a ragged batch packed as rldm_chamfer_matrix takes it (x device fp32
+ * [n][stride >= 3], only xyz read; offsets device int32 [num_clouds + 1], starting at 0): k indices per cloud, LOCAL to the
+ * cloud, in selection order -- idx_out device int32 [num_clouds][k].  start (device int32 [num_clouds], local indices) is
+ * the first selected point of each cloud; NULL means 0.  Per cloud, all fp32, one rounding per operation, no contraction:
+ *   mind[i] = +inf for every i; sel = start; then k times:
+ *     emit sel;  d = ((dx*dx + dy*dy) + dz*dz), dx = x[i] - x[sel] (rldm_chamfer_nn's expression);
+ *     mind[i] = min(mind[i], d);  mind[sel] = -inf;  sel = the LOWEST index attaining max_i mind[i]
+ * The -inf sentinel keeps a selected index from being selected again: the k indices are distinct, also on clouds full of
+ * duplicate points.  The result depends on the cloud, k and start alone (not on the batch or the stride) and equals a
+ * sequential CPU evaluation exactly; the indices for k are the first k of those for any larger k.
+ * One workgroup per cloud, no atomics.  The min-distances of a cloud's first RLDM_FPS_RESIDENT_POINTS points live in
+ * registers; those of the points past them in a workspace of one fp32 per packed point, taken with hipMallocAsync on
+ * `stream` for the call and freed before it returns -- only when a cloud is that large.
+ * Required, else an error naming the cloud (rldm_last_error): 1 <= k <= points of every cloud <= RLDM_FPS_MAX_POINTS,
+ * 0 <= start < points, points * stride * 4 < 2^31, num_clouds * k < 2^31.  Non-finite coordinates give an unspecified
+ * selection (still k in-range indices).  The call synchronises the stream. */
+int rldm_farthest_point_sample(const float* x, const int32_t* offsets, int stride, int num_clouds, int k, const int32_t* start,
+                               int32_t* idx_out, void* stream);
 /* ---- Frechet distance over dumped activations (rangeldm_amd/csrc/frechet.hip) --------------------------------------- */
 #define RLDM_FRECHET_SWEEP_CAP 2   /* return value: the Jacobi loop ran max_sweeps sweeps and the last still rotated */
 #define RLDM_FRECHET_NONFINITE 3   /* return value: an input holds NaN or inf (nothing was computed) */

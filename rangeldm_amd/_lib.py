@@ -169,6 +169,8 @@ PROTOTYPES = {
     "rldm_matrix_row_argmin": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     # all-pairs Earth Mover's Distance (epsilon-scaling auction) between equal-size clouds: emd, assignment, prices, bids
     "rldm_emd_matrix": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, _P]),
+    # farthest point sampling of a ragged batch of clouds: k local indices per cloud, in selection order
+    "rldm_farthest_point_sample": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     # Frechet distance over dumped activations: fp64 Gram product (MFMA), one-sided Jacobi singular values, the distance
     "rldm_gram_f64": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
     "rldm_singular_values_f64": (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_int, _P, C.POINTER(C.c_int), _P]),

@@ -5,7 +5,7 @@
     python -m rangeldm_amd.evaluate inpainting --exp outputs/inpainting/generated [--cfg inpainting]
     python -m rangeldm_amd.evaluate chamfer A_DIR B_DIR
     python -m rangeldm_amd.evaluate generation GEN_DIR REF_DIR [--points 2048] [--limit N] [--seed 0] [--max-depth M]
-                                               [--emd [--emd-eps 0.0078125]]
+                                               [--sampling {random,fps}] [--emd [--emd-eps 0.0078125]]
     python -m rangeldm_amd.evaluate frd FOLDER1 FOLDER2 [--limit 1100]
 
 Every command prints one JSON object on stdout (`--json PATH` also writes it).  Under `torch.distributed.run` the work is
@@ -27,7 +27,8 @@ mean_x min_y |x - y|^2 + mean_y min_x |x - y|^2 over xyz.
   generation     set-level metrics of a folder of generated .bin clouds against a folder of reference sweeps (Achlioptas et
                  al. 2018; Yang et al. 2019): MMD-CD, COV-CD and 1-NNA-CD (metrics.set_metrics) from the all-pairs Chamfer
                  matrices, every cloud cut to the points closer than --max-depth and sub-sampled to --points
-                 (metrics.subsample with seed + file index); the BEV-histogram jsd / mmd of metrics.evaluate_folders on the
+                 (metrics.subsample with seed + file index; --sampling fps: by farthest point sampling, the protocol's
+                 choice, metrics.farthest_point_sample, and the object then carries "sampling": "fps"); the BEV-histogram jsd / mmd of metrics.evaluate_folders on the
                  full clouds beside them.  Each rank computes a block of rows of each matrix; an entry does not depend on the
                  block it was computed in, so the result is the same for any number of ranks.  --emd adds MMD-EMD, COV-EMD
                  and 1-NNA-EMD from the all-pairs Earth Mover's Distance matrices (metrics.emd_matrix: an auction that ends
@@ -91,6 +92,9 @@ def build_parser():
     g.add_argument("--limit", type=int, default=None, help="use the first N files (sorted by name) of each folder")
     g.add_argument("--seed", type=int, default=0, help="sub-sampling seed (file i uses seed + i)")
     g.add_argument("--max-depth", type=float, default=None, help="drop points at this distance from the sensor or farther")
+    g.add_argument("--sampling", choices=("random", "fps"), default="random",
+                   help="how a cloud is cut to --points: a uniform random draw, or farthest point sampling (started at a "
+                        "seeded random point)")
     g.add_argument("--columns", type=int, default=4, choices=(4, 5),
                    help="float32 columns per point of the REFERENCE files (5: nuScenes sweeps); generated files have 4")
     g.add_argument("--emd", action="store_true",
@@ -388,17 +392,24 @@ def _matrix_over_ranks(xs, ys, rank, world, matrix=None):
     return full
 
 
-def load_generation_clouds(files, columns, points, seed, max_depth, device):
-    """xyz of every file: the points closer than max_depth (None: all), then subsample(.., points, seed + file index)."""
-    from .metrics import subsample
+GENERATION_CHUNK = 256      # files read, cut and sub-sampled together (sampling="fps": one kernel launch per chunk)
+
+
+def load_generation_clouds(files, columns, points, seed, max_depth, device, sampling="random"):
+    """xyz of every file: the points closer than max_depth (None: all), then subsample(.., points, seed + file index,
+    sampling), GENERATION_CHUNK files at a time through metrics.subsample_batch."""
+    from .metrics import subsample_batch
     clouds = []
-    for i, path in enumerate(files):
-        xyz = _load_bin(path, columns, device)[:, :3]
-        if max_depth is not None:
-            xyz = xyz[xyz.norm(dim=1) < max_depth]
-        if xyz.shape[0] == 0:
-            raise ValueError(f"{path}: no point left (max_depth={max_depth})")
-        clouds.append(subsample(xyz, points, seed + i))
+    for lo in range(0, len(files), GENERATION_CHUNK):
+        chunk = []
+        for path in files[lo:lo + GENERATION_CHUNK]:
+            xyz = _load_bin(path, columns, device)[:, :3]
+            if max_depth is not None:
+                xyz = xyz[xyz.norm(dim=1) < max_depth]
+            if xyz.shape[0] == 0:
+                raise ValueError(f"{path}: no point left (max_depth={max_depth})")
+            chunk.append(xyz)
+        clouds.extend(subsample_batch(chunk, points, [seed + lo + i for i in range(len(chunk))], sampling))
     return clouds
 
 
@@ -427,12 +438,14 @@ def cmd_generation(a, rank, world, dev):
     ref_files = sorted(glob.glob(os.path.join(a.ref_dir, "*.bin")))[:a.limit]
     if not gen_files or not ref_files:
         raise FileNotFoundError(f"no .bin files in {a.gen_dir if not gen_files else a.ref_dir}")
-    gen = load_generation_clouds(gen_files, 4, a.points, a.seed, a.max_depth, dev)
-    ref = load_generation_clouds(ref_files, a.columns, a.points, a.seed, a.max_depth, dev)
+    gen = load_generation_clouds(gen_files, 4, a.points, a.seed, a.max_depth, dev, a.sampling)
+    ref = load_generation_clouds(ref_files, a.columns, a.points, a.seed, a.max_depth, dev, a.sampling)
     if a.emd:
         require_emd_sizes(gen_files, gen, a.points)
         require_emd_sizes(ref_files, ref, a.points)
     result = {"task": "generation", "points": a.points}
+    if a.sampling != "random":                           # (the default's object is what it was: no new key)
+        result["sampling"] = a.sampling
     result.update(set_metrics(_matrix_over_ranks(gen, None, rank, world), _matrix_over_ranks(gen, ref, rank, world),
                               _matrix_over_ranks(ref, None, rank, world)))
     if a.emd:

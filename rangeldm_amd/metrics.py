@@ -21,6 +21,9 @@ Frechet distance (rangeldm_amd/csrc/frechet.hip; metrics/metrics/fid/{lidargen_f
 over two folders of dumped activations): frechet_distance from an fp64 Gram product (gram_f64, on the fp64 MFMA) and its
 singular values (singular_values, one-sided Jacobi); frechet_distance_host is the numpy statement, frd_indices and
 load_activations the reference's index draw and file reading.
+
+Farthest point sampling (rangeldm_amd/csrc/fps.hip): farthest_point_sample, the sub-sampling of the protocol the set metrics
+come from; subsample(method="fps") / subsample_batch put it behind the sub-sampling step of `evaluate generation`.
 """
 import ctypes as C
 
@@ -30,6 +33,9 @@ from . import _lib
 
 EMD_EPS = 2.0 ** -7         # metres: the auction's final epsilon (the value is within about this of the optimal matching)
 EMD_MAX_POINTS = 2048       # RLDM_EMD_MAX_POINTS
+FPS_BLOCK = 1024            # RLDM_FPS_BLOCK: lanes of the workgroup a cloud gets in farthest_point_sample
+FPS_RESIDENT_POINTS = 65536     # RLDM_FPS_RESIDENT_POINTS: a cloud's first points, min-distance in registers
+FPS_MAX_POINTS = 1048576    # RLDM_FPS_MAX_POINTS: the largest cloud farthest_point_sample takes
 
 
 def _dev_u32(h):
@@ -561,18 +567,96 @@ def load_activations(folder, indices, limit=FRD_LIMIT, total=FRD_TOTAL, device="
     return torch.from_numpy(np.stack(rows, 0)).to(device)
 
 
-def subsample(cloud, n, seed):
-    """`n` points of a (P, k) cloud chosen without replacement, in their original order; all of them if P <= n.  The choice
-    is a function of (P, n, seed) alone (numpy's PCG64 on the host), so two runs and two rank counts pick the same points."""
+def farthest_point_sample(x, k, x_lengths=None, start=0):
+    """Farthest point sampling of every cloud: an int64 device tensor (B, k) of indices into each cloud, in selection order.
+    Inputs as chamfer_matrix takes them (a list of (P_i, >= 3) device tensors, or a padded tensor plus lengths); only xyz is
+    read.  `start` (an int, or one per cloud) is the first selected index.  Per cloud, in fp32, one rounding per operation:
+
+        mind = +inf everywhere; sel = start; k times: emit sel; d = ((dx*dx + dy*dy) + dz*dz), dx = x[i] - x[sel];
+        mind = min(mind, d); mind[sel] = -inf; sel = the LOWEST index attaining max(mind)
+
+    The -inf sentinel keeps a selected index out of every later round, so the k indices are distinct even on a cloud of
+    duplicates.  A row depends on its cloud, k and start alone and equals the sequential numpy evaluation exactly; the
+    indices for k are the first k of those for a larger k.  Raises ValueError (before the device) for k > P_i -- naming the
+    cloud --, a start outside its cloud, clouds above FPS_MAX_POINTS points, and non-finite coordinates: min / arg-max over NaN
+    is not a defined order."""
+    xs = _clouds(x, x_lengths, "x")
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"k must be at least 1, got {k}")
+    starts = [int(start)] * len(xs) if not hasattr(start, "__len__") else [int(v) for v in start]
+    if len(starts) != len(xs):
+        raise ValueError(f"{len(starts)} start indices for {len(xs)} clouds")
+    for i, (c, s0) in enumerate(zip(xs, starts)):
+        p = int(c.shape[0])
+        if k > p:
+            raise ValueError(f"cloud {i} holds {p} points, fewer than k = {k}")
+        if p > FPS_MAX_POINTS:
+            raise ValueError(f"cloud {i} holds {p} points, above the {FPS_MAX_POINTS} farthest_point_sample takes")
+        if not 0 <= s0 < p:
+            raise ValueError(f"start {s0} is not an index of cloud {i} ({p} points)")
+    finite = torch.stack([torch.isfinite(c[:, :3]).all() for c in xs]).tolist()          # (one read-back for the batch)
+    if not all(finite):
+        raise ValueError(f"cloud {finite.index(False)} holds non-finite coordinates (farthest point sampling orders distances)")
+    _lib.require_gpu()
+    xp, xo, xk = _pack(xs)
+    first = torch.tensor(starts, dtype=torch.int32).to(xp.device)
+    idx = torch.empty((len(xs), k), dtype=torch.int32, device=xp.device)
+    _lib.check(_lib.lib().rldm_farthest_point_sample(xp.data_ptr(), xo.data_ptr(), xk, len(xs), k, first.data_ptr(),
+                                                     idx.data_ptr(), _lib.stream_ptr(xp.device)), "rldm_farthest_point_sample")
+    return idx.long()
+
+
+SUBSAMPLE_METHODS = ("random", "fps")
+
+
+def _fps_start(p, seed):
     import numpy as np
+    return int(np.random.Generator(np.random.PCG64(int(seed))).integers(p))
+
+
+def subsample(cloud, n, seed, method="random"):
+    """`n` points of a (P, k) cloud chosen without replacement, in their original order; all of them if P <= n.  The choice
+    is a function of (P, n, seed) alone (numpy's PCG64 on the host), so two runs and two rank counts pick the same points.
+    method="fps" chooses by farthest point sampling instead (farthest_point_sample, started at the index
+    `np.random.Generator(np.random.PCG64(seed)).integers(P)`): a function of the cloud, n and seed."""
+    import numpy as np
+    if method not in SUBSAMPLE_METHODS:
+        raise ValueError(f"method must be one of {SUBSAMPLE_METHODS}, got {method!r}")
     P = int(cloud.shape[0])
     n = int(n)
     if n <= 0:
         raise ValueError(f"n must be positive, got {n}")
     if P <= n:
         return cloud
+    if method == "fps":
+        return subsample_batch([cloud], n, [seed], "fps")[0]
     idx = np.sort(np.random.Generator(np.random.PCG64(int(seed))).choice(P, size=n, replace=False))
     return cloud[torch.from_numpy(idx).to(cloud.device)]
+
+
+def subsample_batch(clouds, n, seeds, method="random"):
+    """[subsample(c, n, s, method) for c, s in zip(clouds, seeds)]; with method="fps" every cloud above n points goes
+    through ONE farthest_point_sample call (one kernel launch for the ragged batch)."""
+    if method not in SUBSAMPLE_METHODS:
+        raise ValueError(f"method must be one of {SUBSAMPLE_METHODS}, got {method!r}")
+    clouds, seeds = list(clouds), list(seeds)
+    if len(clouds) != len(seeds):
+        raise ValueError(f"{len(seeds)} seeds for {len(clouds)} clouds")
+    n = int(n)
+    if n <= 0:
+        raise ValueError(f"n must be positive, got {n}")
+    if method == "random":
+        return [subsample(c, n, s) for c, s in zip(clouds, seeds)]
+    out = list(clouds)
+    large = [i for i, c in enumerate(clouds) if int(c.shape[0]) > n]
+    if large:
+        idx = farthest_point_sample([clouds[i] for i in large], n,
+                                    start=[_fps_start(clouds[i].shape[0], seeds[i]) for i in large])
+        idx = idx.sort(dim=1).values
+        for row, i in zip(idx, large):
+            out[i] = clouds[i][row.to(clouds[i].device)]
+    return out
 
 
 def range_errors(a, b, scale, shift=None, channels=None, window=None):
