@@ -407,6 +407,64 @@ int rldm_singular_values_f64(const double* m, int rows, int cols, double tol, in
 int rldm_frechet_distance(const double* x, int n1, const double* y, int n2, int d, double* out5, void* stream);
 /* Sweeps the Jacobi loop of this thread's last rldm_frechet_distance call ran (0 before the first). */
 int rldm_frechet_last_sweeps(void);
+/* ---- RangeNet++ inference (rangeldm_amd/csrc/rangenet.hip) ---------------------------------------------
+ * The DarkNet21 / DarkNet53 segmentation network the FRD activations and the IoU / accuracy metrics come from.  Activations
+ * are device bf16 channels-last [B][H][W][pitch(C)], pitch(C) = RLDM_RN_PITCH(C) (pad channels hold zeros).  One layer is
+ *     acc = sum_taps W . X              zeros outside the image on both axes (no wrap)
+ *     v   = acc * scale[c] + shift[c]   fp32; BatchNorm (eval) and bias folded by the caller
+ *     v   = v >= 0 ? v : 0.1f * v       if leaky
+ *     v   = v + add0 + add1             optional bf16 tensors of the output's shape, in that order, fp32
+ *     out = bf16(v)                     round to nearest even
+ * on v_mfma_f32_32x32x16_bf16 with fp32 accumulation; every step after the sum is one fp32 operation (no FMA). */
+enum rldm_rangenet_kind {
+    RLDM_RN_CONV1X1 = 0,        /* 1x1                                                                                   */
+    RLDM_RN_CONV3X3 = 1,        /* 3x3, stride (1,1), padding 1                                                          */
+    RLDM_RN_CONV3X3_S2 = 2,     /* 3x3, stride (1,2) along W, padding 1: W_out = (W - 1) / 2 + 1                         */
+    RLDM_RN_UPCONV = 3          /* ConvTranspose2d kernel [1,4], stride [1,2], padding [0,1]: W_out = 2 W, run as two
+                                 * 2-tap convs by output-column parity                                                   */
+};
+#define RLDM_RN_PITCH(c) (((c) + 15) & ~15)
+typedef struct rldm_rangenet_layer_desc {
+    int32_t kind;               /* enum rldm_rangenet_kind */
+    int32_t B, H, W;            /* the INPUT's batch, rows and columns */
+    int32_t Cin, Cout;
+    int32_t leaky;              /* LeakyReLU(0.1) after the affine */
+} rldm_rangenet_layer_desc;
+typedef struct rldm_rangenet_config {
+    int32_t layers;             /* 21 or 53 (the block counts per encoder stage) */
+    int32_t in_channels;        /* 5: range, x, y, z, remission */
+    int32_t num_classes;        /* 20 */
+} rldm_rangenet_config;
+typedef struct rldm_rangenet rldm_rangenet;
+/* bf16 elements of a layer's packed weight image (-1: bad arguments), and the packing itself, on the host:
+ * w fp32 [Cout][T][Cin] with T = 1 (1x1), 9 (3x3, tap = 3 ky + kx) or 4 (up-conv, tap = kx) -> packed [panel of 32 output
+ * channels][16 input channels][T][lane 64][8], the MFMA's A fragment per lane, zero padded; rounded to bf16 (nearest even). */
+long long rldm_rangenet_packed_elems(int kind, int Cin, int Cout);
+int rldm_rangenet_pack_weights(int kind, int Cin, int Cout, const float* w, uint16_t* packed);
+/* One layer, one launch (the network walk calls exactly this).  x device bf16 [B][H][W][pitch(Cin)]; w_packed device;
+ * scale / shift device fp32 [Cout]; add0 / add1 device bf16 of the output's shape or NULL.  Outputs, each optional (at least
+ * one): out device bf16 [B][H][W_out][pitch(Cout)]; out_f32 device fp32 (B, Cout, H, W_out), v before the rounding;
+ * gathered device fp32 (B, n_gather): v at the positions of one image's (Cout, H, W_out) flattening whose bit is set in
+ * gather_mask (uint32 words, bit i & 31 of word i >> 5), written to column gather_slot[i]; argmax device uint8 (B, H, W_out):
+ * the channel of the largest v, lowest index on ties (Cout <= 32).  Every tensor must stay below 2^31 elements. */
+int rldm_rangenet_layer(const rldm_rangenet_layer_desc* d, const void* x, const void* w_packed, const float* scale, const float* shift,
+                        const void* add0, const void* add1, void* out, float* out_f32, const uint32_t* gather_mask,
+                        const int32_t* gather_slot, int n_gather, float* gathered, uint8_t* argmax, void* stream);
+/* The layers of an architecture in walk order: stem; enc1..enc5 (down-sampler, then conv1 / conv2 of every BasicBlock);
+ * dec5..dec1 (up-conv, conv1, conv2); head.  layer_info fills kind / Cin / Cout / leaky (B, H, W are zero). */
+int rldm_rangenet_num_layers(const rldm_rangenet_config* cfg);
+int rldm_rangenet_layer_info(const rldm_rangenet_config* cfg, int index, rldm_rangenet_layer_desc* out);
+/* weights / scale / shift: n_layers HOST pointers in walk order (fp32 [Cout][T][Cin], [Cout], [Cout]); packed and uploaded here. */
+int rldm_rangenet_create(const rldm_rangenet_config* cfg, const float* const* weights, const float* const* scale,
+                         const float* const* shift, int n_layers, rldm_rangenet** out);
+void rldm_rangenet_destroy(rldm_rangenet* net);
+/* proj device fp32 (B, in_channels, H, W), W a multiple of 32.  skips[os] is the input of each down-sampler; each decoder
+ * stage is up-conv -> BasicBlock -> + skips[os]; dropout is the identity.  features: n_gather == 0: device fp32 (B, 32, H, W)
+ * or NULL; n_gather > 0: device fp32 (B, n_gather), see rldm_rangenet_layer.  argmax device uint8 (B, H, W) and / or logits
+ * device fp32 (B, num_classes, H, W).  The net owns its activation arena (grown on demand; one forward per net at a time). */
+int rldm_rangenet_forward(rldm_rangenet* net, const float* proj, int B, int H, int W, const uint32_t* gather_mask,
+                          const int32_t* gather_slot, int n_gather, float* features, uint8_t* argmax, float* logits, void* stream);
+
 /* Range-image errors (ldm/convert_vae.py:236-247 MAE / PSNR; metrics/metrics/mae.py:45-117 range MAE): a, b device fp32
  * (B, C, W, H), C <= 8.  Per image, over the channels of channel_mask and the azimuth columns (w0 + k) mod W,
  * k in [0, w1 - w0) (0 <= w0 < W, w0 < w1 <= w0 + W: the window may wrap past the seam), with v -> v * scale[c] + shift[c]

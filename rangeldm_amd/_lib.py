@@ -15,6 +15,8 @@ RLDM_EMD_RECT, RLDM_EMD_SYMMETRIC, RLDM_EMD_DIAGONAL = 0, 1, 2
 RLDM_EMD_BID_CAP = 2
 # rldm_singular_values_f64 / rldm_frechet_distance: the return values that are not the ordinary error
 RLDM_FRECHET_SWEEP_CAP, RLDM_FRECHET_NONFINITE, RLDM_FRECHET_MAX_SWEEPS = 2, 3, 60
+# rldm_rangenet_layer_desc::kind (enum rldm_rangenet_kind)
+RLDM_RN_CONV1X1, RLDM_RN_CONV3X3, RLDM_RN_CONV3X3_S2, RLDM_RN_UPCONV = 0, 1, 2, 3
 
 
 class Flag(enum.IntFlag):
@@ -80,6 +82,15 @@ class LidarConfigC(C.Structure):
     _fields_ = [("beams", C.c_int32), ("width", C.c_int32), ("mode", C.c_int32), ("mean", C.c_float), ("std", C.c_float),
                 ("range_fill", C.c_float), ("intensity_fill", C.c_float), ("grid", C.c_int32 * 3),
                 ("pc_range", C.c_float * 6), ("normalize_volume_densities", C.c_int32)]
+
+
+class RangeNetLayerDescC(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Cin", C.c_int32),
+                ("Cout", C.c_int32), ("leaky", C.c_int32)]
+
+
+class RangeNetConfigC(C.Structure):
+    _fields_ = [("layers", C.c_int32), ("in_channels", C.c_int32), ("num_classes", C.c_int32)]
 
 
 class TrainConvDescC(C.Structure):
@@ -176,6 +187,15 @@ PROTOTYPES = {
     "rldm_singular_values_f64": (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_int, _P, C.POINTER(C.c_int), _P]),
     "rldm_frechet_distance": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_double), _P]),
     "rldm_frechet_last_sweeps": (C.c_int, []),
+    # RangeNet++ inference (csrc/rangenet.hip): weight packing, one layer, the architecture's layer list, the network
+    "rldm_rangenet_packed_elems": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    "rldm_rangenet_pack_weights": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P]),
+    "rldm_rangenet_layer": (C.c_int, [C.POINTER(RangeNetLayerDescC), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
+    "rldm_rangenet_num_layers": (C.c_int, [C.POINTER(RangeNetConfigC)]),
+    "rldm_rangenet_layer_info": (C.c_int, [C.POINTER(RangeNetConfigC), C.c_int, C.POINTER(RangeNetLayerDescC)]),
+    "rldm_rangenet_create": (C.c_int, [C.POINTER(RangeNetConfigC), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.c_int, C.POINTER(_P)]),
+    "rldm_rangenet_destroy": (None, [_P]),
+    "rldm_rangenet_forward": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P]),
     # MAE / PSNR of ldm/convert_vae.py:236-247 and the range MAE of metrics/metrics/mae.py:45-117
     "rldm_range_errors": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
                                     C.POINTER(C.c_float), C.c_int, C.c_int, _P, _P, _P]),

@@ -6,7 +6,9 @@
     python -m rangeldm_amd.evaluate chamfer A_DIR B_DIR
     python -m rangeldm_amd.evaluate generation GEN_DIR REF_DIR [--points 2048] [--limit N] [--seed 0] [--max-depth M]
                                                [--sampling {random,fps}] [--emd [--emd-eps 0.0078125]]
-    python -m rangeldm_amd.evaluate frd FOLDER1 FOLDER2 [--limit 1100]
+    python -m rangeldm_amd.evaluate frd FOLDER1 FOLDER2 [--limit 1100] [--rangenet MODEL_DIR]
+    python -m rangeldm_amd.evaluate rangenet --model MODEL_DIR --dump CLOUD_DIR --frd-dir OUT_A --output-dir OUT_S
+    python -m rangeldm_amd.evaluate segmentation RESULT_SEG_DIR TARGET_SEG_DIR
 
 Every command prints one JSON object on stdout (`--json PATH` also writes it).  Under `torch.distributed.run` the work is
 sharded over the ranks and rank 0 reduces and prints.  The arithmetic runs in librangeldm_hip (rangeldm_amd/csrc/chamfer.hip
@@ -38,7 +40,18 @@ mean_x min_y |x - y|^2 + mean_y min_x |x - y|^2 over xyz.
                  Frechet distance between two folders of dumped RangeNet++ activations (`.npy`, 2 097 152 values each), on
                  the reference's 4 096 randomly drawn values per file and at most --limit files per folder (sorted by name),
                  by metrics.frechet_distance.  The work is one small matrix: rank 0 alone loads and computes, so the output
-                 is the same for any number of ranks.  (Producing the activations -- RangeNet++ inference -- is not here.)
+                 is the same for any number of ranks.  With --rangenet MODEL_DIR the two folders hold point clouds (`.bin`,
+                 x y z remission) instead: every cloud (sorted by name, at most --limit) is projected and run through
+                 RangeNet++ (rangenet.RangeNet), shared out over the ranks, and only its 4 096 drawn values are kept -- the
+                 same numbers, bit for bit, as `rangenet` dumps and a plain `frd` of the dumped folders then reads.
+  rangenet       `rangenetpp.main(... --dump CLOUD_DIR --frd_dir OUT_A --output_dir OUT_S --point_cloud)` (metric.py's feature
+                 dump; tasks/semantic/infer_lib.py, modules/user.py:130-184): the i-th `.bin` cloud of CLOUD_DIR IN SORTED
+                 ORDER (the reference takes glob order, which is arbitrary) gives OUT_A/i.npy, the decoder's last feature map
+                 (1, 32, 64, 1024) float32, and OUT_S/i.pth, the (64, 1024) int64 argmax tensor (torch.save).  Cloud i is the
+                 work of rank i mod world.  MODEL_DIR is laid out like the reference's darknet53-1024/.
+  segmentation   `metric.py --iou / --accuracy` (metrics/metrics/iou.py): the `.pth` label tensors of two folders, paired by name,
+                 compared through one 20 x 20 confusion matrix counted on the device: accuracy, and
+                 jaccard_score(target, result, average="weighted").
 
 Only the linear range normalisation (x * std + mean, every shipped config) is supported: `log` / `inverse` sensors raise
 NotImplementedError.  nuScenes `.bin` files carry no ring column, so they cannot be re-projected: nuScenes raises too.
@@ -109,7 +122,22 @@ def build_parser():
     f.add_argument("--total", type=int, default=2097152, help="values per dumped file (other than the default: tests)")
     f.add_argument("--count", type=int, default=4096, help="values drawn per file (other than the default: tests)")
 
-    for p in (v, *[sub.choices[k] for k in ("densification", "inpainting")], c, g, f):
+    f.add_argument("--rangenet", default=None, metavar="MODEL_DIR",
+                   help="the folders hold .bin point clouds: run RangeNet++ from this model folder over them first")
+
+    r = sub.add_parser("rangenet", help="RangeNet++ over a folder of clouds: FRD activations and segmentations (rangenetpp --dump)")
+    r.add_argument("--model", required=True, help="model folder: arch_cfg.yaml, backbone, segmentation_decoder, segmentation_head")
+    r.add_argument("--dump", required=True, help="folder of .bin point clouds (x y z remission, float32)")
+    r.add_argument("--frd-dir", required=True, help="where i.npy, the (1, 32, 64, 1024) activation of cloud i, is written")
+    r.add_argument("--output-dir", required=True, help="where i.pth, the argmax tensor of cloud i, is written")
+    r.add_argument("--batch-size", type=int, default=4)
+
+    s = sub.add_parser("segmentation", help="IoU (weighted Jaccard) and accuracy of two folders of .pth label tensors")
+    s.add_argument("result_dir")
+    s.add_argument("target_dir")
+    s.add_argument("--classes", type=int, default=20)
+
+    for p in (v, *[sub.choices[k] for k in ("densification", "inpainting")], c, g, f, r, s):
         p.add_argument("--json", default=None, help="also write the result object to this file")
     return ap
 
@@ -465,21 +493,119 @@ def check_frd_args(a):
         raise ValueError(f"--limit must be at least 2 (a covariance needs 2 samples), got {a.limit}")
     if not 1 <= a.count <= a.total:
         raise ValueError(f"--count {a.count} values cannot be drawn from --total {a.total}")
+    if getattr(a, "rangenet", None) and a.total != RANGENET_SHAPE[0] * RANGENET_SHAPE[1] * RANGENET_SHAPE[2]:
+        raise ValueError(f"--rangenet draws from whole {RANGENET_SHAPE} feature maps: --total {a.total} does not apply")
+
+
+RANGENET_SHAPE = (32, 64, 1024)      # the activation of one scan: channels, beams, azimuth columns
+
+
+def check_rangenet_args(a):
+    """`rangenet`: what can be refused before a file is read."""
+    if a.batch_size < 1:
+        raise ValueError(f"--batch-size must be at least 1, got {a.batch_size}")
+    dirs = {"--dump": a.dump, "--frd-dir": a.frd_dir, "--output-dir": a.output_dir}
+    real = {k: os.path.realpath(v) for k, v in dirs.items()}
+    for k in ("--frd-dir", "--output-dir"):
+        if real[k] == real["--dump"]:
+            raise ValueError(f"{k} is the --dump folder: outputs are numbered files and must not land among the clouds")
+
+
+def check_segmentation_args(a):
+    """`segmentation`: what can be refused before a file is read."""
+    if not 1 <= a.classes <= 256:
+        raise ValueError(f"--classes must be in [1, 256], got {a.classes}")
+
+
+def _cloud_files(folder, limit=None):
+    files = sorted(glob.glob(os.path.join(folder, "*.bin")))[:limit]
+    if not files:
+        raise FileNotFoundError(f"no .bin point clouds in {folder}")
+    return files
+
+
+def _project_files(files, dev):
+    """(len(files), 5, 64, 1024) on the device: rangenet.project_scan of every x y z remission cloud."""
+    from .rangenet import project_scan
+    _, H, W = RANGENET_SHAPE
+    out = np.empty((len(files), 5, H, W), np.float32)
+    for i, path in enumerate(files):
+        scan = np.fromfile(path, dtype=np.float32).reshape(-1, 4)
+        out[i], _ = project_scan(scan[:, :3], scan[:, 3], H=H, W=W)
+    return torch.from_numpy(out).to(dev)
+
+
+def rangenet_activations(net, folder, idx, limit, rank, world, dev, batch_size=4):
+    """(files, len(idx)) fp32: the drawn values of every cloud's activation, the clouds shared out over the ranks (rank r takes
+    i = r, r + world, ...; the rows of the others are zero until the sum over the ranks, which adds zeros: exact)."""
+    files = _cloud_files(folder, limit)
+    rows = torch.zeros((len(files), len(idx)), dtype=torch.float32, device=dev)
+    mine = list(range(rank, len(files), world))
+    for chunk in _chunks(mine, batch_size):
+        _, gathered = net.infer(_project_files([files[i] for i in chunk], dev), gather=idx)
+        rows[torch.as_tensor(chunk, device=dev)] = gathered
+    return _sum_matrix_over_ranks(rows)
 
 
 def cmd_frd(a, rank, world, dev):
     from .metrics import frd_indices, frechet_distance, load_activations
     check_frd_args(a)
-    if rank != 0:                                        # one small matrix: nothing to shard
-        return None
-    idx = frd_indices(a.total, a.count)
-    x = load_activations(a.folder1, idx, a.limit, a.total, dev)
-    y = load_activations(a.folder2, idx, a.limit, a.total, dev)
+    if a.rangenet:                                       # the forwards are shared out; rank 0 then goes on alone
+        from .rangenet import RangeNet
+        net = RangeNet.from_pretrained(a.rangenet, device=dev)
+        idx = frd_indices(a.total, a.count)
+        x = rangenet_activations(net, a.folder1, idx, a.limit, rank, world, dev)
+        y = rangenet_activations(net, a.folder2, idx, a.limit, rank, world, dev)
+        if rank != 0:
+            return None
+    else:
+        if rank != 0:                                    # one small matrix: nothing to shard
+            return None
+        idx = frd_indices(a.total, a.count)
+        x = load_activations(a.folder1, idx, a.limit, a.total, dev)
+        y = load_activations(a.folder2, idx, a.limit, a.total, dev)
     terms = frechet_distance(x, y, return_terms=True)
     return {"task": "frd", **terms, "n1": int(x.shape[0]), "n2": int(y.shape[0]), "dims": int(x.shape[1])}
 
 
-COMMANDS = {"frd": cmd_frd, "generation": cmd_generation, "vae": cmd_vae, "densification": cmd_densification, "inpainting": cmd_inpainting, "chamfer": cmd_chamfer}
+def cmd_rangenet(a, rank, world, dev):
+    from .rangenet import RangeNet
+    check_rangenet_args(a)
+    files = _cloud_files(a.dump)
+    net = RangeNet.from_pretrained(a.model, device=dev)
+    for d in (a.frd_dir, a.output_dir):
+        os.makedirs(d, exist_ok=True)
+    for chunk in _chunks(list(range(rank, len(files), world)), a.batch_size):
+        argmax, features = net.infer(_project_files([files[i] for i in chunk], dev))
+        features, argmax = features.cpu().numpy(), argmax.cpu().to(torch.int64)
+        for k, i in enumerate(chunk):
+            np.save(os.path.join(a.frd_dir, f"{i}.npy"), features[k:k + 1])      # (1, 32, 64, 1024), as Decoder.forward saves it
+            torch.save(argmax[k].clone(), os.path.join(a.output_dir, f"{i}.pth"))
+    return {"task": "rangenet", "files": len(files), "layers": net.layers}
+
+
+def cmd_segmentation(a, rank, world, dev):
+    from .rangenet import confusion_matrix, scores_from_confusion
+    check_segmentation_args(a)
+    res = {os.path.basename(p) for p in glob.glob(os.path.join(a.result_dir, "*.pth"))}
+    tgt = {os.path.basename(p) for p in glob.glob(os.path.join(a.target_dir, "*.pth"))}
+    if not tgt:
+        raise FileNotFoundError(f"no .pth label tensors in {a.target_dir}")
+    if res != tgt:
+        raise FileNotFoundError(f"{a.result_dir} and {a.target_dir} do not hold the same .pth names "
+                                f"(for instance {sorted(res ^ tgt)[0]})")
+    names = sorted(tgt)
+    cm = torch.zeros((a.classes, a.classes), dtype=torch.int64, device=dev)
+    for name in names[rank::world]:
+        pred = torch.load(os.path.join(a.result_dir, name), map_location="cpu", weights_only=True)
+        target = torch.load(os.path.join(a.target_dir, name), map_location="cpu", weights_only=True)
+        cm += confusion_matrix(pred.to(dev), target.to(dev), a.classes)
+    # integer counts below 2^53: their fp64 sum over the ranks is exact and order-free
+    cm = torch.tensor(_sum_over_ranks(cm.reshape(-1).tolist(), dev), dtype=torch.float64).to(torch.int64).reshape(a.classes, a.classes)
+    return {"task": "segmentation", **scores_from_confusion(cm), "n": len(names)}
+
+
+COMMANDS = {"rangenet": cmd_rangenet, "segmentation": cmd_segmentation, "frd": cmd_frd, "generation": cmd_generation, "vae": cmd_vae, "densification": cmd_densification, "inpainting": cmd_inpainting, "chamfer": cmd_chamfer}
 
 
 def main(argv=None):
