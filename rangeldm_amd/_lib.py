@@ -196,6 +196,11 @@ PROTOTYPES = {
     "rldm_rangenet_create": (C.c_int, [C.POINTER(RangeNetConfigC), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.c_int, C.POINTER(_P)]),
     "rldm_rangenet_destroy": (None, [_P]),
     "rldm_rangenet_forward": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, _P, _P]),
+    # around the forward (csrc/rangenet_post.hip): a ragged batch of scans -> the network's input; argmax -> per-point labels
+    "rldm_rangenet_project": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_float),
+                                        C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rldm_rangenet_unproject": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_float,
+                                          C.c_int, _P, _P]),
     # MAE / PSNR of ldm/convert_vae.py:236-247 and the range MAE of metrics/metrics/mae.py:45-117
     "rldm_range_errors": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
                                     C.POINTER(C.c_float), C.c_int, C.c_int, _P, _P, _P]),

@@ -6,8 +6,9 @@
     python -m rangeldm_amd.evaluate chamfer A_DIR B_DIR
     python -m rangeldm_amd.evaluate generation GEN_DIR REF_DIR [--points 2048] [--limit N] [--seed 0] [--max-depth M]
                                                [--sampling {random,fps}] [--emd [--emd-eps 0.0078125]]
-    python -m rangeldm_amd.evaluate frd FOLDER1 FOLDER2 [--limit 1100] [--rangenet MODEL_DIR]
+    python -m rangeldm_amd.evaluate frd FOLDER1 FOLDER2 [--limit 1100] [--rangenet MODEL_DIR [--projection {host,device}]]
     python -m rangeldm_amd.evaluate rangenet --model MODEL_DIR --dump CLOUD_DIR --frd-dir OUT_A --output-dir OUT_S
+                                             [--projection {host,device}] [--labels-dir OUT_L [--knn]]
     python -m rangeldm_amd.evaluate segmentation RESULT_SEG_DIR TARGET_SEG_DIR
 
 Every command prints one JSON object on stdout (`--json PATH` also writes it).  Under `torch.distributed.run` the work is
@@ -44,11 +45,21 @@ mean_x min_y |x - y|^2 + mean_y min_x |x - y|^2 over xyz.
                  x y z remission) instead: every cloud (sorted by name, at most --limit) is projected and run through
                  RangeNet++ (rangenet.RangeNet), shared out over the ranks, and only its 4 096 drawn values are kept -- the
                  same numbers, bit for bit, as `rangenet` dumps and a plain `frd` of the dumped folders then reads.
+                 --projection device projects a chunk of clouds in one call on the GPU (rangenet.project_scans) instead of one
+                 by one in numpy; the object then carries "projection": "device".  The device's atan2 / asin are not
+                 numpy's, so a point within a few ulp of a pixel boundary may land next door: the two projections agree with
+                 themselves (`rangenet --projection device` dumps what `frd --rangenet --projection device` draws from), not
+                 bit for bit with each other.
   rangenet       `rangenetpp.main(... --dump CLOUD_DIR --frd_dir OUT_A --output_dir OUT_S --point_cloud)` (metric.py's feature
                  dump; tasks/semantic/infer_lib.py, modules/user.py:130-184): the i-th `.bin` cloud of CLOUD_DIR IN SORTED
                  ORDER (the reference takes glob order, which is arbitrary) gives OUT_A/i.npy, the decoder's last feature map
                  (1, 32, 64, 1024) float32, and OUT_S/i.pth, the (64, 1024) int64 argmax tensor (torch.save).  Cloud i is the
                  work of rank i mod world.  MODEL_DIR is laid out like the reference's darknet53-1024/.
+                 --labels-dir OUT_L (with --projection device) also writes OUT_L/i.label, one uint32 per point of cloud i
+                 (SemanticKITTI's format): the argmax of the point's pixel (user.py's `proj_argmax[p_y, p_x]`), or with
+                 --knn the vote of postproc/KNN.py with the `post.KNN.params` of MODEL_DIR/arch_cfg.yaml; mapped through
+                 `learning_map_inv` of MODEL_DIR/data_cfg.yaml when that file exists (the reference's to_original), else
+                 the network's class ids.
   segmentation   `metric.py --iou / --accuracy` (metrics/metrics/iou.py): the `.pth` label tensors of two folders, paired by name,
                  compared through one 20 x 20 confusion matrix counted on the device: accuracy, and
                  jaccard_score(target, result, average="weighted").
@@ -124,6 +135,8 @@ def build_parser():
 
     f.add_argument("--rangenet", default=None, metavar="MODEL_DIR",
                    help="the folders hold .bin point clouds: run RangeNet++ from this model folder over them first")
+    f.add_argument("--projection", choices=("host", "device"), default="host",
+                   help="with --rangenet: project the clouds one by one in numpy, or a chunk at a time on the GPU")
 
     r = sub.add_parser("rangenet", help="RangeNet++ over a folder of clouds: FRD activations and segmentations (rangenetpp --dump)")
     r.add_argument("--model", required=True, help="model folder: arch_cfg.yaml, backbone, segmentation_decoder, segmentation_head")
@@ -131,6 +144,12 @@ def build_parser():
     r.add_argument("--frd-dir", required=True, help="where i.npy, the (1, 32, 64, 1024) activation of cloud i, is written")
     r.add_argument("--output-dir", required=True, help="where i.pth, the argmax tensor of cloud i, is written")
     r.add_argument("--batch-size", type=int, default=4)
+    r.add_argument("--projection", choices=("host", "device"), default="host",
+                   help="project the clouds one by one in numpy, or a chunk at a time on the GPU")
+    r.add_argument("--labels-dir", default=None,
+                   help="where i.label, one uint32 label per point of cloud i, is written (needs --projection device)")
+    r.add_argument("--knn", action="store_true",
+                   help="with --labels-dir: clean the labels with the KNN vote of the model's post.KNN.params")
 
     s = sub.add_parser("segmentation", help="IoU (weighted Jaccard) and accuracy of two folders of .pth label tensors")
     s.add_argument("result_dir")
@@ -495,6 +514,8 @@ def check_frd_args(a):
         raise ValueError(f"--count {a.count} values cannot be drawn from --total {a.total}")
     if getattr(a, "rangenet", None) and a.total != RANGENET_SHAPE[0] * RANGENET_SHAPE[1] * RANGENET_SHAPE[2]:
         raise ValueError(f"--rangenet draws from whole {RANGENET_SHAPE} feature maps: --total {a.total} does not apply")
+    if getattr(a, "projection", "host") != "host" and not getattr(a, "rangenet", None):
+        raise ValueError("--projection applies to point clouds: it needs --rangenet MODEL_DIR")
 
 
 RANGENET_SHAPE = (32, 64, 1024)      # the activation of one scan: channels, beams, azimuth columns
@@ -506,9 +527,37 @@ def check_rangenet_args(a):
         raise ValueError(f"--batch-size must be at least 1, got {a.batch_size}")
     dirs = {"--dump": a.dump, "--frd-dir": a.frd_dir, "--output-dir": a.output_dir}
     real = {k: os.path.realpath(v) for k, v in dirs.items()}
-    for k in ("--frd-dir", "--output-dir"):
-        if real[k] == real["--dump"]:
+    labels_dir = getattr(a, "labels_dir", None)
+    if labels_dir:
+        real["--labels-dir"] = os.path.realpath(labels_dir)
+    for k in ("--frd-dir", "--output-dir", "--labels-dir"):
+        if k in real and real[k] == real["--dump"]:
             raise ValueError(f"{k} is the --dump folder: outputs are numbered files and must not land among the clouds")
+    if getattr(a, "knn", False) and not labels_dir:
+        raise ValueError("--knn cleans per-point labels: it needs --labels-dir")
+    if labels_dir and getattr(a, "projection", "host") != "device":
+        raise ValueError("--labels-dir needs --projection device (the host projection keeps no per-point pixels)")
+
+
+def label_settings(model_dir, use_knn):
+    """(knn params or None, uint32 lookup table or None) for `rangenet --labels-dir`: the post.KNN.params of the model's
+    arch_cfg.yaml when --knn is given, and learning_map_inv of its data_cfg.yaml (class id -> SemanticKITTI label, the
+    reference's to_original) when that file exists."""
+    import yaml
+    from .rangenet import NUM_CLASSES, knn_params
+    knn = None
+    if use_knn:
+        with open(os.path.join(model_dir, "arch_cfg.yaml")) as f:
+            knn = knn_params(yaml.safe_load(f))
+    table = None
+    path = os.path.join(model_dir, "data_cfg.yaml")
+    if os.path.isfile(path):
+        with open(path) as f:
+            inv = yaml.safe_load(f)["learning_map_inv"]
+        table = np.zeros(max(NUM_CLASSES, max(int(k) for k in inv) + 1), np.uint32)
+        for k, v in inv.items():
+            table[int(k)] = int(v)
+    return knn, table
 
 
 def check_segmentation_args(a):
@@ -524,9 +573,20 @@ def _cloud_files(folder, limit=None):
     return files
 
 
-def _project_files(files, dev):
-    """(len(files), 5, 64, 1024) on the device: rangenet.project_scan of every x y z remission cloud."""
+def _project_files_device(files, dev):
+    """rangenet.ProjectedScans of the x y z remission clouds: read, packed on the host, one upload, one projection call."""
+    from .rangenet import project_scans
+    _, H, W = RANGENET_SHAPE
+    clouds = [np.fromfile(path, dtype=np.float32).reshape(-1, 4) for path in files]
+    return project_scans(np.concatenate(clouds, 0), [c.shape[0] for c in clouds], H=H, W=W, device=dev)
+
+
+def _project_files(files, dev, projection="host"):
+    """(len(files), 5, 64, 1024) on the device: rangenet.project_scan of every x y z remission cloud (projection "device":
+    rangenet.project_scans of all of them at once)."""
     from .rangenet import project_scan
+    if projection == "device":
+        return _project_files_device(files, dev).proj
     _, H, W = RANGENET_SHAPE
     out = np.empty((len(files), 5, H, W), np.float32)
     for i, path in enumerate(files):
@@ -535,14 +595,14 @@ def _project_files(files, dev):
     return torch.from_numpy(out).to(dev)
 
 
-def rangenet_activations(net, folder, idx, limit, rank, world, dev, batch_size=4):
+def rangenet_activations(net, folder, idx, limit, rank, world, dev, batch_size=4, projection="host"):
     """(files, len(idx)) fp32: the drawn values of every cloud's activation, the clouds shared out over the ranks (rank r takes
     i = r, r + world, ...; the rows of the others are zero until the sum over the ranks, which adds zeros: exact)."""
     files = _cloud_files(folder, limit)
     rows = torch.zeros((len(files), len(idx)), dtype=torch.float32, device=dev)
     mine = list(range(rank, len(files), world))
     for chunk in _chunks(mine, batch_size):
-        _, gathered = net.infer(_project_files([files[i] for i in chunk], dev), gather=idx)
+        _, gathered = net.infer(_project_files([files[i] for i in chunk], dev, projection), gather=idx)
         rows[torch.as_tensor(chunk, device=dev)] = gathered
     return _sum_matrix_over_ranks(rows)
 
@@ -554,8 +614,8 @@ def cmd_frd(a, rank, world, dev):
         from .rangenet import RangeNet
         net = RangeNet.from_pretrained(a.rangenet, device=dev)
         idx = frd_indices(a.total, a.count)
-        x = rangenet_activations(net, a.folder1, idx, a.limit, rank, world, dev)
-        y = rangenet_activations(net, a.folder2, idx, a.limit, rank, world, dev)
+        x = rangenet_activations(net, a.folder1, idx, a.limit, rank, world, dev, projection=a.projection)
+        y = rangenet_activations(net, a.folder2, idx, a.limit, rank, world, dev, projection=a.projection)
         if rank != 0:
             return None
     else:
@@ -565,7 +625,10 @@ def cmd_frd(a, rank, world, dev):
         x = load_activations(a.folder1, idx, a.limit, a.total, dev)
         y = load_activations(a.folder2, idx, a.limit, a.total, dev)
     terms = frechet_distance(x, y, return_terms=True)
-    return {"task": "frd", **terms, "n1": int(x.shape[0]), "n2": int(y.shape[0]), "dims": int(x.shape[1])}
+    result = {"task": "frd", **terms, "n1": int(x.shape[0]), "n2": int(y.shape[0]), "dims": int(x.shape[1])}
+    if a.projection != "host":                           # (the default's object is what it was: no new key)
+        result["projection"] = a.projection
+    return result
 
 
 def cmd_rangenet(a, rank, world, dev):
@@ -573,15 +636,32 @@ def cmd_rangenet(a, rank, world, dev):
     check_rangenet_args(a)
     files = _cloud_files(a.dump)
     net = RangeNet.from_pretrained(a.model, device=dev)
-    for d in (a.frd_dir, a.output_dir):
-        os.makedirs(d, exist_ok=True)
+    knn, to_original = None, None
+    if a.labels_dir:
+        knn, to_original = label_settings(a.model, a.knn)
+    for d in (a.frd_dir, a.output_dir, a.labels_dir):
+        if d:
+            os.makedirs(d, exist_ok=True)
     for chunk in _chunks(list(range(rank, len(files), world)), a.batch_size):
-        argmax, features = net.infer(_project_files([files[i] for i in chunk], dev))
+        names = [files[i] for i in chunk]
+        scans = _project_files_device(names, dev) if a.projection == "device" else None
+        argmax, features = net.infer(scans.proj if scans is not None else _project_files(names, dev))
+        if a.labels_dir:
+            from .rangenet import unproject
+            labels = scans.split(unproject(scans, argmax, knn).cpu())
         features, argmax = features.cpu().numpy(), argmax.cpu().to(torch.int64)
         for k, i in enumerate(chunk):
             np.save(os.path.join(a.frd_dir, f"{i}.npy"), features[k:k + 1])      # (1, 32, 64, 1024), as Decoder.forward saves it
             torch.save(argmax[k].clone(), os.path.join(a.output_dir, f"{i}.pth"))
-    return {"task": "rangenet", "files": len(files), "layers": net.layers}
+            if a.labels_dir:
+                lab = labels[k].numpy().astype(np.uint32)
+                (to_original[lab] if to_original is not None else lab).astype(np.uint32).tofile(os.path.join(a.labels_dir, f"{i}.label"))
+    result = {"task": "rangenet", "files": len(files), "layers": net.layers}
+    if a.projection != "host":                           # (the default's object is what it was: no new keys)
+        result["projection"] = a.projection
+    if a.labels_dir:
+        result["labels"] = "knn" if a.knn else "plain"
+    return result
 
 
 def cmd_segmentation(a, rank, world, dev):

@@ -6,6 +6,8 @@ tasks/semantic/modules/segmentator.py:47-50, 149-153; metrics/metrics/iou.py).
     net = RangeNet.from_pretrained("darknet53-1024")          # arch_cfg.yaml + backbone / segmentation_decoder / segmentation_head
     proj, mask = project_scan(points, remission)              # host: LaserScan.do_range_projection + the parser's normalisation
     argmax, features = net.infer(torch.from_numpy(proj)[None].cuda())
+    scans = project_scans([cloud0, cloud1])                   # device: a ragged batch of (N, 4) clouds -> scans.proj (B, 5, H, W)
+    labels = net.segment([cloud0, cloud1], knn=knn_params(arch))     # per-point uint8 labels, one array per cloud
 
 The forward runs in librangeldm_hip (csrc/rangenet.hip): one launch per layer, bf16 activations, fp32 accumulation.  A layer is
 
@@ -19,10 +21,17 @@ The forward runs in librangeldm_hip (csrc/rangenet.hip): one launch per layer, b
 `layer_host` and `forward_host` restate that in plain torch on the CPU (the house pattern of metrics.frechet_distance_host): fp32
 throughout, or with bf16=True rounded to bf16 at exactly the points where the kernel rounds.
 
-Not built, refused with NotImplementedError: backbones / decoders other than `darknet`, CRF, KNN post-processing, output strides
-other than 32, inputs other than the five channels (range, x, y, z, remission).  The projection of a scan stays on the host.
+Around the forward (csrc/rangenet_post.hip): `project_scans` projects a ragged batch of scans on the device (`project_scan` is
+the host's, one scan at a time, and stays what it was), `unproject` takes the argmax back to per-point labels, plainly
+(`argmax[py, px]`) or through the reference's KNN vote (postproc/KNN.py), and `RangeNet.segment` chains the three.
+`scatter_host` and `knn_labels_host` restate the two device rules in numpy.
+
+Not built, refused with NotImplementedError: backbones / decoders other than `darknet`, CRF, output strides other than 32, inputs
+other than the five channels (range, x, y, z, remission).  An arch_cfg with `post.KNN.use: True` is refused as well: KNN is
+asked for explicitly (`segment(knn=...)`, `evaluate rangenet --knn`), with the params the arch_cfg carries.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -340,6 +349,206 @@ def project_scan(points, remission=None, H=64, W=1024, fov_up=3.0, fov_down=-25.
     return (proj * mask).astype(np.float32), mask
 
 
+# ---- the projection (device) and its restatement -------------------------------------------------------------------------
+class ProjectedScans:
+    """What project_scans returns, all on the device: proj (B, 5, H, W) fp32, mask (B, H, W) fp32, proj_range (B, H, W) fp32
+    (-1 where empty), proj_idx (B, H, W) int32 (the winner's index in its cloud, -1 where empty), px / py (sum N,) int32
+    (-1: the point was dropped), unproj_range (sum N,) fp32, offsets (B + 1,) int32; `lengths` is the host's list of N_i."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def split(self, per_point):
+        """A per-point device tensor (sum N, ...) as a list of per-cloud views."""
+        return list(torch.split(per_point, self.lengths))
+
+
+def pack_clouds(clouds, lengths=None, device="cuda"):
+    """(points (sum N, 4) fp32 on the device, lengths): from a list of (N_i, 4) or (N_i, 3) arrays / tensors (three columns:
+    remission 0), or from a packed (sum N, 3 | 4) array / tensor and its lengths.  Host arrays are joined on the host and go
+    up in one copy."""
+    def four(a):
+        if a.ndim != 2 or a.shape[1] not in (3, 4):
+            raise ValueError(f"a cloud must be (N, 3) or (N, 4), got {tuple(a.shape)}")
+        if a.shape[1] == 4:
+            return a
+        pad = a.new_zeros((a.shape[0], 1)) if torch.is_tensor(a) else np.zeros((a.shape[0], 1), np.float32)
+        return torch.cat([a, pad], 1) if torch.is_tensor(a) else np.concatenate([a, pad], 1)
+
+    if lengths is None:
+        clouds = list(clouds)
+        if not clouds:
+            raise ValueError("no clouds")
+        lengths = [int(c.shape[0]) for c in clouds]
+        if all(torch.is_tensor(c) for c in clouds):
+            packed = torch.cat([four(c.to(device, torch.float32)) for c in clouds], 0)
+        else:
+            host = [four(np.asarray(c.cpu() if torch.is_tensor(c) else c, dtype=np.float32)) for c in clouds]
+            packed = torch.from_numpy(np.ascontiguousarray(np.concatenate(host, 0)))
+    else:
+        lengths = [int(n) for n in lengths]
+        packed = clouds if torch.is_tensor(clouds) else torch.from_numpy(np.ascontiguousarray(clouds, dtype=np.float32))
+        packed = four(packed.to(torch.float32))
+        if not lengths or min(lengths) < 0 or sum(lengths) != packed.shape[0]:
+            raise ValueError(f"lengths sum to {sum(lengths)}, the packed tensor holds {packed.shape[0]} points")
+    if sum(lengths) >= 2 ** 31 // 4:
+        raise ValueError("the packed batch must stay below 2^31 floats")
+    return packed.to(device).contiguous(), lengths
+
+
+def project_scans(clouds, lengths=None, H=64, W=1024, fov_up=3.0, fov_down=-25.0, means=IMG_MEANS, stds=IMG_STDS, device="cuda"):
+    """project_scan for a batch, on the device (rldm_rangenet_project): clouds as pack_clouds takes them -> ProjectedScans.
+    A pixel goes to its nearest point and among equal depths to the lowest index (project_scan leaves that case to numpy's
+    unstable argsort); a point whose depth is 0 or not finite is dropped (px = py = -1; the host code would index out of range).
+    Nothing here waits for the device."""
+    L = _lib.lib()
+    dev = torch.device(device)
+    pts, lengths = pack_clouds(clouds, lengths, dev)
+    B, n = len(lengths), pts.shape[0]
+    if B * 5 * H * W >= 2 ** 31:
+        raise ValueError("the projected batch must stay below 2^31 elements")
+    offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)).to(dev)
+    new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+    out = ProjectedScans(proj=new((B, 5, H, W), torch.float32), mask=new((B, H, W), torch.float32),
+                         proj_range=new((B, H, W), torch.float32), proj_idx=new((B, H, W), torch.int32),
+                         px=new((n,), torch.int32), py=new((n,), torch.int32), unproj_range=new((n,), torch.float32),
+                         offsets=offsets, lengths=lengths, points=pts)
+    keys = new((B, H, W), torch.int64)
+    m5 = (C.c_float * 5)(*[float(v) for v in means])
+    s5 = (C.c_float * 5)(*[float(v) for v in stds])
+    with torch.cuda.device(dev):
+        _lib.check(L.rldm_rangenet_project(_ptr(pts), _ptr(offsets), B, pts.shape[1], H, W, float(fov_up), float(fov_down), m5, s5,
+                                           _ptr(keys), _ptr(out.proj), _ptr(out.mask), _ptr(out.proj_range), _ptr(out.proj_idx),
+                                           _ptr(out.px), _ptr(out.py), _ptr(out.unproj_range), _lib.stream_ptr(dev)),
+                   "rldm_rangenet_project")
+    return out
+
+
+def scatter_host(px, py, depth, points, remission=None, H=64, W=1024, means=IMG_MEANS, stds=IMG_STDS):
+    """The device's pixel rule in numpy, given every point's pixel and depth: (proj (5, H, W), mask (H, W), proj_range (H, W),
+    proj_idx (H, W) int32).  A lexsort on (pixel, depth, index) puts every pixel's winner first: the nearest point, the
+    lowest index among equal depths.  Points with px < 0 take no part.  The normalisation and the mask are project_scan's
+    expressions."""
+    px, py = np.asarray(px).astype(np.int64).reshape(-1), np.asarray(py).astype(np.int64).reshape(-1)
+    depth = np.asarray(depth, dtype=np.float32).reshape(-1)
+    points = np.ascontiguousarray(points, dtype=np.float32)
+    n = points.shape[0]
+    remission = np.zeros(n, np.float32) if remission is None else np.asarray(remission, dtype=np.float32).reshape(-1)
+    if not (px.shape[0] == py.shape[0] == depth.shape[0] == remission.shape[0] == n) or points.shape[1:] != (3,):
+        raise ValueError("px, py, depth, points (N, 3) and remission must describe the same N points")
+    valid = np.flatnonzero(px >= 0)
+    pix = py[valid] * W + px[valid]
+    order = np.lexsort((valid, depth[valid], pix))       # the last key is the primary one
+    pix = pix[order]
+    first = np.ones(pix.shape[0], bool)
+    first[1:] = pix[1:] != pix[:-1]
+    win, at = valid[order][first], pix[first]
+    proj_range = np.full(H * W, -1, dtype=np.float32)
+    proj_xyz = np.full((H * W, 3), -1, dtype=np.float32)
+    proj_rem = np.full(H * W, -1, dtype=np.float32)
+    proj_idx = np.full(H * W, -1, dtype=np.int32)
+    proj_range[at], proj_xyz[at], proj_rem[at], proj_idx[at] = depth[win], points[win], remission[win], win
+    proj_range, proj_rem, proj_idx = proj_range.reshape(H, W), proj_rem.reshape(H, W), proj_idx.reshape(H, W)
+    mask = (proj_idx > 0).astype(np.float32)
+    proj = np.concatenate([proj_range[None], proj_xyz.reshape(H, W, 3).transpose(2, 0, 1), proj_rem[None]], 0)
+    proj = (proj - np.asarray(means, np.float32)[:, None, None]) / np.asarray(stds, np.float32)[:, None, None]
+    return (proj * mask).astype(np.float32), mask, proj_range, proj_idx
+
+
+# ---- back to the points: plain and KNN (postproc/KNN.py) -----------------------------------------------------------------
+def knn_params(arch):
+    """The `post.KNN.params` dict of an arch_cfg (knn, search, sigma, cutoff), checked."""
+    params = arch.get("post", {}).get("KNN", {}).get("params")
+    if not isinstance(params, dict) or any(k not in params for k in ("knn", "search", "sigma", "cutoff")):
+        raise ValueError("the arch_cfg carries no post.KNN.params (knn, search, sigma, cutoff)")
+    return check_knn({k: params[k] for k in ("knn", "search", "sigma", "cutoff")})
+
+
+def check_knn(params):
+    knn, search, sigma, cutoff = int(params["knn"]), int(params["search"]), float(params["sigma"]), float(params["cutoff"])
+    if search % 2 == 0 or not 1 <= search <= 7:
+        raise ValueError(f"KNN search must be odd and at most 7, got {search}")
+    if not 1 <= knn <= search * search:
+        raise ValueError(f"KNN knn must be in [1, search^2 = {search * search}], got {knn}")
+    if not sigma > 0.0 or not cutoff >= 0.0:
+        raise ValueError(f"KNN sigma must be positive and cutoff not negative, got {sigma} and {cutoff}")
+    return {"knn": knn, "search": search, "sigma": sigma, "cutoff": cutoff}
+
+
+def knn_weights(search, sigma):
+    """(search^2,) float32: 1 - the normalised search x search Gaussian, computed in torch fp32 step by step as
+    postproc/KNN.py's get_gaussian_kernel does, so that the bits are the reference's."""
+    coord = torch.arange(search)
+    gx = coord.repeat(search).view(search, search)
+    grid = torch.stack([gx, gx.t()], dim=-1).float()
+    mean, variance = (search - 1) / 2., sigma ** 2.
+    g = (1. / (2. * math.pi * variance)) * torch.exp(-torch.sum((grid - mean) ** 2., dim=-1) / (2 * variance))
+    g = g / torch.sum(g)
+    return (1 - g).reshape(-1).numpy().astype(np.float32)
+
+
+def knn_labels_host(proj_range, unproj_range, argmax, px, py, knn, search, sigma, cutoff, nclasses=NUM_CLASSES):
+    """postproc/KNN.py forward in numpy for one scan: proj_range (H, W) fp32 (-1: empty), argmax (H, W) integer labels, and per
+    point unproj_range, px, py -> (N,) uint8.  The window is search x search around (py, px) without azimuth wrap, entry
+    k = dy * search + dx; outside the image range and label are 0 (F.unfold's padding); an in-image range < 0 becomes +inf; the
+    centre's range is the point's own; distance = |entry - range| * knn_weights[k].  The knn smallest vote (a stable sort: ties
+    go to the lowest k), beyond `cutoff` (if > 0) for nobody; the class in [1, nclasses) with the most votes wins, the lowest
+    on ties, 1 without votes.  A point with px < 0 gets 0."""
+    p = check_knn({"knn": knn, "search": search, "sigma": sigma, "cutoff": cutoff})
+    knn, search = p["knn"], p["search"]
+    proj_range = np.asarray(proj_range, dtype=np.float32)
+    argmax = np.asarray(argmax).astype(np.int64)
+    px, py = np.asarray(px).astype(np.int64).reshape(-1), np.asarray(py).astype(np.int64).reshape(-1)
+    r = np.asarray(unproj_range, dtype=np.float32).reshape(-1)
+    n, pad = r.shape[0], search // 2
+    valid = px >= 0
+    x, y = np.where(valid, px, 0), np.where(valid, py, 0)
+    rp, lp = np.pad(proj_range, pad), np.pad(argmax, pad)            # zeros
+    w = knn_weights(search, p["sigma"])
+    dist = np.empty((n, search * search), np.float32)
+    lab = np.empty((n, search * search), np.int64)
+    for k in range(search * search):
+        dy, dx = divmod(k, search)
+        e = rp[y + dy, x + dx]
+        e = np.where(e < 0, np.float32(np.inf), e)
+        if k == (search * search - 1) // 2:
+            e = r
+        dist[:, k] = np.abs(e - r) * w[k]
+        lab[:, k] = lp[y + dy, x + dx]
+    order = np.argsort(dist, axis=1, kind="stable")[:, :knn]
+    near_d, near_l = np.take_along_axis(dist, order, 1), np.take_along_axis(lab, order, 1)
+    if p["cutoff"] > 0:
+        near_l = np.where(near_d > np.float32(p["cutoff"]), nclasses, near_l)
+    votes = np.zeros((n, nclasses + 1), np.int64)
+    np.add.at(votes, (np.repeat(np.arange(n), knn), np.minimum(near_l, nclasses).reshape(-1)), 1)
+    out = votes[:, 1:-1].argmax(axis=1) + 1
+    return np.where(valid, out, 0).astype(np.uint8)
+
+
+def unproject(scans, argmax, knn=None, num_classes=NUM_CLASSES):
+    """Per-point labels of a ProjectedScans batch from the network's argmax (uint8 (B, H, W), device): uint8 (sum N,) on the
+    device (rldm_rangenet_unproject).  knn None: argmax[py, px]; a params dict (knn_params): the KNN vote.  Does not wait."""
+    L = _lib.lib()
+    dev = scans.proj_range.device
+    B, H, W = scans.proj_range.shape
+    if tuple(argmax.shape) != (B, H, W) or argmax.dtype != torch.uint8 or argmax.device != dev:
+        raise ValueError(f"argmax must be uint8 {(B, H, W)} on {dev}")
+    argmax = argmax.contiguous()
+    labels = torch.empty((scans.px.shape[0],), dtype=torch.uint8, device=dev)
+    k = search = 0
+    cutoff, weights = 0.0, None
+    if knn is not None:
+        k, search, cutoff = int(knn["knn"]), int(knn["search"]), float(knn["cutoff"])
+        if k < 1:
+            raise ValueError(f"KNN knn must be at least 1, got {k}")
+        weights = torch.from_numpy(knn_weights(search, float(knn["sigma"])) if search >= 1 else np.zeros(1, np.float32)).to(dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.rldm_rangenet_unproject(_ptr(scans.proj_range), _ptr(argmax), _ptr(scans.px), _ptr(scans.py),
+                                             _ptr(scans.unproj_range), _ptr(scans.offsets), B, H, W, k, search, _ptr(weights),
+                                             cutoff, int(num_classes), _ptr(labels), _lib.stream_ptr(dev)), "rldm_rangenet_unproject")
+    return labels
+
+
 # ---- segmentation agreement ----------------------------------------------------------------------------------------------
 def confusion_matrix(pred, target, num_classes=NUM_CLASSES):
     """(num_classes, num_classes) int64 counts [target][pred], by integer counting on the tensors' device (torch.bincount)."""
@@ -551,6 +760,15 @@ class RangeNet:
     def logits(self, proj):
         """fp32 (B, 20, H, W): the head's output before the softmax (tests)."""
         return self._forward(proj, None, False, False, True)[2]
+
+    def segment(self, clouds, knn=None, H=64, W=1024, lengths=None):
+        """Per-point labels of a batch of scans (clouds as pack_clouds takes them): a list of uint8 arrays, one per cloud.
+        Projection, forward and unprojection run on the device; the host waits once, for the labels.  knn: a params dict
+        (knn_params(arch)) for the reference's KNN clean-up, None for the plain `argmax[py, px]`."""
+        scans = project_scans(clouds, lengths, H=H, W=W, device=self.device)
+        argmax, _, _ = self._forward(scans.proj, None, False, True, False)
+        labels = unproject(scans, argmax, knn).cpu().numpy()
+        return [part.copy() for part in np.split(labels, np.cumsum(scans.lengths)[:-1])]
 
 
 def load_pretrained(model_dir):
