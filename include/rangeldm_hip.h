@@ -407,6 +407,36 @@ int rldm_singular_values_f64(const double* m, int rows, int cols, double tol, in
 int rldm_frechet_distance(const double* x, int n1, const double* y, int n2, int d, double* out5, void* stream);
 /* Sweeps the Jacobi loop of this thread's last rldm_frechet_distance call ran (0 before the first). */
 int rldm_frechet_last_sweeps(void);
+/* ---- Kernel distance and precision / recall / density / coverage (rangeldm_amd/csrc/feature_metrics.hip) -------------- */
+#define RLDM_FEATURE_MAX_K 16      /* a row keeps its k + 1 smallest squared distances for k up to this */
+/* One scan of the rows of a [n_a][d] against the rows of b [n_b][d] (device fp64), folded into per-row outputs without ever
+ * forming the n_a x n_b matrix: the reductions that KID's unbiased polynomial-kernel MMD^2 (Binkowski et al. 2018) and
+ * precision / recall (Kynkaanniemi et al. 2019) / density / coverage (Naeem et al. 2020; their `prdc` package) are made of.
+ * It stands in for `sklearn.metrics.pairwise.polynomial_kernel(degree=3, coef0=1)` row sums and for
+ * `scipy.spatial.distance.cdist` followed by `np.argpartition` / `<` / `min` along a row.
+ *     g(x, y)   the dot product exactly as rldm_gram_f64 computes it (K ascending in one fixed order, no split-K)
+ *     s(x)      g(x, x), taken from that same product path (the diagonal tiles of x . x^T)
+ *     d2(x, y)  max(0, (s(x) + s(y)) - 2 g(x, y)), in that order: identical rows are at exactly 0; no square root anywhere
+ *     kappa     t = g(x, y) / d + 1; t * t * t                         (degree 3, gamma = 1 / d, coef0 = 1)
+ * Outputs (device, each may be NULL and is then not computed; i is a row of a, j a row of b, comparisons strict):
+ *     kmin_sq  [n_a][k1] fp64   the k1 smallest d2(a_i, b_j) over j, ascending (k1 = k + 1 <= RLDM_FEATURE_MAX_K + 1, k1 <= n_b;
+ *                               NULL exactly when k1 == 0)
+ *     count_a  [n_a] int32      #{j : d2 < radius_sq_a[i]}             (given exactly when radius_sq_a [n_a] is)
+ *     count_b  [n_a] int32      #{j : d2 < radius_sq_b[j]}             (given exactly when radius_sq_b [n_b] is)
+ *     min_sq   [n_a] fp64       min_j d2
+ *     poly_sum [n_a] fp64       sum_j kappa(a_i, b_j) (given exactly when poly != 0); with exclude_diagonal without
+ *                               j == i + row_offset
+ * The columns are cut into chunks of rldm_feature_scan_column_chunk(n_b) = 64 * ceil(ceil(n_b / 64) / 16) rows of b (at most
+ * 16 chunks, a function of n_b alone).  poly_sum is the sum over ascending chunks of each chunk's sum over ascending j; the
+ * other outputs do not depend on the order.  A row's outputs depend on that row, on b and on row_offset alone: a slice of a
+ * scanned on its own gives those rows of the whole scan bit for bit.  Workspace: n_a + n_b fp64 for the norms and, with more
+ * than one chunk, the outputs once per chunk -- O(n_a + n_b).  NaN / inf in a, b or a radius returns RLDM_FRECHET_NONFINITE
+ * before anything else runs (that check synchronises the stream; the scan itself is only enqueued). */
+int rldm_feature_scan_f64(const double* a, int n_a, const double* b, int n_b, int d, int k1, const double* radius_sq_a,
+                          const double* radius_sq_b, int poly, int exclude_diagonal, long long row_offset, double* kmin_sq,
+                          int32_t* count_a, int32_t* count_b, double* min_sq, double* poly_sum, void* stream);
+/* The column chunk rldm_feature_scan_f64 uses for n_b rows of b (0 for n_b <= 0). */
+int rldm_feature_scan_column_chunk(int n_b);
 /* ---- RangeNet++ inference (rangeldm_amd/csrc/rangenet.hip) ---------------------------------------------
  * The DarkNet21 / DarkNet53 segmentation network the FRD activations and the IoU / accuracy metrics come from.  Activations
  * are device bf16 channels-last [B][H][W][pitch(C)], pitch(C) = RLDM_RN_PITCH(C) (pad channels hold zeros).  One layer is

@@ -15,6 +15,8 @@ RLDM_EMD_RECT, RLDM_EMD_SYMMETRIC, RLDM_EMD_DIAGONAL = 0, 1, 2
 RLDM_EMD_BID_CAP = 2
 # rldm_singular_values_f64 / rldm_frechet_distance: the return values that are not the ordinary error
 RLDM_FRECHET_SWEEP_CAP, RLDM_FRECHET_NONFINITE, RLDM_FRECHET_MAX_SWEEPS = 2, 3, 60
+# rldm_feature_scan_f64: the largest k (a row keeps k + 1 squared distances); non-finite input returns RLDM_FRECHET_NONFINITE
+RLDM_FEATURE_MAX_K = 16
 # rldm_rangenet_layer_desc::kind (enum rldm_rangenet_kind)
 RLDM_RN_CONV1X1, RLDM_RN_CONV3X3, RLDM_RN_CONV3X3_S2, RLDM_RN_UPCONV = 0, 1, 2, 3
 
@@ -187,6 +189,10 @@ PROTOTYPES = {
     "rldm_singular_values_f64": (C.c_int, [_P, C.c_int, C.c_int, C.c_double, C.c_int, _P, C.POINTER(C.c_int), _P]),
     "rldm_frechet_distance": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_double), _P]),
     "rldm_frechet_last_sweeps": (C.c_int, []),
+    # kernel distance and precision / recall / density / coverage: one row scan of a against b, per-row outputs only
+    "rldm_feature_scan_f64": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_longlong,
+                                        _P, _P, _P, _P, _P, _P]),
+    "rldm_feature_scan_column_chunk": (C.c_int, [C.c_int]),
     # RangeNet++ inference (csrc/rangenet.hip): weight packing, one layer, the architecture's layer list, the network
     "rldm_rangenet_packed_elems": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     "rldm_rangenet_pack_weights": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P]),

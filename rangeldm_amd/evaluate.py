@@ -7,6 +7,8 @@
     python -m rangeldm_amd.evaluate generation GEN_DIR REF_DIR [--points 2048] [--limit N] [--seed 0] [--max-depth M]
                                                [--sampling {random,fps}] [--emd [--emd-eps 0.0078125]]
     python -m rangeldm_amd.evaluate frd FOLDER1 FOLDER2 [--limit 1100] [--rangenet MODEL_DIR [--projection {host,device}]]
+    python -m rangeldm_amd.evaluate features GEN_DIR REF_DIR [--k 5] [--limit N] [--subset-size M --subsets S --seed 0]
+                                             [--total T --count C] [--rangenet MODEL_DIR [--projection {host,device}]]
     python -m rangeldm_amd.evaluate rangenet --model MODEL_DIR --dump CLOUD_DIR --frd-dir OUT_A --output-dir OUT_S
                                              [--projection {host,device}] [--labels-dir OUT_L [--knn]]
     python -m rangeldm_amd.evaluate segmentation RESULT_SEG_DIR TARGET_SEG_DIR
@@ -50,6 +52,13 @@ mean_x min_y |x - y|^2 + mean_y min_x |x - y|^2 over xyz.
                  numpy's, so a point within a few ulp of a pixel boundary may land next door: the two projections agree with
                  themselves (`rangenet --projection device` dumps what `frd --rangenet --projection device` draws from), not
                  bit for bit with each other.
+  features       what the Frechet distance leaves open, over the same inputs `frd` reads (two folders of dumped activations, or
+                 with --rangenet two folders of clouds; every file, sorted by name, unless --limit): the kernel distance krd
+                 (metrics.kernel_distance: KID's unbiased polynomial-kernel MMD^2, which has no bias that depends on the
+                 number of files; --subset-size M gives the mean krd and krd_std over --subsets draws of M rows per set) and
+                 precision / recall / density / coverage of GEN_DIR against REF_DIR on --k nearest-neighbour manifolds
+                 (metrics.prdc: Kynkaanniemi et al. 2019, Naeem et al. 2020).  Row scans on the fp64 MFMA, no n x n matrix.
+                 As in `frd` the forwards are shared out over the ranks and rank 0 goes on alone.
   rangenet       `rangenetpp.main(... --dump CLOUD_DIR --frd_dir OUT_A --output_dir OUT_S --point_cloud)` (metric.py's feature
                  dump; tasks/semantic/infer_lib.py, modules/user.py:130-184): the i-th `.bin` cloud of CLOUD_DIR IN SORTED
                  ORDER (the reference takes glob order, which is arbitrary) gives OUT_A/i.npy, the decoder's last feature map
@@ -138,6 +147,21 @@ def build_parser():
     f.add_argument("--projection", choices=("host", "device"), default="host",
                    help="with --rangenet: project the clouds one by one in numpy, or a chunk at a time on the GPU")
 
+    ft = sub.add_parser("features", help="kernel distance and precision / recall / density / coverage over the activations frd reads")
+    ft.add_argument("gen_dir")
+    ft.add_argument("ref_dir")
+    ft.add_argument("--k", type=int, default=5, help="neighbours of the manifolds' radii")
+    ft.add_argument("--limit", type=int, default=None, help="use the first N files (sorted by name) of each folder; default: all")
+    ft.add_argument("--subset-size", type=int, default=None, help="rows per set of one kernel-distance estimate; default: the full sets, once")
+    ft.add_argument("--subsets", type=int, default=100, help="with --subset-size: estimates the mean and deviation are taken over")
+    ft.add_argument("--seed", type=int, default=0, help="with --subset-size: seed of the row draws")
+    ft.add_argument("--total", type=int, default=2097152, help="values per dumped file (other than the default: tests)")
+    ft.add_argument("--count", type=int, default=4096, help="values drawn per file (other than the default: tests)")
+    ft.add_argument("--rangenet", default=None, metavar="MODEL_DIR",
+                   help="the folders hold .bin point clouds: run RangeNet++ from this model folder over them first")
+    ft.add_argument("--projection", choices=("host", "device"), default="host",
+                   help="with --rangenet: project the clouds one by one in numpy, or a chunk at a time on the GPU")
+
     r = sub.add_parser("rangenet", help="RangeNet++ over a folder of clouds: FRD activations and segmentations (rangenetpp --dump)")
     r.add_argument("--model", required=True, help="model folder: arch_cfg.yaml, backbone, segmentation_decoder, segmentation_head")
     r.add_argument("--dump", required=True, help="folder of .bin point clouds (x y z remission, float32)")
@@ -156,7 +180,7 @@ def build_parser():
     s.add_argument("target_dir")
     s.add_argument("--classes", type=int, default=20)
 
-    for p in (v, *[sub.choices[k] for k in ("densification", "inpainting")], c, g, f, r, s):
+    for p in (v, *[sub.choices[k] for k in ("densification", "inpainting")], c, g, f, ft, r, s):
         p.add_argument("--json", default=None, help="also write the result object to this file")
     return ap
 
@@ -631,6 +655,53 @@ def cmd_frd(a, rank, world, dev):
     return result
 
 
+def check_features_args(a):
+    """`features`: what can be refused before a file is read."""
+    from .metrics import FEATURE_K_CAP
+    if not 1 <= a.k <= FEATURE_K_CAP:
+        raise ValueError(f"--k must be in [1, {FEATURE_K_CAP}], got {a.k}")
+    if a.limit is not None and a.limit < a.k + 1:
+        raise ValueError(f"--limit must be at least --k + 1 = {a.k + 1} (a row's neighbourhood counts the row itself), got {a.limit}")
+    if a.subset_size is not None and a.subset_size < 2:
+        raise ValueError(f"--subset-size must be at least 2, got {a.subset_size}")
+    if a.subsets < 1:
+        raise ValueError(f"--subsets must be at least 1, got {a.subsets}")
+    if not 1 <= a.count <= a.total:
+        raise ValueError(f"--count {a.count} values cannot be drawn from --total {a.total}")
+    if a.rangenet and a.total != RANGENET_SHAPE[0] * RANGENET_SHAPE[1] * RANGENET_SHAPE[2]:
+        raise ValueError(f"--rangenet draws from whole {RANGENET_SHAPE} feature maps: --total {a.total} does not apply")
+    if a.projection != "host" and not a.rangenet:
+        raise ValueError("--projection applies to point clouds: it needs --rangenet MODEL_DIR")
+
+
+def cmd_features(a, rank, world, dev):
+    from .metrics import frd_indices, kernel_distance, load_activations, prdc
+    check_features_args(a)
+    idx = frd_indices(a.total, a.count)
+    if a.rangenet:                                       # the forwards are shared out; rank 0 then goes on alone
+        from .rangenet import RangeNet
+        net = RangeNet.from_pretrained(a.rangenet, device=dev)
+        gen = rangenet_activations(net, a.gen_dir, idx, a.limit, rank, world, dev, projection=a.projection)
+        ref = rangenet_activations(net, a.ref_dir, idx, a.limit, rank, world, dev, projection=a.projection)
+        if rank != 0:
+            return None
+    else:
+        if rank != 0:                                    # two small matrices: nothing to shard
+            return None
+        gen = load_activations(a.gen_dir, idx, a.limit, a.total, dev)
+        ref = load_activations(a.ref_dir, idx, a.limit, a.total, dev)
+    result = {"task": "features", "k": a.k, "n_gen": int(gen.shape[0]), "n_ref": int(ref.shape[0]), "dims": int(gen.shape[1])}
+    if a.subset_size is None:
+        result["krd"] = kernel_distance(gen, ref)
+    else:
+        result.update(kernel_distance(gen, ref, subset_size=a.subset_size, subsets=a.subsets, seed=a.seed),
+                      subsets=a.subsets, subset_size=a.subset_size)
+    result.update(prdc(ref, gen, k=a.k))
+    if a.projection != "host":
+        result["projection"] = a.projection
+    return result
+
+
 def cmd_rangenet(a, rank, world, dev):
     from .rangenet import RangeNet
     check_rangenet_args(a)
@@ -685,7 +756,7 @@ def cmd_segmentation(a, rank, world, dev):
     return {"task": "segmentation", **scores_from_confusion(cm), "n": len(names)}
 
 
-COMMANDS = {"rangenet": cmd_rangenet, "segmentation": cmd_segmentation, "frd": cmd_frd, "generation": cmd_generation, "vae": cmd_vae, "densification": cmd_densification, "inpainting": cmd_inpainting, "chamfer": cmd_chamfer}
+COMMANDS = {"features": cmd_features, "rangenet": cmd_rangenet, "segmentation": cmd_segmentation, "frd": cmd_frd, "generation": cmd_generation, "vae": cmd_vae, "densification": cmd_densification, "inpainting": cmd_inpainting, "chamfer": cmd_chamfer}
 
 
 def main(argv=None):

@@ -22,9 +22,14 @@ over two folders of dumped activations): frechet_distance from an fp64 Gram prod
 singular values (singular_values, one-sided Jacobi); frechet_distance_host is the numpy statement, frd_indices and
 load_activations the reference's index draw and file reading.
 
+Kernel distance and precision / recall / density / coverage (rangeldm_amd/csrc/feature_metrics.hip): feature_scan, one row
+scan of a set against another on the fp64 MFMA with per-row outputs only (no n x n matrix); knn_radii_sq, prdc and
+kernel_distance on top of it; feature_scan_host, prdc_host and kernel_distance_host are the numpy statements.
+
 Farthest point sampling (rangeldm_amd/csrc/fps.hip): farthest_point_sample, the sub-sampling of the protocol the set metrics
 come from; subsample(method="fps") / subsample_batch put it behind the sub-sampling step of `evaluate generation`.
 """
+import collections
 import ctypes as C
 
 import torch
@@ -565,6 +570,257 @@ def load_activations(folder, indices, limit=FRD_LIMIT, total=FRD_TOTAL, device="
             raise ValueError(f"{path}: {flat.shape[0]} values, expected {total}")
         rows.append(flat[idx])
     return torch.from_numpy(np.stack(rows, 0)).to(device)
+
+
+# ---- kernel distance and precision / recall / density / coverage (rangeldm_amd/csrc/feature_metrics.hip) -----------------
+FEATURE_K_CAP = 16          # RLDM_FEATURE_MAX_K: a row keeps its k + 1 smallest squared distances for k up to this
+
+FeatureScan = collections.namedtuple("FeatureScan", "kmin_sq count_a count_b min_sq poly_sum")
+FeatureScan.__doc__ = """The per-row outputs of feature_scan / feature_scan_host; what was not asked for is None."""
+
+
+def feature_scan_column_chunk(n_b):
+    """Rows of b per column chunk of feature_scan: 64 * ceil(ceil(n_b / 64) / 16), a function of n_b alone (at most 16
+    chunks).  poly_sum is the sum, over ascending chunks, of each chunk's sum over ascending j."""
+    return 64 * -(-(-(-int(n_b) // 64)) // 16)
+
+
+def _scan_shapes(sa, sb, k, ra, rb, row_offset):
+    """The ValueErrors of feature_scan / feature_scan_host, from shapes alone (a shape of None: not given)."""
+    if len(sa) != 2 or len(sb) != 2 or 0 in sa or 0 in sb:
+        raise ValueError(f"a and b must be non-empty 2-D, got {tuple(sa)} and {tuple(sb)}")
+    if sa[1] != sb[1]:
+        raise ValueError(f"a holds {sa[1]} values per row, b {sb[1]}")
+    if k is not None:
+        if int(k) != k or not 1 <= k <= FEATURE_K_CAP:
+            raise ValueError(f"k must be an integer in [1, {FEATURE_K_CAP}], got {k}")
+        if sb[0] < k + 1:
+            raise ValueError(f"the k + 1 = {k + 1} smallest distances of a row need at least {k + 1} rows of b, got {sb[0]}")
+    if ra is not None and tuple(ra) != (sa[0],):
+        raise ValueError(f"radius_sq_a must hold one value per row of a ({sa[0]}), got shape {tuple(ra)}")
+    if rb is not None and tuple(rb) != (sb[0],):
+        raise ValueError(f"radius_sq_b must hold one value per row of b ({sb[0]}), got shape {tuple(rb)}")
+    if int(row_offset) != row_offset or row_offset < 0:
+        raise ValueError(f"row_offset must be a non-negative integer, got {row_offset}")
+
+
+def feature_scan(a, b, k=None, radius_sq_a=None, radius_sq_b=None, poly=False, exclude_diagonal=False, row_offset=0):
+    """One scan of the rows of a (n_a, d) against the rows of b (n_b, d), device tensors of any float dtype (converted to
+    fp64), folded into per-row outputs: a FeatureScan of device tensors.  No (n_a, n_b) matrix is formed; the workspace is
+    O(n_a + n_b).  All arithmetic is fp64:
+
+        g(x, y)   the dot product as gram_f64 computes it (K ascending in one fixed order, no split-K)
+        s(x)      g(x, x), from the same product path
+        d2(x, y)  max(0, (s(x) + s(y)) - 2 g(x, y)), in that order: identical rows are at exactly 0.  No square root is taken
+        kappa     t = g(x, y) / d + 1; t * t * t          (the KID default: degree 3, gamma = 1 / d, coef0 = 1)
+
+        kmin_sq   (n_a, k + 1)  the k + 1 smallest d2 of the row, ascending            (k given; k <= FEATURE_K_CAP, n_b >= k + 1)
+        count_a   (n_a,) int32  #{j : d2 < radius_sq_a[row]}                          (radius_sq_a (n_a,) given)
+        count_b   (n_a,) int32  #{j : d2 < radius_sq_b[j]}                            (radius_sq_b (n_b,) given)
+        min_sq    (n_a,)        the smallest d2 of the row                            (always)
+        poly_sum  (n_a,)        sum_j kappa, ascending j within a column chunk and ascending chunks
+                                (feature_scan_column_chunk); with exclude_diagonal without j == row + row_offset   (poly)
+
+    Comparisons are strict.  A row's outputs depend on that row, on b and on row_offset alone: feature_scan(a[3:9], b, ...,
+    row_offset=3) equals rows 3 .. 8 of the whole scan bit for bit, and two calls agree bit for bit.  Raises ValueError for
+    arguments that do not fit (before the device is looked at) and for NaN / inf, RuntimeError for host tensors."""
+    a, b = _require_matrix(a, "a"), _require_matrix(b, "b")
+    for r in (radius_sq_a, radius_sq_b):
+        if r is not None and (not torch.is_tensor(r) or not r.is_floating_point()):
+            raise ValueError("a radius must be a floating-point tensor")
+    _scan_shapes(a.shape, b.shape, k, None if radius_sq_a is None else radius_sq_a.shape,
+                 None if radius_sq_b is None else radius_sq_b.shape, row_offset)
+    a, b = _on_device(a, b)
+    ra = None if radius_sq_a is None else _on_device(radius_sq_a)[0]
+    rb = None if radius_sq_b is None else _on_device(radius_sq_b)[0]
+    _lib.require_gpu()
+    n_a, n_b, dev = a.shape[0], b.shape[0], a.device
+    k1 = 0 if k is None else int(k) + 1
+    f64 = dict(dtype=torch.float64, device=dev)
+    out = FeatureScan(kmin_sq=torch.empty((n_a, k1), **f64) if k1 else None,
+                      count_a=torch.empty(n_a, dtype=torch.int32, device=dev) if ra is not None else None,
+                      count_b=torch.empty(n_a, dtype=torch.int32, device=dev) if rb is not None else None,
+                      min_sq=torch.empty(n_a, **f64), poly_sum=torch.empty(n_a, **f64) if poly else None)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    _frechet_check(_lib.lib().rldm_feature_scan_f64(a.data_ptr(), n_a, b.data_ptr(), n_b, a.shape[1], k1, ptr(ra), ptr(rb),
+                                                    1 if poly else 0, 1 if exclude_diagonal else 0, int(row_offset),
+                                                    ptr(out.kmin_sq), ptr(out.count_a), ptr(out.count_b), ptr(out.min_sq),
+                                                    ptr(out.poly_sum), _lib.stream_ptr(dev)), "rldm_feature_scan_f64")
+    return out
+
+
+def feature_scan_host(a, b, k=None, radius_sq_a=None, radius_sq_b=None, poly=False, exclude_diagonal=False, row_offset=0):
+    """The numpy statement of feature_scan (numpy arrays in, a FeatureScan of numpy arrays out): g = a @ b.T in fp64, s the
+    rows' sums of squares, np.sort for the smallest values, np.cumsum (one add after the other) for poly_sum within a column
+    chunk and the chunks added in ascending order.  Equal to the device bit for bit wherever the fp64 arithmetic is exact."""
+    import numpy as np
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    ra = None if radius_sq_a is None else np.asarray(radius_sq_a, dtype=np.float64)
+    rb = None if radius_sq_b is None else np.asarray(radius_sq_b, dtype=np.float64)
+    _scan_shapes(a.shape, b.shape, k, None if ra is None else ra.shape, None if rb is None else rb.shape, row_offset)
+    g = a @ b.T
+    s_a, s_b = np.einsum("ij,ij->i", a, a), np.einsum("ij,ij->i", b, b)
+    d2 = np.maximum(0.0, (s_a[:, None] + s_b[None, :]) - 2.0 * g)
+    poly_sum = None
+    if poly:
+        t = g / float(a.shape[1]) + 1.0
+        kappa = t * t * t
+        if exclude_diagonal:
+            rows = np.arange(a.shape[0]) + int(row_offset)
+            inside = rows < b.shape[0]
+            kappa[np.nonzero(inside)[0], rows[inside]] = 0.0             # x + 0.0 is x: the same as skipping it
+        chunk = feature_scan_column_chunk(b.shape[0])
+        poly_sum = np.zeros(a.shape[0])
+        for c0 in range(0, b.shape[0], chunk):
+            poly_sum = poly_sum + np.cumsum(kappa[:, c0:c0 + chunk], axis=1)[:, -1]
+    return FeatureScan(kmin_sq=np.sort(d2, axis=1)[:, :k + 1] if k is not None else None,
+                       count_a=(d2 < ra[:, None]).sum(1).astype(np.int32) if ra is not None else None,
+                       count_b=(d2 < rb[None, :]).sum(1).astype(np.int32) if rb is not None else None,
+                       min_sq=d2.min(1), poly_sum=poly_sum)
+
+
+def knn_radii_sq(x, k=5):
+    """r2_k(i): the (k + 1)-th smallest squared distance from row i of x to the rows of x, itself included (`prdc`'s
+    get_kth_value(..., nearest_k + 1), squared): feature_scan(x, x, k=k).kmin_sq[:, k]."""
+    return feature_scan(x, x, k=k).kmin_sq[:, k]
+
+
+def _prdc_shapes(sr, sf, k):
+    _scan_shapes(sr, sf, None, None, None, 0)
+    if int(k) != k or not 1 <= k <= FEATURE_K_CAP:
+        raise ValueError(f"k must be an integer in [1, {FEATURE_K_CAP}], got {k}")
+    if min(sr[0], sf[0]) < k + 1:
+        raise ValueError(f"a k = {k} neighbourhood needs at least {k + 1} rows per set, got {sr[0]} and {sf[0]}")
+
+
+def _prdc_scores(scan, to_host, real, fake, k, return_terms):
+    """The four scans and the four scores, for the device (scan = feature_scan) and the host statement alike."""
+    n, m = real.shape[0], fake.shape[0]
+    r_real = scan(real, real, k=k).kmin_sq[:, k]
+    r_fake = scan(fake, fake, k=k).kmin_sq[:, k]
+    by_real = scan(real, fake, radius_sq_a=r_real, radius_sq_b=r_fake)           # rows R against F
+    by_fake = scan(fake, real, radius_sq_b=r_real)                               # rows F against R
+    covered = by_real.min_sq < r_real
+    counts = {"precision_count": int(to_host(by_fake.count_b > 0).sum()), "recall_count": int(to_host(by_real.count_b > 0).sum()),
+              "density_count": int(to_host(by_fake.count_b).astype("int64").sum()), "coverage_count": int(to_host(covered).sum())}
+    out = {"precision": counts["precision_count"] / m, "recall": counts["recall_count"] / n,
+           "density": counts["density_count"] / (k * m), "coverage": counts["coverage_count"] / n}
+    if return_terms:
+        out.update(counts, radius_sq_real=r_real, radius_sq_fake=r_fake)
+    return out
+
+
+def prdc(real, fake, k=5, return_terms=False):
+    """Precision and recall (Kynkaanniemi et al. 2019), density and coverage (Naeem et al. 2020; the definitions of their
+    `prdc` package) of the generated set `fake` (M, d) against the real set `real` (N, d) on k-nearest-neighbour manifolds:
+    device tensors of any float dtype, N, M >= k + 1, 1 <= k <= FEATURE_K_CAP.  With d2 and r2_k as feature_scan and
+    knn_radii_sq define them (squared distances throughout, strict <):
+
+        precision = #{j : exists i, d2(R_i, F_j) < r2_k(R_i)} / M          recall   = #{i : exists j, d2(R_i, F_j) < r2_k(F_j)} / N
+        density   = sum_j #{i : d2(R_i, F_j) < r2_k(R_i)} / (k M)          coverage = #{i : min_j d2(R_i, F_j) < r2_k(R_i)} / N
+
+    Four scans (R.R, F.F, rows R against F, rows F against R), no (N, M) matrix; the counts are integers and each score is
+    one division of two Python ints.  Returns a dict of the four scores; return_terms=True adds precision_count,
+    recall_count, density_count, coverage_count and the radius vectors radius_sq_real, radius_sq_fake.  Raises ValueError
+    for arguments that do not fit (before the device is looked at) and for NaN / inf, RuntimeError for host tensors."""
+    real, fake = _require_matrix(real, "real"), _require_matrix(fake, "fake")
+    _prdc_shapes(real.shape, fake.shape, k)
+    real, fake = _on_device(real, fake)
+    return _prdc_scores(feature_scan, lambda t: t.cpu().numpy(), real, fake, int(k), return_terms)
+
+
+def prdc_host(real, fake, k=5, return_terms=False):
+    """The numpy statement of prdc (feature_scan_host underneath)."""
+    import numpy as np
+    real, fake = np.asarray(real, dtype=np.float64), np.asarray(fake, dtype=np.float64)
+    _prdc_shapes(real.shape, fake.shape, k)
+    return _prdc_scores(feature_scan_host, np.asarray, real, fake, int(k), return_terms)
+
+
+def _subset_args(n, m, subsets):
+    if int(subsets) != subsets or subsets < 1:
+        raise ValueError(f"subsets must be a positive integer, got {subsets}")
+    if int(m) != m or m < 2:
+        raise ValueError(f"subset_size must be an integer of at least 2, got {m}")
+    if m > n:
+        raise ValueError(f"subset_size {m} rows cannot be drawn from {n}")
+
+
+def kernel_subsets(n, m, subsets, seed, which):
+    """The rows of the `subsets` subset estimates of kernel_distance: estimate s uses
+    `random.Random(seed + 2 * s + which).sample(range(n), m)`, which = 0 for x and 1 for y (frd_indices' generator)."""
+    import random
+    if which not in (0, 1):
+        raise ValueError(f"which must be 0 (x) or 1 (y), got {which}")
+    _subset_args(n, m, subsets)
+    return [random.Random(int(seed) + 2 * s + which).sample(range(int(n)), int(m)) for s in range(int(subsets))]
+
+
+def _krd_shapes(sx, sy, subset_size, subsets):
+    _scan_shapes(sx, sy, None, None, None, 0)
+    if sx[0] < 2 or sy[0] < 2:
+        raise ValueError(f"the unbiased estimate needs at least 2 rows per set, got {sx[0]} and {sy[0]}")
+    if subset_size is not None:
+        _subset_args(min(sx[0], sy[0]), subset_size, subsets)
+
+
+def _krd_value(scan, to_list, x, y):
+    import math
+    n1, n2 = x.shape[0], y.shape[0]
+    sxx = math.fsum(to_list(scan(x, x, poly=True, exclude_diagonal=True).poly_sum))
+    syy = math.fsum(to_list(scan(y, y, poly=True, exclude_diagonal=True).poly_sum))
+    sxy = math.fsum(to_list(scan(x, y, poly=True).poly_sum))
+    return sxx / (n1 * (n1 - 1)) + syy / (n2 * (n2 - 1)) - (2.0 * sxy) / (n1 * n2), (sxx, syy, sxy)
+
+
+def _krd(scan, to_list, take, x, y, subset_size, subsets, seed, return_terms):
+    import math
+    if subset_size is None:
+        krd, (sxx, syy, sxy) = _krd_value(scan, to_list, x, y)
+        return {"krd": krd, "sum_xx": sxx, "sum_yy": syy, "sum_xy": sxy} if return_terms else krd
+    rows_x = kernel_subsets(x.shape[0], subset_size, subsets, seed, 0)
+    rows_y = kernel_subsets(y.shape[0], subset_size, subsets, seed, 1)
+    estimates = [_krd_value(scan, to_list, take(x, ix), take(y, iy))[0] for ix, iy in zip(rows_x, rows_y)]
+    mean = math.fsum(estimates) / len(estimates)
+    std = math.sqrt(math.fsum((e - mean) ** 2 for e in estimates) / len(estimates))
+    out = {"krd": mean, "krd_std": std}
+    if return_terms:
+        out.update(estimates=estimates, subsets=int(subsets), subset_size=int(subset_size))
+    return out
+
+
+def kernel_distance(x, y, subset_size=None, subsets=100, seed=0, return_terms=False):
+    """KRD: KID's unbiased estimate of the squared MMD (Binkowski et al. 2018) with the polynomial kernel
+    kappa(a, b) = (g(a, b) / d + 1)^3 between two sets of activations, (n1, d) and (n2, d) device tensors of any float dtype,
+    n1, n2 >= 2:
+
+        KRD = sum_{i != j} kappa(x_i, x_j) / (n1 (n1 - 1)) + sum_{i != j} kappa(y_i, y_j) / (n2 (n2 - 1))
+              - 2 sum_{i, j} kappa(x_i, y_j) / (n1 n2)
+
+    Three scans (feature_scan(poly=True): per-row sums over ascending j, the diagonal skipped in the self terms), no (n1, n2)
+    matrix; the three totals are math.fsum of the row sums, so they do not depend on how rows were batched.  Unlike the
+    Frechet distance the estimate has no bias that depends on n.  The value is not clamped at 0.
+
+    subset_size=None: the full-set estimate, a float (return_terms=True: a dict krd, sum_xx, sum_yy, sum_xy).
+    subset_size=m: a dict krd (the mean) and krd_std (the population standard deviation) over `subsets` estimates, estimate s
+    on the rows kernel_subsets(n1, m, subsets, seed, 0)[s] of x and kernel_subsets(n2, m, subsets, seed, 1)[s] of y;
+    return_terms=True adds estimates, subsets and subset_size.
+    Raises ValueError for arguments that do not fit (before the device is looked at) and for NaN / inf, RuntimeError for host
+    tensors."""
+    x, y = _require_matrix(x, "x"), _require_matrix(y, "y")
+    _krd_shapes(x.shape, y.shape, subset_size, subsets)
+    x, y = _on_device(x, y)
+    take = lambda t, rows: t[torch.as_tensor(rows, device=t.device)]
+    return _krd(feature_scan, lambda t: t.cpu().tolist(), take, x, y, subset_size, subsets, seed, return_terms)
+
+
+def kernel_distance_host(x, y, subset_size=None, subsets=100, seed=0, return_terms=False):
+    """The numpy statement of kernel_distance (feature_scan_host underneath)."""
+    import numpy as np
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    _krd_shapes(x.shape, y.shape, subset_size, subsets)
+    return _krd(feature_scan_host, lambda t: t.tolist(), lambda t, rows: t[np.asarray(rows)], x, y, subset_size, subsets, seed,
+                return_terms)
 
 
 def farthest_point_sample(x, k, x_lengths=None, start=0):
