@@ -29,7 +29,7 @@
 //
 // Preconditions: clouds are non-empty (the Python layer raises ValueError); coordinates are finite -- NaN or inf inputs
 // give unspecified results (not checked).
-#include "common.h"
+#include "eval_common.h"
 #include "../../include/rangeldm_hip.h"
 
 #include <cmath>
@@ -129,17 +129,6 @@ __global__ __launch_bounds__(NN_THREADS) void chamfer_nn_kernel(const float* __r
             if (i < nq) atomicMin(out + q0 + i, __float_as_uint(h ? best[k].y : best[k].x));
         }
     }
-}
-
-// fixed-order block sum (shuffle tree inside each wave, then the wave partials in wave order): bit-identical run to run
-__device__ inline double block_sum(double v, double* sh) {
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sh[w];
-    return t;
 }
 
 // grid (num_pairs, 2): y = 0 the x -> y direction, 1 the y -> x direction
@@ -404,8 +393,9 @@ int rldm_chamfer_nn(const float* x, const int32_t* x_offsets, int x_stride, cons
         RLDM_REQUIRE(acc < (1LL << 31) / NN_THREADS, "too many workgroups");
         ws[num_pairs] = (int32_t)acc;
     }
-    int32_t* dstarts = nullptr;
-    RLDM_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&dstarts), starts.size() * sizeof(int32_t), st));
+    DevBuf dbuf(st);
+    RLDM_HIP_CHECK(dbuf.alloc(starts.size() * sizeof(int32_t)));
+    int32_t* dstarts = dbuf.as<int32_t>();
     RLDM_HIP_CHECK(hipMemcpyAsync(dstarts, starts.data(), starts.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     RLDM_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(x_nn_d2), 0x7f800000, (size_t)xo[num_pairs], st));
     RLDM_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(y_nn_d2), 0x7f800000, (size_t)yo[num_pairs], st));
@@ -421,7 +411,6 @@ int rldm_chamfer_nn(const float* x, const int32_t* x_offsets, int x_stride, cons
                                                            reinterpret_cast<unsigned*>(y_nn_d2));
         RLDM_HIP_CHECK(hipGetLastError());
     }
-    RLDM_HIP_CHECK(hipFreeAsync(dstarts, st));
     RLDM_HIP_CHECK(hipStreamSynchronize(st));          // `starts` (pageable host memory) must outlive its upload
     return 0;
 }
@@ -482,10 +471,11 @@ int rldm_chamfer_matrix(const float* x, const int32_t* x_offsets, int x_stride, 
         runs[d] = (int)((n[t] + len - 1) / len);
         RLDM_REQUIRE(blocks * runs[d] < MX_MAX_WGS, "too many workgroups");
     }
-    int32_t* dqb = nullptr;
-    double* part = nullptr;
-    RLDM_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&dqb), qbs.size() * sizeof(int32_t), st));
-    RLDM_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&part), (size_t)part_len * sizeof(double), st));
+    DevBuf qbuf(st), pbuf(st);
+    RLDM_HIP_CHECK(qbuf.alloc(qbs.size() * sizeof(int32_t)));
+    RLDM_HIP_CHECK(pbuf.alloc((size_t)part_len * sizeof(double)));
+    int32_t* dqb = qbuf.as<int32_t>();
+    double* part = pbuf.as<double>();
     RLDM_HIP_CHECK(hipMemcpyAsync(dqb, qbs.data(), qbs.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if (symmetric) {                                     // the diagonal; every other entry is written below
         RLDM_HIP_CHECK(hipMemsetAsync(xy, 0, (size_t)nx * ny * sizeof(double), st));
@@ -510,8 +500,6 @@ int rldm_chamfer_matrix(const float* x, const int32_t* x_offsets, int x_stride, 
         }
         RLDM_HIP_CHECK(hipGetLastError());
     }
-    RLDM_HIP_CHECK(hipFreeAsync(part, st));
-    RLDM_HIP_CHECK(hipFreeAsync(dqb, st));
     RLDM_HIP_CHECK(hipStreamSynchronize(st));          // `qbs` (pageable host memory) must outlive its upload
     return 0;
 }

@@ -26,7 +26,7 @@
 //
 // Preconditions: both clouds of a pair hold the same N <= 2048 points (checked on the host from the offsets); coordinates
 // are finite -- NaN or inf inputs give unspecified results, but the bid cap still ends every pair.
-#include "common.h"
+#include "eval_common.h"
 #include "../../include/rangeldm_hip.h"
 
 #include <cmath>
@@ -256,8 +256,9 @@ int rldm_emd_matrix(const float* x, const int32_t* x_offsets, int x_stride, int 
     for (int c = 0; c < nx; ++c) RLDM_REQUIRE(xo[c + 1] - xo[c] == N, "EMD is a one-to-one matching: every cloud must hold the same number of points");
     for (int c = 0; c < ny; ++c) RLDM_REQUIRE(yo[c + 1] - yo[c] == N, "EMD is a one-to-one matching: every cloud must hold the same number of points");
 
-    int* flag = nullptr;
-    RLDM_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&flag), sizeof(int), st));
+    DevBuf fbuf(st);
+    RLDM_HIP_CHECK(fbuf.alloc(sizeof(int)));
+    int* flag = fbuf.as<int>();
     RLDM_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flag), INT_MAX, 1, st));
     if (symmetric == RLDM_EMD_SYMMETRIC) {               // the diagonal; every other entry is written by its pair
         RLDM_HIP_CHECK(hipMemsetAsync(emd_out, 0, (size_t)nx * ny * sizeof(double), st));
@@ -279,7 +280,6 @@ int rldm_emd_matrix(const float* x, const int32_t* x_offsets, int x_stride, int 
     RLDM_HIP_CHECK(err);
     int flagged = INT_MAX;
     RLDM_HIP_CHECK(hipMemcpyAsync(&flagged, flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    RLDM_HIP_CHECK(hipFreeAsync(flag, st));
     RLDM_HIP_CHECK(hipStreamSynchronize(st));
     if (flagged != INT_MAX) {
         const int i = symmetric == RLDM_EMD_DIAGONAL ? flagged : flagged / ny;

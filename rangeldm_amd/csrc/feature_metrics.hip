@@ -2,12 +2,12 @@
 // an n_a x n_b matrix: what the kernel distance (KID's unbiased polynomial-kernel MMD^2) and precision /
 // recall / density / coverage on k-nearest-neighbour manifolds (Kynkaanniemi et al. 2019, Naeem et al. 2020) reduce to.
 //
-//   g(a, b)   the dot product, K ascending in one fixed order without split-K: the tile of fr_gram_kernel (frechet.hip)
+//   g(a, b)   the dot product, K ascending in one fixed order without split-K: the tile of gram_f64.h, which fr_gram_kernel
+//             (frechet.hip) stores, so g is the value rldm_gram_f64 gives
 //   s(a)      g(a, a), from the same product path (fs_rownorm_kernel runs the diagonal MFMA tiles of x . x^T)
 //   d2(a, b)  max(0, (s(a) + s(b)) - 2 g(a, b)), in that order: two identical rows are at exactly 0
 //   kappa     t = g / d + 1; t * t * t
 //
-//   fs_finite_kernel     NaN / inf anywhere in an input: the call returns before anything else runs
 //   fs_rownorm_kernel    s(x_i): one wave per 16 rows runs their 16 x 16 diagonal tile of x . x^T and keeps its diagonal
 //   fs_scan_kernel       workgroup (c, r) owns rows 64 r .. 64 r + 63 of A and streams the columns of chunk c of B past them
 //                        in tiles of 64: products on v_mfma_f64_16x16x4_f64, the tile to LDS (over the operand stages, which
@@ -19,24 +19,21 @@
 // row's outputs depend on that row and on B alone whatever the grid.  The k + 1 smallest values, integer counts and a
 // minimum do not depend on the merge order; poly_sum is the sum, over ascending chunks, of each chunk's ascending-j sum.
 //
-// f64 MFMA layout: A / B one f64 per lane, row (of A) or column (of B) lane & 15, k = lane >> 4; C / D four f64 per lane,
-// column lane & 15, row (lane >> 4) + 4 * reg.
-#include "common.h"
+// NaN / inf anywhere in an input: the call returns before anything else runs (eval_common.h's check_finite_f64).
+#include "eval_common.h"
+#include "gram_f64.h"
 #include "../../include/rangeldm_hip.h"
 
-#include <algorithm>
 #include <cmath>
+
+#pragma clang fp contract(off)      // (+ -ffp-contract=off in the Makefile) (s_a + s_b) - 2 g and t * t * t are single IEEE ops
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) double f64x4;
-
-constexpr int FS_THREADS = 256;
-constexpr int FS_TILE = 64;              // rows of A a workgroup owns; columns of B per tile: 4 waves x (32 x 32)
-constexpr int FS_BK = 32;                // K per LDS stage
-constexpr int FS_LD = FS_BK + 1;         // LDS row pitch of an operand stage (f64)
+constexpr int FS_THREADS = GR_THREADS;
+constexpr int FS_TILE = GR_TILE;         // rows of A a workgroup owns; columns of B per tile
 constexpr int FS_TLD = FS_TILE + 1;      // LDS row pitch of the product tile (f64)
-constexpr int FS_LDS = 2 * FS_TILE * FS_LD;              // f64 in LDS: two operand stages, or (over them) one product tile
+constexpr int FS_LDS = GR_LDS;           // f64 in LDS: the tile's two operand stages, or (over them) one product tile
 constexpr int FS_K1 = RLDM_FEATURE_MAX_K + 1;            // longest list of smallest values a row keeps
 constexpr int FS_MAX_CHUNKS = 16;
 constexpr int FS_MAX_ROWS = 65535 * FS_TILE;             // rows of A: one grid dimension of row blocks
@@ -52,58 +49,9 @@ struct ScanArgs {
     double* kmin; int* count_a; int* count_b; double* min_sq; double* poly_sum;
 };
 
-__global__ __launch_bounds__(FS_THREADS) void fs_finite_kernel(const double* __restrict__ x, size_t n, int* __restrict__ flag) {
-    bool bad = false;
-    for (size_t i = (size_t)blockIdx.x * FS_THREADS + threadIdx.x; i < n; i += (size_t)gridDim.x * FS_THREADS)
-        bad |= !__builtin_isfinite(x[i]);
-    if (bad) atomicOr(flag, 1);
-}
-
-// acc = rows i0 .. i0 + 63 of a times rows j0 .. j0 + 63 of b, transposed: fr_gram_kernel's loop, stage for stage (K ascending
-// in steps of 32 through LDS, zero filled at every edge), so an entry is the value rldm_gram_f64 gives for its two rows.  Wave w
-// owns the 32 x 32 block (w >> 1, w & 1) as 2 x 2 MFMA tiles.  Ends behind a barrier: LDS is free when it returns.
-__device__ __forceinline__ void tile_products(const double* __restrict__ a, int n_a, int i0, const double* __restrict__ b,
-                                              int n_b, int j0, int d, double* __restrict__ lds, f64x4 (&acc)[2][2]) {
-    double* __restrict__ As = lds;
-    double* __restrict__ Bs = lds + FS_TILE * FS_LD;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
-    const int lk = t & 31, lr = t >> 5;                  // loader: 32 consecutive k of 8 rows per pass
-    const int fr = lane & 15, fk = lane >> 4;            // fragment: row (column) and k of this lane
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n) acc[m][n] = f64x4{0.0, 0.0, 0.0, 0.0};
-    for (int k0 = 0; k0 < d; k0 += FS_BK) {
-        const int k = k0 + lk;
-#pragma unroll
-        for (int p = 0; p < FS_TILE / 8; ++p) {
-            const int r = lr + 8 * p;
-            const int gi = i0 + r, gj = j0 + r;
-            As[r * FS_LD + lk] = (gi < n_a && k < d) ? a[(size_t)gi * d + k] : 0.0;
-            Bs[r * FS_LD + lk] = (gj < n_b && k < d) ? b[(size_t)gj * d + k] : 0.0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < FS_BK; kk += 4) {
-            double af[2], bf[2];
-#pragma unroll
-            for (int m = 0; m < 2; ++m) af[m] = As[(wr + 16 * m + fr) * FS_LD + kk + fk];
-#pragma unroll
-            for (int n = 0; n < 2; ++n) bf[n] = Bs[(wc + 16 * n + fr) * FS_LD + kk + fk];
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int n = 0; n < 2; ++n)
-                    acc[m][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[m], bf[n], acc[m][n], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-}
-
 // norm[i] = g(x_i, x_i), one wave per 16 rows of a (the first blocks) or of b, straight from global memory.  In the f64 MFMA
 // the A fragment of lane (r = lane & 15, q = lane >> 4) is x[r][k + q] and so is the B fragment, so one register feeds both
-// operands; K is walked as tile_products walks it (ascending steps of 4 into one accumulator; its zero-filled steps add +0),
+// operands; K is walked as gram_f64.h's tile walks it (ascending steps of 4 into one accumulator; its zero-filled steps add +0),
 // so the diagonal of the 16 x 16 result is, bit for bit, what a tile holds for a row against itself.  Lane (r, q) holds
 // result rows q + 4 reg of column r: the diagonal entry of row r sits in lane q == r & 3, reg r >> 2.
 constexpr int FS_NORM_STEPS = 16;                        // MFMA steps (of 4 k) per round of loads
@@ -166,7 +114,7 @@ __global__ __launch_bounds__(FS_THREADS, 4) void fs_scan_kernel(const ScanArgs p
 
     for (int j0 = c0; j0 < c1; j0 += FS_TILE) {
         f64x4 acc[2][2];
-        tile_products(p.a, p.n_a, i0, p.b, p.n_b, j0, p.d, lds, acc);
+        gram_tile_f64(p.a, p.n_a, i0, p.b, p.n_b, j0, p.d, lds, acc);
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -258,20 +206,6 @@ __global__ __launch_bounds__(FS_THREADS) void fs_merge_kernel(const MergeArgs p)
     if (p.poly_sum) p.poly_sum[i] = ps;
 }
 
-// a device allocation that is returned to the stream's pool on every way out of a call
-struct DevBuf {
-    void* p = nullptr;
-    hipStream_t st;
-    explicit DevBuf(hipStream_t s) : st(s) {}
-    ~DevBuf() { if (p) (void)hipFreeAsync(p, st); }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    hipError_t alloc(size_t bytes) { return hipMallocAsync(&p, bytes, st); }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-int grid_for(size_t n) { return (int)std::min<size_t>((n + FS_THREADS - 1) / FS_THREADS, 4096); }
-
 int chunk_cols(int n_b) {
     const int tiles = (n_b + FS_TILE - 1) / FS_TILE;
     return FS_TILE * ((tiles + FS_MAX_CHUNKS - 1) / FS_MAX_CHUNKS);
@@ -300,23 +234,9 @@ int rldm_feature_scan_f64(const double* a, int n_a, const double* b, int n_b, in
     const bool self = a == b && n_a == n_b;
     const size_t na = (size_t)n_a, nb = (size_t)n_b;
 
-    {                                                    // NaN / inf anywhere: refused before anything else runs
-        DevBuf flag(st);
-        RLDM_HIP_CHECK(flag.alloc(sizeof(int)));
-        RLDM_HIP_CHECK(hipMemsetAsync(flag.p, 0, sizeof(int), st));
-        fs_finite_kernel<<<grid_for(na * d), FS_THREADS, 0, st>>>(a, na * d, flag.as<int>());
-        if (!self) fs_finite_kernel<<<grid_for(nb * d), FS_THREADS, 0, st>>>(b, nb * d, flag.as<int>());
-        if (radius_sq_a) fs_finite_kernel<<<grid_for(na), FS_THREADS, 0, st>>>(radius_sq_a, na, flag.as<int>());
-        if (radius_sq_b) fs_finite_kernel<<<grid_for(nb), FS_THREADS, 0, st>>>(radius_sq_b, nb, flag.as<int>());
-        RLDM_HIP_CHECK(hipGetLastError());
-        int bad = 0;
-        RLDM_HIP_CHECK(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        RLDM_HIP_CHECK(hipStreamSynchronize(st));
-        if (bad) {
-            rldm::set_error("the input holds NaN or inf; nothing was computed");
-            return RLDM_FRECHET_NONFINITE;
-        }
-    }
+    // NaN / inf anywhere: refused before anything else runs
+    if (int rc = rldm::check_finite_f64({{a, na * d}, {self ? nullptr : b, nb * d}, {radius_sq_a, na}, {radius_sq_b, nb}}, st))
+        return rc;
 
     const int cc = chunk_cols(n_b);
     const int chunks = (n_b + cc - 1) / cc;

@@ -32,7 +32,7 @@
 // are finite (the Python layer refuses others): min / arg-max over NaN is not a defined order.  Even so no index leaves
 // [0, P): a NaN never passes the strict > that tracks a lane's best, every coordinate offset is clamped to the cloud's last
 // point, and the winner is clamped to [0, P) before it is used or written.
-#include "common.h"
+#include "eval_common.h"
 #include "../../include/rangeldm_hip.h"
 
 #include <cmath>
@@ -217,15 +217,14 @@ int rldm_farthest_point_sample(const float* x, const int32_t* offsets, int strid
         RLDM_REQUIRE(!start || (first[c] >= 0 && first[c] < P), who + "start must be an index of the cloud");
         largest = std::max(largest, (int)P);
     }
-    float* ws = nullptr;                                 // the second tier's min-distances, one fp32 per packed point
-    if (largest > FPS_RESIDENT)
-        RLDM_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&ws), (size_t)off[num_clouds] * sizeof(float), st));
     static rldm::DynLdsLimit lds_limit;
     RLDM_HIP_CHECK(lds_limit.ensure(reinterpret_cast<const void*>(&fps_kernel), FPS_LDS_BYTES));
-    fps_kernel<<<num_clouds, FPS_BLOCK, FPS_LDS_BYTES, st>>>(x, offsets, stride, k, start, ws, idx_out);
-    const hipError_t err = hipGetLastError();
-    if (ws) RLDM_HIP_CHECK(hipFreeAsync(ws, st));
-    RLDM_HIP_CHECK(err);
+    {   // the workspace goes back to the pool before the wait below, not after it: measured 1 % on a 131 072-point cloud
+        DevBuf ws(st);                                   // the second tier's min-distances, one fp32 per packed point
+        if (largest > FPS_RESIDENT) RLDM_HIP_CHECK(ws.alloc((size_t)off[num_clouds] * sizeof(float)));
+        fps_kernel<<<num_clouds, FPS_BLOCK, FPS_LDS_BYTES, st>>>(x, offsets, stride, k, start, ws.as<float>(), idx_out);
+        RLDM_HIP_CHECK(hipGetLastError());
+    }
     RLDM_HIP_CHECK(hipStreamSynchronize(st));
     return 0;
 }

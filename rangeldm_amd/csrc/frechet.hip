@@ -5,21 +5,20 @@
 //     Tr sqrtm(C1 C2) = |A B^T|_* / sqrt((n1 - 1)(n2 - 1))          (the non-zero eigenvalues of A^T A B^T B are the squared
 //     Tr C1 = sum A^2 / (n1 - 1)                                      singular values of A B^T)
 //
-//   fr_finite_kernel        NaN / inf anywhere in an input: the call returns before anything else runs
+//   fr_finite_kernel        NaN / inf anywhere in an input: the call returns before anything else runs (the library's one
+//                           finite check, rldm::check_finite_f64 of eval_common.h; feature_metrics.hip calls it too)
 //   fr_colmean_kernel       column means, samples summed in ascending order (one thread per column)
 //   fr_center_kernel        A = X - mean and per-row sum A^2 (one workgroup per row, fixed-order tree)
 //   fr_totals_kernel        sum A^2, sum B^2, |mu1 - mu2|^2 (one workgroup, fixed-order trees)
-//   fr_gram_kernel          M = A . B^T on v_mfma_f64_16x16x4_f64: a 64 x 64 tile per workgroup, K ascending in steps of 32
-//                           through LDS, zero filled at every edge; no split-K, so an entry depends on its two rows alone
+//   fr_gram_kernel          M = A . B^T on v_mfma_f64_16x16x4_f64: the tile of gram_f64.h (64 x 64 per workgroup, K ascending
+//                           in steps of 32 through LDS, no split-K), stored
 //   fr_jacobi_step_kernel   one step of a one-sided (Hestenes) Jacobi sweep: one workgroup per column pair of the round-robin
 //                           schedule.  The pairs of a step are disjoint, so no workgroup reads what another writes; the next
 //                           step is the next launch.  Nothing in here waits on another workgroup or loops on convergence: the
 //                           host counts sweeps and gives up at its cap.
 //   fr_colnorm_kernel       the singular values: the final column norms
-//
-// f64 MFMA layout (NOT the one the f32-accumulator shapes share): A / B one f64 per lane, row (of A) or column (of B)
-// lane & 15, k = lane >> 4; C / D four f64 per lane, column lane & 15, row (lane >> 4) + 4 * reg.
-#include "common.h"
+#include "eval_common.h"
+#include "gram_f64.h"
 #include "../../include/rangeldm_hip.h"
 
 #include <algorithm>
@@ -29,17 +28,13 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) double f64x4;
-
-constexpr int FR_THREADS = 256;
-constexpr int GR_TILE = 64;          // output tile of a workgroup: 4 waves x (32 x 32)
-constexpr int GR_BK = 32;            // K per LDS stage
-constexpr int GR_LD = GR_BK + 1;     // LDS row pitch (f64)
+constexpr int FR_THREADS = GR_THREADS;                   // every kernel here, the tile's among them
 constexpr int GR_MAX_ROWS = 65535 * GR_TILE;             // rows of either operand: one grid dimension of tiles
 
 thread_local int fr_last_sweeps = 0;
 
-// sum of one value per thread over the workgroup, the same tree every time; every thread gets the result
+// sum of one value per thread over the workgroup, the same tree every time; every thread gets the result.  (Not
+// eval_common.h's block_sum: an LDS tree adds in another order, and the Frechet distance's last bits are this order's.)
 __device__ __forceinline__ double block_sum_fixed(double v, double* lds) {
     const int t = threadIdx.x;
     lds[t] = v;
@@ -109,43 +104,12 @@ __global__ __launch_bounds__(FR_THREADS) void fr_totals_kernel(const double* __r
 // grid (ceil(n2 / 64), ceil(n1 / 64)); wave w owns the 32 x 32 block (w >> 1, w & 1) of the tile as 2 x 2 MFMA tiles
 __global__ __launch_bounds__(FR_THREADS) void fr_gram_kernel(const double* __restrict__ a, int n1, const double* __restrict__ b,
                                                             int n2, int d, double* __restrict__ out) {
-    __shared__ double As[GR_TILE * GR_LD], Bs[GR_TILE * GR_LD];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    __shared__ double lds[GR_LDS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i0 = blockIdx.y * GR_TILE, j0 = blockIdx.x * GR_TILE;
-    const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
-    const int lk = t & 31, lr = t >> 5;                  // loader: 32 consecutive k of 8 rows per pass
-    const int fr = lane & 15, fk = lane >> 4;            // fragment: row (column) and k of this lane
+    const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32, fr = lane & 15, fk = lane >> 4;
     f64x4 acc[2][2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n) acc[m][n] = f64x4{0.0, 0.0, 0.0, 0.0};
-
-    for (int k0 = 0; k0 < d; k0 += GR_BK) {
-        const int k = k0 + lk;
-#pragma unroll
-        for (int p = 0; p < GR_TILE / 8; ++p) {
-            const int r = lr + 8 * p;
-            const int gi = i0 + r, gj = j0 + r;
-            As[r * GR_LD + lk] = (gi < n1 && k < d) ? a[(size_t)gi * d + k] : 0.0;
-            Bs[r * GR_LD + lk] = (gj < n2 && k < d) ? b[(size_t)gj * d + k] : 0.0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < GR_BK; kk += 4) {
-            double af[2], bf[2];
-#pragma unroll
-            for (int m = 0; m < 2; ++m) af[m] = As[(wr + 16 * m + fr) * GR_LD + kk + fk];
-#pragma unroll
-            for (int n = 0; n < 2; ++n) bf[n] = Bs[(wc + 16 * n + fr) * GR_LD + kk + fk];
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int n = 0; n < 2; ++n)
-                    acc[m][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[m], bf[n], acc[m][n], 0, 0, 0);
-        }
-        __syncthreads();
-    }
+    gram_tile_f64(a, n1, i0, b, n2, j0, d, lds, acc);
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -215,40 +179,7 @@ __global__ __launch_bounds__(FR_THREADS) void fr_colnorm_kernel(const double* __
     if (threadIdx.x == 0) sv[blockIdx.x] = sqrt(s);
 }
 
-// a device allocation that is returned to the stream's pool on every way out of a call
-struct DevBuf {
-    void* p = nullptr;
-    hipStream_t st;
-    explicit DevBuf(hipStream_t s) : st(s) {}
-    ~DevBuf() { if (p) (void)hipFreeAsync(p, st); }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    hipError_t alloc(size_t bytes) { return hipMallocAsync(&p, bytes, st); }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
 int grid_for(size_t n) { return (int)std::min<size_t>((n + FR_THREADS - 1) / FR_THREADS, 4096); }
-
-// 0, or RLDM_FRECHET_NONFINITE when one of the (up to two) arrays holds NaN / inf.  Synchronises.
-int check_finite(const double* x, size_t nx, const double* y, size_t ny, hipStream_t st) {
-    DevBuf flag(st);
-    RLDM_HIP_CHECK(flag.alloc(sizeof(int)));
-    RLDM_HIP_CHECK(hipMemsetAsync(flag.p, 0, sizeof(int), st));
-    fr_finite_kernel<<<grid_for(nx), FR_THREADS, 0, st>>>(x, nx, flag.as<int>());
-    RLDM_HIP_CHECK(hipGetLastError());
-    if (y) {
-        fr_finite_kernel<<<grid_for(ny), FR_THREADS, 0, st>>>(y, ny, flag.as<int>());
-        RLDM_HIP_CHECK(hipGetLastError());
-    }
-    int bad = 0;
-    RLDM_HIP_CHECK(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    RLDM_HIP_CHECK(hipStreamSynchronize(st));
-    if (bad) {
-        rldm::set_error("the input holds NaN or inf; nothing was computed");
-        return RLDM_FRECHET_NONFINITE;
-    }
-    return 0;
-}
 
 int launch_gram(const double* a, int n1, const double* b, int n2, int d, double* out, hipStream_t st) {
     const dim3 grid((n2 + GR_TILE - 1) / GR_TILE, (n1 + GR_TILE - 1) / GR_TILE);
@@ -305,6 +236,25 @@ int jacobi_singular_values(const double* m, int rows, int cols, double tol, int 
 
 }  // namespace
 
+int rldm::check_finite_f64(std::initializer_list<std::pair<const double*, size_t>> arrays, hipStream_t st) {
+    DevBuf flag(st);
+    RLDM_HIP_CHECK(flag.alloc(sizeof(int)));
+    RLDM_HIP_CHECK(hipMemsetAsync(flag.p, 0, sizeof(int), st));
+    for (const auto& arr : arrays) {
+        if (!arr.first) continue;
+        fr_finite_kernel<<<grid_for(arr.second), FR_THREADS, 0, st>>>(arr.first, arr.second, flag.as<int>());
+        RLDM_HIP_CHECK(hipGetLastError());
+    }
+    int bad = 0;
+    RLDM_HIP_CHECK(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    RLDM_HIP_CHECK(hipStreamSynchronize(st));
+    if (bad) {
+        rldm::set_error("the input holds NaN or inf; nothing was computed");
+        return RLDM_FRECHET_NONFINITE;
+    }
+    return 0;
+}
+
 extern "C" {
 
 int rldm_gram_f64(const double* a, int n1, const double* b, int n2, int d, double* out, void* stream) {
@@ -324,7 +274,7 @@ int rldm_singular_values_f64(const double* m, int rows, int cols, double tol, in
     RLDM_REQUIRE(!(tol > 0.0) || std::isfinite(tol), "tol must be finite");
     hipStream_t st = (hipStream_t)stream;
     if (sweeps_out) *sweeps_out = 0;
-    if (int rc = check_finite(m, (size_t)rows * cols, nullptr, 0, st)) return rc;
+    if (int rc = rldm::check_finite_f64({{m, (size_t)rows * cols}}, st)) return rc;
     std::vector<double> sv;
     if (int rc = jacobi_singular_values(m, rows, cols, tol, max_sweeps, sv, sweeps_out, st)) return rc;
     RLDM_HIP_CHECK(hipMemcpyAsync(sv_out, sv.data(), sv.size() * sizeof(double), hipMemcpyHostToDevice, st));
@@ -340,7 +290,7 @@ int rldm_frechet_distance(const double* x, int n1, const double* y, int n2, int 
     RLDM_REQUIRE(n1 <= GR_MAX_ROWS && n2 <= GR_MAX_ROWS, "too many samples (a grid dimension holds 65535 tiles of 64 rows)");
     hipStream_t st = (hipStream_t)stream;
     fr_last_sweeps = 0;
-    if (int rc = check_finite(x, (size_t)n1 * d, y, (size_t)n2 * d, st)) return rc;
+    if (int rc = rldm::check_finite_f64({{x, (size_t)n1 * d}, {y, (size_t)n2 * d}}, st)) return rc;
 
     // one allocation: A, B, M, mu1, mu2, rowsq1, rowsq2, totals
     const size_t na = (size_t)n1 * d, nb = (size_t)n2 * d, nm = (size_t)n1 * n2;

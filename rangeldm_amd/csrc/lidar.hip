@@ -11,25 +11,17 @@
 //                                                                            ldm/dataset.py:159-226
 // The arithmetic keeps the reference's fp32 operation order (no FMA contraction) so cell indices and the ordered
 // compaction agree with the torch/numpy result wherever the inputs do.
-#include "common.h"
+#include "eval_common.h"
 #include "../../include/rangeldm_hip.h"
 
 #include <cmath>
 #include <map>
 #include <vector>
 
-#pragma clang fp contract(off)      // and -ffp-contract=off for this file in the Makefile (covers the header inlines)
+#pragma clang fp contract(off)      // and -ffp-contract=off for this file in the Makefile (covers the header inlines and
+                                    // eval_common.h's f_mul / f_add / f_sub / f_div / f_sqrt, which the arithmetic here uses)
 
 namespace {
-
-// One IEEE operation each, correctly rounded: plain operators under -ffp-contract=off, and sqrtf / `/` under hipcc's default
-// -fhip-fp32-correctly-rounded-divide-sqrt.  (HIP's __fsqrt_rn / __fdiv_rn intrinsics are the ~1 ulp native
-// instructions: measured 12 % of ranges off by one ulp against numpy.)
-__device__ inline float f_mul(float a, float b) { return a * b; }
-__device__ inline float f_add(float a, float b) { return a + b; }
-__device__ inline float f_sub(float a, float b) { return a - b; }
-__device__ inline float f_div(float a, float b) { return a / b; }
-__device__ inline float f_sqrt(float a) { return sqrtf(a); }
 
 struct LidarDev {
     const float* cos_incl;

@@ -13,7 +13,7 @@
 // bin is corrected against them.  The spectral norm is fp32 (VALU FMA over LDS-resident 100 x 100 matrices): Gram matrix,
 // S trace-normalised squarings (power 2^S), two polishing products and a Rayleigh quotient on the Gram matrix -- the
 // quotient's error is the SQUARE of the eigenvector error, worst case 1 / (2e 2^S) relative.
-#include "common.h"
+#include "eval_common.h"
 #include "../../include/rangeldm_hip.h"
 
 #include <cmath>
@@ -62,16 +62,6 @@ __global__ __launch_bounds__(256) void hist_colsum_kernel(const unsigned* __rest
     unsigned long long acc = 0;
     for (int s = 0; s < S; ++s) acc += h[(size_t)s * nb + i];
     out[i] = acc;
-}
-
-__device__ inline double block_sum(double v, double* sh) {
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sh[w];
-    return t;
 }
 
 __global__ __launch_bounds__(1024) void jsd_kernel(const unsigned long long* __restrict__ px,
@@ -280,8 +270,9 @@ int rldm_hist_jsd(const uint32_t* hx, int nx, const uint32_t* hy, int ny, int bi
     RLDM_REQUIRE(nx > 0 && ny > 0 && bins > 0, "bad shape");
     hipStream_t st = (hipStream_t)stream;
     const int nb = bins * bins;
-    unsigned long long* sums = nullptr;                 // [2][nb] column sums, then one double for the result
-    RLDM_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&sums), (size_t)(2 * nb + 1) * sizeof(unsigned long long), st));
+    DevBuf buf(st);                                     // [2][nb] column sums, then one double for the result
+    RLDM_HIP_CHECK(buf.alloc((size_t)(2 * nb + 1) * sizeof(unsigned long long)));
+    unsigned long long* sums = buf.as<unsigned long long>();
     double* res = reinterpret_cast<double*>(sums + 2 * nb);
     hist_colsum_kernel<<<(nb + 255) / 256, 256, 0, st>>>(hx, nx, nb, sums);
     hist_colsum_kernel<<<(nb + 255) / 256, 256, 0, st>>>(hy, ny, nb, sums + nb);
@@ -289,7 +280,6 @@ int rldm_hist_jsd(const uint32_t* hx, int nx, const uint32_t* hy, int ny, int bi
     RLDM_HIP_CHECK(hipGetLastError());
     RLDM_HIP_CHECK(hipMemcpyAsync(jsd, res, sizeof(double), hipMemcpyDeviceToHost, st));
     RLDM_HIP_CHECK(hipStreamSynchronize(st));
-    RLDM_HIP_CHECK(hipFreeAsync(sums, st));
     return 0;
 }
 
@@ -301,22 +291,19 @@ int rldm_hist_spectral_sq(const uint32_t* hx, int nx, const uint32_t* hy, int ny
     RLDM_REQUIRE(!symmetric || (hx == hy && nx == ny), "symmetric needs the same histogram set on both sides");
     hipStream_t st = (hipStream_t)stream;
     const int nb = bins * bins;
-    double* inv = nullptr;
-    RLDM_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&inv), (size_t)(nx + ny) * sizeof(double), st));
+    DevBuf buf(st);
+    RLDM_HIP_CHECK(buf.alloc((size_t)(nx + ny) * sizeof(double)));
+    double* inv = buf.as<double>();
     hist_inv_total_kernel<<<nx, 256, 0, st>>>(hx, nb, inv);
     hist_inv_total_kernel<<<ny, 256, 0, st>>>(hy, nb, inv + nx);
     RLDM_HIP_CHECK(hipMemsetAsync(lambda, 0, (size_t)nx * ny * sizeof(float), st));
     constexpr int S = 12;
     auto kern = spectral_sq_kernel<S>;
     const size_t lds = (size_t)3 * NBMAX * PITCH * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        RLDM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
+    static rldm::DynLdsLimit lds_limit;
+    RLDM_HIP_CHECK(lds_limit.ensure(reinterpret_cast<const void*>(kern), lds));
     kern<<<dim3(ny, nx), 256, lds, st>>>(hx, hy, inv, inv + nx, bins, symmetric, lambda);
     RLDM_HIP_CHECK(hipGetLastError());
-    RLDM_HIP_CHECK(hipFreeAsync(inv, st));
     return 0;
 }
 
@@ -325,10 +312,11 @@ int rldm_hist_mmd(const uint32_t* hx, int nx, const uint32_t* hy, int ny, int bi
     RLDM_REQUIRE(sigma > 0.f, "sigma must be positive");
     hipStream_t st = (hipStream_t)stream;
     const size_t nmax = (size_t)std::max(nx, ny) * std::max(nx, ny);
-    float* lam = nullptr;
-    double* part = nullptr;
-    RLDM_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&lam), nmax * sizeof(float), st));
-    RLDM_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&part), 6 * sizeof(double), st));
+    DevBuf lbuf(st), pbuf(st);
+    RLDM_HIP_CHECK(lbuf.alloc(nmax * sizeof(float)));
+    RLDM_HIP_CHECK(pbuf.alloc(6 * sizeof(double)));
+    float* lam = lbuf.as<float>();
+    double* part = pbuf.as<double>();
     const double i2s = 1.0 / (2.0 * (double)sigma * (double)sigma);
     int rc = 0;
     rc = rc || rldm_hist_spectral_sq(hx, nx, hx, nx, bins, 1, lam, stream);
@@ -342,8 +330,6 @@ int rldm_hist_mmd(const uint32_t* hx, int nx, const uint32_t* hy, int ny, int bi
         RLDM_HIP_CHECK(hipMemcpyAsync(h, part, sizeof(h), hipMemcpyDeviceToHost, st));
         RLDM_HIP_CHECK(hipStreamSynchronize(st));
     }
-    (void)hipFreeAsync(lam, st);
-    (void)hipFreeAsync(part, st);
     if (rc) return 1;
     out4[0] = h[0];                                   // s1    = mean k(x, x')
     out4[1] = h[2];                                   // s2    = mean k(y, y')

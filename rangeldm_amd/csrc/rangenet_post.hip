@@ -14,20 +14,14 @@
 // Clouds come as a ragged batch: points [sum N][stride] fp32 (x, y, z, remission if stride >= 4) and offsets [B + 1] on the
 // device.  No entry point reads the offsets on the host: the grids are fixed (blockIdx.y is the cloud, the threads of a row
 // stride over its points), nothing is allocated and nothing synchronises.
-#include "common.h"
+#include "eval_common.h"
 #include "../../include/rangeldm_hip.h"
 
 #include <cmath>
 
-#pragma clang fp contract(off)
+#pragma clang fp contract(off)      // (+ -ffp-contract=off in the Makefile) what eval_common.h's f_* operators need
 
 namespace {
-
-__device__ inline float f_mul(float a, float b) { return a * b; }
-__device__ inline float f_add(float a, float b) { return a + b; }
-__device__ inline float f_sub(float a, float b) { return a - b; }
-__device__ inline float f_div(float a, float b) { return a / b; }
-__device__ inline float f_sqrt(float a) { return sqrtf(a); }
 
 typedef unsigned long long u64;
 

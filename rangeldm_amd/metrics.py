@@ -660,18 +660,26 @@ def feature_scan_host(a, b, k=None, radius_sq_a=None, radius_sq_b=None, poly=Fal
     _scan_shapes(a.shape, b.shape, k, None if ra is None else ra.shape, None if rb is None else rb.shape, row_offset)
     g = a @ b.T
     s_a, s_b = np.einsum("ij,ij->i", a, a), np.einsum("ij,ij->i", b, b)
+    return _scan_fold_host(g, s_a, s_b, a.shape[1], k, ra, rb, poly, exclude_diagonal, row_offset)
+
+
+def _scan_fold_host(g, s_a, s_b, d, k, ra, rb, poly, exclude_diagonal, row_offset):
+    """The fold of feature_scan_host over given products g (n_a, n_b) and row norms s_a, s_b of d-term rows: everything
+    after the dot products.  On gram_f64's own values it is what feature_scan returns, bit for bit."""
+    import numpy as np
+    n_a, n_b = g.shape
     d2 = np.maximum(0.0, (s_a[:, None] + s_b[None, :]) - 2.0 * g)
     poly_sum = None
     if poly:
-        t = g / float(a.shape[1]) + 1.0
+        t = g / float(d) + 1.0
         kappa = t * t * t
         if exclude_diagonal:
-            rows = np.arange(a.shape[0]) + int(row_offset)
-            inside = rows < b.shape[0]
+            rows = np.arange(n_a) + int(row_offset)
+            inside = rows < n_b
             kappa[np.nonzero(inside)[0], rows[inside]] = 0.0             # x + 0.0 is x: the same as skipping it
-        chunk = feature_scan_column_chunk(b.shape[0])
-        poly_sum = np.zeros(a.shape[0])
-        for c0 in range(0, b.shape[0], chunk):
+        chunk = feature_scan_column_chunk(n_b)
+        poly_sum = np.zeros(n_a)
+        for c0 in range(0, n_b, chunk):
             poly_sum = poly_sum + np.cumsum(kappa[:, c0:c0 + chunk], axis=1)[:, -1]
     return FeatureScan(kmin_sq=np.sort(d2, axis=1)[:, :k + 1] if k is not None else None,
                        count_a=(d2 < ra[:, None]).sum(1).astype(np.int32) if ra is not None else None,

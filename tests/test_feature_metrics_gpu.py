@@ -238,6 +238,30 @@ def test_real_valued_kernel_sums_against_the_numpy_statement(i):
     assert worst <= 1.0
 
 
+@pytest.mark.parametrize("i", (0, 1, 3), ids=[str(REAL_SHAPES[c]) for c in (0, 1, 3)])
+def test_scan_is_the_fold_of_gram_f64_bit_for_bit(i):
+    """feature_scan's documented promise on real-valued data, where the summation order shows: its g is gram_f64's value and
+    its s the diagonal of gram_f64(x, x), so the numpy fold over those (nothing else in it rounds differently) gives every
+    output bit for bit.  The cases hold a ragged row tile and a ragged column tile, d no multiple of 32 nor of 4, one column
+    chunk (n_b = 63, 64) and three with the merge kernel (n_b = 150)."""
+    real, fake, k = real_case(i)
+    d = real.shape[1]
+    A, B = _dev(real), _dev(fake)
+    g_ab, g_aa, g_bb = (_np(M.gram_f64(p, q)) for p, q in ((A, B), (A, A), (B, B)))
+    s_a, s_b = g_aa.diagonal().copy(), g_bb.diagonal().copy()
+    own_a = M._scan_fold_host(g_aa, s_a, s_a, d, k, None, None, True, True, 0)
+    own_b = M._scan_fold_host(g_bb, s_b, s_b, d, k, None, None, False, False, 0)
+    ra, rb = own_a.kmin_sq[:, k].copy(), own_b.kmin_sq[:, k].copy()
+    want = M._scan_fold_host(g_ab, s_a, s_b, d, k, ra, rb, True, False, 0)
+    got = M.feature_scan(A, B, k=k, radius_sq_a=_dev(ra), radius_sq_b=_dev(rb), poly=True)
+    for name in OUTPUTS:
+        assert np.array_equal(_np(getattr(got, name)), getattr(want, name)), name
+    got = M.feature_scan(A, A, k=k, poly=True, exclude_diagonal=True)
+    assert got.count_a is None and got.count_b is None
+    for name in ("kmin_sq", "min_sq", "poly_sum"):
+        assert np.array_equal(_np(getattr(got, name)), getattr(own_a, name)), name
+
+
 # ---- kernel distance ------------------------------------------------------------------------------------------------------
 def test_kernel_distance_against_the_numpy_statement_and_over_subsets():
     h = _host(0)
