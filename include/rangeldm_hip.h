@@ -331,6 +331,23 @@ int rldm_chamfer_matrix(const float* x, const int32_t* x_offsets, int x_stride, 
  * skips column r of row r; a row left without a column gives +inf / -1.  NaN entries give unspecified results. */
 int rldm_matrix_row_argmin(const double* m, int rows, int cols, int exclude_diag, double* min_out, int32_t* arg_out,
                            void* stream);
+/* ---- voxel occupancy (rangeldm_amd/csrc/voxel.hip) ------------------------------------------------------------------ */
+#define RLDM_VOXEL_RANGE 4               /* return value: a point is out of range (nothing is reported) */
+#define RLDM_VOXEL_MAX_SLOTS (1 << 25)   /* workspace bound: hash slots alive at once (256 MiB of keys + 8 MiB of bitmap) */
+/* Voxel-occupancy counts of a ragged batch of cloud PAIRS, packed and offset exactly as rldm_chamfer_nn takes them (x the
+ * result clouds, y the targets; only xyz read, every cloud non-empty).  With v = voxel as fp32 (positive, finite):
+ *   q(c) = floorf(c / v)       one correctly rounded fp32 division, then floor; fp32 denormals are not flushed
+ *   a point's voxel is (q(x), q(y), q(z));  it is IN RANGE when -2^20 <= q < 2^20 on every axis (NaN / inf are not)
+ *   counts[p] = {a, b, c}:  a = distinct voxels of x_p,  b = distinct voxels of y_p,  c = voxels in both
+ * counts device int32 [num_pairs][3].  The integers do not depend on the order of the points, on the other pairs of the call
+ * or on how the call is chunked, and equal np.unique(np.floor(c / v), axis=0) on the host.  From them, in fp64:
+ *   iou = c / (a + b - c),  precision = c / a,  recall = c / b,  f1 = 2c / (a + b).
+ * A call in which ANY point is out of range reports nothing: counts is cleared and the call returns RLDM_VOXEL_RANGE
+ * (rldm_last_error says why); a later call works normally.  Pairs are processed in chunks whose hash tables (the power of two
+ * >= 2 (n_p + m_p) slots per pair) stay within RLDM_VOXEL_MAX_SLOTS; a single pair that cannot fit (n_p + m_p > 2^24) is an
+ * error (return 1, rldm_last_error names it), as is every other failure.  The call synchronises the stream. */
+int rldm_voxel_counts(const float* x, const int32_t* x_offsets, int x_stride, const float* y, const int32_t* y_offsets,
+                      int y_stride, int num_pairs, float voxel, int32_t* counts, void* stream);
 /* ---- Earth Mover's Distance (rangeldm_amd/csrc/emd.hip) ------------------------------------------------------------ */
 #define RLDM_EMD_RECT 0          /* every cloud of X against every cloud of Y */
 #define RLDM_EMD_SYMMETRIC 1     /* Y is X (the same buffers): j > i computed, mirrored, zero diagonal */

@@ -1,4 +1,4 @@
-// eval_common.h -- what the evaluation files (chamfer, emd, fps, metrics, frechet, feature_metrics, lidar, rangenet_post)
+// eval_common.h -- what the evaluation files (chamfer, voxel, emd, fps, metrics, frechet, feature_metrics, lidar, rangenet_post)
 // share, and nothing else.  No inference or training file includes it.
 #pragma once
 #include "common.h"

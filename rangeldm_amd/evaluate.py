@@ -1,9 +1,9 @@
 """Evaluation on the MI355X: score what the VAE and the conditional sampler reconstruct, and what the sampler generates.
 
-    python -m rangeldm_amd.evaluate vae --weights outputs/RangeLDM --samples 1000 --batch-size 4 [--input DIR]
-    python -m rangeldm_amd.evaluate densification --exp outputs/upsample/generated [--cfg upsample]
-    python -m rangeldm_amd.evaluate inpainting --exp outputs/inpainting/generated [--cfg inpainting]
-    python -m rangeldm_amd.evaluate chamfer A_DIR B_DIR
+    python -m rangeldm_amd.evaluate vae --weights outputs/RangeLDM --samples 1000 --batch-size 4 [--input DIR] [--voxel 0.1]
+    python -m rangeldm_amd.evaluate densification --exp outputs/upsample/generated [--cfg upsample] [--voxel 0.1]
+    python -m rangeldm_amd.evaluate inpainting --exp outputs/inpainting/generated [--cfg inpainting] [--voxel 0.1]
+    python -m rangeldm_amd.evaluate chamfer A_DIR B_DIR [--voxel 0.1]
     python -m rangeldm_amd.evaluate generation GEN_DIR REF_DIR [--points 2048] [--limit N] [--seed 0] [--max-depth M]
                                                [--sampling {random,fps}] [--emd [--emd-eps 0.0078125]]
     python -m rangeldm_amd.evaluate frd FOLDER1 FOLDER2 [--limit 1100] [--rangenet MODEL_DIR [--projection {host,device}]]
@@ -28,7 +28,16 @@ mean_x min_y |x - y|^2 + mean_y min_x |x - y|^2 over xyz.
                  baselines built from every `rate`-th beam of the target.
   inpainting     mae.py:91-117 (`metric.py --inpainting_mae`): range MAE in metres over the config's masked azimuth span,
                  with the reference's denominator (files x W x H, mae.py:111) and per masked pixel; and CD.
-  chamfer        mean CD over the .bin files of two folders, paired by name.
+  chamfer        mean CD over the .bin files of two folders, paired by name (A_DIR the results, B_DIR the targets).
+  --voxel SIZE   (vae, densification, inpainting, chamfer) adds the voxel-occupancy scores of the up-sampling and completion
+                 tables (Implicit LiDAR Network, TULIP: SIZE 0.1) over the clouds the CD is taken on, through
+                 metrics.voxel_scores (rangeldm_amd/csrc/voxel.hip): both clouds of a pair are quantised to floor(c / SIZE)
+                 in fp32, a / b / c = the distinct voxels of the result / of the target / of both.  The object gains
+                 "voxel": SIZE and "occupancy": the means over pairs of iou = c / (a + b - c), precision = c / a,
+                 recall = c / b, f1 = 2c / (a + b), and the integer totals over pairs voxels_result, voxels_target,
+                 voxels_both (the same for any number of ranks).  Precision is about the result: for `vae` the result is
+                 the reconstruction, for `chamfer` A_DIR; `densification` gives one block per method, like "cd".
+                 Without the flag the object is what it was.
   generation     set-level metrics of a folder of generated .bin clouds against a folder of reference sweeps (Achlioptas et
                  al. 2018; Yang et al. 2019): MMD-CD, COV-CD and 1-NNA-CD (metrics.set_metrics) from the all-pairs Chamfer
                  matrices, every cloud cut to the points closer than --max-depth and sub-sampled to --points
@@ -94,7 +103,7 @@ _RESULT_RE = re.compile(r"^(\d+)_seed_(\d+)\.bin$")
 # ---- host-side helpers (no GPU) ---------------------------------------------------------------------------------------
 def build_parser():
     ap = argparse.ArgumentParser(prog="python -m rangeldm_amd.evaluate",
-                                 description="reconstruction metrics (MAE, PSNR, Chamfer distance) and set-level generation "
+                                 description="reconstruction metrics (MAE, PSNR, Chamfer distance, voxel occupancy) and set-level generation "
                                              "metrics (MMD-CD, COV-CD, 1-NNA-CD) on MI355X")
     sub = ap.add_subparsers(dest="cmd", required=True)
 
@@ -106,17 +115,22 @@ def build_parser():
     v.add_argument("--samples", type=int, default=1000)
     v.add_argument("--batch-size", type=int, default=4)
     v.add_argument("--seed", type=int, default=20240310)
+    voxel_help = ("also report voxel-occupancy IoU / precision / recall / F1 of result against target on a grid of SIZE metres "
+                  "(0.1 in the up-sampling literature)")
 
     for task in ("densification", "inpainting"):
         t = sub.add_parser(task, help=f"{task} results of inference_conditional against their targets")
         t.add_argument("--exp", required=True, help=f"directory holding {task}_result/ and {task}_target/")
         t.add_argument("--cfg", default="upsample" if task == "densification" else "inpainting",
                        help="preset name or reference yaml (rate / masked fraction, sensor)")
+        t.add_argument("--voxel", type=float, default=None, metavar="SIZE", help=voxel_help)
 
     c = sub.add_parser("chamfer", help="mean CD over .bin files of two folders, paired by name")
     c.add_argument("a_dir")
     c.add_argument("b_dir")
     c.add_argument("--columns", type=int, default=4, help="float32 columns per point in the .bin files")
+    for p in (v, c):
+        p.add_argument("--voxel", type=float, default=None, metavar="SIZE", help=voxel_help)
 
     g = sub.add_parser("generation", help="MMD-CD / COV-CD / 1-NNA-CD (+ BEV jsd / mmd) of generated against reference clouds")
     g.add_argument("gen_dir")
@@ -278,6 +292,30 @@ def _chunks(seq, n):
         yield seq[i:i + n]
 
 
+def check_voxel_arg(a):
+    """`--voxel`: refused before a file is read unless it is positive and finite (None: the flag was not given)."""
+    if a.voxel is not None:
+        from .metrics import _voxel_size
+        _voxel_size(a.voxel)
+
+
+def _occupancy_sums(result, target, voxel):
+    """[sum iou, sum precision, sum recall, sum f1, sum a, sum b, sum c] over the pairs of one metrics.voxel_scores call
+    (result clouds against target clouds): what a rank accumulates and _sum_over_ranks reduces."""
+    from .metrics import VOXEL_SCORES, voxel_scores
+    s = voxel_scores(result, target, voxel)
+    return [float(s[k].sum()) for k in VOXEL_SCORES] + [float(v) for v in s["counts"].sum(0).tolist()]
+
+
+def _occupancy_block(tot, n):
+    """The "occupancy" object from the seven sums over all ranks and the number of pairs (the counts are integers below
+    2^53: their fp64 sums are exact and order-free)."""
+    from .metrics import VOXEL_SCORES
+    out = {k: tot[i] / n for i, k in enumerate(VOXEL_SCORES)}
+    out.update(voxels_result=int(tot[4]), voxels_target=int(tot[5]), voxels_both=int(tot[6]))
+    return out
+
+
 # ---- commands ---------------------------------------------------------------------------------------------------------
 def _load_vae(a):
     from .vae import AutoencoderKLHIP
@@ -299,6 +337,7 @@ def cmd_vae(a, rank, world, dev):
     from .inference import sensor_for
     from .inference_conditional import load_batch
     from .metrics import chamfer_pairs, range_errors
+    check_voxel_arg(a)
     vae, origin = _load_vae(a)
     shape = (vae._cfg.in_channels, *vae._cfg.sample_size)
     files = sorted(glob.glob(os.path.join(a.input, "*.npy")))[:a.samples] if a.input else None
@@ -309,6 +348,7 @@ def cmd_vae(a, rank, world, dev):
     std, mean = range_affine(to_range)
     fill = float(to_range.range_fill_value[0])
     sums = [0.0, 0.0, 0.0, 0.0]                          # MAE, PSNR, CD, images
+    occ = [0.0] * 7                                      # --voxel: _occupancy_sums
     n_batches = (total + a.batch_size - 1) // a.batch_size
     for b in range(rank, n_batches, world):              # batch b holds global samples [b * bs, (b + 1) * bs)
         lo, hi = b * a.batch_size, min(total, (b + 1) * a.batch_size)
@@ -329,12 +369,18 @@ def cmd_vae(a, rank, world, dev):
         pin, cin = to_range.filter_points(to_range.to_pc_torch(x), 70.0)
         pout, cout = to_range.filter_points(to_range.to_pc_torch(rec), 70.0)
         cin, cout = cin.cpu().tolist(), cout.cpu().tolist()
-        xm, ym = chamfer_pairs([pin[j, :cin[j], :3] for j in range(len(cin))],
-                               [pout[j, :cout[j], :3] for j in range(len(cout))])
+        clouds_in = [pin[j, :cin[j], :3] for j in range(len(cin))]
+        clouds_out = [pout[j, :cout[j], :3] for j in range(len(cout))]
+        xm, ym = chamfer_pairs(clouds_in, clouds_out)
         sums[2] += float((xm + ym).sum())
         sums[3] += hi - lo
-    mae, psnr, cd, n = _sum_over_ranks(sums, dev)
-    return {"task": "vae", "weights": origin, "samples": int(n), "mae": mae / n, "psnr": psnr / n, "cd": cd / n}
+        if a.voxel is not None:                          # the reconstruction is the result, the input the target
+            occ = [s + t for s, t in zip(occ, _occupancy_sums(clouds_out, clouds_in, a.voxel))]
+    mae, psnr, cd, n, *occ = _sum_over_ranks(sums + occ, dev)      # (occ: zeros without --voxel)
+    result = {"task": "vae", "weights": origin, "samples": int(n), "mae": mae / n, "psnr": psnr / n, "cd": cd / n}
+    if a.voxel is not None:
+        result.update(voxel=a.voxel, occupancy=_occupancy_block(occ, n))
+    return result
 
 
 def _conditional_pairs(a, task):
@@ -344,6 +390,7 @@ def _conditional_pairs(a, task):
 
 def cmd_densification(a, rank, world, dev):
     from .metrics import beam_upsample, chamfer_pairs, range_errors
+    check_voxel_arg(a)
     cfg, sensor = task_sensor(a.cfg)
     if cfg["task"] != "upsample":
         raise ValueError(f"{a.cfg} is not an up-sampling config")
@@ -353,6 +400,7 @@ def cmd_densification(a, rank, world, dev):
     methods = ("ours", "nearest", "bicubic")
     abs_sum = {m: 0.0 for m in methods}
     cd_sum = {m: 0.0 for m in methods}
+    occ = {m: [0.0] * 7 for m in methods}                # --voxel: _occupancy_sums per method
     W, H = sensor.width, sensor.H
     for chunk in _chunks(pairs[rank::world], 32):
         clouds = {m: [] for m in methods}
@@ -376,15 +424,23 @@ def cmd_densification(a, rank, world, dev):
         for m in methods:
             xm, ym = chamfer_pairs(clouds[m], targets)
             cd_sum[m] += float((xm + ym).sum())
-    tot = _sum_over_ranks([abs_sum[m] for m in methods] + [cd_sum[m] for m in methods], dev)
+            if a.voxel is not None:
+                occ[m] = [s + t for s, t in zip(occ[m], _occupancy_sums(clouds[m], targets, a.voxel))]
+    tot = _sum_over_ranks([abs_sum[m] for m in methods] + [cd_sum[m] for m in methods] +
+                          [s for m in methods for s in occ[m]], dev)                # (occ: zeros without --voxel)
     n = len(pairs)
-    return {"task": "densification", "pairs": n, "rate": rate,
-            "mae_m": {m: tot[i] / (n * W * H) for i, m in enumerate(methods)},
-            "cd": {m: tot[3 + i] / n for i, m in enumerate(methods)}}
+    result = {"task": "densification", "pairs": n, "rate": rate,
+              "mae_m": {m: tot[i] / (n * W * H) for i, m in enumerate(methods)},
+              "cd": {m: tot[3 + i] / n for i, m in enumerate(methods)}}
+    if a.voxel is not None:
+        result.update(voxel=a.voxel,
+                      occupancy={m: _occupancy_block(tot[6 + 7 * i:13 + 7 * i], n) for i, m in enumerate(methods)})
+    return result
 
 
 def cmd_inpainting(a, rank, world, dev):
     from .metrics import chamfer_pairs, range_errors
+    check_voxel_arg(a)
     cfg, sensor = task_sensor(a.cfg)
     if cfg["task"] != "inpainting":
         raise ValueError(f"{a.cfg} is not an in-painting config")
@@ -393,6 +449,7 @@ def cmd_inpainting(a, rank, world, dev):
     w0, w1 = masked_window(cfg["fraction"], W)
     pairs = _conditional_pairs(a, "inpainting")
     abs_sum = cd_sum = 0.0
+    occ = [0.0] * 7                                      # --voxel: _occupancy_sums
     for chunk in _chunks(pairs[rank::world], 32):
         res_c, tgt_c = [], []
         for rpath, tpath in chunk:
@@ -404,25 +461,37 @@ def cmd_inpainting(a, rank, world, dev):
             tgt_c.append(tgt[:, :3])
         xm, ym = chamfer_pairs(res_c, tgt_c)
         cd_sum += float((xm + ym).sum())
-    abs_sum, cd_sum = _sum_over_ranks([abs_sum, cd_sum], dev)
+        if a.voxel is not None:
+            occ = [s + t for s, t in zip(occ, _occupancy_sums(res_c, tgt_c, a.voxel))]
+    abs_sum, cd_sum, *occ = _sum_over_ranks([abs_sum, cd_sum] + occ, dev)      # (occ: zeros without --voxel)
     n = len(pairs)
-    return {"task": "inpainting", "pairs": n, "window": [w0, w1],
-            "mae_m": {"reference": abs_sum / (n * W * H),            # mae.py:111: divided by files x W x H (a quirk)
-                      "per_masked_pixel": abs_sum / (n * (w1 - w0) * H)},
-            "cd": cd_sum / n}
+    result = {"task": "inpainting", "pairs": n, "window": [w0, w1],
+              "mae_m": {"reference": abs_sum / (n * W * H),            # mae.py:111: divided by files x W x H (a quirk)
+                        "per_masked_pixel": abs_sum / (n * (w1 - w0) * H)},
+              "cd": cd_sum / n}
+    if a.voxel is not None:
+        result.update(voxel=a.voxel, occupancy=_occupancy_block(occ, n))
+    return result
 
 
 def cmd_chamfer(a, rank, world, dev):
     from .metrics import chamfer_pairs
+    check_voxel_arg(a)
     pairs = pair_by_name(a.a_dir, a.b_dir)
     cd = 0.0
+    occ = [0.0] * 7                                      # --voxel: _occupancy_sums
     for chunk in _chunks(pairs[rank::world], 32):
         xs = [_load_bin(p, a.columns, dev)[:, :3] for p, _ in chunk]
         ys = [_load_bin(q, a.columns, dev)[:, :3] for _, q in chunk]
         xm, ym = chamfer_pairs(xs, ys)
         cd += float((xm + ym).sum())
-    (cd,) = _sum_over_ranks([cd], dev)
-    return {"task": "chamfer", "pairs": len(pairs), "cd": cd / len(pairs)}
+        if a.voxel is not None:                          # A_DIR holds the results, B_DIR the targets
+            occ = [s + t for s, t in zip(occ, _occupancy_sums(xs, ys, a.voxel))]
+    cd, *occ = _sum_over_ranks([cd] + occ, dev)          # (occ: zeros without --voxel)
+    result = {"task": "chamfer", "pairs": len(pairs), "cd": cd / len(pairs)}
+    if a.voxel is not None:
+        result.update(voxel=a.voxel, occupancy=_occupancy_block(occ, len(pairs)))
+    return result
 
 
 def _sum_matrix_over_ranks(m):

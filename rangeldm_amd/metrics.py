@@ -9,7 +9,11 @@ device tensors in, librangeldm_hip.so (rangeldm_amd/csrc/metrics.hip) underneath
 Reconstruction metrics (rangeldm_amd/csrc/chamfer.hip): chamfer_distance (pytorch3d call shape), nearest_sq_dists,
 range_errors (MAE / PSNR / range MAE sums) and beam_upsample (the nearest / bicubic baselines).
 
-Set-level generation metrics (same file): chamfer_matrix (every cloud of one set against every cloud of another),
+Voxel occupancy (rangeldm_amd/csrc/voxel.hip): voxel_counts, per pair the distinct voxels of the result, of the target and of
+both on a grid of `voxel` metres (a hash set per pair, filled with atomics alone), and voxel_scores, the IoU / precision /
+recall / F1 of those integers; voxel_counts_host / voxel_scores_host are the numpy statements the device equals exactly.
+
+Set-level generation metrics (chamfer.hip): chamfer_matrix (every cloud of one set against every cloud of another),
 row_argmin (lowest index wins a tie) and generation_metrics (MMD-CD, COV-CD, 1-NNA-CD of Achlioptas et al. 2018 /
 Yang et al. 2019); set_metrics_host is the numpy statement of the three reductions.
 
@@ -218,6 +222,126 @@ def chamfer_distance(x, y, x_lengths=None, y_lengths=None, point_reduction="mean
     if batch_reduction is None:
         return per_pair, None
     return (per_pair.sum() if batch_reduction == "sum" else per_pair.mean()), None
+
+
+# ---- voxel occupancy: IoU / precision / recall / F1 of the occupied voxels (rangeldm_amd/csrc/voxel.hip) ------------------
+VOXEL_HALF_RANGE = 1 << 20      # a voxel index q must satisfy -2^20 <= q < 2^20 on every axis
+VOXEL_SCORES = ("iou", "precision", "recall", "f1")
+
+
+def _voxel_size(voxel):
+    """`voxel` as a float; ValueError unless it is positive and finite as an fp32 number (the kernel divides by float32(voxel))."""
+    import math
+    import numpy as np
+    try:
+        v = float(voxel)
+    except (TypeError, ValueError):
+        raise ValueError(f"voxel must be a positive, finite number, got {voxel!r}") from None
+    with np.errstate(over="ignore"):
+        v32 = float(np.float32(v)) if math.isfinite(v) else v
+    if not (v32 > 0.0 and math.isfinite(v32)):
+        raise ValueError(f"voxel must be positive and finite (as fp32), got {voxel!r}")
+    return v
+
+
+def _voxel_ratios(a, b, c):
+    """The four scores from fp64 arrays / tensors of the counts (integers below 2^53: exact), one IEEE division each."""
+    return {"iou": c / (a + b - c), "precision": c / a, "recall": c / b, "f1": 2.0 * c / (a + b)}
+
+
+def voxel_counts(x, y, voxel=0.1, x_lengths=None, y_lengths=None):
+    """Voxel-occupancy counts of result clouds x against their targets y: an int64 device tensor (N, 3), row p =
+    (a, b, c) = (distinct voxels of x_p, distinct voxels of y_p, voxels in both).  Inputs as chamfer_pairs takes them (padded
+    (N, P, >= 3) tensors with optional lengths, or lists of (n_i, >= 3) device tensors; only xyz is read).
+
+        v = float32(voxel);  q(c) = floor(c / v), one correctly rounded fp32 division, then floor (fp32 denormals kept:
+        floor(-1e-40 / 0.1) is -1);  a point's voxel is (q(x), q(y), q(z))
+
+    A point is in range when its coordinates are finite and -2^20 <= q < 2^20 on every axis; a call holding ANY point out of
+    range raises ValueError and reports nothing (the next call works normally).  The counts are integers: they do not depend
+    on the order of the points or of the pairs, on the other pairs of the call, or on the kernel's chunking, and they equal
+    voxel_counts_host exactly.  Argument errors (an empty cloud, mismatched pair counts, voxel <= 0 or non-finite) are
+    ValueErrors raised before the device is touched."""
+    v = _voxel_size(voxel)
+    xs, ys = _clouds(x, x_lengths, "x"), _clouds(y, y_lengths, "y")
+    if len(xs) != len(ys):
+        raise ValueError(f"{len(xs)} x clouds against {len(ys)} y clouds")
+    _lib.require_gpu()
+    xp, xo, xk = _pack(xs)
+    yp, yo, yk = _pack(ys)
+    counts = torch.empty((len(xs), 3), dtype=torch.int32, device=xp.device)
+    L = _lib.lib()
+    rc = L.rldm_voxel_counts(xp.data_ptr(), xo.data_ptr(), xk, yp.data_ptr(), yo.data_ptr(), yk, len(xs), v,
+                             counts.data_ptr(), _lib.stream_ptr(xp.device))
+    if rc == _lib.RLDM_VOXEL_RANGE:
+        msg = L.rldm_last_error()
+        raise ValueError(f"rldm_voxel_counts: {msg.decode() if msg else 'a point is out of range'}")
+    _lib.check(rc, "rldm_voxel_counts")
+    return counts.long()
+
+
+def voxel_scores(x, y, voxel=0.1, x_lengths=None, y_lengths=None):
+    """Occupancy scores of result clouds x against their targets y on a grid of `voxel` metres (0.1: Implicit LiDAR Network,
+    TULIP and the tables after them).  A dict of fp64 device tensors (N,) and the counts of voxel_counts (int64 (N, 3)):
+
+        iou = c / (a + b - c)      precision = c / a      recall = c / b      f1 = 2c / (a + b)
+
+    each one fp64 division of the integers.  Precision is about the result x (how much of it is geometry the target has),
+    recall about the target y (how much of it was hit at all).  Arguments and errors as voxel_counts."""
+    counts = voxel_counts(x, y, voxel, x_lengths, y_lengths)
+    f = counts.double()
+    return {**_voxel_ratios(f[:, 0], f[:, 1], f[:, 2]), "counts": counts}
+
+
+def _voxel_host_clouds(x, name):
+    import numpy as np
+    if (torch.is_tensor(x) or isinstance(x, np.ndarray)) and x.ndim == 2:
+        x = [x]                                          # one cloud: one pair
+    clouds = [np.asarray(c) for c in x]
+    if not clouds:
+        raise ValueError(f"{name}: no point clouds")
+    for c in clouds:
+        if c.ndim != 2 or c.shape[1] < 3:
+            raise ValueError(f"every cloud of {name} must be (n, >= 3)")
+        if c.shape[0] == 0:
+            raise ValueError(f"{name} holds an empty point cloud")
+    return clouds
+
+
+def _voxel_keys_host(cloud, v32):
+    """The distinct voxels of one cloud, each packed into one int64 (sorted): np.unique(axis=0) of floor(c / v)."""
+    import numpy as np
+    with np.errstate(all="ignore"):
+        q = np.floor(cloud[:, :3].astype(np.float32) / v32)
+    if not ((q >= -VOXEL_HALF_RANGE) & (q < VOXEL_HALF_RANGE)).all():        # (NaN fails both comparisons)
+        raise ValueError(f"a point is out of range: a coordinate is NaN or inf, or floor(c / voxel) lies outside "
+                         f"[-2^20, 2^20)")
+    rows = np.unique(q.astype(np.int64), axis=0) + VOXEL_HALF_RANGE
+    return rows[:, 0] | rows[:, 1] << 21 | rows[:, 2] << 42
+
+
+def voxel_counts_host(x, y, voxel=0.1):
+    """The numpy statement of voxel_counts: lists of (n_i, >= 3) arrays (or one array per side: one pair) -> int64 (N, 3).
+    Per cloud `np.floor(c.astype(np.float32) / np.float32(voxel))`, np.unique(axis=0), and per pair the intersection of the
+    two sets.  Raises the ValueErrors of voxel_counts, the one for a point out of range included."""
+    import numpy as np
+    v32 = np.float32(_voxel_size(voxel))
+    xs, ys = _voxel_host_clouds(x, "x"), _voxel_host_clouds(y, "y")
+    if len(xs) != len(ys):
+        raise ValueError(f"{len(xs)} x clouds against {len(ys)} y clouds")
+    out = np.empty((len(xs), 3), np.int64)
+    for p, (cx, cy) in enumerate(zip(xs, ys)):
+        kx, ky = _voxel_keys_host(cx, v32), _voxel_keys_host(cy, v32)
+        out[p] = (len(kx), len(ky), len(np.intersect1d(kx, ky, assume_unique=True)))
+    return out
+
+
+def voxel_scores_host(x, y, voxel=0.1):
+    """The numpy statement of voxel_scores: fp64 arrays iou, precision, recall, f1 (N,) and the int64 counts (N, 3)."""
+    import numpy as np
+    counts = voxel_counts_host(x, y, voxel)
+    f = counts.astype(np.float64)
+    return {**_voxel_ratios(f[:, 0], f[:, 1], f[:, 2]), "counts": counts}
 
 
 # ---- set-level generation metrics: all-pairs Chamfer matrix, MMD-CD / COV-CD / 1-NNA-CD -------------------------------
