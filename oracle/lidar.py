@@ -54,22 +54,23 @@ class LidarOracle:
         return (a * F(2.) * F(np.pi) - F(np.pi)).astype(F)
 
     # ---- f1: points -> BEV volume (ldm/dataset.py:280-294 + 13-132) -------------------------------------------
-    def to_voxel(self, img, pc=None):
-        """pc: optionally the (B, N, 4) cloud to splat (lets the splat be pinned separately from to_pc's cos / sin)."""
-        pc = self.to_pc(img) if pc is None else np.asarray(pc, F)
-        B = pc.shape[0]
-        D, GH, GW = self.grid_sizes
+    def grid_coords(self, pc):
+        """(B, N, 3) fp32 grid coordinates (x, y, z) of the points: cell `floor` and its +1 neighbours get the votes."""
+        pc = np.asarray(pc, F)
         lo, hi = self.pc_range[:3], self.pc_range[3:]
         p = (pc[:, :, :3] - (hi + lo) / F(2)) / ((hi - lo) / F(2))
-        feat = pc[:, :, 3].astype(np.float64)
-        g_xyz = np.array([GW, GH, D], F)
-        pi = ((p + F(1)) * F(0.5)) * (g_xyz - F(1))
+        D, GH, GW = self.grid_sizes
+        return ((p + F(1)) * F(0.5)) * (np.array([GW, GH, D], F) - F(1))
+
+    def votes(self, pc):
+        """The 8 trilinear votes of every point, corner order (dx, dy, dz) = 000, 001, ..., 111: flat cell index
+        (B, N, 8) int64, fp32 weight (B, N, 8) and whether the corner lies inside the volume (B, N, 8) bool."""
+        D, GH, GW = self.grid_sizes
+        pi = self.grid_coords(pc)
         base = np.floor(pi)
         rem = (pi - base).astype(F)
         base = base.astype(np.int64)
-        nvox = D * GH * GW
-        dens = np.zeros((B, nvox), np.float64)
-        vol = np.zeros((B, nvox), np.float64)
+        idx, wgt, inside = [], [], []
         for dx in (0, 1):
             X = base[..., 0] + dx
             wx = (1 - dx) + (2 * dx - 1) * rem[..., 0]
@@ -79,13 +80,26 @@ class LidarOracle:
                 for dz in (0, 1):
                     Z = base[..., 2] + dz
                     wz = (1 - dz) + (2 * dz - 1) * rem[..., 2]
-                    w = (wx * wy * wz).astype(F)
-                    ok = (X >= 0) & (X < GW) & (Y >= 0) & (Y < GH) & (Z >= 0) & (Z < D)
-                    idx = (Z * GH + Y) * GW + X
-                    for b in range(B):
-                        m = ok[b]
-                        np.add.at(dens[b], idx[b][m], w[b][m].astype(np.float64))
-                        np.add.at(vol[b], idx[b][m], w[b][m].astype(np.float64) * feat[b][m])
+                    wgt.append((wx * wy * wz).astype(F))
+                    inside.append((X >= 0) & (X < GW) & (Y >= 0) & (Y < GH) & (Z >= 0) & (Z < D))
+                    idx.append((Z * GH + Y) * GW + X)
+        return np.stack(idx, -1), np.stack(wgt, -1), np.stack(inside, -1)
+
+    def to_voxel(self, img, pc=None):
+        """pc: optionally the (B, N, 4) cloud to splat (lets the splat be pinned separately from to_pc's cos / sin)."""
+        pc = self.to_pc(img) if pc is None else np.asarray(pc, F)
+        B = pc.shape[0]
+        D, GH, GW = self.grid_sizes
+        feat = pc[:, :, 3].astype(np.float64)
+        idx, w, ok = self.votes(pc)
+        nvox = D * GH * GW
+        dens = np.zeros((B, nvox), np.float64)
+        vol = np.zeros((B, nvox), np.float64)
+        for c in range(8):
+            for b in range(B):
+                m = ok[b, :, c]
+                np.add.at(dens[b], idx[b, :, c][m], w[b, :, c][m].astype(np.float64))
+                np.add.at(vol[b], idx[b, :, c][m], w[b, :, c][m].astype(np.float64) * feat[b][m])
         vol = vol / np.maximum(dens, 1e-4)
         if self.normalize_volume_densities:
             dens = np.log(dens + 1)
@@ -107,19 +121,32 @@ class LidarOracle:
     # ---- f3: point cloud -> range image (ldm/dataset.py:159-226) ----------------------------------------------
     def row_inds_nearest_beam(self, pc):
         """ldm/kitti360_range_image.py:51-61: beam whose inclination is closest to the point's elevation."""
+        return np.argmin(self.beam_errors(pc), axis=-1)
+
+    def col_coord(self, pc):
+        """ldm/dataset.py:162-164: the fractional column of every return, fp32 like the reference's expression."""
+        pc = np.asarray(pc, F)
+        azi = np.arctan2(pc[:, 1], pc[:, 0])
+        return self.width - 1.0 + 0.5 - (azi + np.pi) / (2.0 * np.pi) * self.width
+
+    def col_inds(self, pc):
+        """ldm/dataset.py:165-167: rounded half to even, then clamped into [0, width)."""
+        W = self.width
+        col = np.round(self.col_coord(pc)).astype(np.int32)
+        col[col == W] = W - 1
+        col[col < 0] = 0
+        return col
+
+    def beam_errors(self, pc):
+        """(N, H) |incl[h] - elevation of the return seen from beam h|: what row_inds_nearest_beam minimises."""
         xy = np.linalg.norm(pc[:, :2], ord=2, axis=1)
-        err = np.stack([np.abs(self.incl[i] - np.arctan2(self.height[i] - pc[:, 2], xy)) for i in range(self.H)], -1)
-        return np.argmin(err, axis=-1)
+        return np.stack([np.abs(self.incl[i] - np.arctan2(self.height[i] - pc[:, 2], xy)) for i in range(self.H)], -1)
 
     def project(self, pc, row_inds):
         """ldm/dataset.py:159-187 (`__call__`).  pc: (N, >=4) float32; returns (H, width, 2) with -1 where empty."""
         pc = np.array(pc, F, copy=True)
         W = self.width
-        azi = np.arctan2(pc[:, 1], pc[:, 0])
-        col = W - 1.0 + 0.5 - (azi + np.pi) / (2.0 * np.pi) * W
-        col = np.round(col).astype(np.int32)
-        col[col == W] = W - 1
-        col[col < 0] = 0
+        col = self.col_inds(pc)
         out = np.full((self.H, W, 2), -1, dtype=F)
         pc[:, 2] -= self.height[row_inds]
         rng = np.linalg.norm(pc[:, :3], axis=1, ord=2)

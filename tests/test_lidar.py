@@ -160,7 +160,11 @@ def test_hip_projection_edge_cases():
     # exact range ties: the later return wins (stable farthest-first order)
     tie = np.repeat(pts[:1], 2, 0)
     tie[1, 3] = 0.9
-    assert (t.project(dev(tie))["jpg"][1] == 0.9).sum() >= 1
+    for order in ([0, 1], [1, 0]):
+        raw = o.project(tie[order], o.row_inds_nearest_beam(tie[order]))
+        want = np.transpose(o.normalize(o.process_miss_value(raw)[0]), (2, 1, 0))
+        assert (want[1] == tie[order][1, 3]).sum() >= 1 and (want[1] == tie[order][0, 3]).sum() == 0
+        assert np.array_equal(t.project(dev(tie[order]))["jpg"].cpu().numpy(), want)
 
 
 @pytest.mark.gpu
