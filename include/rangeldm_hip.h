@@ -377,6 +377,8 @@ int rldm_emd_matrix(const float* x, const int32_t* x_offsets, int x_stride, int 
 /* ---- farthest point sampling (rangeldm_amd/csrc/fps.hip) ------------------------------------------------------------- */
 #define RLDM_FPS_BLOCK 1024              /* lanes of the one workgroup a cloud gets: point i belongs to lane i mod 1024 */
 #define RLDM_FPS_RESIDENT_POINTS 65536   /* a cloud's first 64 x 1024 points keep their min-distance in registers */
+#define RLDM_FPS_STAGED_POINTS 12288     /* a cloud's first 12 x 1024 points keep their xyz in LDS; the others are re-read */
+#define RLDM_FPS_GROUP_POINTS 4096       /* the re-read points are taken in groups of 4 x 1024: four per lane in flight */
 #define RLDM_FPS_MAX_POINTS 1048576      /* the largest cloud accepted */
 /* Farthest point sampling of every cloud of a ragged batch packed as rldm_chamfer_matrix takes it (x device fp32
  * [n][stride >= 3], only xyz read; offsets device int32 [num_clouds + 1], starting at 0): k indices per cloud, LOCAL to the

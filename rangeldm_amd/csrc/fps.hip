@@ -52,6 +52,8 @@ constexpr int FPS_LDS_SLOTS = 12;             // slots per lane whose coordinate
 constexpr size_t FPS_LDS_BYTES = (size_t)3 * FPS_LDS_SLOTS * FPS_BLOCK * sizeof(float);
 static_assert(FPS_LDS_SLOTS % FPS_G == 0 && FPS_LDS_SLOTS <= FPS_R, "whole groups are staged");
 static_assert(FPS_RESIDENT == RLDM_FPS_RESIDENT_POINTS, "the header states the resident tier");
+static_assert(FPS_LDS_SLOTS * FPS_BLOCK == RLDM_FPS_STAGED_POINTS, "the header states the staged (LDS) tier");
+static_assert(FPS_G * FPS_BLOCK == RLDM_FPS_GROUP_POINTS, "the header states the group");
 static_assert(FPS_WAVES == 16, "the workgroup level reads one slot per lane & 15");
 
 typedef float f2 __attribute__((ext_vector_type(2)));

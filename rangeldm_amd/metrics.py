@@ -44,6 +44,8 @@ EMD_EPS = 2.0 ** -7         # metres: the auction's final epsilon (the value is 
 EMD_MAX_POINTS = 2048       # RLDM_EMD_MAX_POINTS
 FPS_BLOCK = 1024            # RLDM_FPS_BLOCK: lanes of the workgroup a cloud gets in farthest_point_sample
 FPS_RESIDENT_POINTS = 65536     # RLDM_FPS_RESIDENT_POINTS: a cloud's first points, min-distance in registers
+FPS_STAGED_POINTS = 12288   # RLDM_FPS_STAGED_POINTS: a cloud's first points, xyz staged in LDS (the others are re-read)
+FPS_GROUP_POINTS = 4096     # RLDM_FPS_GROUP_POINTS: the re-read points go in groups of this many, four per lane
 FPS_MAX_POINTS = 1048576    # RLDM_FPS_MAX_POINTS: the largest cloud farthest_point_sample takes
 
 

@@ -2,7 +2,8 @@
 emd_pairs / generation_metrics(emd=True); `evaluate generation --emd`).
 
 The kernel is compared BIT FOR BIT -- assignment, prices, bid count, value -- with tests/test_emd_host.py's sequential numpy
-restatement `auction_host`, and its own output is put through the same certificate against
+restatement `auction_host` on emd_cases() -- every instance K of the kernel at its first size, one short of full and full,
+ties on full rings -- and its own output is put through the same certificate against
 scipy.optimize.linear_sum_assignment (check_certificate: permutation, 0 <= emd - opt <= slack, slack <= eps + roundings,
 bids <= cap / 8), which would hold even if the restatement were wrong.  Then the properties the drivers rely on: an entry
 depends on its two clouds and eps alone (strides, symmetric against rectangular, row blocks, two calls, the pair form), the
@@ -46,6 +47,27 @@ def test_kernel_equals_auction_host_bit_for_bit_and_is_certified(case):
     assert np.array_equal(price.view(np.int32), h_price.view(np.int32))          # bit patterns
     assert emd == h_emd
     assert emd == fixed_order_mean(cost_matrix(x, y)[np.arange(len(x)), h_asg])
+
+
+@pytest.mark.parametrize("n", (100, 1100))              # K = 2 and K = 24: the grid-index decoding had only run with K = 4
+def test_every_matrix_entry_equals_the_single_pair_call(n):
+    xs, ys = _small_set(51 + n, 3, n), _small_set(52 + n, 2, n)
+    dx, dy = _dev(xs), _dev(ys)
+    pair = lambda a, b: [t[0, 0] for t in M.emd_matrix([a], [b], eps=EPS, return_assignment=True)]
+    same = lambda got, want: all(torch.equal(g, w) for g, w in zip(got, want))       # value, assignment, prices, bids
+    rect = M.emd_matrix(dx, dy, eps=EPS, return_assignment=True)
+    assert tuple(rect[0].shape) == (3, 2) and tuple(rect[1].shape) == (3, 2, n)
+    for i in range(3):
+        for j in range(2):
+            assert same([t[i, j] for t in rect], pair(dx[i], dy[j])), (i, j)
+    emd, asg, price, bids = M.emd_matrix(dx, eps=EPS, return_assignment=True)        # the symmetric route
+    for i in range(3):
+        assert emd[i, i] == 0 and bids[i, i] == 0
+        for j in range(i + 1, 3):
+            want = pair(dx[i], dx[j])
+            assert same([emd[i, j], asg[i, j], price[i, j], bids[i, j]], want), (i, j)
+            assert emd[j, i] == want[0] and bids[j, i] == want[3] and emd[i, j] > 0  # the mirror entry
+            assert torch.all(asg[j, i] == -1)
 
 
 def test_strides_3_4_5():

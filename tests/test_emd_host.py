@@ -39,6 +39,7 @@ EPS = 2.0 ** -7
 BID_CAP = 1024                   # bids per point at which a pair is given up
 SLACK_ROUNDINGS = 3.0            # in units of 2^-23 (max c + max p): derived above
 F = np.float32
+EMD_INSTANCES = (1, 2, 4, 8, 16, 24, 32)     # objects per lane of emd_auction_kernel<K>: emd.hip's EMD_LAUNCH(K), held below
 
 
 # ---- the restatement ------------------------------------------------------------------------------------------------------
@@ -116,10 +117,21 @@ def lidar_like(rng, n):
     return np.stack([r * np.cos(el) * np.cos(az), r * np.cos(el) * np.sin(az), r * np.sin(el)], 1).astype(F)
 
 
+def instance_sizes():
+    """For every instance K: its first size 64 K_prev + 1 (nearly half the lanes' last slot is a pad; 3 for K = 1), 64 K - 1
+    (one pad) and 64 K (none: the ring starts full)."""
+    sizes, prev = [], None
+    for k in EMD_INSTANCES:
+        sizes += [3 if prev is None else 64 * prev + 1, 64 * k - 1, 64 * k]
+        prev = k
+    return sizes
+
+
 def emd_cases():
     """[(name, x, y)]: the inputs the restatement and the kernel are both checked on."""
     rng = np.random.default_rng(20240917)
-    cases = [(f"lidar_{n}", lidar_like(rng, n), lidar_like(rng, n)) for n in (1, 2, 777, 2048)]
+    first = (1, 2, 777, 2048)
+    cases = [(f"lidar_{n}", lidar_like(rng, n), lidar_like(rng, n)) for n in first]
     base = lidar_like(rng, 500)
     cases.append(("permutation_of_itself", base, base[rng.permutation(500)]))
     cases.append(("grid_8", rng.integers(-8, 9, (600, 3)).astype(F), rng.integers(-8, 9, (600, 3)).astype(F)))
@@ -129,6 +141,14 @@ def emd_cases():
     # two tight clusters 60 m apart, 200 + 56 points on one side and 56 + 200 on the other: 144 points must cross
     cases.append(("two_clusters", np.concatenate([blob(0.0, 200), blob(60.0, 56)]),
                   np.concatenate([blob(0.0, 56), blob(60.0, 200)])))
+    # every instance of the kernel at its first size, one short of full and full (a generator of their own: the cases above
+    # stay what they were); then ties on the instances K = 2 and K = 24 and on full rings
+    rng = np.random.default_rng(20250720)
+    cases += [(f"lidar_{n}", lidar_like(rng, n), lidar_like(rng, n)) for n in instance_sizes() if n not in first]
+    grid = lambda r, n: rng.integers(-r, r + 1, (n, 3)).astype(F)
+    cases += [(f"grid_2_{n}", grid(2, n), grid(2, n)) for n in (100, 128, 1100, 1536)]
+    cases += [(f"grid_8_{n}", grid(8, n), grid(8, n)) for n in (64, 1100)]
+    cases += [(f"all_identical_{n}", np.full((n, 3), 1.5, F), np.full((n, 3), 1.5, F)) for n in (64, 128, 1536)]
     return cases
 
 
@@ -162,6 +182,19 @@ def test_auction_host_is_certified_against_linear_sum_assignment(case):
     assign, prices, bids, emd = auction_host(x, y, EPS)
     assert assign.dtype == np.int32 and prices.dtype == np.float32
     check_certificate(name, x, y, assign, prices, bids, emd)
+
+
+def test_the_instances_are_the_ones_emd_hip_launches():
+    # the sizes of emd_cases() follow EMD_INSTANCES; an instance added to or taken from emd.hip fails here until it follows
+    import re
+    text = open(os.path.join(ROOT, "rangeldm_amd", "csrc", "emd.hip")).read()
+    launched = tuple(int(k) for k in re.findall(r"EMD_LAUNCH\((\d+)\)", text))
+    assert launched == EMD_INSTANCES and EMD_INSTANCES[-1] * 64 == M.EMD_MAX_POINTS
+    assert instance_sizes() == [3, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 1535, 1536, 1537,
+                                2047, 2048]
+    sizes = {len(x) for _, x, _ in emd_cases()}
+    assert set(instance_sizes()) <= sizes and {100, 1100} <= sizes
+    assert len({name for name, _, _ in emd_cases()}) == len(emd_cases())
 
 
 def test_auction_host_known_answers():

@@ -11,7 +11,8 @@ The rule.  All fp32, one rounding per operation (numpy does not contract):
 
 The certificate.  With D the full fp32 matrix of the same expression, idx[t] (t >= 1) must be the lowest index attaining
 max over the unselected i of min_{s < t} D[idx[s]][i], and the indices must be distinct.  It is evaluated from D with
-boolean masks: no running array, no sentinel, no argmax.
+boolean masks: no running array, no sentinel, no argmax.  It only ever reads the rows D[idx[s]], so it has a second form
+(check_certificate_rows) that computes those k rows alone, by the same expression: k x P work, for clouds of scan size.
 """
 import numpy as np
 import pytest
@@ -50,21 +51,41 @@ def pairwise_sq(x):
     return (dx * dx + dy * dy) + dz * dz
 
 
-def check_certificate(name, x, idx, start, d=None):
-    """The assertions of the module docstring on any index list claimed for the cloud x."""
+def selected_rows(x, idx):
+    """The rows D[idx[t]] of pairwise_sq(x) alone, fp32 [len(idx)][P], by the same expression: k x P work, not P x P."""
+    x = np.ascontiguousarray(np.asarray(x)[:, :3], F)
+    s = x[np.asarray(idx, np.int64)]
+    dx = x[None, :, 0] - s[:, None, 0]
+    dy = x[None, :, 1] - s[:, None, 1]
+    dz = x[None, :, 2] - s[:, None, 2]
+    return (dx * dx + dy * dy) + dz * dz
+
+
+def _check_rounds(name, p, idx, start, rows):
+    """The assertions of the module docstring; rows(idx) gives D[idx] and is only asked once idx is known to be in range."""
     idx = [int(v) for v in idx]
-    p = len(x)
-    d = pairwise_sq(x) if d is None else d
     assert idx[0] == start, f"{name}: starts at {idx[0]}, not {start}"
     assert all(0 <= v < p for v in idx), f"{name}: index out of range"
     assert len(set(idx)) == len(idx), f"{name}: an index is selected twice"
+    r = rows(idx)
     for t in range(1, len(idx)):
         free = np.ones(p, bool)
         free[idx[:t]] = False
-        nearest = d[idx[:t]].min(0)                      # min over the selected s of D[s][i]
+        nearest = r[:t].min(0)                           # min over the selected s of D[s][i]
         top = nearest[free].max()
         want = int(np.flatnonzero(free & (nearest == top))[0])
         assert idx[t] == want, f"{name}: round {t} selected {idx[t]}, the lowest farthest index is {want}"
+
+
+def check_certificate(name, x, idx, start, d=None):
+    """The certificate on any index list claimed for the cloud x, from the full matrix D (computed here unless given)."""
+    d = pairwise_sq(x) if d is None else d
+    _check_rounds(name, len(x), idx, start, lambda sel: d[sel])
+
+
+def check_certificate_rows(name, x, idx, start):
+    """The same certificate from the len(idx) rows of D it reads, computed on their own: for clouds whose D does not fit."""
+    _check_rounds(name, len(x), idx, start, lambda sel: selected_rows(x, sel))
 
 
 # ---- inputs -----------------------------------------------------------------------------------------------------------------
@@ -107,14 +128,27 @@ def test_fps_host_passes_the_certificate(kind):
 def test_the_certificate_refuses_wrong_answers():
     x = lidar_like(np.random.default_rng(3), 50)
     good = fps_host(x, 10, 4)
-    check_certificate("good", x, good, 4)
-    for bad in (good[[0, 2, 1] + list(range(3, 10))], np.concatenate([good[:9], good[:1]])):
-        with pytest.raises(AssertionError):
-            check_certificate("bad", x, bad, 4)
-    # the tie rule is part of it: on a cloud of identical points any order is "farthest", only one is the lowest index
     same = np.ones((6, 3), F)
+    assert np.array_equal(selected_rows(x, good).view(np.int32), pairwise_sq(x)[good].view(np.int32))      # the same rows, bit for bit
+    for check in (check_certificate, check_certificate_rows):
+        check("good", x, good, 4)
+        for bad in (good[[0, 2, 1] + list(range(3, 10))], np.concatenate([good[:9], good[:1]])):
+            with pytest.raises(AssertionError):
+                check("bad", x, bad, 4)
+        # the tie rule is part of it: on a cloud of identical points any order is "farthest", only one is the lowest index
+        with pytest.raises(AssertionError):
+            check("tie", same, [2, 1, 0], 2)
+        check("tie", same, [2, 0, 1], 2)
+    # what the full form cannot see for lack of memory, the row form refuses as well: a wrong start, an index outside the
+    # cloud (before any row is formed from it), a later round's lower-index tie
+    for bad, start in ((good, 5), ([4, 50], 4), ([4, -1], 4)):
+        with pytest.raises(AssertionError):
+            check_certificate_rows("bad", x, bad, start)
+    far = np.zeros((40, 3), F)
+    far[[7, 31], 0] = 3.0                                # two points equally far from the rest: 7 is the answer, 31 is not
+    check_certificate_rows("tie", far, [0, 7], 0)
     with pytest.raises(AssertionError):
-        check_certificate("tie", same, [2, 1, 0], 2)
+        check_certificate_rows("tie", far, [0, 31], 0)
 
 
 def test_known_answers():
@@ -164,6 +198,11 @@ def test_constants_mirror_the_header():
     assert M.FPS_RESIDENT_POINTS == value("RLDM_FPS_RESIDENT_POINTS")
     assert M.FPS_MAX_POINTS == value("RLDM_FPS_MAX_POINTS") >= 262144
     assert M.FPS_RESIDENT_POINTS % M.FPS_BLOCK == 0 and M.FPS_RESIDENT_POINTS >= 65536
+    assert M.FPS_STAGED_POINTS == value("RLDM_FPS_STAGED_POINTS")
+    assert M.FPS_GROUP_POINTS == value("RLDM_FPS_GROUP_POINTS")
+    # whole groups of whole slots are staged, and the resident tier is whole groups: the sizes the GPU tests derive hold
+    assert M.FPS_GROUP_POINTS % M.FPS_BLOCK == 0 and M.FPS_STAGED_POINTS % M.FPS_GROUP_POINTS == 0
+    assert M.FPS_STAGED_POINTS < M.FPS_RESIDENT_POINTS and M.FPS_RESIDENT_POINTS % M.FPS_GROUP_POINTS == 0
 
 
 def test_refusals_come_before_the_device():
