@@ -311,6 +311,20 @@ int rldm_chamfer_nn(const float* x, const int32_t* x_offsets, int x_stride, cons
  * a fixed-order reduction (bit-identical run to run).  CD of pair p = x_mean[p] + y_mean[p]. */
 int rldm_chamfer_mean(const float* x_nn_d2, const int32_t* x_offsets, const float* y_nn_d2, const int32_t* y_offsets,
                       int num_pairs, double* x_mean, double* y_mean, void* stream);
+/* Nearest neighbour WITH ITS INDEX (rangeldm_amd/csrc/nn_index.hip): pairs packed exactly as rldm_chamfer_nn takes them, same
+ * preconditions.  For pair p with clouds X_p (n_p points) and Y_p (m_p points):
+ *   x_nn_d2[i]   min over t in Y_p of ((dx*dx + dy*dy) + dz*dz), uncontracted fp32: the bits rldm_chamfer_nn writes
+ *   x_nn_idx[i]  the LOWEST index j in [0, m_p) (local to Y_p) whose d2 has exactly those bits
+ *   y_nn_d2 / y_nn_idx  the mirror (queries in Y_p, indices local to X_p)
+ *   y_hits[j]    how many points of X_p have x_nn_idx == j;  x_hits[i] the mirror.  int32 counts, integer atomics: exact
+ * d2 device fp32, idx and hits device int32, each laid out like the packed cloud of its name ([x_offsets[num_pairs]] /
+ * [y_offsets[num_pairs]]).  Every value depends on the two clouds of its pair alone: not on the other pairs of the call, not
+ * on how a target cloud is split over workgroups (the parts are merged by a 64-bit atomicMin on d2 bits << 32 | index), not
+ * on the order of tiles.  Non-finite coordinates give unspecified values, with every index still inside its cloud.
+ * The call synchronises the stream. */
+int rldm_nn_index(const float* x, const int32_t* x_offsets, int x_stride, const float* y, const int32_t* y_offsets,
+                  int y_stride, int num_pairs, float* x_nn_d2, int32_t* x_nn_idx, float* y_nn_d2, int32_t* y_nn_idx,
+                  int32_t* x_hits, int32_t* y_hits, void* stream);
 /* All-pairs Chamfer matrix between two ragged SETS of clouds, X (nx clouds) and Y (ny clouds), packed as rldm_chamfer_nn
  * takes them (device fp32 [n][stride >= 3], only xyz read; device int32 offsets [nx + 1] / [ny + 1], starting at 0):
  *   xy[i][j] = mean over points q of X_i of min over points t of Y_j of d2(q, t)

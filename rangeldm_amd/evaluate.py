@@ -1,9 +1,10 @@
 """Evaluation on the MI355X: score what the VAE and the conditional sampler reconstruct, and what the sampler generates.
 
     python -m rangeldm_amd.evaluate vae --weights outputs/RangeLDM --samples 1000 --batch-size 4 [--input DIR] [--voxel 0.1]
-    python -m rangeldm_amd.evaluate densification --exp outputs/upsample/generated [--cfg upsample] [--voxel 0.1]
-    python -m rangeldm_amd.evaluate inpainting --exp outputs/inpainting/generated [--cfg inpainting] [--voxel 0.1]
-    python -m rangeldm_amd.evaluate chamfer A_DIR B_DIR [--voxel 0.1]
+                                        [--match TAU [TAU ...]] [--dcd-alpha A]
+    python -m rangeldm_amd.evaluate densification --exp outputs/upsample/generated [--cfg upsample] [--voxel 0.1] [--match ..] [--dcd-alpha A]
+    python -m rangeldm_amd.evaluate inpainting --exp outputs/inpainting/generated [--cfg inpainting] [--voxel 0.1] [--match ..] [--dcd-alpha A]
+    python -m rangeldm_amd.evaluate chamfer A_DIR B_DIR [--voxel 0.1] [--match TAU [TAU ...]] [--dcd-alpha A]
     python -m rangeldm_amd.evaluate generation GEN_DIR REF_DIR [--points 2048] [--limit N] [--seed 0] [--max-depth M]
                                                [--sampling {random,fps}] [--emd [--emd-eps 0.0078125]]
     python -m rangeldm_amd.evaluate frd FOLDER1 FOLDER2 [--limit 1100] [--rangenet MODEL_DIR [--projection {host,device}]]
@@ -38,6 +39,19 @@ mean_x min_y |x - y|^2 + mean_y min_x |x - y|^2 over xyz.
                  voxels_both (the same for any number of ranks).  Precision is about the result: for `vae` the result is
                  the reconstruction, for `chamfer` A_DIR; `densification` gives one block per method, like "cd".
                  Without the flag the object is what it was.
+  --match TAU [TAU ...]   (the same four commands, the same clouds and the same result / target roles as --voxel) adds the
+                 F-score at each distance threshold TAU in metres: "match": {"tau", "precision", "recall", "fscore"}, each a
+                 list with one entry per TAU, the means over pairs of precision = the share of result points within TAU of the
+                 target, recall = the share of target points within TAU of the result, fscore = 2pr / (p + r) (0 when both
+                 are 0); and in the same block the integer totals over pairs matched_result, matched_target (per TAU),
+                 points_result, points_target.  It also adds "hausdorff": {"mean", "max"} over the pairs' symmetric Hausdorff
+                 distances (the worst point of a pair, which the mean CD hides).
+  --dcd-alpha A  (the same commands) adds "dcd": {"alpha": A, "mean"}: the density-aware Chamfer distance of
+                 metrics.density_aware_chamfer (squared distance in the exponent, no size-ratio factor), the mean over pairs.
+                 With either flag a batch of pairs goes through ONE nearest-neighbour search, metrics.pair_scores
+                 (rangeldm_amd/csrc/nn_index.hip), and "cd" is taken from that search's distances: they are the bits the plain
+                 search gives and go through the same means, so "cd" is unchanged.  Without the flags the object is what
+                 it was.
   generation     set-level metrics of a folder of generated .bin clouds against a folder of reference sweeps (Achlioptas et
                  al. 2018; Yang et al. 2019): MMD-CD, COV-CD and 1-NNA-CD (metrics.set_metrics) from the all-pairs Chamfer
                  matrices, every cloud cut to the points closer than --max-depth and sub-sampled to --points
@@ -103,7 +117,7 @@ _RESULT_RE = re.compile(r"^(\d+)_seed_(\d+)\.bin$")
 # ---- host-side helpers (no GPU) ---------------------------------------------------------------------------------------
 def build_parser():
     ap = argparse.ArgumentParser(prog="python -m rangeldm_amd.evaluate",
-                                 description="reconstruction metrics (MAE, PSNR, Chamfer distance, voxel occupancy) and set-level generation "
+                                 description="reconstruction metrics (MAE, PSNR, Chamfer distance, voxel occupancy, F-score, Hausdorff, DCD) and set-level generation "
                                              "metrics (MMD-CD, COV-CD, 1-NNA-CD) on MI355X")
     sub = ap.add_subparsers(dest="cmd", required=True)
 
@@ -117,6 +131,9 @@ def build_parser():
     v.add_argument("--seed", type=int, default=20240310)
     voxel_help = ("also report voxel-occupancy IoU / precision / recall / F1 of result against target on a grid of SIZE metres "
                   "(0.1 in the up-sampling literature)")
+    match_help = ("also report precision / recall / F-score of result against target at each distance threshold TAU (metres), "
+                  "and the Hausdorff distance")
+    dcd_help = "also report the density-aware Chamfer distance (Wu et al. 2021) with this alpha (per square metre; no default)"
 
     for task in ("densification", "inpainting"):
         t = sub.add_parser(task, help=f"{task} results of inference_conditional against their targets")
@@ -124,6 +141,8 @@ def build_parser():
         t.add_argument("--cfg", default="upsample" if task == "densification" else "inpainting",
                        help="preset name or reference yaml (rate / masked fraction, sensor)")
         t.add_argument("--voxel", type=float, default=None, metavar="SIZE", help=voxel_help)
+        t.add_argument("--match", type=float, nargs="+", default=None, metavar="TAU", help=match_help)
+        t.add_argument("--dcd-alpha", type=float, default=None, metavar="A", help=dcd_help)
 
     c = sub.add_parser("chamfer", help="mean CD over .bin files of two folders, paired by name")
     c.add_argument("a_dir")
@@ -131,6 +150,8 @@ def build_parser():
     c.add_argument("--columns", type=int, default=4, help="float32 columns per point in the .bin files")
     for p in (v, c):
         p.add_argument("--voxel", type=float, default=None, metavar="SIZE", help=voxel_help)
+        p.add_argument("--match", type=float, nargs="+", default=None, metavar="TAU", help=match_help)
+        p.add_argument("--dcd-alpha", type=float, default=None, metavar="A", help=dcd_help)
 
     g = sub.add_parser("generation", help="MMD-CD / COV-CD / 1-NNA-CD (+ BEV jsd / mmd) of generated against reference clouds")
     g.add_argument("gen_dir")
@@ -316,6 +337,73 @@ def _occupancy_block(tot, n):
     return out
 
 
+def _max_over_ranks(values, device):
+    """Element-wise maximum of a list of floats over the ranks (identity on one process)."""
+    t = torch.tensor(values, dtype=torch.float64, device=device)
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    return t.cpu().tolist()
+
+
+def check_nn_args(a):
+    """`--match` / `--dcd-alpha`: refused before a file is read unless positive and finite (None: the flag was not given)."""
+    from .metrics import _alpha_value, _tau_values
+    if a.match is not None:
+        _tau_values(a.match)
+    if a.dcd_alpha is not None:
+        _alpha_value(a.dcd_alpha)
+
+
+def _nn_wanted(a):
+    return a.match is not None or a.dcd_alpha is not None
+
+
+def _nn_len(a):
+    """Length of _nn_sums' vector: with T thresholds [precision x T, recall x T, fscore x T, matched_result x T,
+    matched_target x T, points_result, points_target, sum of Hausdorff], then [sum of dcd]."""
+    return (5 * len(a.match) + 3 if a.match is not None else 0) + (1 if a.dcd_alpha is not None else 0)
+
+
+def _nn_sums(result, target, a):
+    """(sum of CD, the vector of _nn_len, the largest symmetric Hausdorff distance) over the pairs of ONE
+    metrics.pair_scores call (result clouds against target clouds): what a rank accumulates; the first two are reduced by
+    _sum_over_ranks, the last by _max_over_ranks."""
+    from .metrics import pair_scores
+    s = pair_scores(result, target, taus=a.match, alpha=a.dcd_alpha)
+    sums, worst = [], 0.0
+    if a.match is not None:
+        m, h = s["match"], s["hausdorff"][:, 2]
+        for k in ("precision", "recall", "fscore"):
+            sums += m[k].sum(0).tolist()
+        sums += [float(v) for v in m["counts"].sum(0).t().reshape(-1).tolist()]
+        sums += [float(v) for v in m["points"].sum(0).tolist()] + [float(h.sum())]
+        worst = float(h.max())
+    if a.dcd_alpha is not None:
+        sums.append(float(s["dcd"].sum()))
+    return float(s["cd"].sum()), sums, worst
+
+
+def _nn_blocks(tot, worst, n, a):
+    """The "match" / "hausdorff" / "dcd" objects from _nn_sums' vector summed over all ranks, the maximum over all ranks and
+    the number of pairs (the counts are integers below 2^53: their fp64 sums are exact and order-free)."""
+    out = {}
+    if a.match is not None:
+        T = len(a.match)
+        out["match"] = {"tau": list(a.match), **{k: [v / n for v in tot[i * T:(i + 1) * T]]
+                                                 for i, k in enumerate(("precision", "recall", "fscore"))},
+                        "matched_result": [int(v) for v in tot[3 * T:4 * T]], "matched_target": [int(v) for v in tot[4 * T:5 * T]],
+                        "points_result": int(tot[5 * T]), "points_target": int(tot[5 * T + 1])}
+        out["hausdorff"] = {"mean": tot[5 * T + 2] / n, "max": worst}
+    if a.dcd_alpha is not None:
+        out["dcd"] = {"alpha": a.dcd_alpha, "mean": tot[-1] / n}
+    return out
+
+
+def _add(acc, part):
+    return [s + t for s, t in zip(acc, part)]
+
+
 # ---- commands ---------------------------------------------------------------------------------------------------------
 def _load_vae(a):
     from .vae import AutoencoderKLHIP
@@ -338,6 +426,7 @@ def cmd_vae(a, rank, world, dev):
     from .inference_conditional import load_batch
     from .metrics import chamfer_pairs, range_errors
     check_voxel_arg(a)
+    check_nn_args(a)
     vae, origin = _load_vae(a)
     shape = (vae._cfg.in_channels, *vae._cfg.sample_size)
     files = sorted(glob.glob(os.path.join(a.input, "*.npy")))[:a.samples] if a.input else None
@@ -349,6 +438,7 @@ def cmd_vae(a, rank, world, dev):
     fill = float(to_range.range_fill_value[0])
     sums = [0.0, 0.0, 0.0, 0.0]                          # MAE, PSNR, CD, images
     occ = [0.0] * 7                                      # --voxel: _occupancy_sums
+    nn, worst = [0.0] * _nn_len(a), 0.0                  # --match / --dcd-alpha: _nn_sums
     n_batches = (total + a.batch_size - 1) // a.batch_size
     for b in range(rank, n_batches, world):              # batch b holds global samples [b * bs, (b + 1) * bs)
         lo, hi = b * a.batch_size, min(total, (b + 1) * a.batch_size)
@@ -371,15 +461,23 @@ def cmd_vae(a, rank, world, dev):
         cin, cout = cin.cpu().tolist(), cout.cpu().tolist()
         clouds_in = [pin[j, :cin[j], :3] for j in range(len(cin))]
         clouds_out = [pout[j, :cout[j], :3] for j in range(len(cout))]
-        xm, ym = chamfer_pairs(clouds_in, clouds_out)
-        sums[2] += float((xm + ym).sum())
+        if _nn_wanted(a):                                # one search for the CD and the rest; result = reconstruction
+            cd, part, w = _nn_sums(clouds_out, clouds_in, a)
+            sums[2] += cd
+            nn, worst = _add(nn, part), max(worst, w)
+        else:
+            xm, ym = chamfer_pairs(clouds_in, clouds_out)
+            sums[2] += float((xm + ym).sum())
         sums[3] += hi - lo
         if a.voxel is not None:                          # the reconstruction is the result, the input the target
             occ = [s + t for s, t in zip(occ, _occupancy_sums(clouds_out, clouds_in, a.voxel))]
-    mae, psnr, cd, n, *occ = _sum_over_ranks(sums + occ, dev)      # (occ: zeros without --voxel)
+    mae, psnr, cd, n, *rest = _sum_over_ranks(sums + occ + nn, dev)      # (occ: zeros without --voxel)
+    occ, nn = rest[:7], rest[7:]
     result = {"task": "vae", "weights": origin, "samples": int(n), "mae": mae / n, "psnr": psnr / n, "cd": cd / n}
     if a.voxel is not None:
         result.update(voxel=a.voxel, occupancy=_occupancy_block(occ, n))
+    if _nn_wanted(a):
+        result.update(_nn_blocks(nn, _max_over_ranks([worst], dev)[0], n, a))
     return result
 
 
@@ -391,6 +489,7 @@ def _conditional_pairs(a, task):
 def cmd_densification(a, rank, world, dev):
     from .metrics import beam_upsample, chamfer_pairs, range_errors
     check_voxel_arg(a)
+    check_nn_args(a)
     cfg, sensor = task_sensor(a.cfg)
     if cfg["task"] != "upsample":
         raise ValueError(f"{a.cfg} is not an up-sampling config")
@@ -401,6 +500,8 @@ def cmd_densification(a, rank, world, dev):
     abs_sum = {m: 0.0 for m in methods}
     cd_sum = {m: 0.0 for m in methods}
     occ = {m: [0.0] * 7 for m in methods}                # --voxel: _occupancy_sums per method
+    L = _nn_len(a)
+    nn, worst = {m: [0.0] * L for m in methods}, {m: 0.0 for m in methods}      # --match / --dcd-alpha: _nn_sums per method
     W, H = sensor.width, sensor.H
     for chunk in _chunks(pairs[rank::world], 32):
         clouds = {m: [] for m in methods}
@@ -422,12 +523,17 @@ def cmd_densification(a, rank, world, dev):
                 pts, cnt = sensor.filter_points(sensor.to_pc_torch(imgs[m]), lim)
                 clouds[m].append(pts[0, :int(cnt[0]), :3])
         for m in methods:
-            xm, ym = chamfer_pairs(clouds[m], targets)
-            cd_sum[m] += float((xm + ym).sum())
+            if _nn_wanted(a):                            # one search for the CD and the rest
+                cd, part, w = _nn_sums(clouds[m], targets, a)
+                cd_sum[m] += cd
+                nn[m], worst[m] = _add(nn[m], part), max(worst[m], w)
+            else:
+                xm, ym = chamfer_pairs(clouds[m], targets)
+                cd_sum[m] += float((xm + ym).sum())
             if a.voxel is not None:
                 occ[m] = [s + t for s, t in zip(occ[m], _occupancy_sums(clouds[m], targets, a.voxel))]
     tot = _sum_over_ranks([abs_sum[m] for m in methods] + [cd_sum[m] for m in methods] +
-                          [s for m in methods for s in occ[m]], dev)                # (occ: zeros without --voxel)
+                          [s for m in methods for s in occ[m]] + [s for m in methods for s in nn[m]], dev)
     n = len(pairs)
     result = {"task": "densification", "pairs": n, "rate": rate,
               "mae_m": {m: tot[i] / (n * W * H) for i, m in enumerate(methods)},
@@ -435,12 +541,17 @@ def cmd_densification(a, rank, world, dev):
     if a.voxel is not None:
         result.update(voxel=a.voxel,
                       occupancy={m: _occupancy_block(tot[6 + 7 * i:13 + 7 * i], n) for i, m in enumerate(methods)})
+    if _nn_wanted(a):                                    # one block per method, like "cd"
+        worst = _max_over_ranks([worst[m] for m in methods], dev)
+        blocks = [_nn_blocks(tot[27 + L * i:27 + L * (i + 1)], worst[i], n, a) for i in range(len(methods))]
+        result.update({key: {m: blocks[i][key] for i, m in enumerate(methods)} for key in blocks[0]})
     return result
 
 
 def cmd_inpainting(a, rank, world, dev):
     from .metrics import chamfer_pairs, range_errors
     check_voxel_arg(a)
+    check_nn_args(a)
     cfg, sensor = task_sensor(a.cfg)
     if cfg["task"] != "inpainting":
         raise ValueError(f"{a.cfg} is not an in-painting config")
@@ -450,6 +561,7 @@ def cmd_inpainting(a, rank, world, dev):
     pairs = _conditional_pairs(a, "inpainting")
     abs_sum = cd_sum = 0.0
     occ = [0.0] * 7                                      # --voxel: _occupancy_sums
+    nn, worst = [0.0] * _nn_len(a), 0.0                  # --match / --dcd-alpha: _nn_sums
     for chunk in _chunks(pairs[rank::world], 32):
         res_c, tgt_c = [], []
         for rpath, tpath in chunk:
@@ -459,11 +571,17 @@ def cmd_inpainting(a, rank, world, dev):
             abs_sum += float(sa.sum())
             res_c.append(res[:, :3])
             tgt_c.append(tgt[:, :3])
-        xm, ym = chamfer_pairs(res_c, tgt_c)
-        cd_sum += float((xm + ym).sum())
+        if _nn_wanted(a):                                # one search for the CD and the rest
+            cd, part, w = _nn_sums(res_c, tgt_c, a)
+            cd_sum += cd
+            nn, worst = _add(nn, part), max(worst, w)
+        else:
+            xm, ym = chamfer_pairs(res_c, tgt_c)
+            cd_sum += float((xm + ym).sum())
         if a.voxel is not None:
             occ = [s + t for s, t in zip(occ, _occupancy_sums(res_c, tgt_c, a.voxel))]
-    abs_sum, cd_sum, *occ = _sum_over_ranks([abs_sum, cd_sum] + occ, dev)      # (occ: zeros without --voxel)
+    abs_sum, cd_sum, *rest = _sum_over_ranks([abs_sum, cd_sum] + occ + nn, dev)      # (occ: zeros without --voxel)
+    occ, nn = rest[:7], rest[7:]
     n = len(pairs)
     result = {"task": "inpainting", "pairs": n, "window": [w0, w1],
               "mae_m": {"reference": abs_sum / (n * W * H),            # mae.py:111: divided by files x W x H (a quirk)
@@ -471,26 +589,38 @@ def cmd_inpainting(a, rank, world, dev):
               "cd": cd_sum / n}
     if a.voxel is not None:
         result.update(voxel=a.voxel, occupancy=_occupancy_block(occ, n))
+    if _nn_wanted(a):
+        result.update(_nn_blocks(nn, _max_over_ranks([worst], dev)[0], n, a))
     return result
 
 
 def cmd_chamfer(a, rank, world, dev):
     from .metrics import chamfer_pairs
     check_voxel_arg(a)
+    check_nn_args(a)
     pairs = pair_by_name(a.a_dir, a.b_dir)
     cd = 0.0
     occ = [0.0] * 7                                      # --voxel: _occupancy_sums
+    nn, worst = [0.0] * _nn_len(a), 0.0                  # --match / --dcd-alpha: _nn_sums
     for chunk in _chunks(pairs[rank::world], 32):
         xs = [_load_bin(p, a.columns, dev)[:, :3] for p, _ in chunk]
         ys = [_load_bin(q, a.columns, dev)[:, :3] for _, q in chunk]
-        xm, ym = chamfer_pairs(xs, ys)
-        cd += float((xm + ym).sum())
+        if _nn_wanted(a):                                # one search for the CD and the rest
+            c, part, w = _nn_sums(xs, ys, a)
+            cd += c
+            nn, worst = _add(nn, part), max(worst, w)
+        else:
+            xm, ym = chamfer_pairs(xs, ys)
+            cd += float((xm + ym).sum())
         if a.voxel is not None:                          # A_DIR holds the results, B_DIR the targets
             occ = [s + t for s, t in zip(occ, _occupancy_sums(xs, ys, a.voxel))]
-    cd, *occ = _sum_over_ranks([cd] + occ, dev)          # (occ: zeros without --voxel)
+    cd, *rest = _sum_over_ranks([cd] + occ + nn, dev)    # (occ: zeros without --voxel)
+    occ, nn = rest[:7], rest[7:]
     result = {"task": "chamfer", "pairs": len(pairs), "cd": cd / len(pairs)}
     if a.voxel is not None:
         result.update(voxel=a.voxel, occupancy=_occupancy_block(occ, len(pairs)))
+    if _nn_wanted(a):
+        result.update(_nn_blocks(nn, _max_over_ranks([worst], dev)[0], len(pairs), a))
     return result
 
 

@@ -9,6 +9,12 @@ device tensors in, librangeldm_hip.so (rangeldm_amd/csrc/metrics.hip) underneath
 Reconstruction metrics (rangeldm_amd/csrc/chamfer.hip): chamfer_distance (pytorch3d call shape), nearest_sq_dists,
 range_errors (MAE / PSNR / range MAE sums) and beam_upsample (the nearest / bicubic baselines).
 
+Nearest neighbour with its index (rangeldm_amd/csrc/nn_index.hip): nearest_neighbours (d^2, the lowest index attaining it, and
+per point the number of points that chose it), transfer (attributes carried across by those indices), and what is read off
+them: match_counts / match_scores (precision, recall and F-score at distance thresholds), hausdorff, density_aware_chamfer
+(Wu et al. 2021) and pair_scores (all of them and the CD from one search); nearest_neighbours_host, match_counts_host,
+match_scores_host, hausdorff_host and density_aware_chamfer_host are the numpy statements.
+
 Voxel occupancy (rangeldm_amd/csrc/voxel.hip): voxel_counts, per pair the distinct voxels of the result, of the target and of
 both on a grid of `voxel` metres (a hash set per pair, filled with atomics alone), and voxel_scores, the IoU / precision /
 recall / F1 of those integers; voxel_counts_host / voxel_scores_host are the numpy statements the device equals exactly.
@@ -224,6 +230,289 @@ def chamfer_distance(x, y, x_lengths=None, y_lengths=None, point_reduction="mean
     if batch_reduction is None:
         return per_pair, None
     return (per_pair.sum() if batch_reduction == "sum" else per_pair.mean()), None
+
+
+# ---- nearest neighbour with its index: F-score, Hausdorff, density-aware CD (rangeldm_amd/csrc/nn_index.hip) -------------
+# the packed outputs of one rldm_nn_index call: per side d^2 (fp32), index into the pair's other cloud (int64), hits (int32),
+# offsets (host list, pairs + 1 entries), and the device offsets rldm_chamfer_mean reads
+_NNIndex = collections.namedtuple("_NNIndex", "xd xi xh xs yd yi yh ys xo yo")
+
+
+def _nn_index(x, y, x_lengths=None, y_lengths=None):
+    xs, ys = _clouds(x, x_lengths, "x"), _clouds(y, y_lengths, "y")
+    if len(xs) != len(ys):
+        raise ValueError(f"{len(xs)} x clouds against {len(ys)} y clouds")
+    _lib.require_gpu()
+    xp, xo, xk = _pack(xs)
+    yp, yo, yk = _pack(ys)
+    dev = xp.device
+    xd, yd = (torch.empty(t.shape[0], dtype=torch.float32, device=dev) for t in (xp, yp))
+    xi, yi, xh, yh = (torch.empty(t.shape[0], dtype=torch.int32, device=dev) for t in (xp, yp, xp, yp))
+    _lib.check(_lib.lib().rldm_nn_index(xp.data_ptr(), xo.data_ptr(), xk, yp.data_ptr(), yo.data_ptr(), yk, len(xs),
+                                        xd.data_ptr(), xi.data_ptr(), yd.data_ptr(), yi.data_ptr(), xh.data_ptr(),
+                                        yh.data_ptr(), _lib.stream_ptr(dev)), "rldm_nn_index")
+    return _NNIndex(xd, xi.long(), xh, xo.cpu().tolist(), yd, yi.long(), yh, yo.cpu().tolist(), xo, yo)
+
+
+def _per_pair(t, starts):
+    return [t[a:b] for a, b in zip(starts[:-1], starts[1:])]
+
+
+def _pair_ids(starts, device):
+    counts = torch.tensor([b - a for a, b in zip(starts[:-1], starts[1:])], device=device)
+    return torch.repeat_interleave(torch.arange(len(starts) - 1, device=device), counts)
+
+
+def nearest_neighbours(x, y, x_lengths=None, y_lengths=None, return_hits=False):
+    """nearest_sq_dists with the neighbour itself (pytorch3d's knn_points(K=1) in both directions).  Inputs as
+    nearest_sq_dists takes them; returns (x_d2, x_idx, y_d2, y_idx), each a list of one 1-D device tensor per pair:
+
+        x_d2[p][i]   fp32, the bits nearest_sq_dists gives: min over the points t of y_p of ((dx*dx + dy*dy) + dz*dz)
+        x_idx[p][i]  int64, the LOWEST index j of y_p whose d^2 has exactly those bits (it indexes y_p, or any tensor laid
+                     out like it, directly: see transfer)
+        y_d2, y_idx  the mirror: the points of y_p against x_p
+
+    return_hits=True appends (x_hits, y_hits), int32: y_hits[p][j] is the number of points of x_p whose x_idx is j, and
+    x_hits the mirror (so y_hits[p].sum() == len(x_p)).  Everything is exact: it equals nearest_neighbours_host bit for bit
+    and does not depend on the other pairs of the call or on how the kernel splits a cloud."""
+    r = _nn_index(x, y, x_lengths, y_lengths)
+    out = (_per_pair(r.xd, r.xs), _per_pair(r.xi, r.xs), _per_pair(r.yd, r.ys), _per_pair(r.yi, r.ys))
+    return out + (_per_pair(r.xh, r.xs), _per_pair(r.yh, r.ys)) if return_hits else out
+
+
+def transfer(values, idx):
+    """Carry per-point attributes (remission, a SemanticKITTI label, ...) from the y clouds onto the x clouds: `values` is a
+    list of (m_p, ...) tensors that live on the points of y_p, `idx` the x_idx of nearest_neighbours; the result is the list
+    of (n_p, ...) gathers values[p][idx[p]]."""
+    if len(values) != len(idx):
+        raise ValueError(f"{len(values)} value tensors against {len(idx)} index tensors")
+    return [v[i] for v, i in zip(values, idx)]
+
+
+def _tau_values(taus):
+    """`taus` (a number or a sequence of them) as a list of floats; ValueError unless every one is positive and finite as an
+    fp32 number (the comparison is d^2 <= float32(tau) * float32(tau))."""
+    import math
+    import numpy as np
+    try:
+        vals = [float(t) for t in (taus if isinstance(taus, (list, tuple)) else np.atleast_1d(taus).tolist())]
+    except (TypeError, ValueError):
+        raise ValueError(f"tau must be positive, finite numbers, got {taus!r}") from None
+    if not vals:
+        raise ValueError("no distance threshold given")
+    for v in vals:
+        with np.errstate(over="ignore"):
+            v32 = float(np.float32(v)) if math.isfinite(v) else v
+        if not (v32 > 0.0 and math.isfinite(v32)):
+            raise ValueError(f"tau must be positive and finite (as fp32), got {v!r}")
+    return vals
+
+
+def _tau_squares(taus):
+    """float32(tau) * float32(tau), one fp32 multiply each, as an fp32 numpy array."""
+    import numpy as np
+    t = np.asarray(_tau_values(taus), np.float32)
+    with np.errstate(over="ignore", under="ignore"):
+        return t * t
+
+
+def _alpha_value(alpha):
+    import math
+    if alpha is None:
+        raise ValueError("alpha is required: the paper's 1000 is for unit-normalised shapes, there is no canonical value in metres")
+    try:
+        v = float(alpha)
+    except (TypeError, ValueError):
+        raise ValueError(f"alpha must be a positive, finite number, got {alpha!r}") from None
+    if not (v > 0.0 and math.isfinite(v)):
+        raise ValueError(f"alpha must be positive and finite, got {alpha!r}")
+    return v
+
+
+def _match_counts(r, taus):
+    t2 = torch.from_numpy(_tau_squares(taus)).to(r.xd.device)
+    n = len(r.xs) - 1
+    out = torch.zeros((len(t2), 2, n), dtype=torch.int64, device=r.xd.device)
+    for side, (d, starts) in enumerate(((r.xd, r.xs), (r.yd, r.ys))):
+        # integer adds: exact, whatever order index_add_ takes them in
+        out[:, side].index_add_(1, _pair_ids(starts, d.device), (d[None, :] <= t2[:, None]).long())
+    return out.permute(2, 0, 1).contiguous()
+
+
+def _hausdorff(r):
+    n = len(r.xs) - 1
+    # a maximum is order-free; the fp64 square root is taken on the host, where it is correctly rounded
+    mx = torch.stack([torch.zeros(n, dtype=torch.float32, device=d.device).scatter_reduce_(0, _pair_ids(starts, d.device), d, "amax")
+                      for d, starts in ((r.xd, r.xs), (r.yd, r.ys))], 1)
+    import numpy as np
+    h = torch.from_numpy(np.sqrt(mx.cpu().numpy().astype(np.float64)))      # (numpy's sqrt: IEEE, the host statement's)
+    return torch.cat([h, h.max(1, keepdim=True).values], 1).to(r.xd.device)
+
+
+def _dcd(r, alpha):
+    a = _alpha_value(alpha)
+    out = []
+    for xd, xi, xh, yd, yi, yh in zip(*(_per_pair(t, s) for t, s in ((r.xd, r.xs), (r.xi, r.xs), (r.xh, r.xs),
+                                                                    (r.yd, r.ys), (r.yi, r.ys), (r.yh, r.ys)))):
+        tx = 1.0 - torch.exp(-(a * xd.double())) / yh[xi].double()
+        ty = 1.0 - torch.exp(-(a * yd.double())) / xh[yi].double()
+        out.append(0.5 * (tx.sum() / tx.shape[0] + ty.sum() / ty.shape[0]))
+    return torch.stack(out)
+
+
+def _match_ratios(counts, points, where):
+    """precision, recall, fscore (fp64) from the matched counts (N, T, 2) and the cloud sizes (N, 2), torch or numpy alike."""
+    f = counts.double() if torch.is_tensor(counts) else counts.astype("float64")
+    s = points.double() if torch.is_tensor(points) else points.astype("float64")
+    p, q = f[:, :, 0] / s[:, None, 0], f[:, :, 1] / s[:, None, 1]
+    return {"precision": p, "recall": q, "fscore": where(p + q > 0, 2.0 * p * q / (p + q), 0.0 * p)}
+
+
+def match_counts(x, y, taus, x_lengths=None, y_lengths=None):
+    """Per pair and distance threshold tau the number of points within tau of the other cloud: an int64 device tensor
+    (N, len(taus), 2), [p, k] = (points of x_p with d^2 <= t2, points of y_p with d^2 <= t2), t2 = float32(tau) * float32(tau)
+    (one fp32 multiply) compared with the exact fp32 d^2 of nearest_neighbours: the integers equal match_counts_host.
+    `taus` is a number or a sequence; every tau must be positive and finite (ValueError)."""
+    _tau_values(taus)
+    return _match_counts(_nn_index(x, y, x_lengths, y_lengths), taus)
+
+
+def _match_scores(r, taus):
+    counts = _match_counts(r, taus)
+    points = torch.tensor([[b - a for a, b in zip(s[:-1], s[1:])] for s in (r.xs, r.ys)], device=counts.device).t()
+    return {"tau": _tau_values(taus), **_match_ratios(counts, points, torch.where), "counts": counts, "points": points}
+
+
+def match_scores(x, y, taus, x_lengths=None, y_lengths=None):
+    """F-score at distance thresholds (Tatarchenko et al. 2019; Knapitsch et al. 2017) of result clouds x against their
+    targets y.  A dict: "tau" the thresholds, "precision", "recall", "fscore" fp64 device tensors (N, len(taus)), "counts"
+    the integers of match_counts and "points" the cloud sizes, int64 (N, 2):
+
+        precision = matched_x / n_x      recall = matched_y / n_y      fscore = 2 p r / (p + r), 0 when p + r == 0
+
+    Precision is about the result (the share of it within tau of the target), recall about the target.  Arguments and errors
+    as match_counts."""
+    _tau_values(taus)
+    return _match_scores(_nn_index(x, y, x_lengths, y_lengths), taus)
+
+
+def hausdorff(x, y, x_lengths=None, y_lengths=None):
+    """Hausdorff distances per pair: an fp64 device tensor (N, 3), row p = (x_to_y, y_to_x, symmetric).  x_to_y is the
+    fp64 square root of the largest fp32 d^2 of the points of x_p to their nearest neighbours in y_p (the worst point, which
+    a mean hides), y_to_x the mirror, symmetric the larger of the two.  Exact given the d^2: it equals hausdorff_host."""
+    return _hausdorff(_nn_index(x, y, x_lengths, y_lengths))
+
+
+def density_aware_chamfer(x, y, alpha=None, x_lengths=None, y_lengths=None):
+    """Density-aware Chamfer distance (Wu et al., NeurIPS 2021) per pair: an fp64 device tensor (N,).  With d^2_i the
+    squared distance of point i of x_p to its nearest neighbour j(i) in y_p, e^2_j and i(j) the mirror, and y_hits[j] /
+    x_hits[i] the number of points that chose j / i as their neighbour (nearest_neighbours(return_hits=True)):
+
+        dcd = 1/2 [ mean_i (1 - exp(-alpha * d^2_i) / y_hits[j(i)]) + mean_j (1 - exp(-alpha * e^2_j) / x_hits[i(j)]) ]
+
+    THIS variant puts the SQUARED distance in the exponent and has NO size-ratio factor (published code differs on both:
+    some uses the unsquared distance, some scales a term by n_x / n_y when the clouds differ in size).  CD is blind to many
+    result points collapsing onto one target point; here each of them earns only 1 / hits of the credit.  Every term lies
+    in [0, 1] (a point's own hit count is at least 1).  fp64 throughout, alpha * d^2 included; the means are fixed-order sums.
+    `alpha` has no default (ValueError when missing): the paper's 1000 is for unit-normalised shapes and there is no
+    canonical value in metres; it must be positive and finite."""
+    _alpha_value(alpha)
+    return _dcd(_nn_index(x, y, x_lengths, y_lengths), alpha)
+
+
+def pair_scores(x, y, taus=None, alpha=None, x_lengths=None, y_lengths=None):
+    """Everything the nearest-neighbour search of result clouds x against targets y gives, from ONE search: a dict with "cd"
+    (fp64 device (N,), the bits chamfer_pairs' x_mean + y_mean has: the same d^2 through the same fixed-order means) and,
+    with `taus`, "match" (match_scores' dict) and "hausdorff" (hausdorff's tensor); with `alpha`, "dcd"."""
+    if taus is not None:
+        _tau_values(taus)
+    if alpha is not None:
+        _alpha_value(alpha)
+    r = _nn_index(x, y, x_lengths, y_lengths)
+    n = len(r.xs) - 1
+    xm = torch.empty(n, dtype=torch.float64, device=r.xd.device)
+    ym = torch.empty(n, dtype=torch.float64, device=r.xd.device)
+    _lib.check(_lib.lib().rldm_chamfer_mean(r.xd.data_ptr(), r.xo.data_ptr(), r.yd.data_ptr(), r.yo.data_ptr(), n, xm.data_ptr(),
+                                            ym.data_ptr(), _lib.stream_ptr(xm.device)), "rldm_chamfer_mean")
+    out = {"cd": xm + ym}
+    if taus is not None:
+        out.update(match=_match_scores(r, taus), hausdorff=_hausdorff(r))
+    if alpha is not None:
+        out["dcd"] = _dcd(r, alpha)
+    return out
+
+
+def _nn_host_one(q, t):
+    """(d2 fp32, idx int64) of the points of q against t: brute force, a block of rows at a time (about 2^20 distances, so a
+    5 000 x 5 000 pair never holds more than 4 MB per temporary)."""
+    import numpy as np
+    q, t = (np.ascontiguousarray(np.asarray(c)[:, :3].astype(np.float32)) for c in (q, t))
+    tx, ty, tz = t[None, :, 0], t[None, :, 1], t[None, :, 2]
+    d2, idx = np.empty(len(q), np.float32), np.empty(len(q), np.int64)
+    step = max(1, (1 << 20) // len(t))
+    for lo in range(0, len(q), step):
+        c = q[lo:lo + step]
+        dx, dy, dz = c[:, 0:1] - tx, c[:, 1:2] - ty, c[:, 2:3] - tz
+        d = (dx * dx + dy * dy) + dz * dz
+        j = d.argmin(1)                                  # the first minimum: the lowest index
+        idx[lo:lo + step] = j
+        d2[lo:lo + step] = d[np.arange(len(c)), j]
+    return d2, idx
+
+
+def nearest_neighbours_host(x, y, return_hits=False):
+    """The numpy statement of nearest_neighbours: lists of (n_i, >= 3) arrays (or one array per side: one pair) -> lists of
+    arrays.  fp32 brute force with the kernel's expression ((dx*dx + dy*dy) + dz*dz), np.argmin (the first minimum), and
+    np.bincount for the hits (int32)."""
+    import numpy as np
+    xs, ys = _voxel_host_clouds(x, "x"), _voxel_host_clouds(y, "y")
+    if len(xs) != len(ys):
+        raise ValueError(f"{len(xs)} x clouds against {len(ys)} y clouds")
+    fwd = [_nn_host_one(a, b) for a, b in zip(xs, ys)]
+    bwd = [_nn_host_one(b, a) for a, b in zip(xs, ys)]
+    out = ([f[0] for f in fwd], [f[1] for f in fwd], [b[0] for b in bwd], [b[1] for b in bwd])
+    if not return_hits:
+        return out
+    return out + ([np.bincount(b[1], minlength=len(a)).astype(np.int32) for a, b in zip(xs, bwd)],
+                  [np.bincount(f[1], minlength=len(b)).astype(np.int32) for b, f in zip(ys, fwd)])
+
+
+def match_counts_host(x, y, taus):
+    """The numpy statement of match_counts: int64 (N, len(taus), 2)."""
+    import numpy as np
+    t2 = _tau_squares(taus)
+    xd, _, yd, _ = nearest_neighbours_host(x, y)
+    return np.array([[[int((a <= t).sum()), int((b <= t).sum())] for t in t2] for a, b in zip(xd, yd)], np.int64)
+
+
+def match_scores_host(x, y, taus):
+    """The numpy statement of match_scores: the same dict with numpy arrays."""
+    import numpy as np
+    counts = match_counts_host(x, y, taus)
+    points = np.array([[len(a), len(b)] for a, b in zip(_voxel_host_clouds(x, "x"), _voxel_host_clouds(y, "y"))], np.int64)
+    with np.errstate(invalid="ignore"):
+        return {"tau": _tau_values(taus), **_match_ratios(counts, points, np.where), "counts": counts, "points": points}
+
+
+def hausdorff_host(x, y):
+    """The numpy statement of hausdorff: fp64 (N, 3)."""
+    import numpy as np
+    xd, _, yd, _ = nearest_neighbours_host(x, y)
+    h = np.sqrt(np.array([[a.max(), b.max()] for a, b in zip(xd, yd)], np.float64))
+    return np.concatenate([h, h.max(1, keepdims=True)], 1)
+
+
+def density_aware_chamfer_host(x, y, alpha=None):
+    """The numpy statement of density_aware_chamfer: fp64 (N,)."""
+    import numpy as np
+    a = _alpha_value(alpha)
+    xd, xi, yd, yi, xh, yh = nearest_neighbours_host(x, y, return_hits=True)
+    out = []
+    for p in range(len(xd)):
+        tx = 1.0 - np.exp(-(a * xd[p].astype(np.float64))) / yh[p][xi[p]].astype(np.float64)
+        ty = 1.0 - np.exp(-(a * yd[p].astype(np.float64))) / xh[p][yi[p]].astype(np.float64)
+        out.append(0.5 * (tx.sum() / len(tx) + ty.sum() / len(ty)))
+    return np.array(out, np.float64)
 
 
 # ---- voxel occupancy: IoU / precision / recall / F1 of the occupied voxels (rangeldm_amd/csrc/voxel.hip) ------------------
