@@ -325,6 +325,25 @@ int rldm_chamfer_mean(const float* x_nn_d2, const int32_t* x_offsets, const floa
 int rldm_nn_index(const float* x, const int32_t* x_offsets, int x_stride, const float* y, const int32_t* y_offsets,
                   int y_stride, int num_pairs, float* x_nn_d2, int32_t* x_nn_idx, float* y_nn_d2, int32_t* y_nn_idx,
                   int32_t* x_hits, int32_t* y_hits, void* stream);
+/* K nearest neighbours (rangeldm_amd/csrc/knn.hip), ONE direction: the queries of pair p against the targets of pair p, both
+ * packed as rldm_nn_index takes them (device int32 offsets that start at 0, strides >= 3 with only xyz read, clouds non-empty,
+ * coordinates finite).  1 <= K <= RLDM_KNN_MAX_K.  Row i of d2 / idx ([q_offsets[num_pairs]][K], device fp32 / int32) holds the
+ * K targets that are smallest in the order (d2 bits, local target index), ascending in that order, with
+ * d2 = ((dx*dx + dy*dy) + dz*dz), dx = q - t, uncontracted fp32: equal distances go to the lower index, and for K = 1 the row
+ * is rldm_nn_index's answer bit for bit.  exclude_self != 0 requires the two clouds of every pair to have equal sizes and skips
+ * the target whose local index is the query's (another point at the same coordinates stays a neighbour at d2 = 0).  A row with
+ * fewer than K candidates ends in slots (+inf, -1).  A row depends on the two clouds of its pair alone.  The call
+ * synchronises the stream. */
+#define RLDM_KNN_MAX_K 32
+int rldm_knn(const float* q, const int32_t* q_offsets, int q_stride, const float* t, const int32_t* t_offsets, int t_stride,
+             int num_pairs, int K, int exclude_self, float* d2, int32_t* idx, void* stream);
+/* PCA surface normals from rldm_knn(exclude_self) indices: idx is [offsets[num_clouds]][K], local to each cloud; entries
+ * outside a cloud (-1) are skipped.  Per point, in fp64: the covariance (divided by the count) of the point itself and its
+ * valid neighbours about their centroid, a cyclic Jacobi eigen-solve with a fixed number of sweeps, eigenvalues ascending
+ * ([N][3]) and as normal ([N][3]) the unit eigenvector of the smallest, oriented towards the sensor at the origin
+ * (n . p <= 0; when that is 0 the first non-zero component is positive).  Fewer than two valid neighbours: zeros. */
+int rldm_knn_normals(const float* pts, const int32_t* offsets, int stride, int num_clouds, const int32_t* idx, int K,
+                     double* normals, double* eigenvalues, void* stream);
 /* All-pairs Chamfer matrix between two ragged SETS of clouds, X (nx clouds) and Y (ny clouds), packed as rldm_chamfer_nn
  * takes them (device fp32 [n][stride >= 3], only xyz read; device int32 offsets [nx + 1] / [ny + 1], starting at 0):
  *   xy[i][j] = mean over points q of X_i of min over points t of Y_j of d2(q, t)

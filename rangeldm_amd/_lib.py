@@ -181,6 +181,9 @@ PROTOTYPES = {
     "rldm_chamfer_mean": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, _P, _P]),
     # nearest neighbour with its index and the hit counts (csrc/nn_index.hip): packed as rldm_chamfer_nn; d2, idx per side, hits
     "rldm_nn_index": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    # K nearest neighbours, one direction (csrc/knn.hip): d2 and idx [queries][K]; PCA normals and eigenvalues from such indices
+    "rldm_knn": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "rldm_knn_normals": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
     # all-pairs Chamfer matrix of two sets of clouds, and the lowest-index row argmin the set metrics count with
     "rldm_chamfer_matrix": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "rldm_matrix_row_argmin": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),

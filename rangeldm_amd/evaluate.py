@@ -1,10 +1,10 @@
 """Evaluation on the MI355X: score what the VAE and the conditional sampler reconstruct, and what the sampler generates.
 
     python -m rangeldm_amd.evaluate vae --weights outputs/RangeLDM --samples 1000 --batch-size 4 [--input DIR] [--voxel 0.1]
-                                        [--match TAU [TAU ...]] [--dcd-alpha A]
-    python -m rangeldm_amd.evaluate densification --exp outputs/upsample/generated [--cfg upsample] [--voxel 0.1] [--match ..] [--dcd-alpha A]
-    python -m rangeldm_amd.evaluate inpainting --exp outputs/inpainting/generated [--cfg inpainting] [--voxel 0.1] [--match ..] [--dcd-alpha A]
-    python -m rangeldm_amd.evaluate chamfer A_DIR B_DIR [--voxel 0.1] [--match TAU [TAU ...]] [--dcd-alpha A]
+                                        [--match TAU [TAU ...]] [--dcd-alpha A] [--normals K]
+    python -m rangeldm_amd.evaluate densification --exp outputs/upsample/generated [--cfg upsample] [--voxel 0.1] [--match ..] [--dcd-alpha A] [--normals K]
+    python -m rangeldm_amd.evaluate inpainting --exp outputs/inpainting/generated [--cfg inpainting] [--voxel 0.1] [--match ..] [--dcd-alpha A] [--normals K]
+    python -m rangeldm_amd.evaluate chamfer A_DIR B_DIR [--voxel 0.1] [--match TAU [TAU ...]] [--dcd-alpha A] [--normals K]
     python -m rangeldm_amd.evaluate generation GEN_DIR REF_DIR [--points 2048] [--limit N] [--seed 0] [--max-depth M]
                                                [--sampling {random,fps}] [--emd [--emd-eps 0.0078125]]
     python -m rangeldm_amd.evaluate frd FOLDER1 FOLDER2 [--limit 1100] [--rangenet MODEL_DIR [--projection {host,device}]]
@@ -52,6 +52,12 @@ mean_x min_y |x - y|^2 + mean_y min_x |x - y|^2 over xyz.
                  (rangeldm_amd/csrc/nn_index.hip), and "cd" is taken from that search's distances: they are the bits the plain
                  search gives and go through the same means, so "cd" is unchanged.  Without the flags the object is what
                  it was.
+  --normals K    (the same commands, the same clouds and roles) adds "plane": {"k": K, "cd_plane", "normal_consistency"}, the
+                 means over pairs of metrics.plane_scores (rangeldm_amd/csrc/knn.hip): surface normals by PCA over the K
+                 nearest neighbours of each cloud (1 <= K <= 32), the point-to-plane Chamfer distance (the squared distance
+                 to the tangent plane at the nearest point of the other cloud, both directions added) and pytorch3d's normal
+                 consistency.  A pair's values depend on the pair alone, so the block is the same for any number of ranks.
+                 Without the flag the object is what it was.
   generation     set-level metrics of a folder of generated .bin clouds against a folder of reference sweeps (Achlioptas et
                  al. 2018; Yang et al. 2019): MMD-CD, COV-CD and 1-NNA-CD (metrics.set_metrics) from the all-pairs Chamfer
                  matrices, every cloud cut to the points closer than --max-depth and sub-sampled to --points
@@ -133,6 +139,8 @@ def build_parser():
                   "(0.1 in the up-sampling literature)")
     match_help = ("also report precision / recall / F-score of result against target at each distance threshold TAU (metres), "
                   "and the Hausdorff distance")
+    normals_help = ("also report the point-to-plane Chamfer distance and the normal consistency, with PCA normals over the K nearest "
+                    "neighbours (1..32)")
     dcd_help = "also report the density-aware Chamfer distance (Wu et al. 2021) with this alpha (per square metre; no default)"
 
     for task in ("densification", "inpainting"):
@@ -143,6 +151,7 @@ def build_parser():
         t.add_argument("--voxel", type=float, default=None, metavar="SIZE", help=voxel_help)
         t.add_argument("--match", type=float, nargs="+", default=None, metavar="TAU", help=match_help)
         t.add_argument("--dcd-alpha", type=float, default=None, metavar="A", help=dcd_help)
+        t.add_argument("--normals", type=int, default=None, metavar="K", help=normals_help)
 
     c = sub.add_parser("chamfer", help="mean CD over .bin files of two folders, paired by name")
     c.add_argument("a_dir")
@@ -152,6 +161,7 @@ def build_parser():
         p.add_argument("--voxel", type=float, default=None, metavar="SIZE", help=voxel_help)
         p.add_argument("--match", type=float, nargs="+", default=None, metavar="TAU", help=match_help)
         p.add_argument("--dcd-alpha", type=float, default=None, metavar="A", help=dcd_help)
+        p.add_argument("--normals", type=int, default=None, metavar="K", help=normals_help)
 
     g = sub.add_parser("generation", help="MMD-CD / COV-CD / 1-NNA-CD (+ BEV jsd / mmd) of generated against reference clouds")
     g.add_argument("gen_dir")
@@ -400,6 +410,25 @@ def _nn_blocks(tot, worst, n, a):
     return out
 
 
+def check_normals_arg(a):
+    """`--normals`: refused before a file is read unless it is in 1..32 (None: the flag was not given)."""
+    if a.normals is not None:
+        from .metrics import _knn_k
+        _knn_k(a.normals)
+
+
+def _plane_sums(result, target, k):
+    """[sum of cd_plane, sum of normal_consistency] over the pairs of one metrics.plane_scores call (result clouds against
+    target clouds): what a rank accumulates and _sum_over_ranks reduces."""
+    from .metrics import plane_scores
+    s = plane_scores(result, target, k)
+    return [float(s["cd_plane"].sum()), float(s["normal_consistency"].sum())]
+
+
+def _plane_block(tot, n, k):
+    return {"k": k, "cd_plane": tot[0] / n, "normal_consistency": tot[1] / n}
+
+
 def _add(acc, part):
     return [s + t for s, t in zip(acc, part)]
 
@@ -427,6 +456,7 @@ def cmd_vae(a, rank, world, dev):
     from .metrics import chamfer_pairs, range_errors
     check_voxel_arg(a)
     check_nn_args(a)
+    check_normals_arg(a)
     vae, origin = _load_vae(a)
     shape = (vae._cfg.in_channels, *vae._cfg.sample_size)
     files = sorted(glob.glob(os.path.join(a.input, "*.npy")))[:a.samples] if a.input else None
@@ -439,6 +469,7 @@ def cmd_vae(a, rank, world, dev):
     sums = [0.0, 0.0, 0.0, 0.0]                          # MAE, PSNR, CD, images
     occ = [0.0] * 7                                      # --voxel: _occupancy_sums
     nn, worst = [0.0] * _nn_len(a), 0.0                  # --match / --dcd-alpha: _nn_sums
+    plane = [0.0, 0.0]                                   # --normals: _plane_sums
     n_batches = (total + a.batch_size - 1) // a.batch_size
     for b in range(rank, n_batches, world):              # batch b holds global samples [b * bs, (b + 1) * bs)
         lo, hi = b * a.batch_size, min(total, (b + 1) * a.batch_size)
@@ -471,13 +502,17 @@ def cmd_vae(a, rank, world, dev):
         sums[3] += hi - lo
         if a.voxel is not None:                          # the reconstruction is the result, the input the target
             occ = [s + t for s, t in zip(occ, _occupancy_sums(clouds_out, clouds_in, a.voxel))]
-    mae, psnr, cd, n, *rest = _sum_over_ranks(sums + occ + nn, dev)      # (occ: zeros without --voxel)
-    occ, nn = rest[:7], rest[7:]
+        if a.normals is not None:
+            plane = _add(plane, _plane_sums(clouds_out, clouds_in, a.normals))
+    mae, psnr, cd, n, *rest = _sum_over_ranks(sums + occ + plane + nn, dev)      # (occ, plane: zeros without their flags)
+    occ, plane, nn = rest[:7], rest[7:9], rest[9:]
     result = {"task": "vae", "weights": origin, "samples": int(n), "mae": mae / n, "psnr": psnr / n, "cd": cd / n}
     if a.voxel is not None:
         result.update(voxel=a.voxel, occupancy=_occupancy_block(occ, n))
     if _nn_wanted(a):
         result.update(_nn_blocks(nn, _max_over_ranks([worst], dev)[0], n, a))
+    if a.normals is not None:
+        result["plane"] = _plane_block(plane, n, a.normals)
     return result
 
 
@@ -490,6 +525,7 @@ def cmd_densification(a, rank, world, dev):
     from .metrics import beam_upsample, chamfer_pairs, range_errors
     check_voxel_arg(a)
     check_nn_args(a)
+    check_normals_arg(a)
     cfg, sensor = task_sensor(a.cfg)
     if cfg["task"] != "upsample":
         raise ValueError(f"{a.cfg} is not an up-sampling config")
@@ -502,6 +538,7 @@ def cmd_densification(a, rank, world, dev):
     occ = {m: [0.0] * 7 for m in methods}                # --voxel: _occupancy_sums per method
     L = _nn_len(a)
     nn, worst = {m: [0.0] * L for m in methods}, {m: 0.0 for m in methods}      # --match / --dcd-alpha: _nn_sums per method
+    plane = {m: [0.0, 0.0] for m in methods}              # --normals: _plane_sums per method
     W, H = sensor.width, sensor.H
     for chunk in _chunks(pairs[rank::world], 32):
         clouds = {m: [] for m in methods}
@@ -532,8 +569,11 @@ def cmd_densification(a, rank, world, dev):
                 cd_sum[m] += float((xm + ym).sum())
             if a.voxel is not None:
                 occ[m] = [s + t for s, t in zip(occ[m], _occupancy_sums(clouds[m], targets, a.voxel))]
+            if a.normals is not None:
+                plane[m] = _add(plane[m], _plane_sums(clouds[m], targets, a.normals))
     tot = _sum_over_ranks([abs_sum[m] for m in methods] + [cd_sum[m] for m in methods] +
-                          [s for m in methods for s in occ[m]] + [s for m in methods for s in nn[m]], dev)
+                          [s for m in methods for s in occ[m]] + [s for m in methods for s in nn[m]] +
+                          [s for m in methods for s in plane[m]], dev)
     n = len(pairs)
     result = {"task": "densification", "pairs": n, "rate": rate,
               "mae_m": {m: tot[i] / (n * W * H) for i, m in enumerate(methods)},
@@ -545,6 +585,9 @@ def cmd_densification(a, rank, world, dev):
         worst = _max_over_ranks([worst[m] for m in methods], dev)
         blocks = [_nn_blocks(tot[27 + L * i:27 + L * (i + 1)], worst[i], n, a) for i in range(len(methods))]
         result.update({key: {m: blocks[i][key] for i, m in enumerate(methods)} for key in blocks[0]})
+    if a.normals is not None:
+        at = 27 + 3 * L
+        result["plane"] = {m: _plane_block(tot[at + 2 * i:at + 2 * i + 2], n, a.normals) for i, m in enumerate(methods)}
     return result
 
 
@@ -552,6 +595,7 @@ def cmd_inpainting(a, rank, world, dev):
     from .metrics import chamfer_pairs, range_errors
     check_voxel_arg(a)
     check_nn_args(a)
+    check_normals_arg(a)
     cfg, sensor = task_sensor(a.cfg)
     if cfg["task"] != "inpainting":
         raise ValueError(f"{a.cfg} is not an in-painting config")
@@ -562,6 +606,7 @@ def cmd_inpainting(a, rank, world, dev):
     abs_sum = cd_sum = 0.0
     occ = [0.0] * 7                                      # --voxel: _occupancy_sums
     nn, worst = [0.0] * _nn_len(a), 0.0                  # --match / --dcd-alpha: _nn_sums
+    plane = [0.0, 0.0]                                   # --normals: _plane_sums
     for chunk in _chunks(pairs[rank::world], 32):
         res_c, tgt_c = [], []
         for rpath, tpath in chunk:
@@ -580,8 +625,10 @@ def cmd_inpainting(a, rank, world, dev):
             cd_sum += float((xm + ym).sum())
         if a.voxel is not None:
             occ = [s + t for s, t in zip(occ, _occupancy_sums(res_c, tgt_c, a.voxel))]
-    abs_sum, cd_sum, *rest = _sum_over_ranks([abs_sum, cd_sum] + occ + nn, dev)      # (occ: zeros without --voxel)
-    occ, nn = rest[:7], rest[7:]
+        if a.normals is not None:
+            plane = _add(plane, _plane_sums(res_c, tgt_c, a.normals))
+    abs_sum, cd_sum, *rest = _sum_over_ranks([abs_sum, cd_sum] + occ + plane + nn, dev)      # (occ, plane: zeros without their flags)
+    occ, plane, nn = rest[:7], rest[7:9], rest[9:]
     n = len(pairs)
     result = {"task": "inpainting", "pairs": n, "window": [w0, w1],
               "mae_m": {"reference": abs_sum / (n * W * H),            # mae.py:111: divided by files x W x H (a quirk)
@@ -591,6 +638,8 @@ def cmd_inpainting(a, rank, world, dev):
         result.update(voxel=a.voxel, occupancy=_occupancy_block(occ, n))
     if _nn_wanted(a):
         result.update(_nn_blocks(nn, _max_over_ranks([worst], dev)[0], n, a))
+    if a.normals is not None:
+        result["plane"] = _plane_block(plane, n, a.normals)
     return result
 
 
@@ -598,10 +647,12 @@ def cmd_chamfer(a, rank, world, dev):
     from .metrics import chamfer_pairs
     check_voxel_arg(a)
     check_nn_args(a)
+    check_normals_arg(a)
     pairs = pair_by_name(a.a_dir, a.b_dir)
     cd = 0.0
     occ = [0.0] * 7                                      # --voxel: _occupancy_sums
     nn, worst = [0.0] * _nn_len(a), 0.0                  # --match / --dcd-alpha: _nn_sums
+    plane = [0.0, 0.0]                                   # --normals: _plane_sums
     for chunk in _chunks(pairs[rank::world], 32):
         xs = [_load_bin(p, a.columns, dev)[:, :3] for p, _ in chunk]
         ys = [_load_bin(q, a.columns, dev)[:, :3] for _, q in chunk]
@@ -614,13 +665,17 @@ def cmd_chamfer(a, rank, world, dev):
             cd += float((xm + ym).sum())
         if a.voxel is not None:                          # A_DIR holds the results, B_DIR the targets
             occ = [s + t for s, t in zip(occ, _occupancy_sums(xs, ys, a.voxel))]
-    cd, *rest = _sum_over_ranks([cd] + occ + nn, dev)    # (occ: zeros without --voxel)
-    occ, nn = rest[:7], rest[7:]
+        if a.normals is not None:
+            plane = _add(plane, _plane_sums(xs, ys, a.normals))
+    cd, *rest = _sum_over_ranks([cd] + occ + plane + nn, dev)    # (occ, plane: zeros without their flags)
+    occ, plane, nn = rest[:7], rest[7:9], rest[9:]
     result = {"task": "chamfer", "pairs": len(pairs), "cd": cd / len(pairs)}
     if a.voxel is not None:
         result.update(voxel=a.voxel, occupancy=_occupancy_block(occ, len(pairs)))
     if _nn_wanted(a):
         result.update(_nn_blocks(nn, _max_over_ranks([worst], dev)[0], len(pairs), a))
+    if a.normals is not None:
+        result["plane"] = _plane_block(plane, len(pairs), a.normals)
     return result
 
 

@@ -15,6 +15,12 @@ them: match_counts / match_scores (precision, recall and F-score at distance thr
 (Wu et al. 2021) and pair_scores (all of them and the CD from one search); nearest_neighbours_host, match_counts_host,
 match_scores_host, hausdorff_host and density_aware_chamfer_host are the numpy statements.
 
+K nearest neighbours (rangeldm_amd/csrc/knn.hip): knn_points / self_neighbours (pytorch3d's knn_points, exact, K <= 32),
+estimate_normals (PCA over those neighbourhoods in fp64), chamfer_distance(x_normals=, y_normals=) (pytorch3d's loss_normals),
+plane_scores (point-to-plane Chamfer distance and normal consistency per pair) and statistical_outliers (Open3D's rule);
+knn_points_host, estimate_normals_host, normal_consistency_host, plane_scores_host and statistical_outliers_host are the numpy
+statements.
+
 Voxel occupancy (rangeldm_amd/csrc/voxel.hip): voxel_counts, per pair the distinct voxels of the result, of the target and of
 both on a grid of `voxel` metres (a hash set per pair, filled with atomics alone), and voxel_scores, the IoU / precision /
 recall / F1 of those integers; voxel_counts_host / voxel_scores_host are the numpy statements the device equals exactly.
@@ -216,20 +222,36 @@ def chamfer_pairs(x, y, x_lengths=None, y_lengths=None):
     return xm, ym
 
 
-def chamfer_distance(x, y, x_lengths=None, y_lengths=None, point_reduction="mean", batch_reduction="mean", norm=2):
+def chamfer_distance(x, y, x_lengths=None, y_lengths=None, point_reduction="mean", batch_reduction="mean", norm=2,
+                     x_normals=None, y_normals=None):
     """pytorch3d.loss.chamfer_distance with its defaults (ldm/convert_vae.py:262-271): padded (N, P, >= 3) tensors with
-    optional lengths, or lists of (n_i, >= 3) device tensors; only xyz is used.  Returns (dist, None) like pytorch3d (no
-    normals).  dist is an fp64 device scalar: batch_reduction "mean" averages the per-pair sums
-    mean_x min_y d^2 + mean_y min_x d^2, "sum" adds them, None returns the (N,) vector."""
+    optional lengths, or lists of (n_i, >= 3) device tensors; only xyz is used.  Returns (dist, loss_normals) like
+    pytorch3d.  dist is an fp64 device scalar: batch_reduction "mean" averages the per-pair sums
+    mean_x min_y d^2 + mean_y min_x d^2, "sum" adds them, None returns the (N,) vector.
+
+    Without normals loss_normals is None.  With x_normals AND y_normals (each a padded (N, P, 3) tensor or a list of (n_i, 3)
+    device tensors laid out like the clouds; estimate_normals gives such lists) it is pytorch3d's: per pair
+    mean_i (1 - |cos(x_normals[i], y_normals[j(i)])|) + the mirror, j(i) the nearest point of the other cloud (the lowest
+    index among ties: nearest_neighbours), cos = torch.nn.functional.cosine_similarity(eps=1e-6) in fp64; through the same
+    batch_reduction.  dist then comes from that one search and has the bits it has without normals."""
     if point_reduction != "mean" or norm != 2:
         raise NotImplementedError("only point_reduction='mean', norm=2 (pytorch3d's defaults, the call the reference makes)")
     if batch_reduction not in ("mean", "sum", None):
         raise ValueError(f"batch_reduction must be 'mean', 'sum' or None, got {batch_reduction!r}")
-    xm, ym = chamfer_pairs(x, y, x_lengths, y_lengths)
-    per_pair = xm + ym
+    if (x_normals is None) != (y_normals is None):
+        raise ValueError("x_normals and y_normals must be given together")
+    if x_normals is None:
+        xm, ym = chamfer_pairs(x, y, x_lengths, y_lengths)
+        parts = (xm + ym,)
+    else:
+        xs, ys = _clouds(x, x_lengths, "x"), _clouds(y, y_lengths, "y")
+        xn, yn = _normal_lists(x_normals, xs, "x_normals"), _normal_lists(y_normals, ys, "y_normals")
+        r = _nn_index(xs, ys)
+        parts = (_chamfer_means(r), _normal_consistency(r, xn, yn))
     if batch_reduction is None:
-        return per_pair, None
-    return (per_pair.sum() if batch_reduction == "sum" else per_pair.mean()), None
+        return parts + (None,) * (2 - len(parts))
+    parts = tuple(t.sum() if batch_reduction == "sum" else t.mean() for t in parts)
+    return parts + (None,) * (2 - len(parts))
 
 
 # ---- nearest neighbour with its index: F-score, Hausdorff, density-aware CD (rangeldm_amd/csrc/nn_index.hip) -------------
@@ -252,6 +274,16 @@ def _nn_index(x, y, x_lengths=None, y_lengths=None):
                                         xd.data_ptr(), xi.data_ptr(), yd.data_ptr(), yi.data_ptr(), xh.data_ptr(),
                                         yh.data_ptr(), _lib.stream_ptr(dev)), "rldm_nn_index")
     return _NNIndex(xd, xi.long(), xh, xo.cpu().tolist(), yd, yi.long(), yh, yo.cpu().tolist(), xo, yo)
+
+
+def _chamfer_means(r):
+    """x_mean + y_mean of chamfer_pairs (fp64 device (N,)) from the d^2 of one _nn_index search: the same bits."""
+    n = len(r.xs) - 1
+    xm = torch.empty(n, dtype=torch.float64, device=r.xd.device)
+    ym = torch.empty(n, dtype=torch.float64, device=r.xd.device)
+    _lib.check(_lib.lib().rldm_chamfer_mean(r.xd.data_ptr(), r.xo.data_ptr(), r.yd.data_ptr(), r.yo.data_ptr(), n, xm.data_ptr(),
+                                            ym.data_ptr(), _lib.stream_ptr(xm.device)), "rldm_chamfer_mean")
+    return xm + ym
 
 
 def _per_pair(t, starts):
@@ -429,12 +461,7 @@ def pair_scores(x, y, taus=None, alpha=None, x_lengths=None, y_lengths=None):
     if alpha is not None:
         _alpha_value(alpha)
     r = _nn_index(x, y, x_lengths, y_lengths)
-    n = len(r.xs) - 1
-    xm = torch.empty(n, dtype=torch.float64, device=r.xd.device)
-    ym = torch.empty(n, dtype=torch.float64, device=r.xd.device)
-    _lib.check(_lib.lib().rldm_chamfer_mean(r.xd.data_ptr(), r.xo.data_ptr(), r.yd.data_ptr(), r.yo.data_ptr(), n, xm.data_ptr(),
-                                            ym.data_ptr(), _lib.stream_ptr(xm.device)), "rldm_chamfer_mean")
-    out = {"cd": xm + ym}
+    out = {"cd": _chamfer_means(r)}
     if taus is not None:
         out.update(match=_match_scores(r, taus), hausdorff=_hausdorff(r))
     if alpha is not None:
@@ -513,6 +540,288 @@ def density_aware_chamfer_host(x, y, alpha=None):
         ty = 1.0 - np.exp(-(a * yd[p].astype(np.float64))) / xh[p][yi[p]].astype(np.float64)
         out.append(0.5 * (tx.sum() / len(tx) + ty.sum() / len(ty)))
     return np.array(out, np.float64)
+
+
+# ---- K nearest neighbours, PCA normals, point-to-plane CD, normal consistency, outliers (rangeldm_amd/csrc/knn.hip) ------
+KNN_MAX_K = 32              # RLDM_KNN_MAX_K
+
+
+def _knn_k(K):
+    """`K` as an int; ValueError unless it is an integer in 1..KNN_MAX_K."""
+    import numbers
+    if isinstance(K, bool) or not isinstance(K, numbers.Integral) or not 1 <= int(K) <= KNN_MAX_K:
+        raise ValueError(f"K must be an integer in 1..{KNN_MAX_K}, got {K!r}")
+    return int(K)
+
+
+def _knn(xs, ys, K, exclude_self):
+    """One rldm_knn call, the clouds xs against ys (ys None: xs against themselves).  Returns the packed d2 (n, K) fp32 and
+    idx (n, K) int32, the packed queries with their device offsets and stride, and the offsets as a host list."""
+    _lib.require_gpu()
+    xp, xo, xk = _pack(xs)
+    yp, yo, yk = (xp, xo, xk) if ys is None else _pack(ys)
+    d2 = torch.empty((xp.shape[0], K), dtype=torch.float32, device=xp.device)
+    idx = torch.empty((xp.shape[0], K), dtype=torch.int32, device=xp.device)
+    _lib.check(_lib.lib().rldm_knn(xp.data_ptr(), xo.data_ptr(), xk, yp.data_ptr(), yo.data_ptr(), yk, len(xs), K,
+                                   1 if exclude_self else 0, d2.data_ptr(), idx.data_ptr(), _lib.stream_ptr(xp.device)),
+               "rldm_knn")
+    return d2, idx, xp, xo, xk, xo.cpu().tolist()
+
+
+def knn_points(x, y, K, x_lengths=None, y_lengths=None):
+    """pytorch3d's knn_points, exact: for every point of x_p its K nearest points of y_p.  Inputs as nearest_neighbours takes
+    them, 1 <= K <= 32.  Returns (d2, idx), each a list with one entry per pair: d2[p] (n_p, K) fp32, idx[p] (n_p, K) int64.
+    Row i holds the K points of y_p that are smallest in the order (d^2 bits, index), ascending in that order, with the fp32
+    d^2 = ((dx*dx + dy*dy) + dz*dz) of nearest_sq_dists: equal distances go to the lower index, and K = 1 is
+    nearest_neighbours' x_d2 / x_idx bit for bit.  Where y_p has fewer than K points the row ends in (+inf, -1).  Everything
+    equals knn_points_host exactly and depends on the two clouds of the pair alone."""
+    K = _knn_k(K)
+    xs, ys = _clouds(x, x_lengths, "x"), _clouds(y, y_lengths, "y")
+    if len(xs) != len(ys):
+        raise ValueError(f"{len(xs)} x clouds against {len(ys)} y clouds")
+    d2, idx, _, _, _, starts = _knn(xs, ys, K, False)
+    return _per_pair(d2, starts), _per_pair(idx.long(), starts)
+
+
+def self_neighbours(x, K, x_lengths=None):
+    """knn_points of every cloud against itself with the point itself left out (only itself: another point at the same
+    coordinates is a neighbour at d^2 = 0).  A cloud of fewer than K + 1 points has rows that end in (+inf, -1)."""
+    K = _knn_k(K)
+    d2, idx, _, _, _, starts = _knn(_clouds(x, x_lengths, "x"), None, K, True)
+    return _per_pair(d2, starts), _per_pair(idx.long(), starts)
+
+
+def _knn_host_one(q, t, K, exclude_self):
+    import numpy as np
+    q, t = (np.ascontiguousarray(np.asarray(c)[:, :3].astype(np.float32)) for c in (q, t))
+    if exclude_self and len(q) != len(t):
+        raise ValueError("exclude_self needs clouds of equal sizes")
+    tx, ty, tz = t[None, :, 0], t[None, :, 1], t[None, :, 2]
+    d2 = np.full((len(q), K), np.inf, np.float32)
+    idx = np.full((len(q), K), -1, np.int64)
+    step = max(1, (1 << 20) // len(t))
+    for lo in range(0, len(q), step):
+        c = q[lo:lo + step]
+        dx, dy, dz = c[:, 0:1] - tx, c[:, 1:2] - ty, c[:, 2:3] - tz
+        d = (dx * dx + dy * dy) + dz * dz
+        order = np.lexsort((np.broadcast_to(np.arange(len(t)), d.shape), d), axis=-1)      # by d2, then by index
+        if exclude_self:
+            order = order[order != np.arange(lo, lo + len(c))[:, None]].reshape(len(c), len(t) - 1)
+        order = order[:, :K]
+        idx[lo:lo + len(c), :order.shape[1]] = order
+        d2[lo:lo + len(c), :order.shape[1]] = np.take_along_axis(d, order, 1)
+    return d2, idx
+
+
+def knn_points_host(x, y, K, exclude_self=False):
+    """The numpy statement of knn_points (exclude_self=True with y = x: of self_neighbours): lists of (n_i, >= 3) arrays (or
+    one array per side: one pair) -> (d2, idx) lists of (n_i, K) fp32 / int64 arrays.  fp32 brute force with the kernel's
+    expression ((dx*dx + dy*dy) + dz*dz), then np.lexsort((index, d2))[:K] per row; missing slots are (+inf, -1)."""
+    K = _knn_k(K)
+    xs, ys = _voxel_host_clouds(x, "x"), _voxel_host_clouds(y, "y")
+    if len(xs) != len(ys):
+        raise ValueError(f"{len(xs)} x clouds against {len(ys)} y clouds")
+    out = [_knn_host_one(a, b, K, exclude_self) for a, b in zip(xs, ys)]
+    return [o[0] for o in out], [o[1] for o in out]
+
+
+def estimate_normals(x, K=16, x_lengths=None, return_eigenvalues=False):
+    """Surface normals by PCA over the K nearest neighbours (self_neighbours): a list of (n_p, 3) fp64 device tensors.  Per
+    point, in fp64: the covariance of the point and its neighbours about their centroid, divided by their number; the normal
+    is the unit eigenvector of its smallest eigenvalue, oriented towards the sensor at the origin (n . p <= 0; when that is 0
+    the first non-zero component is positive).  A point with fewer than two neighbours (a cloud of one or two points) gets
+    zeros.  return_eigenvalues=True appends the list of (n_p, 3) ascending eigenvalues (lambda_0 / trace is the surface
+    variation).  estimate_normals_host on the same indices is the numpy statement."""
+    K = _knn_k(K)
+    xs = _clouds(x, x_lengths, "x")
+    _, idx, xp, xo, xk, starts = _knn(xs, None, K, True)
+    normals = torch.empty((xp.shape[0], 3), dtype=torch.float64, device=xp.device)
+    eig = torch.empty((xp.shape[0], 3), dtype=torch.float64, device=xp.device)
+    _lib.check(_lib.lib().rldm_knn_normals(xp.data_ptr(), xo.data_ptr(), xk, len(xs), idx.data_ptr(), K, normals.data_ptr(),
+                                           eig.data_ptr(), _lib.stream_ptr(xp.device)), "rldm_knn_normals")
+    out = _per_pair(normals, starts)
+    return (out, _per_pair(eig, starts)) if return_eigenvalues else out
+
+
+def _normals_host_one(pts, idx):
+    import numpy as np
+    pts = np.asarray(pts)[:, :3].astype(np.float32).astype(np.float64)
+    idx = np.asarray(idx).reshape(len(pts), -1)
+    valid = (idx >= 0) & (idx < len(pts))
+    w = np.concatenate([np.ones((len(pts), 1)), valid.astype(np.float64)], 1)             # the point itself, then its neighbours
+    nb = np.concatenate([pts[:, None, :], pts[np.where(valid, idx, 0)]], 1)
+    m = w.sum(1)
+    cen = (nb * w[..., None]).sum(1) / m[:, None]
+    d = (nb - cen[:, None, :]) * w[..., None]
+    cov = np.einsum("nki,nkj->nij", d, d) / m[:, None, None]
+    lam, vec = np.linalg.eigh(cov)                       # ascending
+    n = vec[:, :, 0]
+    dot = (n * pts).sum(1)
+    nz = n != 0.0
+    lead = np.take_along_axis(n, nz.argmax(1)[:, None], 1)[:, 0]
+    flip = (dot > 0.0) | ((dot == 0.0) & (lead < 0.0))
+    n = np.where(flip[:, None], -n, n) + 0.0
+    few = m < 3
+    n[few], lam[few] = 0.0, 0.0
+    return n, lam
+
+
+def estimate_normals_host(x, idx, return_eigenvalues=False):
+    """The numpy statement of estimate_normals given the neighbour indices (self_neighbours' idx, or knn_points_host's with
+    exclude_self): lists of (n_i, >= 3) arrays and of (n_i, K) index arrays (or one of each) -> a list of (n_i, 3) fp64
+    normals.  Covariance in fp64, np.linalg.eigh, the same orientation rule."""
+    import numpy as np
+    xs = _voxel_host_clouds(x, "x")
+    ids = [np.asarray(idx)] if len(xs) == 1 and np.asarray(idx[0]).ndim == 1 else [np.asarray(i) for i in idx]
+    if len(ids) != len(xs) or any(len(i) != len(c) for i, c in zip(ids, xs)):
+        raise ValueError("idx does not match x")
+    out = [_normals_host_one(c, i) for c, i in zip(xs, ids)]
+    return ([o[0] for o in out], [o[1] for o in out]) if return_eigenvalues else [o[0] for o in out]
+
+
+def _normal_lists(normals, clouds, name):
+    """A padded (N, P, 3) tensor or a list of (n_i, 3) tensors -> the list of (n_i, 3) fp64 device tensors that belongs to
+    `clouds`; ValueError when the shapes do not match them."""
+    if torch.is_tensor(normals):
+        if normals.dim() != 3 or normals.shape[0] != len(clouds) or normals.shape[2] != 3 or \
+                any(c.shape[0] > normals.shape[1] for c in clouds):
+            raise ValueError(f"{name} must be (N, P, 3) like its clouds, got {tuple(normals.shape)}")
+        out = [normals[i, :c.shape[0]] for i, c in enumerate(clouds)]
+    else:
+        out = list(normals)
+        if len(out) != len(clouds) or any((not torch.is_tensor(n)) or tuple(n.shape) != (c.shape[0], 3) for n, c in zip(out, clouds)):
+            raise ValueError(f"{name} must hold one (n_i, 3) tensor per cloud")
+    for n in out:
+        if not n.is_cuda:
+            raise RuntimeError("normals must live on the GPU (rangeldm_amd has no CPU path)")
+    return [n.detach().double() for n in out]
+
+
+def _normal_consistency(r, xn, yn):
+    """pytorch3d's loss_normals per pair (fp64 device (N,)) from one _nn_index search and the two sides' normals: each pair is
+    reduced on its own, in a fixed order."""
+    import torch.nn.functional as F
+    out = []
+    for nx, ny, xi, yi in zip(xn, yn, _per_pair(r.xi, r.xs), _per_pair(r.yi, r.ys)):
+        tx = 1.0 - F.cosine_similarity(nx, ny[xi], dim=1, eps=1e-6).abs()
+        ty = 1.0 - F.cosine_similarity(ny, nx[yi], dim=1, eps=1e-6).abs()
+        out.append(tx.sum() / tx.shape[0] + ty.sum() / ty.shape[0])
+    return torch.stack(out)
+
+
+def _plane_term(a, b, bn, j):
+    """mean over the points of a of ((a_i - b_j(i)) . bn_j(i))^2 in fp64, torch or numpy alike."""
+    d, n = a - b[j], bn[j]
+    s = (d[:, 0] * n[:, 0] + d[:, 1] * n[:, 1]) + d[:, 2] * n[:, 2]
+    return (s * s).sum() / a.shape[0]
+
+
+def plane_scores(x, y, K=16, x_lengths=None, y_lengths=None):
+    """What the distance to the nearest SAMPLE cannot tell apart, per pair: a dict of fp64 device (N,) tensors
+
+        "cd"                  pair_scores' "cd" (the same bits)
+        "cd_plane"            mean_i ((x_i - y_j(i)) . n_y[j(i)])^2 + mean_j ((y_j - x_i(j)) . n_x[i(j)])^2: the squared distance
+                              to the tangent plane at the nearest point, which does not charge a point for lying on the right
+                              surface between the other cloud's beams
+        "normal_consistency"  chamfer_distance's loss_normals: mean_i (1 - |cos(n_x[i], n_y[j(i)])|) + the mirror
+
+    j(i) / i(j) are nearest_neighbours' indices, n_x / n_y estimate_normals(K) of each side, all arithmetic fp64.  A pair's
+    values do not depend on the other pairs of the call.  plane_scores_host is the numpy statement."""
+    K = _knn_k(K)
+    xs, ys = _clouds(x, x_lengths, "x"), _clouds(y, y_lengths, "y")
+    if len(xs) != len(ys):
+        raise ValueError(f"{len(xs)} x clouds against {len(ys)} y clouds")
+    xn, yn = estimate_normals(xs, K), estimate_normals(ys, K)
+    r = _nn_index(xs, ys)
+    plane = []
+    for a, b, an, bn, xi, yi in zip(xs, ys, xn, yn, _per_pair(r.xi, r.xs), _per_pair(r.yi, r.ys)):
+        a, b = a.detach()[:, :3].float().double(), b.detach()[:, :3].float().double()
+        plane.append(_plane_term(a, b, bn, xi) + _plane_term(b, a, an, yi))
+    return {"cd": _chamfer_means(r), "cd_plane": torch.stack(plane), "normal_consistency": _normal_consistency(r, xn, yn)}
+
+
+def _cosine_host(a, b, eps=1e-6):
+    import numpy as np
+    na, nb = np.sqrt((a * a).sum(1)), np.sqrt((b * b).sum(1))
+    return (a * b).sum(1) / (np.maximum(na, eps) * np.maximum(nb, eps))
+
+
+def normal_consistency_host(x, y, x_normals, y_normals):
+    """The numpy statement of chamfer_distance's loss_normals per pair: fp64 (N,)."""
+    import numpy as np
+    _, xi, _, yi = nearest_neighbours_host(x, y)
+    out = []
+    for nx, ny, i, j in zip(x_normals, y_normals, xi, yi):
+        nx, ny = np.asarray(nx, np.float64), np.asarray(ny, np.float64)
+        tx, ty = 1.0 - np.abs(_cosine_host(nx, ny[i])), 1.0 - np.abs(_cosine_host(ny, nx[j]))
+        out.append(tx.sum() / len(tx) + ty.sum() / len(ty))
+    return np.array(out, np.float64)
+
+
+def plane_scores_host(x, y, K=16):
+    """The numpy statement of plane_scores: the same dict with fp64 numpy arrays (normals from estimate_normals_host on
+    knn_points_host's self-excluding indices)."""
+    import numpy as np
+    K = _knn_k(K)
+    xs, ys = _voxel_host_clouds(x, "x"), _voxel_host_clouds(y, "y")
+    xn = estimate_normals_host(xs, knn_points_host(xs, xs, K, exclude_self=True)[1])
+    yn = estimate_normals_host(ys, knn_points_host(ys, ys, K, exclude_self=True)[1])
+    xd, xi, yd, yi = nearest_neighbours_host(xs, ys)
+    cd = [a.astype(np.float64).sum() / len(a) + b.astype(np.float64).sum() / len(b) for a, b in zip(xd, yd)]
+    plane = []
+    for a, b, an, bn, i, j in zip(xs, ys, xn, yn, xi, yi):
+        a, b = (c[:, :3].astype(np.float32).astype(np.float64) for c in (a, b))
+        plane.append(_plane_term(a, b, bn, i) + _plane_term(b, a, an, j))
+    return {"cd": np.array(cd, np.float64), "cd_plane": np.array(plane, np.float64),
+            "normal_consistency": normal_consistency_host(xs, ys, xn, yn)}
+
+
+def _std_ratio(std_ratio):
+    import math
+    try:
+        v = float(std_ratio)
+    except (TypeError, ValueError):
+        raise ValueError(f"std_ratio must be a finite number, got {std_ratio!r}") from None
+    if not math.isfinite(v):
+        raise ValueError(f"std_ratio must be finite, got {std_ratio!r}")
+    return v
+
+
+def _outlier_rule(d2, idx, ratio, sqrt, where, zero):
+    """(mask, mean neighbour distance per point, threshold) of one cloud from its self_neighbours rows and a zero array of
+    their shape, torch or numpy alike."""
+    valid = idx >= 0
+    count = valid.sum(1)
+    dist = sqrt(where(valid, d2, zero))                  # an empty slot (+inf, -1) adds nothing
+    mean = dist.sum(1) / where(count > 0, count, count + 1)
+    mu = mean.sum() / mean.shape[0]
+    sd = sqrt(((mean - mu) * (mean - mu)).sum() / mean.shape[0])
+    thr = mu + ratio * sd
+    return mean > thr, mean, thr
+
+
+def statistical_outliers(x, K=20, std_ratio=2.0, x_lengths=None, return_terms=False):
+    """Open3D's remove_statistical_outlier rule (the isolated floating points a sampler leaves between objects): a list of
+    bool device masks, True where a point's mean distance to its K nearest neighbours (self_neighbours; the fp64 mean over the
+    valid slots of sqrt(d^2)) exceeds the cloud's mean of those means plus std_ratio times their population standard
+    deviation.  return_terms=True appends the lists of per-point means and of the clouds' thresholds (fp64).
+    statistical_outliers_host is the numpy statement."""
+    K, ratio = _knn_k(K), _std_ratio(std_ratio)
+    d2, idx, _, _, _, starts = _knn(_clouds(x, x_lengths, "x"), None, K, True)
+    out = [_outlier_rule(d.double(), i, ratio, torch.sqrt, torch.where, torch.zeros_like(d, dtype=torch.float64)) for d, i in zip(_per_pair(d2, starts), _per_pair(idx, starts))]
+    masks = [o[0] for o in out]
+    return (masks, [o[1] for o in out], [o[2] for o in out]) if return_terms else masks
+
+
+def statistical_outliers_host(x, K=20, std_ratio=2.0, return_terms=False):
+    """The numpy statement of statistical_outliers: lists of (n_i, >= 3) arrays (or one array) -> a list of bool arrays."""
+    import numpy as np
+    K, ratio = _knn_k(K), _std_ratio(std_ratio)
+    xs = _voxel_host_clouds(x, "x")
+    d2, idx = knn_points_host(xs, xs, K, exclude_self=True)
+    out = [_outlier_rule(d.astype(np.float64), i, ratio, np.sqrt, np.where, np.zeros(d.shape)) for d, i in zip(d2, idx)]
+    masks = [o[0] for o in out]
+    return (masks, [o[1] for o in out], [float(o[2]) for o in out]) if return_terms else masks
 
 
 # ---- voxel occupancy: IoU / precision / recall / F1 of the occupied voxels (rangeldm_amd/csrc/voxel.hip) ------------------
