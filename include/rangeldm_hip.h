@@ -688,6 +688,32 @@ int rldm_train_reduce_pending(void);   /* 1 while a deferred reduction waits for
 int rldm_train_wgrad_group(int on);
 int rldm_train_wgrad_group_flush(void);
 int rldm_train_wgrad_group_pending(void);   /* queued layers (tests) */
+/* Deterministic mode: a process-wide switch for one caller thread, read when a call is enqueued (so a captured graph keeps the mode
+ * it was captured in).  _enabled returns the current value.  With the switch on, the outputs of every rldm_train_* entry point are a
+ * function of its inputs and shapes alone, bit for bit: no floating-point atomics (global or LDS) run, every sum that crosses
+ * workgroups goes through partial rows in scratch that are added in index order, nothing depends on workgroup arrival order, on other
+ * streams or on graph replay.  It costs launches and speed; default-mode arithmetic is untouched.  What changes:
+ *   conv / conv_fused      never split K (rldm_train_conv_splits returns 1): one workgroup contracts all of K in stage order.
+ *   GroupNorm statistics   ONE canonical order for the (sum, sumsq) pair of an (image, channel), whoever produces it -- the epilogue
+ *                          of rldm_train_conv_fused for its stored y, or rldm_train_chan_stats:  pixel index p = w * H + h inside the
+ *                          image; partial t covers pixels [64 t, 64 t + 64) (the last one may be short); inside a partial, lane k of
+ *                          16 starts from +0 and adds x[p] (sumsq: the fp32-rounded product x[p] * x[p], never fused with the sum) for
+ *                          p = 64 t + k + 16 j, j = 0, 1, 2, 3; the partial is ((((0 + lane 0) + lane 1) + ...) + lane 15); the pair is
+ *                          (((0 + partial 0) + partial 1) + ...) and is ADDED to what cs holds.  The (sum dz, sum dz xhat) pairs of a
+ *                          data-gradient epilogue (gs_out) follow the same order.  train_ops.chan_stats_host restates it in numpy.
+ *   colsum, and the rows / total of wgrad_bias / wgrad_fused (which then sum the fp32 dy, not the staged bf16 tile)
+ *                          slab z covers pixels [256 z, 256 z + 256) of an image; lane k of 16 adds pixels 256 z + k + 16 j in order
+ *                          of j; lanes added k = 0 .. 15; image sum = slabs added in order; rows[b] (+)= image sum; total += the image
+ *                          sums added b = 0 .. B - 1 (from +0).
+ *   weight gradients       always partial tiles per K slice, added in slice order (no atomics into dw).
+ *   gn_forward / backward  the one-block-per-(image, group) kernels at every size; d gamma / d beta per image, added in image order.
+ *   mse / sqnorm           block i's fp64 partial as in the default mode (mse: element i * 256 + t per thread; sqnorm: thread t of
+ *                          block i adds g[(i + j nb) * 256 + t]^2 in order of j, nb = min(ceil(n / 256), 2048) blocks), a block's 256
+ *                          values added as a binary tree (lanes l and l ^ 32, then ^ 16 .. ^ 1, then the four waves in order); the
+ *                          result = the same two steps over the block partials (thread t adds partials t, t + 256, ... first).
+ * The RCCL all-reduce of a multi-rank step is outside this guarantee. */
+int rldm_train_deterministic(int on);
+int rldm_train_deterministic_enabled(void);
 /* cs [B][C][2] += (sum, sumsq) per (image, channel) of x [B][npix][C]: for tensors no fused conv produced. */
 int rldm_train_chan_stats(const float* x, int B, int npix, int C, float* cs, void* stream);
 /* dx = rstd (gamma dz - mean_g(gamma dz) - xhat mean_g(gamma dz xhat)) + res, the GroupNorm over cat(x0, x1) [C0 | C - C0

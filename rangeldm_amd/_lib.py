@@ -240,6 +240,8 @@ PROTOTYPES = {
     "rldm_train_wgrad_group": (C.c_int, [C.c_int]),
     "rldm_train_wgrad_group_flush": (C.c_int, []),
     "rldm_train_wgrad_group_pending": (C.c_int, []),
+    "rldm_train_deterministic": (C.c_int, [C.c_int]),
+    "rldm_train_deterministic_enabled": (C.c_int, []),
     "rldm_train_reduce_pending": (C.c_int, []),
     "rldm_train_chan_stats": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rldm_train_gn_backward_apply": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P,

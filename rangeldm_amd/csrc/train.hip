@@ -19,6 +19,9 @@
 //   elementwise           add, channel copy (concat / split), 2x2 sum (nearest-x2 backward), SiLU, sinusoidal timestep
 //                         embedding, input packing, MSE loss + gradient, sum of squares, AdamW (+ clip scale + EMA),
 //                         weight repacking.
+//   deterministic mode    rldm_train_deterministic (include/rangeldm_hip.h): DET instantiations without floating-point atomics -- convs
+//                         never split K, cross-workgroup sums go through partial rows folded in index order (tr_fold_rows_kernel,
+//                         tr_colsum_finish_kernel, tr_fold_double_kernel), one canonical order for the GroupNorm statistics.
 #include "common.h"
 #include "../../include/rangeldm_hip.h"
 
@@ -110,11 +113,24 @@ struct TrFuse {
     const float* gcs0; const float* gcs1;          //   gs_out += (sum dz, sum dz xhat)
     const float* ggamma; const float* gbeta; int gsilu, ggroups; float geps;
     float* gs_out;
-    unsigned* tickets;                             // split-K launches: a zeroed arrival counter per output tile (left zeroed)
+    union {
+        unsigned* tickets;                         // split-K launches: a zeroed arrival counter per output tile (left zeroed)
+        float* part;                               // deterministic instances (never split): the tiles' partial rows [P / 64][N][2]
+    };
     // a rider: the reduction of the PREVIOUS weight-gradient launch's partial tiles (it does not depend on this conv, and as a launch of
     // its own it cost ~10 us 47 times per step): run by extra z-planes of this launch's grid (rz0 = the first of them; rblocks = 0: none)
     const float* rpart; float* rdw; int rslices, rN, rCin, rtaps, rz0, rblocks;
 };
+
+// (deterministic mode) one fp32 operation, rounded on its own: a product never fuses with the sum it feeds, so a host restates the sums
+__device__ __forceinline__ float det_add(const float a, const float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ float det_mul(const float a, const float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
 
 // (v_exp_f32 + v_rcp_f32: the IEEE division of 1.f / x costs ten more instructions per element of every staged tile)
 __device__ inline float tr_sigmoid(float z) { return __builtin_amdgcn_rcpf(1.f + __expf(-z)); }
@@ -167,7 +183,7 @@ __device__ inline void tr_gn_coeffs_tile(float4* ce, int BN, int n0, const float
 // thread (channel cl = tid % BN, pixel group tid / BN) walks its pixels: + bias / row / residual (add_terms), the GroupNorm-backward
 // transform where asked, the store (coalesced along the channels), and the per-channel sums, which reach cs_out / gs_out as one atomic
 // per (workgroup, channel, component).  colacc: [2 * BN] floats of LDS.
-template <int BN>
+template <int BN, bool DET = false>
 __device__ inline void tr_tile_epilogue(const float* tile, float* colacc, const float4* ce, const TrConv& p, const TrFuse& f, int px0,
                                         int n0, int img, bool add_terms, bool store_y) {
     // thread (channel quad cq = tid % (BN / 4), pixel group tid / (BN / 4)): 16-byte global accesses, all of a thread's loads in flight
@@ -178,6 +194,12 @@ __device__ inline void tr_tile_epilogue(const float* tile, float* colacc, const 
     for (int e = tid; e < 2 * BN; e += NT) colacc[e] = 0.f;
     __syncthreads();
     f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
+    // (DET) the canonical partial of rldm_train_deterministic: lane k of 16 adds the tile's pixels k, k + 16, k + 32, k + 48 in that order;
+    // a thread walks pixels pg + u NPG, so it holds lanes pg + j NPG (NL = 1 or 2 of them)
+    constexpr int NL = DET ? 16 / NPG : 1;
+    f32x4 d1[NL], d2[NL];
+#pragma unroll
+    for (int j = 0; j < NL; ++j) { d1[j] = f32x4{0.f, 0.f, 0.f, 0.f}; d2[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     if (ch < N) {                                                   // (N % 4 == 0: a quad is inside or outside)
         f32x4 addc = {0.f, 0.f, 0.f, 0.f};
         if (add_terms) {
@@ -218,16 +240,51 @@ __device__ inline void tr_tile_epilogue(const float* tile, float* colacc, const 
                         const float z = g * c4[q].x + c4[q].y, sg = tr_sigmoid(z);
                         v[q] *= sg * (1.f + z * (1.f - sg));
                     }
-                    s1[q] += v[q];
-                    s2[q] += v[q] * xh;
+                    if constexpr (DET) {
+                        d1[u % NL][q] = det_add(d1[u % NL][q], v[q]);
+                        d2[u % NL][q] = det_add(d2[u % NL][q], det_mul(v[q], xh));
+                    } else {
+                        s1[q] += v[q];
+                        s2[q] += v[q] * xh;
+                    }
                 }
                 *reinterpret_cast<f32x4*>(ydst + gp * N) = v;
             } else {
-                s1 += v;
-                s2 += v * v;
+                if constexpr (DET) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        d1[u % NL][q] = det_add(d1[u % NL][q], v[q]);
+                        d2[u % NL][q] = det_add(d2[u % NL][q], det_mul(v[q], v[q]));
+                    }
+                } else {
+                    s1 += v;
+                    s2 += v * v;
+                }
                 if (store_y) *reinterpret_cast<f32x4*>(ydst + gp * N) = v;
             }
         }
+    }
+    if constexpr (DET) {
+        // the 16 lanes through LDS (over the tile, which every thread has read by now), folded k = 0 .. 15 by one thread per (channel,
+        // component); the tile's row of partials goes to scratch and tr_fold_rows_kernel adds the tiles of an image in tile order
+        float* lanes = const_cast<float*>(tile);                    // [16][2 * BN]  (16 * 2 BN <= 64 (BN + 1) floats)
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < NL; ++j)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                lanes[(pg + j * NPG) * (2 * BN) + 2 * (cl + q)] = d1[j][q];
+                lanes[(pg + j * NPG) * (2 * BN) + 2 * (cl + q) + 1] = d2[j][q];
+            }
+        __syncthreads();
+        for (int e = tid; e < 2 * BN; e += NT) {
+            const int c2 = n0 + (e >> 1);
+            float a = 0.f;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) a = det_add(a, lanes[k * (2 * BN) + e]);
+            if (c2 < N) f.part[((size_t)(px0 >> 6) * N + c2) * 2 + (e & 1)] = a;
+        }
+        return;
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -327,7 +384,7 @@ __global__ __launch_bounds__(256) void tr_conv_kernel(const TrConv p) {
 // been copied to LDS) was measured on the low-resolution launches (2 - 9 stages per workgroup) and changes nothing: a 4-stage 1x1 conv of
 // 16 workgroups takes 9.6 us against 9.4 us, the 3x3 convs of the 64x4 level 19.0 against 21.6 us, the step 798 against 796 samples/s --
 // those launches are bound by launch + first-touch + drain latency, not by the per-stage round trip.  Not instantiated.
-template <int CK, int BN, bool FU = false, int D = 1>
+template <int CK, int BN, bool FU = false, int D = 1, bool DET = false>
 __global__ __launch_bounds__(256) void tr_conv_lds_kernel(const TrConv p, const TrFuse f) {
     static_assert(BN == 64 || BN == 128, "channel tile");
     constexpr int TPR = 256 / BN, NR = BN / 64;     // threads per weight row of a stage; 32-channel MFMA rows per wave
@@ -488,7 +545,7 @@ __global__ __launch_bounds__(256) void tr_conv_lds_kernel(const TrConv p, const 
             }
         }
     }
-    if (ksplit > 1) {
+    if (!DET && ksplit > 1) {                       // (the deterministic instances are never launched split: no atomics in them)
         // through LDS so that the atomics run along the channels (one cache line per 32 lanes; lane = pixel would touch 64 lines
         // per instruction: measured 4x slower than not splitting at all)
         float* tile = reinterpret_cast<float*>(raw);
@@ -569,7 +626,7 @@ __global__ __launch_bounds__(256) void tr_conv_lds_kernel(const TrConv p, const 
 #pragma unroll
                 for (int r = 0; r < 16; ++r) trow[32 * h + 8 * (r >> 2) + 4 * kg + (r & 3)] = h ? acc1[r] : acc0[r];
             __syncthreads();
-            tr_tile_epilogue<BN>(tile, sCol, sCe, p, f, px0, n0, img, true, true);
+            tr_tile_epilogue<BN, DET>(tile, sCol, sCe, p, f, px0, n0, img, true, true);
             return;
         }
     }
@@ -615,7 +672,7 @@ __global__ __launch_bounds__(256) void tr_conv_lds_kernel(const TrConv p, const 
 // (64 / H + 2) azimuth columns x (H + 2) beams, circular in azimuth, zero rows above and below -- and the nine taps read
 // their B fragments from it at a uniform row offset dw * (H + 2) + dh; only the weight tile is staged per tap.  x traffic
 // and fp32->bf16 conversions drop 5x.  Stage order: chunk-major, tap fastest.
-template <int BN, bool FU = false>
+template <int BN, bool FU = false, bool DET = false>
 __global__ __launch_bounds__(256) void tr_conv_halo_kernel(const TrConv p, const TrFuse f) {
     static_assert(BN == 64 || BN == 128, "channel tile");
     constexpr int CK = 64;
@@ -796,7 +853,7 @@ __global__ __launch_bounds__(256) void tr_conv_halo_kernel(const TrConv p, const
 #pragma unroll
                 for (int r = 0; r < 16; ++r) trow[32 * h + 8 * (r >> 2) + 4 * kg + (r & 3)] = h ? acc1[r] : acc0[r];
             __syncthreads();
-            tr_tile_epilogue<BN>(tile, sCol, sCe, p, f, px0, n0, b, true, true);
+            tr_tile_epilogue<BN, DET>(tile, sCol, sCe, p, f, px0, n0, b, true, true);
             return;
         }
     }
@@ -1453,6 +1510,9 @@ __global__ __launch_bounds__(256) void tr_wgrad_reduce_kernel(const float* __res
 // rows[b][n] += sum over the pixels of image b of dy[p][n]; total[n] += the same over all images.  grid (64-channel tiles,
 // images, 256-pixel slabs), 256 threads = 16 pixel lanes x 16 channel quads (16-byte loads when N % 4 == 0): fp32 atomics
 // into buffers the caller zeroed (rows) / accumulates into (total = bias gradient).
+// DET (rldm_train_deterministic): the slab's sums are stored as a partial row instead -- rows = part [B][slabs][N] -- and
+// tr_colsum_finish_kernel adds the slabs of an image, then the images, in index order.
+template <bool DET = false>
 __global__ __launch_bounds__(256) void tr_colsum_kernel(const float* __restrict__ dy, int npix, int N, float* __restrict__ rows,
                                                         int rows_ld, float* __restrict__ total) {
     __shared__ float sh[16][68];
@@ -1483,10 +1543,45 @@ __global__ __launch_bounds__(256) void tr_colsum_kernel(const float* __restrict_
             float v = 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) v += sh[r][threadIdx.x];
-            if (rows) unsafeAtomicAdd(rows + (size_t)b * rows_ld + c, v);
-            if (total) unsafeAtomicAdd(total + c, v);
+            if constexpr (DET) rows[((size_t)b * gridDim.z + blockIdx.z) * N + c] = v;
+            else {
+                if (rows) unsafeAtomicAdd(rows + (size_t)b * rows_ld + c, v);
+                if (total) unsafeAtomicAdd(total + c, v);
+            }
         }
     }
+}
+
+// (deterministic mode) image sums = the slabs of part [B][S][N] added in slab order; rows[b][c] (+)= image sum; total[c] += the image
+// sums added in image order.  One thread per channel.
+__global__ __launch_bounds__(256) void tr_colsum_finish_kernel(const float* __restrict__ part, int B, int S, int N, float* __restrict__ rows,
+                                                               int rows_ld, int rows_accumulate, float* __restrict__ total) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= N) return;
+    float t = 0.f;
+    for (int b = 0; b < B; ++b) {
+        float a = 0.f;
+        for (int z = 0; z < S; ++z) a = det_add(a, part[((size_t)b * S + z) * N + c]);
+        if (rows) {
+            float* d = rows + (size_t)b * rows_ld + c;
+            *d = rows_accumulate ? det_add(*d, a) : a;
+        }
+        t = det_add(t, a);
+    }
+    if (total) total[c] = det_add(total[c], t);
+}
+
+// (deterministic mode) out[o][i] (+)= part[o][0][i] + part[o][1][i] + ... + part[o][nparts - 1][i], added in that order from +0
+__global__ __launch_bounds__(256) void tr_fold_rows_kernel(const float* __restrict__ part, int outer, int nparts, int inner,
+                                                           float* __restrict__ out, int out_ld, int accumulate) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)outer * inner) return;
+    const int o = (int)(idx / inner), i = (int)(idx % inner);
+    const float* src = part + (size_t)o * nparts * inner + i;
+    float a = 0.f;
+    for (int t = 0; t < nparts; ++t) a = det_add(a, src[(size_t)t * inner]);
+    float* d = out + (size_t)o * out_ld + i;
+    *d = accumulate ? det_add(*d, a) : a;
 }
 
 // ---- GroupNorm ----------------------------------------------------------------------------------------------------------
@@ -1674,6 +1769,8 @@ __global__ __launch_bounds__(256) void tr_gn_bwd_apply_vec_kernel(const float* _
 
 // grid (groups, B): sums[b][g] = (sum dz gamma, sum dz gamma xhat); dgamma[c] += sum dz xhat, dbeta[c] += sum dz
 // (dz = dy * act'(z)); the first T = 256 - 256 % cpg threads stride by T, so thread t always meets channel t % cpg
+// DET (rldm_train_deterministic): dgamma / dbeta = partial rows [B][C], added over the images in image order by tr_fold_rows_kernel
+template <bool DET = false>
 __global__ __launch_bounds__(256) void tr_gn_bwd_reduce_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                                const float2* __restrict__ stats, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, int npix, int C, int groups, int silu,
@@ -1710,8 +1807,13 @@ __global__ __launch_bounds__(256) void tr_gn_bwd_reduce_kernel(const float* __re
     if (threadIdx.x < cpg) {
         float tg = 0.f, tb = 0.f;
         for (int t = threadIdx.x; t < TT; t += cpg) { tg += shg[t]; tb += shb[t]; }
-        unsafeAtomicAdd(dgamma + g * cpg + threadIdx.x, tg);
-        unsafeAtomicAdd(dbeta + g * cpg + threadIdx.x, tb);
+        if constexpr (DET) {
+            dgamma[(size_t)b * C + g * cpg + threadIdx.x] = tg;
+            dbeta[(size_t)b * C + g * cpg + threadIdx.x] = tb;
+        } else {
+            unsafeAtomicAdd(dgamma + g * cpg + threadIdx.x, tg);
+            unsafeAtomicAdd(dbeta + g * cpg + threadIdx.x, tb);
+        }
     }
     if (threadIdx.x == 0) sums[b * groups + g] = make_float2((float)s1, (float)s2);
 }
@@ -1836,6 +1938,45 @@ __global__ __launch_bounds__(256) void tr_chan_stats_kernel(const float* __restr
     }
     __syncthreads();
     for (int e = threadIdx.x; e < 2 * C; e += 256) unsafeAtomicAdd(cs + (size_t)b * C * 2 + e, sacc[e]);
+}
+
+// (deterministic mode) the canonical partials of the GroupNorm statistics (include/rangeldm_hip.h, rldm_train_deterministic): partial t
+// of image b covers pixels [64 t, 64 t + 64); lane k of 16 adds x (and the rounded x * x) of pixels 64 t + k + 16 j, j = 0 .. 3, in
+// that order; the lanes are added k = 0 .. 15: exactly what tr_tile_epilogue<BN, true> leaves for the tile a fused conv stored.
+// part [B][T][C][2]; grid (T, B, C / 64 rounded up), thread (lane tid / 16, channel quad tid % 16).
+__global__ __launch_bounds__(256) void tr_chan_stats_det_kernel(const float* __restrict__ x, int npix, int C, float* __restrict__ part) {
+    __shared__ float lanes[16][128];
+    const int t = blockIdx.x, b = blockIdx.y, k = threadIdx.x >> 4, cq = threadIdx.x & 15;
+    const int ch = blockIdx.z * 64 + 4 * cq;
+    f32x4 s = {0.f, 0.f, 0.f, 0.f}, ss = {0.f, 0.f, 0.f, 0.f};
+    if (ch < C) {                                                   // (C % 4 == 0: a quad is inside or outside)
+        const float* base = x + (size_t)b * npix * C + ch;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int px = 64 * t + k + 16 * j;
+            if (px < npix) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(base + (size_t)px * C);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    s[q] = det_add(s[q], v[q]);
+                    ss[q] = det_add(ss[q], det_mul(v[q], v[q]));
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        lanes[k][2 * (4 * cq + q)] = s[q];
+        lanes[k][2 * (4 * cq + q) + 1] = ss[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < 128) {
+        const int c2 = blockIdx.z * 64 + (threadIdx.x >> 1);
+        float a = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) a = det_add(a, lanes[r][threadIdx.x]);
+        if (c2 < C) part[(((size_t)b * gridDim.x + t) * C + c2) * 2 + (threadIdx.x & 1)] = a;
+    }
 }
 
 // dx = rstd (gamma dz - s1 / n - xhat s2 / n) [+ res] of a GroupNorm over cat(x0, x1), from dz = dy act'(z) (stored by the data-gradient
@@ -2003,6 +2144,8 @@ __global__ __launch_bounds__(256) void tr_unpack_kernel(const float* __restrict_
 
 // loss = mean_b( weight[b] * mean_{c,w,h} (pred - target)^2 ); dpred = weight[b] * 2 (pred - target) / (B * C * W * H)
 // pred NHWC, target NCHW; loss accumulated in fp64
+// DET (rldm_train_deterministic): loss = one partial per block, added by tr_fold_double_kernel
+template <bool DET = false>
 __global__ __launch_bounds__(256) void tr_mse_kernel(const float* __restrict__ pred, const float* __restrict__ target,
                                                      const float* __restrict__ weight, int B, int C, int W, int H,
                                                      float* __restrict__ dpred, double* __restrict__ loss) {
@@ -2022,15 +2165,32 @@ __global__ __launch_bounds__(256) void tr_mse_kernel(const float* __restrict__ p
         part = (double)wb * (double)d * (double)d / (double)total;
     }
     part = block_sum_d(part, sh);
-    if (threadIdx.x == 0) unsafeAtomicAdd(loss, part);
+    if (threadIdx.x == 0) {
+        if constexpr (DET) loss[blockIdx.x] = part;
+        else unsafeAtomicAdd(loss, part);
+    }
 }
 
+template <bool DET = false>
 __global__ __launch_bounds__(256) void tr_sqnorm_kernel(const float* __restrict__ g, size_t n, double* __restrict__ out) {
     __shared__ double sh[4];
     double acc = 0.0;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) acc += (double)g[i] * g[i];
     acc = block_sum_d(acc, sh);
-    if (threadIdx.x == 0) unsafeAtomicAdd(out, acc);
+    if (threadIdx.x == 0) {
+        if constexpr (DET) out[blockIdx.x] = acc;
+        else unsafeAtomicAdd(out, acc);
+    }
+}
+
+// (deterministic mode) *out = the n block partials: thread t of 256 adds part[t], part[t + 256], ... in that order, then block_sum_d
+// (a fixed tree).  One block.
+__global__ __launch_bounds__(256) void tr_fold_double_kernel(const double* __restrict__ part, int n, double* __restrict__ out) {
+    __shared__ double sh[4];
+    double a = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) a += part[i];
+    a = block_sum_d(a, sh);
+    if (threadIdx.x == 0) *out = a;
 }
 
 // torch.optim.AdamW step on flat buffers with the clip_grad_norm_ coefficient folded in, then diffusers EMAModel.step
@@ -2314,6 +2474,16 @@ inline unsigned nblk(size_t n) { return (unsigned)((n + 255) / 256); }
 
 extern "C" {
 
+// rldm_train_deterministic: read by every entry point when its launches are enqueued (one caller thread)
+static int g_deterministic = 0;
+
+int rldm_train_deterministic(int on) {
+    g_deterministic = on ? 1 : 0;
+    return 0;
+}
+
+int rldm_train_deterministic_enabled(void) { return g_deterministic; }
+
 // launch shape of the LDS-staged conv: narrow (64-channel) tile? how many K splits?  (shared by rldm_train_conv and
 // rldm_train_conv_splits, which lets the host hand out pre-zeroed outputs to the split launches)
 static void conv_lds_plan(int P, int N, int Cin, int taps, bool* narrow_out, int* ksplit_out) {
@@ -2329,7 +2499,8 @@ static void conv_lds_plan(int P, int N, int Cin, int taps, bool* narrow_out, int
     constexpr int kTarget = 512, kMinStages = 3;
     const int niter = taps * (Cin / (Cin % 64 == 0 ? 64 : 32));
     const long long wgs = gx * gy;
-    const int ksplit = wgs > 192 ? 1 : (int)std::min<long long>((kTarget + wgs - 1) / wgs, niter / kMinStages);
+    // (deterministic mode: never split -- a workgroup contracts all of K in stage order)
+    const int ksplit = wgs > 192 || g_deterministic ? 1 : (int)std::min<long long>((kTarget + wgs - 1) / wgs, niter / kMinStages);
     *narrow_out = narrow;
     *ksplit_out = std::max(1, std::min(ksplit, niter));
 }
@@ -2350,10 +2521,15 @@ int rldm_train_conv_splits(const rldm_train_conv_desc* d, int rowadd_ld) {
 // another device is refused instead of handing it a pointer into the first device's memory.  One caller thread; launches are stream
 // ordered, so consecutive launches may share a buffer.  A buffer grows outside stream captures only (the first, eager, step of a shape
 // sizes it), and the block it outgrew is kept, never freed: a step graph captured at an earlier, smaller shape still holds its address.
-enum TrScratchSlot { kFuseTickets, kGnAccumulators, kWgradPartials, kGroupPartials, kGroupTickets, kScratchSlots };
+enum TrScratchSlot { kFuseTickets, kGnAccumulators, kWgradPartials, kGroupPartials, kGroupTickets, kDetPartials, kScratchSlots };
 
 // -> *out: at least `bytes` of the slot's buffer; `zeroed`: a new block is zeroed once (tickets / accumulators, which every user leaves
 // zeroed).  Growth rounds up to `min_bytes`.
+static int tr_scratch(TrScratchSlot slot, size_t bytes, size_t min_bytes, bool zeroed, hipStream_t st, void** out);
+
+// the partial rows of the deterministic mode's sums (written and folded by consecutive launches of one call)
+static int det_partials(size_t bytes, hipStream_t st, void** out) { return tr_scratch(kDetPartials, bytes, 1u << 20, false, st, out); }
+
 static int tr_scratch(TrScratchSlot slot, size_t bytes, size_t min_bytes, bool zeroed, hipStream_t st, void** out) {
     static int dev0 = -1;
     static void* buf[kScratchSlots] = {};
@@ -2497,9 +2673,13 @@ static int train_conv_impl(const rldm_train_conv_desc* d, const rldm_train_fuse*
                            reinterpret_cast<void**>(&f.tickets)))
                 return 1;
         } else if (fu && (f.cs_out || f.gs_out)) {
-            RLDM_REQUIRE(!accumulate, "rldm_train_conv_fused: the fused epilogue writes y (no accumulation)");
+            // (deterministic mode: a caller that asked rldm_train_conv_splits with the mode off may hand in a zeroed y; it is written)
+            RLDM_REQUIRE(!accumulate || g_deterministic, "rldm_train_conv_fused: the fused epilogue writes y (no accumulation)");
             p.accumulate = 0;
         }
+        // deterministic mode: the epilogue leaves one partial row per 64-pixel tile, folded in tile order behind the launch
+        const bool det_sums = g_deterministic && fu && (f.cs_out || f.gs_out);
+        if (det_sums && det_partials((size_t)grid.x * p.N * 2 * sizeof(float), st, reinterpret_cast<void**>(&f.part))) return 1;
         {                                           // the previous weight gradient's reduction rides on this launch
             const int planes = attach_reduce(f, st, grid.x, grid.y, grid.z);
             if (planes < 0) return 1;
@@ -2508,7 +2688,22 @@ static int train_conv_impl(const rldm_train_conv_desc* d, const rldm_train_fuse*
         const int H = p.Hout;
         const bool halo = ksplit == 1 && p.taps == 9 && p.stride == 1 && p.mode == 0 && p.Cin % 64 == 0 && p.N % 4 == 0 &&
                           H >= 2 && H <= 32 && (H & (H - 1)) == 0 && (p.Wout * H) % 64 == 0 && p.Wout % (64 / H) == 0 && p.Wout >= 64 / H + 2;
-        if (fu) {                                   // the fused instances (conv_fuse_ok held)
+        if (det_sums) {
+            if (halo) {
+                if (narrow) tr_conv_halo_kernel<64, true, true><<<grid, 256, 0, st>>>(p, f);
+                else tr_conv_halo_kernel<128, true, true><<<grid, 256, 0, st>>>(p, f);
+            } else if (p.Cin % 64 == 0) {
+                if (narrow) tr_conv_lds_kernel<64, 64, true, 1, true><<<grid, 256, 0, st>>>(p, f);
+                else tr_conv_lds_kernel<64, 128, true, 1, true><<<grid, 256, 0, st>>>(p, f);
+            } else {
+                if (narrow) tr_conv_lds_kernel<32, 64, true, 1, true><<<grid, 256, 0, st>>>(p, f);
+                else tr_conv_lds_kernel<32, 128, true, 1, true><<<grid, 256, 0, st>>>(p, f);
+            }
+            TR_LAUNCH_CHECK();
+            const int tiles = p.Wout * p.Hout / 64;     // per image (conv_fuse_ok: a multiple of 64 pixels)
+            tr_fold_rows_kernel<<<nblk((size_t)p.B * p.N * 2), 256, 0, st>>>(f.part, p.B, tiles, 2 * p.N, f.gs_out ? f.gs_out : f.cs_out,
+                                                                            2 * p.N, 1);
+        } else if (fu) {                            // the fused instances (conv_fuse_ok held)
             if (halo) {
                 if (narrow) tr_conv_halo_kernel<64, true><<<grid, 256, 0, st>>>(p, f);
                 else tr_conv_halo_kernel<128, true><<<grid, 256, 0, st>>>(p, f);
@@ -2717,6 +2912,14 @@ static int train_wgrad_impl(const rldm_train_conv_desc* d, const rldm_train_fuse
         }
     }
     hipStream_t st = (hipStream_t)stream;
+    if (g_deterministic && v2 && (rows || total)) {
+        // deterministic mode: the all-taps kernels add their column sums atomically; the sums come from the fixed-order colsum instead
+        // (of the fp32 dy, not of the staged bf16 tile)
+        const int rc = rldm_train_colsum(dy, p.B, p.Wout * p.Hout, p.N, rows, rows_ld, rows_accumulate, total, stream);
+        if (rc) return rc;
+        rows = nullptr;
+        total = nullptr;
+    }
     if (v2 && g_wg_group) {
         // queued for a grouped launch (tr_wgrad2_group_kernel; K slices: wg_group_launch)
         const bool dw_queued = std::any_of(g_wgq.begin(), g_wgq.end(), [dw](const WgQueued& q) { return q.it.dw == dw; });
@@ -2750,8 +2953,9 @@ static int train_wgrad_impl(const rldm_train_conv_desc* d, const rldm_train_fuse
     p.dw = scratch;
     if (v2) {
         w2.dy = dy; w2.x = x; w2.part = scratch;
-        w2.dw = p.taps == 9 ? nullptr : dw;                     // (measured: 3x3 tiles are 9x larger, their 38 MB of atomics lose to the
-                                                                //  partial tiles + reduction launch by 10-30 %; 1x1 wins 25-35 %)
+        w2.dw = p.taps == 9 || g_deterministic ? nullptr : dw;  // (measured: 3x3 tiles are 9x larger, their 38 MB of atomics lose to the
+                                                                //  partial tiles + reduction launch by 10-30 %; 1x1 wins 25-35 %;
+                                                                //  deterministic mode: always partial tiles, summed in slice order)
         w2.rows = rows; w2.rows_ld = rows_ld; w2.total = total;
         if (rows && !rows_accumulate) tr_zero2d_kernel<<<nblk((size_t)p.B * p.N), 256, 0, st>>>(rows, rows_ld, p.N, p.B);
         size_t smem = (size_t)64 * w2.pitchA * 2 + (size_t)(p.taps == 9 ? 3 : 1) * 64 * w2.pitchB * 2;
@@ -2818,8 +3022,17 @@ int rldm_train_colsum(const float* dy, int B, int npix, int N, float* rows, int 
                       void* stream) {
     RLDM_REQUIRE(dy && (rows || total), "null argument");
     hipStream_t st = (hipStream_t)stream;
+    if (g_deterministic) {
+        const int S = (npix + 255) / 256;
+        float* part = nullptr;
+        if (det_partials((size_t)B * S * N * sizeof(float), st, reinterpret_cast<void**>(&part))) return 1;
+        tr_colsum_kernel<true><<<dim3((N + 63) / 64, B, S), 256, 0, st>>>(dy, npix, N, part, 0, nullptr);
+        tr_colsum_finish_kernel<<<nblk((size_t)N), 256, 0, st>>>(part, B, S, N, rows, rows_ld, rows_accumulate, total);
+        TR_LAUNCH_CHECK();
+        return 0;
+    }
     if (rows && !rows_accumulate) tr_zero2d_kernel<<<nblk((size_t)B * N), 256, 0, st>>>(rows, rows_ld, N, B);
-    tr_colsum_kernel<<<dim3((N + 63) / 64, B, (npix + 255) / 256), 256, 0, st>>>(dy, npix, N, rows, rows_ld, total);
+    tr_colsum_kernel<false><<<dim3((N + 63) / 64, B, (npix + 255) / 256), 256, 0, st>>>(dy, npix, N, rows, rows_ld, total);
     TR_LAUNCH_CHECK();
     return 0;
 }
@@ -2834,7 +3047,8 @@ int rldm_train_gn_forward(const float* x, int B, int npix, int C, int groups, fl
     RLDM_REQUIRE(x && gamma && beta && stats && y, "null argument");
     RLDM_REQUIRE(C % groups == 0, "channels must be a multiple of the group count");
     hipStream_t st = (hipStream_t)stream;
-    const bool slab = 1024 % C == 0 && C >= 4 && groups <= 64 && (size_t)npix * C >= (1u << 18);     // large tensors, see the kernel
+    // (deterministic mode: the slab kernels meet in atomics; the one-block-per-(image, group) kernels add in a fixed order)
+    const bool slab = !g_deterministic && 1024 % C == 0 && C >= 4 && groups <= 64 && (size_t)npix * C >= (1u << 18);     // large tensors, see the kernel
     if (slab) {
         double* acc = nullptr;
         if (gn_accumulators((size_t)B * groups * 2, st, &acc)) return 1;
@@ -2865,8 +3079,16 @@ int rldm_train_gn_backward(const float* x, const float* dy, const float* stats, 
     RLDM_REQUIRE(x && dy && stats && gamma && beta && scratch && dx && dgamma && dbeta, "null argument");
     RLDM_REQUIRE(C % groups == 0 && C / groups <= 256, "channels per group must be <= 256");
     hipStream_t st = (hipStream_t)stream;
-    const bool slab = 1024 % C == 0 && C >= 4 && C <= 1024 && groups <= 64 && (size_t)npix * C >= (1u << 18);
-    if (slab) {
+    const bool slab = !g_deterministic && 1024 % C == 0 && C >= 4 && C <= 1024 && groups <= 64 && (size_t)npix * C >= (1u << 18);
+    if (g_deterministic) {
+        float* part = nullptr;                      // [2][B][C]: d gamma, d beta per image
+        if (det_partials((size_t)2 * B * C * sizeof(float), st, reinterpret_cast<void**>(&part))) return 1;
+        tr_gn_bwd_reduce_kernel<true><<<dim3(groups, B), 256, 0, st>>>(x, dy, reinterpret_cast<const float2*>(stats), gamma, beta, npix, C,
+                                                                       groups, silu, reinterpret_cast<float2*>(scratch), part,
+                                                                       part + (size_t)B * C);
+        tr_fold_rows_kernel<<<nblk((size_t)C), 256, 0, st>>>(part, 1, B, C, dgamma, C, 1);
+        tr_fold_rows_kernel<<<nblk((size_t)C), 256, 0, st>>>(part + (size_t)B * C, 1, B, C, dbeta, C, 1);
+    } else if (slab) {
         double* acc = nullptr;
         if (gn_accumulators((size_t)B * groups * 2, st, &acc)) return 1;
         constexpr int kSlab = 64;                   // pixels per block
@@ -2876,7 +3098,7 @@ int rldm_train_gn_backward(const float* x, const float* dy, const float* stats, 
     } else
         // (a four-channels-per-thread form measured 14.0 us against this kernel's 10.1: four sigmoids per iteration and the wider
         //  LDS epilogue cost more than the 16-byte loads save)
-        tr_gn_bwd_reduce_kernel<<<dim3(groups, B), 256, 0, st>>>(x, dy, reinterpret_cast<const float2*>(stats), gamma, beta, npix, C,
+        tr_gn_bwd_reduce_kernel<false><<<dim3(groups, B), 256, 0, st>>>(x, dy, reinterpret_cast<const float2*>(stats), gamma, beta, npix, C,
                                                                  groups, silu, reinterpret_cast<float2*>(scratch), dgamma, dbeta);
     const size_t total = (size_t)B * npix * C;
     if ((C / groups) % 4 == 0 && total < (1ull << 31))
@@ -2895,6 +3117,16 @@ int rldm_train_gn_backward(const float* x, const float* dy, const float* stats, 
 int rldm_train_chan_stats(const float* x, int B, int npix, int C, float* cs, void* stream) {
     RLDM_REQUIRE(x && cs && B > 0 && npix > 0, "null argument");
     RLDM_REQUIRE(C % 4 == 0 && C <= 1024, "channels: a multiple of 4, <= 1024");
+    if (g_deterministic) {
+        hipStream_t st = (hipStream_t)stream;
+        const int T = (npix + 63) / 64;
+        float* part = nullptr;
+        if (det_partials((size_t)B * T * C * 2 * sizeof(float), st, reinterpret_cast<void**>(&part))) return 1;
+        tr_chan_stats_det_kernel<<<dim3(T, B, (C + 63) / 64), 256, 0, st>>>(x, npix, C, part);
+        tr_fold_rows_kernel<<<nblk((size_t)B * C * 2), 256, 0, st>>>(part, B, T, 2 * C, cs, 2 * C, 1);
+        TR_LAUNCH_CHECK();
+        return 0;
+    }
     const int slab = npix >= 4096 ? 256 : 64;
     tr_chan_stats_kernel<<<dim3((npix + slab - 1) / slab, B), 256, 0, (hipStream_t)stream>>>(x, npix, C, slab, cs);
     TR_LAUNCH_CHECK();
@@ -3011,8 +3243,17 @@ int rldm_train_mse(const float* pred, const float* target, const float* weight, 
                    double* loss, void* stream) {
     RLDM_REQUIRE(pred && target && dpred && loss, "null argument");
     hipStream_t st = (hipStream_t)stream;
+    if (g_deterministic) {
+        const unsigned nb = nblk((size_t)B * W * H * C);
+        double* part = nullptr;
+        if (det_partials((size_t)nb * sizeof(double), st, reinterpret_cast<void**>(&part))) return 1;
+        tr_mse_kernel<true><<<nb, 256, 0, st>>>(pred, target, weight, B, C, W, H, dpred, part);
+        tr_fold_double_kernel<<<1, 256, 0, st>>>(part, (int)nb, loss);
+        TR_LAUNCH_CHECK();
+        return 0;
+    }
     tr_zero_kernel<<<1, 256, 0, st>>>(reinterpret_cast<float*>(loss), 2);
-    tr_mse_kernel<<<nblk((size_t)B * W * H * C), 256, 0, st>>>(pred, target, weight, B, C, W, H, dpred, loss);
+    tr_mse_kernel<false><<<nblk((size_t)B * W * H * C), 256, 0, st>>>(pred, target, weight, B, C, W, H, dpred, loss);
     TR_LAUNCH_CHECK();
     return 0;
 }
@@ -3020,8 +3261,17 @@ int rldm_train_mse(const float* pred, const float* target, const float* weight, 
 int rldm_train_sqnorm(const float* g, int64_t n, double* out, void* stream) {
     RLDM_REQUIRE(g && out && n >= 0, "null argument");
     hipStream_t st = (hipStream_t)stream;
+    if (g_deterministic && n) {
+        const unsigned nb = std::min<unsigned>(nblk((size_t)n), 2048u);
+        double* part = nullptr;
+        if (det_partials((size_t)nb * sizeof(double), st, reinterpret_cast<void**>(&part))) return 1;
+        tr_sqnorm_kernel<true><<<nb, 256, 0, st>>>(g, (size_t)n, part);
+        tr_fold_double_kernel<<<1, 256, 0, st>>>(part, (int)nb, out);
+        TR_LAUNCH_CHECK();
+        return 0;
+    }
     tr_zero_kernel<<<1, 256, 0, st>>>(reinterpret_cast<float*>(out), 2);
-    if (n) tr_sqnorm_kernel<<<std::min<unsigned>(nblk((size_t)n), 2048u), 256, 0, st>>>(g, (size_t)n, out);
+    if (n) tr_sqnorm_kernel<false><<<std::min<unsigned>(nblk((size_t)n), 2048u), 256, 0, st>>>(g, (size_t)n, out);
     TR_LAUNCH_CHECK();
     return 0;
 }

@@ -5,6 +5,7 @@ only; every arithmetic operation below is a HIP kernel behind the C ABI.  No CPU
 """
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -456,3 +457,118 @@ def wgrad_group_flush():
 
 def wgrad_group_pending():
     return int(_lib.lib().rldm_train_wgrad_group_pending())
+
+
+# ---- deterministic mode (include/rangeldm_hip.h: rldm_train_deterministic) ------------------------------------------------
+def deterministic(on):
+    """Set the library's deterministic switch (process-wide, one caller thread, read when a call is enqueued): with it on, every
+    op of this module gives the same bits for the same inputs, whatever else runs on the device.  UNetTrainer(deterministic=True)
+    scopes it around its own calls; the RCCL all-reduce is outside the guarantee."""
+    _chk(_lib.lib().rldm_train_deterministic(1 if on else 0), "rldm_train_deterministic")
+
+
+def deterministic_enabled():
+    return bool(_lib.lib().rldm_train_deterministic_enabled())
+
+
+# The fixed orders of the deterministic mode restated in numpy (host arrays in, host arrays out; every `+` and `*` below is one fp32 --
+# or, for the two fp64 reductions, one fp64 -- operation on arrays, so each line is one rounding per element).
+def _lane_partials(v, slab):
+    """v (B, npix, C) fp32 -> (B, slabs, C): slab z covers pixels [slab z, slab z + slab); lane k of 16 adds pixels k + 16 j in order
+    of j from +0; the lanes are added k = 0 .. 15 from +0.  (A missing pixel of a short last slab adds +0, which changes nothing: an
+    accumulator that started at +0 is never -0.)"""
+    B, npix, Cc = v.shape
+    S = (npix + slab - 1) // slab
+    pad = np.zeros((B, S * slab - npix, Cc), np.float32)
+    v = np.concatenate([v.astype(np.float32, copy=False), pad], axis=1).reshape(B, S, slab // 16, 16, Cc)
+    lanes = np.zeros((B, S, 16, Cc), np.float32)
+    for j in range(slab // 16):
+        lanes = lanes + v[:, :, j]
+    part = np.zeros((B, S, Cc), np.float32)
+    for k in range(16):
+        part = part + lanes[:, :, k]
+    return part
+
+
+def _fold(part, axis=1):
+    """The entries along `axis` added in index order from +0."""
+    part = np.moveaxis(part, axis, 0)
+    acc = np.zeros(part.shape[1:], part.dtype)
+    for t in range(part.shape[0]):
+        acc = acc + part[t]
+    return acc
+
+
+def chan_stats_host(x, cs=None):
+    """`chan_stats` (and the statistics of `conv_fused(..., want_stats=True)` for its stored output) in the deterministic mode:
+    x (B, W, H, C) or (B, npix, C) fp32 -> cs (B, C, 2) = (sum, sum of squares), 64-pixel partials (see _lane_partials) added in
+    partial order and then to `cs` (default: zeros)."""
+    x = np.asarray(x, np.float32)
+    x = x.reshape(x.shape[0], -1, x.shape[-1])
+    s = _fold(_lane_partials(x, 64))
+    ss = _fold(_lane_partials(x * x, 64))              # (the product is rounded to fp32 before it is added)
+    out = np.stack([s, ss], axis=-1)
+    base = np.zeros_like(out) if cs is None else np.asarray(cs, np.float32)
+    return base + out
+
+
+def colsum_host(dy, rows=None, total=None):
+    """`colsum` in the deterministic mode: dy (B, W, H, N) -> (rows (B, N), total (N,)): image sums = 256-pixel slabs (see
+    _lane_partials) added in slab order; rows = image sums (added to `rows` if given: rows_accumulate); total = `total` (default
+    zeros) + the image sums added in image order."""
+    dy = np.asarray(dy, np.float32)
+    dy = dy.reshape(dy.shape[0], -1, dy.shape[-1])
+    img = _fold(_lane_partials(dy, 256))
+    t = _fold(img, axis=0)
+    r = img if rows is None else np.asarray(rows, np.float32) + img
+    return r, (np.zeros_like(t) if total is None else np.asarray(total, np.float32)) + t
+
+
+def _block_sum(a):
+    """block_sum_d of train.hip: a (n, 256) fp64 -> (n,): per 64-lane wave a binary tree (lane l with l ^ 32, then ^ 16 .. ^ 1), then the
+    four waves added in order from 0."""
+    v = a.reshape(a.shape[0], 4, 64)
+    o = 32
+    while o:
+        v = v[..., :o] + v[..., o:2 * o]
+        o >>= 1
+    acc = np.zeros(a.shape[0], np.float64)
+    for w in range(4):
+        acc = acc + v[:, w, 0]
+    return acc
+
+
+def _fold_double(part):
+    """tr_fold_double_kernel: thread t of 256 adds part[t], part[t + 256], ... in order, then _block_sum."""
+    n = part.shape[0]
+    J = max(1, (n + 255) // 256)
+    p = np.concatenate([part, np.zeros(J * 256 - n, np.float64)]).reshape(J, 256)
+    return _block_sum(_fold(p, axis=0)[None, :])[0]
+
+
+def mse_host(pred_nhwc, target_nchw, weight=None):
+    """The loss of `mse` in the deterministic mode (fp64): element i of pred (NHWC order) contributes w[b] d d / total with
+    d = fp32(pred - target); blocks of 256 elements (_block_sum), the block sums folded by _fold_double."""
+    pred = np.asarray(pred_nhwc, np.float32)
+    tgt = np.asarray(target_nchw, np.float32).transpose(0, 2, 3, 1)
+    B = pred.shape[0]
+    d = (pred - tgt).astype(np.float64)
+    w = np.ones(B, np.float64) if weight is None else np.asarray(weight, np.float32).astype(np.float64)
+    total = float(pred.size)
+    part = (w.reshape(B, 1, 1, 1) * d * d / total).reshape(-1)
+    nb = (part.size + 255) // 256
+    part = np.concatenate([part, np.zeros(nb * 256 - part.size, np.float64)]).reshape(nb, 256)
+    return _fold_double(_block_sum(part))
+
+
+def sqnorm_host(g):
+    """`sqnorm` in the deterministic mode (fp64): nb = min(ceil(n / 256), 2048) blocks; thread t of block i adds g[(i + j nb) 256 + t]^2
+    in order of j; _block_sum per block; the block sums folded by _fold_double."""
+    g = np.asarray(g, np.float32).reshape(-1).astype(np.float64)
+    n = g.size
+    if n == 0:
+        return np.float64(0.0)
+    nb = min((n + 255) // 256, 2048)
+    J = (n + nb * 256 - 1) // (nb * 256)
+    sq = np.concatenate([g * g, np.zeros(J * nb * 256 - n, np.float64)]).reshape(J, nb, 256)
+    return _fold_double(_block_sum(_fold(sq, axis=0)))

@@ -11,6 +11,7 @@ allocates and zeroes buffers and runs the collectives); no CPU fallback.
 Parity: tests/test_training.py compares every parameter gradient of a small UNet, and the parameters after optimizer
 steps, with torch autograd / torch.optim.AdamW on the oracle (oracle/unet.py).
 """
+import contextlib
 import math
 import os
 from collections import OrderedDict
@@ -127,7 +128,12 @@ def fused_levels(W, H, num_levels, min_pixels):
 class UNetTrainer:
     def __init__(self, config, state_dict, device="cuda", lr=1e-4, betas=(0.95, 0.999), weight_decay=1e-6, eps=1e-8,
                  max_grad_norm=1.0, use_ema=True, ema_max_decay=0.9999, ema_inv_gamma=1.0, ema_power=0.75,
-                 lr_warmup_steps=500, total_steps=100000, bucket_mb=32, gradient_accumulation_steps=1):
+                 lr_warmup_steps=500, total_steps=100000, bucket_mb=32, gradient_accumulation_steps=1, deterministic=False):
+        """deterministic: run every kernel of this trainer in the library's deterministic mode (rldm_train_deterministic,
+        include/rangeldm_hip.h): the same inputs give the same bits -- parameters, optimizer state, EMA, loss -- run after run,
+        eagerly or replayed from the captured step graph, under `fused_tape` True / False and `wgrad_group` True / False.  Fixed
+        for the trainer's life (a captured step graph never mixes modes); slower.  The RCCL all-reduce of a
+        multi-rank step is outside the guarantee: the order in which a collective adds the ranks' gradients is RCCL's."""
         self.cfg = config if isinstance(config, UNetConfig) else UNetConfig(**config)
         if not self.cfg.flip_sin_to_cos or self.cfg.freq_shift != 0:
             raise NotImplementedError("the training step implements UNet2DModel's default time embedding "
@@ -207,6 +213,22 @@ class UNetTrainer:
         self.wgrad_group = True
         self._wg_on, self._wg_keep = False, []
         self._cs = {}
+        self._deterministic = bool(deterministic)
+
+    @property
+    def deterministic(self):
+        return self._deterministic
+
+    @contextlib.contextmanager
+    def _mode(self):
+        """The library's deterministic switch set to this trainer's mode for the duration of a call, the previous value restored
+        afterwards (also when the call raises)."""
+        prev = T.deterministic_enabled()
+        T.deterministic(self._deterministic)
+        try:
+            yield
+        finally:
+            T.deterministic(prev)
 
     # ---- parameters -------------------------------------------------------------------------------------------
     def _view(self, flat, n):
@@ -682,6 +704,10 @@ class UNetTrainer:
         """sample (B, C, W, H) fp32 on the device; pos_encoding=True appends the azimuth-0 marker channel here (the
         `torch.cat([noisy_images, pos_encoding], dim=1)` of ldm/train_unconditional.py:500-501), so C + 1 == in_channels.
         timesteps (B,) int64 -> model_output (B, W, H, out_channels) NHWC.  Records the tape for `backward`."""
+        with self._mode():
+            return self._forward(sample_nchw, timesteps, pos_encoding)
+
+    def _forward(self, sample_nchw, timesteps, pos_encoding=False):
         cfg = self.cfg
         self._tape, self._grad, self._cs = [], {}, {}
         T.set_zero_arena(self._arena)                   # split-K conv outputs of this step: pre-zeroed slices, one fill
@@ -760,6 +786,10 @@ class UNetTrainer:
     def backward(self, dpred, reduce=None, launch_collectives=True):
         """Replays the tape in reverse.  reduce: None = single process; True = bucketed RCCL all-reduce (average) of the flat
         gradient buffer, overlapped with the rest of backward."""
+        with self._mode():
+            return self._backward(dpred, reduce, launch_collectives)
+
+    def _backward(self, dpred, reduce=None, launch_collectives=True):
         if reduce is None:
             reduce = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
         self._pending = []
@@ -796,6 +826,10 @@ class UNetTrainer:
         """clip_grad_norm_(1.0) + AdamW + cosine/warmup lr + EMA (ldm/train_unconditional.py:546-556), then refresh the
         bf16 operand copies and zero the gradients.  device_scalars: the step number lives in device memory and the
         learning rate / bias corrections / EMA decay are computed there (what a captured step graph replays)."""
+        with self._mode():
+            return self._optimizer_step(grad_world, device_scalars)
+
+    def _optimizer_step(self, grad_world=1, device_scalars=False):
         hp = self.hp
         if device_scalars and self._step_dev_mirror != self.global_step:
             self._step_dev.fill_(self.global_step)
@@ -826,6 +860,10 @@ class UNetTrainer:
     def train_step(self, noisy_nchw, timesteps, target_nchw, loss_weights=None, pos_encoding=False):
         """model_output = model(noisy, t); loss = mse(model_output, target) [* min-SNR weights]; backward; step.
         Returns the loss (0-d float64 device tensor; no host sync)."""
+        with self._mode():
+            return self._train_step(noisy_nchw, timesteps, target_nchw, loss_weights, pos_encoding)
+
+    def _train_step(self, noisy_nchw, timesteps, target_nchw, loss_weights=None, pos_encoding=False):
         pred = self.forward(noisy_nchw, timesteps, pos_encoding)
         loss, dpred = T.mse(pred, target_nchw.float().contiguous(), loss_weights)
         k = self.gradient_accumulation_steps
@@ -848,6 +886,10 @@ class UNetTrainer:
         step is cut into one graph per gradient bucket: after each, the bucket's RCCL all-reduce is launched eagerly on
         the communication stream and overlaps the next segment of backward; the optimizer segment waits for all of them.
         Returns the loss (0-d float64 device tensor, a copy)."""
+        with self._mode():
+            return self._train_step_graphed(noisy_nchw, timesteps, target_nchw, loss_weights, pos_encoding, reduce)
+
+    def _train_step_graphed(self, noisy_nchw, timesteps, target_nchw, loss_weights=None, pos_encoding=False, reduce=None):
         if self.gradient_accumulation_steps != 1:
             raise NotImplementedError("train_step_graphed captures one optimizer step per call; use train_step with "
                                       "gradient_accumulation_steps > 1")
@@ -955,7 +997,9 @@ def training_step(trainer, vae, noise_scheduler, clean_images, generator=None, p
     (`condition_encoder(batch["down"])`) or `cat([masked latents, mask])`, concatenated to the noisy latents.
     graphed: replay the UNet forward / backward / optimizer from captured HIP graphs (UNetTrainer.train_step_graphed).
     latents: `vae.encode(clean_images).latent_dist.sample() * scaling_factor` computed by the caller (input pipelining:
-    `encode_ahead`); clean_images is ignored then."""
+    `encode_ahead`); clean_images is ignored then.
+    The step runs in the trainer's mode: `UNetTrainer(deterministic=True)` makes the UNet forward / loss / backward / optimizer
+    bit-reproducible (the VAE encode, the noise draw and a multi-rank RCCL all-reduce are outside that guarantee)."""
     dev = trainer.device
     if latents is not None:                 # encoded ahead of time (e.g. on a second stream while the previous step ran)
         latents = latents.to(dev).float()

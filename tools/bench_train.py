@@ -3,6 +3,7 @@
 data-parallel): samples/sec = global batch / step time, same barrier + max-over-ranks timing as bench.py.
 
     python tools/bench_train.py [--batch 8] [--steps 5] [--warmup 2] [--no-vae]
+    python tools/bench_train.py --deterministic      # default and deterministic mode in one process, interleaved (one GPU)
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/bench_train.py --gpus N ...
 
 One step = the loop body of ldm/train_unconditional.py:479-556 on synthetic range images resident in HBM:
@@ -32,6 +33,9 @@ def main():
     ap.add_argument("--overlap-vae", action="store_true", help="encode batch i + 1 on a second stream while batch i trains (measured: 4 % slower than in-step)")
     ap.add_argument("--eager", action="store_true", help="launch every kernel from the host instead of replaying the captured step graphs")
     ap.add_argument("--prio", action="store_true", help="with --overlap-vae: the training step on a HIGH-priority stream, the encode on a default-priority one")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="time UNetTrainer(deterministic=False) and (deterministic=True) in this process: five interleaved repetitions "
+                         "of --steps steps after the warm-up, median [min, max]; launches per step; run-to-run spread of both modes")
     ap.add_argument("--seed", type=int, default=20240310)
     a = ap.parse_args()
     from rangeldm_amd import distributed as D
@@ -52,6 +56,12 @@ def main():
         vae.load_state_dict(synth_state_dict(vae_param_shapes(p["vae"]), seed=a.seed, prefix="vae."))
     sched = DDPMSchedulerHIP()
     B = a.batch
+    if a.deterministic:
+        if world != 1:
+            raise SystemExit("--deterministic compares the two modes on one GPU")
+        sd = synth_state_dict(unet_param_shapes(p["unet"]), seed=a.seed)
+        compare_modes(a, {False: tr, True: UNetTrainer(p["unet"], sd, device=dev, deterministic=True)}, vae, sched, dev)
+        return
     if not a.eager:
         a.warmup = max(a.warmup, 2)                    # (step 1 runs eagerly and sizes the scratch buffers, step 2 captures)
     n_iter = a.warmup + a.steps
@@ -106,6 +116,82 @@ def main():
     D.barrier()
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
+
+
+def compare_modes(a, trainers, vae, sched, dev):
+    """Default against deterministic mode in one process: after the warm-up (eager sizing step + capture), five repetitions of
+    `--steps` steps each, the two modes alternating; kernel launches of one eager step (torch.profiler); and the run-to-run spread
+    of the loss and of the gradient (rel-L2 against the first run) over five identical forward + backward passes per mode."""
+    from rangeldm_amd import train_ops as T
+    from rangeldm_amd.synth import normal
+    from rangeldm_amd.training import training_step
+    B = a.batch
+    warm = max(a.warmup, 2)
+    shape = (B, 2, 1024, 64) if vae is not None else (B, 4, 256, 16)
+    imgs = [torch.from_numpy(normal(a.seed, f"train/0/{i}", shape)).mul_(0.5).to(dev) for i in range(max(warm, a.steps))]
+    gens = {m: torch.Generator().manual_seed(a.seed) for m in trainers}
+
+    def steps(mode, n, graphed=True):
+        for i in range(n):
+            training_step(trainers[mode], vae, sched, imgs[i], generator=gens[mode], pos_encoding=True, graphed=graphed)
+
+    for m in trainers:
+        steps(m, warm)
+    sps = {m: [] for m in trainers}
+    for _ in range(5):
+        for m in trainers:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            steps(m, a.steps)
+            torch.cuda.synchronize()
+            sps[m].append(B * a.steps / (time.perf_counter() - t0))
+    launches = {}
+    for m in trainers:
+        try:
+            from torch.profiler import ProfilerActivity, profile
+            with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                steps(m, 1, graphed=False)
+                torch.cuda.synchronize()
+            launches[m] = sum(1 for e in prof.events() if str(e.device_type).endswith("CUDA") and "emcpy" not in e.name
+                              and "emset" not in e.name)
+        except Exception as exc:      # noqa: BLE001 (the count is a side figure: the timing stands without it)
+            launches[m] = f"unavailable ({type(exc).__name__})"
+    # spread: identical inputs, five forward + backward passes
+    g = torch.Generator().manual_seed(a.seed + 1)
+    x, target = torch.randn(B, 4, 256, 16, generator=g).to(dev), torch.randn(B, 4, 256, 16, generator=g).to(dev)
+    t = torch.randint(0, 1000, (B,), generator=g).to(dev)
+    spread = {}
+    for m, tr in trainers.items():
+        tr.grads.zero_()
+        ls, rels, g0 = [], [], None
+        for _ in range(5):
+            pred = tr.forward(x, t, pos_encoding=True)
+            T.deterministic(m)
+            try:
+                loss, dpred = T.mse(pred, target)
+            finally:
+                T.deterministic(False)
+            tr.backward(dpred)
+            ls.append(float(loss))
+            if g0 is None:
+                g0 = tr.grads.double().clone()
+            else:
+                rels.append(float((tr.grads.double() - g0).norm() / g0.norm()))
+            tr.grads.zero_()
+        spread[m] = {"loss_min": min(ls), "loss_max": max(ls), "loss_rel_spread": (max(ls) - min(ls)) / abs(ls[0]),
+                     "grad_rel_l2_max": max(rels), "grad_rel_l2": rels}
+
+    def tri(v):
+        return {"median": float(np.median(v)), "min": min(v), "max": max(v), "samples_per_sec": v}
+
+    name = {False: "default", True: "deterministic"}
+    print(json.dumps({"metric": "training samples/sec, default against deterministic mode, interleaved in one process",
+                      "unit": "samples/sec", "n_gpus": 1, "batch": B, "steps": a.steps, "warmup": warm, "repetitions": 5,
+                      "vae_encode": vae is not None,
+                      **{name[m]: tri(sps[m]) for m in trainers},
+                      "deterministic_over_default": float(np.median(sps[True]) / np.median(sps[False])),
+                      "launches_per_eager_step": {name[m]: launches[m] for m in trainers},
+                      "spread_five_identical_passes": {name[m]: spread[m] for m in trainers}}))
 
 
 if __name__ == "__main__":
