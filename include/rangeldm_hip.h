@@ -711,6 +711,7 @@ int rldm_train_wgrad_group_pending(void);   /* queued layers (tests) */
  *                          block i adds g[(i + j nb) * 256 + t]^2 in order of j, nb = min(ceil(n / 256), 2048) blocks), a block's 256
  *                          values added as a binary tree (lanes l and l ^ 32, then ^ 16 .. ^ 1, then the four waves in order); the
  *                          result = the same two steps over the block partials (thread t adds partials t, t + 256, ... first).
+ *   l1                     mse's partials and folds, for the loss and for each channel's absolute-error sum (see rldm_train_l1).
  * The RCCL all-reduce of a multi-rank step is outside this guarantee. */
 int rldm_train_deterministic(int on);
 int rldm_train_deterministic_enabled(void);
@@ -753,6 +754,16 @@ int rldm_train_unpack_output(const float* x, int B, int C, int W, int H, float* 
  * (B, C, W, H); dpred [B][W][H][C]; *loss device double. */
 int rldm_train_mse(const float* pred, const float* target, const float* weight, int B, int C, int W, int H, float* dpred,
                    double* loss, void* stream);
+/* The VAE's reconstruction term before the discriminator starts (channel-weighted L1, summed, divided by the batch):
+ *   loss = (1 / B) sum_{b,w,h,c} wc[c] |pred[b][w][h][c] - target[b][c][w][h]|
+ * pred [B][W][H][C], target (B, C, W, H), wc device [C] (C <= 16); dpred [B][W][H][C] = s g[c] with s = -1 / 0 / +1 the sign of
+ * the fp32 difference (0 at equality) and g[c] = wc[c] / B one fp32 division: every element is one exact product.  out: device
+ * double [1 + C] = (loss, the unweighted sum of |difference| per channel).  fp64 sums like rldm_train_mse: element i * 256 + t
+ * (NHWC order) is lane t of partial i, a partial's 256 values are added as mse's binary tree, the partials meet in fp64 atomics
+ * -- or, in the deterministic mode, are folded as mse's are (channel k's partial takes +0 from the other channels' lanes).
+ * train_ops.l1_host restates it in numpy. */
+int rldm_train_l1(const float* pred, const float* target, const float* wc, int B, int C, int W, int H, float* dpred, double* out,
+                  void* stream);
 int rldm_train_sqnorm(const float* g, int64_t n, double* out /*device*/, void* stream);
 typedef struct rldm_adamw_config {
     float lr, beta1, beta2, eps, weight_decay;  /* torch.optim.AdamW, ldm/train_unconditional.py:357-363           */

@@ -1,4 +1,5 @@
-// train.hip -- kernels of the UNet training step (ldm/train_unconditional.py:466-558) for gfx950.
+// train.hip -- kernels of the UNet training step (ldm/train_unconditional.py:466-558) and of the VAE decoder's
+// fine-tuning step (rangeldm_amd/vae_training.py) for gfx950.
 //
 // First correct version: self-contained and deliberately simple.  Activations and gradients are fp32 channels-last
 // [B][W][H][C] (W = azimuth wraps, H = beams zero-padded); GEMM operands are rounded to bf16 on their way into
@@ -17,7 +18,8 @@
 //   attention             head_dim 8 softmax attention, forward (+ log-sum-exp) and backward: the matrix-core kernels of
 //                         train_attn.hip behind this file's C entry points.
 //   elementwise           add, channel copy (concat / split), 2x2 sum (nearest-x2 backward), SiLU, sinusoidal timestep
-//                         embedding, input packing, MSE loss + gradient, sum of squares, AdamW (+ clip scale + EMA),
+//                         embedding, input packing, MSE loss + gradient, channel-weighted L1 loss + gradient (the VAE's reconstruction
+//                         term), sum of squares, AdamW (+ clip scale + EMA),
 //                         weight repacking.
 //   deterministic mode    rldm_train_deterministic (include/rangeldm_hip.h): DET instantiations without floating-point atomics -- convs
 //                         never split K, cross-workgroup sums go through partial rows folded in index order (tr_fold_rows_kernel,
@@ -2171,6 +2173,98 @@ __global__ __launch_bounds__(256) void tr_mse_kernel(const float* __restrict__ p
     }
 }
 
+// rldm_train_l1: loss = (1 / B) sum wc[c] |pred - target|, dpred = sign(pred - target) * (wc[c] / B), pred / dpred NHWC, target NCHW.
+// out[0] = the loss, out[1 + c] = sum of |pred - target| over channel c, fp64.  Partial i = the 256 elements [256 i, 256 i + 256) in NHWC
+// order, element 256 i + t in lane t of block_sum_d's tree (tr_mse_kernel's partial); DET: the partials go to part[k][nparts]
+// (k = 0: loss, 1 + c: channel c) and are added by tr_fold_double_kernel, else they meet in fp64 atomics.
+struct L1Elem { double loss, a; int c; };
+__device__ inline L1Elem l1_elem(float p, float t, size_t i, int C, int B, const float* __restrict__ wc, float* __restrict__ dp) {
+    const int c = (int)(i % C);
+    // g = wc[c] / B rounded once to fp32: the fp64 quotient of two fp32 values has bits to spare (53 >= 2 * 24 + 2), so rounding it
+    // again is the fp32 division's own rounding, whatever the fp32 division of this build is
+    const float d = p - t, w = wc[c], g = (float)((double)w / (double)B);
+    const float s = (float)(d > 0.f) - (float)(d < 0.f);
+    *dp = s * g;
+    const double a = (double)fabsf(d);
+    return {(double)w * a / (double)B, a, c};
+}
+__device__ inline size_t l1_target_index(size_t i, int C, int W, int H) {
+    const int c = (int)(i % C);
+    size_t t = i / C;
+    const int h = (int)(t % H);
+    t /= H;
+    const int w = (int)(t % W);
+    const size_t b = t / W;
+    return ((b * C + c) * W + w) * H + h;
+}
+
+// one element per thread (any C, any element count)
+template <bool DET>
+__global__ __launch_bounds__(256) void tr_l1_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                    const float* __restrict__ wc, int B, int C, int W, int H, float* __restrict__ dpred,
+                                                    double* __restrict__ out, size_t nparts) {
+    __shared__ double sh[4];
+    const size_t total = (size_t)B * W * H * C;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    L1Elem e = {0.0, 0.0, -1};
+    if (i < total) e = l1_elem(pred[i], target[l1_target_index(i, C, W, H)], i, C, B, wc, dpred + i);
+    for (int k = 0; k <= C; ++k) {
+        const double v = block_sum_d(k == 0 ? e.loss : (e.c == k - 1 ? e.a : 0.0), sh);
+        if (threadIdx.x == 0) {
+            if constexpr (DET) out[(size_t)k * nparts + blockIdx.x] = v;
+            else unsafeAtomicAdd(out + k, v);
+        }
+    }
+}
+
+// block_sum_d's tree over a partial whose element 4 L + q sits in component q of lane L of ONE wave: the tree's steps l ^ 32 .. l ^ 4 are
+// L ^ 8 .. L ^ 1 per component, its steps l ^ 2, l ^ 1 are (v0 + v2) + (v1 + v3), and its four waves are the lane groups 0-15 .. 48-63
+__device__ inline double l1_wave_partial(double v0, double v1, double v2, double v3) {
+    for (int o = 8; o; o >>= 1) {
+        v0 += __shfl_xor(v0, o);
+        v1 += __shfl_xor(v1, o);
+        v2 += __shfl_xor(v2, o);
+        v3 += __shfl_xor(v3, o);
+    }
+    const double g = (v0 + v2) + (v1 + v3);
+    double t = 0.0;
+    for (int w = 0; w < 4; ++w) t += __shfl(g, 16 * w);
+    return t;
+}
+
+// four consecutive NHWC elements per thread (C = 1, 2 or 4, so a thread holds whole pixels; element count a multiple of 4; pred / dpred
+// 16-byte aligned): one 16-byte load and store per thread, the target's planes read along h by consecutive lanes.  A wave owns a partial.
+template <bool DET>
+__global__ __launch_bounds__(256) void tr_l1_vec_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                        const float* __restrict__ wc, int B, int C, int W, int H,
+                                                        float* __restrict__ dpred, double* __restrict__ out, size_t nparts) {
+    const size_t total = (size_t)B * W * H * C;
+    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    const size_t part = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    L1Elem e[4] = {{0.0, 0.0, -1}, {0.0, 0.0, -1}, {0.0, 0.0, -1}, {0.0, 0.0, -1}};
+    if (i < total) {
+        const f32x4 p = *reinterpret_cast<const f32x4*>(pred + i);
+        f32x4 dp;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            float o;
+            e[q] = l1_elem(p[q], target[l1_target_index(i + q, C, W, H)], i + q, C, B, wc, &o);
+            dp[q] = o;
+        }
+        *reinterpret_cast<f32x4*>(dpred + i) = dp;
+    }
+    for (int k = 0; k <= C; ++k) {
+        double v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = k == 0 ? e[q].loss : (e[q].c == k - 1 ? e[q].a : 0.0);
+        const double s = l1_wave_partial(v[0], v[1], v[2], v[3]);
+        if ((threadIdx.x & 63) == 0 && part < nparts) {
+            if constexpr (DET) out[(size_t)k * nparts + part] = s;
+            else unsafeAtomicAdd(out + k, s);
+        }
+    }
+}
+
 template <bool DET = false>
 __global__ __launch_bounds__(256) void tr_sqnorm_kernel(const float* __restrict__ g, size_t n, double* __restrict__ out) {
     __shared__ double sh[4];
@@ -3254,6 +3348,33 @@ int rldm_train_mse(const float* pred, const float* target, const float* weight, 
     }
     tr_zero_kernel<<<1, 256, 0, st>>>(reinterpret_cast<float*>(loss), 2);
     tr_mse_kernel<false><<<nblk((size_t)B * W * H * C), 256, 0, st>>>(pred, target, weight, B, C, W, H, dpred, loss);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int rldm_train_l1(const float* pred, const float* target, const float* wc, int B, int C, int W, int H, float* dpred, double* out,
+                  void* stream) {
+    RLDM_REQUIRE(pred && target && wc && dpred && out, "null argument");
+    RLDM_REQUIRE(B > 0 && W > 0 && H > 0 && C > 0 && C <= 16, "rldm_train_l1: B, W, H >= 1 and 1 <= C <= 16");
+    RLDM_REQUIRE(reinterpret_cast<uintptr_t>(out) % 16 == 0, "rldm_train_l1: out must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t total = (size_t)B * W * H * C;
+    const unsigned nparts = nblk(total);
+    // four elements per thread where a thread then holds whole pixels and the 16-byte accesses are aligned
+    const bool vec = 4 % C == 0 && total % 4 == 0 && (reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(dpred)) % 16 == 0;
+    const unsigned grid = vec ? (nparts + 3) / 4 : nparts;
+    if (g_deterministic) {
+        double* part = nullptr;
+        if (det_partials((size_t)(C + 1) * nparts * sizeof(double), st, reinterpret_cast<void**>(&part))) return 1;
+        if (vec) tr_l1_vec_kernel<true><<<grid, 256, 0, st>>>(pred, target, wc, B, C, W, H, dpred, part, nparts);
+        else tr_l1_kernel<true><<<grid, 256, 0, st>>>(pred, target, wc, B, C, W, H, dpred, part, nparts);
+        for (int k = 0; k <= C; ++k) tr_fold_double_kernel<<<1, 256, 0, st>>>(part + (size_t)k * nparts, (int)nparts, out + k);
+        TR_LAUNCH_CHECK();
+        return 0;
+    }
+    tr_zero_kernel<<<1, 256, 0, st>>>(reinterpret_cast<float*>(out), 2 * (size_t)(C + 1));
+    if (vec) tr_l1_vec_kernel<false><<<grid, 256, 0, st>>>(pred, target, wc, B, C, W, H, dpred, out, nparts);
+    else tr_l1_kernel<false><<<grid, 256, 0, st>>>(pred, target, wc, B, C, W, H, dpred, out, nparts);
     TR_LAUNCH_CHECK();
     return 0;
 }

@@ -267,6 +267,21 @@ def mse(pred_nhwc, target_nchw, weight=None):
     return loss, dpred
 
 
+def l1(pred_nhwc, target_nchw, channel_weights):
+    """Channel-weighted L1, summed and divided by the batch: loss = (1 / B) sum wc[c] |pred - target|.  channel_weights: device fp32
+    (C,).  -> (loss: 0-d float64 device tensor, dpred (B, W, H, C) = sign(pred - target) * (wc[c] / B), abs_sums: float64 (C,) =
+    the unweighted sum of |pred - target| per channel; MAE of channel c = abs_sums[c] / (B W H)).  loss and abs_sums are views
+    of one buffer."""
+    B, W, H, Cc = pred_nhwc.shape
+    if tuple(target_nchw.shape) != (B, Cc, W, H) or channel_weights.numel() != Cc:
+        raise ValueError(f"l1: pred {tuple(pred_nhwc.shape)} (NHWC) needs a target {(B, Cc, W, H)} and {Cc} channel weights")
+    dpred = torch.empty_like(pred_nhwc)
+    out = torch.empty(1 + Cc, dtype=torch.float64, device=pred_nhwc.device)
+    _chk(_lib.lib().rldm_train_l1(_p(pred_nhwc), _p(target_nchw), _p(channel_weights), B, Cc, W, H, _p(dpred), _p(out),
+                                  _s(pred_nhwc)), "rldm_train_l1")
+    return out[0], dpred, out[1:]
+
+
 def sqnorm(g):
     out = torch.empty((), dtype=torch.float64, device=g.device)
     _chk(_lib.lib().rldm_train_sqnorm(_p(g), g.numel(), _p(out), _s(g)), "rldm_train_sqnorm")
@@ -559,6 +574,32 @@ def mse_host(pred_nhwc, target_nchw, weight=None):
     nb = (part.size + 255) // 256
     part = np.concatenate([part, np.zeros(nb * 256 - part.size, np.float64)]).reshape(nb, 256)
     return _fold_double(_block_sum(part))
+
+
+def l1_host(pred_nhwc, target_nchw, channel_weights):
+    """`l1` in the deterministic mode -> (loss fp64, dpred fp32 (B, W, H, C), abs_sums fp64 (C,)).  d = fp32(pred - target);
+    dpred = s * g[c], s = -1 / 0 / +1 the sign of d, g[c] = fp32(wc[c] / B); element i of pred (NHWC order) contributes
+    (wc[c] * |d|) / B to the loss and |d| to its channel's sum (+0 to the other channels'), in fp64; the sums are mse_host's:
+    blocks of 256 elements (_block_sum), the block sums folded by _fold_double."""
+    pred = np.asarray(pred_nhwc, np.float32)
+    tgt = np.asarray(target_nchw, np.float32).transpose(0, 2, 3, 1)
+    wc = np.asarray(channel_weights, np.float32).reshape(-1)
+    B, Cc = pred.shape[0], pred.shape[3]
+    d = pred - tgt
+    g = wc / np.float32(B)
+    s = (d > 0).astype(np.float32) - (d < 0).astype(np.float32)
+    dpred = s * g
+    a = np.abs(d).astype(np.float64)
+    nb = (a.size + 255) // 256
+
+    def total(v):
+        v = np.concatenate([v.reshape(-1), np.zeros(nb * 256 - v.size, np.float64)]).reshape(nb, 256)
+        return _fold_double(_block_sum(v))
+
+    loss = total(wc.astype(np.float64) * a / float(B))
+    chan = np.arange(Cc).reshape(1, 1, 1, Cc)
+    sums = np.array([total(np.where(chan == c, a, 0.0)) for c in range(Cc)], np.float64)
+    return loss, dpred, sums
 
 
 def sqnorm_host(g):

@@ -1,0 +1,108 @@
+"""python -m rangeldm_amd.train_vae: fine-tune the VAE's decoder against its frozen encoder (rangeldm_amd/vae_training.py).
+
+    python -m rangeldm_amd.train_vae --weights DIR | --sgm-ckpt F --sgm-yaml Y  [--input NPY_DIR] --out DIR --steps N
+                                     [--batch-size 8] [--lr 4.5e-6] [--mode] [--seed S] [--log-every K] [--deterministic]
+
+--input holds the (2, W, H) .npy range images `evaluate vae --input` reads (batches walk the sorted files and wrap around); without
+it the run trains on the synthetic batch of `evaluate vae`.  Without --weights / --sgm-ckpt the synthetic weights of `evaluate vae`
+are trained (a plumbing check).  One JSON line per --log-every steps: {"step", "loss", "mae": [per channel]}; the result is written
+to OUT/vae/, which `evaluate vae --weights OUT` reads."""
+import argparse
+import glob
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(prog="python -m rangeldm_amd.train_vae", description=__doc__.split("\n")[0])
+    ap.add_argument("--weights", default=None, help="diffusers VAE directory, or a training output_dir holding vae/")
+    ap.add_argument("--sgm-ckpt", default=None, help="sgm AutoencodingEngine .ckpt")
+    ap.add_argument("--sgm-yaml", default=None, help="the yaml the sgm checkpoint was trained with")
+    ap.add_argument("--input", default=None, help="directory of (2, W, H) .npy range images (default: synthetic batch)")
+    ap.add_argument("--out", required=True, help="output directory: OUT/vae/ is written")
+    ap.add_argument("--steps", type=int, required=True)
+    ap.add_argument("--batch-size", type=int, default=8)
+    ap.add_argument("--lr", type=float, default=4.5e-6)
+    ap.add_argument("--mode", action="store_true", help="decode the posterior's mode instead of a sample")
+    ap.add_argument("--seed", type=int, default=20240310)
+    ap.add_argument("--log-every", type=int, default=10, metavar="K")
+    ap.add_argument("--deterministic", action="store_true", help="bit-reproducible decoder step (slower)")
+    return ap
+
+
+def check_args(a):
+    if a.steps < 1 or a.batch_size < 1 or a.log_every < 1:
+        raise ValueError("--steps, --batch-size and --log-every must be at least 1")
+    if a.weights and a.sgm_ckpt:
+        raise ValueError("--weights and --sgm-ckpt exclude each other")
+    if a.sgm_yaml and not a.sgm_ckpt:
+        raise ValueError("--sgm-yaml goes with --sgm-ckpt")
+
+
+def log_record(step, loss, abs_sums, pixels):
+    """One log line: the loss of `step` (1-based) and the per-channel MAE = abs_sums[c] / pixels (pixels = B W H)."""
+    return {"step": int(step), "loss": float(loss), "mae": [float(s) / float(pixels) for s in abs_sums]}
+
+
+def batch_files(files, step, batch_size):
+    """The files of batch `step` (0-based): consecutive, wrapping around the sorted list."""
+    n = len(files)
+    return [files[(step * batch_size + i) % n] for i in range(batch_size)]
+
+
+def load_model(a):
+    """(VAEConfig, whole state dict) from --weights / --sgm-ckpt, or the synthetic weights."""
+    from .checkpoint import load_sgm_vae_checkpoint, load_vae_dir
+    if a.sgm_ckpt:
+        return load_sgm_vae_checkpoint(a.sgm_ckpt, a.sgm_yaml)
+    if a.weights:
+        sub = os.path.join(a.weights, "vae")
+        return load_vae_dir(sub if os.path.isdir(sub) else a.weights)
+    from .config import VAEConfig
+    from .params import vae_param_shapes
+    from .synth import synth_state_dict
+    cfg = VAEConfig()
+    return cfg, synth_state_dict(vae_param_shapes(cfg), seed=a.seed, prefix="vae.")
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    check_args(a)
+    from .inference_conditional import load_batch
+    from .vae import AutoencoderKLHIP
+    from .vae_training import VAEDecoderTrainer, training_step
+    cfg, sd = load_model(a)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    vae = AutoencoderKLHIP(cfg, device=dev)
+    vae.load_state_dict(sd)
+    sd = vae.state_dict()                                # (diffusers keys, whatever layout the checkpoint had)
+    trainer = VAEDecoderTrainer(cfg, sd, device=dev, lr=a.lr, deterministic=a.deterministic)
+    shape = (cfg.in_channels, *cfg.sample_size)
+    files = sorted(glob.glob(os.path.join(a.input, "*.npy"))) if a.input else None
+    if files is not None and not files:
+        raise ValueError(f"{a.input}: no .npy range images")
+    gen = torch.Generator().manual_seed(a.seed)
+    pixels = a.batch_size * shape[1] * shape[2]
+    last = None
+    for step in range(a.steps):
+        if files is not None:
+            x = torch.from_numpy(np.stack([np.load(f).astype(np.float32) for f in batch_files(files, step, a.batch_size)]))
+            if tuple(x.shape[1:]) != shape:
+                raise ValueError(f"range images of shape {tuple(x.shape[1:])}, the VAE expects {shape}")
+        else:
+            x = load_batch(None, a.batch_size, shape, a.seed)
+        loss = training_step(trainer, vae, x.to(dev), sample_posterior=not a.mode, generator=gen)
+        if (step + 1) % a.log_every == 0 or step + 1 == a.steps:
+            last = log_record(step + 1, loss, trainer.last_abs_sums.cpu().tolist(), pixels)
+            print(json.dumps(last), flush=True)
+    trainer.save_pretrained(a.out)
+    return last
+
+
+if __name__ == "__main__":
+    main()
+    sys.exit(0)

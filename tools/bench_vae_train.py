@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""Throughput of VAE decoder fine-tuning at the shipped config (rangeldm_amd/vae_training.py): samples/s of `training_step` -- frozen
+encode + posterior sample on the inference kernels, decoder forward, L1, backward, Adam, operand repack -- batch 8, 1024 x 64, one GPU,
+eager launches (no captured step graph exists for this trainer).
+
+    python tools/bench_vae_train.py [--batch 8] [--steps 10] [--warmup 3] [--repeats 5] [--no-unet] [--deterministic]
+
+After the warm-up, --repeats timed runs of --steps steps each (a host clock around work that ends in a device synchronise): median
+[min, max].  Achieved TFLOP/s counts 3 x AutoencoderKLHIP.decode_flops (decoder forward + backward; the encode is not counted).  In the
+same process the UNet step of tools/bench_train.py (VAE encode + UNet forward / backward / AdamW / EMA from captured step graphs) is
+timed the same way, interleaved with the decoder runs, for scale.  One JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def tri(v):
+    return {"median": float(np.median(v)), "min": float(min(v)), "max": float(max(v)), "runs": [float(x) for x in v]}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--no-unet", action="store_true", help="skip the UNet step (a profiler run wants the decoder step alone)")
+    ap.add_argument("--deterministic", action="store_true", help="VAEDecoderTrainer(deterministic=True)")
+    ap.add_argument("--seed", type=int, default=20240310)
+    a = ap.parse_args()
+    from rangeldm_amd import _lib
+    from rangeldm_amd.config import PRESETS
+    from rangeldm_amd.params import unet_param_shapes, vae_param_shapes
+    from rangeldm_amd.synth import normal, synth_state_dict
+    from rangeldm_amd.vae import AutoencoderKLHIP
+    from rangeldm_amd.vae_training import VAEDecoderTrainer, training_step
+    _lib.require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    p = PRESETS["RangeLDM"]
+    cfg = p["vae"]
+    sd = synth_state_dict(vae_param_shapes(cfg), seed=a.seed, prefix="vae.")
+    vae = AutoencoderKLHIP(cfg)
+    vae.load_state_dict(sd)
+    tr = VAEDecoderTrainer(cfg, sd, device=dev, deterministic=a.deterministic)
+    B = a.batch
+    W, H = cfg.sample_size
+    n_img = max(a.warmup, a.steps)
+    imgs = [torch.from_numpy(normal(a.seed, f"train/0/{i}", (B, cfg.in_channels, W, H))).mul_(0.5).to(dev) for i in range(n_img)]
+    gen = torch.Generator().manual_seed(a.seed)
+    losses = []
+
+    def vae_steps(n):
+        for i in range(n):
+            losses.append(training_step(tr, vae, imgs[i], generator=gen))
+
+    unet_steps = None
+    if not a.no_unet:
+        from rangeldm_amd.schedulers import DDPMSchedulerHIP
+        from rangeldm_amd.training import UNetTrainer
+        from rangeldm_amd.training import training_step as unet_training_step
+        utr = UNetTrainer(p["unet"], synth_state_dict(unet_param_shapes(p["unet"]), seed=a.seed), device=dev)
+        sched = DDPMSchedulerHIP()
+        ugen = torch.Generator().manual_seed(a.seed)
+
+        def unet_steps(n):
+            for i in range(n):
+                unet_training_step(utr, vae, sched, imgs[i], generator=ugen, pos_encoding=True, graphed=True)
+
+    vae_steps(a.warmup)
+    if unet_steps is not None:
+        unet_steps(max(a.warmup, 2))                    # (step 1 runs eagerly and sizes the scratch buffers, step 2 captures)
+    torch.cuda.synchronize()
+    sps = {"vae_decoder": [], "unet": []}
+    for _ in range(a.repeats):
+        for name, fn in (("vae_decoder", vae_steps), ("unet", unet_steps)):
+            if fn is None:
+                continue
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn(a.steps)
+            torch.cuda.synchronize()
+            sps[name].append(B * a.steps / (time.perf_counter() - t0))
+    f = cfg.downscale
+    gflop = 3.0 * vae.decode_flops(1, W // f, H // f) / 1e9
+    v = tri(sps["vae_decoder"])
+    out = {"metric": "VAE decoder fine-tuning samples/sec, shipped config, batch %d, %d x %d, eager" % (B, W, H),
+           "unit": "samples/sec", "value": v["median"], "samples_per_sec": v, "ms_per_step": 1e3 * B / v["median"],
+           "n_gpus": 1, "batch": B, "steps": a.steps, "warmup": a.warmup, "repeats": a.repeats, "deterministic": bool(a.deterministic),
+           "gflop_per_sample": gflop, "flop_model": "3 x decode_flops (decoder forward + backward); frozen encode not counted",
+           "achieved_tflops": v["median"] * gflop / 1e3, "decoder_parameters": tr.numel,
+           "loss_first_last": [float(losses[0]), float(losses[-1])]}
+    if unet_steps is not None:
+        out["unet_step_samples_per_sec"] = tri(sps["unet"])
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
