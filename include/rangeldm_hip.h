@@ -604,8 +604,17 @@ typedef struct rldm_train_conv_desc {
     int32_t taps;               /* 9: 3x3 pad 1 (ldm/utils.py:40-55), 1: 1x1 / Linear                             */
     int32_t stride;             /* 1 | 2 (Downsample2D, ldm/utils.py:107-116)                                      */
     int32_t mode;               /* 0 plain, 1 nearest-x2 of the input first (Upsample2D), 2 zero insertion (data
-                                   gradient of a stride-2 conv); output = (Win << (mode != 0)) / stride            */
+                                   gradient of a stride-2 conv); output = (Win << (mode != 0)) / stride;
+                                   | RLDM_TRAIN_PAD_END: end-only padding (below)                                  */
 } rldm_train_conv_desc;
+/* End-only padding, the VAE encoder's down-sampler (vae/sgm/.../model.py:164-172: one wrapped column behind W, one zero row
+ * behind H, then 3x3 stride 2 without padding), as a flag in `mode` -- the struct keeps its size.  Valid for 9 taps with
+ * stride 2, mode 0 (forward and weight gradient: output (wo, ho) under tap (dw, dh) in {-1, 0, 1}^2 reads the virtual pixel
+ * (2 wo + dw + 1, 2 ho + dh + 1); W wraps, row Hin is zero) and with stride 1, mode 2 (the data gradient: the zero-insertion
+ * conv over dy with the transposed, flipped weight copy reads (v + d - 1); W wraps in the zero-inserted space, a negative row
+ * is zero).  Anything else with the flag is a "bad conv desc"; without it every launch is what it was.  The fused and all-taps
+ * kernels have no such instance (_fused_ok: 0); rldm_train_conv_splits treats the desc like its symmetric twin. */
+#define RLDM_TRAIN_PAD_END 4
 /* y = conv(x) + bias + rowadd[b] + res (each optional); w_packed = bf16 [N][taps][ceil16(Cin)] from
  * rldm_train_pack_weights (forward copy, or the transposed copy with Cin/N swapped for the data gradient). */
 int rldm_train_conv(const rldm_train_conv_desc* d, const float* x, const void* w_packed, const float* bias, const float* rowadd,
@@ -712,6 +721,7 @@ int rldm_train_wgrad_group_pending(void);   /* queued layers (tests) */
  *                          values added as a binary tree (lanes l and l ^ 32, then ^ 16 .. ^ 1, then the four waves in order); the
  *                          result = the same two steps over the block partials (thread t adds partials t, t + 256, ... first).
  *   l1                     mse's partials and folds, for the loss and for each channel's absolute-error sum (see rldm_train_l1).
+ *   gaussian               mse's partials and folds for the KL sum (see rldm_train_gaussian); z and the backward are element-wise.
  * The RCCL all-reduce of a multi-rank step is outside this guarantee. */
 int rldm_train_deterministic(int on);
 int rldm_train_deterministic_enabled(void);
@@ -764,6 +774,18 @@ int rldm_train_mse(const float* pred, const float* target, const float* weight, 
  * train_ops.l1_host restates it in numpy. */
 int rldm_train_l1(const float* pred, const float* target, const float* wc, int B, int C, int W, int H, float* dpred, double* out,
                   void* stream);
+/* The VAE's posterior (vae/sgm/modules/distributions/distributions.py:24-64, DiagonalGaussianRegularizer): moments
+ * [B][W][H][2 Z] NHWC, mean in channels [0, Z), logvar in [Z, 2 Z); noise (B, Z, W, H) or NULL (sample_posterior = False: z = mean).
+ *   lc = clamp(logvar, -30, 20);  z[b][w][h][c] = mean + expf(0.5 lc) noise  (fp32);
+ *   *kl (device double) = (1 / B) sum 0.5 (mean^2 + exp(lc) - 1 - lc), fp64 per element, summed like rldm_train_l1's loss: element
+ *   i * 256 + t of z is lane t of partial i, the partials meet in an fp64 atomic -- or, in the deterministic mode, are folded as
+ *   mse's are.
+ * _backward, for loss = rec + kl_weight kl and kw = kl_weight / B: dmoments [B][W][H][2 Z],
+ *   dmean = dz + kw mean;  dlogvar = pass (dz noise 0.5 expf(0.5 lc) + kw 0.5 (expf(lc) - 1)),  pass = (-30 <= logvar <= 20), both
+ *   ends included (torch.clamp's gradient); noise NULL drops the first term.  train_ops.gaussian_host restates both in numpy. */
+int rldm_train_gaussian(const float* moments, const float* noise, int B, int W, int H, int Z, float* z, double* kl, void* stream);
+int rldm_train_gaussian_backward(const float* moments, const float* noise, const float* dz, float kw, int B, int W, int H, int Z,
+                                 float* dmoments, void* stream);
 int rldm_train_sqnorm(const float* g, int64_t n, double* out /*device*/, void* stream);
 typedef struct rldm_adamw_config {
     float lr, beta1, beta2, eps, weight_decay;  /* torch.optim.AdamW, ldm/train_unconditional.py:357-363           */

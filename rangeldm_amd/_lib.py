@@ -19,6 +19,7 @@ RLDM_VOXEL_RANGE, RLDM_VOXEL_MAX_SLOTS = 4, 1 << 25
 RLDM_FRECHET_SWEEP_CAP, RLDM_FRECHET_NONFINITE, RLDM_FRECHET_MAX_SWEEPS = 2, 3, 60
 # rldm_feature_scan_f64: the largest k (a row keeps k + 1 squared distances); non-finite input returns RLDM_FRECHET_NONFINITE
 RLDM_FEATURE_MAX_K = 16
+RLDM_TRAIN_PAD_END = 4  # rldm_train_conv_desc.mode flag: end-only padding
 # rldm_rangenet_layer_desc::kind (enum rldm_rangenet_kind)
 RLDM_RN_CONV1X1, RLDM_RN_CONV3X3, RLDM_RN_CONV3X3_S2, RLDM_RN_UPCONV = 0, 1, 2, 3
 
@@ -261,6 +262,8 @@ PROTOTYPES = {
     "rldm_train_unpack_output": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rldm_train_mse": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "rldm_train_l1": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "rldm_train_gaussian": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "rldm_train_gaussian_backward": (C.c_int, [_P, _P, _P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rldm_train_sqnorm": (C.c_int, [_P, C.c_int64, _P, _P]),
     "rldm_train_adamw": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(AdamWConfigC), _P]),
     "rldm_train_adamw_dyn": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(AdamWConfigC), _P, C.c_int, _P]),

@@ -70,10 +70,12 @@ __device__ inline void tr_wgrad_reduce_items(const float* __restrict__ part, int
 
 // source pixel of output pixel (b, wo, ho) under tap (dw, dh): index into the input's pixel array, or -1 for a zero.
 // mode 0: plain; 1: nearest x2 (virtual input is twice as large); 2: zero insertion (virtual odd coordinates are zeros)
-__device__ inline int src_pixel(int b, int wo, int ho, int dw, int dh, int stride, int mode, int Win, int Hin) {
+// shift: 0 for the symmetric pad; end-only padding (one wrapped column behind W, one zero row behind H) moves every tap by +1 in the
+// stride-2 forward / weight gradient and by -1 in the zero-insertion data gradient (|shift| <= 1, so one wrap step still suffices)
+__device__ inline int src_pixel(int b, int wo, int ho, int dw, int dh, int stride, int mode, int Win, int Hin, int shift) {
     const int sh = mode ? 1 : 0;
     const int Wv = Win << sh, Hv = Hin << sh;
-    int vw = wo * stride + dw, vh = ho * stride + dh;
+    int vw = wo * stride + dw + shift, vh = ho * stride + dh + shift;
     if (vh < 0 || vh >= Hv) return -1;
     vw = vw < 0 ? vw + Wv : (vw >= Wv ? vw - Wv : vw);
     if (mode == 2 && ((vw | vh) & 1)) return -1;
@@ -99,7 +101,7 @@ __device__ inline bf16x8 load_bf16x8_from_f32(const float* p, int valid, bool ve
 // ---- convolution / linear (forward and data gradient) ---------------------------------------------------------------
 struct TrConv {
     const float* x; const bf16_t* w; const float* bias; const float* rowadd; const float* res; float* y;
-    int B, Win, Hin, Cin, Cin_pad, Wout, Hout, N, taps, stride, mode, rowadd_ld, accumulate;
+    int B, Win, Hin, Cin, Cin_pad, Wout, Hout, N, taps, stride, mode, rowadd_ld, accumulate, shift;
 };
 
 // (round 5) what the fused launches fold into a conv / weight-gradient kernel (include/rangeldm_hip.h: rldm_train_fuse).  A tensor's
@@ -325,7 +327,7 @@ __global__ __launch_bounds__(256) void tr_conv_kernel(const TrConv p) {
     for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
     for (int t = 0; t < p.taps; ++t) {
         const int dw = p.taps == 9 ? t / 3 - 1 : 0, dh = p.taps == 9 ? t % 3 - 1 : 0;
-        const int sp = pxok ? src_pixel(b, wo, ho, dw, dh, p.stride, p.mode, p.Win, p.Hin) : -1;
+        const int sp = pxok ? src_pixel(b, wo, ho, dw, dh, p.stride, p.mode, p.Win, p.Hin, p.shift) : -1;
         const float* xrow = p.x + (size_t)(sp < 0 ? 0 : sp) * p.Cin + 8 * kg;
         const size_t toff = (size_t)t * p.Cin_pad;
         if (FAST) {
@@ -439,7 +441,7 @@ __global__ __launch_bounds__(256) void tr_conv_lds_kernel(const TrConv p, const 
     const float* const x1p = FU ? f.x1 : nullptr;
     auto new_tap = [&]() __attribute__((always_inline)) {
         const int dw = taps == 9 ? tap / 3 - 1 : 0, dh = taps == 9 ? tap % 3 - 1 : 0;
-        const int sp = gpx_ok ? src_pixel(sb, swo, sho, dw, dh, p.stride, p.mode, p.Win, p.Hin) : -1;
+        const int sp = gpx_ok ? src_pixel(sb, swo, sho, dw, dh, p.stride, p.mode, p.Win, p.Hin, p.shift) : -1;
         live = sp < 0 ? 0.f : 1.f;
         sp_cur = sp < 0 ? 0 : sp;
         xs = xbase + (size_t)sp_cur * Cin;
@@ -885,7 +887,7 @@ __global__ __launch_bounds__(256) void tr_conv_halo_kernel(const TrConv p, const
 // ---- weight gradient --------------------------------------------------------------------------------------------------
 struct TrWgrad {
     const float* dy; const float* x; float* dw;   // dw: partial sums [taps][slices][N][Cin], slices = grid.z * 4 waves
-    int B, Win, Hin, Cin, Wout, Hout, N, taps, stride, mode, chunk;      // chunk: pixels per wave (multiple of 16)
+    int B, Win, Hin, Cin, Wout, Hout, N, taps, stride, mode, chunk, shift;   // chunk: pixels per wave (multiple of 16); shift: src_pixel
 };
 
 // 16 consecutive channels of one pixel row: `valid` of them exist; vec: the row pointer is 16-byte aligned
@@ -939,7 +941,7 @@ __global__ __launch_bounds__(256) void tr_wgrad_kernel(const TrWgrad p) {
             validA = p.N - (n0 + seg);
             pa = p.dy + (size_t)px * p.N + n0 + seg;
             const int ho = px % p.Hout, t1 = px / p.Hout, wo = t1 % p.Wout, b = t1 / p.Wout;
-            const int sp = src_pixel(b, wo, ho, dw, dh, p.stride, p.mode, p.Win, p.Hin);
+            const int sp = src_pixel(b, wo, ho, dw, dh, p.stride, p.mode, p.Win, p.Hin, p.shift);
             if (sp >= 0) {
                 validB = p.Cin - (c0 + seg);
                 pb = p.x + (size_t)sp * p.Cin + c0 + seg;
@@ -2265,6 +2267,63 @@ __global__ __launch_bounds__(256) void tr_l1_vec_kernel(const float* __restrict_
     }
 }
 
+// rldm_train_gaussian: the VAE's diagonal Gaussian posterior.  moments [B][W][H][2 Z] NHWC (mean | logvar), noise (B, Z, W, H) or null
+// (z = mean), z [B][W][H][Z]; lc = clamp(logvar, -30, 20); z = mean + expf(0.5 lc) noise in fp32 (product and sum rounded separately).
+// kl = (1 / B) sum 0.5 (mean^2 + exp(lc) - 1 - lc) in fp64: element 256 i + t of z (NHWC order) is lane t of partial i (block_sum_d's
+// tree, tr_l1_kernel's partial); DET: the partials go to part[i] and are added by tr_fold_double_kernel, else they meet in an fp64 atomic.
+__device__ inline size_t gaussian_noise_index(size_t i, int Z, int W, int H) {
+    const int c = (int)(i % Z);
+    size_t t = i / Z;
+    const int h = (int)(t % H);
+    t /= H;
+    const int w = (int)(t % W);
+    const size_t b = t / W;
+    return ((b * Z + c) * W + w) * H + h;
+}
+__device__ inline float gaussian_clamp(float logvar) { return fminf(fmaxf(logvar, -30.f), 20.f); }
+
+template <bool DET>
+__global__ __launch_bounds__(256) void tr_gaussian_kernel(const float* __restrict__ moments, const float* __restrict__ noise, int B, int W,
+                                                          int H, int Z, float* __restrict__ z, double* __restrict__ kl) {
+    __shared__ double sh[4];
+    const size_t total = (size_t)B * W * H * Z;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    double part = 0.0;
+    if (i < total) {
+        const size_t px = i / Z;
+        const int c = (int)(i - px * Z);
+        const float mean = moments[px * (2 * Z) + c], lc = gaussian_clamp(moments[px * (2 * Z) + Z + c]);
+        float v = mean;
+        if (noise) v = __fadd_rn(mean, __fmul_rn(expf(0.5f * lc), noise[gaussian_noise_index(i, Z, W, H)]));
+        z[i] = v;
+        const double m = (double)mean, l = (double)lc;
+        part = 0.5 * (m * m + exp(l) - 1.0 - l) / (double)B;
+    }
+    part = block_sum_d(part, sh);
+    if (threadIdx.x == 0) {
+        if constexpr (DET) kl[blockIdx.x] = part;
+        else unsafeAtomicAdd(kl, part);
+    }
+}
+
+// dmoments [B][W][H][2 Z]: dmean = dz + kw mean; dlogvar = pass (dz noise 0.5 expf(0.5 lc) + kw 0.5 (expf(lc) - 1)), pass = (-30 <= logvar
+// <= 20) (torch's clamp gradient: both ends pass); noise null: the first term is dropped.  fp32, every product and sum rounded separately.
+__global__ __launch_bounds__(256) void tr_gaussian_bwd_kernel(const float* __restrict__ moments, const float* __restrict__ noise,
+                                                              const float* __restrict__ dz, float kw, int B, int W, int H, int Z,
+                                                              float* __restrict__ dmoments) {
+    const size_t total = (size_t)B * W * H * Z;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const size_t px = i / Z;
+    const int c = (int)(i - px * Z);
+    const float mean = moments[px * (2 * Z) + c], logvar = moments[px * (2 * Z) + Z + c], lc = gaussian_clamp(logvar);
+    const float g = dz[i];
+    dmoments[px * (2 * Z) + c] = __fadd_rn(g, __fmul_rn(kw, mean));
+    float dl = __fmul_rn(__fmul_rn(kw, 0.5f), __fsub_rn(expf(lc), 1.f));
+    if (noise) dl = __fadd_rn(__fmul_rn(__fmul_rn(g, noise[gaussian_noise_index(i, Z, W, H)]), __fmul_rn(0.5f, expf(0.5f * lc))), dl);
+    dmoments[px * (2 * Z) + Z + c] = (logvar >= -30.f && logvar <= 20.f) ? dl : 0.f;
+}
+
 template <bool DET = false>
 __global__ __launch_bounds__(256) void tr_sqnorm_kernel(const float* __restrict__ g, size_t n, double* __restrict__ out) {
     __shared__ double sh[4];
@@ -2599,8 +2658,24 @@ static void conv_lds_plan(int P, int N, int Cin, int taps, bool* narrow_out, int
     *ksplit_out = std::max(1, std::min(ksplit, niter));
 }
 
-int rldm_train_conv_splits(const rldm_train_conv_desc* d, int rowadd_ld) {
-    if (!d || d->stride < 1) return 1;
+// A desc's `mode` = the input transform (0, 1, 2) | RLDM_TRAIN_PAD_END.  -> *plain: the desc with the flag taken off (its symmetric twin:
+// same shapes, same launch plan), *pad: 0 | 1.  false: "bad conv desc" -- an unknown mode, or end-only padding on anything but the 3x3
+// stride-2 forward / weight gradient (mode 0) and its zero-insertion data gradient (stride 1, mode 2).
+static bool conv_desc_split(const rldm_train_conv_desc* d, rldm_train_conv_desc* plain, int* pad) {
+    *plain = *d;
+    *pad = (d->mode & RLDM_TRAIN_PAD_END) ? 1 : 0;
+    plain->mode = d->mode & ~RLDM_TRAIN_PAD_END;
+    if (!((d->taps == 1 || d->taps == 9) && (d->stride == 1 || d->stride == 2) && plain->mode >= 0 && plain->mode <= 2)) return false;
+    return !*pad || (d->taps == 9 && ((d->stride == 2 && plain->mode == 0) || (d->stride == 1 && plain->mode == 2)));
+}
+// src_pixel's tap shift of a desc
+static int conv_desc_shift(const rldm_train_conv_desc* plain, int pad) { return !pad ? 0 : (plain->mode == 2 ? -1 : 1); }
+
+int rldm_train_conv_splits(const rldm_train_conv_desc* d0, int rowadd_ld) {
+    rldm_train_conv_desc plain;
+    int pad;
+    if (!d0 || d0->stride < 1 || !conv_desc_split(d0, &plain, &pad)) return 1;
+    const rldm_train_conv_desc* d = &plain;
     const int sh = d->mode ? 1 : 0;
     const int P = d->B * ((d->Win << sh) / d->stride) * ((d->Hin << sh) / d->stride);
     if (!(P >= 64 && (rowadd_ld & 3) == 0 && d->Cin % 32 == 0)) return 1;
@@ -2717,7 +2792,8 @@ static bool conv_fuse_ok(const rldm_train_conv_desc* d, const rldm_train_fuse* f
 }
 
 int rldm_train_conv_fused_ok(const rldm_train_conv_desc* d, const rldm_train_fuse* fu, int rowadd_ld) {
-    return d && fu && d->stride >= 1 && conv_fuse_ok(d, fu, rowadd_ld) ? 1 : 0;
+    // (no fused instance reads the end-only padding: RLDM_TRAIN_PAD_END is refused like every mode past 2)
+    return d && fu && d->stride >= 1 && d->mode >= 0 && d->mode <= 2 && conv_fuse_ok(d, fu, rowadd_ld) ? 1 : 0;
 }
 
 static int train_conv_impl(const rldm_train_conv_desc* d, const rldm_train_fuse* fu, const float* x, const void* w_packed, const float* bias,
@@ -2731,14 +2807,17 @@ int rldm_train_conv(const rldm_train_conv_desc* d, const float* x, const void* w
 int rldm_train_conv_fused(const rldm_train_conv_desc* d, const rldm_train_fuse* fu, const float* x, const void* w_packed, const float* bias,
                           const float* rowadd, int rowadd_ld, const float* res, float* y, int prezeroed, void* stream) {
     RLDM_REQUIRE(d && fu, "null argument");
-    RLDM_REQUIRE(conv_fuse_ok(d, fu, rowadd_ld), "rldm_train_conv_fused: shape not supported (ask rldm_train_conv_fused_ok)");
+    RLDM_REQUIRE(rldm_train_conv_fused_ok(d, fu, rowadd_ld), "rldm_train_conv_fused: shape not supported (ask rldm_train_conv_fused_ok)");
     return train_conv_impl(d, fu, x, w_packed, bias, rowadd, rowadd_ld, res, y, prezeroed, stream);
 }
 
-static int train_conv_impl(const rldm_train_conv_desc* d, const rldm_train_fuse* fu, const float* x, const void* w_packed, const float* bias,
+static int train_conv_impl(const rldm_train_conv_desc* d0, const rldm_train_fuse* fu, const float* x, const void* w_packed, const float* bias,
                            const float* rowadd, int rowadd_ld, const float* res, float* y, int accumulate, void* stream) {
-    RLDM_REQUIRE(d && x && w_packed && y, "null argument");
-    RLDM_REQUIRE((d->taps == 1 || d->taps == 9) && (d->stride == 1 || d->stride == 2) && d->mode >= 0 && d->mode <= 2, "bad conv desc");
+    RLDM_REQUIRE(d0 && x && w_packed && y, "null argument");
+    rldm_train_conv_desc plain;
+    int pad;
+    RLDM_REQUIRE(conv_desc_split(d0, &plain, &pad), "bad conv desc");
+    const rldm_train_conv_desc* d = &plain;
     RLDM_REQUIRE(d->B > 0 && d->Win > 0 && d->Hin > 0 && d->Cin > 0 && d->N > 0, "bad shape");
     TrConv p;
     p.x = x; p.w = static_cast<const bf16_t*>(w_packed); p.bias = bias; p.rowadd = rowadd; p.res = res; p.y = y;
@@ -2747,6 +2826,7 @@ static int train_conv_impl(const rldm_train_conv_desc* d, const rldm_train_fuse*
     p.Wout = (d->Win << sh) / d->stride; p.Hout = (d->Hin << sh) / d->stride;
     RLDM_REQUIRE(p.Wout > 0 && p.Hout > 0, "empty output");
     p.N = d->N; p.taps = d->taps; p.stride = d->stride; p.mode = d->mode; p.rowadd_ld = rowadd_ld; p.accumulate = accumulate;
+    p.shift = conv_desc_shift(d, pad);
     const int P = p.B * p.Wout * p.Hout;
     dim3 grid((P + 63) / 64, (p.N + 127) / 128);
     const bool aligned = (rowadd_ld & 3) == 0;         // (vector epilogue reads the per-sample row 16 bytes at a time)
@@ -2833,6 +2913,7 @@ int rldm_train_wgrad(const rldm_train_conv_desc* d, const float* dy, const float
 }
 
 static bool wgrad_v2_shape(const rldm_train_conv_desc* d) {
+    if (d->mode < 0 || d->mode > 2) return false;       // (RLDM_TRAIN_PAD_END: the one-tap kernel)
     const int sh = d->mode ? 1 : 0;
     const int Wout = (d->Win << sh) / d->stride, Hout = (d->Hin << sh) / d->stride;
     if (!(d->stride == 1 && d->mode <= 1 && d->N % 64 == 0 && d->Cin % 64 == 0 && Hout >= 2 && Hout <= 16 && (Hout & (Hout - 1)) == 0)) return false;
@@ -2960,14 +3041,18 @@ int rldm_train_wgrad_fused(const rldm_train_conv_desc* d, const rldm_train_fuse*
     return train_wgrad_impl(d, fu, dy, x, dw, rows, rows_ld, rows_accumulate, total, stream);
 }
 
-static int train_wgrad_impl(const rldm_train_conv_desc* d, const rldm_train_fuse* fu, const float* dy, const float* x, float* dw, float* rows,
+static int train_wgrad_impl(const rldm_train_conv_desc* d0, const rldm_train_fuse* fu, const float* dy, const float* x, float* dw, float* rows,
                             int rows_ld, int rows_accumulate, float* total, void* stream) {
-    RLDM_REQUIRE(d && dy && x && dw, "null argument");
+    RLDM_REQUIRE(d0 && dy && x && dw, "null argument");
     if (flush_reduce()) return 1;                     // (the partial-tile scratch is about to be rewritten)
-    RLDM_REQUIRE((d->taps == 1 || d->taps == 9) && (d->stride == 1 || d->stride == 2) && d->mode >= 0 && d->mode <= 2, "bad conv desc");
+    rldm_train_conv_desc plain;
+    int pad;
+    RLDM_REQUIRE(conv_desc_split(d0, &plain, &pad), "bad conv desc");
+    const rldm_train_conv_desc* d = &plain;
     TrWgrad p;
     p.dy = dy; p.x = x; p.dw = dw;
     p.B = d->B; p.Win = d->Win; p.Hin = d->Hin; p.Cin = d->Cin; p.N = d->N; p.taps = d->taps; p.stride = d->stride; p.mode = d->mode;
+    p.shift = conv_desc_shift(d, pad);
     const int sh = d->mode ? 1 : 0;
     p.Wout = (d->Win << sh) / d->stride; p.Hout = (d->Hin << sh) / d->stride;
     const int P = p.B * p.Wout * p.Hout;
@@ -3375,6 +3460,34 @@ int rldm_train_l1(const float* pred, const float* target, const float* wc, int B
     tr_zero_kernel<<<1, 256, 0, st>>>(reinterpret_cast<float*>(out), 2 * (size_t)(C + 1));
     if (vec) tr_l1_vec_kernel<false><<<grid, 256, 0, st>>>(pred, target, wc, B, C, W, H, dpred, out, nparts);
     else tr_l1_kernel<false><<<grid, 256, 0, st>>>(pred, target, wc, B, C, W, H, dpred, out, nparts);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int rldm_train_gaussian(const float* moments, const float* noise, int B, int W, int H, int Z, float* z, double* kl, void* stream) {
+    RLDM_REQUIRE(moments && z && kl, "null argument");
+    RLDM_REQUIRE(B > 0 && W > 0 && H > 0 && Z > 0, "rldm_train_gaussian: B, W, H, Z >= 1");
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned nb = nblk((size_t)B * W * H * Z);
+    if (g_deterministic) {
+        double* part = nullptr;
+        if (det_partials((size_t)nb * sizeof(double), st, reinterpret_cast<void**>(&part))) return 1;
+        tr_gaussian_kernel<true><<<nb, 256, 0, st>>>(moments, noise, B, W, H, Z, z, part);
+        tr_fold_double_kernel<<<1, 256, 0, st>>>(part, (int)nb, kl);
+        TR_LAUNCH_CHECK();
+        return 0;
+    }
+    tr_zero_kernel<<<1, 256, 0, st>>>(reinterpret_cast<float*>(kl), 2);
+    tr_gaussian_kernel<false><<<nb, 256, 0, st>>>(moments, noise, B, W, H, Z, z, kl);
+    TR_LAUNCH_CHECK();
+    return 0;
+}
+
+int rldm_train_gaussian_backward(const float* moments, const float* noise, const float* dz, float kw, int B, int W, int H, int Z,
+                                 float* dmoments, void* stream) {
+    RLDM_REQUIRE(moments && dz && dmoments, "null argument");
+    RLDM_REQUIRE(B > 0 && W > 0 && H > 0 && Z > 0, "rldm_train_gaussian_backward: B, W, H, Z >= 1");
+    tr_gaussian_bwd_kernel<<<nblk((size_t)B * W * H * Z), 256, 0, (hipStream_t)stream>>>(moments, noise, dz, kw, B, W, H, Z, dmoments);
     TR_LAUNCH_CHECK();
     return 0;
 }

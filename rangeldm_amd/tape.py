@@ -1,8 +1,8 @@
 """The model-independent half of the HIP training steps: `TapeTrainer` owns the flat fp32 buffers (parameters, gradients, AdamW
 moments, optional EMA copy; state-dict views into them), the bf16 operand copies of every conv / linear weight, the host-side tape
 (`forward` of a subclass records one backward closure per op, `_run_tape` replays them in reverse) with its gradient slots, the queue
-of grouped weight gradients, the zero arena of the split-K convs and the clip + AdamW call.  `UNetTrainer` (training.py) and
-`VAEDecoderTrainer` (vae_training.py) add their networks, losses and schedules on top.  No torch autograd, no torch compute ops on
+of grouped weight gradients, the zero arena of the split-K convs and the clip + AdamW call.  `UNetTrainer` (training.py),
+`VAEDecoderTrainer` and `VAETrainer` (vae_training.py) add their networks, losses and schedules on top.  No torch autograd, no torch compute ops on
 the path; no CPU fallback."""
 import contextlib
 from collections import OrderedDict
@@ -210,7 +210,11 @@ class TapeTrainer:
         T.set_zero_arena(None)
 
     # ---- ops --------------------------------------------------------------------------------------------------
-    def _conv(self, x, name, stride=1, mode=0, rowadd=None, res=None, need_dx=True, done=None, stats=False):
+    def _conv(self, x, name, stride=1, mode=0, rowadd=None, res=None, need_dx=True, done=None, stats=False, pad=0):
+        """pad = 1 (a stride-2 layer only): end-only padding in the forward, the weight gradient and the data gradient
+        (train_ops.conv_desc)."""
+        if pad and (stride != 2 or mode != 0 or stats):
+            raise ValueError("end-only padding belongs to a plain stride-2 conv")
         w = name + ".weight"
         N, _, taps = self.layers[w][:3]
         done = done or (w, name + ".bias")
@@ -218,7 +222,7 @@ class TapeTrainer:
             y, cs_y = T.conv_fused([T.Src(x)], self.wf[w], N, taps, stride, mode, bias=self.p[name + ".bias"], want_stats=True)
             self._cs_set(y, cs_y)
         else:
-            y = T.conv(x, self.wf[w], N, taps, stride, mode, bias=self.p[name + ".bias"], rowadd=rowadd, res=res)
+            y = T.conv(x, self.wf[w], N, taps, stride, mode, bias=self.p[name + ".bias"], rowadd=rowadd, res=res, pad=pad)
 
         def bwd():
             dy = self._pop(y)
@@ -234,7 +238,7 @@ class TapeTrainer:
                         self._grad[id(rows)] = (torch.zeros(rows.shape, dtype=torch.float32, device=rows.device), True)
                     drow = self._grad[id(rows)][0][:, off:off + rowadd.shape[1]]
             T.wgrad_bias(dy, x, self.g[w], taps, stride, mode, rows=drow, total=self.g[name + ".bias"],
-                         rows_accumulate=rowadd is not None and self._row_parent.get(id(rowadd)) is not None)
+                         rows_accumulate=rowadd is not None and self._row_parent.get(id(rowadd)) is not None, pad=pad)
             self._pin(dy, x, drow)
             self._done(*done)
             if rowadd is not None and self._row_parent.get(id(rowadd)) is None:
@@ -248,7 +252,7 @@ class TapeTrainer:
                 Cin = x.shape[3]
                 cur = self._slot(x) if mode != 1 else None
                 if stride == 2:
-                    dx = T.conv(dy, wt, Cin, taps, 1, 2, out=cur, accumulate=cur is not None)
+                    dx = T.conv(dy, wt, Cin, taps, 1, 2, out=cur, accumulate=cur is not None, pad=pad)
                 elif mode == 1:
                     dx = T.sum2x2(T.conv(dy, wt, Cin, taps, 1, 0))
                 else:

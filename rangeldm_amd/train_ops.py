@@ -27,10 +27,15 @@ def empty(shape, like=None, device=None):
     return torch.empty(shape, dtype=torch.float32, device=like.device if like is not None else device)
 
 
-def conv_desc(x, N, taps, stride=1, mode=0):
+def conv_desc(x, N, taps, stride=1, mode=0, pad=0):
+    """pad: 0 the symmetric pad 1; 1 end-only padding (the VAE encoder's down-sampler: one wrapped column behind W, one zero row behind
+    H), carried as RLDM_TRAIN_PAD_END in the desc's mode -- 3x3 with stride 2, mode 0 (forward, weight gradient) or stride 1, mode 2
+    (data gradient); the library refuses anything else."""
+    if pad not in (0, 1):
+        raise ValueError(f"pad is 0 (symmetric) or 1 (end-only), not {pad!r}")
     d = _lib.TrainConvDescC()
     d.B, d.Win, d.Hin, d.Cin = x.shape
-    d.N, d.taps, d.stride, d.mode = N, taps, stride, mode
+    d.N, d.taps, d.stride, d.mode = N, taps, stride, mode | (_lib.RLDM_TRAIN_PAD_END if pad else 0)
     return d
 
 
@@ -87,9 +92,9 @@ def set_zero_arena(arena):
     _arena = arena
 
 
-def conv(x, w_packed, N, taps, stride=1, mode=0, bias=None, rowadd=None, res=None, out=None, accumulate=False):
-    """y = conv(x) + bias + rowadd[b] + res.  x (B, W, H, Cin) -> (B, Wo, Ho, N)."""
-    d = conv_desc(x, N, taps, stride, mode)
+def conv(x, w_packed, N, taps, stride=1, mode=0, bias=None, rowadd=None, res=None, out=None, accumulate=False, pad=0):
+    """y = conv(x) + bias + rowadd[b] + res.  x (B, W, H, Cin) -> (B, Wo, Ho, N).  pad: see conv_desc."""
+    d = conv_desc(x, N, taps, stride, mode, pad)
     Wo, Ho = out_size(x.shape[1], x.shape[2], stride, mode)
     y = out
     if y is None and _arena is not None and \
@@ -104,15 +109,15 @@ def conv(x, w_packed, N, taps, stride=1, mode=0, bias=None, rowadd=None, res=Non
     return y
 
 
-def wgrad(dy, x, dw, taps, stride=1, mode=0):
+def wgrad(dy, x, dw, taps, stride=1, mode=0, pad=0):
     """dw (N, Cin, k, k) += dy (x) x  (dw is a view into the zeroed flat gradient buffer)."""
-    d = conv_desc(x, dy.shape[3], taps, stride, mode)
+    d = conv_desc(x, dy.shape[3], taps, stride, mode, pad)
     _chk(_lib.lib().rldm_train_wgrad(C.byref(d), _p(dy), _p(x), _p(dw), _s(x)), "rldm_train_wgrad")
 
 
-def wgrad_bias(dy, x, dw, taps, stride=1, mode=0, rows=None, total=None, rows_accumulate=False):
+def wgrad_bias(dy, x, dw, taps, stride=1, mode=0, rows=None, total=None, rows_accumulate=False, pad=0):
     """wgrad + colsum in one call (one launch where the all-taps kernel applies)."""
-    d = conv_desc(x, dy.shape[3], taps, stride, mode)
+    d = conv_desc(x, dy.shape[3], taps, stride, mode, pad)
     _chk(_lib.lib().rldm_train_wgrad_bias(C.byref(d), _p(dy), _p(x), _p(dw), _p(rows), 0 if rows is None else rows.stride(0),
                                           1 if rows_accumulate else 0, _p(total), _s(x)), "rldm_train_wgrad_bias")
 
@@ -280,6 +285,32 @@ def l1(pred_nhwc, target_nchw, channel_weights):
     _chk(_lib.lib().rldm_train_l1(_p(pred_nhwc), _p(target_nchw), _p(channel_weights), B, Cc, W, H, _p(dpred), _p(out),
                                   _s(pred_nhwc)), "rldm_train_l1")
     return out[0], dpred, out[1:]
+
+
+def gaussian(moments_nhwc, noise_nchw=None):
+    """The VAE's posterior: moments (B, W, H, 2 Z) NHWC (mean | logvar), noise (B, Z, W, H) or None (z = mean) -> (z (B, W, H, Z) =
+    mean + exp(0.5 lc) noise with lc = clamp(logvar, -30, 20), kl: 0-d float64 device tensor = (1 / B) sum 0.5 (mean^2 + exp(lc) - 1 - lc))."""
+    B, W, H, Z2 = moments_nhwc.shape
+    Z = Z2 // 2
+    if Z2 % 2 or (noise_nchw is not None and tuple(noise_nchw.shape) != (B, Z, W, H)):
+        raise ValueError(f"gaussian: moments {tuple(moments_nhwc.shape)} (NHWC) need an even channel count and noise {(B, Z, W, H)}")
+    z = empty((B, W, H, Z), moments_nhwc)
+    kl = torch.empty((), dtype=torch.float64, device=moments_nhwc.device)
+    _chk(_lib.lib().rldm_train_gaussian(_p(moments_nhwc), _p(noise_nchw), B, W, H, Z, _p(z), _p(kl), _s(moments_nhwc)),
+         "rldm_train_gaussian")
+    return z, kl
+
+
+def gaussian_backward(moments_nhwc, noise_nchw, dz_nhwc, kw):
+    """-> dmoments (B, W, H, 2 Z) for loss = rec + kl_weight kl, kw = kl_weight / B: dmean = dz + kw mean; dlogvar = pass (dz noise 0.5
+    exp(0.5 lc) + kw 0.5 (exp(lc) - 1)), pass = (-30 <= logvar <= 20); noise None: the first term of dlogvar is dropped."""
+    B, W, H, Z2 = moments_nhwc.shape
+    if tuple(dz_nhwc.shape) != (B, W, H, Z2 // 2):
+        raise ValueError(f"gaussian_backward: dz {tuple(dz_nhwc.shape)} for moments {tuple(moments_nhwc.shape)}")
+    dm = torch.empty_like(moments_nhwc)
+    _chk(_lib.lib().rldm_train_gaussian_backward(_p(moments_nhwc), _p(noise_nchw), _p(dz_nhwc), float(kw), B, W, H, Z2 // 2, _p(dm),
+                                                 _s(moments_nhwc)), "rldm_train_gaussian_backward")
+    return dm
 
 
 def sqnorm(g):
@@ -613,3 +644,26 @@ def sqnorm_host(g):
     J = (n + nb * 256 - 1) // (nb * 256)
     sq = np.concatenate([g * g, np.zeros(J * nb * 256 - n, np.float64)]).reshape(J, nb, 256)
     return _fold_double(_block_sum(_fold(sq, axis=0)))
+
+
+def gaussian_host(moments_nhwc, noise_nchw=None, dz_nhwc=None, kw=0.0, dtype=np.float64):
+    """`gaussian` and `gaussian_backward` restated in numpy, evaluated in `dtype` (host arrays in and out): -> (z (B, W, H, Z), kl,
+    dmoments (B, W, H, 2 Z) or None without dz).  lc = clamp(logvar, -30, 20); z = mean + exp(0.5 lc) noise; kl = (1 / B) sum 0.5
+    (mean^2 + exp(lc) - 1 - lc); dmean = dz + kw mean; dlogvar = pass (dz noise 0.5 exp(0.5 lc) + kw 0.5 (exp(lc) - 1)) with
+    pass = (-30 <= logvar <= 20); noise None: z = mean and the noise term of dlogvar is dropped."""
+    m = np.asarray(moments_nhwc).astype(dtype)
+    Z = m.shape[-1] // 2
+    mean, logvar = m[..., :Z], m[..., Z:]
+    lc = np.clip(logvar, dtype(-30.0), dtype(20.0))
+    n = None if noise_nchw is None else np.asarray(noise_nchw).astype(dtype).transpose(0, 2, 3, 1)
+    half = dtype(0.5)
+    z = mean if n is None else mean + np.exp(half * lc) * n
+    kl = (half * (mean.astype(np.float64) ** 2 + np.exp(lc.astype(np.float64)) - 1.0 - lc)).sum() / m.shape[0]
+    if dz_nhwc is None:
+        return z, kl, None
+    dz, kw = np.asarray(dz_nhwc).astype(dtype), dtype(kw)
+    dl = kw * half * (np.exp(lc) - dtype(1.0))
+    if n is not None:
+        dl = dz * n * (half * np.exp(half * lc)) + dl
+    keep = (logvar >= -30.0) & (logvar <= 20.0)
+    return z, kl, np.concatenate([dz + kw * mean, np.where(keep, dl, dtype(0.0))], axis=-1)

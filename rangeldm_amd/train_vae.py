@@ -1,7 +1,12 @@
-"""python -m rangeldm_amd.train_vae: fine-tune the VAE's decoder against its frozen encoder (rangeldm_amd/vae_training.py).
+"""python -m rangeldm_amd.train_vae: fine-tune the VAE's decoder against its frozen encoder, or the whole VAE (rangeldm_amd/vae_training.py).
 
     python -m rangeldm_amd.train_vae --weights DIR | --sgm-ckpt F --sgm-yaml Y  [--input NPY_DIR] --out DIR --steps N
+                                     [--trainable decoder|all] [--kl-weight 1e-6]
                                      [--batch-size 8] [--lr 4.5e-6] [--mode] [--seed S] [--log-every K] [--deterministic]
+
+--trainable decoder (the default) leaves the encoder, and with it the latent space, as it is.  --trainable all trains encoder and
+decoder jointly with loss = L1 + kl_weight * kl and adds "kl" to every log line; it moves the latent space, so UNets trained on the old
+latents no longer apply and scaling_factor must be estimated again.
 
 --input holds the (2, W, H) .npy range images `evaluate vae --input` reads (batches walk the sorted files and wrap around); without
 it the run trains on the synthetic batch of `evaluate vae`.  Without --weights / --sgm-ckpt the synthetic weights of `evaluate vae`
@@ -25,6 +30,9 @@ def build_parser():
     ap.add_argument("--input", default=None, help="directory of (2, W, H) .npy range images (default: synthetic batch)")
     ap.add_argument("--out", required=True, help="output directory: OUT/vae/ is written")
     ap.add_argument("--steps", type=int, required=True)
+    ap.add_argument("--trainable", choices=("decoder", "all"), default="decoder",
+                    help="decoder: the encoder stays frozen; all: encoder + decoder with the KL term (moves the latent space)")
+    ap.add_argument("--kl-weight", type=float, default=1e-6, help="weight of the KL term (--trainable all)")
     ap.add_argument("--batch-size", type=int, default=8)
     ap.add_argument("--lr", type=float, default=4.5e-6)
     ap.add_argument("--mode", action="store_true", help="decode the posterior's mode instead of a sample")
@@ -37,15 +45,21 @@ def build_parser():
 def check_args(a):
     if a.steps < 1 or a.batch_size < 1 or a.log_every < 1:
         raise ValueError("--steps, --batch-size and --log-every must be at least 1")
+    if a.kl_weight < 0:
+        raise ValueError("--kl-weight must not be negative")
     if a.weights and a.sgm_ckpt:
         raise ValueError("--weights and --sgm-ckpt exclude each other")
     if a.sgm_yaml and not a.sgm_ckpt:
         raise ValueError("--sgm-yaml goes with --sgm-ckpt")
 
 
-def log_record(step, loss, abs_sums, pixels):
-    """One log line: the loss of `step` (1-based) and the per-channel MAE = abs_sums[c] / pixels (pixels = B W H)."""
-    return {"step": int(step), "loss": float(loss), "mae": [float(s) / float(pixels) for s in abs_sums]}
+def log_record(step, loss, abs_sums, pixels, kl=None):
+    """One log line: the loss of `step` (1-based) and the per-channel MAE = abs_sums[c] / pixels (pixels = B W H); kl (--trainable all):
+    the KL term, unweighted."""
+    rec = {"step": int(step), "loss": float(loss), "mae": [float(s) / float(pixels) for s in abs_sums]}
+    if kl is not None:
+        rec["kl"] = float(kl)
+    return rec
 
 
 def batch_files(files, step, batch_size):
@@ -74,13 +88,17 @@ def main(argv=None):
     check_args(a)
     from .inference_conditional import load_batch
     from .vae import AutoencoderKLHIP
-    from .vae_training import VAEDecoderTrainer, training_step
+    from .vae_training import VAEDecoderTrainer, VAETrainer, training_step
     cfg, sd = load_model(a)
     dev = torch.device("cuda", torch.cuda.current_device())
     vae = AutoencoderKLHIP(cfg, device=dev)
     vae.load_state_dict(sd)
     sd = vae.state_dict()                                # (diffusers keys, whatever layout the checkpoint had)
-    trainer = VAEDecoderTrainer(cfg, sd, device=dev, lr=a.lr, deterministic=a.deterministic)
+    everything = a.trainable == "all"
+    if everything:
+        trainer = VAETrainer(cfg, sd, device=dev, lr=a.lr, kl_weight=a.kl_weight, deterministic=a.deterministic)
+    else:
+        trainer = VAEDecoderTrainer(cfg, sd, device=dev, lr=a.lr, deterministic=a.deterministic)
     shape = (cfg.in_channels, *cfg.sample_size)
     files = sorted(glob.glob(os.path.join(a.input, "*.npy"))) if a.input else None
     if files is not None and not files:
@@ -95,9 +113,12 @@ def main(argv=None):
                 raise ValueError(f"range images of shape {tuple(x.shape[1:])}, the VAE expects {shape}")
         else:
             x = load_batch(None, a.batch_size, shape, a.seed)
-        loss = training_step(trainer, vae, x.to(dev), sample_posterior=not a.mode, generator=gen)
+        if everything:
+            loss = trainer.train_step(x.to(dev), sample_posterior=not a.mode, generator=gen)
+        else:
+            loss = training_step(trainer, vae, x.to(dev), sample_posterior=not a.mode, generator=gen)
         if (step + 1) % a.log_every == 0 or step + 1 == a.steps:
-            last = log_record(step + 1, loss, trainer.last_abs_sums.cpu().tolist(), pixels)
+            last = log_record(step + 1, loss, trainer.last_abs_sums.cpu().tolist(), pixels, trainer.last_kl if everything else None)
             print(json.dumps(last), flush=True)
     trainer.save_pretrained(a.out)
     return last

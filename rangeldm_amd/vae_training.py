@@ -1,16 +1,22 @@
-"""VAE decoder fine-tuning on MI355X: the decoder of the range-image VAE trained against its frozen encoder with the reference's
-reconstruction term before the discriminator starts (channel-weighted L1, summed over the image and divided by the batch --
-`GeneralLPIPSWithDiscriminator` with logvar = 0, perceptual_weight = 0, range_weight = 40, intensity_weight = 10).  The latent
-space does not move: every trained UNet and every captured sampler stays valid.
+"""VAE training on MI355X, the reference's reconstruction phase before its discriminator starts (`GeneralLPIPSWithDiscriminator`
+with logvar = 0, perceptual_weight = 0, range_weight = 40, intensity_weight = 10: channel-weighted L1, summed over the image and divided
+by the batch).
 
-`VAEDecoderTrainer` (on `TapeTrainer`, tape.py) drives the op-level HIP kernels of rangeldm_amd/csrc/train.hip through the same
-host-side tape as `UNetTrainer`: 3x3 / 1x1 stride-1 convs, nearest x2 + conv, GroupNorm + SiLU, residual adds; the loss is
-rldm_train_l1.  Not built: encoder gradients and the KL term (the training convs have no end-only padding, which the encoder's two
-down-samplers use), the discriminator, EMA, a captured step graph, gradient exchange between ranks.  No torch autograd, no torch
-compute ops on the path; no CPU fallback.
+`VAEDecoderTrainer` trains the decoder against the frozen encoder.  The latent space does not move: every trained UNet and every
+captured sampler stays valid.
 
-Parity: tests/test_vae_training_gpu.py compares every parameter gradient, and the parameters after optimizer steps, with torch
-autograd / torch.optim.Adam on the oracle (oracle/vae.py)."""
+`VAETrainer` trains encoder and decoder jointly, as vae/sgm/models/autoencoder.py does: loss = L1 + kl_weight * kl with the
+reference's `regularization_weights: {kl_loss: 1e-6}`.  TRAINING THE ENCODER MOVES THE LATENT SPACE: a UNet trained on the old
+latents no longer applies to the new VAE, and `scaling_factor` (1 / std of the latents) must be estimated again before one is trained.
+
+Both sit on `TapeTrainer` (tape.py) and drive the op-level HIP kernels of rangeldm_amd/csrc/train.hip through the same host-side tape as
+`UNetTrainer`: 3x3 / 1x1 stride-1 convs, nearest x2 + conv, the encoder's end-padded stride-2 conv (train_ops.conv_desc, pad = 1),
+GroupNorm + SiLU, residual adds; the posterior is rldm_train_gaussian, the loss rldm_train_l1.  Not built: the discriminator, a
+trainable `logvar` of the loss (it stays at its initial 0, the reference's `learn_logvar: False`), the BEV / perceptual terms, EMA, a
+captured step graph, gradient exchange between ranks.  No torch autograd, no torch compute ops on the path; no CPU fallback.
+
+Parity: tests/test_vae_training_gpu.py and tests/test_vae_encoder_training_gpu.py compare every parameter gradient, and the parameters
+after optimizer steps, with torch autograd / torch.optim.Adam on the oracle (oracle/vae.py)."""
 import os
 from collections import OrderedDict
 
@@ -34,12 +40,22 @@ def decoder_blocks(cfg):
     return out + [("norm_out", "decoder.conv_norm_out"), ("conv_out", "decoder.conv_out")]
 
 
-def decoder_param_names(cfg, shapes=None):
-    """The `decoder.*` keys of vae_param_shapes(cfg) in the order the forward tape first reads them (inside a resnet: norm1, conv1,
-    norm2, conv_shortcut, conv2), so backward finishes them in exactly the reverse order."""
-    shapes = shapes if shapes is not None else vae_param_shapes(cfg)
+def encoder_blocks(cfg):
+    """The encoder's layers in forward (tape) order, as oracle.vae.vae_encode visits them: [(kind, prefix)], kind in conv_in / resnet /
+    downsample / norm_out / conv_out."""
+    L = len(cfg.ch_mult)
+    out = [("conv_in", "encoder.conv_in")]
+    for i in range(L):
+        out += [("resnet", f"encoder.down_blocks.{i}.resnets.{j}") for j in range(cfg.num_res_blocks)]
+        if i != L - 1:
+            out.append(("downsample", f"encoder.down_blocks.{i}.downsamplers.0.conv"))
+    return out + [("resnet", "encoder.mid_block.resnets.0"), ("resnet", "encoder.mid_block.resnets.1"),
+                  ("norm_out", "encoder.conv_norm_out"), ("conv_out", "encoder.conv_out")]
+
+
+def _param_names(blocks, shapes, side):
     names = []
-    for kind, p in decoder_blocks(cfg):
+    for kind, p in blocks:
         layers = [p]
         if kind == "resnet":
             layers = [p + ".norm1", p + ".conv1", p + ".norm2"]
@@ -48,8 +64,19 @@ def decoder_param_names(cfg, shapes=None):
             layers.append(p + ".conv2")
         for l in layers:
             names += [l + ".weight", l + ".bias"]
-    assert sorted(names) == sorted(k for k in shapes if k.startswith("decoder."))
+    assert sorted(names) == sorted(k for k in shapes if k.startswith(side))
     return names
+
+
+def decoder_param_names(cfg, shapes=None):
+    """The `decoder.*` keys of vae_param_shapes(cfg) in the order the forward tape first reads them (inside a resnet: norm1, conv1,
+    norm2, conv_shortcut, conv2), so backward finishes them in exactly the reverse order."""
+    return _param_names(decoder_blocks(cfg), shapes if shapes is not None else vae_param_shapes(cfg), "decoder.")
+
+
+def encoder_param_names(cfg, shapes=None):
+    """The `encoder.*` keys in the order the forward tape first reads them (see decoder_param_names)."""
+    return _param_names(encoder_blocks(cfg), shapes if shapes is not None else vae_param_shapes(cfg), "encoder.")
 
 
 def merged_state_dict(encoder_source, decoder_sd):
@@ -66,22 +93,21 @@ def save_vae_dir(output_dir, cfg, state_dict):
     save_model_dir(os.path.join(output_dir, "vae"), vae_config_to_diffusers(cfg), sd)
 
 
-class VAEDecoderTrainer(TapeTrainer):
-    def __init__(self, config, state_dict, device="cuda", lr=4.5e-6, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 max_grad_norm=None, channel_weights=(40.0, 10.0), deterministic=False):
-        """The defaults are the reference's: torch.optim.Adam (AdamW with zero decay is Adam) at base_learning_rate 4.5e-6, no
-        clipping, range_weight 40 / intensity_weight 10.  state_dict may hold the whole VAE: the encoder's tensors are kept as
-        they are (handed on by load_into / save_pretrained), never read by a kernel of this class.
-        deterministic: every kernel of this trainer runs in the library's deterministic mode (rldm_train_deterministic), as
-        UNetTrainer(deterministic=True): the same inputs give the same parameter bits."""
+class _VAETape(TapeTrainer):
+    """What the two VAE trainers share: the hyper-parameters, the resnet block, the decoder walk, the optimizer step and the training
+    state."""
+
+    def _init_vae(self, config, state_dict, names, no_dx, device, lr, betas, eps, weight_decay, max_grad_norm, channel_weights,
+                  deterministic):
         self.cfg = config if isinstance(config, VAEConfig) else VAEConfig(**config)
         if len(channel_weights) != self.cfg.out_channels:
             raise ValueError(f"{len(channel_weights)} channel weights for {self.cfg.out_channels} output channels")
         shapes = vae_param_shapes(self.cfg)
-        names = decoder_param_names(self.cfg, shapes)
-        self._frozen = OrderedDict((k, v) for k, v in state_dict.items() if k in shapes and not k.startswith("decoder."))
-        self._init_parameters(OrderedDict((n, shapes[n]) for n in names), names, state_dict, device,
-                              no_dx=("decoder.conv_in.weight",), deterministic=deterministic)
+        names = names(self.cfg, shapes)
+        trained = set(names)
+        self._frozen = OrderedDict((k, v) for k, v in state_dict.items() if k in shapes and k not in trained)
+        self._init_parameters(OrderedDict((n, shapes[n]) for n in names), names, state_dict, device, no_dx=no_dx,
+                              deterministic=deterministic)
         self.hp = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
         self.channel_weights = torch.tensor([float(w) for w in channel_weights], dtype=torch.float32, device=self.device)
         self.last_abs_sums = None
@@ -94,23 +120,18 @@ class VAEDecoderTrainer(TapeTrainer):
         sc = self._conv(x, p + ".conv_shortcut") if (p + ".conv_shortcut.weight") in self.shapes else x
         return self._conv(h, p + ".conv2", res=sc)
 
-    def forward(self, z_nchw):
-        """z (B, z_channels, W / f, H / f) fp32 on the device, as the encoder emits it (not multiplied by scaling_factor)
-        -> the reconstruction (B, W, H, out_channels) NHWC.  Records the tape for `backward`."""
-        with self._mode():
-            if z_nchw.shape[1] != self.cfg.z_channels:
-                raise ValueError(f"latent has {z_nchw.shape[1]} channels, the decoder expects {self.cfg.z_channels}")
-            self._begin_tape()
-            h = T.pack_input(z_nchw.to(self.device).float().contiguous(), False)
-            for kind, p in decoder_blocks(self.cfg):
-                if kind == "resnet":
-                    h = self._resnet(h, p)
-                elif kind == "norm_out":
-                    h = self._gn(h, p, True)
-                else:
-                    h = self._conv(h, p, mode=1 if kind == "upsample" else 0, need_dx=kind != "conv_in")
-            self._out = h
-            return h
+    def _decode(self, h, dz):
+        """The decoder on the tape: z (B, W / f, H / f, z_channels) NHWC -> the reconstruction (B, W, H, out_channels) NHWC, kept as
+        `_out`.  dz: conv_in computes the gradient of z."""
+        for kind, p in decoder_blocks(self.cfg):
+            if kind == "resnet":
+                h = self._resnet(h, p)
+            elif kind == "norm_out":
+                h = self._gn(h, p, True)
+            else:
+                h = self._conv(h, p, mode=1 if kind == "upsample" else 0, need_dx=dz or kind != "conv_in")
+        self._out = h
+        return h
 
     def sample_nchw(self):
         """The last forward's reconstruction as (B, out_channels, W, H)."""
@@ -129,34 +150,10 @@ class VAEDecoderTrainer(TapeTrainer):
             self._clip_adamw(self.hp["lr"])
             return self.hp["lr"]
 
-    def train_step(self, z_nchw, target_nchw, as_float=False):
-        """pred = decoder(z); loss = (1 / B) sum wc[c] |pred - target|; backward; step.  Returns the loss: a 0-d float64 device
-        tensor (no host sync), or a Python float with as_float.  `last_abs_sums`: float64 (C,) device, the unweighted sum of
-        |pred - target| per channel (MAE of channel c = last_abs_sums[c] / (B W H))."""
-        with self._mode():
-            pred = self.forward(z_nchw)
-            loss, dpred, self.last_abs_sums = T.l1(pred, target_nchw.to(self.device).float().contiguous(), self.channel_weights)
-            self.backward(dpred)
-            self.optimizer_step()
-        return float(loss) if as_float else loss
-
     # ---- weights ----------------------------------------------------------------------------------------------
     def full_state_dict(self):
-        """The whole VAE: the frozen encoder's tensors as they were given, the decoder's fp32 masters."""
+        """The whole VAE: the tensors this trainer does not train as they were given, the fp32 masters of those it does."""
         return merged_state_dict(self._frozen, self.state_dict())
-
-    def load_into(self, vae):
-        """Hand the trained decoder (and the unchanged encoder) to an AutoencoderKLHIP: its load_state_dict advances the VAE's
-        generation counter, so every sampler built on it plans again."""
-        enc = self._frozen if self._frozen else {k: v for k, v in vae.state_dict().items() if not k.startswith("decoder.")}
-        return vae.load_state_dict(merged_state_dict(enc, self.state_dict()))
-
-    def save_pretrained(self, output_dir):
-        """`output_dir/vae/` as AutoencoderKLHIP.from_pretrained reads it; the encoder's weights pass through from the state dict
-        the trainer was given."""
-        if not self._frozen:
-            raise RuntimeError("save_pretrained writes a whole VAE: the trainer was built from decoder weights only")
-        save_vae_dir(output_dir, self.cfg, self.full_state_dict())
 
     def save_state(self, path):
         """Everything a resumed run needs: parameters, Adam moments, step counter."""
@@ -173,6 +170,134 @@ class VAEDecoderTrainer(TapeTrainer):
         self.global_step = int(st["global_step"])
         self.grads.zero_()
         self.repack()
+
+
+class VAEDecoderTrainer(_VAETape):
+    def __init__(self, config, state_dict, device="cuda", lr=4.5e-6, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                 max_grad_norm=None, channel_weights=(40.0, 10.0), deterministic=False):
+        """The defaults are the reference's: torch.optim.Adam (AdamW with zero decay is Adam) at base_learning_rate 4.5e-6, no
+        clipping, range_weight 40 / intensity_weight 10.  state_dict may hold the whole VAE: the encoder's tensors are kept as
+        they are (handed on by load_into / save_pretrained), never read by a kernel of this class.
+        deterministic: every kernel of this trainer runs in the library's deterministic mode (rldm_train_deterministic), as
+        UNetTrainer(deterministic=True): the same inputs give the same parameter bits."""
+        self._init_vae(config, state_dict, decoder_param_names, ("decoder.conv_in.weight",), device, lr, betas, eps, weight_decay,
+                       max_grad_norm, channel_weights, deterministic)
+
+    def forward(self, z_nchw):
+        """z (B, z_channels, W / f, H / f) fp32 on the device, as the encoder emits it (not multiplied by scaling_factor)
+        -> the reconstruction (B, W, H, out_channels) NHWC.  Records the tape for `backward`."""
+        with self._mode():
+            if z_nchw.shape[1] != self.cfg.z_channels:
+                raise ValueError(f"latent has {z_nchw.shape[1]} channels, the decoder expects {self.cfg.z_channels}")
+            self._begin_tape()
+            return self._decode(T.pack_input(z_nchw.to(self.device).float().contiguous(), False), dz=False)
+
+    def train_step(self, z_nchw, target_nchw, as_float=False):
+        """pred = decoder(z); loss = (1 / B) sum wc[c] |pred - target|; backward; step.  Returns the loss: a 0-d float64 device
+        tensor (no host sync), or a Python float with as_float.  `last_abs_sums`: float64 (C,) device, the unweighted sum of
+        |pred - target| per channel (MAE of channel c = last_abs_sums[c] / (B W H))."""
+        with self._mode():
+            pred = self.forward(z_nchw)
+            loss, dpred, self.last_abs_sums = T.l1(pred, target_nchw.to(self.device).float().contiguous(), self.channel_weights)
+            self.backward(dpred)
+            self.optimizer_step()
+        return float(loss) if as_float else loss
+
+    def load_into(self, vae):
+        """Hand the trained decoder (and the unchanged encoder) to an AutoencoderKLHIP: its load_state_dict advances the VAE's
+        generation counter, so every sampler built on it plans again."""
+        enc = self._frozen if self._frozen else {k: v for k, v in vae.state_dict().items() if not k.startswith("decoder.")}
+        return vae.load_state_dict(merged_state_dict(enc, self.state_dict()))
+
+    def save_pretrained(self, output_dir):
+        """`output_dir/vae/` as AutoencoderKLHIP.from_pretrained reads it; the encoder's weights pass through from the state dict
+        the trainer was given."""
+        if not self._frozen:
+            raise RuntimeError("save_pretrained writes a whole VAE: the trainer was built from decoder weights only")
+        save_vae_dir(output_dir, self.cfg, self.full_state_dict())
+
+
+class VAETrainer(_VAETape):
+    def __init__(self, config, state_dict, device="cuda", lr=4.5e-6, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                 max_grad_norm=None, kl_weight=1e-6, channel_weights=(40.0, 10.0), deterministic=False):
+        """Encoder and decoder trained jointly; the defaults are the reference's (VAEDecoderTrainer's, and kl_loss: 1e-6).  The
+        parameters are every key of vae_param_shapes in tape order: the encoder as oracle.vae.vae_encode visits it, then the
+        decoder.  Training the encoder moves the latent space: UNets trained on the old latents no longer apply, and scaling_factor
+        must be estimated again (module docstring).  deterministic: as VAEDecoderTrainer."""
+        self._init_vae(config, state_dict, lambda cfg, shapes: encoder_param_names(cfg, shapes) + decoder_param_names(cfg, shapes),
+                       ("encoder.conv_in.weight",), device, lr, betas, eps, weight_decay, max_grad_norm, channel_weights, deterministic)
+        self.kl_weight = float(kl_weight)
+        self.last_kl = None
+        self._moments = self._z = None
+
+    def _encode(self, h):
+        for kind, p in encoder_blocks(self.cfg):
+            if kind == "resnet":
+                h = self._resnet(h, p)
+            elif kind == "norm_out":
+                h = self._gn(h, p, True)
+            elif kind == "downsample":
+                h = self._conv(h, p, stride=2, pad=1)
+            else:
+                h = self._conv(h, p, need_dx=kind != "conv_in")
+        return h
+
+    def _gaussian(self, moments, noise):
+        """z = mean + std noise (noise None: z = mean) and the KL term on the tape; backward adds kl_weight d(kl) / d(moments)."""
+        z, self.last_kl = T.gaussian(moments, noise)
+        kw = self.kl_weight / moments.shape[0]
+
+        def bwd():
+            self._acc(moments, T.gaussian_backward(moments, noise, self._pop(z), kw), True)
+        self._tape.append(bwd)
+        return z
+
+    def forward(self, images, noise=None):
+        """images (B, in_channels, W, H) fp32; noise (B, z_channels, W / f, H / f), or None for z = mean -> the reconstruction
+        (B, W, H, out_channels) NHWC.  Records the tape for `backward`; `last_kl` and `moments()` are this pass's."""
+        with self._mode():
+            if images.shape[1] != self.cfg.in_channels:
+                raise ValueError(f"images have {images.shape[1]} channels, the encoder expects {self.cfg.in_channels}")
+            self._begin_tape()
+            self._moments = self._encode(T.pack_input(images.to(self.device).float().contiguous(), False))
+            if noise is not None:
+                noise = noise.to(self.device).float().contiguous()
+            self._z = self._gaussian(self._moments, noise)
+            return self._decode(self._z, dz=True)
+
+    def moments(self):
+        """The last forward's moments as (B, 2 z_channels, W / f, H / f): [mean | logvar], what `vae.encode` returns."""
+        return T.unpack_output(self._moments)
+
+    def latents(self):
+        """The last forward's z as (B, z_channels, W / f, H / f): what its decoder saw."""
+        return T.unpack_output(self._z)
+
+    def train_step(self, images, noise=None, generator=None, sample_posterior=True, as_float=False):
+        """moments = encoder(images); z = mean + std noise (sample_posterior=False: z = mean); pred = decoder(z);
+        loss = (1 / B) sum wc[c] |pred - images| + kl_weight kl; backward through decoder, posterior and encoder; one Adam step over
+        all parameters.  noise: (B, z_channels, W / f, H / f); None draws it on the host from `generator`, as the reference does.
+        Returns the loss: a 0-d float64 device tensor (no host sync), or a Python float with as_float.  `last_abs_sums` as
+        VAEDecoderTrainer's; `last_kl`: the KL term, a 0-d float64 device tensor."""
+        images = images.to(self.device).float().contiguous()
+        if sample_posterior and noise is None:
+            f = self.cfg.downscale
+            noise = torch.randn((images.shape[0], self.cfg.z_channels, images.shape[2] // f, images.shape[3] // f), generator=generator)
+        with self._mode():
+            pred = self.forward(images, noise if sample_posterior else None)
+            rec, dpred, self.last_abs_sums = T.l1(pred, images, self.channel_weights)
+            self.backward(dpred)
+            self.optimizer_step()
+        loss = rec + self.kl_weight * self.last_kl          # (two device scalars, for the log: no kernel reads the sum)
+        return float(loss) if as_float else loss
+
+    def load_into(self, vae):
+        """Hand the trained VAE to an AutoencoderKLHIP (see VAEDecoderTrainer.load_into)."""
+        return vae.load_state_dict(self.full_state_dict())
+
+    def save_pretrained(self, output_dir):
+        """`output_dir/vae/` as AutoencoderKLHIP.from_pretrained reads it."""
+        save_vae_dir(output_dir, self.cfg, self.full_state_dict())
 
 
 def training_step(trainer, vae, images, sample_posterior=True, generator=None, noise=None, as_float=False):

@@ -4,11 +4,14 @@ encode + posterior sample on the inference kernels, decoder forward, L1, backwar
 eager launches (no captured step graph exists for this trainer).
 
     python tools/bench_vae_train.py [--batch 8] [--steps 10] [--warmup 3] [--repeats 5] [--no-unet] [--deterministic]
+                                    [--trainable decoder|all]
 
 After the warm-up, --repeats timed runs of --steps steps each (a host clock around work that ends in a device synchronise): median
 [min, max].  Achieved TFLOP/s counts 3 x AutoencoderKLHIP.decode_flops (decoder forward + backward; the encode is not counted).  In the
 same process the UNet step of tools/bench_train.py (VAE encode + UNet forward / backward / AdamW / EMA from captured step graphs) is
-timed the same way, interleaved with the decoder runs, for scale.  One JSON line."""
+timed the same way, interleaved with the decoder runs, for scale.  --trainable all adds the whole-VAE step (`VAETrainer.train_step`:
+encoder, posterior, decoder, L1 + KL, backward through all three, Adam over every parameter; noise drawn on the host as in
+`training_step`), interleaved with the other two in the same run (samples/s only: the library counts no encoder FLOPs).  One JSON line."""
 import argparse
 import json
 import os
@@ -33,6 +36,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--no-unet", action="store_true", help="skip the UNet step (a profiler run wants the decoder step alone)")
     ap.add_argument("--deterministic", action="store_true", help="VAEDecoderTrainer(deterministic=True)")
+    ap.add_argument("--trainable", choices=("decoder", "all"), default="decoder", help="all: also time VAETrainer's whole-VAE step")
     ap.add_argument("--seed", type=int, default=20240310)
     a = ap.parse_args()
     from rangeldm_amd import _lib
@@ -40,7 +44,7 @@ def main():
     from rangeldm_amd.params import unet_param_shapes, vae_param_shapes
     from rangeldm_amd.synth import normal, synth_state_dict
     from rangeldm_amd.vae import AutoencoderKLHIP
-    from rangeldm_amd.vae_training import VAEDecoderTrainer, training_step
+    from rangeldm_amd.vae_training import VAEDecoderTrainer, VAETrainer, training_step
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
     p = PRESETS["RangeLDM"]
@@ -60,6 +64,15 @@ def main():
         for i in range(n):
             losses.append(training_step(tr, vae, imgs[i], generator=gen))
 
+    all_steps, losses_all = None, []
+    if a.trainable == "all":
+        tra = VAETrainer(cfg, sd, device=dev, deterministic=a.deterministic)
+        agen = torch.Generator().manual_seed(a.seed)
+
+        def all_steps(n):
+            for i in range(n):
+                losses_all.append(tra.train_step(imgs[i], generator=agen))
+
     unet_steps = None
     if not a.no_unet:
         from rangeldm_amd.schedulers import DDPMSchedulerHIP
@@ -74,12 +87,14 @@ def main():
                 unet_training_step(utr, vae, sched, imgs[i], generator=ugen, pos_encoding=True, graphed=True)
 
     vae_steps(a.warmup)
+    if all_steps is not None:
+        all_steps(a.warmup)
     if unet_steps is not None:
         unet_steps(max(a.warmup, 2))                    # (step 1 runs eagerly and sizes the scratch buffers, step 2 captures)
     torch.cuda.synchronize()
-    sps = {"vae_decoder": [], "unet": []}
+    sps = {"vae_decoder": [], "vae_all": [], "unet": []}
     for _ in range(a.repeats):
-        for name, fn in (("vae_decoder", vae_steps), ("unet", unet_steps)):
+        for name, fn in (("vae_decoder", vae_steps), ("vae_all", all_steps), ("unet", unet_steps)):
             if fn is None:
                 continue
             torch.cuda.synchronize()
@@ -96,6 +111,11 @@ def main():
            "gflop_per_sample": gflop, "flop_model": "3 x decode_flops (decoder forward + backward); frozen encode not counted",
            "achieved_tflops": v["median"] * gflop / 1e3, "decoder_parameters": tr.numel,
            "loss_first_last": [float(losses[0]), float(losses[-1])]}
+    if all_steps is not None:
+        va = tri(sps["vae_all"])
+        out["vae_all"] = {"metric": "whole-VAE training samples/sec (encoder + posterior + decoder, L1 + KL), same run", "value": va["median"],
+                          "samples_per_sec": va, "ms_per_step": 1e3 * B / va["median"], "parameters": tra.numel,
+                          "loss_first_last": [float(losses_all[0]), float(losses_all[-1])]}
     if unet_steps is not None:
         out["unet_step_samples_per_sec"] = tri(sps["unet"])
     print(json.dumps(out))
