@@ -44,6 +44,13 @@ int tr_attention_backward_mfma(const float* q, const float* k, const float* v, i
 
 namespace {
 
+// Four consecutive floats of a parameter or gradient view (bias, gamma, beta, dw ...).  The trainers pack these views end to end in flat
+// buffers (tape.py: _init_parameters), so one starts at ANY 4-byte offset -- behind the VAE's 2-channel bias, 8 bytes off a 16-byte
+// boundary -- and its alignment is 4 bytes.  The code says so: four element accesses, no cast to a 16-byte type.  (The compiler still
+// merges them into one dwordx4 instruction, which global memory on this target takes at 4-byte alignment: same machine code, no claim.)
+__device__ __forceinline__ f32x4 tr_load4(const float* __restrict__ p) { return f32x4{p[0], p[1], p[2], p[3]}; }
+__device__ __forceinline__ void tr_store4(float* __restrict__ p, const f32x4 v) { p[0] = v[0]; p[1] = v[1]; p[2] = v[2]; p[3] = v[3]; }
+
 // dw[n][c][t] += sum over slices of part[t][slice][n][c], four channels per thread (Cin % 4 == 0), `nb` workgroups of `nt` threads
 // striding over the (tap, channel quad) items: the body of tr_wgrad_reduce_vec_kernel, also run as a rider of the next conv launch.
 __device__ inline void tr_wgrad_reduce_items(const float* __restrict__ part, int slices, int N, int Cin, int taps, float* __restrict__ dw,
@@ -207,7 +214,7 @@ __device__ inline void tr_tile_epilogue(const float* tile, float* colacc, const 
     if (ch < N) {                                                   // (N % 4 == 0: a quad is inside or outside)
         f32x4 addc = {0.f, 0.f, 0.f, 0.f};
         if (add_terms) {
-            if (p.bias) addc += *reinterpret_cast<const f32x4*>(p.bias + ch);
+            if (p.bias) addc += tr_load4(p.bias + ch);
             if (p.rowadd) addc += *reinterpret_cast<const f32x4*>(p.rowadd + (size_t)img * p.rowadd_ld + ch);
         }
         const bool gn = f.gs_out != nullptr, act = gn && f.gsilu != 0;
@@ -650,7 +657,7 @@ __global__ __launch_bounds__(256) void tr_conv_lds_kernel(const TrConv p, const 
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = h ? acc1[r + e] : acc0[r + e];
             if (ch + 3 < p.N && (p.N & 3) == 0) {
-                if (p.bias) { const float4 t = *reinterpret_cast<const float4*>(p.bias + ch); v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
+                if (p.bias) { const f32x4 t = tr_load4(p.bias + ch); v[0] += t[0]; v[1] += t[1]; v[2] += t[2]; v[3] += t[3]; }
                 if (p.rowadd) { const float4 t = *reinterpret_cast<const float4*>(p.rowadd + (size_t)b * p.rowadd_ld + ch); v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
                 if (rrow) { const float4 t = *reinterpret_cast<const float4*>(rrow + ch); v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
                 if (p.accumulate) { const float4 t = *reinterpret_cast<const float4*>(yrow + ch); v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
@@ -874,7 +881,7 @@ __global__ __launch_bounds__(256) void tr_conv_halo_kernel(const TrConv p, const
             float v[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = h ? acc1[r + e] : acc0[r + e];
-            if (p.bias) { const float4 t = *reinterpret_cast<const float4*>(p.bias + ch); v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
+            if (p.bias) { const f32x4 t = tr_load4(p.bias + ch); v[0] += t[0]; v[1] += t[1]; v[2] += t[2]; v[3] += t[3]; }
             if (p.rowadd) { const float4 t = *reinterpret_cast<const float4*>(p.rowadd + (size_t)b * p.rowadd_ld + ch); v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
             if (rrow) { const float4 t = *reinterpret_cast<const float4*>(rrow + ch); v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
             if (p.accumulate) { const float4 t = *reinterpret_cast<const float4*>(yrow + ch); v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
@@ -1650,7 +1657,7 @@ __global__ __launch_bounds__(256) void tr_gn_fwd_fused_vec_kernel(const float* _
     }
     __syncthreads();
     const float2 st = sst;
-    const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + g * cpg + 4 * q), be = *reinterpret_cast<const f32x4*>(beta + g * cpg + 4 * q);
+    const f32x4 ga = tr_load4(gamma + g * cpg + 4 * q), be = tr_load4(beta + g * cpg + 4 * q);
     for (int p = pl; p < npix; p += step) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(x + off + (size_t)p * C);
         f32x4 out;
@@ -1733,7 +1740,7 @@ __global__ __launch_bounds__(256) void tr_gn_fwd_vec_kernel(const float* __restr
     const unsigned i = i4 * 4, c = i % C, b = i / per_image;
     const float2 st = stats[b * groups + c / cpg];
     const f32x4 xv = *reinterpret_cast<const f32x4*>(x + i);
-    const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c), be = *reinterpret_cast<const f32x4*>(beta + c);
+    const f32x4 ga = tr_load4(gamma + c), be = tr_load4(beta + c);
     f32x4 out;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -1754,7 +1761,7 @@ __global__ __launch_bounds__(256) void tr_gn_bwd_apply_vec_kernel(const float* _
     const int sg_i = b * groups + c / cpg;
     const float2 st = stats[sg_i], sm = sums[sg_i];
     const f32x4 xv = *reinterpret_cast<const f32x4*>(x + i), dv = *reinterpret_cast<const f32x4*>(dy + i);
-    const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c), be = *reinterpret_cast<const f32x4*>(beta + c);
+    const f32x4 ga = tr_load4(gamma + c), be = tr_load4(beta + c);
     f32x4 out;
     if (accumulate) out = *reinterpret_cast<const f32x4*>(dx + i);
 #pragma unroll
@@ -2517,7 +2524,7 @@ __global__ __launch_bounds__(256) void tr_linear_rows_wgrad_kernel(const float* 
     const int kq = K >> 2;
     if (i >= (size_t)N * kq) return;
     const int n = (int)(i / kq), k = (int)(i % kq) * 4;
-    f32x4 acc = *reinterpret_cast<const f32x4*>(dw + (size_t)n * K + k);
+    f32x4 acc = tr_load4(dw + (size_t)n * K + k);
     float sb = 0.f;
     for (int b = 0; b < B; ++b) {
         const float g = dy[(size_t)b * ldy + n];
@@ -2525,7 +2532,7 @@ __global__ __launch_bounds__(256) void tr_linear_rows_wgrad_kernel(const float* 
         acc += g * xv;
         sb += g;
     }
-    *reinterpret_cast<f32x4*>(dw + (size_t)n * K + k) = acc;
+    tr_store4(dw + (size_t)n * K + k, acc);
     if (k == 0 && dbias) dbias[n] += sb;
 }
 

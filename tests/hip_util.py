@@ -643,3 +643,145 @@ def gn_shift_scale_tokens(o, seed):
     live = torch.isfinite(lo) & (err > 0)
     assert bool((err[live] <= 0.1 * bf16_ulp(lo[live])).all()), "the folded bias could move a q / k / v value"
     return xs.float()
+
+
+# ---- placement: operands as the trainers place them ---------------------------------------------------------------------------------
+# TapeTrainer packs parameters and gradients end to end in flat buffers and ZeroArena packs split-K outputs at a 16-byte granule, so the
+# other side of a view's last element is somebody else's live data.  `place` builds such a neighbourhood with known contents:
+# [guard | t0 | guard | t1 | ... | guard] in ONE allocation, every view at the same offset modulo 16 bytes as the first (`lead`), every
+# guard >= GUARD elements of one bit pattern.  Inputs sit between quiet NaNs (a stray load that is consumed -- also as x * 0 -- poisons the
+# result); outputs sit between finite sentinels, their interior pre-filled with a second NaN pattern (an element never written shows;
+# a cached block of an earlier call cannot hand it the right value); accumulating outputs carry the caller's pre-fill values.
+GUARD = 64
+_PLACE_PATTERNS = {       # dtype: (integer view, NaN around inputs, NaN inside unwritten outputs, finite sentinel around outputs)
+    torch.float32: (torch.int32, 0x7FC0A5A5, 0x7FC05A5A, 0xF5A5A5A5 - (1 << 32)),                         # sentinel = -4.2e32
+    torch.bfloat16: (torch.int16, 0x7FE5, 0x7FDA, 0xF5A5 - (1 << 16)),
+    torch.float64: (torch.int64, 0x7FF80000A5A5A5A5, 0x7FF800005A5A5A5A, 0xF5A5A5A5A5A5A5A5 - (1 << 64)),
+}
+PLACE_KINDS = ("in", "out", "acc")
+
+
+class Placement:
+    """What `place` returns: buf[name] (or buf.views in order) are the contiguous views; the rest is assert_placement's record."""
+
+    def __init__(self, flat, kind, names, views, spans, put):
+        self.flat, self.kind, self.names, self.views, self.spans, self.put = flat, kind, names, views, spans, put
+
+    def __getitem__(self, name):
+        return self.views[self.names.index(name)] if isinstance(name, str) else self.views[name]
+
+    def __iter__(self):
+        return iter(self.views)
+
+    def offset(self, name):
+        """element offset of the view inside the allocation (offset % (16 / itemsize): its residue)"""
+        return self.spans[self.names.index(name)][0]
+
+
+def place(tensors, lead=GUARD, kind="in", device=None, dtype=None):
+    """tensors: {name: tensor} (kind "in": the values; "acc": the pre-fill values of an accumulating output) or {name: shape} (kind
+    "out": a non-accumulating output).  lead: the first view's offset in elements (>= GUARD); lead % (16 bytes / itemsize) is the
+    residue every view of the buffer gets (fp32: lead % 4).  -> Placement."""
+    assert kind in PLACE_KINDS, kind
+    items = list(tensors.items())
+    if dtype is None:
+        dtype = next((t.dtype for _, t in items if torch.is_tensor(t)), torch.float32)
+    if device is None:
+        device = next((t.device for _, t in items if torch.is_tensor(t)), torch.device("cpu"))
+    ityp, nan_in, nan_out, sentinel = _PLACE_PATTERNS[dtype]
+    per16 = 16 // torch.empty((), dtype=dtype).element_size()
+    assert lead >= GUARD, f"the leading guard needs {GUARD} elements"
+    shapes = [tuple(t.shape) if torch.is_tensor(t) else tuple(int(v) for v in t) for _, t in items]
+    spans, pos = [], lead
+    for shp in shapes:
+        n = int(np.prod(shp)) if len(shp) else 1
+        spans.append((pos, n))
+        pos += n + GUARD
+        pos += (lead - pos) % per16                                  # the next view at the same residue
+    total = pos                                                      # (the last guard is >= GUARD wide as well)
+    bits = torch.full((total,), nan_in if kind == "in" else sentinel, dtype=ityp)
+    for (start, n), (name, t) in zip(spans, items):
+        if kind == "out":
+            bits[start:start + n] = nan_out
+        else:
+            assert torch.is_tensor(t) and t.dtype == dtype, f"{name}: kind {kind!r} needs a {dtype} tensor"
+            bits[start:start + n] = t.detach().cpu().contiguous().view(-1).view(ityp)
+    flat = bits.clone().to(device).view(dtype)                      # (`bits` stays as the record of what was put in)
+    views = [flat[start:start + n].view(shp) for (start, n), shp in zip(spans, shapes)]
+    return Placement(flat, kind, [n for n, _ in items], views, spans, bits)
+
+
+def assert_placement(buf, what=""):
+    """After the kernels ran: every guard of `buf` still holds its pattern bit for bit; kind "in": so does every interior (kernels do not
+    write their inputs); kind "out": no interior element still holds the unwritten pattern, and none is any other NaN (the operands are
+    finite: such a NaN was loaded from an input's guard).  A failure names the operand, the side and the element offset relative to the
+    operand's first element (negative: before it; >= its size: past it)."""
+    ityp, nan_in, nan_out, sentinel = _PLACE_PATTERNS[buf.flat.dtype]
+    now = buf.flat.detach().cpu().view(ityp)
+    guard = torch.ones(now.numel(), dtype=torch.bool)
+    for start, n in buf.spans:
+        guard[start:start + n] = False
+    bad = (guard & (now != (nan_in if buf.kind == "in" else sentinel))).nonzero().flatten().tolist()
+    msgs = []
+    for j in bad[:8]:
+        # the nearer operand owns the complaint: past the end of the one before j, or before the start of the one behind j
+        cands = []
+        for name, (start, n) in zip(buf.names, buf.spans):
+            if j >= start + n:
+                cands.append((j - (start + n - 1), f"operand {name!r}: a store PAST the view, at element offset {j - start} (size {n})"))
+            if j < start:
+                cands.append((start - j, f"operand {name!r}: a store BEFORE the view, at element offset {j - start}"))
+        msgs.append(min(cands)[1])
+    if len(bad) > 8:
+        msgs.append(f"(+{len(bad) - 8} more guard elements)")
+    for name, (start, n) in zip(buf.names, buf.spans):
+        cur = now[start:start + n]
+        if buf.kind == "in":
+            k = (cur != buf.put[start:start + n]).nonzero().flatten().tolist()
+            if k:
+                msgs.append(f"operand {name!r}: an INPUT was modified, {len(k)} elements, first at element offset {k[0]}")
+        elif buf.kind == "out":
+            k = (cur == nan_out).nonzero().flatten().tolist()
+            if k:
+                msgs.append(f"operand {name!r}: {len(k)} output elements NEVER WRITTEN, first at element offset {k[0]} (size {n})")
+            vals = buf.flat[start:start + n].detach().cpu()
+            k = (torch.isnan(vals) & (cur != nan_out)).nonzero().flatten().tolist()
+            if k:
+                msgs.append(f"operand {name!r}: {len(k)} output elements are NaN, first at element offset {k[0]}: finite operands give "
+                            f"none, so a GUARD of an input was loaded and consumed")
+        else:
+            vals = buf.flat[start:start + n].detach().cpu()
+            k = torch.isnan(vals).nonzero().flatten().tolist()
+            if k:
+                msgs.append(f"operand {name!r}: {len(k)} accumulated elements are NaN, first at element offset {k[0]}: finite operands "
+                            f"give none, so a GUARD of an input was loaded and consumed")
+    assert not msgs, f"{what}: " + "; ".join(msgs)
+
+
+def flat_buffer_residues(names, shapes):
+    """offset % 4 (in floats: the position inside a 16-byte granule) of every view TapeTrainer._init_parameters makes for parameters
+    packed end to end in the order `names`."""
+    out, pos = set(), 0
+    for n in names:
+        out.add(pos % 4)
+        pos += int(np.prod(shapes[n]))
+    return out
+
+
+def trainer_residues():
+    """The residues the project's own trainers produce: VAEDecoderTrainer, VAETrainer (the shipped VAE), UNetTrainer (the full and the
+    nuScenes configuration), from the shape tables and parameter orders those trainers use -- no GPU, no trainer object."""
+    from rangeldm_amd.config import PRESETS
+    from rangeldm_amd.params import unet_param_shapes, vae_param_shapes
+    from rangeldm_amd.training import plan_parameter_order
+    from rangeldm_amd.vae_training import decoder_param_names, encoder_param_names
+    per = {}
+    for preset in ("RangeLDM", "nuscenes"):
+        vcfg, ucfg = PRESETS[preset]["vae"], PRESETS[preset]["unet"]
+        vs = vae_param_shapes(vcfg)
+        dec, enc = decoder_param_names(vcfg, vs), encoder_param_names(vcfg, vs)
+        per[f"VAEDecoderTrainer/{preset}"] = flat_buffer_residues(dec, vs)
+        per[f"VAETrainer/{preset}"] = flat_buffer_residues(enc + dec, vs)
+        us = unet_param_shapes(ucfg)
+        per[f"UNetTrainer/{preset}"] = flat_buffer_residues(plan_parameter_order(list(us), us)[0], us)
+    return per
