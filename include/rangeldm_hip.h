@@ -722,6 +722,12 @@ int rldm_train_wgrad_group_pending(void);   /* queued layers (tests) */
  *                          result = the same two steps over the block partials (thread t adds partials t, t + 256, ... first).
  *   l1                     mse's partials and folds, for the loss and for each channel's absolute-error sum (see rldm_train_l1).
  *   gaussian               mse's partials and folds for the KL sum (see rldm_train_gaussian); z and the backward are element-wise.
+ *   disc_conv / _dgrad     no split across workgroups: the four waves of a tile's workgroup take a quarter of the taps each, in tap
+ *                          order, and are added ((w0 + w1) + w2) + w3 (both modes).
+ *   disc_wgrad             partial tiles per K slice, added in slice order (both modes); dbias is colsum's.
+ *   disc_bn_forward / _backward   fp64 partials per 256 rows, added in index order (both modes); no atomics.
+ *   disc_hinge / _generator       l1's partials and folds (see rldm_train_disc_hinge); the gradients are element-wise.
+ *   disc_lrelu / _adaptive_mix    element-wise.
  * The RCCL all-reduce of a multi-rank step is outside this guarantee. */
 int rldm_train_deterministic(int on);
 int rldm_train_deterministic_enabled(void);
@@ -808,7 +814,7 @@ typedef struct rldm_hyper_config {
 /* step = ++*step_counter (device int64); dyn[4] <- the scalars of optimizer step `step` (lr of step - 1 scheduler steps). */
 int rldm_train_hyper_step(int64_t* step_counter, const rldm_hyper_config* c, float* dyn, void* stream);
 /* master fp32 [N][Cin][taps] -> bf16 [N][taps][ceil16(Cin)] (forward) and bf16 [Cin][taps][ceil16(N)] (flipped / transposed:
- * data gradient; may be NULL). */
+ * data gradient; may be NULL).  taps: 1, 9, or 16 (the discriminator's 4x4 convs, tap t = 4 i + j). */
 int rldm_train_pack_weights(const float* w, int N, int Cin, int taps, void* w_forward, void* w_transposed, void* stream);
 /* the same for every layer of the model in one launch: descs = DEVICE array sorted by `first` (cumulative count of
  * max(forward, transposed) copy elements), params = the flat fp32 parameter buffer. */
@@ -823,6 +829,76 @@ int rldm_train_pack_weights_all(const float* params, const rldm_pack_desc* descs
 /* the same as a tiled transpose (coalesced reads and writes): descs[i].first = cumulative count of 64 x 64 (N, Cin) tiles,
  * total_tiles = their sum = the grid. */
 int rldm_train_pack_weights_tiled(const float* params, const rldm_pack_desc* descs, int num_layers, int64_t total_tiles, void* stream);
+
+/* ---- PatchGAN discriminator (rangeldm_amd/csrc/train_disc.hip; vae/sgm/modules/autoencoding/lpips/model/model.py:18-89,
+ * NLayerDiscriminator, and losses/__init__.py, GeneralLPIPSWithDiscriminator after disc_start) ----
+ * Driven by rangeldm_amd/discriminator.py.  Tensors as above: device fp32, NHWC [B][W][H][C], GEMM operands rounded to bf16 into the
+ * MFMA with fp32 accumulation.  Scratch is the caller's: an entry point that needs some takes a workspace and says how large.
+ *
+ * 4x4 convolution with ZERO padding 1 ON BOTH AXES, stride 1 or 2.  W DOES NOT WRAP HERE, unlike every other conv of this library
+ * (a range image is a cylinder, but the reference's discriminator is a plain nn.Conv2d(padding=1)): output (wo, ho) under tap
+ * (i, j) in {0..3}^2 reads input (s wo + i - 1, s ho + j - 1), anything outside the tensor is zero.  Output size per axis:
+ * (n + 2 - 4) / s + 1 (integer division; odd extents are legal at stride 2: 7 -> 3).  The desc describes the FORWARD conv in all
+ * three directions.  Instances: Cin = 2 or a multiple of 16; N = 1 or a multiple of 16; Win, Hin >= 2; anything else is an error
+ * (_ok: 0).  All of them run the same bf16 MFMA kernels (32x32x16), the boundary layers 2 -> 64 and 512 -> 1 on partly empty tiles. */
+typedef struct rldm_train_disc_conv_desc {
+    int32_t B, Win, Hin, Cin;   /* input tensor of the forward conv */
+    int32_t N;                  /* output channels                  */
+    int32_t stride;             /* 1 | 2                            */
+} rldm_train_disc_conv_desc;
+int rldm_train_disc_conv_ok(const rldm_train_disc_conv_desc* d);
+/* y [B][Wo][Ho][N] = conv(x) + bias (bias may be NULL); w_packed = bf16 [N][16][ceil16(Cin)], tap t = 4 i + j, from
+ * rldm_train_pack_weights(taps = 16). */
+int rldm_train_disc_conv(const rldm_train_disc_conv_desc* d, const float* x, const void* w_packed, const float* bias, float* y,
+                         void* stream);
+/* dx [B][Win][Hin][Cin] = the data gradient for dy [B][Wo][Ho][N]; w_transposed = bf16 [Cin][16][ceil16(N)], taps flipped, from the
+ * same call.  Stride 2: the four output parities (wi & 1, hi & 1) are four 2x2 convolutions over dy (the sub-pixel form), one grid
+ * plane each; no tap that falls between the samples is multiplied. */
+int rldm_train_disc_conv_dgrad(const rldm_train_disc_conv_desc* d, const float* dy, const void* w_transposed, float* dx, void* stream);
+/* dw (N, Cin, 4, 4) torch layout += sum over pixels of dy (x) x (dw zeroed by the caller, as rldm_train_wgrad); dbias[N] += the
+ * column sums of dy (NULL: none; rldm_train_colsum's arithmetic).  The pixels are cut into K slices whose partial tiles go to the
+ * workspace and are added in slice order (from +0, then onto dw) IN BOTH MODES: no atomics reach dw.  _workspace: bytes needed. */
+int64_t rldm_train_disc_wgrad_workspace(const rldm_train_disc_conv_desc* d);
+int rldm_train_disc_wgrad(const rldm_train_disc_conv_desc* d, const float* dy, const float* x, float* dw, float* dbias,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+/* BatchNorm2d + LeakyReLU(0.2) over x [M][C] (M = B W H values per channel), eps 1e-5, momentum 0.1.
+ *   training != 0: mean and BIASED variance per channel from fp64 sums (partial s covers rows [256 s, 256 s + 256): four lanes add
+ *     rows s0 + k, s0 + k + 4, ... in order and meet k = 0 .. 3; the partials are added in order of s: fixed order in both modes);
+ *     running_mean = 0.9 running_mean + 0.1 mean, running_var = 0.9 running_var + 0.1 var M / (M - 1) (the UNBIASED variance), both
+ *     evaluated in fp64 and rounded once; *num_batches_tracked (device int64) += 1.  M < 2 is an error, as in torch.
+ *   training == 0: mean = running_mean, var = running_var; nothing is updated.
+ *   save [2 C] = (mean[C] | rstd[C]) fp32, rstd = the fp32 rounding of 1 / sqrt(var + 1e-5) in fp64: written in both cases, read by
+ *     the backward.
+ *   xhat = (x - mean) rstd;  z = xhat gamma + beta;  y = z > 0 ? z : 0.2 z     (fp32, every operation rounded on its own)
+ * LeakyReLU's gradient at z == 0 is the slope-0.2 side (z <= 0), as torch's leaky_relu_backward (x > 0 ? dy : 0.2 dy).
+ * _backward (training-mode statistics): dz = dy (z > 0 ? 1 : 0.2);  dbeta[c] += S1 = sum dz;  dgamma[c] += S2 = sum dz xhat (fp64
+ *   sums, the forward's order);  dx = (gamma rstd) (dz - S1 / M - xhat S2 / M).  dgamma / dbeta may be NULL (input gradient only).
+ * workspace: rldm_train_disc_bn_workspace(M, C) bytes. */
+int64_t rldm_train_disc_bn_workspace(int64_t M, int C);
+int rldm_train_disc_bn_forward(const float* x, int64_t M, int C, const float* gamma, const float* beta, float* running_mean,
+                               float* running_var, int64_t* num_batches_tracked, int training, float* save, float* y,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+int rldm_train_disc_bn_backward(const float* x, const float* dy, const float* save, int64_t M, int C, const float* gamma,
+                                const float* beta, float* dx, float* dgamma, float* dbeta, void* workspace, int64_t workspace_bytes,
+                                void* stream);
+/* LeakyReLU(0.2) on its own (behind the first conv): backward == 0: y = x > 0 ? x : 0.2 x (dy unused);  backward != 0:
+ * y = dy (x > 0 ? 1 : 0.2), the slope-0.2 side at x == 0. */
+int rldm_train_disc_lrelu(const float* x, const float* dy, float* y, int64_t n, int backward, void* stream);
+/* vqperceptual.hinge_d_loss times `factor`, over n logits each:  out (device double [3]) = (factor 0.5 (mean relu(1 - real) + mean
+ * relu(1 + fake)), mean real, mean fake);  dreal = -g [1 - real > 0], dfake = +g [1 + fake > 0], g = factor 0.5 / n rounded once to
+ * fp32 (1 - real and 1 + fake are the fp32 expressions).  Sums as rldm_train_l1: element 256 i + t is lane t of partial i, a
+ * partial's 256 fp64 values meet in mse's binary tree, the partials in fp64 atomics -- or, in the deterministic mode, go to
+ * partials [3][ceil(n / 256)] (device doubles, the caller's; may be NULL otherwise) and are folded as mse's.  No host sync. */
+int rldm_train_disc_hinge(const float* real, const float* fake, int64_t n, float factor, float* dreal, float* dfake, double* out,
+                          double* partials, void* stream);
+/* The generator term: *out (device double) = -mean(fake), dfake = -1 / n (rounded once to fp32); sums and partials [ceil(n / 256)]
+ * as above. */
+int rldm_train_disc_generator(const float* fake, int64_t n, float* dfake, double* out, double* partials, void* stream);
+/* The adaptive weight and the gradient mix in one element-wise launch that reads the squared norms from device memory:
+ *   d_weight = clamp(sqrt(*sq_nll) / (sqrt(*sq_g) + 1e-4), 0, 1e4) disc_weight   (fp64; written to *d_weight, a device double)
+ *   dpred[i] = dnll[i] + s dg[i],  s = d_weight disc_factor rounded once to fp32; product and sum rounded on their own. */
+int rldm_train_disc_adaptive_mix(const float* dnll, const float* dg, const double* sq_nll, const double* sq_g, float disc_weight,
+                                 float disc_factor, float* dpred, double* d_weight, int64_t n, void* stream);
 
 /* ---- introspection used by bench.py / tests ----------------------------------------------------------------- */
 /* algorithmic FLOPs (2*MACs of conv/linear/QK^T/PV) of one UNet forward / VAE decode / encode for batch B */

@@ -103,6 +103,11 @@ class TrainConvDescC(C.Structure):
                 ("taps", C.c_int32), ("stride", C.c_int32), ("mode", C.c_int32)]
 
 
+class TrainDiscConvDescC(C.Structure):
+    """rldm_train_disc_conv_desc: the discriminator's 4x4 conv, zero-padded 1 on both axes (W does not wrap)."""
+    _fields_ = [("B", C.c_int32), ("Win", C.c_int32), ("Hin", C.c_int32), ("Cin", C.c_int32), ("N", C.c_int32), ("stride", C.c_int32)]
+
+
 class TrainFuseC(C.Structure):
     """rldm_train_fuse (include/rangeldm_hip.h): what a fused conv / weight-gradient launch folds in."""
     _fields_ = [("x1", C.c_void_p), ("C0", C.c_int32), ("cs0", C.c_void_p), ("cs1", C.c_void_p), ("gamma", C.c_void_p),
@@ -271,6 +276,19 @@ PROTOTYPES = {
     "rldm_train_pack_weights": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "rldm_train_pack_weights_all": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P]),
     "rldm_train_pack_weights_tiled": (C.c_int, [_P, _P, C.c_int, C.c_int64, _P]),
+    # the PatchGAN discriminator (csrc/train_disc.hip): 4x4 zero-padded convs, BatchNorm + LeakyReLU, the adversarial losses
+    "rldm_train_disc_conv_ok": (C.c_int, [C.POINTER(TrainDiscConvDescC)]),
+    "rldm_train_disc_conv": (C.c_int, [C.POINTER(TrainDiscConvDescC), _P, _P, _P, _P, _P]),
+    "rldm_train_disc_conv_dgrad": (C.c_int, [C.POINTER(TrainDiscConvDescC), _P, _P, _P, _P]),
+    "rldm_train_disc_wgrad_workspace": (C.c_int64, [C.POINTER(TrainDiscConvDescC)]),
+    "rldm_train_disc_wgrad": (C.c_int, [C.POINTER(TrainDiscConvDescC), _P, _P, _P, _P, _P, C.c_int64, _P]),
+    "rldm_train_disc_bn_workspace": (C.c_int64, [C.c_int64, C.c_int]),
+    "rldm_train_disc_bn_forward": (C.c_int, [_P, C.c_int64, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, C.c_int64, _P]),
+    "rldm_train_disc_bn_backward": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    "rldm_train_disc_lrelu": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P]),
+    "rldm_train_disc_hinge": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P, _P, _P, _P, _P]),
+    "rldm_train_disc_generator": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
+    "rldm_train_disc_adaptive_mix": (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, _P, _P, C.c_int64, _P]),
     "rldm_unet_flops": (C.c_double, [_P, C.c_int]),
     "rldm_vae_decode_flops": (C.c_double, [_P, C.c_int, C.c_int, C.c_int]),
     "rldm_unet_num_launches": (C.c_int, [_P, C.c_int]),

@@ -3556,7 +3556,7 @@ static int adamw_launch(float* params, float* grads, float* exp_avg, float* exp_
 }
 
 int rldm_train_pack_weights(const float* w, int N, int Cin, int taps, void* w_forward, void* w_transposed, void* stream) {
-    RLDM_REQUIRE(w && w_forward && (taps == 1 || taps == 9), "null argument");
+    RLDM_REQUIRE(w && w_forward && (taps == 1 || taps == 9 || taps == 16), "null argument");     // (16: train_disc.hip's 4x4 convs)
     const int Cin_pad = (Cin + 15) / 16 * 16, N_pad = (N + 15) / 16 * 16;
     const size_t n = std::max((size_t)N * taps * Cin_pad, w_transposed ? (size_t)Cin * taps * N_pad : (size_t)0);
     tr_pack_weights_kernel<<<nblk(n), 256, 0, (hipStream_t)stream>>>(w, N, Cin, taps, Cin_pad, N_pad, static_cast<bf16_t*>(w_forward),

@@ -50,7 +50,7 @@ class TapeTrainer:
         for n in self.names:
             if n.endswith(".weight") and len(self.shapes[n]) >= 2 and n not in members:
                 N, Cin = self.shapes[n][:2]
-                taps = 9 if len(self.shapes[n]) == 4 and self.shapes[n][2] == 3 else 1
+                taps = self.shapes[n][2] * self.shapes[n][3] if len(self.shapes[n]) == 4 else 1      # (k x k: 9, 1; 16 in the discriminator)
                 self.layers[n] = (N, Cin, taps, self.offsets[n], n not in no_dx)
         for key, grp in self.fused.items():
             N = sum(self.shapes[m][0] for m in grp["weights"])

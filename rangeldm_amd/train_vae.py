@@ -3,10 +3,15 @@
     python -m rangeldm_amd.train_vae --weights DIR | --sgm-ckpt F --sgm-yaml Y  [--input NPY_DIR] --out DIR --steps N
                                      [--trainable decoder|all] [--kl-weight 1e-6]
                                      [--batch-size 8] [--lr 4.5e-6] [--mode] [--seed S] [--log-every K] [--deterministic]
+                                     [--discriminator patchgan --disc-start N --disc-weight 0.5 [--disc-state FILE]]
 
 --trainable decoder (the default) leaves the encoder, and with it the latent space, as it is.  --trainable all trains encoder and
 decoder jointly with loss = L1 + kl_weight * kl and adds "kl" to every log line; it moves the latent space, so UNets trained on the old
 latents no longer apply and scaling_factor must be estimated again.
+
+--discriminator patchgan adds the reference's adversarial phase (rangeldm_amd/discriminator.py) from step --disc-start on: every log
+line of that phase gains "g_loss", "d_weight", "disc_loss", "logits_real", "logits_fake", and OUT/discriminator.pt (PatchDiscriminator's
+save_state; --disc-state FILE resumes from one) is written beside OUT/vae/.  Without it the command prints and writes what it always did.
 
 --input holds the (2, W, H) .npy range images `evaluate vae --input` reads (batches walk the sorted files and wrap around); without
 it the run trains on the synthetic batch of `evaluate vae`.  Without --weights / --sgm-ckpt the synthetic weights of `evaluate vae`
@@ -39,6 +44,10 @@ def build_parser():
     ap.add_argument("--seed", type=int, default=20240310)
     ap.add_argument("--log-every", type=int, default=10, metavar="K")
     ap.add_argument("--deterministic", action="store_true", help="bit-reproducible decoder step (slower)")
+    ap.add_argument("--discriminator", choices=("patchgan",), default=None, help="train adversarially against a PatchGAN from --disc-start on")
+    ap.add_argument("--disc-start", type=int, default=0, metavar="N", help="first step (0-based) of the adversarial phase")
+    ap.add_argument("--disc-weight", type=float, default=0.5, help="factor of the adaptive weight")
+    ap.add_argument("--disc-state", default=None, metavar="FILE", help="a discriminator.pt to resume the PatchGAN from")
     return ap
 
 
@@ -51,14 +60,22 @@ def check_args(a):
         raise ValueError("--weights and --sgm-ckpt exclude each other")
     if a.sgm_yaml and not a.sgm_ckpt:
         raise ValueError("--sgm-yaml goes with --sgm-ckpt")
+    if a.disc_start < 0 or a.disc_weight < 0:
+        raise ValueError("--disc-start and --disc-weight must not be negative")
+    if a.disc_state and not a.discriminator:
+        raise ValueError("--disc-state goes with --discriminator")
 
 
-def log_record(step, loss, abs_sums, pixels, kl=None):
+def log_record(step, loss, abs_sums, pixels, kl=None, adversarial=None):
     """One log line: the loss of `step` (1-based) and the per-channel MAE = abs_sums[c] / pixels (pixels = B W H); kl (--trainable all):
-    the KL term, unweighted."""
+    the KL term, unweighted; adversarial (once that phase has started): (g_loss, d_weight, (disc_loss, logits_real, logits_fake))."""
     rec = {"step": int(step), "loss": float(loss), "mae": [float(s) / float(pixels) for s in abs_sums]}
     if kl is not None:
         rec["kl"] = float(kl)
+    if adversarial is not None:
+        g_loss, d_weight, (disc_loss, logits_real, logits_fake) = adversarial
+        rec.update(g_loss=float(g_loss), d_weight=float(d_weight), disc_loss=float(disc_loss), logits_real=float(logits_real),
+                   logits_fake=float(logits_fake))
     return rec
 
 
@@ -95,10 +112,18 @@ def main(argv=None):
     vae.load_state_dict(sd)
     sd = vae.state_dict()                                # (diffusers keys, whatever layout the checkpoint had)
     everything = a.trainable == "all"
+    adv = {}
+    if a.discriminator:
+        from .discriminator import DiscriminatorConfig, PatchDiscriminator
+        disc = PatchDiscriminator(DiscriminatorConfig(in_channels=cfg.out_channels), seed=a.seed, device=dev, lr=a.lr,
+                                  deterministic=a.deterministic)
+        if a.disc_state:
+            disc.load_state(a.disc_state)
+        adv = dict(discriminator=disc, disc_start=a.disc_start, disc_weight=a.disc_weight)
     if everything:
-        trainer = VAETrainer(cfg, sd, device=dev, lr=a.lr, kl_weight=a.kl_weight, deterministic=a.deterministic)
+        trainer = VAETrainer(cfg, sd, device=dev, lr=a.lr, kl_weight=a.kl_weight, deterministic=a.deterministic, **adv)
     else:
-        trainer = VAEDecoderTrainer(cfg, sd, device=dev, lr=a.lr, deterministic=a.deterministic)
+        trainer = VAEDecoderTrainer(cfg, sd, device=dev, lr=a.lr, deterministic=a.deterministic, **adv)
     shape = (cfg.in_channels, *cfg.sample_size)
     files = sorted(glob.glob(os.path.join(a.input, "*.npy"))) if a.input else None
     if files is not None and not files:
@@ -118,9 +143,13 @@ def main(argv=None):
         else:
             loss = training_step(trainer, vae, x.to(dev), sample_posterior=not a.mode, generator=gen)
         if (step + 1) % a.log_every == 0 or step + 1 == a.steps:
-            last = log_record(step + 1, loss, trainer.last_abs_sums.cpu().tolist(), pixels, trainer.last_kl if everything else None)
+            started = a.discriminator and trainer.last_disc is not None
+            last = log_record(step + 1, loss, trainer.last_abs_sums.cpu().tolist(), pixels, trainer.last_kl if everything else None,
+                              (trainer.last_g_loss, trainer.last_d_weight, trainer.last_disc) if started else None)
             print(json.dumps(last), flush=True)
     trainer.save_pretrained(a.out)
+    if a.discriminator:
+        trainer.discriminator.save_state(os.path.join(a.out, "discriminator.pt"))
     return last
 
 

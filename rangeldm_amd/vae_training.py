@@ -1,6 +1,6 @@
-"""VAE training on MI355X, the reference's reconstruction phase before its discriminator starts (`GeneralLPIPSWithDiscriminator`
+"""VAE training on MI355X: the reference's reconstruction phase before its discriminator starts (`GeneralLPIPSWithDiscriminator`
 with logvar = 0, perceptual_weight = 0, range_weight = 40, intensity_weight = 10: channel-weighted L1, summed over the image and divided
-by the batch).
+by the batch) and, with a `discriminator` (discriminator.PatchDiscriminator), its adversarial phase from `disc_start` on.
 
 `VAEDecoderTrainer` trains the decoder against the frozen encoder.  The latent space does not move: every trained UNet and every
 captured sampler stays valid.
@@ -11,7 +11,16 @@ latents no longer applies to the new VAE, and `scaling_factor` (1 / std of the l
 
 Both sit on `TapeTrainer` (tape.py) and drive the op-level HIP kernels of rangeldm_amd/csrc/train.hip through the same host-side tape as
 `UNetTrainer`: 3x3 / 1x1 stride-1 convs, nearest x2 + conv, the encoder's end-padded stride-2 conv (train_ops.conv_desc, pad = 1),
-GroupNorm + SiLU, residual adds; the posterior is rldm_train_gaussian, the loss rldm_train_l1.  Not built: the discriminator, a
+GroupNorm + SiLU, residual adds; the posterior is rldm_train_gaussian, the loss rldm_train_l1.
+
+The adversarial phase (both trainers; `_VAETape._adversarial_step`): the autoencoder's loss becomes nll + d_weight disc_factor g_loss
+with g_loss = -mean(D(pred)) and d_weight = clamp(|d nll / d w| / (|d g_loss / d w| + 1e-4), 0, 1e4) disc_weight over
+w = decoder.conv_out.weight (the KL term is not part of nll there, as in the reference); then the PatchGAN takes one hinge-loss Adam
+step of its own.  ONE DEVIATION, on purpose: the reference runs the autoencoder's forward a second time -- updated weights, a fresh
+posterior sample -- for the discriminator's step; here the discriminator sees the reconstruction of the generator's step, which saves
+a VAE forward.  `PatchDiscriminator.discriminator_step` is public: a caller who wants the other thing runs it on a fresh forward.
+
+Not built: the Meta-Kernel discriminators, `disc_bev`, the vanilla GAN loss, a
 trainable `logvar` of the loss (it stays at its initial 0, the reference's `learn_logvar: False`), the BEV / perceptual terms, EMA, a
 captured step graph, gradient exchange between ranks.  No torch autograd, no torch compute ops on the path; no CPU fallback.
 
@@ -98,7 +107,7 @@ class _VAETape(TapeTrainer):
     state."""
 
     def _init_vae(self, config, state_dict, names, no_dx, device, lr, betas, eps, weight_decay, max_grad_norm, channel_weights,
-                  deterministic):
+                  deterministic, discriminator=None, disc_start=0, disc_weight=0.5, disc_factor=1.0):
         self.cfg = config if isinstance(config, VAEConfig) else VAEConfig(**config)
         if len(channel_weights) != self.cfg.out_channels:
             raise ValueError(f"{len(channel_weights)} channel weights for {self.cfg.out_channels} output channels")
@@ -111,6 +120,10 @@ class _VAETape(TapeTrainer):
         self.hp = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
         self.channel_weights = torch.tensor([float(w) for w in channel_weights], dtype=torch.float32, device=self.device)
         self.last_abs_sums = None
+        self.discriminator, self.disc_start = discriminator, int(disc_start)
+        self.disc_weight, self.disc_factor = float(disc_weight), float(disc_factor)
+        self.last_g_loss = self.last_d_weight = self.last_disc = None
+        self._conv_out_in = None
 
     # ---- network ----------------------------------------------------------------------------------------------
     def _resnet(self, x, p):
@@ -129,6 +142,8 @@ class _VAETape(TapeTrainer):
             elif kind == "norm_out":
                 h = self._gn(h, p, True)
             else:
+                if kind == "conv_out":
+                    self._conv_out_in = h               # (the adversarial phase takes conv_out's weight gradient twice more)
                 h = self._conv(h, p, mode=1 if kind == "upsample" else 0, need_dx=dz or kind != "conv_in")
         self._out = h
         return h
@@ -150,15 +165,47 @@ class _VAETape(TapeTrainer):
             self._clip_adamw(self.hp["lr"])
             return self.hp["lr"]
 
+    # ---- adversarial phase ------------------------------------------------------------------------------------
+    def adversarial(self):
+        """True when the next train_step runs the adversarial phase: a discriminator was given and global_step (the steps taken so
+        far) has reached disc_start -- the reference's adopt_weight(disc_factor, global_step, threshold=disc_start)."""
+        return self.discriminator is not None and self.global_step >= self.disc_start
+
+    def _adversarial_step(self, pred, dnll, real_nchw):
+        """The steps behind the forward and the L1 of an adversarial train_step (module docstring): generator term through the
+        discriminator (training-mode BatchNorm, as the reference), the adaptive weight from two weight gradients of conv_out alone,
+        one backward with the mixed gradient, the VAE's Adam step, then the discriminator's own step on (real, pred) with the
+        trainer's step count.  Sets last_g_loss / last_d_weight / last_disc = (d_loss, mean logits real, mean logits fake): device
+        scalars, no host sync."""
+        from . import discriminator as D
+        disc = self.discriminator
+        disc.forward(pred, training=True, layout="nhwc")
+        self.last_g_loss, dlogits = disc.generator_loss()
+        dg = disc.input_gradient(dlogits)
+        w = "decoder.conv_out.weight"
+        sq = []
+        for d in (dnll, dg):
+            gw = torch.zeros(self.shapes[w], dtype=torch.float32, device=self.device)
+            T.wgrad(d, self._conv_out_in, gw, 9)
+            sq.append(T.sqnorm(gw))
+        dpred, self.last_d_weight = D.adaptive_mix(dnll, dg, sq[0], sq[1], self.disc_weight, self.disc_factor)
+        self.backward(dpred)
+        self.optimizer_step()
+        self.last_disc = disc.discriminator_step(real_nchw, pred, factor=self.disc_factor, step=self.global_step)
+
     # ---- weights ----------------------------------------------------------------------------------------------
     def full_state_dict(self):
         """The whole VAE: the tensors this trainer does not train as they were given, the fp32 masters of those it does."""
         return merged_state_dict(self._frozen, self.state_dict())
 
     def save_state(self, path):
-        """Everything a resumed run needs: parameters, Adam moments, step counter."""
-        torch.save({"params": self.params.cpu(), "exp_avg": self.exp_avg.cpu(), "exp_avg_sq": self.exp_avg_sq.cpu(),
-                    "global_step": self.global_step, "names": list(self.names)}, path)
+        """Everything a resumed run needs: parameters, Adam moments, step counter -- and, with a discriminator, its state under the
+        key `discriminator` (a file written without one has no such key)."""
+        st = {"params": self.params.cpu(), "exp_avg": self.exp_avg.cpu(), "exp_avg_sq": self.exp_avg_sq.cpu(),
+              "global_step": self.global_step, "names": list(self.names)}
+        if self.discriminator is not None:
+            st["discriminator"] = self.discriminator.state_payload()
+        torch.save(st, path)
 
     def load_state(self, path):
         st = torch.load(path, map_location="cpu", weights_only=True)
@@ -170,18 +217,24 @@ class _VAETape(TapeTrainer):
         self.global_step = int(st["global_step"])
         self.grads.zero_()
         self.repack()
+        if self.discriminator is not None and "discriminator" in st:
+            self.discriminator.load_payload(st["discriminator"])
 
 
 class VAEDecoderTrainer(_VAETape):
     def __init__(self, config, state_dict, device="cuda", lr=4.5e-6, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 max_grad_norm=None, channel_weights=(40.0, 10.0), deterministic=False):
+                 max_grad_norm=None, channel_weights=(40.0, 10.0), deterministic=False, discriminator=None, disc_start=0,
+                 disc_weight=0.5, disc_factor=1.0):
         """The defaults are the reference's: torch.optim.Adam (AdamW with zero decay is Adam) at base_learning_rate 4.5e-6, no
         clipping, range_weight 40 / intensity_weight 10.  state_dict may hold the whole VAE: the encoder's tensors are kept as
         they are (handed on by load_into / save_pretrained), never read by a kernel of this class.
         deterministic: every kernel of this trainer runs in the library's deterministic mode (rldm_train_deterministic), as
-        UNetTrainer(deterministic=True): the same inputs give the same parameter bits."""
+        UNetTrainer(deterministic=True): the same inputs give the same parameter bits.
+        discriminator: a discriminator.PatchDiscriminator; from step disc_start on train_step runs the adversarial phase (module
+        docstring) with disc_weight / disc_factor, the reference's names.  None, or before disc_start: the step is exactly what it
+        is without one, and the discriminator is not run."""
         self._init_vae(config, state_dict, decoder_param_names, ("decoder.conv_in.weight",), device, lr, betas, eps, weight_decay,
-                       max_grad_norm, channel_weights, deterministic)
+                       max_grad_norm, channel_weights, deterministic, discriminator, disc_start, disc_weight, disc_factor)
 
     def forward(self, z_nchw):
         """z (B, z_channels, W / f, H / f) fp32 on the device, as the encoder emits it (not multiplied by scaling_factor)
@@ -195,12 +248,17 @@ class VAEDecoderTrainer(_VAETape):
     def train_step(self, z_nchw, target_nchw, as_float=False):
         """pred = decoder(z); loss = (1 / B) sum wc[c] |pred - target|; backward; step.  Returns the loss: a 0-d float64 device
         tensor (no host sync), or a Python float with as_float.  `last_abs_sums`: float64 (C,) device, the unweighted sum of
-        |pred - target| per channel (MAE of channel c = last_abs_sums[c] / (B W H))."""
+        |pred - target| per channel (MAE of channel c = last_abs_sums[c] / (B W H)).  In the adversarial phase (`adversarial()`) the
+        step is `_adversarial_step`'s and `last_g_loss`, `last_d_weight`, `last_disc` report it; the returned loss stays the L1."""
         with self._mode():
             pred = self.forward(z_nchw)
-            loss, dpred, self.last_abs_sums = T.l1(pred, target_nchw.to(self.device).float().contiguous(), self.channel_weights)
-            self.backward(dpred)
-            self.optimizer_step()
+            target = target_nchw.to(self.device).float().contiguous()
+            loss, dpred, self.last_abs_sums = T.l1(pred, target, self.channel_weights)
+            if self.adversarial():
+                self._adversarial_step(pred, dpred, target)
+            else:
+                self.backward(dpred)
+                self.optimizer_step()
         return float(loss) if as_float else loss
 
     def load_into(self, vae):
@@ -219,13 +277,16 @@ class VAEDecoderTrainer(_VAETape):
 
 class VAETrainer(_VAETape):
     def __init__(self, config, state_dict, device="cuda", lr=4.5e-6, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 max_grad_norm=None, kl_weight=1e-6, channel_weights=(40.0, 10.0), deterministic=False):
+                 max_grad_norm=None, kl_weight=1e-6, channel_weights=(40.0, 10.0), deterministic=False, discriminator=None,
+                 disc_start=0, disc_weight=0.5, disc_factor=1.0):
         """Encoder and decoder trained jointly; the defaults are the reference's (VAEDecoderTrainer's, and kl_loss: 1e-6).  The
         parameters are every key of vae_param_shapes in tape order: the encoder as oracle.vae.vae_encode visits it, then the
         decoder.  Training the encoder moves the latent space: UNets trained on the old latents no longer apply, and scaling_factor
-        must be estimated again (module docstring).  deterministic: as VAEDecoderTrainer."""
+        must be estimated again (module docstring).  deterministic, discriminator, disc_start, disc_weight, disc_factor: as
+        VAEDecoderTrainer."""
         self._init_vae(config, state_dict, lambda cfg, shapes: encoder_param_names(cfg, shapes) + decoder_param_names(cfg, shapes),
-                       ("encoder.conv_in.weight",), device, lr, betas, eps, weight_decay, max_grad_norm, channel_weights, deterministic)
+                       ("encoder.conv_in.weight",), device, lr, betas, eps, weight_decay, max_grad_norm, channel_weights, deterministic,
+                       discriminator, disc_start, disc_weight, disc_factor)
         self.kl_weight = float(kl_weight)
         self.last_kl = None
         self._moments = self._z = None
@@ -278,7 +339,8 @@ class VAETrainer(_VAETape):
         loss = (1 / B) sum wc[c] |pred - images| + kl_weight kl; backward through decoder, posterior and encoder; one Adam step over
         all parameters.  noise: (B, z_channels, W / f, H / f); None draws it on the host from `generator`, as the reference does.
         Returns the loss: a 0-d float64 device tensor (no host sync), or a Python float with as_float.  `last_abs_sums` as
-        VAEDecoderTrainer's; `last_kl`: the KL term, a 0-d float64 device tensor."""
+        VAEDecoderTrainer's; `last_kl`: the KL term, a 0-d float64 device tensor.  In the adversarial phase: as VAEDecoderTrainer's
+        (the returned loss stays L1 + kl_weight kl; the discriminator is given `images` as the real batch)."""
         images = images.to(self.device).float().contiguous()
         if sample_posterior and noise is None:
             f = self.cfg.downscale
@@ -286,8 +348,11 @@ class VAETrainer(_VAETape):
         with self._mode():
             pred = self.forward(images, noise if sample_posterior else None)
             rec, dpred, self.last_abs_sums = T.l1(pred, images, self.channel_weights)
-            self.backward(dpred)
-            self.optimizer_step()
+            if self.adversarial():
+                self._adversarial_step(pred, dpred, images)
+            else:
+                self.backward(dpred)
+                self.optimizer_step()
         loss = rec + self.kl_weight * self.last_kl          # (two device scalars, for the log: no kernel reads the sum)
         return float(loss) if as_float else loss
 

@@ -4,14 +4,17 @@ encode + posterior sample on the inference kernels, decoder forward, L1, backwar
 eager launches (no captured step graph exists for this trainer).
 
     python tools/bench_vae_train.py [--batch 8] [--steps 10] [--warmup 3] [--repeats 5] [--no-unet] [--deterministic]
-                                    [--trainable decoder|all]
+                                    [--trainable decoder|all] [--discriminator]
 
 After the warm-up, --repeats timed runs of --steps steps each (a host clock around work that ends in a device synchronise): median
 [min, max].  Achieved TFLOP/s counts 3 x AutoencoderKLHIP.decode_flops (decoder forward + backward; the encode is not counted).  In the
 same process the UNet step of tools/bench_train.py (VAE encode + UNet forward / backward / AdamW / EMA from captured step graphs) is
 timed the same way, interleaved with the decoder runs, for scale.  --trainable all adds the whole-VAE step (`VAETrainer.train_step`:
 encoder, posterior, decoder, L1 + KL, backward through all three, Adam over every parameter; noise drawn on the host as in
-`training_step`), interleaved with the other two in the same run (samples/s only: the library counts no encoder FLOPs).  One JSON line."""
+`training_step`), interleaved with the other two in the same run (samples/s only: the library counts no encoder FLOPs).  --discriminator
+adds the adversarial step of every timed VAE trainer -- a second trainer of the same kind with a PatchDiscriminator and disc_start = 0:
+generator term, adaptive weight, mixed backward, the PatchGAN's own hinge step -- interleaved with the plain ones in the same run, and
+reports its ratio to the plain step.  One JSON line."""
 import argparse
 import json
 import os
@@ -37,6 +40,7 @@ def main():
     ap.add_argument("--no-unet", action="store_true", help="skip the UNet step (a profiler run wants the decoder step alone)")
     ap.add_argument("--deterministic", action="store_true", help="VAEDecoderTrainer(deterministic=True)")
     ap.add_argument("--trainable", choices=("decoder", "all"), default="decoder", help="all: also time VAETrainer's whole-VAE step")
+    ap.add_argument("--discriminator", action="store_true", help="also time the adversarial step (PatchGAN, disc_start = 0)")
     ap.add_argument("--seed", type=int, default=20240310)
     a = ap.parse_args()
     from rangeldm_amd import _lib
@@ -73,6 +77,26 @@ def main():
             for i in range(n):
                 losses_all.append(tra.train_step(imgs[i], generator=agen))
 
+    adv_steps, adv_all_steps = None, None
+    if a.discriminator:
+        from rangeldm_amd.discriminator import PatchDiscriminator
+        tr_adv = VAEDecoderTrainer(cfg, sd, device=dev, deterministic=a.deterministic,
+                                   discriminator=PatchDiscriminator(seed=a.seed, device=dev, deterministic=a.deterministic))
+        ggen = torch.Generator().manual_seed(a.seed)
+
+        def adv_steps(n):
+            for i in range(n):
+                training_step(tr_adv, vae, imgs[i], generator=ggen)
+
+        if a.trainable == "all":
+            tra_adv = VAETrainer(cfg, sd, device=dev, deterministic=a.deterministic,
+                                 discriminator=PatchDiscriminator(seed=a.seed, device=dev, deterministic=a.deterministic))
+            gagen = torch.Generator().manual_seed(a.seed)
+
+            def adv_all_steps(n):
+                for i in range(n):
+                    tra_adv.train_step(imgs[i], generator=gagen)
+
     unet_steps = None
     if not a.no_unet:
         from rangeldm_amd.schedulers import DDPMSchedulerHIP
@@ -89,12 +113,16 @@ def main():
     vae_steps(a.warmup)
     if all_steps is not None:
         all_steps(a.warmup)
+    for fn in (adv_steps, adv_all_steps):
+        if fn is not None:
+            fn(a.warmup)
     if unet_steps is not None:
         unet_steps(max(a.warmup, 2))                    # (step 1 runs eagerly and sizes the scratch buffers, step 2 captures)
     torch.cuda.synchronize()
-    sps = {"vae_decoder": [], "vae_all": [], "unet": []}
+    sps = {"vae_decoder": [], "vae_all": [], "unet": [], "vae_decoder_adv": [], "vae_all_adv": []}
     for _ in range(a.repeats):
-        for name, fn in (("vae_decoder", vae_steps), ("vae_all", all_steps), ("unet", unet_steps)):
+        for name, fn in (("vae_decoder", vae_steps), ("vae_decoder_adv", adv_steps), ("vae_all", all_steps), ("vae_all_adv", adv_all_steps),
+                         ("unet", unet_steps)):
             if fn is None:
                 continue
             torch.cuda.synchronize()
@@ -116,6 +144,12 @@ def main():
         out["vae_all"] = {"metric": "whole-VAE training samples/sec (encoder + posterior + decoder, L1 + KL), same run", "value": va["median"],
                           "samples_per_sec": va, "ms_per_step": 1e3 * B / va["median"], "parameters": tra.numel,
                           "loss_first_last": [float(losses_all[0]), float(losses_all[-1])]}
+    for name, plain in (("vae_decoder_adv", "vae_decoder"), ("vae_all_adv", "vae_all")):
+        if sps[name]:
+            t = tri(sps[name])
+            out[name] = {"metric": "adversarial step samples/sec (PatchGAN ndf 64, disc_start 0), same run", "value": t["median"],
+                         "samples_per_sec": t, "ms_per_step": 1e3 * B / t["median"],
+                         "time_ratio_to_plain": float(np.median(sps[plain]) / t["median"])}
     if unet_steps is not None:
         out["unet_step_samples_per_sec"] = tri(sps["unet"])
     print(json.dumps(out))
