@@ -728,6 +728,9 @@ int rldm_train_wgrad_group_pending(void);   /* queued layers (tests) */
  *   disc_bn_forward / _backward   fp64 partials per 256 rows, added in index order (both modes); no atomics.
  *   disc_hinge / _generator       l1's partials and folds (see rldm_train_disc_hinge); the gradients are element-wise.
  *   disc_lrelu / _adaptive_mix    element-wise.
+ *   meta_forward / _backward      GEMM reductions cut into K slices leave partial tiles that are added in slice order, the gathers
+ *                          (dx, dr) add their rows in a fixed order (both modes); the three bias sums are colsum's.
+ *   meta_range / _range_grad      element-wise.
  * The RCCL all-reduce of a multi-rank step is outside this guarantee. */
 int rldm_train_deterministic(int on);
 int rldm_train_deterministic_enabled(void);
@@ -899,6 +902,46 @@ int rldm_train_disc_generator(const float* fake, int64_t n, float* dfake, double
  *   dpred[i] = dnll[i] + s dg[i],  s = d_weight disc_factor rounded once to fp32; product and sum rounded on their own. */
 int rldm_train_disc_adaptive_mix(const float* dnll, const float* dg, const double* sq_nll, const double* sq_g, float disc_weight,
                                  float disc_factor, float* dpred, double* d_weight, int64_t n, void* stream);
+
+/* ---- Meta-Kernel discriminator layer (rangeldm_amd/csrc/train_meta.hip; model.py:91-265, MetaKernel and
+ * NLayerDiscriminatorMetaKernel, which vae/configs/kitti360.yaml selects) ----
+ * Driven by rangeldm_amd/metakernel.py.  One layer: a 4x4 window, padding 1, stride 1 | 2, over x [B][W][H][C] and the range image
+ * r [B][W][H].  For output pixel (wo, ho) and tap t = 4 i + j (i: shift along H, j: shift along W) the source is w = (s wo + j - 1)
+ * mod W (W WRAPS), h = s ho + i - 1; outside [0, H) x reads 0 and r reads 100.  Wo = (W - 2) / s + 1, Ho = (H - 2) / s + 1.  A ROW
+ * is a (pixel, tap) pair, row = 16 px + t.  In fp32, in this order, with tables [4][16] = cos_azi | sin_azi | cos_inc | sin_inc:
+ *   rc = r[(s wo + 1) mod W][s ho + 1];  pe0 = (rt ca[t]) ci[t] - rc;  pe1 = (rt ca[t]) si[t];  pe2 = rt sa[t]
+ *   h[k] = lrelu_0.2(((W1[k][0] pe0 + W1[k][1] pe1) + W1[k][2] pe2) + b1[k])
+ *   m[c] = sum_k r(h[k]) r(W2[c][k]) + b2[c]           (bf16 MFMA, fp32 accumulation; C = 2: fp32 on the VALU, nothing rounded)
+ *   y[n] = sum_{t,c} r(m[c] x[c]) r(coov[n][16 c + t]) + bias[n]    (bf16 MFMA);   r_next[px] = rc
+ * r(.) rounds to bf16 as the operand tile is staged in LDS.  Kept for the backward, the caller's: pe [rows][3], src [rows] (the
+ * source pixel index, -1 outside H), m [rows][C] fp32.  Backward, from dy [B][Wo][Ho][N]:
+ *   G = r(dy) r(coov);  dcoov += r(dy)^T r(m x);  dbias += colsum dy;  dx = gather of G m;  dm = G x;  db2 += colsum dm;
+ *   dW2 += r(dm)^T r(h);  dh = r(dm) r(W2);  dpre = dh lrelu'(pre);  db1 += colsum dpre;  dW1 += dpre^T pe and dpe = dpre W1 in fp32;
+ *   dr = gather of dpe over both roles of a pixel (tap: (dpe0 ci) ca + (dpe1 si) ca + dpe2 sa; centre: minus its pixel's sixteen
+ *   dpe0) + dr_next of the pixel whose centre it is.
+ * Gathers, not scatters: no floating-point atomics; split reductions leave partial tiles that are added in slice order in both modes
+ * of rldm_train_deterministic (the three column sums are rldm_train_colsum's).  The six parameter gradients (into zeroed or
+ * accumulating buffers) are given together or all NULL (input gradient alone); dx may be NULL (no data gradient), dr NULL with or
+ * without it (no range gradient: a discriminator step never needs one).
+ * Instances: C = 2 or a multiple of 16; N = 1 or a multiple of 16; stride 1 | 2; W, H >= 2; anything else is an error (_ok: 0). */
+typedef struct rldm_train_meta_desc {
+    int32_t B, Win, Hin, C;     /* input tensor */
+    int32_t N;                  /* output channels */
+    int32_t stride;             /* 1 | 2 */
+} rldm_train_meta_desc;
+int rldm_train_meta_ok(const rldm_train_meta_desc* d);
+/* bytes of scratch for _forward / _backward */
+int64_t rldm_train_meta_workspace(const rldm_train_meta_desc* d);
+/* r[p] = (x[p][0] range_std + range_mean) / 10 over npix pixels of C channels; _range_grad: dx[p][0] += (dr[p] / 10) range_std */
+int rldm_train_meta_range(const float* x, int64_t npix, int C, float range_mean, float range_std, float* r, void* stream);
+int rldm_train_meta_range_grad(const float* dr, int64_t npix, int C, float range_std, float* dx, void* stream);
+int rldm_train_meta_forward(const rldm_train_meta_desc* d, const float* x, const float* r, const float* tables, const float* w1,
+                            const float* b1, const float* w2, const float* b2, const float* coov, const float* bias, float* y,
+                            float* r_next, float* pe, int32_t* src, float* m, void* workspace, int64_t workspace_bytes, void* stream);
+int rldm_train_meta_backward(const rldm_train_meta_desc* d, const float* x, const float* dy, const float* tables, const float* w1,
+                             const float* b1, const float* w2, const float* coov, const float* pe, const int32_t* src, const float* m,
+                             const float* dr_next, float* dx, float* dr, float* dw1, float* db1, float* dw2, float* db2, float* dcoov,
+                             float* dbias, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- introspection used by bench.py / tests ----------------------------------------------------------------- */
 /* algorithmic FLOPs (2*MACs of conv/linear/QK^T/PV) of one UNet forward / VAE decode / encode for batch B */

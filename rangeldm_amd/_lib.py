@@ -103,6 +103,11 @@ class TrainConvDescC(C.Structure):
                 ("taps", C.c_int32), ("stride", C.c_int32), ("mode", C.c_int32)]
 
 
+class TrainMetaDescC(C.Structure):
+    """rldm_train_meta_desc: one Meta-Kernel layer (4x4 window, padding 1, W wraps) over an input (B, Win, Hin, C)."""
+    _fields_ = [("B", C.c_int32), ("Win", C.c_int32), ("Hin", C.c_int32), ("C", C.c_int32), ("N", C.c_int32), ("stride", C.c_int32)]
+
+
 class TrainDiscConvDescC(C.Structure):
     """rldm_train_disc_conv_desc: the discriminator's 4x4 conv, zero-padded 1 on both axes (W does not wrap)."""
     _fields_ = [("B", C.c_int32), ("Win", C.c_int32), ("Hin", C.c_int32), ("Cin", C.c_int32), ("N", C.c_int32), ("stride", C.c_int32)]
@@ -289,6 +294,13 @@ PROTOTYPES = {
     "rldm_train_disc_hinge": (C.c_int, [_P, _P, C.c_int64, C.c_float, _P, _P, _P, _P, _P]),
     "rldm_train_disc_generator": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
     "rldm_train_disc_adaptive_mix": (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, _P, _P, C.c_int64, _P]),
+    # the Meta-Kernel discriminator layer (csrc/train_meta.hip)
+    "rldm_train_meta_ok": (C.c_int, [C.POINTER(TrainMetaDescC)]),
+    "rldm_train_meta_workspace": (C.c_int64, [C.POINTER(TrainMetaDescC)]),
+    "rldm_train_meta_range": (C.c_int, [_P, C.c_int64, C.c_int, C.c_float, C.c_float, _P, _P]),
+    "rldm_train_meta_range_grad": (C.c_int, [_P, C.c_int64, C.c_int, C.c_float, _P, _P]),
+    "rldm_train_meta_forward": (C.c_int, [C.POINTER(TrainMetaDescC)] + [_P] * 15 + [C.c_int64, _P]),
+    "rldm_train_meta_backward": (C.c_int, [C.POINTER(TrainMetaDescC)] + [_P] * 20 + [C.c_int64, _P]),
     "rldm_unet_flops": (C.c_double, [_P, C.c_int]),
     "rldm_vae_decode_flops": (C.c_double, [_P, C.c_int, C.c_int, C.c_int]),
     "rldm_unet_num_launches": (C.c_int, [_P, C.c_int]),

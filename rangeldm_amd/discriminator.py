@@ -13,9 +13,10 @@ training mode (batch statistics, running averages, num_batches_tracked) whenever
 
 `PatchDiscriminator` drives the HIP kernels of rangeldm_amd/csrc/train_disc.hip (rldm_train_disc_*) from a host-side tape, on
 `TapeTrainer`'s flat buffers; `forward_host` restates the network in torch functional ops (autograd-capable, optionally with the conv
-operands rounded to bf16 where the kernels round) and is the tests' reference.  Not built: the Meta-Kernel variants
-(NLayerDiscriminatorMetaKernel*), `disc_bev`, `vanilla_d_loss`, ActNorm, gradient exchange between ranks.  No torch autograd and no torch
-compute ops on the device path; no CPU fallback."""
+operands rounded to bf16 where the kernels round) and is the tests' reference.  The range-guided Meta-Kernel network that
+vae/configs/kitti360.yaml selects is metakernel.py's, built on this module's BatchNorm, LeakyReLU and loss kernels.  Not built: its
+variant 2 (NLayerDiscriminatorMetaKernel2), `disc_bev`, `vanilla_d_loss`, ActNorm, gradient exchange between ranks.  No torch autograd
+and no torch compute ops on the device path; no CPU fallback."""
 import ctypes as C
 from collections import OrderedDict
 from dataclasses import dataclass

@@ -3,7 +3,7 @@
     python -m rangeldm_amd.train_vae --weights DIR | --sgm-ckpt F --sgm-yaml Y  [--input NPY_DIR] --out DIR --steps N
                                      [--trainable decoder|all] [--kl-weight 1e-6]
                                      [--batch-size 8] [--lr 4.5e-6] [--mode] [--seed S] [--log-every K] [--deterministic]
-                                     [--discriminator patchgan --disc-start N --disc-weight 0.5 [--disc-state FILE]]
+                                     [--discriminator patchgan|metakernel --disc-start N --disc-weight 0.5 [--disc-state FILE]]
 
 --trainable decoder (the default) leaves the encoder, and with it the latent space, as it is.  --trainable all trains encoder and
 decoder jointly with loss = L1 + kl_weight * kl and adds "kl" to every log line; it moves the latent space, so UNets trained on the old
@@ -11,7 +11,9 @@ latents no longer apply and scaling_factor must be estimated again.
 
 --discriminator patchgan adds the reference's adversarial phase (rangeldm_amd/discriminator.py) from step --disc-start on: every log
 line of that phase gains "g_loss", "d_weight", "disc_loss", "logits_real", "logits_fake", and OUT/discriminator.pt (PatchDiscriminator's
-save_state; --disc-state FILE resumes from one) is written beside OUT/vae/.  Without it the command prints and writes what it always did.
+save_state; --disc-state FILE resumes from one) is written beside OUT/vae/.  --discriminator metakernel does the same against the
+range-guided Meta-Kernel discriminator that the reference's kitti360.yaml selects (rangeldm_amd/metakernel.py,
+MetaKernelDiscriminator).  Without the option the command prints and writes what it always did.
 
 --input holds the (2, W, H) .npy range images `evaluate vae --input` reads (batches walk the sorted files and wrap around); without
 it the run trains on the synthetic batch of `evaluate vae`.  Without --weights / --sgm-ckpt the synthetic weights of `evaluate vae`
@@ -44,10 +46,11 @@ def build_parser():
     ap.add_argument("--seed", type=int, default=20240310)
     ap.add_argument("--log-every", type=int, default=10, metavar="K")
     ap.add_argument("--deterministic", action="store_true", help="bit-reproducible decoder step (slower)")
-    ap.add_argument("--discriminator", choices=("patchgan",), default=None, help="train adversarially against a PatchGAN from --disc-start on")
+    ap.add_argument("--discriminator", choices=("patchgan", "metakernel"), default=None,
+                    help="train adversarially from --disc-start on against the PatchGAN or the Meta-Kernel discriminator")
     ap.add_argument("--disc-start", type=int, default=0, metavar="N", help="first step (0-based) of the adversarial phase")
     ap.add_argument("--disc-weight", type=float, default=0.5, help="factor of the adaptive weight")
-    ap.add_argument("--disc-state", default=None, metavar="FILE", help="a discriminator.pt to resume the PatchGAN from")
+    ap.add_argument("--disc-state", default=None, metavar="FILE", help="a discriminator.pt to resume the discriminator from")
     return ap
 
 
@@ -114,9 +117,14 @@ def main(argv=None):
     everything = a.trainable == "all"
     adv = {}
     if a.discriminator:
-        from .discriminator import DiscriminatorConfig, PatchDiscriminator
-        disc = PatchDiscriminator(DiscriminatorConfig(in_channels=cfg.out_channels), seed=a.seed, device=dev, lr=a.lr,
-                                  deterministic=a.deterministic)
+        if a.discriminator == "metakernel":
+            from .metakernel import MetaKernelConfig, MetaKernelDiscriminator
+            disc = MetaKernelDiscriminator(MetaKernelConfig(in_channels=cfg.out_channels), seed=a.seed, device=dev, lr=a.lr,
+                                           deterministic=a.deterministic)
+        else:
+            from .discriminator import DiscriminatorConfig, PatchDiscriminator
+            disc = PatchDiscriminator(DiscriminatorConfig(in_channels=cfg.out_channels), seed=a.seed, device=dev, lr=a.lr,
+                                      deterministic=a.deterministic)
         if a.disc_state:
             disc.load_state(a.disc_state)
         adv = dict(discriminator=disc, disc_start=a.disc_start, disc_weight=a.disc_weight)

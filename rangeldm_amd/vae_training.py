@@ -1,6 +1,7 @@
 """VAE training on MI355X: the reference's reconstruction phase before its discriminator starts (`GeneralLPIPSWithDiscriminator`
 with logvar = 0, perceptual_weight = 0, range_weight = 40, intensity_weight = 10: channel-weighted L1, summed over the image and divided
-by the batch) and, with a `discriminator` (discriminator.PatchDiscriminator), its adversarial phase from `disc_start` on.
+by the batch) and, with a `discriminator` (discriminator.PatchDiscriminator, or metakernel.MetaKernelDiscriminator: the one the
+reference's kitti360.yaml selects), its adversarial phase from `disc_start` on.
 
 `VAEDecoderTrainer` trains the decoder against the frozen encoder.  The latent space does not move: every trained UNet and every
 captured sampler stays valid.
@@ -20,7 +21,7 @@ step of its own.  ONE DEVIATION, on purpose: the reference runs the autoencoder'
 posterior sample -- for the discriminator's step; here the discriminator sees the reconstruction of the generator's step, which saves
 a VAE forward.  `PatchDiscriminator.discriminator_step` is public: a caller who wants the other thing runs it on a fresh forward.
 
-Not built: the Meta-Kernel discriminators, `disc_bev`, the vanilla GAN loss, a
+Not built: variant 2 of the Meta-Kernel discriminator and its `log=True` range mapping, `disc_bev`, the vanilla GAN loss, a
 trainable `logvar` of the loss (it stays at its initial 0, the reference's `learn_logvar: False`), the BEV / perceptual terms, EMA, a
 captured step graph, gradient exchange between ranks.  No torch autograd, no torch compute ops on the path; no CPU fallback.
 
@@ -230,9 +231,9 @@ class VAEDecoderTrainer(_VAETape):
         they are (handed on by load_into / save_pretrained), never read by a kernel of this class.
         deterministic: every kernel of this trainer runs in the library's deterministic mode (rldm_train_deterministic), as
         UNetTrainer(deterministic=True): the same inputs give the same parameter bits.
-        discriminator: a discriminator.PatchDiscriminator; from step disc_start on train_step runs the adversarial phase (module
-        docstring) with disc_weight / disc_factor, the reference's names.  None, or before disc_start: the step is exactly what it
-        is without one, and the discriminator is not run."""
+        discriminator: a discriminator.PatchDiscriminator or a metakernel.MetaKernelDiscriminator; from step disc_start on train_step
+        runs the adversarial phase (module docstring) with disc_weight / disc_factor, the reference's names.  None, or before
+        disc_start: the step is exactly what it is without one, and the discriminator is not run."""
         self._init_vae(config, state_dict, decoder_param_names, ("decoder.conv_in.weight",), device, lr, betas, eps, weight_decay,
                        max_grad_norm, channel_weights, deterministic, discriminator, disc_start, disc_weight, disc_factor)
 

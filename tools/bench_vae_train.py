@@ -4,7 +4,7 @@ encode + posterior sample on the inference kernels, decoder forward, L1, backwar
 eager launches (no captured step graph exists for this trainer).
 
     python tools/bench_vae_train.py [--batch 8] [--steps 10] [--warmup 3] [--repeats 5] [--no-unet] [--deterministic]
-                                    [--trainable decoder|all] [--discriminator]
+                                    [--trainable decoder|all] [--discriminator [patchgan|metakernel]]
 
 After the warm-up, --repeats timed runs of --steps steps each (a host clock around work that ends in a device synchronise): median
 [min, max].  Achieved TFLOP/s counts 3 x AutoencoderKLHIP.decode_flops (decoder forward + backward; the encode is not counted).  In the
@@ -14,7 +14,8 @@ encoder, posterior, decoder, L1 + KL, backward through all three, Adam over ever
 `training_step`), interleaved with the other two in the same run (samples/s only: the library counts no encoder FLOPs).  --discriminator
 adds the adversarial step of every timed VAE trainer -- a second trainer of the same kind with a PatchDiscriminator and disc_start = 0:
 generator term, adaptive weight, mixed backward, the PatchGAN's own hinge step -- interleaved with the plain ones in the same run, and
-reports its ratio to the plain step.  One JSON line."""
+reports its ratio to the plain step.  --discriminator metakernel times, beside those, the same step against the Meta-Kernel
+discriminator (rangeldm_amd/metakernel.py; `vae_decoder_meta` / `vae_all_meta`), all in the same interleaved run.  One JSON line."""
 import argparse
 import json
 import os
@@ -40,7 +41,8 @@ def main():
     ap.add_argument("--no-unet", action="store_true", help="skip the UNet step (a profiler run wants the decoder step alone)")
     ap.add_argument("--deterministic", action="store_true", help="VAEDecoderTrainer(deterministic=True)")
     ap.add_argument("--trainable", choices=("decoder", "all"), default="decoder", help="all: also time VAETrainer's whole-VAE step")
-    ap.add_argument("--discriminator", action="store_true", help="also time the adversarial step (PatchGAN, disc_start = 0)")
+    ap.add_argument("--discriminator", nargs="?", const="patchgan", default=None, choices=("patchgan", "metakernel"),
+                    help="also time the adversarial step (disc_start = 0) against the PatchGAN; metakernel: and against the Meta-Kernel one")
     ap.add_argument("--seed", type=int, default=20240310)
     a = ap.parse_args()
     from rangeldm_amd import _lib
@@ -97,6 +99,26 @@ def main():
                 for i in range(n):
                     tra_adv.train_step(imgs[i], generator=gagen)
 
+    meta_steps, meta_all_steps = None, None
+    if a.discriminator == "metakernel":
+        from rangeldm_amd.metakernel import MetaKernelDiscriminator
+        tr_meta = VAEDecoderTrainer(cfg, sd, device=dev, deterministic=a.deterministic,
+                                    discriminator=MetaKernelDiscriminator(seed=a.seed, device=dev, deterministic=a.deterministic))
+        mgen = torch.Generator().manual_seed(a.seed)
+
+        def meta_steps(n):
+            for i in range(n):
+                training_step(tr_meta, vae, imgs[i], generator=mgen)
+
+        if a.trainable == "all":
+            tra_meta = VAETrainer(cfg, sd, device=dev, deterministic=a.deterministic,
+                                  discriminator=MetaKernelDiscriminator(seed=a.seed, device=dev, deterministic=a.deterministic))
+            magen = torch.Generator().manual_seed(a.seed)
+
+            def meta_all_steps(n):
+                for i in range(n):
+                    tra_meta.train_step(imgs[i], generator=magen)
+
     unet_steps = None
     if not a.no_unet:
         from rangeldm_amd.schedulers import DDPMSchedulerHIP
@@ -113,16 +135,17 @@ def main():
     vae_steps(a.warmup)
     if all_steps is not None:
         all_steps(a.warmup)
-    for fn in (adv_steps, adv_all_steps):
+    for fn in (adv_steps, adv_all_steps, meta_steps, meta_all_steps):
         if fn is not None:
             fn(a.warmup)
     if unet_steps is not None:
         unet_steps(max(a.warmup, 2))                    # (step 1 runs eagerly and sizes the scratch buffers, step 2 captures)
     torch.cuda.synchronize()
-    sps = {"vae_decoder": [], "vae_all": [], "unet": [], "vae_decoder_adv": [], "vae_all_adv": []}
+    sps = {"vae_decoder": [], "vae_all": [], "unet": [], "vae_decoder_adv": [], "vae_all_adv": [], "vae_decoder_meta": [],
+           "vae_all_meta": []}
     for _ in range(a.repeats):
         for name, fn in (("vae_decoder", vae_steps), ("vae_decoder_adv", adv_steps), ("vae_all", all_steps), ("vae_all_adv", adv_all_steps),
-                         ("unet", unet_steps)):
+                         ("vae_decoder_meta", meta_steps), ("vae_all_meta", meta_all_steps), ("unet", unet_steps)):
             if fn is None:
                 continue
             torch.cuda.synchronize()
@@ -144,10 +167,12 @@ def main():
         out["vae_all"] = {"metric": "whole-VAE training samples/sec (encoder + posterior + decoder, L1 + KL), same run", "value": va["median"],
                           "samples_per_sec": va, "ms_per_step": 1e3 * B / va["median"], "parameters": tra.numel,
                           "loss_first_last": [float(losses_all[0]), float(losses_all[-1])]}
-    for name, plain in (("vae_decoder_adv", "vae_decoder"), ("vae_all_adv", "vae_all")):
+    for name, plain in (("vae_decoder_adv", "vae_decoder"), ("vae_all_adv", "vae_all"), ("vae_decoder_meta", "vae_decoder"),
+                        ("vae_all_meta", "vae_all")):
         if sps[name]:
             t = tri(sps[name])
-            out[name] = {"metric": "adversarial step samples/sec (PatchGAN ndf 64, disc_start 0), same run", "value": t["median"],
+            kind = "Meta-Kernel" if name.endswith("_meta") else "PatchGAN"
+            out[name] = {"metric": f"adversarial step samples/sec ({kind} ndf 64, disc_start 0), same run", "value": t["median"],
                          "samples_per_sec": t, "ms_per_step": 1e3 * B / t["median"],
                          "time_ratio_to_plain": float(np.median(sps[plain]) / t["median"])}
     if unet_steps is not None:
