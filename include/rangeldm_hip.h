@@ -263,6 +263,19 @@ int rldm_lidar_to_points(rldm_lidar* l, const float* range_images, int B, int C,
 /* to_voxel (ldm/dataset.py:280-294 over _splat_points_to_volumes :13-132): -> voxel device fp32 (B, 2*D, H, W):
  * D planes of [log(1 +)] vote density, then D planes of density-normalised remission.  C >= 2. */
 int rldm_lidar_to_voxel(rldm_lidar* l, const float* range_images, int B, int C, int W, float* voxel, void* stream);
+/* to_voxel for training: `voxel` takes the bits rldm_lidar_to_voxel writes, `raw` device fp32 (B, 2*D, H, W) keeps the
+ * accumulators before the finalise step: D planes of the vote density d, then D planes of the weighted remission sum S
+ * (voxel = log(d + 1) or d | S / max(d, 1e-4)).  The votes are fp32 atomics, as rldm_lidar_to_voxel's. */
+int rldm_lidar_to_voxel_train(rldm_lidar* l, const float* range_images, int B, int C, int W, float* raw, float* voxel,
+                              void* stream);
+/* d(loss) / d(range_images) for d(loss) / d(voxel) = dvoxel (B, 2*D, H, W), given the image and the raw accumulators of
+ * rldm_lidar_to_voxel_train: dimages device fp32 (B, 2, W, beams), channel 0 the range value's, channel 1 the remission's.
+ * Two launches, no atomics: per cell a = gD / (d + 1) [or gD] - [d >= 1e-4] gF S / d^2 and e = gF / max(d, 1e-4) into
+ * cell_grad (scratch, the shape of dvoxel); per pixel a gather over its 8 cells, recomputed with the forward's expressions
+ * (votes of weight 0 inside the grid included).  0 in both channels where the forward dropped the pixel; 0 in channel 0
+ * where the decoded range was negative and replaced by range_fill.  fp32, a fixed operation order: bit-reproducible. */
+int rldm_lidar_to_voxel_backward(rldm_lidar* l, const float* range_images, int B, int C, int W, const float* raw,
+                                 const float* dvoxel, float* cell_grad, float* dimages, void* stream);
 /* `pc[np.linalg.norm(pc[:, :3], 2, axis=1) < max_depth]` per image, order preserved (ldm/inference.py:177-179):
  * points [B][N][cols] -> out [B][N][cols] (first counts[b] rows valid), counts device int32 [B]. cols = 3 or 4. */
 int rldm_lidar_filter_points(rldm_lidar* l, const float* points, int B, int N, int cols, float max_depth, float* out,

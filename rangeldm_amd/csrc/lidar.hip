@@ -5,6 +5,8 @@
 //   range_to_points_kernel   point_cloud_to_range_image.to_pc_torch          ldm/dataset.py:228-278
 //   bev_splat_kernel         to_voxel + _splat_points_to_volumes (votes)     ldm/dataset.py:280-288, 13-124
 //   bev_finalize_kernel      feature / clamp(density), log(density + 1)      ldm/dataset.py:126-130, 289-293
+//   bev_finalize_train / bev_cell_grad / bev_pixel_grad   to_voxel for training: raw accumulators kept, the backward a gather
+//                                                         (vae/sgm/modules/autoencoding/losses: disc_bev, bev_rec_weight)
 //   filter_count / filter_scatter   `pc[norm(pc[:, :3]) < 90]` in order      ldm/inference.py:177-179
 //   render_u8_kernel         `(x.permute(2,1,0).clip(0,1)*255).astype(u8)`   ldm/inference.py:180-183
 //   project_* kernels        point_cloud_to_range_image.__call__ + process_miss_value + normalize
@@ -33,11 +35,17 @@ struct LidarDev {
     float mean, std, range_fill, intensity_fill;
 };
 
-__device__ inline float decode_range(float v, const LidarDev& L) {
+// the decoded range before `r_true[r_true < 0] = range_fill` (ldm/dataset.py:240-245)
+__device__ inline float decode_range_raw(float v, const LidarDev& L) {
     float r;
     if (L.mode == 1) r = f_sub(exp2f(f_mul(v, 6.f)), 1.f);
     else if (L.mode == 2) r = f_div(1.f, fmaxf(v, 0.0001f));
     else r = f_add(f_mul(v, L.std), L.mean);
+    return r;
+}
+
+__device__ inline float decode_range(float v, const LidarDev& L) {
+    const float r = decode_range_raw(v, L);
     return r < 0.f ? L.range_fill : r;
 }
 
@@ -142,6 +150,115 @@ __global__ __launch_bounds__(256) void bev_finalize_kernel(float* __restrict__ v
     if (d == 0.f) return;               // no votes: feature 0 / min_weight = 0 and log(0 + 1) = 0 are already there
     feat[i] = f_div(feat[i], fmaxf(d, min_weight));
     if (log_density) dens[i] = logf(f_add(d, 1.f));
+}
+
+// ---- to_voxel for training: the raw accumulators are kept, the backward is a gather --------------------------------
+// bev_finalize_kernel out of place: raw (B, 2*gz, gy, gx) = (d | S) stays as the splat left it, vox takes the bits
+// rldm_lidar_to_voxel writes (an empty cell: 0 and 0).
+__global__ __launch_bounds__(256) void bev_finalize_train_kernel(const float* __restrict__ raw, float* __restrict__ vox,
+                                                                 size_t nvox, int log_density, float min_weight) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const int b = blockIdx.y;
+    if (i >= nvox) return;
+    const float* rd = raw + (size_t)b * 2 * nvox;
+    float* dens = vox + (size_t)b * 2 * nvox;
+    const float d = rd[i], S = rd[nvox + i];
+    if (d == 0.f) { dens[i] = d; dens[nvox + i] = S; return; }
+    dens[nvox + i] = f_div(S, fmaxf(d, min_weight));
+    dens[i] = log_density ? logf(f_add(d, 1.f)) : d;
+}
+
+// Backward, launch 1, one thread per cell: the finalise step's derivative.  With gD, gF the upstream gradients of the two
+// output planes:  a = d(loss) / d(d) = gD / (d + 1) [log] or gD, minus [d >= min_weight] gF S / d^2 (clamp(min) passes the
+// gradient where d >= min);  e = d(loss) / d(S) = gF / max(d, min_weight).  cg (B, 2*gz, gy, gx) = (a | e).
+__global__ __launch_bounds__(256) void bev_cell_grad_kernel(const float* __restrict__ raw, const float* __restrict__ dvox,
+                                                            float* __restrict__ cg, size_t nvox, int log_density,
+                                                            float min_weight) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const int b = blockIdx.y;
+    if (i >= nvox) return;
+    const size_t o = (size_t)b * 2 * nvox;
+    const float d = raw[o + i], S = raw[o + nvox + i];
+    const float gD = dvox[o + i], gF = dvox[o + nvox + i];
+    float a = log_density ? f_div(gD, f_add(d, 1.f)) : gD;
+    if (d >= min_weight) a = f_sub(a, f_div(f_mul(gF, S), f_mul(d, d)));
+    cg[o + i] = a;
+    cg[o + nvox + i] = f_div(gF, fmaxf(d, min_weight));
+}
+
+// Backward, launch 2, one thread per pixel: the pixel recomputes its cell, remainders and in-grid tests with the forward's own
+// expressions and GATHERS from cg -- no atomics.  A vote of weight 0 whose cell is inside the grid is included: its
+// weight's derivative is not 0.  dimg (B, 2, W, H): channel 0 = d / d(range value), channel 1 = d / d(remission).
+// A pixel the forward dropped gets 0 in both; one whose decoded range was negative (replaced by range_fill, a constant) gets 0
+// in channel 0 and, should the fill point lie inside the volume, its remission gradient in channel 1.
+__global__ __launch_bounds__(256) void bev_pixel_grad_kernel(const float* __restrict__ img, int C, int W, int H, LidarDev L,
+                                                             const float* __restrict__ cos_azi, const float* __restrict__ sin_azi,
+                                                             GridDev G, const float* __restrict__ cg, float* __restrict__ dimg) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    const int b = blockIdx.y;
+    const int N = W * H;
+    if (n >= N) return;
+    const float* im = img + (size_t)b * C * N;
+    float* out = dimg + (size_t)b * 2 * N;
+    const float v = im[n];
+    const float r = decode_range(v, L);
+    const float f = im[N + n];
+    const int w_ = n / H, h_ = n % H;
+    float x, y, z;
+    pixel_to_xyz(r, w_, h_, L, cos_azi, sin_azi, &x, &y, &z);
+    const float px = grid_coord(x, G.cx, G.hx, G.gx), py = grid_coord(y, G.cy, G.hy, G.gy), pz = grid_coord(z, G.cz, G.hz, G.gz);
+    if (!(px > -1.f && px < (float)G.gx && py > -1.f && py < (float)G.gy && pz > -1.f && pz < (float)G.gz)) {
+        out[n] = 0.f;
+        out[N + n] = 0.f;
+        return;
+    }
+    const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);
+    const int X = (int)fx, Y = (int)fy, Z = (int)fz;
+    const float rx = f_sub(px, fx), ry = f_sub(py, fy), rz = f_sub(pz, fz);
+    const size_t nvox = (size_t)G.gz * G.gy * G.gx;
+    const float* A = cg + (size_t)b * 2 * nvox;
+    const float* E = A + nvox;
+    float df = 0.f, dpx = 0.f, dpy = 0.f, dpz = 0.f;
+#pragma unroll
+    for (int dx = 0; dx < 2; ++dx) {
+        const int X_ = X + dx;
+        const float wx = dx ? rx : f_sub(1.f, rx);
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy) {
+            const int Y_ = Y + dy;
+            const float wy = dy ? ry : f_sub(1.f, ry);
+#pragma unroll
+            for (int dz = 0; dz < 2; ++dz) {
+                const int Z_ = Z + dz;
+                const float wz = dz ? rz : f_sub(1.f, rz);
+                const bool ok = X_ >= 0 && X_ < G.gx && Y_ >= 0 && Y_ < G.gy && Z_ >= 0 && Z_ < G.gz;
+                if (ok) {
+                    const size_t idx = ((size_t)Z_ * G.gy + Y_) * G.gx + X_;
+                    const float e = E[idx];
+                    const float q = f_add(A[idx], f_mul(f, e));
+                    df = f_add(df, f_mul(f_mul(f_mul(wx, wy), wz), e));
+                    const float tx = f_mul(q, f_mul(wy, wz)), ty = f_mul(q, f_mul(wx, wz)), tz = f_mul(q, f_mul(wx, wy));
+                    dpx = dx ? f_add(dpx, tx) : f_sub(dpx, tx);
+                    dpy = dy ? f_add(dpy, ty) : f_sub(dpy, ty);
+                    dpz = dz ? f_add(dpz, tz) : f_sub(dpz, tz);
+                }
+            }
+        }
+    }
+    // d(range) / d(value); 0 where the decoded range was replaced by the constant range_fill
+    float drdv;
+    if (decode_range_raw(v, L) < 0.f) drdv = 0.f;
+    else if (L.mode == 1) drdv = f_mul(4.1588830833596715f, exp2f(f_mul(v, 6.f)));          // 6 ln 2
+    else if (L.mode == 2) drdv = v > 0.0001f ? f_div(-1.f, f_mul(v, v)) : 0.f;
+    else drdv = L.std;
+    const float kx = f_div(f_mul(0.5f, (float)(G.gx - 1)), G.hx), ky = f_div(f_mul(0.5f, (float)(G.gy - 1)), G.hy),
+                kz = f_div(f_mul(0.5f, (float)(G.gz - 1)), G.hz);
+    const float ci = L.cos_incl[h_], si = L.sin_incl[h_];
+    const float gx_ = f_mul(f_mul(f_mul(dpx, kx), ci), cos_azi[w_]);
+    const float gy_ = f_mul(f_mul(f_mul(dpy, ky), ci), sin_azi[w_]);
+    const float gz_ = f_mul(f_mul(dpz, kz), si);
+    out[n] = f_mul(f_sub(f_add(gx_, gy_), gz_), drdv);
+    out[N + n] = df;
 }
 
 // ---- ordered depth filter ---------------------------------------------------------------------------------------
@@ -428,6 +545,57 @@ int rldm_lidar_to_voxel(rldm_lidar* l, const float* range_images, int B, int C, 
     bev_splat_kernel<<<dim3((N + 255) / 256, B), 256, 0, st>>>(range_images, C, W, c.beams, l->dev(), ca, sa, G, voxel);
     RLDM_HIP_CHECK(hipGetLastError());
     bev_finalize_kernel<<<dim3((unsigned)((nvox + 255) / 256), B), 256, 0, st>>>(voxel, nvox, c.normalize_volume_densities, 1e-4f);
+    RLDM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+static GridDev lidar_grid(const rldm_lidar_config& c) {
+    GridDev G;
+    G.gz = c.grid[0]; G.gy = c.grid[1]; G.gx = c.grid[2];
+    G.cx = (c.pc_range[3] + c.pc_range[0]) / 2.f; G.hx = (c.pc_range[3] - c.pc_range[0]) / 2.f;
+    G.cy = (c.pc_range[4] + c.pc_range[1]) / 2.f; G.hy = (c.pc_range[4] - c.pc_range[1]) / 2.f;
+    G.cz = (c.pc_range[5] + c.pc_range[2]) / 2.f; G.hz = (c.pc_range[5] - c.pc_range[2]) / 2.f;
+    return G;
+}
+
+int rldm_lidar_to_voxel_train(rldm_lidar* l, const float* range_images, int B, int C, int W, float* raw, float* voxel,
+                              void* stream) {
+    RLDM_REQUIRE(l && range_images && raw && voxel, "null argument");
+    RLDM_REQUIRE(B > 0 && W > 0, "bad shape");
+    RLDM_REQUIRE(C >= 2, "to_voxel needs the remission channel (ldm/dataset.py:286 splats pc[:, :, 3:])");
+    const float *ca, *sa;
+    if (lidar_azimuth(l, W, &ca, &sa)) return 1;
+    const rldm_lidar_config& c = l->cfg;
+    const GridDev G = lidar_grid(c);
+    const size_t nvox = (size_t)G.gz * G.gy * G.gx;
+    hipStream_t st = (hipStream_t)stream;
+    RLDM_HIP_CHECK(hipMemsetAsync(raw, 0, (size_t)B * 2 * nvox * sizeof(float), st));
+    const int N = W * c.beams;
+    bev_splat_kernel<<<dim3((N + 255) / 256, B), 256, 0, st>>>(range_images, C, W, c.beams, l->dev(), ca, sa, G, raw);
+    RLDM_HIP_CHECK(hipGetLastError());
+    bev_finalize_train_kernel<<<dim3((unsigned)((nvox + 255) / 256), B), 256, 0, st>>>(raw, voxel, nvox,
+                                                                                     c.normalize_volume_densities, 1e-4f);
+    RLDM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int rldm_lidar_to_voxel_backward(rldm_lidar* l, const float* range_images, int B, int C, int W, const float* raw,
+                                 const float* dvoxel, float* cell_grad, float* dimages, void* stream) {
+    RLDM_REQUIRE(l && range_images && raw && dvoxel && cell_grad && dimages, "null argument");
+    RLDM_REQUIRE(B > 0 && W > 0, "bad shape");
+    RLDM_REQUIRE(C >= 2, "to_voxel needs the remission channel (ldm/dataset.py:286 splats pc[:, :, 3:])");
+    const float *ca, *sa;
+    if (lidar_azimuth(l, W, &ca, &sa)) return 1;
+    const rldm_lidar_config& c = l->cfg;
+    const GridDev G = lidar_grid(c);
+    const size_t nvox = (size_t)G.gz * G.gy * G.gx;
+    hipStream_t st = (hipStream_t)stream;
+    bev_cell_grad_kernel<<<dim3((unsigned)((nvox + 255) / 256), B), 256, 0, st>>>(raw, dvoxel, cell_grad, nvox,
+                                                                                c.normalize_volume_densities, 1e-4f);
+    RLDM_HIP_CHECK(hipGetLastError());
+    const int N = W * c.beams;
+    bev_pixel_grad_kernel<<<dim3((N + 255) / 256, B), 256, 0, st>>>(range_images, C, W, c.beams, l->dev(), ca, sa, G, cell_grad,
+                                                                    dimages);
     RLDM_HIP_CHECK(hipGetLastError());
     return 0;
 }

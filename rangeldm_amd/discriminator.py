@@ -15,7 +15,8 @@ training mode (batch statistics, running averages, num_batches_tracked) whenever
 `TapeTrainer`'s flat buffers; `forward_host` restates the network in torch functional ops (autograd-capable, optionally with the conv
 operands rounded to bf16 where the kernels round) and is the tests' reference.  The range-guided Meta-Kernel network that
 vae/configs/kitti360.yaml selects is metakernel.py's, built on this module's BatchNorm, LeakyReLU and loss kernels.  Not built: its
-variant 2 (NLayerDiscriminatorMetaKernel2), `disc_bev`, `vanilla_d_loss`, ActNorm, gradient exchange between ranks.  No torch autograd
+variant 2 (NLayerDiscriminatorMetaKernel2), `vanilla_d_loss`, ActNorm, gradient exchange between ranks.  (`disc_bev`, the PatchGAN on
+the BEV volume of the reconstruction, is the VAE trainers': vae_training.py.)  No torch autograd
 and no torch compute ops on the device path; no CPU fallback."""
 import ctypes as C
 from collections import OrderedDict

@@ -93,6 +93,182 @@ class point_cloud_to_range_image:
                                                   _lib.stream_ptr(x.device)), "rldm_lidar_to_voxel")
         return out
 
+    # ---- to_voxel for training (vae_training.py: disc_bev, bev_rec_weight) ----------------------------------
+    def to_voxel_train(self, range_images):
+        """`to_voxel` that keeps what its backward needs: -> (voxel, saved).  voxel holds the bits `to_voxel` returns; saved =
+        (the fp32 image, raw (B, 2 * D, H, W): the vote density d and the weighted remission sum S before the finalise step)."""
+        x = self._images(range_images)
+        B, Cc, W, H = x.shape
+        D, GH, GW = self.grid_sizes
+        raw = torch.empty((B, 2 * D, GH, GW), dtype=torch.float32, device=x.device)
+        out = torch.empty_like(raw)
+        _lib.check(_lib.lib().rldm_lidar_to_voxel_train(self._handle(), x.data_ptr(), B, Cc, W, raw.data_ptr(), out.data_ptr(),
+                                                        _lib.stream_ptr(x.device)), "rldm_lidar_to_voxel_train")
+        return out, (x, raw)
+
+    def to_voxel_backward(self, saved, dvoxel):
+        """d(loss) / d(range_images) (B, 2, W, H) for d(loss) / d(voxel) = dvoxel (B, 2 * D, H, W) and `saved` of to_voxel_train: two
+        launches, no atomics, bit-reproducible (rldm_lidar_to_voxel_backward).  Channels beyond the first two get no vote and no
+        gradient."""
+        x, raw = saved
+        B, Cc, W, H = x.shape
+        if tuple(dvoxel.shape) != tuple(raw.shape) or not dvoxel.is_cuda:
+            raise ValueError(f"dvoxel must be a device tensor of shape {tuple(raw.shape)}, got {tuple(dvoxel.shape)}")
+        g = dvoxel.detach().float().contiguous()
+        cell = torch.empty_like(raw)
+        out = torch.empty((B, 2, W, H), dtype=torch.float32, device=x.device)
+        _lib.check(_lib.lib().rldm_lidar_to_voxel_backward(self._handle(), x.data_ptr(), B, Cc, W, raw.data_ptr(), g.data_ptr(),
+                                                           cell.data_ptr(), out.data_ptr(), _lib.stream_ptr(x.device)),
+                   "rldm_lidar_to_voxel_backward")
+        return out
+
+    # ---- host statements of to_voxel and its backward (plain torch; the tests' references) -------------------
+    def _bev_geometry(self, x, points=None, tables="reference"):
+        """What bev_splat_kernel computes per pixel before it votes, in x's dtype, one torch operation per device operation (in fp32
+        every step is the kernel's single rounding).  tables: "reference" -- cos / sin of the fp32 inclinations by torch in fp32, as
+        the reference's to_pc_torch takes them -- or "library": in fp64, rounded once to fp32, as rldm_lidar_create builds them (the
+        two differ in the last bit of a few beams).  The azimuth's cos / sin are taken in fp64 of the angle in x's dtype (the
+        reference's own in fp64, the library's table in fp32).  points (B, W * H, >= 3): take x, y, z from there instead (the device's
+        own to_pc_torch output, which removes the libm's exp2f from a comparison).  Differentiable in x through the remainders."""
+        B, Cc, W, H = x.shape
+        dt, dev = x.dtype, x.device
+        gz, gy, gx = (int(g) for g in self.grid_sizes)
+        if tables not in ("reference", "library"):
+            raise ValueError(f"tables is 'reference' or 'library', not {tables!r}")
+        incl = torch.from_numpy(np.ascontiguousarray(self.incl, np.float32))
+        if tables == "library":
+            incl = incl.double()
+        ci, si = torch.cos(incl).float().to(dt).to(dev), torch.sin(incl).float().to(dt).to(dev)
+        hgt = torch.from_numpy(np.ascontiguousarray(self.height, np.float32)).to(dt).to(dev)
+        azi = (W - 0.5 - torch.arange(0, W, dtype=dt, device=dev)) / W * 2. * torch.pi - torch.pi
+        ca, sa = torch.cos(azi.double()).to(dt), torch.sin(azi.double()).to(dt)
+        v, f = x[:, 0], x[:, 1]
+        if self.log:
+            raw = 2 ** (v * 6) - 1
+        elif self.inverse:
+            raw = 1 / torch.where(v > 1e-4, v, torch.full_like(v, 1e-4))
+        else:
+            raw = v * self.std + self.mean
+        replaced = raw < 0
+        r = torch.where(replaced, torch.full_like(raw, float(self.range_fill_value[0])), raw)
+        xy = r * ci[None, None, :]
+        pz_m = hgt[None, None, :] - r * si[None, None, :]
+        px_m, py_m = xy * ca[None, :, None], xy * sa[None, :, None]
+        if points is not None:
+            p3 = points.to(dt).reshape(B, W, H, -1)
+            px_m, py_m, pz_m = p3[..., 0], p3[..., 1], p3[..., 2]
+        rng = torch.tensor([float(c) for c in self.pc_range], dtype=dt, device=dev)
+        centre, half = (rng[3:] + rng[:3]) / 2, (rng[3:] - rng[:3]) / 2
+        coords, touch = [], torch.ones_like(replaced)
+        for m, k, g in ((px_m, 0, gx), (py_m, 1, gy), (pz_m, 2, gz)):
+            p = (((m - centre[k]) / half[k] + 1) * 0.5) * (g - 1)
+            coords.append(p)
+            touch = touch & (p > -1) & (p < g)                       # (False for NaN, as the kernel's test)
+        fl = [torch.floor(torch.where(touch, p.detach(), torch.zeros_like(p))) for p in coords]
+        rem = [torch.where(touch, p, torch.zeros_like(p)) - q for p, q in zip(coords, fl)]
+        return dict(v=v, f=f, replaced=replaced, touch=touch, cell=[q.long() for q in fl], rem=rem, tables=(ci, si, ca, sa),
+                    half=half, grid=(gx, gy, gz))
+
+    @staticmethod
+    def _bev_votes(geo):
+        """The 8 votes of every pixel: [(dx, dy, dz, flat cell index (0 where the vote is dropped), in-grid mask, wx, wy, wz)]."""
+        gx, gy, gz = geo["grid"]
+        (X, Y, Z), (rx, ry, rz) = geo["cell"], geo["rem"]
+        out = []
+        for dx in (0, 1):
+            wx = rx if dx else 1 - rx
+            for dy in (0, 1):
+                wy = ry if dy else 1 - ry
+                for dz in (0, 1):
+                    wz = rz if dz else 1 - rz
+                    X_, Y_, Z_ = X + dx, Y + dy, Z + dz
+                    ok = geo["touch"] & (X_ >= 0) & (X_ < gx) & (Y_ >= 0) & (Y_ < gy) & (Z_ >= 0) & (Z_ < gz)
+                    idx = torch.where(ok, (Z_ * gy + Y_) * gx + X_, torch.zeros_like(X_))
+                    out.append((dx, dy, dz, idx, ok, wx, wy, wz))
+        return out
+
+    def to_voxel_host(self, range_images, return_raw=False, tables="reference"):
+        """The reference's to_pc_torch + to_voxel + _splat_points_to_volumes (ldm/dataset.py:13-132, 228-294) in plain torch, on any
+        device, in the input's dtype (fp32 or fp64), differentiable in range_images.  Votes outside the volume are dropped (the
+        reference adds them to a random voxel with weight 0).  return_raw: -> (voxel, d, S), the accumulators (B, D, H, W) before the
+        finalise step.  tables: see _bev_geometry."""
+        x = range_images
+        if x.dim() != 4 or x.shape[3] != self.H or x.shape[1] < 2:
+            raise ValueError(f"range_images must be (B, >= 2, W, {self.H}), got {tuple(x.shape)}")
+        B = x.shape[0]
+        geo = self._bev_geometry(x, tables=tables)
+        gx, gy, gz = geo["grid"]
+        nvox = gx * gy * gz
+        base = (torch.arange(B, device=x.device) * nvox).reshape(B, 1, 1)
+        d = torch.zeros(B * nvox, dtype=x.dtype, device=x.device)
+        S = torch.zeros_like(d)
+        for _, _, _, idx, ok, wx, wy, wz in self._bev_votes(geo):
+            w = torch.where(ok, wx * wy * wz, torch.zeros_like(wx))
+            flat = (idx + base).reshape(-1)
+            d = d.index_add(0, flat, w.reshape(-1))
+            S = S.index_add(0, flat, (w * geo["f"]).reshape(-1))
+        d, S = d.reshape(B, gz, gy, gx), S.reshape(B, gz, gy, gx)
+        feat = S / d.clamp(min=1e-4)
+        vox = torch.cat([torch.log(d + 1) if self.normalize_volume_densities else d, feat], 1)
+        return (vox, d, S) if return_raw else vox
+
+    def to_voxel_backward_host(self, images, d_raw, S_raw, dvoxel, points=None, return_terms=False, tables="reference"):
+        """rldm_lidar_to_voxel_backward stated in torch: the geometry (cells, remainders, in-grid tests) in `images`' dtype by
+        _bev_geometry -- the kernel's own fp32 numbers for an fp32 image --, then the two steps in fp64, given the accumulators d_raw,
+        S_raw (B, D, H, W): per cell a = gD / (d + 1) [or gD] - [d >= 1e-4] gF S / d^2, e = gF / max(d, 1e-4); per pixel the gather
+        over its in-grid votes (weight 0 included) and the chain rule through grid coordinate, point and decoded range.  The 1e-4 is
+        the fp32 number the kernels compare with when images are fp32.  -> dimages (B, 2, W, H) fp64; return_terms: also the sum of
+        |every product the gather adds| per output element (same shape), what a rounding bound of the device's result scales with.
+        points, tables: see _bev_geometry (a comparison with the device passes its points and tables="library")."""
+        with torch.no_grad():
+            x = images.detach()
+            B, Cc, W, H = x.shape
+            geo = self._bev_geometry(x, points, tables)
+            gx, gy, gz = geo["grid"]
+            nvox = gx * gy * gz
+            mw = float(np.float32(1e-4)) if x.dtype == torch.float32 else 1e-4
+            d, S = d_raw.detach().double().reshape(B, nvox), S_raw.detach().double().reshape(B, nvox)
+            g = dvoxel.detach().double().reshape(B, 2, nvox)
+            gD, gF = g[:, 0], g[:, 1]
+            a1 = gD / (d + 1) if self.normalize_volume_densities else gD
+            a2 = torch.where(d >= mw, gF * S / torch.where(d >= mw, d * d, torch.ones_like(d)), torch.zeros_like(d))
+            a, e = a1 - a2, gF / d.clamp(min=mw)
+            a_abs = a1.abs() + a2.abs()
+            f = geo["f"].double()
+            zero = torch.zeros_like(f)
+            df, dp, df_abs, dp_abs = zero.clone(), [zero.clone() for _ in range(3)], zero.clone(), [zero.clone() for _ in range(3)]
+            for dx, dy, dz, idx, ok, wx, wy, wz in self._bev_votes(geo):
+                wx, wy, wz = wx.double(), wy.double(), wz.double()
+                flat = idx.reshape(B, -1)
+                av, ev = (torch.gather(t, 1, flat).reshape(f.shape) for t in (a, e))
+                aa = torch.gather(a_abs, 1, flat).reshape(f.shape)
+                q, q_abs = av + f * ev, aa + (f * ev).abs()
+                m = ok.double()
+                df += m * wx * wy * wz * ev
+                df_abs += m * (wx * wy * wz * ev).abs()
+                for k, (s, ww) in enumerate(((dx, wy * wz), (dy, wx * wz), (dz, wx * wy))):
+                    dp[k] += m * (2 * s - 1) * q * ww
+                    dp_abs[k] += m * q_abs * ww.abs()
+            v = geo["v"].double()
+            if self.log:
+                drdv = 6 * np.log(2.0) * 2 ** (6 * v)
+            elif self.inverse:
+                drdv = torch.where(v > mw, -1 / (v * v), torch.zeros_like(v))
+            else:
+                drdv = torch.full_like(v, float(self.std))
+            drdv = torch.where(geo["replaced"], torch.zeros_like(drdv), drdv)
+            ci, si, ca, sa = (t.double() for t in geo["tables"])
+            half = geo["half"].double()
+            k = [0.5 * (n - 1) / half[i] for i, n in enumerate((gx, gy, gz))]
+            jac = (k[0] * ci[None, None, :] * ca[None, :, None], k[1] * ci[None, None, :] * sa[None, :, None],
+                   (-k[2] * si[None, None, :]).expand(1, W, H))
+            dv = (dp[0] * jac[0] + dp[1] * jac[1] + dp[2] * jac[2]) * drdv
+            out = torch.stack([dv, df], 1)
+            if not return_terms:
+                return out
+            dv_abs = (dp_abs[0] * jac[0].abs() + dp_abs[1] * jac[1].abs() + dp_abs[2] * jac[2].abs()) * drdv.abs()
+            return out, torch.stack([dv_abs, df_abs], 1)
+
     def filter_points(self, point_cloud, max_depth=90.0):
         """Per image `pc[np.linalg.norm(pc[:, :3], 2, axis=1) < max_depth]`, order kept (ldm/inference.py:177-179).
         Returns (points (B, N, cols) with the kept rows packed to the front, counts (B,) int32), both on device."""

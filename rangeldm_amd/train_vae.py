@@ -4,6 +4,7 @@
                                      [--trainable decoder|all] [--kl-weight 1e-6]
                                      [--batch-size 8] [--lr 4.5e-6] [--mode] [--seed S] [--log-every K] [--deterministic]
                                      [--discriminator patchgan|metakernel --disc-start N --disc-weight 0.5 [--disc-state FILE]]
+                                     [--disc-bev] [--bev-rec-weight X] [--bev-grid D H W] [--bev-range x0 y0 z0 x1 y1 z1]
 
 --trainable decoder (the default) leaves the encoder, and with it the latent space, as it is.  --trainable all trains encoder and
 decoder jointly with loss = L1 + kl_weight * kl and adds "kl" to every log line; it moves the latent space, so UNets trained on the old
@@ -14,6 +15,11 @@ line of that phase gains "g_loss", "d_weight", "disc_loss", "logits_real", "logi
 save_state; --disc-state FILE resumes from one) is written beside OUT/vae/.  --discriminator metakernel does the same against the
 range-guided Meta-Kernel discriminator that the reference's kitti360.yaml selects (rangeldm_amd/metakernel.py,
 MetaKernelDiscriminator).  Without the option the command prints and writes what it always did.
+
+--bev-rec-weight X adds the BEV density term of rangeldm_amd/vae_training.py to the loss and "bev_rec" (the unweighted sum of
+|V(target) - V(pred)| over the density planes) to every log line; --disc-bev (with --discriminator patchgan) hands the PatchGAN the BEV
+volume of the reconstruction instead of the range image.  The volume is --bev-grid / --bev-range (defaults: the reference's
+kitti360.yaml); the sensor follows the image height: 64 beams KITTI-360, 32 nuScenes.  Neither runs with --deterministic.
 
 --input holds the (2, W, H) .npy range images `evaluate vae --input` reads (batches walk the sorted files and wrap around); without
 it the run trains on the synthetic batch of `evaluate vae`.  Without --weights / --sgm-ckpt the synthetic weights of `evaluate vae`
@@ -51,6 +57,11 @@ def build_parser():
     ap.add_argument("--disc-start", type=int, default=0, metavar="N", help="first step (0-based) of the adversarial phase")
     ap.add_argument("--disc-weight", type=float, default=0.5, help="factor of the adaptive weight")
     ap.add_argument("--disc-state", default=None, metavar="FILE", help="a discriminator.pt to resume the discriminator from")
+    ap.add_argument("--disc-bev", action="store_true", help="the PatchGAN judges the BEV volume of the reconstruction")
+    ap.add_argument("--bev-rec-weight", type=float, default=0.0, metavar="X", help="weight of the BEV density L1 term (0: off)")
+    ap.add_argument("--bev-grid", type=int, nargs=3, default=[1, 512, 512], metavar=("D", "H", "W"), help="grid_sizes of the BEV volume")
+    ap.add_argument("--bev-range", type=float, nargs=6, default=[-51.2, -51.2, -3.0, 51.2, 51.2, 1.0],
+                    metavar=("x0", "y0", "z0", "x1", "y1", "z1"), help="pc_range of the BEV volume [m]")
     return ap
 
 
@@ -67,11 +78,20 @@ def check_args(a):
         raise ValueError("--disc-start and --disc-weight must not be negative")
     if a.disc_state and not a.discriminator:
         raise ValueError("--disc-state goes with --discriminator")
+    if a.bev_rec_weight < 0:
+        raise ValueError("--bev-rec-weight must not be negative")
+    if a.disc_bev and a.discriminator != "patchgan":
+        raise ValueError("--disc-bev goes with --discriminator patchgan (the Meta-Kernel discriminator needs a range image)")
+    if (a.disc_bev or a.bev_rec_weight > 0) and a.deterministic:
+        raise ValueError("--disc-bev / --bev-rec-weight do not run with --deterministic (the BEV splat sums with fp32 atomics)")
+    if min(a.bev_grid) < 1 or any(a.bev_range[i + 3] <= a.bev_range[i] for i in range(3)):
+        raise ValueError("--bev-grid must be positive and --bev-range must be x0 y0 z0 x1 y1 z1 with x0 < x1, y0 < y1, z0 < z1")
 
 
-def log_record(step, loss, abs_sums, pixels, kl=None, adversarial=None):
+def log_record(step, loss, abs_sums, pixels, kl=None, adversarial=None, bev=None):
     """One log line: the loss of `step` (1-based) and the per-channel MAE = abs_sums[c] / pixels (pixels = B W H); kl (--trainable all):
-    the KL term, unweighted; adversarial (once that phase has started): (g_loss, d_weight, (disc_loss, logits_real, logits_fake))."""
+    the KL term, unweighted; adversarial (once that phase has started): (g_loss, d_weight, (disc_loss, logits_real, logits_fake)); bev
+    (--bev-rec-weight): the trainer's last_bev_rec, logged as "bev_rec"."""
     rec = {"step": int(step), "loss": float(loss), "mae": [float(s) / float(pixels) for s in abs_sums]}
     if kl is not None:
         rec["kl"] = float(kl)
@@ -79,7 +99,18 @@ def log_record(step, loss, abs_sums, pixels, kl=None, adversarial=None):
         g_loss, d_weight, (disc_loss, logits_real, logits_fake) = adversarial
         rec.update(g_loss=float(g_loss), d_weight=float(d_weight), disc_loss=float(disc_loss), logits_real=float(logits_real),
                    logits_fake=float(logits_fake))
+    if bev is not None:
+        rec["bev_rec"] = float(bev)
     return rec
+
+
+def bev_sensor(height, width, grid, pc_range):
+    """The point_cloud_to_range_image of the sensor with `height` beams (64: KITTI-360, 32: nuScenes) over the given BEV volume."""
+    from .range_image import point_cloud_to_range_image_KITTI, point_cloud_to_range_image_nuScenes
+    sensors = {64: point_cloud_to_range_image_KITTI, 32: point_cloud_to_range_image_nuScenes}
+    if height not in sensors:
+        raise ValueError(f"no sensor with {height} beams: the BEV terms need images of height 64 (KITTI-360) or 32 (nuScenes)")
+    return sensors[height](width=int(width), grid_sizes=[int(g) for g in grid], pc_range=[float(v) for v in pc_range])
 
 
 def batch_files(files, step, batch_size):
@@ -123,11 +154,14 @@ def main(argv=None):
                                            deterministic=a.deterministic)
         else:
             from .discriminator import DiscriminatorConfig, PatchDiscriminator
-            disc = PatchDiscriminator(DiscriminatorConfig(in_channels=cfg.out_channels), seed=a.seed, device=dev, lr=a.lr,
-                                      deterministic=a.deterministic)
+            disc = PatchDiscriminator(DiscriminatorConfig(in_channels=2 * a.bev_grid[0] if a.disc_bev else cfg.out_channels),
+                                      seed=a.seed, device=dev, lr=a.lr, deterministic=a.deterministic)
         if a.disc_state:
             disc.load_state(a.disc_state)
         adv = dict(discriminator=disc, disc_start=a.disc_start, disc_weight=a.disc_weight)
+    if a.disc_bev or a.bev_rec_weight > 0:
+        adv.update(bev=bev_sensor(cfg.sample_size[1], cfg.sample_size[0], a.bev_grid, a.bev_range), bev_rec_weight=a.bev_rec_weight,
+                   disc_bev=a.disc_bev)
     if everything:
         trainer = VAETrainer(cfg, sd, device=dev, lr=a.lr, kl_weight=a.kl_weight, deterministic=a.deterministic, **adv)
     else:
@@ -153,7 +187,8 @@ def main(argv=None):
         if (step + 1) % a.log_every == 0 or step + 1 == a.steps:
             started = a.discriminator and trainer.last_disc is not None
             last = log_record(step + 1, loss, trainer.last_abs_sums.cpu().tolist(), pixels, trainer.last_kl if everything else None,
-                              (trainer.last_g_loss, trainer.last_d_weight, trainer.last_disc) if started else None)
+                              (trainer.last_g_loss, trainer.last_d_weight, trainer.last_disc) if started else None,
+                              trainer.last_bev_rec if a.bev_rec_weight > 0 else None)
             print(json.dumps(last), flush=True)
     trainer.save_pretrained(a.out)
     if a.discriminator:

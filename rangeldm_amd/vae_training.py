@@ -21,9 +21,24 @@ step of its own.  ONE DEVIATION, on purpose: the reference runs the autoencoder'
 posterior sample -- for the discriminator's step; here the discriminator sees the reconstruction of the generator's step, which saves
 a VAE forward.  `PatchDiscriminator.discriminator_step` is public: a caller who wants the other thing runs it on a fresh forward.
 
-Not built: variant 2 of the Meta-Kernel discriminator and its `log=True` range mapping, `disc_bev`, the vanilla GAN loss, a
-trainable `logvar` of the loss (it stays at its initial 0, the reference's `learn_logvar: False`), the BEV / perceptual terms, EMA, a
-captured step graph, gradient exchange between ranks.  No torch autograd, no torch compute ops on the path; no CPU fallback.
+The BEV terms (both trainers; `bev=` a range_image.point_cloud_to_range_image of the images' sensor) rest on a differentiable
+`to_voxel`: range_image.to_voxel_train keeps the splat's raw accumulators, to_voxel_backward brings a volume gradient back to the image
+in two launches without atomics (rangeldm_amd/csrc/lidar.hip).  The target's volume is the inference `to_voxel`'s, once per step.
+  bev_rec_weight > 0   adds (bev_rec_weight / B) sum |V(target)[:, :gz] - V(pred)[:, :gz]| (rldm_train_l1 over the density planes) to
+                       the loss; its image-space gradient joins the L1's before the adaptive weight is taken, so it counts in
+                       |d nll / d w|.  `last_bev_rec`: the unweighted sum, a 0-d float64 device tensor; the returned loss includes the
+                       term.  DEVIATION, on purpose: the reference adds the term to `nll_loss` AFTER `weighted_nll_loss` was formed, so
+                       there it reaches the adaptive weight and the log but never the optimised loss.  Here it is a real loss term.
+  disc_bev=True        the PatchGAN judges V(pred), all 2 gz planes (a MetaKernelDiscriminator is refused: its range guidance needs a
+                       range image); its input gradient returns through to_voxel_backward, and its own step sees (V(target), V(pred)).
+SECOND DEVIATION: the reference reassigns `inputs` and `reconstructions` to the volumes once bev_rec_weight > 0, so its discriminator
+then sees volumes whatever `disc_bev` says; here the two switches are independent -- pass both to reproduce the reference.  Neither
+runs with deterministic=True (NotImplementedError): the forward splat sums its votes with fp32 atomics.
+
+Not built: variant 2 of the Meta-Kernel discriminator and its `log=True` range mapping, an order-fixed (bit-reproducible) BEV splat, the
+vanilla GAN loss, a trainable `logvar` of the loss (it stays at its initial 0, the reference's `learn_logvar: False`), the perceptual
+terms (`bev_perceptual` among them), EMA, a captured step graph, gradient exchange between ranks.  No torch autograd, no torch compute
+ops on the path; no CPU fallback.
 
 Parity: tests/test_vae_training_gpu.py and tests/test_vae_encoder_training_gpu.py compare every parameter gradient, and the parameters
 after optimizer steps, with torch autograd / torch.optim.Adam on the oracle (oracle/vae.py)."""
@@ -108,7 +123,9 @@ class _VAETape(TapeTrainer):
     state."""
 
     def _init_vae(self, config, state_dict, names, no_dx, device, lr, betas, eps, weight_decay, max_grad_norm, channel_weights,
-                  deterministic, discriminator=None, disc_start=0, disc_weight=0.5, disc_factor=1.0):
+                  deterministic, discriminator=None, disc_start=0, disc_weight=0.5, disc_factor=1.0, bev=None, bev_rec_weight=0.0,
+                  disc_bev=False):
+        self._init_bev(bev, bev_rec_weight, disc_bev, deterministic, discriminator)
         self.cfg = config if isinstance(config, VAEConfig) else VAEConfig(**config)
         if len(channel_weights) != self.cfg.out_channels:
             raise ValueError(f"{len(channel_weights)} channel weights for {self.cfg.out_channels} output channels")
@@ -125,6 +142,33 @@ class _VAETape(TapeTrainer):
         self.disc_weight, self.disc_factor = float(disc_weight), float(disc_factor)
         self.last_g_loss = self.last_d_weight = self.last_disc = None
         self._conv_out_in = None
+        if self.bev is not None and (self.disc_bev or self.bev_rec_weight > 0) and int(self.bev.H) != int(self.cfg.sample_size[1]):
+            raise ValueError(f"bev is a {self.bev.H}-beam sensor, the VAE's images have H = {self.cfg.sample_size[1]}")
+
+    def _init_bev(self, bev, bev_rec_weight, disc_bev, deterministic, discriminator):
+        """The BEV switches and their refusals (module docstring); with the defaults nothing here is ever read again."""
+        self.bev, self.bev_rec_weight, self.disc_bev = bev, float(bev_rec_weight), bool(disc_bev)
+        self.last_bev_rec = None
+        if self.bev_rec_weight < 0:
+            raise ValueError("bev_rec_weight must not be negative")
+        if not (self.disc_bev or self.bev_rec_weight > 0):
+            return
+        if bev is None:
+            raise ValueError("disc_bev / bev_rec_weight need bev=, a point_cloud_to_range_image of the images' sensor")
+        if deterministic:
+            raise NotImplementedError("the BEV terms are not bit-reproducible: to_voxel's splat sums its votes with fp32 atomics "
+                                      "(an order-fixed splat is not built)")
+        gz = int(bev.grid_sizes[0])
+        if self.bev_rec_weight > 0 and gz > 16:
+            raise ValueError(f"bev_rec_weight: rldm_train_l1 takes at most 16 density planes, the grid has {gz}")
+        if self.disc_bev:
+            from .discriminator import PatchDiscriminator
+            from .metakernel import MetaKernelDiscriminator                 # (a subclass of PatchDiscriminator)
+            if not isinstance(discriminator, PatchDiscriminator) or isinstance(discriminator, MetaKernelDiscriminator):
+                raise ValueError("disc_bev needs a discriminator.PatchDiscriminator (the Meta-Kernel discriminator's range guidance "
+                                 "needs a range image, not a BEV volume)")
+            if discriminator.cfg.in_channels != 2 * gz:
+                raise ValueError(f"disc_bev: the BEV volume has {2 * gz} planes, the discriminator takes {discriminator.cfg.in_channels}")
 
     # ---- network ----------------------------------------------------------------------------------------------
     def _resnet(self, x, p):
@@ -172,7 +216,30 @@ class _VAETape(TapeTrainer):
         far) has reached disc_start -- the reference's adopt_weight(disc_factor, global_step, threshold=disc_start)."""
         return self.discriminator is not None and self.global_step >= self.disc_start
 
-    def _adversarial_step(self, pred, dnll, real_nchw):
+    # ---- BEV terms ----------------------------------------------------------------------------------------------
+    def _bev_active(self):
+        return self.bev_rec_weight > 0 or (self.disc_bev and self.adversarial())
+
+    def _bev_volumes(self, pred, target_nchw):
+        """-> (V(target): the inference to_voxel, no gradient; V(pred), saved: to_voxel_train of the reconstruction)."""
+        vt = self.bev.to_voxel(target_nchw)
+        vp, saved = self.bev.to_voxel_train(T.unpack_output(pred))
+        return vt, vp, saved
+
+    def _bev_rec(self, dpred, volumes):
+        """The term (bev_rec_weight / B) sum |V(target)[:, :gz] - V(pred)[:, :gz]|: rldm_train_l1 over the density planes, its gradient
+        brought to image space by to_voxel_backward and added to dpred.  -> (dpred, the weighted term); last_bev_rec = the
+        unweighted sum, a 0-d float64 device tensor."""
+        vt, vp, saved = volumes
+        gz = int(self.bev.grid_sizes[0])
+        wc = torch.full((gz,), self.bev_rec_weight, dtype=torch.float32, device=self.device)
+        term, dplanes, sums = T.l1(T.pack_input(vp[:, :gz].contiguous(), False), vt[:, :gz].contiguous(), wc)
+        self.last_bev_rec = sums.sum()
+        dvox = torch.zeros_like(vp)
+        dvox[:, :gz] = T.unpack_output(dplanes)
+        return T.add(dpred, T.pack_input(self.bev.to_voxel_backward(saved, dvox), False)), term
+
+    def _adversarial_step(self, pred, dnll, real_nchw, volumes=None):
         """The steps behind the forward and the L1 of an adversarial train_step (module docstring): generator term through the
         discriminator (training-mode BatchNorm, as the reference), the adaptive weight from two weight gradients of conv_out alone,
         one backward with the mixed gradient, the VAE's Adam step, then the discriminator's own step on (real, pred) with the
@@ -180,9 +247,16 @@ class _VAETape(TapeTrainer):
         scalars, no host sync."""
         from . import discriminator as D
         disc = self.discriminator
-        disc.forward(pred, training=True, layout="nhwc")
-        self.last_g_loss, dlogits = disc.generator_loss()
-        dg = disc.input_gradient(dlogits)
+        if self.disc_bev:       # the discriminator judges the BEV volume: its input gradient comes back through to_voxel_backward
+            vt, vp, saved = volumes
+            disc.forward(vp, training=True, layout="nchw")
+            self.last_g_loss, dlogits = disc.generator_loss()
+            dg = T.pack_input(self.bev.to_voxel_backward(saved, T.unpack_output(disc.input_gradient(dlogits))), False)
+            real_nchw, pred = vt, vp
+        else:
+            disc.forward(pred, training=True, layout="nhwc")
+            self.last_g_loss, dlogits = disc.generator_loss()
+            dg = disc.input_gradient(dlogits)
         w = "decoder.conv_out.weight"
         sq = []
         for d in (dnll, dg):
@@ -225,7 +299,7 @@ class _VAETape(TapeTrainer):
 class VAEDecoderTrainer(_VAETape):
     def __init__(self, config, state_dict, device="cuda", lr=4.5e-6, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  max_grad_norm=None, channel_weights=(40.0, 10.0), deterministic=False, discriminator=None, disc_start=0,
-                 disc_weight=0.5, disc_factor=1.0):
+                 disc_weight=0.5, disc_factor=1.0, bev=None, bev_rec_weight=0.0, disc_bev=False):
         """The defaults are the reference's: torch.optim.Adam (AdamW with zero decay is Adam) at base_learning_rate 4.5e-6, no
         clipping, range_weight 40 / intensity_weight 10.  state_dict may hold the whole VAE: the encoder's tensors are kept as
         they are (handed on by load_into / save_pretrained), never read by a kernel of this class.
@@ -233,9 +307,11 @@ class VAEDecoderTrainer(_VAETape):
         UNetTrainer(deterministic=True): the same inputs give the same parameter bits.
         discriminator: a discriminator.PatchDiscriminator or a metakernel.MetaKernelDiscriminator; from step disc_start on train_step
         runs the adversarial phase (module docstring) with disc_weight / disc_factor, the reference's names.  None, or before
-        disc_start: the step is exactly what it is without one, and the discriminator is not run."""
+        disc_start: the step is exactly what it is without one, and the discriminator is not run.
+        bev, bev_rec_weight, disc_bev: the BEV terms (module docstring); with the defaults no code of theirs runs."""
         self._init_vae(config, state_dict, decoder_param_names, ("decoder.conv_in.weight",), device, lr, betas, eps, weight_decay,
-                       max_grad_norm, channel_weights, deterministic, discriminator, disc_start, disc_weight, disc_factor)
+                       max_grad_norm, channel_weights, deterministic, discriminator, disc_start, disc_weight, disc_factor, bev,
+                       bev_rec_weight, disc_bev)
 
     def forward(self, z_nchw):
         """z (B, z_channels, W / f, H / f) fp32 on the device, as the encoder emits it (not multiplied by scaling_factor)
@@ -255,8 +331,14 @@ class VAEDecoderTrainer(_VAETape):
             pred = self.forward(z_nchw)
             target = target_nchw.to(self.device).float().contiguous()
             loss, dpred, self.last_abs_sums = T.l1(pred, target, self.channel_weights)
+            volumes = None
+            if self._bev_active():
+                volumes = self._bev_volumes(pred, target)
+                if self.bev_rec_weight > 0:
+                    dpred, term = self._bev_rec(dpred, volumes)
+                    loss = loss + term
             if self.adversarial():
-                self._adversarial_step(pred, dpred, target)
+                self._adversarial_step(pred, dpred, target, volumes)
             else:
                 self.backward(dpred)
                 self.optimizer_step()
@@ -279,15 +361,15 @@ class VAEDecoderTrainer(_VAETape):
 class VAETrainer(_VAETape):
     def __init__(self, config, state_dict, device="cuda", lr=4.5e-6, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  max_grad_norm=None, kl_weight=1e-6, channel_weights=(40.0, 10.0), deterministic=False, discriminator=None,
-                 disc_start=0, disc_weight=0.5, disc_factor=1.0):
+                 disc_start=0, disc_weight=0.5, disc_factor=1.0, bev=None, bev_rec_weight=0.0, disc_bev=False):
         """Encoder and decoder trained jointly; the defaults are the reference's (VAEDecoderTrainer's, and kl_loss: 1e-6).  The
         parameters are every key of vae_param_shapes in tape order: the encoder as oracle.vae.vae_encode visits it, then the
         decoder.  Training the encoder moves the latent space: UNets trained on the old latents no longer apply, and scaling_factor
-        must be estimated again (module docstring).  deterministic, discriminator, disc_start, disc_weight, disc_factor: as
-        VAEDecoderTrainer."""
+        must be estimated again (module docstring).  deterministic, discriminator, disc_start, disc_weight, disc_factor, bev,
+        bev_rec_weight, disc_bev: as VAEDecoderTrainer."""
         self._init_vae(config, state_dict, lambda cfg, shapes: encoder_param_names(cfg, shapes) + decoder_param_names(cfg, shapes),
                        ("encoder.conv_in.weight",), device, lr, betas, eps, weight_decay, max_grad_norm, channel_weights, deterministic,
-                       discriminator, disc_start, disc_weight, disc_factor)
+                       discriminator, disc_start, disc_weight, disc_factor, bev, bev_rec_weight, disc_bev)
         self.kl_weight = float(kl_weight)
         self.last_kl = None
         self._moments = self._z = None
@@ -349,8 +431,14 @@ class VAETrainer(_VAETape):
         with self._mode():
             pred = self.forward(images, noise if sample_posterior else None)
             rec, dpred, self.last_abs_sums = T.l1(pred, images, self.channel_weights)
+            volumes = None
+            if self._bev_active():
+                volumes = self._bev_volumes(pred, images)
+                if self.bev_rec_weight > 0:
+                    dpred, term = self._bev_rec(dpred, volumes)
+                    rec = rec + term
             if self.adversarial():
-                self._adversarial_step(pred, dpred, images)
+                self._adversarial_step(pred, dpred, images, volumes)
             else:
                 self.backward(dpred)
                 self.optimizer_step()

@@ -4,7 +4,7 @@ encode + posterior sample on the inference kernels, decoder forward, L1, backwar
 eager launches (no captured step graph exists for this trainer).
 
     python tools/bench_vae_train.py [--batch 8] [--steps 10] [--warmup 3] [--repeats 5] [--no-unet] [--deterministic]
-                                    [--trainable decoder|all] [--discriminator [patchgan|metakernel]]
+                                    [--trainable decoder|all] [--discriminator [patchgan|metakernel]] [--disc-bev] [--bev-rec-weight X]
 
 After the warm-up, --repeats timed runs of --steps steps each (a host clock around work that ends in a device synchronise): median
 [min, max].  Achieved TFLOP/s counts 3 x AutoencoderKLHIP.decode_flops (decoder forward + backward; the encode is not counted).  In the
@@ -15,7 +15,9 @@ encoder, posterior, decoder, L1 + KL, backward through all three, Adam over ever
 adds the adversarial step of every timed VAE trainer -- a second trainer of the same kind with a PatchDiscriminator and disc_start = 0:
 generator term, adaptive weight, mixed backward, the PatchGAN's own hinge step -- interleaved with the plain ones in the same run, and
 reports its ratio to the plain step.  --discriminator metakernel times, beside those, the same step against the Meta-Kernel
-discriminator (rangeldm_amd/metakernel.py; `vae_decoder_meta` / `vae_all_meta`), all in the same interleaved run.  One JSON line."""
+discriminator (rangeldm_amd/metakernel.py; `vae_decoder_meta` / `vae_all_meta`), all in the same interleaved run.  --disc-bev and / or
+--bev-rec-weight X (with --discriminator) time, beside those, the PatchGAN step with the BEV terms of vae_training.py on the KITTI-360
+sensor and the reference's [1, 512, 512] volume over +-51.2 m (`vae_decoder_bev` / `vae_all_bev`).  One JSON line."""
 import argparse
 import json
 import os
@@ -43,8 +45,12 @@ def main():
     ap.add_argument("--trainable", choices=("decoder", "all"), default="decoder", help="all: also time VAETrainer's whole-VAE step")
     ap.add_argument("--discriminator", nargs="?", const="patchgan", default=None, choices=("patchgan", "metakernel"),
                     help="also time the adversarial step (disc_start = 0) against the PatchGAN; metakernel: and against the Meta-Kernel one")
+    ap.add_argument("--disc-bev", action="store_true", help="also time the PatchGAN step on the BEV volume of the reconstruction")
+    ap.add_argument("--bev-rec-weight", type=float, default=0.0, metavar="X", help="also time the step with the BEV density L1 term")
     ap.add_argument("--seed", type=int, default=20240310)
     a = ap.parse_args()
+    if (a.disc_bev or a.bev_rec_weight > 0) and not a.discriminator:
+        ap.error("--disc-bev / --bev-rec-weight are timed against the PatchGAN step: pass --discriminator")
     from rangeldm_amd import _lib
     from rangeldm_amd.config import PRESETS
     from rangeldm_amd.params import unet_param_shapes, vae_param_shapes
@@ -119,6 +125,30 @@ def main():
                 for i in range(n):
                     tra_meta.train_step(imgs[i], generator=magen)
 
+    bev_steps, bev_all_steps = None, None
+    if a.disc_bev or a.bev_rec_weight > 0:
+        from rangeldm_amd.discriminator import PatchDiscriminator
+        from rangeldm_amd.range_image import point_cloud_to_range_image_KITTI
+
+        def bev_kw():
+            return dict(discriminator=PatchDiscriminator(seed=a.seed, device=dev),
+                        bev=point_cloud_to_range_image_KITTI(width=W, grid_sizes=[1, 512, 512], pc_range=[-51.2, -51.2, -3., 51.2, 51.2, 1.]),
+                        bev_rec_weight=a.bev_rec_weight, disc_bev=a.disc_bev)
+        tr_bev = VAEDecoderTrainer(cfg, sd, device=dev, **bev_kw())
+        bgen = torch.Generator().manual_seed(a.seed)
+
+        def bev_steps(n):
+            for i in range(n):
+                training_step(tr_bev, vae, imgs[i], generator=bgen)
+
+        if a.trainable == "all":
+            tra_bev = VAETrainer(cfg, sd, device=dev, **bev_kw())
+            bagen = torch.Generator().manual_seed(a.seed)
+
+            def bev_all_steps(n):
+                for i in range(n):
+                    tra_bev.train_step(imgs[i], generator=bagen)
+
     unet_steps = None
     if not a.no_unet:
         from rangeldm_amd.schedulers import DDPMSchedulerHIP
@@ -135,17 +165,18 @@ def main():
     vae_steps(a.warmup)
     if all_steps is not None:
         all_steps(a.warmup)
-    for fn in (adv_steps, adv_all_steps, meta_steps, meta_all_steps):
+    for fn in (adv_steps, adv_all_steps, meta_steps, meta_all_steps, bev_steps, bev_all_steps):
         if fn is not None:
             fn(a.warmup)
     if unet_steps is not None:
         unet_steps(max(a.warmup, 2))                    # (step 1 runs eagerly and sizes the scratch buffers, step 2 captures)
     torch.cuda.synchronize()
     sps = {"vae_decoder": [], "vae_all": [], "unet": [], "vae_decoder_adv": [], "vae_all_adv": [], "vae_decoder_meta": [],
-           "vae_all_meta": []}
+           "vae_all_meta": [], "vae_decoder_bev": [], "vae_all_bev": []}
     for _ in range(a.repeats):
         for name, fn in (("vae_decoder", vae_steps), ("vae_decoder_adv", adv_steps), ("vae_all", all_steps), ("vae_all_adv", adv_all_steps),
-                         ("vae_decoder_meta", meta_steps), ("vae_all_meta", meta_all_steps), ("unet", unet_steps)):
+                         ("vae_decoder_meta", meta_steps), ("vae_all_meta", meta_all_steps), ("vae_decoder_bev", bev_steps),
+                         ("vae_all_bev", bev_all_steps), ("unet", unet_steps)):
             if fn is None:
                 continue
             torch.cuda.synchronize()
@@ -168,10 +199,12 @@ def main():
                           "samples_per_sec": va, "ms_per_step": 1e3 * B / va["median"], "parameters": tra.numel,
                           "loss_first_last": [float(losses_all[0]), float(losses_all[-1])]}
     for name, plain in (("vae_decoder_adv", "vae_decoder"), ("vae_all_adv", "vae_all"), ("vae_decoder_meta", "vae_decoder"),
-                        ("vae_all_meta", "vae_all")):
+                        ("vae_all_meta", "vae_all"), ("vae_decoder_bev", "vae_decoder"), ("vae_all_bev", "vae_all")):
         if sps[name]:
             t = tri(sps[name])
             kind = "Meta-Kernel" if name.endswith("_meta") else "PatchGAN"
+            if name.endswith("_bev"):
+                kind = f"PatchGAN, disc_bev {bool(a.disc_bev)}, bev_rec_weight {a.bev_rec_weight:g}, BEV 512 x 512;"
             out[name] = {"metric": f"adversarial step samples/sec ({kind} ndf 64, disc_start 0), same run", "value": t["median"],
                          "samples_per_sec": t, "ms_per_step": 1e3 * B / t["median"],
                          "time_ratio_to_plain": float(np.median(sps[plain]) / t["median"])}
