@@ -11,10 +11,11 @@ discriminator half of `GeneralLPIPSWithDiscriminator` (hinge loss, a second Adam
 The padding is ZERO padding on both axes: W does not wrap in this network, unlike every other conv of the library.  BatchNorm runs in
 training mode (batch statistics, running averages, num_batches_tracked) whenever the reference's does.
 
-`PatchDiscriminator` drives the HIP kernels of rangeldm_amd/csrc/train_disc.hip (rldm_train_disc_*) from a host-side tape, on
-`TapeTrainer`'s flat buffers; `forward_host` restates the network in torch functional ops (autograd-capable, optionally with the conv
-operands rounded to bf16 where the kernels round) and is the tests' reference.  The range-guided Meta-Kernel network that
-vae/configs/kitti360.yaml selects is metakernel.py's, built on this module's BatchNorm, LeakyReLU and loss kernels.  Not built: its
+`PatchDiscriminator` drives the HIP kernels of rangeldm_amd/csrc/train_disc.hip (rldm_train_disc_*) from its own walk over the
+layers, on `FlatParameters`' flat buffers (tape.py); `forward_host` restates the network in torch functional ops (autograd-capable,
+optionally with the conv operands rounded to bf16 where the kernels round) and is the tests' reference.  The range-guided Meta-Kernel
+network that vae/configs/kitti360.yaml selects is metakernel.py's: this module's walk, BatchNorm, LeakyReLU, loss kernels, optimizer
+step and state handling around its own layer.  Not built: its
 variant 2 (NLayerDiscriminatorMetaKernel2), `vanilla_d_loss`, ActNorm, gradient exchange between ranks.  (`disc_bev`, the PatchGAN on
 the BEV volume of the reconstruction, is the VAE trainers': vae_training.py.)  No torch autograd
 and no torch compute ops on the device path; no CPU fallback."""
@@ -28,7 +29,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import train_ops as T
-from .tape import TapeTrainer
+from .tape import FlatParameters
 
 BN_EPS, BN_MOMENTUM, SLOPE = 1e-5, 0.1, 0.2
 SGM_PREFIX = "loss.discriminator."
@@ -47,18 +48,23 @@ def _cfg(config):
     return config if isinstance(config, DiscriminatorConfig) else DiscriminatorConfig(**config)
 
 
-def layer_specs(cfg):
-    """The convs in forward order: dicts with name (`main.K`), cin, cout, stride, bias (bool), bn (`main.K+1` or None), act (bool)."""
-    cfg = _cfg(cfg)
-    out = [dict(name="main.0", cin=cfg.in_channels, cout=cfg.ndf, stride=2, bias=True, bn=None, act=True)]
+def pyramid(cfg):
+    """(name `main.K`, cin, cout, stride, bn `main.K+1` or None, act) of the layers in forward order: the widths and strides that the
+    PatchGAN and the Meta-Kernel network (whose config extends this one) share."""
+    yield "main.0", cfg.in_channels, cfg.ndf, 2, None, True
     mult = 1
     for n in range(1, cfg.n_layers + 1):
         prev, mult = mult, min(2 ** n, 8)
         k = 2 + 3 * (n - 1)
-        out.append(dict(name=f"main.{k}", cin=cfg.ndf * prev, cout=cfg.ndf * mult, stride=2 if n < cfg.n_layers else 1, bias=False,
-                        bn=f"main.{k + 1}", act=True))
-    out.append(dict(name=f"main.{2 + 3 * cfg.n_layers}", cin=cfg.ndf * mult, cout=1, stride=1, bias=True, bn=None, act=False))
-    return out
+        yield f"main.{k}", cfg.ndf * prev, cfg.ndf * mult, 2 if n < cfg.n_layers else 1, f"main.{k + 1}", True
+    yield f"main.{2 + 3 * cfg.n_layers}", cfg.ndf * mult, 1, 1, None, False
+
+
+def layer_specs(cfg):
+    """The convs in forward order: dicts with name (`main.K`), cin, cout, stride, bias (bool), bn (`main.K+1` or None), act (bool).
+    A conv in front of a BatchNorm has no bias."""
+    return [dict(name=name, cin=cin, cout=cout, stride=stride, bias=bn is None, bn=bn, act=act)
+            for name, cin, cout, stride, bn, act in pyramid(_cfg(cfg))]
 
 
 def param_shapes(cfg=None):
@@ -83,9 +89,10 @@ def trainable_names(cfg=None):
 
 
 def output_size(cfg, W, H):
-    """(Wo, Ho) of the logits for a (W, H) input."""
-    for L in layer_specs(cfg):
-        W, H = (W - 2) // L["stride"] + 1, (H - 2) // L["stride"] + 1
+    """(Wo, Ho) of the logits for a (W, H) input, for either network (the Meta-Kernel's W is counted on its W + 2 wrapped columns:
+    the same extents as with zero padding)."""
+    for _, _, _, stride, _, _ in pyramid(_cfg(cfg)):
+        W, H = conv_out_size(W, H, stride)
     return W, H
 
 
@@ -159,6 +166,19 @@ class _Bf16Conv(torch.autograd.Function):
         return dx, dw, (dy.sum((0, 2, 3)) if ctx.has_bias else None), None
 
 
+def batchnorm_running_host(h, state, buffers, bn, training):
+    """F.batch_norm of layer `bn` (its weight and bias from `state`); training: batch statistics, and the running statistics and
+    the counter updated IN `buffers`."""
+    rm, rv = buffers[bn + ".running_mean"], buffers[bn + ".running_var"]
+    rm_, rv_ = rm.detach().to(h.dtype, copy=True), rv.detach().to(h.dtype, copy=True)     # (autograd keeps what it is given)
+    h = F.batch_norm(h, rm_, rv_, state[bn + ".weight"].to(h.dtype), state[bn + ".bias"].to(h.dtype), training, BN_MOMENTUM, BN_EPS)
+    if training:
+        rm.copy_(rm_)
+        rv.copy_(rv_)
+        buffers[bn + ".num_batches_tracked"] += 1
+    return h
+
+
 def forward_host(state, x, training=True, bf16=False, buffers=None):
     """The network in plain torch: x (B, in_channels, W, H) -> logits (B, 1, Wo, Ho), differentiable in x and in every tensor of
     `state` that requires grad.  training: BatchNorm uses batch statistics and updates the running statistics IN `buffers` (a dict with
@@ -174,14 +194,7 @@ def forward_host(state, x, training=True, bf16=False, buffers=None):
         b = state[L["name"] + ".bias"].to(h.dtype) if L["bias"] else None
         h = _Bf16Conv.apply(h, w, b, L["stride"]) if bf16 else F.conv2d(h, w, b, stride=L["stride"], padding=1)
         if L["bn"]:
-            rm, rv = buffers[L["bn"] + ".running_mean"], buffers[L["bn"] + ".running_var"]
-            rm_, rv_ = rm.detach().to(h.dtype, copy=True), rv.detach().to(h.dtype, copy=True)     # (autograd keeps what it is given)
-            h = F.batch_norm(h, rm_, rv_, state[L["bn"] + ".weight"].to(h.dtype), state[L["bn"] + ".bias"].to(h.dtype), training,
-                             BN_MOMENTUM, BN_EPS)
-            if training:
-                rm.copy_(rm_)
-                rv.copy_(rv_)
-                buffers[L["bn"] + ".num_batches_tracked"] += 1
+            h = batchnorm_running_host(h, state, buffers, L["bn"], training)
         if L["act"]:
             h = F.leaky_relu(h, SLOPE)
     return h
@@ -370,44 +383,68 @@ def adaptive_mix(dnll, dg, sq_nll, sq_g, disc_weight, disc_factor):
     return dpred, dw
 
 
+
+
 # ---- the network on the tape -------------------------------------------------------------------------------------------------------
 class _Pass:
-    """One forward pass: per layer (spec, conv input, conv output, BatchNorm statistics), the logits, the mode."""
+    """One forward pass: per layer (spec, layer input, layer output, BatchNorm statistics, what the layer saved), the logits, the
+    mode.  A layer may hang per-pass extras on it (the Meta-Kernel's range image)."""
 
     def __init__(self, training):
         self.rec, self.logits, self.training = [], None, training
 
 
-class PatchDiscriminator(TapeTrainer):
+class PatchDiscriminator(FlatParameters):
+    """Owns the walk over `specs` -- layer, then BatchNorm + LeakyReLU / LeakyReLU / nothing, and the mirror image backwards --, the
+    losses, the optimizer step and the state.  What a layer is stands in `_layer_forward` / `_layer_backward` alone: here the 4x4
+    zero-padded conv, in metakernel.MetaKernelDiscriminator the Meta-Kernel layer."""
+    _state_name = "discriminator state"
+
     def __init__(self, config=None, state=None, seed=0, device="cuda", lr=4.5e-6, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  deterministic=False):
         """state: a dict with the reference's keys (init_state, or pick_discriminator_state of an sgm checkpoint); None:
         init_state(config, seed).  The optimizer's defaults are the reference's second Adam (base_learning_rate 4.5e-6, no decay).
         deterministic: every kernel of this object runs in the library's deterministic mode (rldm_train_deterministic), as on the
         other trainers: the same inputs give the same parameter bits."""
-        self.cfg = _cfg(config) if state is None or config is not None else config_from_state(state)
-        state = state if state is not None else init_state(self.cfg, seed)
-        self.specs = layer_specs(self.cfg)
-        shapes = param_shapes(self.cfg)
-        names = trainable_names(self.cfg)
-        # (no zero arena: none of these kernels splits K into a pre-zeroed output)
-        self._init_parameters(OrderedDict((n, shapes[n]) for n in names), names, state, device, deterministic=deterministic, arena_bytes=0)
-        self.hp = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=None)
+        cfg = _cfg(config) if state is None or config is not None else config_from_state(state)
+        state = state if state is not None else init_state(cfg, seed)
+        # tiled=False: the tiled packer stages 64 x 64 x taps weights in LDS and is sized for 9 taps
+        self._build(cfg, state, layer_specs(cfg), param_shapes(cfg), trainable_names(cfg), BUFFER_SUFFIXES, device,
+                    dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=None), deterministic, tiled=False)
+
+    def _build(self, cfg, state, specs, shapes, names, buffer_suffixes, device, hp, deterministic, **store):
+        """shapes: every key of the reference's state dict, in its order; names: the trainable ones; buffer_suffixes: the rest, loaded
+        into `buffers` (BatchNorm's get their fresh values when `state` has none); store: FlatParameters' packing options."""
+        self.cfg, self.specs, self.hp, self._keys = cfg, specs, hp, list(shapes)
+        self._init_parameters(OrderedDict((n, shapes[n]) for n in names), names, state, device, deterministic=deterministic, **store)
         self.buffers = OrderedDict()
         for k, shape in shapes.items():
-            if k.endswith(BUFFER_SUFFIXES):
+            if k.endswith(buffer_suffixes):
                 v = state.get(k)
                 if v is None:
+                    if not k.endswith(BUFFER_SUFFIXES):
+                        raise KeyError(f"the state dict has no buffer {k}")
                     v = torch.ones(shape) if k.endswith("running_var") else torch.zeros(shape)
                 v = torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v)
                 dt = torch.int64 if k.endswith("num_batches_tracked") else torch.float32
                 self.buffers[k] = v.detach().to(dt).reshape(shape).clone().to(self.device)
         self._pass = None
 
-    def repack(self, tiled=False):
-        """The bf16 operand copies with the element-wise packing kernel: the tiled one stages 64 x 64 x taps weights in LDS and is sized
-        for 9 taps."""
-        super().repack(tiled=False)
+    # ---- one layer --------------------------------------------------------------------------------------------
+    def _layer_forward(self, ps, L, x):
+        """-> (the layer's output, what its backward needs besides x)."""
+        n = L["name"]
+        return conv4(x, self.wf[n + ".weight"], L["cout"], L["stride"], self.p[n + ".bias"] if L["bias"] else None), None
+
+    def _layer_backward(self, ps, L, x, dy, saved, params, want_input):
+        """params: the layer's parameter gradients += theirs.  -> d / dx; None from the first layer unless want_input: the gradient
+        of the network's input is wanted."""
+        n = L["name"]
+        if params:
+            conv4_wgrad(dy, x, self.g[n + ".weight"], L["stride"], self.g[n + ".bias"] if L["bias"] else None)
+        if L is self.specs[0] and not want_input:
+            return None
+        return conv4_dgrad(dy, self.wt[n + ".weight"], x.shape, L["stride"])
 
     # ---- forward ----------------------------------------------------------------------------------------------
     def _input(self, x, layout):
@@ -431,9 +468,8 @@ class PatchDiscriminator(TapeTrainer):
             h = self._input(x, layout)
             ps = _Pass(bool(training))
             for L in self.specs:
-                n = L["name"]
                 xin = h
-                y = conv4(xin, self.wf[n + ".weight"], L["cout"], L["stride"], self.p[n + ".bias"] if L["bias"] else None)
+                y, saved = self._layer_forward(ps, L, xin)
                 save = None
                 if L["bn"]:
                     b = L["bn"]
@@ -443,7 +479,7 @@ class PatchDiscriminator(TapeTrainer):
                     h = lrelu(y)
                 else:
                     h = y
-                ps.rec.append((L, xin, y, save))
+                ps.rec.append((L, xin, y, save, saved))
             ps.logits = h
             self._pass = ps
             return h
@@ -459,19 +495,14 @@ class PatchDiscriminator(TapeTrainer):
         if tuple(dlogits.shape) != tuple(ps.logits.shape):
             raise ValueError(f"dlogits {tuple(dlogits.shape)} for logits {tuple(ps.logits.shape)}")
         d = dlogits.contiguous()
-        for L, xin, y, save in reversed(ps.rec):
-            n = L["name"]
+        for L, xin, y, save, saved in reversed(ps.rec):
             if L["bn"]:
                 b = L["bn"]
                 d = bn_lrelu_backward(y, d, save, self.p[b + ".weight"], self.p[b + ".bias"],
                                       self.g[b + ".weight"] if params else None, self.g[b + ".bias"] if params else None)
             elif L["act"]:
                 d = lrelu_backward(y, d)
-            if params:
-                conv4_wgrad(d, xin, self.g[n + ".weight"], L["stride"], self.g[n + ".bias"] if L["bias"] else None)
-            if L is self.specs[0] and not want_input:
-                return None
-            d = conv4_dgrad(d, self.wt[n + ".weight"], xin.shape, L["stride"])
+            d = self._layer_backward(ps, L, xin, d, saved, params, want_input)
         return d
 
     def generator_loss(self):
@@ -517,30 +548,15 @@ class PatchDiscriminator(TapeTrainer):
 
     # ---- state ------------------------------------------------------------------------------------------------
     def state_dict(self):
-        """Parameters and BatchNorm buffers under the reference's keys, in its order (host tensors)."""
+        """Parameters and buffers under the reference's keys, in its order (host tensors)."""
         p = super().state_dict()
-        return OrderedDict((k, p[k] if k in p else self.buffers[k].cpu().clone()) for k in param_shapes(self.cfg))
+        return OrderedDict((k, p[k] if k in p else self.buffers[k].cpu().clone()) for k in self._keys)
 
     def state_payload(self):
-        return {"params": self.params.cpu(), "exp_avg": self.exp_avg.cpu(), "exp_avg_sq": self.exp_avg_sq.cpu(),
-                "global_step": self.global_step, "names": list(self.names),
-                "buffers": OrderedDict((k, v.cpu()) for k, v in self.buffers.items())}
+        """Everything a resumed run needs: parameters, Adam moments, step counter, and the buffers (running statistics)."""
+        return dict(super().state_payload(), buffers=OrderedDict((k, v.cpu()) for k, v in self.buffers.items()))
 
     def load_payload(self, st):
-        if list(st["names"]) != list(self.names):
-            raise RuntimeError("discriminator state was saved for a different parameter layout")
-        self.params.copy_(st["params"])
-        self.exp_avg.copy_(st["exp_avg"])
-        self.exp_avg_sq.copy_(st["exp_avg_sq"])
-        self.global_step = int(st["global_step"])
+        super().load_payload(st)
         for k, v in st["buffers"].items():
             self.buffers[k].copy_(v)
-        self.grads.zero_()
-        self.repack()
-
-    def save_state(self, path):
-        """Everything a resumed run needs: parameters, running statistics, Adam moments, step counter."""
-        torch.save(self.state_payload(), path)
-
-    def load_state(self, path):
-        self.load_payload(torch.load(path, map_location="cpu", weights_only=True))

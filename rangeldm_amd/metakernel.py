@@ -18,9 +18,9 @@ input, afterwards what the previous layer returned:
     out[n] = sum_{c,i,j} coov.weight[n, 16 c + 4 i + j] m[c](wo, ho, i, j) x[c](w, h) + coov.bias[n]
 The four 4 x 4 tables are buffers of the state dict.  Every layer has its coov bias, also in front of a BatchNorm.
 
-`MetaKernelDiscriminator` drives the HIP kernels of rangeldm_amd/csrc/train_meta.hip (rldm_train_meta_*) and discriminator.py's
-BatchNorm / LeakyReLU / loss kernels from a host-side tape; `forward_host` restates the network in torch (autograd-capable) and is
-the tests' reference, `layer_host` and its three pieces restate one layer with its gradients by hand.  The device keeps pe
+`MetaKernelDiscriminator` drives the HIP kernels of rangeldm_amd/csrc/train_meta.hip (rldm_train_meta_*) as the layers of
+`PatchDiscriminator`'s walk (discriminator.py: its BatchNorm / LeakyReLU / loss kernels, optimizer step and state);
+`forward_host` restates the network in torch (autograd-capable) and is the tests' reference, `layer_host` and its three pieces restate one layer with its gradients by hand.  The device keeps pe
 (rows x 3), the source index of every row and the modulation m (rows x C, fp32: about 133 M elements = 0.53 GB per pass at batch 8,
 1024 x 64) for the backward; a row is one (output pixel, tap) pair.  Not built: variant 2 (NLayerDiscriminatorMetaKernel2),
 `log=True`, `disc_bev`, `vanilla_d_loss`, ActNorm.  No torch autograd and no torch compute ops on the device path; no CPU fallback."""
@@ -36,7 +36,8 @@ import torch.nn.functional as F
 from . import _lib
 from . import discriminator as D
 from . import train_ops as T
-from .discriminator import BN_EPS, BN_MOMENTUM, BUFFER_SUFFIXES, SLOPE, PatchDiscriminator, _p, _s, _workspace
+from .discriminator import (BUFFER_SUFFIXES, SLOPE, DiscriminatorConfig, PatchDiscriminator, _bf16, _p, _s, _workspace,  # noqa: F401
+                            batchnorm_running_host, output_size)
 
 TABLES = ("cos_azi", "sin_azi", "cos_inc", "sin_inc")           # the reference's registration order
 TABLE_SUFFIXES = tuple("." + t for t in TABLES)
@@ -44,10 +45,8 @@ R_OUTSIDE = 100.0
 
 
 @dataclass(frozen=True)
-class MetaKernelConfig:
-    in_channels: int = 2
-    ndf: int = 64
-    n_layers: int = 3
+class MetaKernelConfig(DiscriminatorConfig):
+    """in_channels, ndf, n_layers: the PatchGAN's (the same pyramid of widths and strides)."""
     azi: float = 0.00613592
     inc: float = 0.0074594
     range_mean: float = 20.0
@@ -68,18 +67,10 @@ def _cfg(config):
 def layer_specs(cfg=None):
     """The layers in forward order: dicts with name (`main.K`), cin, cout, stride, azi, inc, bn (`main.K+1` or None), act (bool)."""
     cfg = _cfg(cfg)
-    azi, inc = cfg.azi, cfg.inc
-    out = [dict(name="main.0", cin=cfg.in_channels, cout=cfg.ndf, stride=2, azi=azi, inc=inc, bn=None, act=True)]
-    azi, inc = azi * 2, inc * 2
-    mult = 1
-    for n in range(1, cfg.n_layers + 1):
-        prev, mult = mult, min(2 ** n, 8)
-        k = 2 + 3 * (n - 1)
-        out.append(dict(name=f"main.{k}", cin=cfg.ndf * prev, cout=cfg.ndf * mult, stride=2 if n < cfg.n_layers else 1, azi=azi, inc=inc,
-                        bn=f"main.{k + 1}", act=True))
-        if n < cfg.n_layers:
-            azi, inc = azi * 2, inc * 2
-    out.append(dict(name=f"main.{2 + 3 * cfg.n_layers}", cin=cfg.ndf * mult, cout=1, stride=1, azi=azi, inc=inc, bn=None, act=False))
+    out, azi, inc = [], cfg.azi, cfg.inc
+    for name, cin, cout, stride, bn, act in D.pyramid(cfg):
+        out.append(dict(name=name, cin=cin, cout=cout, stride=stride, azi=azi, inc=inc, bn=bn, act=act))
+        azi, inc = azi * stride, inc * stride           # the angular step between neighbours doubles behind every stride-2 layer
     return out
 
 
@@ -103,13 +94,6 @@ def param_shapes(cfg=None):
 
 def trainable_names(cfg=None):
     return [k for k in param_shapes(cfg) if not k.endswith(BUFFER_SUFFIXES + TABLE_SUFFIXES)]
-
-
-def output_size(cfg, W, H):
-    """(Wo, Ho) of the logits for a (W, H) input (W is counted on its W + 2 wrapped columns)."""
-    for L in layer_specs(cfg):
-        W, H = (W - 2) // L["stride"] + 1, (H - 2) // L["stride"] + 1
-    return W, H
 
 
 def make_tables(azi, inc):
@@ -164,10 +148,6 @@ def config_from_state(state, range_mean=20.0, range_std=40.0):
 
 
 # ---- host statements ---------------------------------------------------------------------------------------------------------------
-def _bf16(t):
-    return t.to(torch.bfloat16).to(t.dtype)
-
-
 class _Bf16Linear(torch.autograd.Function):
     """a (rows, K) @ w (N, K)^T whose three GEMMs see bf16-rounded operands, as the kernels': forward r(a) r(w)^T; input gradient
     r(dy) r(w); weight gradient r(dy)^T r(a)."""
@@ -250,14 +230,7 @@ def forward_host(state, x, training=True, bf16=False, buffers=None, detach_r=Fal
         h, r = _layer_torch(h, r, _tables(state, n, h.dtype), g("mlp_coord.0.weight"), g("mlp_coord.0.bias"), g("mlp_coord.2.weight"),
                             g("mlp_coord.2.bias"), g("coov.weight"), g("coov.bias"), L["stride"], bf16)
         if L["bn"]:
-            rm, rv = buffers[L["bn"] + ".running_mean"], buffers[L["bn"] + ".running_var"]
-            rm_, rv_ = rm.detach().to(h.dtype, copy=True), rv.detach().to(h.dtype, copy=True)
-            h = F.batch_norm(h, rm_, rv_, state[L["bn"] + ".weight"].to(h.dtype), state[L["bn"] + ".bias"].to(h.dtype), training,
-                             BN_MOMENTUM, BN_EPS)
-            if training:
-                rm.copy_(rm_)
-                rv.copy_(rv_)
-                buffers[L["bn"] + ".num_batches_tracked"] += 1
+            h = batchnorm_running_host(h, state, buffers, L["bn"], training)
         if L["act"]:
             h = F.leaky_relu(h, SLOPE)
     return h
@@ -422,95 +395,48 @@ def meta_backward(x, dy, tables, w1, b1, w2, coov, saved, stride, grads=None, wa
 
 
 # ---- the network on the tape -------------------------------------------------------------------------------------------------------
+LAYER_PARAMS = (".mlp_coord.0.weight", ".mlp_coord.0.bias", ".mlp_coord.2.weight", ".mlp_coord.2.bias", ".coov.weight", ".coov.bias")
+
+
 class MetaKernelDiscriminator(PatchDiscriminator):
-    """PatchDiscriminator's interface (forward, logits, generator_loss, input_gradient, backward, optimizer_step, discriminator_step,
-    state_dict, state_payload / load_payload, save_state / load_state) over the Meta-Kernel network; the loss kernels, the fused
-    BatchNorm + LeakyReLU, the optimizer step and the state handling are PatchDiscriminator's own."""
+    """PatchDiscriminator with the Meta-Kernel layer in place of the conv.  The walk over the layers with its BatchNorm / LeakyReLU
+    tail, the losses, the optimizer step and the state handling are PatchDiscriminator's, unchanged; this class states the layer
+    (`_layer_forward` / `_layer_backward`: rldm_train_meta_* with the range image threaded from layer to layer on the pass, the input's
+    range mapping in front of the first layer and its gradient behind it) and keeps the tables: buffers of the state, handed to
+    the kernels as one (4, 16) argument per layer.  The kernels read the fp32 masters, so no weight has a bf16 operand copy."""
 
     def __init__(self, config=None, state=None, seed=0, device="cuda", lr=4.5e-6, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  deterministic=False):
-        self.cfg = _cfg(config) if state is None or config is not None else config_from_state(state)
-        state = state if state is not None else init_state(self.cfg, seed)
-        self.specs = layer_specs(self.cfg)
-        shapes = param_shapes(self.cfg)
-        names = trainable_names(self.cfg)
-        self._init_parameters(OrderedDict((n, shapes[n]) for n in names), names, state, device, deterministic=deterministic, arena_bytes=0)
-        self.hp = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=None)
-        self.buffers = OrderedDict()
-        for k, shape in shapes.items():
-            if k.endswith(BUFFER_SUFFIXES + TABLE_SUFFIXES):
-                v = state.get(k)
-                if v is None:
-                    if k.endswith(TABLE_SUFFIXES):
-                        raise KeyError(f"the state dict has no table {k}")
-                    v = torch.ones(shape) if k.endswith("running_var") else torch.zeros(shape)
-                v = torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v)
-                dt = torch.int64 if k.endswith("num_batches_tracked") else torch.float32
-                self.buffers[k] = v.detach().to(dt).reshape(shape).clone().to(self.device)
-        # the kernels take a layer's four tables as one (4, 16) argument
-        self.tables = {L["name"]: torch.cat([self.buffers[f"{L['name']}.{t}"].reshape(1, 16) for t in TABLES]).contiguous()
-                       for L in self.specs}
-        self._pass = None
+        cfg = _cfg(config) if state is None or config is not None else config_from_state(state)
+        state = state if state is not None else init_state(cfg, seed)
+        self._build(cfg, state, layer_specs(cfg), param_shapes(cfg), trainable_names(cfg), BUFFER_SUFFIXES + TABLE_SUFFIXES, device,
+                    dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=None), deterministic, packed=())
+        self.tables = {L["name"]: self._table(L["name"]).contiguous() for L in self.specs}
 
-    def _layer_params(self, n):
-        return [self.p[n + k] for k in (".mlp_coord.0.weight", ".mlp_coord.0.bias", ".mlp_coord.2.weight", ".mlp_coord.2.bias",
-                                        ".coov.weight", ".coov.bias")]
+    def _table(self, n):
+        return torch.cat([self.buffers[f"{n}.{t}"].reshape(1, 16) for t in TABLES])
 
-    def forward(self, x, training=True, layout=None):
-        """As PatchDiscriminator.forward: -> the logits (B, Wo, Ho, 1) NHWC on the device."""
-        with self._mode():
-            h = self._input(x, layout)
-            r = input_range(h, self.cfg.range_mean, self.cfg.range_std)
-            ps = D._Pass(bool(training))
-            for L in self.specs:
-                n = L["name"]
-                xin = h
-                w1, b1, w2, b2, coov, bias = self._layer_params(n)
-                y, r, saved = meta_forward(xin, r, self.tables[n], w1, b1, w2, b2, coov, bias, L["stride"])
-                save = None
-                if L["bn"]:
-                    b = L["bn"]
-                    h, save = D.bn_lrelu_forward(y, self.p[b + ".weight"], self.p[b + ".bias"], self.buffers[b + ".running_mean"],
-                                                 self.buffers[b + ".running_var"], self.buffers[b + ".num_batches_tracked"], training)
-                elif L["act"]:
-                    h = D.lrelu(y)
-                else:
-                    h = y
-                ps.rec.append((L, xin, y, save, saved))
-            ps.logits = h
-            self._pass = ps
-            return h
+    def _layer_forward(self, ps, L, x):
+        n = L["name"]
+        if L is self.specs[0]:
+            ps.r = input_range(x, self.cfg.range_mean, self.cfg.range_std)
+        y, ps.r, saved = meta_forward(x, ps.r, self.tables[n], *[self.p[n + k] for k in LAYER_PARAMS], L["stride"])
+        return y, saved
 
-    def _backward(self, ps, dlogits, params, want_input):
-        if not ps.training:
-            raise RuntimeError("the backward pass needs a training-mode forward (batch statistics)")
-        if tuple(dlogits.shape) != tuple(ps.logits.shape):
-            raise ValueError(f"dlogits {tuple(dlogits.shape)} for logits {tuple(ps.logits.shape)}")
-        d, dr = dlogits.contiguous(), None
-        for L, xin, y, save, saved in reversed(ps.rec):
-            n = L["name"]
-            if L["bn"]:
-                b = L["bn"]
-                d = D.bn_lrelu_backward(y, d, save, self.p[b + ".weight"], self.p[b + ".bias"],
-                                        self.g[b + ".weight"] if params else None, self.g[b + ".bias"] if params else None)
-            elif L["act"]:
-                d = D.lrelu_backward(y, d)
-            w1, b1, w2, _, coov, _ = self._layer_params(n)
-            grads = [self.g[n + k] for k in (".mlp_coord.0.weight", ".mlp_coord.0.bias", ".mlp_coord.2.weight", ".mlp_coord.2.bias",
-                                             ".coov.weight", ".coov.bias")] if params else None
-            # (the range path ends at the input: without want_input no layer computes dr, and the first layer has no data gradient)
-            d, dr = meta_backward(xin, d, self.tables[n], w1, b1, w2, coov, saved, L["stride"], grads,
-                                  want_input=want_input or L is not self.specs[0], want_range=want_input, dr_next=dr)
-        if not want_input:
-            return None
-        return input_range_backward(dr, d, self.cfg.range_std)
+    def _layer_backward(self, ps, L, x, dy, saved, params, want_input):
+        """As PatchDiscriminator's; ps.dr carries the range image's gradient from the layer behind to the layer in front.  The range
+        path ends at the input: without want_input no layer computes dr."""
+        n = L["name"]
+        first, last = L is self.specs[0], L is self.specs[-1]
+        w1, b1, w2, _, coov, _ = [self.p[n + k] for k in LAYER_PARAMS]
+        dx, ps.dr = meta_backward(x, dy, self.tables[n], w1, b1, w2, coov, saved, L["stride"],
+                                  [self.g[n + k] for k in LAYER_PARAMS] if params else None, want_input=want_input or not first,
+                                  want_range=want_input, dr_next=None if last else ps.dr)
+        return input_range_backward(ps.dr, dx, self.cfg.range_std) if first and want_input else dx
 
     def load_payload(self, st):
         super().load_payload(st)
         for n, t in self.tables.items():
-            t.copy_(torch.cat([self.buffers[f"{n}.{k}"].reshape(1, 16) for k in TABLES]))
+            t.copy_(self._table(n))
 
-    def state_dict(self):
-        """Parameters, tables and BatchNorm buffers under the reference's keys, in its order (host tensors)."""
-        p = super(PatchDiscriminator, self).state_dict()
-        return OrderedDict((k, p[k] if k in p else self.buffers[k].cpu().clone()) for k in param_shapes(self.cfg))
+

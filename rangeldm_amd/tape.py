@@ -1,9 +1,14 @@
-"""The model-independent half of the HIP training steps: `TapeTrainer` owns the flat fp32 buffers (parameters, gradients, AdamW
-moments, optional EMA copy; state-dict views into them), the bf16 operand copies of every conv / linear weight, the host-side tape
-(`forward` of a subclass records one backward closure per op, `_run_tape` replays them in reverse) with its gradient slots, the queue
-of grouped weight gradients, the zero arena of the split-K convs and the clip + AdamW call.  `UNetTrainer` (training.py),
-`VAEDecoderTrainer` and `VAETrainer` (vae_training.py) add their networks, losses and schedules on top.  No torch autograd, no torch compute ops on
-the path; no CPU fallback."""
+"""The model-independent half of the HIP training steps, in two classes.
+
+`FlatParameters` is the parameter store: the flat fp32 buffers (parameters, gradients, AdamW moments, optional EMA copy; state-dict
+views into them), the bf16 operand copies of the conv / linear weights it is told to pack, the deterministic switch, the clip + AdamW
+call and the training state every owner of parameters saves and loads (`state_payload` / `load_payload`).  The discriminators
+(discriminator.py, metakernel.py) sit on it directly: they walk their layers themselves and record no tape.
+
+`TapeTrainer` adds the host-side tape (`forward` of a subclass records one backward closure per op, `_run_tape` replays them in
+reverse) with its gradient slots, the queue of grouped weight gradients, the zero arena of the split-K convs and the conv / GroupNorm /
+SiLU ops.  `UNetTrainer` (training.py), `VAEDecoderTrainer` and `VAETrainer` (vae_training.py) add their networks, losses and
+schedules on top.  No torch autograd, no torch compute ops on the path; no CPU fallback."""
 import contextlib
 from collections import OrderedDict
 
@@ -14,12 +19,16 @@ from . import _lib
 from . import train_ops as T
 
 
-class TapeTrainer:
+class FlatParameters:
+    _state_name = "training state"                      # (what load_payload calls a file it refuses)
+
     def _init_parameters(self, shapes, names, state_dict, device, fused=None, no_dx=(), use_ema=False, deterministic=False,
-                         arena_bytes=256 << 20):
+                         packed=None, tiled=True):
         """shapes: name -> shape; names: the order of the parameters inside the flat buffers; fused: plan_parameter_order's layer
         groups (consecutive parameters run as ONE layer); no_dx: weights whose layer never computes a data gradient (no transposed
-        operand copy)."""
+        operand copy).  packed: the weights that get bf16 operand copies (None: every `*.weight` of two or more dimensions outside a
+        fused group, and every fused group); tiled: the packer `repack()` uses when it is not told (True: the 64 x 64 tile
+        transpose)."""
         _lib.require_gpu()
         self.device = torch.device(device)
         self.shapes, self.names, self.fused = shapes, list(names), fused if fused is not None else OrderedDict()
@@ -42,13 +51,16 @@ class TapeTrainer:
             self.ema.copy_(self.params)
         self.p = {n: self._view(self.params, n) for n in self.names}
         self.g = {n: self._view(self.grads, n) for n in self.names}
-        # bf16 operand copies of every conv / linear weight: forward [N][taps][Cin], data gradient [Cin][taps][N].
+        # bf16 operand copies of the packed conv / linear weights: forward [N][taps][Cin], data gradient [Cin][taps][N].
         # layers: key -> (N, Cin, taps, offset of the fp32 weight in the flat buffer).  A fused group (all time_emb_proj
         # layers; to_q / to_k / to_v of an attention block) is ONE layer over its members' contiguous parameters.
         self.layers, self.wf, self.wt = OrderedDict(), {}, {}
         members = {m for grp in self.fused.values() for m in grp["weights"] + grp["biases"]}
+        if packed is None:
+            packed = [n for n in self.names if n.endswith(".weight") and len(self.shapes[n]) >= 2 and n not in members]
+        packed = set(packed)
         for n in self.names:
-            if n.endswith(".weight") and len(self.shapes[n]) >= 2 and n not in members:
+            if n in packed:
                 N, Cin = self.shapes[n][:2]
                 taps = self.shapes[n][2] * self.shapes[n][3] if len(self.shapes[n]) == 4 else 1      # (k x k: 9, 1; 16 in the discriminator)
                 self.layers[n] = (N, Cin, taps, self.offsets[n], n not in no_dx)
@@ -63,19 +75,10 @@ class TapeTrainer:
         for n, (N, Cin, taps, _, need_t) in self.layers.items():
             self.wf[n] = torch.empty((N, taps, (Cin + 15) // 16 * 16), dtype=torch.bfloat16, device=self.device)
             self.wt[n] = torch.empty((Cin, taps, (N + 15) // 16 * 16), dtype=torch.bfloat16, device=self.device) if need_t else None
+        self._tiled, self._pack_table = bool(tiled), None
         self.repack()
         self.global_step = 0
-        self._tape, self._grad, self._keep = [], {}, []
-        self._rows, self._row_parent = {}, {}
-        self._arena = T.ZeroArena(self.device, arena_bytes)
         self.last_grad_norm = None
-        # (round 6) the weight gradients of the step are queued and run as a few grouped launches (rldm_train_wgrad_group: nothing in
-        # backward waits for a weight gradient, and ~85 launches of them each sat at its launch floor); wgrad_group = False: launched
-        # where the tape reaches them, the cross-check.  _wg_keep: the queued launches' operands (dy, inputs, statistics), alive until
-        # the flush
-        self.wgrad_group = True
-        self._wg_on, self._wg_keep = False, []
-        self._cs = {}
         self._deterministic = bool(deterministic)
 
     @property
@@ -97,11 +100,15 @@ class TapeTrainer:
     def _view(self, flat, n):
         return flat[self.offsets[n]:self.offsets[n] + self.sizes[n]].view(self.shapes[n])
 
-    def repack(self, tiled=True):
-        """Refresh the bf16 operand copies of every conv / linear weight from the fp32 masters: one launch (tiled: a 64 x 64
-        tile transpose per workgroup; False: the element-wise kernel, kept as the cross-check)."""
+    def repack(self, tiled=None):
+        """Refresh the bf16 operand copies of the packed weights from the fp32 masters: one launch (tiled: a 64 x 64 tile
+        transpose per workgroup; False: the element-wise kernel, kept as the cross-check; None: the store's default), none when
+        no weight is packed."""
         import ctypes as C
-        if getattr(self, "_pack_table", None) is None:
+        if not self.wf:
+            return
+        tiled = self._tiled if tiled is None else tiled
+        if self._pack_table is None:
             tables = []
             for per_tile in (False, True):
                 descs = (_lib.PackDescC * len(self.wf))()
@@ -126,6 +133,60 @@ class TapeTrainer:
         flat = (self.ema if ema else self.params).cpu()
         return OrderedDict((n, flat[self.offsets[n]:self.offsets[n] + self.sizes[n]].view(self.shapes[n]).clone())
                            for n in self.names)
+
+    # ---- training state ---------------------------------------------------------------------------------------
+    def state_payload(self):
+        """What every owner of parameters saves: the fp32 masters, the Adam moments, the step counter and the parameter layout
+        (host tensors).  A subclass adds its own entries to the dict."""
+        return {"params": self.params.cpu(), "exp_avg": self.exp_avg.cpu(), "exp_avg_sq": self.exp_avg_sq.cpu(),
+                "global_step": self.global_step, "names": list(self.names)}
+
+    def load_payload(self, st):
+        """Restores state_payload's entries IN PLACE (views, operand copies and captured graphs keep pointing at the buffers), zeroes
+        the gradients and refreshes the bf16 operand copies."""
+        if list(st["names"]) != list(self.names):
+            raise RuntimeError(f"{self._state_name} was saved for a different parameter layout")
+        self.params.copy_(st["params"])
+        self.exp_avg.copy_(st["exp_avg"])
+        self.exp_avg_sq.copy_(st["exp_avg_sq"])
+        self.global_step = int(st["global_step"])
+        self.grads.zero_()
+        self.repack()
+
+    def save_state(self, path):
+        torch.save(self.state_payload(), path)
+
+    def load_state(self, path):
+        self.load_payload(torch.load(path, map_location="cpu", weights_only=True))     # tensors, lists, dicts, numbers: nothing to unpickle
+
+    # ---- optimizer --------------------------------------------------------------------------------------------
+    def _clip_adamw(self, lr, ema_decay=0.0):
+        """clip_grad_norm_ (hp["max_grad_norm"]; None / <= 0: off) folded into torch.optim.AdamW on the flat buffers (+ the EMA copy's
+        step), then the bf16 operand copies refreshed and the gradients zeroed.  `global_step` is the 1-based step being taken."""
+        hp = self.hp
+        sq = T.sqnorm(self.grads)
+        T.adamw(self.params, self.grads, self.exp_avg, self.exp_avg_sq, self.global_step, lr, hp["betas"], hp["eps"],
+                hp["weight_decay"], ema=self.ema, ema_decay=ema_decay, sqnorm_dev=sq, max_grad_norm=hp["max_grad_norm"] or 0.0)
+        self.last_grad_norm = sq
+        self.repack()
+        self.grads.zero_()
+
+
+class TapeTrainer(FlatParameters):
+    def _init_parameters(self, shapes, names, state_dict, device, fused=None, no_dx=(), use_ema=False, deterministic=False,
+                         arena_bytes=256 << 20):
+        """FlatParameters' arguments (every weight packed, the tiled packer) and arena_bytes: the size of the zero arena."""
+        super()._init_parameters(shapes, names, state_dict, device, fused=fused, no_dx=no_dx, use_ema=use_ema,
+                                 deterministic=deterministic)
+        self._tape, self._grad, self._keep = [], {}, []
+        self._rows, self._row_parent = {}, {}
+        self._arena = T.ZeroArena(self.device, arena_bytes)
+        # the weight gradients of the step are queued and run as a few grouped launches (rldm_train_wgrad_group: nothing in backward
+        # waits for a weight gradient, and ~85 launches of them each sat at its launch floor); wgrad_group = False: launched where the
+        # tape reaches them, the cross-check.  _wg_keep: the queued launches' operands (dy, inputs, statistics), alive until the flush
+        self.wgrad_group = True
+        self._wg_on, self._wg_keep = False, []
+        self._cs = {}
 
     # ---- tape -------------------------------------------------------------------------------------------------
     def _acc(self, t, g, owned):
@@ -286,15 +347,3 @@ class TapeTrainer:
             self._acc(x, T.silu_backward(x, dy), True)
         self._tape.append(bwd)
         return y
-
-    # ---- optimizer --------------------------------------------------------------------------------------------
-    def _clip_adamw(self, lr, ema_decay=0.0):
-        """clip_grad_norm_ (hp["max_grad_norm"]; None / <= 0: off) folded into torch.optim.AdamW on the flat buffers (+ the EMA copy's
-        step), then the bf16 operand copies refreshed and the gradients zeroed.  `global_step` is the 1-based step being taken."""
-        hp = self.hp
-        sq = T.sqnorm(self.grads)
-        T.adamw(self.params, self.grads, self.exp_avg, self.exp_avg_sq, self.global_step, lr, hp["betas"], hp["eps"],
-                hp["weight_decay"], ema=self.ema, ema_decay=ema_decay, sqnorm_dev=sq, max_grad_norm=hp["max_grad_norm"] or 0.0)
-        self.last_grad_norm = sq
-        self.repack()
-        self.grads.zero_()

@@ -1,7 +1,7 @@
 """UNet training step on MI355X: the counterpart of ldm/train_unconditional.py:466-558.
 
-`UNetTrainer` (on `TapeTrainer`, tape.py: the flat fp32 buffers -- parameters, gradients, AdamW moments, EMA copy; state-dict
-views into them -- and the tape helpers every trainer shares) drives the op-level HIP kernels of
+`UNetTrainer` (on `TapeTrainer`, tape.py: the tape helpers every tape trainer shares, over `FlatParameters`' flat fp32 buffers --
+parameters, gradients, AdamW moments, EMA copy; state-dict views into them -- and its training state) drives the op-level HIP kernels of
 rangeldm_amd/csrc/train.hip through a host-side tape: `forward` records one backward closure per op (conv / linear, GroupNorm(+SiLU), head_dim-8 attention, concat, nearest-x2, stride-2), `backward` replays
 them in reverse.  Data parallelism = one process per GPU; gradients are averaged with RCCL all-reduce over a few large
 buckets of the flat gradient buffer, each launched as soon as backward has finished the bucket's parameters
@@ -168,33 +168,24 @@ class UNetTrainer(TapeTrainer):
         if self.ema is not None:
             save_model_dir(os.path.join(output_dir, "unet_ema"), unet_config_to_diffusers(self.cfg), self.state_dict(ema=True))
 
-    def save_state(self, path):
+    def state_payload(self):
         """`accelerator.save_state(checkpoint-N)` counterpart (ldm/train_unconditional.py:560-584): everything a resumed run
         needs besides the weights -- AdamW moments, EMA copy, step counter (lr schedule, bias corrections, EMA warm-up)."""
         # inside an accumulation window the partially summed gradient buffer is part of the state (the next optimizer step divides by
         # the window length whatever the buffer holds)
-        torch.save({"params": self.params.cpu(), "ema": None if self.ema is None else self.ema.cpu(),
-                    "exp_avg": self.exp_avg.cpu(), "exp_avg_sq": self.exp_avg_sq.cpu(), "global_step": self.global_step,
-                    "micro": self._micro, "grads": self.grads.cpu() if self._micro else None,
-                    "names": list(self.names), "hp": {k: (v if isinstance(v, (int, float, str, bool, type(None))) else list(v))
-                                                      for k, v in self.hp.items()}}, path)
+        return dict(super().state_payload(), ema=None if self.ema is None else self.ema.cpu(), micro=self._micro,
+                    grads=self.grads.cpu() if self._micro else None,
+                    hp={k: (v if isinstance(v, (int, float, str, bool, type(None))) else list(v)) for k, v in self.hp.items()})
 
-    def load_state(self, path):
+    def load_payload(self, st):
         """`accelerator.load_state` (resume_from_checkpoint, ldm/train_unconditional.py:449-463): restores the buffers IN PLACE
         (captured step graphs keep pointing at them) and resynchronises the device-side step counter."""
-        st = torch.load(path, map_location="cpu", weights_only=True)       # tensors, lists, dicts, numbers: nothing to unpickle
-        if list(st["names"]) != list(self.names):
-            raise RuntimeError("training state was saved for a different parameter layout")
-        self.params.copy_(st["params"])
-        self.exp_avg.copy_(st["exp_avg"])
-        self.exp_avg_sq.copy_(st["exp_avg_sq"])
+        super().load_payload(st)
         if self.ema is not None:
             if st["ema"] is None:
                 raise RuntimeError("training state holds no EMA copy")
             self.ema.copy_(st["ema"])
-        self.global_step = int(st["global_step"])
         self._micro = int(st.get("micro", 0))
-        self.grads.zero_()
         if self._micro:
             if st.get("grads") is None:                  # (a state written before the gradient buffer was saved: restart the window)
                 self._micro = 0
@@ -202,7 +193,6 @@ class UNetTrainer(TapeTrainer):
                 self.grads.copy_(st["grads"])
         self._step_dev.fill_(self.global_step)
         self._step_dev_mirror = self.global_step
-        self.repack()
 
     # ---- tape -------------------------------------------------------------------------------------------------
     def _done(self, *names):

@@ -122,9 +122,10 @@ class _VAETape(TapeTrainer):
     """What the two VAE trainers share: the hyper-parameters, the resnet block, the decoder walk, the optimizer step and the training
     state."""
 
-    def _init_vae(self, config, state_dict, names, no_dx, device, lr, betas, eps, weight_decay, max_grad_norm, channel_weights,
-                  deterministic, discriminator=None, disc_start=0, disc_weight=0.5, disc_factor=1.0, bev=None, bev_rec_weight=0.0,
-                  disc_bev=False):
+    def _init_vae(self, config, state_dict, names, no_dx, *, device, lr, betas, eps, weight_decay, max_grad_norm, channel_weights,
+                  deterministic, discriminator, disc_start, disc_weight, disc_factor, bev, bev_rec_weight, disc_bev):
+        """names(cfg, shapes): the trained parameters in tape order; no_dx: TapeTrainer's; the rest: the options both public
+        constructors share, under their names there (the defaults stand in those signatures alone)."""
         self._init_bev(bev, bev_rec_weight, disc_bev, deterministic, discriminator)
         self.cfg = config if isinstance(config, VAEConfig) else VAEConfig(**config)
         if len(channel_weights) != self.cfg.out_channels:
@@ -268,30 +269,38 @@ class _VAETape(TapeTrainer):
         self.optimizer_step()
         self.last_disc = disc.discriminator_step(real_nchw, pred, factor=self.disc_factor, step=self.global_step)
 
+    def _reconstruction_step(self, pred, target):
+        """What a train_step does behind its forward: the L1 against target (sets last_abs_sums), the BEV volumes and term when they
+        are on, then the adversarial phase's step or backward + optimizer step.  -> the reconstruction loss (L1 + the BEV term)."""
+        rec, dpred, self.last_abs_sums = T.l1(pred, target, self.channel_weights)
+        volumes = None
+        if self._bev_active():
+            volumes = self._bev_volumes(pred, target)
+            if self.bev_rec_weight > 0:
+                dpred, term = self._bev_rec(dpred, volumes)
+                rec = rec + term
+        if self.adversarial():
+            self._adversarial_step(pred, dpred, target, volumes)
+        else:
+            self.backward(dpred)
+            self.optimizer_step()
+        return rec
+
     # ---- weights ----------------------------------------------------------------------------------------------
     def full_state_dict(self):
         """The whole VAE: the tensors this trainer does not train as they were given, the fp32 masters of those it does."""
         return merged_state_dict(self._frozen, self.state_dict())
 
-    def save_state(self, path):
+    def state_payload(self):
         """Everything a resumed run needs: parameters, Adam moments, step counter -- and, with a discriminator, its state under the
         key `discriminator` (a file written without one has no such key)."""
-        st = {"params": self.params.cpu(), "exp_avg": self.exp_avg.cpu(), "exp_avg_sq": self.exp_avg_sq.cpu(),
-              "global_step": self.global_step, "names": list(self.names)}
+        st = super().state_payload()
         if self.discriminator is not None:
             st["discriminator"] = self.discriminator.state_payload()
-        torch.save(st, path)
+        return st
 
-    def load_state(self, path):
-        st = torch.load(path, map_location="cpu", weights_only=True)
-        if list(st["names"]) != list(self.names):
-            raise RuntimeError("training state was saved for a different parameter layout")
-        self.params.copy_(st["params"])
-        self.exp_avg.copy_(st["exp_avg"])
-        self.exp_avg_sq.copy_(st["exp_avg_sq"])
-        self.global_step = int(st["global_step"])
-        self.grads.zero_()
-        self.repack()
+    def load_payload(self, st):
+        super().load_payload(st)
         if self.discriminator is not None and "discriminator" in st:
             self.discriminator.load_payload(st["discriminator"])
 
@@ -309,9 +318,10 @@ class VAEDecoderTrainer(_VAETape):
         runs the adversarial phase (module docstring) with disc_weight / disc_factor, the reference's names.  None, or before
         disc_start: the step is exactly what it is without one, and the discriminator is not run.
         bev, bev_rec_weight, disc_bev: the BEV terms (module docstring); with the defaults no code of theirs runs."""
-        self._init_vae(config, state_dict, decoder_param_names, ("decoder.conv_in.weight",), device, lr, betas, eps, weight_decay,
-                       max_grad_norm, channel_weights, deterministic, discriminator, disc_start, disc_weight, disc_factor, bev,
-                       bev_rec_weight, disc_bev)
+        self._init_vae(config, state_dict, decoder_param_names, ("decoder.conv_in.weight",), device=device, lr=lr, betas=betas, eps=eps,
+                       weight_decay=weight_decay, max_grad_norm=max_grad_norm, channel_weights=channel_weights,
+                       deterministic=deterministic, discriminator=discriminator, disc_start=disc_start, disc_weight=disc_weight,
+                       disc_factor=disc_factor, bev=bev, bev_rec_weight=bev_rec_weight, disc_bev=disc_bev)
 
     def forward(self, z_nchw):
         """z (B, z_channels, W / f, H / f) fp32 on the device, as the encoder emits it (not multiplied by scaling_factor)
@@ -329,19 +339,7 @@ class VAEDecoderTrainer(_VAETape):
         step is `_adversarial_step`'s and `last_g_loss`, `last_d_weight`, `last_disc` report it; the returned loss stays the L1."""
         with self._mode():
             pred = self.forward(z_nchw)
-            target = target_nchw.to(self.device).float().contiguous()
-            loss, dpred, self.last_abs_sums = T.l1(pred, target, self.channel_weights)
-            volumes = None
-            if self._bev_active():
-                volumes = self._bev_volumes(pred, target)
-                if self.bev_rec_weight > 0:
-                    dpred, term = self._bev_rec(dpred, volumes)
-                    loss = loss + term
-            if self.adversarial():
-                self._adversarial_step(pred, dpred, target, volumes)
-            else:
-                self.backward(dpred)
-                self.optimizer_step()
+            loss = self._reconstruction_step(pred, target_nchw.to(self.device).float().contiguous())
         return float(loss) if as_float else loss
 
     def load_into(self, vae):
@@ -368,8 +366,10 @@ class VAETrainer(_VAETape):
         must be estimated again (module docstring).  deterministic, discriminator, disc_start, disc_weight, disc_factor, bev,
         bev_rec_weight, disc_bev: as VAEDecoderTrainer."""
         self._init_vae(config, state_dict, lambda cfg, shapes: encoder_param_names(cfg, shapes) + decoder_param_names(cfg, shapes),
-                       ("encoder.conv_in.weight",), device, lr, betas, eps, weight_decay, max_grad_norm, channel_weights, deterministic,
-                       discriminator, disc_start, disc_weight, disc_factor, bev, bev_rec_weight, disc_bev)
+                       ("encoder.conv_in.weight",), device=device, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                       max_grad_norm=max_grad_norm, channel_weights=channel_weights, deterministic=deterministic,
+                       discriminator=discriminator, disc_start=disc_start, disc_weight=disc_weight, disc_factor=disc_factor, bev=bev,
+                       bev_rec_weight=bev_rec_weight, disc_bev=disc_bev)
         self.kl_weight = float(kl_weight)
         self.last_kl = None
         self._moments = self._z = None
@@ -430,18 +430,7 @@ class VAETrainer(_VAETape):
             noise = torch.randn((images.shape[0], self.cfg.z_channels, images.shape[2] // f, images.shape[3] // f), generator=generator)
         with self._mode():
             pred = self.forward(images, noise if sample_posterior else None)
-            rec, dpred, self.last_abs_sums = T.l1(pred, images, self.channel_weights)
-            volumes = None
-            if self._bev_active():
-                volumes = self._bev_volumes(pred, images)
-                if self.bev_rec_weight > 0:
-                    dpred, term = self._bev_rec(dpred, volumes)
-                    rec = rec + term
-            if self.adversarial():
-                self._adversarial_step(pred, dpred, images, volumes)
-            else:
-                self.backward(dpred)
-                self.optimizer_step()
+            rec = self._reconstruction_step(pred, images)
         loss = rec + self.kl_weight * self.last_kl          # (two device scalars, for the log: no kernel reads the sum)
         return float(loss) if as_float else loss
 

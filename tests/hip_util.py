@@ -646,7 +646,7 @@ def gn_shift_scale_tokens(o, seed):
 
 
 # ---- placement: operands as the trainers place them ---------------------------------------------------------------------------------
-# TapeTrainer packs parameters and gradients end to end in flat buffers and ZeroArena packs split-K outputs at a 16-byte granule, so the
+# FlatParameters (tape.py) packs parameters and gradients end to end in flat buffers and TapeTrainer's ZeroArena packs split-K outputs at a 16-byte granule, so the
 # other side of a view's last element is somebody else's live data.  `place` builds such a neighbourhood with known contents:
 # [guard | t0 | guard | t1 | ... | guard] in ONE allocation, every view at the same offset modulo 16 bytes as the first (`lead`), every
 # guard >= GUARD elements of one bit pattern.  Inputs sit between quiet NaNs (a stray load that is consumed -- also as x * 0 -- poisons the
@@ -759,7 +759,7 @@ def assert_placement(buf, what=""):
 
 
 def flat_buffer_residues(names, shapes):
-    """offset % 4 (in floats: the position inside a 16-byte granule) of every view TapeTrainer._init_parameters makes for parameters
+    """offset % 4 (in floats: the position inside a 16-byte granule) of every view FlatParameters._init_parameters makes for parameters
     packed end to end in the order `names`."""
     out, pos = set(), 0
     for n in names:

@@ -1,69 +1,9 @@
-"""What tests/test_metakernel_host.py and tests/test_metakernel_gpu.py share: the golden file of the reference's Meta-Kernel
-discriminator (tools/make_metakernel_golden.py), the same sequence -- forward(real), forward(fake), hinge loss, generator term -- on
-rangeldm_amd.metakernel.forward_host, computed once per (ndf, size, bf16) and left unchanged, and the integer-valued operands of
-the exact layer tests."""
-import os
-
+"""The integer-valued operands of the Meta-Kernel's exact layer tests (tests/test_metakernel_gpu.py).  The golden file and the
+sequences on it are tests/disc_util.py's (`META`)."""
 import numpy as np
 import torch
 
-from rangeldm_amd import discriminator as D
 from rangeldm_amd import metakernel as MK
-from tests.disc_util import rel, sampled  # noqa: F401
-
-_GOLDEN = None
-CASES = [(16, 32, 24), (64, 32, 24), (16, 64, 32), (64, 64, 32)]
-
-
-def golden():
-    global _GOLDEN
-    if _GOLDEN is None:
-        with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "metakernel.npz")) as z:
-            _GOLDEN = {k: z[k] for k in z.files}
-    return _GOLDEN
-
-
-def golden_case(ndf, W, H):
-    """The arrays of one case without their prefix, plus the two inputs as `real` / `fake`."""
-    g, pre = golden(), f"n{ndf}_{W}x{H}_"
-    out = {k[len(pre):]: v for k, v in g.items() if k.startswith(pre)}
-    out["real"], out["fake"] = g[f"x{W}x{H}_real"], g[f"x{W}x{H}_fake"]
-    return out
-
-
-def init(ndf):
-    return MK.init_state(MK.MetaKernelConfig(2, ndf, 3), int(golden()["seed"]))
-
-
-_HOST = {}
-
-
-def host_case(ndf, W, H, bf16=False, detach_r=False):
-    """forward_host's version of a golden case: logits, losses, buffers after the two passes, and the FULL gradients of d and g as
-    `d_full.<key>` / `g_full.<key>` (torch tensors; keys as the golden's, `real` / `fake` for the inputs)."""
-    key = (ndf, W, H, bf16, detach_r)
-    if key not in _HOST:
-        gc = golden_case(ndf, W, H)
-        state = init(ndf)
-        names = MK.trainable_names(MK.config_from_state(state))
-        for n in names:
-            state[n].requires_grad_()
-        buffers = {k: v.clone() for k, v in state.items() if k.endswith(D.BUFFER_SUFFIXES)}
-        real, fake = torch.from_numpy(gc["real"]).clone().requires_grad_(), torch.from_numpy(gc["fake"]).clone().requires_grad_()
-        lr = MK.forward_host(state, real, True, bf16, buffers, detach_r=detach_r)
-        lf = MK.forward_host(state, fake, True, bf16, buffers, detach_r=detach_r)
-        d, g = D.hinge_d_loss_host(lr, lf), -torch.mean(lf)
-        out = {"logits_real": lr.detach(), "logits_fake": lf.detach(), "d_loss": float(d.detach()), "g_loss": float(g.detach())}
-        wrt = [state[n] for n in names] + [real, fake]
-        for tag, loss in (("d", d), ("g", g)):
-            grads = torch.autograd.grad(loss, wrt, retain_graph=True, allow_unused=True)
-            for n, gr in zip(names + ["real", "fake"], grads):
-                if gr is not None:
-                    out[f"{tag}_full.{n}"] = gr.detach()
-        out.update({"buf." + k: v for k, v in buffers.items()})
-        _HOST[key] = out
-    return _HOST[key]
-
 
 # ---- integer-valued operands of one layer ------------------------------------------------------------------------------------------
 # Everything the kernels round to bf16 is an integer of at most 8 bits, and every sum is exact in fp32 in any order:

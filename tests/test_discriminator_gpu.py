@@ -25,35 +25,13 @@ import torch
 import torch.nn.functional as F
 
 from rangeldm_amd import discriminator as D
-from tests import disc_util as U
+from tests.disc_util import PATCH as U
+from tests.disc_util import mode, nchw, nhwc
+from tests.disc_util import param_errors as _param_errors
 from tests.hip_util import amax, assert_bitexact, assert_exact_bound, int_grid
 
 pytestmark = pytest.mark.gpu
 UNIT = 2.0 ** -5
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous().cuda()
-
-
-def nchw(t):
-    return t.permute(0, 3, 1, 2).contiguous().cpu()
-
-
-class mode:
-    """The library's deterministic switch for the duration of a block."""
-
-    def __init__(self, det):
-        self.det = det
-
-    def __enter__(self):
-        from rangeldm_amd import train_ops as T
-        self.prev = T.deterministic_enabled()
-        T.deterministic(self.det)
-
-    def __exit__(self, *exc):
-        from rangeldm_amd import train_ops as T
-        T.deterministic(self.prev)
 
 
 # ---- the 4x4 convs, exact --------------------------------------------------------------------------------------------------------------
@@ -324,62 +302,14 @@ def test_adaptive_mix():
 
 
 # ---- the network against the golden ------------------------------------------------------------------------------------------------------
-def _param_errors(got, ref, names):
-    """(worst per-parameter relative L2 with the floor of tests/test_training.py, its name, relative L2 over the flat buffer)."""
-    flat_ref = torch.cat([ref[n].reshape(-1).double() for n in names])
-    flat_got = torch.cat([got[n].reshape(-1).double().cpu() for n in names])
-    rms = float(flat_ref.norm() / flat_ref.numel() ** 0.5)
-
-    def err(n):
-        d = float((got[n].double().cpu() - ref[n].double()).norm())
-        return d / (float(ref[n].double().norm()) + 2e-2 * rms * ref[n].numel() ** 0.5)
-    worst = max((err(n), n) for n in names)
-    return worst[0], worst[1], float((flat_got - flat_ref).norm() / flat_ref.norm())
+def _dx_figures(tag, got, ref):
+    """The input gradients as whole tensors."""
+    return {tag + "_dx": max(U.rel(got[k], ref[k]) for k in ("real", "fake") if k in ref)}
 
 
 def network_figures(ndf, W, H, det=False):
     """One run of the golden's sequence on the device -> the figures the gates are about (and the same for forward_host(bf16=True))."""
-    gc, hc, he = U.golden_case(ndf, W, H), U.host_case(ndf, W, H), U.host_case(ndf, W, H, bf16=True)
-    disc = D.PatchDiscriminator(state=U.init(ndf), deterministic=det)
-    names = disc.names
-    real, fake = torch.from_numpy(gc["real"]).cuda(), torch.from_numpy(gc["fake"]).cuda()
-    with mode(det):
-        lr_ = disc.forward(real)
-        pr, logits_real = disc._pass, disc.logits().cpu()
-        lf = disc.forward(fake)
-        pf, logits_fake = disc._pass, disc.logits().cpu()
-        out, dreal, dfake = D.hinge(lr_, lf, 1.0)
-        disc._backward(pr, dreal, True, False)
-        disc._backward(pf, dfake, True, False)
-        d_grads = {n: disc.g[n].cpu().clone() for n in names}
-        d_grads["real"], d_grads["fake"] = nchw(disc._backward(pr, dreal, False, True)), nchw(disc._backward(pf, dfake, False, True))
-        assert torch.equal(torch.cat([d_grads[n].reshape(-1) for n in names]), disc.grads.cpu())      # the input gradient touched no parameter
-        disc.grads.zero_()
-        g, dlog = disc.generator_loss()
-        disc.backward(dlog)
-        g_grads = {n: disc.g[n].cpu().clone() for n in names}
-        g_grads["fake"] = nchw(disc.input_gradient(dlog))
-    sd = disc.state_dict()
-    if ndf == 64:
-        assert list(sd) == [str(k) for k in U.golden()["keys"]]
-    fig, floor = {}, {}
-    for dst, src in ((fig, dict(logits_real=logits_real, logits_fake=logits_fake, d_loss=float(out[0]), g_loss=float(g), d=d_grads, g=g_grads,
-                                buf={k: sd[k] for k in sd if k.endswith(D.BUFFER_SUFFIXES)})),
-                     (floor, dict(logits_real=he["logits_real"], logits_fake=he["logits_fake"], d_loss=he["d_loss"], g_loss=he["g_loss"],
-                                  d={k[7:]: v for k, v in he.items() if k.startswith("d_full.")},
-                                  g={k[7:]: v for k, v in he.items() if k.startswith("g_full.")},
-                                  buf={k[4:]: v for k, v in he.items() if k.startswith("buf.")}))):
-        dst["logits"] = max(U.rel(src["logits_real"], gc["logits_real"]), U.rel(src["logits_fake"], gc["logits_fake"]))
-        dst["d_loss"] = abs(src["d_loss"] - float(gc["d_loss"])) / abs(float(gc["d_loss"]))
-        dst["g_loss"] = abs(src["g_loss"] - float(gc["g_loss"])) / abs(float(gc["g_loss"]))
-        for tag in ("d", "g"):
-            ref = {k[7:]: v for k, v in hc.items() if k.startswith(tag + "_full.")}          # (== the golden: test_discriminator_host)
-            w, n, a = _param_errors(src[tag], ref, names)
-            dst[tag + "_worst"], dst[tag + "_worst_name"], dst[tag + "_all"] = w, n, a
-            dst[tag + "_dx"] = max(U.rel(src[tag][k], ref[k]) for k in ("real", "fake") if k in ref)
-        dst["running"] = max(U.rel(src["buf"][k], gc["buf." + k]) for k in src["buf"] if not k.endswith("num_batches_tracked"))
-        assert all(int(src["buf"][k]) == 2 for k in src["buf"] if k.endswith("num_batches_tracked"))
-    return fig, floor
+    return U.network_figures(ndf, W, H, _dx_figures, det)
 
 
 GATE_KEYS = ("logits", "d_loss", "g_loss", "d_worst", "d_all", "d_dx", "g_worst", "g_all", "g_dx", "running")
@@ -418,46 +348,11 @@ def test_network_matches_the_golden(ndf, W, H):
 
 
 def test_discriminator_step_is_bit_reproducible_in_deterministic_mode():
-    gc = U.golden_case(16, 64, 32)
-    real, fake = torch.from_numpy(gc["real"]).cuda(), torch.from_numpy(gc["fake"]).cuda()
-    runs = []
-    for _ in range(2):
-        disc = D.PatchDiscriminator(state=U.init(16), lr=1e-3, deterministic=True)
-        outs = [tuple(float(v) for v in disc.discriminator_step(real, nhwc(fake.cpu()), factor=1.0)) for _ in range(2)]
-        runs.append((outs, disc.params.cpu().clone(), disc.exp_avg_sq.cpu().clone(), {k: v.cpu().clone() for k, v in disc.buffers.items()}))
-        assert disc.global_step == 2 and int(disc.buffers["main.3.num_batches_tracked"]) == 4
-        assert float(disc.grads.abs().max()) == 0.0
-    assert runs[0][0] == runs[1][0]
-    assert torch.equal(runs[0][1], runs[1][1]) and torch.equal(runs[0][2], runs[1][2])
-    assert all(torch.equal(runs[0][3][k], runs[1][3][k]) for k in runs[0][3])
-    init = torch.cat([U.init(16)[n].reshape(-1) for n in disc.names])
-    assert not torch.equal(runs[0][1], init)
-    # NHWC and NCHW inputs are the same input
-    a, b = D.PatchDiscriminator(state=U.init(16), deterministic=True), D.PatchDiscriminator(state=U.init(16), deterministic=True)
-    assert torch.equal(a.forward(real), b.forward(nhwc(real.cpu()), layout="nhwc"))
-    assert a.logits().shape == (2, 1, 6, 2)
-    ev = a.forward(real, training=False)
-    assert int(a.buffers["main.3.num_batches_tracked"]) == 1 and torch.isfinite(ev).all()
-    with pytest.raises(RuntimeError, match="training-mode forward"):
-        a.input_gradient(torch.zeros_like(ev))
+    U.check_step_is_bit_reproducible()
 
 
 def test_discriminator_state_round_trip(tmp_path):
-    gc = U.golden_case(16, 32, 24)
-    real, fake = torch.from_numpy(gc["real"]).cuda(), torch.from_numpy(gc["fake"]).cuda()
-    a = D.PatchDiscriminator(state=U.init(16), lr=1e-3, deterministic=True)
-    a.discriminator_step(real, fake)
-    a.save_state(str(tmp_path / "d.pt"))
-    a.discriminator_step(real, fake)
-    b = D.PatchDiscriminator(D.DiscriminatorConfig(2, 16, 3), seed=99, lr=1e-3, deterministic=True)
-    b.load_state(str(tmp_path / "d.pt"))
-    assert b.global_step == 1
-    b.discriminator_step(real, fake)
-    assert torch.equal(a.params, b.params) and torch.equal(a.exp_avg, b.exp_avg) and torch.equal(a.exp_avg_sq, b.exp_avg_sq)
-    sa, sb = a.state_dict(), b.state_dict()
-    assert list(sa) == list(D.param_shapes(a.cfg)) and all(torch.equal(sa[k], sb[k]) for k in sa)
-    c = D.PatchDiscriminator(state=sa)                                # a state dict with the reference's keys loads, buffers included
-    assert torch.equal(c.buffers["main.9.running_var"].cpu(), sa["main.9.running_var"]) and int(c.buffers["main.6.num_batches_tracked"]) == 4
+    U.check_state_round_trip(tmp_path)
 
 
 # ---- the adversarial phase of the VAE trainers ------------------------------------------------------------------------------------------
@@ -625,7 +520,9 @@ def test_saved_state_continues_bit_identically_across_the_phase_boundary(tmp_pat
     assert int(a.discriminator.buffers["main.3.num_batches_tracked"]) == 6
     b = make(3)
     b.load_state(path)
-    assert b.global_step == 1 and "discriminator" in torch.load(path, map_location="cpu", weights_only=True)
+    VAE_KEYS = {"params", "exp_avg", "exp_avg_sq", "global_step", "names"}
+    st = torch.load(path, map_location="cpu", weights_only=True)
+    assert b.global_step == 1 and set(st) == VAE_KEYS | {"discriminator"} and set(st["discriminator"]) == U.STATE_KEYS
     for x, n in batches[1:]:
         b.train_step(x.cuda(), noise=n.cuda())
     for x, y in zip(_vae_bits(a) + _vae_bits(a.discriminator), _vae_bits(b) + _vae_bits(b.discriminator)):
@@ -636,7 +533,7 @@ def test_saved_state_continues_bit_identically_across_the_phase_boundary(tmp_pat
     plain = VAETrainer(cfg, sd, lr=1e-3, deterministic=True)
     plain.train_step(batches[0][0].cuda(), noise=batches[0][1].cuda())
     plain.save_state(path)
-    assert "discriminator" not in torch.load(path, map_location="cpu", weights_only=True)
+    assert set(torch.load(path, map_location="cpu", weights_only=True)) == VAE_KEYS
     c = make(5)
     before = c.discriminator.params.clone()
     c.load_state(path)

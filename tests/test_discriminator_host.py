@@ -12,7 +12,7 @@ import torch.nn.functional as F
 
 from rangeldm_amd import discriminator as D
 from rangeldm_amd.params import sgm_to_diffusers_vae_key
-from tests import disc_util as U
+from tests.disc_util import PATCH as U
 
 
 def test_keys_are_the_reference_modules():

@@ -14,9 +14,12 @@ import torch
 
 from rangeldm_amd import discriminator as D
 from rangeldm_amd import metakernel as MK
-from tests import meta_util as U
+from tests.disc_util import META as U
+from tests.disc_util import mode
+from tests.disc_util import param_errors as _param_errors
 from tests.hip_util import assert_bitexact
-from tests.test_discriminator_gpu import _param_errors, _vae_batch, _vae_bits, mode, nchw, nhwc
+from tests.meta_util import exact_layer_case
+from tests.test_discriminator_gpu import _vae_batch, _vae_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -50,7 +53,7 @@ def _run_layer(c, stride, params=True, want_input=True):
 @pytest.mark.parametrize("case", LAYER_CASES, ids=lambda c: "x".join(map(str, c)))
 def test_layer_exact(case, det):
     B, W, H, Cc, N, stride = case
-    c = U.exact_layer_case(*case)
+    c = exact_layer_case(*case)
     ref = c["ref"]
     what = f"{case} {'deterministic' if det else 'default'}"
     f = lambda a: torch.from_numpy(np.asarray(a)).float()        # noqa: E731
@@ -79,7 +82,7 @@ def test_w_wraps(stride):
     """An input that is non-zero in column W - 1 alone changes output column 0 (tap j = 0 of column 0 reads column -1 = W - 1): the
     opposite of test_conv4_does_not_wrap_w.  And the gradient of output column 0 reaches input column W - 1."""
     case = (1, 8, 6, 16, 16, stride)
-    c = dict(U.exact_layer_case(*case))
+    c = dict(exact_layer_case(*case))
     x = torch.zeros_like(c["x"])
     x[:, 7] = 1.0
     c["x"], c["bias"] = x, torch.zeros_like(c["bias"])
@@ -101,7 +104,7 @@ def test_w_wraps(stride):
 def test_border_rows_and_centre_tap():
     """Outside [0, H): x = 0 (src = -1) and r = 100; r_c is tap (2, 2) of the window."""
     B, W, H, Cc, N, stride = case = (2, 8, 6, 16, 16, 2)
-    c = U.exact_layer_case(*case)
+    c = exact_layer_case(*case)
     _, rn, (pe, src, _), _, _, _ = _run_layer(c, stride, params=False)
     pe, src, rn = pe.cpu().reshape(B, 4, 3, 4, 4, 3), src.cpu().reshape(B, 4, 3, 4, 4), rn.cpu()
     r, tab = c["r"], c["tables"].reshape(4, 4, 4)
@@ -134,51 +137,15 @@ def test_shapes_without_an_instance_are_refused():
 GATE_KEYS = ("logits", "d_loss", "g_loss", "d_worst", "d_all", "d_dx0", "d_dx1", "g_worst", "g_all", "g_dx0", "g_dx1", "running")
 
 
+def _dx_figures(tag, got, ref):
+    """The input gradients per channel: channel 0 carries the range path's gradient as well."""
+    return {f"{tag}_dx{ch}": max(U.rel(got[k][:, ch], ref[k][:, ch]) for k in ("real", "fake") if k in ref) for ch in (0, 1)}
+
+
 def network_figures(ndf, W, H, det=False):
     """One run of the golden's sequence on the device -> (the device's figures, forward_host(bf16=True)'s): each figure is a distance
     from the reference's recording (through forward_host in fp32, which tests/test_metakernel_host.py ties to the golden arrays)."""
-    gc, hc, he = U.golden_case(ndf, W, H), U.host_case(ndf, W, H), U.host_case(ndf, W, H, bf16=True)
-    disc = MK.MetaKernelDiscriminator(state=U.init(ndf), deterministic=det)
-    names = disc.names
-    real, fake = torch.from_numpy(gc["real"]).cuda(), torch.from_numpy(gc["fake"]).cuda()
-    with mode(det):
-        lr_ = disc.forward(real)
-        pr, logits_real = disc._pass, disc.logits().cpu()
-        lf = disc.forward(fake)
-        pf, logits_fake = disc._pass, disc.logits().cpu()
-        out, dreal, dfake = D.hinge(lr_, lf, 1.0)
-        disc._backward(pr, dreal, True, False)
-        disc._backward(pf, dfake, True, False)
-        d_grads = {n: disc.g[n].cpu().clone() for n in names}
-        d_grads["real"], d_grads["fake"] = nchw(disc._backward(pr, dreal, False, True)), nchw(disc._backward(pf, dfake, False, True))
-        assert torch.equal(torch.cat([d_grads[n].reshape(-1) for n in names]), disc.grads.cpu())      # the input gradient touched no parameter
-        disc.grads.zero_()
-        g, dlog = disc.generator_loss()
-        disc.backward(dlog)
-        g_grads = {n: disc.g[n].cpu().clone() for n in names}
-        g_grads["fake"] = nchw(disc.input_gradient(dlog))
-    sd = disc.state_dict()
-    if ndf == 64:
-        assert list(sd) == [str(k) for k in U.golden()["keys"]]
-    fig, floor = {}, {}
-    for dst, src in ((fig, dict(logits_real=logits_real, logits_fake=logits_fake, d_loss=float(out[0]), g_loss=float(g), d=d_grads, g=g_grads,
-                                buf={k: sd[k] for k in sd if k.endswith(D.BUFFER_SUFFIXES)})),
-                     (floor, dict(logits_real=he["logits_real"], logits_fake=he["logits_fake"], d_loss=he["d_loss"], g_loss=he["g_loss"],
-                                  d={k[7:]: v for k, v in he.items() if k.startswith("d_full.")},
-                                  g={k[7:]: v for k, v in he.items() if k.startswith("g_full.")},
-                                  buf={k[4:]: v for k, v in he.items() if k.startswith("buf.")}))):
-        dst["logits"] = max(U.rel(src["logits_real"], gc["logits_real"]), U.rel(src["logits_fake"], gc["logits_fake"]))
-        dst["d_loss"] = abs(src["d_loss"] - float(gc["d_loss"])) / abs(float(gc["d_loss"]))
-        dst["g_loss"] = abs(src["g_loss"] - float(gc["g_loss"])) / abs(float(gc["g_loss"]))
-        for tag in ("d", "g"):
-            ref = {k[7:]: v for k, v in hc.items() if k.startswith(tag + "_full.")}
-            w, n, a = _param_errors(src[tag], ref, names)
-            dst[tag + "_worst"], dst[tag + "_worst_name"], dst[tag + "_all"] = w, n, a
-            for ch in (0, 1):
-                dst[f"{tag}_dx{ch}"] = max(U.rel(src[tag][k][:, ch], ref[k][:, ch]) for k in ("real", "fake") if k in ref)
-        dst["running"] = max(U.rel(src["buf"][k], gc["buf." + k]) for k in src["buf"] if not k.endswith("num_batches_tracked"))
-        assert all(int(src["buf"][k]) == 2 for k in src["buf"] if k.endswith("num_batches_tracked"))
-    return fig, floor
+    return U.network_figures(ndf, W, H, _dx_figures, det)
 
 
 @pytest.mark.parametrize("ndf,W,H", U.CASES)
@@ -192,47 +159,14 @@ def test_network_matches_the_golden(ndf, W, H):
 
 # ---- behaviour ---------------------------------------------------------------------------------------------------------------------
 def test_discriminator_step_is_bit_reproducible_in_deterministic_mode():
-    gc = U.golden_case(16, 64, 32)
-    real, fake = torch.from_numpy(gc["real"]).cuda(), torch.from_numpy(gc["fake"]).cuda()
-    runs = []
-    for _ in range(2):
-        disc = MK.MetaKernelDiscriminator(state=U.init(16), lr=1e-3, deterministic=True)
-        outs = [tuple(float(v) for v in disc.discriminator_step(real, nhwc(fake.cpu()), factor=1.0)) for _ in range(2)]
-        runs.append((outs, disc.params.cpu().clone(), disc.exp_avg_sq.cpu().clone(), {k: v.cpu().clone() for k, v in disc.buffers.items()}))
-        assert disc.global_step == 2 and int(disc.buffers["main.3.num_batches_tracked"]) == 4
-        assert float(disc.grads.abs().max()) == 0.0
-    assert runs[0][0] == runs[1][0]
-    assert torch.equal(runs[0][1], runs[1][1]) and torch.equal(runs[0][2], runs[1][2])
-    assert all(torch.equal(runs[0][3][k], runs[1][3][k]) for k in runs[0][3])
-    init = torch.cat([U.init(16)[n].reshape(-1) for n in disc.names])
-    assert not torch.equal(runs[0][1], init)
-    a, b = MK.MetaKernelDiscriminator(state=U.init(16), deterministic=True), MK.MetaKernelDiscriminator(state=U.init(16), deterministic=True)
-    assert torch.equal(a.forward(real), b.forward(nhwc(real.cpu()), layout="nhwc"))
-    assert a.logits().shape == (2, 1, 6, 2)
-    ev = a.forward(real, training=False)
-    assert int(a.buffers["main.3.num_batches_tracked"]) == 1 and torch.isfinite(ev).all()
-    with pytest.raises(RuntimeError, match="training-mode forward"):
-        a.input_gradient(torch.zeros_like(ev))
+    U.check_step_is_bit_reproducible()
 
 
 def test_state_round_trip(tmp_path):
-    gc = U.golden_case(16, 32, 24)
-    real, fake = torch.from_numpy(gc["real"]).cuda(), torch.from_numpy(gc["fake"]).cuda()
-    a = MK.MetaKernelDiscriminator(state=U.init(16), lr=1e-3, deterministic=True)
-    a.discriminator_step(real, fake)
-    a.save_state(str(tmp_path / "d.pt"))
-    a.discriminator_step(real, fake)
-    b = MK.MetaKernelDiscriminator(MK.MetaKernelConfig(2, 16, 3), seed=99, lr=1e-3, deterministic=True)
-    b.load_state(str(tmp_path / "d.pt"))
-    assert b.global_step == 1
-    b.discriminator_step(real, fake)
-    assert torch.equal(a.params, b.params) and torch.equal(a.exp_avg, b.exp_avg) and torch.equal(a.exp_avg_sq, b.exp_avg_sq)
-    sa, sb = a.state_dict(), b.state_dict()
-    assert list(sa) == list(MK.param_shapes(a.cfg)) and all(torch.equal(sa[k], sb[k]) for k in sa)
+    sa, c = U.check_state_round_trip(tmp_path)                      # (a state dict with the reference's keys loads, tables included)
     assert torch.equal(sa["main.5.sin_inc"], U.init(16)["main.5.sin_inc"])
-    c = MK.MetaKernelDiscriminator(state=sa)                        # a state dict with the reference's keys loads, buffers and tables included
-    assert torch.equal(c.buffers["main.9.running_var"].cpu(), sa["main.9.running_var"]) and int(c.buffers["main.6.num_batches_tracked"]) == 4
     assert c.cfg.ndf == 16 and c.cfg.n_layers == 3
+    assert c.wf == {} and c.wt == {}                                # the kernels read the fp32 masters: no bf16 operand copy, no pack launch
 
 
 # ---- the adversarial phase of the VAE trainers -------------------------------------------------------------------------------------

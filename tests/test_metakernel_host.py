@@ -16,7 +16,7 @@ import torch
 
 from rangeldm_amd import discriminator as D
 from rangeldm_amd import metakernel as MK
-from tests import meta_util as U
+from tests.disc_util import META as U
 
 
 def test_keys_are_the_reference_modules():

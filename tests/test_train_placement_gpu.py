@@ -1,7 +1,7 @@
 """GPU: the training kernels (rangeldm_amd/csrc/train.hip, train_attn.hip) on operands placed as the trainers place them.
 
 Every other kernel test allocates each operand as its own torch tensor.  The trainers do not: parameters and gradients are views of flat
-buffers packed end to end (TapeTrainer._init_parameters), split-K outputs are slices of one pre-zeroed arena (ZeroArena.take), and the
+buffers packed end to end (FlatParameters._init_parameters), split-K outputs are slices of one pre-zeroed arena (ZeroArena.take), and the
 wrappers' own outputs come from a caching allocator that hands back the block just freed.  Here every operand is a view between guards
 (tests/hip_util.py: place / assert_placement; tests/test_placement_host.py tests those):
 

@@ -291,6 +291,8 @@ def test_save_state_resume_and_gradient_accumulation(tmp_path):
     for x, t, y in batches[:2]:
         a.train_step(x, t, y)
     a.save_state(str(tmp_path / "state.pt"))
+    assert set(torch.load(str(tmp_path / "state.pt"), map_location="cpu", weights_only=True)) == {
+        "params", "exp_avg", "exp_avg_sq", "global_step", "names", "ema", "micro", "grads", "hp"}
     for x, t, y in batches[2:]:
         a.train_step(x, t, y)
     b = TR.UNetTrainer(cfg, synth_state_dict(unet_param_shapes(cfg), prefix="other."), **kw)      # different weights: all restored
