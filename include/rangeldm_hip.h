@@ -394,6 +394,41 @@ int rldm_matrix_row_argmin(const double* m, int rows, int cols, int exclude_diag
  * error (return 1, rldm_last_error names it), as is every other failure.  The call synchronises the stream. */
 int rldm_voxel_counts(const float* x, const int32_t* x_offsets, int x_stride, const float* y, const int32_t* y_offsets,
                       int y_stride, int num_pairs, float voxel, int32_t* counts, void* stream);
+/* ---- sensor tables by Hough voting (rangeldm_amd/csrc/hough.hip) --------------------------------------------------- */
+#define RLDM_HOUGH_MAX_THETA 65536       /* inclination rows of an accumulator */
+#define RLDM_HOUGH_MAX_H 4096            /* height bins of a row (the rows of a workgroup live in 32 KiB of LDS) */
+#define RLDM_HOUGH_MAX_BEAMS 256         /* candidate beams of assign / moments */
+/* The tables rldm_lidar_create takes (ldm/kitti360_range_image.py:19-48) from the sensor's own sweeps, by the Hough vote of
+ * the RangeLDM paper (the reference ships the tables, not the step).  A return of beam k satisfies
+ * atan2(height_k - z, d) = incl_k with d = sqrt(x^2 + y^2) (ldm/kitti360_range_image.py:51-61, to_pc_torch,
+ * ldm/dataset.py:228-278), so with t = tan(incl): h = z + d t.  Every fp32 expression below is ONE correctly rounded
+ * operation, there is no transcendental on the device, and fp32 denormals are kept: numpy restates pack, vote, row_max and
+ * assign bit for bit (rangeldm_amd/sensor.py).  n < 2^31 everywhere; n = 0 is a no-op.  All pointers but the tables'
+ * arguments are device pointers; nothing synchronises.
+ *
+ * pack: points device fp32 [n][stride >= 3] -> packed device fp32 [n][2] = (d, z), d = sqrt(x * x + y * y).  A point is
+ * valid iff x, y, z are finite and d_min <= d <= d_max; an invalid point is written as d = -1.  Order kept. */
+int rldm_hough_pack(const float* points, int64_t n, int stride, float d_min, float d_max, float* packed, void* stream);
+/* vote: for every valid packed point and every row i < n_theta:  h = z + d * tan_table[i];  jf = floorf((h - h_min) * inv_dh);
+ * acc[i][(int)jf] += 1 iff 0 <= jf < n_h, compared as floats before the cast.  tan_table device fp32 [n_theta] (the host's
+ * float32(tan(float64(theta_i)))), acc device uint32 [n_theta][n_h]: added into, never cleared; the caller keeps the number
+ * of valid points below 2^32, so no counter wraps.  Integer votes: the result does not depend on any order. */
+int rldm_hough_vote(const float* packed, int64_t n, const float* tan_table, int n_theta, float h_min, float inv_dh, int n_h,
+                    uint32_t* acc, void* stream);
+/* how rldm_hough_vote cuts such a call (host only): rows of one workgroup, points of one slice */
+int rldm_hough_vote_shape(int64_t n, int n_theta, int n_h, int32_t* rows, int64_t* slice);
+/* per row the largest counter and the lowest bin holding it; a row of zeros gives (0, 0).  Device outputs [n_theta]. */
+int rldm_hough_row_max(const uint32_t* acc, int n_theta, int n_h, uint32_t* row_max, int32_t* row_arg, void* stream);
+/* assign: candidates device fp32 [beams][2] = (tan_k, h_k), beams <= RLDM_HOUGH_MAX_BEAMS.  Per packed point the residual in
+ * tangent space e_k = |(h_k - z) / d - tan_k| (the nearest-inclination rule of ldm/kitti360_range_image.py:51-61 without its
+ * atan2); ids[i] = the k of the smallest e_k (ties: the lowest k), or -1 when the point is invalid or that e_k is not < tol.
+ * ids device int16 [n]. */
+int rldm_hough_assign(const float* packed, int64_t n, const float* candidates, int beams, float tol, int16_t* ids, void* stream);
+/* moments: per beam the number of points assigned to it (counts device int64 [beams]) and sums device fp64 [beams][4] =
+ * sum d, sum z, sum d^2, sum d z, every value converted to fp64 before any product.  No floating-point atomics; the order of
+ * every sum is a function of n alone, so two calls give the same bits. */
+int rldm_hough_moments(const float* packed, const int16_t* ids, int64_t n, int beams, int64_t* counts, double* sums,
+                       void* stream);
 /* ---- Earth Mover's Distance (rangeldm_amd/csrc/emd.hip) ------------------------------------------------------------ */
 #define RLDM_EMD_RECT 0          /* every cloud of X against every cloud of Y */
 #define RLDM_EMD_SYMMETRIC 1     /* Y is X (the same buffers): j > i computed, mirrored, zero diagonal */

@@ -15,6 +15,8 @@ RLDM_EMD_RECT, RLDM_EMD_SYMMETRIC, RLDM_EMD_DIAGONAL = 0, 1, 2
 RLDM_EMD_BID_CAP = 2
 # rldm_voxel_counts: the return value that reports a point out of range, and the workspace bound in hash slots
 RLDM_VOXEL_RANGE, RLDM_VOXEL_MAX_SLOTS = 4, 1 << 25
+# rldm_hough_*: the largest accumulator (rows, bins per row) and the most candidate beams
+RLDM_HOUGH_MAX_THETA, RLDM_HOUGH_MAX_H, RLDM_HOUGH_MAX_BEAMS = 65536, 4096, 256
 # rldm_singular_values_f64 / rldm_frechet_distance: the return values that are not the ordinary error
 RLDM_FRECHET_SWEEP_CAP, RLDM_FRECHET_NONFINITE, RLDM_FRECHET_MAX_SWEEPS = 2, 3, 60
 # rldm_feature_scan_f64: the largest k (a row keeps k + 1 squared distances); non-finite input returns RLDM_FRECHET_NONFINITE
@@ -202,6 +204,13 @@ PROTOTYPES = {
     "rldm_matrix_row_argmin": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     # voxel-occupancy counts {a, b, c} per pair (csrc/voxel.hip): packed as rldm_chamfer_nn, voxel size, int32 [pairs][3]
     "rldm_voxel_counts": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_float, _P, _P]),
+    # sensor tables by Hough voting (csrc/hough.hip): (d, z) pairs, the vote, row maxima, beam assignment, per-beam moments
+    "rldm_hough_pack": (C.c_int, [_P, C.c_int64, C.c_int, C.c_float, C.c_float, _P, _P]),
+    "rldm_hough_vote": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P]),
+    "rldm_hough_vote_shape": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "rldm_hough_row_max": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
+    "rldm_hough_assign": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_float, _P, _P]),
+    "rldm_hough_moments": (C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, _P]),
     # all-pairs Earth Mover's Distance (epsilon-scaling auction) between equal-size clouds: emd, assignment, prices, bids
     "rldm_emd_matrix": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, _P]),
     # farthest point sampling of a ragged batch of clouds: k local indices per cloud, in selection order

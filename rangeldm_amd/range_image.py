@@ -380,3 +380,24 @@ class point_cloud_to_range_image_nuScenes(point_cloud_to_range_image):
 
     def get_row_inds(self, pc):
         return 31 - pc[:, 4].to(torch.int32)
+
+
+class point_cloud_to_range_image_tables(point_cloud_to_range_image):
+    """A sensor given by its tables: height [m] and incl [rad, positive downwards] per beam, top beam first -- what
+    sensor.estimate_sensor returns for a sensor without shipped constants.  `height` may also be a sensor.SensorTables (or any
+    object with .height and .incl), with `incl` left out.  Beam of a return = closest inclination, found inside the
+    projection kernel, as for KITTI-360."""
+
+    def __init__(self, height, incl=None, **kwargs) -> None:
+        if incl is None:
+            height, incl = height.height, height.incl
+        self.height = np.array(height, dtype=np.float32).reshape(-1)
+        self.incl = np.array(incl, dtype=np.float32).reshape(-1)
+        if self.height.shape != self.incl.shape or not 1 <= len(self.incl) <= 4096:
+            raise ValueError("height and incl must be two vectors of 1 .. 4096 beams")
+        self.zenith = -self.incl
+        self.H = len(self.incl)
+        super().__init__(**kwargs)
+
+    def get_row_inds(self, pc):
+        return None                     # nearest-inclination search runs on the device
