@@ -12,24 +12,17 @@
 //                          an azimuth window that may wrap past the seam
 //   beam_upsample_kernel   (B, C, W, Hs) -> (B, C, W, Hs * rate) along the beam axis: cv2 INTER_NEAREST / INTER_CUBIC
 //
-// Nearest-neighbour numerics.  d^2 is computed directly as ((dx*dx + dy*dy) + dz*dz) with dx = xq - xt, every operation a
-// single IEEE fp32 rounding (no FMA contraction: -ffp-contract=off in the Makefile plus the pragma below; packed
-// v_pk_add_f32 / v_pk_mul_f32 round each half like the scalar op).  Every per-point minimum is therefore bit-equal to a CPU
-// fp32 evaluation of the same expression, whatever the order in which the targets are visited.  The GEMM expansion
-// |x|^2 + |y|^2 - 2 x.y (on the VALU or on the exact-f32 MFMA) is NOT used: at 70 m |x|^2 is about 4900 m^2, one fp32 ulp
-// there is about 5e-4 m^2, larger than the typical nearest-neighbour d^2 of a dense scan -- the cancellation would leave
-// no correct digit in the quantity being measured.
+// Nearest-neighbour numerics and the streaming loop are nn_stream.h's (see its header): d^2 = ((dx*dx + dy*dy) + dz*dz), every
+// operation one IEEE fp32 rounding, so every per-point minimum is bit-equal to a CPU fp32 evaluation of the same expression.
 //
-// Structure.  A workgroup owns NN_QB = 256 x 8 query points of one pair (8 per thread, held as 4 packed pairs in VGPRs)
-// and one contiguous chunk of that pair's target cloud, which it streams through an LDS tile of NN_TILE points stored as
-// float4; every lane reads the same tile entry at the same time (an LDS broadcast).  Long target clouds are split over
-// several workgroups so that a handful of pairs still fills the chip; the partial minima are merged with atomicMin on the
-// bit pattern (non-negative floats order like uint32), so the result does not depend on the split.  Tile entries past the
-// end of the chunk hold +inf coordinates: their d^2 is +inf and never wins.
+// Structure.  A chamfer_nn_kernel workgroup owns one query block of one pair and one contiguous chunk of that pair's target
+// cloud.  Long target clouds are split over several workgroups so that a handful of pairs still fills the chip; the partial
+// minima are merged with atomicMin on the bit pattern (non-negative floats order like uint32), so the result does not depend
+// on the split.
 //
 // Preconditions: clouds are non-empty (the Python layer raises ValueError); coordinates are finite -- NaN or inf inputs
 // give unspecified results (not checked).
-#include "eval_common.h"
+#include "nn_stream.h"
 #include "../../include/rangeldm_hip.h"
 
 #include <cmath>
@@ -39,37 +32,17 @@
 
 namespace {
 
-constexpr int NN_THREADS = 256;
-constexpr int NN_R = 8;                       // query points per thread
-constexpr int NN_QB = NN_THREADS * NN_R;      // query points per workgroup
-constexpr int NN_TILE = 512;                  // target points per LDS tile (8 KiB)
-constexpr int NN_FILL_WGS = 256 * 8;          // split targets until about 8 workgroups per CU exist
-
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-__device__ inline f2 min2(f2 a, f2 b) { return f2{fminf(a.x, b.x), fminf(a.y, b.y)}; }
-
-// splits of one pair's target cloud: at most `splits`, and no chunk shorter than a tile (host and device agree on this)
-__host__ __device__ inline int pair_splits(int splits, int nt) {
-    const int by_len = (nt + NN_TILE - 1) / NN_TILE;
-    return splits < by_len ? splits : by_len;
-}
-
 // grid: one workgroup per (pair, query block, target chunk); wg_start[p] = first workgroup of pair p (num_pairs + 1 entries).
-// out (pre-filled with +inf) receives atomicMin of the float bit patterns, indexed like the packed query array.
-__global__ __launch_bounds__(NN_THREADS) void chamfer_nn_kernel(const float* __restrict__ q, const int* __restrict__ qoff,
-                                                                int qstride, const float* __restrict__ t,
-                                                                const int* __restrict__ toff, int tstride, int num_pairs,
-                                                                const int* __restrict__ wg_start, int splits,
-                                                                unsigned* __restrict__ out) {
+// out (pre-filled with +inf) receives atomicMin of the float bit patterns, indexed like the packed query array.  Eight waves
+// per SIMD: the loop's state fits 64 VGPRs, and saying so keeps the sweep's tile reads from being hoisted into 84.
+__global__ __launch_bounds__(NN_THREADS, 8) void chamfer_nn_kernel(const float* __restrict__ q, const int* __restrict__ qoff,
+                                                                   int qstride, const float* __restrict__ t,
+                                                                   const int* __restrict__ toff, int tstride, int num_pairs,
+                                                                   const int* __restrict__ wg_start, int splits,
+                                                                   unsigned* __restrict__ out) {
     __shared__ float4 tile[NN_TILE];
     const int wg = blockIdx.x, tid = threadIdx.x;
-    int lo = 0, hi = num_pairs;                          // wg_start[lo] <= wg < wg_start[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (wg_start[mid] <= wg) lo = mid; else hi = mid;
-    }
-    const int p = lo;
+    const int p = segment_of(wg_start, num_pairs, wg);
     const int q0 = qoff[p], nq = qoff[p + 1] - q0, t0 = toff[p], nt = toff[p + 1] - t0;
     const int sp = pair_splits(splits, nt);
     const int local = wg - wg_start[p];
@@ -77,48 +50,13 @@ __global__ __launch_bounds__(NN_THREADS) void chamfer_nn_kernel(const float* __r
     const int chunk = (nt + sp - 1) / sp;
     const int t_begin = s * chunk, t_end = min(nt, t_begin + chunk);
 
-    f2 qx[NN_R / 2], qy[NN_R / 2], qz[NN_R / 2], best[NN_R / 2];
+    const PackedQueries pq = load_queries(q, q0, nq, qstride, qb, tid);
+    f2 best[NN_R / 2];
 #pragma unroll
-    for (int k = 0; k < NN_R / 2; ++k) {
-        float v[2][3];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int i = min(qb * NN_QB + (2 * k + h) * NN_THREADS + tid, nq - 1);     // past the end: a valid duplicate
-            const float* pt = q + (size_t)(q0 + i) * qstride;
-            v[h][0] = pt[0]; v[h][1] = pt[1]; v[h][2] = pt[2];
-        }
-        qx[k] = f2{v[0][0], v[1][0]};
-        qy[k] = f2{v[0][1], v[1][1]};
-        qz[k] = f2{v[0][2], v[1][2]};
-        best[k] = f2{INFINITY, INFINITY};
-    }
-
+    for (int k = 0; k < NN_R / 2; ++k) best[k] = f2{INFINITY, INFINITY};
     for (int base = t_begin; base < t_end; base += NN_TILE) {
-        const int n = min(NN_TILE, t_end - base);
-        __syncthreads();                                 // the previous tile has been read
-        for (int i = tid; i < NN_TILE; i += NN_THREADS) {
-            float4 v = make_float4(INFINITY, INFINITY, INFINITY, 0.f);
-            if (i < n) {
-                const float* pt = t + (size_t)(t0 + base + i) * tstride;
-                v = make_float4(pt[0], pt[1], pt[2], 0.f);
-            }
-            tile[i] = v;
-        }
-        __syncthreads();
-        const int n4 = (n + 3) & ~3;                     // entries [n, n4) are the +inf padding
-        for (int j = 0; j < n4; j += 4) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float4 tp = tile[j + u];
-                const f2 tx = f2{tp.x, tp.x}, ty = f2{tp.y, tp.y}, tz = f2{tp.z, tp.z};
-#pragma unroll
-                for (int k = 0; k < NN_R / 2; ++k) {
-                    const f2 dx = qx[k] - tx, dy = qy[k] - ty, dz = qz[k] - tz;
-                    const f2 d2 = (dx * dx + dy * dy) + dz * dz;
-                    best[k] = min2(best[k], d2);
-                }
-            }
-        }
+        const int n4 = stage_tile(tile, t, t0 + base, min(NN_TILE, t_end - base), tstride, tid);
+        sweep_tile(tile, 0, n4, pq, best);
     }
 
 #pragma unroll
@@ -149,7 +87,7 @@ __global__ __launch_bounds__(256) void chamfer_mean_kernel(const float* __restri
 // ---- all-pairs matrix -----------------------------------------------------------------------------------------------
 // One direction: query set Q (nq clouds), target set T (nt clouds).  Workgroup = (query block g, run r): the block's NN_QB
 // points stay in registers while the target clouds [r * run, (r + 1) * run) -- in the symmetric case only those above
-// (tri > 0) or below (tri < 0) the query cloud -- stream through the LDS tile with chamfer_nn_kernel's inner loop.  A target
+// (tri > 0) or below (tri < 0) the query cloud -- stream through the LDS tile under nn_stream.h's sweep.  A target
 // cloud is never split, so each minimum is final when its cloud ends: the block then adds its minima in fp64 (per thread in
 // slot order, block_sum across threads) into part[qb_start[c] * nt + j * nqb(c) + qb].  That sum depends on (c, qb, j)
 // alone -- not on `run`, the grid, or which other clouds the call holds.
@@ -162,32 +100,14 @@ __global__ __launch_bounds__(NN_THREADS) void chamfer_matrix_kernel(const float*
     __shared__ double sh[NN_THREADS / 64];
     const int tid = threadIdx.x;
     const int g = blockIdx.x / runs, r = blockIdx.x - g * runs;
-    int lo = 0, hi = nq;                                 // qb_start[lo] <= g < qb_start[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (qb_start[mid] <= g) lo = mid; else hi = mid;
-    }
-    const int c = lo, qb = g - qb_start[c], nqb = qb_start[c + 1] - qb_start[c];
+    const int c = segment_of(qb_start, nq, g), qb = g - qb_start[c], nqb = qb_start[c + 1] - qb_start[c];
     int j0 = r * run, j1 = min(nt, j0 + run);
     if (tri > 0) j0 = max(j0, c + 1);
     if (tri < 0) j1 = min(j1, c);
     if (j0 >= j1) return;                                // (uniform over the workgroup)
     const int q0 = qoff[c], nqp = qoff[c + 1] - q0;
 
-    f2 qx[NN_R / 2], qy[NN_R / 2], qz[NN_R / 2];
-#pragma unroll
-    for (int k = 0; k < NN_R / 2; ++k) {
-        float v[2][3];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int i = min(qb * NN_QB + (2 * k + h) * NN_THREADS + tid, nqp - 1);    // past the end: a valid duplicate
-            const float* pt = q + (size_t)(q0 + i) * qstride;
-            v[h][0] = pt[0]; v[h][1] = pt[1]; v[h][2] = pt[2];
-        }
-        qx[k] = f2{v[0][0], v[1][0]};
-        qy[k] = f2{v[0][1], v[1][1]};
-        qz[k] = f2{v[0][2], v[1][2]};
-    }
+    const PackedQueries pq = load_queries(q, q0, nqp, qstride, qb, tid);
 
     for (int j = j0; j < j1; ++j) {
         const int t0 = toff[j], ntp = toff[j + 1] - t0;
@@ -195,31 +115,8 @@ __global__ __launch_bounds__(NN_THREADS) void chamfer_matrix_kernel(const float*
 #pragma unroll
         for (int k = 0; k < NN_R / 2; ++k) best[k] = f2{INFINITY, INFINITY};
         for (int base = 0; base < ntp; base += NN_TILE) {
-            const int n = min(NN_TILE, ntp - base);
-            __syncthreads();                             // the previous tile has been read
-            for (int i = tid; i < NN_TILE; i += NN_THREADS) {
-                float4 v = make_float4(INFINITY, INFINITY, INFINITY, 0.f);
-                if (i < n) {
-                    const float* pt = t + (size_t)(t0 + base + i) * tstride;
-                    v = make_float4(pt[0], pt[1], pt[2], 0.f);
-                }
-                tile[i] = v;
-            }
-            __syncthreads();
-            const int n4 = (n + 3) & ~3;                 // entries [n, n4) are the +inf padding
-            for (int e = 0; e < n4; e += 4) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float4 tp = tile[e + u];
-                    const f2 tx = f2{tp.x, tp.x}, ty = f2{tp.y, tp.y}, tz = f2{tp.z, tp.z};
-#pragma unroll
-                    for (int k = 0; k < NN_R / 2; ++k) {
-                        const f2 dx = qx[k] - tx, dy = qy[k] - ty, dz = qz[k] - tz;
-                        const f2 d2 = (dx * dx + dy * dy) + dz * dz;
-                        best[k] = min2(best[k], d2);
-                    }
-                }
-            }
+            const int n4 = stage_tile(tile, t, t0 + base, min(NN_TILE, ntp - base), tstride, tid);
+            sweep_tile(tile, 0, n4, pq, best);
         }
         double acc = 0.0;
 #pragma unroll
@@ -366,42 +263,17 @@ int rldm_chamfer_nn(const float* x, const int32_t* x_offsets, int x_stride, cons
     RLDM_REQUIRE(num_pairs > 0 && x_stride >= 3 && y_stride >= 3, "bad shape");
     hipStream_t st = (hipStream_t)stream;
     std::vector<int32_t> xo(num_pairs + 1), yo(num_pairs + 1);
-    RLDM_HIP_CHECK(hipMemcpyAsync(xo.data(), x_offsets, xo.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    RLDM_HIP_CHECK(hipMemcpyAsync(yo.data(), y_offsets, yo.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    RLDM_HIP_CHECK(hipStreamSynchronize(st));
-    RLDM_REQUIRE(xo[0] == 0 && yo[0] == 0, "offsets must start at 0");
-    long long qblocks[2] = {0, 0};
-    for (int p = 0; p < num_pairs; ++p) {
-        RLDM_REQUIRE(xo[p + 1] > xo[p] && yo[p + 1] > yo[p], "every cloud must be non-empty");
-        qblocks[0] += (xo[p + 1] - xo[p] + NN_QB - 1) / NN_QB;
-        qblocks[1] += (yo[p + 1] - yo[p] + NN_QB - 1) / NN_QB;
-    }
-    // workgroup tables of both directions in one allocation: [dir][num_pairs + 1]
-    std::vector<int32_t> starts(2 * (num_pairs + 1));
+    if (int rc = fetch_offsets(st, x_offsets, xo, y_offsets, yo)) return rc;
+    PairGrid wgs(st);                                    // [dir][num_pairs + 1]
     int splits[2];
-    for (int dir = 0; dir < 2; ++dir) {
-        const std::vector<int32_t>& qo = dir ? yo : xo;
-        const std::vector<int32_t>& to = dir ? xo : yo;
-        splits[dir] = (int)std::max<long long>(1, (NN_FILL_WGS + qblocks[dir] - 1) / qblocks[dir]);
-        int32_t* ws = starts.data() + dir * (num_pairs + 1);
-        long long acc = 0;
-        for (int p = 0; p < num_pairs; ++p) {
-            ws[p] = (int32_t)acc;
-            const long long nqb = (qo[p + 1] - qo[p] + NN_QB - 1) / NN_QB;
-            acc += nqb * pair_splits(splits[dir], to[p + 1] - to[p]);
-        }
-        RLDM_REQUIRE(acc < (1LL << 31) / NN_THREADS, "too many workgroups");
-        ws[num_pairs] = (int32_t)acc;
-    }
-    DevBuf dbuf(st);
-    RLDM_HIP_CHECK(dbuf.alloc(starts.size() * sizeof(int32_t)));
-    int32_t* dstarts = dbuf.as<int32_t>();
-    RLDM_HIP_CHECK(hipMemcpyAsync(dstarts, starts.data(), starts.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (int rc = wgs.plan(xo, yo, NN_QB, NN_FILL_WGS, &splits[0])) return rc;
+    if (int rc = wgs.plan(yo, xo, NN_QB, NN_FILL_WGS, &splits[1])) return rc;
+    if (int rc = wgs.upload()) return rc;
+    const int32_t* dstarts = wgs.dev.as<int32_t>();
     RLDM_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(x_nn_d2), 0x7f800000, (size_t)xo[num_pairs], st));
     RLDM_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(y_nn_d2), 0x7f800000, (size_t)yo[num_pairs], st));
     for (int dir = 0; dir < 2; ++dir) {
-        const int32_t* ws = starts.data() + dir * (num_pairs + 1);
-        const int grid = ws[num_pairs];
+        const int grid = wgs.host[dir * (num_pairs + 1) + num_pairs];
         if (dir == 0)
             chamfer_nn_kernel<<<grid, NN_THREADS, 0, st>>>(x, x_offsets, x_stride, y, y_offsets, y_stride, num_pairs, dstarts,
                                                            splits[0], reinterpret_cast<unsigned*>(x_nn_d2));
@@ -411,8 +283,7 @@ int rldm_chamfer_nn(const float* x, const int32_t* x_offsets, int x_stride, cons
                                                            reinterpret_cast<unsigned*>(y_nn_d2));
         RLDM_HIP_CHECK(hipGetLastError());
     }
-    RLDM_HIP_CHECK(hipStreamSynchronize(st));          // `starts` (pageable host memory) must outlive its upload
-    return 0;
+    return wgs.finish();
 }
 
 int rldm_chamfer_mean(const float* x_nn_d2, const int32_t* x_offsets, const float* y_nn_d2, const int32_t* y_offsets,
@@ -434,23 +305,13 @@ int rldm_chamfer_matrix(const float* x, const int32_t* x_offsets, int x_stride, 
     RLDM_REQUIRE((long long)nx * ny < (1LL << 31), "matrix too large (nx * ny must stay below 2^31)");
     hipStream_t st = (hipStream_t)stream;
     std::vector<int32_t> off[2] = {std::vector<int32_t>(nx + 1), std::vector<int32_t>(ny + 1)};
-    RLDM_HIP_CHECK(hipMemcpyAsync(off[0].data(), x_offsets, off[0].size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    RLDM_HIP_CHECK(hipMemcpyAsync(off[1].data(), y_offsets, off[1].size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    RLDM_HIP_CHECK(hipStreamSynchronize(st));
-    RLDM_REQUIRE(off[0][0] == 0 && off[1][0] == 0, "offsets must start at 0");
+    if (int rc = fetch_offsets(st, x_offsets, off[0], y_offsets, off[1])) return rc;
     const int n[2] = {nx, ny};
-    // query-block tables of both sets in one allocation: [x: nx + 1][y: ny + 1]
-    std::vector<int32_t> qbs(nx + ny + 2);
-    int32_t* qb[2] = {qbs.data(), qbs.data() + nx + 1};
-    for (int s = 0; s < 2; ++s) {
-        long long acc = 0;
-        for (int c = 0; c < n[s]; ++c) {
-            RLDM_REQUIRE(off[s][c + 1] > off[s][c], "every cloud must be non-empty");
-            qb[s][c] = (int32_t)acc;
-            acc += (off[s][c + 1] - off[s][c] + NN_QB - 1) / NN_QB;
-        }
-        qb[s][n[s]] = (int32_t)acc;
-    }
+    // query-block tables of both sets in one allocation, [x: nx + 1][y: ny + 1]: the pair grid of a set against itself, unsplit
+    PairGrid qbs(st);
+    for (int s = 0; s < 2; ++s)
+        if (int rc = qbs.plan(off[s], off[s], NN_QB, 0)) return rc;
+    const int32_t* qb[2] = {qbs.host.data(), qbs.host.data() + nx + 1};
     // direction 0: X queries, Y targets; direction 1: Y queries, X targets.  A run is a whole number of target clouds: long
     // enough to amortise the query load (>= MX_RUN_POINTS targets on average), short enough that the grid has many more
     // workgroups than the chip has slots (the tail of an uneven last wave of workgroups stays small)
@@ -471,12 +332,11 @@ int rldm_chamfer_matrix(const float* x, const int32_t* x_offsets, int x_stride, 
         runs[d] = (int)((n[t] + len - 1) / len);
         RLDM_REQUIRE(blocks * runs[d] < MX_MAX_WGS, "too many workgroups");
     }
-    DevBuf qbuf(st), pbuf(st);
-    RLDM_HIP_CHECK(qbuf.alloc(qbs.size() * sizeof(int32_t)));
+    if (int rc = qbs.upload()) return rc;
+    DevBuf pbuf(st);
     RLDM_HIP_CHECK(pbuf.alloc((size_t)part_len * sizeof(double)));
-    int32_t* dqb = qbuf.as<int32_t>();
+    const int32_t* dqb = qbs.dev.as<int32_t>();
     double* part = pbuf.as<double>();
-    RLDM_HIP_CHECK(hipMemcpyAsync(dqb, qbs.data(), qbs.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if (symmetric) {                                     // the diagonal; every other entry is written below
         RLDM_HIP_CHECK(hipMemsetAsync(xy, 0, (size_t)nx * ny * sizeof(double), st));
         RLDM_HIP_CHECK(hipMemsetAsync(yx, 0, (size_t)nx * ny * sizeof(double), st));
@@ -500,8 +360,7 @@ int rldm_chamfer_matrix(const float* x, const int32_t* x_offsets, int x_stride, 
         }
         RLDM_HIP_CHECK(hipGetLastError());
     }
-    RLDM_HIP_CHECK(hipStreamSynchronize(st));          // `qbs` (pageable host memory) must outlive its upload
-    return 0;
+    return qbs.finish();
 }
 
 int rldm_matrix_row_argmin(const double* m, int rows, int cols, int exclude_diag, double* min_out, int32_t* arg_out,

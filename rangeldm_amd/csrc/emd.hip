@@ -247,10 +247,7 @@ int rldm_emd_matrix(const float* x, const int32_t* x_offsets, int x_stride, int 
     RLDM_REQUIRE(eps > 0.f && std::isfinite(eps), "eps must be positive and finite");
     hipStream_t st = (hipStream_t)stream;
     std::vector<int32_t> xo(nx + 1), yo(ny + 1);
-    RLDM_HIP_CHECK(hipMemcpyAsync(xo.data(), x_offsets, xo.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    RLDM_HIP_CHECK(hipMemcpyAsync(yo.data(), y_offsets, yo.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    RLDM_HIP_CHECK(hipStreamSynchronize(st));
-    RLDM_REQUIRE(xo[0] == 0 && yo[0] == 0, "offsets must start at 0");
+    if (int rc = fetch_offsets(st, x_offsets, xo, y_offsets, yo)) return rc;
     const int N = xo[1] - xo[0];
     RLDM_REQUIRE(N >= 1 && N <= RLDM_EMD_MAX_POINTS, "clouds must hold 1 to 2048 points");
     for (int c = 0; c < nx; ++c) RLDM_REQUIRE(xo[c + 1] - xo[c] == N, "EMD is a one-to-one matching: every cloud must hold the same number of points");

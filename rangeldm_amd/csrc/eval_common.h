@@ -1,10 +1,11 @@
-// eval_common.h -- what the evaluation files (chamfer, voxel, emd, fps, metrics, frechet, feature_metrics, lidar, rangenet_post)
-// share, and nothing else.  No inference or training file includes it.
+// eval_common.h -- what the evaluation files (chamfer, nn_index and knn through nn_stream.h, voxel, emd, fps, metrics, frechet,
+// feature_metrics, lidar, rangenet_post) share, and nothing else.  No inference or training file includes it.
 #pragma once
 #include "common.h"
 
 #include <initializer_list>
 #include <utility>
+#include <vector>
 
 namespace rldm {
 
@@ -27,6 +28,36 @@ struct DevBuf {
     hipError_t alloc(size_t bytes) { return hipMallocAsync(&p, bytes, st); }
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
+
+// Packed clouds: the offsets of one or two sets of clouds (a, and b unless dev_b is null) from the device into vectors the
+// caller has sized, one synchronise for both, and what every caller requires of them.
+inline int fetch_offsets(hipStream_t st, const int32_t* dev_a, std::vector<int32_t>& a, const int32_t* dev_b,
+                         std::vector<int32_t>& b) {
+    RLDM_HIP_CHECK(hipMemcpyAsync(a.data(), dev_a, a.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (dev_b) RLDM_HIP_CHECK(hipMemcpyAsync(b.data(), dev_b, b.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    RLDM_HIP_CHECK(hipStreamSynchronize(st));
+    RLDM_REQUIRE(a[0] == 0 && (!dev_b || b[0] == 0), "offsets must start at 0");
+    const auto nonempty = [](const std::vector<int32_t>& off) {
+        for (size_t c = 0; c + 1 < off.size(); ++c)
+            if (off[c + 1] <= off[c]) return false;
+        return true;
+    };
+    RLDM_REQUIRE(nonempty(a) && (!dev_b || nonempty(b)), "every cloud must be non-empty");
+    return 0;
+}
+inline int fetch_offsets(hipStream_t st, const int32_t* dev_a, std::vector<int32_t>& a) {
+    return fetch_offsets(st, dev_a, a, nullptr, a);
+}
+
+// the segment of an ascending table that holds v: start[s] <= v < start[s + 1], for start[0] <= v < start[n]
+__device__ inline int segment_of(const int* __restrict__ start, int n, int v) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (start[mid] <= v) lo = mid; else hi = mid;
+    }
+    return lo;
+}
 
 // fixed-order block sum (shuffle tree inside each wave, then the wave partials in wave order): bit-identical run to run.
 // sh holds one double per wave of the workgroup.

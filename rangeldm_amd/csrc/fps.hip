@@ -204,15 +204,12 @@ int rldm_farthest_point_sample(const float* x, const int32_t* offsets, int strid
     RLDM_REQUIRE((long long)num_clouds * k < (1LL << 31), "too many indices (num_clouds * k must stay below 2^31)");
     hipStream_t st = (hipStream_t)stream;
     std::vector<int32_t> off(num_clouds + 1), first(start ? num_clouds : 0);
-    RLDM_HIP_CHECK(hipMemcpyAsync(off.data(), offsets, off.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (start) RLDM_HIP_CHECK(hipMemcpyAsync(first.data(), start, first.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    RLDM_HIP_CHECK(hipStreamSynchronize(st));
-    RLDM_REQUIRE(off[0] == 0, "offsets must start at 0");
+    if (int rc = fetch_offsets(st, offsets, off)) return rc;      // its synchronise covers `first` too
     int largest = 0;
     for (int c = 0; c < num_clouds; ++c) {
         const long long P = (long long)off[c + 1] - off[c];
         const std::string who = "cloud " + std::to_string(c) + ": ";
-        RLDM_REQUIRE(P >= 1, who + "every cloud must be non-empty");
         RLDM_REQUIRE(P <= RLDM_FPS_MAX_POINTS, who + "more than RLDM_FPS_MAX_POINTS (1048576) points");
         RLDM_REQUIRE(P * stride * 4 < (1LL << 31), who + "points x stride too large (byte offsets into a cloud are 32-bit)");
         RLDM_REQUIRE(k <= P, who + "k exceeds the number of points");

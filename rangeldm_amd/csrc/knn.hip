@@ -7,12 +7,13 @@
 //   knn_normals_kernel   per point the covariance of the point and its neighbours in fp64, a cyclic Jacobi eigen-solve, the
 //                        unit eigenvector of the smallest eigenvalue turned towards the sensor at the origin
 //
-// Numerics are nn_index.hip's: d^2 = ((dx*dx + dy*dy) + dz*dz) with dx = q - t, every operation one IEEE fp32 rounding, so
-// for K = 1 the row is rldm_nn_index's answer bit for bit, index included.
+// Numerics are nn_stream.h's (see its header): d^2 = ((dx*dx + dy*dy) + dz*dz) with dx = q - t, every operation one IEEE fp32
+// rounding, so for K = 1 the row is rldm_nn_index's answer bit for bit, index included.
 //
-// Structure.  The streaming loop is nn_index_kernel's: a workgroup owns 256 x R query points in registers and streams the whole
-// target cloud of its pair through an LDS tile that every lane reads in step.  A query keeps its list as KT 64-bit keys
-// (d^2 bits << 32) | index, ascending; non-negative floats order like their bit patterns.  The keys start as all ones, which
+// Structure.  The tile, its staging and the grid plan are nn_stream.h's: a workgroup owns 256 x R query points in registers and
+// streams the whole target cloud of its pair through an LDS tile that every lane reads in step.  The candidate loop is this
+// file's own (scalar, and exactly the tile's n entries: a padding entry would be a candidate).  A query keeps its list as KT
+// 64-bit keys (d^2 bits << 32) | index, ascending; non-negative floats order like their bit patterns.  The keys start as all ones, which
 // sorts above +inf and is stored as the (+inf, -1) slot.  Targets arrive in ascending index order, so a candidate belongs in
 // the list only if its d^2 bits are STRICTLY below the list's last: an equal one has a higher index than everything the list
 // holds.  That one unsigned compare is all a target costs beyond its distance; a lane that passes it runs a fully unrolled
@@ -22,7 +23,7 @@
 // Three tiers, 32 keys (64 VGPRs) per lane in each: KT = 8 with R = 4 queries per lane, KT = 16 with R = 2, KT = 32 with
 // R = 1.  K rounds up to its tier and the store truncates.  A target cloud is never split over workgroups: one route, and a row
 // depends on the two clouds of its pair alone.
-#include "eval_common.h"
+#include "nn_stream.h"
 #include "../../include/rangeldm_hip.h"
 
 #include <cmath>
@@ -32,8 +33,6 @@
 
 namespace {
 
-constexpr int KN_THREADS = 256;
-constexpr int KN_TILE = 512;                  // target points per LDS tile (8 KiB)
 constexpr int KN_KEYS = 32;                   // keys per lane in every tier: KT * R
 constexpr int KN_MAX_K = 32;
 
@@ -44,19 +43,14 @@ constexpr u64 KN_EMPTY = ~0ull;
 // self != 0: the target whose local index equals the query's is skipped (the clouds of a pair then have equal sizes).
 // Four waves per SIMD: 128 VGPRs hold the 64 of the keys, the queries and the chain's carry without scratch.
 template <int KT, int R>
-__global__ __launch_bounds__(KN_THREADS, 4) void knn_kernel(const float* __restrict__ q, const int* __restrict__ qoff, int qstride,
+__global__ __launch_bounds__(NN_THREADS, 4) void knn_kernel(const float* __restrict__ q, const int* __restrict__ qoff, int qstride,
                                                             const float* __restrict__ t, const int* __restrict__ toff,
                                                             int tstride, int num_pairs, const int* __restrict__ wg_start, int K,
                                                             int self, float* __restrict__ d2_out, int* __restrict__ idx_out) {
     static_assert(KT * R == KN_KEYS, "32 keys per lane");
-    __shared__ float4 tile[KN_TILE];
+    __shared__ float4 tile[NN_TILE];
     const int wg = blockIdx.x, tid = threadIdx.x;
-    int lo = 0, hi = num_pairs;                          // wg_start[lo] <= wg < wg_start[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (wg_start[mid] <= wg) lo = mid; else hi = mid;
-    }
-    const int p = lo;
+    const int p = segment_of(wg_start, num_pairs, wg);
     const int q0 = qoff[p], nq = qoff[p + 1] - q0, t0 = toff[p], nt = toff[p + 1] - t0;
     const int qb = wg - wg_start[p];
 
@@ -65,7 +59,7 @@ __global__ __launch_bounds__(KN_THREADS, 4) void knn_kernel(const float* __restr
     u64 key[R][KT];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const int i = min(qb * (KN_THREADS * R) + r * KN_THREADS + tid, nq - 1);     // past the end: a valid duplicate
+        const int i = min(qb * (NN_THREADS * R) + r * NN_THREADS + tid, nq - 1);     // past the end: a valid duplicate
         const float* pt = q + (size_t)(q0 + i) * qstride;
         qx[r] = pt[0]; qy[r] = pt[1]; qz[r] = pt[2];
         skip[r] = self ? i : -1;
@@ -73,14 +67,9 @@ __global__ __launch_bounds__(KN_THREADS, 4) void knn_kernel(const float* __restr
         for (int s = 0; s < KT; ++s) key[r][s] = KN_EMPTY;
     }
 
-    for (int base = 0; base < nt; base += KN_TILE) {
-        const int n = min(KN_TILE, nt - base);
-        __syncthreads();                                 // the previous tile has been read
-        for (int i = tid; i < n; i += KN_THREADS) {
-            const float* pt = t + (size_t)(t0 + base + i) * tstride;
-            tile[i] = make_float4(pt[0], pt[1], pt[2], 0.f);
-        }
-        __syncthreads();
+    for (int base = 0; base < nt; base += NN_TILE) {
+        const int n = min(NN_TILE, nt - base);
+        stage_tile(tile, t, t0 + base, n, tstride, tid, false);     // no padding: nothing past n is read
         for (int j = 0; j < n; ++j) {                    // exactly n: a padding entry would be a candidate
             const float4 tp = tile[j];
             const int tj = base + j;
@@ -105,7 +94,7 @@ __global__ __launch_bounds__(KN_THREADS, 4) void knn_kernel(const float* __restr
 
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const int i = qb * (KN_THREADS * R) + r * KN_THREADS + tid;
+        const int i = qb * (NN_THREADS * R) + r * NN_THREADS + tid;
         if (i >= nq) continue;
         float* drow = d2_out + (size_t)(q0 + i) * K;
         int* irow = idx_out + (size_t)(q0 + i) * K;
@@ -154,11 +143,7 @@ __global__ __launch_bounds__(256) void knn_normals_kernel(const float* __restric
                                                           double* __restrict__ normals, double* __restrict__ eig) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= off[num_clouds]) return;
-    int lo = 0, hi = num_clouds;                         // off[lo] <= i < off[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
+    const int lo = segment_of(off, num_clouds, i);
     const int c0 = off[lo], n = off[lo + 1] - c0;
     const int* row = idx + (size_t)i * K;
     const float* self = pts + (size_t)i * stride;
@@ -222,7 +207,7 @@ __global__ __launch_bounds__(256) void knn_normals_kernel(const float* __restric
 template <int KT, int R>
 void launch_knn(int grid, hipStream_t st, const float* q, const int* qoff, int qstride, const float* t, const int* toff, int tstride,
                 int num_pairs, const int* wg_start, int K, int self, float* d2, int* idx) {
-    knn_kernel<KT, R><<<grid, KN_THREADS, 0, st>>>(q, qoff, qstride, t, toff, tstride, num_pairs, wg_start, K, self, d2, idx);
+    knn_kernel<KT, R><<<grid, NN_THREADS, 0, st>>>(q, qoff, qstride, t, toff, tstride, num_pairs, wg_start, K, self, d2, idx);
 }
 
 }  // namespace
@@ -236,33 +221,20 @@ int rldm_knn(const float* q, const int32_t* q_offsets, int q_stride, const float
     RLDM_REQUIRE(K >= 1 && K <= KN_MAX_K, "K must be in 1..32");
     hipStream_t st = (hipStream_t)stream;
     std::vector<int32_t> qo(num_pairs + 1), to(num_pairs + 1);
-    RLDM_HIP_CHECK(hipMemcpyAsync(qo.data(), q_offsets, qo.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    RLDM_HIP_CHECK(hipMemcpyAsync(to.data(), t_offsets, to.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    RLDM_HIP_CHECK(hipStreamSynchronize(st));
-    RLDM_REQUIRE(qo[0] == 0 && to[0] == 0, "offsets must start at 0");
-    const int R = K <= 8 ? 4 : (K <= 16 ? 2 : 1);
-    const int qblock = KN_THREADS * R;
-    std::vector<int32_t> starts(num_pairs + 1);
-    long long acc = 0;
-    for (int p = 0; p < num_pairs; ++p) {
-        RLDM_REQUIRE(qo[p + 1] > qo[p] && to[p + 1] > to[p], "every cloud must be non-empty");
+    if (int rc = fetch_offsets(st, q_offsets, qo, t_offsets, to)) return rc;
+    for (int p = 0; p < num_pairs; ++p)
         RLDM_REQUIRE(!exclude_self || qo[p + 1] - qo[p] == to[p + 1] - to[p], "exclude_self needs clouds of equal sizes");
-        starts[p] = (int32_t)acc;
-        acc += (qo[p + 1] - qo[p] + qblock - 1) / qblock;
-    }
-    RLDM_REQUIRE(acc < (1LL << 31) / KN_THREADS, "too many workgroups");
-    starts[num_pairs] = (int32_t)acc;
-    DevBuf sbuf(st);
-    RLDM_HIP_CHECK(sbuf.alloc(starts.size() * sizeof(int32_t)));
-    int32_t* dstarts = sbuf.as<int32_t>();
-    RLDM_HIP_CHECK(hipMemcpyAsync(dstarts, starts.data(), starts.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    const int grid = (int)acc, self = exclude_self ? 1 : 0;
+    const int R = K <= 8 ? 4 : (K <= 16 ? 2 : 1);
+    PairGrid wgs(st);                                    // a target cloud is never split
+    if (int rc = wgs.plan(qo, to, NN_THREADS * R, 0)) return rc;
+    if (int rc = wgs.upload()) return rc;
+    const int32_t* dstarts = wgs.dev.as<int32_t>();
+    const int grid = wgs.host[num_pairs], self = exclude_self ? 1 : 0;
     if (R == 4) launch_knn<8, 4>(grid, st, q, q_offsets, q_stride, t, t_offsets, t_stride, num_pairs, dstarts, K, self, d2, idx);
     else if (R == 2) launch_knn<16, 2>(grid, st, q, q_offsets, q_stride, t, t_offsets, t_stride, num_pairs, dstarts, K, self, d2, idx);
     else launch_knn<32, 1>(grid, st, q, q_offsets, q_stride, t, t_offsets, t_stride, num_pairs, dstarts, K, self, d2, idx);
     RLDM_HIP_CHECK(hipGetLastError());
-    RLDM_HIP_CHECK(hipStreamSynchronize(st));          // `starts` (pageable host memory) must outlive its upload
-    return 0;
+    return wgs.finish();
 }
 
 int rldm_knn_normals(const float* pts, const int32_t* offsets, int stride, int num_clouds, const int32_t* idx, int K,

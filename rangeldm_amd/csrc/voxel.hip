@@ -68,11 +68,7 @@ __global__ __launch_bounds__(VOX_THREADS) void voxel_insert_kernel(const float* 
         const int side = e >= nx;
         const int* off = side ? yoff : xoff;
         const int i = side ? y0 + (e - nx) : x0 + e;         // index into the packed points of its side
-        int lo = 0, hi = pairs;                              // off[lo] <= i < off[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (off[mid] <= i) lo = mid; else hi = mid;
-        }
+        const int lo = segment_of(off, pairs, i);
         const float* pt = side ? y + (size_t)i * ystride : x + (size_t)i * xstride;
         const float q0 = floorf(f_div(pt[0], v)), q1 = floorf(f_div(pt[1], v)), q2 = floorf(f_div(pt[2], v));
         if (!(q0 >= -VOX_HALF && q0 < VOX_HALF && q1 >= -VOX_HALF && q1 < VOX_HALF && q2 >= -VOX_HALF && q2 < VOX_HALF)) {
@@ -133,10 +129,7 @@ int rldm_voxel_counts(const float* x, const int32_t* x_offsets, int x_stride, co
     RLDM_REQUIRE(voxel > 0.0f && std::isfinite(voxel), "voxel must be positive and finite");
     hipStream_t st = (hipStream_t)stream;
     std::vector<int32_t> xo(num_pairs + 1), yo(num_pairs + 1);
-    RLDM_HIP_CHECK(hipMemcpyAsync(xo.data(), x_offsets, xo.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    RLDM_HIP_CHECK(hipMemcpyAsync(yo.data(), y_offsets, yo.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    RLDM_HIP_CHECK(hipStreamSynchronize(st));
-    RLDM_REQUIRE(xo[0] == 0 && yo[0] == 0, "offsets must start at 0");
+    if (int rc = fetch_offsets(st, x_offsets, xo, y_offsets, yo)) return rc;
     // per pair: capacity, and the first slot of its table inside its chunk's allocation: [tbase: num_pairs][tcap: num_pairs]
     std::vector<int32_t> tab(2 * (size_t)num_pairs);
     int32_t* tbase = tab.data();
@@ -144,7 +137,6 @@ int rldm_voxel_counts(const float* x, const int32_t* x_offsets, int x_stride, co
     std::vector<int> chunk_first;                            // first pair of every chunk, then num_pairs
     long long used = 0, largest = 0;
     for (int p = 0; p < num_pairs; ++p) {
-        RLDM_REQUIRE(xo[p + 1] > xo[p] && yo[p + 1] > yo[p], "every cloud must be non-empty");
         const long long need = 2LL * ((long long)(xo[p + 1] - xo[p]) + (yo[p + 1] - yo[p]));
         if (need > VOX_MAX_SLOTS) {
             rldm::set_error("pair " + std::to_string(p) + " holds " + std::to_string(need / 2) + " points, above the " +

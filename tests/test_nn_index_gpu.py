@@ -114,6 +114,28 @@ def test_bit_equality(ragged, fillers, strides):
     _same(_call(fx[:40], fy[:40]), M.nearest_neighbours_host([t.cpu().numpy() for t in fx[:40]], [t.cpu().numpy() for t in fy[:40]], True))
 
 
+def test_tile_end_residues_agree_on_every_route(fillers):
+    """The shared tile stage and sweep at the tile ends SIZES does not hold.  511, 512 and 513 are n mod 4 = 3, 0 and 1; here
+    the targets are 509, 510, 514 and 515 points (1, 2, 2, 3, on both sides of the 512-point tile).  Alone the call splits
+    514 and 515 into chunks of 257 and 258; among the fillers every cloud is streamed whole (a full tile, then 2 or 3 points).
+    nearest_sq_dists, nearest_neighbours and knn_points(K=1) must give the host statement's d^2 bits in both directions, and
+    the last two its indices."""
+    rng = np.random.default_rng(9)
+    xs = [_lidar_like(rng, n, 3).astype(np.float32) for n in (5, 2049, 257, 1)]
+    ys = [_lidar_like(rng, m, 3).astype(np.float32) for m in (509, 510, 514, 515)]
+    want = M.nearest_neighbours_host(xs, ys)
+    fx, fy = fillers
+    for at in (0, 150):                                  # alone; pairs 150 .. 153 of 2 104
+        ax, ay = fx[:at] + _dev(xs) + (fx[at:] if at else []), fy[:at] + _dev(ys) + (fy[at:] if at else [])
+        routes = (M.nearest_sq_dists(ax, ay), M.nearest_neighbours(ax, ay), M.knn_points(ax, ay, 1) + M.knn_points(ay, ax, 1))
+        plain, index, knn = [[[t.cpu().numpy() for t in part[at:at + 4]] for part in route] for route in routes]
+        knn = [[col[:, 0] for col in part] for part in knn]
+        _same(plain, [want[0], want[2]])
+        _same(index, want)
+        _same(knn, want)
+        _same([index[1], index[3]], [knn[1], knn[3]])
+
+
 def test_ties_take_the_lowest_index(fillers):
     rng = np.random.default_rng(1)
     q = rng.uniform(-5, 5, (300, 3)).astype(np.float32)
