@@ -652,13 +652,16 @@ def gn_shift_scale_tokens(o, seed):
 # guard >= GUARD elements of one bit pattern.  Inputs sit between quiet NaNs (a stray load that is consumed -- also as x * 0 -- poisons the
 # result); outputs sit between finite sentinels, their interior pre-filled with a second NaN pattern (an element never written shows;
 # a cached block of an earlier call cannot hand it the right value); accumulating outputs carry the caller's pre-fill values.
+# Caller-owned workspaces ("scratch": the *_workspace() sizes of train_disc.hip / train_meta.hip, the losses' partials) sit between the
+# same finite sentinels and start from the unwritten-output pattern, but only their guards are checked: a workspace may stay partly
+# unwritten (a route that needs no partials), and the low words of fp64 partials kept in an fp32 view can look like any fp32 NaN.
 GUARD = 64
 _PLACE_PATTERNS = {       # dtype: (integer view, NaN around inputs, NaN inside unwritten outputs, finite sentinel around outputs)
     torch.float32: (torch.int32, 0x7FC0A5A5, 0x7FC05A5A, 0xF5A5A5A5 - (1 << 32)),                         # sentinel = -4.2e32
     torch.bfloat16: (torch.int16, 0x7FE5, 0x7FDA, 0xF5A5 - (1 << 16)),
     torch.float64: (torch.int64, 0x7FF80000A5A5A5A5, 0x7FF800005A5A5A5A, 0xF5A5A5A5A5A5A5A5 - (1 << 64)),
 }
-PLACE_KINDS = ("in", "out", "acc")
+PLACE_KINDS = ("in", "out", "acc", "scratch")
 
 
 class Placement:
@@ -680,8 +683,9 @@ class Placement:
 
 def place(tensors, lead=GUARD, kind="in", device=None, dtype=None):
     """tensors: {name: tensor} (kind "in": the values; "acc": the pre-fill values of an accumulating output) or {name: shape} (kind
-    "out": a non-accumulating output).  lead: the first view's offset in elements (>= GUARD); lead % (16 bytes / itemsize) is the
-    residue every view of the buffer gets (fp32: lead % 4).  -> Placement."""
+    "out": a non-accumulating output; "scratch": a caller-owned workspace of exactly that many elements).  lead: the first view's
+    offset in elements (>= GUARD); lead % (16 bytes / itemsize) is the residue every view of the buffer gets (fp32: lead % 4).
+    -> Placement."""
     assert kind in PLACE_KINDS, kind
     items = list(tensors.items())
     if dtype is None:
@@ -701,7 +705,7 @@ def place(tensors, lead=GUARD, kind="in", device=None, dtype=None):
     total = pos                                                      # (the last guard is >= GUARD wide as well)
     bits = torch.full((total,), nan_in if kind == "in" else sentinel, dtype=ityp)
     for (start, n), (name, t) in zip(spans, items):
-        if kind == "out":
+        if kind in ("out", "scratch"):
             bits[start:start + n] = nan_out
         else:
             assert torch.is_tensor(t) and t.dtype == dtype, f"{name}: kind {kind!r} needs a {dtype} tensor"
@@ -714,8 +718,8 @@ def place(tensors, lead=GUARD, kind="in", device=None, dtype=None):
 def assert_placement(buf, what=""):
     """After the kernels ran: every guard of `buf` still holds its pattern bit for bit; kind "in": so does every interior (kernels do not
     write their inputs); kind "out": no interior element still holds the unwritten pattern, and none is any other NaN (the operands are
-    finite: such a NaN was loaded from an input's guard).  A failure names the operand, the side and the element offset relative to the
-    operand's first element (negative: before it; >= its size: past it)."""
+    finite: such a NaN was loaded from an input's guard); kind "scratch": the guards alone.  A failure names the operand, the side and
+    the element offset relative to the operand's first element (negative: before it; >= its size: past it)."""
     ityp, nan_in, nan_out, sentinel = _PLACE_PATTERNS[buf.flat.dtype]
     now = buf.flat.detach().cpu().view(ityp)
     guard = torch.ones(now.numel(), dtype=torch.bool)
@@ -735,6 +739,8 @@ def assert_placement(buf, what=""):
     if len(bad) > 8:
         msgs.append(f"(+{len(bad) - 8} more guard elements)")
     for name, (start, n) in zip(buf.names, buf.spans):
+        if buf.kind == "scratch":                                    # a workspace: the guards above are all there is to ask
+            continue
         cur = now[start:start + n]
         if buf.kind == "in":
             k = (cur != buf.put[start:start + n]).nonzero().flatten().tolist()
@@ -785,3 +791,39 @@ def trainer_residues():
         us = unet_param_shapes(ucfg)
         per[f"UNetTrainer/{preset}"] = flat_buffer_residues(plan_parameter_order(list(us), us)[0], us)
     return per
+
+
+def flat_buffer_offsets(names, shapes):
+    """name -> offset % 4 of its view, in the order `names` (what flat_buffer_residues collects into a set)."""
+    out, pos = {}, 0
+    for n in names:
+        out[n] = pos % 4
+        pos += int(np.prod(shapes[n]))
+    return out
+
+
+def discriminator_layouts():
+    """name -> (trainable names in order, shapes) of every discriminator flat buffer the project builds or tests: the PatchGAN on the
+    image (the reference's in_channels = 2, ndf = 64, n_layers = 3, and the small networks of the tests) and on the BEV volume
+    (vae_training.py's disc_bev: in_channels = 2 gz planes, gz <= 16 and a channel count the 4x4 conv has an instance for: 2, 16, 32);
+    the Meta-Kernel network at its default config (vae/configs/kitti360.yaml's) and at the configs of tests/disc_util.py and of the
+    trainer tests (ndf = 16, one to three BatchNorm layers).  No GPU, no discriminator object."""
+    from rangeldm_amd import discriminator as D
+    from rangeldm_amd import metakernel as MK
+    out = {}
+    for tag, cfg in (("image", D.DiscriminatorConfig(2, 64, 3)), ("image/ndf16", D.DiscriminatorConfig(2, 16, 3)),
+                     ("image/ndf16/n_layers1", D.DiscriminatorConfig(2, 16, 1)), ("disc_bev/gz1", D.DiscriminatorConfig(2, 64, 3)),
+                     ("disc_bev/gz8", D.DiscriminatorConfig(16, 64, 3)), ("disc_bev/gz16", D.DiscriminatorConfig(32, 64, 3)),
+                     ("disc_bev/gz16/ndf16", D.DiscriminatorConfig(32, 16, 3))):
+        out["PatchDiscriminator/" + tag] = (D.trainable_names(cfg), D.param_shapes(cfg))
+    for tag, cfg in (("default", MK.MetaKernelConfig()), ("ndf16", MK.MetaKernelConfig(2, 16, 3)), ("ndf16/n_layers2", MK.MetaKernelConfig(2, 16, 2)),
+                     ("ndf16/n_layers1", MK.MetaKernelConfig(2, 16, 1))):
+        out["MetaKernelDiscriminator/" + tag] = (MK.trainable_names(cfg), MK.param_shapes(cfg))
+    return out
+
+
+def discriminator_residues():
+    """trainer_residues() for the two discriminators, which keep their parameters and gradients in FlatParameters' flat buffers as
+    well and hand views of them to train_disc.hip / train_meta.hip (and to rldm_train_colsum): name -> set, over
+    discriminator_layouts()."""
+    return {k: flat_buffer_residues(names, shapes) for k, (names, shapes) in discriminator_layouts().items()}

@@ -1,12 +1,13 @@
-"""CPU: the placement helpers of tests/hip_util.py (tests/test_train_placement_gpu.py is only as good as these), and the residues the
-project's trainers give their flat-buffer views.
+"""CPU: the placement helpers of tests/hip_util.py (tests/test_train_placement_gpu.py and tests/test_disc_placement_gpu.py are only as
+good as these), and the residues the project's trainers and discriminators give their flat-buffer views.
 
 Plain torch stand-ins for a faulty kernel get what a kernel gets -- the views, as pointers: `_raw` reaches around a view the way an index
 that is off by one does -- and each planted fault must be reported with the operand, the side and the element offset."""
 import pytest
 import torch
 
-from tests.hip_util import GUARD, assert_placement, flat_buffer_residues, int_grid, place, trainer_residues
+from tests.hip_util import (GUARD, PLACE_KINDS, assert_placement, discriminator_layouts, discriminator_residues, flat_buffer_offsets,
+                            flat_buffer_residues, int_grid, place, trainer_residues)
 
 N = 37                                  # not a multiple of 4: the views end inside a 16-byte granule
 
@@ -132,8 +133,9 @@ def test_the_gpu_tests_run_the_residues_the_trainers_produce():
     """offset % 4 of every parameter / gradient view of VAEDecoderTrainer, VAETrainer and UNetTrainer (full and nuScenes), from the
     shape tables and orders those trainers use.  The shipped VAE's 2-float `decoder.conv_out.bias` would put whatever follows it at
     residue 2 -- but the decoder is last in both VAE trainers' order and conv_out is last in the decoder, so nothing follows it: every
-    view starts on a 16-byte boundary today.  The GPU test takes its list from the same function, so it follows a configuration that
-    changes the set."""
+    view of these three tape trainers starts on a 16-byte boundary today.  (Of these three only: the discriminators keep flat buffers
+    too, and the Meta-Kernel network's do not -- test_the_discriminators_residues below.)  tests/test_train_placement_gpu.py takes its
+    list from the same function, so it follows a configuration that changes the set."""
     from tests import test_train_placement_gpu as G
     per = trainer_residues()
     assert set(per) == {f"{t}/{p}" for t in ("VAEDecoderTrainer", "VAETrainer", "UNetTrainer") for p in ("RangeLDM", "nuscenes")}
@@ -149,3 +151,102 @@ def test_the_gpu_tests_run_the_residues_the_trainers_produce():
     vs = vae_param_shapes(PRESETS["RangeLDM"]["vae"])
     names = decoder_param_names(PRESETS["RangeLDM"]["vae"], vs)
     assert names[-1] == "decoder.conv_out.bias" and tuple(vs[names[-1]]) == (2,)
+
+
+def test_the_discriminators_residues():
+    """offset % 4 of every parameter / gradient view of PatchDiscriminator and MetaKernelDiscriminator (hip_util.discriminator_layouts:
+    the image and disc_bev PatchGANs, the Meta-Kernel network at its default and at the tests' configs).  Every PatchGAN parameter is a
+    multiple of 16 floats but the last bias, which nothing follows: {0}.  The Meta-Kernel network's first layer has C = 2 --
+    mlp_coord.0.weight 6 floats, mlp_coord.0.bias 2, mlp_coord.2.weight 4, mlp_coord.2.bias 2: 14 floats in front of coov.weight -- and
+    every later parameter is a multiple of 4 floats, so the 8-byte offset stays to the end of the buffer: {0, 2}.
+    tests/test_disc_placement_gpu.py takes its list from the same function."""
+    from tests import test_disc_placement_gpu as G
+    per = discriminator_residues()
+    layouts = discriminator_layouts()
+    assert set(per) == set(layouts) and len(per) >= 8
+    patch = {k for k in per if k.startswith("PatchDiscriminator/")}
+    meta = {k for k in per if k.startswith("MetaKernelDiscriminator/")}
+    assert patch and meta and patch | meta == set(per)
+    assert {"PatchDiscriminator/image", "PatchDiscriminator/disc_bev/gz16", "MetaKernelDiscriminator/default"} <= set(per)
+    for k in patch:
+        assert per[k] == {0}, (k, per[k])
+    for k in meta:
+        assert per[k] == {0, 2}, (k, per[k])
+        names, shapes = layouts[k]
+        off = flat_buffer_offsets(names, shapes)
+        assert set(off.values()) == per[k] and list(off) == list(names)
+        at2 = [n for n in names if off[n] == 2]
+        assert at2[0] == "main.0.mlp_coord.0.bias"
+        tail = names[names.index("main.0.coov.weight"):]
+        assert all(off[n] == 2 for n in tail), [n for n in tail if off[n] != 2]
+        assert [n for n in names if off[n] == 0] == ["main.0.mlp_coord.0.weight", "main.0.mlp_coord.2.weight", "main.0.mlp_coord.2.bias"]
+        # ... which is every later MLP weight, every coov weight and bias, every BatchNorm gamma and beta
+        assert any(n.endswith(".mlp_coord.2.weight") for n in tail) and any(n.endswith("coov.bias") for n in tail)
+        assert any(n.startswith("main.3.") for n in tail)
+    assert list(G.DISC_RESIDUES) == sorted(set().union(*per.values())) == [0, 2]
+
+
+# ---- kind "scratch": a caller-owned workspace ------------------------------------------------------------------------------------------
+def _scratch(kernel, lead=GUARD, dtype=torch.float32):
+    ws = place({"ws": (N,), "partials": (6,)}, lead, "scratch", dtype=dtype)
+    kernel(ws["ws"])
+    return ws
+
+
+def k_ws_untouched(ws):
+    pass
+
+
+def k_ws_partly_written(ws):
+    ws[:N // 2] = 1.5
+
+
+def k_ws_holds_foreign_nans(ws):
+    """the low words of fp64 partials seen through an fp32 view, the unwritten pattern next to them"""
+    ws[3] = float("nan")
+    ws[4:8] = torch.tensor([1.0, -2.5], dtype=torch.float64).view(ws.dtype)[:4] if ws.dtype == torch.float32 else 0.0
+
+
+def k_ws_store_past(ws):
+    ws[:] = 0
+    _raw(ws, N, 1)[0] = 3.0
+
+
+def k_ws_store_before(ws):
+    ws[:] = 0
+    _raw(ws, -2, 1)[0] = 3.0
+
+
+def test_scratch_is_a_fourth_kind_and_changes_no_other():
+    assert PLACE_KINDS == ("in", "out", "acc", "scratch")
+    ws, o = place({"ws": (5,)}, GUARD + 2, "scratch"), place({"ws": (5,)}, GUARD + 2, "out")
+    assert torch.equal(ws.flat.view(torch.int32), o.flat.view(torch.int32))           # an output's sentinels and unwritten pattern
+    assert ws.kind == "scratch" and ws["ws"].shape == (5,) and ws.offset("ws") % 4 == 2
+    with pytest.raises(AssertionError):
+        place({"ws": (5,)}, GUARD, "workspace")
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+@pytest.mark.parametrize("kernel", [k_ws_untouched, k_ws_partly_written, k_ws_holds_foreign_nans], ids=lambda k: k.__name__)
+def test_scratch_interior_is_not_judged(kernel, dtype):
+    """A workspace may stay unwritten, be written in part, or hold any bit pattern: only the guards are checked -- where the same
+    interior fails as an "out"."""
+    assert_placement(_scratch(kernel, GUARD + 2, dtype), "workspace")
+    out = place({"ws": (N,)}, GUARD, "out", dtype=dtype)
+    kernel(out["ws"])
+    with pytest.raises(AssertionError, match="NEVER WRITTEN"):
+        assert_placement(out)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+@pytest.mark.parametrize("kernel,needles", [
+    (k_ws_store_past, ("operand 'ws'", "PAST", f"element offset {N} ")),
+    (k_ws_store_before, ("operand 'ws'", "BEFORE", "element offset -2")),
+], ids=lambda v: v.__name__ if callable(v) else None)
+def test_a_store_outside_a_scratch_view_is_named(kernel, needles, dtype):
+    ws = _scratch(kernel, GUARD, dtype)
+    with pytest.raises(AssertionError) as e:
+        assert_placement(ws, "case 9")
+    s = str(e.value)
+    assert s.startswith("case 9: ") and all(n in s for n in needles), s
+    assert s.count("operand '") == 1, s
