@@ -268,6 +268,16 @@ int rldm_lidar_to_voxel(rldm_lidar* l, const float* range_images, int B, int C, 
  * (voxel = log(d + 1) or d | S / max(d, 1e-4)).  The votes are fp32 atomics, as rldm_lidar_to_voxel's. */
 int rldm_lidar_to_voxel_train(rldm_lidar* l, const float* range_images, int B, int C, int W, float* raw, float* voxel,
                               void* stream);
+/* rldm_lidar_to_voxel_train with an order-fixed splat: per image and cell, with the vote id v = n * 8 + (dx * 4 + dy * 2 + dz)
+ * (n = w * beams + h) and the votes that count exactly those the atomic splat casts (pixel touches the volume, corner inside the
+ * grid, w != 0), d = ((0.f + w_v1) + w_v2) + ... over the cell's votes in ascending v, S the same over w * f, every + one fp32
+ * addition; a cell without votes holds +0.f in both.  `raw` (required) and `voxel` as rldm_lidar_to_voxel_train; the result does
+ * not depend on B, on the image's place in the batch, on the launch geometry or on the run.  No floating-point atomics: the
+ * votes are sorted by cell with a stable radix sort and summed left to right.  Scratch (kept by the handle, grown on demand):
+ * B * (25 * 8 * W * beams + 8 * cells + 1024) bytes.  Refuses 8 * B * W * beams >= 2^31 and grids of 2^31 cells or more.
+ * rldm_lidar_to_voxel_backward reads this `raw` as it reads the atomic one. */
+int rldm_lidar_to_voxel_ordered(rldm_lidar* l, const float* range_images, int B, int C, int W, float* raw, float* voxel,
+                                void* stream);
 /* d(loss) / d(range_images) for d(loss) / d(voxel) = dvoxel (B, 2*D, H, W), given the image and the raw accumulators of
  * rldm_lidar_to_voxel_train: dimages device fp32 (B, 2, W, beams), channel 0 the range value's, channel 1 the remission's.
  * Two launches, no atomics: per cell a = gD / (d + 1) [or gD] - [d >= 1e-4] gF S / d^2 and e = gF / max(d, 1e-4) into

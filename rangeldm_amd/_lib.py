@@ -183,6 +183,7 @@ PROTOTYPES = {
     "rldm_lidar_to_points": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rldm_lidar_to_voxel": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rldm_lidar_to_voxel_train": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "rldm_lidar_to_voxel_ordered": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "rldm_lidar_to_voxel_backward": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "rldm_lidar_filter_points": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P]),
     "rldm_render_u8": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),

@@ -7,6 +7,8 @@
 //   bev_finalize_kernel      feature / clamp(density), log(density + 1)      ldm/dataset.py:126-130, 289-293
 //   bev_finalize_train / bev_cell_grad / bev_pixel_grad   to_voxel for training: raw accumulators kept, the backward a gather
 //                                                         (vae/sgm/modules/autoencoding/losses: disc_bev, bev_rec_weight)
+//   bev_votes / radix_hist / radix_scan / radix_scatter / bev_segments / bev_ordered_sum   the order-fixed splat: votes sorted by
+//                                                         cell (stable), each cell summed left to right; no fp32 atomics
 //   filter_count / filter_scatter   `pc[norm(pc[:, :3]) < 90]` in order      ldm/inference.py:177-179
 //   render_u8_kernel         `(x.permute(2,1,0).clip(0,1)*255).astype(u8)`   ldm/inference.py:180-183
 //   project_* kernels        point_cloud_to_range_image.__call__ + process_miss_value + normalize
@@ -261,6 +263,276 @@ __global__ __launch_bounds__(256) void bev_pixel_grad_kernel(const float* __rest
     out[N + n] = df;
 }
 
+// ---- order-fixed to_voxel: every cell is the fp32 sum of its votes in ascending vote id -------------------------------
+// A vote has the id v = n * 8 + (dx * 4 + dy * 2 + dz).  The votes are written out at position v, sorted by cell with a STABLE
+// LSD radix sort (a pixel votes at most once into a cell, so within a cell ascending v is what a stable sort of votes that start
+// in v order leaves), and each cell then adds its segment left to right: d = ((0 + w_1) + w_2) + .., S the same over f_mul(w, f).
+// No floating-point atomic anywhere; no workgroup waits on another (every histogram, scan and scatter is its own launch).
+//
+// The sort's unit is a CHUNK of ORD_CHUNK consecutive positions, owned by one wave, which walks it in ORD_CHUNK / 64 rounds of 64;
+// a workgroup is four independent waves (four chunks).  Per 8-bit digit pass: radix_hist (per-chunk digit counts -> table
+// [digit][chunk]), radix_scan (one wave per image and digit: exclusive scan of that digit's row, and its total), radix_scatter
+// (start of the digit = the totals below it; rank inside the round from __ballot masks, base from the wave's running per-digit
+// counters in LDS -- never from an atomic's return value).
+constexpr int ORD_CHUNK = 1024;             // positions per wave
+constexpr int ORD_ROUNDS = ORD_CHUNK / 64;
+constexpr int ORD_SHORT = 16;               // segments up to this long are added by their cell's own lane (bev_ordered_sum_kernel)
+constexpr int ORD_LOADS = 4;                // 64-vote loads a wave keeps in flight while it adds a long segment
+
+// One thread per pixel: bev_splat_kernel's votes, written instead of cast.  keys[v] = the cell, or nvox (the sentinel, sorted
+// behind every cell) for a vote the atomic kernel would not cast; vals[v] = (w, w f), read only where the key is a cell.
+__global__ __launch_bounds__(256) void bev_votes_kernel(const float* __restrict__ img, int C, int W, int H, LidarDev L,
+                                                        const float* __restrict__ cos_azi, const float* __restrict__ sin_azi,
+                                                        GridDev G, unsigned* __restrict__ keys, float2* __restrict__ vals) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    const int b = blockIdx.y;
+    const int N = W * H;
+    if (n >= N) return;
+    const size_t M = (size_t)N * 8;
+    const unsigned nvox = (unsigned)((size_t)G.gz * G.gy * G.gx);
+    const float* im = img + (size_t)b * C * N;
+    unsigned k[8];
+    float2 wv[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) { k[c] = nvox; wv[c] = make_float2(0.f, 0.f); }
+    const float r = decode_range(im[n], L);
+    const float f = im[N + n];
+    float x, y, z;
+    pixel_to_xyz(r, n / H, n % H, L, cos_azi, sin_azi, &x, &y, &z);
+    const float px = grid_coord(x, G.cx, G.hx, G.gx), py = grid_coord(y, G.cy, G.hy, G.gy), pz = grid_coord(z, G.cz, G.hz, G.gz);
+    if (px > -1.f && px < (float)G.gx && py > -1.f && py < (float)G.gy && pz > -1.f && pz < (float)G.gz) {
+        const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);
+        const int X = (int)fx, Y = (int)fy, Z = (int)fz;
+        const float rx = f_sub(px, fx), ry = f_sub(py, fy), rz = f_sub(pz, fz);
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+            const int X_ = X + dx;
+            const float wx = dx ? rx : f_sub(1.f, rx);
+#pragma unroll
+            for (int dy = 0; dy < 2; ++dy) {
+                const int Y_ = Y + dy;
+                const float wy = dy ? ry : f_sub(1.f, ry);
+#pragma unroll
+                for (int dz = 0; dz < 2; ++dz) {
+                    const int Z_ = Z + dz;
+                    const float wz = dz ? rz : f_sub(1.f, rz);
+                    const float w = f_mul(f_mul(wx, wy), wz);
+                    const bool ok = X_ >= 0 && X_ < G.gx && Y_ >= 0 && Y_ < G.gy && Z_ >= 0 && Z_ < G.gz;
+                    if (ok && w != 0.f) {
+                        k[dx * 4 + dy * 2 + dz] = (unsigned)(((size_t)Z_ * G.gy + Y_) * G.gx + X_);
+                        wv[dx * 4 + dy * 2 + dz] = make_float2(w, f_mul(w, f));
+                    }
+                }
+            }
+        }
+    }
+    uint4* ko = reinterpret_cast<uint4*>(keys + (size_t)b * M + (size_t)n * 8);
+    ko[0] = make_uint4(k[0], k[1], k[2], k[3]);
+    ko[1] = make_uint4(k[4], k[5], k[6], k[7]);
+    float4* vo = reinterpret_cast<float4*>(vals + (size_t)b * M + (size_t)n * 8);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) vo[c] = make_float4(wv[2 * c].x, wv[2 * c].y, wv[2 * c + 1].x, wv[2 * c + 1].y);
+}
+
+// Digit counts of every chunk: table[b][digit * nchunks + chunk].  The LDS integer atomics' return values are not used.
+__global__ __launch_bounds__(256) void radix_hist_kernel(const unsigned* __restrict__ keys, int M, int nchunks, int shift,
+                                                         int* __restrict__ table) {
+    __shared__ int cnt[4][256];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int chunk = blockIdx.x * 4 + wave;
+    const int b = blockIdx.y;
+#pragma unroll
+    for (int d = lane; d < 256; d += 64) cnt[wave][d] = 0;
+    __syncthreads();
+    const unsigned* kb = keys + (size_t)b * M;
+    for (int r = 0; r < ORD_ROUNDS; ++r) {
+        const long long i = (long long)chunk * ORD_CHUNK + r * 64 + lane;
+        if (i < M) atomicAdd(&cnt[wave][(kb[i] >> shift) & 255u], 1);
+    }
+    __syncthreads();
+    if (chunk < nchunks) {
+        int* tb = table + (size_t)b * 256 * nchunks;
+#pragma unroll
+        for (int d = lane; d < 256; d += 64) tb[(size_t)d * nchunks + chunk] = cnt[wave][d];
+    }
+}
+
+// inclusive scan over the 64 lanes of a wave
+__device__ inline int wave_scan_incl(int v, int lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int up = __shfl_up(v, off);
+        if (lane >= off) v += up;
+    }
+    return v;
+}
+
+// One wave per (image, digit): the digit's row of the table, nchunks counts, becomes its exclusive scan in place (64 entries a step,
+// coalesced, the carry in a register) and the row's total goes to totals[b][digit].  radix_scatter adds the digits below.
+__global__ __launch_bounds__(256) void radix_scan_kernel(int* __restrict__ table, int nchunks, int* __restrict__ totals) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int digit = blockIdx.x * 4 + wave;
+    const int b = blockIdx.y;
+    int* row = table + ((size_t)b * 256 + digit) * nchunks;
+    int carry = 0;
+    for (int base = 0; base < nchunks; base += 64) {
+        const int i = base + lane;
+        const int c = i < nchunks ? row[i] : 0;
+        const int incl = wave_scan_incl(c, lane);
+        if (i < nchunks) row[i] = carry + incl - c;
+        carry += __shfl(incl, 63);
+    }
+    if (lane == 0) totals[b * 256 + digit] = carry;
+}
+
+// Stable scatter of one digit pass.  ids_in == nullptr: the first pass, where position i holds vote i.  Per round of 64 the lanes
+// that share a digit are found with eight ballots; a lane's place is its wave's running count of that digit (LDS, started from
+// the scanned table) plus the number of such lanes below it; the lowest of them then moves the count on.
+__global__ __launch_bounds__(256) void radix_scatter_kernel(const unsigned* __restrict__ keys_in, const int* __restrict__ ids_in,
+                                                            int M, int nchunks, int shift, const int* __restrict__ table,
+                                                            const int* __restrict__ totals, unsigned* __restrict__ keys_out,
+                                                            int* __restrict__ ids_out) {
+    __shared__ int base[4][256];
+    __shared__ int first[256];              // where the image's votes of digit d start: the totals of the digits below d
+    __shared__ int wave_tot[4];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int chunk = blockIdx.x * 4 + wave;
+    const int b = blockIdx.y;
+    {
+        const int c = totals[b * 256 + threadIdx.x];
+        const int incl = wave_scan_incl(c, lane);
+        if (lane == 63) wave_tot[wave] = incl;
+        __syncthreads();
+        int below = 0;
+        for (int w = 0; w < wave; ++w) below += wave_tot[w];
+        first[threadIdx.x] = below + incl - c;
+    }
+    __syncthreads();
+    if (chunk < nchunks) {
+        const int* tb = table + (size_t)b * 256 * nchunks;
+#pragma unroll
+        for (int d = lane; d < 256; d += 64) base[wave][d] = first[d] + tb[(size_t)d * nchunks + chunk];
+    }
+    __syncthreads();
+    const size_t o = (size_t)b * M;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int r = 0; r < ORD_ROUNDS; ++r) {
+        const long long i = (long long)chunk * ORD_CHUNK + r * 64 + lane;
+        const bool valid = i < M;
+        const unsigned key = valid ? keys_in[o + i] : 0u;
+        const int id = valid ? (ids_in ? ids_in[o + i] : (int)i) : 0;
+        const unsigned digit = (key >> shift) & 255u;
+        unsigned long long same = __ballot(valid);
+#pragma unroll
+        for (int bit = 0; bit < 8; ++bit) {
+            const unsigned long long m = __ballot((digit >> bit) & 1u);
+            same &= ((digit >> bit) & 1u) ? m : ~m;
+        }
+        int pos = 0;
+        if (valid) pos = base[wave][digit] + __popcll(same & below);
+        __syncthreads();                                    // every lane has read its count before the lowest lane moves it
+        if (valid && (same & below) == 0ull) base[wave][digit] += __popcll(same);
+        __syncthreads();
+        if (valid) {
+            keys_out[o + pos] = key;
+            ids_out[o + pos] = id;
+        }
+    }
+}
+
+// seg[b][cell] = (first, one past last) position of the cell's votes in the sorted order; cleared to (0, 0) before the launch.
+__global__ __launch_bounds__(256) void bev_segments_kernel(const unsigned* __restrict__ keys, int M, unsigned nvox,
+                                                           int2* __restrict__ seg) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int b = blockIdx.y;
+    if (i >= M) return;
+    const unsigned* kb = keys + (size_t)b * M;
+    int2* sb = seg + (size_t)b * nvox;
+    const unsigned k = kb[i];
+    if (i == 0) {
+        if (k < nvox) sb[k].x = 0;
+    } else {
+        const unsigned kp = kb[i - 1];
+        if (k != kp) {
+            if (k < nvox) sb[k].x = (int)i;
+            if (kp < nvox) sb[kp].y = (int)i;
+        }
+    }
+    if (i == M - 1 && k < nvox) sb[k].y = M;
+}
+
+// a += v.x, q += v.y of lanes 0 .. cnt - 1, one lane after the other (cnt <= 0: nothing); every lane of the wave ends with the same sums
+__device__ inline void add_lanes_in_order(float2 v, int cnt, float& a, float& q) {
+    const int x = __float_as_int(v.x), y = __float_as_int(v.y);
+    if (cnt >= 64) {
+#pragma unroll
+        for (int t = 0; t < 64; ++t) {
+            a = f_add(a, __int_as_float(__builtin_amdgcn_readlane(x, t)));
+            q = f_add(q, __int_as_float(__builtin_amdgcn_readlane(y, t)));
+        }
+    } else {
+        for (int t = 0; t < cnt; ++t) {
+            a = f_add(a, __int_as_float(__builtin_amdgcn_readlane(x, t)));
+            q = f_add(q, __int_as_float(__builtin_amdgcn_readlane(y, t)));
+        }
+    }
+}
+
+// One thread per cell writes raw = (d | S): 0.f, then one fp32 addition per vote of the cell's segment, left to right.  A segment
+// of up to ORD_SHORT votes is read by the cell's own lane.  A longer one (every pixel that decodes to a range near 0 votes into
+// the few cells under the sensor) is read by the whole wave, 64 votes a load, the next ORD_LOADS loads in flight while the values
+// of the current ones are handed lane by lane to the one running sum -- the same additions in the same order.
+__global__ __launch_bounds__(256) void bev_ordered_sum_kernel(const int2* __restrict__ seg, const int* __restrict__ ids,
+                                                              const float2* __restrict__ vals, int M, unsigned nvox,
+                                                              float* __restrict__ raw) {
+    const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int* ib = ids + (size_t)b * M;
+    const float2* vb = vals + (size_t)b * M;
+    const int2 se = c < nvox ? seg[(size_t)b * nvox + c] : make_int2(0, 0);
+    const int len = se.y - se.x;
+    float d = 0.f, S = 0.f;
+    if (len <= ORD_SHORT) {
+        for (int j = se.x; j < se.y; ++j) {
+            const float2 v = vb[ib[j]];
+            d = f_add(d, v.x);
+            S = f_add(S, v.y);
+        }
+    }
+    unsigned long long todo = __ballot(len > ORD_SHORT);
+    while (todo) {
+        const int src = __ffsll((long long)todo) - 1;
+        todo &= todo - 1ull;
+        const int s0 = __builtin_amdgcn_readlane(se.x, src), e0 = __builtin_amdgcn_readlane(se.y, src);
+        float a = 0.f, q = 0.f;
+        float2 cur[ORD_LOADS], nxt[ORD_LOADS];
+#pragma unroll
+        for (int g = 0; g < ORD_LOADS; ++g) {
+            const long long i = (long long)s0 + g * 64 + lane;
+            cur[g] = i < e0 ? vb[ib[i]] : make_float2(0.f, 0.f);
+        }
+        for (long long j = s0; j < e0; j += 64 * ORD_LOADS) {
+#pragma unroll
+            for (int g = 0; g < ORD_LOADS; ++g) {
+                const long long i = j + (ORD_LOADS + g) * 64 + lane;
+                nxt[g] = i < e0 ? vb[ib[i]] : make_float2(0.f, 0.f);
+            }
+#pragma unroll
+            for (int g = 0; g < ORD_LOADS; ++g) {
+                add_lanes_in_order(cur[g], (int)min(64ll, e0 - (j + g * 64)), a, q);
+                cur[g] = nxt[g];
+            }
+        }
+        if (lane == src) { d = a; S = q; }
+    }
+    if (c < nvox) {
+        float* rb = raw + (size_t)b * 2 * nvox;
+        rb[c] = d;
+        rb[(size_t)nvox + c] = S;
+    }
+}
+
 // ---- ordered depth filter ---------------------------------------------------------------------------------------
 // pass 1: kept points per 256-point chunk; pass 2: chunk base = sum of the preceding counts, wave ballots give the
 // rank inside the chunk.  The kept points keep their order (what `pc[mask]` does), no atomics.
@@ -435,6 +707,8 @@ struct rldm_lidar {
     unsigned long long* keys = nullptr;       // projection scratch [H][W] + raw (H, W, 2)
     float2* raw = nullptr;
     size_t proj_cap = 0;
+    void* ordered = nullptr;                  // rldm_lidar_to_voxel_ordered's scratch: keys, ids (both twice), votes, table, segments
+    size_t ordered_cap = 0;                   // bytes
     LidarDev dev() const {
         LidarDev L;
         L.cos_incl = tables;
@@ -510,6 +784,7 @@ void rldm_lidar_destroy(rldm_lidar* l) {
     if (l->chunk_counts) (void)hipFree(l->chunk_counts);
     if (l->keys) (void)hipFree(l->keys);
     if (l->raw) (void)hipFree(l->raw);
+    if (l->ordered) (void)hipFree(l->ordered);
     delete l;
 }
 
@@ -575,6 +850,70 @@ int rldm_lidar_to_voxel_train(rldm_lidar* l, const float* range_images, int B, i
     RLDM_HIP_CHECK(hipGetLastError());
     bev_finalize_train_kernel<<<dim3((unsigned)((nvox + 255) / 256), B), 256, 0, st>>>(raw, voxel, nvox,
                                                                                      c.normalize_volume_densities, 1e-4f);
+    RLDM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int rldm_lidar_to_voxel_ordered(rldm_lidar* l, const float* range_images, int B, int C, int W, float* raw, float* voxel,
+                                void* stream) {
+    RLDM_REQUIRE(l && range_images && raw && voxel, "null argument");
+    RLDM_REQUIRE(B > 0 && W > 0, "bad shape");
+    RLDM_REQUIRE(C >= 2, "to_voxel needs the remission channel (ldm/dataset.py:286 splats pc[:, :, 3:])");
+    const rldm_lidar_config& c = l->cfg;
+    const GridDev G = lidar_grid(c);
+    const size_t nvox = (size_t)G.gz * G.gy * G.gx;
+    RLDM_REQUIRE(8ull * (unsigned long long)B * (unsigned long long)W * (unsigned long long)c.beams < (1ull << 31),
+                 "to_voxel_ordered: 8 * B * W * beams votes must stay below 2^31");
+    RLDM_REQUIRE(nvox < ((size_t)1 << 31), "to_voxel_ordered: the grid must have fewer than 2^31 cells");
+    const float *ca, *sa;
+    if (lidar_azimuth(l, W, &ca, &sa)) return 1;
+    const int N = W * c.beams;
+    const int M = 8 * N;                                        // votes per image
+    const int nchunks = (M + ORD_CHUNK - 1) / ORD_CHUNK;
+    int bits = 0;
+    while (((size_t)1 << bits) < nvox + 1) ++bits;              // ceil(log2(nvox + 1)): the sentinel nvox is a key, too
+    const int passes = (bits + 7) / 8;
+    // scratch, every part rounded up to 256 bytes: keys and ids twice (the sort alternates), the votes, the digit table, the digit
+    // totals, the segments
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t words = up((size_t)B * M * 4), votes = up((size_t)B * M * 8), table_b = up((size_t)B * 256 * nchunks * 4),
+                 totals_b = up((size_t)B * 256 * 4), seg_b = up((size_t)B * nvox * 8);
+    const size_t need = 4 * words + votes + table_b + totals_b + seg_b;
+    if (need > l->ordered_cap) {
+        if (l->ordered) RLDM_HIP_CHECK(hipFree(l->ordered));
+        l->ordered = nullptr;
+        l->ordered_cap = 0;
+        RLDM_HIP_CHECK(hipMalloc(&l->ordered, need));
+        l->ordered_cap = need;
+    }
+    char* p = static_cast<char*>(l->ordered);
+    unsigned* keys[2] = {reinterpret_cast<unsigned*>(p), reinterpret_cast<unsigned*>(p + words)};
+    int* ids[2] = {reinterpret_cast<int*>(p + 2 * words), reinterpret_cast<int*>(p + 3 * words)};
+    float2* vals = reinterpret_cast<float2*>(p + 4 * words);
+    int* table = reinterpret_cast<int*>(p + 4 * words + votes);
+    int* totals = reinterpret_cast<int*>(p + 4 * words + votes + table_b);
+    int2* seg = reinterpret_cast<int2*>(p + 4 * words + votes + table_b + totals_b);
+    hipStream_t st = (hipStream_t)stream;
+    bev_votes_kernel<<<dim3((N + 255) / 256, B), 256, 0, st>>>(range_images, C, W, c.beams, l->dev(), ca, sa, G, keys[0], vals);
+    RLDM_HIP_CHECK(hipGetLastError());
+    const dim3 sort_grid((nchunks + 3) / 4, B);
+    int cur = 0;
+    for (int pass = 0; pass < passes; ++pass, cur ^= 1) {
+        radix_hist_kernel<<<sort_grid, 256, 0, st>>>(keys[cur], M, nchunks, 8 * pass, table);
+        RLDM_HIP_CHECK(hipGetLastError());
+        radix_scan_kernel<<<dim3(64, B), 256, 0, st>>>(table, nchunks, totals);
+        RLDM_HIP_CHECK(hipGetLastError());
+        radix_scatter_kernel<<<sort_grid, 256, 0, st>>>(keys[cur], pass ? ids[cur] : nullptr, M, nchunks, 8 * pass, table, totals,
+                                                       keys[cur ^ 1], ids[cur ^ 1]);
+        RLDM_HIP_CHECK(hipGetLastError());
+    }
+    RLDM_HIP_CHECK(hipMemsetAsync(seg, 0, (size_t)B * nvox * sizeof(int2), st));
+    bev_segments_kernel<<<dim3((M + 255) / 256, B), 256, 0, st>>>(keys[cur], M, (unsigned)nvox, seg);
+    RLDM_HIP_CHECK(hipGetLastError());
+    const dim3 cell_grid((unsigned)((nvox + 255) / 256), B);
+    bev_ordered_sum_kernel<<<cell_grid, 256, 0, st>>>(seg, ids[cur], vals, M, (unsigned)nvox, raw);
+    RLDM_HIP_CHECK(hipGetLastError());
+    bev_finalize_train_kernel<<<cell_grid, 256, 0, st>>>(raw, voxel, nvox, c.normalize_volume_densities, 1e-4f);
     RLDM_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -83,8 +83,11 @@ class point_cloud_to_range_image:
                                                    _lib.stream_ptr(x.device)), "rldm_lidar_to_points")
         return out
 
-    def to_voxel(self, range_images):
-        """-> (B, 2 * D, H, W) BEV volume: vote density and density-normalised remission (ldm/dataset.py:280-294)"""
+    def to_voxel(self, range_images, ordered=False):
+        """-> (B, 2 * D, H, W) BEV volume: vote density and density-normalised remission (ldm/dataset.py:280-294).  ordered: the
+        order-fixed splat of to_voxel_train(ordered=True) -- the same bits on every run, slower."""
+        if ordered:
+            return self.to_voxel_train(range_images, ordered=True)[0]
         x = self._images(range_images)
         B, Cc, W, H = x.shape
         D, GH, GW = self.grid_sizes
@@ -94,16 +97,22 @@ class point_cloud_to_range_image:
         return out
 
     # ---- to_voxel for training (vae_training.py: disc_bev, bev_rec_weight) ----------------------------------
-    def to_voxel_train(self, range_images):
+    def to_voxel_train(self, range_images, ordered=False):
         """`to_voxel` that keeps what its backward needs: -> (voxel, saved).  voxel holds the bits `to_voxel` returns; saved =
-        (the fp32 image, raw (B, 2 * D, H, W): the vote density d and the weighted remission sum S before the finalise step)."""
+        (the fp32 image, raw (B, 2 * D, H, W): the vote density d and the weighted remission sum S before the finalise step).
+        ordered: rldm_lidar_to_voxel_ordered instead of the atomic splat -- every cell the fp32 sum of its votes in ascending vote
+        id (to_voxel_ordered_host states it), so the result is the same on every run, for every batch size and batch position."""
         x = self._images(range_images)
         B, Cc, W, H = x.shape
         D, GH, GW = self.grid_sizes
         raw = torch.empty((B, 2 * D, GH, GW), dtype=torch.float32, device=x.device)
         out = torch.empty_like(raw)
-        _lib.check(_lib.lib().rldm_lidar_to_voxel_train(self._handle(), x.data_ptr(), B, Cc, W, raw.data_ptr(), out.data_ptr(),
-                                                        _lib.stream_ptr(x.device)), "rldm_lidar_to_voxel_train")
+        if ordered:
+            _lib.check(_lib.lib().rldm_lidar_to_voxel_ordered(self._handle(), x.data_ptr(), B, Cc, W, raw.data_ptr(), out.data_ptr(),
+                                                              _lib.stream_ptr(x.device)), "rldm_lidar_to_voxel_ordered")
+        else:
+            _lib.check(_lib.lib().rldm_lidar_to_voxel_train(self._handle(), x.data_ptr(), B, Cc, W, raw.data_ptr(), out.data_ptr(),
+                                                            _lib.stream_ptr(x.device)), "rldm_lidar_to_voxel_train")
         return out, (x, raw)
 
     def to_voxel_backward(self, saved, dvoxel):
@@ -210,6 +219,50 @@ class point_cloud_to_range_image:
         d, S = d.reshape(B, gz, gy, gx), S.reshape(B, gz, gy, gx)
         feat = S / d.clamp(min=1e-4)
         vox = torch.cat([torch.log(d + 1) if self.normalize_volume_densities else d, feat], 1)
+        return (vox, d, S) if return_raw else vox
+
+    def to_voxel_ordered_host(self, range_images, points=None, tables="library", return_raw=True):
+        """rldm_lidar_to_voxel_ordered stated in numpy fp32.  Geometry, in-grid tests and weights are _bev_geometry / _bev_votes in
+        fp32 (points, tables: see _bev_geometry; the device's own to_pc_torch output as points removes the log mode's exp2f from a
+        comparison).  A vote has the id v = n * 8 + (dx * 4 + dy * 2 + dz), n = w * H + h; it counts when its pixel touches the
+        volume, its corner lies inside the grid and w != 0.  Per image and cell, over the cell's counted votes in ascending v:
+        d = ((0 + w_1) + w_2) + ..., S the same over w * f -- np.cumsum on fp32, which adds left to right --, +0 in a cell without
+        votes.  Then the finalise step: S / max(d, 1e-4) and log(d + 1) or d (numpy's log, not the device's logf).
+        -> (voxel (B, 2 D, H, W), d (B, D, H, W), S) as fp32 numpy arrays, or voxel alone."""
+        x = torch.as_tensor(np.asarray(range_images.detach().cpu() if torch.is_tensor(range_images) else range_images, np.float32))
+        if x.dim() != 4 or x.shape[3] != self.H or x.shape[1] < 2:
+            raise ValueError(f"range_images must be (B, >= 2, W, {self.H}), got {tuple(x.shape)}")
+        if points is not None:
+            points = torch.as_tensor(np.asarray(points.detach().cpu() if torch.is_tensor(points) else points, np.float32))
+        B = x.shape[0]
+        geo = self._bev_geometry(x, points, tables)
+        gx, gy, gz = geo["grid"]
+        nvox = gx * gy * gz
+        f = geo["f"]
+        cell, counted, w, wf = [], [], [], []
+        for _, _, _, idx, ok, wx, wy, wz in self._bev_votes(geo):                        # (dx, dy, dz) in the kernel's loop order
+            wv = (wx * wy) * wz
+            cell.append(idx.reshape(B, -1))
+            counted.append((ok & (wv != 0)).reshape(B, -1))
+            w.append(wv.reshape(B, -1))
+            wf.append((wv * f).reshape(B, -1))
+        # (B, N, 8) flattened: position v = n * 8 + (dx * 4 + dy * 2 + dz)
+        cell, counted, w, wf = (torch.stack(t, 2).reshape(B, -1).numpy() for t in (cell, counted, w, wf))
+        d, S = np.zeros((B, nvox), np.float32), np.zeros((B, nvox), np.float32)
+        zero = np.zeros(1, np.float32)
+        for b in range(B):
+            v = np.flatnonzero(counted[b])                                                # ascending v
+            order = v[np.argsort(cell[b][v], kind="stable")]                              # by cell; within a cell still ascending v
+            cells, first = np.unique(cell[b][order], return_index=True)
+            for c, lo, hi in zip(cells, first, list(first[1:]) + [len(order)]):
+                seg = order[lo:hi]
+                d[b, c] = np.cumsum(np.concatenate([zero, w[b][seg]]), dtype=np.float32)[-1]
+                S[b, c] = np.cumsum(np.concatenate([zero, wf[b][seg]]), dtype=np.float32)[-1]
+        d, S = d.reshape(B, gz, gy, gx), S.reshape(B, gz, gy, gx)
+        with np.errstate(all="ignore"):
+            feat = S / np.maximum(d, np.float32(1e-4))
+            dens = np.log(d + np.float32(1)) if self.normalize_volume_densities else d
+        vox = np.concatenate([dens, feat], 1).astype(np.float32)
         return (vox, d, S) if return_raw else vox
 
     def to_voxel_backward_host(self, images, d_raw, S_raw, dvoxel, points=None, return_terms=False, tables="reference"):

@@ -4,7 +4,7 @@
                                      [--trainable decoder|all] [--kl-weight 1e-6]
                                      [--batch-size 8] [--lr 4.5e-6] [--mode] [--seed S] [--log-every K] [--deterministic]
                                      [--discriminator patchgan|metakernel --disc-start N --disc-weight 0.5 [--disc-state FILE]]
-                                     [--disc-bev] [--bev-rec-weight X] [--bev-grid D H W] [--bev-range x0 y0 z0 x1 y1 z1]
+                                     [--disc-bev] [--bev-rec-weight X] [--bev-ordered] [--bev-grid D H W] [--bev-range x0 y0 z0 x1 y1 z1]
 
 --trainable decoder (the default) leaves the encoder, and with it the latent space, as it is.  --trainable all trains encoder and
 decoder jointly with loss = L1 + kl_weight * kl and adds "kl" to every log line; it moves the latent space, so UNets trained on the old
@@ -19,7 +19,8 @@ MetaKernelDiscriminator).  Without the option the command prints and writes what
 --bev-rec-weight X adds the BEV density term of rangeldm_amd/vae_training.py to the loss and "bev_rec" (the unweighted sum of
 |V(target) - V(pred)| over the density planes) to every log line; --disc-bev (with --discriminator patchgan) hands the PatchGAN the BEV
 volume of the reconstruction instead of the range image.  The volume is --bev-grid / --bev-range (defaults: the reference's
-kitti360.yaml); the sensor follows the image height: 64 beams KITTI-360, 32 nuScenes.  Neither runs with --deterministic.
+kitti360.yaml); the sensor follows the image height: 64 beams KITTI-360, 32 nuScenes.  --bev-ordered forms every BEV volume with the
+order-fixed splat (bev_ordered=True: slower, the same bits on every run); --deterministic takes the BEV flags only together with it.
 
 --input holds the (2, W, H) .npy range images `evaluate vae --input` reads (batches walk the sorted files and wrap around); without
 it the run trains on the synthetic batch of `evaluate vae`.  Without --weights / --sgm-ckpt the synthetic weights of `evaluate vae`
@@ -59,6 +60,7 @@ def build_parser():
     ap.add_argument("--disc-state", default=None, metavar="FILE", help="a discriminator.pt to resume the discriminator from")
     ap.add_argument("--disc-bev", action="store_true", help="the PatchGAN judges the BEV volume of the reconstruction")
     ap.add_argument("--bev-rec-weight", type=float, default=0.0, metavar="X", help="weight of the BEV density L1 term (0: off)")
+    ap.add_argument("--bev-ordered", action="store_true", help="order-fixed BEV splat: bit-reproducible BEV terms (slower)")
     ap.add_argument("--bev-grid", type=int, nargs=3, default=[1, 512, 512], metavar=("D", "H", "W"), help="grid_sizes of the BEV volume")
     ap.add_argument("--bev-range", type=float, nargs=6, default=[-51.2, -51.2, -3.0, 51.2, 51.2, 1.0],
                     metavar=("x0", "y0", "z0", "x1", "y1", "z1"), help="pc_range of the BEV volume [m]")
@@ -82,8 +84,9 @@ def check_args(a):
         raise ValueError("--bev-rec-weight must not be negative")
     if a.disc_bev and a.discriminator != "patchgan":
         raise ValueError("--disc-bev goes with --discriminator patchgan (the Meta-Kernel discriminator needs a range image)")
-    if (a.disc_bev or a.bev_rec_weight > 0) and a.deterministic:
-        raise ValueError("--disc-bev / --bev-rec-weight do not run with --deterministic (the BEV splat sums with fp32 atomics)")
+    if (a.disc_bev or a.bev_rec_weight > 0) and a.deterministic and not a.bev_ordered:
+        raise ValueError("--disc-bev / --bev-rec-weight do not run with --deterministic (the BEV splat sums with fp32 atomics) "
+                         "unless --bev-ordered is given")
     if min(a.bev_grid) < 1 or any(a.bev_range[i + 3] <= a.bev_range[i] for i in range(3)):
         raise ValueError("--bev-grid must be positive and --bev-range must be x0 y0 z0 x1 y1 z1 with x0 < x1, y0 < y1, z0 < z1")
 
@@ -161,7 +164,7 @@ def main(argv=None):
         adv = dict(discriminator=disc, disc_start=a.disc_start, disc_weight=a.disc_weight)
     if a.disc_bev or a.bev_rec_weight > 0:
         adv.update(bev=bev_sensor(cfg.sample_size[1], cfg.sample_size[0], a.bev_grid, a.bev_range), bev_rec_weight=a.bev_rec_weight,
-                   disc_bev=a.disc_bev)
+                   disc_bev=a.disc_bev, bev_ordered=a.bev_ordered)
     if everything:
         trainer = VAETrainer(cfg, sd, device=dev, lr=a.lr, kl_weight=a.kl_weight, deterministic=a.deterministic, **adv)
     else:

@@ -32,11 +32,15 @@ in two launches without atomics (rangeldm_amd/csrc/lidar.hip).  The target's vol
   disc_bev=True        the PatchGAN judges V(pred), all 2 gz planes (a MetaKernelDiscriminator is refused: its range guidance needs a
                        range image); its input gradient returns through to_voxel_backward, and its own step sees (V(target), V(pred)).
 SECOND DEVIATION: the reference reassigns `inputs` and `reconstructions` to the volumes once bev_rec_weight > 0, so its discriminator
-then sees volumes whatever `disc_bev` says; here the two switches are independent -- pass both to reproduce the reference.  Neither
-runs with deterministic=True (NotImplementedError): the forward splat sums its votes with fp32 atomics.
+then sees volumes whatever `disc_bev` says; here the two switches are independent -- pass both to reproduce the reference.
+  bev_ordered=True     every BEV volume of the step -- V(pred), V(target), and with them what the discriminator's own step sees -- comes
+                       from the order-fixed splat (to_voxel_train(ordered=True), rldm_lidar_to_voxel_ordered: the votes sorted by cell,
+                       each cell summed in ascending vote id), slower than the atomic one and the same bits on every run.  With it the
+                       BEV terms run under deterministic=True; without it they refuse there (NotImplementedError): the default splat
+                       sums its votes with fp32 atomics.  Allowed with deterministic=False (an ordered splat inside an otherwise
+                       unordered step); never read when no BEV term is on.
 
-Not built: variant 2 of the Meta-Kernel discriminator and its `log=True` range mapping, an order-fixed (bit-reproducible) BEV splat, the
-vanilla GAN loss, a trainable `logvar` of the loss (it stays at its initial 0, the reference's `learn_logvar: False`), the perceptual
+Not built: variant 2 of the Meta-Kernel discriminator and its `log=True` range mapping, the vanilla GAN loss, a trainable `logvar` of the loss (it stays at its initial 0, the reference's `learn_logvar: False`), the perceptual
 terms (`bev_perceptual` among them), EMA, a captured step graph, gradient exchange between ranks.  No torch autograd, no torch compute
 ops on the path; no CPU fallback.
 
@@ -123,10 +127,10 @@ class _VAETape(TapeTrainer):
     state."""
 
     def _init_vae(self, config, state_dict, names, no_dx, *, device, lr, betas, eps, weight_decay, max_grad_norm, channel_weights,
-                  deterministic, discriminator, disc_start, disc_weight, disc_factor, bev, bev_rec_weight, disc_bev):
+                  deterministic, discriminator, disc_start, disc_weight, disc_factor, bev, bev_rec_weight, disc_bev, bev_ordered):
         """names(cfg, shapes): the trained parameters in tape order; no_dx: TapeTrainer's; the rest: the options both public
         constructors share, under their names there (the defaults stand in those signatures alone)."""
-        self._init_bev(bev, bev_rec_weight, disc_bev, deterministic, discriminator)
+        self._init_bev(bev, bev_rec_weight, disc_bev, deterministic, discriminator, bev_ordered)
         self.cfg = config if isinstance(config, VAEConfig) else VAEConfig(**config)
         if len(channel_weights) != self.cfg.out_channels:
             raise ValueError(f"{len(channel_weights)} channel weights for {self.cfg.out_channels} output channels")
@@ -146,9 +150,10 @@ class _VAETape(TapeTrainer):
         if self.bev is not None and (self.disc_bev or self.bev_rec_weight > 0) and int(self.bev.H) != int(self.cfg.sample_size[1]):
             raise ValueError(f"bev is a {self.bev.H}-beam sensor, the VAE's images have H = {self.cfg.sample_size[1]}")
 
-    def _init_bev(self, bev, bev_rec_weight, disc_bev, deterministic, discriminator):
+    def _init_bev(self, bev, bev_rec_weight, disc_bev, deterministic, discriminator, bev_ordered):
         """The BEV switches and their refusals (module docstring); with the defaults nothing here is ever read again."""
         self.bev, self.bev_rec_weight, self.disc_bev = bev, float(bev_rec_weight), bool(disc_bev)
+        self.bev_ordered = bool(bev_ordered)
         self.last_bev_rec = None
         if self.bev_rec_weight < 0:
             raise ValueError("bev_rec_weight must not be negative")
@@ -156,9 +161,9 @@ class _VAETape(TapeTrainer):
             return
         if bev is None:
             raise ValueError("disc_bev / bev_rec_weight need bev=, a point_cloud_to_range_image of the images' sensor")
-        if deterministic:
+        if deterministic and not self.bev_ordered:
             raise NotImplementedError("the BEV terms are not bit-reproducible: to_voxel's splat sums its votes with fp32 atomics "
-                                      "(an order-fixed splat is not built)")
+                                      "(pass bev_ordered=True for the order-fixed splat)")
         gz = int(bev.grid_sizes[0])
         if self.bev_rec_weight > 0 and gz > 16:
             raise ValueError(f"bev_rec_weight: rldm_train_l1 takes at most 16 density planes, the grid has {gz}")
@@ -223,8 +228,8 @@ class _VAETape(TapeTrainer):
 
     def _bev_volumes(self, pred, target_nchw):
         """-> (V(target): the inference to_voxel, no gradient; V(pred), saved: to_voxel_train of the reconstruction)."""
-        vt = self.bev.to_voxel(target_nchw)
-        vp, saved = self.bev.to_voxel_train(T.unpack_output(pred))
+        vt = self.bev.to_voxel(target_nchw, ordered=self.bev_ordered)
+        vp, saved = self.bev.to_voxel_train(T.unpack_output(pred), ordered=self.bev_ordered)
         return vt, vp, saved
 
     def _bev_rec(self, dpred, volumes):
@@ -308,7 +313,7 @@ class _VAETape(TapeTrainer):
 class VAEDecoderTrainer(_VAETape):
     def __init__(self, config, state_dict, device="cuda", lr=4.5e-6, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  max_grad_norm=None, channel_weights=(40.0, 10.0), deterministic=False, discriminator=None, disc_start=0,
-                 disc_weight=0.5, disc_factor=1.0, bev=None, bev_rec_weight=0.0, disc_bev=False):
+                 disc_weight=0.5, disc_factor=1.0, bev=None, bev_rec_weight=0.0, disc_bev=False, bev_ordered=False):
         """The defaults are the reference's: torch.optim.Adam (AdamW with zero decay is Adam) at base_learning_rate 4.5e-6, no
         clipping, range_weight 40 / intensity_weight 10.  state_dict may hold the whole VAE: the encoder's tensors are kept as
         they are (handed on by load_into / save_pretrained), never read by a kernel of this class.
@@ -317,11 +322,11 @@ class VAEDecoderTrainer(_VAETape):
         discriminator: a discriminator.PatchDiscriminator or a metakernel.MetaKernelDiscriminator; from step disc_start on train_step
         runs the adversarial phase (module docstring) with disc_weight / disc_factor, the reference's names.  None, or before
         disc_start: the step is exactly what it is without one, and the discriminator is not run.
-        bev, bev_rec_weight, disc_bev: the BEV terms (module docstring); with the defaults no code of theirs runs."""
+        bev, bev_rec_weight, disc_bev, bev_ordered: the BEV terms (module docstring); with the defaults no code of theirs runs."""
         self._init_vae(config, state_dict, decoder_param_names, ("decoder.conv_in.weight",), device=device, lr=lr, betas=betas, eps=eps,
                        weight_decay=weight_decay, max_grad_norm=max_grad_norm, channel_weights=channel_weights,
                        deterministic=deterministic, discriminator=discriminator, disc_start=disc_start, disc_weight=disc_weight,
-                       disc_factor=disc_factor, bev=bev, bev_rec_weight=bev_rec_weight, disc_bev=disc_bev)
+                       disc_factor=disc_factor, bev=bev, bev_rec_weight=bev_rec_weight, disc_bev=disc_bev, bev_ordered=bev_ordered)
 
     def forward(self, z_nchw):
         """z (B, z_channels, W / f, H / f) fp32 on the device, as the encoder emits it (not multiplied by scaling_factor)
@@ -359,17 +364,17 @@ class VAEDecoderTrainer(_VAETape):
 class VAETrainer(_VAETape):
     def __init__(self, config, state_dict, device="cuda", lr=4.5e-6, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
                  max_grad_norm=None, kl_weight=1e-6, channel_weights=(40.0, 10.0), deterministic=False, discriminator=None,
-                 disc_start=0, disc_weight=0.5, disc_factor=1.0, bev=None, bev_rec_weight=0.0, disc_bev=False):
+                 disc_start=0, disc_weight=0.5, disc_factor=1.0, bev=None, bev_rec_weight=0.0, disc_bev=False, bev_ordered=False):
         """Encoder and decoder trained jointly; the defaults are the reference's (VAEDecoderTrainer's, and kl_loss: 1e-6).  The
         parameters are every key of vae_param_shapes in tape order: the encoder as oracle.vae.vae_encode visits it, then the
         decoder.  Training the encoder moves the latent space: UNets trained on the old latents no longer apply, and scaling_factor
         must be estimated again (module docstring).  deterministic, discriminator, disc_start, disc_weight, disc_factor, bev,
-        bev_rec_weight, disc_bev: as VAEDecoderTrainer."""
+        bev_rec_weight, disc_bev, bev_ordered: as VAEDecoderTrainer."""
         self._init_vae(config, state_dict, lambda cfg, shapes: encoder_param_names(cfg, shapes) + decoder_param_names(cfg, shapes),
                        ("encoder.conv_in.weight",), device=device, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                        max_grad_norm=max_grad_norm, channel_weights=channel_weights, deterministic=deterministic,
                        discriminator=discriminator, disc_start=disc_start, disc_weight=disc_weight, disc_factor=disc_factor, bev=bev,
-                       bev_rec_weight=bev_rec_weight, disc_bev=disc_bev)
+                       bev_rec_weight=bev_rec_weight, disc_bev=disc_bev, bev_ordered=bev_ordered)
         self.kl_weight = float(kl_weight)
         self.last_kl = None
         self._moments = self._z = None

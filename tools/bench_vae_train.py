@@ -5,6 +5,7 @@ eager launches (no captured step graph exists for this trainer).
 
     python tools/bench_vae_train.py [--batch 8] [--steps 10] [--warmup 3] [--repeats 5] [--no-unet] [--deterministic]
                                     [--trainable decoder|all] [--discriminator [patchgan|metakernel]] [--disc-bev] [--bev-rec-weight X]
+                                    [--bev-ordered]
 
 After the warm-up, --repeats timed runs of --steps steps each (a host clock around work that ends in a device synchronise): median
 [min, max].  Achieved TFLOP/s counts 3 x AutoencoderKLHIP.decode_flops (decoder forward + backward; the encode is not counted).  In the
@@ -17,7 +18,9 @@ generator term, adaptive weight, mixed backward, the PatchGAN's own hinge step -
 reports its ratio to the plain step.  --discriminator metakernel times, beside those, the same step against the Meta-Kernel
 discriminator (rangeldm_amd/metakernel.py; `vae_decoder_meta` / `vae_all_meta`), all in the same interleaved run.  --disc-bev and / or
 --bev-rec-weight X (with --discriminator) time, beside those, the PatchGAN step with the BEV terms of vae_training.py on the KITTI-360
-sensor and the reference's [1, 512, 512] volume over +-51.2 m (`vae_decoder_bev` / `vae_all_bev`).  One JSON line."""
+sensor and the reference's [1, 512, 512] volume over +-51.2 m (`vae_decoder_bev` / `vae_all_bev`); with --bev-ordered those trainers
+form their volumes with the order-fixed splat (bev_ordered=True) and, under --deterministic, run deterministically like the others
+(without it the BEV trainers stay in the default mode: the atomic splat refuses deterministic=True).  One JSON line."""
 import argparse
 import json
 import os
@@ -47,6 +50,7 @@ def main():
                     help="also time the adversarial step (disc_start = 0) against the PatchGAN; metakernel: and against the Meta-Kernel one")
     ap.add_argument("--disc-bev", action="store_true", help="also time the PatchGAN step on the BEV volume of the reconstruction")
     ap.add_argument("--bev-rec-weight", type=float, default=0.0, metavar="X", help="also time the step with the BEV density L1 term")
+    ap.add_argument("--bev-ordered", action="store_true", help="the BEV trainers use the order-fixed splat (and follow --deterministic)")
     ap.add_argument("--seed", type=int, default=20240310)
     a = ap.parse_args()
     if (a.disc_bev or a.bev_rec_weight > 0) and not a.discriminator:
@@ -131,7 +135,9 @@ def main():
         from rangeldm_amd.range_image import point_cloud_to_range_image_KITTI
 
         def bev_kw():
-            return dict(discriminator=PatchDiscriminator(seed=a.seed, device=dev),
+            det = bool(a.deterministic and a.bev_ordered)
+            return dict(discriminator=PatchDiscriminator(seed=a.seed, device=dev, deterministic=det), deterministic=det,
+                        bev_ordered=a.bev_ordered,
                         bev=point_cloud_to_range_image_KITTI(width=W, grid_sizes=[1, 512, 512], pc_range=[-51.2, -51.2, -3., 51.2, 51.2, 1.]),
                         bev_rec_weight=a.bev_rec_weight, disc_bev=a.disc_bev)
         tr_bev = VAEDecoderTrainer(cfg, sd, device=dev, **bev_kw())
@@ -204,7 +210,8 @@ def main():
             t = tri(sps[name])
             kind = "Meta-Kernel" if name.endswith("_meta") else "PatchGAN"
             if name.endswith("_bev"):
-                kind = f"PatchGAN, disc_bev {bool(a.disc_bev)}, bev_rec_weight {a.bev_rec_weight:g}, BEV 512 x 512;"
+                kind = (f"PatchGAN, disc_bev {bool(a.disc_bev)}, bev_rec_weight {a.bev_rec_weight:g}, BEV 512 x 512"
+                        f"{', ordered splat' if a.bev_ordered else ''};")
             out[name] = {"metric": f"adversarial step samples/sec ({kind} ndf 64, disc_start 0), same run", "value": t["median"],
                          "samples_per_sec": t, "ms_per_step": 1e3 * B / t["median"],
                          "time_ratio_to_plain": float(np.median(sps[plain]) / t["median"])}
