@@ -652,7 +652,7 @@ int rldm_range_errors(const float* a, const float* b, int B, int C, int W, int H
  * fp32 (B, C, W, Hs) -> dst device fp32 (B, C, W, Hs * rate) along the beam (last) axis. */
 int rldm_beam_upsample(const float* src, int B, int C, int W, int Hs, int rate, int mode, float* dst, void* stream);
 
-/* ---- UNet training step (rangeldm_amd/csrc/train.hip; ldm/train_unconditional.py:466-558) ----
+/* ---- UNet training step (rangeldm_amd/csrc/train*.hip, mapped in DESIGN.md 3; ldm/train_unconditional.py:466-558) ----
  * Op-level entry points driven by rangeldm_amd/training.py (the autograd tape is host-side).  Every tensor is device
  * fp32, activations / gradients channels-last [B][W][H][C] (W wraps, H zero-pads); GEMM operands are rounded to bf16 into
  * the MFMA with fp32 accumulation (the reference's `mixed_precision: bf16`). */

@@ -6,16 +6,15 @@
 //   - LeakyReLU(0.2), the hinge loss, the generator term, the adaptive weight + gradient mix.
 // Nothing here keeps state or scratch of its own: workspaces are the caller's.  The element-wise arithmetic is restated expression by
 // expression on the host (discriminator.batchnorm_host, hinge_d_loss_host): this file is compiled without FMA contraction.
-#include "common.h"
-#include "../../include/rangeldm_hip.h"
+#include "train_common.h"
 
 #include <algorithm>
 #include <cstdint>
 #include <string>
 
-namespace {
+using namespace rldm::train;
 
-inline unsigned nblk(size_t n) { return (unsigned)((n + 255) / 256); }
+namespace {
 
 // ---- 4x4 convolution: forward and data gradient --------------------------------------------------------------------------------
 // One gather kernel.  The produced tensor is [B][Wo][Ho][N], the gathered one [B][Wi][Hi][K]; w = bf16 [N][16][Kpad], tap t = 4 i + j.
@@ -29,7 +28,7 @@ struct DcConv {
     int B, Wi, Hi, K, Kpad, Wo, Ho, N, mode, stride;
 };
 
-// D[channel][pixel]: lane (pixel l & 31, half l >> 5) holds channels (r & 3) + 8 (r >> 2) + 4 half of its pixel (train.hip:
+// D[channel][pixel]: lane (pixel l & 31, half l >> 5) holds channels (r & 3) + 8 (r >> 2) + 4 half of its pixel (train_conv.hip:
 // tr_conv_kernel).  A workgroup owns 32 pixels x 64 channels; its four waves split the TAPS (wave v: taps [v T / 4, (v + 1) T / 4) in
 // order, all of K under each) and meet in LDS, where wave 0 adds ((w0 + w1) + w2) + w3: at the discriminator's sizes a launch has a few
 // hundred tiles, and a wave that walked all sixteen taps alone (the first form of this kernel: 64 x 128 tiles, one workgroup per CU)
@@ -334,30 +333,7 @@ __global__ __launch_bounds__(256) void dc_lrelu_kernel(const float* __restrict__
 }
 
 // ---- losses -----------------------------------------------------------------------------------------------------------------------
-// train.hip's block_sum_d: lanes l and l ^ 32, ^ 16 .. ^ 1, then the four waves in order
-__device__ inline double dc_block_sum_d(double v, double* sh) {
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < 4; ++w) t += sh[w];
-    return t;
-}
-
-__global__ __launch_bounds__(256) void dc_zero_d_kernel(double* __restrict__ p, int n) {
-    if ((int)threadIdx.x < n) p[threadIdx.x] = 0.0;
-}
-
-// thread t adds part[t], part[t + 256], ... in that order, then the tree; one block (train.hip: tr_fold_double_kernel)
-__global__ __launch_bounds__(256) void dc_fold_double_kernel(const double* __restrict__ part, int n, double* __restrict__ out) {
-    __shared__ double sh[4];
-    double a = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) a += part[i];
-    a = dc_block_sum_d(a, sh);
-    if (threadIdx.x == 0) *out = a;
-}
-
+// (block partials through train_common.h's block_sum_d, folded by sums_begin / sums_end: pure fp64 adds)
 template <bool DET>
 __global__ __launch_bounds__(256) void dc_hinge_kernel(const float* __restrict__ real, const float* __restrict__ fake, size_t n, float factor,
                                                        float* __restrict__ dreal, float* __restrict__ dfake, double* __restrict__ out,
@@ -375,7 +351,7 @@ __global__ __launch_bounds__(256) void dc_hinge_kernel(const float* __restrict__
         v[2] = (double)f / (double)n;
     }
     for (int k = 0; k < 3; ++k) {
-        const double s = dc_block_sum_d(v[k], sh);
+        const double s = block_sum_d(v[k], sh);
         if (threadIdx.x == 0) {
             if constexpr (DET) out[(size_t)k * nparts + blockIdx.x] = s;
             else unsafeAtomicAdd(out + k, s);
@@ -393,7 +369,7 @@ __global__ __launch_bounds__(256) void dc_generator_kernel(const float* __restri
         dfake[i] = (float)(-1.0 / (double)n);
         v = -(double)fake[i] / (double)n;
     }
-    v = dc_block_sum_d(v, sh);
+    v = block_sum_d(v, sh);
     if (threadIdx.x == 0) {
         if constexpr (DET) out[blockIdx.x] = v;
         else unsafeAtomicAdd(out, v);
@@ -435,8 +411,6 @@ inline void dc_wgrad_plan(const rldm_train_disc_conv_desc* d, const DcShape& s, 
 
 }  // namespace
 
-#define DC_LAUNCH_CHECK() RLDM_HIP_CHECK(hipGetLastError())
-
 extern "C" {
 
 int rldm_train_disc_conv_ok(const rldm_train_disc_conv_desc* d) {
@@ -454,7 +428,7 @@ int rldm_train_disc_conv(const rldm_train_disc_conv_desc* d, const float* x, con
     const dim3 grid(((unsigned)(d->B * s.Wo * s.Ho) + 31) / 32, ((unsigned)d->N + 63) / 64, 1);
     if (d->Cin % 16 == 0) dc_conv_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(p);
     else dc_conv_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(p);
-    DC_LAUNCH_CHECK();
+    TR_LAUNCH_CHECK();
     return 0;
 }
 
@@ -469,7 +443,7 @@ int rldm_train_disc_conv_dgrad(const rldm_train_disc_conv_desc* d, const float* 
     const dim3 grid((P + 31) / 32, ((unsigned)d->Cin + 63) / 64, d->stride == 2 ? 4 : 1);
     if (d->N % 16 == 0) dc_conv_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(p);
     else dc_conv_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(p);
-    DC_LAUNCH_CHECK();
+    TR_LAUNCH_CHECK();
     return 0;
 }
 
@@ -497,7 +471,7 @@ int rldm_train_disc_wgrad(const rldm_train_disc_conv_desc* d, const float* dy, c
     const dim3 grid((unsigned)(((d->N + 63) / 64) * ((d->Cin + 63) / 64)), 16, (unsigned)slices);
     dc_wgrad_kernel<<<grid, 256, 0, st>>>(p);
     if (slices > 1) dc_wgrad_reduce_kernel<<<nblk(n), 256, 0, st>>>(static_cast<const float*>(workspace), slices, n, dw);
-    DC_LAUNCH_CHECK();
+    TR_LAUNCH_CHECK();
     if (dbias) return rldm_train_colsum(dy, d->B, s.Wo * s.Ho, d->N, nullptr, 0, 0, dbias, stream);
     return 0;
 }
@@ -528,7 +502,7 @@ int rldm_train_disc_bn_forward(const float* x, int64_t M, int C, const float* ga
         dc_bn_eval_stats_kernel<<<nblk((size_t)C), 256, 0, st>>>(running_mean, running_var, C, save);
     }
     dc_bn_apply_fwd_kernel<<<nblk((size_t)M * C), 256, 0, st>>>(x, save, gamma, beta, (size_t)M * C, C, y);
-    DC_LAUNCH_CHECK();
+    TR_LAUNCH_CHECK();
     return 0;
 }
 
@@ -546,14 +520,14 @@ int rldm_train_disc_bn_backward(const float* x, const float* dy, const float* sa
     dc_bn_partial_kernel<true><<<dim3(((unsigned)C + 63) / 64, (unsigned)S), 256, 0, st>>>(x, dy, save, gamma, beta, M, C, part);
     dc_bn_finish_bwd_kernel<<<nblk((size_t)C), 256, 0, st>>>(part, S, M, C, coef, dgamma, dbeta);
     dc_bn_apply_bwd_kernel<<<nblk((size_t)M * C), 256, 0, st>>>(x, dy, save, gamma, beta, coef, (size_t)M * C, C, dx);
-    DC_LAUNCH_CHECK();
+    TR_LAUNCH_CHECK();
     return 0;
 }
 
 int rldm_train_disc_lrelu(const float* x, const float* dy, float* y, int64_t n, int backward, void* stream) {
     RLDM_REQUIRE(x && y && n >= 0 && (!backward || dy), "null argument");
     if (n) dc_lrelu_kernel<<<nblk((size_t)n), 256, 0, (hipStream_t)stream>>>(x, dy, y, (size_t)n, backward);
-    DC_LAUNCH_CHECK();
+    TR_LAUNCH_CHECK();
     return 0;
 }
 
@@ -562,32 +536,26 @@ int rldm_train_disc_hinge(const float* real, const float* fake, int64_t n, float
     RLDM_REQUIRE(real && fake && dreal && dfake && out && n >= 1, "null argument");
     hipStream_t st = (hipStream_t)stream;
     const unsigned nparts = nblk((size_t)n);
-    if (rldm_train_deterministic_enabled()) {
-        RLDM_REQUIRE(partials, "rldm_train_disc_hinge: the deterministic mode needs the partials buffer");
-        dc_hinge_kernel<true><<<nparts, 256, 0, st>>>(real, fake, (size_t)n, factor, dreal, dfake, partials, nparts);
-        for (int k = 0; k < 3; ++k) dc_fold_double_kernel<<<1, 256, 0, st>>>(partials + (size_t)k * nparts, (int)nparts, out + k);
-    } else {
-        dc_zero_d_kernel<<<1, 256, 0, st>>>(out, 3);
-        dc_hinge_kernel<false><<<nparts, 256, 0, st>>>(real, fake, (size_t)n, factor, dreal, dfake, out, nparts);
-    }
-    DC_LAUNCH_CHECK();
-    return 0;
+    const bool det = deterministic();
+    RLDM_REQUIRE(!det || partials, "rldm_train_disc_hinge: the deterministic mode needs the partials buffer");
+    double* dst = nullptr;
+    if (sums_begin(det, 3, nparts, out, partials, st, &dst)) return 1;
+    if (det) dc_hinge_kernel<true><<<nparts, 256, 0, st>>>(real, fake, (size_t)n, factor, dreal, dfake, dst, nparts);
+    else dc_hinge_kernel<false><<<nparts, 256, 0, st>>>(real, fake, (size_t)n, factor, dreal, dfake, dst, nparts);
+    return sums_end(det, 3, nparts, dst, out, st);
 }
 
 int rldm_train_disc_generator(const float* fake, int64_t n, float* dfake, double* out, double* partials, void* stream) {
     RLDM_REQUIRE(fake && dfake && out && n >= 1, "null argument");
     hipStream_t st = (hipStream_t)stream;
     const unsigned nparts = nblk((size_t)n);
-    if (rldm_train_deterministic_enabled()) {
-        RLDM_REQUIRE(partials, "rldm_train_disc_generator: the deterministic mode needs the partials buffer");
-        dc_generator_kernel<true><<<nparts, 256, 0, st>>>(fake, (size_t)n, dfake, partials);
-        dc_fold_double_kernel<<<1, 256, 0, st>>>(partials, (int)nparts, out);
-    } else {
-        dc_zero_d_kernel<<<1, 256, 0, st>>>(out, 1);
-        dc_generator_kernel<false><<<nparts, 256, 0, st>>>(fake, (size_t)n, dfake, out);
-    }
-    DC_LAUNCH_CHECK();
-    return 0;
+    const bool det = deterministic();
+    RLDM_REQUIRE(!det || partials, "rldm_train_disc_generator: the deterministic mode needs the partials buffer");
+    double* dst = nullptr;
+    if (sums_begin(det, 1, nparts, out, partials, st, &dst)) return 1;
+    if (det) dc_generator_kernel<true><<<nparts, 256, 0, st>>>(fake, (size_t)n, dfake, dst);
+    else dc_generator_kernel<false><<<nparts, 256, 0, st>>>(fake, (size_t)n, dfake, dst);
+    return sums_end(det, 1, nparts, dst, out, st);
 }
 
 int rldm_train_disc_adaptive_mix(const float* dnll, const float* dg, const double* sq_nll, const double* sq_g, float disc_weight,
@@ -595,7 +563,7 @@ int rldm_train_disc_adaptive_mix(const float* dnll, const float* dg, const doubl
     RLDM_REQUIRE(dnll && dg && sq_nll && sq_g && dpred && d_weight && n >= 1, "null argument");
     dc_adaptive_mix_kernel<<<nblk((size_t)n), 256, 0, (hipStream_t)stream>>>(dnll, dg, sq_nll, sq_g, disc_weight, disc_factor, dpred,
                                                                              d_weight, (size_t)n);
-    DC_LAUNCH_CHECK();
+    TR_LAUNCH_CHECK();
     return 0;
 }
 

@@ -1,4 +1,4 @@
-"""Thin wrappers over the op-level training entry points of librangeldm_hip (rangeldm_amd/csrc/train.hip).
+"""Thin wrappers over the op-level training entry points of librangeldm_hip (rangeldm_amd/csrc/train*.hip: DESIGN.md 3 maps them).
 
 Tensors are device fp32, activations / gradients channels-last (B, W, H, C).  torch is used for allocation and streams
 only; every arithmetic operation below is a HIP kernel behind the C ABI.  No CPU fallback.
@@ -571,7 +571,7 @@ def colsum_host(dy, rows=None, total=None):
 
 
 def _block_sum(a):
-    """block_sum_d of train.hip: a (n, 256) fp64 -> (n,): per 64-lane wave a binary tree (lane l with l ^ 32, then ^ 16 .. ^ 1), then the
+    """block_sum_d of train_common.h: a (n, 256) fp64 -> (n,): per 64-lane wave a binary tree (lane l with l ^ 32, then ^ 16 .. ^ 1), then the
     four waves added in order from 0."""
     v = a.reshape(a.shape[0], 4, 64)
     o = 32

@@ -2,7 +2,7 @@
 
 `UNetTrainer` (on `TapeTrainer`, tape.py: the tape helpers every tape trainer shares, over `FlatParameters`' flat fp32 buffers --
 parameters, gradients, AdamW moments, EMA copy; state-dict views into them -- and its training state) drives the op-level HIP kernels of
-rangeldm_amd/csrc/train.hip through a host-side tape: `forward` records one backward closure per op (conv / linear, GroupNorm(+SiLU), head_dim-8 attention, concat, nearest-x2, stride-2), `backward` replays
+rangeldm_amd/csrc/train*.hip through a host-side tape: `forward` records one backward closure per op (conv / linear, GroupNorm(+SiLU), head_dim-8 attention, concat, nearest-x2, stride-2), `backward` replays
 them in reverse.  Data parallelism = one process per GPU; gradients are averaged with RCCL all-reduce over a few large
 buckets of the flat gradient buffer, each launched as soon as backward has finished the bucket's parameters
 (bucket boundaries: rangeldm_amd.training.plan_buckets).  No torch autograd, no torch compute ops on the path (torch

@@ -10,7 +10,7 @@ captured sampler stays valid.
 reference's `regularization_weights: {kl_loss: 1e-6}`.  TRAINING THE ENCODER MOVES THE LATENT SPACE: a UNet trained on the old
 latents no longer applies to the new VAE, and `scaling_factor` (1 / std of the latents) must be estimated again before one is trained.
 
-Both sit on `TapeTrainer` (tape.py) and drive the op-level HIP kernels of rangeldm_amd/csrc/train.hip through the same host-side tape as
+Both sit on `TapeTrainer` (tape.py) and drive the op-level HIP kernels of rangeldm_amd/csrc/train*.hip through the same host-side tape as
 `UNetTrainer`: 3x3 / 1x1 stride-1 convs, nearest x2 + conv, the encoder's end-padded stride-2 conv (train_ops.conv_desc, pad = 1),
 GroupNorm + SiLU, residual adds; the posterior is rldm_train_gaussian, the loss rldm_train_l1.
 

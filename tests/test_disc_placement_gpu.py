@@ -1,5 +1,5 @@
 """GPU: the discriminators' and the BEV terms' training kernels (rangeldm_amd/csrc/train_disc.hip, train_meta.hip, lidar.hip's
-to_voxel_train / to_voxel_backward, and train.hip's colsum and pack_weights as the discriminators call them) on operands placed as
+to_voxel_train / to_voxel_backward, and train_wgrad.hip's colsum and train.hip's pack_weights as the discriminators call them) on operands placed as
 PatchDiscriminator and MetaKernelDiscriminator place them.
 
 tests/test_train_placement_gpu.py's observation, for the kernels added since: a test that gives every operand its own torch tensor

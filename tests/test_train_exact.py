@@ -1,4 +1,4 @@
-"""GPU, bit-exact: the training conv / weight-gradient kernels (rangeldm_amd/csrc/train.hip) on integer-grid operands.
+"""GPU, bit-exact: the training conv / weight-gradient kernels (rangeldm_amd/csrc/train_conv.hip, train_wgrad.hip) on integer-grid operands.
 
 Activations and gradients are integers in [-3, 3], weights {-4 .. 4} * 2^-5, bias / row / residual on the 2^-5 grid: every product and
 every sum is exact in fp32 in any order (asserted per case), so the fp32 outputs -- conv, data gradient, weight gradient, column sums

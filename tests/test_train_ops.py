@@ -1,4 +1,4 @@
-"""GPU: the op-level training kernels (rangeldm_amd/csrc/train.hip) against torch fp32 autograd of
+"""GPU: the op-level training kernels (rangeldm_amd/csrc/train.hip, train_conv.hip, train_wgrad.hip, train_norm.hip) against torch fp32 autograd of
 the oracle's leaf ops (oracle/ops.py: circular-W / zero-H conv, GroupNorm + SiLU, head_dim-8 attention).
 
 Tolerances: GEMM operands are rounded to bf16 (8 mantissa bits) with fp32 accumulation, so conv / linear results and

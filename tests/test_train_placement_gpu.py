@@ -1,4 +1,4 @@
-"""GPU: the training kernels (rangeldm_amd/csrc/train.hip, train_attn.hip) on operands placed as the trainers place them.
+"""GPU: the training kernels (rangeldm_amd/csrc/train.hip, train_conv.hip, train_wgrad.hip, train_norm.hip, train_attn.hip) on operands placed as the trainers place them.
 
 Every other kernel test allocates each operand as its own torch tensor.  The trainers do not: parameters and gradients are views of flat
 buffers packed end to end (FlatParameters._init_parameters), split-K outputs are slices of one pre-zeroed arena (ZeroArena.take), and the
@@ -47,7 +47,7 @@ arena are 16-byte aligned).
 
 What the read-through of the flat-buffer operands found (one line per operand class; "scalar" = 4-byte accesses only).  FIXED = the
 cast to a 16-byte type, which claims an alignment these views do not promise, is replaced by four element accesses (tr_load4 /
-tr_store4 in train.hip: alignment 4; the compiler may still merge them where the target takes a 16-byte access at 4-byte alignment):
+tr_store4 in train_common.h: alignment 4; the compiler may still merge them where the target takes a 16-byte access at 4-byte alignment):
   bias     16-byte loads in tr_tile_epilogue, the register epilogue of tr_conv_lds_kernel and tr_conv_halo_kernel: FIXED;
            tr_conv_kernel, the split-K epilogue and tr_linear_rows_kernel: scalar
   gamma,   16-byte loads in tr_gn_fwd_fused_vec_kernel, tr_gn_fwd_vec_kernel and tr_gn_bwd_apply_vec_kernel: FIXED;
@@ -62,7 +62,7 @@ tr_store4 in train.hip: alignment 4; the compiler may still merge them where the
   dbeta    tr_gn_bwd_apply2_kernel: scalar
   weights  (fp32 masters read by the pack kernels) tr_pack_tile_fast's 16-byte loads are already chosen from `param_offset & 3`; the
            element-wise kernels are scalar
-  Nothing else in train.hip looks at a pointer's alignment except rldm_train_l1 (pred / dpred, activations).
+  Nothing else in these files looks at a pointer's alignment except rldm_train_l1 (pred / dpred, activations).
 
 Ops on integer grids (tests/test_train_exact.py's operands and bounds) must EQUAL the fp64 reference; the others are compared with the
 same call on plain torch allocations -- bit for bit in the deterministic mode and wherever the default route has no floating-point

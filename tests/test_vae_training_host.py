@@ -25,7 +25,7 @@ def _data(B, Cc, W, H, seed):
 
 
 def _tree(v):
-    """A 256-value block added as train.hip's block_sum_d adds it, one scalar operation at a time: per 64-lane wave lane l with
+    """A 256-value block added as train_common.h's block_sum_d adds it, one scalar operation at a time: per 64-lane wave lane l with
     l ^ 32, then ^ 16 .. ^ 1; then the four waves in order from 0."""
     assert len(v) == 256
     acc = np.float64(0.0)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time single training ops (rangeldm_amd/csrc/train.hip) at the RangeLDM level shapes, batch 8: conv forward (= data
+"""Time single training ops (rangeldm_amd/csrc/train_conv.hip, train_wgrad.hip, train_attn.hip) at the RangeLDM level shapes, batch 8: conv forward (= data
 gradient), weight gradient, attention forward / backward.  One JSON line per case with TFLOP/s."""
 import json
 import os
