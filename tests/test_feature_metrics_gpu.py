@@ -9,6 +9,13 @@ neighbour, and the small alphabets make squared distances that EQUAL a radius co
 before it looks at the device), so the strict `<` and the ties are exercised.  For the kernel, d = 64 and entries in
 -2 .. 2 make t = g / 64 + 1 = m / 64 with |m| <= 320 and t^3 = m^3 / 2^18 exact, and sums of a few thousand of those too.
 
+Tiles per chunk.  A column chunk is one tile of 64 columns for every n_b <= 1024, so only a larger b makes a workgroup take
+a second trip through its tile loop: reload the row's k + 1 smallest values, keep the threshold, and go on counting and
+summing.  The `..._with_several_tiles_per_chunk` tests run at n_b = 1025 .. 2049 (two and three tiles per chunk; a last chunk
+of 1, 76, 129 and 128 columns) with k up to FEATURE_K_CAP = 16, the longest list a row keeps: exactly on integer features
+(test_feature_metrics_host.LARGE_EXACT_CASES, whose host test asserts that rows really have their nearest columns in several
+tiles of one chunk), for the kernel sums, for the fold over gram_f64's values on real data, and for row independence.
+
 Real-valued cases (test_feature_metrics_host.real_case).  A d-term dot product in any order is within
 d 2^-53 sum |a b| <= d 2^-54 (s_i + s_j) of the exact one, so device and numpy squared distances differ by at most
 
@@ -30,7 +37,8 @@ import pytest
 import torch
 
 from rangeldm_amd import metrics as M
-from test_feature_metrics_host import REAL_SHAPES, real_case
+from test_feature_metrics_host import (LARGE_EXACT_CASES, LARGE_REAL_SHAPE, REAL_SHAPES, exact_inputs, large_exact_case,
+                                       nearest_column_spread, real_case, real_inputs)
 from test_generation_metrics import _run_evaluate
 
 pytestmark = pytest.mark.gpu
@@ -58,13 +66,7 @@ def _same_scan(got, want):
 
 # ---- exact on integer-valued features -------------------------------------------------------------------------------------
 def _exact_inputs(case):
-    n, m, d, k, lim = EXACT_CASES[case]
-    rng = np.random.default_rng(100 + case)
-    real = rng.integers(-lim, lim + 1, (n, d))
-    fake = rng.integers(-lim, lim + 1, (m, d))
-    real[n // 3 + 1] = real[n // 3]                      # one real row duplicates its neighbour
-    fake[[0, m // 2, m - 1]] = real[[0, n // 2, n - 1]]  # three generated rows equal real rows
-    return real, fake, k
+    return exact_inputs(EXACT_CASES[case], 100 + case)
 
 
 def _brute(a, b):
@@ -74,11 +76,31 @@ def _brute(a, b):
 @pytest.mark.parametrize("case", range(len(EXACT_CASES)), ids=[str(c) for c in EXACT_CASES])
 def test_scan_and_prdc_are_exact_on_integer_features(case):
     real, fake, k = _exact_inputs(case)
+    _assert_scan_and_prdc_are_the_brute_force(EXACT_CASES[case], real, fake, k, _brute(real, real), _brute(fake, fake), _brute(real, fake))
+
+
+@pytest.mark.parametrize("case", range(len(LARGE_EXACT_CASES)), ids=[str(c) for c in LARGE_EXACT_CASES])
+def test_scan_and_prdc_are_exact_with_several_tiles_per_chunk(case):
+    """The same assertions where a workgroup streams two or three tiles of a chunk past its rows and carries their state from
+    one to the next (what makes each case engage that carry: test_feature_metrics_host.test_large_cases_engage_the_tile_carry).
+    The generated set's own scan has n_a = n_b > 1024: many row blocks, shared norms, the diagonal column in a later tile."""
+    h = large_exact_case(case)
+    m, k = len(h["fake"]), h["k"]
+    cc = M.feature_scan_column_chunk(m)
+    in_one_chunk, across_chunks = nearest_column_spread(h["rf"], k, cc)
+    print(f"{LARGE_EXACT_CASES[case]}: chunk of {cc} columns ({cc // 64} tiles), {-(-m // cc)} chunks; rows with their k + 1 nearest "
+          f"columns in >= 2 tiles of one chunk {int(in_one_chunk.sum())}, in >= 2 chunks {int(across_chunks.sum())} of {len(h['real'])}")
+    assert cc > 64 and in_one_chunk.any() and across_chunks.any()
+    _assert_scan_and_prdc_are_the_brute_force(LARGE_EXACT_CASES[case], h["real"], h["fake"], k, h["rr"], h["ff"], h["rf"])
+
+
+def _assert_scan_and_prdc_are_the_brute_force(label, real, fake, k, rr, ff, rf):
+    """real, fake: integer-valued sets; rr, ff, rf: their int64 squared distances.  Every output of the own-set scans, the
+    cross scan with both radii, the reverse scan and prdc equals the brute force bit for bit."""
     n, m = len(real), len(fake)
-    rr, ff, rf = _brute(real, real), _brute(fake, fake), _brute(real, fake)
     r_real, r_fake = np.sort(rr, 1)[:, k], np.sort(ff, 1)[:, k]
     ties = int((rf == r_real[:, None]).sum() + (rf == r_fake[None, :]).sum())
-    print(f"{EXACT_CASES[case]}: {ties} squared distances equal a radius; largest squared distance {int(max(rr.max(), ff.max(), rf.max()))}")
+    print(f"{label}: {ties} squared distances equal a radius; largest squared distance {int(max(rr.max(), ff.max(), rf.max()))}")
     assert ties > 0 and max(rr.max(), ff.max()) < 2 ** 40
     R, F = _dev(real.astype(np.float64)), _dev(fake.astype(np.float64))
 
@@ -87,6 +109,8 @@ def test_scan_and_prdc_are_exact_on_integer_features(case):
     assert np.array_equal(_np(own.kmin_sq), np.sort(rr, 1)[:, :k + 1].astype(np.float64))
     assert np.array_equal(_np(own.min_sq), np.zeros(n)) and own.count_a is None and own.poly_sum is None
     assert np.array_equal(_np(M.knn_radii_sq(F, k=k)), r_fake.astype(np.float64))
+    own = M.feature_scan(F, F, k=k)
+    assert np.array_equal(_np(own.kmin_sq), np.sort(ff, 1)[:, :k + 1].astype(np.float64)) and np.array_equal(_np(own.min_sq), np.zeros(m))
 
     both = M.feature_scan(R, F, k=min(k, m - 1), radius_sq_a=_dev(r_real.astype(np.float64)), radius_sq_b=_dev(r_fake.astype(np.float64)))
     assert np.array_equal(_np(both.kmin_sq), np.sort(rf, 1)[:, :min(k, m - 1) + 1].astype(np.float64))
@@ -135,6 +159,35 @@ def test_kernel_sums_are_exact_on_integer_features():
     assert got == M.kernel_distance_host(x, y, return_terms=True) and got["krd"] == M.kernel_distance(X, Y)
 
 
+def test_kernel_sums_are_exact_with_several_tiles_per_chunk():
+    """1100 and 1300 rows: chunks of two tiles, the last one ragged, so a row's kernel sum is carried from tile to tile and the
+    skipped diagonal column lies in a second tile for half of the rows.  d = 64, entries in -2 .. 2: t = m / 64 with m = g + 64
+    an integer and t^3 = m^3 / 2^18, so a row sum is exact in any order while sum |m^3| stays below 2^53 -- asserted from the
+    operands, in int64, before the device is touched."""
+    rng = np.random.default_rng(65)
+    xi, yi = rng.integers(-2, 3, (1100, 64)), rng.integers(-2, 3, (1300, 64))
+    x, y = xi.astype(np.float64), yi.astype(np.float64)
+    cubes = {}
+    for name, (p, q) in (("xx", (xi, xi)), ("yy", (yi, yi)), ("xy", (xi, yi)), ("yx", (yi, xi))):
+        m3 = (p.astype(np.int64) @ q.astype(np.int64).T + 64) ** 3
+        cubes[name] = m3
+        print(f"{name}: largest |m| {int(np.cbrt(np.abs(m3).max()) + 0.5)}, largest row sum of |m^3| 2^{math.log2(np.abs(m3).sum(1).max()):.1f}")
+        assert np.abs(m3).sum(1).max() < 2 ** 53
+    assert M.feature_scan_column_chunk(1100) == 128 and M.feature_scan_column_chunk(1300) == 128
+    X, Y = _dev(x), _dev(y)
+    for name, p, q, hp, hq, skip in (("xx", X, X, x, x, True), ("yy", Y, Y, y, y, True), ("xy", X, Y, x, y, False), ("yx", Y, X, y, x, False),
+                                     ("xx", X, X, x, x, False), ("yy", Y, Y, y, y, False)):
+        got = _np(M.feature_scan(p, q, poly=True, exclude_diagonal=skip).poly_sum)
+        want = M.feature_scan_host(hp, hq, poly=True, exclude_diagonal=skip).poly_sum
+        m3 = cubes[name]
+        brute = (m3.sum(1) - (np.diagonal(m3) if skip else 0)).astype(np.float64) / 2.0 ** 18         # exact: integers below 2^53
+        print(f"{name} exclude_diagonal={skip}: {int((got != brute).sum())} of {len(brute)} row sums differ from the brute sum, "
+              f"{int((want != brute).sum())} of the host statement's")
+        assert np.array_equal(got, want) and np.array_equal(want, brute)
+    got = M.kernel_distance(X, Y, return_terms=True)
+    assert got == M.kernel_distance_host(x, y, return_terms=True) and got["krd"] == M.kernel_distance(X, Y)
+
+
 # ---- properties -----------------------------------------------------------------------------------------------------------
 def test_self_distance_is_exactly_zero():
     x = np.random.default_rng(7).normal(size=(70, 77))
@@ -163,6 +216,27 @@ def test_a_row_depends_on_itself_and_b_alone():
     assert not torch.equal(kept, whole.poly_sum)
     t = (a[5] @ b[5]).item() / 77 + 1.0
     assert abs((kept[5] - whole.poly_sum[5]).item() - t * t * t) <= 1e-9 * abs(kept[5].item())
+
+
+def test_a_row_depends_on_itself_and_b_alone_with_several_tiles_per_chunk():
+    """The same promise at n_b = 1100: nine chunks of two tiles.  The slices start inside a row block, and the skipped diagonal
+    column of rows 64 .. 127 and of row 1099 lies in the second tile of its chunk."""
+    rng = np.random.default_rng(9)
+    n = 1100
+    a, b = _dev(rng.normal(size=(n, 77))), _dev(rng.normal(size=(n, 77)))
+    ra, rb = _dev(rng.uniform(100.0, 200.0, n)), _dev(rng.uniform(100.0, 200.0, n))
+    kw = dict(k=16, radius_sq_b=rb, poly=True, exclude_diagonal=True)
+    whole = M.feature_scan(a, b, radius_sq_a=ra, **kw)
+    print(f"count_a sums to {int(whole.count_a.sum())}, count_b to {int(whole.count_b.sum())} of {n * n}")
+    assert 0 < int(whole.count_a.sum()) < n * n and 0 < int(whole.count_b.sum()) < n * n
+    for lo, hi in ((3, 9), (60, 131), (1099, 1100)):
+        part = M.feature_scan(a[lo:hi], b, radius_sq_a=ra[lo:hi], row_offset=lo, **kw)
+        _same_scan(part, M.FeatureScan(*[getattr(whole, name)[lo:hi] for name in OUTPUTS]))
+    _same_scan(M.feature_scan(a, b, radius_sq_a=ra, **kw), whole)               # two calls agree bit for bit
+    kept = M.feature_scan(a, b, poly=True).poly_sum
+    differ = (kept != whole.poly_sum).cpu().numpy()
+    print(f"{int(differ.sum())} of {n} row sums change when the diagonal column is kept")
+    assert differ[[5, 70, 1099]].all()                   # (70, 1099: the second tile of chunks 0 and 8)
 
 
 # ---- real-valued, against the numpy statement -------------------------------------------------------------------------------
@@ -244,7 +318,20 @@ def test_scan_is_the_fold_of_gram_f64_bit_for_bit(i):
     its s the diagonal of gram_f64(x, x), so the numpy fold over those (nothing else in it rounds differently) gives every
     output bit for bit.  The cases hold a ragged row tile and a ragged column tile, d no multiple of 32 nor of 4, one column
     chunk (n_b = 63, 64) and three with the merge kernel (n_b = 150)."""
-    real, fake, k = real_case(i)
+    _assert_scan_is_the_fold_of_gram_f64(*real_case(i))
+
+
+def test_scan_is_the_fold_of_gram_f64_with_several_tiles_per_chunk():
+    """The same at n_b = 1100 and k = FEATURE_K_CAP: nine chunks of two tiles (the last one ragged), the list of smallest
+    values completely full.  On real values the order of the additions shows, so poly_sum pins the carry of a row's sum from
+    one tile of a chunk to the next: ascending j within the chunk, then ascending chunks."""
+    real, fake, k = real_inputs(LARGE_REAL_SHAPE, 4)
+    assert M.feature_scan_column_chunk(len(fake)) == 128 and k == M.FEATURE_K_CAP
+    _assert_scan_is_the_fold_of_gram_f64(real, fake, k)
+    _assert_scan_is_the_fold_of_gram_f64(fake, real, k)  # the 1100 rows against themselves, the diagonal skipped in later tiles
+
+
+def _assert_scan_is_the_fold_of_gram_f64(real, fake, k):
     d = real.shape[1]
     A, B = _dev(real), _dev(fake)
     g_ab, g_aa, g_bb = (_np(M.gram_f64(p, q)) for p, q in ((A, B), (A, A), (B, B)))
@@ -254,12 +341,15 @@ def test_scan_is_the_fold_of_gram_f64_bit_for_bit(i):
     ra, rb = own_a.kmin_sq[:, k].copy(), own_b.kmin_sq[:, k].copy()
     want = M._scan_fold_host(g_ab, s_a, s_b, d, k, ra, rb, True, False, 0)
     got = M.feature_scan(A, B, k=k, radius_sq_a=_dev(ra), radius_sq_b=_dev(rb), poly=True)
+    own = M.feature_scan(A, A, k=k, poly=True, exclude_diagonal=True)
+    shape = f"({len(real)}, {len(fake)}, {d}, {k})"
+    print(f"{shape}: values that differ from the fold: " + ", ".join(f"{name} {int((_np(getattr(got, name)) != getattr(want, name)).sum())}" for name in OUTPUTS)
+          + "; own set: " + ", ".join(f"{name} {int((_np(getattr(own, name)) != getattr(own_a, name)).sum())}" for name in ("kmin_sq", "min_sq", "poly_sum")))
     for name in OUTPUTS:
         assert np.array_equal(_np(getattr(got, name)), getattr(want, name)), name
-    got = M.feature_scan(A, A, k=k, poly=True, exclude_diagonal=True)
-    assert got.count_a is None and got.count_b is None
+    assert own.count_a is None and own.count_b is None
     for name in ("kmin_sq", "min_sq", "poly_sum"):
-        assert np.array_equal(_np(getattr(got, name)), getattr(own_a, name)), name
+        assert np.array_equal(_np(getattr(own, name)), getattr(own_a, name)), name
 
 
 # ---- kernel distance ------------------------------------------------------------------------------------------------------

@@ -7,7 +7,16 @@ and `<`.  The comparison is on the integer counts, so it is exact.  kernel_dista
 sklearn.metrics.pairwise.polynomial_kernel(degree=3, coef0=1) (gamma defaults to 1 / d) with KID's unbiased estimator.
 
 real_case(i) are the real-valued inputs tests/test_feature_metrics_gpu.py holds the device to as well.
+
+Several tiles per column chunk.  feature_scan_column_chunk(n_b) is 64, one tile, for every n_b <= 1024; only above that does
+a workgroup of the device's scan carry a row's state (its k + 1 smallest values, the counts, the minimum, the kernel sum) from
+one tile of 64 columns to the next.  LARGE_EXACT_CASES are integer-valued inputs with 1025 .. 2049 generated rows (two and
+three tiles per chunk, a last chunk of one column, of a ragged second tile, of a third tile that holds one column, and a full
+one) and k up to FEATURE_K_CAP.  test_large_cases_engage_the_tile_carry asserts, on numpy alone, what makes them worth
+running on the device: radius ties, rows whose k + 1 nearest columns lie in two or more tiles of ONE chunk (the values a
+workgroup must carry) and in two chunks (the merge), and that feature_scan_host is the int64 brute force on them.
 """
+import functools
 import math
 
 import numpy as np
@@ -16,15 +25,71 @@ import pytest
 from rangeldm_amd import metrics as M
 
 REAL_SHAPES = [(65, 63, 33, 5), (130, 64, 259, 5), (17, 33, 5, 1), (200, 150, 64, 3)]        # (N, M, d, k)
+LARGE_REAL_SHAPE = (70, 1100, 37, 16)                    # two tiles per chunk, the last chunk ragged; k = FEATURE_K_CAP
+LARGE_EXACT_CASES = [(70, 1025, 8, 5, 2), (130, 1100, 33, 16, 3), (65, 2049, 16, 16, 2), (64, 1664, 12, 1, 2)]   # (N, M, d, k, L)
+TILE = 64                                                # columns per tile of the device's scan
 
 
-def real_case(i):
-    """(real, generated, k) of case i: rng = default_rng(i), real = rng.normal, generated = rng.normal * 0.8 + 0.3."""
-    n, m, d, k = REAL_SHAPES[i]
-    rng = np.random.default_rng(i)
+def real_inputs(shape, seed):
+    """(real, generated, k) for (N, M, d, k): rng = default_rng(seed), real = rng.normal, generated = rng.normal * 0.8 + 0.3."""
+    n, m, d, k = shape
+    rng = np.random.default_rng(seed)
     real = rng.normal(size=(n, d))
     fake = rng.normal(size=(m, d)) * 0.8 + 0.3
     return real, fake, k
+
+
+def real_case(i):
+    """(real, generated, k) of case i: real_inputs(REAL_SHAPES[i], seed i)."""
+    return real_inputs(REAL_SHAPES[i], i)
+
+
+def exact_inputs(shape, seed):
+    """(real, generated, k) for (N, M, d, k, L): integer entries in -L .. L, one real row duplicating its neighbour and three
+    generated rows equal to real rows."""
+    n, m, d, k, lim = shape
+    rng = np.random.default_rng(seed)
+    real = rng.integers(-lim, lim + 1, (n, d))
+    fake = rng.integers(-lim, lim + 1, (m, d))
+    real[n // 3 + 1] = real[n // 3]                      # one real row duplicates its neighbour
+    fake[[0, m // 2, m - 1]] = real[[0, n // 2, n - 1]]  # three generated rows equal real rows
+    return real, fake, k
+
+
+def brute_sq(a, b):
+    """All squared distances of integer rows as int64 (n_a, n_b), by the exact integer identity |a|^2 + |b|^2 - 2 a.b: no
+    (n_a, n_b, d) temporary."""
+    a, b = np.asarray(a).astype(np.int64), np.asarray(b).astype(np.int64)
+    return (a * a).sum(1)[:, None] + (b * b).sum(1)[None, :] - 2 * (a @ b.T)
+
+
+@functools.lru_cache(maxsize=None)
+def large_exact_case(case):
+    """Large case `case`, computed once and left unchanged: real, fake, k, the three int64 distance matrices, both radius
+    vectors and the number of squared distances that equal a radius."""
+    real, fake, k = exact_inputs(LARGE_EXACT_CASES[case], 200 + case)
+    rr, ff, rf = brute_sq(real, real), brute_sq(fake, fake), brute_sq(real, fake)
+    r_real, r_fake = np.sort(rr, 1)[:, k], np.sort(ff, 1)[:, k]
+    ties = int((rf == r_real[:, None]).sum() + (rf == r_fake[None, :]).sum())
+    out = {"real": real, "fake": fake, "k": k, "rr": rr, "ff": ff, "rf": rf, "r_real": r_real, "r_fake": r_fake, "ties": ties}
+    for v in out.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return out
+
+
+def nearest_column_spread(d2, k, chunk_cols):
+    """For every row of d2, where its k + 1 nearest columns (stable order) lie: (rows with two or more tiles of one chunk
+    among them, rows with two or more chunks among them), as boolean vectors."""
+    near = np.argsort(d2, axis=1, kind="stable")[:, :k + 1]
+    tiles, chunks = near // TILE, near // chunk_cols
+    in_one_chunk = np.zeros(d2.shape[0], bool)
+    for c in range(-(-d2.shape[1] // chunk_cols)):
+        held = np.where(chunks == c, tiles, -1)          # the tiles of chunk c among the row's nearest, -1 elsewhere
+        top = held.max(1, keepdims=True)
+        in_one_chunk |= ((held >= 0) & (held != top)).any(1)
+    across_chunks = (chunks != chunks[:, :1]).any(1)
+    return in_one_chunk, across_chunks
 
 
 def prdc_counts_independent(real, fake, k):
@@ -90,6 +155,43 @@ def test_feature_scan_host_outputs():
     assert skipped.kmin_sq is None and skipped.count_a is None and skipped.count_b is None
     # the column chunk: a function of n_b alone, at most 16 chunks of a multiple of 64 rows
     assert [M.feature_scan_column_chunk(n) for n in (1, 64, 65, 1024, 1025, 10000, 50000)] == [64, 64, 64, 64, 128, 640, 3136]
+
+
+@pytest.mark.parametrize("case", range(len(LARGE_EXACT_CASES)), ids=[str(c) for c in LARGE_EXACT_CASES])
+def test_large_cases_engage_the_tile_carry(case):
+    """What makes a large case worth running on the device, asserted on numpy alone, and feature_scan_host against the int64
+    brute force on it (kmin_sq, count_a, count_b, min_sq: the outputs that are exact here; d is no power of two, so t is not)."""
+    n, m, d, k, lim = LARGE_EXACT_CASES[case]
+    h = large_exact_case(case)
+    real, fake, rr, ff, rf, r_real, r_fake = (h[name] for name in ("real", "fake", "rr", "ff", "rf", "r_real", "r_fake"))
+    cc = M.feature_scan_column_chunk(m)
+    chunks = -(-m // cc)
+    in_one_chunk, across_chunks = nearest_column_spread(rf, k, cc)
+    own_one, own_across = nearest_column_spread(ff, k, cc)
+    largest = int(max(rr.max(), ff.max(), rf.max()))
+    print(f"{LARGE_EXACT_CASES[case]}: chunk of {cc} columns, {chunks} chunks, the last of {m - (chunks - 1) * cc}; {h['ties']} squared "
+          f"distances equal a radius; largest squared distance {largest}; rows with their k + 1 nearest generated columns in >= 2 "
+          f"tiles of one chunk {int(in_one_chunk.sum())} of {n}, in >= 2 chunks {int(across_chunks.sum())} of {n}; generated rows "
+          f"against their own set: {int(own_one.sum())} and {int(own_across.sum())} of {m}")
+    assert cc > TILE and chunks > 1 and cc % TILE == 0 and chunks <= 16
+    assert h["ties"] > 0 and largest < 2 ** 40
+    assert in_one_chunk.any() and across_chunks.any()
+    if case < 3:
+        assert 4 * int(in_one_chunk.sum()) >= n
+    assert (np.diagonal(rr) == 0).all() and (np.diagonal(ff) == 0).all() and rf.min() == 0
+    assert np.array_equal(rf[:4], ((real[:4, None, :] - fake[None, :, :]) ** 2).sum(-1))       # the identity, on a row block
+
+    f64 = lambda a: a.astype(np.float64)
+    own = M.feature_scan_host(f64(real), f64(real), k=k)
+    assert np.array_equal(own.kmin_sq, f64(np.sort(rr, 1)[:, :k + 1])) and np.array_equal(own.min_sq, np.zeros(n))
+    own = M.feature_scan_host(f64(fake), f64(fake), k=k)
+    assert np.array_equal(own.kmin_sq, f64(np.sort(ff, 1)[:, :k + 1])) and np.array_equal(own.min_sq, np.zeros(m))
+    both = M.feature_scan_host(f64(real), f64(fake), k=k, radius_sq_a=f64(r_real), radius_sq_b=f64(r_fake))
+    assert np.array_equal(both.kmin_sq, f64(np.sort(rf, 1)[:, :k + 1])) and np.array_equal(both.min_sq, f64(rf.min(1)))
+    assert np.array_equal(both.count_a, (rf < r_real[:, None]).sum(1)) and np.array_equal(both.count_b, (rf < r_fake[None, :]).sum(1))
+    back = M.feature_scan_host(f64(fake), f64(real), k=k, radius_sq_a=f64(r_fake), radius_sq_b=f64(r_real))
+    assert np.array_equal(back.kmin_sq, f64(np.sort(rf.T, 1)[:, :k + 1])) and np.array_equal(back.min_sq, f64(rf.min(0)))
+    assert np.array_equal(back.count_a, (rf < r_fake[None, :]).sum(0)) and np.array_equal(back.count_b, (rf < r_real[:, None]).sum(0))
 
 
 def test_kernel_subsets_is_reproducible_and_distinct():

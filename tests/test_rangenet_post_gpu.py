@@ -8,6 +8,16 @@ lies in [0, 1]) is 8 * 2^-23 = 2^-20, and `* 0.5 * W` carries that to dx = W * 2
 integer, and the share of points inside that band must itself be at most 0.5 % -- else the band would excuse anything.
 Everything after the pixels is exact: given the device's own px, py and depth, rangenet.scatter_host must reproduce proj, mask,
 proj_range and proj_idx bit for bit, and given the device's images, rangenet.knn_labels_host the labels.  Nothing is excluded.
+
+Instances.  The unprojection is one of six instances unproject_kernel<S, K> (window S x S, K slots kept): <1, 1>, <3, 9>,
+<5, 8> and <7, 8> while knn <= 8, <5, 25> and <7, 49> above.  KNN_PAIRS sits on both sides of that switch and at
+knn == search^2, with cutoffs that include 0 ("no cutoff": entries at infinite distance vote); a test derives each pair's
+instance from the dispatcher's rule and requires all six.
+
+The stride.  scan_keys_kernel and unproject_kernel give a cloud 128 blocks of 256 threads, which stride over its points in
+steps of STRIDE = 32 768.  The `long_cloud` tests project and unproject a ragged batch whose first cloud has about 39 960
+points (a KITTI scan has about 120 000), so that threads take a second trip, and hold it to everything the shorter batch is
+held to.
 """
 import json
 
@@ -30,7 +40,13 @@ def _cloud(seed, n):
     return np.concatenate([pts, rem[:, None]], 1).astype(np.float32)
 
 
+STRIDE = 128 * 256                                       # points one trip of the per-point kernels covers: SCAN_BLOCKS_X * 256
 _batches = {}
+
+
+def _downloaded(s):
+    names = ("proj", "mask", "proj_range", "proj_idx", "px", "py", "unproj_range", "offsets")
+    return {k: getattr(s, k).cpu().numpy() for k in names}
 
 
 def _ragged_batch(hw):
@@ -40,9 +56,24 @@ def _ragged_batch(hw):
         clouds = [big, np.zeros((0, 4), np.float32), _cloud(8, 1000)[500:501], _cloud(9, 800)[:777]]
         assert [c.shape[0] for c in clouds][1:] == [0, 1, 777] and 19900 <= clouds[0].shape[0] <= 20000
         s = R.project_scans(clouds, H=hw[0], W=hw[1])
-        names = ("proj", "mask", "proj_range", "proj_idx", "px", "py", "unproj_range", "offsets")
-        _batches[hw] = (clouds, {k: getattr(s, k).cpu().numpy() for k in names})
+        _batches[hw] = (clouds, _downloaded(s))
     return _batches[hw]
+
+
+_long_batches = {}
+
+
+def _long_batch(hw):
+    """A batch whose first cloud is longer than one stride, [about 39 960, 0, 777], projected on the device at hw and
+    downloaded once: (clouds, the ProjectedScans, dict of numpy arrays)."""
+    if hw not in _long_batches:
+        clouds = [_cloud(17, 40000), np.zeros((0, 4), np.float32), _cloud(9, 800)[:777]]
+        n0 = clouds[0].shape[0]
+        print(f"{hw}: clouds of {[c.shape[0] for c in clouds]} points, {n0 - STRIDE} of the first beyond one stride of {STRIDE}")
+        assert STRIDE + 5000 < n0 <= 40000 and [c.shape[0] for c in clouds][1:] == [0, 777]
+        s = R.project_scans(clouds, H=hw[0], W=hw[1])
+        _long_batches[hw] = (clouds, s, _downloaded(s))
+    return _long_batches[hw]
 
 
 def _assert_image_is_scatter_host(cloud, got, b, lo, hi, hw, what):
@@ -59,8 +90,11 @@ def _assert_image_is_scatter_host(cloud, got, b, lo, hi, hw, what):
 # ---- 1. pixels ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("hw", SIZES, ids=str)
 def test_pixels_equal_the_hosts_outside_a_libm_band(hw):
+    _assert_pixels_equal_the_hosts_outside_a_libm_band(*_ragged_batch(hw), hw)
+
+
+def _assert_pixels_equal_the_hosts_outside_a_libm_band(clouds, got, hw):
     H, W = hw
-    clouds, got = _ragged_batch(hw)
     assert got["offsets"].tolist() == np.concatenate([[0], np.cumsum([c.shape[0] for c in clouds])]).tolist()
     pts = np.concatenate(clouds, 0)[:, :3]
     hx, hy, depth, fx, fy = host_pixels(pts, H, W)
@@ -180,6 +214,110 @@ def test_knn_labels_equal_the_host_restatement(hw, search, knn, cutoff):
         print(f"{hw} search {search} knn {knn} cutoff {cutoff} cloud {b}: {bad} of {hi - lo} labels differ")
         assert bad == 0
     assert changed > 0
+
+
+INSTANCES = {(1, 1), (3, 9), (5, 8), (5, 25), (7, 8), (7, 49)}                  # unproject_kernel<S, K>: window, slots kept
+KNN_PAIRS = [(1, 1), (3, 9), (5, 8), (5, 9), (5, 25), (7, 8), (7, 9), (7, 20), (7, 49)]       # (search, knn)
+
+
+def _instance(search, knn):
+    """The dispatcher's rule: a window of 1 or 3 keeps every entry; a window of 5 or 7 keeps 8 slots while knn <= 8 and else
+    the whole window."""
+    return (search, search * search if search <= 3 or knn > 8 else 8)
+
+
+def test_the_knn_pairs_reach_every_instance():
+    reached = {pair: _instance(*pair) for pair in KNN_PAIRS}
+    print(", ".join(f"{pair} -> <{s}, {k}>" for pair, (s, k) in reached.items()))
+    assert set(reached.values()) == INSTANCES
+    for s in (5, 7):                                     # both sides of the switch, and knn == search^2
+        assert {(s, 8), (s, 9), (s, s * s)} <= set(KNN_PAIRS)
+
+
+@pytest.mark.parametrize("cutoff", [0.0, 0.5, 2.0])
+@pytest.mark.parametrize("search,knn", KNN_PAIRS, ids=[f"search{s}-knn{k}" for s, k in KNN_PAIRS])
+@pytest.mark.parametrize("hw", [(8, 32), (16, 64)], ids=str)
+def test_every_unprojection_instance_equals_the_host_restatement(hw, search, knn, cutoff):
+    """Each of the six unproject_kernel instances, on both sides of the knn <= 8 switch and with knn == search^2, where every
+    window entry and every padding entry is a candidate; cutoff 0 is "no cutoff", the only mode in which an entry at infinite
+    distance (an empty pixel) votes."""
+    s, argmax, host = _knn_batch(hw)
+    got = R.unproject(s, argmax, {"knn": knn, "search": search, "sigma": 1.0, "cutoff": cutoff}).cpu().numpy()
+    labels = argmax.cpu().numpy()
+    bad = changed = voters_at_inf = 0
+    for b in (0, 2):
+        lo, hi = host["offsets"][b], host["offsets"][b + 1]
+        px, py = host["px"][lo:hi], host["py"][lo:hi]
+        want = R.knn_labels_host(host["proj_range"][b], host["unproj_range"][lo:hi], labels[b], px, py, knn, search, 1.0, cutoff)
+        bad += int((got[lo:hi] != want).sum())
+        changed += int((want != labels[b][py, px]).sum())
+        if cutoff == 0.0 and knn == search * search and search > 1:
+            empty = np.pad(host["proj_range"][b] < 0, search // 2)
+            window = sum(empty[py + dy, px + dx] for dy in range(search) for dx in range(search)) - empty[py + search // 2, px + search // 2]
+            voters_at_inf += int((window > 0).sum())
+    print(f"{hw} search {search} knn {knn} cutoff {cutoff}: instance <{_instance(search, knn)[0]}, {_instance(search, knn)[1]}>, {bad} of "
+          f"{host['offsets'][-1]} labels differ, {changed} differ from the pixel's own label, {voters_at_inf} points with a voter at infinite distance")
+    assert _instance(search, knn) in INSTANCES
+    assert bad == 0
+    assert changed > 0                                   # (a window of one pixel: class 0 never wins, such a point gets 1)
+    if cutoff == 0.0 and knn == search * search and search > 1:
+        assert voters_at_inf > 0
+
+
+# ---- 3b. clouds longer than one stride of the per-point kernels -------------------------------------------------------------
+LONG_SIZES = [(16, 64), (64, 1024)]
+
+
+@pytest.mark.parametrize("hw", LONG_SIZES, ids=str)
+def test_long_cloud_pixels_equal_the_hosts_outside_a_libm_band(hw):
+    """scan_keys_kernel strides over a cloud in steps of STRIDE points: here the first cloud needs a second trip."""
+    clouds, _, got = _long_batch(hw)
+    _assert_pixels_equal_the_hosts_outside_a_libm_band(clouds, got, hw)
+    H, W = hw
+    n0 = clouds[0].shape[0]
+    hx, hy, depth, fx, fy = host_pixels(clouds[0][STRIDE:, :3], H, W)
+    px, py, r = got["px"][STRIDE:n0], got["py"][STRIDE:n0], got["unproj_range"][STRIDE:n0]
+    print(f"{hw}: points {STRIDE} .. {n0 - 1}: {int((px != hx).sum())} px and {int((py != hy).sum())} py differ from the host's")
+    assert px.min() >= 0 and px.max() < W and py.min() >= 0 and py.max() < H          # written, every one
+    assert np.array_equal(r.view(np.uint32), depth.astype(np.float32).view(np.uint32))
+    assert (np.abs(px.astype(np.int64) - hx) <= 1).all() and (np.abs(py.astype(np.int64) - hy) <= 1).all()
+    assert len(set(zip(px.tolist(), py.tolist()))) > min(H * W, n0 - STRIDE) // 4                # and they are not one value
+
+
+@pytest.mark.parametrize("hw", LONG_SIZES, ids=str)
+def test_long_cloud_image_is_scatter_host_of_the_devices_pixels(hw):
+    clouds, _, got = _long_batch(hw)
+    off = got["offsets"]
+    for b, cloud in enumerate(clouds):
+        _assert_image_is_scatter_host(cloud, got, b, off[b], off[b + 1], hw, f"{hw} cloud {b} ({cloud.shape[0]} points)")
+    assert (got["proj_idx"][1] == -1).all() and not got["mask"][1].any()         # the empty cloud
+    late = int((got["proj_idx"][0] >= STRIDE).sum())
+    print(f"{hw}: {late} of {int((got['proj_idx'][0] >= 0).sum())} pixels are won by a point at index {STRIDE} or beyond")
+    assert late > 0 and got["proj_idx"][0].max() < clouds[0].shape[0]
+
+
+@pytest.mark.parametrize("knn", [None, {"knn": 5, "search": 5, "sigma": 1.0, "cutoff": 1.0}, {"knn": 20, "search": 7, "sigma": 1.0, "cutoff": 0.0}],
+                         ids=["plain", "search5-knn5", "search7-knn20-nocutoff"])
+@pytest.mark.parametrize("hw", LONG_SIZES, ids=str)
+def test_long_cloud_labels_equal_the_host_restatement(hw, knn):
+    """unproject_kernel strides like scan_keys_kernel: every point of the long cloud gets its label, plain and by KNN."""
+    clouds, s, host = _long_batch(hw)
+    argmax = torch.from_numpy(_blocky(hw[0] + 1, 3, *hw)).cuda()
+    labels = argmax.cpu().numpy()
+    got = R.unproject(s, argmax, knn).cpu().numpy()
+    assert got.dtype == np.uint8 and got.shape == (host["offsets"][-1],)
+    for b in (0, 2):
+        lo, hi = host["offsets"][b], host["offsets"][b + 1]
+        px, py = host["px"][lo:hi], host["py"][lo:hi]
+        own = labels[b][py, px]
+        want = own if knn is None else R.knn_labels_host(host["proj_range"][b], host["unproj_range"][lo:hi], labels[b], px, py, **knn)
+        bad = got[lo:hi] != want
+        print(f"{hw} cloud {b}: {int(bad.sum())} of {hi - lo} labels differ ({int(bad[STRIDE:].sum())} at index {STRIDE} or beyond); "
+              f"{int((want != own).sum())} differ from the pixel's own label")
+        assert not bad.any()
+        assert knn is None or (want != own).any()
+        if b == 0:
+            assert len(set(want[STRIDE:].tolist())) > 1                           # the late points carry labels worth comparing
 
 
 @pytest.mark.parametrize("i", [0, 1])

@@ -2,8 +2,8 @@
 (rangeldm_amd/csrc/chamfer.hip, rangeldm_amd/evaluate.py; ldm/convert_vae.py:193-271, metrics/metrics/mae.py:45-117).
 
 CPU: the driver's argument parsing and file pairing, the cubic-weight restatement, the refusals (nuScenes, log sensors).
-GPU: range_errors against an fp64 numpy restatement, both beam_upsample modes bit-equal to numpy restatements,
-`vae(x)` against encode -> mode -> decode, and `evaluate densification` end to end on inference_conditional's output.
+GPU: range_errors against an fp64 numpy restatement, both beam_upsample modes bit-equal to numpy restatements (also past
+the 4 194 304 outputs that one pass of the kernel's capped grid of 256 * 64 workgroups covers), `vae(x)` against encode -> mode -> decode, and `evaluate densification` end to end on inference_conditional's output.
 """
 import json
 import math
@@ -177,6 +177,25 @@ def test_beam_upsample_matches_restatement(mode, rate):
     if mode == "bicubic":                 # a constant image stays (nearly) constant: the weights sum to 1
         c = M.beam_upsample(torch.full((1, 1, 3, 8), 2.5, device="cuda"), rate, mode)
         assert float((c - 2.5).abs().max()) <= 1e-6
+
+
+UPSAMPLE_GRID = 256 * 64 * 256                           # outputs one pass of beam_upsample_kernel's capped grid covers
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["nearest", "bicubic"])
+def test_beam_upsample_past_one_grid_matches_restatement(mode):
+    """More than 4 194 304 outputs: the grid is capped at 256 * 64 workgroups and the first threads take a second trip."""
+    rate = 4
+    src = np.random.default_rng(5).standard_normal((1, 1, 65537, 16)).astype(np.float32)
+    assert src.size * rate > UPSAMPLE_GRID
+    out = M.beam_upsample(torch.from_numpy(src).cuda(), rate, mode).cpu().numpy()
+    ref = _ref_upsample(src, rate, mode).astype(np.float32)
+    assert out.shape == (1, 1, 65537, 16 * rate)
+    bad = out.view(np.uint32) != ref.view(np.uint32)
+    print(f"{mode}: {out.size} outputs, {out.size - UPSAMPLE_GRID} past one grid; {int(bad.sum())} differ "
+          f"({int(bad.reshape(-1)[UPSAMPLE_GRID:].sum())} of those past one grid)")
+    assert not bad.any()
 
 
 def _small_vae():
