@@ -1087,6 +1087,29 @@ int rldm_debug_graph_trace(unsigned long long* stamps, int cap, char* names, siz
  * (sum, sum of squares) of the bf16 outputs of conv(x0); plain single-input conv only. */
 int rldm_test_conv_stats(const rldm_conv_desc* d, const float* x0, const float* weight, const float* bias, float* stats,
                          void* stream);
+/* (tests) the scheduler step where a captured sampler runs it: in the epilogue of the UNet's output layer.  The conv of `d` (Cout <= 4,
+ * no x1) is built as an output layer -- fp32 NCHW, whatever RLDM_FLAG2_FP32_OUT says -- and run once with the plan's scheduler block
+ * filled from `sch`, exactly the fields a sampler fills: the mode word comes from the function the sampler uses.  All pointers of
+ * the struct are device pointers.  The launch reads row *step of coef_table and, when that row's coef[4] != 0, the noise at
+ * noise + *step * noise_step_stride; RLDM_SAMPLER_DPMSOLVER: `noise` is the x0 history (stride 0), read under the same rule and
+ * then overwritten with this step's x0.  x, noise, x_prev: fp32 [B][Cout][W][H]; x_prev may alias x.  pack (or NULL): the next
+ * step's conv_in input, bf16 [B][W][H][pack_ld], of which channels < Cout receive bf16(x_prev). */
+typedef struct rldm_conv_sched_desc {
+    int32_t sampler_mode;             /* RLDM_SAMPLER_*                                                        */
+    int32_t prediction_type;          /* RLDM_PRED_*                                                           */
+    const float* coef_table;          /* [rows][5]                                                             */
+    const int32_t* step;
+    const float* x;
+    const float* noise;
+    int64_t noise_step_stride;
+    float* x_prev;
+    void* pack;
+    int32_t pack_ld;
+} rldm_conv_sched_desc;
+/* x0 device fp32 NCHW; weight, bias, gamma, beta HOST fp32 as in rldm_test_conv; eps: device fp32 [B][Cout][W][H], the conv's own
+ * output.  op_name receives the name of the launch that carried the step (e.g. "conv_o4_kernel<128,32,taps9>"). */
+int rldm_test_conv_sched(const rldm_conv_desc* d, const float* x0, const float* weight, const float* bias, const float* gamma,
+                         const float* beta, const rldm_conv_sched_desc* sch, float* eps, char* op_name, size_t name_cap, void* stream);
 /* multi-head (d=8) self-attention core: qkv device fp32 [B][L][3C] -> out device fp32 [B][L][C] */
 int rldm_test_attention(const float* qkv, int B, int L, int C, float* out, void* stream);
 /* the launch every attention block of the UNet actually runs -- GroupNorm -> to_q / to_k / to_v -> softmax(q k^T/sqrt 8) v

@@ -85,6 +85,13 @@ class ConvDescC(C.Structure):
                 ("upsample", C.c_int32), ("gn", C.c_int32), ("silu", C.c_int32), ("eps", C.c_float)]
 
 
+class ConvSchedDescC(C.Structure):
+    """rldm_conv_sched_desc: the scheduler block of rldm_test_conv_sched (device pointers)."""
+    _fields_ = [("sampler_mode", C.c_int32), ("prediction_type", C.c_int32), ("coef_table", C.c_void_p), ("step", C.c_void_p),
+                ("x", C.c_void_p), ("noise", C.c_void_p), ("noise_step_stride", C.c_int64), ("x_prev", C.c_void_p),
+                ("pack", C.c_void_p), ("pack_ld", C.c_int32)]
+
+
 class LidarConfigC(C.Structure):
     _fields_ = [("beams", C.c_int32), ("width", C.c_int32), ("mode", C.c_int32), ("mean", C.c_float), ("std", C.c_float),
                 ("range_fill", C.c_float), ("intensity_fill", C.c_float), ("grid", C.c_int32 * 3),
@@ -323,6 +330,8 @@ PROTOTYPES = {
                                   C.c_char_p, C.c_size_t, _P]),
     "rldm_debug_force_tile": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "rldm_test_conv_stats": (C.c_int, [C.POINTER(ConvDescC), _P, _P, _P, _P, _P]),
+    "rldm_test_conv_sched": (C.c_int, [C.POINTER(ConvDescC), _P, _P, _P, _P, _P, C.POINTER(ConvSchedDescC), _P, C.c_char_p, C.c_size_t,
+                                       _P]),
     "rldm_debug_set_flags": (C.c_int, [C.c_int]),
     "rldm_debug_set_flags2": (C.c_int, [C.c_int]),
     "rldm_debug_graph_trace": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_size_t]),

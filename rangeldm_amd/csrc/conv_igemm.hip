@@ -705,8 +705,7 @@ __global__ void __launch_bounds__(64 * NW, 1) conv_igemm_kernel(const ConvParams
                         if (sched) {
                             const float x = p.sch.x[i];
                             float x0;
-                            float prev = sched_prev(p.sch.mode, c0, c1, c2, c3, x, e, x0);
-                            if (nz) prev += c4 * nz[i];
+                            const float prev = sched_prev(p.sch.mode, c0, c1, c2, c3, c4, x, e, nz ? nz[i] : 0.f, nz != nullptr, x0);
                             if (hist) hist[i] = x0;
                             p.sch.x_prev[i] = prev;
                             if (p.sch.pack) p.sch.pack[(((size_t)b * p.Wout + ow) * p.Hout + oh) * p.sch.pack_ld + ch] = f32_to_bf16(prev);

@@ -742,8 +742,7 @@ __global__ void __launch_bounds__(256, 2) conv_o4_kernel(const ConvParams p) {
                 if (sched) {
                     const float x = p.sch.x[i];
                     float x0;
-                    float prev = sched_prev(p.sch.mode, c0, c1, c2, c3, x, e[ch], x0);
-                    if (nz) prev += c4 * nz[i];
+                    const float prev = sched_prev(p.sch.mode, c0, c1, c2, c3, c4, x, e[ch], nz ? nz[i] : 0.f, nz != nullptr, x0);
                     if (hist) hist[i] = x0;
                     p.sch.x_prev[i] = prev;
                     if (p.sch.pack) p.sch.pack[(((size_t)b * p.Wout + ow) * p.Hout + oh) * p.sch.pack_ld + ch] = f32_to_bf16(prev);

@@ -170,8 +170,7 @@ __global__ void __launch_bounds__(256) sched_step_kernel(const SchedParams p) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < p.n; i += (long long)gridDim.x * 256) {
         const float x = p.x[i], e = p.eps[i];
         float x0;
-        float prev = sched_prev(p.mode, c0, c1, c2, c3, x, e, x0);
-        if (use_noise) prev += c4 * nz[i];
+        const float prev = sched_prev(p.mode, c0, c1, c2, c3, c4, x, e, use_noise ? nz[i] : 0.f, use_noise, x0);
         if (hist) hist[i] = x0;
         p.x_prev[i] = prev;
     }
@@ -190,31 +189,8 @@ int launch_sched_step(const SchedParams& p, hipStream_t stream) {
 // Row = {c0 .. c4, ka, kb, ra, rb}.  m == 1 and m == 0 are SELECTIONS: a known pixel does not depend on u (an inf there stays
 // there), an unknown one not on z0 / nk.  ka * z0 + kb * nk is two roundings of the products and one of the sum (no contraction),
 // so a host can restate it bit for bit; nk is read only when kb != 0, nr only when the row jumps.
-// u, rounding by rounding as sched_step_kernel evaluates sched_prev (+ its noise term): which products are fused into an fma and which
-// are rounded on their own is spelled out here, so this kernel cannot drift from that one with the shape of the code around it
+// u is sched_prev (kernels.h), whose roundings are stated there: this kernel and sched_step_kernel evaluate the same sequence
 // (tests/test_guided_gpu.py holds the two bit-equal for every mode and prediction type).
-__device__ __forceinline__ float guided_sched_u(const int mode, const float c0, const float c1, const float c2, const float c3, const float c4,
-                                                const float x, const float e, const float nz, const bool use_noise) {
-#pragma clang fp contract(off)
-    const int pred = (mode >> 1) & 3;
-    float x0, pe;
-    if (pred == 0) {
-        x0 = __builtin_fmaf(-c1, e, x) / c0;
-        pe = e;
-    } else if (pred == 1) {
-        const float c1e = c1 * e, c0e = c0 * e;
-        x0 = __builtin_fmaf(c0, x, -c1e);
-        pe = __builtin_fmaf(c1, x, c0e);
-    } else {
-        x0 = e;
-        pe = __builtin_fmaf(-c0, e, x) / c1;
-    }
-    const float a = c2 * x0;
-    const float b = c3 * ((mode & 1) == 0 ? pe : x);
-    float u = a + b;
-    if (use_noise) u = __builtin_fmaf(c4, nz, u);
-    return u;
-}
 __device__ __forceinline__ float guided_known(const float ka, const float z0, const float kb, const float nk, const bool use_nk) {
 #pragma clang fp contract(off)
     const float a = ka * z0;
@@ -271,7 +247,8 @@ template <int V> __global__ void __launch_bounds__(256) sched_guided_step_kernel
         if (jump) zr = guided_load<V>(nr + i);
 #pragma unroll
         for (int j = 0; j < V; ++j) {
-            const float u = guided_sched_u(p.s.mode, c0, c1, c2, c3, c4, x.v[j], e.v[j], use_noise ? zn.v[j] : 0.f, use_noise);
+            float x0;
+            const float u = sched_prev(p.s.mode, c0, c1, c2, c3, c4, x.v[j], e.v[j], use_noise ? zn.v[j] : 0.f, use_noise, x0);
             const float kn = guided_known(ka, z0.v[j], kb, use_nk ? zk.v[j] : 0.f, use_nk);
             const float mm = m.v[j];
             float g = mm == 1.f ? kn : u;

@@ -38,23 +38,35 @@ struct NormView {
 // Multistep mode (DPM-Solver++(2M), diffusers DPMSolverMultistepScheduler): the DDPM update with c0 = alpha_i, c1 = sigma_i,
 // c2 / c3 = the coefficients of x0 / x_t, and the third term c4 * x0 of the PREVIOUS step read from the history buffer that sits in
 // the noise slot (step stride 0); the same thread then stores this step's x0 there.  The buffer is not read when c4 == 0.
+// The step is inlined into four kernels (sched_step_kernel, sched_guided_step_kernel, the fp32-NCHW epilogue of conv_igemm.hip and
+// conv_o4_kernel), and a sampler may run any of them for the same step, so its roundings are stated here, once, with contraction off:
+// which products are fused into an fma and which are rounded on their own does not depend on the code around the inlining site
+// (left to the compiler, the generic conv's epilogue rounded the v_prediction products differently from the other three).  The
+// sequence is the one sched_step_kernel has always compiled to; tests/test_sched_tail_exact.py holds the sites bit-equal.
+// nz: the noise (multistep mode: the previous x0) of this element, read by the caller only when use_noise (c4 != 0).
 constexpr int kSchedMultistep = 8;
-__device__ __forceinline__ float sched_prev(const int mode, const float c0, const float c1, const float c2, const float c3, const float x,
-                                            const float e, float& x0_out) {
+__device__ __forceinline__ float sched_prev(const int mode, const float c0, const float c1, const float c2, const float c3, const float c4,
+                                            const float x, const float e, const float nz, const bool use_noise, float& x0_out) {
+#pragma clang fp contract(off)
     const int pred = (mode >> 1) & 3;
     float x0, pe;
     if (pred == 0) {
-        x0 = (x - c1 * e) / c0;
+        x0 = __builtin_fmaf(-c1, e, x) / c0;
         pe = e;
     } else if (pred == 1) {
-        x0 = c0 * x - c1 * e;
-        pe = c0 * e + c1 * x;
+        const float c1e = c1 * e, c0e = c0 * e;
+        x0 = __builtin_fmaf(c0, x, -c1e);
+        pe = __builtin_fmaf(c1, x, c0e);
     } else {
         x0 = e;
-        pe = (x - c0 * e) / c1;
+        pe = __builtin_fmaf(-c0, e, x) / c1;
     }
     x0_out = x0;
-    return (mode & 1) == 0 ? c2 * x0 + c3 * pe : c2 * x0 + c3 * x;
+    const float a = c2 * x0;
+    const float b = c3 * ((mode & 1) == 0 ? pe : x);
+    float u = a + b;
+    if (use_noise) u = __builtin_fmaf(c4, nz, u);
+    return u;
 }
 // the x0 history of a multistep step (the noise slot, written after it was read), or null
 __device__ __forceinline__ float* sched_history(const int mode, const float* slot) {

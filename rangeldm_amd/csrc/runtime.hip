@@ -2774,11 +2774,11 @@ static Plan* g_trace_plan = nullptr;
 
 // (RLDM_FLAG_SCHED_LAUNCH at sampler creation keeps the scheduler step and the step counter as launches of their own)
 
-// SchedParams / SchedFuse::mode of a sampler's scheduler step (sched_prev)
-static int sampler_sched_mode(const rldm_sampler* s) {
-    const int m = s->cfg.mode;
-    return (m == RLDM_SAMPLER_DDIM ? 0 : 1) | (s->cfg.prediction_type << 1) | (m == RLDM_SAMPLER_DPMSOLVER ? kSchedMultistep : 0);
+// SchedParams / SchedFuse::mode of a scheduler step (sched_prev) from RLDM_SAMPLER_* and RLDM_PRED_*
+static int sched_mode_word(int sampler_mode, int prediction_type) {
+    return (sampler_mode == RLDM_SAMPLER_DDIM ? 0 : 1) | (prediction_type << 1) | (sampler_mode == RLDM_SAMPLER_DPMSOLVER ? kSchedMultistep : 0);
 }
+static int sampler_sched_mode(const rldm_sampler* s) { return sched_mode_word(s->cfg.mode, s->cfg.prediction_type); }
 
 // x_T (just copied into the lane's x) as conv_in's input: once per call when the steps' pack_input launch is fused into conv_out
 static int sampler_pack_x(rldm_sampler* s, SamplerLane* ln, hipStream_t st) {
@@ -3203,13 +3203,13 @@ int rldm_sched_dpmsolver_step(int prediction_type, const float coef[5], const fl
     RLDM_REQUIRE(x0_history != nullptr, "null argument");
     RLDM_REQUIRE(x0_history != x_prev && x0_history != x && x0_history != model_output, "x0_history must not alias another tensor");
     // (coef[4] == 0: the history is not read, only overwritten -- sched_step's noise check passes with the pointer set)
-    return sched_step(1 | (prediction_type << 1) | kSchedMultistep, coef, model_output, x, x0_history, x_prev, n, stream);
+    return sched_step(sched_mode_word(RLDM_SAMPLER_DPMSOLVER, prediction_type), coef, model_output, x, x0_history, x_prev, n, stream);
 }
 int rldm_sched_step(int sampler_mode, int prediction_type, const float coef[5], const float* model_output, const float* x,
                     const float* noise, float* x_prev, int64_t n, void* stream) {
     RLDM_REQUIRE(sampler_mode == RLDM_SAMPLER_DDIM || sampler_mode == RLDM_SAMPLER_DDPM, "unknown sampler mode");
     RLDM_REQUIRE(prediction_type >= RLDM_PRED_EPSILON && prediction_type <= RLDM_PRED_SAMPLE, "unknown prediction type");
-    return sched_step((sampler_mode == RLDM_SAMPLER_DDIM ? 0 : 1) | (prediction_type << 1), coef, model_output, x, noise, x_prev, n, stream);
+    return sched_step(sched_mode_word(sampler_mode, prediction_type), coef, model_output, x, noise, x_prev, n, stream);
 }
 int rldm_sched_guided_step(int sampler_mode, int prediction_type, const float coef[9], const float* model_output, const float* x,
                            const float* noise, const float* known, const float* mask, const float* known_noise,
@@ -3596,7 +3596,7 @@ struct ConvCase {
 };
 // one fused conv as a plan: [statistics of x0/x1 when gn] + conv
 int make_conv_case(ConvCase& cc, const rldm_conv_desc* d, const float* weight, const float* bias, const float* gamma,
-                   const float* beta, int res_channels, bool with_temb) {
+                   const float* beta, int res_channels, bool with_temb, bool output_layer = false) {
     const bool with_res = res_channels > 0;
     const int Cin = d->Cin0 + d->Cin1;
     cc.C0p = d->Cin1 ? d->Cin0 : pad16(d->Cin0);
@@ -3627,7 +3627,8 @@ int make_conv_case(ConvCase& cc, const rldm_conv_desc* d, const float* weight, c
     const int s = d->stride, up = d->upsample ? 2 : 1;
     cc.Wout = d->Win * up / s;
     cc.Hout = d->Hin * up / s;
-    auto walk = [&cc, d, with_res, res_channels, with_temb, s, up](Builder& bb) -> int {
+    RLDM_REQUIRE(!output_layer || (d->Cout <= 4 && !with_res && !with_temb), "an output layer has <= 4 channels, no residual, no time embedding");
+    auto walk = [&cc, d, with_res, res_channels, with_temb, output_layer, s, up](Builder& bb) -> int {
         cc.t0 = bb.make(d->B, d->Win, d->Hin, cc.C0p);
         cc.t1 = Tensor();
         cc.tr = Tensor();
@@ -3648,7 +3649,7 @@ int make_conv_case(ConvCase& cc, const rldm_conv_desc* d, const float* weight, c
         a.want_stats = true;
         // RLDM_FLAG2_FP32_OUT: a conv of <= 4 output channels is a network OUTPUT layer -- fp32 NCHW into plan.io.out (the VAE
         // decoder's conv_out), no bf16 tensor, no statistics
-        if ((dbg2() & RLDM_FLAG2_FP32_OUT) && d->Cout <= 4 && !with_res && !with_temb) {
+        if (output_layer || ((dbg2() & RLDM_FLAG2_FP32_OUT) && d->Cout <= 4 && !with_res && !with_temb)) {
             a.out_f32_nchw = true;
             a.want_stats = false;
         }
@@ -3705,6 +3706,42 @@ int rldm_test_conv_stats(const rldm_conv_desc* d, const float* x0, const float* 
                 hs[((size_t)b * d->Cout + c) * 2 + 1] += v.y;
             }
     RLDM_HIP_CHECK(hipMemcpy(stats, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// the scheduler step in the output layer's epilogue, as a sampler's fused tail runs it (sampler_build_plans)
+int rldm_test_conv_sched(const rldm_conv_desc* d, const float* x0, const float* weight, const float* bias, const float* gamma,
+                         const float* beta, const rldm_conv_sched_desc* sch, float* eps, char* op_name, size_t name_cap, void* stream) {
+    RLDM_REQUIRE(d && x0 && weight && bias && sch && eps && op_name && name_cap > 0, "null argument");
+    RLDM_REQUIRE(d->Cin1 == 0 && d->Cout >= 1 && d->Cout <= 4, "sched test: single-input conv of <= 4 output channels only");
+    RLDM_REQUIRE(sch->sampler_mode >= RLDM_SAMPLER_DDIM && sch->sampler_mode <= RLDM_SAMPLER_DPMSOLVER, "unknown sampler mode");
+    RLDM_REQUIRE(sch->prediction_type >= RLDM_PRED_EPSILON && sch->prediction_type <= RLDM_PRED_SAMPLE, "unknown prediction type");
+    RLDM_REQUIRE(sch->coef_table && sch->step && sch->x && sch->x_prev, "null argument");
+    RLDM_REQUIRE(sch->sampler_mode != RLDM_SAMPLER_DPMSOLVER || sch->noise != nullptr, "multistep mode needs the x0 history");
+    RLDM_REQUIRE(!sch->pack || sch->pack_ld >= d->Cout, "pack_ld below the output channels");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    ConvCase cc;
+    if (make_conv_case(cc, d, weight, bias, gamma, beta, 0, false, true)) return 1;
+    RLDM_REQUIRE(!cc.out.valid() && !cc.plan.ops.empty(), "internal: the output layer was not built as one");
+    char* base = cc.plan.arena.as<char>();
+    if (launch_nchw_f32_to_nhwc_bf16(x0, reinterpret_cast<bf16_t*>(base + cc.t0.off), d->B, d->Cin0, d->Win, d->Hin, cc.C0p, st)) return 1;
+    PlanIO& io = cc.plan.io;
+    io.out = eps;
+    SchedFuse& f = io.sch;
+    f.coef_table = sch->coef_table;
+    f.step_ptr = sch->step;
+    f.x = sch->x;
+    f.x_prev = sch->x_prev;
+    f.mode = sched_mode_word(sch->sampler_mode, sch->prediction_type);
+    f.noise = sch->noise;
+    f.noise_step_stride = sch->noise_step_stride;
+    f.pack = reinterpret_cast<bf16_t*>(sch->pack);
+    f.pack_ld = sch->pack_ld;
+    if (cc.plan.run(st)) return 1;
+    RLDM_HIP_CHECK(hipStreamSynchronize(st));
+    const std::string& name = cc.plan.ops.back().name;       // (the conv is the plan's last launch: an output layer emits no statistics to fold)
+    RLDM_REQUIRE(name.size() + 1 <= name_cap, "op name buffer too small");
+    memcpy(op_name, name.c_str(), name.size() + 1);
     return 0;
 }
 

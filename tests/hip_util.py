@@ -93,6 +93,50 @@ def hip_conv_stats(x0, weight, bias, stride=1):
     return st.cpu()
 
 
+def hip_conv_sched(x0, weight, bias, gamma, beta, sampler_mode, prediction_type, coef_table, step, x, noise, noise_step_stride, x_prev,
+                   pack=None, pack_ld=0, silu=True, eps=1e-5):
+    """rldm_test_conv_sched: the 3x3 output layer conv(silu(GN(x0))) with the scheduler step in its epilogue, as a captured sampler runs
+    it.  x0 fp32 NCHW and weight / bias / gamma / beta as hip_conv takes them; coef_table (float32 [rows][5]), step (int32 [1]), x,
+    noise, x_prev (float32) and pack (int16 bit patterns of bf16, or None) are CUDA tensors used IN PLACE -- views are fine, their
+    data_ptr is what the kernel gets (a lane's noise offset, x_prev aliasing x).  -> (eps on the device, name of the carrying launch)."""
+    dev = torch.device("cuda")
+    d = _lib.ConvDescC()
+    B, C0, W, H = x0.shape
+    d.B, d.Cin0, d.Cin1, d.Win, d.Hin = B, C0, 0, W, H
+    d.Cout, d.ksize = weight.shape[0], weight.shape[2]
+    d.stride, d.pad_mode, d.upsample = 1, 0, 0
+    d.gn, d.silu, d.eps = (1 if gamma is not None else 0), (1 if silu else 0), eps
+    for t, dt in ((coef_table, torch.float32), (step, torch.int32), (x, torch.float32), (x_prev, torch.float32)):
+        assert t.is_cuda and t.dtype == dt and t.is_contiguous()
+    assert noise is None or (noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous())
+    assert pack is None or (pack.is_cuda and pack.dtype == torch.int16 and pack.is_contiguous())
+    s = _lib.ConvSchedDescC()
+    s.sampler_mode, s.prediction_type = int(sampler_mode), int(prediction_type)
+    s.coef_table, s.step, s.x, s.x_prev = coef_table.data_ptr(), step.data_ptr(), x.data_ptr(), x_prev.data_ptr()
+    s.noise = noise.data_ptr() if noise is not None else None
+    s.noise_step_stride = int(noise_step_stride)
+    s.pack = pack.data_ptr() if pack is not None else None
+    s.pack_ld = int(pack_ld)
+    xs = x0.to(dev, torch.float32).contiguous()
+    y = torch.empty((B, d.Cout, W, H), device=dev, dtype=torch.float32)
+
+    def hostp(t):
+        if t is None:
+            return None, None
+        a = np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32)
+        return a, a.ctypes.data_as(C.c_void_p)
+
+    hw, pw = hostp(weight)
+    hb, pb = hostp(bias)
+    hg, pg = hostp(gamma)
+    hbt, pbt = hostp(beta)
+    name = C.create_string_buffer(128)
+    _lib.check(_lib.lib().rldm_test_conv_sched(C.byref(d), C.c_void_p(xs.data_ptr()), pw, pb, pg, pbt, C.byref(s),
+                                               C.c_void_p(y.data_ptr()), name, len(name), _lib.stream_ptr(dev)), "rldm_test_conv_sched")
+    torch.cuda.synchronize()
+    return y, name.value.decode()
+
+
 def hip_attention_qkv(x, gamma, beta, wqkv, bqkv, groups=32, eps=1e-5):
     """rldm_test_attention_qkv: the fused GroupNorm -> q/k/v -> softmax.V launch of every UNet attention block.
     x (B, L, C) token-major fp32 -> (B, L, C) heads concatenated (before to_out)."""

@@ -57,6 +57,8 @@ def test_struct_layouts_match_header():
     assert ctypes.sizeof(_lib.UNetConfigC) == 4 * (6 + 3 * 8 + 6)
     assert ctypes.sizeof(_lib.VAEConfigC) == 4 * (4 + 8 + 6)
     assert ctypes.sizeof(_lib.ConvDescC) == 4 * 13
+    assert ctypes.sizeof(_lib.ConvSchedDescC) == 72 and _lib.ConvSchedDescC.noise_step_stride.offset == 40
+    assert _lib.ConvSchedDescC.pack_ld.offset == 64
     assert ctypes.sizeof(_lib.TrainConvDescC) == 4 * 8 and ctypes.sizeof(_lib.AdamWConfigC) == 4 * 8
     assert ctypes.sizeof(_lib.PackDescC) == 48 and _lib.PackDescC.N.offset == 32
     assert ctypes.sizeof(_lib.TrainFuseC) == 152 and _lib.TrainFuseC.cs_out.offset == 64 and _lib.TrainFuseC.gs_out.offset == 144
