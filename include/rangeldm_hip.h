@@ -216,6 +216,33 @@ int rldm_sample_guided(rldm_sampler* s, const float* x_T, const float* step_nois
  * pipeline __call__ and raises RuntimeError. */
 int rldm_sampler_status(rldm_sampler* s);
 
+/* ---- counter-based normals (rangeldm_amd/csrc/rng.hip; the numpy statement is rangeldm_amd/rng.py) ------------------------
+ * normal(seed, stream, row, sample, e): Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (e >> 2, sample, row,
+ * stream), whose words (o0, o1, o2, o3) give four normals by two Box-Muller pairs; element e takes z[e & 3].  stream = 4 * draw +
+ * purpose (0 x_T and any plain randn, row 0; 1 step noise, 2 known-region noise, 3 re-noise of row r).  Known answers of the block:
+ *   counter 0, key 0                         -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *   counter 0xffffffff x 4, key 0xffffffff x 2 -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ * rldm_randn: out device fp32 [B][per_sample] = normal(seed, stream, row, sample_offset + b, e).  per_sample < 2^31 and
+ * sample_offset + B <= 2^32, so the values of a sample do not depend on B or on how a batch is cut. */
+int rldm_randn(float* out, int64_t B, int64_t per_sample, uint64_t seed, uint32_t stream_id, uint32_t row, uint64_t sample_offset,
+               void* stream);
+/* tests: the integer half (counters device uint32 [n][4], key host uint32 [2], out device uint32 [n][4]) and the transform
+ * (bits device uint32 [n][4] -> out device fp32 [n][4]) on chosen inputs */
+int rldm_rng_philox(const uint32_t* counters, const uint32_t key[2], int64_t n, uint32_t* out, void* stream);
+int rldm_rng_normals_from_bits(const uint32_t* bits, int64_t n, float* out, void* stream);
+/* rldm_sample / rldm_sample_guided with the noise drawn on the device inside the step graph: (seed, draw, sample_offset) stand
+ * in place of step_noise, known_noise and renoise_noise, and x_T may be NULL (then drawn with purpose 0, row 0).  Each lane keeps one
+ * row buffer [lane batch, out_ch, W, H] per purpose its rows need; a fill launch at the head of every step writes the row that step's
+ * scheduler launch reads.  Sample b of the call is sample_offset + b whatever lane runs it.  The three words travel through a
+ * 16-byte device record written on the lanes' streams, so a call with another seed or draw replays the same graphs.  The result
+ * equals the explicit entry point fed with rldm_randn tensors for the same (seed, draw, purpose, row).  draw < 2^30. */
+int rldm_sample_rng(rldm_sampler* s, const float* x_T, uint64_t seed, uint32_t draw, uint64_t sample_offset, const float* cond,
+                    float* images, float* latents_out, void* stream);
+int rldm_sample_guided_rng(rldm_sampler* s, const float* x_T, uint64_t seed, uint32_t draw, uint64_t sample_offset, const float* known,
+                           const float* mask, float* images, float* latents_out, void* stream);
+/* tests: how many times the lanes of `s` captured a step graph since creation */
+int rldm_debug_sampler_captures(rldm_sampler* s);
+
 /* ---- multi-GPU exchange steps: RCCL over xGMI on the caller's stream (rangeldm_amd/csrc/collective.hip) --
  * One process per GPU.  Rank 0 makes the id and hands its RLDM_UNIQUE_ID_BYTES bytes to the other ranks by any side channel
  * (MPI, a file, torch.distributed's store); every rank then calls rldm_comm_create with its current HIP device set.  RCCL is

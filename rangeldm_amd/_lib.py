@@ -176,6 +176,13 @@ PROTOTYPES = {
     "rldm_sample": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "rldm_sample_guided": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rldm_sampler_status": (C.c_int, [_P]),
+    # counter-based normals (csrc/rng.hip; rng.py): the fill, its two test entry points, the samplers that draw inside their graphs
+    "rldm_randn": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, _P]),
+    "rldm_rng_philox": (C.c_int, [_P, C.POINTER(C.c_uint32), C.c_int64, _P, _P]),
+    "rldm_rng_normals_from_bits": (C.c_int, [_P, C.c_int64, _P, _P]),
+    "rldm_sample_rng": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint64, _P, _P, _P, _P]),
+    "rldm_sample_guided_rng": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint64, _P, _P, _P, _P, _P]),
+    "rldm_debug_sampler_captures": (C.c_int, [_P]),
     "rldm_unet_set_plan_flags": (C.c_int, [_P, C.c_int]),
     "rldm_debug_inject_trunk_error": (C.c_int, [_P, C.c_int]),
     "rldm_comm_bind": (C.c_int, []),

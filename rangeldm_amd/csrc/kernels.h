@@ -454,4 +454,21 @@ int launch_trunk_check(const int* err, float* a, long long na, float* b, long lo
 int launch_stamp(unsigned long long* slot, hipStream_t stream);   // *slot = wall_clock64() (100 MHz)
 int launch_scale_f32(const float* src, float* dst, float scale, long long n, hipStream_t stream);
 
+// rng.hip: out[b][e] = normal(seed, 4 * draw + purpose, row, sample0 + b, e) for b < B, e < per_sample (include/rangeldm_hip.h).
+// Immediate form: record == null, the generator is (seed, draw, sample0) and the row is `row`.  Sampler form (inside a captured
+// graph): record -> {seed low, seed high, draw, sample offset} on the device, the first sample is record[3] + sample0, and the row
+// is *step_ptr + row (step_ptr may be null: row).
+struct RngFillParams {
+    float* out;
+    long long per_sample;
+    int B;
+    unsigned purpose;
+    unsigned long long seed;
+    unsigned draw, row, sample0;
+    const unsigned* record;
+    const int* step_ptr;
+};
+int launch_rng_fill(const RngFillParams& p, hipStream_t stream);
+int launch_rng_record(unsigned* record, unsigned long long seed, unsigned draw, unsigned sample_offset, hipStream_t stream);
+
 }  // namespace rldm

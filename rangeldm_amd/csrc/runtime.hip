@@ -2698,6 +2698,10 @@ struct SamplerLane {
     std::unique_ptr<Plan> dplan;                    // private VAE decode plan
     DevBuf x, eps, cond, step, image;
     DevBuf hist;                                    // RLDM_SAMPLER_DPMSOLVER: the previous step's x0 (sized like x)
+    // rldm_sample_rng / rldm_sample_guided_rng: {seed low, seed high, draw, sample offset} of the call, and one row of noise (sized
+    // like x) per purpose the rows need -- filled at the head of every step, read by the scheduler step with stride 0 like hist
+    DevBuf rng_record, rng_step, rng_known, rng_renoise;
+    bool own_noise = false;                         // this call's noise tensors are the lane's row buffers
     hipStream_t stream = nullptr;
     hipEvent_t ev_out = nullptr;
     hipGraphExec_t step_graph = nullptr, decode_graph = nullptr;
@@ -2735,6 +2739,10 @@ struct rldm_sampler {
                                                     // launches at the next call instead of meeting that sampler's launches again
     int latched_error = 0;                          // self-check code of a call whose pending word was read while the plans were rebuilt
     int inject_error = 0;                           // tests: rldm_debug_inject_trunk_error (one shot)
+    int captures = 0;                               // step graphs captured so far (rldm_debug_sampler_captures)
+    bool rng_on = false;                            // the call in progress draws its noise on the device (rldm_sample_rng):
+    uint64_t rng_seed = 0;                          //   its generator, set by the entry point
+    uint32_t rng_draw = 0, rng_offset = 0;
     bool needs_known_noise = false, needs_renoise_noise = false;   // guided: some row has kb != 0 / (ra, rb) != (1, 0)
     bool has_persistent() const {
         for (auto& ln : lanes)
@@ -2799,7 +2807,28 @@ static int sampler_enqueue_step(rldm_sampler* s, SamplerLane* ln, const float* n
     const bool fused = ln->fused_tail;
     const bool multistep = s->cfg.mode == RLDM_SAMPLER_DPMSOLVER;
     // (the rest of io.sch / io.step_inc: sampler_build_plans; a multistep sampler's x0 history is fixed there)
-    if (fused && !multistep) ln->uplan->io.sch.noise = noise;
+    if (fused && !multistep) {
+        ln->uplan->io.sch.noise = noise;
+        ln->uplan->io.sch.noise_step_stride = ln->own_noise ? 0 : s->n_latent;
+    }
+    if (ln->own_noise) {
+        // the row this step's scheduler launch reads: the step word itself where it is advanced AFTER that launch (it starts at 0),
+        // the word + 1 with the fused tail (it starts at -1 and the step's first launch, which follows this one, advances it)
+        RngFillParams rp{};
+        rp.per_sample = ln->n_latent / ln->nb;
+        rp.B = ln->nb;
+        rp.record = ln->rng_record.as<unsigned>();
+        rp.sample0 = (unsigned)ln->b0;
+        rp.step_ptr = ln->step.as<int>();
+        rp.row = fused ? 1u : 0u;
+        const float* bufs[3] = {noise, ln->guided.known_noise, ln->guided.renoise_noise};
+        for (int k = 0; k < 3; ++k) {
+            if (!bufs[k]) continue;
+            rp.out = const_cast<float*>(bufs[k]);
+            rp.purpose = 1u + k;
+            if (launch_rng_fill(rp, st)) return 1;
+        }
+    }
     if ((g_dbg_flags | s->plan_flags) & RLDM_FLAG_GRAPH_TRACE) {
         if (!g_trace.p) {
             if (g_trace.alloc(4096 * 8)) return 1;
@@ -2821,7 +2850,7 @@ static int sampler_enqueue_step(rldm_sampler* s, SamplerLane* ln, const float* n
         sp.noise_step_stride = 0;
     } else {
         sp.noise = noise;                           // already offset to this lane's first sample
-        sp.noise_step_stride = s->n_latent;         // the caller's tensor is [steps][whole batch][...]
+        sp.noise_step_stride = ln->own_noise ? 0 : s->n_latent;     // the caller's tensor is [steps][whole batch][...]
     }
     sp.x_prev = ln->x.as<float>();
     sp.n = ln->n_latent;
@@ -3371,10 +3400,10 @@ int rldm_debug_inject_trunk_error(rldm_sampler* s, int code) {
 
 static int sample_impl(rldm_sampler* s, const float* x_T, const float* step_noise, const float* cond, const GuidedIO& gio, float* images,
                        float* latents_out, void* stream) {
-    RLDM_REQUIRE(s && x_T, "null argument");
+    RLDM_REQUIRE(s && (x_T || s->rng_on), "null argument");
     RLDM_REQUIRE(images || latents_out, "no output requested");
     RLDM_REQUIRE((s->cfg.cond_channels == 0) == (cond == nullptr), "cond tensor does not match sampler.cond_channels");
-    RLDM_REQUIRE(s->cfg.mode != RLDM_SAMPLER_DDPM || step_noise != nullptr, "DDPM sampling needs step_noise");
+    RLDM_REQUIRE(s->cfg.mode != RLDM_SAMPLER_DDPM || step_noise != nullptr || s->rng_on, "DDPM sampling needs step_noise");
     hipStream_t caller = reinterpret_cast<hipStream_t>(stream);
     if (s->unet_gen != s->unet->generation || (s->vae && s->vae_gen != s->vae->generation) || !s->unet->params.finalized ||
         (s->vae && !s->vae->params.finalized)) {
@@ -3423,19 +3452,46 @@ static int sample_impl(rldm_sampler* s, const float* x_T, const float* step_nois
         hipStream_t st = ln->stream;
         const size_t lat_off = (size_t)ln->b0 * (ln->n_latent / ln->nb);
         RLDM_HIP_CHECK(hipStreamWaitEvent(st, s->ev_in, 0));
-        RLDM_HIP_CHECK(hipMemcpyAsync(ln->x.p, x_T + lat_off, ln->n_latent * 4, hipMemcpyDeviceToDevice, st));
+        ln->own_noise = s->rng_on;
+        if (s->rng_on) {
+            // the call's generator, stream-ordered in front of everything that reads it (no host synchronisation)
+            if (!ln->rng_record.p && ln->rng_record.alloc(64)) return 1;
+            if (launch_rng_record(ln->rng_record.as<unsigned>(), s->rng_seed, s->rng_draw, s->rng_offset, st)) return 1;
+            if (s->cfg.mode == RLDM_SAMPLER_DDPM && !ln->rng_step.p && ln->rng_step.alloc(ln->n_latent * 4)) return 1;
+            if (s->needs_known_noise && !ln->rng_known.p && ln->rng_known.alloc(ln->n_latent * 4)) return 1;
+            if (s->needs_renoise_noise && !ln->rng_renoise.p && ln->rng_renoise.alloc(ln->n_latent * 4)) return 1;
+        }
+        // x_T into the lane: the caller's, or purpose 0 / row 0 of the call's generator for the lane's samples
+        const auto load_x = [&]() -> int {
+            if (x_T) {
+                RLDM_HIP_CHECK(hipMemcpyAsync(ln->x.p, x_T + lat_off, ln->n_latent * 4, hipMemcpyDeviceToDevice, st));
+                return 0;
+            }
+            RngFillParams rp{};
+            rp.out = ln->x.as<float>();
+            rp.per_sample = ln->n_latent / ln->nb;
+            rp.B = ln->nb;
+            rp.record = ln->rng_record.as<unsigned>();
+            rp.sample0 = (unsigned)ln->b0;
+            return launch_rng_fill(rp, st);
+        };
+        if (load_x()) return 1;
         if (cond)
             RLDM_HIP_CHECK(hipMemcpyAsync(ln->cond.p, cond + (size_t)ln->b0 * (ln->n_cond / ln->nb), ln->n_cond * 4,
                                           hipMemcpyDeviceToDevice, st));
         if (sampler_pack_x(s, ln, st)) return 1;
         if (launch_step_counter(ln->step.as<int>(), ln->fused_tail ? -1 : 0, 0, st)) return 1;
-        const float* noise = s->cfg.mode == RLDM_SAMPLER_DDPM ? step_noise + lat_off : nullptr;
+        const float* noise = s->cfg.mode != RLDM_SAMPLER_DDPM ? nullptr : s->rng_on ? ln->rng_step.as<float>() : step_noise + lat_off;
         ln->guided = GuidedIO();
         if (s->cfg.guided) {                        // each offset to the lane's first sample, exactly as step_noise is
             ln->guided.known = gio.known + lat_off;
             ln->guided.mask = gio.mask + (size_t)ln->b0 * s->unet->cfg.sample_w * s->unet->cfg.sample_h;
             ln->guided.known_noise = gio.known_noise ? gio.known_noise + lat_off : nullptr;
             ln->guided.renoise_noise = gio.renoise_noise ? gio.renoise_noise + lat_off : nullptr;
+            if (s->rng_on) {
+                ln->guided.known_noise = s->needs_known_noise ? ln->rng_known.as<float>() : nullptr;
+                ln->guided.renoise_noise = s->needs_renoise_noise ? ln->rng_renoise.as<float>() : nullptr;
+            }
         }
         if (!ln->step_graph || ln->captured_noise != noise || !(ln->captured_guided == ln->guided)) {
             // one eager step first (sets kernel attributes, packs weights), then rewind and capture
@@ -3455,7 +3511,7 @@ static int sample_impl(rldm_sampler* s, const float* x_T, const float* step_nois
                 RLDM_REQUIRE(terr == 0, "persistent trunk launch failed its self-check (code " + std::to_string(terr) +
                                             "): set RLDM_DBG_FLAGS=16777216 to run the levels as separate launches");
             }
-            RLDM_HIP_CHECK(hipMemcpyAsync(ln->x.p, x_T + lat_off, ln->n_latent * 4, hipMemcpyDeviceToDevice, st));
+            if (load_x()) return 1;
             if (sampler_pack_x(s, ln, st)) return 1;
             if (launch_step_counter(ln->step.as<int>(), ln->fused_tail ? -1 : 0, 0, st)) return 1;
             // the graph holds `gs` consecutive steps (the step index lives on the device, so the steps are identical launches):
@@ -3470,13 +3526,14 @@ static int sample_impl(rldm_sampler* s, const float* x_T, const float* step_nois
                 }, &ln->step_graph)) return 1;
             ln->captured_noise = noise;
             ln->captured_guided = ln->guided;
+            ++s->captures;
         }
         if (images && s->vae && !ln->decode_graph) {
             // (the decode runs on whatever x holds now: only its launch list is recorded)
             if (ln->dplan->run(st)) return 1;
             RLDM_HIP_CHECK(hipStreamSynchronize(st));
             if (capture(st, [&]() { return ln->dplan->run(st); }, &ln->decode_graph)) return 1;
-            RLDM_HIP_CHECK(hipMemcpyAsync(ln->x.p, x_T + lat_off, ln->n_latent * 4, hipMemcpyDeviceToDevice, st));
+            if (load_x()) return 1;
             if (sampler_pack_x(s, ln, st)) return 1;
         }
     }
@@ -3528,6 +3585,7 @@ int rldm_sample(rldm_sampler* s, const float* x_T, const float* step_noise, cons
     RLDM_REQUIRE(s, "null argument");
     RLDM_REQUIRE(!s->cfg.guided, "this sampler was created with guided = 1: call rldm_sample_guided (known, mask and the two noise "
                                  "tensors are part of every row)");
+    s->rng_on = false;
     return sample_impl(s, x_T, step_noise, cond, GuidedIO(), images, latents_out, stream);
 }
 
@@ -3540,7 +3598,48 @@ int rldm_sample_guided(rldm_sampler* s, const float* x_T, const float* step_nois
     RLDM_REQUIRE(renoise_noise || !s->needs_renoise_noise, "some row jumps back up: renoise_noise must be given");
     GuidedIO gio;
     gio.known = known; gio.mask = mask; gio.known_noise = known_noise; gio.renoise_noise = renoise_noise;
+    s->rng_on = false;
     return sample_impl(s, x_T, step_noise, nullptr, gio, images, latents_out, stream);
+}
+
+// the two calls above with the noise drawn inside the step graph (rng.hip): the generator in place of the noise tensors
+static int sampler_set_generator(rldm_sampler* s, uint64_t seed, uint32_t draw, uint64_t sample_offset) {
+    RLDM_REQUIRE(draw < (1u << 30), "draw must be below 2^30 (stream = 4 * draw + purpose is 32 bits)");
+    RLDM_REQUIRE(sample_offset + (uint64_t)s->cfg.batch <= (1ULL << 32), "sample_offset + batch must not exceed 2^32");
+    RLDM_REQUIRE(s->n_latent / s->cfg.batch < (1LL << 31), "a sample must hold fewer than 2^31 elements");
+    s->rng_on = true;
+    s->rng_seed = seed;
+    s->rng_draw = draw;
+    s->rng_offset = (uint32_t)sample_offset;
+    return 0;
+}
+
+int rldm_sample_rng(rldm_sampler* s, const float* x_T, uint64_t seed, uint32_t draw, uint64_t sample_offset, const float* cond,
+                    float* images, float* latents_out, void* stream) {
+    RLDM_REQUIRE(s, "null argument");
+    RLDM_REQUIRE(!s->cfg.guided, "this sampler was created with guided = 1: call rldm_sample_guided_rng");
+    if (sampler_set_generator(s, seed, draw, sample_offset)) return 1;
+    const int rc = sample_impl(s, x_T, nullptr, cond, GuidedIO(), images, latents_out, stream);
+    s->rng_on = false;
+    return rc;
+}
+
+int rldm_sample_guided_rng(rldm_sampler* s, const float* x_T, uint64_t seed, uint32_t draw, uint64_t sample_offset, const float* known,
+                           const float* mask, float* images, float* latents_out, void* stream) {
+    RLDM_REQUIRE(s, "null argument");
+    RLDM_REQUIRE(s->cfg.guided, "rldm_sample_guided_rng needs a sampler created with guided = 1");
+    RLDM_REQUIRE(known && mask, "null argument: known / mask");
+    if (sampler_set_generator(s, seed, draw, sample_offset)) return 1;
+    GuidedIO gio;
+    gio.known = known; gio.mask = mask;
+    const int rc = sample_impl(s, x_T, nullptr, nullptr, gio, images, latents_out, stream);
+    s->rng_on = false;
+    return rc;
+}
+
+int rldm_debug_sampler_captures(rldm_sampler* s) {
+    RLDM_REQUIRE(s, "null argument");
+    return s->captures;
 }
 
 // one instrumented UNet step + scheduler step (+ VAE decode) of lane 0: per-kernel launch counts, HIP-event time,

@@ -14,7 +14,9 @@ ldm/inference.py:171-183 writes it: `<idx>.bin` (float32 [N, 4] x, y, z, remissi
 `<idx>.png` (8-bit BEV density) and `<idx>_range.png` (8-bit range channel) -- the point cloud, the BEV volume, the depth
 filter and the 8-bit rendering all run on the GPU (rangeldm_amd.range_image); only finished bytes cross PCIe.
 `--save-npy` adds `<idx>.npy`, the raw (2, W, H) fp32 range image.  `--scheduler {ddpm,ddim,dpmsolver++}` and `--steps N`
-override the sampler and step count the config runs (e.g. `--scheduler dpmsolver++ --steps 20`).
+override the sampler and step count the config runs (e.g. `--scheduler dpmsolver++ --steps 20`).  `--device-rng` draws x_T and the
+ancestral noise inside the sampler from rangeldm_amd.rng.DeviceGenerator(--seed) at sample_offset = the global image index: no
+[steps, B, ...] noise tensor, and the same noise per image for any GPU count.
 """
 import argparse
 import os
@@ -99,6 +101,9 @@ def add_sampling_args(ap):
     ap.add_argument("--scheduler", choices=SCHEDULER_CHOICES, default=None,
                     help="sampler (default: what the config runs; dpmsolver++ = DPM-Solver++(2M), for 20-25 steps)")
     ap.add_argument("--steps", type=int, default=None, help="num_inference_steps (default: the config's)")
+    ap.add_argument("--device-rng", action="store_true",
+                    help="draw x_T and every row of noise on the device from the counter-based generator (rangeldm_amd.rng): seed = --seed, "
+                         "sample = the global image index, so any GPU count and batch size draws the same noise per image")
 
 
 def device_step_noise(seed, global_indices, steps, lat_shape, device):
@@ -172,6 +177,7 @@ def main(argv=None):
 
     from .params import unet_param_shapes, vae_param_shapes
     from .pipelines import DDIMPipelineRange, DDPMPipelineRange, LDMPipelineRange
+    from .rng import DeviceGenerator
     from .schedulers import DDIMSchedulerHIP, DDPMSchedulerHIP
     from .synth import latent_noise, synth_state_dict
     from .unet import UNet2DModelHIP
@@ -226,11 +232,14 @@ def main(argv=None):
             continue
         # x_T AND the ancestral step noise are functions of the GLOBAL image index: any GPU count produces the same images
         idx = D.global_sample_indices(i, B, rank, world)
-        x_T = torch.from_numpy(np.stack([latent_noise(a.seed, j, lat_shape) for j in idx])).to(dev)
-        kw = {}
-        if ddpm:
-            kw["step_noise"] = device_step_noise(a.seed, idx, steps, lat_shape, dev)
-        image = pipe(batch_size=B, num_inference_steps=steps, output_type="torch", latents=x_T, **kw)
+        if a.device_rng:
+            # one draw per call, always draw 0: the global index alone tells the samples apart
+            kw = dict(generator=DeviceGenerator(a.seed), sample_offset=idx[0])
+        else:
+            kw = dict(latents=torch.from_numpy(np.stack([latent_noise(a.seed, j, lat_shape) for j in idx])).to(dev))
+            if ddpm:
+                kw["step_noise"] = device_step_noise(a.seed, idx, steps, lat_shape, dev)
+        image = pipe(batch_size=B, num_inference_steps=steps, output_type="torch", **kw)
         if to_range is None:
             to_range = sensor_for(image.shape[3])
         points, counts, bev_u8, range_u8 = postprocess(to_range, image)

@@ -111,6 +111,7 @@ def main_guided(a):
     from .inference import load_config
     from .params import unet_param_shapes, vae_param_shapes
     from .pipelines import DDIMPipelineRange, LDMPipelineRange
+    from .rng import DeviceGenerator
     from .schedulers import DDIMSchedulerHIP
     from .synth import synth_state_dict
     from .unet import UNet2DModelHIP
@@ -171,9 +172,11 @@ def main_guided(a):
     n_iter = a.samples // B // world + 1
     for i in range(n_iter):
         seed = rank + world * i
-        generator = torch.Generator().manual_seed(seed)
+        generator, kw = torch.Generator().manual_seed(seed), {}
+        if a.device_rng:                                   # --seed and the global sample index (draw 0 of every call)
+            generator, kw = DeviceGenerator(a.seed), dict(sample_offset=D.global_sample_indices(i, B, rank, world)[0])
         images = pipe(batch_size=B, generator=generator, num_inference_steps=steps, output_type="torch", known=jpg,
-                      known_mask=known_mask, jump_length=a.jump_length, jump_n_sample=a.jump_n_sample)
+                      known_mask=known_mask, jump_length=a.jump_length, jump_n_sample=a.jump_n_sample, **kw)
         write(result_path, images.contiguous(), seed)
         if seed == 0:
             write(target_path, jpg, seed)
@@ -207,6 +210,7 @@ def main(argv=None):
     from .encoders import SparseRangeImageEncoder2
     from .params import unet_param_shapes, vae_param_shapes
     from .pipelines import LDMUpscalePipelineRange
+    from .rng import DeviceGenerator
     from .synth import synth_state_dict
     from .unet import UNet2DModelHIP
     from .vae import AutoencoderKLHIP
@@ -260,11 +264,13 @@ def main(argv=None):
     n_iter = a.samples // B // world + 1                   # ldm/inference_conditional.py:158
     for i in range(n_iter):
         seed = rank + world * i
-        generator = torch.Generator().manual_seed(seed)    # :159 (a CPU generator: x_T is drawn on the host, as there)
+        generator, kw = torch.Generator().manual_seed(seed), {}    # :159 (a CPU generator: x_T is drawn on the host, as there)
+        if a.device_rng:                                   # --seed and the global sample index (the draws of one call start at 0)
+            generator, kw = DeviceGenerator(a.seed), dict(sample_offset=D.global_sample_indices(i, B, rank, world)[0])
         images = pipe(image=batch["down"] if cfg["task"] == "upsample" else batch["masked_image"],
                       mask=None if cfg["task"] == "upsample" else batch["inpainting_mask"],
                       condition_encoder=condition_encoder, generator=generator, batch_size=B,
-                      num_inference_steps=steps, output_type="torch")
+                      num_inference_steps=steps, output_type="torch", **kw)
         write(result_path, images, seed)
         if seed == 0:                                      # :196-210
             write(target_path, jpg, seed)

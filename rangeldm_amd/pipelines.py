@@ -6,6 +6,12 @@ Two execution modes, same results:
     step, VAE decode -- runs as HIP graphs inside librangeldm_hip (`rldm_sample`); one host call per batch.
   * `fused=False`: the reference's Python loop verbatim, each `unet(...)` / `scheduler.step(...)` / `vae.decode(...)`
     going through the C ABI individually (this is what "ldm/pipelines.py calls it unchanged" exercises).
+
+`generator=rng.DeviceGenerator(seed)` (with `sample_offset=`): the noise comes from the counter-based generator of csrc/rng.hip.  A
+pipeline call consumes ONE draw d: x_T is (d, purpose 0, row 0), the step noise of row r (d, 1, r), the known-region noise (d, 2, r),
+the re-noise (d, 3, r); sample b of the call is sample_offset + b.  fused=True draws the rows inside the step graph (rldm_sample_rng /
+rldm_sample_guided_rng: one row buffer per lane, no [rows, B, ...] tensor); fused=False draws the same values row by row with
+rng.randn.  Explicit latents= / step_noise= / known_noise= / renoise_noise= keep priority.  DDIM and DPM-Solver++ draw only x_T.
 """
 import ctypes as C
 import inspect
@@ -14,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .rng import DeviceGenerator, randn, randn_rows
 from .schedulers import (DDIMSchedulerHIP, DDPMSchedulerHIP, DPMSolverMultistepSchedulerHIP, guided_step, randn_tensor,
                          repaint_program)
 
@@ -112,6 +119,29 @@ class _FusedSampler:
         if check:
             self.status(h)
 
+    def run_rng(self, h, x_T, seed, draw, sample_offset, cond, out, latents_out=None, check=True):
+        """One rldm_sample_rng call: (seed, draw, sample_offset) in place of step_noise; x_T None = drawn (purpose 0); `check` as in run."""
+        def p(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        dev = next(t for t in (x_T, out, latents_out) if t is not None).device
+        _lib.check(_lib.lib().rldm_sample_rng(h, p(x_T), int(seed), int(draw), int(sample_offset), p(cond), p(out), p(latents_out),
+                                              _lib.stream_ptr(dev)), "rldm_sample_rng")
+        if check:
+            self.status(h)
+
+    def run_guided_rng(self, h, x_T, seed, draw, sample_offset, known, mask, out, latents_out=None, check=True):
+        """One rldm_sample_guided_rng call on a sampler made with `program`; `check` as in run."""
+        def p(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(_lib.lib().rldm_sample_guided_rng(h, p(x_T), int(seed), int(draw), int(sample_offset), p(known), p(mask), p(out),
+                                                     p(latents_out), _lib.stream_ptr(known.device)), "rldm_sample_guided_rng")
+        if check:
+            self.status(h)
+
+    def captures(self, h):
+        """rldm_debug_sampler_captures: step graphs this sampler has captured so far."""
+        return int(_lib.lib().rldm_debug_sampler_captures(h))
+
     def status(self, h):
         """rldm_sampler_status: waits for the sampler's last call; raises if its outputs are invalid."""
         _lib.check(_lib.lib().rldm_sampler_status(h), "rldm_sample (self-check of the persistent launches)")
@@ -197,16 +227,19 @@ class _PipelineBase:
 
 
     def _guided_latents(self, vae, x_T, z0, mask, num_inference_steps, jump_length, jump_n_sample, generator, step_noise, known_noise,
-                        renoise_noise, fused, check, out=None):
+                        renoise_noise, fused, check, out=None, draw=None, sample_offset=0):
         """The guided loop (schedulers.repaint_program) on the unconditional UNet: x_T, z0 (B, C, W, H) and mask (B, 1, W, H) at the
         UNet's sample resolution -> the final sample; with `out` (and a VAE, fused) the decoded images are written as well.
         Noise not injected is drawn from `generator` in this order: the step noise (one draw per row with sigma != 0), the
-        known-region noise (rows with kb != 0), the re-noise (rows that jump)."""
+        known-region noise (rows with kb != 0), the re-noise (rows that jump).  A DeviceGenerator (`draw`: the call's draw) addresses
+        row r of each purpose instead; with nothing injected the fused loop draws the rows itself."""
         dev = self.device
         sch = self.scheduler
         ts, table = repaint_program(sch, num_inference_steps, jump_length, jump_n_sample)
         rows, shape = len(ts), tuple(x_T.shape)
         mode = _sampler_mode(sch)
+        dev_rng = isinstance(generator, DeviceGenerator)
+        in_graph = dev_rng and fused and step_noise is None and known_noise is None and renoise_noise is None
 
         def per_row(given, col, name):
             need = table[:, col] != 0.0 if col != 7 else (table[:, 7] != 1.0) | (table[:, 8] != 0.0)
@@ -214,8 +247,10 @@ class _PipelineBase:
                 if tuple(given.shape) != (rows, *shape):
                     raise ValueError(f"{name} shape {tuple(given.shape)} != {(rows, *shape)} (one slice per row of the program)")
                 return given.to(dev, torch.float32).contiguous()
-            if not need.any():
+            if not need.any() or in_graph:
                 return None
+            if dev_rng:
+                return randn_rows(rows, shape, generator, draw, {4: 1, 6: 2, 7: 3}[col], sample_offset, dev)
             zs = torch.zeros((rows, *shape), device=dev, dtype=torch.float32)
             for i in np.nonzero(need)[0]:
                 zs[i] = randn_tensor(shape, generator=generator, device=dev, dtype=torch.float32)
@@ -228,6 +263,12 @@ class _PipelineBase:
         mask = mask.to(dev, torch.float32).expand(shape[0], 1, *shape[2:]).contiguous()
         if z0.shape != x.shape:
             raise ValueError(f"known sample {tuple(z0.shape)} != sample shape {shape}")
+        if in_graph:
+            h = self._fused.get(self.unet, vae, sch, shape[0], rows, mode, self.pos_encoding, 0, program=(ts, table))
+            lat = torch.empty_like(x)
+            self._fused.run_guided_rng(h, x, generator.seed, draw, sample_offset, z0, mask, out if vae is not None else None,
+                                       latents_out=lat, check=check)
+            return lat
         if fused:
             if zs is None and mode == _lib.RLDM_SAMPLER_DDPM:      # (a one-row program: sigma == 0, the tensor is still asked for)
                 zs = torch.zeros((rows, *shape), device=dev, dtype=torch.float32)
@@ -255,21 +296,35 @@ class DDPMPipelineRange(_PipelineBase):
 
     @torch.no_grad()
     def __call__(self, batch_size=1, generator=None, num_inference_steps=1000, output_type="torch", return_dict=True,
-                 fused=True, latents=None, step_noise=None, **kwargs):
+                 fused=True, latents=None, step_noise=None, sample_offset=0, **kwargs):
         """`latents` / `step_noise` (not in the reference signature): x_T and the [steps][B, C, W, H] ancestral noise
-        already on the device, instead of drawing them from `generator`."""
+        already on the device, instead of drawing them from `generator`.  `sample_offset`: the first sample's index (DeviceGenerator)."""
         cfg = self.unet.config
         ss = cfg.sample_size if not isinstance(cfg.sample_size, int) else (cfg.sample_size, cfg.sample_size)
         shape = (batch_size, cfg.in_channels, *ss)
+        dev_rng = isinstance(generator, DeviceGenerator)
+        draw = generator.next_draw() if dev_rng else None
+        # the captured loop draws x_T (when it is not given) and every row of step noise by itself
+        in_graph = fused and dev_rng and step_noise is None and isinstance(self.scheduler, DDPMSchedulerHIP)
         if latents is not None:
             if tuple(latents.shape) != shape:
                 raise ValueError(f"latents shape {tuple(latents.shape)} != {shape}")
             image = latents.to(device=self.device, dtype=torch.float32)
+        elif in_graph:
+            image = None
+        elif dev_rng:
+            image = randn(shape, generator.at(draw), sample_offset, self.device)
         else:
             image = randn_tensor(shape, generator=generator, device=self.device, dtype=torch.float32)
         self.scheduler.set_timesteps(num_inference_steps)
         is_dpm = isinstance(self.scheduler, DPMSolverMultistepSchedulerHIP)
-        if fused and (isinstance(self.scheduler, DDPMSchedulerHIP) or is_dpm):
+        if in_graph:
+            h = self._fused.get(self.unet, None, self.scheduler, batch_size, num_inference_steps, _lib.RLDM_SAMPLER_DDPM, False, 0)
+            out = torch.empty(shape, device=self.device, dtype=torch.float32)
+            self._fused.run_rng(h, image.contiguous() if image is not None else None, generator.seed, draw, sample_offset, None, out,
+                                check=kwargs.get("check", True))
+            image = out
+        elif fused and (isinstance(self.scheduler, DDPMSchedulerHIP) or is_dpm):
             zs = None
             if not is_dpm:
                 zs = step_noise if step_noise is not None else self._draw_step_noise(
@@ -284,6 +339,10 @@ class DDPMPipelineRange(_PipelineBase):
             for i, t in enumerate(self.progress_bar(self.scheduler.timesteps)):
                 model_output = self.unet(image, t).sample
                 kw = {"noise": step_noise[i]} if step_noise is not None and not is_dpm else {"generator": generator}
+                if dev_rng:
+                    kw.pop("generator", None)
+                    if step_noise is None and isinstance(self.scheduler, DDPMSchedulerHIP):
+                        kw["noise"] = randn(shape, generator.at(draw, 1, i), sample_offset, self.device)
                 image = self.scheduler.step(model_output, t, image, **kw).prev_sample
         return self._finish(image, output_type, return_dict)
 
@@ -300,7 +359,7 @@ class DDIMPipelineRange(_PipelineBase):
     @torch.no_grad()
     def __call__(self, batch_size=1, generator=None, eta=0.0, num_inference_steps=50, use_clipped_model_output=None,
                  output_type="torch", return_dict=True, fused=True, latents=None, known=None, known_mask=None, jump_length=1,
-                 jump_n_sample=1, known_noise=None, renoise_noise=None, **kwargs):
+                 jump_n_sample=1, known_noise=None, renoise_noise=None, sample_offset=0, **kwargs):
         """`latents` (not in the reference signature): x_T already resident on the device, instead of drawing it.
         `known` (B, C, W, H normalised range image) + `known_mask` (B, 1, W, H; 1 / True = known, any pattern -- every 4th beam
         densifies): guided completion with these unconditional weights (schedulers.repaint_program; jump_length / jump_n_sample
@@ -308,6 +367,10 @@ class DDIMPipelineRange(_PipelineBase):
         cfg = self.unet.config
         ss = cfg.sample_size if not isinstance(cfg.sample_size, int) else (cfg.sample_size, cfg.sample_size)
         shape = (batch_size, cfg.out_channels, *ss)
+        dev_rng = isinstance(generator, DeviceGenerator)
+        draw = generator.next_draw() if dev_rng else None
+        if dev_rng and eta != 0.0:
+            raise NotImplementedError("DDIM with eta > 0 draws its variance noise from a torch generator")
         if isinstance(generator, list) and len(generator) != batch_size:
             raise ValueError(
                 f"You have passed a list of generators of length {len(generator)}, but requested an effective batch"
@@ -316,6 +379,8 @@ class DDIMPipelineRange(_PipelineBase):
             if tuple(latents.shape) != shape:
                 raise ValueError(f"latents shape {tuple(latents.shape)} != {shape}")
             image = latents.to(device=self._execution_device, dtype=self.unet.dtype)
+        elif dev_rng:
+            image = randn(shape, generator.at(draw), sample_offset, self._execution_device)
         else:
             image = randn_tensor(shape, generator=generator, device=self._execution_device, dtype=self.unet.dtype)
         self.scheduler.set_timesteps(num_inference_steps)
@@ -326,7 +391,8 @@ class DDIMPipelineRange(_PipelineBase):
                 raise NotImplementedError("guided DDIM sampling is eta = 0")
             m = (known_mask.to(torch.float32) > 0.5).to(torch.float32)
             image = self._guided_latents(None, image, known, m, num_inference_steps, jump_length, jump_n_sample, generator, None,
-                                         known_noise, renoise_noise, fused, kwargs.get("check", True))
+                                         known_noise, renoise_noise, fused, kwargs.get("check", True), draw=draw,
+                                         sample_offset=sample_offset)
             return self._finish(image, output_type, return_dict)
         if fused and eta == 0.0:
             h = self._fused.get(self.unet, None, self.scheduler, batch_size, num_inference_steps, 0,
@@ -345,7 +411,7 @@ class DDIMPipelineRange(_PipelineBase):
                 model_output = self.unet(model_input, t).sample
                 image = self.scheduler.step(model_output, t, image, eta=eta,
                                             use_clipped_model_output=use_clipped_model_output,
-                                            generator=generator).prev_sample
+                                            generator=None if dev_rng else generator).prev_sample
         return self._finish(image, output_type, return_dict)
 
 
@@ -362,7 +428,7 @@ class LDMPipelineRange(_PipelineBase):
     @torch.no_grad()
     def __call__(self, batch_size=1, generator=None, eta=0.0, num_inference_steps=50, output_type="torch",
                  return_dict=True, final_only=True, fused=True, latents=None, step_noise=None, known=None, known_mask=None,
-                 jump_length=1, jump_n_sample=1, known_noise=None, renoise_noise=None, **kwargs):
+                 jump_length=1, jump_n_sample=1, known_noise=None, renoise_noise=None, sample_offset=0, **kwargs):
         """`known` (B, 2, W, H normalised range image) + `known_mask` (B, 1, W, H pixel mask; 1 / True = known): guided completion
         with these unconditional weights.  z0 = vae.encode(known).latent_dist.mode() * scaling_factor; a latent pixel counts as
         known only if its whole footprint is (latent_known_mask), so an azimuth-span mask works and a beam-subsampling mask raises.
@@ -370,7 +436,11 @@ class LDMPipelineRange(_PipelineBase):
         `return_latents=True` (guided only) returns (images, final latents, z0, latent mask)."""
         cfg = self.unet.config
         shape = (batch_size, cfg.out_channels, *cfg.sample_size)
-        if latents is None:
+        dev_rng = isinstance(generator, DeviceGenerator)
+        draw = generator.next_draw() if dev_rng else None
+        if latents is None and dev_rng:
+            latents = randn(shape, generator.at(draw), sample_offset, self.device)
+        elif latents is None:
             latents = randn_tensor(shape, generator=generator)          # CPU draw, as ldm/pipelines.py:329-333
         latents = latents.to(self.device)
         latents = latents * self.scheduler.init_noise_sigma
@@ -378,6 +448,8 @@ class LDMPipelineRange(_PipelineBase):
         accepts_eta = "eta" in set(inspect.signature(self.scheduler.step).parameters.keys())
         is_ddim = isinstance(self.scheduler, DDIMSchedulerHIP)
         is_ddpm = isinstance(self.scheduler, DDPMSchedulerHIP)
+        if dev_rng and is_ddim and eta != 0.0:
+            raise NotImplementedError("DDIM with eta > 0 draws its variance noise from a torch generator")
         if known is not None:
             if known_mask is None:
                 raise ValueError("`known` needs `known_mask`")
@@ -392,7 +464,8 @@ class LDMPipelineRange(_PipelineBase):
             image = torch.empty((batch_size, self.vae._cfg.out_channels, shape[2] * f, shape[3] * f), device=self.device,
                                 dtype=torch.float32)
             lat = self._guided_latents(self.vae, latents.float(), z0, lat_mask, num_inference_steps, jump_length, jump_n_sample,
-                                       generator, step_noise, known_noise, renoise_noise, fused, kwargs.get("check", True), out=image)
+                                       generator, step_noise, known_noise, renoise_noise, fused, kwargs.get("check", True), out=image,
+                                       draw=draw, sample_offset=sample_offset)
             if not fused:
                 image = self.vae.decode(lat / sf).sample
             if kwargs.get("return_latents", False):
@@ -400,8 +473,9 @@ class LDMPipelineRange(_PipelineBase):
             return self._finish(image, output_type, return_dict)
         if fused and final_only and (not is_ddim or eta == 0.0):
             mode = _sampler_mode(self.scheduler)
+            in_graph = dev_rng and mode == _lib.RLDM_SAMPLER_DDPM and step_noise is None
             zs = None
-            if mode == _lib.RLDM_SAMPLER_DDPM:
+            if mode == _lib.RLDM_SAMPLER_DDPM and not in_graph:
                 zs = step_noise if step_noise is not None else self._draw_step_noise(
                     num_inference_steps, self.scheduler.timesteps, shape, generator, self.device)
                 zs = zs.to(self.device, torch.float32).contiguous()
@@ -410,7 +484,11 @@ class LDMPipelineRange(_PipelineBase):
             f = self.vae._cfg.downscale
             image = torch.empty((batch_size, self.vae._cfg.out_channels, shape[2] * f, shape[3] * f),
                                 device=self.device, dtype=torch.float32)
-            self._fused.run(h, latents.float().contiguous(), zs, None, image, check=kwargs.get("check", True))
+            if in_graph:
+                self._fused.run_rng(h, latents.float().contiguous(), generator.seed, draw, sample_offset, None, image,
+                                    check=kwargs.get("check", True))
+            else:
+                self._fused.run(h, latents.float().contiguous(), zs, None, image, check=kwargs.get("check", True))
             return self._finish(image, output_type, return_dict)
         extra_kwargs = {"eta": eta} if accepts_eta else {}
         if self.pos_encoding:
@@ -429,6 +507,8 @@ class LDMPipelineRange(_PipelineBase):
             kw = dict(extra_kwargs)
             if step_noise is not None and is_ddpm:
                 kw["noise"] = step_noise[i]
+            elif dev_rng and is_ddpm:
+                kw["noise"] = randn(shape, generator.at(draw, 1, i), sample_offset, self.device)
             latents = self.scheduler.step(noise_prediction, t, latents, **kw).prev_sample
         latents = latents / self.vae.config.scaling_factor
         image = self.vae.decode(latents).sample
@@ -459,19 +539,26 @@ class LDMUpscalePipelineRange(_PipelineBase):
     @torch.no_grad()
     def __call__(self, image, mask=None, condition_encoder=None, batch_size=1, generator=None, eta=0.0,
                  num_inference_steps=50, output_type="torch", return_dict=True, fused=True, latents=None,
-                 step_noise=None, encode_noise=None, **kwargs):
+                 step_noise=None, encode_noise=None, sample_offset=0, **kwargs):
+        """A DeviceGenerator gives the in-painting posterior draw (encode_noise) a draw of its own, before the sampler's."""
         if image is None:
             raise ValueError("`image` input cannot be undefined.")
         cfg = self.unet.config
         shape = (batch_size, cfg.out_channels, *cfg.sample_size)
-        if latents is None:
+        dev_rng = isinstance(generator, DeviceGenerator)
+        if dev_rng and mask is not None and encode_noise is None:
+            encode_noise = randn(shape, generator, sample_offset, self.unet.device)
+        draw = generator.next_draw() if dev_rng else None
+        if latents is None and dev_rng:
+            latents = randn(shape, generator.at(draw), sample_offset, self.unet.device)
+        elif latents is None:
             latents = randn_tensor(shape, generator=generator)
         latents = latents.to(self.unet.device)
         if mask is None:
             assert condition_encoder is not None
             image = condition_encoder(image)
         else:
-            image = self.encode_masked_image(image, mask, generator=generator, noise=encode_noise)
+            image = self.encode_masked_image(image, mask, generator=None if dev_rng else generator, noise=encode_noise)
         image = image.to(dtype=latents.dtype, device=self.unet.device)
         height, width = image.shape[2:]
         assert cfg.in_channels == cfg.out_channels + image.shape[1]
@@ -484,8 +571,9 @@ class LDMUpscalePipelineRange(_PipelineBase):
         is_ddpm = isinstance(self.scheduler, DDPMSchedulerHIP)
         if fused and (not is_ddim or eta == 0.0):
             mode = _sampler_mode(self.scheduler)
+            in_graph = dev_rng and mode == _lib.RLDM_SAMPLER_DDPM and step_noise is None
             zs = None
-            if mode == _lib.RLDM_SAMPLER_DDPM:
+            if mode == _lib.RLDM_SAMPLER_DDPM and not in_graph:
                 zs = step_noise if step_noise is not None else self._draw_step_noise(
                     num_inference_steps, self.scheduler.timesteps, shape, generator, self.device)
                 zs = zs.to(self.device, torch.float32).contiguous()
@@ -494,7 +582,11 @@ class LDMUpscalePipelineRange(_PipelineBase):
             f = self.vae._cfg.downscale
             out = torch.empty((batch_size, self.vae._cfg.out_channels, shape[2] * f, shape[3] * f),
                               device=self.device, dtype=torch.float32)
-            self._fused.run(h, latents.float().contiguous(), zs, image.float().contiguous(), out, check=kwargs.get("check", True))
+            if in_graph:
+                self._fused.run_rng(h, latents.float().contiguous(), generator.seed, draw, sample_offset, image.float().contiguous(), out,
+                                    check=kwargs.get("check", True))
+            else:
+                self._fused.run(h, latents.float().contiguous(), zs, image.float().contiguous(), out, check=kwargs.get("check", True))
             return self._finish(out, output_type, return_dict)
         extra_kwargs = {"eta": eta} if accepts_eta else {}
         for i, t in enumerate(self.progress_bar(self.scheduler.timesteps)):
@@ -504,6 +596,8 @@ class LDMUpscalePipelineRange(_PipelineBase):
             kw = dict(extra_kwargs)
             if step_noise is not None and is_ddpm:
                 kw["noise"] = step_noise[i]
+            elif dev_rng and is_ddpm:
+                kw["noise"] = randn(shape, generator.at(draw, 1, i), sample_offset, self.device)
             latents = self.scheduler.step(noise_prediction, t, latents, **kw).prev_sample
         latents = latents / self.vae.config.scaling_factor
         out = self.vae.decode(latents).sample

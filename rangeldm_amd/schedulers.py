@@ -23,7 +23,12 @@ class SchedulerOutput:
 
 
 def randn_tensor(shape, generator=None, device=None, dtype=None):
-    """diffusers.utils.torch_utils.randn_tensor semantics: a CPU generator draws on the CPU and moves."""
+    """diffusers.utils.torch_utils.randn_tensor semantics: a CPU generator draws on the CPU and moves.  A rng.DeviceGenerator draws
+    on the device with rng.randn (fp32, one draw consumed, shape[0] the sample axis)."""
+    from .rng import DeviceGenerator, StreamAddress, randn
+    if isinstance(generator, (DeviceGenerator, StreamAddress)):
+        x = randn(shape, generator, device=device if device is not None else "cuda")
+        return x if dtype in (None, torch.float32) else x.to(dtype)
     device = torch.device(device) if device is not None else torch.device("cpu")
     rand_device = device
     if generator is not None:

@@ -728,7 +728,7 @@ def encode_ahead(vae, clean_images, stream, generator=None):
 
 
 def training_step(trainer, vae, noise_scheduler, clean_images, generator=None, pos_encoding=True, snr_gamma=None,
-                  noise=None, timesteps=None, condition=None, graphed=False, latents=None):
+                  noise=None, timesteps=None, condition=None, graphed=False, latents=None, sample_offset=0):
     """One iteration of the reference's loop body (ldm/train_unconditional.py:479-556) with `with_vae: True`:
     latents = vae.encode(x).latent_dist.sample() * scaling_factor; eps ~ N(0, 1); t ~ U{0..T-1}; add_noise; pos-encoding
     channel; epsilon- or v-prediction MSE (optionally min-SNR weighted); backward; clip; AdamW; lr schedule; EMA.
@@ -738,17 +738,33 @@ def training_step(trainer, vae, noise_scheduler, clean_images, generator=None, p
     latents: `vae.encode(clean_images).latent_dist.sample() * scaling_factor` computed by the caller (input pipelining:
     `encode_ahead`); clean_images is ignored then.
     The step runs in the trainer's mode: `UNetTrainer(deterministic=True)` makes the UNet forward / loss / backward / optimizer
-    bit-reproducible (the VAE encode, the noise draw and a multi-rank RCCL all-reduce are outside that guarantee)."""
+    bit-reproducible (the VAE encode, the noise draw and a multi-rank RCCL all-reduce are outside that guarantee).
+    generator: a torch generator draws noise and timesteps on the host; a rng.DeviceGenerator draws the noise on the device
+    (rng.randn at `sample_offset`, the first sample's global index) and takes the B timesteps from rng.timesteps_host, both at one
+    draw -- after a draw of its own for the posterior sample when this call encodes."""
+    from .rng import DeviceGenerator, randn, timesteps_host
     dev = trainer.device
+    dev_rng = isinstance(generator, DeviceGenerator)
     if latents is not None:                 # encoded ahead of time (e.g. on a second stream while the previous step ran)
         latents = latents.to(dev).float()
+    elif vae is not None and dev_rng:
+        dist = vae.encode(clean_images.to(dev)).latent_dist
+        Bz, z2, zw, zh = dist.parameters.shape
+        latents = dist.sample(noise=randn((Bz, z2 // 2, zw, zh), generator, sample_offset, dev), scale=vae.config.scaling_factor)
     elif vae is not None:
         latents = vae.encode(clean_images.to(dev)).latent_dist.sample(generator=generator, scale=vae.config.scaling_factor)
     else:
         latents = clean_images.to(dev).float()
     B = latents.shape[0]
+    if dev_rng and (noise is None or timesteps is None):
+        draw = generator.next_draw()
+        if noise is None:
+            noise = randn(tuple(latents.shape), generator.at(draw), sample_offset, dev)
+        if timesteps is None:
+            timesteps = torch.from_numpy(timesteps_host(B, generator.seed, draw, noise_scheduler.config.num_train_timesteps, sample_offset))
     if noise is None:
         noise = torch.randn(latents.shape, generator=generator, dtype=torch.float32).to(dev)
+    noise = noise.to(dev)                   # (it is the regression target as well: the loss kernel reads it on the device)
     if timesteps is None:
         timesteps = torch.randint(0, noise_scheduler.config.num_train_timesteps, (B,), generator=generator).long()
     noisy = noise_scheduler.add_noise(latents, noise, timesteps)

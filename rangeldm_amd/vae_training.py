@@ -422,17 +422,23 @@ class VAETrainer(_VAETape):
         """The last forward's z as (B, z_channels, W / f, H / f): what its decoder saw."""
         return T.unpack_output(self._z)
 
-    def train_step(self, images, noise=None, generator=None, sample_posterior=True, as_float=False):
+    def train_step(self, images, noise=None, generator=None, sample_posterior=True, as_float=False, sample_offset=0):
         """moments = encoder(images); z = mean + std noise (sample_posterior=False: z = mean); pred = decoder(z);
         loss = (1 / B) sum wc[c] |pred - images| + kl_weight kl; backward through decoder, posterior and encoder; one Adam step over
-        all parameters.  noise: (B, z_channels, W / f, H / f); None draws it on the host from `generator`, as the reference does.
+        all parameters.  noise: (B, z_channels, W / f, H / f); None draws it on the host from `generator`, as the reference does, or
+        on the device when `generator` is a rng.DeviceGenerator (rng.randn, one draw, at `sample_offset`).
         Returns the loss: a 0-d float64 device tensor (no host sync), or a Python float with as_float.  `last_abs_sums` as
         VAEDecoderTrainer's; `last_kl`: the KL term, a 0-d float64 device tensor.  In the adversarial phase: as VAEDecoderTrainer's
         (the returned loss stays L1 + kl_weight kl; the discriminator is given `images` as the real batch)."""
         images = images.to(self.device).float().contiguous()
         if sample_posterior and noise is None:
+            from .rng import DeviceGenerator, randn
             f = self.cfg.downscale
-            noise = torch.randn((images.shape[0], self.cfg.z_channels, images.shape[2] // f, images.shape[3] // f), generator=generator)
+            zshape = (images.shape[0], self.cfg.z_channels, images.shape[2] // f, images.shape[3] // f)
+            if isinstance(generator, DeviceGenerator):
+                noise = randn(zshape, generator, sample_offset, self.device)
+            else:
+                noise = torch.randn(zshape, generator=generator)
         with self._mode():
             pred = self.forward(images, noise if sample_posterior else None)
             rec = self._reconstruction_step(pred, images)
