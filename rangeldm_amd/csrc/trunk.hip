@@ -12,7 +12,7 @@
 // previous phase (the next phase's weight fragments are requested behind the K loop).
 //
 // A phase = conv_small_body<..., TRUNK = true> on a ConvParams record in device memory.  Nothing here orders workgroups of
-// DIFFERENT images: they drift apart freely (so activations of a segment are never recycled inside it: runtime.hip defers the
+// DIFFERENT images: they drift apart freely (so activations of a segment are never recycled inside it: plan.hip defers the
 // arena releases to the segment's end).
 //
 // Second generation: the same seam for images of SEVERAL tiles.  At 13..16 images an image is 16 workgroups at every level --

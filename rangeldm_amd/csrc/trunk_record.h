@@ -1,4 +1,4 @@
-// The phase record of the persistent trunk launch (trunk.hip): the format, the plan builder's encoders (runtime.hip) and the kernel's
+// The phase record of the persistent trunk launch (trunk.hip): the format, the plan builder's encoders (plan.hip) and the kernel's
 // decoders, side by side -- a field added to one must be added to the other.
 #pragma once
 #include "kernels.h"

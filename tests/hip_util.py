@@ -286,7 +286,7 @@ def silu_targets(values):
 # permuted differently per (image, head)), dim 6 a tier (qh = 8) that lifts or sinks whole key tiles, dim 7 a fine tier (qh = 1/4).
 # Every value is a bit pattern of per-token +-1 "bits" through one linear map, so the same q / k / v can also come out of
 # GroupNorm -> to_q / to_k / to_v: x carries each bit and its negation in adjacent channels (every group: mean 0, variance 1).
-QS_INFER = float(np.float32(1.4426950408889634) / np.sqrt(np.float32(8.0)))          # attention.hip / runtime.hip (host, fp32)
+QS_INFER = float(np.float32(1.4426950408889634) / np.sqrt(np.float32(8.0)))          # attention.hip / attn_q_scale, runtime.h (host, fp32)
 QS_TRAIN = float(np.float32(0.35355339059327373) * np.float32(1.4426950408889634))   # train_attn.hip kScale * kLog2e (fp32)
 R2_MARGINS, R3_MARGINS = (32, 48, 64, 88), (144, 160, 200)
 

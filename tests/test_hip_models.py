@@ -608,7 +608,7 @@ def test_two_samplers_on_two_streams_do_not_share_persistent_launches():
 
 
 def test_concurrent_chains_match_single_chain(monkeypatch):
-    """The sampler splits a batch >= 32 into chains of >= 16 samples on separate streams (sampler_num_lanes, runtime.hip);
+    """The sampler splits a batch >= 32 into chains of >= 16 samples on separate streams (sampler_num_lanes, sampler.hip);
     RLDM_LANES forces the split at a small batch here.  Samples never interact, so the chains must reproduce the
     single-chain images (up to the tile routing, which depends on the chain's batch) -- for DDIM and for the DDPM mode,
     whose step noise is sliced per chain."""
@@ -630,6 +630,55 @@ def test_concurrent_chains_match_single_chain(monkeypatch):
         assert rel_l2(out["4"], out["1"]) < 2e-2, sched.__name__
         for j in range(4):                                              # every sample, not just the average
             assert rel_l2(out["2"][j], out["1"][j]) < 3e-2
+
+
+@pytest.mark.gpu
+def test_graph_trace_names_only_a_live_plan():
+    """rldm_debug_graph_trace walks the ops of the plan the last traced step ran.  That plan belongs to a sampler lane: once the
+    sampler is destroyed there is no traced plan and the call returns 0 (as before any trace was taken), and a second traced
+    sampler makes the trace live again.  Smallest shape that builds a plan: the smoke UNet, no VAE, batch 2, 2 DDIM steps."""
+    import ctypes as C
+    from rangeldm_amd import _lib
+    from rangeldm_amd.schedulers import DDIMSchedulerHIP
+    cfg = UNetConfig(sample_size=(64, 8), block_out_channels=(32, 32, 64, 64))
+    unet, _ = hip_unet(cfg, "trace.")
+    x_T = T(normal(21, "trace/xT", (2, 4, 64, 8))).cuda()
+    out = torch.empty_like(x_T)
+    sched = DDIMSchedulerHIP()
+    sched.set_timesteps(2)
+    ts = np.ascontiguousarray(sched.timesteps.numpy().astype(np.int64))
+    coef = sched.sampler_table(0.0)
+    L = _lib.lib()
+
+    def trace():
+        stamps = (C.c_ulonglong * 4096)()
+        names = C.create_string_buffer(1 << 16)
+        n = L.rldm_debug_graph_trace(stamps, 4096, names, len(names))
+        return n, [s for s in names.value.decode().split("\n") if s]
+
+    def traced_sample():
+        sc = _lib.SamplerConfigC()
+        sc.batch, sc.num_steps, sc.mode, sc.pos_encoding = 2, 2, _lib.RLDM_SAMPLER_DDIM, 1
+        sc.plan_flags = int(Flag.GRAPH_TRACE)
+        sc.coef = coef.ctypes.data_as(C.POINTER(C.c_float))
+        sc.timesteps = ts.ctypes.data_as(C.POINTER(C.c_int64))
+        h = C.c_void_p()
+        _lib.check(L.rldm_sampler_create(unet._h, None, C.byref(sc), C.byref(h)), "rldm_sampler_create")
+        _lib.check(L.rldm_sample(h, C.c_void_p(x_T.data_ptr()), None, None, C.c_void_p(out.data_ptr()), None,
+                                 _lib.stream_ptr(x_T.device)), "rldm_sample")
+        _lib.check(L.rldm_sampler_status(h), "rldm_sampler_status")
+        return h
+
+    h = traced_sample()
+    n, names = trace()
+    assert n > 0 and len(names) == n
+    L.rldm_sampler_destroy(h)
+    assert trace()[0] == 0
+    h2 = traced_sample()
+    n2, names2 = trace()
+    L.rldm_sampler_destroy(h2)
+    assert n2 == n and names2 == names
+    assert torch.isfinite(out).all()
 
 
 # ---- goldens computed BY REFERENCE CODE (oracle/validate_unet_against_reference.py): the skip-concat / temb UNet `Model`
