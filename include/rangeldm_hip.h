@@ -1137,6 +1137,13 @@ typedef struct rldm_conv_sched_desc {
  * output.  op_name receives the name of the launch that carried the step (e.g. "conv_o4_kernel<128,32,taps9>"). */
 int rldm_test_conv_sched(const rldm_conv_desc* d, const float* x0, const float* weight, const float* bias, const float* gamma,
                          const float* beta, const rldm_conv_sched_desc* sch, float* eps, char* op_name, size_t name_cap, void* stream);
+/* (tests) the time-embedding table on its own: n timesteps (host), converted as rldm_unet_forward converts them, through the model's
+ * Timesteps -> TimestepEmbedding -> every resnet's time_emb_proj(SiLU(emb)) launches -> table device fp32 [n][ld].  The model needs
+ * to be finalized only; any n >= 1 (a forward takes 1 or B rows, a sampler num_steps). */
+int rldm_test_temb(rldm_unet* m, const int64_t* timesteps, int n, float* table, void* stream);
+/* (tests) the table's layout: resnet_prefix NULL -> *value = ld, the row length; else (e.g. "down_blocks.0.resnets.1") the column
+ * at which that resnet's projection starts (its out_channels columns follow).  Fails on a prefix the model does not have. */
+int rldm_test_temb_layout(rldm_unet* m, const char* resnet_prefix, int* value);
 /* multi-head (d=8) self-attention core: qkv device fp32 [B][L][3C] -> out device fp32 [B][L][C] */
 int rldm_test_attention(const float* qkv, int B, int L, int C, float* out, void* stream);
 /* the launch every attention block of the UNet actually runs -- GroupNorm -> to_q / to_k / to_v -> softmax(q k^T/sqrt 8) v

@@ -339,6 +339,9 @@ PROTOTYPES = {
     "rldm_test_conv_stats": (C.c_int, [C.POINTER(ConvDescC), _P, _P, _P, _P, _P]),
     "rldm_test_conv_sched": (C.c_int, [C.POINTER(ConvDescC), _P, _P, _P, _P, _P, C.POINTER(ConvSchedDescC), _P, C.c_char_p, C.c_size_t,
                                        _P]),
+    # the time-embedding table of n timesteps on its own, and its layout (row length; a resnet's first column)
+    "rldm_test_temb": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "rldm_test_temb_layout": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int)]),
     "rldm_debug_set_flags": (C.c_int, [C.c_int]),
     "rldm_debug_set_flags2": (C.c_int, [C.c_int]),
     "rldm_debug_graph_trace": (C.c_int, [_P, C.c_int, C.c_char_p, C.c_size_t]),

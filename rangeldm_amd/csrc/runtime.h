@@ -496,6 +496,7 @@ namespace rldm {
 // concurrent_plans: how many plans of this kind will run side by side (a sampler's chains)
 int unet_make_plan(rldm_unet* m, int B, std::unique_ptr<Plan>* out, int* launches = nullptr, int flags = 0, int concurrent_plans = 1);
 int unet_temb_ld(const rldm_unet* m);       // row length of the time-embedding table
+int unet_temb_off(const rldm_unet* m, const std::string& resnet_prefix);   // that resnet's first column in a row, or -1
 // time-embedding table for `rows` timesteps (host floats) into `tab`
 int unet_temb(rldm_unet* m, const float* t_dev, int rows, float* tab, hipStream_t s);
 int vae_make_plan(rldm_vae* m, int B, int w, int h, bool enc, std::unique_ptr<Plan>* out, int flags = 0);

@@ -427,6 +427,10 @@ rldm_unet::~rldm_unet() = default;
 rldm_vae::rldm_vae() : net(std::make_unique<NetCommon>()) {}
 rldm_vae::~rldm_vae() = default;
 int rldm::unet_temb_ld(const rldm_unet* m) { return m->net->temb_ld; }
+int rldm::unet_temb_off(const rldm_unet* m, const std::string& resnet_prefix) {
+    auto it = m->net->temb_off.find(resnet_prefix);
+    return it == m->net->temb_off.end() ? -1 : it->second;
+}
 
 static void unet_expect(rldm_unet* m) {
     const auto& c = m->cfg;

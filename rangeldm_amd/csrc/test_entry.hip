@@ -266,6 +266,28 @@ int rldm_bench_conv(const rldm_conv_desc* d, int with_res, int with_temb, int wa
     return timed_loop(st, iters, run_unit, avg_us);
 }
 
+// the time-embedding table of n timesteps, through the conversion and the call rldm_unet_forward and the samplers make
+int rldm_test_temb(rldm_unet* m, const int64_t* timesteps, int n, float* table, void* stream) {
+    RLDM_REQUIRE(m && timesteps && table && n >= 1, "bad argument");
+    RLDM_REQUIRE(m->params.finalized, "rldm_unet_finalize has not been called");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    std::vector<float> tf(n);
+    for (int i = 0; i < n; ++i) tf[i] = (float)timesteps[i];
+    DevBuf td;
+    if (upload(td, tf.data(), (size_t)n * 4)) return 1;
+    if (unet_temb(m, td.as<float>(), n, table, st)) return 1;
+    RLDM_HIP_CHECK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int rldm_test_temb_layout(rldm_unet* m, const char* resnet_prefix, int* value) {
+    RLDM_REQUIRE(m && value, "null argument");
+    RLDM_REQUIRE(m->params.finalized, "rldm_unet_finalize has not been called");
+    *value = resnet_prefix ? unet_temb_off(m, resnet_prefix) : unet_temb_ld(m);
+    RLDM_REQUIRE(*value >= 0, std::string("no resnet '") + resnet_prefix + "' with a time-embedding projection");
+    return 0;
+}
+
 int rldm_test_attention(const float* qkv, int B, int L, int C, float* out, void* stream) {
     RLDM_REQUIRE(qkv && out, "null argument");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

@@ -137,6 +137,34 @@ def hip_conv_sched(x0, weight, bias, gamma, beta, sampler_mode, prediction_type,
     return y, name.value.decode()
 
 
+def hip_temb_layout(model):
+    """rldm_test_temb_layout of a finalized UNet2DModelHIP -> (ld, {resnet prefix: first column}), the prefixes in column order."""
+    L = _lib.lib()
+    v = C.c_int(0)
+    _lib.check(L.rldm_test_temb_layout(model._h, None, C.byref(v)), "rldm_test_temb_layout")
+    ld = v.value
+    offs = {}
+    for name in model._shapes:
+        if name.endswith(".time_emb_proj.bias"):
+            prefix = name[:-len(".time_emb_proj.bias")]
+            _lib.check(L.rldm_test_temb_layout(model._h, prefix.encode(), C.byref(v)), "rldm_test_temb_layout")
+            offs[prefix] = v.value
+    return ld, dict(sorted(offs.items(), key=lambda kv: kv[1]))
+
+
+def hip_temb(model, timesteps, ld=None):
+    """rldm_test_temb: the time-embedding table of a finalized UNet2DModelHIP for `timesteps` (ints, any count >= 1), through the
+    conversion and the launches rldm_unet_forward and the samplers use.  -> fp32 [n][ld] on the CPU (ld: hip_temb_layout's, if known)."""
+    ts = np.ascontiguousarray(np.asarray(timesteps, dtype=np.int64).reshape(-1))
+    if ld is None:
+        ld = hip_temb_layout(model)[0]
+    tab = torch.empty((len(ts), ld), device=model.device, dtype=torch.float32)
+    _lib.check(_lib.lib().rldm_test_temb(model._h, ts.ctypes.data_as(C.c_void_p), len(ts), C.c_void_p(tab.data_ptr()),
+                                         _lib.stream_ptr(model.device)), "rldm_test_temb")
+    torch.cuda.synchronize()
+    return tab.cpu()
+
+
 def hip_attention_qkv(x, gamma, beta, wqkv, bqkv, groups=32, eps=1e-5):
     """rldm_test_attention_qkv: the fused GroupNorm -> q/k/v -> softmax.V launch of every UNet attention block.
     x (B, L, C) token-major fp32 -> (B, L, C) heads concatenated (before to_out)."""
