@@ -880,6 +880,25 @@ int rldm_train_l1(const float* pred, const float* target, const float* wc, int B
 int rldm_train_gaussian(const float* moments, const float* noise, int B, int W, int H, int Z, float* z, double* kl, void* stream);
 int rldm_train_gaussian_backward(const float* moments, const float* noise, const float* dz, float kw, int B, int W, int H, int Z,
                                  float* dmoments, void* stream);
+/* Decoder-guided sampling (csrc/guide.hip; rangeldm_amd/guidance.py restates each entry point in numpy): the measurement-consistency
+ * step on the clean-latent estimate z0 of a DDIM step.  Plain fp32, one rounding per stated operation (no contraction), for every
+ * setting of rldm_train_deterministic.
+ * _residual: xhat [B][W][H][C] (the tape decoder's reconstruction), y (B, C, W, H) the known image, m (B, 1, W, H) fp32 (> 0.5: known),
+ *   wc device [C].  d = xhat - y;  gx [B][W][H][C] = (2 wc[c]) d where known (one product: 2 wc[c] is exact), +0 elsewhere;
+ *   L device double [B], L[b] = sum over image b of wc[c] d d where known, fp64 per element, in ONE order at every call: element
+ *   256 i + t of the image (NHWC order) is lane t of partial i, a partial's 256 values are added as rldm_train_mse's binary tree, and the
+ *   image's partials are folded as mse's are (thread t adds partials t, t + 256, ... first).  No floating-point atomics.
+ * _latent:   zin [B][W][H][C] = z0 (B, C, W, H) * inv_sf: the decoder's input (inv_sf = 1 / scaling_factor rounded to fp32 by the caller).
+ * _update:   g [B][W][H][C] (the tape's input gradient), z0 / delta (B, C, W, H), both updated in place:
+ *   rho_b = (float)(scale / max(sqrt(L[b]), 1e-8)) evaluated in fp64 on the device (L NULL: rho = 1);  t = g * inv_sf;  u = rho_b * t;
+ *   z0 = z0 - u;  delta = delta + u.
+ * _correct:  out = z_plain - p with p = c * delta, and z_plain's own bits where p is a zero of either sign. */
+int rldm_guide_residual(const float* xhat, const float* y, const float* m, const float* wc, int B, int C, int W, int H, float* gx,
+                        double* L, void* stream);
+int rldm_guide_latent(const float* z0, float inv_sf, int B, int C, int W, int H, float* zin, void* stream);
+int rldm_guide_update(const float* g, const double* L, double scale, float inv_sf, int B, int C, int W, int H, float* z0, float* delta,
+                      void* stream);
+int rldm_guide_correct(const float* z_plain, const float* delta, float c, int64_t n, float* out, void* stream);
 int rldm_train_sqnorm(const float* g, int64_t n, double* out /*device*/, void* stream);
 typedef struct rldm_adamw_config {
     float lr, beta1, beta2, eps, weight_decay;  /* torch.optim.AdamW, ldm/train_unconditional.py:357-363           */

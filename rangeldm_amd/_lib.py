@@ -301,6 +301,12 @@ PROTOTYPES = {
     "rldm_train_gaussian": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "rldm_train_gaussian_backward": (C.c_int, [_P, _P, _P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rldm_train_sqnorm": (C.c_int, [_P, C.c_int64, _P, _P]),
+    # decoder-guided sampling (csrc/guide.hip): masked residual + its fixed-order fp64 sum, the decoder's input, the update of the
+    # clean-latent estimate, the correction of the plain DDIM step
+    "rldm_guide_residual": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "rldm_guide_latent": (C.c_int, [_P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "rldm_guide_update": (C.c_int, [_P, _P, C.c_double, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "rldm_guide_correct": (C.c_int, [_P, _P, C.c_float, C.c_int64, _P, _P]),
     "rldm_train_adamw": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(AdamWConfigC), _P]),
     "rldm_train_adamw_dyn": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(AdamWConfigC), _P, C.c_int, _P]),
     "rldm_train_hyper_step": (C.c_int, [_P, C.POINTER(HyperConfigC), _P, _P]),

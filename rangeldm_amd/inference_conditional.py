@@ -22,7 +22,12 @@ known-region replacement inside the captured loop (RePaint; rangeldm_amd.schedul
     python -m rangeldm_amd.inference_conditional --guided --task densification --cfg RangeDM --jump-length 10 --jump-n-sample 10
 
 The same folders are written (`inpainting_*` / `densification_*`), so `rangeldm_amd.evaluate inpainting | densification` scores them
-unchanged.  Densification (every 4th beam known) needs the pixel-space model: no latent pixel is fully known under that mask.
+unchanged.  Densification (every 4th beam known) by latent replacement needs the pixel-space model: no latent pixel is fully known
+under that mask.  `--decoder-guidance` densifies (or in-paints) with the LATENT model instead: DDIM with eta = 0 whose clean estimate
+is guided through the VAE decoder (rangeldm_amd.guidance), any pixel mask:
+
+    python -m rangeldm_amd.inference_conditional --guided --task densification --cfg RangeLDM --decoder-guidance \
+        --guidance-scale 1.0 --guidance-iters 1 --guidance-window 0 1
 """
 import argparse
 import glob
@@ -120,6 +125,17 @@ def main_guided(a):
     cfg = load_config(a.cfg)
     if cfg.get("cond_channels", 0):
         raise ValueError(f"--guided takes an unconditional config (RangeLDM, RangeDM); {a.cfg} is conditional")
+    guide_kw = {}
+    if a.decoder_guidance:
+        if cfg["vae"] is None:
+            raise ValueError(f"--decoder-guidance guides the latent model through its VAE decoder; {a.cfg} is pixel-space")
+        if (a.scheduler or "ddim") != "ddim":
+            raise NotImplementedError("--decoder-guidance runs DDIM (eta = 0)")
+        if a.jump_length != 1 or a.jump_n_sample != 1:
+            raise NotImplementedError("--decoder-guidance does not resample (--jump-length / --jump-n-sample)")
+        a.scheduler = "ddim"
+        guide_kw = dict(decoder_guidance=True, guidance_scale=a.guidance_scale, guidance_iters=a.guidance_iters,
+                        guidance_start=a.guidance_window[0], guidance_stop=a.guidance_window[1])
     if (a.scheduler or "ddpm") == "dpmsolver++":
         raise NotImplementedError("--guided runs DDPM or DDIM rows (DPM-Solver++ keeps an x0 history that a jump invalidates)")
     B = a.batch_size or cfg.get("batch", 16)
@@ -176,7 +192,7 @@ def main_guided(a):
         if a.device_rng:                                   # --seed and the global sample index (draw 0 of every call)
             generator, kw = DeviceGenerator(a.seed), dict(sample_offset=D.global_sample_indices(i, B, rank, world)[0])
         images = pipe(batch_size=B, generator=generator, num_inference_steps=steps, output_type="torch", known=jpg,
-                      known_mask=known_mask, jump_length=a.jump_length, jump_n_sample=a.jump_n_sample, **kw)
+                      known_mask=known_mask, jump_length=a.jump_length, jump_n_sample=a.jump_n_sample, **guide_kw, **kw)
         write(result_path, images.contiguous(), seed)
         if seed == 0:
             write(target_path, jpg, seed)
@@ -202,6 +218,12 @@ def main(argv=None):
     ap.add_argument("--jump-length", type=int, default=1, help="--guided: RePaint's jump length (rows re-noised per jump)")
     ap.add_argument("--jump-n-sample", type=int, default=1, help="--guided: RePaint's resampling count (1: no jumps)")
     ap.add_argument("--save-npy", action="store_true", help="--guided: also write the raw (2, W, H) fp32 range images")
+    ap.add_argument("--decoder-guidance", action="store_true",
+                    help="--guided with a latent config: guide DDIM's clean estimate through the VAE decoder (any mask; densification too)")
+    ap.add_argument("--guidance-scale", type=float, default=1.0, help="--decoder-guidance: step length along grad sqrt(L)")
+    ap.add_argument("--guidance-iters", type=int, default=1, help="--decoder-guidance: guidance iterations per sampling step")
+    ap.add_argument("--guidance-window", type=float, nargs=2, default=(0.0, 1.0), metavar=("A", "B"),
+                    help="--decoder-guidance: guide the steps i with A <= i / steps < B")
     add_sampling_args(ap)
     a = ap.parse_args(argv)
     if a.guided:

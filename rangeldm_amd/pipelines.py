@@ -425,15 +425,41 @@ class LDMPipelineRange(_PipelineBase):
         self.register_modules(vae=vae, unet=unet, scheduler=scheduler)
         self.pos_encoding = pos_encoding
 
+    def _decoder_guide(self, given):
+        """decoder_guidance=True: one guidance.DecoderGuide built from self.vae and kept until the VAE's weights are reloaded; a
+        DecoderGuide is used as it is, unless it no longer holds this VAE's decoder."""
+        from .guidance import DecoderGuide
+        if isinstance(given, DecoderGuide):
+            if given.stale(self.vae):
+                raise ValueError("decoder_guidance was built from another VAE, or the VAE's weights were reloaded since")
+            return given
+        if given is not True:
+            raise TypeError(f"decoder_guidance is a guidance.DecoderGuide or True, not {type(given).__name__}")
+        cached = getattr(self, "_guide", None)
+        if cached is None or cached.stale(self.vae):
+            self._guide = cached = DecoderGuide(self.vae)
+        return cached
+
     @torch.no_grad()
     def __call__(self, batch_size=1, generator=None, eta=0.0, num_inference_steps=50, output_type="torch",
                  return_dict=True, final_only=True, fused=True, latents=None, step_noise=None, known=None, known_mask=None,
-                 jump_length=1, jump_n_sample=1, known_noise=None, renoise_noise=None, sample_offset=0, **kwargs):
+                 jump_length=1, jump_n_sample=1, known_noise=None, renoise_noise=None, sample_offset=0, decoder_guidance=None,
+                 guidance_scale=1.0, guidance_iters=1, guidance_start=0.0, guidance_stop=1.0, **kwargs):
         """`known` (B, 2, W, H normalised range image) + `known_mask` (B, 1, W, H pixel mask; 1 / True = known): guided completion
         with these unconditional weights.  z0 = vae.encode(known).latent_dist.mode() * scaling_factor; a latent pixel counts as
         known only if its whole footprint is (latent_known_mask), so an azimuth-span mask works and a beam-subsampling mask raises.
         step_noise / known_noise / renoise_noise are then [rows, B, C, W / f, H / f] of schedulers.repaint_program's rows.
-        `return_latents=True` (guided only) returns (images, final latents, z0, latent mask)."""
+        `return_latents=True` (guided only) returns (images, final latents, z0, latent mask).
+        `decoder_guidance` (a guidance.DecoderGuide, or True to build and cache one from `self.vae`): `known` / `known_mask` take ANY
+        pixel mask -- every 4th beam densifies -- and no latent replacement runs; the known pixels guide each step's clean estimate
+        through the VAE decoder instead (guidance.py: DDIM with eta = 0, the eager loop; guidance_scale, guidance_iters per step,
+        inside the window [guidance_start, guidance_stop) of the schedule; guidance_scale = 0 gives the bits of the unguided
+        fused=False loop).  A scheduler other than DDIMSchedulerHIP, eta != 0, jump_length / jump_n_sample != 1 and final_only=False
+        are refused (NotImplementedError).  `return_latents=True` then returns (images, final latents, L (B,) float64 of the last
+        guided iteration); `latent_trace=` a list receives every step's latents."""
+        if decoder_guidance is not None and decoder_guidance is not False:
+            from .guidance import refuse_unsupported
+            refuse_unsupported(self.scheduler, eta, jump_length, jump_n_sample, final_only)
         cfg = self.unet.config
         shape = (batch_size, cfg.out_channels, *cfg.sample_size)
         dev_rng = isinstance(generator, DeviceGenerator)
@@ -450,6 +476,14 @@ class LDMPipelineRange(_PipelineBase):
         is_ddpm = isinstance(self.scheduler, DDPMSchedulerHIP)
         if dev_rng and is_ddim and eta != 0.0:
             raise NotImplementedError("DDIM with eta > 0 draws its variance noise from a torch generator")
+        if decoder_guidance is not None and decoder_guidance is not False:
+            from .guidance import decoder_guided_call
+            image, lat, last = decoder_guided_call(self, self._decoder_guide(decoder_guidance), latents.float(), num_inference_steps,
+                                                   known, known_mask, guidance_scale, guidance_iters, guidance_start, guidance_stop,
+                                                   trace=kwargs.get("latent_trace"))
+            if kwargs.get("return_latents", False):
+                return image, lat, last
+            return self._finish(image, output_type, return_dict)
         if known is not None:
             if known_mask is None:
                 raise ValueError("`known` needs `known_mask`")

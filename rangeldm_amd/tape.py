@@ -23,12 +23,13 @@ class FlatParameters:
     _state_name = "training state"                      # (what load_payload calls a file it refuses)
 
     def _init_parameters(self, shapes, names, state_dict, device, fused=None, no_dx=(), use_ema=False, deterministic=False,
-                         packed=None, tiled=True):
+                         packed=None, tiled=True, moments=True):
         """shapes: name -> shape; names: the order of the parameters inside the flat buffers; fused: plan_parameter_order's layer
         groups (consecutive parameters run as ONE layer); no_dx: weights whose layer never computes a data gradient (no transposed
         operand copy).  packed: the weights that get bf16 operand copies (None: every `*.weight` of two or more dimensions outside a
         fused group, and every fused group); tiled: the packer `repack()` uses when it is not told (True: the 64 x 64 tile
-        transpose)."""
+        transpose).  moments=False: no AdamW moments are allocated (an owner that never takes an optimizer step: guidance.DecoderGuide);
+        `_clip_adamw`, `state_payload` and `load_payload` are then not to be called."""
         _lib.require_gpu()
         self.device = torch.device(device)
         self.shapes, self.names, self.fused = shapes, list(names), fused if fused is not None else OrderedDict()
@@ -37,7 +38,8 @@ class FlatParameters:
         self.sizes = dict(zip(self.names, sizes))
         self.numel = int(sum(sizes))
         z = lambda: torch.zeros(self.numel, dtype=torch.float32, device=self.device)      # noqa: E731
-        self.params, self.grads, self.exp_avg, self.exp_avg_sq = z(), z(), z(), z()
+        self.params, self.grads = z(), z()
+        self.exp_avg, self.exp_avg_sq = (z(), z()) if moments else (None, None)
         self.ema = z() if use_ema else None
         host = np.empty(self.numel, np.float32)
         for n in self.names:
@@ -174,10 +176,10 @@ class FlatParameters:
 
 class TapeTrainer(FlatParameters):
     def _init_parameters(self, shapes, names, state_dict, device, fused=None, no_dx=(), use_ema=False, deterministic=False,
-                         arena_bytes=256 << 20):
+                         arena_bytes=256 << 20, moments=True):
         """FlatParameters' arguments (every weight packed, the tiled packer) and arena_bytes: the size of the zero arena."""
         super()._init_parameters(shapes, names, state_dict, device, fused=fused, no_dx=no_dx, use_ema=use_ema,
-                                 deterministic=deterministic)
+                                 deterministic=deterministic, moments=moments)
         self._tape, self._grad, self._keep = [], {}, []
         self._rows, self._row_parent = {}, {}
         self._arena = T.ZeroArena(self.device, arena_bytes)
@@ -187,6 +189,9 @@ class TapeTrainer(FlatParameters):
         self.wgrad_group = True
         self._wg_on, self._wg_keep = False, []
         self._cs = {}
+        # _params_on: False only inside _run_tape(params=False), the replay for the input gradient alone; _dy_shared: a conv's dy is
+        # (or, in that replay, counts as) an operand of a queued weight gradient, so a residual branch takes a buffer of its own
+        self._params_on, self._dy_shared, self._sink_buf = True, False, None
 
     # ---- tape -------------------------------------------------------------------------------------------------
     def _acc(self, t, g, owned):
@@ -253,19 +258,41 @@ class TapeTrainer(FlatParameters):
         T.set_zero_arena(self._arena)                   # split-K conv outputs of this step: pre-zeroed slices, one fill
         self._arena.begin()
 
-    def _run_tape(self, out, dpred):
-        """Replays the tape in reverse from d(loss) / d(out) = dpred; every gradient is final when it returns."""
+    def _sink(self, n):
+        """n floats nobody reads: where the input-gradient-only replay lets the GroupNorm backward put d gamma / d beta."""
+        if self._sink_buf is None or self._sink_buf.numel() < n:
+            self._sink_buf = torch.zeros(max(n, 4096), dtype=torch.float32, device=self.device)
+        return self._sink_buf[:n]
+
+    def _run_tape(self, out, dpred, params=True):
+        """Replays the tape in reverse from d(loss) / d(out) = dpred; every gradient is final when it returns.
+        params=False: the data gradients alone -- the same launches in the same order with the same operands as the default replay, so the
+        gradient that reaches the tape's input has the same bits; no weight-gradient / bias launch, nothing queued or pinned, no
+        weight-gradient group or deferred reduction opened, the flat gradient buffer untouched (the GroupNorm backward's d gamma /
+        d beta go to `_sink`), `_done` not called."""
         self._acc(out, dpred, False)
+        if not params:
+            self._params_on, self._dy_shared = False, bool(self.wgrad_group)
+            try:
+                for fn in reversed(self._tape):
+                    fn()
+            finally:
+                self._params_on, self._dy_shared = True, False
+            self._tape, self._grad, self._cs = [], {}, {}
+            T.set_zero_arena(None)
+            return
         # the reduction of a weight gradient's partial tiles rides on the layer's data-gradient launch
         T.defer_reduce(True)
-        self._wg_on = bool(self.wgrad_group)
+        self._wg_on = self._dy_shared = bool(self.wgrad_group)
         try:
             T.wgrad_group(self._wg_on)
             for fn in reversed(self._tape):
                 fn()
         except BaseException:
+            self._dy_shared = False
             self._end_queues(report=False)              # (the tape's error is the one to report)
             raise
+        self._dy_shared = False
         self._end_queues()
         self._tape, self._grad, self._cs = [], {}, {}
         T.set_zero_arena(None)
@@ -289,6 +316,8 @@ class TapeTrainer(FlatParameters):
             dy = self._pop(y)
             dy_owned = self._popped_owned
             drow = None
+            if rowadd is not None and not self._params_on:     # (drow is the weight-gradient launch's output)
+                raise NotImplementedError("the input-gradient-only replay does not carry a conv's row term (time embedding)")
             if rowadd is not None:
                 parent = self._row_parent.get(id(rowadd))
                 if parent is None:
@@ -298,16 +327,17 @@ class TapeTrainer(FlatParameters):
                     if id(rows) not in self._grad:       # zeroed once for all 22 slices (they accumulate into it)
                         self._grad[id(rows)] = (torch.zeros(rows.shape, dtype=torch.float32, device=rows.device), True)
                     drow = self._grad[id(rows)][0][:, off:off + rowadd.shape[1]]
-            T.wgrad_bias(dy, x, self.g[w], taps, stride, mode, rows=drow, total=self.g[name + ".bias"],
-                         rows_accumulate=rowadd is not None and self._row_parent.get(id(rowadd)) is not None, pad=pad)
-            self._pin(dy, x, drow)
-            self._done(*done)
+            if self._params_on:
+                T.wgrad_bias(dy, x, self.g[w], taps, stride, mode, rows=drow, total=self.g[name + ".bias"],
+                             rows_accumulate=rowadd is not None and self._row_parent.get(id(rowadd)) is not None, pad=pad)
+                self._pin(dy, x, drow)
+                self._done(*done)
             if rowadd is not None and self._row_parent.get(id(rowadd)) is None:
                 self._acc(rowadd, drow, True)
             if res is not None:
                 # (everything below that reads dy is enqueued before anyone adds to it -- unless the weight gradient above is
                 #  queued: then dy must stay as it is until the flush, and later gradients of `res` go to a buffer of their own)
-                self._acc(res, dy, dy_owned and not self._wg_on)
+                self._acc(res, dy, dy_owned and not self._dy_shared)
             if need_dx:
                 wt = self.wt[w]
                 Cin = x.shape[3]
@@ -331,9 +361,10 @@ class TapeTrainer(FlatParameters):
         def bwd():
             dy = self._pop(y)
             cur = self._slot(x)
-            dx = T.gn_backward(x, dy, stats, gamma, beta, cfg.norm_num_groups, silu, self.g[name + ".weight"], self.g[name + ".bias"],
-                               dx=cur, accumulate=cur is not None)
-            self._done(name + ".weight", name + ".bias")
+            dg, db = (self.g[name + ".weight"], self.g[name + ".bias"]) if self._params_on else self._sink(2 * gamma.numel()).chunk(2)
+            dx = T.gn_backward(x, dy, stats, gamma, beta, cfg.norm_num_groups, silu, dg, db, dx=cur, accumulate=cur is not None)
+            if self._params_on:
+                self._done(name + ".weight", name + ".bias")
             if cur is None:
                 self._acc(x, dx, True)
         self._tape.append(bwd)

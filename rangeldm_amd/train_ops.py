@@ -313,6 +313,48 @@ def gaussian_backward(moments_nhwc, noise_nchw, dz_nhwc, kw):
     return dm
 
 
+# ---- decoder-guided sampling (csrc/guide.hip; guidance.py holds the numpy statements) --------------------------------------------
+def guide_residual(xhat_nhwc, y_nchw, mask, channel_weights):
+    """-> (gx (B, W, H, C) = (2 wc[c]) (xhat - y) where mask > 0.5, +0 elsewhere; L (B,) float64 device = sum wc[c] (xhat - y)^2 over the
+    known pixels of each image, in one fixed order).  y (B, C, W, H), mask (B, 1, W, H) fp32, channel_weights device fp32 (C,)."""
+    B, W, H, Cc = xhat_nhwc.shape
+    if tuple(y_nchw.shape) != (B, Cc, W, H) or tuple(mask.shape) != (B, 1, W, H) or channel_weights.numel() != Cc:
+        raise ValueError(f"guide_residual: xhat {tuple(xhat_nhwc.shape)} (NHWC) needs y {(B, Cc, W, H)}, a mask {(B, 1, W, H)} and {Cc} "
+                         f"channel weights; got {tuple(y_nchw.shape)}, {tuple(mask.shape)}, {channel_weights.numel()}")
+    gx = torch.empty_like(xhat_nhwc)
+    L = torch.empty(B, dtype=torch.float64, device=xhat_nhwc.device)
+    _chk(_lib.lib().rldm_guide_residual(_p(xhat_nhwc), _p(y_nchw), _p(mask), _p(channel_weights), B, Cc, W, H, _p(gx), _p(L),
+                                        _s(xhat_nhwc)), "rldm_guide_residual")
+    return gx, L
+
+
+def guide_latent(z0_nchw, inv_sf):
+    """-> the decoder's input (B, W, H, C) = z0 (B, C, W, H) * inv_sf (inv_sf: a Python float that is an fp32 value)."""
+    B, Cc, W, H = z0_nchw.shape
+    zin = empty((B, W, H, Cc), z0_nchw)
+    _chk(_lib.lib().rldm_guide_latent(_p(z0_nchw), float(inv_sf), B, Cc, W, H, _p(zin), _s(z0_nchw)), "rldm_guide_latent")
+    return zin
+
+
+def guide_update(g_nhwc, L, scale, inv_sf, z0_nchw, delta_nchw):
+    """In place: u = rho_b (g * inv_sf), z0 -= u, delta += u with rho_b = fp32(scale / max(sqrt(L[b]), 1e-8)) read from the device's L
+    (L None: rho = 1)."""
+    B, W, H, Cc = g_nhwc.shape
+    if tuple(z0_nchw.shape) != (B, Cc, W, H) or tuple(delta_nchw.shape) != (B, Cc, W, H) or (L is not None and L.numel() != B):
+        raise ValueError(f"guide_update: g {tuple(g_nhwc.shape)} (NHWC) needs z0 and delta {(B, Cc, W, H)} and {B} sums")
+    _chk(_lib.lib().rldm_guide_update(_p(g_nhwc), _p(L), float(scale), float(inv_sf), B, Cc, W, H, _p(z0_nchw), _p(delta_nchw),
+                                      _s(g_nhwc)), "rldm_guide_update")
+
+
+def guide_correct(z_plain, delta, c):
+    """-> z_plain - c * delta (z_plain's own bits where the product is a zero); c: a Python float that is an fp32 value."""
+    if z_plain.shape != delta.shape:
+        raise ValueError(f"guide_correct: z_plain {tuple(z_plain.shape)} and delta {tuple(delta.shape)} differ")
+    out = torch.empty_like(z_plain)
+    _chk(_lib.lib().rldm_guide_correct(_p(z_plain), _p(delta), float(c), z_plain.numel(), _p(out), _s(z_plain)), "rldm_guide_correct")
+    return out
+
+
 def sqnorm(g):
     out = torch.empty((), dtype=torch.float64, device=g.device)
     _chk(_lib.lib().rldm_train_sqnorm(_p(g), g.numel(), _p(out), _s(g)), "rldm_train_sqnorm")
