@@ -390,6 +390,11 @@ def check(rc, what=""):
         raise RuntimeError(f"librangeldm_hip: {what} failed: {msg.decode() if msg else 'unknown error'}")
 
 
+def ptr(t):
+    """The device pointer of a tensor as the C ABI takes it; None stays None (a null argument)."""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
 def stream_ptr(device=None):
     import torch
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)

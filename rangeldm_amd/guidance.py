@@ -29,6 +29,7 @@ import torch
 
 from . import train_ops as T
 from .params import vae_param_shapes
+from .pipelines import _pos_channel
 from .vae_training import _VAETape, decoder_param_names
 
 
@@ -238,8 +239,7 @@ def decoder_guided_call(pipe, guide, latents, num_inference_steps, known, known_
         raise ValueError(f"known {tuple(y.shape)} is not the image of a latent {tuple(z.shape)}: expected {guide._latent_shape(z)}")
     inside = set(guided_steps(num_inference_steps, start, stop)) if int(iters) > 0 else set()
     if pipe.pos_encoding:
-        pos_encoding = torch.zeros([B, 1, z.shape[2], z.shape[3]], device=dev)
-        pos_encoding[:, :, 0, :] = 1
+        pos_encoding = _pos_channel(B, z.shape[2], z.shape[3], dev)
     last = None
     for i, t in enumerate(pipe.progress_bar(sch.timesteps)):
         model_input = sch.scale_model_input(z, t)
@@ -347,8 +347,7 @@ def decoder_guided_sample_host(unet, scheduler, state_dict, cfg, x_T, known, kno
     z = x_T.detach().to(dtype) * scheduler.init_noise_sigma
     y, m = known.detach().to(dtype), known_mask.detach().to(dtype)
     if pos_encoding:
-        pe = torch.zeros([z.shape[0], 1, z.shape[2], z.shape[3]], dtype=dtype)
-        pe[:, :, 0, :] = 1
+        pe = _pos_channel(z.shape[0], z.shape[2], z.shape[3], "cpu", dtype)
     last = None
     for i, t in enumerate(scheduler.timesteps):
         inp = scheduler.scale_model_input(z, t)

@@ -106,6 +106,41 @@ def add_sampling_args(ap):
                          "sample = the global image index, so any GPU count and batch size draws the same noise per image")
 
 
+def device_rng_kwargs(seed, iteration, batch_size, rank, world):
+    """--device-rng: the pipeline keywords of one call.  One draw per call, always draw 0 of a fresh generator: sample_offset, the
+    global index of the call's first sample, alone tells the samples apart."""
+    from .rng import DeviceGenerator
+    return dict(generator=DeviceGenerator(seed), sample_offset=D.global_sample_indices(iteration, batch_size, rank, world)[0])
+
+
+def build_models(cfg, weights, ema, seed):
+    """-> (unet, vae or None, scheduler config or None).  `weights`: the training run's output_dir (ldm/inference.py:46-52,84-127),
+    whose own configs then replace cfg["unet"] / cfg["vae"]; None: the deterministic synthetic state dicts of `seed`."""
+    from .params import unet_param_shapes, vae_param_shapes
+    from .synth import synth_state_dict
+    from .unet import UNet2DModelHIP
+    from .vae import AutoencoderKLHIP
+    latent = cfg["vae"] is not None
+    sched_cfg = vsd = None
+    if weights:
+        from .checkpoint import load_output_dir
+        ck = load_output_dir(weights, with_vae=latent, ema=ema)
+        cfg["unet"], usd, sched_cfg = ck["unet_config"], ck["unet"], ck["scheduler_config"]
+        if latent:
+            cfg["vae"], vsd = ck["vae_config"], ck["vae"]
+    else:
+        usd = synth_state_dict(unet_param_shapes(cfg["unet"]), seed=seed, prefix="")
+        if latent:
+            vsd = synth_state_dict(vae_param_shapes(cfg["vae"]), seed=seed, prefix="vae.")
+    unet = UNet2DModelHIP(cfg["unet"])
+    unet.load_state_dict(usd)
+    vae = None
+    if latent:
+        vae = AutoencoderKLHIP(cfg["vae"])
+        vae.load_state_dict(vsd)
+    return unet, vae, sched_cfg
+
+
 def device_step_noise(seed, global_indices, steps, lat_shape, device):
     """[steps][B, C, W, H] ancestral noise, drawn ON THE DEVICE from one generator per GLOBAL sample index (seed and index
     only: independent of rank, world size and batch composition).  The reference draws it from the unseeded global device RNG
@@ -162,6 +197,17 @@ def postprocess(to_range, image, max_depth=90.0):
     return kept.cpu().numpy(), counts.cpu().numpy(), bev_u8.cpu().numpy(), range_u8.cpu().numpy()
 
 
+def write_results(dirname, to_range, image, seed, max_depth, save_npy=False):
+    """The conditional drivers' files of one batch (ldm/inference_conditional.py:190-195): `<j>_seed_<seed>.bin` (the points closer
+    than max_depth) and `.png` (the BEV density); save_npy: `.npy`, the raw range image, as well."""
+    points, counts, bev_u8, _ = postprocess(to_range, image, max_depth=max_depth)
+    for j in range(image.shape[0]):
+        points[j, :counts[j]].tofile(os.path.join(dirname, f"{j}_seed_{seed}.bin"))
+        save_png(bev_u8[j], os.path.join(dirname, f"{j}_seed_{seed}.png"))
+        if save_npy:
+            np.save(os.path.join(dirname, f"{j}_seed_{seed}.npy"), image[j].float().cpu().numpy())
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="RangeLDM sampler on MI355X (ldm/inference.py counterpart)")
     ap.add_argument("--cfg", required=True)
@@ -175,13 +221,9 @@ def main(argv=None):
     add_sampling_args(ap)
     a = ap.parse_args(argv)
 
-    from .params import unet_param_shapes, vae_param_shapes
     from .pipelines import DDIMPipelineRange, DDPMPipelineRange, LDMPipelineRange
-    from .rng import DeviceGenerator
     from .schedulers import DDIMSchedulerHIP, DDPMSchedulerHIP
-    from .synth import latent_noise, synth_state_dict
-    from .unet import UNet2DModelHIP
-    from .vae import AutoencoderKLHIP
+    from .synth import latent_noise
 
     cfg = load_config(a.cfg)
     B = a.batch_size or cfg.get("batch", 16)
@@ -192,23 +234,8 @@ def main(argv=None):
     out_dir = a.out or os.path.join("outputs", os.path.splitext(os.path.basename(a.cfg))[0], "generated")
     os.makedirs(out_dir, exist_ok=True)
 
-    sched_cfg = None
-    if a.weights:
-        # ldm/inference.py:46-52,84-127: configs and weights come from the training run's output_dir
-        from .checkpoint import load_output_dir
-        ck = load_output_dir(a.weights, with_vae=cfg["vae"] is not None, ema=a.ema)
-        cfg["unet"], usd, sched_cfg = ck["unet_config"], ck["unet"], ck["scheduler_config"]
-        if cfg["vae"] is not None:
-            cfg["vae"], vsd = ck["vae_config"], ck["vae"]
-    else:
-        usd = synth_state_dict(unet_param_shapes(cfg["unet"]), seed=a.seed, prefix="")
-        if cfg["vae"] is not None:
-            vsd = synth_state_dict(vae_param_shapes(cfg["vae"]), seed=a.seed, prefix="vae.")
-    unet = UNet2DModelHIP(cfg["unet"])
-    unet.load_state_dict(usd)
-    if cfg["vae"] is not None:
-        vae = AutoencoderKLHIP(cfg["vae"])
-        vae.load_state_dict(vsd)
+    unet, vae, sched_cfg = build_models(cfg, a.weights, a.ema, a.seed)
+    if vae is not None:
         # ldm/inference.py:131-136: the LDM branch keeps the DDPM scheduler (strided ancestral sampling)
         pipe = LDMPipelineRange(vae=vae, unet=unet, scheduler=make_scheduler(a.scheduler or "ddpm", sched_cfg),
                                 pos_encoding=cfg["pos_encoding"])
@@ -233,8 +260,7 @@ def main(argv=None):
         # x_T AND the ancestral step noise are functions of the GLOBAL image index: any GPU count produces the same images
         idx = D.global_sample_indices(i, B, rank, world)
         if a.device_rng:
-            # one draw per call, always draw 0: the global index alone tells the samples apart
-            kw = dict(generator=DeviceGenerator(a.seed), sample_offset=idx[0])
+            kw = device_rng_kwargs(a.seed, i, B, rank, world)
         else:
             kw = dict(latents=torch.from_numpy(np.stack([latent_noise(a.seed, j, lat_shape) for j in idx])).to(dev))
             if ddpm:

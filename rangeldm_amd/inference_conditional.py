@@ -39,7 +39,8 @@ import torch
 from . import distributed as D
 from .conditional import downsample_range_image, inpainting_inputs, sparse_input_image
 from .config import PRESETS, UNetConfig, VAEConfig
-from .inference import add_sampling_args, make_scheduler, postprocess, save_png, sensor_for, vae_config_for
+from .inference import (add_sampling_args, build_models, device_rng_kwargs, make_scheduler, sensor_for, vae_config_for,
+                        write_results)
 
 
 def load_conditional_config(cfg):
@@ -114,13 +115,8 @@ def guided_known_mask(jpg, task, fraction=0.0625, rate=4):
 def main_guided(a):
     """--guided: LDMPipelineRange / DDIMPipelineRange with `known` / `known_mask` on an unconditional config."""
     from .inference import load_config
-    from .params import unet_param_shapes, vae_param_shapes
     from .pipelines import DDIMPipelineRange, LDMPipelineRange
-    from .rng import DeviceGenerator
     from .schedulers import DDIMSchedulerHIP
-    from .synth import synth_state_dict
-    from .unet import UNet2DModelHIP
-    from .vae import AutoencoderKLHIP
 
     cfg = load_config(a.cfg)
     if cfg.get("cond_channels", 0):
@@ -148,23 +144,8 @@ def main_guided(a):
     result_path, target_path, input_path = (os.path.join(out, f"{stem}_{k}") for k in ("result", "target", "input"))
     for d in (result_path, target_path, input_path):
         os.makedirs(d, exist_ok=True)
-    sched_cfg = None
-    latent = cfg["vae"] is not None
-    if a.weights:
-        from .checkpoint import load_output_dir
-        ck = load_output_dir(a.weights, with_vae=latent, ema=a.ema)
-        cfg["unet"], usd, sched_cfg = ck["unet_config"], ck["unet"], ck["scheduler_config"]
-        if latent:
-            cfg["vae"], vsd = ck["vae_config"], ck["vae"]
-    else:
-        usd = synth_state_dict(unet_param_shapes(cfg["unet"]), seed=a.seed, prefix="")
-        if latent:
-            vsd = synth_state_dict(vae_param_shapes(cfg["vae"]), seed=a.seed, prefix="vae.")
-    unet = UNet2DModelHIP(cfg["unet"])
-    unet.load_state_dict(usd)
-    if latent:
-        vae = AutoencoderKLHIP(cfg["vae"])
-        vae.load_state_dict(vsd)
+    unet, vae, sched_cfg = build_models(cfg, a.weights, a.ema, a.seed)
+    if vae is not None:
         pipe = LDMPipelineRange(vae=vae, unet=unet, scheduler=make_scheduler(a.scheduler or "ddpm", sched_cfg),
                                 pos_encoding=cfg["pos_encoding"])
         f = cfg["vae"].downscale
@@ -177,26 +158,16 @@ def main_guided(a):
     to_range = sensor_for(jpg.shape[3])
     lim = 90.0 if jpg.shape[3] == 32 else 70.0
 
-    def write(dirname, image, seed):
-        points, counts, bev_u8, _ = postprocess(to_range, image, max_depth=lim)
-        for j in range(image.shape[0]):
-            points[j, :counts[j]].tofile(os.path.join(dirname, f"{j}_seed_{seed}.bin"))
-            save_png(bev_u8[j], os.path.join(dirname, f"{j}_seed_{seed}.png"))
-            if a.save_npy:
-                np.save(os.path.join(dirname, f"{j}_seed_{seed}.npy"), image[j].float().cpu().numpy())
-
     n_iter = a.samples // B // world + 1
     for i in range(n_iter):
         seed = rank + world * i
-        generator, kw = torch.Generator().manual_seed(seed), {}
-        if a.device_rng:                                   # --seed and the global sample index (draw 0 of every call)
-            generator, kw = DeviceGenerator(a.seed), dict(sample_offset=D.global_sample_indices(i, B, rank, world)[0])
-        images = pipe(batch_size=B, generator=generator, num_inference_steps=steps, output_type="torch", known=jpg,
+        kw = device_rng_kwargs(a.seed, i, B, rank, world) if a.device_rng else dict(generator=torch.Generator().manual_seed(seed))
+        images = pipe(batch_size=B, num_inference_steps=steps, output_type="torch", known=jpg,
                       known_mask=known_mask, jump_length=a.jump_length, jump_n_sample=a.jump_n_sample, **guide_kw, **kw)
-        write(result_path, images.contiguous(), seed)
+        write_results(result_path, to_range, images.contiguous(), seed, lim, a.save_npy)
         if seed == 0:
-            write(target_path, jpg, seed)
-            write(input_path, shown.contiguous(), seed)
+            write_results(target_path, to_range, jpg, seed, lim, a.save_npy)
+            write_results(input_path, to_range, shown.contiguous(), seed, lim, a.save_npy)
     D.barrier()
     if rank == 0:
         print(f"wrote {n_iter * B} guided {stem} results to {result_path}")
@@ -230,12 +201,7 @@ def main(argv=None):
         return main_guided(a)
 
     from .encoders import SparseRangeImageEncoder2
-    from .params import unet_param_shapes, vae_param_shapes
     from .pipelines import LDMUpscalePipelineRange
-    from .rng import DeviceGenerator
-    from .synth import synth_state_dict
-    from .unet import UNet2DModelHIP
-    from .vae import AutoencoderKLHIP
 
     cfg = load_conditional_config(a.cfg)
     B = a.batch_size or cfg["batch"]
@@ -250,18 +216,7 @@ def main(argv=None):
     for d in (result_path, target_path, input_path):
         os.makedirs(d, exist_ok=True)
 
-    sched_cfg = None
-    if a.weights:
-        from .checkpoint import load_output_dir
-        ck = load_output_dir(a.weights, with_vae=True, ema=a.ema)
-        cfg["unet"], usd, sched_cfg, cfg["vae"], vsd = ck["unet_config"], ck["unet"], ck["scheduler_config"], ck["vae_config"], ck["vae"]
-    else:
-        usd = synth_state_dict(unet_param_shapes(cfg["unet"]), seed=a.seed, prefix="")
-        vsd = synth_state_dict(vae_param_shapes(cfg["vae"]), seed=a.seed, prefix="vae.")
-    unet = UNet2DModelHIP(cfg["unet"])
-    unet.load_state_dict(usd)
-    vae = AutoencoderKLHIP(cfg["vae"])
-    vae.load_state_dict(vsd)
+    unet, vae, sched_cfg = build_models(cfg, a.weights, a.ema, a.seed)
     # ldm/inference_conditional.py:121-134: DDPM scheduler (strided ancestral sampling), SparseRangeImageEncoder2 for up-sampling
     pipe = LDMUpscalePipelineRange(unet=unet, scheduler=make_scheduler(a.scheduler or "ddpm", sched_cfg), vae=vae)
     condition_encoder = SparseRangeImageEncoder2() if cfg["task"] == "upsample" else None
@@ -277,28 +232,21 @@ def main(argv=None):
     to_range = sensor_for(jpg.shape[3])
     lim = cfg["range_limit"]
 
-    def write(dirname, image, seed):
-        points, counts, bev_u8, _ = postprocess(to_range, image, max_depth=lim)
-        for j in range(image.shape[0]):
-            points[j, :counts[j]].tofile(os.path.join(dirname, f"{j}_seed_{seed}.bin"))     # ldm/inference_conditional.py:190-193
-            save_png(bev_u8[j], os.path.join(dirname, f"{j}_seed_{seed}.png"))              # :194-195
-
     n_iter = a.samples // B // world + 1                   # ldm/inference_conditional.py:158
     for i in range(n_iter):
         seed = rank + world * i
-        generator, kw = torch.Generator().manual_seed(seed), {}    # :159 (a CPU generator: x_T is drawn on the host, as there)
-        if a.device_rng:                                   # --seed and the global sample index (the draws of one call start at 0)
-            generator, kw = DeviceGenerator(a.seed), dict(sample_offset=D.global_sample_indices(i, B, rank, world)[0])
+        # :159 (a CPU generator: x_T is drawn on the host, as there)
+        kw = device_rng_kwargs(a.seed, i, B, rank, world) if a.device_rng else dict(generator=torch.Generator().manual_seed(seed))
         images = pipe(image=batch["down"] if cfg["task"] == "upsample" else batch["masked_image"],
                       mask=None if cfg["task"] == "upsample" else batch["inpainting_mask"],
-                      condition_encoder=condition_encoder, generator=generator, batch_size=B,
+                      condition_encoder=condition_encoder, batch_size=B,
                       num_inference_steps=steps, output_type="torch", **kw)
-        write(result_path, images, seed)
+        write_results(result_path, to_range, images, seed, lim)
         if seed == 0:                                      # :196-210
-            write(target_path, jpg, seed)
+            write_results(target_path, to_range, jpg, seed, lim)
             shown = (sparse_input_image(jpg, batch["down"], cfg["rate"]) if cfg["task"] == "upsample"
                      else batch["masked_image"])
-            write(input_path, shown.contiguous(), seed)
+            write_results(input_path, to_range, shown.contiguous(), seed, lim)
     D.barrier()
     if rank == 0:
         print(f"wrote {n_iter * B} {stem} results to {result_path}")

@@ -22,7 +22,7 @@ import torch
 from . import _lib
 from .rng import DeviceGenerator, randn, randn_rows
 from .schedulers import (DDIMSchedulerHIP, DDPMSchedulerHIP, DPMSolverMultistepSchedulerHIP, guided_step, randn_tensor,
-                         repaint_program)
+                         repaint_program, sampler_mode)
 
 
 class ImagePipelineOutput:
@@ -30,13 +30,89 @@ class ImagePipelineOutput:
         self.images = images
 
 
-def _sampler_mode(scheduler):
-    """rldm_sampler_config::mode of a scheduler: DDIM, DPM-Solver++, else the (strided ancestral) DDPM step."""
-    if isinstance(scheduler, DDIMSchedulerHIP):
-        return _lib.RLDM_SAMPLER_DDIM
-    if isinstance(scheduler, DPMSolverMultistepSchedulerHIP):
-        return _lib.RLDM_SAMPLER_DPMSOLVER
-    return _lib.RLDM_SAMPLER_DDPM
+def _pos_channel(B, W, H, device, dtype=torch.float32):
+    """The position channel (B, 1, W, H) concatenated to the UNet's input: 1 on the first row, 0 elsewhere (ldm/pipelines.py:229-231)."""
+    pos_encoding = torch.zeros([B, 1, W, H], device=device, dtype=dtype)
+    pos_encoding[:, :, 0, :] = 1
+    return pos_encoding
+
+
+class _CallNoise:
+    """The noise of ONE pipeline call, made from (generator, sample_offset, device) at the top of the call; the only code that knows
+    which kind of generator it holds.
+
+    None / a torch generator / a list of them: x_T is one randn_tensor, the [rows, ...] tensor of a purpose one randn_tensor per row
+    that needs one, in row order (a guided call: step, known, re-noise), and an eager loop lets the scheduler draw.
+    A rng.DeviceGenerator: the call consumes ONE draw d here; x_T is (d, purpose 0, row 0), row r of purpose P is (d, P, r), sample b of
+    the call is sample_offset + b -- the same values whether a tensor is built (randn_rows), an eager loop asks row by row, or the
+    captured loop draws them itself (`in_graph`).  A tensor the caller gives always wins, purpose by purpose."""
+
+    def __init__(self, generator, sample_offset, device):
+        self.generator, self.sample_offset, self.device = generator, sample_offset, device
+        self._counter = isinstance(generator, DeviceGenerator)
+        self.draw = generator.next_draw() if self._counter else None
+
+    @staticmethod
+    def own_draw(shape, generator, sample_offset, device):
+        """Noise that gets a whole draw of a DeviceGenerator to itself, consumed now (the in-painting posterior, before the sampler's
+        draw); None for a torch generator, which its consumer draws from in its own turn."""
+        return randn(shape, generator, sample_offset, device) if isinstance(generator, DeviceGenerator) else None
+
+    @property
+    def torch_generator(self):
+        """What a scheduler or latent_dist.sample may draw from by itself: the torch generator(s), None for a DeviceGenerator."""
+        return None if self._counter else self.generator
+
+    def refuse_variance_noise(self, eta):
+        if self._counter and eta != 0.0:
+            raise NotImplementedError("DDIM with eta > 0 draws its variance noise from a torch generator")
+
+    def x_T(self, shape, given, on_host):
+        """`given`, else the call's x_T.  A torch draw is made on the CPU when `on_host` (the latent pipelines, as ldm/pipelines.py:329-333)
+        and on the device otherwise (the pixel pipelines, which also check the shape of a given one)."""
+        if given is not None:
+            if not on_host and tuple(given.shape) != tuple(shape):
+                raise ValueError(f"latents shape {tuple(given.shape)} != {shape}")
+            return given
+        if self._counter:
+            return randn(shape, self.generator.at(self.draw), self.sample_offset, self.device)
+        if on_host:
+            return randn_tensor(shape, generator=self.generator)
+        return randn_tensor(shape, generator=self.generator, device=self.device, dtype=torch.float32)
+
+    def rows(self, purpose, need, shape, given=None, name=None, always=False):
+        """The [len(need), *shape] fp32 device tensor of `purpose`: `given` (with `name`: shape-checked), else drawn for the rows r with
+        need[r] -- a torch generator leaves the others 0.  None when no row needs one, a zero tensor with `always`."""
+        n = len(need)
+        if given is not None:
+            if name is not None and tuple(given.shape) != (n, *shape):
+                raise ValueError(f"{name} shape {tuple(given.shape)} != {(n, *shape)} (one slice per row of the program)")
+            return given.to(self.device, torch.float32).contiguous()
+        if not any(need):
+            return torch.zeros((n, *shape), device=self.device, dtype=torch.float32) if always else None
+        if self._counter:
+            return randn_rows(n, shape, self.generator, self.draw, purpose, self.sample_offset, self.device)
+        zs = torch.zeros((n, *shape), device=self.device, dtype=torch.float32)
+        for r in np.nonzero(need)[0]:
+            zs[r] = randn_tensor(shape, generator=self.generator, device=self.device, dtype=torch.float32)
+        return zs
+
+    def row(self, purpose, r, shape, given=None):
+        """Row r of `purpose` for an eager loop: given[r], else the DeviceGenerator's row; None = let the scheduler draw."""
+        if given is not None:
+            return given[r]
+        if self._counter:
+            return randn(shape, self.generator.at(self.draw, purpose, r), self.sample_offset, self.device)
+        return None
+
+    def in_graph(self, fused, *given):
+        """May the captured loop draw the rows itself?  A DeviceGenerator, the fused route, and none of the purposes it needs given;
+        `seed_draw_offset` is then what the entry point takes in place of the tensors."""
+        return self._counter and fused and all(g is None for g in given)
+
+    @property
+    def seed_draw_offset(self):
+        return (self.generator.seed, self.draw, self.sample_offset)
 
 
 def latent_known_mask(known_mask, downscale):
@@ -97,46 +173,35 @@ class _FusedSampler:
         self._cache[key] = (h, unet, vae)
         return h
 
-    def run(self, h, x_T, step_noise, cond, out, latents_out=None, check=True):
-        """One rldm_sample call.  `check` (default): wait for it and raise RuntimeError if the self-check of its persistent
-        launches tripped -- the reference's contract is a correct tensor or an exception (ldm/pipelines.py:218-222,463-464);
-        the failed call's outputs are NaN-marked on the device either way, and the sampler has then already rebuilt itself as
-        one launch per layer, so calling again works.  check=False keeps the call asynchronous (throughput loops that ask
-        `status(h)` themselves before they use the images)."""
-        def p(t):
-            return C.c_void_p(t.data_ptr()) if t is not None else None
-        _lib.check(_lib.lib().rldm_sample(h, p(x_T), p(step_noise), p(cond), p(out), p(latents_out),
-                                          _lib.stream_ptr(x_T.device)), "rldm_sample")
+    def _call(self, entry, h, x_T, args, out, latents_out, check):
+        """The one call into the library, `entry`(h, x_T, *args, out, latents_out, stream): every tensor (or None) goes as its pointer,
+        every other argument as an int, on the current stream of the tensors' device.
+        `check` (default): wait for it and raise RuntimeError if the self-check of its persistent launches tripped -- the reference's
+        contract is a correct tensor or an exception (ldm/pipelines.py:218-222,463-464); the failed call's outputs are NaN-marked on the
+        device either way, and the sampler has then already rebuilt itself as one launch per layer, so calling again works.
+        check=False keeps the call asynchronous (throughput loops that ask `status(h)` themselves before they use the images)."""
+        args = (x_T, *args, out, latents_out)
+        dev = next(a.device for a in args if torch.is_tensor(a))
+        _lib.check(getattr(_lib.lib(), entry)(h, *(_lib.ptr(a) if a is None or torch.is_tensor(a) else int(a) for a in args),
+                                              _lib.stream_ptr(dev)), entry)
         if check:
             self.status(h)
+
+    def run(self, h, x_T, step_noise, cond, out, latents_out=None, check=True):
+        """One rldm_sample call; `check` as in _call."""
+        self._call("rldm_sample", h, x_T, (step_noise, cond), out, latents_out, check)
 
     def run_guided(self, h, x_T, step_noise, known, mask, known_noise, renoise_noise, out, latents_out=None, check=True):
-        """One rldm_sample_guided call on a sampler made with `program`; `check` as in run."""
-        def p(t):
-            return C.c_void_p(t.data_ptr()) if t is not None else None
-        _lib.check(_lib.lib().rldm_sample_guided(h, p(x_T), p(step_noise), p(known), p(mask), p(known_noise), p(renoise_noise), p(out),
-                                                 p(latents_out), _lib.stream_ptr(x_T.device)), "rldm_sample_guided")
-        if check:
-            self.status(h)
+        """One rldm_sample_guided call on a sampler made with `program`."""
+        self._call("rldm_sample_guided", h, x_T, (step_noise, known, mask, known_noise, renoise_noise), out, latents_out, check)
 
     def run_rng(self, h, x_T, seed, draw, sample_offset, cond, out, latents_out=None, check=True):
-        """One rldm_sample_rng call: (seed, draw, sample_offset) in place of step_noise; x_T None = drawn (purpose 0); `check` as in run."""
-        def p(t):
-            return C.c_void_p(t.data_ptr()) if t is not None else None
-        dev = next(t for t in (x_T, out, latents_out) if t is not None).device
-        _lib.check(_lib.lib().rldm_sample_rng(h, p(x_T), int(seed), int(draw), int(sample_offset), p(cond), p(out), p(latents_out),
-                                              _lib.stream_ptr(dev)), "rldm_sample_rng")
-        if check:
-            self.status(h)
+        """One rldm_sample_rng call: (seed, draw, sample_offset) in place of step_noise; x_T None = drawn (purpose 0)."""
+        self._call("rldm_sample_rng", h, x_T, (seed, draw, sample_offset, cond), out, latents_out, check)
 
     def run_guided_rng(self, h, x_T, seed, draw, sample_offset, known, mask, out, latents_out=None, check=True):
-        """One rldm_sample_guided_rng call on a sampler made with `program`; `check` as in run."""
-        def p(t):
-            return C.c_void_p(t.data_ptr()) if t is not None else None
-        _lib.check(_lib.lib().rldm_sample_guided_rng(h, p(x_T), int(seed), int(draw), int(sample_offset), p(known), p(mask), p(out),
-                                                     p(latents_out), _lib.stream_ptr(known.device)), "rldm_sample_guided_rng")
-        if check:
-            self.status(h)
+        """One rldm_sample_guided_rng call on a sampler made with `program`."""
+        self._call("rldm_sample_guided_rng", h, x_T, (seed, draw, sample_offset, known, mask), out, latents_out, check)
 
     def captures(self, h):
         """rldm_debug_sampler_captures: step graphs this sampler has captured so far."""
@@ -215,70 +280,93 @@ class _PipelineBase:
         return ImagePipelineOutput(images=image)
 
     def _draw_step_noise(self, n_steps, timesteps, shape, generator, device):
-        """One randn per step with t > 0, in loop order.  The reference's latent pipelines call `scheduler.step` without a
-        generator (ldm/pipelines.py:362,502), i.e. they draw from the unseeded global RNG of the device; here the caller's
-        `generator` seeds the step noise as well (after x_T, in loop order), so a seeded call is reproducible.  With
-        generator=None the global device RNG is used, as in the reference."""
-        zs = torch.zeros((n_steps, *shape), device=device, dtype=torch.float32)
-        for i, t in enumerate(timesteps):
-            if int(t) > 0:
-                zs[i] = randn_tensor(shape, generator=generator, device=device, dtype=torch.float32)
-        return zs
+        """The [n_steps, *shape] step noise `generator` gives: one randn per step with t > 0, in loop order."""
+        return _CallNoise(generator, 0, device).rows(1, [int(t) > 0 for t in timesteps], shape, always=True)
 
+    def _sample_fused(self, shape, x_T, noise, step_noise, steps, check, vae=None, cond=None, pos_encoding=False):
+        """The fused unguided route of all four pipelines: x_T (None: the captured loop draws it) -> the decoded images with a VAE, the
+        final sample without.  An ancestral (DDPM) sampler takes its step noise from the captured loop itself when `noise` allows, else
+        as a [steps, *shape] tensor: `step_noise`, or one draw per step with t > 0 in loop order.  The reference's latent pipelines call
+        `scheduler.step` without a generator (ldm/pipelines.py:362,502), i.e. they draw from the unseeded global RNG of the device;
+        here the caller's generator seeds the step noise as well (after x_T), so a seeded call is reproducible."""
+        sch = self.scheduler
+        mode = sampler_mode(sch)
+        ancestral = mode == _lib.RLDM_SAMPLER_DDPM
+        in_graph = ancestral and noise.in_graph(True, step_noise)
+        zs = None
+        if ancestral and not in_graph:
+            zs = noise.rows(1, [int(t) > 0 for t in sch.timesteps], shape, step_noise, always=True)
+        h = self._fused.get(self.unet, vae, sch, shape[0], steps, mode, pos_encoding, 0 if cond is None else cond.shape[1])
+        out_shape = shape
+        if vae is not None:
+            f = vae._cfg.downscale
+            out_shape = (shape[0], vae._cfg.out_channels, shape[2] * f, shape[3] * f)
+        out = torch.empty(out_shape, device=self.device, dtype=torch.float32)
+        x_T = None if x_T is None else x_T.float().contiguous()
+        cond = None if cond is None else cond.float().contiguous()
+        if in_graph:
+            self._fused.run_rng(h, x_T, *noise.seed_draw_offset, cond, out, check=check)
+        else:
+            self._fused.run(h, x_T, zs, cond, out, check=check)
+        return out
 
-    def _guided_latents(self, vae, x_T, z0, mask, num_inference_steps, jump_length, jump_n_sample, generator, step_noise, known_noise,
-                        renoise_noise, fused, check, out=None, draw=None, sample_offset=0):
+    def _latent_loop(self, latents, extra, noise, step_noise, eta, images=None):
+        """The eager loop of the latent pipelines (ldm/pipelines.py:340-383, 487-519): scale, concatenate the `extra` input channels (None:
+        none), UNet, scheduler step -- an ancestral one with `noise`'s row -- and the final decode, which is returned.  `images`: a
+        list that receives the decode of every step's input latents (final_only=False)."""
+        sch, sf = self.scheduler, self.vae.config.scaling_factor
+        shape = tuple(latents.shape)
+        extra_kwargs = {"eta": eta} if "eta" in set(inspect.signature(sch.step).parameters.keys()) else {}
+        ancestral = isinstance(sch, DDPMSchedulerHIP)
+        for i, t in enumerate(self.progress_bar(sch.timesteps)):
+            if images is not None:
+                images.append(self.vae.decode(latents / sf).sample)
+            latent_model_input = sch.scale_model_input(latents, t)
+            if extra is not None:
+                latent_model_input = torch.cat([latent_model_input, extra], dim=1)
+            noise_prediction = self.unet(latent_model_input, t).sample
+            kw = dict(extra_kwargs)
+            z = noise.row(1, i, shape, step_noise) if ancestral else None
+            if z is not None:
+                kw["noise"] = z
+            latents = sch.step(noise_prediction, t, latents, **kw).prev_sample
+        return self.vae.decode(latents / sf).sample
+
+    def _guided_latents(self, vae, x_T, z0, mask, num_inference_steps, jump_length, jump_n_sample, noise, step_noise, known_noise,
+                        renoise_noise, fused, check, out=None):
         """The guided loop (schedulers.repaint_program) on the unconditional UNet: x_T, z0 (B, C, W, H) and mask (B, 1, W, H) at the
         UNet's sample resolution -> the final sample; with `out` (and a VAE, fused) the decoded images are written as well.
-        Noise not injected is drawn from `generator` in this order: the step noise (one draw per row with sigma != 0), the
-        known-region noise (rows with kb != 0), the re-noise (rows that jump).  A DeviceGenerator (`draw`: the call's draw) addresses
-        row r of each purpose instead; with nothing injected the fused loop draws the rows itself."""
+        Noise not injected comes from `noise` (_CallNoise) in this order: the step noise (rows with sigma != 0), the known-region noise
+        (rows with kb != 0), the re-noise (rows that jump); tensors are built only for purposes some row needs, and with nothing
+        injected the fused loop may draw the rows itself."""
         dev = self.device
         sch = self.scheduler
         ts, table = repaint_program(sch, num_inference_steps, jump_length, jump_n_sample)
         rows, shape = len(ts), tuple(x_T.shape)
-        mode = _sampler_mode(sch)
-        dev_rng = isinstance(generator, DeviceGenerator)
-        in_graph = dev_rng and fused and step_noise is None and known_noise is None and renoise_noise is None
-
-        def per_row(given, col, name):
-            need = table[:, col] != 0.0 if col != 7 else (table[:, 7] != 1.0) | (table[:, 8] != 0.0)
-            if given is not None:
-                if tuple(given.shape) != (rows, *shape):
-                    raise ValueError(f"{name} shape {tuple(given.shape)} != {(rows, *shape)} (one slice per row of the program)")
-                return given.to(dev, torch.float32).contiguous()
-            if not need.any() or in_graph:
-                return None
-            if dev_rng:
-                return randn_rows(rows, shape, generator, draw, {4: 1, 6: 2, 7: 3}[col], sample_offset, dev)
-            zs = torch.zeros((rows, *shape), device=dev, dtype=torch.float32)
-            for i in np.nonzero(need)[0]:
-                zs[i] = randn_tensor(shape, generator=generator, device=dev, dtype=torch.float32)
-            return zs
-        zs = per_row(step_noise, 4, "step_noise")
-        nk = per_row(known_noise, 6, "known_noise")
-        nr = per_row(renoise_noise, 7, "renoise_noise")
+        mode = sampler_mode(sch)
+        in_graph = noise.in_graph(fused, step_noise, known_noise, renoise_noise)
+        zs = nk = nr = None
+        if not in_graph:
+            # (a one-row DDPM program: sigma == 0, the fused sampler still asks for the tensor)
+            zs = noise.rows(1, table[:, 4] != 0.0, shape, step_noise, "step_noise", always=fused and mode == _lib.RLDM_SAMPLER_DDPM)
+            nk = noise.rows(2, table[:, 6] != 0.0, shape, known_noise, "known_noise")
+            nr = noise.rows(3, (table[:, 7] != 1.0) | (table[:, 8] != 0.0), shape, renoise_noise, "renoise_noise")
         x = x_T.to(dev, torch.float32).contiguous()
         z0 = z0.to(dev, torch.float32).contiguous()
         mask = mask.to(dev, torch.float32).expand(shape[0], 1, *shape[2:]).contiguous()
         if z0.shape != x.shape:
             raise ValueError(f"known sample {tuple(z0.shape)} != sample shape {shape}")
-        if in_graph:
-            h = self._fused.get(self.unet, vae, sch, shape[0], rows, mode, self.pos_encoding, 0, program=(ts, table))
-            lat = torch.empty_like(x)
-            self._fused.run_guided_rng(h, x, generator.seed, draw, sample_offset, z0, mask, out if vae is not None else None,
-                                       latents_out=lat, check=check)
-            return lat
         if fused:
-            if zs is None and mode == _lib.RLDM_SAMPLER_DDPM:      # (a one-row program: sigma == 0, the tensor is still asked for)
-                zs = torch.zeros((rows, *shape), device=dev, dtype=torch.float32)
             h = self._fused.get(self.unet, vae, sch, shape[0], rows, mode, self.pos_encoding, 0, program=(ts, table))
             lat = torch.empty_like(x)
-            self._fused.run_guided(h, x, zs, z0, mask, nk, nr, out if vae is not None else None, latents_out=lat, check=check)
+            image = out if vae is not None else None
+            if in_graph:
+                self._fused.run_guided_rng(h, x, *noise.seed_draw_offset, z0, mask, image, latents_out=lat, check=check)
+            else:
+                self._fused.run_guided(h, x, zs, z0, mask, nk, nr, image, latents_out=lat, check=check)
             return lat
         if self.pos_encoding:
-            pos_encoding = torch.zeros([shape[0], 1, shape[2], shape[3]], device=dev)
-            pos_encoding[:, :, 0, :] = 1
+            pos_encoding = _pos_channel(shape[0], shape[2], shape[3], dev)
         for i, t in enumerate(self.progress_bar(ts)):
             model_input = torch.cat([x, pos_encoding], dim=1) if self.pos_encoding else x
             model_output = self.unet(model_input, t).sample
@@ -302,47 +390,21 @@ class DDPMPipelineRange(_PipelineBase):
         cfg = self.unet.config
         ss = cfg.sample_size if not isinstance(cfg.sample_size, int) else (cfg.sample_size, cfg.sample_size)
         shape = (batch_size, cfg.in_channels, *ss)
-        dev_rng = isinstance(generator, DeviceGenerator)
-        draw = generator.next_draw() if dev_rng else None
-        # the captured loop draws x_T (when it is not given) and every row of step noise by itself
-        in_graph = fused and dev_rng and step_noise is None and isinstance(self.scheduler, DDPMSchedulerHIP)
-        if latents is not None:
-            if tuple(latents.shape) != shape:
-                raise ValueError(f"latents shape {tuple(latents.shape)} != {shape}")
-            image = latents.to(device=self.device, dtype=torch.float32)
-        elif in_graph:
-            image = None
-        elif dev_rng:
-            image = randn(shape, generator.at(draw), sample_offset, self.device)
-        else:
-            image = randn_tensor(shape, generator=generator, device=self.device, dtype=torch.float32)
-        self.scheduler.set_timesteps(num_inference_steps)
+        noise = _CallNoise(generator, sample_offset, self.device)
+        ancestral = isinstance(self.scheduler, DDPMSchedulerHIP)
         is_dpm = isinstance(self.scheduler, DPMSolverMultistepSchedulerHIP)
-        if in_graph:
-            h = self._fused.get(self.unet, None, self.scheduler, batch_size, num_inference_steps, _lib.RLDM_SAMPLER_DDPM, False, 0)
-            out = torch.empty(shape, device=self.device, dtype=torch.float32)
-            self._fused.run_rng(h, image.contiguous() if image is not None else None, generator.seed, draw, sample_offset, None, out,
-                                check=kwargs.get("check", True))
-            image = out
-        elif fused and (isinstance(self.scheduler, DDPMSchedulerHIP) or is_dpm):
-            zs = None
-            if not is_dpm:
-                zs = step_noise if step_noise is not None else self._draw_step_noise(
-                    num_inference_steps, self.scheduler.timesteps, shape, generator, self.device)
-                zs = zs.to(self.device, torch.float32).contiguous()
-            h = self._fused.get(self.unet, None, self.scheduler, batch_size, num_inference_steps, _sampler_mode(self.scheduler),
-                                False, 0)
-            out = torch.empty_like(image)
-            self._fused.run(h, image.contiguous(), zs, None, out, check=kwargs.get("check", True))
-            image = out
+        image = None
+        # (the captured loop that draws its step noise draws x_T as well when none is given: the one route with a null x_T)
+        if latents is not None or not (ancestral and noise.in_graph(fused, step_noise)):
+            image = noise.x_T(shape, latents, on_host=False).to(device=self.device, dtype=torch.float32)
+        self.scheduler.set_timesteps(num_inference_steps)
+        if fused and (ancestral or is_dpm):
+            image = self._sample_fused(shape, image, noise, step_noise, num_inference_steps, kwargs.get("check", True))
         else:
             for i, t in enumerate(self.progress_bar(self.scheduler.timesteps)):
                 model_output = self.unet(image, t).sample
-                kw = {"noise": step_noise[i]} if step_noise is not None and not is_dpm else {"generator": generator}
-                if dev_rng:
-                    kw.pop("generator", None)
-                    if step_noise is None and isinstance(self.scheduler, DDPMSchedulerHIP):
-                        kw["noise"] = randn(shape, generator.at(draw, 1, i), sample_offset, self.device)
+                z = noise.row(1, i, shape, step_noise) if ancestral or (step_noise is not None and not is_dpm) else None
+                kw = {"noise": z} if z is not None else {"generator": noise.torch_generator}
                 image = self.scheduler.step(model_output, t, image, **kw).prev_sample
         return self._finish(image, output_type, return_dict)
 
@@ -367,43 +429,28 @@ class DDIMPipelineRange(_PipelineBase):
         cfg = self.unet.config
         ss = cfg.sample_size if not isinstance(cfg.sample_size, int) else (cfg.sample_size, cfg.sample_size)
         shape = (batch_size, cfg.out_channels, *ss)
-        dev_rng = isinstance(generator, DeviceGenerator)
-        draw = generator.next_draw() if dev_rng else None
-        if dev_rng and eta != 0.0:
-            raise NotImplementedError("DDIM with eta > 0 draws its variance noise from a torch generator")
+        noise = _CallNoise(generator, sample_offset, self._execution_device)
+        noise.refuse_variance_noise(eta)
         if isinstance(generator, list) and len(generator) != batch_size:
             raise ValueError(
                 f"You have passed a list of generators of length {len(generator)}, but requested an effective batch"
                 f" size of {batch_size}. Make sure the batch size matches the length of the generators.")
-        if latents is not None:
-            if tuple(latents.shape) != shape:
-                raise ValueError(f"latents shape {tuple(latents.shape)} != {shape}")
-            image = latents.to(device=self._execution_device, dtype=self.unet.dtype)
-        elif dev_rng:
-            image = randn(shape, generator.at(draw), sample_offset, self._execution_device)
-        else:
-            image = randn_tensor(shape, generator=generator, device=self._execution_device, dtype=self.unet.dtype)
+        image = noise.x_T(shape, latents, on_host=False).to(device=self._execution_device, dtype=self.unet.dtype)
         self.scheduler.set_timesteps(num_inference_steps)
+        check = kwargs.get("check", True)
         if known is not None:
             if known_mask is None:
                 raise ValueError("`known` needs `known_mask`")
             if eta != 0.0:
                 raise NotImplementedError("guided DDIM sampling is eta = 0")
             m = (known_mask.to(torch.float32) > 0.5).to(torch.float32)
-            image = self._guided_latents(None, image, known, m, num_inference_steps, jump_length, jump_n_sample, generator, None,
-                                         known_noise, renoise_noise, fused, kwargs.get("check", True), draw=draw,
-                                         sample_offset=sample_offset)
-            return self._finish(image, output_type, return_dict)
-        if fused and eta == 0.0:
-            h = self._fused.get(self.unet, None, self.scheduler, batch_size, num_inference_steps, 0,
-                                self.pos_encoding, 0, eta)
-            out = torch.empty_like(image)
-            self._fused.run(h, image.contiguous(), None, None, out, check=kwargs.get("check", True))
-            image = out
+            image = self._guided_latents(None, image, known, m, num_inference_steps, jump_length, jump_n_sample, noise, None,
+                                         known_noise, renoise_noise, fused, check)
+        elif fused and eta == 0.0:
+            image = self._sample_fused(shape, image, noise, None, num_inference_steps, check, pos_encoding=self.pos_encoding)
         else:
             if self.pos_encoding:
-                pos_encoding = torch.zeros([shape[0], 1, shape[2], shape[3]], device=self.device)
-                pos_encoding[:, :, 0, :] = 1
+                pos_encoding = _pos_channel(shape[0], shape[2], shape[3], self.device)
             for t in self.progress_bar(self.scheduler.timesteps):
                 model_input = image
                 if self.pos_encoding:
@@ -411,7 +458,7 @@ class DDIMPipelineRange(_PipelineBase):
                 model_output = self.unet(model_input, t).sample
                 image = self.scheduler.step(model_output, t, image, eta=eta,
                                             use_clipped_model_output=use_clipped_model_output,
-                                            generator=None if dev_rng else generator).prev_sample
+                                            generator=noise.torch_generator).prev_sample
         return self._finish(image, output_type, return_dict)
 
 
@@ -457,27 +504,21 @@ class LDMPipelineRange(_PipelineBase):
         fused=False loop).  A scheduler other than DDIMSchedulerHIP, eta != 0, jump_length / jump_n_sample != 1 and final_only=False
         are refused (NotImplementedError).  `return_latents=True` then returns (images, final latents, L (B,) float64 of the last
         guided iteration); `latent_trace=` a list receives every step's latents."""
-        if decoder_guidance is not None and decoder_guidance is not False:
-            from .guidance import refuse_unsupported
+        decoder_guided = decoder_guidance is not None and decoder_guidance is not False
+        if decoder_guided:
+            from .guidance import decoder_guided_call, refuse_unsupported
             refuse_unsupported(self.scheduler, eta, jump_length, jump_n_sample, final_only)
         cfg = self.unet.config
         shape = (batch_size, cfg.out_channels, *cfg.sample_size)
-        dev_rng = isinstance(generator, DeviceGenerator)
-        draw = generator.next_draw() if dev_rng else None
-        if latents is None and dev_rng:
-            latents = randn(shape, generator.at(draw), sample_offset, self.device)
-        elif latents is None:
-            latents = randn_tensor(shape, generator=generator)          # CPU draw, as ldm/pipelines.py:329-333
-        latents = latents.to(self.device)
+        noise = _CallNoise(generator, sample_offset, self.device)
+        latents = noise.x_T(shape, latents, on_host=True).to(self.device)
         latents = latents * self.scheduler.init_noise_sigma
         self.scheduler.set_timesteps(num_inference_steps)
-        accepts_eta = "eta" in set(inspect.signature(self.scheduler.step).parameters.keys())
         is_ddim = isinstance(self.scheduler, DDIMSchedulerHIP)
-        is_ddpm = isinstance(self.scheduler, DDPMSchedulerHIP)
-        if dev_rng and is_ddim and eta != 0.0:
-            raise NotImplementedError("DDIM with eta > 0 draws its variance noise from a torch generator")
-        if decoder_guidance is not None and decoder_guidance is not False:
-            from .guidance import decoder_guided_call
+        check = kwargs.get("check", True)
+        if is_ddim:
+            noise.refuse_variance_noise(eta)
+        if decoder_guided:
             image, lat, last = decoder_guided_call(self, self._decoder_guide(decoder_guidance), latents.float(), num_inference_steps,
                                                    known, known_mask, guidance_scale, guidance_iters, guidance_start, guidance_stop,
                                                    trace=kwargs.get("latent_trace"))
@@ -498,54 +539,21 @@ class LDMPipelineRange(_PipelineBase):
             image = torch.empty((batch_size, self.vae._cfg.out_channels, shape[2] * f, shape[3] * f), device=self.device,
                                 dtype=torch.float32)
             lat = self._guided_latents(self.vae, latents.float(), z0, lat_mask, num_inference_steps, jump_length, jump_n_sample,
-                                       generator, step_noise, known_noise, renoise_noise, fused, kwargs.get("check", True), out=image,
-                                       draw=draw, sample_offset=sample_offset)
+                                       noise, step_noise, known_noise, renoise_noise, fused, check, out=image)
             if not fused:
                 image = self.vae.decode(lat / sf).sample
             if kwargs.get("return_latents", False):
                 return image, lat, z0, lat_mask.to(self.device)
             return self._finish(image, output_type, return_dict)
         if fused and final_only and (not is_ddim or eta == 0.0):
-            mode = _sampler_mode(self.scheduler)
-            in_graph = dev_rng and mode == _lib.RLDM_SAMPLER_DDPM and step_noise is None
-            zs = None
-            if mode == _lib.RLDM_SAMPLER_DDPM and not in_graph:
-                zs = step_noise if step_noise is not None else self._draw_step_noise(
-                    num_inference_steps, self.scheduler.timesteps, shape, generator, self.device)
-                zs = zs.to(self.device, torch.float32).contiguous()
-            h = self._fused.get(self.unet, self.vae, self.scheduler, batch_size, num_inference_steps, mode,
-                                self.pos_encoding, 0)
-            f = self.vae._cfg.downscale
-            image = torch.empty((batch_size, self.vae._cfg.out_channels, shape[2] * f, shape[3] * f),
-                                device=self.device, dtype=torch.float32)
-            if in_graph:
-                self._fused.run_rng(h, latents.float().contiguous(), generator.seed, draw, sample_offset, None, image,
-                                    check=kwargs.get("check", True))
-            else:
-                self._fused.run(h, latents.float().contiguous(), zs, None, image, check=kwargs.get("check", True))
+            image = self._sample_fused(shape, latents, noise, step_noise, num_inference_steps, check, vae=self.vae,
+                                       pos_encoding=self.pos_encoding)
             return self._finish(image, output_type, return_dict)
-        extra_kwargs = {"eta": eta} if accepts_eta else {}
-        if self.pos_encoding:
-            pos_encoding = torch.zeros([shape[0], 1, shape[2], shape[3]], device=self.device)
-            pos_encoding[:, :, 0, :] = 1
         if not final_only:
             assert output_type == "torch"
-            image_list = []
-        for i, t in enumerate(self.progress_bar(self.scheduler.timesteps)):
-            if not final_only:
-                image_list.append(self.vae.decode(latents / self.vae.config.scaling_factor).sample)
-            latent_model_input = self.scheduler.scale_model_input(latents, t)
-            if self.pos_encoding:
-                latent_model_input = torch.cat([latent_model_input, pos_encoding], dim=1)
-            noise_prediction = self.unet(latent_model_input, t).sample
-            kw = dict(extra_kwargs)
-            if step_noise is not None and is_ddpm:
-                kw["noise"] = step_noise[i]
-            elif dev_rng and is_ddpm:
-                kw["noise"] = randn(shape, generator.at(draw, 1, i), sample_offset, self.device)
-            latents = self.scheduler.step(noise_prediction, t, latents, **kw).prev_sample
-        latents = latents / self.vae.config.scaling_factor
-        image = self.vae.decode(latents).sample
+        image_list = None if final_only else []
+        pos_encoding = _pos_channel(shape[0], shape[2], shape[3], self.device) if self.pos_encoding else None
+        image = self._latent_loop(latents, pos_encoding, noise, step_noise, eta, images=image_list)
         if output_type == "torch" and not final_only:
             image_list.append(image)
             return image_list
@@ -579,20 +587,15 @@ class LDMUpscalePipelineRange(_PipelineBase):
             raise ValueError("`image` input cannot be undefined.")
         cfg = self.unet.config
         shape = (batch_size, cfg.out_channels, *cfg.sample_size)
-        dev_rng = isinstance(generator, DeviceGenerator)
-        if dev_rng and mask is not None and encode_noise is None:
-            encode_noise = randn(shape, generator, sample_offset, self.unet.device)
-        draw = generator.next_draw() if dev_rng else None
-        if latents is None and dev_rng:
-            latents = randn(shape, generator.at(draw), sample_offset, self.unet.device)
-        elif latents is None:
-            latents = randn_tensor(shape, generator=generator)
-        latents = latents.to(self.unet.device)
+        if mask is not None and encode_noise is None:
+            encode_noise = _CallNoise.own_draw(shape, generator, sample_offset, self.unet.device)
+        noise = _CallNoise(generator, sample_offset, self.unet.device)
+        latents = noise.x_T(shape, latents, on_host=True).to(self.unet.device)
         if mask is None:
             assert condition_encoder is not None
             image = condition_encoder(image)
         else:
-            image = self.encode_masked_image(image, mask, generator=None if dev_rng else generator, noise=encode_noise)
+            image = self.encode_masked_image(image, mask, generator=noise.torch_generator, noise=encode_noise)
         image = image.to(dtype=latents.dtype, device=self.unet.device)
         height, width = image.shape[2:]
         assert cfg.in_channels == cfg.out_channels + image.shape[1]
@@ -600,39 +603,9 @@ class LDMUpscalePipelineRange(_PipelineBase):
         assert width == cfg.sample_size[1]
         latents = latents * self.scheduler.init_noise_sigma
         self.scheduler.set_timesteps(num_inference_steps)
-        accepts_eta = "eta" in set(inspect.signature(self.scheduler.step).parameters.keys())
-        is_ddim = isinstance(self.scheduler, DDIMSchedulerHIP)
-        is_ddpm = isinstance(self.scheduler, DDPMSchedulerHIP)
-        if fused and (not is_ddim or eta == 0.0):
-            mode = _sampler_mode(self.scheduler)
-            in_graph = dev_rng and mode == _lib.RLDM_SAMPLER_DDPM and step_noise is None
-            zs = None
-            if mode == _lib.RLDM_SAMPLER_DDPM and not in_graph:
-                zs = step_noise if step_noise is not None else self._draw_step_noise(
-                    num_inference_steps, self.scheduler.timesteps, shape, generator, self.device)
-                zs = zs.to(self.device, torch.float32).contiguous()
-            h = self._fused.get(self.unet, self.vae, self.scheduler, batch_size, num_inference_steps, mode, False,
-                                image.shape[1])
-            f = self.vae._cfg.downscale
-            out = torch.empty((batch_size, self.vae._cfg.out_channels, shape[2] * f, shape[3] * f),
-                              device=self.device, dtype=torch.float32)
-            if in_graph:
-                self._fused.run_rng(h, latents.float().contiguous(), generator.seed, draw, sample_offset, image.float().contiguous(), out,
-                                    check=kwargs.get("check", True))
-            else:
-                self._fused.run(h, latents.float().contiguous(), zs, image.float().contiguous(), out, check=kwargs.get("check", True))
-            return self._finish(out, output_type, return_dict)
-        extra_kwargs = {"eta": eta} if accepts_eta else {}
-        for i, t in enumerate(self.progress_bar(self.scheduler.timesteps)):
-            latent_model_input = self.scheduler.scale_model_input(latents, t)
-            latent_model_input = torch.cat([latent_model_input, image], dim=1)
-            noise_prediction = self.unet(latent_model_input, t).sample
-            kw = dict(extra_kwargs)
-            if step_noise is not None and is_ddpm:
-                kw["noise"] = step_noise[i]
-            elif dev_rng and is_ddpm:
-                kw["noise"] = randn(shape, generator.at(draw, 1, i), sample_offset, self.device)
-            latents = self.scheduler.step(noise_prediction, t, latents, **kw).prev_sample
-        latents = latents / self.vae.config.scaling_factor
-        out = self.vae.decode(latents).sample
+        if fused and (not isinstance(self.scheduler, DDIMSchedulerHIP) or eta == 0.0):
+            out = self._sample_fused(shape, latents, noise, step_noise, num_inference_steps, kwargs.get("check", True), vae=self.vae,
+                                     cond=image)
+        else:
+            out = self._latent_loop(latents, image, noise, step_noise, eta)
         return self._finish(out, output_type, return_dict)

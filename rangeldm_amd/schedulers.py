@@ -140,38 +140,30 @@ class _SchedulerBase:
         a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self._alpha_final()
         return a_t, a_prev
 
+    def _noised(self, first, second, timesteps, sign, what):
+        """sqrt(abar_t) * first + sign * sqrt(1 - abar_t) * second per sample (rldm_sched_add_noise); `first` gives device and shape."""
+        a = self.alphas_cumprod[timesteps.detach().to("cpu", torch.int64).reshape(-1)]
+        sa = (a ** 0.5).numpy().astype(np.float32)
+        sb = (sign * (1 - a) ** 0.5).numpy().astype(np.float32)
+        B = first.shape[0]
+        out = torch.empty_like(first)
+        _lib.check(_lib.lib().rldm_sched_add_noise(
+            _lib.ptr(first), _lib.ptr(second), sa.ctypes.data_as(C.POINTER(C.c_float)), sb.ctypes.data_as(C.POINTER(C.c_float)), B,
+            first.numel() // B, _lib.ptr(out), _lib.stream_ptr(first.device)), what)
+        return out
+
     def add_noise(self, original_samples, noise, timesteps):
         x0 = original_samples.to(dtype=torch.float32).contiguous()
         nz = noise.to(device=x0.device, dtype=torch.float32).contiguous()
-        t = timesteps.detach().to("cpu", torch.int64).reshape(-1)
-        a = self.alphas_cumprod[t]
-        sa = (a ** 0.5).numpy().astype(np.float32)
-        sb = ((1 - a) ** 0.5).numpy().astype(np.float32)
-        B = x0.shape[0]
-        out = torch.empty_like(x0)
-        _lib.check(_lib.lib().rldm_sched_add_noise(
-            C.c_void_p(x0.data_ptr()), C.c_void_p(nz.data_ptr()), sa.ctypes.data_as(C.POINTER(C.c_float)),
-            sb.ctypes.data_as(C.POINTER(C.c_float)), B, x0.numel() // B, C.c_void_p(out.data_ptr()),
-            _lib.stream_ptr(x0.device)), "rldm_sched_add_noise")
-        return out
+        return self._noised(x0, nz, timesteps, 1.0, "rldm_sched_add_noise")
 
     def get_velocity(self, sample, noise, timesteps):
         """`DDPMScheduler.get_velocity` (the v_prediction target, ldm/train_unconditional.py:507-508):
         v = sqrt(alpha_prod_t) * noise - sqrt(1 - alpha_prod_t) * sample.  The same elementwise map as add_noise with the two
-        tensors swapped and the second coefficient negated (rldm_sched_add_noise)."""
+        tensors swapped and the second coefficient negated."""
         x0 = sample.to(dtype=torch.float32).contiguous()
         nz = noise.to(device=x0.device, dtype=torch.float32).contiguous()
-        t = timesteps.detach().to("cpu", torch.int64).reshape(-1)
-        a = self.alphas_cumprod[t]
-        sa = (a ** 0.5).numpy().astype(np.float32)
-        sb = (-((1 - a) ** 0.5)).numpy().astype(np.float32)
-        B = x0.shape[0]
-        out = torch.empty_like(x0)
-        _lib.check(_lib.lib().rldm_sched_add_noise(
-            C.c_void_p(nz.data_ptr()), C.c_void_p(x0.data_ptr()), sa.ctypes.data_as(C.POINTER(C.c_float)),
-            sb.ctypes.data_as(C.POINTER(C.c_float)), B, x0.numel() // B, C.c_void_p(out.data_ptr()),
-            _lib.stream_ptr(x0.device)), "rldm_sched_add_noise (get_velocity)")
-        return out
+        return self._noised(nz, x0, timesteps, -1.0, "rldm_sched_add_noise (get_velocity)")
 
     def _launch(self, sampler_mode, coef, model_output, sample, noise):
         e = model_output.to(dtype=torch.float32).contiguous()
@@ -179,8 +171,7 @@ class _SchedulerBase:
         nz = None if noise is None else noise.to(device=e.device, dtype=torch.float32).contiguous()
         out = torch.empty_like(x)
         cf = (C.c_float * 5)(*[float(v) for v in coef])
-        _lib.check(_lib.lib().rldm_sched_step(sampler_mode, self.prediction_code, cf, C.c_void_p(e.data_ptr()), C.c_void_p(x.data_ptr()),
-                                              C.c_void_p(nz.data_ptr()) if nz is not None else None, C.c_void_p(out.data_ptr()),
+        _lib.check(_lib.lib().rldm_sched_step(sampler_mode, self.prediction_code, cf, _lib.ptr(e), _lib.ptr(x), _lib.ptr(nz), _lib.ptr(out),
                                               x.numel(), _lib.stream_ptr(e.device)), "scheduler step")
         return out
 
@@ -412,12 +403,20 @@ class DPMSolverMultistepSchedulerHIP(_SchedulerBase):
         row = self._table[i] if self._have_x0 else self._table_first[i]
         out = torch.empty_like(x)
         cf = (C.c_float * 5)(*[float(v) for v in row])
-        _lib.check(_lib.lib().rldm_sched_dpmsolver_step(self.prediction_code, cf, C.c_void_p(e.data_ptr()), C.c_void_p(x.data_ptr()),
-                                                        C.c_void_p(self._hist.data_ptr()), C.c_void_p(out.data_ptr()), x.numel(),
-                                                        _lib.stream_ptr(e.device)), "DPM-Solver++ step")
+        _lib.check(_lib.lib().rldm_sched_dpmsolver_step(self.prediction_code, cf, _lib.ptr(e), _lib.ptr(x), _lib.ptr(self._hist), _lib.ptr(out),
+                                                        x.numel(), _lib.stream_ptr(e.device)), "DPM-Solver++ step")
         self._have_x0 = True
         self._step_index = i + 1
         return SchedulerOutput(out) if return_dict else (out,)
+
+
+def sampler_mode(scheduler):
+    """rldm_sampler_config::mode of a scheduler: DDIM, DPM-Solver++, else the (strided ancestral) DDPM step."""
+    if isinstance(scheduler, DDIMSchedulerHIP):
+        return _lib.RLDM_SAMPLER_DDIM
+    if isinstance(scheduler, DPMSolverMultistepSchedulerHIP):
+        return _lib.RLDM_SAMPLER_DPMSOLVER
+    return _lib.RLDM_SAMPLER_DDPM
 
 
 # ---- guided sampling on unconditional weights (RePaint-style known-region replacement) -----------------------------------
@@ -467,16 +466,14 @@ def repaint_program(scheduler, num_inference_steps, jump_length=1, jump_n_sample
 def guided_step(scheduler, row, model_output, sample, noise, known, mask, known_noise, renoise_noise):
     """One row of a guided program outside the captured loop (rldm_sched_guided_step): the scheduler's step with row[0:5], the
     known-region blend with row[5:7], the re-noise with row[7:9].  mask: [B, 1, W, H], 1 = known."""
-    if isinstance(scheduler, DPMSolverMultistepSchedulerHIP):
+    mode = sampler_mode(scheduler)
+    if mode == _lib.RLDM_SAMPLER_DPMSOLVER:
         raise NotImplementedError("guided sampling runs DDPM or DDIM (eta = 0) rows")
-    mode = _lib.RLDM_SAMPLER_DDIM if isinstance(scheduler, DDIMSchedulerHIP) else _lib.RLDM_SAMPLER_DDPM
     e = model_output.to(dtype=torch.float32).contiguous()
+    ptr = _lib.ptr
 
     def dev(t):
         return None if t is None else t.to(device=e.device, dtype=torch.float32).contiguous()
-
-    def ptr(t):
-        return C.c_void_p(t.data_ptr()) if t is not None else None
     x, z0, m = dev(sample), dev(known), dev(mask)
     nz = dev(noise) if row[4] != 0.0 else None
     nk = dev(known_noise) if row[6] != 0.0 else None

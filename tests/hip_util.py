@@ -899,3 +899,34 @@ def discriminator_residues():
     well and hand views of them to train_disc.hip / train_meta.hip (and to rldm_train_colsum): name -> set, over
     discriminator_layouts()."""
     return {k: flat_buffer_residues(names, shapes) for k, (names, shapes) in discriminator_layouts().items()}
+
+
+# ---- the small models of the sampler and pipeline tests --------------------------------------------------------------------
+def small_cfg(in_ch, out_ch):
+    from rangeldm_amd.config import UNetConfig
+    return UNetConfig(sample_size=(32, 8), in_channels=in_ch, out_channels=out_ch, block_out_channels=(32, 32, 64, 64))
+
+
+def hip_unet(cfg, prefix):
+    from rangeldm_amd.params import unet_param_shapes
+    from rangeldm_amd.synth import synth_state_dict
+    from rangeldm_amd.unet import UNet2DModelHIP
+    m = UNet2DModelHIP(cfg)
+    m.load_state_dict(synth_state_dict(unet_param_shapes(cfg), prefix=prefix))
+    return m
+
+
+_VAE = {}
+
+
+def hip_vae():
+    """One default-config VAE with synthetic weights, shared by every test that asks."""
+    from rangeldm_amd.config import VAEConfig
+    from rangeldm_amd.params import vae_param_shapes
+    from rangeldm_amd.synth import synth_state_dict
+    from rangeldm_amd.vae import AutoencoderKLHIP
+    if "m" not in _VAE:
+        m = AutoencoderKLHIP(VAEConfig())
+        m.load_state_dict(synth_state_dict(vae_param_shapes(VAEConfig()), prefix="vae."))
+        _VAE["m"] = m
+    return _VAE["m"]

@@ -13,11 +13,12 @@ import pytest
 import torch
 
 from rangeldm_amd import _lib, rng
-from rangeldm_amd.config import UNetConfig, VAEConfig
+from rangeldm_amd.config import UNetConfig
 from rangeldm_amd.params import unet_param_shapes, vae_param_shapes
 from rangeldm_amd.schedulers import (DDIMSchedulerHIP, DDPMSchedulerHIP, DPMSolverMultistepSchedulerHIP, randn_tensor,
                                      repaint_program)
 from rangeldm_amd.synth import normal, synth_state_dict
+from tests.hip_util import hip_unet, hip_vae, small_cfg
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -149,29 +150,6 @@ def test_randn_into_an_unaligned_view_and_through_randn_tensor():
 
 
 # ---- the captured samplers ------------------------------------------------------------------------------------------------
-def small_cfg(in_ch, out_ch):
-    return UNetConfig(sample_size=(32, 8), in_channels=in_ch, out_channels=out_ch, block_out_channels=(32, 32, 64, 64))
-
-
-def hip_unet(cfg, prefix):
-    from rangeldm_amd.unet import UNet2DModelHIP
-    m = UNet2DModelHIP(cfg)
-    m.load_state_dict(synth_state_dict(unet_param_shapes(cfg), prefix=prefix))
-    return m
-
-
-_VAE = {}
-
-
-def hip_vae():
-    from rangeldm_amd.vae import AutoencoderKLHIP
-    if "m" not in _VAE:
-        m = AutoencoderKLHIP(VAEConfig())
-        m.load_state_dict(synth_state_dict(vae_param_shapes(VAEConfig()), prefix="vae."))
-        _VAE["m"] = m
-    return _VAE["m"]
-
-
 def explicit(gen, draw, rows, shape, offset, purposes=(1,)):
     """x_T and the [rows, *shape] tensors of `purposes` that a sampler drawing (gen.seed, draw) at `offset` reads."""
     return rng.randn(shape, gen.at(draw), offset), [rng.randn_rows(rows, shape, gen, draw, q, offset) for q in purposes]
