@@ -156,6 +156,24 @@ int rldm_sched_guided_step(int sampler_mode, int prediction_type, const float co
  * step's x0; it must not alias the other tensors.  The same rows are rldm_sampler_config::coef for RLDM_SAMPLER_DPMSOLVER. */
 int rldm_sched_dpmsolver_step(int prediction_type, const float coef[5], const float* model_output, const float* x,
                               float* x0_history, float* x_prev, int64_t n, void* stream);
+/* replaces UniPCMultistepScheduler.step (diffusers; solver_type "bh2", predict_x0, solver_order 1..3, lower_order_final,
+ * final_sigmas_type "zero"): the predictor UniP and the corrector UniC of Zhao et al. 2023 on the grid of rldm_sched_dpmsolver_step.
+ * Step i runs with order o_i = min(solver_order, N - i, steps taken + 1); m_k is the x0 prediction of step k.  One launch, fp32:
+ *   m_i    = the RLDM_PRED_* conversion above with sqrt_alpha_t = alpha_i, sqrt_beta_t = s_i, on the x the network saw
+ *   x_c    = use_corr ? k_last*last + k_1*m_{i-1} + k_2*m_{i-2} + k_3*m_{i-3} + k_t*m_i : x        (UniC of order o_{i-1}; i >= 1)
+ *   x_prev = p_x*x_c + p_0*m_i + p_1*m_{i-1} + p_2*m_{i-2}                                        (UniP of order o_i)
+ *   last <- x_c;  hist[2] <- hist[1];  hist[1] <- hist[0];  hist[0] <- m_i
+ * coef = {alpha_i, s_i, use_corr, k_last, k_1, k_2, k_3, k_t, p_x, p_0, p_1, p_2}, from the host in float64
+ * (rangeldm_amd/schedulers.py, UniPCMultistepSchedulerHIP: B = phi1 = expm1(-h), the rho of the R rho = b systems folded in); the last
+ * row is {alpha, s, ., ..., 0, 1, 0, 0}: the step returns m_i.
+ * last: device fp32 [n], the previous step's x_c; hist: device fp32 [3][n], hist[k] = m_{i-1-k} on entry.  Both are read only under a
+ * non-zero coefficient (a term whose coefficient is 0 is left out, so a first step may find anything there, NaN included; the shift
+ * still moves hist[0] and hist[1]) and rewritten element-wise by the thread that read them, so a replayed graph needs no pointer
+ * rotation.  x_prev may be x itself (no other overlap with x, none with model_output).  last and hist must not overlap
+ * model_output, x, x_prev or each other.  Any other overlap is refused.
+ * The same rows are rldm_sampler_config::coef for RLDM_SAMPLER_UNIPC. */
+int rldm_sched_unipc_step(int prediction_type, const float coef[12], const float* model_output, const float* x, float* last,
+                          float* hist, float* x_prev, int64_t n, void* stream);
 /* replaces DDPMScheduler.add_noise (ldm/train_unconditional.py:498): out = sa[b]*x0 + sb[b]*noise (sa, sb HOST [B]).
  * DDPMScheduler.get_velocity (ldm/train_unconditional.py:508) is the same map: v = sa[b]*noise - sb[b]*x0, i.e. this entry point
  * with (x0, noise) swapped and sb negated (rangeldm_amd/schedulers.py get_velocity). */
@@ -167,6 +185,9 @@ int rldm_sched_add_noise(const float* x0, const float* noise, const float* sqrt_
 #define RLDM_SAMPLER_DDPM 1   /* strided ancestral DDPM (LDMPipelineRange as shipped, ldm/pipelines.py:282-383) */
 #define RLDM_SAMPLER_DPMSOLVER 2   /* DPM-Solver++(2M), rows of rldm_sched_dpmsolver_step; each lane keeps its x0 history on the
                                     * device, so rldm_sample takes no step_noise (NULL) and no state carries between calls */
+#define RLDM_SAMPLER_UNIPC 3       /* UniPC (bh2), rows of rldm_sched_unipc_step; each lane keeps `last` and the three-entry x0 history
+                                    * on the device; unguided only, no step_noise, no state carries between calls.  The step is always
+                                    * a launch of its own behind conv_out (as with RLDM_FLAG_SCHED_LAUNCH) */
 
 typedef struct rldm_sampler_config {
     int32_t batch;            /* per-GPU batch                                                                */
@@ -180,7 +201,8 @@ typedef struct rldm_sampler_config {
      * epilogue cannot pack the next step's input.  0 (what a zeroed struct says): everything else here, unchanged.  The field is the
      * newest one; it sits in what was the alignment hole in front of `coef`, so no existing offset and not the struct's size moved. */
     int32_t guided;
-    /* per-step scheduler coefficients, HOST, [num_steps][5] in the layout of rldm_sched_{ddim,ddpm,dpmsolver}_step ([9]: guided) */
+    /* per-step scheduler coefficients, HOST, [num_steps][5] in the layout of rldm_sched_{ddim,ddpm,dpmsolver}_step ([9]: guided;
+     * [12]: RLDM_SAMPLER_UNIPC, the layout of rldm_sched_unipc_step) */
     const float* coef;
     /* timesteps, HOST int64 [num_steps] (scheduler.timesteps)                                                 */
     const int64_t* timesteps;
@@ -195,7 +217,7 @@ typedef struct rldm_sampler_config {
 int rldm_sampler_create(rldm_unet* unet, rldm_vae* vae, const rldm_sampler_config* cfg, rldm_sampler** out);
 void rldm_sampler_destroy(rldm_sampler* s);
 /* replaces the loop + decode of ldm/pipelines.py:353-367 (:496-507 with cond, :234-246 without VAE).
- * x_T: device fp32 [B, out_ch, W, H]; step_noise: device fp32 [num_steps, B, out_ch, W, H] (DDPM) or NULL (DDIM, DPMSOLVER);
+ * x_T: device fp32 [B, out_ch, W, H]; step_noise: device fp32 [num_steps, B, out_ch, W, H] (DDPM) or NULL (DDIM, DPMSOLVER, UNIPC);
  * cond: device fp32 [B, cond_channels, W, H] or NULL; images: device fp32 [B, 2, 4W, 4H] (or the final x_0 when
  * the sampler has no VAE); latents_out: optional device fp32 [B, out_ch, W, H] receiving the final latent. */
 int rldm_sample(rldm_sampler* s, const float* x_T, const float* step_noise, const float* cond, float* images,

@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RLDM_LIB") or os.path.join(_HERE, "librangeldm_hip.so")
 RLDM_MAX_LEVELS = 8
 # rldm_sampler_config::mode (RLDM_SAMPLER_*)
-RLDM_SAMPLER_DDIM, RLDM_SAMPLER_DDPM, RLDM_SAMPLER_DPMSOLVER = 0, 1, 2
+RLDM_SAMPLER_DDIM, RLDM_SAMPLER_DDPM, RLDM_SAMPLER_DPMSOLVER, RLDM_SAMPLER_UNIPC = 0, 1, 2, 3
 # rldm_emd_matrix: the `symmetric` argument, and the return value that reports a pair at the bid cap
 RLDM_EMD_RECT, RLDM_EMD_SYMMETRIC, RLDM_EMD_DIAGONAL = 0, 1, 2
 RLDM_EMD_BID_CAP = 2
@@ -167,6 +167,7 @@ PROTOTYPES = {
     "rldm_sched_ddpm_step": (C.c_int, [C.POINTER(C.c_float), _P, _P, _P, _P, C.c_int64, _P]),
     "rldm_sched_step": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_float), _P, _P, _P, _P, C.c_int64, _P]),
     "rldm_sched_dpmsolver_step": (C.c_int, [C.c_int, C.POINTER(C.c_float), _P, _P, _P, _P, C.c_int64, _P]),
+    "rldm_sched_unipc_step": (C.c_int, [C.c_int, C.POINTER(C.c_float), _P, _P, _P, _P, _P, C.c_int64, _P]),
     # rldm_sched_step + known-region blend + re-noise (the row of a guided sampler)
     "rldm_sched_guided_step": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int,
                                          C.c_int64, _P]),

@@ -176,6 +176,7 @@ __global__ void __launch_bounds__(256) sched_step_kernel(const SchedParams p) {
     }
 }
 int launch_sched_step(const SchedParams& p, hipStream_t stream) {
+    RLDM_REQUIRE(p.mode >= 0, "scheduler step: this sampler mode has no 5-wide row (sched_mode_word)");
     const unsigned grid = (unsigned)((p.n + 255) / 256 > 2048 ? 2048 : (p.n + 255) / 256);
     hipLaunchKernelGGL(sched_step_kernel, dim3(grid), dim3(256), 0, stream, p);
     RLDM_HIP_CHECK(hipGetLastError());
@@ -260,6 +261,7 @@ template <int V> __global__ void __launch_bounds__(256) sched_guided_step_kernel
     }
 }
 int launch_sched_guided_step(const GuidedSchedParams& p, hipStream_t stream) {
+    RLDM_REQUIRE(p.s.mode >= 0, "guided scheduler step: this sampler mode has no 5-wide row (sched_mode_word)");
     auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     const bool vec = p.s.n % 4 == 0 && p.spatial % 4 == 0 && p.s.noise_step_stride % 4 == 0 && al(p.s.x) && al(p.s.eps) &&
                      al(p.s.x_prev) && al(p.s.noise) && al(p.known) && al(p.mask) && al(p.known_noise) && al(p.renoise_noise);
@@ -267,6 +269,108 @@ int launch_sched_guided_step(const GuidedSchedParams& p, hipStream_t stream) {
     const unsigned grid = (unsigned)((groups + 255) / 256 > 2048 ? 2048 : (groups + 255) / 256);
     if (vec) hipLaunchKernelGGL(sched_guided_step_kernel<4>, dim3(grid), dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(sched_guided_step_kernel<1>, dim3(grid), dim3(256), 0, stream, p);
+    RLDM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---- UniPC step (diffusers UniPCMultistepScheduler.step: bh2, predict_x0; include/rangeldm_hip.h, rldm_sched_unipc_step) --------------
+// Per element, fp32, row c = {alpha, s, use_corr, k_last, k_1, k_2, k_3, k_t, p_x, p_0, p_1, p_2}, h0 / h1 / h2 = the x0 predictions of the
+// three previous steps:
+//   m   = x0 of the model output (the conversions of sched_prev, with the sample the network saw)
+//   x_c = use_corr ? k_last * last + k_1 * h0 + k_2 * h1 + k_3 * h2 + k_t * m : x          (UniC, order of the previous step)
+//   x'  = p_x * x_c + p_0 * m + p_1 * h0 + p_2 * h1                                         (UniP)
+//   last <- x_c, h2 <- h1, h1 <- h0, h0 <- m       by the thread that read them: the step graph replays with the same pointers
+// A term whose coefficient is 0 is left out, not multiplied: a first step runs on a history that holds anything (NaN included), and
+// `last` / h2 are then not even loaded.  h0 and h1 are always loaded -- the shift moves them.
+// Groups of four elements move as one 16-byte load or store per tensor (global_load_dwordx4 / global_store_dwordx4: up to 6 loads and 5
+// stores per group); the n % 4 last elements are a scalar tail of workgroup 0.  No LDS.
+// (a native vector, not HIP's float4 struct, whose store is split into four 4-byte stores and not merged again; aligned(4): a hist slot
+//  starts n floats behind the previous one, and gfx950's global_load / global_store_dwordx4 take any 4-byte-aligned address)
+typedef float unipc_f4 __attribute__((ext_vector_type(4), aligned(4)));
+struct UniPCVec { float v[4]; };
+__device__ __forceinline__ UniPCVec unipc_load(const float* p) {
+    const unipc_f4 t = *reinterpret_cast<const unipc_f4*>(p);
+    return UniPCVec{{t.x, t.y, t.z, t.w}};
+}
+__device__ __forceinline__ void unipc_store(float* p, const UniPCVec& r) {
+    unipc_f4 t;
+    t.x = r.v[0]; t.y = r.v[1]; t.z = r.v[2]; t.w = r.v[3];
+    *reinterpret_cast<unipc_f4*>(p) = t;
+}
+__device__ __forceinline__ void unipc_element(const float* c, const int pred, const float e, const float x, const float last, const float h0,
+                                              const float h1, const float h2, float& m_out, float& xc_out, float& xn_out) {
+#pragma clang fp contract(off)
+    float m;
+    if (pred == 0) {
+        m = __builtin_fmaf(-c[1], e, x) / c[0];
+    } else if (pred == 1) {
+        const float se = c[1] * e;
+        m = __builtin_fmaf(c[0], x, -se);
+    } else {
+        m = e;
+    }
+    float xc = x;
+    if (c[2] != 0.f) {
+        xc = c[7] * m;
+        if (c[3] != 0.f) xc = __builtin_fmaf(c[3], last, xc);
+        if (c[4] != 0.f) xc = __builtin_fmaf(c[4], h0, xc);
+        if (c[5] != 0.f) xc = __builtin_fmaf(c[5], h1, xc);
+        if (c[6] != 0.f) xc = __builtin_fmaf(c[6], h2, xc);
+    }
+    float xn = c[9] * m;
+    if (c[8] != 0.f) xn = __builtin_fmaf(c[8], xc, xn);
+    if (c[10] != 0.f) xn = __builtin_fmaf(c[10], h0, xn);
+    if (c[11] != 0.f) xn = __builtin_fmaf(c[11], h1, xn);
+    m_out = m; xc_out = xc; xn_out = xn;
+}
+__global__ void __launch_bounds__(256) sched_unipc_kernel(const UniPCParams p) {
+    float c[12];
+    if (p.coef_table) {
+        const float* row = p.coef_table + 12 * (long long)*p.step_ptr;
+#pragma unroll
+        for (int j = 0; j < 12; ++j) c[j] = row[j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < 12; ++j) c[j] = p.coef[j];
+    }
+    const bool corr = c[2] != 0.f;
+    const bool rd_last = corr && c[3] != 0.f, rd_h2 = corr && c[6] != 0.f;
+    float* const h0p = p.hist;
+    float* const h1p = p.hist + p.n;
+    float* const h2p = p.hist + 2 * p.n;
+    const long long groups = p.n / 4;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < groups; q += (long long)gridDim.x * 256) {
+        const long long i = q * 4;
+        const UniPCVec e = unipc_load(p.out + i), x = unipc_load(p.x + i);
+        const UniPCVec h0 = unipc_load(h0p + i), h1 = unipc_load(h1p + i);
+        UniPCVec last = {}, h2 = {}, m, xc, xn;
+        if (rd_last) last = unipc_load(p.last + i);
+        if (rd_h2) h2 = unipc_load(h2p + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) unipc_element(c, p.pred, e.v[j], x.v[j], last.v[j], h0.v[j], h1.v[j], h2.v[j], m.v[j], xc.v[j], xn.v[j]);
+        unipc_store(p.x_prev + i, xn);
+        unipc_store(p.last + i, xc);
+        unipc_store(h2p + i, h1);
+        unipc_store(h1p + i, h0);
+        unipc_store(h0p + i, m);
+    }
+    const long long i = groups * 4 + threadIdx.x;
+    if (blockIdx.x == 0 && i < p.n) {
+        const float h0 = h0p[i], h1 = h1p[i];
+        float m, xc, xn;
+        unipc_element(c, p.pred, p.out[i], p.x[i], rd_last ? p.last[i] : 0.f, h0, h1, rd_h2 ? h2p[i] : 0.f, m, xc, xn);
+        p.x_prev[i] = xn;
+        p.last[i] = xc;
+        h2p[i] = h1;
+        h1p[i] = h0;
+        h0p[i] = m;
+    }
+}
+int launch_sched_unipc_step(const UniPCParams& p, hipStream_t stream) {
+    RLDM_REQUIRE(p.n >= 1 && p.out && p.x && p.last && p.hist && p.x_prev, "UniPC step: null argument or empty tensor");
+    const long long blocks = (p.n / 4 + 255) / 256;
+    const unsigned grid = (unsigned)(blocks > 2048 ? 2048 : blocks < 1 ? 1 : blocks);
+    hipLaunchKernelGGL(sched_unipc_kernel, dim3(grid), dim3(256), 0, stream, p);
     RLDM_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -445,6 +445,22 @@ struct GuidedSchedParams {
     long long spatial;
 };
 int launch_sched_guided_step(const GuidedSchedParams& p, hipStream_t stream);
+// UniPC step (elementwise.hip, sched_unipc_kernel): the row {alpha, s, use_corr, k_last, k_1, k_2, k_3, k_t, p_x, p_0, p_1, p_2} of
+// rldm_sched_unipc_step, baked or row *step_ptr of a [steps][12] device table.  last [n] and hist [3][n] are the solver's state, read
+// (only under a non-zero coefficient) and rewritten element-wise by the same thread; they alias nothing.  x_prev may be x itself.
+struct UniPCParams {
+    int pred;                 // RLDM_PRED_*
+    float coef[12];
+    const float* coef_table;  // device [steps][12] or null
+    const int* step_ptr;
+    const float* out;         // the model output
+    const float* x;
+    float* last;
+    float* hist;
+    float* x_prev;
+    long long n;
+};
+int launch_sched_unipc_step(const UniPCParams& p, hipStream_t stream);
 int launch_add_noise(const float* x0, const float* noise, const float* sa, const float* sb, int B, long long per,
                      float* out, hipStream_t stream);
 int launch_diag_gaussian(const float* moments, const float* noise, float scale, int B, int z, int spatial, float* out,

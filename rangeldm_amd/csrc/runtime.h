@@ -445,7 +445,8 @@ int build_plan(Plan* plan, int temb_ld, const std::function<int(Builder&)>& walk
 // ---------------------------------------------------------------------------------------------------------------
 // what the sampler (sampler.hip) and the test entry points share
 // ---------------------------------------------------------------------------------------------------------------
-// SchedParams / SchedFuse::mode of a scheduler step (sched_prev) from RLDM_SAMPLER_* and RLDM_PRED_*
+// SchedParams / SchedFuse::mode of a scheduler step (sched_prev) from RLDM_SAMPLER_* and RLDM_PRED_*; -1 for RLDM_SAMPLER_UNIPC, whose
+// rows are 12 wide and run through sched_unipc_kernel alone
 int sched_mode_word(int sampler_mode, int prediction_type);
 // where a scheduler step reads its noise: the tensor (offset to the first sample) and the elements between two steps' rows
 struct NoiseSrc {

@@ -45,7 +45,8 @@ struct SamplerLane {
     std::unique_ptr<Plan> uplan;                    // private UNet plan (graph-baked pointers)
     std::unique_ptr<Plan> dplan;                    // private VAE decode plan
     DevBuf x, eps, cond, step, image;
-    DevBuf hist;                                    // RLDM_SAMPLER_DPMSOLVER: the previous step's x0 (sized like x)
+    DevBuf hist;                                    // RLDM_SAMPLER_DPMSOLVER: the previous step's x0 (sized like x); RLDM_SAMPLER_UNIPC: the
+    DevBuf last;                                    // three previous steps' x0 ([3] like x) and the previous step's corrected sample
     // rldm_sample_rng / rldm_sample_guided_rng: {seed low, seed high, draw, sample offset} of the call, and one row of noise (sized
     // like x) per purpose the rows need -- filled at the head of every step, read by the scheduler step with stride 0 like hist
     DevBuf rng_record, rng_step, rng_known, rng_renoise;
@@ -126,9 +127,11 @@ rldm_sampler::~rldm_sampler() {
     if (ev_in) (void)hipEventDestroy(ev_in);
 }
 
-// (RLDM_FLAG_SCHED_LAUNCH at sampler creation keeps the scheduler step and the step counter as launches of their own)
+// (RLDM_FLAG_SCHED_LAUNCH at sampler creation keeps the scheduler step and the step counter as launches of their own; a guided sampler
+//  and RLDM_SAMPLER_UNIPC always run that way)
 
 int rldm::sched_mode_word(int sampler_mode, int prediction_type) {
+    if (sampler_mode == RLDM_SAMPLER_UNIPC) return -1;     // no 5-wide row, no word: launch_sched_step refuses it
     return (sampler_mode == RLDM_SAMPLER_DDIM ? 0 : 1) | (prediction_type << 1) | (sampler_mode == RLDM_SAMPLER_DPMSOLVER ? kSchedMultistep : 0);
 }
 static int sampler_sched_mode(const rldm_sampler* s) { return sched_mode_word(s->cfg.mode, s->cfg.prediction_type); }
@@ -151,6 +154,7 @@ void rldm::fill_sched_fuse(SchedFuse& f, const float* coef_table, const int* ste
 // [steps][whole batch][...] tensor
 static NoiseSrc lane_noise_src(const rldm_sampler* s, const SamplerLane* ln, const float* noise, bool own_noise) {
     if (s->cfg.mode == RLDM_SAMPLER_DPMSOLVER) return {ln->hist.as<float>(), 0};
+    if (s->cfg.mode == RLDM_SAMPLER_UNIPC) return {nullptr, 0};     // (its step takes its state by name: sampler_enqueue_step)
     return {noise, own_noise ? 0 : s->n_latent};
 }
 
@@ -211,6 +215,23 @@ static int sampler_enqueue_step(rldm_sampler* s, SamplerLane* ln, const SampleCa
         if (ln->uplan->run_stamped(st, g_trace.as<unsigned long long>(), 4096)) return 1;
     } else if (ln->uplan->run(st)) return 1;
     if (fused) return 0;
+    if (s->cfg.mode == RLDM_SAMPLER_UNIPC) {
+        // row *step of the [steps][12] table on the lane's own state; row 0 has no corrector and reads none of it, so a call starts
+        // clean on whatever the previous call (or the warm-up step) left there
+        UniPCParams up;
+        memset(&up, 0, sizeof(up));
+        up.pred = s->cfg.prediction_type;
+        up.coef_table = s->coef.as<float>();
+        up.step_ptr = ln->step.as<int>();
+        up.out = ln->eps.as<float>();
+        up.x = ln->x.as<float>();
+        up.last = ln->last.as<float>();
+        up.hist = ln->hist.as<float>();
+        up.x_prev = ln->x.as<float>();
+        up.n = ln->n_latent;
+        if (launch_sched_unipc_step(up, st)) return 1;
+        return launch_step_counter(ln->step.as<int>(), 0, 1, st);
+    }
     SchedParams sp;
     memset(&sp, 0, sizeof(sp));
     sp.mode = sampler_sched_mode(s);
@@ -279,7 +300,8 @@ static int sampler_build_plans(rldm_sampler* s) {
         io.temb_rows_per_step = 1;
         io.temb_per_sample = 0;
         // (a guided sampler blends AFTER the scheduler step: the input conv_out's epilogue would pack for the next step would be stale)
-        ln->fused_tail = !((dbg_process() | s->plan_flags) & RLDM_FLAG_SCHED_LAUNCH) && !s->cfg.guided;
+        // (UniPC's step reads and shifts more state than conv_out's epilogue carries: a launch of its own)
+        ln->fused_tail = !((dbg_process() | s->plan_flags) & RLDM_FLAG_SCHED_LAUNCH) && !s->cfg.guided && s->cfg.mode != RLDM_SAMPLER_UNIPC;
         if (ln->fused_tail) {
             // the scheduler step rides in conv_out's epilogue, the step index is advanced by pack_input: 2 launches per step fewer
             // ... and the next step's conv_in input: no pack_input launch inside the steps
@@ -355,6 +377,23 @@ int rldm_sched_dpmsolver_step(int prediction_type, const float coef[5], const fl
     // (coef[4] == 0: the history is not read, only overwritten -- sched_step's noise check passes with the pointer set)
     return sched_step(sched_mode_word(RLDM_SAMPLER_DPMSOLVER, prediction_type), coef, model_output, x, x0_history, x_prev, n, stream);
 }
+int rldm_sched_unipc_step(int prediction_type, const float coef[12], const float* model_output, const float* x, float* last,
+                          float* hist, float* x_prev, int64_t n, void* stream) {
+    RLDM_REQUIRE(prediction_type >= RLDM_PRED_EPSILON && prediction_type <= RLDM_PRED_SAMPLE, "unknown prediction type");
+    RLDM_REQUIRE(coef && model_output && x && last && hist && x_prev && n >= 1, "null argument");
+    auto overlap = [](const float* a, int64_t na, const float* b, int64_t nb) { return a < b + nb && b < a + na; };
+    RLDM_REQUIRE(!overlap(last, n, hist, 3 * n), "last and hist must not overlap");
+    for (const float* t : {model_output, x, static_cast<const float*>(x_prev)})
+        RLDM_REQUIRE(!overlap(t, n, last, n) && !overlap(t, n, hist, 3 * n), "last / hist must not overlap another tensor");
+    RLDM_REQUIRE(x_prev == x || !overlap(x_prev, n, x, n), "x_prev may be x itself, not a tensor that overlaps it in part");
+    RLDM_REQUIRE(!overlap(x_prev, n, model_output, n), "x_prev must not overlap model_output");
+    UniPCParams up;
+    memset(&up, 0, sizeof(up));
+    up.pred = prediction_type;
+    for (int i = 0; i < 12; ++i) up.coef[i] = coef[i];
+    up.out = model_output; up.x = x; up.last = last; up.hist = hist; up.x_prev = x_prev; up.n = n;
+    return launch_sched_unipc_step(up, reinterpret_cast<hipStream_t>(stream));
+}
 int rldm_sched_step(int sampler_mode, int prediction_type, const float coef[5], const float* model_output, const float* x,
                     const float* noise, float* x_prev, int64_t n, void* stream) {
     RLDM_REQUIRE(sampler_mode == RLDM_SAMPLER_DDIM || sampler_mode == RLDM_SAMPLER_DDPM, "unknown sampler mode");
@@ -415,13 +454,13 @@ int rldm_sampler_create(rldm_unet* unet, rldm_vae* vae, const rldm_sampler_confi
     RLDM_REQUIRE(!vae || vae->params.finalized, "vae not finalized");
     RLDM_REQUIRE(cfg->batch >= 1 && cfg->num_steps >= 1 && cfg->coef && cfg->timesteps, "bad sampler config");
     RLDM_REQUIRE(cfg->prediction_type >= RLDM_PRED_EPSILON && cfg->prediction_type <= RLDM_PRED_SAMPLE, "bad sampler config: prediction_type");
-    RLDM_REQUIRE(cfg->mode == RLDM_SAMPLER_DDIM || cfg->mode == RLDM_SAMPLER_DDPM || cfg->mode == RLDM_SAMPLER_DPMSOLVER,
-                 "bad sampler config: mode");
+    RLDM_REQUIRE(cfg->mode == RLDM_SAMPLER_DDIM || cfg->mode == RLDM_SAMPLER_DDPM || cfg->mode == RLDM_SAMPLER_DPMSOLVER ||
+                     cfg->mode == RLDM_SAMPLER_UNIPC, "bad sampler config: mode");
     RLDM_REQUIRE(cfg->guided == 0 || cfg->guided == 1, "bad sampler config: guided");
-    RLDM_REQUIRE(!cfg->guided || cfg->mode != RLDM_SAMPLER_DPMSOLVER,
-                 "a guided sampler runs DDIM (eta = 0) or DDPM rows: DPM-Solver++'s x0 history means nothing across a jump back up");
+    RLDM_REQUIRE(!cfg->guided || (cfg->mode != RLDM_SAMPLER_DPMSOLVER && cfg->mode != RLDM_SAMPLER_UNIPC),
+                 "a guided sampler runs DDIM (eta = 0) or DDPM rows: the x0 history of DPM-Solver++ and UniPC means nothing across a jump back up");
     RLDM_REQUIRE(!cfg->guided || cfg->cond_channels == 0, "a guided sampler is unconditional (cond_channels == 0)");
-    const int coef_w = cfg->guided ? 9 : 5;
+    const int coef_w = cfg->guided ? 9 : cfg->mode == RLDM_SAMPLER_UNIPC ? 12 : 5;
     if (cfg->guided)
         for (int i = 0; i < cfg->num_steps; ++i)
             RLDM_REQUIRE(cfg->mode != RLDM_SAMPLER_DDIM || cfg->coef[(size_t)i * 9 + 4] == 0.f, "a guided DDIM sampler needs eta = 0 rows");
@@ -470,6 +509,7 @@ int rldm_sampler_create(rldm_unet* unet, rldm_vae* vae, const rldm_sampler_confi
         RLDM_HIP_CHECK(hipEventCreateWithFlags(&ln->ev_out, hipEventDisableTiming));
         if (ln->x.alloc(ln->n_latent * 4) || ln->eps.alloc(ln->n_latent * 4) || ln->step.alloc(64)) return 1;
         if (cfg->mode == RLDM_SAMPLER_DPMSOLVER && ln->hist.alloc(ln->n_latent * 4)) return 1;
+        if (cfg->mode == RLDM_SAMPLER_UNIPC && (ln->hist.alloc(ln->n_latent * 3 * 4) || ln->last.alloc(ln->n_latent * 4))) return 1;
         if (cfg->cond_channels && ln->cond.alloc((size_t)ln->n_cond * 4)) return 1;
         if (vae && ln->image.alloc(ln->n_image * 4)) return 1;
         s->lanes.push_back(std::move(ln));

@@ -13,8 +13,9 @@ none is given, the deterministic synthetic state dict (no checkpoints exist offl
 ldm/inference.py:171-183 writes it: `<idx>.bin` (float32 [N, 4] x, y, z, remission of the returns closer than 90 m),
 `<idx>.png` (8-bit BEV density) and `<idx>_range.png` (8-bit range channel) -- the point cloud, the BEV volume, the depth
 filter and the 8-bit rendering all run on the GPU (rangeldm_amd.range_image); only finished bytes cross PCIe.
-`--save-npy` adds `<idx>.npy`, the raw (2, W, H) fp32 range image.  `--scheduler {ddpm,ddim,dpmsolver++}` and `--steps N`
-override the sampler and step count the config runs (e.g. `--scheduler dpmsolver++ --steps 20`).  `--device-rng` draws x_T and the
+`--save-npy` adds `<idx>.npy`, the raw (2, W, H) fp32 range image.  `--scheduler {ddpm,ddim,dpmsolver++,unipc}` and `--steps N`
+override the sampler and step count the config runs (e.g. `--scheduler dpmsolver++ --steps 20`, `--scheduler unipc --steps 10`);
+`--solver-order` sets the order of the two multistep solvers.  `--device-rng` draws x_T and the
 ancestral noise inside the sampler from rangeldm_amd.rng.DeviceGenerator(--seed) at sample_offset = the global image index: no
 [steps, B, ...] noise tensor, and the same noise per image for any GPU count.
 """
@@ -87,19 +88,28 @@ def vae_config_for(y, unet, base_dir):
     return VAEConfig(sample_size=(unet.sample_size[0] * f_, unet.sample_size[1] * f_))
 
 
-SCHEDULER_CHOICES = ("ddpm", "ddim", "dpmsolver++")
+SCHEDULER_CHOICES = ("ddpm", "ddim", "dpmsolver++", "unipc")
 
 
-def make_scheduler(name, sched_cfg):
-    """--scheduler NAME: the scheduler class of that name on the run's scheduler config (None: the defaults)."""
-    from .schedulers import DDIMSchedulerHIP, DDPMSchedulerHIP, DPMSolverMultistepSchedulerHIP
-    cls = {"ddpm": DDPMSchedulerHIP, "ddim": DDIMSchedulerHIP, "dpmsolver++": DPMSolverMultistepSchedulerHIP}[name]
-    return cls(sched_cfg)
+def make_scheduler(name, sched_cfg, solver_order=None):
+    """--scheduler NAME: the scheduler class of that name on the run's scheduler config (None: the defaults).  --solver-order: the
+    order of a multistep solver (dpmsolver++ 1-2, unipc 1-3; None: 2)."""
+    from .schedulers import DDIMSchedulerHIP, DDPMSchedulerHIP, DPMSolverMultistepSchedulerHIP, UniPCMultistepSchedulerHIP
+    cls = {"ddpm": DDPMSchedulerHIP, "ddim": DDIMSchedulerHIP, "dpmsolver++": DPMSolverMultistepSchedulerHIP,
+           "unipc": UniPCMultistepSchedulerHIP}[name]
+    if solver_order is None:
+        return cls(sched_cfg)
+    if name not in ("dpmsolver++", "unipc"):
+        raise ValueError(f"--solver-order is a setting of dpmsolver++ and unipc, not of {name}")
+    return cls(sched_cfg, solver_order=solver_order)
 
 
 def add_sampling_args(ap):
     ap.add_argument("--scheduler", choices=SCHEDULER_CHOICES, default=None,
-                    help="sampler (default: what the config runs; dpmsolver++ = DPM-Solver++(2M), for 20-25 steps)")
+                    help="sampler (default: what the config runs; dpmsolver++ = DPM-Solver++(2M), for 20-25 steps; unipc = UniPC "
+                         "predictor-corrector, for 8-15 steps)")
+    ap.add_argument("--solver-order", type=int, default=None,
+                    help="order of the multistep solver: dpmsolver++ 1 or 2, unipc 1, 2 or 3 (default 2)")
     ap.add_argument("--steps", type=int, default=None, help="num_inference_steps (default: the config's)")
     ap.add_argument("--device-rng", action="store_true",
                     help="draw x_T and every row of noise on the device from the counter-based generator (rangeldm_amd.rng): seed = --seed, "
@@ -237,11 +247,11 @@ def main(argv=None):
     unet, vae, sched_cfg = build_models(cfg, a.weights, a.ema, a.seed)
     if vae is not None:
         # ldm/inference.py:131-136: the LDM branch keeps the DDPM scheduler (strided ancestral sampling)
-        pipe = LDMPipelineRange(vae=vae, unet=unet, scheduler=make_scheduler(a.scheduler or "ddpm", sched_cfg),
+        pipe = LDMPipelineRange(vae=vae, unet=unet, scheduler=make_scheduler(a.scheduler or "ddpm", sched_cfg, a.solver_order),
                                 pos_encoding=cfg["pos_encoding"])
-    elif a.scheduler == "dpmsolver++":
-        # (DDIMPipelineRange forces DDIM, ldm/pipelines.py:135-139: pixel-space DPM-Solver++ runs in DDPMPipelineRange)
-        pipe = DDPMPipelineRange(unet=unet, scheduler=make_scheduler(a.scheduler, sched_cfg))
+    elif a.scheduler in ("dpmsolver++", "unipc"):
+        # (DDIMPipelineRange forces DDIM, ldm/pipelines.py:135-139: the pixel-space multistep solvers run in DDPMPipelineRange)
+        pipe = DDPMPipelineRange(unet=unet, scheduler=make_scheduler(a.scheduler, sched_cfg, a.solver_order))
     elif a.scheduler == "ddim" or (a.scheduler is None and cfg.get("ddim", True)):
         pipe = DDIMPipelineRange(unet=unet, scheduler=DDIMSchedulerHIP(sched_cfg), pos_encoding=cfg["pos_encoding"])
     else:

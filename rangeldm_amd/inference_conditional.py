@@ -132,8 +132,8 @@ def main_guided(a):
         a.scheduler = "ddim"
         guide_kw = dict(decoder_guidance=True, guidance_scale=a.guidance_scale, guidance_iters=a.guidance_iters,
                         guidance_start=a.guidance_window[0], guidance_stop=a.guidance_window[1])
-    if (a.scheduler or "ddpm") == "dpmsolver++":
-        raise NotImplementedError("--guided runs DDPM or DDIM rows (DPM-Solver++ keeps an x0 history that a jump invalidates)")
+    if (a.scheduler or "ddpm") in ("dpmsolver++", "unipc"):
+        raise NotImplementedError("--guided runs DDPM or DDIM rows (DPM-Solver++ and UniPC keep an x0 history that a jump invalidates)")
     B = a.batch_size or cfg.get("batch", 16)
     steps = a.steps or cfg.get("steps", 50)
     rank, world, local = D.init_from_env()
@@ -146,7 +146,7 @@ def main_guided(a):
         os.makedirs(d, exist_ok=True)
     unet, vae, sched_cfg = build_models(cfg, a.weights, a.ema, a.seed)
     if vae is not None:
-        pipe = LDMPipelineRange(vae=vae, unet=unet, scheduler=make_scheduler(a.scheduler or "ddpm", sched_cfg),
+        pipe = LDMPipelineRange(vae=vae, unet=unet, scheduler=make_scheduler(a.scheduler or "ddpm", sched_cfg, a.solver_order),
                                 pos_encoding=cfg["pos_encoding"])
         f = cfg["vae"].downscale
         img_shape = (cfg["vae"].in_channels, cfg["unet"].sample_size[0] * f, cfg["unet"].sample_size[1] * f)
@@ -218,7 +218,7 @@ def main(argv=None):
 
     unet, vae, sched_cfg = build_models(cfg, a.weights, a.ema, a.seed)
     # ldm/inference_conditional.py:121-134: DDPM scheduler (strided ancestral sampling), SparseRangeImageEncoder2 for up-sampling
-    pipe = LDMUpscalePipelineRange(unet=unet, scheduler=make_scheduler(a.scheduler or "ddpm", sched_cfg), vae=vae)
+    pipe = LDMUpscalePipelineRange(unet=unet, scheduler=make_scheduler(a.scheduler or "ddpm", sched_cfg, a.solver_order), vae=vae)
     condition_encoder = SparseRangeImageEncoder2() if cfg["task"] == "upsample" else None
 
     f = cfg["vae"].downscale

@@ -21,8 +21,8 @@ import torch
 
 from . import _lib
 from .rng import DeviceGenerator, randn, randn_rows
-from .schedulers import (DDIMSchedulerHIP, DDPMSchedulerHIP, DPMSolverMultistepSchedulerHIP, guided_step, randn_tensor,
-                         repaint_program, sampler_mode)
+from .schedulers import (DDIMSchedulerHIP, DDPMSchedulerHIP, MultistepSchedulerBase, guided_step, randn_tensor, repaint_program,
+                         sampler_mode)
 
 
 class ImagePipelineOutput:
@@ -253,7 +253,7 @@ class _PipelineBase:
             vae.save_pretrained(os.path.join(output_dir, "vae"))
         self.scheduler.save_pretrained(os.path.join(output_dir, "scheduler"))
         import json
-        sched = "DPMSolverMultistepScheduler" if isinstance(self.scheduler, DPMSolverMultistepSchedulerHIP) else "DDPMScheduler"
+        sched = self.scheduler._DIFFUSERS_NAME if isinstance(self.scheduler, MultistepSchedulerBase) else "DDPMScheduler"
         index = {"_class_name": type(self).__name__, "_diffusers_version": "0.21.0",
                  "unet": ["diffusers", "UNet2DModel"], "scheduler": ["diffusers", sched]}
         if vae is not None:
@@ -392,18 +392,18 @@ class DDPMPipelineRange(_PipelineBase):
         shape = (batch_size, cfg.in_channels, *ss)
         noise = _CallNoise(generator, sample_offset, self.device)
         ancestral = isinstance(self.scheduler, DDPMSchedulerHIP)
-        is_dpm = isinstance(self.scheduler, DPMSolverMultistepSchedulerHIP)
+        multistep = isinstance(self.scheduler, MultistepSchedulerBase)      # DPM-Solver++ or UniPC: no noise, fused like DDPM here
         image = None
         # (the captured loop that draws its step noise draws x_T as well when none is given: the one route with a null x_T)
         if latents is not None or not (ancestral and noise.in_graph(fused, step_noise)):
             image = noise.x_T(shape, latents, on_host=False).to(device=self.device, dtype=torch.float32)
         self.scheduler.set_timesteps(num_inference_steps)
-        if fused and (ancestral or is_dpm):
+        if fused and (ancestral or multistep):
             image = self._sample_fused(shape, image, noise, step_noise, num_inference_steps, kwargs.get("check", True))
         else:
             for i, t in enumerate(self.progress_bar(self.scheduler.timesteps)):
                 model_output = self.unet(image, t).sample
-                z = noise.row(1, i, shape, step_noise) if ancestral or (step_noise is not None and not is_dpm) else None
+                z = noise.row(1, i, shape, step_noise) if ancestral or (step_noise is not None and not multistep) else None
                 kw = {"noise": z} if z is not None else {"generator": noise.torch_generator}
                 image = self.scheduler.step(model_output, t, image, **kw).prev_sample
         return self._finish(image, output_type, return_dict)
@@ -465,7 +465,7 @@ class DDIMPipelineRange(_PipelineBase):
 class LDMPipelineRange(_PipelineBase):
     """ldm/pipelines.py:261-383 (latent sampling + VAE decode).  With a DDPM scheduler this is the strided ancestral
     sampler the reference actually runs; pass a DDIMSchedulerHIP for the BASELINE's DDIM eta=0, or a
-    DPMSolverMultistepSchedulerHIP for DPM-Solver++(2M) in 20-25 steps."""
+    DPMSolverMultistepSchedulerHIP for DPM-Solver++(2M) in 20-25 steps, or a UniPCMultistepSchedulerHIP for UniPC in 8-15."""
 
     def __init__(self, vae, unet, scheduler, pos_encoding=False):
         super().__init__()
